@@ -20,6 +20,11 @@ Every line carries `parity`: the timed library checked in the same process again
 tests/golden/convert_cfg2_B4_T200.npz (utterances 0..3 of configs[1], gap-checked index seed 8) - waveform rms and kNN index equality.
 
 value = 16 kHz-equivalent audio samples converted per second by the whole job (audio seconds x 16 000 / wall seconds).
+ms_per_step = wall milliseconds of one timed step (--steps of them).
+
+--dump-outputs DIR writes what the last timed step returned (rank 0: its waveforms, or the gathered job output at N > 1) as
+DIR/<name>.npy.  The device generator is seeded before the first step, so with the same arguments the inputs and the
+noise phases drawn in the timed steps are the same in every run, and two builds can be compared output for output.
 """
 import argparse
 import glob
@@ -45,6 +50,30 @@ SPLIT_PRODUCTS = 3                         # two-term fp16 split: three fp16 par
 
 
 STAGE_STEPS = 5      # untimed steps with every stage bracketed, after the timed region
+RNG_SEED = 20260101  # torch.manual_seed before the first step: the phases the library draws in the timed steps repeat from run to run
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(d, arrays, seed=0):
+    """--dump-outputs: write every array of `arrays` ({name: tensor}) as d/<name>.npy, float32.  When the whole set is larger than
+    DUMP_BYTES_MAX, each array keeps a fixed, seeded sample of its rows (leading dims flattened) in ascending order, and
+    d/<name>_rows.npy (float64) names the rows kept.  Returns {name: {"shape", "rows_kept"}}."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    total = sum(a.numel() * 4 for a in arrays.values())
+    info = {}
+    for name, a in arrays.items():
+        a = a.detach().float().cpu()
+        rows = a.reshape(-1, a.shape[-1]) if a.dim() > 1 else a.reshape(1, -1)
+        keep = None
+        if total > DUMP_BYTES_MAX:
+            k = max(1, int(rows.shape[0] * 0.99 * DUMP_BYTES_MAX / total))      # (1 % left for the <name>_rows.npy files)
+            keep = np.sort(np.random.default_rng(seed).choice(rows.shape[0], size=min(k, rows.shape[0]), replace=False))
+            rows = rows[torch.from_numpy(keep)]
+            np.save(os.path.join(d, name + "_rows.npy"), keep.astype(np.float64))
+        np.save(os.path.join(d, name + ".npy"), (rows if keep is not None else a).numpy().astype(np.float32))
+        info[name] = {"shape": list(a.shape), "rows_kept": None if keep is None else int(len(keep))}
+    return info
 
 
 def measured_filter_traffic(B, L):
@@ -362,7 +391,11 @@ def main():
     ap.add_argument("--no-gather", action="store_true", help="N > 1: leave every rank's waveforms on its own GPU (not configs[3])")
     ap.add_argument("--force-dist", action="store_true", help="run the N > 1 branch (RCCL communicator, gather, its JSON keys) even at world size 1")
     ap.add_argument("--no-parity", action="store_true", help="skip the untimed parity call against the committed reference fixture")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     force_dist = args.force_dist or bool(os.environ.get("TVC_BENCH_FORCE_DIST"))
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -428,6 +461,7 @@ def main():
     timers = not os.environ.get("TVC_BENCH_NOTIMERS")     # diagnostic: run without the library's hipEvent stage timers (no roofline then)
     # During the timed steps only the roofline's region (FilterNet) is bracketed: one hipEvent pair per step.  All 19 regions cost
     # ~0.12 ms of a step (38 event records); the stage split is taken from STAGE_STEPS extra, untimed steps afterwards.
+    torch.manual_seed(RNG_SEED)
     eng.profile(1 if timers else 0)                       # every region once, so that the context's event pool is populated before the timed steps
     step()
     eng.profile_read()
@@ -462,6 +496,9 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     last = state["i"]
+    dumped = None
+    if args.dump_outputs and rank == 0:                   # the last timed step's result, before the untimed steps below replace it
+        dumped = dump_outputs(args.dump_outputs, {"wave_gathered": dest} if gather else {"wave": state["out"]})
     prof = eng.profile_read()                             # {"filter_net": ms summed over the timed steps}
     stage_prof = {}
     if timers:
@@ -532,6 +569,8 @@ def main():
             "stage_ms_per_step": dict(sorted(stage_prof.items())),
             "stage_ms_note": f"hipEvent pairs around every stage over {STAGE_STEPS} extra steps after the timed region (the timed steps carry the filter_net pair only)",
         }
+        if dumped is not None:
+            res["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "rng_seed": RNG_SEED}
         if multi:
             res["rccl_ranks"] = rccl_ranks            # all_reduce of ones over the communicator
             res["forced_dist_rehearsal"] = bool(force_dist and world == 1)

@@ -62,3 +62,41 @@ def test_default_line_carries_parity_roofline_and_cpu_baseline_keys():
     assert p["drawn_equals_injected_hash"] is True, "the timed instantiation (phases drawn in-kernel) must equal the injected restatement of its hash"
     rf = j["roofline"]
     assert rf["bound"] in ("hbm", "mfma") and 0 < rf["frac"] < 1 and rf["launch_ms"] > 0
+
+
+def test_dump_outputs_keeps_a_seeded_sample_under_the_cap(tmp_path, monkeypatch):
+    """Above the size cap every array keeps a fixed sample of its rows, the same on every call, and the files stay under the cap."""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 1 << 20)
+    x = torch.randn(4, 64, 2000)
+    info = bench.dump_outputs(str(tmp_path / "a"), {"wave_gathered": x})
+    bench.dump_outputs(str(tmp_path / "b"), {"wave_gathered": x})
+    assert info["wave_gathered"]["shape"] == [4, 64, 2000] and 0 < info["wave_gathered"]["rows_kept"] < 256
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 1 << 20
+    w, rows = np.load(tmp_path / "a" / "wave_gathered.npy"), np.load(tmp_path / "a" / "wave_gathered_rows.npy")
+    assert w.dtype == np.float32 and rows.dtype == np.float64
+    assert np.array_equal(w, x.reshape(-1, 2000)[torch.from_numpy(rows.astype(np.int64))].numpy())
+    assert np.array_equal(w, np.load(tmp_path / "b" / "wave_gathered.npy"))
+    # below the cap the array is written whole
+    small = bench.dump_outputs(str(tmp_path / "c"), {"wave": x[0]})
+    assert small["wave"]["rows_kept"] is None and np.array_equal(np.load(tmp_path / "c" / "wave.npy"), x[0].numpy())
+
+
+@pytest.mark.gpu
+def test_dump_outputs_repeats_from_run_to_run(tmp_path):
+    """--dump-outputs: the last timed step's waveforms, float32, the same in two runs with the same arguments (inputs and the
+    noise phases the library draws are seeded), and --steps is the number of timed steps the line reports."""
+    import numpy as np
+    outs = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = _run(["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-stream", "--no-parity", "--dump-outputs", str(d)], 900)
+        assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+        j = _line(r.stdout)
+        assert j["steps"] == 2 and j["ms_per_step"] > 0 and j["dump_outputs"]["arrays"]["wave"]["shape"] == [64, 96000]
+        w = np.load(d / "wave.npy")
+        assert w.dtype == np.float32 and w.shape == (64, 96000) and np.isfinite(w).all() and np.abs(w).max() > 0
+        outs.append(w)
+    assert np.array_equal(outs[0], outs[1])
