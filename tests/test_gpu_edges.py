@@ -278,3 +278,49 @@ def test_seeded_draw_is_refused_inside_a_stream_capture_and_push_equals_roll(gen
     b2 = torch.randn(3, 1999, device=DEV)
     w2 = torch.cat([odd[:, 1999:], b2], dim=1)
     assert torch.equal(eng.stream_push(odd.clone(), b2), w2)
+
+
+def test_workspace_of_exactly_the_measured_peak_and_one_byte_less(gen):
+    """Every entry measures its workspace with a walk that launches nothing (ws.dry) before its launching walk, and checks behind the second
+    that it took no more (api.hip TVC_RUN).  tvc_workspace_bytes - 4096 is that peak: a conversion in exactly it equals one in the engine's
+    own workspace bit for bit, and one byte less is refused with TVC_ERR_WORKSPACE before anything launches (the output keeps its NaN fill).
+    The same for a ragged call with tvc_workspace_bytes_ragged - 4096."""
+    import ctypes
+    from tinyvc_amd.engine import _ptr
+    eng = gen.engine(DEV)
+    B, T = 2, 40
+    L = 480 * T
+    wf = synth.synth_wave(B, L, seed=41).to(DEV)
+    blob, n = eng.knn_prepare(synth.synth_index(300, seed=42).to(DEV))
+    angle = synth.synth_angle(B, T, 43).to(DEV)
+    want = eng.convert(wf, blob, n, 0.5, noise_angle=angle)
+    need = ctypes.c_size_t()
+    assert eng.lib.tvc_workspace_bytes(eng.ctx, B, L, n, ctypes.byref(need)) == 0
+    for extra, rc_want in ((0, 0), (-1, -4)):                          # -4: TVC_ERR_WORKSPACE
+        ws = torch.empty(need.value - 4096 + extra, dtype=torch.uint8, device=DEV)
+        out = torch.full((B, L), float("nan"), device=DEV)
+        rc = eng.lib.tvc_convert_f32(eng.ctx, eng._stream(), _ptr(wf), _ptr(blob), n, 0.5, _ptr(angle), 0, _ptr(out), B, L, _ptr(ws), ws.numel())
+        torch.cuda.synchronize()
+        assert rc == rc_want, (extra, rc, eng.lib.tvc_last_error(eng.ctx))
+        if rc == 0:
+            assert torch.equal(out, want), "a conversion in exactly the measured workspace"
+        else:
+            assert out.isnan().all(), "a refused call launched something"
+
+    frames = [40, 13, 7]
+    lens = (ctypes.c_int64 * 3)(*[480 * f for f in frames])
+    wr = torch.zeros(3, L, device=DEV)
+    for b, f in enumerate(frames):
+        wr[b, :480 * f] = wf[b % B, :480 * f]
+    ar = synth.synth_angle(3, T, 44).to(DEV)
+    assert eng.lib.tvc_workspace_bytes_ragged(eng.ctx, 3, L, lens, n, ctypes.byref(need)) == 0
+    for extra, rc_want in ((0, 0), (-1, -4)):
+        ws = torch.empty(need.value - 4096 + extra, dtype=torch.uint8, device=DEV)
+        out = torch.full((3, L), float("nan"), device=DEV)
+        rc = eng.lib.tvc_convert_ragged_f32(eng.ctx, eng._stream(), _ptr(wr), L, lens, _ptr(blob), n, 0.5, _ptr(ar), 0, _ptr(out), 3, _ptr(ws), ws.numel())
+        torch.cuda.synchronize()
+        assert rc == rc_want, (extra, rc, eng.lib.tvc_last_error(eng.ctx))
+        if rc == 0:
+            assert torch.equal(out, eng.convert_ragged(wr, [480 * f for f in frames], blob, n, 0.5, noise_angle=ar)), "a ragged call in exactly the measured workspace"
+        else:
+            assert out.isnan().all(), "a refused ragged call launched something"

@@ -829,7 +829,7 @@ static int need_ready(tvc_ctx* ctx, int need) {
     return 0;
 }
 
-static int convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* wav, const float* prepared,
+static int convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* wav, const float* prepared,
                         int64_t N, float pitch_shift, const float* angle,
                         uint64_t seed, float* wave, int B, int64_t L) {
     const int T = (int)(L / kHop);
@@ -851,53 +851,61 @@ static int convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const flo
     const bool bounds = true;
     size_t m = ws.mark();
     {
-        ProfScope ps(ctx, s, dry, "stft");
-        TVC_CHECK(run_stft(ctx, s, ws, dry, wav, spec, B, L));
+        ProfScope ps(ctx, s, ws, "stft");
+        TVC_CHECK(run_stft(ctx, s, ws, wav, spec, B, L));
     }
     ws.release(m);
     {
-        ProfScope ps(ctx, s, dry, "energy");
-        TVC_CHECK(run_energy(ctx, s, ws, dry, wav, energy, B, L, bounds ? emax : nullptr, bounds ? spec_bound : nullptr, bounds ? enc_slots : nullptr, 3 * NB));
+        ProfScope ps(ctx, s, ws, "energy");
+        TVC_CHECK(run_energy(ctx, s, ws, wav, energy, B, L, bounds ? emax : nullptr, bounds ? spec_bound : nullptr, bounds ? enc_slots : nullptr, 3 * NB));
     }
     ws.release(m);
     {
-        ProfScope ps(ctx, s, dry, "encoder");
-        TVC_CHECK(run_encoder(ctx, s, ws, dry, spec, ssl, f0, nullptr, B, T, bounds ? spec_bound : nullptr, bounds ? enc_slots : nullptr, f0s, pitch_shift));
+        ProfScope ps(ctx, s, ws, "encoder");
+        TVC_CHECK(run_encoder(ctx, s, ws, spec, ssl, f0, nullptr, B, T, bounds ? spec_bound : nullptr, bounds ? enc_slots : nullptr, f0s, pitch_shift));
     }
     ws.release(m);
     {
-        ProfScope ps(ctx, s, dry, "knn");
-        TVC_CHECK(run_knn(ctx, s, ws, dry, ssl, prepared, N, matched, nullptr, B, T));
+        ProfScope ps(ctx, s, ws, "knn");
+        TVC_CHECK(run_knn(ctx, s, ws, ssl, prepared, N, matched, nullptr, B, T));
     }
     ws.release(m);
-    TVC_CHECK(run_decoder(ctx, s, ws, dry, matched, f0s, energy, angle, seed, wave, nullptr, nullptr, nullptr, B, T, dry ? nullptr : knn_index_amax(prepared),
+    TVC_CHECK(run_decoder(ctx, s, ws, matched, f0s, energy, angle, seed, wave, nullptr, nullptr, nullptr, B, T, ws.dry ? nullptr : knn_index_amax(prepared),
                           bounds ? emax : nullptr));
     ws.release(m);
     return 0;
+}
+
+// stands for a caller's buffer in a walk that only sizes the workspace (ws.dry: no pointer is dereferenced)
+static float* const kDryPtr = (float*)(uintptr_t)256;
+
+// behind the launching walk of an entry: it took no more workspace than its measuring walk (ws.dry) found
+static int walks_agree(tvc_ctx* ctx, const char* entry, size_t real_peak, size_t measured) {
+    return real_peak <= measured ? TVC_OK : fail(ctx, TVC_ERR_WORKSPACE, "%s: the launching walk took %zu workspace bytes, the measuring walk %zu", entry, real_peak, measured);
 }
 
 int tvc_workspace_bytes(tvc_ctx* ctx, int B, int64_t L, int64_t N, size_t* out_bytes) {
     TVC_CHECK(need_ready(ctx, NEED_NONE));
     if (!out_bytes || B <= 0 || L <= 0 || L % kHop != 0 || N < 4) return fail(ctx, TVC_ERR_ARG, "tvc_workspace_bytes: need B>0, L%%480==0, N>=4");
     Ws ws(nullptr, 0, true);
-    TVC_CHECK(convert_impl(ctx, nullptr, ws, true, nullptr, nullptr, N, 0.f, nullptr, 0, nullptr, B, L));
+    TVC_CHECK(convert_impl(ctx, nullptr, ws, kDryPtr, kDryPtr, N, 0.f, nullptr, 0, kDryPtr, B, L));
     *out_bytes = ws.peak + 4096;
     return TVC_OK;
 }
 
-// Workspace is validated *before* launching: every entry runs its driver once in dry mode.
-#define TVC_RUN(call_dry, call_real)                                                              \
-    {                                                                                             \
-        Ws dryws(nullptr, 0, true);                                                               \
-        {                                                                                         \
-            Ws& ws = dryws;                                                                       \
-            int rc0 = (call_dry);                                                                 \
-            if (rc0) return rc0;                                                                  \
-        }                                                                                         \
-        if (dryws.peak > ws_bytes)                                                                \
-            return fail(ctx, TVC_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", dryws.peak, ws_bytes); \
-        Ws ws(wsp, ws_bytes, false);                                                              \
-        return (call_real);                                                                       \
+// Workspace is validated *before* launching: every entry walks `call` twice, first with a Ws that only measures (ws.dry), then with the
+// caller's workspace.  Both walks take the same allocations (tvc_common.h Ws); the host check behind the second one states it.
+#define TVC_RUN(call)                                                                                                           \
+    {                                                                                                                           \
+        Ws need(nullptr, 0, true);                                                                                              \
+        {                                                                                                                       \
+            Ws& ws = need;                                                                                                      \
+            TVC_CHECK(call);                                                                                                    \
+        }                                                                                                                       \
+        if (need.peak > ws_bytes) return fail(ctx, TVC_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need.peak, ws_bytes); \
+        Ws ws(wsp, ws_bytes, false);                                                                                            \
+        TVC_CHECK(call);                                                                                                        \
+        return walks_agree(ctx, __func__, ws.peak, need.peak);                                                                  \
     }
 
 int tvc_stft_mag_f32(tvc_ctx* ctx, void* stream, const float* wav, float* spec, int B, int64_t L, void* wsp, size_t ws_bytes) {
@@ -906,7 +914,7 @@ int tvc_stft_mag_f32(tvc_ctx* ctx, void* stream, const float* wav, float* spec, 
     if (L < kNfft / 2 + 1) return fail(ctx, TVC_ERR_ARG, "tvc_stft_mag_f32: L must exceed 960 (reflect padding)");
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    TVC_RUN(run_stft(ctx, s, ws, true, wav, spec, B, L), run_stft(ctx, s, ws, false, wav, spec, B, L));
+    TVC_RUN(run_stft(ctx, s, ws, wav, spec, B, L));
 }
 
 int64_t tvc_resample_out_len(int64_t n, int orig_freq, int new_freq) { return resample_out_len(n, orig_freq, new_freq); }
@@ -937,7 +945,7 @@ int tvc_energy_f32(tvc_ctx* ctx, void* stream, const float* wav, float* energy, 
     if (!wav || !energy || B <= 0 || L < 128) return fail(ctx, TVC_ERR_ARG, "tvc_energy_f32: bad argument");
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    TVC_RUN(run_energy(ctx, s, ws, true, wav, energy, B, L), run_energy(ctx, s, ws, false, wav, energy, B, L));
+    TVC_RUN(run_energy(ctx, s, ws, wav, energy, B, L));
 }
 
 int tvc_encoder_f32(tvc_ctx* ctx, void* stream, const float* spec, float* ssl, float* f0, float* logits, int B, int T, void* wsp, size_t ws_bytes) {
@@ -945,7 +953,7 @@ int tvc_encoder_f32(tvc_ctx* ctx, void* stream, const float* spec, float* ssl, f
     if (!spec || !ssl || !f0 || B <= 0 || T <= 0) return fail(ctx, TVC_ERR_ARG, "tvc_encoder_f32: bad argument");
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    TVC_RUN(run_encoder(ctx, s, ws, true, spec, ssl, f0, logits, B, T), run_encoder(ctx, s, ws, false, spec, ssl, f0, logits, B, T));
+    TVC_RUN(run_encoder(ctx, s, ws, spec, ssl, f0, logits, B, T));
 }
 
 int tvc_pitch_decode_f32(tvc_ctx* ctx, void* stream, const float* logits, float* f0, int B, int T) {
@@ -1004,8 +1012,7 @@ int tvc_knn_match_f32(tvc_ctx* ctx, void* stream, const float* src, const float*
     TVC_CHECK(blob_check(ctx, (hipStream_t)stream, prepared, N, "tvc_knn_match_f32"));
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    TVC_RUN(run_knn(ctx, s, ws, true, src, prepared, N, out, idx_out, B, T),
-            run_knn(ctx, s, ws, false, src, prepared, N, out, idx_out, B, T));
+    TVC_RUN(run_knn(ctx, s, ws, src, prepared, N, out, idx_out, B, T));
 }
 
 int tvc_knn_match_general_f32(tvc_ctx* ctx, void* stream, const float* src, const float* index, int64_t N, int k, int metric, float* out,
@@ -1018,8 +1025,7 @@ int tvc_knn_match_general_f32(tvc_ctx* ctx, void* stream, const float* src, cons
     if (N > 0x7ffffffe || (long)B * T > 0x7fffffff) return fail(ctx, TVC_ERR_ARG, "tvc_knn_match_general_f32: sizes beyond 32-bit indexing");
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    TVC_RUN(run_knn_general(ctx, s, ws, true, src, index, N, k, metric, out, idx_out, sim_out, B, T),
-            run_knn_general(ctx, s, ws, false, src, index, N, k, metric, out, idx_out, sim_out, B, T));
+    TVC_RUN(run_knn_general(ctx, s, ws, src, index, N, k, metric, out, idx_out, sim_out, B, T));
 }
 
 int tvc_knn_topk_f32(tvc_ctx* ctx, void* stream, const float* src, const float* prepared, int64_t N, float* sims_out,
@@ -1030,8 +1036,7 @@ int tvc_knn_topk_f32(tvc_ctx* ctx, void* stream, const float* src, const float* 
     TVC_CHECK(blob_check(ctx, (hipStream_t)stream, prepared, N, "tvc_knn_topk_f32"));
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    TVC_RUN(run_knn_topk(ctx, s, ws, true, src, prepared, N, sims_out, idx_out, B, T),
-            run_knn_topk(ctx, s, ws, false, src, prepared, N, sims_out, idx_out, B, T));
+    TVC_RUN(run_knn_topk(ctx, s, ws, src, prepared, N, sims_out, idx_out, B, T));
 }
 
 int tvc_knn_gather_slots_f32(tvc_ctx* ctx, void* stream, const float* prepared, int64_t N, const int64_t* idx, float* slots,
@@ -1072,8 +1077,7 @@ int tvc_decoder_stages_f32(tvc_ctx* ctx, void* stream, const float* content, con
     if (wave || source) TVC_CHECK(draw_under_capture(ctx, (hipStream_t)stream, noise_angle, "tvc_decoder_f32"));
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    TVC_RUN(run_decoder(ctx, s, ws, true, content, f0, energy, noise_angle, seed, wave, amps, kernel, source, B, T),
-            run_decoder(ctx, s, ws, false, content, f0, energy, noise_angle, seed, wave, amps, kernel, source, B, T));
+    TVC_RUN(run_decoder(ctx, s, ws, content, f0, energy, noise_angle, seed, wave, amps, kernel, source, B, T));
 }
 
 int tvc_filter_net_f32(tvc_ctx* ctx, void* stream, const float* content, const float* f0, const float* energy, const float* source,
@@ -1085,8 +1089,7 @@ int tvc_filter_net_f32(tvc_ctx* ctx, void* stream, const float* content, const f
     FilterTaps taps;
     for (int i = 0; i < 5 && skips; ++i) taps.skips[i] = skips[i];
     for (int i = 0; i < 4 && ups; ++i) taps.ups[i] = ups[i];
-    TVC_RUN(run_filter(ctx, s, ws, true, content, f0, energy, source, wave, B, T, nullptr),
-            run_filter(ctx, s, ws, false, content, f0, energy, source, wave, B, T, &taps));
+    TVC_RUN(run_filter(ctx, s, ws, content, f0, energy, source, wave, B, T, &taps));
 }
 
 int tvc_dsp_f32(tvc_ctx* ctx, void* stream, const float* f0, const float* amps, const float* kernel, const float* noise_angle,
@@ -1096,8 +1099,7 @@ int tvc_dsp_f32(tvc_ctx* ctx, void* stream, const float* f0, const float* amps, 
     TVC_CHECK(draw_under_capture(ctx, (hipStream_t)stream, noise_angle, "tvc_dsp_f32"));
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    TVC_RUN(run_dsp(ctx, s, ws, true, f0, amps, kernel, noise_angle, seed, source, B, T),
-            run_dsp(ctx, s, ws, false, f0, amps, kernel, noise_angle, seed, source, B, T));
+    TVC_RUN(run_dsp(ctx, s, ws, f0, amps, kernel, noise_angle, seed, source, B, T));
 }
 
 int tvc_decoder_f32(tvc_ctx* ctx, void* stream, const float* content, const float* f0, const float* energy,
@@ -1116,8 +1118,7 @@ int tvc_convert_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* p
     TVC_CHECK(draw_under_capture(ctx, (hipStream_t)stream, noise_angle, "tvc_convert_f32"));
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    TVC_RUN(convert_impl(ctx, s, ws, true, wav, prepared, N, pitch_shift, noise_angle, seed, wave, B, L),
-            convert_impl(ctx, s, ws, false, wav, prepared, N, pitch_shift, noise_angle, seed, wave, B, L));
+    TVC_RUN(convert_impl(ctx, s, ws, wav, prepared, N, pitch_shift, noise_angle, seed, wave, B, L));
 }
 
 // ---- ragged batches ---------------------------------------------------------------------------------------------------------
@@ -1154,30 +1155,19 @@ int ragged_split(tvc_ctx* ctx, int cap, int B, int64_t Lmax, const int64_t* lens
         if (!open[c].rows.empty()) batches->push_back(open[c]);
     return 0;
 }
-// one in-kernel ragged batch: [tables][convert workspace]; the drivers run it as ONE utterance of Ttot frames (B = 1) with ctx->rag set
-int ragged_batch(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const RagBatchPlan& p, const float* wav, int64_t Lmax, const float* prepared, int64_t N,
-                 float pitch_shift, const float* angle, uint64_t seed, float* wave) {
-    int* scratch = ws.get<int>(rag_scratch_ints((int)p.rows.size(), p.Ttot));
-    RagHost h;
-    TVC_CHECK(rag_setup(ctx, s, dry, h, p.frames, p.rows, (int)(Lmax / kHop), scratch));
-    ctx->rag = &h;
-    const int rc = convert_impl(ctx, s, ws, dry, wav, prepared, N, pitch_shift, angle, seed, wave, 1, (int64_t)p.Ttot * kHop);
-    ctx->rag = nullptr;
-    return rc;
-}
-// the batches of a call run one after the other on the caller's stream and share one workspace region.  Sized for a call with AND without
-// caller-supplied noise phases (the library's own draw needs a buffer the injected phases do not).
-// angle_mode: 0 / 1 = a call without / with caller-supplied phases (what a conversion needs), -1 = the larger of the two (what
-// tvc_workspace_bytes_ragged promises: it does not know which call will follow)
-int ragged_batch_bytes(tvc_ctx* ctx, const std::vector<RagBatchPlan>& batches, int64_t Lmax, int64_t N, size_t* bytes, int angle_mode) {
-    *bytes = 0;
-    for (auto& p : batches)
-        for (int with_angle = angle_mode < 0 ? 0 : angle_mode; with_angle <= (angle_mode < 0 ? 1 : angle_mode); ++with_angle) {
-            Ws ws(nullptr, 0, true);
-            TVC_CHECK(ragged_batch(ctx, nullptr, ws, true, p, nullptr, Lmax, nullptr, N, 0.f, with_angle ? (const float*)256 : nullptr, 0, nullptr));
-            const size_t need = (ws.peak + 4095) & ~size_t(4095);
-            if (need > *bytes) *bytes = need;
-        }
+// the batches of a call, one after the other on the caller's stream, each from the start of the same workspace region: [tables][convert
+// workspace].  The drivers run a batch as ONE utterance of Ttot frames (B = 1) with ctx->rag set.
+int ragged_batches(tvc_ctx* ctx, hipStream_t s, Ws& ws, const std::vector<RagBatchPlan>& batches, const float* wav, int64_t Lmax, const float* prepared,
+                   int64_t N, float pitch_shift, const float* angle, uint64_t seed, float* wave) {
+    for (auto& p : batches) {
+        ws.release(0);
+        RagHost h;
+        TVC_CHECK(rag_setup(ctx, s, ws, h, p.frames, p.rows, (int)(Lmax / kHop)));
+        ctx->rag = &h;
+        const int rc = convert_impl(ctx, s, ws, wav, prepared, N, pitch_shift, angle, seed, wave, 1, (int64_t)p.Ttot * kHop);
+        ctx->rag = nullptr;
+        TVC_CHECK(rc);
+    }
     return 0;
 }
 }  // namespace
@@ -1204,9 +1194,9 @@ int tvc_workspace_bytes_ragged(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t*
     if (!out_bytes || !lens || B <= 0 || Lmax <= 0 || Lmax % kHop != 0 || N < 4) return fail(ctx, TVC_ERR_ARG, "tvc_workspace_bytes_ragged: need B>0, Lmax%%480==0, N>=4");
     std::vector<RagBatchPlan> batches;
     TVC_CHECK(ragged_split(ctx, ctx->rag_batch_frames, B, Lmax, lens, &batches));
-    size_t bytes = 0;
-    TVC_CHECK(ragged_batch_bytes(ctx, batches, Lmax, N, &bytes, -1));
-    *out_bytes = bytes + 4096;
+    Ws ws(nullptr, 0, true);      // (no allocation depends on whether the call brings its own noise phases)
+    TVC_CHECK(ragged_batches(ctx, nullptr, ws, batches, kDryPtr, Lmax, kDryPtr, N, 0.f, nullptr, 0, kDryPtr));
+    *out_bytes = ((ws.peak + 4095) & ~size_t(4095)) + 4096;
     return TVC_OK;
 }
 
@@ -1221,16 +1211,15 @@ int tvc_convert_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t
     hipStream_t s = (hipStream_t)stream;
     std::vector<RagBatchPlan> batches;
     TVC_CHECK(ragged_split(ctx, ctx->rag_batch_frames, B, Lmax, lens, &batches));
-    size_t bytes = 0;
-    TVC_CHECK(ragged_batch_bytes(ctx, batches, Lmax, N, &bytes, noise_angle ? 1 : 0));      // one dry walk per batch: host time on the launch path
+    Ws need(nullptr, 0, true);
+    TVC_CHECK(ragged_batches(ctx, s, need, batches, wav, Lmax, prepared, N, pitch_shift, noise_angle, seed, wave));      // host time on the launch path
+    const size_t bytes = (need.peak + 4095) & ~size_t(4095);      // (whole 4 KiB pages, as tvc_workspace_bytes_ragged promises)
     if (bytes > ws_bytes) return fail(ctx, TVC_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", bytes, ws_bytes);
     // the whole padded output is cleared once: every kernel writes its utterance's own samples only
     TVC_HIP(ctx, hipMemsetAsync(wave, 0, (size_t)B * Lmax * sizeof(float), s));
-    for (auto& p : batches) {
-        Ws ws(wsp, bytes, false);
-        TVC_CHECK(ragged_batch(ctx, s, ws, false, p, wav, Lmax, prepared, N, pitch_shift, noise_angle, seed, wave));
-    }
-    return TVC_OK;
+    Ws ws(wsp, bytes, false);
+    TVC_CHECK(ragged_batches(ctx, s, ws, batches, wav, Lmax, prepared, N, pitch_shift, noise_angle, seed, wave));
+    return walks_agree(ctx, __func__, ws.peak, need.peak);
 }
 
 int tvc_profile_enable(tvc_ctx* ctx, int on) {

@@ -192,23 +192,23 @@ static __global__ __launch_bounds__(256) void noise_ola_kernel(const float* __re
 // SourceNet + dsp
 // =================================================================================================
 // cmax: per-utterance |max| slot of `content` (block-floating-point guard of the fp16 split, conv3s.h)
-static int run_source_net(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* content, const float* f0,
+static int run_source_net(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* content, const float* f0,
                           const float* energy, float* amps, float* kern, int B, int T, const float* cmax, float* xmax_zeroed, hipEvent_t amps_ready = nullptr) {
     const int ncols = B * T;
     float* ef = ws.get<float>((size_t)B * T);
     float* x = ws.get<float>((size_t)B * kSrcCh * T);
     const int NB = ctx->rag ? ctx->rag->B : B;      // utterances (a ragged batch runs as B = 1, T = all its frames: ragged.h)
     float* xmax = xmax_zeroed ? xmax_zeroed : ws.get<float>((size_t)NB);      // (the caller's, zeroed with its other slots, or an own one)
-    if (!dry) {
+    if (!ws.dry) {
         hipLaunchKernelGGL(window_max_kernel, dim3(grid_for((long)ncols * 64)), dim3(256), 0, s, energy, ef, (long)B, T, kHop);
         EpiSumCond ep{x, ctx->src_content_in.bias, ef, f0, ctx->src_e_w, ctx->src_e_b, ctx->src_f_w, ctx->src_f_b, kSrcCh, T, ncols};
         int rc = 0;
         if (!gemm_s2_try(&rc, ctx, s, ctx->src_content_in, content, B, kSslDim, T, 0, ep, cmax)) rc = gemm_s_launch<2, 4, 2>(ctx, s, ctx->src_content_in, content, B, kSslDim, T, 0, ep, cmax);
         TVC_CHECK(rc);
     }
-    if (!dry && !xmax_zeroed) TVC_HIP(ctx, hipMemsetAsync(xmax, 0, (size_t)NB * sizeof(float), s));
-    for (int i = 0; i < 3; ++i) TVC_CHECK(run_convnext(ctx, s, ws, dry, ctx->src_mid[i], x, B, T, i == 2 ? xmax : nullptr));     // the last layer publishes the |max| slot of its output
-    if (dry) return 0;
+    if (!ws.dry && !xmax_zeroed) TVC_HIP(ctx, hipMemsetAsync(xmax, 0, (size_t)NB * sizeof(float), s));
+    for (int i = 0; i < 3; ++i) TVC_CHECK(run_convnext(ctx, s, ws, ctx->src_mid[i], x, B, T, i == 2 ? xmax : nullptr));     // the last layer publishes the |max| slot of its output
+    if (ws.dry) return 0;
     // to_amps (128 -> 15 rows: one 32-row m-tile)
     EpiBias<ACT_ELU1, false> ea{amps, ctx->src_to_amps.bias, nullptr, kHarm, T, ncols, (long)kHarm * T, 0};
     TVC_CHECK((gemm_s_launch<1, 4, 2>(ctx, s, ctx->src_to_amps, x, B, kSrcCh, T, 0, ea, xmax)));
@@ -234,15 +234,15 @@ static int run_harm_sums(tvc_ctx* ctx, hipStream_t s, const float* f0, double* c
 
 // Decoder.dsp (decoder.py:259-266): f0 [B,1,T], amps [B,15,T], kernel [B,961,T] -> source [B,16,L]
 // smax (nullable): per-utterance |max| slot [B] of `source`, zeroed by the caller; the two kernels that write `source` publish into it
-int run_dsp(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* f0, const float* amps, const float* kern,
-            const float* angle, uint64_t seed, float* source, int B, int T, float* smax, const DspFork* fk) {
+int run_dsp(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* f0, const float* amps, const float* kern, const float* angle, uint64_t seed, float* source, int B, int T,
+            float* smax, double* csum, const DspFork* fk) {
     const long L = (long)T * kHop;
-    double* csum = fk ? fk->csum : ws.get<double>((size_t)B * kHarm * T);
+    if (!csum) csum = ws.get<double>((size_t)B * kHarm * T);
     float* frames = ws.get<float>((size_t)B * T * kNfft);
     const int NB = ctx->rag ? ctx->rag->B : B;
     const int Tg = ctx->rag ? ctx->rag->Tlong : T;      // frames of the longest utterance: the per-utterance grids' extent
     float* smax_own = smax ? nullptr : ws.get<float>((size_t)NB);
-    if (dry) return 0;
+    if (ws.dry) return 0;
     if (!smax) {
         smax = smax_own;
         TVC_HIP(ctx, hipMemsetAsync(smax, 0, (size_t)NB * sizeof(float), s));
@@ -253,7 +253,7 @@ int run_dsp(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* f0, cons
     const float scale_size = (float)T / (float)L;         // F.interpolate(f0, Lw): size given
     const float scale_amp = (float)(1.0 / (double)kHop);  // F.interpolate(amps, scale_factor=480)
     hipStream_t sh = s;      // the harmonic branch's stream
-    if (fk) {                // forked (equal-length batches only): the frame sums are already scanned on the side stream; the synthesis waits for the amplitudes
+    if (fk) {                // forked: the frame sums are already scanned on the side stream; the synthesis waits for the amplitudes
         sh = fk->side;
         TVC_HIP(ctx, hipStreamWaitEvent(sh, fk->amps_ready, 0));
     } else {
@@ -355,9 +355,9 @@ static int filter_input_gemm(tvc_ctx* ctx, hipStream_t s, const float* content, 
     return rc;
 }
 
-int run_filter(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* content, const float* f0,
+int run_filter(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* content, const float* f0,
                const float* energy, const float* source, float* wave, int B, int T, const FilterTaps* taps, const float* cmax, const float* smax, float* zeroed_slots, bool x_slot_set,
-               float* x_pre, hipEvent_t x_ready) {
+               float* x_pre, bool x_pre_filled) {
     const long L = (long)T * kHop;
     static const int ch[5] = {384, 192, 96, 48, 24};
     const long len_dn[5] = {L, L / 5, L / 20, L / 80, L / 240};   // skip i lives at len_dn[i]
@@ -379,8 +379,8 @@ int run_filter(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* conte
     float* slots = zeroed_slots ? zeroed_slots : ws.get<float>((size_t)S_COUNT * NB);
     auto slot = [&](int i) { return slots + (size_t)i * NB; };
 
-    if (!dry) {
-        ProfScope ps(ctx, s, dry, "filter.in+down0");
+    if (!ws.dry) {
+        ProfScope ps(ctx, s, ws, "filter.in+down0");
         if (!zeroed_slots) TVC_HIP(ctx, hipMemsetAsync(slots, 0, (size_t)S_COUNT * NB * sizeof(float), s));
         if (!cmax) {
             TVC_CHECK(run_amax_rows(ctx, s, content, B, kSslDim, T, slot(S_CONTENT)));
@@ -391,7 +391,7 @@ int run_filter(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* conte
             TVC_CHECK(run_amax_rows(ctx, s, energy, B, 1, L, slot(S_SRC)));
             smax = slot(S_SRC);
         }
-        if (!x_ready) TVC_CHECK(filter_input_gemm(ctx, s, content, f0, x, B, T, cmax));      // (x_ready: the caller launched it on its side stream)
+        if (!x_pre_filled) TVC_CHECK(filter_input_gemm(ctx, s, content, f0, x, B, T, cmax));      // (filled: the caller ran it on its side stream and joined)
         // x0's |max| slot: the functor finishes the elements, so the slot is the bound bw |content|max + bb instead of a pass over x0
         if (!(zeroed_slots && x_slot_set)) TVC_CHECK(run_slot_affine(ctx, s, slot(S_X), cmax, 1, ctx->flt_in_bw, ctx->flt_in_bb, NB));
         // skips[0] is read as FiLM cond only (ups[4]): it is written as the two halves' ready operand; the fp32 tensor exists for the parity tap alone
@@ -405,9 +405,9 @@ int run_filter(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* conte
         float* xi = xi_pre[i];
         float* h1 = d.cin == 24 ? nullptr : ws.get<float>((size_t)B * d.cin * len);      // (the 24-channel block keeps its intermediates on chip)
         float* h2 = d.cin == 24 ? nullptr : ws.get<float>((size_t)B * d.cin * len);
-        if (!dry) {
+        if (!ws.dry) {
             static const char* names[4] = {"filter.down1", "filter.down2", "filter.down3", "filter.down4"};
-            ProfScope ps(ctx, s, dry, names[i - 1]);
+            ProfScope ps(ctx, s, ws, names[i - 1]);
             float* y2 = i < 4 ? xi_pre[i + 1] : nullptr;              // the next block's 1/f-rate input
             const int f2 = i < 4 ? ctx->downs[i].factor : 0;
             const float* mxi = slot(S_SKIP0 + i - 1);
@@ -429,7 +429,6 @@ int run_filter(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* conte
         }
         ws.release(mk);
     }
-    if (!dry && x_ready) TVC_HIP(ctx, hipStreamWaitEvent(s, x_ready, 0));      // the up path is x0's first reader: join here, behind the whole down path
     // up path: level outputs are persistent, block temporaries are released per level
     float* xlev[5];
     {
@@ -452,13 +451,13 @@ int run_filter(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* conte
         float* xu = ws.get<float>((size_t)B * C * lo);
         float* h = ws.get<float>((size_t)B * C * lo);
         float* x1 = ws.get<float>((size_t)B * C * lo);
-        if (!dry && C == 24) {
+        if (!ws.dry && C == 24) {
             // last level: Upsample block + output_layer in two launches, waveform written directly
-            ProfScope ps(ctx, s, dry, "filter.up4+out");
+            ProfScope ps(ctx, s, ws, "filter.up4+out");
             TVC_CHECK(run_up24_split(ctx, s, u, x, cond, ctx->down0_bw, ctx->down0_bb, x1, wave, B, lo, mx_in, smax, slot(S_UX1 + i)));
-        } else if (!dry) {
+        } else if (!ws.dry) {
             static const char* names[4] = {"filter.up0", "filter.up1", "filter.up2", "filter.up3"};
-            ProfScope ps(ctx, s, dry, names[i]);
+            ProfScope ps(ctx, s, ws, names[i]);
             const float lscale = (float)(1.0 / (double)u.factor);   // F.interpolate(scale_factor=f): ATen uses float(1/f)
             for (int half = 0; half < 2; ++half) {
                 const PackedW& ca = half ? u.c3 : u.c1;
@@ -499,7 +498,7 @@ int run_filter(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* conte
         x = xlev[i];
         mx_in = slot(S_LEV + i);
     }
-    if (!dry && taps) {   // parity taps: the block outputs are still live in the workspace
+    if (!ws.dry && taps) {   // parity taps: the block outputs are still live in the workspace
         for (int i = 1; i < 5; ++i)      // (skips[0] was written into the tap by its producer)
             if (taps->skips[i] && i == 1)      // the 48-channel skip travels in the G8 layout (down24f_kernel -> conv48s.hip's FiLM cond)
                 hipLaunchKernelGGL(g8_to_planar_kernel, dim3(grid_for((long)B * 48 * len_dn[1])), dim3(256), 0, s, skip[1], taps->skips[1], (long)B, len_dn[1], 48);
@@ -514,10 +513,10 @@ int run_filter(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* conte
                 TVC_HIP(ctx, hipMemcpyAsync(taps->ups[i], xlev[i], (size_t)B * ctx->ups[i].cout * l * sizeof(float), hipMemcpyDeviceToDevice, s));
         }
     }
-    return dry ? 0 : launch_check(ctx, "filter_net");
+    return ws.dry ? 0 : launch_check(ctx, "filter_net");
 }
 
-int run_decoder(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* content, const float* f0,
+int run_decoder(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* content, const float* f0,
                 const float* energy, const float* angle, uint64_t seed, float* wave, float* amps_out,
                 float* kernel_out, float* source_out, int B, int T, const float* content_bound, const float* energy_bound) {
     const long L = (long)T * kHop;
@@ -531,61 +530,44 @@ int run_decoder(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* cont
     float* smax = cmax + NB;
     float* xmax = smax + NB;
     float* fslots = xmax + NB;
-    if (!dry) {
+    // FilterNet's input contraction's output and the oscillator's frame sums
+    float* x0 = ws.get<float>((size_t)B * 384 * T);
+    double* csum = ws.get<double>((size_t)B * kHarm * T);
+    if (!ws.dry) {
         TVC_CHECK(run_slot_prep(ctx, s, cmax, (3 + kFilterSlots) * NB, content_bound ? cmax : nullptr, content_bound, 0, 1.f, 0.f, energy_bound ? smax : nullptr,
                                 energy_bound, 1, 1.f, 0.f, content_bound ? fslots + (size_t)kFilterSlotX * NB : nullptr, ctx->flt_in_bw, ctx->flt_in_bb,
                                 NB));      // (the dsp kernels raise smax to cat[source, energy]'s; the third: FilterNet's x0 slot from |content|max)
         if (!content_bound) TVC_CHECK(run_amax_rows(ctx, s, content, B, kSslDim, T, cmax));
         if (!energy_bound) TVC_CHECK(run_amax_rows(ctx, s, energy, B, 1, L, smax));
     }
-    // FilterNet's input contraction (768 -> 384 at the frame rate: 48 us at the bench shape) reads nothing SourceNet or the DSP stage produce and
-    // its output is first read by Upsample 0, behind the whole down path: outside a stream capture (a fork inside a replayed graph costs more than
-    // it hides) it runs on the
-    // context's side stream - free again since the encoder joined its pitch chain - beside SourceNet's small launches and the vector-ALU-bound
-    // oscillator, and run_filter waits for it where the up path begins.
-    float* x0 = nullptr;
-    double* csum = nullptr;
-    bool fork = false;
-    if (wave || dry) {      // (a dry run sizes the workspace for the full decoder whatever pointers it was handed)
-        x0 = ws.get<float>((size_t)B * 384 * T);
-        csum = ws.get<double>((size_t)B * kHarm * T);
-        fork = !dry && ctx->side && ctx->ev_fork2 && ctx->ev_join2 && ctx->ev_amps;      // (a ragged batch too: the side stream's kernels read its base tables only - rag_setup built them on s in front of the fork -, no column-tile table)
-        if (fork) {
-            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) fork = false;
-        }
-        if (fork) {
-            // The side stream's chain: the oscillator's frame sums (f0 only) -> FilterNet's input contraction -> [amplitudes ready] -> the harmonic
-            // synthesis (vector-ALU-bound, no LDS) beside SourceNet's to_kernel GEMM and the noise branch's FFTs on the launch stream.
-            TVC_HIP(ctx, hipEventRecord(ctx->ev_fork2, s));            // content, f0 and cmax are complete on s
-            TVC_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork2, 0));
-            TVC_CHECK(run_harm_sums(ctx, ctx->side, f0, csum, B, T));
-            {
-                ProfScope ps(ctx, ctx->side, dry, "filter_net.input@side");      // FilterNet's work outside its region on the launch stream: bench.py adds it to the roofline's duration
-                TVC_CHECK(filter_input_gemm(ctx, ctx->side, content, f0, x0, B, T, cmax));
-            }
-        }
+    // FilterNet's input contraction (768 -> 384 at the frame rate: 48 us at the bench shape) reads nothing SourceNet or dsp produce: with the
+    // waveform asked for, it runs on the context's side stream behind the oscillator's frame sums (f0 only), beside SourceNet; the harmonic
+    // synthesis (vector-ALU-bound) follows there beside to_kernel and the noise FFTs on s; the join follows dsp.  Ragged batches too: the side
+    // stream's kernels read the batch's base tables only (built on s in front of the fork), no column-tile table.
+    SideFork fk(ctx, s);
+    if (wave) TVC_CHECK(fk.fork(ws, ctx->ev_fork2, ctx->ev_join2));      // content, f0 and cmax are complete on s
+    if (fk.forked()) {
+        TVC_CHECK(run_harm_sums(ctx, fk.side, f0, csum, B, T));
+        ProfScope ps(ctx, fk.side, ws, "filter_net.input@side");      // FilterNet's work outside its region on the launch stream: bench.py adds it to the roofline's duration
+        TVC_CHECK(filter_input_gemm(ctx, fk.side, content, f0, x0, B, T, cmax));
     }
     size_t mk = ws.mark();
     {
-        ProfScope ps(ctx, s, dry, "source_net");
-        TVC_CHECK(run_source_net(ctx, s, ws, dry, content, f0, energy, amps, kern, B, T, cmax, xmax, fork ? ctx->ev_amps : nullptr));
+        ProfScope ps(ctx, s, ws, "source_net");
+        TVC_CHECK(run_source_net(ctx, s, ws, content, f0, energy, amps, kern, B, T, cmax, xmax, fk.forked() ? ctx->ev_amps : nullptr));
     }
     ws.release(mk);
-    if (!dry && !wave && !source_out) return 0;  // SourceNet.forward alone (decoder.py:126-134): the caller asked for amps / kernel only
+    if (!wave && !source_out) return 0;  // SourceNet.forward alone (decoder.py:126-134): the caller asked for amps / kernel only
     {
-        ProfScope ps(ctx, s, dry, "dsp");
-        const DspFork fk{ctx->side, csum, ctx->ev_amps};
-        TVC_CHECK(run_dsp(ctx, s, ws, dry, f0, amps, kern, angle, seed, source, B, T, smax, fork ? &fk : nullptr));
-        if (fork) {      // join: the side stream's whole chain (harmonics, FilterNet's input contraction) is behind this event
-            TVC_HIP(ctx, hipEventRecord(ctx->ev_join2, ctx->side));
-            TVC_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_join2, 0));
-        }
+        ProfScope ps(ctx, s, ws, "dsp");
+        const DspFork df{fk.side, ctx->ev_amps};
+        TVC_CHECK(run_dsp(ctx, s, ws, f0, amps, kern, angle, seed, source, B, T, smax, csum, fk.forked() ? &df : nullptr));
+        TVC_CHECK(fk.join());      // the side stream's whole chain (harmonics, FilterNet's input contraction) is behind s from here
     }
     ws.release(mk);
-    if (!dry && !wave) return 0;                 // ... or for Decoder.dsp's output (decoder.py:259-266) without the FilterNet pass
-    ProfScope ps(ctx, s, dry, "filter_net");
-    TVC_CHECK(run_filter(ctx, s, ws, dry, content, f0, energy, source, wave, B, T, nullptr, cmax, smax, fslots, content_bound != nullptr, x0, fork ? ctx->ev_join2 : nullptr));
+    if (!wave) return 0;                 // ... or for Decoder.dsp's output (decoder.py:259-266) without the FilterNet pass
+    ProfScope ps(ctx, s, ws, "filter_net");
+    TVC_CHECK(run_filter(ctx, s, ws, content, f0, energy, source, wave, B, T, nullptr, cmax, smax, fslots, content_bound != nullptr, x0, fk.forked()));
     ws.release(mk);
     return 0;
 }

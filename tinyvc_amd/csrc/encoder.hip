@@ -270,7 +270,7 @@ static bool cnx_try(int* rc, tvc_ctx* ctx, hipStream_t s, const ConvNeXtW& w, fl
 }
 
 // amax_out: optional per-utterance |max| slot of the layer's output (zeroed by the caller), for the contraction that reads it next
-int run_convnext(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const ConvNeXtW& w, float* x, int B, int T, float* amax_out) {
+int run_convnext(tvc_ctx* ctx, hipStream_t s, Ws& ws, const ConvNeXtW& w, float* x, int B, int T, float* amax_out) {
     const int C = w.C, C2 = 2 * w.C, ncols = B * T;
     const int NB = ctx->rag ? ctx->rag->B : B;      // utterances (a ragged batch runs as B = 1, T = all its frames: ragged.h)
     size_t mk = ws.mark();
@@ -282,7 +282,7 @@ int run_convnext(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const ConvNeXtW&
     float* ymax = ws.get<float>((size_t)NB);      // |max| slots of the two 1x1s' inputs (block-floating-point guard, conv3s.h)
     float* hmax = ws.get<float>((size_t)NB);
     ws.release(mk);
-    if (dry) return 0;
+    if (ws.dry) return 0;
 #ifndef TVC_CNX_OLD
     {
         int rc = 0;
@@ -420,7 +420,7 @@ int run_pitch_decode(tvc_ctx* ctx, hipStream_t s, const float* logits, float* f0
     return launch_check(ctx, "pitch_decode");
 }
 
-int run_encoder(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* spec, float* ssl, float* f0,
+int run_encoder(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* spec, float* ssl, float* f0,
                 float* logits, int B, int T, const float* spec_bound, float* zeroed_slots, float* f0_shifted, float shift) {
     const int ncols = B * T;
     float* xs = ws.get<float>((size_t)B * kSslCh * T);
@@ -431,7 +431,7 @@ int run_encoder(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* spec
     const int NB = ctx->rag ? ctx->rag->B : B;      // utterances (ragged batch: B = 1, T = all frames)
     float* slots = zeroed_slots ? zeroed_slots : ws.get<float>((size_t)3 * NB);
     float *spec_max = slots, *xs_max = slots + NB, *xp_max = slots + 2 * NB;
-    if (!dry) {
+    if (!ws.dry) {
         if (!zeroed_slots) TVC_HIP(ctx, hipMemsetAsync(slots, 0, (size_t)3 * NB * sizeof(float), s));
         if (spec_bound) spec_max = const_cast<float*>(spec_bound);      // the caller's bound IS the slot: no pass over the 961 x T tensor
         else TVC_CHECK(run_amax_rows(ctx, s, spec, B, kBins, T, spec_max));
@@ -444,43 +444,35 @@ int run_encoder(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* spec
     // The pitch estimator (4 narrow ConvNeXt layers + logits + decode) and the SSL chain are independent after the
     // stacked input 1x1: fork the pitch chain onto the context's side stream and join before returning, so its
     // small launches fill the gaps of the SSL chain instead of extending the critical path.  Each chain gets its own
-    // scratch block (the per-layer mark/release scratch would alias otherwise).
+    // scratch block (the per-layer mark/release scratch would alias otherwise).  Not while the stream is being captured: a replayed
+    // graph with the second branch is slower than the one chain (32-stream block 1.90 -> 1.71 ms; one 4 s utterance 1.36 ... 1.59 ms
+    // from box to box with the branch, 1.43 without).
     const int gtiles = ((ctx->rag ? ctx->rag->Tlong : T) + 63) / 64;      // run_convnext: y, h, the GRN tile sums, nx, two slots
     const size_t ssl_scratch = ((size_t)B * kSslCh * T * 3 + (size_t)NB * kSslCh * 2 * (gtiles + 1)) * sizeof(float) + (size_t)NB * 8 + 4096;
     char* ssl_blk = ws.get<char>(ssl_scratch);
-    Ws wssl(ssl_blk, ssl_scratch, dry);
-    hipStream_t sp = s;
-    bool fork = !dry && ctx->side;
-    if (fork) {
-        // Not while the stream is being captured: a replayed graph with the second branch is slower than the one chain (32-stream block
-        // 1.90 -> 1.71 ms; one 4 s utterance 1.36 ... 1.59 ms from box to box with the branch, 1.43 without)
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) fork = false;
-    }
-    if (fork) {
-        TVC_HIP(ctx, hipEventRecord(ctx->ev_fork, s));
-        TVC_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-        sp = ctx->side;
-    }
-    for (int i = 0; i < 4; ++i) TVC_CHECK(run_convnext(ctx, sp, ws, dry, ctx->pit_mid[i], xp, B, T, i == 3 ? xp_max : nullptr));      // the last layer publishes the |max| slot of its output
-    if (!dry) {
+    Ws wssl(ssl_blk, ssl_scratch, ws.dry);
+    SideFork fk(ctx, s);
+    TVC_CHECK(fk.fork(ws, ctx->ev_fork, ctx->ev_join));
+    const hipStream_t sp = fk.side;
+    for (int i = 0; i < 4; ++i) TVC_CHECK(run_convnext(ctx, sp, ws, ctx->pit_mid[i], xp, B, T, i == 3 ? xp_max : nullptr));      // the last layer publishes the |max| slot of its output
+    if (!ws.dry) {
         EpiBias<ACT_NONE, false> ep{lg, ctx->pit_out.bias, nullptr, kPitchClasses, T, ncols, (long)kPitchClasses * T, 0};
         int rc = 0;
         if (!gemm_s2_try(&rc, ctx, sp, ctx->pit_out, xp, B, kPitchCh, T, 0, ep, xp_max)) rc = gemm_s_launch<ENC_MTB, ENC_NWV, ENC_BPC>(ctx, sp, ctx->pit_out, xp, B, kPitchCh, T, 0, ep, xp_max);
         TVC_CHECK(rc);
         hipLaunchKernelGGL(pitch_decode_kernel, dim3((ncols + 63) / 64), dim3(kPdWaves * 64), 0, sp, lg, ctx->pitch_freq, f0, B, T, f0_shifted, shift);
     }
-    if (fork) TVC_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->side));
-    for (int i = 0; i < 6; ++i) TVC_CHECK(run_convnext(ctx, s, wssl, dry, ctx->ssl_mid[i], xs, B, T, i == 5 ? xs_max : nullptr));
-    if (!wssl.ok()) return fail(ctx, TVC_ERR_WORKSPACE, "encoder: SSL scratch block too small");
-    if (dry) return 0;
+    TVC_CHECK(fk.end());
+    for (int i = 0; i < 6; ++i) TVC_CHECK(run_convnext(ctx, s, wssl, ctx->ssl_mid[i], xs, B, T, i == 5 ? xs_max : nullptr));
+    if (wssl.peak > wssl.cap) return fail(ctx, TVC_ERR_WORKSPACE, "encoder: SSL scratch block too small");      // (the measuring walk finds it first)
+    if (ws.dry) return 0;
     {
         EpiBias<ACT_NONE, false> ep{ssl, ctx->ssl_out.bias, nullptr, kSslDim, T, ncols, (long)kSslDim * T, 0};
         int rc = 0;
         if (!gemm_s2_try(&rc, ctx, s, ctx->ssl_out, xs, B, kSslCh, T, 0, ep, xs_max)) rc = gemm_s_launch<ENC_MTB, ENC_NWV, ENC_BPC>(ctx, s, ctx->ssl_out, xs, B, kSslCh, T, 0, ep, xs_max);
         TVC_CHECK(rc);
     }
-    if (fork) TVC_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
+    TVC_CHECK(fk.join());
     return launch_check(ctx, "encoder");
 }
 

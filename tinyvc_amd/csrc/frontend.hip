@@ -7,9 +7,8 @@ namespace tvc {
 
 // |STFT| (spectrogram.py:8-15): one wavefront per 1920-sample frame, a 960-point complex FFT on the packed real frame
 // (fft.hip).  Needs no scratch.
-int run_stft(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* wav, float* spec, int B, int64_t L) {
-    (void)ws;
-    return dry ? 0 : run_stft_fft(ctx, s, wav, spec, B, L);
+int run_stft(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* wav, float* spec, int B, int64_t L) {
+    return ws.dry ? 0 : run_stft_fft(ctx, s, wav, spec, B, L);
 }
 
 // ---- energy -------------------------------------------------------------------------------------
@@ -136,10 +135,10 @@ static __global__ __launch_bounds__(256) void pooled_max_rag_kernel(const float*
     }
 }
 
-int run_energy(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* wav, float* energy, int B, int64_t L, float* emax, float* spec_bound, float* zero, int nz) {
+int run_energy(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* wav, float* energy, int B, int64_t L, float* emax, float* spec_bound, float* zero, int nz) {
     const int ne = (int)((L + 2 * 32 - 128) / 64 + 1);
     float* e = ws.get<float>((size_t)B * ne + 8);
-    if (dry) return 0;
+    if (ws.dry) return 0;
     if (ctx->rag) {
         RagDev rg;
         TVC_CHECK(rag_view(ctx, s, kHop, 0, &rg, nullptr));

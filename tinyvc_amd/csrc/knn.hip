@@ -1150,8 +1150,9 @@ static int coarse_max_nsplit(int qtiles) { return (768 + qtiles - 1) / qtiles; }
 
 // query normalisation + the per-query top-4 lists; shared by the whole-index match and the index-sharded variant.
 // (The blob's kind lives in device memory - its header -, so the host cannot pick an instantiation: the kernels branch on it.)
-static int knn_candidates(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* src, const float* prepared, int64_t N, int B, int T,
+static int knn_candidates(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const float* prepared, int64_t N, int B, int T,
                           const KnnPlan& p, KnnLists* L) {
+    if (N > 0x7fffff00L) return fail(ctx, TVC_ERR_ARG, "index too large");
     float* qn = ws.get<float>((size_t)B * KD * T);
     L->cv = ws.get<float>((size_t)p.nsplit * p.ncols * 4);
     L->ci = ws.get<int>((size_t)p.nsplit * p.ncols * 4);
@@ -1171,12 +1172,11 @@ static int knn_candidates(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const f
         L->ri = ws.get<int>((size_t)p.ncols * 4);
         L->flag = ws.get<int>(64);
     }
-    if (dry) return 0;
-    if (N > 0x7fffff00L) return fail(ctx, TVC_ERR_ARG, "index too large");
+    if (ws.dry) return 0;
     const int nblk = two_stage ? cq * 4 : (p.ncols + 63) / 64;      // the fp16 query image is written for whole 256-query tiles
     hipLaunchKernelGGL(query_normalize_kernel, dim3(nblk), dim3(QN_WAVES * 64), 0, s, src, qn, B, T, qh, cnt, L->flag);
     if (two_stage) {
-        ProfScope ps(ctx, s, dry, "knn.coarse+rescore");
+        ProfScope ps(ctx, s, ws, "knn.coarse+rescore");
         const int t2 = (int)((p.Npad + C_MT - 1) / C_MT);          // 256-vector tiles
         // pass A: an eighth of the index, at least 1280 vectors.  (A smaller sample lowers the threshold: longer lists - whose rows the
         // rescoring wave's own threshold then drops unscored - and, past C_CAP entries, the exact fallback: a sixteenth sends the
@@ -1189,18 +1189,18 @@ static int knn_candidates(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const f
         TVC_CHECK((coarse_launch<1>(ctx, s, prepared, p.Npad, (int)N, qh, p.ncols, cq, t2, c4v, nsA, cnt, cand, candv, L->flag, nullptr)));
         hipLaunchKernelGGL(knn_rescore_kernel, dim3((p.ncols + 3) / 4), dim3(256), 0, s, prepared, p.Npad, (int)N, qn, p.ncols, T, cnt, cand, candv, L->rv, L->ri);
     }
-    ProfScope ps(ctx, s, dry, "knn.exact");       // ~0 when the two-stage search succeeded (the kernel exits on the flag)
+    ProfScope ps(ctx, s, ws, "knn.exact");       // ~0 when the two-stage search succeeded (the kernel exits on the flag)
     hipLaunchKernelGGL(knn_topk_split_kernel, dim3((unsigned)(p.qtiles * p.nsplit)), dim3(512), 0, s, prepared, p.Npad, (int)N, qn, p.ncols, T,
                        p.nsplit, p.tps, L->cv, L->ci, (const int*)L->flag);
     return 0;
 }
 
-int run_knn_topk(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* src, const float* prepared, int64_t N,
+int run_knn_topk(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const float* prepared, int64_t N,
                  float* sims_out, int64_t* idx_out, int B, int T) {
     const KnnPlan p = knn_plan(B, T, N);
     KnnLists L;
-    TVC_CHECK(knn_candidates(ctx, s, ws, dry, src, prepared, N, B, T, p, &L));
-    if (dry) return 0;
+    TVC_CHECK(knn_candidates(ctx, s, ws, src, prepared, N, B, T, p, &L));
+    if (ws.dry) return 0;
     hipLaunchKernelGGL(knn_merge_kernel, dim3((p.ncols + 255) / 256), dim3(256), 0, s, L.cv, L.ci, p.nsplit, p.ncols, sims_out, idx_out, L.rv, L.ri, L.flag);
     return launch_check(ctx, "knn_topk");
 }
@@ -1216,12 +1216,12 @@ int run_knn_finish(tvc_ctx* ctx, hipStream_t s, const float* slots, float* out, 
     return launch_check(ctx, "knn_finish");
 }
 
-int run_knn(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* src, const float* prepared, int64_t N,
+int run_knn(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const float* prepared, int64_t N,
             float* out, int64_t* idx_out, int B, int T) {
     const KnnPlan p = knn_plan(B, T, N);
     KnnLists L;
-    TVC_CHECK(knn_candidates(ctx, s, ws, dry, src, prepared, N, B, T, p, &L));
-    if (dry) return 0;
+    TVC_CHECK(knn_candidates(ctx, s, ws, src, prepared, N, B, T, p, &L));
+    if (ws.dry) return 0;
     hipLaunchKernelGGL(knn_merge_gather_kernel, dim3((p.ncols + 31) / 32), dim3(256), 0, s, L.cv, L.ci, p.nsplit, p.ncols, T, (int)N, p.Npad,
                        prepared, out, idx_out, L.rv, L.ri, L.flag);
     return launch_check(ctx, "knn_match");

@@ -169,11 +169,11 @@ __global__ __launch_bounds__(256) void knn_general_gather_kernel(const float* __
 
 }  // namespace
 
-int run_knn_general(tvc_ctx* ctx, hipStream_t s, Ws& ws, bool dry, const float* src, const float* index, int64_t N, int k, int metric, float* out, int64_t* idx_out,
+int run_knn_general(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const float* index, int64_t N, int k, int metric, float* out, int64_t* idx_out,
                     float* val_out, int B, int T) {
     const long ncols = (long)B * T;
     int64_t* idx = idx_out ? idx_out : ws.get<int64_t>((size_t)ncols * k);
-    if (dry) return 0;
+    if (ws.dry) return 0;
     static_assert(GT / 64 == GQ, "one merging wave per query");
     constexpr int lds = (KDG * GQ + 16 + 2 * GQ * GT * GK) * 4;
     static bool ready_dev[64] = {};

@@ -19,6 +19,8 @@ struct tvc_ctx;
 
 namespace tvc {
 
+struct Ws;
+
 struct RagDev {                   // device view handed to a kernel (tb == nullptr: equal lengths, the kernel's ordinary path)
     const int* tb = nullptr;      // [B] frames of utterance b
     const int* pre = nullptr;     // [B + 1] exclusive prefix of tb
@@ -50,8 +52,8 @@ constexpr int kRagTabSlots = 24;      // distinct (rate, tile width) pairs a con
 // ints of device scratch a ragged batch of B utterances and Ttot frames needs (tb, pre, row, col2b, the tile tables)
 inline size_t rag_scratch_ints(int B, int Ttot) { return (size_t)3 * (B + 1) + (size_t)Ttot + (size_t)kRagTabSlots * (B + 1) + 64; }
 
-// fills `h` from the host lengths (frames), uploads the tables into `scratch` (rag_scratch_ints ints) on stream s
-int rag_setup(tvc_ctx* ctx, hipStream_t s, bool dry, RagHost& h, const std::vector<int>& frames, const std::vector<int>& rows, int Tmax, int* scratch);
+// fills `h` from the host lengths (frames), takes rag_scratch_ints ints from ws and uploads the tables into them on stream s
+int rag_setup(tvc_ctx* ctx, hipStream_t s, Ws& ws, RagHost& h, const std::vector<int>& frames, const std::vector<int>& rows, int Tmax);
 // the view of the context's current ragged batch for a launch at `mult` samples per frame; bn > 0: with the column-tile table of
 // bn-wide tiles (built on first use), *ntiles = its total.  Equal-length calls (no current batch) get the empty view.
 int rag_view(tvc_ctx* ctx, hipStream_t s, int mult, int bn, RagDev* out, int* ntiles);

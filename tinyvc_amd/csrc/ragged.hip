@@ -69,7 +69,7 @@ int upload_ints(tvc_ctx* ctx, hipStream_t s, const std::vector<int>& src, int* d
 }
 }  // namespace
 
-int rag_setup(tvc_ctx* ctx, hipStream_t s, bool dry, RagHost& h, const std::vector<int>& frames, const std::vector<int>& rows, int Tmax, int* scratch) {
+int rag_setup(tvc_ctx* ctx, hipStream_t s, Ws& ws, RagHost& h, const std::vector<int>& frames, const std::vector<int>& rows, int Tmax) {
     h.B = (int)frames.size();
     h.tb = frames;
     h.row = rows;
@@ -83,7 +83,7 @@ int rag_setup(tvc_ctx* ctx, hipStream_t s, bool dry, RagHost& h, const std::vect
         if (frames[b] < h.Tshort) h.Tshort = frames[b];
     }
     h.Ttot = h.pre[h.B];
-    int* p = scratch;
+    int* p = ws.get<int>(rag_scratch_ints(h.B, h.Ttot));
     int* d_tb = p;
     p += h.B + 1;
     int* d_pre = p;
@@ -99,7 +99,7 @@ int rag_setup(tvc_ctx* ctx, hipStream_t s, bool dry, RagHost& h, const std::vect
     h.d_pre = d_pre;
     h.d_row = d_row;
     h.d_col2b = d_col2b;
-    if (dry) return 0;
+    if (ws.dry) return 0;
     TVC_CHECK(upload_ints(ctx, s, frames, d_tb));
     TVC_CHECK(upload_ints(ctx, s, rows, d_row));
     hipLaunchKernelGGL(rag_prefix_kernel, dim3(1), dim3(1024), 0, s, d_tb, d_pre, d_col2b, h.B, 1, 0);

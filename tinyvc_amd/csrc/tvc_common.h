@@ -168,13 +168,33 @@ inline int fail(tvc_ctx* ctx, int code, const char* fmt, ...) {
         if (rc_ != 0) return rc_; \
     } while (0)
 
-// RAII region timer: records a hipEvent pair on the launch stream when ctx->profiling is on.
+// Bump allocator over the caller's workspace; in dry mode it only measures (api.hip TVC_RUN: every entry walks its driver dry, then for
+// real).  The drivers make the same get() calls in both walks - only launches, memsets, events and uploads look at `dry` -: equal peaks.
+struct Ws {
+    char* base;
+    size_t cap, off = 0, peak = 0;
+    bool dry;
+    Ws(void* p, size_t c, bool d) : base((char*)p), cap(c), dry(d) {}
+    template <class T>
+    T* get(size_t n) {
+        size_t bytes = (n * sizeof(T) + 255) & ~size_t(255);
+        size_t o = off;
+        off += bytes;
+        if (off > peak) peak = off;
+        if (dry) return (T*)(uintptr_t)256;  // never dereferenced
+        return (T*)(base + o);
+    }
+    size_t mark() const { return off; }
+    void release(size_t m) { off = m; }
+};
+
+// RAII region timer: records a hipEvent pair on the launch stream when ctx->profiling is on (never while ws.dry).
 struct ProfScope {
     tvc_ctx* ctx;
     hipStream_t s;
     int idx = -1;
-    ProfScope(tvc_ctx* c, hipStream_t st, bool dry, const char* name) : ctx(c), s(st) {
-        if (!c || !c->profiling || dry) return;
+    ProfScope(tvc_ctx* c, hipStream_t st, const Ws& ws, const char* name) : ctx(c), s(st) {
+        if (!c || !c->profiling || ws.dry) return;
         if (c->profiling == 2 && std::strncmp(name, "filter_net", 10) != 0) return;     // the roofline's regions alone (filter_net, and filter_net.input@side when the input contraction is forked): 2-4 event records per step instead of 38
         tvc_prof_region r;
         r.name = name;
@@ -196,24 +216,39 @@ struct ProfScope {
     }
 };
 
-// Bump allocator over the caller's workspace.  In dry mode it only measures.
-struct Ws {
-    char* base;
-    size_t cap, off = 0, peak = 0;
-    bool dry;
-    Ws(void* p, size_t c, bool d) : base((char*)p), cap(c), dry(d) {}
-    template <class T>
-    T* get(size_t n) {
-        size_t bytes = (n * sizeof(T) + 255) & ~size_t(255);
-        size_t o = off;
-        off += bytes;
-        if (off > peak) peak = off;
-        if (dry) return (T*)(uintptr_t)256;  // never dereferenced
-        return (T*)(base + o);
+// A branch on the context's side stream (run_encoder's pitch chain, run_decoder's oscillator and FilterNet input contraction).  fork() forks
+// only when the side stream and both events exist, ws.dry is false and `s` is not being captured; `side` = the branch's
+// stream (`s` unforked).  end() records `ev_join` behind the branch; join() makes `s` wait for it (recording it first if end() has not run),
+// and so does the destructor if join() has not run: an error return leaves `s` behind every side launch (they write into the workspace).
+struct SideFork {
+    tvc_ctx* ctx;
+    hipStream_t s, side;
+    hipEvent_t ev_join = nullptr;      // non-null while forked
+    bool ended = false;
+    SideFork(tvc_ctx* c, hipStream_t st) : ctx(c), s(st), side(st) {}
+    bool forked() const { return ev_join != nullptr; }
+    int fork(const Ws& ws, hipEvent_t ev_fork, hipEvent_t join) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (ws.dry || !ctx->side || !ev_fork || !join || hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return 0;
+        TVC_HIP(ctx, hipEventRecord(ev_fork, s));
+        TVC_HIP(ctx, hipStreamWaitEvent(ctx->side, ev_fork, 0));
+        side = ctx->side;
+        ev_join = join;
+        return 0;
     }
-    size_t mark() const { return off; }
-    void release(size_t m) { off = m; }
-    bool ok() const { return dry || peak <= cap; }
+    int end() {
+        if (forked() && !ended) TVC_HIP(ctx, hipEventRecord(ev_join, side));
+        ended = true;
+        return 0;
+    }
+    hipError_t record_and_wait() {
+        hipEvent_t e = ev_join;
+        ev_join = nullptr;
+        const hipError_t r = e && !ended ? hipEventRecord(e, side) : hipSuccess;
+        return e && r == hipSuccess ? hipStreamWaitEvent(s, e, 0) : r;
+    }
+    int join() { TVC_HIP(ctx, record_and_wait()); return 0; }
+    ~SideFork() { (void)record_and_wait(); }      // (an error return between fork and join keeps its own message)
 };
 
 inline int launch_check(tvc_ctx* ctx, const char* what) {
@@ -222,12 +257,12 @@ inline int launch_check(tvc_ctx* ctx, const char* what) {
     return 0;
 }
 
-// ---- stage drivers (each enqueues kernels on `s`; `dry` = measure workspace only) ----------
-int run_stft(tvc_ctx*, hipStream_t, Ws&, bool dry, const float* wav, float* spec, int B, int64_t L);
+// ---- stage drivers (each enqueues kernels on `s`; ws.dry = measure the workspace only) ----------
+int run_stft(tvc_ctx*, hipStream_t, Ws&, const float* wav, float* spec, int B, int64_t L);
 int run_stft_fft(tvc_ctx*, hipStream_t, const float* wav, float* spec, int B, int64_t L);
 int run_noise_ifft(tvc_ctx*, hipStream_t, const float* kern, const float* angle, uint64_t seed, float* frames, int B, int T, bool angle_padded = false);      // angle == nullptr: phases drawn in the kernel from `seed`
 // emax (optional, equal-length batches only): per-utterance max of the pooled |x| = max |wav| of the utterance, written (not accumulated)
-int run_energy(tvc_ctx*, hipStream_t, Ws&, bool dry, const float* wav, float* energy, int B, int64_t L, float* emax = nullptr, float* spec_bound = nullptr,
+int run_energy(tvc_ctx*, hipStream_t, Ws&, const float* wav, float* energy, int B, int64_t L, float* emax = nullptr, float* spec_bound = nullptr,
                float* zero = nullptr, int nz = 0);      // (emax given: the pooled-maximum launch also zeroes zero[0 .. nz))
 const float* knn_index_amax(const float* prepared);
 // out[b] = a * in[b * in_stride] + c for b < n: a |max| slot from the slot of the tensor it is a bounded function of (frontend.hip)
@@ -241,16 +276,16 @@ constexpr int kFilterSlotX = 2;       // ... and the one of its input contractio
 constexpr int kFilterSlots = 41;      // run_filter's |max| slots per utterance (decoder.hip S_COUNT)
       // device pointer to the prepared index's |max| (one float)
 // spec_bound (optional): per-utterance upper bounds of |spec| (the slot of the input contraction); nullptr = one pass over spec measures it
-int run_encoder(tvc_ctx*, hipStream_t, Ws&, bool dry, const float* spec, float* ssl, float* f0,
+int run_encoder(tvc_ctx*, hipStream_t, Ws&, const float* spec, float* ssl, float* f0,
                 float* logits, int B, int T, const float* spec_bound = nullptr, float* zeroed_slots = nullptr,      // zeroed_slots: 3 x utterances floats already zeroed on this stream
                 float* f0_shifted = nullptr, float shift = 0.f);      // f0_shifted: also shift_frequency(f0, shift)
 int run_pitch_decode(tvc_ctx*, hipStream_t, const float* logits, float* f0, int B, int T);
-int run_knn(tvc_ctx*, hipStream_t, Ws&, bool dry, const float* src, const float* prepared, int64_t N,
+int run_knn(tvc_ctx*, hipStream_t, Ws&, const float* src, const float* prepared, int64_t N,
             float* out, int64_t* idx_out, int B, int T);
-int run_knn_topk(tvc_ctx*, hipStream_t, Ws&, bool dry, const float* src, const float* prepared, int64_t N,
+int run_knn_topk(tvc_ctx*, hipStream_t, Ws&, const float* src, const float* prepared, int64_t N,
                  float* sims_out, int64_t* idx_out, int B, int T);
 // match_features for any k <= 8 and metric (0 cos, 1 IP, 2 L2) on the RAW index [768][N] in plain fp32 (knn_general.hip)
-int run_knn_general(tvc_ctx*, hipStream_t, Ws&, bool dry, const float* src, const float* index, int64_t N, int k, int metric, float* out, int64_t* idx_out,
+int run_knn_general(tvc_ctx*, hipStream_t, Ws&, const float* src, const float* index, int64_t N, int k, int metric, float* out, int64_t* idx_out,
                     float* val_out, int B, int T);
 int run_knn_slots(tvc_ctx*, hipStream_t, const float* prepared, int64_t N, const int64_t* idx, float* slots, int64_t nslots);
 int run_knn_finish(tvc_ctx*, hipStream_t, const float* slots, float* out, int B, int T);
@@ -258,7 +293,7 @@ int run_shift(tvc_ctx*, hipStream_t, const float* f0, float* out, int64_t n, flo
 int run_uniform_to_angle(tvc_ctx*, hipStream_t, float* u, int64_t n);
 // content_bound (optional): ONE float, an upper bound of |content| (the prepared index's |max| when content came out of the kNN match);
 // energy_bound (optional): per-utterance upper bounds of |energy|.  nullptr = measured by a pass over the tensor.
-int run_decoder(tvc_ctx*, hipStream_t, Ws&, bool dry, const float* content, const float* f0,
+int run_decoder(tvc_ctx*, hipStream_t, Ws&, const float* content, const float* f0,
                 const float* energy, const float* angle, uint64_t seed, float* wave, float* amps_out,
                 float* kernel_out, float* source_out, int B, int T, const float* content_bound = nullptr, const float* energy_bound = nullptr);
 struct FilterTaps {   // optional copies of FilterNet's block outputs (tvc_filter_net_f32)
@@ -267,21 +302,20 @@ struct FilterTaps {   // optional copies of FilterNet's block outputs (tvc_filte
 };
 // cmax / smax / the trailing float* of run_dsp: per-utterance |max| slots of content / cat[source, energy] (block-floating-point
 // guard of the fp16 split, conv3s.h); nullptr = the stage computes (or keeps) its own
-int run_filter(tvc_ctx*, hipStream_t, Ws&, bool dry, const float* content, const float* f0, const float* energy,
+int run_filter(tvc_ctx*, hipStream_t, Ws&, const float* content, const float* f0, const float* energy,
                const float* source, float* wave, int B, int T, const FilterTaps* taps = nullptr, const float* cmax = nullptr, const float* smax = nullptr,
-               float* zeroed_slots = nullptr, bool x_slot_set = false, float* x_pre = nullptr, hipEvent_t x_ready = nullptr);      // zeroed_slots: kFilterSlots x utterances floats the caller has already zeroed on this
-                                                                             // stream; x_slot_set: ... and has set slot kFilterSlotX to flt_in_bw |content|max + flt_in_bb; x_pre / x_ready: the input contraction's output, already
-                                                                             // launched by the caller on another stream, and the event that says it is there (run_decoder's fork)
-// run_decoder's fork (decoder.hip): the harmonic oscillator on the context's side stream beside SourceNet's output GEMMs and the noise branch.
-// csum = the frame sums' buffer, already holding the scanned sums (launched on `side` by the caller); amps_ready = recorded on the launch stream
-// behind the amplitudes' GEMM; the caller joins `side` itself.
+               float* zeroed_slots = nullptr, bool x_slot_set = false, float* x_pre = nullptr, bool x_pre_filled = false);      // zeroed_slots: kFilterSlots x utterances floats the caller has already zeroed on this
+                                                                             // stream; x_slot_set: ... and has set slot kFilterSlotX to flt_in_bw |content|max + flt_in_bb; x_pre: the buffer of the input
+                                                                             // contraction's output; x_pre_filled: ... which already holds it, ordered in front of `s` (run_decoder's fork)
+// run_decoder's fork (decoder.hip): the harmonic synthesis on `side` beside SourceNet's to_kernel GEMM and the noise branch; csum's frame sums
+// are already scanned there, amps_ready is recorded on the launch stream behind the amplitudes' GEMM.  The caller joins `side` itself.
 struct DspFork {
     hipStream_t side;
-    double* csum;
     hipEvent_t amps_ready;
 };
-int run_dsp(tvc_ctx*, hipStream_t, Ws&, bool dry, const float* f0, const float* amps, const float* kern,
-            const float* angle, uint64_t seed, float* source, int B, int T, float* smax = nullptr, const DspFork* fk = nullptr);
+// csum: the oscillator's frame sums [B][15][T] (doubles); nullptr = run_dsp takes its own from ws
+int run_dsp(tvc_ctx*, hipStream_t, Ws&, const float* f0, const float* amps, const float* kern, const float* angle, uint64_t seed, float* source, int B, int T,
+            float* smax = nullptr, double* csum = nullptr, const DspFork* fk = nullptr);
 int run_sola(tvc_ctx*, hipStream_t, const float* y, float* sola_buf, const float* fade_in, float* out, int32_t* shift_out,
              int S, int64_t Ly, int block, int use_pv);
 int run_stream_push(tvc_ctx* ctx, hipStream_t s, float* buf, const float* blocks, int S, int n, int m);
@@ -311,6 +345,6 @@ int run_conv48_pair(tvc_ctx*, hipStream_t, const PackedW& wa, const PackedW& wb,
                     const float* amax_x, const float* amax_c, float* amax_y);
 
 // ConvNeXt-v2 layer on x [B, C, T] in place (convnext.py:49-58); tmp buffers from ws.
-int run_convnext(tvc_ctx*, hipStream_t, Ws&, bool dry, const ConvNeXtW& w, float* x, int B, int T, float* amax_out = nullptr);
+int run_convnext(tvc_ctx*, hipStream_t, Ws&, const ConvNeXtW& w, float* x, int B, int T, float* amax_out = nullptr);
 
 }  // namespace tvc
