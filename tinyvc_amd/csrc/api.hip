@@ -1,4 +1,4 @@
-// libtinyvc_hip.so — context, checkpoint packing, workspace sizing and the extern "C" surface.
+// libtinyvc_hip.so — context, workspace sizing and the extern "C" surface (checkpoint packing: pack.hip).
 #include <atomic>
 #include <cmath>
 #include <functional>
@@ -13,515 +13,6 @@ using namespace tvc;
 #ifndef TVC_SIDE_PRIO_EXPR
 #define TVC_SIDE_PRIO_EXPR prio_least
 #endif
-namespace {
-
-struct ArenaBuilder {
-    std::vector<float> buf;
-    size_t put(const std::vector<float>& v) {
-        size_t off = (buf.size() + 63) & ~size_t(63);  // 256-byte aligned
-        buf.resize(off + v.size(), 0.f);
-        std::copy(v.begin(), v.end(), buf.begin() + off);
-        return off;
-    }
-};
-
-// Offsets are resolved to device pointers after the single upload.
-struct Fixup {
-    const float** slot;
-    size_t off;
-};
-
-int pad_m(int M) {
-    if (M <= 32) return 32;
-    if (M <= 64) return 64;
-    if (M <= 96) return 96;
-    if (M % 96 == 0 && M % 128 != 0) return M;
-    return (M + 127) / 128 * 128;
-}
-
-struct Packer {
-    tvc_ctx* ctx;
-    ArenaBuilder ab;
-    std::vector<Fixup> fix;
-    std::string missing;
-
-    const HostTensor* find(const std::string& key) {
-        auto it = ctx->host.find(key);
-        if (it == ctx->host.end()) {
-            if (missing.empty()) missing = key;
-            return nullptr;
-        }
-        return &it->second;
-    }
-    void raw(const std::string& key, const float** slot, size_t expect) {
-        const HostTensor* t = find(key);
-        if (!t) return;
-        if (t->data.size() != expect) {
-            if (missing.empty()) missing = key + " (wrong size)";
-            return;
-        }
-        fix.push_back({slot, ab.put(t->data)});
-    }
-    // ---- two-part fp16 split of the packed weights (conv3s.h): w = (h1 + 2^-11 h2) * 2^e, e per 32-row m-tile -------------------
-    static uint16_t f16_bits(float f) {
-        const _Float16 h = (_Float16)f;          // round to nearest even, subnormals kept
-        uint16_t u;
-        std::memcpy(&u, &h, 2);
-        return u;
-    }
-    static float f16_value(uint16_t u) {
-        _Float16 h;
-        std::memcpy(&h, &u, 2);
-        return (float)h;
-    }
-    // the two parts of w / scale (scale = a power of two: the division is exact)
-    static void split2(float w, float scale, uint16_t* h1, uint16_t* h2) {
-        const float x = w / scale;
-        *h1 = f16_bits(x);
-        *h2 = f16_bits((x - f16_value(*h1)) * 2048.f);
-    }
-    // power of two that brings `amax` into [1, 2) (1 for an all-zero tile)
-    static float pow2_scale(float amax) {
-        if (!(amax > 0.f) || !std::isfinite(amax)) return 1.f;
-        int e;
-        std::frexp(amax, &e);                    // amax = m * 2^e, m in [0.5, 1)
-        return std::ldexp(1.f, e - 1);
-    }
-    std::map<const PackedW*, std::vector<float>> host_wscale;      // the scales chosen for every packed image (joint packing, fused-block blobs)
-
-    // Stack one or more conv weights [cout_i][cin][taps] along cout into the host staging layout At[k][m], k = ci*taps + tap
-    // (zero-padded to Kpad x Mpad) and the bias row [Mpad].
-    bool stage(const std::vector<std::string>& names, PackedW* pw, int cin, int taps, std::vector<float>* At, std::vector<float>* bias, int* group_rows) {
-        int M = 0;
-        std::vector<const HostTensor*> ws, bs;
-        for (auto& n : names) {
-            const HostTensor* w = find(n + ".weight");
-            const HostTensor* b = find(n + ".bias");
-            if (!w || !b) return false;
-            if (w->shape.size() != 3 || w->shape[1] != cin || w->shape[2] != taps ||
-                (int64_t)b->data.size() != w->shape[0]) {
-                if (missing.empty()) missing = n + " (unexpected shape)";
-                return false;
-            }
-            ws.push_back(w);
-            bs.push_back(b);
-            M += (int)w->shape[0];
-        }
-        pw->M = M;
-        pw->K = cin * taps;
-        pw->cin = cin;
-        pw->taps = taps;
-        pw->Mpad = pad_m(M);
-        pw->Kpad = (pw->K + 15) / 16 * 16;
-        At->assign((size_t)pw->Kpad * pw->Mpad, 0.f);
-        bias->assign(pw->Mpad, 0.f);
-        int m0 = 0;
-        for (size_t i = 0; i < ws.size(); ++i) {
-            int cout = (int)ws[i]->shape[0];
-            for (int m = 0; m < cout; ++m) {
-                (*bias)[m0 + m] = bs[i]->data[m];
-                for (int k = 0; k < pw->K; ++k) (*At)[(size_t)k * pw->Mpad + m0 + m] = ws[i]->data[(size_t)m * pw->K + k];
-            }
-            m0 += cout;
-        }
-        bool equal_groups = ws.size() > 1;
-        for (auto* w : ws) equal_groups = equal_groups && w->shape[0] == ws[0]->shape[0];
-        *group_rows = equal_groups ? (int)ws[0]->shape[0] : 0;
-        return true;
-    }
-    // image geometry: group_rows > 0 = the M rows are `M / group_rows` stacked groups (FiLM scale ; shift), each padded to whole 32-row tiles
-    static int image_mt(const PackedW* pw, int group_rows) {
-        const int gp = group_rows > 0 ? (group_rows + 31) / 32 * 32 : 0;
-        return group_rows > 0 ? (pw->M / group_rows) * gp / 32 : pw->Mpad / 32;
-    }
-    static int image_row(const PackedW* pw, int group_rows, int m) {      // staged row of image row m (pw->M = a padding row)
-        if (group_rows <= 0) return m < pw->M ? m : pw->M;
-        const int gp = (group_rows + 31) / 32 * 32, g = m / gp, mi = m - g * gp;
-        return mi < group_rows ? g * group_rows + mi : pw->M;
-    }
-    std::vector<float> mt_amax(const PackedW* pw, const std::vector<float>& At, int group_rows) {
-        const int MT = image_mt(pw, group_rows);
-        std::vector<float> amax(MT, 0.f);
-        for (int mt = 0; mt < MT; ++mt)
-            for (int r = 0; r < 32; ++r) {
-                const int m = image_row(pw, group_rows, mt * 32 + r);
-                if (m >= pw->M) continue;
-                for (int k = 0; k < pw->K; ++k) amax[mt] = std::max(amax[mt], std::fabs(At[(size_t)k * pw->Mpad + m]));
-            }
-        return amax;
-    }
-    void conv(const std::vector<std::string>& names, PackedW* pw, int cin, int taps) {
-        std::vector<float> At, bias;
-        int group_rows = 0;
-        if (!stage(names, pw, cin, taps, &At, &bias, &group_rows)) return;
-        // only the split image goes to the device: `At` is the host-side staging layout it is built from
-        fix.push_back({&pw->bias, ab.put(bias)});
-        std::vector<float> sc = mt_amax(pw, At, group_rows);
-        for (auto& v : sc) v = pow2_scale(v);
-        a6(pw, At, group_rows, sc);
-    }
-    // two convs whose results are accumulated into ONE tile (Downsample: c3(h2) + down_res(xi)): the same per-m-tile scales for both
-    void conv_joint(const std::string& na, PackedW* pa, int cin_a, int taps_a, const std::string& nb, PackedW* pb, int cin_b, int taps_b) {
-        std::vector<float> Aa, ba, Ab, bb;
-        int ga = 0, gb = 0;
-        if (!stage({na}, pa, cin_a, taps_a, &Aa, &ba, &ga) || !stage({nb}, pb, cin_b, taps_b, &Ab, &bb, &gb)) return;
-        if (pa->Mpad != pb->Mpad) {
-            if (missing.empty()) missing = na + " / " + nb + " (row counts differ)";
-            return;
-        }
-        fix.push_back({&pa->bias, ab.put(ba)});
-        fix.push_back({&pb->bias, ab.put(bb)});
-        std::vector<float> sa = mt_amax(pa, Aa, 0), sb = mt_amax(pb, Ab, 0);
-        for (size_t i = 0; i < sa.size(); ++i) sa[i] = pow2_scale(std::max(sa[i], sb[i]));
-        const size_t off_a = a6(pa, Aa, 0, sa);
-        a6(pb, Ab, 0, sa);
-        fix.push_back({&pb->wjoint, off_a});      // resolves to pa->A6: the launch checks that the pair was packed together
-    }
-    // two-part fp16 image of At for conv3s.h: [step = slab*taps + tap][m-tile][part][lane][8 fp16],
-    // lane -> row m = 32*mt + (lane & 31), channel ci = 16*slab + 8*(lane >> 5) + j.  Returns the image's arena offset.
-    size_t a6(PackedW* pw, const std::vector<float>& At, int group_rows, const std::vector<float>& scale) {
-        const int taps = pw->taps, cin = pw->cin, nslab = ((cin + 15) / 16 + 5) / 6 * 6;   // zero slabs up to a multiple of 6: any slab depth divides
-        const int MT = image_mt(pw, group_rows);
-        std::vector<float> img((size_t)nslab * taps * MT * 2 * 256, 0.f);
-        uint16_t* o = reinterpret_cast<uint16_t*>(img.data());
-        for (int s = 0; s < nslab; ++s)
-            for (int tap = 0; tap < taps; ++tap)
-                for (int mt = 0; mt < MT; ++mt)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 8; ++j) {
-                            const int ci = s * 16 + 8 * (lane >> 5) + j, m = image_row(pw, group_rows, mt * 32 + (lane & 31));
-                            const float w = (ci < cin && m < pw->M) ? At[(size_t)(ci * taps + tap) * pw->Mpad + m] : 0.f;
-                            const size_t base = (((size_t)(s * taps + tap) * MT + mt) * 2 * 64 + lane) * 8 + j;
-                            split2(w, scale[mt], &o[base], &o[base + 512]);
-                        }
-        pw->MT6 = MT;
-        pw->S6 = nslab;
-        const size_t off = ab.put(img);
-        fix.push_back({&pw->A6, off});
-        fix.push_back({&pw->wscale, ab.put(scale)});
-        host_wscale[pw] = scale;
-        return off;
-    }
-    // conv (k3) + FiLM (two 1x1s) of one Upsample half for film_s2.h.  Image: [96-row block][16-channel slab][30 pieces][lane][8 fp16],
-    // piece q < 18: conv tap q / 6, m-tile (q % 6) / 2 of the block, part q % 2; q >= 18: to_scale (q < 24) / to_shift, m-tile, part.
-    // Lane order as in a6 (row = lane & 31, channel = 16 slab + 8 (lane >> 5) + j).  This kernel adds all three part products into ONE
-    // accumulator, so the second part is the UNSCALED fp16 residual and every m-tile is normalised to |max| in [2^13, 2^14): the
-    // residual's absolute fp16 resolution (2^-24, subnormals kept) is then 2^-37 of the tile's largest weight.
-    void film_u(FilmU* fu, const std::string& conv_name, const std::string& film, int C, const std::string& first_conv) {
-        const HostTensor* w = find(conv_name + ".weight");
-        const HostTensor* b = find(conv_name + ".bias");
-        const HostTensor* wsc = find(film + ".to_scale.weight");
-        const HostTensor* bsc = find(film + ".to_scale.bias");
-        const HostTensor* wsh = find(film + ".to_shift.weight");
-        const HostTensor* bsh = find(film + ".to_shift.bias");
-        if (!w || !b || !wsc || !bsc || !wsh || !bsh) return;
-        if (C % 96 != 0 || w->data.size() != (size_t)C * C * 3 || wsc->data.size() != (size_t)C * C || wsh->data.size() != (size_t)C * C ||
-            b->data.size() != (size_t)C || bsc->data.size() != (size_t)C || bsh->data.size() != (size_t)C) {
-            if (missing.empty()) missing = conv_name + " / " + film + " (unexpected shape)";
-            return;
-        }
-        const int MT = C / 32, nslab = C / 16, mblocks = C / 96;
-        auto tile_scale = [&](const std::vector<float>& wt, int per_row, int mt) {
-            float amax = 0.f;
-            for (int r = 0; r < 32; ++r)
-                for (int k = 0; k < per_row; ++k) amax = std::max(amax, std::fabs(wt[(size_t)(mt * 32 + r) * per_row + k]));
-            return pow2_scale(amax) * (1.f / 8192.f);
-        };
-        std::vector<float> tab((size_t)6 * C);
-        std::vector<float> s_conv(MT), s_sc(MT), s_sh(MT);
-        for (int mt = 0; mt < MT; ++mt) {
-            s_conv[mt] = tile_scale(w->data, 3 * C, mt);
-            s_sc[mt] = tile_scale(wsc->data, C, mt);
-            s_sh[mt] = tile_scale(wsh->data, C, mt);
-        }
-        for (int m = 0; m < C; ++m) {
-            tab[m] = b->data[m];
-            tab[(size_t)C + m] = s_conv[m / 32];
-            tab[(size_t)2 * C + m] = bsc->data[m];
-            tab[(size_t)3 * C + m] = bsh->data[m];
-            tab[(size_t)4 * C + m] = s_sc[m / 32];
-            tab[(size_t)5 * C + m] = s_sh[m / 32];
-        }
-        std::vector<float> img((size_t)mblocks * nslab * 30 * 64 * 4, 0.f);
-        uint16_t* o = reinterpret_cast<uint16_t*>(img.data());
-        for (int mb = 0; mb < mblocks; ++mb)
-            for (int s = 0; s < nslab; ++s)
-                for (int q = 0; q < 30; ++q) {
-                    const bool conv = q < 18;
-                    const int qq = conv ? q : q - 18, grp = qq / 6, mi = (qq % 6) / 2, part = qq % 2, mt = mb * 3 + mi;
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 8; ++j) {
-                            const int m = mt * 32 + (lane & 31), ci = s * 16 + 8 * (lane >> 5) + j;
-                            float x;
-                            if (conv) x = w->data[((size_t)m * C + ci) * 3 + grp] / s_conv[mt];
-                            else if (grp == 0) x = wsc->data[(size_t)m * C + ci] / s_sc[mt];
-                            else x = wsh->data[(size_t)m * C + ci] / s_sh[mt];
-                            const uint16_t h1 = f16_bits(x);
-                            o[((((size_t)mb * nslab + s) * 30 + q) * 64 + lane) * 8 + j] = part == 0 ? h1 : f16_bits(x - f16_value(h1));
-                        }
-                }
-        // the bound the half's first conv normalises its pre-split output by (conv_s2.h PRE): max_m sum_{k, tap} |w[m][k][tap]| and max |b|, a
-        // hair above in float so that rounding cannot undercut them
-        if (const HostTensor* w1 = find(first_conv + ".weight")) {
-            const HostTensor* b1 = find(first_conv + ".bias");
-            if (b1 && w1->data.size() == (size_t)C * C * 3 && b1->data.size() == (size_t)C) {
-                double wl1 = 0.0, bm = 0.0;
-                for (int m = 0; m < C; ++m) {
-                    double sum = 0.0;
-                    for (int k = 0; k < 3 * C; ++k) sum += std::fabs((double)w1->data[(size_t)m * 3 * C + k]);
-                    wl1 = std::max(wl1, sum);
-                    bm = std::max(bm, std::fabs((double)b1->data[m]));
-                }
-                fu->hb_w = (float)(wl1 * 1.0001);
-                fu->hb_b = (float)(bm * 1.0001);
-            }
-        }
-        fu->C = C;
-        fix.push_back({&fu->img, ab.put(img)});
-        fix.push_back({&fu->tab, ab.put(tab)});
-    }
-    // Weight blob of one half of the fused ups.4 kernel (filter_up24s.hip): 28 pieces of 1 KiB in
-    // v_mfma_f32_32x32x16_f16 A-lane order (row m = lane & 31, k = 8 * (lane >> 5) + j), two fp16 parts each:
-    //   [conv a: 5 steps][2 parts] [conv b: 5 steps][2 parts] [FiLM: 2 steps][to_scale, to_shift][2 parts]
-    // followed by 304 floats: biases a, b, scale, shift (32 each), the folded output taps [24][7] and their bias [296], then
-    // [297..300] the power-of-two scales of conv a, conv b, to_scale, to_shift, [301] max_m sum_k |w_a[m][k]| and [302] max |b_a|
-    // (the bound of the block's on-chip intermediate, see the kernel).
-    // K runs in units of (tap, 8-channel group): unit u = 2 * step + (lane >> 5), tap = u / 3, group = u % 3 (a 24-channel
-    // conv has 9 units, the 10th is zero; FiLM's 1x1 has 3).
-    // Second half: Upsample.c5 (1x1, decoder.py:171,189) and FilterNet.output_layer (k7, decoder.py:220,233) have nothing
-    // between them, so they are one k7 conv 24 -> 1: w75[c][j] = sum_m w7[m][j] w5[m][c], b75 = b7 + sum_{m,j} w7[m][j] b5[m]
-    // (replicate padding commutes with the 1x1), accumulated in double.
-    void up24s_half(const float** slot, const std::string& ca, const std::string& cb, const std::string& film, const std::string& c5,
-                    const std::string& out7) {
-        const HostTensor* wa = find(ca + ".weight");
-        const HostTensor* ba = find(ca + ".bias");
-        const HostTensor* wb = find(cb + ".weight");
-        const HostTensor* bb = find(cb + ".bias");
-        const HostTensor* wsc = find(film + ".to_scale.weight");
-        const HostTensor* bsc = find(film + ".to_scale.bias");
-        const HostTensor* wsh = find(film + ".to_shift.weight");
-        const HostTensor* bsh = find(film + ".to_shift.bias");
-        if (!wa || !ba || !wb || !bb || !wsc || !bsc || !wsh || !bsh) return;
-        const int C = 24;
-        if (wa->data.size() != (size_t)C * C * 3 || wb->data.size() != (size_t)C * C * 3 || wsc->data.size() != (size_t)C * C ||
-            wsh->data.size() != (size_t)C * C) {
-            if (missing.empty()) missing = ca + " (unexpected shape for the 24-channel block)";
-            return;
-        }
-        std::vector<float> img(28 * 256 + 304, 0.f);
-        uint16_t* o = reinterpret_cast<uint16_t*>(img.data());
-        auto amax_of = [](const HostTensor* t) {
-            float a = 0.f;
-            for (float v : t->data) a = std::max(a, std::fabs(v));
-            return a;
-        };
-        const float sa = pow2_scale(amax_of(wa)), sb = pow2_scale(amax_of(wb)), ssc = pow2_scale(amax_of(wsc)), ssh = pow2_scale(amax_of(wsh));
-        auto put2 = [&](int piece0, int lane, int j, float w, float scale) {   // parts of one value into pieces piece0, +1
-            const size_t base = ((size_t)piece0 * 64 + lane) * 8 + j;
-            split2(w, scale, &o[base], &o[base + 512]);
-        };
-        for (int lane = 0; lane < 64; ++lane)
-            for (int j = 0; j < 8; ++j) {
-                const int m = lane & 31, lh = lane >> 5;
-                for (int s = 0; s < 5; ++s) {
-                    const int u = 2 * s + lh, tap = u / 3, ci = 8 * (u % 3) + j;
-                    const bool real = u < 9 && m < C;
-                    put2(s * 2, lane, j, real ? wa->data[((size_t)m * C + ci) * 3 + tap] : 0.f, sa);
-                    put2(10 + s * 2, lane, j, real ? wb->data[((size_t)m * C + ci) * 3 + tap] : 0.f, sb);
-                }
-                for (int s = 0; s < 2; ++s) {
-                    const int u = 2 * s + lh, ci = 8 * u + j;
-                    const bool real = u < 3 && m < C;
-                    put2(20 + (s * 2 + 0) * 2, lane, j, real ? wsc->data[(size_t)m * C + ci] : 0.f, ssc);
-                    put2(20 + (s * 2 + 1) * 2, lane, j, real ? wsh->data[(size_t)m * C + ci] : 0.f, ssh);
-                }
-            }
-        float* fl = img.data() + 28 * 256;
-        double l1max = 0.0;
-        float bamax = 0.f;
-        for (int m = 0; m < C; ++m) {
-            fl[m] = ba->data[m];
-            fl[32 + m] = bb->data[m];
-            fl[64 + m] = bsc->data[m];
-            fl[96 + m] = bsh->data[m];
-            double l1 = 0.0;
-            for (int k = 0; k < C * 3; ++k) l1 += std::fabs((double)wa->data[(size_t)m * C * 3 + k]);
-            l1max = std::max(l1max, l1);
-            bamax = std::max(bamax, std::fabs(ba->data[m]));
-        }
-        fl[297] = sa;
-        fl[298] = sb;
-        fl[299] = ssc;
-        fl[300] = ssh;
-        fl[301] = (float)(l1max * 1.0000002);      // rounded up: it is a bound
-        fl[302] = bamax;
-        if (!c5.empty()) {
-            const HostTensor* w5 = find(c5 + ".weight");
-            const HostTensor* b5 = find(c5 + ".bias");
-            const HostTensor* w7 = find(out7 + ".weight");
-            const HostTensor* b7 = find(out7 + ".bias");
-            if (!w5 || !b5 || !w7 || !b7) return;
-            if (w5->data.size() != (size_t)C * C || w7->data.size() != (size_t)C * 7 || b7->data.size() != 1) {
-                if (missing.empty()) missing = c5 + " (unexpected shape for the folded output conv)";
-                return;
-            }
-            double bias = b7->data[0];
-            for (int c = 0; c < C; ++c)
-                for (int j = 0; j < 7; ++j) {
-                    double acc = 0.0;
-                    for (int m = 0; m < C; ++m) acc += (double)w7->data[(size_t)m * 7 + j] * (double)w5->data[(size_t)m * C + c];
-                    fl[128 + c * 7 + j] = (float)acc;
-                }
-            for (int m = 0; m < C; ++m)
-                for (int j = 0; j < 7; ++j) bias += (double)w7->data[(size_t)m * 7 + j] * (double)b5->data[m];
-            fl[128 + 168] = (float)bias;
-        }
-        fix.push_back({slot, ab.put(img)});
-    }
-    // Weight blob of the downs.0 kernel (filter_up24s.hip): the 17 -> 24 k3 conv in the same 10-piece layout
-    // as a 24-channel conv (input rows 17..23 zero), then 32 floats: bias [24], [31] = the image's power-of-two scale.
-    void down0s(const float** slot, const std::string& name, float* bound_w, float* bound_b) {
-        const HostTensor* w = find(name + ".weight");
-        const HostTensor* b = find(name + ".bias");
-        if (!w || !b) return;
-        const int C = 24, CI = 17;
-        if (w->data.size() != (size_t)C * CI * 3 || b->data.size() != (size_t)C) {
-            if (missing.empty()) missing = name + " (unexpected shape for the split-precision downs.0 blob)";
-            return;
-        }
-        std::vector<float> img(10 * 256 + 32, 0.f);
-        uint16_t* o = reinterpret_cast<uint16_t*>(img.data());
-        float amax = 0.f;
-        for (float v : w->data) amax = std::max(amax, std::fabs(v));
-        const float sc = pow2_scale(amax);
-        for (int lane = 0; lane < 64; ++lane)
-            for (int j = 0; j < 8; ++j)
-                for (int s = 0; s < 5; ++s) {
-                    const int m = lane & 31, u = 2 * s + (lane >> 5), tap = u / 3, ci = 8 * (u % 3) + j;
-                    const float v = (u < 9 && m < C && ci < CI) ? w->data[((size_t)m * CI + ci) * 3 + tap] : 0.f;
-                    const size_t base = ((size_t)(s * 2) * 64 + lane) * 8 + j;
-                    split2(v, sc, &o[base], &o[base + 512]);
-                }
-        double l1max = 0.0;
-        float bmax = 0.f;
-        for (int m = 0; m < C; ++m) {
-            img[10 * 256 + m] = b->data[m];
-            double l1 = 0.0;
-            for (int k = 0; k < CI * 3; ++k) l1 += std::fabs((double)w->data[(size_t)m * CI * 3 + k]);
-            l1max = std::max(l1max, l1);
-            bmax = std::max(bmax, std::fabs(b->data[m]));
-        }
-        // |out| <= l1max |x|max + bmax (rounded up a little: the bound must hold for the fp32-rounded sums too): the scale of the pre-split planes
-        img[10 * 256 + 29] = *bound_w = (float)(l1max * 1.0001);
-        img[10 * 256 + 30] = *bound_b = bmax * 1.0001f;
-        img[10 * 256 + 31] = sc;
-        fix.push_back({slot, ab.put(img)});
-    }
-    // Weight blob of one 24-input-channel k3 conv for down24f_kernel (filter_up24s.hip): pieces [step][m-tile][part]
-    // (same (tap, group) K order as up24s_half), then 64 floats: bias [M <= 48], [62], [63] = the power-of-two scales of the (at
-    // most two) m-tiles.  M = 24 (one m-tile) or 48 (two).  `joint`: take the scales of this already packed image instead of the
-    // weight's own (c3 of the 24-channel Downsample block is accumulated with down_res into one tile: conv_joint).
-    void conv24s(const float** slot, const std::string& name, int M, const std::string& extra_bias = "", const PackedW* joint = nullptr) {
-        const HostTensor* w = find(name + ".weight");
-        const HostTensor* b = find(name + ".bias");
-        const HostTensor* eb = extra_bias.empty() ? nullptr : find(extra_bias);
-        if (!extra_bias.empty() && (!eb || eb->data.size() != (size_t)M)) {
-            if (missing.empty()) missing = extra_bias + " (wrong size)";
-            return;
-        }
-        if (!w || !b) return;
-        const int CI = 24, MT = (M + 31) / 32;
-        if (w->data.size() != (size_t)M * CI * 3 || b->data.size() != (size_t)M) {
-            if (missing.empty()) missing = name + " (unexpected shape for the 24-channel split-precision blob)";
-            return;
-        }
-        std::vector<float> img((size_t)10 * MT * 256 + 64, 0.f);
-        uint16_t* o = reinterpret_cast<uint16_t*>(img.data());
-        std::vector<float> sc(MT, 1.f);
-        if (joint) {
-            auto it = host_wscale.find(joint);
-            if (it == host_wscale.end() || (int)it->second.size() != MT) {
-                if (missing.empty()) missing = name + " (its joint image is not packed yet)";
-                return;
-            }
-            sc = it->second;
-        } else {
-            for (int mt = 0; mt < MT; ++mt) {
-                float amax = 0.f;
-                for (int m = 32 * mt; m < std::min(M, 32 * mt + 32); ++m)
-                    for (int k = 0; k < CI * 3; ++k) amax = std::max(amax, std::fabs(w->data[(size_t)m * CI * 3 + k]));
-                sc[mt] = pow2_scale(amax);
-            }
-        }
-        for (int lane = 0; lane < 64; ++lane)
-            for (int j = 0; j < 8; ++j)
-                for (int s = 0; s < 5; ++s)
-                    for (int mt = 0; mt < MT; ++mt) {
-                        const int m = 32 * mt + (lane & 31), u = 2 * s + (lane >> 5), tap = u / 3, ci = 8 * (u % 3) + j;
-                        const float v = (u < 9 && m < M) ? w->data[((size_t)m * CI + ci) * 3 + tap] : 0.f;
-                        const size_t base = ((size_t)((s * MT + mt) * 2) * 64 + lane) * 8 + j;
-                        split2(v, sc[mt], &o[base], &o[base + 512]);
-                    }
-        for (int m = 0; m < M; ++m) img[(size_t)10 * MT * 256 + m] = b->data[m] + (eb ? eb->data[m] : 0.f);
-        for (int mt = 0; mt < MT; ++mt) img[(size_t)10 * MT * 256 + 62 + mt] = sc[mt];
-        fix.push_back({slot, ab.put(img)});
-    }
-    void convnext(const std::string& p, ConvNeXtW* w, int C, int dil) {
-        w->C = C;
-        w->dilation = dil;
-        raw(p + ".c1.weight", &w->dw_w, (size_t)C * 7);
-        raw(p + ".c1.bias", &w->dw_b, C);
-        raw(p + ".norm.gamma", &w->ln_g, C);
-        raw(p + ".norm.beta", &w->ln_b, C);
-        {   // |LayerNorm output| <= sqrt(C - 1) max|gamma| + max|beta| whatever the data (a normalised column has |x_hat| <= sqrt(C - 1))
-            const HostTensor* g = find(p + ".norm.gamma");
-            const HostTensor* bt = find(p + ".norm.beta");
-            float gm = 0.f, bm = 0.f;
-            if (g) for (float v : g->data) gm = std::max(gm, std::fabs(v));
-            if (bt) for (float v : bt->data) bm = std::max(bm, std::fabs(v));
-            w->ln_bound = std::sqrt((float)C) * gm + bm;
-        }
-        conv({p + ".c2"}, &w->c2, C, 1);
-        raw(p + ".grn.gamma", &w->grn_g, 2 * C);
-        raw(p + ".grn.beta", &w->grn_b, 2 * C);
-        conv({p + ".c3"}, &w->c3, 2 * C, 1);
-        const HostTensor* w3 = find(p + ".c3.weight");
-        const HostTensor* b3 = find(p + ".c3.bias");
-        const HostTensor* gb = find(p + ".grn.beta");
-        if (w3 && b3 && gb && gb->data.size() == (size_t)2 * C && w3->data.size() == (size_t)C * 2 * C) {
-            std::vector<float> fb(w->c3.Mpad, 0.f);
-            for (int m = 0; m < C; ++m) {
-                double acc = b3->data[m];
-                for (int k = 0; k < 2 * C; ++k) acc += (double)w3->data[(size_t)m * 2 * C + k] * (double)gb->data[k];
-                fb[m] = (float)acc;
-            }
-            fix.push_back({&w->c3_bias_grn, ab.put(fb)});
-        }
-    }
-};
-
-// Tables of the wave-level 1920-point FFTs (fft.hip), computed in fp64: (cos, sin)(2 pi j / 960), (cos, sin)(2 pi k / 1920),
-// periodic Hann window.
-void build_fft_tables(Packer& pk, tvc_ctx* ctx) {
-    const int N = kNfft;
-    const double two_pi = 6.283185307179586476925286766559;
-    std::vector<float> t960(2 * 960), t1920(2 * 961 + 2), hann(N);
-    for (int j = 0; j < 960; ++j) {
-        t960[2 * j] = (float)std::cos(two_pi * j / 960.0);
-        t960[2 * j + 1] = (float)std::sin(two_pi * j / 960.0);
-    }
-    for (int k = 0; k <= 960; ++k) {
-        t1920[2 * k] = (float)std::cos(two_pi * k / 1920.0);
-        t1920[2 * k + 1] = (float)std::sin(two_pi * k / 1920.0);
-    }
-    for (int n = 0; n < N; ++n) hann[n] = (float)(0.5 - 0.5 * std::cos(two_pi * n / N));
-    pk.fix.push_back({&ctx->fft_tw960, pk.ab.put(t960)});
-    pk.fix.push_back({&ctx->fft_tw1920, pk.ab.put(t1920)});
-    pk.fix.push_back({&ctx->fft_hann, pk.ab.put(hann)});
-    pk.fix.push_back({&ctx->sola_part, pk.ab.put(std::vector<float>(tvc::kSolaPartFloats, 0.f))});   // device scratch, not a table (sola.hip)
-}
-
-}  // namespace
 
 // Prepared kNN blobs of this process: device pointer -> N it was prepared for.  The kernels take the blob's geometry (offsets of the
 // inverse norms and the fp16 image) from the caller's N, so a call whose N differs from the one the blob was prepared with would read
@@ -591,16 +82,16 @@ int tvc_ctx_create(int hip_device, tvc_ctx** out) {
     tvc_ctx* c = new tvc_ctx();
     c->device = hip_device;
     {   // constant tables (FFT twiddles, Hann window): independent of any checkpoint
-        Packer pk{c};
-        build_fft_tables(pk, c);
+        ArenaBuilder ab;
+        pack_constants(c, &ab);
         if (hipSetDevice(hip_device) != hipSuccess ||
-            hipMalloc((void**)&c->const_arena, pk.ab.buf.size() * sizeof(float)) != hipSuccess ||
-            hipMemcpy(c->const_arena, pk.ab.buf.data(), pk.ab.buf.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+            hipMalloc((void**)&c->const_arena, ab.buf.size() * sizeof(float)) != hipSuccess ||
+            hipMemcpy(c->const_arena, ab.buf.data(), ab.buf.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
             if (c->const_arena) (void)hipFree(c->const_arena);
             delete c;
             return TVC_ERR_HIP;
         }
-        for (auto& f : pk.fix) *f.slot = c->const_arena + f.off;
+        ab.resolve(c->const_arena);
     }
     // the side stream carries the pitch estimator beside the SSL trunk (encoder.hip): lowest priority, so that its workgroups take the
     // slots the trunk's launches leave free instead of competing with them (the pitch chain has ~150 us of slack)
@@ -666,139 +157,9 @@ int tvc_set_pitch_table(tvc_ctx* ctx, const float* host_freqs, int n) {
 int tvc_finalize_weights(tvc_ctx* ctx) {
     if (!ctx) return TVC_ERR_ARG;
     ctx->enc_ready = ctx->dec_ready = false;
-    Packer pk{ctx};
-    if (ctx->pitch_table.size() == (size_t)kPitchClasses)
-        pk.fix.push_back({&ctx->pitch_freq, pk.ab.put(ctx->pitch_table)});
-    else
-        pk.missing = "pitch table (tvc_set_pitch_table)";
-
-    // encoder (encoder.py:75-116): both estimators read the same spectrogram -> stacked input 1x1
-    pk.conv({"ssl_feature_estimator.input_layer", "pitch_estimator.input_layer"}, &ctx->enc_in, kBins, 1);
-    pk.raw("ssl_feature_estimator.norm.gamma", &ctx->ssl_ln_g, kSslCh);
-    pk.raw("ssl_feature_estimator.norm.beta", &ctx->ssl_ln_b, kSslCh);
-    pk.raw("pitch_estimator.norm.gamma", &ctx->pit_ln_g, kPitchCh);
-    pk.raw("pitch_estimator.norm.beta", &ctx->pit_ln_b, kPitchCh);
-    static const int ssl_dil[6] = {1, 3, 9, 1, 1, 1};
-    for (int i = 0; i < 6; ++i)
-        pk.convnext("ssl_feature_estimator.mid_layers." + std::to_string(i), &ctx->ssl_mid[i], kSslCh, ssl_dil[i]);
-    for (int i = 0; i < 4; ++i)
-        pk.convnext("pitch_estimator.mid_layers." + std::to_string(i), &ctx->pit_mid[i], kPitchCh, 1);
-    pk.conv({"ssl_feature_estimator.output_layer"}, &ctx->ssl_out, kSslCh, 1);
-    pk.conv({"pitch_estimator.output_layer"}, &ctx->pit_out, kPitchCh, 1);
-    const std::string missing_enc = pk.missing;
-    pk.missing.clear();
-
-    // source net (decoder.py:102-134)
-    pk.conv({"source_net.content_in"}, &ctx->src_content_in, kSslDim, 1);
-    pk.raw("source_net.energy_in.weight", &ctx->src_e_w, kSrcCh);
-    pk.raw("source_net.energy_in.bias", &ctx->src_e_b, kSrcCh);
-    pk.raw("source_net.f0_in.weight", &ctx->src_f_w, kSrcCh);
-    pk.raw("source_net.f0_in.bias", &ctx->src_f_b, kSrcCh);
-    for (int i = 0; i < 3; ++i)
-        pk.convnext("source_net.mid_layers." + std::to_string(i), &ctx->src_mid[i], kSrcCh, 1);
-    pk.conv({"source_net.to_amps"}, &ctx->src_to_amps, kSrcCh, 1);
-    pk.conv({"source_net.to_kernel"}, &ctx->src_to_kernel, kSrcCh, 1);
-
-    // filter net (decoder.py:193-233)
-    static const int ch[5] = {384, 192, 96, 48, 24};
-    static const int fac[5] = {2, 3, 4, 4, 5};
-    pk.conv({"filter_net.content_in"}, &ctx->flt_content_in, kSslDim, 1);
-    pk.raw("filter_net.f0_in.weight", &ctx->flt_f_w, ch[0]);
-    pk.raw("filter_net.f0_in.bias", &ctx->flt_f_b, ch[0]);
-    // analytic |max| bounds of 1x1 outputs (a hair above max_m sum_k |w_mk| and max |b|): the slot of a tensor an epilogue functor finishes
-    // comes from its input's slot instead of a pass over the tensor
-    auto bound_1x1 = [&](const std::string& name, int cout, int cin, float* bw, float* bb) {
-        const HostTensor* w = pk.find(name + ".weight");
-        const HostTensor* b = pk.find(name + ".bias");
-        if (!w || !b || w->data.size() != (size_t)cout * cin || b->data.size() != (size_t)cout) return;
-        double wl1 = 0.0, bm = 0.0;
-        for (int m = 0; m < cout; ++m) {
-            double sum = 0.0;
-            for (int k = 0; k < cin; ++k) sum += std::fabs((double)w->data[(size_t)m * cin + k]);
-            wl1 = std::max(wl1, sum);
-            bm = std::max(bm, std::fabs((double)b->data[m]));
-        }
-        *bw = (float)(wl1 * 1.0001);
-        *bb = (float)(bm * 1.0001);
-    };
-    {
-        bound_1x1("filter_net.content_in", ch[0], kSslDim, &ctx->flt_in_bw, &ctx->flt_in_bb);
-        const HostTensor* fw = pk.find("filter_net.f0_in.weight");
-        const HostTensor* fb = pk.find("filter_net.f0_in.bias");
-        if (fw && fb) {      // + f0_in(log(relu(f0) + 1e-6)): |log| < 89 for every finite fp32 f0
-            double wm = 0.0, bm = 0.0;
-            for (float v : fw->data) wm = std::max(wm, std::fabs((double)v));
-            for (float v : fb->data) bm = std::max(bm, std::fabs((double)v));
-            ctx->flt_in_bb += (float)((wm * 89.0 + bm) * 1.0001);
-        }
-    }
-    pk.down0s(&ctx->flt_down0s, "filter_net.downs.0", &ctx->down0_bw, &ctx->down0_bb);
-    for (int i = 1; i <= 4; ++i) {
-        DownW& d = ctx->downs[i - 1];
-        d.cin = ch[5 - i];
-        d.cout = ch[4 - i];
-        d.factor = fac[5 - i];
-        std::string p = "filter_net.downs." + std::to_string(i);
-        pk.conv({p + ".c1"}, &d.c1, d.cin, 3);
-        pk.conv({p + ".c2"}, &d.c2, d.cin, 3);
-        pk.conv_joint(p + ".c3", &d.c3, d.cin, 3, p + ".down_res", &d.res, d.cin, 1);      // c3(h2) + down_res(xi) land in one tile: joint scales
-        {   // c3.bias + down_res.bias for the launches that accumulate both convs into one tile
-            const HostTensor* b3 = pk.find(p + ".c3.bias");
-            const HostTensor* br = pk.find(p + ".down_res.bias");
-            if (b3 && br && b3->data.size() == (size_t)d.cout && br->data.size() == (size_t)d.cout) {
-                std::vector<float> sum(d.c3.Mpad, 0.f);
-                for (int m = 0; m < d.cout; ++m) sum[m] = b3->data[m] + br->data[m];
-                pk.fix.push_back({&d.c3res_bias, pk.ab.put(sum)});
-            }
-        }
-        if (d.cin == 24 && d.cout == 48) {
-            pk.conv24s(&d.s24c1, p + ".c1", 24);
-            pk.conv24s(&d.s24c2, p + ".c2", 24);
-            pk.conv24s(&d.s24c3r, p + ".c3", 48, p + ".down_res.bias", &d.c3);
-            // bounds of the fused block's on-chip intermediates (down24f_kernel): max_m sum_k |w| and max |b| of c1 and c2, a hair above
-            auto bound = [&](const std::string& name, float* bw, float* bb) {
-                const HostTensor* w = pk.find(name + ".weight");
-                const HostTensor* b = pk.find(name + ".bias");
-                if (!w || !b || w->data.size() != (size_t)24 * 24 * 3 || b->data.size() != 24) return;
-                double wl1 = 0.0, bm = 0.0;
-                for (int m = 0; m < 24; ++m) {
-                    double sum = 0.0;
-                    for (int k = 0; k < 72; ++k) sum += std::fabs((double)w->data[(size_t)m * 72 + k]);
-                    wl1 = std::max(wl1, sum);
-                    bm = std::max(bm, std::fabs((double)b->data[m]));
-                }
-                *bw = (float)(wl1 * 1.0001);
-                *bb = (float)(bm * 1.0001);
-            };
-            bound(p + ".c1", &d.b1_w, &d.b1_b);
-            bound(p + ".c2", &d.b2_w, &d.b2_b);
-        }
-    }
-    for (int i = 0; i < 5; ++i) {
-        UpW& u = ctx->ups[i];
-        u.cin = ch[i];
-        u.cout = i < 4 ? ch[i + 1] : ch[4];
-        u.factor = fac[i];
-        std::string p = "filter_net.ups." + std::to_string(i);
-        pk.conv({p + ".c1"}, &u.c1, u.cin, 3);
-        pk.conv({p + ".c2"}, &u.c2, u.cin, 3);
-        pk.conv({p + ".c3"}, &u.c3, u.cin, 3);
-        pk.conv({p + ".c4"}, &u.c4, u.cin, 3);
-        pk.conv({p + ".c5"}, &u.c5, u.cin, 1);
-        bound_1x1(p + ".c5", u.cout, u.cin, &u.c5_bw, &u.c5_bb);
-        pk.conv({p + ".film1.to_scale", p + ".film1.to_shift"}, &u.film1, u.cin, 1);
-        pk.conv({p + ".film2.to_scale", p + ".film2.to_shift"}, &u.film2, u.cin, 1);
-        if (u.cin >= 96) {
-            pk.film_u(&u.fu1, p + ".c2", p + ".film1", u.cin, p + ".c1");
-            pk.film_u(&u.fu2, p + ".c4", p + ".film2", u.cin, p + ".c3");
-        }
-        if (u.cin == 24) {
-            pk.up24s_half(&u.s24a, p + ".c1", p + ".c2", p + ".film1", "", "");
-            pk.up24s_half(&u.s24b, p + ".c3", p + ".c4", p + ".film2", p + ".c5", "filter_net.output_layer");
-        }
-    }
-
-    const std::string missing_dec = pk.missing;
+    ArenaBuilder ab;
+    std::string missing_enc, missing_dec;
+    pack_checkpoint(ctx, &ab, &missing_enc, &missing_dec);
     snprintf(ctx->enc_missing, sizeof(ctx->enc_missing), "%s", missing_enc.c_str());
     snprintf(ctx->dec_missing, sizeof(ctx->dec_missing), "%s", missing_dec.c_str());
     if (!missing_enc.empty() && !missing_dec.empty())
@@ -809,10 +170,10 @@ int tvc_finalize_weights(tvc_ctx* ctx) {
         TVC_HIP(ctx, hipFree(ctx->arena));
         ctx->arena = nullptr;
     }
-    ctx->arena_floats = pk.ab.buf.size();
+    ctx->arena_floats = ab.buf.size();
     TVC_HIP(ctx, hipMalloc((void**)&ctx->arena, ctx->arena_floats * sizeof(float)));
-    TVC_HIP(ctx, hipMemcpy(ctx->arena, pk.ab.buf.data(), ctx->arena_floats * sizeof(float), hipMemcpyHostToDevice));
-    for (auto& f : pk.fix) *f.slot = ctx->arena + f.off;
+    TVC_HIP(ctx, hipMemcpy(ctx->arena, ab.buf.data(), ctx->arena_floats * sizeof(float), hipMemcpyHostToDevice));
+    ab.resolve(ctx->arena);
     ctx->enc_ready = missing_enc.empty();
     ctx->dec_ready = missing_dec.empty();
     ctx->host.clear();   // staged copies are no longer needed

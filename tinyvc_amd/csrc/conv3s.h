@@ -19,7 +19,7 @@
 // FilterNet Downsample/Upsample convs (decoder.py:143-146, 166-171) and their FiLM (decoder.py:94-97).
 //
 // Layout.  K is walked in slabs of 16 input channels; a K16 step is (slab, tap).
-//   weights   pre-split on the host (api.hip Packer::a6): image [step][m-tile][part][lane][8 fp16], one
+//   weights   pre-split on the host (pack.hip Packer::a6): image [step][m-tile][part][lane][8 fp16], one
 //             1 KiB piece per (step, m-tile, part) already in MFMA lane order (row = lane & 31,
 //             k = 8 * (lane >> 5) + j); a piece is one 16-byte load + one ds_write_b128 per lane.
 //   input     the slab's halo tile is staged once: each thread loads 8 channels of one sample (coalesced
@@ -1079,7 +1079,7 @@ __global__ __launch_bounds__(TL::NTHR) __attribute__((amdgpu_waves_per_eu(FILM ?
                 // Downsample (decoder.py:148-157): out = c3(lrelu(h2)) + down_res(xi).  Both are linear into the same output tile:
                 // the 1x1 runs as a second K phase over xi (a.cond, a.Ccond channels, image a.sc6) on the same accumulators, so
                 // the residual tensor is never written or read back and its launch disappears (ep.bias = the two biases summed).
-                // One accumulator pair, one unit: the two images are packed with JOINT per-m-tile scales (api.hip) and the two
+                // One accumulator pair, one unit: the two images are packed with JOINT per-m-tile scales (pack.hip) and the two
                 // inputs share the smaller of their block-floating-point scales.
                 const float* cb = RAGT ? a.cond + coloff : a.cond + (long)b * a.Ccond * len;
                 const Bfp s2 = bfp_min(sx, bfp_load_u(a.amax_c, b));

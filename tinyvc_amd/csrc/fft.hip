@@ -9,7 +9,7 @@
 // 8 waves = 8 consecutive frames of one utterance per workgroup, so the [961][T] spectrogram is written / read in
 // 32-byte runs along time through an LDS transpose.  ~0.1 MFLOP per frame instead of the 3.7 MFLOP of the half-size
 // real-DFT GEMMs this replaces (frontend.hip, decoder.hip keep those behind -DTVC_FFT=0).
-// Twiddles come from fp64-computed tables (api.hip build_dft_tables): tw960[j] = (cos, sin)(2 pi j / 960),
+// Twiddles come from fp64-computed tables (pack.hip pack_constants): tw960[j] = (cos, sin)(2 pi j / 960),
 // tw1920[k] = (cos, sin)(2 pi k / 1920), hann[n] = 0.5 - 0.5 cos(2 pi n / 1920).
 #include "small_kernels.h"
 #include "tvc_common.h"

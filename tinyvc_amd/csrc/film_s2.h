@@ -11,7 +11,7 @@
 // Three results per element (conv, scale, shift) leave no registers for accumulator PAIRS (conv3s.h: 2 x 3 x 32 at three waves per
 // SIMD), so this kernel adds the three part products of the fp16 split into ONE fp32 accumulator per result.  The low parts are then
 // plain fp16 residuals (x - fp16(x), not scaled by 2^11), whose absolute resolution is fp16's 2^-24 (subnormals are kept by the MFMA);
-// to make that negligible every operand is normalised first: weights per 32-row m-tile to |max| in [2^13, 2^14) at pack time (api.hip
+// to make that negligible every operand is normalised first: weights per 32-row m-tile to |max| in [2^13, 2^14) at pack time (pack.hip
 // film_u), activations per utterance to |max| in [2^14, 2^15) by the power of two taken from the tensor's |max| slot - always, not only
 // outside fp16's range.  A residual is then resolved to 2^-38 of its tensor's largest value; products stay below 2^29 and sums over
 // K = 3 * 384 below 2^40.  Error against fp64 on N(0,1) operands, K = 768: 3.1e-7 rel rms at every input scale from 1e-7 to 1e5 (accumulator
@@ -318,13 +318,13 @@ __global__ __launch_bounds__(FS2T<NWV_>::NTHR) __attribute__((amdgpu_waves_per_e
 #pragma unroll
             for (int i = 0; i < WM; ++i) {
             const int row0 = (cmb * MTB + wm * WM + i) * 32;
-            const float kc = Tb[384 + row0] * ix, ks = Tb[4 * 384 + row0] * ic_, kh = Tb[5 * 384 + row0] * ic_;      // one m-tile: one scale each
+            const float kc = Tb[FilmU::TAB_SCALE * 384 + row0] * ix, ks = Tb[FilmU::TAB_SSC * 384 + row0] * ic_, kh = Tb[FilmU::TAB_SSH * 384 + row0] * ic_;      // one m-tile: one scale each
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int rr = row0 + 8 * g + 4 * eh;
-                const float4 b0 = *reinterpret_cast<const float4*>(Tb + rr);
-                const float4 b1 = *reinterpret_cast<const float4*>(Tb + 2 * 384 + rr);
-                const float4 b2 = *reinterpret_cast<const float4*>(Tb + 3 * 384 + rr);
+                const float4 b0 = *reinterpret_cast<const float4*>(Tb + FilmU::TAB_BIAS * 384 + rr);
+                const float4 b1 = *reinterpret_cast<const float4*>(Tb + FilmU::TAB_BSC * 384 + rr);
+                const float4 b2 = *reinterpret_cast<const float4*>(Tb + FilmU::TAB_BSH * 384 + rr);
                 const float bm[4] = {b0.x, b0.y, b0.z, b0.w}, bs[4] = {b1.x, b1.y, b1.z, b1.w}, bh[4] = {b2.x, b2.y, b2.z, b2.w};
 #pragma unroll
                 for (int q = 0; q < 4; ++q)

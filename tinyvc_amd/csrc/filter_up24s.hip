@@ -9,7 +9,7 @@
 //   LDS     Xs[part][8-channel group][position][8 fp16]: lrelu(input tile), split while it is deposited;
 //           Hs, same layout: lrelu(first conv + bias), split by the first conv's epilogue;
 //           R[24][PS] fp32: the raw input tile (residual); half B overwrites it in place with x2 for the output conv;
-//           Wt: the block's weights, pre-split on the host into MFMA A-lane order (api.hip up24s_half), resident.
+//           Wt: the block's weights, pre-split on the host into MFMA A-lane order (pack.hip up24s_half), resident.
 //   K order a 24-channel k3 conv has 9 (tap, 8-channel group) units; a K16 step takes two of them, one per lane half
 //           (5 steps, the 10th unit has zero weights).  A tap is a row offset in Xs / Hs, so every B fragment is one
 //           ds_read_b128 of a contiguous 512-byte run per lane half.
@@ -43,7 +43,7 @@ struct U24S {
     static constexpr int XP = XW;
     static constexpr int PS = W2r + 16;                        // fp32 residual tile row stride: 272 = the one stride <= 300 for which the output pass's 16-byte reads (8 lanes x 3 rows apart, 4 columns per lane) are conflict-free in all four ds_read_b128 lane groups (W2r + 4 was 3-way)
     static constexpr int ITEMS = 3 * XW, XPER = (ITEMS + NT - 1) / NT;
-    static constexpr int PIECES = 28, FL = 320;      // floats behind the pieces: the blob's 304, then 8 for the |max| exchange
+    static constexpr int PIECES = Up24sBlob::PIECES, FL = 320;      // floats behind the pieces: the blob's, then the |max| exchange
     static constexpr int LDS_BYTES = (6 * XP + 6 * HP + PIECES * 64) * 16 + (FL + C * PS) * 4;
     static_assert(NT2 <= NWAVES, "one second-conv tile per wave");
     static_assert(XW - H >= W2, "residual columns");
@@ -57,7 +57,7 @@ struct Up24SArgs {
                          // cond * 2^k, k from the bound cbw |max of downs.0's input| + cbb >= |cond| (amax_c = that input's slot; both kernels evaluate it alike)
     float cbw, cbb;
     float* out;          // half A: x1 (G8 layout); half B: waveform [B][len]
-    const u32x4* img;    // weight blob (api.hip up24s_half)
+    const u32x4* img;    // weight blob (pack.hip up24s_half, layout Up24sBlob)
     int len, xf, tiles_per_utt, ntiles;
     float interp_scale;
     // block-floating-point guard (conv3s.h): per-utterance |max| slots of x / of the tensor cond was computed from (read, nullable) and of `out` (half A: written, nullable)
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE
     u32x4* Xs = reinterpret_cast<u32x4*>(smem_u);
     u32x4* Hs = Xs + 6 * XP;
     u32x4* Wt = Hs + 6 * HP;
-    float* Fl = reinterpret_cast<float*>(Wt + CF::PIECES * 64);   // ba, bb, bsc, bsh [32 each], w75 [24][7], b75, weight scales [297..300], the bound constants [301], [302]
+    float* Fl = reinterpret_cast<float*>(Wt + CF::PIECES * 64);   // the blob's floats (Up24sBlob), then the |max| exchange
     float* R = Fl + CF::FL;                                       // [24][PS]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, lh = lane >> 5;
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE
     auto utt = [&](int tile) __attribute__((always_inline)) { return rag_tile<RAG>(a.rag, tile, a.tiles_per_utt, rs, bh).b; };
 
     // ---- once per workgroup: weights and biases -> LDS -------------------------------------------------
-    for (int i = tid; i < CF::PIECES * 64 + 304 / 4; i += NT) Wt[i] = a.img[i];
+    for (int i = tid; i < CF::PIECES * 64 + Up24sBlob::FLOATS / 4; i += NT) Wt[i] = a.img[i];
 
     // ---- input tile staging: an item = 8 channels of one position ---------------------------------------
     // Per-thread item geometry is tile-invariant; global addresses are a uniform per-channel base (SGPRs) plus one 32-bit
@@ -252,7 +252,7 @@ __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE
         deposit(bfp_load_u(a.amax_x, bh).s);
     }
     slab_barrier();
-    const float wsa = Fl[297], wsb = Fl[298], wssc = Fl[299], wssh = Fl[300], wl1 = Fl[301], bamax = Fl[302];
+    const float wsa = Fl[Up24sBlob::SA], wsb = Fl[Up24sBlob::SB], wssc = Fl[Up24sBlob::SSC], wssh = Fl[Up24sBlob::SSH], wl1 = Fl[Up24sBlob::L1A], bamax = Fl[Up24sBlob::BMA];
     float mx_run = 0.f;
     int mx_b = bh;
     int slot_b = -1;
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE
         const int b = rt.b, len = rt.len;
         bh = b;
         if (!CF::SECOND && a.amax_y && b != mx_b) {
-            amax_flush_wg(a.amax_y + mx_b, mx_run, Fl + 304);
+            amax_flush_wg(a.amax_y + mx_b, mx_run, Fl + Up24sBlob::FLOATS);
             mx_run = 0.f;
             mx_b = b;
         }
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE
             const float c = wsa * sx.inv, cl = c * kLoInv;
 #pragma unroll
             for (int g = 0; g < 3; ++g) {
-                const f32x4s bv = *reinterpret_cast<const f32x4s*>(Fl + 8 * g + 4 * lh);
+                const f32x4s bv = *reinterpret_cast<const f32x4s*>(Fl + Up24sBlob::BA + 8 * g + 4 * lh);
                 float v[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -373,7 +373,7 @@ __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE
                 conv24_phase<HP, D2>(acc, alo, Hs, Wt + 10 * 64, n, lo, hi, lane);
 #pragma unroll
                 for (int g = 0; g < 3; ++g) {
-                    const f32x4s bb = *reinterpret_cast<const f32x4s*>(Fl + 32 + 8 * g + 4 * lh);
+                    const f32x4s bb = *reinterpret_cast<const f32x4s*>(Fl + Up24sBlob::BB + 8 * g + 4 * lh);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) hv[g][q] = comb(acc[4 * g + q], alo[4 * g + q], cb, cbl) + bb[q];
                 }
@@ -400,8 +400,8 @@ __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE
 #pragma unroll
             for (int g = 0; g < 3; ++g) {
                 float v4[4];
-                const f32x4s bs = *reinterpret_cast<const f32x4s*>(Fl + 64 + 8 * g + 4 * lh);
-                const f32x4s bh = *reinterpret_cast<const f32x4s*>(Fl + 96 + 8 * g + 4 * lh);
+                const f32x4s bs = *reinterpret_cast<const f32x4s*>(Fl + Up24sBlob::BSC + 8 * g + 4 * lh);
+                const f32x4s bh = *reinterpret_cast<const f32x4s*>(Fl + Up24sBlob::BSH + 8 * g + 4 * lh);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int m = 8 * g + 4 * lh + q;
@@ -430,7 +430,7 @@ __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE
             // ---- S4: c5 and output_layer folded into one Conv1d(24 -> 1, k7, replicate) on the parked x2 tile ----
             // 8 lanes per group of 4 consecutive outputs, 3 channels each: per channel 10 activations and 7
             // (broadcast) weights feed 28 FMAs; the 8 partial sums meet through three shuffles.
-            const float* W7 = Fl + 128;
+            const float* W7 = Fl + Up24sBlob::W75;
             const int part = tid & 7;
             const int lo = -p20 > 0 ? -p20 : 0;
             const int hi = (len - 1 - p20) < (CF::W2 - 1) ? (len - 1 - p20) : (CF::W2 - 1);
@@ -474,7 +474,7 @@ __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE
                 const int o = 4 * g + part;                  // lanes 0..3 of a group store outputs 4g..4g+3
                 const float v = part == 0 ? o4[0] : (part == 1 ? o4[1] : (part == 2 ? o4[2] : o4[3]));
                 static_assert((W + 3) / 4 <= NT / 8, "one output per thread: it waits in a register until the deposit is through");
-                wv_out = v + W7[168];
+                wv_out = v + Fl[Up24sBlob::B75];
                 wv_live = part < 4 && o < W && t0 + o < len;
                 wv_off = t0 + o;
             }
@@ -501,7 +501,7 @@ __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE
 #ifdef U24_TRACE
     if (tr_on) g_u24_trace[((CF::SECOND ? 1 : 0) * 4 + tr_slot) * 64] = (unsigned long long)tr_n;
 #endif
-    if (!CF::SECOND && a.amax_y && tend > (int)((long)a.ntiles * blockIdx.x / gridDim.x)) amax_flush_wg(a.amax_y + mx_b, mx_run, Fl + 304);
+    if (!CF::SECOND && a.amax_y && tend > (int)((long)a.ntiles * blockIdx.x / gridDim.x)) amax_flush_wg(a.amax_y + mx_b, mx_run, Fl + Up24sBlob::FLOATS);
 }
 
 template <class CF>
@@ -583,9 +583,9 @@ struct Down0SArgs {
     const float* energy;   // [B][1][L]
     float* out;            // optional (parity taps) [B][24][L] fp32
     uint4* planes;         // the output as the FiLM 1x1s' ready B operand (up24s_kernel): two fp16 planes [B][part][3 groups][L][8 fp16] of out * 2^k,
-                           // k from the analytic bound Bi[29] |x|max + Bi[30] >= |out| (amax_x non-null)
+                           // k from the analytic bound BW |x|max + BB >= |out| (Down0sBlob; amax_x non-null)
     float* y2;             // optional, G8 layout [B][3][L / 5][8]: F.interpolate(out, scale_factor = 1/5) = the sample at 5 d + 2
-    const u32x4* img;      // 10 weight pieces + 32 floats: bias, [31] = the image's scale (api.hip down0s)
+    const u32x4* img;      // weight blob (pack.hip down0s, layout Down0sBlob)
     int len, tiles_per_utt, ntiles;
     const float* amax_x;   // per-utterance |max| of cat[source, energy] (block-floating-point guard, conv3s.h), nullable
     float* amax_y;         // ... of the output (written), nullable
@@ -599,12 +599,12 @@ static __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4)))
     constexpr int W = 254, XW = 256, XP = XW, NT = 512;
     extern __shared__ __attribute__((aligned(16))) uint4 smem_d[];
     u32x4* Xs = reinterpret_cast<u32x4*>(smem_d);              // [2 buffers][2 parts][3 groups][XP]
-    u32x4* Wt = Xs + 2 * 6 * XP;                               // 10 pieces
-    float* Bi = reinterpret_cast<float*>(Wt + 10 * 64);        // bias [32] ([31] = weight scale), [32..39] = |max| exchange
+    u32x4* Wt = Xs + 2 * 6 * XP;                               // the blob's pieces
+    float* Bi = reinterpret_cast<float*>(Wt + Down0sBlob::PIECES * 64);      // its floats (Down0sBlob), then the |max| exchange
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, lh = lane >> 5;
     const int rs = a.len;                // row stride (= every utterance's length unless RAG)
-    for (int i = tid; i < 10 * 64 + 8; i += NT) Wt[i] = a.img[i];
+    for (int i = tid; i < Down0sBlob::PIECES * 64 + Down0sBlob::FLOATS / 4; i += NT) Wt[i] = a.img[i];
 
     // staging: thread -> (group tid >> 8 of the 16 source rows, column tid & 255); threads 0..255 also carry the energy row
     const int g = tid >> 8, c = tid & 255;
@@ -647,7 +647,7 @@ static __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4)))
     if (tile + 1 < tend) fetch(tile + 1);
     slab_barrier();
     const int len2 = rs / 5;             // row stride of the 1/5-rate copy
-    const float cw = Bi[31];
+    const float cw = Bi[Down0sBlob::SCALE];
     float mx_run = 0.f;
     int mx_b = bh;
     for (; tile < tend; ++tile, cur ^= 1) {
@@ -655,7 +655,7 @@ static __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4)))
         const int b = rt.b, len = rt.len;
         bh = b;
         if (a.amax_y && b != mx_b) {
-            amax_flush_wg(a.amax_y + mx_b, mx_run, Bi + 32);
+            amax_flush_wg(a.amax_y + mx_b, mx_run, Bi + Down0sBlob::FLOATS);
             mx_run = 0.f;
             mx_b = b;
         }
@@ -670,7 +670,7 @@ static __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4)))
         conv24_phase<XP, 1>(acc, alo, Xs + cur * 6 * XP, Wt, n, 0, XW - 1, lane);
         // the planes' scale 2^k (up24s_kernel undoes it) rides in the epilogue's constants: (acc c + lo cl + bias) 2^k is formed as
         // acc (c 2^k) + lo (cl 2^k) + bias 2^k - powers of two, the same bits - and the fp32 values the tap / the 1/5-rate copy / the |max| want are vs 2^-k
-        const Bfp pn = a.amax_x ? norm_from_amax(fmaf(Bi[29], sload_f32(a.amax_x + b), Bi[30])) : Bfp{1.f, 1.f};
+        const Bfp pn = a.amax_x ? norm_from_amax(fmaf(Bi[Down0sBlob::BW], sload_f32(a.amax_x + b), Bi[Down0sBlob::BB])) : Bfp{1.f, 1.f};
         const float ps = pn.s, pinv = pn.inv;
         const float cc = cw * bfp_load_u(a.amax_x, b).inv * ps, ccl = cc * kLoInv;
         const int t = t0 + n;
@@ -686,7 +686,7 @@ static __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4)))
             const bool pick = live && a.y2 != nullptr && tc - 5 * q5 == 2;
 #pragma unroll
             for (int gg = 0; gg < 3; ++gg) {
-                const f32x4s bv = *reinterpret_cast<const f32x4s*>(Bi + 8 * gg + 4 * lh);
+                const f32x4s bv = *reinterpret_cast<const f32x4s*>(Bi + Down0sBlob::BIAS + 8 * gg + 4 * lh);
                 float v[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -712,7 +712,7 @@ static __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4)))
         mx_run = fmaxf(mx_run, mx * pinv);
         slab_barrier();
     }
-    if (a.amax_y) amax_flush_wg(a.amax_y + mx_b, mx_run, Bi + 32);
+    if (a.amax_y) amax_flush_wg(a.amax_y + mx_b, mx_run, Bi + Down0sBlob::FLOATS);
 }
 
 int run_down0_split(tvc_ctx* ctx, hipStream_t s, const float* blob, const float* source, const float* energy, float* planes, float* out_fp32, float* y2, int B, int len,
@@ -757,7 +757,7 @@ struct Down24FArgs {
     const float* x;        // xi, G8 layout [B][3][len][8] (down0s_kernel's 1/5-rate copy)
     float* out;            // [B][6][len][8]: the block's output in the G8 layout (conv48s.hip: 16-byte stores here, 16-byte fragment loads there)
     float* y2;             // optional [B][48][len / 4]: mean of samples 4 d + 1, 4 d + 2 (the next block's 1/4-rate input)
-    const u32x4* img1;     // the three convs' blobs (api.hip Packer::conv24s): c1 (10 pieces + 64 floats), c2, c3 (20 pieces, bias = c3 + down_res, joint scales)
+    const u32x4* img1;     // the three convs' blobs (pack.hip conv24s, layout Conv24sBlob): c1 (one m-tile), c2, c3 (two, bias = c3 + down_res, joint scales)
     const u32x4* img2;
     const u32x4* img3;
     const u32x4* rimg;     // down_res image (8 pieces)
@@ -784,7 +784,8 @@ static __global__ __launch_bounds__(D24F::NT) __attribute__((amdgpu_waves_per_eu
     u32x4* W2 = W1 + 10 * 64;
     u32x4* W3 = W2 + 10 * 64;
     u32x4* Wr = W3 + 20 * 64;
-    float* Bi = reinterpret_cast<float*>(Wr + 8 * 64);         // the three blobs' 64 floats (bias, [62 + mt] = scales), then the |max| exchange
+    float* Bi = reinterpret_cast<float*>(Wr + 8 * 64);         // the three blobs' floats (Conv24sBlob), then the |max| exchange
+    using CB = Conv24sBlob;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, lh = lane >> 5;
     const int rs = a.len;                // row stride (= every utterance's length unless RAG)
@@ -796,10 +797,10 @@ static __global__ __launch_bounds__(D24F::NT) __attribute__((amdgpu_waves_per_eu
     }
     for (int i = tid; i < 20 * 64; i += NT) W3[i] = a.img3[i];
     for (int i = tid; i < 8 * 64; i += NT) Wr[i] = a.rimg[i];
-    if (tid < 64) {
-        Bi[tid] = reinterpret_cast<const float*>(a.img1 + 10 * 64)[tid];
-        Bi[64 + tid] = reinterpret_cast<const float*>(a.img2 + 10 * 64)[tid];
-        Bi[128 + tid] = reinterpret_cast<const float*>(a.img3 + 20 * 64)[tid];
+    if (tid < CB::FLOATS) {
+        Bi[tid] = reinterpret_cast<const float*>(a.img1 + K24_PIECES * 64)[tid];
+        Bi[CB::FLOATS + tid] = reinterpret_cast<const float*>(a.img2 + K24_PIECES * 64)[tid];
+        Bi[2 * CB::FLOATS + tid] = reinterpret_cast<const float*>(a.img3 + 2 * K24_PIECES * 64)[tid];
     }
 
     // staging items (8-channel group, column): 3 * XW = 774, two per thread
@@ -891,7 +892,7 @@ static __global__ __launch_bounds__(D24F::NT) __attribute__((amdgpu_waves_per_eu
         const int b = rt.b, len = rt.len;
         bh = b;
         if (a.amax_y && b != mx_b) {
-            amax_flush_wg(a.amax_y + mx_b, mx_run, Bi + 192);
+            amax_flush_wg(a.amax_y + mx_b, mx_run, Bi + 3 * CB::FLOATS);
             mx_run = 0.f;
             mx_b = b;
         }
@@ -923,7 +924,7 @@ static __global__ __launch_bounds__(D24F::NT) __attribute__((amdgpu_waves_per_eu
             for (int r = 0; r < 16; ++r) acc[r] = alo[r] = 0.f;
             conv24_phase<XP, 1>(acc, alo, Xs + cur * 6 * XP, W1, n, 0, XW - 1, lane);       // Xs holds the replicate-padded input
             fetch(next2 < tend ? next2 : tile);      // tile i + 2 flies across this tile; requested behind c1's MFMAs (up24s_kernel has the note), the last tiles re-read themselves
-            to_tile(acc, alo, Bi[62] * sc.x.inv, Bi, sc.h1.s, H1, n);
+            to_tile(acc, alo, Bi[CB::SCALE] * sc.x.inv, Bi + CB::BIAS, sc.h1.s, H1, n);
         }
         slab_barrier();
         // ---- c2: H1 -> H2 (position t0 - 4 + n needs h1 at positions ... + 2 (tap - 1) = H1 columns n + 2 tap) -------------------
@@ -934,7 +935,7 @@ static __global__ __launch_bounds__(D24F::NT) __attribute__((amdgpu_waves_per_eu
             const int lo = 6 - t0 > 0 ? 6 - t0 : 0;                                  // the layer's own replicate padding: h1 exists on [0, len)
             const int hi = len - 1 - t0 + 6 < HP - 1 ? len - 1 - t0 + 6 : HP - 1;
             conv24_phase<HP, 2>(acc, alo, H1, W2, n, lo, hi, lane);
-            to_tile(acc, alo, Bi[64 + 62] * sc.h1.inv, Bi + 64, sc.hj.s, H2, n);
+            to_tile(acc, alo, Bi[CB::FLOATS + CB::SCALE] * sc.h1.inv, Bi + CB::FLOATS + CB::BIAS, sc.hj.s, H2, n);
         }
         slab_barrier();
         // ---- c3 + down_res: H2 (columns n + 4 tap) and xi -> out, two m-tiles sharing every B fragment ---------------------------
@@ -1003,11 +1004,11 @@ static __global__ __launch_bounds__(D24F::NT) __attribute__((amdgpu_waves_per_eu
             const bool pair = a.y2 != nullptr && (t & 3) == 1 && t + 1 < len;      // 1/4-rate copy: mean of samples 4 d + 1, 4 d + 2
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) {
-                const float c = Bi[128 + 62 + mt] * sc.hj.inv, cl = c * kLoInv;
+                const float c = Bi[2 * CB::FLOATS + CB::SCALE + mt] * sc.hj.inv, cl = c * kLoInv;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     if (32 * mt + 8 * g >= 48) continue;
-                    const f32x4s bv = *reinterpret_cast<const f32x4s*>(Bi + 128 + 32 * mt + 8 * g + 4 * lh);
+                    const f32x4s bv = *reinterpret_cast<const f32x4s*>(Bi + 2 * CB::FLOATS + CB::BIAS + 32 * mt + 8 * g + 4 * lh);
                     float v4[4];
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
@@ -1027,7 +1028,7 @@ static __global__ __launch_bounds__(D24F::NT) __attribute__((amdgpu_waves_per_eu
         mx_run = fmaxf(mx_run, mx);
         // (no barrier here: the next tile's c1 writes H1, which nobody reads any more; its first barrier comes before anybody rewrites H2)
     }
-    if (a.amax_y) amax_flush_wg(a.amax_y + mx_b, mx_run, Bi + 192);
+    if (a.amax_y) amax_flush_wg(a.amax_y + mx_b, mx_run, Bi + 3 * CB::FLOATS);
 }
 
 int run_down24_fused(tvc_ctx* ctx, hipStream_t s, const DownW& d, const float* xi, float* out, float* y2, int B, int len, const float* amax_xi, float* amax_out) {

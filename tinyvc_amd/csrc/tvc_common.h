@@ -52,8 +52,32 @@ struct ConvNeXtW {
     int C = 0, dilation = 1;
 };
 
+// Weight blobs of the 24-channel split-precision kernels (filter_up24s.hip), written by pack.hip: 1 KiB pieces of fp16 pairs in
+// v_mfma_f32_32x32x16_f16 A-lane order (a k3 conv's m-tile takes K24_PIECES: 5 K16 steps x 2 parts), then FLOATS floats at the offsets below.
+constexpr int K24_PIECES = 10;
+struct Up24sBlob {        // one half of the fused ups.4 block (Packer::up24s_half)
+    static constexpr int PIECES = 28;
+    static constexpr int BA = 0, BB = 32, BSC = 64, BSH = 96;     // biases of conv a, conv b, to_scale, to_shift [32 each]
+    static constexpr int W75 = 128, B75 = 296;                    // the folded output conv c5 . output_layer: taps [24][7], bias
+    static constexpr int SA = 297, SB = 298, SSC = 299, SSH = 300; // power-of-two scales of conv a, conv b, to_scale, to_shift
+    static constexpr int L1A = 301, BMA = 302;                    // max_m sum_k |w_a[m][k]|, max |b_a|: the bound of conv a's output
+    static constexpr int FLOATS = 304;
+};
+struct Down0sBlob {       // the 17 -> 24 k3 conv of downs.0 (Packer::down0s)
+    static constexpr int PIECES = K24_PIECES;
+    static constexpr int BIAS = 0;                                // [24]
+    static constexpr int BW = 29, BB = 30;                        // |out| <= BW |x|max + BB
+    static constexpr int SCALE = 31;                              // the image's power-of-two scale
+    static constexpr int FLOATS = 32;
+};
+struct Conv24sBlob {      // one 24-input-channel k3 conv of down24f_kernel, M = 24 or 48 rows: K24_PIECES per m-tile (Packer::conv24s)
+    static constexpr int BIAS = 0;                                // [M]
+    static constexpr int SCALE = 62;                              // + m-tile: power-of-two scales
+    static constexpr int FLOATS = 64;
+};
+
 struct DownW {
-    PackedW res, c1, c2, c3;             // c3 and res share their per-m-tile scales (accumulated into one tile)
+    PackedW res, c1, c2, c3;             // c3 and res share their per-m-tile scales (accumulated into one tile); cin == 24 packs c3 and res only
     const float* c3res_bias = nullptr;   // c3.bias + down_res.bias [c3.Mpad]: c3 launches that fold the residual 1x1 in as a second K phase
     const float* s24c1 = nullptr;   // cin == 24: weight blobs of down24f_kernel (filter_up24s.hip)
     const float* s24c2 = nullptr;
@@ -65,13 +89,14 @@ struct DownW {
 // step multiplies - the conv's three taps and the to_scale / to_shift columns of the same 16 channels - and one table of per-row
 // constants [6][C]: conv bias, conv row scale, b_scale, b_shift, to_scale row scale, to_shift row scale.
 struct FilmU {
+    static constexpr int TAB_BIAS = 0, TAB_SCALE = 1, TAB_BSC = 2, TAB_BSH = 3, TAB_SSC = 4, TAB_SSH = 5;      // rows of `tab`
     const float* img = nullptr;
     const float* tab = nullptr;
     int C = 0;
     float hb_w = 0.f, hb_b = 0.f;      // bound of the half's FIRST conv (the producer of this kernel's h): |c(x) + b| <= hb_w |x|max + hb_b
 };
 struct UpW {
-    PackedW c1, c2, c3, c4, c5, film1, film2;  // film = [to_scale ; to_shift] stacked on M (2C); film.bias = [b_scale (C) ; b_shift (C)]
+    PackedW c1, c2, c3, c4, c5, film1, film2;  // film = [to_scale ; to_shift] stacked on M (2C); film.bias = [b_scale (C) ; b_shift (C)]; cin == 24 packs none
     FilmU fu1, fu2;                            // (c2, film1) and (c4, film2) for the single-accumulator pipelined kernel
     const float* s24a = nullptr;               // cin == 24: weight blobs of the two halves of the split-precision fused block (filter_up24s.hip)
     const float* s24b = nullptr;
@@ -82,6 +107,17 @@ struct UpW {
 struct HostTensor {
     std::vector<float> data;
     std::vector<int64_t> shape;
+};
+
+// Host image of one device arena (pack.hip): the floats to upload and the context slots that point into them.
+struct ArenaBuilder {
+    std::vector<float> buf;
+    std::vector<std::pair<const float**, size_t>> fix;      // (slot, offset): *slot = arena + offset once uploaded
+    size_t put(const float** slot, const float* v, size_t n);      // a copy of v[0 .. n) at a 256-byte aligned offset, which `slot` will point at
+    size_t put(const float** slot, const std::vector<float>& v) { return put(slot, v.data(), v.size()); }
+    void resolve(const float* arena) const {
+        for (auto& f : fix) *f.first = arena + f.second;
+    }
 };
 
 }  // namespace tvc
@@ -256,6 +292,13 @@ inline int launch_check(tvc_ctx* ctx, const char* what) {
     if (e != hipSuccess) return fail(ctx, TVC_ERR_HIP, "launch %s: %s", what, hipGetErrorString(e));
     return 0;
 }
+
+// ---- checkpoint packing (pack.hip: host only, no HIP call) ---------------------------------------
+// the constant arena: FFT tables and the SOLA search's scratch, independent of any checkpoint
+void pack_constants(tvc_ctx*, ArenaBuilder*);
+// the weight arena from ctx->host and ctx->pitch_table; it also sets the images' geometry and the analytic bounds in ctx.
+// missing_enc / missing_dec: the first missing or misshapen key of the encoder's / the decoder's tensors (empty: complete).
+void pack_checkpoint(tvc_ctx*, ArenaBuilder*, std::string* missing_enc, std::string* missing_dec);
 
 // ---- stage drivers (each enqueues kernels on `s`; ws.dry = measure the workspace only) ----------
 int run_stft(tvc_ctx*, hipStream_t, Ws&, const float* wav, float* spec, int B, int64_t L);
