@@ -1,4 +1,4 @@
-"""The fp16 range guard of the split-precision kernels (conv3s.h: block floating point).
+"""The fp16 range guard of the split-precision kernels (split_fp16.h: block floating point).
 
 Every fp32 operand is multiplied as two fp16 parts; fp16 tops out at 65 504 and loses relative precision below 6e-5, the fp32
 reference does neither.  The guard: weights normalised per 32-row m-tile at pack time, activations scaled by a per-utterance power

@@ -23,7 +23,7 @@ def _stale(target, deps):
 
 def build(force=False, verbose=True):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    flags = FLAGS + os.environ.get("TVC_EXTRA_FLAGS", "").split()   # e.g. -DUP24_NT=1024 for A/B runs
+    flags = FLAGS + os.environ.get("TVC_EXTRA_FLAGS", "").split()   # extra hipcc flags of an A/B build, e.g. -O2
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     headers.append(os.path.join(os.path.dirname(HERE), "include", "tinyvc_hip.h"))
     objs, jobs = [], []

@@ -10,10 +10,6 @@
 
 using namespace tvc;
 
-#ifndef TVC_SIDE_PRIO_EXPR
-#define TVC_SIDE_PRIO_EXPR prio_least
-#endif
-
 // Prepared kNN blobs of this process: device pointer -> N it was prepared for.  The kernels take the blob's geometry (offsets of the
 // inverse norms and the fp16 image) from the caller's N, so a call whose N differs from the one the blob was prepared with would read
 // out of bounds: such a call is refused.  (A blob this process did not prepare - e.g. a copy - is unknown here and trusted.)
@@ -97,7 +93,7 @@ int tvc_ctx_create(int hip_device, tvc_ctx** out) {
     // slots the trunk's launches leave free instead of competing with them (the pitch chain has ~150 us of slack)
     int prio_least = 0, prio_greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    if (hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, TVC_SIDE_PRIO_EXPR) != hipSuccess ||
+    if (hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, prio_least) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_fork2, hipEventDisableTiming) != hipSuccess ||
@@ -200,7 +196,7 @@ static int convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* wav, c
     float* matched = ws.get<float>((size_t)B * kSslDim * T);
     float* f0 = ws.get<float>((size_t)B * T);
     float* f0s = ws.get<float>((size_t)B * T);
-    // |max| slots the path can bound without a pass over the tensors (block-floating-point guard of the fp16 split, conv3s.h; equal-length
+    // |max| slots the path can bound without a pass over the tensors (block-floating-point guard of the fp16 split, split_fp16.h; equal-length
     // batches): emax = max |wav| per utterance (the energy stage's pooled maxima, 1 500 values each) bounds the energy envelope - a linear
     // interpolation of them - and, times the Hann window's sum (960), every |STFT| bin; `matched` is a mean of index rows.
     // A ragged batch (the driver passed B = 1, T = all frames: ragged.h) derives them per utterance in the same way - an utterance's scales,

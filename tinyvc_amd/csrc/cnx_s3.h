@@ -17,15 +17,15 @@
 // walks its own 32-row m-tiles of the weight image: the A fragments come straight from global memory - the image is already in MFMA
 // lane order, one 16-byte load per lane and piece, no LDS round trip, a 4-step register ring keeps them ahead of the MFMAs - and the B
 // fragments are 16-byte LDS reads of the resident tile.  The gemm_s2 pipeline these launches ran on spends 1 650 of a slab's 3 800
-// cycles at its barrier (S_TRACE stamps); here waves never meet after the prologue, one wave's GELU / store
+// cycles at its barrier (cycle stamps, round 4: DESIGN.md section 4); here waves never meet after the prologue, one wave's GELU / store
 // epilogue runs under the other wave's MFMAs on the same SIMD, and the LayerNorm output (cnx1) never exists in HBM.
 // K = 768 (cnx2 at C = 384) does not fit the LDS at 64 columns: the operand tile is staged in two K halves with the accumulators
 // kept across them (one m-tile per wave, twelve waves).
 // Small launches (a streaming block, one utterance) split the rows of the weight image over blockIdx.z so that the chip is covered;
 // the prologue is then recomputed per row block, which costs nothing on an idle chip.
 #pragma once
-#include "conv3s.h"
 #include "gemm_epi.h"
+#include "split_fp16.h"
 
 namespace tvc {
 
@@ -47,30 +47,10 @@ struct CnxArgs {
     int gp_sum;          // cnx2: 0 = add this utterance's own tiles up in ascending order; 1 = grn_tiles_kernel already did, into slot 0
     const float* grn_g;  // [2C]
     float* amax_y;       // optional per-utterance |max| slot of the output x (zeroed by the caller)
-#ifdef CNX_TRACE
-    unsigned long long* trace;   // diagnostic build (tools/micro/cnx_bench.hip): s_memtime stamps of two waves of workgroup CNX_TRACE
-#endif
 };
-#ifdef CNX_TRACE
-#define CNX_STAMP(id)                                                                                   \
-    do {                                                                                                \
-        __builtin_amdgcn_sched_barrier(0);                                                              \
-        if (a.trace && (int)(blockIdx.x + gridDim.x * blockIdx.y) == CNX_TRACE && (tid & 255) == 0 && tid < 512) {   \
-            unsigned long long t_;                                                                      \
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");               \
-            a.trace[(tid >> 8) * 32 + (id)] = t_;                                                       \
-        }                                                                                               \
-        __builtin_amdgcn_sched_barrier(0);                                                              \
-    } while (0)
-#else
-#define CNX_STAMP(id) do {} while (0)
-#endif
 
 constexpr int CNX_GP_INLINE = 16;   // tile sums a cnx2 workgroup adds up itself
 constexpr int CNX_PD = 4;      // A-fragment ring depth (K16 steps in flight)
-#ifndef CNX_ABL
-#define CNX_ABL 0                // what-if builds of tools/micro/cnx_bench.hip (timing only, wrong results)
-#endif
 typedef float f32x4s_t __attribute__((ext_vector_type(4)));
 
 // hi / lo += (A6 pieces of m-tile mt) x (the resident operand tile Ys), K16 steps [k_begin, k_begin + KSL) of the image against local
@@ -105,10 +85,8 @@ __device__ __forceinline__ void cnx_mma(f32x16 (&hi)[NT], f32x16 (&lo)[NT], u32x
                 kg = k_next;
             }
             const uint4* ab = A6 + ((long)(kg + kn) * MT + mtl) * kPU4;
-            if (!(CNX_ABL & 16)) {
-                ring[u][0] = ldg_so4(ab, 16u * (unsigned)lane);
-                ring[u][1] = ldg_so4(ab, 16u * (unsigned)(64 + lane));
-            }
+            ring[u][0] = ldg_so4(ab, 16u * (unsigned)lane);
+            ring[u][1] = ldg_so4(ab, 16u * (unsigned)(64 + lane));
             // next step's B fragments (the walk's last step reads step 0 again: harmless)
             const int kb = k + 1 < KSL ? k + 1 : 0;
 #pragma unroll
@@ -169,9 +147,7 @@ __global__ __launch_bounds__((Cnx1<C, NT>::NTHR)) void cnx1_kernel(CnxArgs a) {
         Gl[i] = a.ln_g[i];
         Gl[C + i] = a.ln_b[i];
     }
-    CNX_STAMP(0);
     __syncthreads();
-    CNX_STAMP(1);
 
     // ---- depthwise conv + LayerNorm moments: thread = (column, channel class(es) v = c % 16), dwconv_ln_kernel's arithmetic ----
     const int col = NT == 2 ? lane : l31;
@@ -197,7 +173,7 @@ __global__ __launch_bounds__((Cnx1<C, NT>::NTHR)) void cnx1_kernel(CnxArgs a) {
             if (NT == 2) {
                 const float* xr = xb + (long)c * rs;                // wave-uniform row
 #pragma unroll
-                for (int j = 0; j < 7; ++j) acc = fmaf(wj[j], (CNX_ABL & 1) ? (float)tt[j] : ldg_so(xr, tt[j]), acc);
+                for (int j = 0; j < 7; ++j) acc = fmaf(wj[j], ldg_so(xr, tt[j]), acc);
             } else {
                 const char* xr = reinterpret_cast<const char*>(xb + (long)c * rs);
 #pragma unroll
@@ -209,9 +185,7 @@ __global__ __launch_bounds__((Cnx1<C, NT>::NTHR)) void cnx1_kernel(CnxArgs a) {
         }
         red[vw * NC + col] = sum;
     }
-    CNX_STAMP(2);
     __syncthreads();
-    CNX_STAMP(3);
     float tot = 0.f;
 #pragma unroll
     for (int w = 0; w < 16; ++w) tot += red[w * NC + col];
@@ -234,7 +208,6 @@ __global__ __launch_bounds__((Cnx1<C, NT>::NTHR)) void cnx1_kernel(CnxArgs a) {
     for (int w = 0; w < 16; ++w) tot2 += red[w * NC + col];
     const float var = tot2 / (float)C;
     const float rstd = 1.f / sqrtf(var + 1e-5f);
-    CNX_STAMP(4);
 
     // ---- normalise, split, operand tile: wave w rewrites the 16-channel blocks w, w + 8, ... in place (a block's fp32 values and
     // its four fragment rows per column are the same 64 * NC bytes; a wave's LDS accesses execute in order) -------------------
@@ -256,9 +229,7 @@ __global__ __launch_bounds__((Cnx1<C, NT>::NTHR)) void cnx1_kernel(CnxArgs a) {
             Ys[((i * 2 + 1) * 2 + half) * NC + col] = p2;
         }
     }
-    CNX_STAMP(5);
     __syncthreads();
-    CNX_STAMP(6);
 
     // ---- c2: every wave walks its own m-tiles; no barrier from here on ----------------------------------------------------
     const int mt_lo = blockIdx.z * a.mt_per_wg;
@@ -301,11 +272,11 @@ __global__ __launch_bounds__((Cnx1<C, NT>::NTHR)) void cnx1_kernel(CnxArgs a) {
         const int j = e >> 4;
         f32x2e v = {pend[e], pend[e + 1]};
         asm volatile("" : "+v"(v));       // pins the arithmetic to the step that stores it (free-floating, all 32 GELUs were hoisted to the top of the walk and spilled)
-        const f32x2e o = (CNX_ABL & 4) ? v : gelu_pair(v);
+        const f32x2e o = gelu_pair(v);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int r = (e + i) & 15;
-            if (!((CNX_ABL & 8) && o[i] != 1.2345f)) stg_so(hb + (long)(pmt * 32 + (r & 3) + 8 * (r >> 2)) * rs, oo[j], o[i]);
+            stg_so(hb + (long)(pmt * 32 + (r & 3) + 8 * (r >> 2)) * rs, oo[j], o[i]);
             if (j == 0) sq[r] = live[0] ? o[i] * o[i] : 0.f;
             else sq[r] = live[j] ? fmaf(o[i], o[i], sq[r]) : sq[r];
         }
@@ -340,7 +311,7 @@ __global__ __launch_bounds__((Cnx1<C, NT>::NTHR)) void cnx1_kernel(CnxArgs a) {
         for (int j = 0; j < NT; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) hi[j][r] = lo[j][r] = 0.f;
-        if (!(CNX_ABL & 2)) cnx_mma<NT, NC, KS>(hi, lo, ring, a.A6, a.MT, mt, 0, mtn, 0, Ys, lane, poster);
+        cnx_mma<NT, NC, KS>(hi, lo, ring, a.A6, a.MT, mt, 0, mtn, 0, Ys, lane, poster);
         const float cw = a.wsc[mt] * 1.f, cl = cw * kLoInv;
 #pragma unroll
         for (int j = 0; j < NT; ++j)
@@ -348,21 +319,16 @@ __global__ __launch_bounds__((Cnx1<C, NT>::NTHR)) void cnx1_kernel(CnxArgs a) {
             for (int r = 0; r < 16; ++r) pend[j * 16 + r] = comb(hi[j][r], lo[j][r], cw, cl) + bv[r];
         pmt = mt;
     };
-    [[maybe_unused]] int stamp = 7;
     {
         CnxNoPost none;
         walk(none);
     }
-    CNX_STAMP(stamp);
     while (mt + WAVES < mt_hi) {
         mt += WAVES;
         walk(post);
-        ++stamp;
-        CNX_STAMP(stamp);
     }
 #pragma unroll
     for (int e = 0; e < NPEND; e += 2) finish2(e);
-    CNX_STAMP(12);
 }
 
 template <int C, int KPASS>
@@ -428,7 +394,7 @@ __global__ __launch_bounds__((Cnx2<C, KPASS>::NTHR)) void cnx2_kernel(CnxArgs a)
         for (int i = 0; i < XPER; ++i) {
             const int gg = pass * CF::GPP + wave + i * WAVES;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) xr[i][q] = (CNX_ABL & 32) ? (float)(gg + q) : ldg_so(hb + (long)(8 * gg + q) * rs, so);
+            for (int q = 0; q < 8; ++q) xr[i][q] = ldg_so(hb + (long)(8 * gg + q) * rs, so);
         }
     };
     auto deposit = [&](int pass) __attribute__((always_inline)) {
@@ -503,14 +469,14 @@ __global__ __launch_bounds__((Cnx2<C, KPASS>::NTHR)) void cnx2_kernel(CnxArgs a)
 #pragma unroll
             for (int r = 0; r < 16; ++r) hi[j][r] = lo[j][r] = 0.f;
         if (KPASS == 1) {
-            if (!(CNX_ABL & 2)) cnx_mma<NT, NC, KSL>(hi, lo, ring, a.A6, a.MT, mt, 0, mtn, 0, Ys, lane);
+            cnx_mma<NT, NC, KSL>(hi, lo, ring, a.A6, a.MT, mt, 0, mtn, 0, Ys, lane);
         } else {
-            if (has && !(CNX_ABL & 2)) cnx_mma<NT, NC, KSL>(hi, lo, ring, a.A6, a.MT, mt, 0, mt, KSL, Ys, lane);
+            if (has) cnx_mma<NT, NC, KSL>(hi, lo, ring, a.A6, a.MT, mt, 0, mt, KSL, Ys, lane);
             slab_barrier();                                         // every wave is done with the first K half
             deposit(1);
             slab_barrier();
             if (!has) break;
-            if (!(CNX_ABL & 2)) cnx_mma<NT, NC, KSL>(hi, lo, ring, a.A6, a.MT, mt, KSL, mt, KSL, Ys, lane);
+            cnx_mma<NT, NC, KSL>(hi, lo, ring, a.A6, a.MT, mt, KSL, mt, KSL, Ys, lane);
         }
         // epilogue: EpiBias<ACT_NONE, true> (bias' = c3.bias + c3.weight . grn.beta), residual = the layer's input, in place
         const float cw = a.wsc[mt] * sx.inv, cl = cw * kLoInv;
@@ -536,7 +502,7 @@ __global__ __launch_bounds__((Cnx2<C, KPASS>::NTHR)) void cnx2_kernel(CnxArgs a)
                 mx = fmaxf(mx, fabsf(o));
             }
             // (in place: only the column's own lane stores - a clamped lane of the second n-tile would re-read a column the first n-tile has already updated)
-            if (n < tw && !((CNX_ABL & 8) && res[0] != 1.2345f)) {
+            if (n < tw) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) stg_so(xb + (long)(mt * 32 + (r & 3) + 8 * (r >> 2)) * rs, oo, res[r]);
                 mx_out = fmaxf(mx_out, mx);

@@ -4,7 +4,7 @@
 // two thirds of the time.  Here a persistent 8-wave workgroup loads the conv's 36 weight pieces (and FiLM's 24) once, stages
 // the whole 48-channel halo tile of 128 samples in one go and then issues the tile's 27 (+18) MFMAs per wave back to back:
 // one staging round trip and two barriers per tile instead of per slab.  Two-term fp16 split, accumulator pairs and the
-// block-floating-point guard as in conv3s.h.
+// block-floating-point guard as in split_fp16.h.
 //   weights   the same pre-split images as conv3s (PackedW::A6: [K16 step = slab*3 + tap][m-tile][part][lane][8 fp16];
 //             stacked FiLM image [slab][scale mt0, mt1, shift mt0, mt1][part]) - no new packing;
 //   input     Xs[part][8-channel group (6)][position][8 fp16]: lrelu (and, for c1, F.interpolate) applied while depositing;
@@ -12,8 +12,8 @@
 //             B-fragment order and are split in registers; (conv, scale, shift) combine in registers;
 //   epilogue  bias / FiLM / residual (direct, or F.interpolate of the low-rate tensor evaluated in place), 128-byte runs
 //             per row and store instruction; residual and cond are requested before the MFMAs.
-#include "conv3s.h"
 #include "small_kernels.h"
+#include "split_fp16.h"
 #include "tvc_common.h"
 
 namespace tvc {
@@ -66,7 +66,7 @@ struct Conv48Args {
     const float* wsc;      // per-m-tile power-of-two scales of the images: conv [2], FiLM [4] (scale mt0, mt1, shift mt0, mt1), c5 [1]
     const float* fsc;
     const float* w5sc;
-    // block-floating-point guard (conv3s.h): per-utterance |max| slots of x / cond (read, nullable) and of the output (written, nullable)
+    // block-floating-point guard (split_fp16.h): per-utterance |max| slots of x / cond (read, nullable) and of the output (written, nullable)
     const float* amax_x;
     const float* amax_c;
     float* amax_y;
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(kNT48) __attribute__((amdgpu_waves_per_eu(FILM ? 2 
     };
 
     // persistent: a contiguous range of tiles per workgroup (one or two utterances: the output's |max| slot is published once
-    // per utterance and workgroup, conv3s.h amax_flush_wg)
+    // per utterance and workgroup, split_fp16.h amax_flush_wg)
     int tile, tend;
     tile_range(a.ntiles, tile, tend);
     if (tile >= tend) return;

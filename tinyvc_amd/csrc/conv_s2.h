@@ -12,7 +12,8 @@
 // instructions between the queued MFMAs.  The output tile leaves straight from the accumulators (no LDS park: the two staging
 // buffers take its place), 128 contiguous bytes per row and store instruction.
 #pragma once
-#include "conv3s.h"
+#include "small_kernels.h"
+#include "split_fp16.h"
 
 namespace tvc {
 
@@ -26,7 +27,7 @@ struct ConvS2Args {
     float* y;              // [B][M][len]
     const float* bias;
     int M, tiles_per_utt, ntiles, mblocks;
-    const float* amax_x;   // per-utterance |max| slots (conv3s.h): input (read, nullable), output (written, nullable)
+    const float* amax_x;   // per-utterance |max| slots (split_fp16.h): input (read, nullable), output (written, nullable)
     float* amax_y;
     // PRE: the output is written as the NEXT conv's ready operand (film_s2.h: split(lrelu(y) * 2^k) as two fp16 planes
     // [B][part][M / 8][len][8 fp16], k from the analytic bound pre_w * |x|max + pre_b >= |y|, which both kernels evaluate alike)

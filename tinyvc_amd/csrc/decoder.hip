@@ -191,7 +191,7 @@ static __global__ __launch_bounds__(256) void noise_ola_kernel(const float* __re
 // =================================================================================================
 // SourceNet + dsp
 // =================================================================================================
-// cmax: per-utterance |max| slot of `content` (block-floating-point guard of the fp16 split, conv3s.h)
+// cmax: per-utterance |max| slot of `content` (block-floating-point guard of the fp16 split, split_fp16.h)
 static int run_source_net(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* content, const float* f0,
                           const float* energy, float* amps, float* kern, int B, int T, const float* cmax, float* xmax_zeroed, hipEvent_t amps_ready = nullptr) {
     const int ncols = B * T;
@@ -573,9 +573,3 @@ int run_decoder(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* content, const
 }
 
 }  // namespace tvc
-
-#ifdef S_TRACE
-extern "C" int tvc_debug_trace_dec(unsigned long long* host) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(tvc::g_trace), sizeof(tvc::g_trace)) == hipSuccess ? 0 : -1;
-}
-#endif

@@ -279,16 +279,14 @@ int run_convnext(tvc_ctx* ctx, hipStream_t s, Ws& ws, const ConvNeXtW& w, float*
     const int Tlong = ctx->rag ? ctx->rag->Tlong : T;
     float* gx = ws.get<float>((size_t)NB * C2 * ((Tlong + 63) / 64));      // row norms; the fused launches keep one sum of squares per 64-column tile
     float* nx = ws.get<float>((size_t)NB * C2);
-    float* ymax = ws.get<float>((size_t)NB);      // |max| slots of the two 1x1s' inputs (block-floating-point guard, conv3s.h)
+    float* ymax = ws.get<float>((size_t)NB);      // |max| slots of the two 1x1s' inputs (block-floating-point guard, split_fp16.h)
     float* hmax = ws.get<float>((size_t)NB);
     ws.release(mk);
     if (ws.dry) return 0;
-#ifndef TVC_CNX_OLD
     {
         int rc = 0;
         if (C == 384 ? cnx_try<384>(&rc, ctx, s, w, x, h, gx, B, T, amax_out) : (C == 128 && cnx_try<128>(&rc, ctx, s, w, x, h, gx, B, T, amax_out))) return rc;
     }
-#endif
     {
         TVC_CHECK(dwconv_ln_launch<true>(ctx, s, x, y, w.dw_w, w.dw_b, w.ln_g, w.ln_b, B, C, T, w.dilation));
     }
@@ -426,7 +424,7 @@ int run_encoder(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* spec, float* s
     float* xs = ws.get<float>((size_t)B * kSslCh * T);
     float* xp = ws.get<float>((size_t)B * kPitchCh * T);
     float* lg = logits ? logits : ws.get<float>((size_t)B * kPitchClasses * T);
-    // |max| slots (block-floating-point guard of the fp16 split, conv3s.h): the spectrogram and the two residual streams the output
+    // |max| slots (block-floating-point guard of the fp16 split, split_fp16.h): the spectrogram and the two residual streams the output
     // projections read; the ConvNeXt layers keep their own (run_convnext)
     const int NB = ctx->rag ? ctx->rag->B : B;      // utterances (ragged batch: B = 1, T = all frames)
     float* slots = zeroed_slots ? zeroed_slots : ws.get<float>((size_t)3 * NB);
@@ -477,9 +475,3 @@ int run_encoder(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* spec, float* s
 }
 
 }  // namespace tvc
-
-#ifdef S_TRACE
-extern "C" int tvc_debug_trace_enc(unsigned long long* host) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(tvc::g_trace), sizeof(tvc::g_trace)) == hipSuccess ? 0 : -1;
-}
-#endif

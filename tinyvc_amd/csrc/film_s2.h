@@ -17,8 +17,8 @@
 // K = 3 * 384 below 2^40.  Error against fp64 on N(0,1) operands, K = 768: 3.1e-7 rel rms at every input scale from 1e-7 to 1e5 (accumulator
 // pairs: 1.9e-7, fp32 MFMA: 4.9e-7, bf16 x 3: 4.2e-7; tools/micro/f16split.hip, profiles/r03_f16split.txt).  The slots this kernel reads are exact maxima written by the producing kernels' epilogues.
 #pragma once
-#include "conv3s.h"
 #include "conv_s2.h"
+#include "split_fp16.h"
 
 namespace tvc {
 

@@ -1,6 +1,6 @@
 // The fused 24-channel full-rate block (FilterNet ups[4] + output_layer, decoder.py:173-190,220,233): every conv / FiLM 1x1
 // runs on v_mfma_f32_32x32x16_f16 with both operands split into two fp16 parts (three part-products into an accumulator
-// pair, fp32-equivalent accuracy, block-floating-point range guard: conv3s.h).
+// pair, fp32-equivalent accuracy, block-floating-point range guard: split_fp16.h).
 //
 //   half A:  x_up = interp(x, x5) -> lrelu -> c1(d1) -> lrelu -> c2(d3) -> FiLM1(cond) -> + x_up          => x1
 //   half B:  x1 -> lrelu -> c3(d9) -> lrelu -> c4(d27) -> FiLM2(cond) -> + x1 -> [c5 . output k7 folded]   => wave
@@ -17,9 +17,9 @@
 //           (cond fragments are loaded from HBM straight into B-fragment order and split in registers).
 //   HBM     per tile: input tile + halo and cond in, one tile out; the next tile's input is in flight in registers
 //           across the whole tile (raw s_barrier: __syncthreads would wait for it).
-#include "conv3s.h"
 #include "conv_s2.h"
 #include "small_kernels.h"
+#include "split_fp16.h"
 #include "tvc_common.h"
 
 namespace tvc {
@@ -60,7 +60,7 @@ struct Up24SArgs {
     const u32x4* img;    // weight blob (pack.hip up24s_half, layout Up24sBlob)
     int len, xf, tiles_per_utt, ntiles;
     float interp_scale;
-    // block-floating-point guard (conv3s.h): per-utterance |max| slots of x / of the tensor cond was computed from (read, nullable) and of `out` (half A: written, nullable)
+    // block-floating-point guard (split_fp16.h): per-utterance |max| slots of x / of the tensor cond was computed from (read, nullable) and of `out` (half A: written, nullable)
     const float* amax_x;
     const float* amax_c;
     float* amax_y;
@@ -124,23 +124,6 @@ __device__ __forceinline__ void conv24_phase(f32x16& hi, f32x16& lo, const u32x4
     }
 }
 
-#ifdef U24_TRACE
-// diagnostic build only (tools/micro/u24_trace.py): s_memtime stamps of waves 0, 1, 4, 7 of workgroup U24_TRACE over its first tiles, [half][wave slot][64]
-static __device__ unsigned long long g_u24_trace[2 * 4 * 64];
-#define U24_STAMP(id)                                                                                  \
-    do {                                                                                               \
-        __builtin_amdgcn_sched_barrier(0);                                                             \
-        if (tr_on && tr_n < 60) {                                                                      \
-            unsigned long long t_;                                                                     \
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");              \
-            g_u24_trace[((CF::SECOND ? 1 : 0) * 4 + tr_slot) * 64 + 1 + tr_n++] = (t_ << 8) | (unsigned)(id); \
-        }                                                                                              \
-        __builtin_amdgcn_sched_barrier(0);                                                             \
-    } while (0)
-#else
-#define U24_STAMP(id) do {} while (0)
-#endif
-
 template <class CF, bool RAG>
 __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE))) void up24s_kernel(Up24SArgs a) {
     constexpr int C = CF::C, W = CF::W, D1 = CF::D1, D2 = CF::D2, H = CF::H, E = CF::E, NT = CF::NT;
@@ -153,11 +136,6 @@ __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE
     float* R = Fl + CF::FL;                                       // [24][PS]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, lh = lane >> 5;
-#ifdef U24_TRACE
-    const int tr_slot = wave == 0 ? 0 : (wave == 1 ? 1 : (wave == 4 ? 2 : 3));
-    const bool tr_on = (int)blockIdx.x == U24_TRACE && lane == 0 && (wave == 0 || wave == 1 || wave == 4 || wave == 7);
-    int tr_n = 0;
-#endif
     const int rs = a.len;                                  // row stride of cond / x1 (= every utterance's length unless RAG)
     const int rsl = CF::SECOND ? rs : rs / a.xf;           // row stride of the input x
     int bh = 0;                                            // RAG: utterance hint of the table walk
@@ -198,14 +176,7 @@ __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE
             p = p < 0 ? 0 : (p > len - 1 ? len - 1 : p);
             const int g = ig8[i] >> 3;
             if (CF::SECOND) {
-#ifdef X1_PLANAR
-                const float* xp = RAG ? a.x + rt.off : a.x + (long)rt.b * C * rsl;
-                const unsigned o = 4u * (unsigned)(ig8[i] * rsl + p);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) xr0[i][j] = ldg_so(xp + (long)j * rsl, o);
-#else
                 ld8(xr0[i], 32u * (unsigned)(g * rsl + p));
-#endif
             } else {
                 const Lerp lc = lerp_coord(p, a.interp_scale, lin);
                 lam[i] = lc.w1;
@@ -243,7 +214,7 @@ __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE
     };
 
     // persistent: a contiguous range of tiles per workgroup (one or two utterances: x1's |max| slot is published once per
-    // utterance and workgroup, conv3s.h amax_flush_wg)
+    // utterance and workgroup, split_fp16.h amax_flush_wg)
     int tile, tend;
     tile_range(a.ntiles, tile, tend);
     if (tile < tend) {
@@ -259,7 +230,6 @@ __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE
     Bfp sx{1.f, 1.f}, sc{1.f, 1.f}, sh_{1.f, 1.f};
 
     for (; tile < tend; ++tile) {
-        U24_STAMP(0);
         const RagTile rt = rag_tile<RAG>(a.rag, tile, a.tiles_per_utt, rs, bh);
         const int b = rt.b, len = rt.len;
         bh = b;
@@ -305,7 +275,6 @@ __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE
                 cq[1][p] = ldg_so4(cb + (long)(3 * p + 2) * rs, o1);
             }
         }
-        U24_STAMP(1);
 
         // ---- S1: Hs = split(lrelu(conv_a(lrelu(x)) + ba)) ---------------------------------------------
         // The next tile's input is requested behind the wave's first group of MFMAs: the loads are independent of everything in this
@@ -345,9 +314,7 @@ __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE
             }
         }
         if (!fetched && next < tend) fetch(next);
-        U24_STAMP(2);
         slab_barrier();
-        U24_STAMP(3);
 
         // ---- S2: (conv_b(Hs) + bb) * scale + shift + res ------------------------------------------------
         if (wave < CF::NT2) {
@@ -423,10 +390,8 @@ __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE
             keep_live = !CF::SECOND && n < W && t < len;
             keep_oo = 32u * (unsigned)t + 16u * (unsigned)lh;
         }
-        U24_STAMP(4);
         if (CF::SECOND) {
             slab_barrier();
-            U24_STAMP(5);
             // ---- S4: c5 and output_layer folded into one Conv1d(24 -> 1, k7, replicate) on the parked x2 tile ----
             // 8 lanes per group of 4 consecutive outputs, 3 channels each: per channel 10 activations and 7
             // (broadcast) weights feed 28 FMAs; the 8 partial sums meet through three shuffles.
@@ -480,9 +445,7 @@ __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE
             }
         }
         // ---- next tile's input: registers -> LDS ----------------------------------------------------------
-        U24_STAMP(6);
         slab_barrier();                                   // every wave is done with Xs, Hs and R
-        U24_STAMP(7);
         if (next < tend) {
             const int bn = utt(next);
             deposit(bn == slot_b ? sx.s : bfp_load_u(a.amax_x, bn).s);
@@ -495,12 +458,8 @@ __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE
 #pragma unroll
             for (int g = 0; g < 3; ++g) stg_so4(ob + (long)g * 8 * rs, keep_oo, keep[g]);
         }
-        U24_STAMP(8);
         slab_barrier();
     }
-#ifdef U24_TRACE
-    if (tr_on) g_u24_trace[((CF::SECOND ? 1 : 0) * 4 + tr_slot) * 64] = (unsigned long long)tr_n;
-#endif
     if (!CF::SECOND && a.amax_y && tend > (int)((long)a.ntiles * blockIdx.x / gridDim.x)) amax_flush_wg(a.amax_y + mx_b, mx_run, Fl + Up24sBlob::FLOATS);
 }
 
@@ -530,14 +489,6 @@ static int launch_up24s(tvc_ctx* ctx, hipStream_t s, Up24SArgs a, int B) {
     else hipLaunchKernelGGL((up24s_kernel<CF, false>), dim3(grid), dim3(CF::NT), lds, s, a);
     return launch_check(ctx, "up24s");
 }
-
-#ifdef U24_TRACE
-}  // namespace tvc
-extern "C" int tvc_debug_trace_u24(unsigned long long* host) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(tvc::g_u24_trace), sizeof(tvc::g_u24_trace)) == hipSuccess ? 0 : -1;
-}
-namespace tvc {
-#endif
 
 constexpr int U24S_WA = 250, U24S_WB = 250;     // output samples per tile of the two halves (196 / 218 for the second half - one round of first-conv tiles instead of two - measured 8 % slower: the halo dominates)
 
@@ -587,7 +538,7 @@ struct Down0SArgs {
     float* y2;             // optional, G8 layout [B][3][L / 5][8]: F.interpolate(out, scale_factor = 1/5) = the sample at 5 d + 2
     const u32x4* img;      // weight blob (pack.hip down0s, layout Down0sBlob)
     int len, tiles_per_utt, ntiles;
-    const float* amax_x;   // per-utterance |max| of cat[source, energy] (block-floating-point guard, conv3s.h), nullable
+    const float* amax_x;   // per-utterance |max| of cat[source, energy] (block-floating-point guard, split_fp16.h), nullable
     float* amax_y;         // ... of the output (written), nullable
     RagDev rag;            // RAG kernels (ragged.h): `len` = row stride of the batch-wide tensors, tiles / extents from the table
 };
@@ -638,7 +589,7 @@ static __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4)))
         }
     };
 
-    int tile, tend, cur = 0;                             // a contiguous range of tiles per workgroup (amax_flush_wg, conv3s.h)
+    int tile, tend, cur = 0;                             // a contiguous range of tiles per workgroup (amax_flush_wg, split_fp16.h)
     tile_range(a.ntiles, tile, tend);
     if (tile >= tend) return;
     bh = utt(tile);

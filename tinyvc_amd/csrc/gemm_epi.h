@@ -5,8 +5,6 @@
 
 namespace tvc {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 enum { ACT_NONE = 0, ACT_GELU = 1, ACT_ELU1 = 2 };
 
 // erf(a): two fma chains and one expf, both evaluated and selected (no branch): |a| <= 0.9277: a + a P(a^2), above: 1 - exp(Q(|a|)) (N. Juffa's

@@ -2,7 +2,7 @@
 //
 // Same arithmetic, weight image and epilogue functors as the TAPS = 1 launches of conv3s.h (two fp16 parts per fp32
 // operand, three part-products per product into an accumulator pair), different schedule.  The cycle stamps
-// of conv3s's slab loop (tools/micro/slab_trace.py) showed its two halves - stage a slab (wait for the loads, split,
+// of conv3s's slab loop (round 2, profiles/r02_slab_stamps.txt) showed its two halves - stage a slab (wait for the loads, split,
 // ds_write, request the next slab: ~1850 cycles) and multiply it (~1840 cycles, matrix-pipe bound) - strictly
 // alternating between two barriers, so the matrix pipe idles half of the time.  Here
 //   * the LDS staging area is double-buffered and a slab costs ONE barrier: while slab u multiplies out of buffer
@@ -20,8 +20,8 @@
 //   * GRN's per-(utterance, channel) factors travel with the slab (two 16-byte loads per staged item), so a flat
 //     column tile may straddle any number of utterances.
 #pragma once
-#include "conv3s.h"
 #include "gemm_epi.h"
+#include "split_fp16.h"
 
 namespace tvc {
 
@@ -210,12 +210,6 @@ __global__ __launch_bounds__(2 * NWV * 64) void gemm_s2_kernel(Gemm2Args a, Epi 
             for (int j = 0; j < WN; ++j) lo[i][j] = TVC_MFMA16(af[i][0], bf[j][1], lo[i][j]);
     };
 
-#ifdef S_TRACE
-    struct { unsigned long long* tr = nullptr; int trn = 0; } trs;
-    __shared__ unsigned long long tr_lds[256];
-    if (blockIdx.x == S_TRACE_WG && threadIdx.x == S_TRACE_TID) trs.tr = tr_lds;
-#endif
-
     issue_load();                 // unit 0
     advance_load();
     lstore(0);
@@ -224,15 +218,10 @@ __global__ __launch_bounds__(2 * NWV * 64) void gemm_s2_kernel(Gemm2Args a, Epi 
     slab_barrier();
     int buf = 0;
     while (true) {
-        TR_STAMP(trs, 0);
         multiply(buf, 0);
-        TR_STAMP(trs, 1);
         lstore(buf ^ 1);          // unit u + 1 -> the other buffer
-        TR_STAMP(trs, 2);
         issue_load();             // unit u + 2
-        TR_STAMP(trs, 3);
         multiply(buf, 1);
-        TR_STAMP(trs, 4);
         advance_load();           // (behind the MFMAs: the slab body above is one basic block)
         if (++cs == nslab) {
             // epilogue straight from the accumulators (gemm_epi.h functors finish the element)
@@ -260,20 +249,8 @@ __global__ __launch_bounds__(2 * NWV * 64) void gemm_s2_kernel(Gemm2Args a, Epi 
             coords(cv, cmt0, cn0);
         }
         slab_barrier();           // buffer buf ^ 1 is complete, and nobody reads buffer buf any more
-        TR_STAMP(trs, 5);
         buf ^= 1;
     }
-#ifdef S_TRACE
-    if (trs.tr) {
-        const unsigned slot = atomicAdd(&g_trace_slot, 1u) & 63u;
-        unsigned long long* g = g_trace + slot * 256;
-        g[0] = 0x5452414345000000ull | (2ull << 20) | ((unsigned long long)NWV << 16) | ((unsigned long long)WN << 12) | ((unsigned long long)SCALED << 8);
-        g[1] = ((unsigned long long)a.Cin << 32) | (unsigned)trs.trn;
-        g[2] = ((unsigned long long)gridDim.x << 32) | (unsigned)(a.ncoltiles * a.mblocks);
-        g[3] = 0;
-        for (int i = 0; i < trs.trn; ++i) g[4 + i] = trs.tr[i];
-    }
-#endif
 }
 
 template <int NWV, int WN, class Epi, bool SCALED>

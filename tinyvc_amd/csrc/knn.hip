@@ -19,8 +19,8 @@
 // Tie-break: equal similarities -> lower index first (torch.topk leaves it unspecified).
 #include <hip/hip_fp16.h>
 
-#include "conv3s.h"
 #include "small_kernels.h"
+#include "split_fp16.h"
 #include "tvc_common.h"
 
 namespace tvc {
@@ -42,9 +42,7 @@ __host__ __device__ inline const uint4* blob_img16(const float* blob, int kind, 
 __host__ __device__ inline const float* blob_invmax(const float* blob, long Npad) {      // fp16 kind only
     return blob + HDR + Npad + (size_t)Npad * KD / 2;
 }
-#ifndef KNN_BLOCKS
-#define KNN_BLOCKS 1024   // target workgroup count (query tiles x index splits)
-#endif
+constexpr int KNN_BLOCKS = 1024;   // target workgroup count (query tiles x index splits)
 
 static inline int64_t npad128(int64_t N) { return (N + 127) / 128 * 128; }
 
@@ -130,7 +128,7 @@ static __global__ __launch_bounds__(256) void index_prepare_f16_kernel(const __h
 }
 
 // header[4] = the largest |value| of the index: `matched` (the mean of four of its rows) is bounded by it, so the conversion takes the
-// |max| slot of the decoder's content input from here instead of a pass over the tensor (block-floating-point guard, conv3s.h)
+// |max| slot of the decoder's content input from here instead of a pass over the tensor (block-floating-point guard, split_fp16.h)
 template <class T>
 static __global__ __launch_bounds__(256) void index_amax_kernel(const T* __restrict__ p, long n, float* __restrict__ slot) {
     __shared__ float red[4];
@@ -413,11 +411,7 @@ __device__ __forceinline__ void knn_topk_body(const float* __restrict__ blob, lo
 #pragma unroll
             for (int p = 0; p < NP; ++p) af[i][p] = __builtin_bit_cast(bf16x8, as[(i * NP + p) * 64]);
         // part-products, least significant first: (index part, query part)
-#ifdef KNN_NQ_TEST
-        constexpr int NQ = KNN_NQ_TEST;      // timing experiment only (wrong results): fewer part-products
-#else
         constexpr int NQ = F16 ? 5 : 6;
-#endif
         constexpr int PA3[6] = {2, 1, 0, 1, 0, 0}, PB3[6] = {0, 1, 2, 0, 1, 0};
         constexpr int PA2[5] = {1, 0, 1, 0, 0}, PB2[5] = {1, 2, 0, 1, 0};
 #pragma unroll
@@ -655,9 +649,7 @@ constexpr int C_CAP = 256;                                                     /
 // range), fp32 accumulation of 768 exact products (<= 768 * 2^-24), the rescoring's own rounding (< 1e-6):
 // 2^-10 * 1.01 + 768 * 2^-25 + 768 * 2^-24 + 1e-6 < 1.06e-3; C_EPS leaves a margin.
 constexpr float C_EPS = 1.25e-3f;
-#ifndef KNN_COARSE_MIN
-#define KNN_COARSE_MIN 4096
-#endif
+constexpr int KNN_COARSE_MIN = 4096;   // index size from which the two-stage search runs
 
 struct Top4V {   // four largest values
     float v[4];
@@ -754,11 +746,6 @@ static __device__ __forceinline__ void knn_coarse_body(const float* __restrict__
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-#ifdef S_TRACE
-    struct { unsigned long long* tr = nullptr; int trn = 0; } trs;
-    __shared__ unsigned long long tr_lds[256];
-    if (MODE == 1 && blockIdx.x == S_TRACE_WG && threadIdx.x == S_TRACE_TID) trs.tr = tr_lds;
-#endif
     if (G > 0) {
         gload(0);
         lstore(0);
@@ -767,12 +754,10 @@ static __device__ __forceinline__ void knn_coarse_body(const float* __restrict__
     }
     for (int g = 0; g < G; ++g) {
         const int cur = g & 1;
-        TR_STAMP(trs, 0);
         // no branch around the staging: past the end it re-stages the last step into the idle buffer (harmless), and the
         // compiler is free to thread the stores and loads between this step's MFMAs
         lstore(cur ^ 1);
         gload(g + 2 < G ? g + 2 : G - 1);
-        TR_STAMP(trs, 1);
         const uint4* as = As + cur * C_A_U4 + wm * (4 * 64) + lane;
         const uint4* xs = Xs + cur * C_X_U4 + lh * C_QT + wn * 64 + l31;
 #pragma unroll
@@ -787,7 +772,6 @@ static __device__ __forceinline__ void knn_coarse_body(const float* __restrict__
 #pragma unroll
                 for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bf[j], acc[i][j], 0, 0, 0);
         }
-        TR_STAMP(trs, 2);
         const int st = g - (g / C_STEPS) * C_STEPS;
         if (st == C_STEPS - 1) {
             const int t2 = t_lo + g / C_STEPS;
@@ -857,21 +841,8 @@ static __device__ __forceinline__ void knn_coarse_body(const float* __restrict__
                     for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
                 }
         }
-        TR_STAMP(trs, 3);
         slab_barrier();
-        TR_STAMP(trs, 4);
     }
-#ifdef S_TRACE
-    if (trs.tr) {
-        const unsigned slot = atomicAdd(&g_trace_slot, 1u) & 63u;
-        unsigned long long* gt = g_trace + slot * 256;
-        gt[0] = 0x5452414345000000ull | (9ull << 20) | ((unsigned long long)F16 << 8);
-        gt[1] = ((unsigned long long)G << 32) | (unsigned)trs.trn;
-        gt[2] = ((unsigned long long)gridDim.x << 32) | (unsigned)nsplit;
-        gt[3] = 0;
-        for (int i = 0; i < trs.trn; ++i) gt[4 + i] = trs.tr[i];
-    }
-#endif
     if (MODE == 1) return;
 
     // merge the 4 partial lists (wm x lh) of every query through LDS, write this split's four largest coarse values
@@ -1228,9 +1199,3 @@ int run_knn(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const float* 
 }
 
 }  // namespace tvc
-
-#ifdef S_TRACE
-extern "C" int tvc_debug_trace_knn(unsigned long long* host) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(tvc::g_trace), sizeof(tvc::g_trace)) == hipSuccess ? 0 : -1;
-}
-#endif

@@ -26,7 +26,7 @@ int pad_m(int M) {
     return (M + 127) / 128 * 128;
 }
 
-// ---- two-part fp16 split of the packed weights (conv3s.h): w = (h1 + 2^-11 h2) * 2^e, e per 32-row m-tile -------------------
+// ---- two-part fp16 split of the packed weights (split_fp16.h): w = (h1 + 2^-11 h2) * 2^e, e per 32-row m-tile -------------------
 uint16_t f16_bits(float f) {
     const _Float16 h = (_Float16)f;          // round to nearest even, subnormals kept
     uint16_t u;

@@ -344,7 +344,7 @@ struct FilterTaps {   // optional copies of FilterNet's block outputs (tvc_filte
     float* ups[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 // cmax / smax / the trailing float* of run_dsp: per-utterance |max| slots of content / cat[source, energy] (block-floating-point
-// guard of the fp16 split, conv3s.h); nullptr = the stage computes (or keeps) its own
+// guard of the fp16 split, split_fp16.h); nullptr = the stage computes (or keeps) its own
 int run_filter(tvc_ctx*, hipStream_t, Ws&, const float* content, const float* f0, const float* energy,
                const float* source, float* wave, int B, int T, const FilterTaps* taps = nullptr, const float* cmax = nullptr, const float* smax = nullptr,
                float* zeroed_slots = nullptr, bool x_slot_set = false, float* x_pre = nullptr, bool x_pre_filled = false);      // zeroed_slots: kFilterSlots x utterances floats the caller has already zeroed on this
@@ -371,7 +371,7 @@ int run_prepare_index(tvc_ctx*, hipStream_t, const float* index, float* prepared
 int run_prepare_index_f16(tvc_ctx*, hipStream_t, const void* rows_f16, float* prepared, int64_t N);
 
 // fused FilterNet kernels (filter_up24s.hip, conv48s.hip)
-// (the amax_* arguments are the per-utterance |max| slots of the block-floating-point guard, conv3s.h)
+// (the amax_* arguments are the per-utterance |max| slots of the block-floating-point guard, split_fp16.h)
 // skips[0] travels as the FiLM 1x1s' ready operand (two fp16 planes, scaled by the bound cbw |max of downs.0's input| + cbb): run_down0_split writes
 // it (out_fp32: optional fp32 copy for the parity taps), run_up24_split reads it (amax_c = the slot of downs.0's INPUT)
 int run_up24_split(tvc_ctx*, hipStream_t, const UpW& u, const float* x, const float* cond_planes, float cbw, float cbb, float* x1, float* out, int B, int len,
