@@ -89,6 +89,10 @@ int tvc_ctx_create(int hip_device, tvc_ctx** out) {
         }
         ab.resolve(c->const_arena);
     }
+    if (hipDeviceGetAttribute(&c->ncu, hipDeviceAttributeMultiprocessorCount, hip_device) != hipSuccess) {
+        tvc_ctx_destroy(c);
+        return TVC_ERR_HIP;
+    }
     // the side stream carries the pitch estimator beside the SSL trunk (encoder.hip): lowest priority, so that its workgroups take the
     // slots the trunk's launches leave free instead of competing with them (the pitch chain has ~150 us of slack)
     int prio_least = 0, prio_greatest = 0;

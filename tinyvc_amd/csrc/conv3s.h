@@ -965,15 +965,8 @@ inline int conv3s_launch_t(tvc_ctx* ctx, hipStream_t s, const PackedW& w, const 
                            const float* kscale = nullptr, bool flat = false, int cmax = 0, int lin = 0, float lscale = 0.f, const BfpSlots& bfp = {}) {
     if (Cin % (16 * TL::KG) != 0 || (FILM && Ccond % (16 * TL::KG) != 0)) return fail(ctx, TVC_ERR_ARG, "conv3s: channel counts must be multiples of the slab depth");
     if (Cin / 16 > w.S6) return fail(ctx, TVC_ERR_ARG, "conv3s: weight image has fewer K16 steps than the launch walks");
-    static bool ready_dev[64] = {};                 // the attribute is per (function, device): one flag per device of this process
-    bool& ready = ready_dev[ctx->device & 63];
     constexpr int lds = TL::lds_bytes(TAPS);
-    if (!ready) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv3s_kernel<TL, TAPS, LRELU, Epi, FILM, SCALED, LERP, CLAMP>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return fail(ctx, TVC_ERR_HIP, "conv3s setup: %s", hipGetErrorString(e));
-        ready = true;
-    }
+    TVC_CHECK((lds_optin<conv3s_kernel<TL, TAPS, LRELU, Epi, FILM, SCALED, LERP, CLAMP>>(ctx, lds, "conv3s")));
     ConvSArgs a;
     a.A6 = reinterpret_cast<const uint4*>(w.A6);
     a.wsc = w.wscale;
@@ -1017,27 +1010,14 @@ inline int conv3s_launch_t(tvc_ctx* ctx, hipStream_t s, const PackedW& w, const 
         a.Ccond = Ccond;
     }
     a.ntiles = (a.MT / TL::MTB) * a.tiles_per_utt * B;
-    static int ncu_dev[64] = {};
-    int& ncu = ncu_dev[ctx->device & 63];
-    if (!ncu) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) return fail(ctx, TVC_ERR_HIP, "conv3s: device properties");
-        ncu = prop.multiProcessorCount;
-    }
-    const int slots = ncu * bpc;        // persistent: one resident workgroup per slot walks a contiguous range of the tiles
+    const int slots = ctx->ncu * bpc;        // persistent: one resident workgroup per slot walks a contiguous range of the tiles
     if (ctx->rag) {
         // ragged batch (ragged.h): the driver passed B = 1 and len = the batch's columns at this rate (= the row stride)
         if constexpr (!LERP && !SCALED && !(FILM && TL::WN > 1)) {
-            if (B != 1 || flat || a.len % ctx->rag->Ttot != 0) return fail(ctx, TVC_ERR_STATE, "conv3s: a ragged batch runs as one long utterance");
-            static bool ready_rag[64] = {};
-            bool& rr = ready_rag[ctx->device & 63];
-            if (!rr) {
-                hipError_t e = hipFuncSetAttribute((const void*)conv3s_kernel<TL, TAPS, LRELU, Epi, FILM, SCALED, LERP, CLAMP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                if (e != hipSuccess) return fail(ctx, TVC_ERR_HIP, "conv3s setup: %s", hipGetErrorString(e));
-                rr = true;
-            }
+            if (flat) return fail(ctx, TVC_ERR_STATE, "conv3s: a ragged batch runs as one long utterance");
             int ncol = a.tiles_per_utt;
-            TVC_CHECK(rag_view(ctx, s, a.len / ctx->rag->Ttot, Epi::kIgemm ? 0 : TL::BN, &a.rag, Epi::kIgemm ? nullptr : &ncol));
+            TVC_CHECK(rag_tiles(ctx, s, B, a.len, Epi::kIgemm ? 0 : TL::BN, &a.rag, &ncol, "conv3s"));
+            TVC_CHECK((lds_optin<conv3s_kernel<TL, TAPS, LRELU, Epi, FILM, SCALED, LERP, CLAMP, true>>(ctx, lds, "conv3s")));
             a.ntiles = (a.MT / TL::MTB) * ncol;
             dim3 g((unsigned)(a.ntiles < slots ? a.ntiles : slots));
             hipLaunchKernelGGL((conv3s_kernel<TL, TAPS, LRELU, Epi, FILM, SCALED, LERP, CLAMP, true>), g, dim3(TL::NTHR), lds, s, a, ep);

@@ -424,26 +424,13 @@ __global__ __launch_bounds__(kNT48) __attribute__((amdgpu_waves_per_eu(FILM ? 2 
 
 template <bool FILM, bool LERP, int RES, bool C5 = false>
 int launch48(tvc_ctx* ctx, hipStream_t s, Conv48Args a, int B) {
-    static int ncu_dev[64] = {};
-    int& ncu = ncu_dev[ctx->device & 63];
     constexpr size_t lds = (size_t)(12 * kXP48 + 36 * 64 + (FILM ? 24 * 64 : 0) + (C5 ? 6 * 64 : 0)) * 16 + 240 * 4;
-    if (!ncu) {
-        hipDeviceProp_t prop;
-        hipError_t e = hipGetDeviceProperties(&prop, ctx->device);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv48s_kernel<FILM, LERP, RES, C5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv48s_kernel<FILM, LERP, RES, C5, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(ctx, TVC_ERR_HIP, "conv48s setup: %s", hipGetErrorString(e));
-        ncu = prop.multiProcessorCount;
-    }
+    TVC_CHECK((lds_optin<conv48s_kernel<FILM, LERP, RES, C5>, conv48s_kernel<FILM, LERP, RES, C5, true>>(ctx, (int)lds, "conv48s")));
     a.tiles_per_utt = (a.len + kBN48 - 1) / kBN48;
     a.ntiles = a.tiles_per_utt * B;
-    a.rag = RagDev{};
-    if (ctx->rag) {
-        if (B != 1 || a.len % ctx->rag->Ttot != 0) return fail(ctx, TVC_ERR_STATE, "conv48s: a ragged batch runs as one long utterance");
-        TVC_CHECK(rag_view(ctx, s, a.len / ctx->rag->Ttot, kBN48, &a.rag, &a.ntiles));
-    }
+    TVC_CHECK(rag_tiles(ctx, s, B, a.len, kBN48, &a.rag, &a.ntiles, "conv48s"));
     const int wpc = FILM ? 1 : 2;                     // persistent workgroups per CU
-    const int grid = a.ntiles < wpc * ncu ? a.ntiles : wpc * ncu;
+    const int grid = a.ntiles < wpc * ctx->ncu ? a.ntiles : wpc * ctx->ncu;
     if (ctx->rag) hipLaunchKernelGGL((conv48s_kernel<FILM, LERP, RES, C5, true>), dim3(grid), dim3(kNT48), lds, s, a);
     else hipLaunchKernelGGL((conv48s_kernel<FILM, LERP, RES, C5>), dim3(grid), dim3(kNT48), lds, s, a);
     return launch_check(ctx, "conv48s");
@@ -811,27 +798,14 @@ __global__ __launch_bounds__(kNT48) __attribute__((amdgpu_waves_per_eu(2))) void
 
 template <bool FILM, bool LERP, int RES>
 int launch48p(tvc_ctx* ctx, hipStream_t s, Conv48PArgs a, int B) {
-    static int ncu_dev[64] = {};
-    int& ncu = ncu_dev[ctx->device & 63];
     constexpr size_t lds = (size_t)(12 * kXPP + 12 * 128 + 72 * 64 + (FILM ? 24 * 64 : 0)) * 16 + 272 * 4;
     static_assert(lds <= 160 * 1024, "LDS");
-    if (!ncu) {
-        hipDeviceProp_t prop;
-        hipError_t e = hipGetDeviceProperties(&prop, ctx->device);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv48p_kernel<FILM, LERP, RES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv48p_kernel<FILM, LERP, RES, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(ctx, TVC_ERR_HIP, "conv48p setup: %s", hipGetErrorString(e));
-        ncu = prop.multiProcessorCount;
-    }
+    TVC_CHECK((lds_optin<conv48p_kernel<FILM, LERP, RES>, conv48p_kernel<FILM, LERP, RES, true>>(ctx, (int)lds, "conv48p")));
     const int bno = 128 - 2 * a.db;
     a.tiles_per_utt = (a.len + bno - 1) / bno;
     a.ntiles = a.tiles_per_utt * B;
-    a.rag = RagDev{};
-    if (ctx->rag) {
-        if (B != 1 || a.len % ctx->rag->Ttot != 0) return fail(ctx, TVC_ERR_STATE, "conv48p: a ragged batch runs as one long utterance");
-        TVC_CHECK(rag_view(ctx, s, a.len / ctx->rag->Ttot, bno, &a.rag, &a.ntiles));
-    }
-    const int grid = a.ntiles < ncu ? a.ntiles : ncu;
+    TVC_CHECK(rag_tiles(ctx, s, B, a.len, bno, &a.rag, &a.ntiles, "conv48p"));
+    const int grid = a.ntiles < ctx->ncu ? a.ntiles : ctx->ncu;
     if (ctx->rag) hipLaunchKernelGGL((conv48p_kernel<FILM, LERP, RES, true>), dim3(grid), dim3(kNT48), lds, s, a);
     else hipLaunchKernelGGL((conv48p_kernel<FILM, LERP, RES>), dim3(grid), dim3(kNT48), lds, s, a);
     return launch_check(ctx, "conv48p");

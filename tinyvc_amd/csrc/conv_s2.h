@@ -302,19 +302,7 @@ inline bool conv_s2_try(int* rc, tvc_ctx* ctx, hipStream_t s, const PackedW& w, 
     if ((long)B * w.M * len >= (1L << 31) / 4 * 4 && (long)w.M * len * 4 >= (1L << 32)) return false;
     if ((long)Cin * (LERP ? lin : len) * 4 >= (1L << 32) || (long)w.M * len * 4 >= (1L << 32)) return false;      // 32-bit byte offsets inside an utterance
     if (LERP != (lin > 0)) return false;
-    static bool ready_dev[64] = {};
-    static int ncu_dev[64] = {};
-    bool& ready = ready_dev[ctx->device & 63];
-    int& ncu = ncu_dev[ctx->device & 63];
-    if (!ready) {
-        hipDeviceProp_t prop;
-        hipError_t e = hipGetDeviceProperties(&prop, ctx->device);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv_s2_kernel<LERP, PRE>, hipFuncAttributeMaxDynamicSharedMemorySize, CS2::lds_bytes);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv_s2_kernel<LERP, PRE, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CS2::lds_bytes);
-        if (e != hipSuccess) { *rc = fail(ctx, TVC_ERR_HIP, "conv_s2 setup: %s", hipGetErrorString(e)); return true; }
-        ncu = prop.multiProcessorCount;
-        ready = true;
-    }
+    if ((*rc = lds_optin<conv_s2_kernel<LERP, PRE>, conv_s2_kernel<LERP, PRE, true>>(ctx, CS2::lds_bytes, "conv_s2"))) return true;
     ConvS2Args a;
     a.A6 = reinterpret_cast<const uint4*>(w.A6);
     a.wsc = w.wscale;
@@ -330,22 +318,16 @@ inline bool conv_s2_try(int* rc, tvc_ctx* ctx, hipStream_t s, const PackedW& w, 
     a.M = w.M;
     a.mblocks = w.MT6 / CS2::MTB;
     a.tiles_per_utt = (len + CS2::BN - 1) / CS2::BN;
-    a.ntiles = a.tiles_per_utt * B * a.mblocks;
     a.amax_x = bfp.x;
     a.amax_y = PRE ? nullptr : bfp.y;
     a.ypre = reinterpret_cast<uint4*>(y);
     a.pre_w = pre_w;
     a.pre_b = pre_b;
-    a.rag = RagDev{};
-    if (ctx->rag) {
-        // ragged batch (ragged.h): the driver passed B = 1 and len = the batch's columns at this rate (= the row stride)
-        if (B != 1 || len % ctx->rag->Ttot != 0) { *rc = fail(ctx, TVC_ERR_STATE, "conv_s2: a ragged batch runs as one long utterance"); return true; }
-        int ncol = 0;
-        *rc = rag_view(ctx, s, len / ctx->rag->Ttot, CS2::BN, &a.rag, &ncol);
-        if (*rc) return true;
-        a.ntiles = ncol * a.mblocks;
-    }
-    const int grid = a.ntiles < ncu ? a.ntiles : ncu;
+    // ragged batch (ragged.h): the driver passed B = 1 and len = the batch's columns at this rate (= the row stride)
+    int ncol = a.tiles_per_utt * B;
+    if ((*rc = rag_tiles(ctx, s, B, len, CS2::BN, &a.rag, &ncol, "conv_s2"))) return true;
+    a.ntiles = ncol * a.mblocks;
+    const int grid = a.ntiles < ctx->ncu ? a.ntiles : ctx->ncu;
     if (ctx->rag) hipLaunchKernelGGL((conv_s2_kernel<LERP, PRE, true>), dim3(grid), dim3(CS2::NTHR), CS2::lds_bytes, s, a);
     else hipLaunchKernelGGL((conv_s2_kernel<LERP, PRE>), dim3(grid), dim3(CS2::NTHR), CS2::lds_bytes, s, a);
     *rc = launch_check(ctx, "conv_s2");

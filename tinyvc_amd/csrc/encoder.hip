@@ -203,20 +203,10 @@ static bool cnx_try(int* rc, tvc_ctx* ctx, hipStream_t s, const ConvNeXtW& w, fl
     const int NB = ctx->rag ? ctx->rag->B : B, Tl = ctx->rag ? ctx->rag->Tlong : T, rs = T;      // (ragged: T = all frames = the row stride)
     if ((long)rs * 8 * 4 >= (1L << 31)) return false;                                             // 32-bit lane offsets
     constexpr int KP = C == 384 ? 2 : 1;
-    static int ncu_dev[64] = {};
-    int& ncu = ncu_dev[ctx->device & 63];
-    if (!ncu) {
-        hipDeviceProp_t prop;
-        hipError_t e = hipGetDeviceProperties(&prop, ctx->device);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)cnx1_kernel<C, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, Cnx1<C, 1>::LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)cnx1_kernel<C, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, Cnx1<C, 2>::LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)cnx2_kernel<C, KP>, hipFuncAttributeMaxDynamicSharedMemorySize, Cnx2<C, KP>::LDS_BYTES);
-        if (e != hipSuccess) {
-            *rc = fail(ctx, TVC_ERR_HIP, "cnx setup: %s", hipGetErrorString(e));
-            return true;
-        }
-        ncu = prop.multiProcessorCount;
-    }
+    if ((*rc = lds_optin<cnx1_kernel<C, 1>>(ctx, Cnx1<C, 1>::LDS_BYTES, "cnx")) ||
+        (*rc = lds_optin<cnx1_kernel<C, 2>>(ctx, Cnx1<C, 2>::LDS_BYTES, "cnx")) ||
+        (*rc = lds_optin<cnx2_kernel<C, KP>>(ctx, Cnx2<C, KP>::LDS_BYTES, "cnx")))
+        return true;
     CnxArgs a{};
     a.x = x;
     a.h = h;
@@ -227,7 +217,7 @@ static bool cnx_try(int* rc, tvc_ctx* ctx, hipStream_t s, const ConvNeXtW& w, fl
     auto split = [&](int MT, int tiles) {
         int d = 1;
         for (int c = 1; c <= MT; ++c)
-            if (MT % c == 0 && (long)tiles * c <= ncu) d = c;
+            if (MT % c == 0 && (long)tiles * c <= ctx->ncu) d = c;
         return d;
     };
     {

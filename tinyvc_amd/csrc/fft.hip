@@ -278,15 +278,9 @@ __global__ __launch_bounds__(kFW * 64) void noise_ifft_kernel(const float* __res
 int run_stft_fft(tvc_ctx* ctx, hipStream_t s, const float* wav, float* spec, int B, int64_t L) {
     if (!ctx->fft_tw960 || !ctx->fft_tw1920 || !ctx->fft_hann) return fail(ctx, TVC_ERR_STATE, "fft tables missing");
     const int T = (int)(L / kHop);
-    static bool ready_dev[64] = {};
-    bool& ready = ready_dev[ctx->device & 63];
     constexpr int lds = kFW * kM * 8;
     static_assert(kBins * kFW * 4 <= lds, "the magnitude tile overlays the bins");
-    if (!ready) {
-        hipError_t e = hipFuncSetAttribute((const void*)stft_fft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return fail(ctx, TVC_ERR_HIP, "stft_fft setup: %s", hipGetErrorString(e));
-        ready = true;
-    }
+    TVC_CHECK(lds_optin<stft_fft_kernel>(ctx, lds, "stft_fft"));
     RagDev rg;
     TVC_CHECK(rag_view(ctx, s, 1, 0, &rg, nullptr));
     const int groups = ((ctx->rag ? ctx->rag->Tlong : T) + kFW - 1) / kFW;
@@ -299,15 +293,8 @@ int run_stft_fft(tvc_ctx* ctx, hipStream_t s, const float* wav, float* spec, int
 // angle_padded (ragged batches only): `angle` is the caller's padded [rows][961][Tmax] tensor, not the batch-wide [961][T] layout
 int run_noise_ifft(tvc_ctx* ctx, hipStream_t s, const float* kern, const float* angle, uint64_t seed, float* frames, int B, int T, bool angle_padded) {
     if (!ctx->fft_tw960 || !ctx->fft_tw1920) return fail(ctx, TVC_ERR_STATE, "fft tables missing");
-    static bool ready_dev[64] = {};
-    bool& ready = ready_dev[ctx->device & 63];
     constexpr int lds = kFW * (kBins + 1) * 8;
-    if (!ready) {
-        hipError_t e = hipFuncSetAttribute((const void*)noise_ifft_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)noise_ifft_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return fail(ctx, TVC_ERR_HIP, "noise_ifft setup: %s", hipGetErrorString(e));
-        ready = true;
-    }
+    TVC_CHECK((lds_optin<noise_ifft_kernel<false>, noise_ifft_kernel<true>>(ctx, lds, "noise_ifft")));
     RagDev rg;
     TVC_CHECK(rag_view(ctx, s, 1, 0, &rg, nullptr));
     const int* rowmap = rg.row;                    // ragged batch: utterance -> row of the call (the hash's row index)

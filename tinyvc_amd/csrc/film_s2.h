@@ -418,26 +418,9 @@ inline bool film_s2_try(int* rc, tvc_ctx* ctx, hipStream_t s, const FilmU& fu, c
                         const float* res, int res_lin, float res_scale, const BfpSlots& bfp, bool pre = false, float pre_w = 0.f, float pre_b = 0.f) {
     if (!fu.img || fu.C != C || C % 96 != 0 || C > 384 || dil < 1 || dil > FS2::MAXD || !bfp.x || !bfp.c || !res) return false;
     if ((long)C * len * 4 >= (1L << 32) || (res_lin > 0 && (long)C * res_lin * 4 >= (1L << 32))) return false;
-    static bool ready_dev[64] = {};
-    static int ncu_dev[64] = {};
-    bool& ready = ready_dev[ctx->device & 63];
-    int& ncu = ncu_dev[ctx->device & 63];
-    if (!ready) {
-        hipDeviceProp_t prop;
-        hipError_t e = hipGetDeviceProperties(&prop, ctx->device);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)film_s2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, FS2::lds_bytes);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)film_s2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, FS2::lds_bytes);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)film_s2_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FS2::lds_bytes);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)film_s2_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FS2::lds_bytes);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)film_s2_kernel<false, false, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, FS2T<7>::lds_bytes);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)film_s2_kernel<true, false, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, FS2T<7>::lds_bytes);
-        if (e != hipSuccess) {
-            *rc = fail(ctx, TVC_ERR_HIP, "film_s2 setup: %s", hipGetErrorString(e));
-            return true;
-        }
-        ncu = prop.multiProcessorCount;
-        ready = true;
-    }
+    if ((*rc = lds_optin<film_s2_kernel<false>, film_s2_kernel<true>, film_s2_kernel<false, true>, film_s2_kernel<true, true>>(ctx, FS2::lds_bytes, "film_s2")) ||
+        (*rc = lds_optin<film_s2_kernel<false, false, 7>, film_s2_kernel<true, false, 7>>(ctx, FS2T<7>::lds_bytes, "film_s2")))
+        return true;
     FilmS2Args a{};
     a.img = reinterpret_cast<const uint4*>(fu.img);
     a.tab = fu.tab;
@@ -452,22 +435,17 @@ inline bool film_s2_try(int* rc, tvc_ctx* ctx, hipStream_t s, const FilmU& fu, c
     a.res_scale = res_scale;
     a.mblocks = C / 96;
     a.tiles_per_utt = (len + FS2::BN - 1) / FS2::BN;
-    a.ntiles = a.tiles_per_utt * B * a.mblocks;
     a.amax_x = bfp.x;
     a.xpre = reinterpret_cast<const uint4*>(h);
     a.pre_w = pre_w;
     a.pre_b = pre_b;
     a.amax_c = bfp.c;
     a.amax_y = bfp.y;
-    if (ctx->rag) {
-        // ragged batch (ragged.h): the driver passed B = 1 and len = the batch's columns at this rate (= the row stride)
-        if (B != 1 || len % ctx->rag->Ttot != 0) { *rc = fail(ctx, TVC_ERR_STATE, "film_s2: a ragged batch runs as one long utterance"); return true; }
-        int ncol = 0;
-        *rc = rag_view(ctx, s, len / ctx->rag->Ttot, FS2::BN, &a.rag, &ncol);
-        if (*rc) return true;
-        a.ntiles = ncol * a.mblocks;
-    }
-    const int grid = a.ntiles < ncu ? a.ntiles : ncu;
+    // ragged batch (ragged.h): the driver passed B = 1 and len = the batch's columns at this rate (= the row stride)
+    int ncol = a.tiles_per_utt * B;
+    if ((*rc = rag_tiles(ctx, s, B, len, FS2::BN, &a.rag, &ncol, "film_s2"))) return true;
+    a.ntiles = ncol * a.mblocks;
+    const int grid = a.ntiles < ctx->ncu ? a.ntiles : ctx->ncu;
     if (ctx->rag) {
         if (pre) hipLaunchKernelGGL((film_s2_kernel<true, true>), dim3(grid), dim3(FS2::NTHR), FS2::lds_bytes, s, a);
         else hipLaunchKernelGGL((film_s2_kernel<false, true>), dim3(grid), dim3(FS2::NTHR), FS2::lds_bytes, s, a);
@@ -475,7 +453,7 @@ inline bool film_s2_try(int* rc, tvc_ctx* ctx, hipStream_t s, const FilmU& fu, c
         // the narrower tile computes fewer padded columns at this length
         a.tiles_per_utt = (len + 223) / 224;
         a.ntiles = a.tiles_per_utt * B * a.mblocks;
-        const int g7 = a.ntiles < ncu ? a.ntiles : ncu;
+        const int g7 = a.ntiles < ctx->ncu ? a.ntiles : ctx->ncu;
         if (pre) hipLaunchKernelGGL((film_s2_kernel<true, false, 7>), dim3(g7), dim3(FS2T<7>::NTHR), FS2T<7>::lds_bytes, s, a);
         else hipLaunchKernelGGL((film_s2_kernel<false, false, 7>), dim3(g7), dim3(FS2T<7>::NTHR), FS2T<7>::lds_bytes, s, a);
     } else if (pre) hipLaunchKernelGGL(film_s2_kernel<true>, dim3(grid), dim3(FS2::NTHR), FS2::lds_bytes, s, a);

@@ -465,25 +465,13 @@ __global__ __launch_bounds__(CF::NT) __attribute__((amdgpu_waves_per_eu(U24S_WPE
 
 template <class CF>
 static int launch_up24s(tvc_ctx* ctx, hipStream_t s, Up24SArgs a, int B) {
-    static int ncu_dev[64] = {};                    // per device of this process (the LDS attribute is per function and device)
-    int& ncu = ncu_dev[ctx->device & 63];
     const size_t lds = (size_t)CF::LDS_BYTES;
-    if (!ncu) {
-        hipDeviceProp_t prop;
-        hipError_t e = hipGetDeviceProperties(&prop, ctx->device);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)up24s_kernel<CF, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)up24s_kernel<CF, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(ctx, TVC_ERR_HIP, "up24s setup: %s", hipGetErrorString(e));
-        ncu = prop.multiProcessorCount;
-    }
+    TVC_CHECK((lds_optin<up24s_kernel<CF, false>, up24s_kernel<CF, true>>(ctx, (int)lds, "up24s")));
     a.tiles_per_utt = (a.len + CF::W - 1) / CF::W;
     a.ntiles = a.tiles_per_utt * B;
     static_assert(CF::WGS_PER_CU * CF::LDS_BYTES <= 160 * 1024, "LDS for the workgroups that share a CU");
-    const int slots = ncu * CF::WGS_PER_CU;
-    if (ctx->rag) {
-        if (B != 1 || a.len != ctx->rag->Ttot * kHop) return fail(ctx, TVC_ERR_STATE, "up24s: a ragged batch runs as one long utterance");
-        TVC_CHECK(rag_view(ctx, s, kHop, CF::W, &a.rag, &a.ntiles));
-    }
+    const int slots = ctx->ncu * CF::WGS_PER_CU;
+    TVC_CHECK(rag_tiles(ctx, s, B, a.len, CF::W, &a.rag, &a.ntiles, "up24s", kHop));
     int grid = a.ntiles < slots ? a.ntiles : slots;
     if (ctx->rag) hipLaunchKernelGGL((up24s_kernel<CF, true>), dim3(grid), dim3(CF::NT), lds, s, a);
     else hipLaunchKernelGGL((up24s_kernel<CF, false>), dim3(grid), dim3(CF::NT), lds, s, a);
@@ -671,24 +659,12 @@ int run_down0_split(tvc_ctx* ctx, hipStream_t s, const float* blob, const float*
     if (!blob) return fail(ctx, TVC_ERR_STATE, "down0s: the split weight blob of downs.0 is missing");
     if ((long)len * 24 * 4 >= (1L << 32)) return fail(ctx, TVC_ERR_ARG, "down0s: utterance too long for 32-bit byte offsets");
     if (y2 && len % 5 != 0) return fail(ctx, TVC_ERR_ARG, "down0s: the 1/5-rate copy needs len % 5 == 0");
-    static int ncu_dev[64] = {};
-    int& ncu = ncu_dev[ctx->device & 63];
     constexpr size_t lds = (2 * 6 * 256 + 10 * 64 + 8 + 2) * 16;
-    if (!ncu) {
-        hipDeviceProp_t prop;
-        hipError_t e = hipGetDeviceProperties(&prop, ctx->device);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)down0s_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)down0s_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(ctx, TVC_ERR_HIP, "down0s setup: %s", hipGetErrorString(e));
-        ncu = prop.multiProcessorCount;
-    }
+    TVC_CHECK((lds_optin<down0s_kernel<false>, down0s_kernel<true>>(ctx, (int)lds, "down0s")));
     Down0SArgs a{source, energy, out_fp32, reinterpret_cast<uint4*>(planes), y2, reinterpret_cast<const u32x4*>(blob), len, (len + 253) / 254, 0, amax_x, amax_y, RagDev{}};
     a.ntiles = a.tiles_per_utt * B;
-    if (ctx->rag) {
-        if (B != 1 || len != ctx->rag->Ttot * kHop) return fail(ctx, TVC_ERR_STATE, "down0s: a ragged batch runs as one long utterance");
-        TVC_CHECK(rag_view(ctx, s, kHop, 254, &a.rag, &a.ntiles));
-    }
-    const int grid = a.ntiles < 2 * ncu ? a.ntiles : 2 * ncu;      // two persistent workgroups per CU
+    TVC_CHECK(rag_tiles(ctx, s, B, len, 254, &a.rag, &a.ntiles, "down0s", kHop));
+    const int grid = a.ntiles < 2 * ctx->ncu ? a.ntiles : 2 * ctx->ncu;      // two persistent workgroups per CU
     if (ctx->rag) hipLaunchKernelGGL(down0s_kernel<true>, dim3(grid), dim3(512), lds, s, a);
     else hipLaunchKernelGGL(down0s_kernel<false>, dim3(grid), dim3(512), lds, s, a);
     return launch_check(ctx, "down0s");
@@ -988,16 +964,7 @@ int run_down24_fused(tvc_ctx* ctx, hipStream_t s, const DownW& d, const float* x
     if (d.cin != 24 || d.cout != 48) return fail(ctx, TVC_ERR_ARG, "down24f: 24 -> 48 channels only");
     if ((long)len * 48 * 4 >= (1L << 32)) return fail(ctx, TVC_ERR_ARG, "down24f: utterance too long for 32-bit byte offsets");
     if (y2 && len % 4 != 0) return fail(ctx, TVC_ERR_ARG, "down24f: the 1/4-rate copy needs len % 4 == 0");
-    static int ncu_dev[64] = {};
-    int& ncu = ncu_dev[ctx->device & 63];
-    if (!ncu) {
-        hipDeviceProp_t prop;
-        hipError_t e = hipGetDeviceProperties(&prop, ctx->device);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)down24f_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, D24F::LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)down24f_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, D24F::LDS_BYTES);
-        if (e != hipSuccess) return fail(ctx, TVC_ERR_HIP, "down24f setup: %s", hipGetErrorString(e));
-        ncu = prop.multiProcessorCount;
-    }
+    TVC_CHECK((lds_optin<down24f_kernel<false>, down24f_kernel<true>>(ctx, D24F::LDS_BYTES, "down24f")));
     Down24FArgs a{};
     a.x = xi;
     a.out = out;
@@ -1015,11 +982,8 @@ int run_down24_fused(tvc_ctx* ctx, hipStream_t s, const DownW& d, const float* x
     a.b2_b = d.b2_b;
     a.amax_x = amax_xi;
     a.amax_y = amax_out;
-    if (ctx->rag) {
-        if (B != 1 || len != ctx->rag->Ttot * (kHop / 5)) return fail(ctx, TVC_ERR_STATE, "down24f: a ragged batch runs as one long utterance");
-        TVC_CHECK(rag_view(ctx, s, kHop / 5, D24F::W, &a.rag, &a.ntiles));
-    }
-    const int grid = a.ntiles < ncu ? a.ntiles : ncu;
+    TVC_CHECK(rag_tiles(ctx, s, B, len, D24F::W, &a.rag, &a.ntiles, "down24f", kHop / 5));
+    const int grid = a.ntiles < ctx->ncu ? a.ntiles : ctx->ncu;
     if (ctx->rag) hipLaunchKernelGGL(down24f_kernel<true>, dim3(grid), dim3(D24F::NT), D24F::LDS_BYTES, s, a);
     else hipLaunchKernelGGL(down24f_kernel<false>, dim3(grid), dim3(D24F::NT), D24F::LDS_BYTES, s, a);
     return launch_check(ctx, "down24f");

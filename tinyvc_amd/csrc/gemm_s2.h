@@ -255,15 +255,9 @@ __global__ __launch_bounds__(2 * NWV * 64) void gemm_s2_kernel(Gemm2Args a, Epi 
 
 template <int NWV, int WN, class Epi, bool SCALED>
 inline int gemm_s2_launch_t(tvc_ctx* ctx, hipStream_t s, const PackedW& w, const float* x, int B, int Cin, int T, long xstride, const Epi& ep,
-                            const float* kscale, int ncu, const float* amax_x) {
+                            const float* kscale, const float* amax_x) {
     using TL = G2Tile<NWV, WN>;
-    static bool ready_dev[64] = {};
-    bool& ready = ready_dev[ctx->device & 63];
-    if (!ready) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_s2_kernel<NWV, WN, Epi, SCALED>, hipFuncAttributeMaxDynamicSharedMemorySize, TL::lds_bytes);
-        if (e != hipSuccess) return fail(ctx, TVC_ERR_HIP, "gemm_s2 setup: %s", hipGetErrorString(e));
-        ready = true;
-    }
+    TVC_CHECK((lds_optin<gemm_s2_kernel<NWV, WN, Epi, SCALED>>(ctx, TL::lds_bytes, "gemm_s2")));
     Gemm2Args a;
     a.A6 = reinterpret_cast<const uint4*>(w.A6);
     a.wsc = w.wscale;
@@ -283,7 +277,7 @@ inline int gemm_s2_launch_t(tvc_ctx* ctx, hipStream_t s, const PackedW& w, const
         if (B != 1 || T != ctx->rag->Ttot) return fail(ctx, TVC_ERR_STATE, "gemm_s2: a ragged batch runs as one long utterance at the frame rate");
         a.col2b = ctx->rag->d_col2b;
     }
-    const int slots = ncu / 8 * 8;       // one persistent workgroup per CU, a multiple of 8 (XCD walk)
+    const int slots = ctx->ncu / 8 * 8;       // one persistent workgroup per CU, a multiple of 8 (XCD walk)
     dim3 g((unsigned)(a.vtiles < slots ? a.vtiles : slots));
     hipLaunchKernelGGL((gemm_s2_kernel<NWV, WN, Epi, SCALED>), g, dim3(TL::NTHR), TL::lds_bytes, s, a, ep);
     return 0;
@@ -295,16 +289,9 @@ inline bool gemm_s2_try(int* rc, tvc_ctx* ctx, hipStream_t s, const PackedW& w, 
                         const float* amax_x, const float* kscale = nullptr) {
     const long xs = xstride ? xstride : (long)Cin * T;
     if (Cin % 32 != 0 || Cin / 16 > w.S6 || w.MT6 % 4 != 0 || xs * B >= (1L << 29) || (long)B * T >= (1L << 29) || (SCALED && !kscale)) return false;
-    static int ncu_dev[64] = {};
-    int& ncu = ncu_dev[ctx->device & 63];
-    if (!ncu) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) { *rc = fail(ctx, TVC_ERR_HIP, "gemm_s2: device properties"); return true; }
-        ncu = prop.multiProcessorCount;
-    }
     // column-tile width: whole rounds of the CUs, then the fewest staging round trips (wider tiles reuse a weight slab more)
     const long ncols = (long)B * T;
-    const int mblocks = w.MT6 / 4, slots = ncu / 8 * 8;
+    const int mblocks = w.MT6 / 4, slots = ctx->ncu / 8 * 8;
     int best = 4;
     long best_cost = -1;
     for (int nwv = G2_NWV_MIN; nwv <= 6; ++nwv) {     // 64-column tiles only pay when the launch cannot fill the chip (a streaming block: 896 columns)
@@ -313,11 +300,11 @@ inline bool gemm_s2_try(int* rc, tvc_ctx* ctx, hipStream_t s, const PackedW& w, 
         const long cost = rounds * (nwv * 32 + 64);
         if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = nwv; }
     }
-    if (best == 2) *rc = gemm_s2_launch_t<2, 1, Epi, SCALED>(ctx, s, w, x, B, Cin, T, xstride, ep, kscale, ncu, amax_x);
-    else if (best == 3) *rc = gemm_s2_launch_t<3, 1, Epi, SCALED>(ctx, s, w, x, B, Cin, T, xstride, ep, kscale, ncu, amax_x);
-    else if (best == 4) *rc = gemm_s2_launch_t<4, 1, Epi, SCALED>(ctx, s, w, x, B, Cin, T, xstride, ep, kscale, ncu, amax_x);
-    else if (best == 5) *rc = gemm_s2_launch_t<5, 1, Epi, SCALED>(ctx, s, w, x, B, Cin, T, xstride, ep, kscale, ncu, amax_x);
-    else *rc = gemm_s2_launch_t<6, 1, Epi, SCALED>(ctx, s, w, x, B, Cin, T, xstride, ep, kscale, ncu, amax_x);
+    if (best == 2) *rc = gemm_s2_launch_t<2, 1, Epi, SCALED>(ctx, s, w, x, B, Cin, T, xstride, ep, kscale, amax_x);
+    else if (best == 3) *rc = gemm_s2_launch_t<3, 1, Epi, SCALED>(ctx, s, w, x, B, Cin, T, xstride, ep, kscale, amax_x);
+    else if (best == 4) *rc = gemm_s2_launch_t<4, 1, Epi, SCALED>(ctx, s, w, x, B, Cin, T, xstride, ep, kscale, amax_x);
+    else if (best == 5) *rc = gemm_s2_launch_t<5, 1, Epi, SCALED>(ctx, s, w, x, B, Cin, T, xstride, ep, kscale, amax_x);
+    else *rc = gemm_s2_launch_t<6, 1, Epi, SCALED>(ctx, s, w, x, B, Cin, T, xstride, ep, kscale, amax_x);
     return true;
 }
 

@@ -1098,13 +1098,7 @@ struct KnnLists {        // where the merge kernels find the per-query top-4 lis
 template <int MODE>
 static int coarse_launch(tvc_ctx* ctx, hipStream_t s, const float* prepared, long Npad, int N, const uint4* qh, int ncols, int qtiles, int t2_cover,
                          float* c4v, int ns_sample, int* cnt, int* cand, float* candv, int* flag, int* nsplit_out) {
-    static bool ready_dev[64] = {};
-    bool& ready = ready_dev[ctx->device & 63];
-    if (!ready) {
-        hipError_t e = hipFuncSetAttribute((const void*)knn_coarse_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, C_LDS);
-        if (e != hipSuccess) return fail(ctx, TVC_ERR_HIP, "knn coarse setup: %s", hipGetErrorString(e));
-        ready = true;
-    }
+    TVC_CHECK(lds_optin<knn_coarse_kernel<MODE>>(ctx, C_LDS, "knn coarse"));
     int nsplit = (768 + qtiles - 1) / qtiles;           // ~3 workgroups per CU's worth of work units (one resident workgroup per CU: 128 KiB of LDS)
     if (nsplit > t2_cover) nsplit = t2_cover;
     if (nsplit < 1) nsplit = 1;

@@ -176,13 +176,7 @@ int run_knn_general(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const
     if (ws.dry) return 0;
     static_assert(GT / 64 == GQ, "one merging wave per query");
     constexpr int lds = (KDG * GQ + 16 + 2 * GQ * GT * GK) * 4;
-    static bool ready_dev[64] = {};
-    bool& ready = ready_dev[ctx->device & 63];
-    if (!ready) {
-        hipError_t e = hipFuncSetAttribute((const void*)knn_general_topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return fail(ctx, TVC_ERR_HIP, "knn_match_general setup: %s", hipGetErrorString(e));
-        ready = true;
-    }
+    TVC_CHECK(lds_optin<knn_general_topk_kernel>(ctx, lds, "knn_match_general"));
     hipLaunchKernelGGL(knn_general_topk_kernel, dim3((unsigned)((ncols + GQ - 1) / GQ)), dim3(GT), lds, s, src, index, (int)N, (int)ncols, T, k, metric, idx, val_out);
     hipLaunchKernelGGL(knn_general_gather_kernel, dim3((unsigned)((ncols + 63) / 64), 16), dim3(256), 0, s, index, (int)N, idx, k, (int)ncols, T, out);
     return launch_check(ctx, "knn_match_general");

@@ -57,6 +57,9 @@ int rag_setup(tvc_ctx* ctx, hipStream_t s, Ws& ws, RagHost& h, const std::vector
 // the view of the context's current ragged batch for a launch at `mult` samples per frame; bn > 0: with the column-tile table of
 // bn-wide tiles (built on first use), *ntiles = its total.  Equal-length calls (no current batch) get the empty view.
 int rag_view(tvc_ctx* ctx, hipStream_t s, int mult, int bn, RagDev* out, int* ntiles);
+// rag_view for a launch of B utterances of len columns: a ragged batch must come as one long utterance (B = 1) whose len is Ttot * mult
+// (mult = 0: any whole multiple, which sets mult) - else TVC_ERR_STATE "<what>: ...".  Equal-length calls: the empty view, *ntiles untouched.
+int rag_tiles(tvc_ctx* ctx, hipStream_t s, int B, long len, int bn, RagDev* out, int* ntiles, const char* what, int mult = 0);
 
 // Shape-dependent kernel choices (decoder.hip: film_s2 needs one 256-column tile per utterance) look at the SHORTEST utterance of a ragged batch:
 // a batch only holds utterances that make the same choices (api.hip ragged_split), so this is every member's own decision.

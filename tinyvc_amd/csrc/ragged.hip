@@ -138,4 +138,13 @@ int rag_view(tvc_ctx* ctx, hipStream_t s, int mult, int bn, RagDev* out, int* nt
     return 0;
 }
 
+int rag_tiles(tvc_ctx* ctx, hipStream_t s, int B, long len, int bn, RagDev* out, int* ntiles, const char* what, int mult) {
+    if (const RagHost* h = ctx->rag) {
+        if (B != 1 || (mult ? len != (long)h->Ttot * mult : len % h->Ttot != 0))
+            return fail(ctx, TVC_ERR_STATE, "%s: a ragged batch runs as one long utterance", what);
+        if (!mult) mult = (int)(len / h->Ttot);
+    }
+    return rag_view(ctx, s, mult, bn, out, ntiles);
+}
+
 }  // namespace tvc

@@ -194,9 +194,8 @@ static __global__ __launch_bounds__(256) void amax_rag_kernel(const float* __res
 // slot must have been zeroed (one memset per stage covers all of a stage's slots); rows of C * len floats must be 16-byte aligned
 inline int run_amax_rows(tvc_ctx* ctx, hipStream_t s, const float* x, int B, int C, long len, float* slot) {
     if (ctx->rag) {     // (the driver passed B = 1 and len = the batch's columns at this tensor's rate)
-        if (B != 1 || len % ctx->rag->Ttot != 0) return fail(ctx, TVC_ERR_STATE, "amax_rows: a ragged batch runs as one long utterance");
         RagDev rg;
-        TVC_CHECK(rag_view(ctx, s, (int)(len / ctx->rag->Ttot), 0, &rg, nullptr));
+        TVC_CHECK(rag_tiles(ctx, s, B, len, 0, &rg, nullptr, "amax_rows"));
         const int gx = C < 8 ? C : (ctx->rag->B >= 64 ? 8 : 16);
         hipLaunchKernelGGL(amax_rag_kernel, dim3((unsigned)gx, (unsigned)ctx->rag->B), dim3(256), 0, s, x, C, (int)len, rg, slot);
         return launch_check(ctx, "amax_rows (ragged)");

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -129,6 +130,7 @@ struct tvc_prof_region {
 
 struct tvc_ctx {
     int device = 0;
+    int ncu = 0;                              // compute units of the device (tvc_ctx_create): persistent launches size their grids by it
     int profiling = 0;                        // tvc_profile_enable: 0 = off, 1 = hipEvent pairs around every named region, 2 = around `filter_net` only
     std::vector<tvc_prof_region> regions;
     std::vector<hipEvent_t> event_pool;       // recycled hipEvents: no hipEventCreate on the hot path
@@ -290,6 +292,21 @@ struct SideFork {
 inline int launch_check(tvc_ctx* ctx, const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(ctx, TVC_ERR_HIP, "launch %s: %s", what, hipGetErrorString(e));
+    return 0;
+}
+
+// Opts the kernels K... into `bytes` of dynamic LDS on the first call per device.  The attribute is per (function, device), so the flag is
+// process-wide and not the context's: a second context whose first call is being captured must not set the attribute inside the capture.
+template <auto... K>
+int lds_optin(tvc_ctx* ctx, int bytes, const char* what) {
+    static std::atomic<bool> ready_dev[64];
+    std::atomic<bool>& ready = ready_dev[ctx->device & 63];
+    if (ready.load(std::memory_order_acquire)) return 0;
+    for (const void* k : {(const void*)K...}) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) return fail(ctx, TVC_ERR_HIP, "%s setup: %s", what, hipGetErrorString(e));
+    }
+    ready.store(true, std::memory_order_release);
     return 0;
 }
 
