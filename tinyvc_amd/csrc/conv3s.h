@@ -1031,17 +1031,14 @@ inline int conv3s_launch_t(tvc_ctx* ctx, hipStream_t s, const PackedW& w, const 
     return 0;
 }
 
-// k3 conv on the split path; Mpad = 64 (48 channels) or a multiple of 96 (FilterNet levels with C = 96, 192, 384).
+// k3 conv on the split path; Mpad a multiple of 96 (FilterNet levels with C = 96, 192, 384: the 48-channel convs run in conv48s.hip).
 // Tiles (each swept on the part): plain convs 96 x 256 (a wave owns two 32-sample n-tiles: every weight
-// fragment and every slab's staging round trip serves twice the columns), 48-output-channel convs 64 x 192 (six waves per m-tile),
-// FiLM-fused convs 96 x 128 or 96 x 256.
+// fragment and every slab's staging round trip serves twice the columns), FiLM-fused convs 96 x 128 or 96 x 256.
 template <bool LRELU, class Epi, bool FILM = false, bool LERP = false>
 inline int conv3s_launch(tvc_ctx* ctx, hipStream_t s, const PackedW& w, const float* x, int B, int Cin, int len, int dil, const Epi& ep,
                          const BfpSlots& bfp, const PackedW* wsc = nullptr, const PackedW* wsh = nullptr, const float* cond = nullptr, int Ccond = 0, int lin = 0,
                          float lscale = 0.f) {
-    if (w.MT6 == 2)     // 48 output channels: two m-tiles, the second half empty
-        return conv3s_launch_t<SplitTile<2, 1, 6, 1>, 3, LRELU, Epi, FILM, false, LERP>(ctx, s, w, x, B, Cin, len, dil, ep, wsc, wsh, cond, Ccond, 0, S_BPC, nullptr, false, 0,
-                                                                                       lin, lscale, bfp);
+    if (w.MT6 % 3 != 0) return fail(ctx, TVC_ERR_ARG, "conv3s: k3 convs need a multiple of 96 output rows");
     if constexpr (FILM) {
         // Two tiles for the FiLM-fused launches.  96 x 256 (the plain convs' tile): the conv phase stages a slab for twice the columns,
         // scale and shift run one after the other on one extra accumulator pair (split_phase<TWO>) and the cond tile is staged twice.

@@ -1,17 +1,16 @@
-// 48-channel k3 dilated convs of FilterNet (ups.3's c1..c4 with their FiLM, Downsample 2's c1 / c2; decoder.py:143-190) with
-// the layer's weights RESIDENT in LDS.  At 48 channels a conv is only three 16-channel K slabs: the generic split kernel
-// (conv3s.h) restages its weights and passes two barriers per slab for a handful of MFMAs per wave, and its matrix pipe sat idle
-// two thirds of the time.  Here a persistent 8-wave workgroup loads the conv's 36 weight pieces (and FiLM's 24) once, stages
-// the whole 48-channel halo tile of 128 samples in one go and then issues the tile's 27 (+18) MFMAs per wave back to back:
-// one staging round trip and two barriers per tile instead of per slab.  Two-term fp16 split, accumulator pairs and the
-// block-floating-point guard as in split_fp16.h.
+// 48-channel k3 dilated convs of FilterNet (decoder.py:143-190) with the layer's weights RESIDENT in LDS: conv48s_kernel runs
+// ups.3's c3 and c4 + FiLM2 + residual (+ c5), conv48p_kernel the pairs c1 -> c2 (ups.3's first half with FiLM1, Downsample 2).
+// At 48 channels a conv is only three 16-channel K slabs: the generic split kernel (conv3s.h) restages its weights and passes
+// two barriers per slab for a handful of MFMAs per wave, and its matrix pipe sat idle two thirds of the time.  Here a persistent
+// 8-wave workgroup loads the conv's 36 weight pieces (and FiLM's 24) once, stages the whole 48-channel halo tile of 128 samples
+// in one go and then issues the tile's 27 (+18) MFMAs per wave back to back: one staging round trip and two barriers per tile
+// instead of per slab.  Two-term fp16 split, accumulator pairs and the block-floating-point guard as in split_fp16.h.
 //   weights   the same pre-split images as conv3s (PackedW::A6: [K16 step = slab*3 + tap][m-tile][part][lane][8 fp16];
 //             stacked FiLM image [slab][scale mt0, mt1, shift mt0, mt1][part]) - no new packing;
-//   input     Xs[part][8-channel group (6)][position][8 fp16]: lrelu (and, for c1, F.interpolate) applied while depositing;
+//   input     Xs[part][8-channel group (6)][position][8 fp16]: lrelu applied while depositing;
 //   waves     wave w = m-tile (w >> 2) x 32-sample n-tile (w & 3); FiLM's cond fragments come from HBM straight into
 //             B-fragment order and are split in registers; (conv, scale, shift) combine in registers;
-//   epilogue  bias / FiLM / residual (direct, or F.interpolate of the low-rate tensor evaluated in place), 128-byte runs
-//             per row and store instruction; residual and cond are requested before the MFMAs.
+//   epilogue  bias / FiLM / residual, 128-byte runs per row and store instruction; residual and cond are requested before the MFMAs.
 #include "small_kernels.h"
 #include "split_fp16.h"
 #include "tvc_common.h"
@@ -51,9 +50,9 @@ __device__ __forceinline__ void ld4_g8(float (&dst)[4], const float* base, unsig
 struct Conv48Args {
     // The level's own tensors - x1, h, the skip tensor cond - travel in the G8 layout [B][6 groups][len][8 channels] (a staged item, a cond
     // fragment or a lane's four output channels are 32 / 32 / 16 contiguous bytes: 16-byte accesses instead of strided 4-byte ones)
-    const float* x;        // G8 [B][6][len][8]; LERP: the low-rate tensor, planar [B][48][lin]
+    const float* x;        // G8 [B][6][len][8]
     const float* cond;     // FILM: G8
-    const float* res;      // RES 1: G8; RES 2: low-rate planar [B][48][rlin], interpolated here
+    const float* res;      // FILM: G8
     float* out;            // G8
     const u32x4* A6;       // conv image, 36 pieces
     const u32x4* F6;       // stacked FiLM image, 24 pieces
@@ -70,14 +69,13 @@ struct Conv48Args {
     const float* amax_x;
     const float* amax_c;
     float* amax_y;
-    int len, dil, lin, rlin, tiles_per_utt, ntiles;
-    float lscale, rscale;
-    RagDev rag;            // RAG kernels (ragged.h): len / lin / rlin = row strides of the batch-wide tensors, tiles / extents from the table
+    int len, dil, tiles_per_utt, ntiles;
+    RagDev rag;            // RAG kernels (ragged.h): len = row stride of the batch-wide tensors, tiles / extents from the table
 };
 
-// RES: 0 none, 1 direct, 2 interpolated.  C5: Upsample.c5 (1x1, 48 -> 24, decoder.py:171,189) applied to the finished tile
+// FILM: FiLM over cond and the residual res.  C5: Upsample.c5 (1x1, 48 -> 24, decoder.py:171,189) applied to the finished tile
 // before it leaves the CU: the 48-channel block output is never written, only c5's 24 rows are.
-template <bool FILM, bool LERP, int RES, bool C5 = false, bool RAG = false>
+template <bool FILM, bool C5 = false, bool RAG = false>
 // (launches without FiLM - 73 KB of LDS, <= 128 registers - run TWO workgroups per CU: a plain 48-channel conv waits on its 0.47 GB of HBM traffic more
 // than on its 27 MFMAs per tile, and the second workgroup's loads fly under the first one's arithmetic: Upsample 3 0.80 -> 0.765 ms same-box, round 4)
 __global__ __launch_bounds__(kNT48) __attribute__((amdgpu_waves_per_eu(FILM ? 2 : 4))) void conv48s_kernel(Conv48Args a) {
@@ -93,8 +91,6 @@ __global__ __launch_bounds__(kNT48) __attribute__((amdgpu_waves_per_eu(FILM ? 2 
     const int mt = wave >> 2, nt = wave & 3;
     const int rs = a.len, dil = a.dil;                       // rs = row stride of cond / res / out (= every utterance's length unless RAG, ragged.h)
     const int XW = BN + 2 * dil;
-    const int rsl = LERP ? a.lin : rs;                         // row stride of x
-    const int xf = LERP ? rs / a.lin : 1, rf = RES == 2 ? rs / a.rlin : 1;     // RAG: an utterance's low-rate lengths = len / xf, len / rf
     int bh = 0;                                                // RAG: utterance hint of the table walk
     auto utt = [&](int tile) __attribute__((always_inline)) { return rag_tile<RAG>(a.rag, tile, a.tiles_per_utt, rs, bh).b; };
 
@@ -119,7 +115,7 @@ __global__ __launch_bounds__(kNT48) __attribute__((amdgpu_waves_per_eu(FILM ? 2 
 
     // staging items (8-channel group, column): 6 * XW <= 1092 of them, three per thread
     constexpr int XPER = 3;
-    float xr0[XPER][8], xr1[LERP ? XPER : 1][8], lam[LERP ? XPER : 1];
+    float xr0[XPER][8];
     int ig[XPER], ic[XPER];
 #pragma unroll
     for (int i = 0; i < XPER; ++i) {
@@ -130,26 +126,15 @@ __global__ __launch_bounds__(kNT48) __attribute__((amdgpu_waves_per_eu(FILM ? 2 
     }
     auto fetch = [&](int tile) __attribute__((always_inline)) {
         const RagTile rt = rag_tile<RAG>(a.rag, tile, a.tiles_per_utt, rs, bh);
-        const int len = rt.len, lin = LERP ? len / xf : len;
+        const int len = rt.len;
         const int px0 = rt.tin * BN - dil;
-        const float* xb = RAG ? a.x + (LERP ? rt.off / xf : 8L * rt.off) : a.x + (long)rt.b * C * rsl;
+        const float* xb = RAG ? a.x + 8L * rt.off : a.x + (long)rt.b * C * rs;
 #pragma unroll
         for (int i = 0; i < XPER; ++i) {
             const int g = ig[i] > 5 ? 5 : ig[i];
             int p = px0 + ic[i];
             p = p < 0 ? 0 : (p > len - 1 ? len - 1 : p);
-            if (LERP) {
-                const Lerp lc = lerp_coord(p, a.lscale, lin);
-                lam[i] = lc.w1;
-                const unsigned o0 = 4u * (unsigned)(8 * g * rsl + lc.i0), o1 = 4u * (unsigned)(8 * g * rsl + lc.i1);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    xr0[i][j] = ldg_so(xb + (long)j * rsl, o0);
-                    xr1[i][j] = ldg_so(xb + (long)j * rsl, o1);
-                }
-            } else {
-                ld8_g8(xr0[i], xb, 32u * (unsigned)(g * rsl + p));
-            }
+            ld8_g8(xr0[i], xb, 32u * (unsigned)(g * rs + p));
         }
     };
     auto deposit = [&](float xs) __attribute__((always_inline)) {      // xs = the tile's block-floating-point input scale
@@ -159,7 +144,7 @@ __global__ __launch_bounds__(kNT48) __attribute__((amdgpu_waves_per_eu(FILM ? 2 
             float v[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                float t = LERP ? fmaf(1.f - lam[i], xr0[i][j], __fmul_rn(lam[i], xr1[i][j])) : xr0[i][j];   // = lerp_eval
+                const float t = xr0[i][j];
                 v[j] = fmaxf(t, 0.1f * t) * xs;                                                             // = leaky_relu(x, 0.1), scaled
             }
             uint4 p1, p2;
@@ -212,8 +197,8 @@ __global__ __launch_bounds__(kNT48) __attribute__((amdgpu_waves_per_eu(FILM ? 2 
             for (int s = 0; s < 3; ++s) ld8_g8(cr[s], cb + (long)s * 16 * rs, oc);
         }
         // residual values of this lane's 16 rows
-        float rv[RES ? 4 : 1][4];
-        if (RES == 1) {
+        float rv[FILM ? 4 : 1][4];
+        if constexpr (FILM) {
             const float* rb = RAG ? a.res + 8L * rt.off : a.res + (long)b * C * rs;
             const unsigned og = 32u * (unsigned)(4 * mt * rs + tc) + 16u * (unsigned)lh;      // group 4 mt + g, column tc, channels 4 lh ..
 #pragma unroll
@@ -225,21 +210,6 @@ __global__ __launch_bounds__(kNT48) __attribute__((amdgpu_waves_per_eu(FILM ? 2 
                     for (int q = 0; q < 4; ++q) rv[g][q] = 0.f;                      // rows past 48 do not exist
                 }
             }
-        } else if (RES == 2) {
-            const float* rb = RAG ? a.res + rt.off / rf : a.res + (long)b * C * a.rlin;
-            const Lerp lc = lerp_coord(tc, a.rscale, RAG ? len / rf : a.rlin);
-            const unsigned o0 = 4u * (unsigned)((32 * mt + 4 * lh) * a.rlin + lc.i0), o1 = 4u * (unsigned)((32 * mt + 4 * lh) * a.rlin + lc.i1);
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    float x0 = 0.f, x1 = 0.f;
-                    if (32 * mt + 8 * g < C) {
-                        x0 = ldg_so(rb + (long)(8 * g + q) * a.rlin, o0);
-                        x1 = ldg_so(rb + (long)(8 * g + q) * a.rlin, o1);
-                    }
-                    rv[g][q] = fmaf(lc.w0, x0, __fmul_rn(lc.w1, x1));      // = lerp_eval
-                }
         }
 
         // ---- conv: 9 K16 steps (slab, tap), this wave's m-tile x n-tile ------------------------------------
@@ -331,8 +301,10 @@ __global__ __launch_bounds__(kNT48) __attribute__((amdgpu_waves_per_eu(FILM ? 2 
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     float v = acc[4 * g + q] + bv[q];
-                    if (FILM) v = __fadd_rn(__fmul_rn(v, asc[4 * g + q] + bs[q]), ash[4 * g + q] + bh[q]);
-                    if (RES) v = __fadd_rn(v, rv[g][q]);
+                    if (FILM) {
+                        v = __fadd_rn(__fmul_rn(v, asc[4 * g + q] + bs[q]), ash[4 * g + q] + bh[q]);
+                        v = __fadd_rn(v, rv[g][q]);                                  // + residual
+                    }
                     v4[q] = v;
                     if (C5) {
                         xv[g][q] = v;
@@ -422,32 +394,32 @@ __global__ __launch_bounds__(kNT48) __attribute__((amdgpu_waves_per_eu(FILM ? 2 
     if (a.amax_y) amax_flush_wg(a.amax_y + mx_b, mx_run, Bi + 228);
 }
 
-template <bool FILM, bool LERP, int RES, bool C5 = false>
+template <bool FILM, bool C5 = false>
 int launch48(tvc_ctx* ctx, hipStream_t s, Conv48Args a, int B) {
     constexpr size_t lds = (size_t)(12 * kXP48 + 36 * 64 + (FILM ? 24 * 64 : 0) + (C5 ? 6 * 64 : 0)) * 16 + 240 * 4;
-    TVC_CHECK((lds_optin<conv48s_kernel<FILM, LERP, RES, C5>, conv48s_kernel<FILM, LERP, RES, C5, true>>(ctx, (int)lds, "conv48s")));
+    TVC_CHECK((lds_optin<conv48s_kernel<FILM, C5>, conv48s_kernel<FILM, C5, true>>(ctx, (int)lds, "conv48s")));
     a.tiles_per_utt = (a.len + kBN48 - 1) / kBN48;
     a.ntiles = a.tiles_per_utt * B;
     TVC_CHECK(rag_tiles(ctx, s, B, a.len, kBN48, &a.rag, &a.ntiles, "conv48s"));
     const int wpc = FILM ? 1 : 2;                     // persistent workgroups per CU
     const int grid = a.ntiles < wpc * ctx->ncu ? a.ntiles : wpc * ctx->ncu;
-    if (ctx->rag) hipLaunchKernelGGL((conv48s_kernel<FILM, LERP, RES, C5, true>), dim3(grid), dim3(kNT48), lds, s, a);
-    else hipLaunchKernelGGL((conv48s_kernel<FILM, LERP, RES, C5>), dim3(grid), dim3(kNT48), lds, s, a);
+    if (ctx->rag) hipLaunchKernelGGL((conv48s_kernel<FILM, C5, true>), dim3(grid), dim3(kNT48), lds, s, a);
+    else hipLaunchKernelGGL((conv48s_kernel<FILM, C5>), dim3(grid), dim3(kNT48), lds, s, a);
     return launch_check(ctx, "conv48s");
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Two consecutive 48-channel convs in ONE kernel: out = conv_b(lrelu(conv_a(lrelu(x)) + b_a)) [FiLM(cond), + residual], the
 // first conv's output never leaves the CU (Upsample 3: c1 -> c2 + FiLM1 + x_up, decoder.py:173-182; Downsample 2: c1 -> c2,
-// decoder.py:150-155).  The second conv's halo is 2 * dil_b samples of a 128-column tile (5 % recompute at dil_b = 3; the
-// c3 -> c4 pair, dil 27, would recompute 42 %: not fused), so a tile is 128 columns of the intermediate h and 128 - 2 dil_b
-// output columns.  Both convs' weights (and FiLM's) are resident in LDS; h is split into the second conv's operand tile by
+// decoder.py:150-155).  FILM: x is the level's low-rate input; x_up = F.interpolate(x) is evaluated while the input tile is
+// staged and again for the residual.  The second conv's halo is 2 * dil_b samples of a 128-column tile (5 % recompute at
+// dil_b = 3; the c3 -> c4 pair, dil 27, would recompute 42 %: not fused), so a tile is 128 columns of the intermediate h and
+// 128 - 2 dil_b output columns.  Both convs' weights (and FiLM's) are resident in LDS; h is split into the second conv's operand tile by
 // the first conv's epilogue with an exact per-tile power-of-two pre-scale (the tile's |max| meets in LDS behind the barrier
 // between the two convs); replicate padding of h at the utterance ends = a column clamp when the second conv reads it.
 struct Conv48PArgs {
-    const float* x;        // planar [B][48][len], or (LERP) the low-rate level output in the G8 layout [B][6][lin][8]
+    const float* x;        // planar [B][48][len], or (FILM) the low-rate level output in the G8 layout [B][6][lin][8]
     const float* cond;     // FILM: G8 [B][6][len][8] (Conv48Args)
-    const float* res;      // RES 2: the low-rate level output again (G8), interpolated here
     float* out;            // FILM: G8 (Upsample 3's x1); else planar [B][48][len]
     const u32x4* Aa;       // first / second conv image, 36 pieces each
     const u32x4* Ab;
@@ -457,13 +429,13 @@ struct Conv48PArgs {
     const float* amax_x;
     const float* amax_c;
     float* amax_y;
-    RagDev rag;            // RAG kernels (ragged.h): len / lin / rlin = row strides of the batch-wide tensors, tiles / extents from the table
-    int len, da, db, lin, rlin, tiles_per_utt, ntiles;
-    float lscale, rscale;
+    RagDev rag;            // RAG kernels (ragged.h): len / lin = row strides of the batch-wide tensors, tiles / extents from the table
+    int len, da, db, lin, tiles_per_utt, ntiles;
+    float lscale;
 };
 constexpr int kXPP = 136;      // input tile columns: 128 + 2 * dil_a (dil_a <= 4)
 
-template <bool FILM, bool LERP, int RES, bool RAG = false>
+template <bool FILM, bool RAG = false>
 __global__ __launch_bounds__(kNT48) __attribute__((amdgpu_waves_per_eu(2))) void conv48p_kernel(Conv48PArgs a) {
     constexpr int C = kC48, NT = kNT48, XP = kXPP, HP = 128;
     extern __shared__ __attribute__((aligned(16))) uint4 smem_p[];
@@ -479,8 +451,8 @@ __global__ __launch_bounds__(kNT48) __attribute__((amdgpu_waves_per_eu(2))) void
     const int rs = a.len, da = a.da, db = a.db;                 // rs = row stride of cond / out (= every utterance's length unless RAG, ragged.h)
     const int BNO = 128 - 2 * db;                              // output columns per tile
     const int XW = 128 + 2 * da;
-    const int rsl = LERP ? a.lin : rs;                         // row stride of x
-    const int xf = LERP ? rs / a.lin : 1, rf = RES == 2 ? rs / a.rlin : 1;     // RAG: an utterance's low-rate lengths = len / xf, len / rf
+    const int rsl = FILM ? a.lin : rs;                         // row stride of x
+    const int xf = FILM ? rs / a.lin : 1;                      // RAG: an utterance's low-rate length = len / xf
     int bh = 0;                                                // RAG: utterance hint of the table walk
     auto utt = [&](int tile) __attribute__((always_inline)) { return rag_tile<RAG>(a.rag, tile, a.tiles_per_utt, rs, bh).b; };
 
@@ -507,7 +479,7 @@ __global__ __launch_bounds__(kNT48) __attribute__((amdgpu_waves_per_eu(2))) void
 
     // staging items (8-channel group, column): 6 * XW <= 816 of them, two per thread
     constexpr int XPER = 2;
-    float xr0[XPER][8], xr1[LERP ? XPER : 1][8], lam[LERP ? XPER : 1];
+    float xr0[XPER][8], xr1[FILM ? XPER : 1][8], lam[FILM ? XPER : 1];
     int ig[XPER], ic[XPER];
 #pragma unroll
     for (int i = 0; i < XPER; ++i) {
@@ -518,15 +490,15 @@ __global__ __launch_bounds__(kNT48) __attribute__((amdgpu_waves_per_eu(2))) void
     }
     auto fetch = [&](int tile) __attribute__((always_inline)) {
         const RagTile rt = rag_tile<RAG>(a.rag, tile, a.tiles_per_utt, rs, bh);
-        const int len = rt.len, lin = LERP ? len / xf : len;
+        const int len = rt.len, lin = FILM ? len / xf : len;
         const int px0 = rt.tin * BNO - db - da;
-        const float* xb = RAG ? a.x + (LERP ? 8L * (rt.off / xf) : rt.off) : a.x + (long)rt.b * C * rsl;      // LERP: the low-rate level output, G8 (EpiBiasG8)
+        const float* xb = RAG ? a.x + (FILM ? 8L * (rt.off / xf) : rt.off) : a.x + (long)rt.b * C * rsl;      // FILM: the low-rate level output, G8 (EpiBiasG8)
 #pragma unroll
         for (int i = 0; i < XPER; ++i) {
             const int g = ig[i] > 5 ? 5 : ig[i];
             int p = px0 + ic[i];
             p = p < 0 ? 0 : (p > len - 1 ? len - 1 : p);
-            if (LERP) {
+            if (FILM) {
                 const Lerp lc = lerp_coord(p, a.lscale, lin);
                 lam[i] = lc.w1;
                 ld8_g8(xr0[i], xb, 32u * (unsigned)(g * rsl + lc.i0));
@@ -551,7 +523,7 @@ __global__ __launch_bounds__(kNT48) __attribute__((amdgpu_waves_per_eu(2))) void
             float v[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                float t = LERP ? fmaf(1.f - lam[i], xr0[i][j], __fmul_rn(lam[i], xr1[i][j])) : xr0[i][j];   // = lerp_eval
+                float t = FILM ? fmaf(1.f - lam[i], xr0[i][j], __fmul_rn(lam[i], xr1[i][j])) : xr0[i][j];   // = lerp_eval
                 v[j] = fmaxf(t, 0.1f * t) * xs;                                                             // = leaky_relu(x, 0.1), scaled
             }
             uint4 p1, p2;
@@ -602,17 +574,17 @@ __global__ __launch_bounds__(kNT48) __attribute__((amdgpu_waves_per_eu(2))) void
 #pragma unroll
             for (int s = 0; s < 3; ++s) ld8_g8(cr[s], cb + (long)s * 16 * rs, oc);
         }
-        float rv[RES ? 4 : 1][4];
-        if (RES == 2) {      // the interpolated residual: the low-rate level output again (G8)
-            const float* rb = RAG ? a.res + 8L * (rt.off / rf) : a.res + (long)b * C * a.rlin;
-            const Lerp lc = lerp_coord(tc, a.rscale, RAG ? len / rf : a.rlin);
-            const unsigned o0 = 32u * (unsigned)(4 * mt * a.rlin + lc.i0) + 16u * (unsigned)lh, o1 = 32u * (unsigned)(4 * mt * a.rlin + lc.i1) + 16u * (unsigned)lh;
+        float rv[FILM ? 4 : 1][4];
+        if constexpr (FILM) {      // the residual F.interpolate(x): the low-rate level output again (G8)
+            const float* rb = RAG ? a.x + 8L * (rt.off / xf) : a.x + (long)b * C * a.lin;
+            const Lerp lc = lerp_coord(tc, a.lscale, RAG ? len / xf : a.lin);
+            const unsigned o0 = 32u * (unsigned)(4 * mt * a.lin + lc.i0) + 16u * (unsigned)lh, o1 = 32u * (unsigned)(4 * mt * a.lin + lc.i1) + 16u * (unsigned)lh;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 float x0[4] = {0.f, 0.f, 0.f, 0.f}, x1[4] = {0.f, 0.f, 0.f, 0.f};
                 if (32 * mt + 8 * g < C) {
-                    ld4_g8(x0, rb + (long)g * 8 * a.rlin, o0);
-                    ld4_g8(x1, rb + (long)g * 8 * a.rlin, o1);
+                    ld4_g8(x0, rb + (long)g * 8 * a.lin, o0);
+                    ld4_g8(x1, rb + (long)g * 8 * a.lin, o1);
                 }
 #pragma unroll
                 for (int q = 0; q < 4; ++q) rv[g][q] = fmaf(lc.w0, x0[q], __fmul_rn(lc.w1, x1[q]));      // = lerp_eval
@@ -773,8 +745,10 @@ __global__ __launch_bounds__(kNT48) __attribute__((amdgpu_waves_per_eu(2))) void
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     float v = acc[4 * g + q] + bv[q];
-                    if (FILM) v = __fadd_rn(__fmul_rn(v, asc[4 * g + q] + bs[q]), ash[4 * g + q] + bh[q]);
-                    if (RES) v = __fadd_rn(v, rv[g][q]);
+                    if (FILM) {
+                        v = __fadd_rn(__fmul_rn(v, asc[4 * g + q] + bs[q]), ash[4 * g + q] + bh[q]);
+                        v = __fadd_rn(v, rv[g][q]);                                  // + residual
+                    }
                     v4[q] = v;
                     if (!FILM && live) stg_so(ob + (long)(8 * g + q) * rs, oo, v);
                 }
@@ -796,28 +770,28 @@ __global__ __launch_bounds__(kNT48) __attribute__((amdgpu_waves_per_eu(2))) void
     if (a.amax_y) amax_flush_wg(a.amax_y + mx_b, mx_run, Bi + 260);
 }
 
-template <bool FILM, bool LERP, int RES>
+template <bool FILM>
 int launch48p(tvc_ctx* ctx, hipStream_t s, Conv48PArgs a, int B) {
     constexpr size_t lds = (size_t)(12 * kXPP + 12 * 128 + 72 * 64 + (FILM ? 24 * 64 : 0)) * 16 + 272 * 4;
     static_assert(lds <= 160 * 1024, "LDS");
-    TVC_CHECK((lds_optin<conv48p_kernel<FILM, LERP, RES>, conv48p_kernel<FILM, LERP, RES, true>>(ctx, (int)lds, "conv48p")));
+    TVC_CHECK((lds_optin<conv48p_kernel<FILM>, conv48p_kernel<FILM, true>>(ctx, (int)lds, "conv48p")));
     const int bno = 128 - 2 * a.db;
     a.tiles_per_utt = (a.len + bno - 1) / bno;
     a.ntiles = a.tiles_per_utt * B;
     TVC_CHECK(rag_tiles(ctx, s, B, a.len, bno, &a.rag, &a.ntiles, "conv48p"));
     const int grid = a.ntiles < ctx->ncu ? a.ntiles : ctx->ncu;
-    if (ctx->rag) hipLaunchKernelGGL((conv48p_kernel<FILM, LERP, RES, true>), dim3(grid), dim3(kNT48), lds, s, a);
-    else hipLaunchKernelGGL((conv48p_kernel<FILM, LERP, RES>), dim3(grid), dim3(kNT48), lds, s, a);
+    if (ctx->rag) hipLaunchKernelGGL((conv48p_kernel<FILM, true>), dim3(grid), dim3(kNT48), lds, s, a);
+    else hipLaunchKernelGGL((conv48p_kernel<FILM>), dim3(grid), dim3(kNT48), lds, s, a);
     return launch_check(ctx, "conv48p");
 }
 
 }  // namespace
 
-// mode bits: 1 = the input is the low-rate tensor [B][48][lin] (F.interpolate fused into the staging), 2 = FiLM over cond,
-// residual: rlin == 0 and res != nullptr -> direct, rlin > 0 -> F.interpolate(res low-rate)
-int run_conv48s(tvc_ctx* ctx, hipStream_t s, const PackedW& w, const float* x, int lin, float lscale, const PackedW* film, const float* bsc,
-                const float* bsh, const float* cond, const float* res, int rlin, float rscale, float* out, int B, int len, int dil, const float* amax_x,
-                const float* amax_c, float* amax_y, const PackedW* c5, float* out5) {
+// One 48 -> 48 k3 conv over G8 tensors: film == nullptr: out = conv(lrelu(x)) + b (no residual);
+// else out = FiLM(conv(lrelu(x)) + b, cond) + res, and with c5 only c5's 24 rows of it are written (to out5).
+int run_conv48s(tvc_ctx* ctx, hipStream_t s, const PackedW& w, const float* x, const PackedW* film, const float* bsc, const float* bsh,
+                const float* cond, const float* res, float* out, int B, int len, int dil, const float* amax_x, const float* amax_c, float* amax_y,
+                const PackedW* c5, float* out5) {
     if (w.cin != kC48 || w.M != kC48 || w.taps != 3 || w.MT6 != 2 || !w.A6) return fail(ctx, TVC_ERR_ARG, "conv48s: 48 -> 48 channel k3 convs only");
     if (dil < 1 || dil > 27) return fail(ctx, TVC_ERR_ARG, "conv48s: dilation must be 1..27");
     if ((long)len * kC48 * 4 >= (1L << 32)) return fail(ctx, TVC_ERR_ARG, "conv48s: utterance too long for 32-bit byte offsets");
@@ -830,50 +804,47 @@ int run_conv48s(tvc_ctx* ctx, hipStream_t s, const PackedW& w, const float* x, i
     a.wsc = w.wscale;
     a.fsc = film ? film->wscale : nullptr;
     a.amax_x = amax_x; a.amax_c = amax_c; a.amax_y = amax_y;
-    a.len = len; a.dil = dil; a.lin = lin; a.rlin = rlin; a.lscale = lscale; a.rscale = rscale;
-    // (the level's tensors are in the G8 layout; the interpolating input / residual variants of this kernel read planar low-rate tensors and
-    // are not launched any more: the first half of Upsample 3 is run_conv48_pair)
-    if (lin > 0 || rlin > 0) return fail(ctx, TVC_ERR_ARG, "conv48s: interpolated inputs / residuals go through run_conv48_pair");
+    a.len = len; a.dil = dil;
     if (film) {
         if (!res) return fail(ctx, TVC_ERR_ARG, "conv48s: the FiLM variants carry a residual");
         if (c5) {   // FiLM2 + residual + c5: only c5's 24 rows leave the CU
-            if (rlin > 0 || !out5 || c5->M != 24 || c5->cin != kC48 || c5->taps != 1 || c5->MT6 != 1 || !c5->A6)
+            if (!out5 || c5->M != 24 || c5->cin != kC48 || c5->taps != 1 || c5->MT6 != 1 || !c5->A6)
                 return fail(ctx, TVC_ERR_ARG, "conv48s: the fused c5 is the 48 -> 24 1x1 after the second FiLM");
             a.W5 = reinterpret_cast<const u32x4*>(c5->A6);
             a.b5 = c5->bias;
             a.w5sc = c5->wscale;
             a.out5 = out5;
-            return launch48<true, false, 1, true>(ctx, s, a, B);
+            return launch48<true, true>(ctx, s, a, B);
         }
-        return launch48<true, false, 1>(ctx, s, a, B);
+        return launch48<true>(ctx, s, a, B);
     }
     if (res) return fail(ctx, TVC_ERR_ARG, "conv48s: plain convs carry no residual");
-    return launch48<false, false, 0>(ctx, s, a, B);
+    return launch48<false>(ctx, s, a, B);
 }
 
-// The fused pair (conv48p_kernel): x (or, lin > 0, the low-rate tensor it is interpolated from) -> conv_a(dil da) -> lrelu -> conv_b(dil db)
-// [-> FiLM(cond) + F.interpolate(res_low)] -> out.  film == nullptr: plain pair (Downsample), no residual.
+// The fused pair (conv48p_kernel): film == nullptr: x -> conv_a(dil da) -> lrelu -> conv_b(dil db) -> out (Downsample), no residual;
+// else x is the low-rate tensor [B][6][lin][8]: F.interpolate(x) -> conv_a -> lrelu -> conv_b -> FiLM(cond) + F.interpolate(x) -> out.
 int run_conv48_pair(tvc_ctx* ctx, hipStream_t s, const PackedW& wa, const PackedW& wb, const float* x, int lin, float lscale, const PackedW* film,
-                    const float* bsc, const float* bsh, const float* cond, const float* res, int rlin, float rscale, float* out, int B, int len, int da,
-                    int db, const float* amax_x, const float* amax_c, float* amax_y) {
+                    const float* bsc, const float* bsh, const float* cond, float* out, int B, int len, int da, int db, const float* amax_x,
+                    const float* amax_c, float* amax_y) {
     for (const PackedW* w : {&wa, &wb})
         if (w->cin != kC48 || w->M != kC48 || w->taps != 3 || w->MT6 != 2 || !w->A6) return fail(ctx, TVC_ERR_ARG, "conv48 pair: 48 -> 48 channel k3 convs only");
     if (da < 1 || da > 4 || db < 1 || db > 8) return fail(ctx, TVC_ERR_ARG, "conv48 pair: dilations (1..4, 1..8)");
     if ((long)len * kC48 * 4 >= (1L << 32)) return fail(ctx, TVC_ERR_ARG, "conv48 pair: utterance too long for 32-bit byte offsets");
-    if (film && (film->MT6 != 4 || !film->A6 || !cond || !bsc || !bsh || !res || rlin <= 0))
-        return fail(ctx, TVC_ERR_ARG, "conv48 pair: the FiLM variant needs the stacked image, both biases, cond and the low-rate residual");
+    if (film && (film->MT6 != 4 || !film->A6 || !cond || !bsc || !bsh))
+        return fail(ctx, TVC_ERR_ARG, "conv48 pair: the FiLM variant needs the stacked image, both biases and cond");
     Conv48PArgs a{};
-    a.x = x; a.cond = cond; a.res = res; a.out = out;
+    a.x = x; a.cond = cond; a.out = out;
     a.Aa = reinterpret_cast<const u32x4*>(wa.A6);
     a.Ab = reinterpret_cast<const u32x4*>(wb.A6);
     a.F6 = film ? reinterpret_cast<const u32x4*>(film->A6) : nullptr;
     a.bias_a = wa.bias; a.bias_b = wb.bias; a.bsc = bsc; a.bsh = bsh;
     a.wsc_a = wa.wscale; a.wsc_b = wb.wscale; a.fsc = film ? film->wscale : nullptr;
     a.amax_x = amax_x; a.amax_c = amax_c; a.amax_y = amax_y;
-    a.len = len; a.da = da; a.db = db; a.lin = lin; a.rlin = rlin; a.lscale = lscale; a.rscale = rscale;
-    if (film) return lin > 0 ? launch48p<true, true, 2>(ctx, s, a, B) : fail(ctx, TVC_ERR_ARG, "conv48 pair: the FiLM pair starts from the low-rate tensor");
-    if (lin > 0 || res) return fail(ctx, TVC_ERR_ARG, "conv48 pair: the plain pair has neither an interpolated input nor a residual");
-    return launch48p<false, false, 0>(ctx, s, a, B);
+    a.len = len; a.da = da; a.db = db; a.lin = lin; a.lscale = lscale;
+    if (film) return lin > 0 ? launch48p<true>(ctx, s, a, B) : fail(ctx, TVC_ERR_ARG, "conv48 pair: the FiLM pair starts from the low-rate tensor");
+    if (lin > 0) return fail(ctx, TVC_ERR_ARG, "conv48 pair: the plain pair has no interpolated input");
+    return launch48p<false>(ctx, s, a, B);
 }
 
 }  // namespace tvc

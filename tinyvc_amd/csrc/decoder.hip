@@ -271,15 +271,15 @@ int run_dsp(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* f0, const float* a
 }
 
 // =================================================================================================
-// FilterNet (decoder.py:193-233).  Every Conv1d runs on the split-precision fp16 MFMA path (conv3s.h):
+// FilterNet (decoder.py:193-233).  Every Conv1d runs on the split-precision fp16 MFMA path (split_fp16.h):
 //   level (channels @ rate)     kernels
 //   24 @ L        downs[0]      down0s_kernel (+ the 1/5-rate pick Downsample 1 starts from)
 //   24 -> 48 @ L/5  Downsample 1  down24f_kernel: the whole block in one launch (h1 / h2 on chip; c3 also accumulates down_res(xi) and writes Downsample 2's 1/4-rate input)
-//   48 -> 96 @ L/20 Downsample 2  conv48s_kernel (c1, c2: LDS-resident weights), conv3s (c3 + down_res as a second K phase)
-//   96 -> 192, 192 -> 384       conv3s x3 per block, same c3 fusion
-//   384, 192, 96  Upsample 0-2  conv3s: c1 (interpolating while it stages), c2 + FiLM1 + interpolated residual, c3, c4 + FiLM2 + residual;
-//                               c5 as a split-precision GEMM launch
-//   48            Upsample 3    conv48s_kernel x4, c5 inside the c4 + FiLM2 launch
+//   48 -> 96 @ L/20 Downsample 2  conv48p_kernel (c1 -> c2 in one launch, LDS-resident weights), conv3s (c3 + down_res as a second K phase)
+//   96 -> 192, 192 -> 384       conv_s2 (c1, c2), conv3s (c3, same down_res fusion)
+//   384, 192, 96  Upsample 0-2  conv_s2: c1 (interpolating while it stages), c3; film_s2: c2 + FiLM1 + interpolated residual, c4 + FiLM2 + residual;
+//                               conv3s for the convs outside conv_s2's / film_s2's preconditions; c5 as a split-precision GEMM launch
+//   48            Upsample 3    conv48p_kernel (c1 -> c2 + FiLM1 + interpolated residual), conv48s_kernel x2 (c3; c4 + FiLM2 + residual with c5 inside)
 //   24 @ L        Upsample 4    up24s_kernel x2 (second half = c3, c4, FiLM2, and c5 folded into the k7 output conv)
 // F.interpolate is never materialised: Downsample's 1/f pick / two-sample mean is written by the producing conv's
 // epilogue, Upsample's xf is evaluated while c1 stages its input and again by c2's epilogue for the residual.
@@ -416,7 +416,7 @@ int run_filter(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* content, const 
                 TVC_CHECK(run_down24_fused(ctx, s, d, xi, skip[i], y2, B, len, mxi, mout));
             } else {
                 if (d.cin == 48) {   // c1 -> c2 in one launch, weights resident in LDS, c1's output never leaves the CU (conv48s.hip)
-                    TVC_CHECK(run_conv48_pair(ctx, s, d.c1, d.c2, xi, 0, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0.f, h2, B, len, 1, 2, mxi, nullptr, mh2));
+                    TVC_CHECK(run_conv48_pair(ctx, s, d.c1, d.c2, xi, 0, 0.f, nullptr, nullptr, nullptr, nullptr, h2, B, len, 1, 2, mxi, nullptr, mh2));
                 } else {
                     TVC_CHECK(plain_conv(ctx, s, d.c1, xi, B, d.cin, len, 1, h1, BfpSlots{mxi, nullptr, mh1}));
                     TVC_CHECK(plain_conv(ctx, s, d.c2, h1, B, d.cin, len, 2, h2, BfpSlots{mh1, nullptr, mh2}));
@@ -472,11 +472,11 @@ int run_filter(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* content, const 
                 float* mout = slot((half ? S_UXU : S_UX1) + i);                  // the half's output
                 if (C == 48) {   // LDS-resident weights (conv48s.hip)
                     if (half == 0) {   // c1 (interpolating) -> c2 + FiLM1 + interpolated residual in one launch
-                        TVC_CHECK(run_conv48_pair(ctx, s, ca, cb, x, lin, lscale, &fw, bsc, bsh, cond, x, lin, lscale, xout, B, lo, da, db, ma_in, mcond, mout));
+                        TVC_CHECK(run_conv48_pair(ctx, s, ca, cb, x, lin, lscale, &fw, bsc, bsh, cond, xout, B, lo, da, db, ma_in, mcond, mout));
                     } else {
-                        TVC_CHECK(run_conv48s(ctx, s, ca, x1, 0, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0.f, h, B, lo, da, ma_in, nullptr, mh));
+                        TVC_CHECK(run_conv48s(ctx, s, ca, x1, nullptr, nullptr, nullptr, nullptr, nullptr, h, B, lo, da, ma_in, nullptr, mh));
                         // c4 + FiLM2 + residual + c5 (48 -> 24) in one launch: the level's output (and its |max|) is written directly
-                        TVC_CHECK(run_conv48s(ctx, s, cb, h, 0, 0.f, &fw, bsc, bsh, cond, x1, 0, 0.f, nullptr, B, lo, db, mh, mcond, slot(S_LEV + i), &u.c5, xlev[i]));
+                        TVC_CHECK(run_conv48s(ctx, s, cb, h, &fw, bsc, bsh, cond, x1, nullptr, B, lo, db, mh, mcond, slot(S_LEV + i), &u.c5, xlev[i]));
                     }
                 } else if (half == 0) {
                     TVC_CHECK(conv_film_half(ctx, s, ca, cb, fw, u.fu1, x, lin, lscale, da, db, h, cond, B, C, lo, xout, bsc, bsh, x, lin, lscale, ma_in, mh, mcond, mout));

@@ -396,13 +396,13 @@ int run_up24_split(tvc_ctx*, hipStream_t, const UpW& u, const float* x, const fl
 int run_down0_split(tvc_ctx*, hipStream_t, const float* blob, const float* source, const float* energy, float* planes, float* out_fp32, float* y2, int B, int len,
                     const float* amax_x, float* amax_y);
 int run_down24_fused(tvc_ctx*, hipStream_t, const DownW& d, const float* xi, float* out, float* y2, int B, int len, const float* amax_xi, float* amax_out);
-int run_conv48s(tvc_ctx*, hipStream_t, const PackedW& w, const float* x, int lin, float lscale, const PackedW* film, const float* bsc, const float* bsh,
-                const float* cond, const float* res, int rlin, float rscale, float* out, int B, int len, int dil, const float* amax_x, const float* amax_c,
-                float* amax_y, const PackedW* c5 = nullptr, float* out5 = nullptr);
+int run_conv48s(tvc_ctx*, hipStream_t, const PackedW& w, const float* x, const PackedW* film, const float* bsc, const float* bsh, const float* cond,
+                const float* res, float* out, int B, int len, int dil, const float* amax_x, const float* amax_c, float* amax_y,
+                const PackedW* c5 = nullptr, float* out5 = nullptr);
 
 int run_conv48_pair(tvc_ctx*, hipStream_t, const PackedW& wa, const PackedW& wb, const float* x, int lin, float lscale, const PackedW* film, const float* bsc,
-                    const float* bsh, const float* cond, const float* res, int rlin, float rscale, float* out, int B, int len, int da, int db,
-                    const float* amax_x, const float* amax_c, float* amax_y);
+                    const float* bsh, const float* cond, float* out, int B, int len, int da, int db, const float* amax_x, const float* amax_c,
+                    float* amax_y);
 
 // ConvNeXt-v2 layer on x [B, C, T] in place (convnext.py:49-58); tmp buffers from ws.
 int run_convnext(tvc_ctx*, hipStream_t, Ws&, const ConvNeXtW& w, float* x, int B, int T, float* amax_out = nullptr);

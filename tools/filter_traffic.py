@@ -26,12 +26,11 @@ def per_dispatch(db, counter):
 
 
 def is_up24(name, second):
-    """the fused ups.4 kernels: up24_kernel<Up24Cfg<W, D1, D2, SECOND, ...>> (fp32) or up24s_kernel<U24S<W, D1, D2, SECOND, E>> (split)."""
-    for tag in ("Up24Cfg", "U24S"):
-        if tag in name:
-            args = name.split(tag)[-1]
-            return ("true" in args) == second
-    return False
+    """the fused ups.4 kernels, up24s_kernel<U24S<W, D1, D2, SECOND, E>, RAG>: the fourth U24S argument tells the two halves apart."""
+    if "U24S<" not in name:
+        return False
+    args = name.split("U24S<", 1)[1].split(">", 1)[0].split(",")
+    return args[3].strip() == ("true" if second else "false")
 
 
 def filter_segments(disp):
