@@ -253,6 +253,35 @@ int tvc_convert_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t
                            int64_t N, float pitch_shift, const float* noise_angle, uint64_t seed, float* wave, int B, void* ws,
                            size_t ws_bytes);
 
+/* one speaker index per utterance ----------------------------------------------------------- */
+/* The calls above with a TABLE of prepared indices instead of one: prepared[b] (a device blob) and N[b] are HOST arrays of B entries,
+ * row b of the batch searches prepared[b] (the reference's form: match_features(source [B,768,T], reference [B,768,N]) is a bmm over the
+ * batch, feature_retrieval.py:15-33).  Blobs may differ in size and storage (fp32 / fp16), rows may share a blob.
+ *   - segments: a maximal run of consecutive query columns that search one blob is a segment (an equal-length batch: rows b..b' with one
+ *     blob; a ragged batch: the utterances of an in-kernel batch in its order).  Every pass of the search is ONE launch over all segments'
+ *     work units, a query tile never crosses a segment, and each segment has its own candidate-overflow flag: a segment takes exactly the
+ *     path its own B = 1 call takes.  A table whose rows all share one blob is one segment and launches what tvc_convert_f32 launches.
+ *   - per-row contract: row b is bit-identical to the single-index call (tvc_knn_match_f32 / tvc_convert_f32 / tvc_convert_ragged_f32)
+ *     with B = 1, prepared[b], the row's noise phases and its pitch shift - including the decoder's fp16-split scales, which take row b's
+ *     bound from prepared[b]'s own |max|.
+ *   - pitch_shifts: a HOST array of B semitone shifts (or NULL: every row takes pitch_shift).  The shift belongs to the (source, target)
+ *     pair, so a batch of different targets takes one per row.
+ *   - every entry is checked like the single-index calls' blob (non-null, N[b] >= 4, the N it was prepared for; a blob this process did not
+ *     prepare has its header read once, outside a capture only); nothing is launched when any entry fails (TVC_ERR_ARG).
+ *   - capture: the segment table, the per-row bounds' sources and the shifts travel as kernel ARGUMENTS (no host synchronisation), so a
+ *     captured graph replays the table of the call it recorded - re-capture when the table changes.  The seeded-draw rule still holds.
+ * Workspace: tvc_workspace_bytes_multi / _ragged_multi (they assume every row has a blob of its own: enough for any sharing). */
+int tvc_knn_match_multi_f32(tvc_ctx* ctx, void* stream, const float* src, const float* const* prepared, const int64_t* N,
+                            float* out, int64_t* idx_out, int B, int T, void* ws, size_t ws_bytes);
+int tvc_workspace_bytes_multi(tvc_ctx* ctx, int B, int64_t L, const int64_t* N, size_t* out_bytes);
+int tvc_convert_multi_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N,
+                          float pitch_shift, const float* pitch_shifts, const float* noise_angle, uint64_t seed, float* wave,
+                          int B, int64_t L, void* ws, size_t ws_bytes);
+int tvc_workspace_bytes_ragged_multi(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, const int64_t* N, size_t* out_bytes);
+int tvc_convert_ragged_multi_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens,
+                                 const float* const* prepared, const int64_t* N, float pitch_shift, const float* pitch_shifts,
+                                 const float* noise_angle, uint64_t seed, float* wave, int B, void* ws, size_t ws_bytes);
+
 /* streaming tail -------------------------------------------------------------------------- */
 /* StreamInfer.audio_callback after convert (reference module/infer/stream.py:74-95), batched over
  * S streams: y [S, Ly] converted buffers; sola_buf [S,1920] in/out; fade_in [1920] = the sin^2

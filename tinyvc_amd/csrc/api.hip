@@ -190,9 +190,16 @@ static int need_ready(tvc_ctx* ctx, int need) {
     return 0;
 }
 
+// One prepared index (and optionally one pitch shift) per row of a call (tvc_*_multi): host arrays indexed by the caller's row.
+struct RowIndex {
+    const float* const* blob;
+    const int64_t* N;
+    const float* shifts;       // nullptr: every row takes the call's pitch_shift
+};
+
 static int convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* wav, const float* prepared,
                         int64_t N, float pitch_shift, const float* angle,
-                        uint64_t seed, float* wave, int B, int64_t L) {
+                        uint64_t seed, float* wave, int B, int64_t L, const RowIndex* rows = nullptr) {
     const int T = (int)(L / kHop);
     float* spec = ws.get<float>((size_t)B * kBins * T);
     float* energy = ws.get<float>((size_t)B * L);
@@ -210,6 +217,31 @@ static int convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* wav, c
     float* spec_bound = emax + NB;
     float* enc_slots = spec_bound + NB;      // the encoder's three atomicMax slots: zeroed by the energy stage's pooled-maximum launch
     const bool bounds = true;
+    // one index per row: every utterance's matched-content bound is its own index's |max| (so its fp16-split scales, and its bits, are those
+    // of its own B = 1 call), and its runs of query columns go to the search as segments; per-row pitch shifts travel like the lengths
+    float* rowmax = rows ? ws.get<float>((size_t)NB) : nullptr;
+    float* rshift = rows && rows->shifts ? ws.get<float>((size_t)NB) : nullptr;
+    std::vector<KnnSegIn> segs;
+    if (rows) {
+        for (int i = 0; i < NB; ++i) {
+            const int r = ctx->rag ? ctx->rag->row[i] : i;
+            const int c0 = ctx->rag ? ctx->rag->pre[i] : i * T, nc = ctx->rag ? ctx->rag->tb[i] : T;
+            segs.push_back(KnnSegIn{rows->blob[r], rows->N[r], c0, nc});
+        }
+    } else {
+        segs.push_back(KnnSegIn{prepared, N, 0, B * T});
+    }
+    if (rows && !ws.dry) {
+        std::vector<const float*> bl(NB);
+        std::vector<int> sh(NB);
+        for (int i = 0; i < NB; ++i) {
+            const int r = ctx->rag ? ctx->rag->row[i] : i;
+            bl[i] = rows->blob[r];
+            if (rshift) std::memcpy(&sh[i], &rows->shifts[r], sizeof(int));
+        }
+        TVC_CHECK(run_knn_amax_rows(ctx, s, bl, rowmax));
+        if (rshift) TVC_CHECK(upload_ints(ctx, s, sh, reinterpret_cast<int*>(rshift)));
+    }
     size_t m = ws.mark();
     {
         ProfScope ps(ctx, s, ws, "stft");
@@ -223,16 +255,16 @@ static int convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* wav, c
     ws.release(m);
     {
         ProfScope ps(ctx, s, ws, "encoder");
-        TVC_CHECK(run_encoder(ctx, s, ws, spec, ssl, f0, nullptr, B, T, bounds ? spec_bound : nullptr, bounds ? enc_slots : nullptr, f0s, pitch_shift));
+        TVC_CHECK(run_encoder(ctx, s, ws, spec, ssl, f0, nullptr, B, T, bounds ? spec_bound : nullptr, bounds ? enc_slots : nullptr, f0s, pitch_shift, rshift));
     }
     ws.release(m);
     {
         ProfScope ps(ctx, s, ws, "knn");
-        TVC_CHECK(run_knn(ctx, s, ws, ssl, prepared, N, matched, nullptr, B, T));
+        TVC_CHECK(run_knn_segs(ctx, s, ws, ssl, segs.data(), (int)segs.size(), matched, nullptr, B, T));
     }
     ws.release(m);
-    TVC_CHECK(run_decoder(ctx, s, ws, matched, f0s, energy, angle, seed, wave, nullptr, nullptr, nullptr, B, T, ws.dry ? nullptr : knn_index_amax(prepared),
-                          bounds ? emax : nullptr));
+    TVC_CHECK(run_decoder(ctx, s, ws, matched, f0s, energy, angle, seed, wave, nullptr, nullptr, nullptr, B, T, ws.dry ? nullptr : (rows ? rowmax : knn_index_amax(prepared)),
+                          bounds ? emax : nullptr, rows ? 1 : 0));
     ws.release(m);
     return 0;
 }
@@ -519,13 +551,13 @@ int ragged_split(tvc_ctx* ctx, int cap, int B, int64_t Lmax, const int64_t* lens
 // the batches of a call, one after the other on the caller's stream, each from the start of the same workspace region: [tables][convert
 // workspace].  The drivers run a batch as ONE utterance of Ttot frames (B = 1) with ctx->rag set.
 int ragged_batches(tvc_ctx* ctx, hipStream_t s, Ws& ws, const std::vector<RagBatchPlan>& batches, const float* wav, int64_t Lmax, const float* prepared,
-                   int64_t N, float pitch_shift, const float* angle, uint64_t seed, float* wave) {
+                   int64_t N, float pitch_shift, const float* angle, uint64_t seed, float* wave, const RowIndex* rows = nullptr) {
     for (auto& p : batches) {
         ws.release(0);
         RagHost h;
         TVC_CHECK(rag_setup(ctx, s, ws, h, p.frames, p.rows, (int)(Lmax / kHop)));
         ctx->rag = &h;
-        const int rc = convert_impl(ctx, s, ws, wav, prepared, N, pitch_shift, angle, seed, wave, 1, (int64_t)p.Ttot * kHop);
+        const int rc = convert_impl(ctx, s, ws, wav, prepared, N, pitch_shift, angle, seed, wave, 1, (int64_t)p.Ttot * kHop, rows);
         ctx->rag = nullptr;
         TVC_CHECK(rc);
     }
@@ -580,6 +612,103 @@ int tvc_convert_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t
     TVC_HIP(ctx, hipMemsetAsync(wave, 0, (size_t)B * Lmax * sizeof(float), s));
     Ws ws(wsp, bytes, false);
     TVC_CHECK(ragged_batches(ctx, s, ws, batches, wav, Lmax, prepared, N, pitch_shift, noise_angle, seed, wave));
+    return walks_agree(ctx, __func__, ws.peak, need.peak);
+}
+
+// ---- one prepared index per row ------------------------------------------------------------------------------------------------
+// The table is checked whole before anything is enqueued: every entry non-null, N >= 4, and the blob_check of the single-index calls.
+static int rows_check(tvc_ctx* ctx, hipStream_t s, int B, const float* const* prepared, const int64_t* N, const char* what) {
+    if (!prepared || !N) return fail(ctx, TVC_ERR_ARG, "%s: prepared and N are host arrays of B entries", what);
+    for (int b = 0; b < B; ++b) {
+        if (!prepared[b]) return fail(ctx, TVC_ERR_ARG, "%s: prepared[%d] is NULL", what, b);
+        if (N[b] < 4) return fail(ctx, TVC_ERR_ARG, "%s: N[%d] = %lld: an index needs at least k=4 vectors", what, b, (long long)N[b]);
+    }
+    for (int b = 0; b < B; ++b) TVC_CHECK(blob_check(ctx, s, prepared[b], N[b], what));
+    return 0;
+}
+// the workspace queries plan every row as a segment of its own (distinct stand-in blobs): a call whose rows share blobs needs less
+static std::vector<const float*> dry_blobs(int B) {
+    std::vector<const float*> v((size_t)B);
+    for (int b = 0; b < B; ++b) v[b] = kDryPtr + 64 * (size_t)b;
+    return v;
+}
+
+int tvc_knn_match_multi_f32(tvc_ctx* ctx, void* stream, const float* src, const float* const* prepared, const int64_t* N, float* out,
+                            int64_t* idx_out, int B, int T, void* wsp, size_t ws_bytes) {
+    if (!ctx) return TVC_ERR_ARG;
+    if (!src || !out || B <= 0 || T <= 0 || (int64_t)B * T > 0x7fffffff) return fail(ctx, TVC_ERR_ARG, "tvc_knn_match_multi_f32: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    TVC_CHECK(rows_check(ctx, s, B, prepared, N, "tvc_knn_match_multi_f32"));
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<KnnSegIn> in((size_t)B);
+    for (int b = 0; b < B; ++b) in[b] = KnnSegIn{prepared[b], N[b], b * T, T};
+    TVC_RUN(run_knn_segs(ctx, s, ws, src, in.data(), B, out, idx_out, B, T));
+}
+
+int tvc_workspace_bytes_multi(tvc_ctx* ctx, int B, int64_t L, const int64_t* N, size_t* out_bytes) {
+    TVC_CHECK(need_ready(ctx, NEED_NONE));
+    if (!out_bytes || !N || B <= 0 || L <= 0 || L % kHop != 0) return fail(ctx, TVC_ERR_ARG, "tvc_workspace_bytes_multi: need B>0, L%%480==0, N[B]");
+    for (int b = 0; b < B; ++b)
+        if (N[b] < 4) return fail(ctx, TVC_ERR_ARG, "tvc_workspace_bytes_multi: N[%d] < 4", b);
+    const std::vector<const float*> blobs = dry_blobs(B);
+    const float shift = 0.f;
+    const RowIndex rows{blobs.data(), N, &shift};      // (a shift table takes workspace: counted; never read in this walk)
+    Ws ws(nullptr, 0, true);
+    TVC_CHECK(convert_impl(ctx, nullptr, ws, kDryPtr, kDryPtr, N[0], 0.f, nullptr, 0, kDryPtr, B, L, &rows));
+    *out_bytes = ws.peak + 4096;
+    return TVC_OK;
+}
+
+int tvc_convert_multi_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, float pitch_shift,
+                          const float* pitch_shifts, const float* noise_angle, uint64_t seed, float* wave, int B, int64_t L, void* wsp, size_t ws_bytes) {
+    TVC_CHECK(need_ready(ctx, NEED_ENC | NEED_DEC));
+    if (!wav || !wave || B <= 0 || L <= 0 || L % kHop) return fail(ctx, TVC_ERR_ARG, "tvc_convert_multi_f32: bad argument (L must be a positive multiple of 480)");
+    if (L < kNfft / 2 + 1) return fail(ctx, TVC_ERR_ARG, "tvc_convert_multi_f32: L must exceed 960 samples (STFT reflect padding, as torch.stft requires)");
+    hipStream_t s = (hipStream_t)stream;
+    TVC_CHECK(rows_check(ctx, s, B, prepared, N, "tvc_convert_multi_f32"));
+    TVC_CHECK(draw_under_capture(ctx, s, noise_angle, "tvc_convert_multi_f32"));
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    const RowIndex rows{prepared, N, pitch_shifts};
+    TVC_RUN(convert_impl(ctx, s, ws, wav, prepared[0], N[0], pitch_shift, noise_angle, seed, wave, B, L, &rows));
+}
+
+int tvc_workspace_bytes_ragged_multi(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, const int64_t* N, size_t* out_bytes) {
+    TVC_CHECK(need_ready(ctx, NEED_NONE));
+    if (!out_bytes || !lens || !N || B <= 0 || Lmax <= 0 || Lmax % kHop != 0)
+        return fail(ctx, TVC_ERR_ARG, "tvc_workspace_bytes_ragged_multi: need B>0, Lmax%%480==0, lens[B], N[B]");
+    for (int b = 0; b < B; ++b)
+        if (N[b] < 4) return fail(ctx, TVC_ERR_ARG, "tvc_workspace_bytes_ragged_multi: N[%d] < 4", b);
+    std::vector<RagBatchPlan> batches;
+    TVC_CHECK(ragged_split(ctx, ctx->rag_batch_frames, B, Lmax, lens, &batches));
+    const std::vector<const float*> blobs = dry_blobs(B);
+    const float shift = 0.f;
+    const RowIndex rows{blobs.data(), N, &shift};
+    Ws ws(nullptr, 0, true);
+    TVC_CHECK(ragged_batches(ctx, nullptr, ws, batches, kDryPtr, Lmax, kDryPtr, N[0], 0.f, nullptr, 0, kDryPtr, &rows));
+    *out_bytes = ((ws.peak + 4095) & ~size_t(4095)) + 4096;
+    return TVC_OK;
+}
+
+int tvc_convert_ragged_multi_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens, const float* const* prepared,
+                                 const int64_t* N, float pitch_shift, const float* pitch_shifts, const float* noise_angle, uint64_t seed, float* wave,
+                                 int B, void* wsp, size_t ws_bytes) {
+    TVC_CHECK(need_ready(ctx, NEED_ENC | NEED_DEC));
+    if (!wav || !lens || !wave || B <= 0 || Lmax <= 0 || Lmax % kHop)
+        return fail(ctx, TVC_ERR_ARG, "tvc_convert_ragged_multi_f32: bad argument (Lmax must be a positive multiple of 480)");
+    hipStream_t s = (hipStream_t)stream;
+    TVC_CHECK(rows_check(ctx, s, B, prepared, N, "tvc_convert_ragged_multi_f32"));
+    TVC_CHECK(draw_under_capture(ctx, s, noise_angle, "tvc_convert_ragged_multi_f32"));
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<RagBatchPlan> batches;
+    TVC_CHECK(ragged_split(ctx, ctx->rag_batch_frames, B, Lmax, lens, &batches));
+    const RowIndex rows{prepared, N, pitch_shifts};
+    Ws need(nullptr, 0, true);
+    TVC_CHECK(ragged_batches(ctx, s, need, batches, wav, Lmax, prepared[0], N[0], pitch_shift, noise_angle, seed, wave, &rows));
+    const size_t bytes = (need.peak + 4095) & ~size_t(4095);
+    if (bytes > ws_bytes) return fail(ctx, TVC_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", bytes, ws_bytes);
+    TVC_HIP(ctx, hipMemsetAsync(wave, 0, (size_t)B * Lmax * sizeof(float), s));
+    Ws ws(wsp, bytes, false);
+    TVC_CHECK(ragged_batches(ctx, s, ws, batches, wav, Lmax, prepared[0], N[0], pitch_shift, noise_angle, seed, wave, &rows));
     return walks_agree(ctx, __func__, ws.peak, need.peak);
 }
 

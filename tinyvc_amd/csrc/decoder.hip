@@ -518,7 +518,8 @@ int run_filter(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* content, const 
 
 int run_decoder(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* content, const float* f0,
                 const float* energy, const float* angle, uint64_t seed, float* wave, float* amps_out,
-                float* kernel_out, float* source_out, int B, int T, const float* content_bound, const float* energy_bound) {
+                float* kernel_out, float* source_out, int B, int T, const float* content_bound, const float* energy_bound,
+                int content_bound_stride) {
     const long L = (long)T * kHop;
     float* amps = amps_out ? amps_out : ws.get<float>((size_t)B * kHarm * T);
     float* kern = kernel_out ? kernel_out : ws.get<float>((size_t)B * kBins * T);
@@ -534,7 +535,7 @@ int run_decoder(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* content, const
     float* x0 = ws.get<float>((size_t)B * 384 * T);
     double* csum = ws.get<double>((size_t)B * kHarm * T);
     if (!ws.dry) {
-        TVC_CHECK(run_slot_prep(ctx, s, cmax, (3 + kFilterSlots) * NB, content_bound ? cmax : nullptr, content_bound, 0, 1.f, 0.f, energy_bound ? smax : nullptr,
+        TVC_CHECK(run_slot_prep(ctx, s, cmax, (3 + kFilterSlots) * NB, content_bound ? cmax : nullptr, content_bound, content_bound_stride, 1.f, 0.f, energy_bound ? smax : nullptr,
                                 energy_bound, 1, 1.f, 0.f, content_bound ? fslots + (size_t)kFilterSlotX * NB : nullptr, ctx->flt_in_bw, ctx->flt_in_bb,
                                 NB));      // (the dsp kernels raise smax to cat[source, energy]'s; the third: FilterNet's x0 slot from |content|max)
         if (!content_bound) TVC_CHECK(run_amax_rows(ctx, s, content, B, kSslDim, T, cmax));

@@ -356,7 +356,8 @@ struct PTop4 {
 
 constexpr int kPdWaves = 16;
 static __global__ __launch_bounds__(kPdWaves * 64) void pitch_decode_kernel(const float* __restrict__ logits, const float* __restrict__ freq,
-                                                                  float* __restrict__ f0, int B, int T, float* __restrict__ f0s, float shift) {
+                                                                  float* __restrict__ f0, int B, int T, float* __restrict__ f0s, float shift,
+                                                                  const float* __restrict__ shifts, const int* __restrict__ col2b) {
     __shared__ float sv[kPdWaves][4][64];     // [wave][entry][lane]: lanes along the fastest axis (the [lane][entry] order was a 4-way bank conflict)
     __shared__ int si[kPdWaves][4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -398,18 +399,19 @@ static __global__ __launch_bounds__(kPdWaves * 64) void pitch_decode_kernel(cons
     acc = __fadd_rn(acc, __fmul_rn(e3 / den, freq[top.i[3]]));
     const float fv = acc <= 20.f ? 0.f : acc;
     f0[n] = fv;
-    if (f0s) f0s[n] = shift_frequency_one(fv, shift);      // the caller's shift_frequency(f0, shift), in the same launch
+    // the caller's shift_frequency(f0, shift), in the same launch; shifts (optional): one per utterance (row b, or col2b[n] in a ragged batch)
+    if (f0s) f0s[n] = shift_frequency_one(fv, shifts ? shifts[col2b ? col2b[n] : b] : shift);
 }
 
 int run_pitch_decode(tvc_ctx* ctx, hipStream_t s, const float* logits, float* f0, int B, int T) {
     if (!ctx->pitch_freq) return fail(ctx, TVC_ERR_STATE, "pitch table not uploaded (tvc_set_pitch_table + tvc_finalize_weights)");
     const long ncols = (long)B * T;
-    hipLaunchKernelGGL(pitch_decode_kernel, dim3((unsigned)((ncols + 63) / 64)), dim3(kPdWaves * 64), 0, s, logits, ctx->pitch_freq, f0, B, T, (float*)nullptr, 0.f);
+    hipLaunchKernelGGL(pitch_decode_kernel, dim3((unsigned)((ncols + 63) / 64)), dim3(kPdWaves * 64), 0, s, logits, ctx->pitch_freq, f0, B, T, (float*)nullptr, 0.f, (const float*)nullptr, (const int*)nullptr);
     return launch_check(ctx, "pitch_decode");
 }
 
 int run_encoder(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* spec, float* ssl, float* f0,
-                float* logits, int B, int T, const float* spec_bound, float* zeroed_slots, float* f0_shifted, float shift) {
+                float* logits, int B, int T, const float* spec_bound, float* zeroed_slots, float* f0_shifted, float shift, const float* shifts) {
     const int ncols = B * T;
     float* xs = ws.get<float>((size_t)B * kSslCh * T);
     float* xp = ws.get<float>((size_t)B * kPitchCh * T);
@@ -448,7 +450,8 @@ int run_encoder(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* spec, float* s
         int rc = 0;
         if (!gemm_s2_try(&rc, ctx, sp, ctx->pit_out, xp, B, kPitchCh, T, 0, ep, xp_max)) rc = gemm_s_launch<ENC_MTB, ENC_NWV, ENC_BPC>(ctx, sp, ctx->pit_out, xp, B, kPitchCh, T, 0, ep, xp_max);
         TVC_CHECK(rc);
-        hipLaunchKernelGGL(pitch_decode_kernel, dim3((ncols + 63) / 64), dim3(kPdWaves * 64), 0, sp, lg, ctx->pitch_freq, f0, B, T, f0_shifted, shift);
+        hipLaunchKernelGGL(pitch_decode_kernel, dim3((ncols + 63) / 64), dim3(kPdWaves * 64), 0, sp, lg, ctx->pitch_freq, f0, B, T, f0_shifted, shift, shifts,
+                           shifts && ctx->rag ? ctx->rag->d_col2b : (const int*)nullptr);
     }
     TVC_CHECK(fk.end());
     for (int i = 0; i < 6; ++i) TVC_CHECK(run_convnext(ctx, s, wssl, ctx->ssl_mid[i], xs, B, T, i == 5 ? xs_max : nullptr));

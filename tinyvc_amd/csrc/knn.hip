@@ -19,6 +19,10 @@
 // Tie-break: equal similarities -> lower index first (torch.topk leaves it unspecified).
 #include <hip/hip_fp16.h>
 
+#include <cstring>
+#include <vector>
+
+#include "ragged.h"
 #include "small_kernels.h"
 #include "split_fp16.h"
 #include "tvc_common.h"
@@ -45,6 +49,69 @@ __host__ __device__ inline const float* blob_invmax(const float* blob, long Npad
 constexpr int KNN_BLOCKS = 1024;   // target workgroup count (query tiles x index splits)
 
 static inline int64_t npad128(int64_t N) { return (N + 127) / 128 * 128; }
+
+// ---- segments: one call, several prepared indices -------------------------------------------------------------------------
+// A segment is a maximal run of consecutive query columns that search the same blob (tvc_*_multi: one speaker index per row; a
+// ragged sub-batch's rows in its own order).  Query tiles (KNN_QT = C_QT = 256) never cross a segment; every pass is ONE launch
+// over the concatenated (segment, query tile, split) work units of the segments that take it, a workgroup finds its segment in the
+// unit prefix u[], and the per-query kernels (rescore, merge + gather) look it up in col2seg[].  Each segment has its own overflow
+// flag, so it takes exactly the path its own B = 1 call takes.  A call with one blob is one segment - the table then travels by
+// value in the kernel arguments (KnnSegs::one) and nothing is uploaded: the single-index launch sequence is the degenerate case.
+struct KnnSeg {
+    const float* blob;
+    int N, col0, ncols;        // query columns [col0, col0 + ncols) of the call
+    int two;                   // two-stage search (N >= KNN_COARSE_MIN); else the exact kernel only
+    int sample, t2;            // 256-vector tiles covered by coarse pass A / pass B
+    int nsA, tpsA, nsB, tpsB;  // coarse splits
+    int nsE, tpsE;             // exact kernel splits
+    int u[4];                  // first work unit of pass A, pass B and the exact kernel; [3]: first 256-query tile
+};
+static_assert(sizeof(KnnSeg) % sizeof(int) == 0, "uploaded as ints");
+struct KnnSegs {               // kernel argument
+    const KnnSeg* d;           // device table (n > 1)
+    int n;
+    KnnSeg one;                // the table when n == 1
+};
+// last segment whose key (u[F]; F == 4: col0) is <= v - segments without units of a launch share their successor's prefix and are skipped
+template <int F>
+__device__ __forceinline__ int seg_find(const KnnSegs& S, int v) {
+    if (S.n == 1) return 0;
+    int lo = 0, hi = S.n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        const int key = F == 4 ? S.d[mid].col0 : S.d[mid].u[F];
+        if (key <= v) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+// field by field: a select between the kernel-argument copy and the device table (selecting the whole struct put it on the stack)
+__device__ __forceinline__ KnnSeg seg_get(const KnnSegs& S, int i) {
+    KnnSeg g;
+    const bool one = S.n == 1;
+    const KnnSeg* __restrict__ d = S.d + (one ? 0 : i);
+#define TVC_SEG_FIELD(f) g.f = one ? S.one.f : d->f
+    TVC_SEG_FIELD(blob);
+    TVC_SEG_FIELD(N);
+    TVC_SEG_FIELD(col0);
+    TVC_SEG_FIELD(ncols);
+    TVC_SEG_FIELD(two);
+    TVC_SEG_FIELD(sample);
+    TVC_SEG_FIELD(t2);
+    TVC_SEG_FIELD(nsA);
+    TVC_SEG_FIELD(tpsA);
+    TVC_SEG_FIELD(nsB);
+    TVC_SEG_FIELD(tpsB);
+    TVC_SEG_FIELD(nsE);
+    TVC_SEG_FIELD(tpsE);
+    TVC_SEG_FIELD(u[0]);
+    TVC_SEG_FIELD(u[1]);
+    TVC_SEG_FIELD(u[2]);
+    TVC_SEG_FIELD(u[3]);
+#undef TVC_SEG_FIELD
+    return g;
+}
+__device__ __forceinline__ long seg_npad(const KnnSeg& g) { return ((long)g.N + 127) / 128 * 128; }
 
 // element (vector n, channel k) of a 128-vector-tiled MFMA-ordered image with P parts per (m-tile, step): the index of
 // part 0's 8-value piece row; row = lane & 31, k = 16 step + 8 (lane >> 5) + j
@@ -145,6 +212,25 @@ static __global__ __launch_bounds__(256) void index_amax_kernel(const T* __restr
 }
 const float* knn_index_amax(const float* prepared) { return prepared + 4; }
 
+// out[i] = the |max| of blob i (one index per utterance: each utterance's content bound is its own index's): the pointers travel as kernel
+// arguments, like ragged.h's upload_ints
+struct BlobChunk {
+    const float* p[480];
+};
+static __global__ void index_amax_rows_kernel(BlobChunk c, float* __restrict__ out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = c.p[i][4];
+}
+int run_knn_amax_rows(tvc_ctx* ctx, hipStream_t s, const std::vector<const float*>& blobs, float* out) {
+    for (size_t o = 0; o < blobs.size(); o += 480) {
+        BlobChunk c;
+        const int n = (int)(blobs.size() - o < 480 ? blobs.size() - o : 480);
+        for (int i = 0; i < n; ++i) c.p[i] = blobs[o + i];
+        hipLaunchKernelGGL(index_amax_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, s, c, out + o, n);
+    }
+    return launch_check(ctx, "knn_amax_rows");
+}
+
 int run_prepare_index(tvc_ctx* ctx, hipStream_t s, const float* index, float* prepared, int64_t N) {
     const long Npad = npad128(N);
     hipLaunchKernelGGL(blob_header_kernel, dim3(1), dim3(64), 0, s, prepared, KIND_F32, (long)N);
@@ -181,17 +267,38 @@ int run_prepare_index_f16(tvc_ctx* ctx, hipStream_t s, const void* rows16, float
 // its 4 waves each sum a quarter of the 768 channels (lanes along time, coalesced), partial sums of
 // squares meet in LDS in a fixed order, then every wave rescales its quarter.
 // qh (optional) = the same values in fp16, in the coarse pass's B-fragment order [256-query tile][K16 step][8-channel half][query][8]
-// (columns beyond ncols of the last tile are zero); cnt / flag (optional) = the two-stage search's per-query candidate
-// counters and its overflow flag, zeroed here.
+// (a segment's tiles are consecutive, its columns beyond its own count in its last tile are zero: the grid then runs over whole tiles);
+// cnt / flag (optional) = the two-stage search's per-query candidate counters and the segments' overflow flags, zeroed here;
+// col2seg (optional, several segments) = the segment of every column.
 constexpr int QN_WAVES = 16;     // waves per 64-column group: each squares / scales KD / 16 = 48 channels (strided rows: the loop is a latency chain)
 static __global__ __launch_bounds__(QN_WAVES * 64) void query_normalize_kernel(const float* __restrict__ src, float* __restrict__ qn, int B, int T,
-                                                                     uint4* __restrict__ qh, int* __restrict__ cnt, int* __restrict__ flag) {
+                                                                     uint4* __restrict__ qh, int* __restrict__ cnt, int* __restrict__ flag,
+                                                                     const KnnSegs segs, int* __restrict__ col2seg) {
     __shared__ float part[QN_WAVES][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long ncols = (long)B * T;
-    const long n = blockIdx.x * 64L + lane;
-    const bool ok = n < ncols;
-    const long nn = ok ? n : ncols - 1;
+    long n, nn;
+    bool ok;
+    int sg;
+    if (qh) {      // tile-aligned: the group's four 64-column quarters of one query tile belong to one segment
+        const int tile = blockIdx.x >> 2;
+        sg = seg_find<3>(segs, tile);
+        const KnnSeg g = seg_get(segs, sg);
+        const long loc = (long)(tile - g.u[3]) * 256 + (blockIdx.x & 3) * 64 + lane;
+        ok = loc < g.ncols;
+        n = g.col0 + loc;
+        nn = ok ? n : g.col0 + g.ncols - 1;
+    } else {
+        n = blockIdx.x * 64L + lane;
+        ok = n < ncols;
+        nn = ok ? n : ncols - 1;
+        sg = col2seg ? seg_find<4>(segs, (int)nn) : 0;
+    }
+    // bookkeeping first: nothing of it stays live across the 48-channel loads (this kernel runs at 128 registers)
+    if (blockIdx.x == 0 && flag)
+        for (int i = threadIdx.x; i < segs.n; i += QN_WAVES * 64) flag[i] = 0;
+    if (wave == 0 && ok && cnt) cnt[n] = 0;
+    if (wave == 0 && ok && col2seg) col2seg[n] = sg;
     const int b = (int)(nn / T), t = (int)(nn - (long)b * T);
     const float* p = src + (long)b * KD * T + t;
     float* q = qn + (long)b * KD * T + t;
@@ -209,9 +316,7 @@ static __global__ __launch_bounds__(QN_WAVES * 64) void query_normalize_kernel(c
 #pragma unroll
     for (int w = 1; w < QN_WAVES; ++w) ss += part[w][lane];      // fixed order
     const float den = sqrtf(ss) + 1e-6f;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && flag) *flag = 0;
-    if (wave == 0 && ok && cnt) cnt[n] = 0;
-    uint4* qhp = qh ? qh + (n >> 8) * (long)(STEPS * 2 * 256) + (n & 255) : nullptr;
+    uint4* qhp = qh ? qh + (blockIdx.x >> 2) * (long)(STEPS * 2 * 256) + (blockIdx.x & 3) * 64 + lane : nullptr;
 #pragma unroll
     for (int i = 0; i < KW; i += 8) {
         const int k = k0 + i;
@@ -308,9 +413,11 @@ __device__ __forceinline__ void split8_half(const u32x4 h8, uint4& p1, uint4& p2
 // NP = bf16 parts per index value in LDS (3: fp32 storage, 2: fp16 storage).
 constexpr int KNN_QT = 256;                                      // queries per workgroup
 constexpr int KNN_A_U4 = 12 * 64, KNN_X_U4 = 3 * 2 * KNN_QT;    // one LDS buffer each: 12 KiB + 24 KiB
+// (unit = this workgroup's work unit inside its segment; the segment's ncols queries start at column col0 of the call, the candidate
+// lists are [split][cstride][4] over all columns of the call)
 template <bool F16>
-__device__ __forceinline__ void knn_topk_body(const float* __restrict__ blob, long Npad, int N, const float* __restrict__ qn, int ncols, int T,
-                                              int nsplit, int tiles_per_split, float* __restrict__ cand_v, int* __restrict__ cand_i,
+__device__ __forceinline__ void knn_topk_body(const float* __restrict__ blob, long Npad, int N, const float* __restrict__ qn, int ncols, int col0, int cstride,
+                                              int T, int unit, int nsplit, int tiles_per_split, float* __restrict__ cand_v, int* __restrict__ cand_i,
                                               uint4* smem) {
     constexpr int NP = F16 ? 2 : 3;                    // parts per index value in LDS
     constexpr int GP = F16 ? 4 : 12;                   // 1 KiB pieces per (tile, step) in the global image
@@ -322,8 +429,8 @@ __device__ __forceinline__ void knn_topk_body(const float* __restrict__ blob, lo
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 2, wn = wave & 3;
     const int l31 = lane & 31, lh = lane >> 5;
-    const int split = blockIdx.x % nsplit;
-    const int qtile = blockIdx.x / nsplit;
+    const int split = unit % nsplit;
+    const int qtile = unit / nsplit;
     const int n0 = qtile * KNN_QT;
     const int mtiles = (int)(Npad >> 7);
     const int mt_lo = split * tiles_per_split;
@@ -338,7 +445,7 @@ __device__ __forceinline__ void knn_topk_body(const float* __restrict__ blob, lo
     {
         const int g = tid >> 8, pos = tid & 255;
         int n = n0 + pos;
-        n = n < ncols ? n : ncols - 1;
+        n = col0 + (n < ncols ? n : ncols - 1);
         const int b = n / T, t = n - b * T;
         qp = qn + ((long)b * KD + 8 * g) * T + t;
         xdst = g * KNN_QT + pos;
@@ -464,7 +571,7 @@ __device__ __forceinline__ void knn_topk_body(const float* __restrict__ blob, lo
         for (int e = 0; e < 16; ++e) t4.insert(mv[tid][e], mi[tid][e]);
         int n = n0 + tid;
         if (n < ncols) {
-            long o = ((long)split * ncols + n) * 4;
+            long o = ((long)split * cstride + col0 + n) * 4;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 cand_v[o + e] = t4.v[e];
@@ -474,54 +581,68 @@ __device__ __forceinline__ void knn_topk_body(const float* __restrict__ blob, lo
     }
 }
 
-static __global__ __launch_bounds__(512) void knn_topk_split_kernel(const float* __restrict__ blob, long Npad, int N,
-                                                                    const float* __restrict__ qn, int ncols, int T,
-                                                                    int nsplit, int tiles_per_split,
+// grid = the exact plan's units of every segment; flags = the segments' overflow flags (nullptr: no segment searches in two stages)
+static __global__ __launch_bounds__(512) void knn_topk_split_kernel(const KnnSegs segs, const float* __restrict__ qn, int cstride, int T,
                                                                     float* __restrict__ cand_v, int* __restrict__ cand_i,
-                                                                    const int* __restrict__ run_flag) {
+                                                                    const int* __restrict__ flags) {
     __shared__ __attribute__((aligned(16))) uint4 smem[2 * (KNN_A_U4 + KNN_X_U4)];      // 72 KiB; the final merge reuses 32 KiB of it
-    if (run_flag && *run_flag == 0) return;                      // two-stage search succeeded: nothing to do (uniform)
-    const int kind = reinterpret_cast<const int*>(blob)[1];      // uniform: which storage this prepared index uses
-    if (kind == KIND_F16) knn_topk_body<true>(blob, Npad, N, qn, ncols, T, nsplit, tiles_per_split, cand_v, cand_i, smem);
-    else knn_topk_body<false>(blob, Npad, N, qn, ncols, T, nsplit, tiles_per_split, cand_v, cand_i, smem);
+    const int si = seg_find<2>(segs, blockIdx.x);
+    const KnnSeg g = seg_get(segs, si);
+    if (g.two && flags[si] == 0) return;                         // the segment's two-stage search succeeded: nothing to do (uniform)
+    const int kind = reinterpret_cast<const int*>(g.blob)[1];    // uniform: which storage this prepared index uses
+    const int unit = blockIdx.x - g.u[2];
+    if (kind == KIND_F16) knn_topk_body<true>(g.blob, seg_npad(g), g.N, qn, g.ncols, g.col0, cstride, T, unit, g.nsE, g.tpsE, cand_v, cand_i, smem);
+    else knn_topk_body<false>(g.blob, seg_npad(g), g.N, qn, g.ncols, g.col0, cstride, T, unit, g.nsE, g.tpsE, cand_v, cand_i, smem);
 }
 
 // One workgroup = 32 consecutive query columns: merge split candidates -> top-4, write indices,
 // gather the 4 raw rows per query (coalesced along the feature axis), average, and write
-// out[b][k][t] through an LDS transpose so stores run along t.
+// out[b][k][t] through an LDS transpose so stores run along t.  Every query takes its segment's blob and lists (col2seg: several
+// segments; the 32 columns may straddle a segment boundary).  MULTI = false: one segment, whose blob the gather reads as a uniform value.
+template <bool MULTI>
 static __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
-                                                                      int nsplit, int ncols, int T, int N, long Npad,
-                                                                      const float* __restrict__ blob,
+                                                                      const KnnSegs segs, const int* __restrict__ col2seg, int ncols, int T,
                                                                       float* __restrict__ out, int64_t* __restrict__ idx_out,
                                                                       const float* __restrict__ rv, const int* __restrict__ ri,
-                                                                      const int* __restrict__ flag) {
+                                                                      const int* __restrict__ flags) {
     __shared__ int sel[32][4];
     __shared__ float tile[32][193];
-    if (flag && *flag == 0) {      // the two-stage search's rescored lists (one "split") are the result
-        cand_v = rv;
-        cand_i = ri;
-        nsplit = 1;
-    }
+    __shared__ const float* sblob[32];
+    __shared__ int skind[32], sN[32];
     const int tid = threadIdx.x;
     const int n0 = blockIdx.x * 32;
-    const int kind = reinterpret_cast<const int*>(blob)[1];
     if (tid < 32) {
         int n = n0 + tid;
+        const int nc = n < ncols ? n : ncols - 1;      // (a column past the end gathers row 0 of the last column's blob: never stored)
+        const int si = MULTI ? col2seg[nc] : 0;
+        const KnnSeg g = seg_get(segs, si);
+        const bool rescored = g.two && flags[si] == 0;  // the two-stage search's rescored lists (one "split") are the result
+        const float* cv = rescored ? rv : cand_v;
+        const int* ci = rescored ? ri : cand_i;
+        const int nsplit = rescored ? 1 : g.nsE;
+        const int N = g.N;
         Top4 t4;
         t4.init();
         if (n < ncols) {
             for (int s = 0; s < nsplit; ++s) {
                 long o = ((long)s * ncols + n) * 4;
-                for (int e = 0; e < 4; ++e) t4.insert(cand_v[o + e], cand_i[o + e]);
+                for (int e = 0; e < 4; ++e) t4.insert(cv[o + e], ci[o + e]);
             }
             for (int e = 0; e < 4; ++e) t4.i[e] = (unsigned)t4.i[e] < (unsigned)N ? t4.i[e] : 0;   // never gather through a sentinel
             if (idx_out)
                 for (int e = 0; e < 4; ++e) idx_out[(long)n * 4 + e] = (int64_t)t4.i[e];
         }
         for (int e = 0; e < 4; ++e) sel[tid][e] = n < ncols ? t4.i[e] : 0;
+        if (MULTI) {
+            sblob[tid] = g.blob;
+            skind[tid] = reinterpret_cast<const int*>(g.blob)[1];
+            sN[tid] = N;
+        }
     }
     __syncthreads();
     const int lane = tid & 63, wave = tid >> 6;
+    const float* const blob0 = segs.one.blob;
+    const int kind0 = MULTI ? 0 : reinterpret_cast<const int*>(blob0)[1], N0 = segs.one.N;
     for (int kc = 0; kc < KD; kc += 192) {
         // gather: wave handles queries wave, wave+4, ...; lanes run along k (3 x 64 = 192)
         // (four queries' 48 loads in flight per lane: one query at a time was eight serial round trips per wave and chunk - 48 us per
@@ -529,11 +650,16 @@ static __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const floa
         for (int q0 = wave; q0 < 32; q0 += 16) {
             float r[4][3][4];
 #pragma unroll
-            for (int qq = 0; qq < 4; ++qq)
+            for (int qq = 0; qq < 4; ++qq) {
+                const int q = q0 + 4 * qq;
+                const float* blob = MULTI ? sblob[q] : blob0;
+                const int kind = MULTI ? skind[q] : kind0, N = MULTI ? sN[q] : N0;
+                const long Npad = ((long)N + 127) / 128 * 128;
 #pragma unroll
                 for (int u = 0; u < 3; ++u)
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) r[qq][u][e] = blob_row_value(blob, kind, N, Npad, sel[q0 + 4 * qq][e], kc + lane + 64 * u);
+                    for (int e = 0; e < 4; ++e) r[qq][u][e] = blob_row_value(blob, kind, N, Npad, sel[q][e], kc + lane + 64 * u);
+            }
 #pragma unroll
             for (int qq = 0; qq < 4; ++qq)
 #pragma unroll
@@ -668,9 +794,11 @@ struct Top4V {   // four largest values
 // MFMA tiles (v_mfma_f32_32x32x16_f16); both operands arrive as ready 16-byte fragments rows (the index's fp16 image,
 // the queries' fp16 image), so staging is copies only: 8 loads + 8 ds_write_b128 per thread and K = 64 step, 32 MFMAs per
 // wave and step.  MODE 0: coarse top-4 values per (split, query) -> c4v.  MODE 1: rows with c >= theta -> candidate lists.
+// (per segment: qh / c4v / cnt / cand / candv / overflow come offset to the segment's first tile / column / flag, the segment's ncols
+// queries are its own, c4v rows are cstride columns apart, unit = the workgroup's unit inside the segment)
 template <bool F16, int MODE>
 static __device__ __forceinline__ void knn_coarse_body(const float* __restrict__ blob, long Npad, int N, const uint4* __restrict__ qh,
-                                                       int ncols, int nsplit, int tiles_per_split, int t2_cover,
+                                                       int ncols, int cstride, int unit, int nsplit, int tiles_per_split, int t2_cover,
                                                        float* __restrict__ c4v, int ns_sample,
                                                        int* __restrict__ cnt, int* __restrict__ cand, float* __restrict__ candv,
                                                        int* __restrict__ overflow) {
@@ -684,8 +812,8 @@ static __device__ __forceinline__ void knn_coarse_body(const float* __restrict__
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 2, wn = wave & 3;
     const int l31 = lane & 31, lh = lane >> 5;
-    const int split = blockIdx.x % nsplit;
-    const int qtile = blockIdx.x / nsplit;
+    const int split = unit % nsplit;
+    const int qtile = unit / nsplit;
     const int n0 = qtile * C_QT;
     const int mtiles = (int)(Npad >> 7);                         // 128-vector tiles of the image
     const int t_lo = split * tiles_per_split;
@@ -728,7 +856,7 @@ static __device__ __forceinline__ void knn_coarse_body(const float* __restrict__
                 Top4V t4;
                 t4.init();
                 for (int sp = 0; sp < ns_sample; ++sp) {
-                    const float4 v4 = *reinterpret_cast<const float4*>(c4v + ((long)sp * ncols + n) * 4);
+                    const float4 v4 = *reinterpret_cast<const float4*>(c4v + ((long)sp * cstride + n) * 4);
                     t4.insert(v4.x);
                     t4.insert(v4.y);
                     t4.insert(v4.z);
@@ -861,7 +989,7 @@ static __device__ __forceinline__ void knn_coarse_body(const float* __restrict__
         for (int e = 0; e < 16; ++e) t4.insert(mv[tid][e]);
         const int n = n0 + tid;
         if (n < ncols) {
-            const long o = ((long)split * ncols + n) * 4;
+            const long o = ((long)split * cstride + n) * 4;
 #pragma unroll
             for (int e = 0; e < 4; ++e) c4v[o + e] = t4.v[e];
         }
@@ -870,29 +998,43 @@ static __device__ __forceinline__ void knn_coarse_body(const float* __restrict__
 
 // The blob's kind lives in device memory (its header): one launch, the workgroup branches to the storage's instantiation of the body
 // (both fit the 256 registers a wave has at one 128 KiB workgroup per CU; two launches cost an empty 4.6 us one per pass).
+// grid = the pass's units of every two-stage segment (MODE 0: pass A, 1: pass B); flags = the segments' overflow flags
 template <int MODE>
-static __global__ __launch_bounds__(512) void knn_coarse_kernel(const float* __restrict__ blob, long Npad, int N, const uint4* __restrict__ qh,
-                                                                int ncols, int nsplit, int tiles_per_split, int t2_cover,
-                                                                float* __restrict__ c4v, int ns_sample,
-                                                                int* __restrict__ cnt, int* __restrict__ cand, float* __restrict__ candv,
-                                                                int* __restrict__ overflow) {
-    if (reinterpret_cast<const int*>(blob)[1] == KIND_F16)
-        knn_coarse_body<true, MODE>(blob, Npad, N, qh, ncols, nsplit, tiles_per_split, t2_cover, c4v, ns_sample, cnt, cand, candv, overflow);
+static __global__ __launch_bounds__(512) void knn_coarse_kernel(const KnnSegs segs, const uint4* __restrict__ qh, int cstride,
+                                                                float* __restrict__ c4v, int* __restrict__ cnt, int* __restrict__ cand,
+                                                                float* __restrict__ candv, int* __restrict__ flags) {
+    const int si = seg_find<MODE>(segs, blockIdx.x);
+    const KnnSeg g = seg_get(segs, si);
+    const int unit = blockIdx.x - g.u[MODE];
+    const int nsplit = MODE ? g.nsB : g.nsA, tps = MODE ? g.tpsB : g.tpsA, cover = MODE ? g.t2 : g.sample;
+    const uint4* q = qh + (long)g.u[3] * (STEPS * 2 * 256);
+    float* c4 = c4v + (long)g.col0 * 4;
+    int* ct = cnt + g.col0;
+    int* cd = cand + (long)g.col0 * C_CAP;
+    float* cdv = candv + (long)g.col0 * C_CAP;
+    if (reinterpret_cast<const int*>(g.blob)[1] == KIND_F16)
+        knn_coarse_body<true, MODE>(g.blob, seg_npad(g), g.N, q, g.ncols, cstride, unit, nsplit, tps, cover, c4, g.nsA, ct, cd, cdv, flags + si);
     else
-        knn_coarse_body<false, MODE>(blob, Npad, N, qh, ncols, nsplit, tiles_per_split, t2_cover, c4v, ns_sample, cnt, cand, candv, overflow);
+        knn_coarse_body<false, MODE>(g.blob, seg_npad(g), g.N, q, g.ncols, cstride, unit, nsplit, tps, cover, c4, g.nsA, ct, cd, cdv, flags + si);
 }
 
 // One wavefront per query: exact similarity of every candidate = (fp32 FMA chain of q_hat against the raw vector, lanes
 // along k, fixed-order shuffle reduction) * (1 / norm); top-4 in the library's order -> rv / ri [ncols][4].
 // A query with fewer than four candidates had non-finite coarse similarities (NaN / Inf samples upstream): rows 0..3 with
 // similarity +inf, what the exact kernel's NaN-as-maximum rule selects.
-static __global__ __launch_bounds__(256) void knn_rescore_kernel(const float* __restrict__ blob, long Npad, int N, const float* __restrict__ qn,
+// (the query's blob: its segment's, col2seg; a query of a segment that searches with the exact kernel only has no list: the wave leaves)
+static __global__ __launch_bounds__(256) void knn_rescore_kernel(const KnnSegs segs, const int* __restrict__ col2seg, const float* __restrict__ qn,
                                                                  int ncols, int T, const int* __restrict__ cnt, const int* __restrict__ cand,
                                                                  const float* __restrict__ candv, float* __restrict__ rv, int* __restrict__ ri) {
     constexpr int RG = 4;                           // candidates scored together
     const int lane = threadIdx.x & 63;
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= ncols) return;
+    const KnnSeg g = seg_get(segs, col2seg ? __builtin_amdgcn_readfirstlane(col2seg[n]) : 0);
+    if (!g.two) return;
+    const float* __restrict__ blob = g.blob;
+    const int N = g.N;
+    const long Npad = seg_npad(g);
     const int kind = reinterpret_cast<const int*>(blob)[1];
     const float* inv = blob_inv(blob, kind, N, Npad);
     const int b = n / T, t = n - b * T;
@@ -1069,22 +1211,84 @@ static __global__ __launch_bounds__(256) void knn_rescore_kernel(const float* __
     }
 }
 
-struct KnnPlan {
-    int ncols, qtiles, nsplit, tps;
-    long Npad;
+// ---- host plan ------------------------------------------------------------------------------------------------------------
+// splits of one pass over `cover` index tiles: about `blocks` workgroups over the call's `qtiles` query tiles
+static void split_plan(int blocks, int qtiles, int cover, int* ns, int* tps) {
+    int n = (blocks + qtiles - 1) / qtiles;
+    if (n > cover) n = cover;
+    if (n < 1) n = 1;
+    *tps = (cover + n - 1) / n;
+    *ns = (cover + *tps - 1) / *tps;
+}
+
+struct KnnCall {                 // one call's segments and launch geometry
+    std::vector<KnnSeg> seg;
+    int ncols = 0, cq = 0;       // query columns; 256-query tiles (each segment's own)
+    int units[3] = {0, 0, 0};    // workgroups of pass A, pass B, the exact kernel
+    int ns_cv = 1;               // splits the exact kernel's lists are sized for
+    bool two = false;            // some segment searches in two stages
 };
-static KnnPlan knn_plan(int B, int T, int64_t N) {
-    KnnPlan p;
-    p.ncols = B * T;
-    p.Npad = npad128(N);
-    p.qtiles = (p.ncols + KNN_QT - 1) / KNN_QT;
-    const int mtiles = (int)(p.Npad / 128);
-    int nsplit = (KNN_BLOCKS + p.qtiles - 1) / p.qtiles;
-    if (nsplit > mtiles) nsplit = mtiles;
-    if (nsplit < 1) nsplit = 1;
-    p.tps = (mtiles + nsplit - 1) / nsplit;
-    p.nsplit = (mtiles + p.tps - 1) / p.tps;
-    return p;
+
+// Segments from the callers' runs (in column order): adjacent runs of the same blob merge.  Every split count follows from the call's
+// total query tiles, so a one-segment call plans exactly what the single-index search always planned.
+static int knn_call_plan(tvc_ctx* ctx, const KnnSegIn* in, int nin, int ncols, KnnCall* c) {
+    static_assert(KNN_QT == C_QT, "one query tiling for both searches");
+    c->ncols = ncols;
+    for (int i = 0; i < nin; ++i) {
+        if (in[i].N > 0x7fffff00L) return fail(ctx, TVC_ERR_ARG, "index too large");
+        if (in[i].ncols <= 0) continue;
+        if (!c->seg.empty() && c->seg.back().blob == in[i].blob && c->seg.back().col0 + c->seg.back().ncols == in[i].col0) {
+            c->seg.back().ncols += in[i].ncols;
+            continue;
+        }
+        KnnSeg g{};
+        g.blob = in[i].blob;
+        g.N = (int)in[i].N;
+        g.col0 = in[i].col0;
+        g.ncols = in[i].ncols;
+        c->seg.push_back(g);
+    }
+    if (c->seg.empty()) return fail(ctx, TVC_ERR_ARG, "knn: no query columns");
+    for (auto& g : c->seg) c->cq += (g.ncols + C_QT - 1) / C_QT;
+    int mt_max = 1;
+    int tile = 0;
+    for (auto& g : c->seg) {
+        const long Npad = npad128(g.N);
+        const int mtiles = (int)(Npad / 128);
+        const int qt = (g.ncols + C_QT - 1) / C_QT;
+        mt_max = mtiles > mt_max ? mtiles : mt_max;
+        g.two = g.N >= KNN_COARSE_MIN;
+        g.t2 = (int)((Npad + C_MT - 1) / C_MT);          // 256-vector tiles
+        // pass A: an eighth of the index, at least 1280 vectors.  (A smaller sample lowers the threshold: longer lists - whose rows the
+        // rescoring wave's own threshold then drops unscored - and, past C_CAP entries, the exact fallback: a sixteenth sends the
+        // 100 000-vector index there.  Five tiles x 50 query tiles of the bench batch are one round of the chip.)
+        g.sample = g.t2 / 8 < 5 ? 5 : g.t2 / 8;
+        if (g.sample > g.t2) g.sample = g.t2;
+        // coarse passes: ~3 workgroups per CU's worth of work units (one resident workgroup per CU: 128 KiB of LDS)
+        split_plan(768, c->cq, g.sample, &g.nsA, &g.tpsA);
+        split_plan(768, c->cq, g.t2, &g.nsB, &g.tpsB);
+        split_plan(KNN_BLOCKS, c->cq, mtiles, &g.nsE, &g.tpsE);
+        g.u[0] = c->units[0];
+        g.u[1] = c->units[1];
+        g.u[2] = c->units[2];
+        g.u[3] = tile;
+        if (g.two) {
+            c->units[0] += qt * g.nsA;
+            c->units[1] += qt * g.nsB;
+            c->two = true;
+        }
+        c->units[2] += qt * g.nsE;
+        tile += qt;
+    }
+    // several segments: a bound that no split of the columns into segments exceeds (the workspace query of the multi-index calls plans
+    // every row as its own segment, a call whose rows share blobs has fewer)
+    if (c->seg.size() == 1) c->ns_cv = c->seg[0].nsE;
+    else {
+        const int cq_min = (ncols + C_QT - 1) / C_QT;
+        c->ns_cv = (KNN_BLOCKS + cq_min - 1) / cq_min;
+        c->ns_cv = c->ns_cv < mt_max ? c->ns_cv : mt_max;
+    }
+    return 0;
 }
 
 struct KnnLists {        // where the merge kernels find the per-query top-4 lists
@@ -1092,21 +1296,15 @@ struct KnnLists {        // where the merge kernels find the per-query top-4 lis
     int* ci = nullptr;
     float* rv = nullptr;    // two-stage search: [ncols][4]
     int* ri = nullptr;
-    int* flag = nullptr;    // 0 = the two-stage lists are valid; nullptr = exact kernel only
+    int* flag = nullptr;    // per segment: 0 = its two-stage lists are valid; nullptr = no segment searches in two stages
+    int* col2seg = nullptr; // [ncols] (several segments)
+    KnnSegs segs{};
 };
 
 template <int MODE>
-static int coarse_launch(tvc_ctx* ctx, hipStream_t s, const float* prepared, long Npad, int N, const uint4* qh, int ncols, int qtiles, int t2_cover,
-                         float* c4v, int ns_sample, int* cnt, int* cand, float* candv, int* flag, int* nsplit_out) {
+static int coarse_launch(tvc_ctx* ctx, hipStream_t s, const KnnCall& c, const KnnLists& L, const uint4* qh, float* c4v, int* cnt, int* cand, float* candv) {
     TVC_CHECK(lds_optin<knn_coarse_kernel<MODE>>(ctx, C_LDS, "knn coarse"));
-    int nsplit = (768 + qtiles - 1) / qtiles;           // ~3 workgroups per CU's worth of work units (one resident workgroup per CU: 128 KiB of LDS)
-    if (nsplit > t2_cover) nsplit = t2_cover;
-    if (nsplit < 1) nsplit = 1;
-    const int tps = (t2_cover + nsplit - 1) / nsplit;
-    nsplit = (t2_cover + tps - 1) / tps;
-    if (nsplit_out) *nsplit_out = nsplit;
-    hipLaunchKernelGGL((knn_coarse_kernel<MODE>), dim3((unsigned)(qtiles * nsplit)), dim3(512), C_LDS, s, prepared, Npad, N, qh, ncols, nsplit, tps, t2_cover,
-                       c4v, ns_sample, cnt, cand, candv, flag);
+    hipLaunchKernelGGL((knn_coarse_kernel<MODE>), dim3((unsigned)c.units[MODE]), dim3(512), C_LDS, s, L.segs, qh, c.ncols, c4v, cnt, cand, candv, L.flag);
     return 0;
 }
 
@@ -1115,58 +1313,59 @@ static int coarse_max_nsplit(int qtiles) { return (768 + qtiles - 1) / qtiles; }
 
 // query normalisation + the per-query top-4 lists; shared by the whole-index match and the index-sharded variant.
 // (The blob's kind lives in device memory - its header -, so the host cannot pick an instantiation: the kernels branch on it.)
-static int knn_candidates(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const float* prepared, int64_t N, int B, int T,
-                          const KnnPlan& p, KnnLists* L) {
-    if (N > 0x7fffff00L) return fail(ctx, TVC_ERR_ARG, "index too large");
+// The segment table of a several-segment call is uploaded as kernel arguments (ragged.h upload_ints): asynchronous, capturable.
+static int knn_candidates(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const KnnCall& c, int B, int T, KnnLists* L) {
+    const int nseg = (int)c.seg.size();
     float* qn = ws.get<float>((size_t)B * KD * T);
-    L->cv = ws.get<float>((size_t)p.nsplit * p.ncols * 4);
-    L->ci = ws.get<int>((size_t)p.nsplit * p.ncols * 4);
-    const bool two_stage = N >= KNN_COARSE_MIN;
+    L->cv = ws.get<float>((size_t)c.ns_cv * c.ncols * 4);
+    L->ci = ws.get<int>((size_t)c.ns_cv * c.ncols * 4);
+    int* dtab = nseg > 1 ? ws.get<int>((size_t)nseg * sizeof(KnnSeg) / sizeof(int)) : nullptr;
+    L->col2seg = nseg > 1 ? ws.get<int>((size_t)c.ncols) : nullptr;
     uint4* qh = nullptr;
     float* c4v = nullptr;
     int *cnt = nullptr, *cand = nullptr;
     float* candv = nullptr;
-    const int cq = (p.ncols + C_QT - 1) / C_QT;
-    if (two_stage) {
-        qh = ws.get<uint4>((size_t)cq * STEPS * 2 * 256);
-        c4v = ws.get<float>((size_t)coarse_max_nsplit(cq) * p.ncols * 4);
-        cnt = ws.get<int>((size_t)p.ncols);
-        cand = ws.get<int>((size_t)p.ncols * C_CAP);
-        candv = ws.get<float>((size_t)p.ncols * C_CAP);
-        L->rv = ws.get<float>((size_t)p.ncols * 4);
-        L->ri = ws.get<int>((size_t)p.ncols * 4);
-        L->flag = ws.get<int>(64);
+    if (c.two) {
+        qh = ws.get<uint4>((size_t)c.cq * STEPS * 2 * 256);
+        c4v = ws.get<float>((size_t)coarse_max_nsplit((c.ncols + C_QT - 1) / C_QT) * c.ncols * 4);
+        cnt = ws.get<int>((size_t)c.ncols);
+        cand = ws.get<int>((size_t)c.ncols * C_CAP);
+        candv = ws.get<float>((size_t)c.ncols * C_CAP);
+        L->rv = ws.get<float>((size_t)c.ncols * 4);
+        L->ri = ws.get<int>((size_t)c.ncols * 4);
+        L->flag = ws.get<int>((size_t)(nseg > 64 ? nseg : 64));
     }
     if (ws.dry) return 0;
-    const int nblk = two_stage ? cq * 4 : (p.ncols + 63) / 64;      // the fp16 query image is written for whole 256-query tiles
-    hipLaunchKernelGGL(query_normalize_kernel, dim3(nblk), dim3(QN_WAVES * 64), 0, s, src, qn, B, T, qh, cnt, L->flag);
-    if (two_stage) {
+    L->segs.n = nseg;
+    L->segs.one = c.seg[0];
+    L->segs.d = reinterpret_cast<const KnnSeg*>(dtab);
+    if (dtab) {
+        std::vector<int> words((size_t)nseg * sizeof(KnnSeg) / sizeof(int));
+        std::memcpy(words.data(), c.seg.data(), words.size() * sizeof(int));
+        TVC_CHECK(upload_ints(ctx, s, words, dtab));
+    }
+    const int nblk = c.two ? c.cq * 4 : (c.ncols + 63) / 64;      // the fp16 query image is written for whole 256-query tiles
+    hipLaunchKernelGGL(query_normalize_kernel, dim3(nblk), dim3(QN_WAVES * 64), 0, s, src, qn, B, T, qh, cnt, L->flag, L->segs, L->col2seg);
+    if (c.two) {
         ProfScope ps(ctx, s, ws, "knn.coarse+rescore");
-        const int t2 = (int)((p.Npad + C_MT - 1) / C_MT);          // 256-vector tiles
-        // pass A: an eighth of the index, at least 1280 vectors.  (A smaller sample lowers the threshold: longer lists - whose rows the
-        // rescoring wave's own threshold then drops unscored - and, past C_CAP entries, the exact fallback: a sixteenth sends the
-        // 100 000-vector index there.  Five tiles x 50 query tiles of the bench batch are one round of the chip.)
-        int sample = t2 / 8;
-        if (sample < 5) sample = 5;
-        if (sample > t2) sample = t2;
-        int nsA = 1;
-        TVC_CHECK((coarse_launch<0>(ctx, s, prepared, p.Npad, (int)N, qh, p.ncols, cq, sample, c4v, 0, cnt, cand, candv, L->flag, &nsA)));
-        TVC_CHECK((coarse_launch<1>(ctx, s, prepared, p.Npad, (int)N, qh, p.ncols, cq, t2, c4v, nsA, cnt, cand, candv, L->flag, nullptr)));
-        hipLaunchKernelGGL(knn_rescore_kernel, dim3((p.ncols + 3) / 4), dim3(256), 0, s, prepared, p.Npad, (int)N, qn, p.ncols, T, cnt, cand, candv, L->rv, L->ri);
+        TVC_CHECK((coarse_launch<0>(ctx, s, c, *L, qh, c4v, cnt, cand, candv)));
+        TVC_CHECK((coarse_launch<1>(ctx, s, c, *L, qh, c4v, cnt, cand, candv)));
+        hipLaunchKernelGGL(knn_rescore_kernel, dim3((c.ncols + 3) / 4), dim3(256), 0, s, L->segs, (const int*)L->col2seg, qn, c.ncols, T, cnt, cand, candv, L->rv, L->ri);
     }
     ProfScope ps(ctx, s, ws, "knn.exact");       // ~0 when the two-stage search succeeded (the kernel exits on the flag)
-    hipLaunchKernelGGL(knn_topk_split_kernel, dim3((unsigned)(p.qtiles * p.nsplit)), dim3(512), 0, s, prepared, p.Npad, (int)N, qn, p.ncols, T,
-                       p.nsplit, p.tps, L->cv, L->ci, (const int*)L->flag);
+    hipLaunchKernelGGL(knn_topk_split_kernel, dim3((unsigned)c.units[2]), dim3(512), 0, s, L->segs, qn, c.ncols, T, L->cv, L->ci, (const int*)L->flag);
     return 0;
 }
 
 int run_knn_topk(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const float* prepared, int64_t N,
                  float* sims_out, int64_t* idx_out, int B, int T) {
-    const KnnPlan p = knn_plan(B, T, N);
+    const KnnSegIn one{prepared, N, 0, B * T};
+    KnnCall c;
+    TVC_CHECK(knn_call_plan(ctx, &one, 1, B * T, &c));
     KnnLists L;
-    TVC_CHECK(knn_candidates(ctx, s, ws, src, prepared, N, B, T, p, &L));
+    TVC_CHECK(knn_candidates(ctx, s, ws, src, c, B, T, &L));
     if (ws.dry) return 0;
-    hipLaunchKernelGGL(knn_merge_kernel, dim3((p.ncols + 255) / 256), dim3(256), 0, s, L.cv, L.ci, p.nsplit, p.ncols, sims_out, idx_out, L.rv, L.ri, L.flag);
+    hipLaunchKernelGGL(knn_merge_kernel, dim3((c.ncols + 255) / 256), dim3(256), 0, s, L.cv, L.ci, c.seg[0].nsE, c.ncols, sims_out, idx_out, L.rv, L.ri, L.flag);
     return launch_check(ctx, "knn_topk");
 }
 
@@ -1181,15 +1380,25 @@ int run_knn_finish(tvc_ctx* ctx, hipStream_t s, const float* slots, float* out, 
     return launch_check(ctx, "knn_finish");
 }
 
+int run_knn_segs(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const KnnSegIn* in, int nin, float* out, int64_t* idx_out, int B, int T) {
+    KnnCall c;
+    TVC_CHECK(knn_call_plan(ctx, in, nin, B * T, &c));
+    KnnLists L;
+    TVC_CHECK(knn_candidates(ctx, s, ws, src, c, B, T, &L));
+    if (ws.dry) return 0;
+    if (L.col2seg)
+        hipLaunchKernelGGL(knn_merge_gather_kernel<true>, dim3((c.ncols + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)L.col2seg, c.ncols, T,
+                           out, idx_out, L.rv, L.ri, (const int*)L.flag);
+    else
+        hipLaunchKernelGGL(knn_merge_gather_kernel<false>, dim3((c.ncols + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)nullptr, c.ncols, T,
+                           out, idx_out, L.rv, L.ri, (const int*)L.flag);
+    return launch_check(ctx, "knn_match");
+}
+
 int run_knn(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const float* prepared, int64_t N,
             float* out, int64_t* idx_out, int B, int T) {
-    const KnnPlan p = knn_plan(B, T, N);
-    KnnLists L;
-    TVC_CHECK(knn_candidates(ctx, s, ws, src, prepared, N, B, T, p, &L));
-    if (ws.dry) return 0;
-    hipLaunchKernelGGL(knn_merge_gather_kernel, dim3((p.ncols + 31) / 32), dim3(256), 0, s, L.cv, L.ci, p.nsplit, p.ncols, T, (int)N, p.Npad,
-                       prepared, out, idx_out, L.rv, L.ri, L.flag);
-    return launch_check(ctx, "knn_match");
+    const KnnSegIn one{prepared, N, 0, B * T};
+    return run_knn_segs(ctx, s, ws, src, &one, 1, out, idx_out, B, T);
 }
 
 }  // namespace tvc

@@ -49,6 +49,10 @@ struct RagHost {                  // one ragged (sub-)batch of a call; lives for
 
 constexpr int kRagTabSlots = 24;      // distinct (rate, tile width) pairs a conversion launches with (13 today)
 
+// dst[0 .. src.size()) = src on stream s: the values travel as kernel ARGUMENTS (960 per launch) - asynchronous, no host buffer to keep
+// alive, capturable (a captured graph replays the values of the call it recorded)
+int upload_ints(tvc_ctx* ctx, hipStream_t s, const std::vector<int>& src, int* dst);
+
 // ints of device scratch a ragged batch of B utterances and Ttot frames needs (tb, pre, row, col2b, the tile tables)
 inline size_t rag_scratch_ints(int B, int Ttot) { return (size_t)3 * (B + 1) + (size_t)Ttot + (size_t)kRagTabSlots * (B + 1) + 64; }
 

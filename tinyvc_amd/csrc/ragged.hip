@@ -58,6 +58,8 @@ __global__ __launch_bounds__(1024) void rag_prefix_kernel(const int* __restrict_
         }
     }
 }
+}  // namespace
+
 int upload_ints(tvc_ctx* ctx, hipStream_t s, const std::vector<int>& src, int* dst) {
     for (size_t o = 0; o < src.size(); o += 960) {
         IntChunk c;
@@ -67,7 +69,6 @@ int upload_ints(tvc_ctx* ctx, hipStream_t s, const std::vector<int>& src, int* d
     }
     return launch_check(ctx, "rag upload");
 }
-}  // namespace
 
 int rag_setup(tvc_ctx* ctx, hipStream_t s, Ws& ws, RagHost& h, const std::vector<int>& frames, const std::vector<int>& rows, int Tmax) {
     h.B = (int)frames.size();

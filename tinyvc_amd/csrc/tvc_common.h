@@ -325,6 +325,7 @@ int run_noise_ifft(tvc_ctx*, hipStream_t, const float* kern, const float* angle,
 int run_energy(tvc_ctx*, hipStream_t, Ws&, const float* wav, float* energy, int B, int64_t L, float* emax = nullptr, float* spec_bound = nullptr,
                float* zero = nullptr, int nz = 0);      // (emax given: the pooled-maximum launch also zeroes zero[0 .. nz))
 const float* knn_index_amax(const float* prepared);
+int run_knn_amax_rows(tvc_ctx*, hipStream_t, const std::vector<const float*>& blobs, float* out);      // out[i] = *knn_index_amax(blobs[i])
 // out[b] = a * in[b * in_stride] + c for b < n: a |max| slot from the slot of the tensor it is a bounded function of (frontend.hip)
 int run_slot_affine(tvc_ctx*, hipStream_t, float* out, const float* in, int in_stride, float a, float c, int n);
 int run_slot_prep(tvc_ctx*, hipStream_t, float* zero, int nz, float* o1, const float* in1, int s1, float a1, float c1, float* o2, const float* in2, int s2, float a2,
@@ -338,10 +339,19 @@ constexpr int kFilterSlots = 41;      // run_filter's |max| slots per utterance 
 // spec_bound (optional): per-utterance upper bounds of |spec| (the slot of the input contraction); nullptr = one pass over spec measures it
 int run_encoder(tvc_ctx*, hipStream_t, Ws&, const float* spec, float* ssl, float* f0,
                 float* logits, int B, int T, const float* spec_bound = nullptr, float* zeroed_slots = nullptr,      // zeroed_slots: 3 x utterances floats already zeroed on this stream
-                float* f0_shifted = nullptr, float shift = 0.f);      // f0_shifted: also shift_frequency(f0, shift)
+                float* f0_shifted = nullptr, float shift = 0.f,      // f0_shifted: also shift_frequency(f0, shift)
+                const float* shifts = nullptr);                      // ... with shifts[utterance] (device, one per utterance) instead of `shift`
 int run_pitch_decode(tvc_ctx*, hipStream_t, const float* logits, float* f0, int B, int T);
 int run_knn(tvc_ctx*, hipStream_t, Ws&, const float* src, const float* prepared, int64_t N,
             float* out, int64_t* idx_out, int B, int T);
+// several prepared indices in one call (knn.hip segments): in[] = runs of query columns [col0, col0 + ncols) of the [B][768][T] queries
+// that search `blob` (prepared for N vectors), in column order, covering all B * T columns; adjacent runs of one blob are one segment
+struct KnnSegIn {
+    const float* blob;
+    int64_t N;
+    int col0, ncols;
+};
+int run_knn_segs(tvc_ctx*, hipStream_t, Ws&, const float* src, const KnnSegIn* in, int nin, float* out, int64_t* idx_out, int B, int T);
 int run_knn_topk(tvc_ctx*, hipStream_t, Ws&, const float* src, const float* prepared, int64_t N,
                  float* sims_out, int64_t* idx_out, int B, int T);
 // match_features for any k <= 8 and metric (0 cos, 1 IP, 2 L2) on the RAW index [768][N] in plain fp32 (knn_general.hip)
@@ -351,11 +361,13 @@ int run_knn_slots(tvc_ctx*, hipStream_t, const float* prepared, int64_t N, const
 int run_knn_finish(tvc_ctx*, hipStream_t, const float* slots, float* out, int B, int T);
 int run_shift(tvc_ctx*, hipStream_t, const float* f0, float* out, int64_t n, float semitones);
 int run_uniform_to_angle(tvc_ctx*, hipStream_t, float* u, int64_t n);
-// content_bound (optional): ONE float, an upper bound of |content| (the prepared index's |max| when content came out of the kNN match);
+// content_bound (optional): an upper bound of |content| (the prepared index's |max| when content came out of the kNN match): ONE float, or
+// with content_bound_stride = 1 one per utterance (a match against one index per utterance);
 // energy_bound (optional): per-utterance upper bounds of |energy|.  nullptr = measured by a pass over the tensor.
 int run_decoder(tvc_ctx*, hipStream_t, Ws&, const float* content, const float* f0,
                 const float* energy, const float* angle, uint64_t seed, float* wave, float* amps_out,
-                float* kernel_out, float* source_out, int B, int T, const float* content_bound = nullptr, const float* energy_bound = nullptr);
+                float* kernel_out, float* source_out, int B, int T, const float* content_bound = nullptr, const float* energy_bound = nullptr,
+                int content_bound_stride = 0);
 struct FilterTaps {   // optional copies of FilterNet's block outputs (tvc_filter_net_f32)
     float* skips[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     float* ups[4] = {nullptr, nullptr, nullptr, nullptr};

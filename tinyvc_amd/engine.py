@@ -240,6 +240,92 @@ class Engine:
         self._ok(self.lib.tvc_knn_match_f32(self.ctx, self._stream(), _ptr(src), _ptr(prepared), N, _ptr(out), _ptr(idx), B, T, p, n), "tvc_knn_match_f32")
         return (out, idx) if want_indices else out
 
+    # ---- one prepared index per row (tvc_*_multi) ----
+    def _table(self, prepared, Ns, B):
+        """(blob tensors, Ns) of B rows -> host arrays (void* [B], int64 [B]); the blobs must be 1-D float tensors on this device."""
+        prepared, Ns = list(prepared), [int(n) for n in Ns]
+        if len(prepared) != B or len(Ns) != B:
+            raise ValueError(f"one prepared index and one N per row: got {len(prepared)} blobs and {len(Ns)} sizes for {B} rows")
+        for b, t in enumerate(prepared):
+            _check_dev(t, f"prepared[{b}]", self.device)
+        return (ctypes.c_void_p * B)(*[t.data_ptr() for t in prepared]), (ctypes.c_int64 * B)(*Ns)
+
+    @staticmethod
+    def _shifts(pitch_shift, B):
+        """float -> (pitch_shift, NULL); a sequence / 1-D tensor of B floats -> (0, float [B])."""
+        if isinstance(pitch_shift, torch.Tensor):
+            if pitch_shift.dim() == 0:
+                return float(pitch_shift), None
+            pitch_shift = pitch_shift.detach().cpu().reshape(-1).tolist() if pitch_shift.dim() == 1 else None
+            if pitch_shift is None:
+                raise ValueError("pitch_shift: a float or a 1-D sequence of one shift per row")
+        if not hasattr(pitch_shift, "__len__"):
+            return float(pitch_shift), None
+        sh = [float(x) for x in pitch_shift]
+        if len(sh) != B:
+            raise ValueError(f"pitch_shift: {len(sh)} shifts for {B} rows")
+        return 0.0, (ctypes.c_float * B)(*sh)
+
+    def _grow_ws(self, nbytes):
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = None
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def knn_match_multi(self, src, prepared, Ns, want_indices=False):
+        """src [B, 768, T]; row b searches prepared[b] (a blob of knn_prepare, Ns[b] vectors) -> matched [B, 768, T] (, indices [B, T, 4]):
+        one call, every row equal to its own knn_match."""
+        src = _prep(src, "source", self.device)
+        B, C, T = src.shape
+        if C != spec.SSL_DIM:
+            raise ValueError(f"source must have {spec.SSL_DIM} channels")
+        blobs, ns = self._table(prepared, Ns, B)
+        out = torch.empty_like(src)
+        idx = torch.empty(B, T, 4, dtype=torch.int64, device=self.device) if want_indices else None
+        need = ctypes.c_size_t()
+        self._ok(self.lib.tvc_workspace_bytes_multi(self.ctx, B, T * spec.HOP, ns, ctypes.byref(need)), "tvc_workspace_bytes_multi")
+        ws = self._grow_ws(need.value)
+        self._ok(self.lib.tvc_knn_match_multi_f32(self.ctx, self._stream(), _ptr(src), blobs, ns, _ptr(out), _ptr(idx), B, T, _ptr(ws),
+                                                  ctypes.c_size_t(ws.numel())), "tvc_knn_match_multi_f32")
+        return (out, idx) if want_indices else out
+
+    def convert_multi(self, wav, prepared, Ns, pitch_shift, noise_angle=None, out=None):
+        """convert with one prepared index per row (and pitch_shift a float or one per row): tvc_convert_multi_f32."""
+        wav = _prep(wav, "wave", self.device)
+        B, L = wav.shape
+        if L % spec.HOP:
+            raise ValueError("waveform length must be a multiple of 480 (autopad_waveform)")
+        blobs, ns = self._table(prepared, Ns, B)
+        shift, shifts = self._shifts(pitch_shift, B)
+        a, seed = self._angle(noise_angle, B, L // spec.HOP)
+        wave = out if out is not None else torch.empty(B, L, dtype=_F32, device=self.device)
+        need = ctypes.c_size_t()
+        self._ok(self.lib.tvc_workspace_bytes_multi(self.ctx, B, L, ns, ctypes.byref(need)), "tvc_workspace_bytes_multi")
+        ws = self._grow_ws(need.value)
+        self._ok(self.lib.tvc_convert_multi_f32(self.ctx, self._stream(), _ptr(wav), blobs, ns, shift, shifts, _ptr(a), seed, _ptr(wave), B, L,
+                                                _ptr(ws), ctypes.c_size_t(ws.numel())), "tvc_convert_multi_f32")
+        return wave
+
+    def convert_ragged_multi(self, wav, lengths, prepared, Ns, pitch_shift, noise_angle=None):
+        """convert_ragged with one prepared index per row (and pitch_shift a float or one per row): tvc_convert_ragged_multi_f32."""
+        wav = _prep(wav, "wave", self.device)
+        B, Lmax = wav.shape
+        if Lmax % spec.HOP:
+            raise ValueError("the padded length must be a multiple of 480")
+        if len(lengths) != B:
+            raise ValueError(f"lengths: {len(lengths)} entries for {B} rows")
+        blobs, ns = self._table(prepared, Ns, B)
+        shift, shifts = self._shifts(pitch_shift, B)
+        lens = (ctypes.c_int64 * B)(*[int(x) for x in lengths])
+        a, seed = self._angle(noise_angle, B, Lmax // spec.HOP)
+        need = ctypes.c_size_t()
+        self._ok(self.lib.tvc_workspace_bytes_ragged_multi(self.ctx, B, Lmax, lens, ns, ctypes.byref(need)), "tvc_workspace_bytes_ragged_multi")
+        ws = self._grow_ws(need.value)
+        wave = torch.empty(B, Lmax, dtype=_F32, device=self.device)
+        self._ok(self.lib.tvc_convert_ragged_multi_f32(self.ctx, self._stream(), _ptr(wav), Lmax, lens, blobs, ns, shift, shifts, _ptr(a), seed,
+                                                       _ptr(wave), B, _ptr(ws), ctypes.c_size_t(ws.numel())), "tvc_convert_ragged_multi_f32")
+        return wave
+
     # ---- index-sharded match (one prepared index shard per rank; merged by parallel.match_features_sharded) ----
     METRICS = {"cos": 0, "IP": 1, "L2": 2}
 

@@ -4,8 +4,24 @@ import torch
 
 from .. import utils
 from .._base import HipModule
-from ..tinyvc import Decoder, Encoder, match_features
-from ..tinyvc.feature_retrieval import prepare_reference
+from ..tinyvc import Decoder, Encoder
+from ..tinyvc.feature_retrieval import check_references, prepare_reference, prepare_references
+
+
+def _per_row_shift(pitch_shift, B):
+    """None for a scalar shift; else the list of B floats (a sequence or 1-D tensor), checked on the host."""
+    if isinstance(pitch_shift, torch.Tensor):
+        if pitch_shift.dim() == 0:
+            return None
+        if pitch_shift.dim() != 1:
+            raise ValueError("pitch_shift: a float or a 1-D sequence of one shift per row")
+        pitch_shift = pitch_shift.detach().cpu().tolist()
+    if not hasattr(pitch_shift, "__len__"):
+        return None
+    sh = [float(x) for x in pitch_shift]
+    if len(sh) != B:
+        raise ValueError(f"pitch_shift: {len(sh)} shifts for a batch of {B}")
+    return sh
 
 
 class Generator(HipModule):
@@ -36,28 +52,40 @@ class Generator(HipModule):
         `lengths` (extension): a RAGGED batch - row b of wf holds an utterance of lengths[b] samples, zero-padded behind it.
         Every utterance is converted over its own length (padded to a multiple of 480), exactly as if it were converted
         alone (the reference's loop, infer.py:60-66; GRN and the oscillator's phase run over the whole time axis, so padding
-        to a common length would change the results); row b of the result holds it, zeros behind."""
+        to a common length would change the results); row b of the result holds it, zeros behind.
+        One index per row: tgt [B, 768, N] (the reference's form) or a list of B [1, 768, N_b] tensors (extension: fp32 or fp16,
+        any N_b), equal or ragged batches, in one call (tvc_convert_multi_f32 / tvc_convert_ragged_multi_f32: row b equals its own
+        B = 1 conversion against tgt[b]).  `pitch_shift` (extension): a float, or a sequence / 1-D tensor of one shift per row."""
+        B = wf.shape[0] if wf.dim() == 2 else 1
+        multi = isinstance(tgt, (list, tuple)) or (isinstance(tgt, torch.Tensor) and tgt.dim() == 3 and tgt.shape[0] != 1)
+        if multi:
+            check_references(tgt, B)           # malformed tables / shift lists are refused before any engine or device work
+        shifts = _per_row_shift(pitch_shift, B)
         wf = utils.autopad_waveform(self._input_device(wf))
-        tgt = self._input_device(tgt)
         eng = self.engine(wf.device)
         B, L = wf.shape
         if noise_angle is not None:
             noise_angle = self._input_device(noise_angle)
+        if multi:
+            tgt = [self._input_device(t) for t in tgt] if isinstance(tgt, (list, tuple)) else self._input_device(tgt)
+        else:
+            tgt = self._input_device(tgt)
+        lens = None
         if lengths is not None:
             lens = [-(-int(n) // 480) * 480 for n in lengths]
             if len(lens) != B or max(lens) > L or min(lens) <= 960:
                 raise ValueError("lengths: one entry per row, each in (960, L]")
-            if tgt.shape[0] != 1:
-                raise ValueError("a ragged batch takes one shared index")
+        if not multi and shifts is None:
             blob, n = prepare_reference(tgt)
-            return eng.convert_ragged(wf, lens, blob, n, pitch_shift, noise_angle)
-        if tgt.shape[0] == 1:
-            blob, n = prepare_reference(tgt)
+            if lens is not None:
+                return eng.convert_ragged(wf, lens, blob, n, pitch_shift, noise_angle)
             return eng.convert(wf, blob, n, pitch_shift, noise_angle)
-        # one index per utterance: staged path
-        spec = eng.stft_mag(wf)
-        energy = eng.energy(wf)
-        z, f0, _ = eng.encoder(spec)
-        z = match_features(z, tgt)
-        f0 = eng.shift_frequency(f0, pitch_shift)
-        return eng.decoder(z, f0, energy, noise_angle)
+        if multi:
+            blobs, ns = prepare_references(tgt)
+        else:                                   # one shared index, a shift per row: the shared blob in every row (one segment)
+            blob, n = prepare_reference(tgt)
+            blobs, ns = [blob] * B, [n] * B
+        shift = shifts if shifts is not None else float(pitch_shift)
+        if lens is not None:
+            return eng.convert_ragged_multi(wf, lens, blobs, ns, shift, noise_angle)
+        return eng.convert_multi(wf, blobs, ns, shift, noise_angle)

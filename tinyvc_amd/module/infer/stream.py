@@ -15,6 +15,9 @@ def _fade_windows(crossfade_size, device):
 
 
 class BatchedStreamInfer:
+    """`target`: one index for every stream ([1, 768, N]) or one per stream ([S, 768, N], or a list of S [1, 768, N_s] tensors), prepared
+    once and cached on those tensors; `pitch_shift`: a float or one per stream."""
+
     def __init__(self, generator: Generator, n_streams=1, target=None, pitch_shift=0., device=None,
                  block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False):
         self.generator = generator
@@ -65,8 +68,13 @@ class BatchedStreamInfer:
         one), the prepared index riding on `target`, plus the scalars captured by value."""
         eng = self.generator.engine(self.device)          # re-packs the weights first if a parameter changed
         ws, tgt = eng._ws, self.target
+        tgts = tgt if isinstance(tgt, (list, tuple)) else [tgt]      # one index per stream: every blob's tensor
+        ps = self.pitch_shift
+        if isinstance(ps, torch.Tensor):
+            ps = ps.detach().cpu().reshape(-1).tolist()
+        shifts = tuple(float(x) for x in ps) if hasattr(ps, "__len__") else float(ps)
         return (eng.weights_key, ws.data_ptr() if ws is not None else 0, ws.numel() if ws is not None else 0,
-                id(tgt), tgt._version, tgt.data_ptr(), float(self.pitch_shift), bool(self.use_phase_vocoder))
+                tuple((id(t), t._version, t.data_ptr()) for t in tgts), shifts, bool(self.use_phase_vocoder))
 
     @torch.no_grad()
     def audio_callback(self, blocks, noise_angle=None):

@@ -21,6 +21,51 @@ def prepare_reference(reference):
     return blob, n
 
 
+def check_references(tgt, B=None):
+    """Shape check of a multi-index target, on the host (no engine, no device work): a [B, 768, N] tensor or a list of B [1, 768, N_b]
+    tensors (fp32 or fp16).  Returns the number of indices; raises ValueError when the form is malformed or B does not match."""
+    if isinstance(tgt, torch.Tensor):
+        if tgt.dim() != 3 or tgt.shape[1] != 768 or tgt.shape[0] < 1 or tgt.shape[2] < 4:
+            raise ValueError(f"target indices: a [B, 768, N >= 4] tensor, got {tuple(tgt.shape)}")
+        n = tgt.shape[0]
+    elif isinstance(tgt, (list, tuple)):
+        if not tgt:
+            raise ValueError("target indices: an empty list")
+        for i, t in enumerate(tgt):
+            if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[0] != 1 or t.shape[1] != 768 or t.shape[2] < 4:
+                raise ValueError(f"target indices: element {i} must be a [1, 768, N >= 4] tensor, got "
+                                 f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+            if t.dtype not in (torch.float32, torch.float16):
+                raise ValueError(f"target indices: element {i} must be fp32 or fp16, got {t.dtype}")
+        n = len(tgt)
+    else:
+        raise ValueError(f"target indices: a tensor or a list of tensors, got {type(tgt).__name__}")
+    if B is not None and n != B:
+        raise ValueError(f"{n} target indices for a batch of {B}")
+    return n
+
+
+def prepare_references(tgt):
+    """One prepared index per row: `tgt` is a [B, 768, N] tensor (the reference's form) or a list of B [1, 768, N_b] tensors (speakers with
+    different amounts of target audio, fp32 or fp16 storage) -> (blobs [B], Ns [B]).  Cached on the tensor object(s) the caller holds,
+    keyed by their version and device like prepare_reference - never on slices, so a second call prepares nothing."""
+    check_references(tgt)
+    if isinstance(tgt, (list, tuple)):
+        pairs = [prepare_reference(t) for t in tgt]
+        return [p[0] for p in pairs], [p[1] for p in pairs]
+    hit = getattr(tgt, "_tvc_prepared_rows", None)
+    if hit is not None and hit[0] == tgt._version and hit[1] == str(tgt.device):
+        return hit[2], hit[3]
+    eng = default_engine(tgt.device)
+    pairs = [eng.knn_prepare(tgt[b:b + 1]) for b in range(tgt.shape[0])]
+    blobs, ns = [p[0] for p in pairs], [p[1] for p in pairs]
+    try:
+        tgt._tvc_prepared_rows = (tgt._version, str(tgt.device), blobs, ns)
+    except Exception:
+        pass
+    return blobs, ns
+
+
 @torch.no_grad()
 def match_features(source, reference, k=4, alpha=0.0, metrics="cos", return_indices=False):
     """source [B, C, T], reference [B or 1, C, N] -> [B, C, T] (mean of the k nearest index vectors under `metrics` in
@@ -48,15 +93,9 @@ def match_features(source, reference, k=4, alpha=0.0, metrics="cos", return_indi
         res = eng.knn_match(source, blob, n, want_indices=return_indices)
         out, idx = res if return_indices else (res, None)
     elif reference.shape[0] == B:
-        outs, idxs = [], []
-        for b in range(B):                       # one index per utterance
-            blob, n = prepare_reference(reference[b:b + 1])
-            res = eng.knn_match(source[b:b + 1], blob, n, want_indices=return_indices)
-            o, i = res if return_indices else (res, None)
-            outs.append(o)
-            idxs.append(i)
-        out = torch.cat(outs, 0)
-        idx = torch.cat(idxs, 0) if return_indices else None
+        blobs, ns = prepare_references(reference)      # one index per utterance, one call (tvc_knn_match_multi_f32)
+        res = eng.knn_match_multi(source, blobs, ns, want_indices=return_indices)
+        out, idx = res if return_indices else (res, None)
     else:
         raise RuntimeError(f"batch of reference ({reference.shape[0]}) must be 1 or match source ({B})")
     if alpha != 0.0:
