@@ -295,7 +295,8 @@ int tvc_sola_f32(tvc_ctx* ctx, void* stream, const float* y, float* sola_buf, co
 
 /* StreamInfer.audio_callback before convert (reference module/infer/stream.py:69-70: `input_wav = torch.roll(input_wav, -block)`,
  * `input_wav[-block:] = block`), batched over S streams, in place and in one launch: buf [S, n] rolling input buffers,
- * blocks [S, block] the new blocks; afterwards buf[s] = (old buf[s][block:], blocks[s]).  n <= 32 768. */
+ * blocks [S, block] the new blocks; afterwards buf[s] = (old buf[s][block:], blocks[s]).  Any block <= n < 2^31 - 32 768; a row longer
+ * than 32 768 samples is shifted in 32 768-sample tiles inside the same launch (capturable like every other call). */
 int tvc_stream_push_f32(tvc_ctx* ctx, void* stream, float* buf, const float* blocks, int S, int64_t n, int block);
 
 /* measurement ----------------------------------------------------------------------------- */

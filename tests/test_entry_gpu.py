@@ -184,3 +184,23 @@ def test_infer_py_chunked_mode(workdir):
     r_w, r_c = float(whole[:, 12000:60000].pow(2).mean().sqrt()), float(ch[:, 12000:60000].pow(2).mean().sqrt())
     print(f"[f4] whole-file rms {r_w:.4f}, chunked rms {r_c:.4f}")
     assert abs(r_w - r_c) / r_w < 0.25
+
+
+def test_entry_scripts_with_stream_buffers_past_32768_samples(workdir):
+    """infer.py --chunked -c 9600 rolls a 48 000-sample input buffer per block and infer_streaming.py -c 24000 one of 35 520 (the reference
+    runs both): the buffer push takes any length, so both convert their whole input."""
+    import infer
+    import infer_streaming
+    d = workdir / "in_9600"
+    d.mkdir()
+    audio_io.save(str(d / "e.wav"), synth.synth_wave(1, 24000 * 2, seed=78), 24000)
+    assert infer.main(["-i", str(d), "-o", str(workdir / "o_9600"), "-encp", str(workdir / "encoder.pt"), "-decp", str(workdir / "decoder.pt"),
+                       "-idx", str(workdir / "index.pt"), "-d", "cuda:0", "--chunked", "-c", "9600", "-b", "4"]) == 0
+    y, sr = audio_io.load(str(workdir / "o_9600" / "e.wav"))
+    assert sr == 24000 and y.shape == (1, 48000) and torch.isfinite(y).all() and float(y.abs().max()) > 1e-3
+    audio_io.save(str(workdir / "mic_24k.wav"), synth.synth_wave(1, 24000 * 3, seed=79), 24000)
+    rc = infer_streaming.main(["-encp", str(workdir / "encoder.pt"), "-decp", str(workdir / "decoder.pt"), "-idx", str(workdir / "index.pt"),
+                               "-c", "24000", "--input-wav", str(workdir / "mic_24k.wav"), "--output-wav", str(workdir / "conv_24k.wav"), "-d", "cuda:0"])
+    assert rc == 0
+    y, sr = audio_io.load(str(workdir / "conv_24k.wav"))
+    assert sr == 24000 and y.shape == (1, 3 * 24000) and torch.isfinite(y).all() and float(y.abs().max()) > 1e-3

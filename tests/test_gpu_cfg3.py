@@ -126,18 +126,20 @@ def test_knn_exact_fallback_runs_when_a_candidate_list_overflows(gen):
     assert profz["knn.exact"] > 3 * prof0["knn.exact"]
 
 
-@pytest.mark.parametrize("use_pv", [False, True])
-def test_chunked_mode_matches_the_oracle_stream_loop(gen, use_pv):
+@pytest.mark.parametrize("use_pv,chunk", [pytest.param(False, 1920, id="False"), pytest.param(True, 1920, id="True"),
+                                           pytest.param(False, 9600, id="False-9600"), pytest.param(True, 9600, id="True-9600")])
+def test_chunked_mode_matches_the_oracle_stream_loop(gen, use_pv, chunk):
     """infer.py's --chunked path against oracle.ref_cpu.stream_callback (= reference stream.py:68-96) fed the
     same blocks and the same noise phases: SOLA lags identical, every block within 1e-4; and the trimmed output is aligned
     with the whole-file conversion.
     A SOLA lag is an arg-max over 1921 correlation values of a quasi-periodic signal: lags one pitch period apart can tie to
     within the CPU's own reproducibility (the oracle on 1 thread and on all host threads picked 1673 and 1694 for one block of
     seed 77, the GPU 1651).  Like the gap-checked kNN fixtures, the input is therefore chosen so that the arg-max is decidable:
-    the first seed on which the oracle agrees with itself across thread counts on every lag."""
+    the first seed on which the oracle agrees with itself across thread counts on every lag.
+    chunk = 9600 (infer.py --chunked -c 9600): a 48 000-sample input buffer, past the 32 768 samples one tile of the buffer push holds."""
     import infer
     enc_sd, dec_sd = state_dicts(0)
-    chunk, buf = 1920, 4
+    buf = 4
     L = 24000 * 2 + 333
     tgt = synth.synth_index(300, seed=2)
     T = R.StreamState(block_size=chunk, extra_size=buf * chunk).input_size // 480

@@ -280,6 +280,23 @@ def test_seeded_draw_is_refused_inside_a_stream_capture_and_push_equals_roll(gen
     assert torch.equal(eng.stream_push(odd.clone(), b2), w2)
 
 
+@pytest.mark.parametrize("n", [32768, 32769, 48000, 120000])
+def test_stream_push_equals_roll_past_32768_samples(gen, n):
+    """tvc_stream_push_f32 on stream buffers of any length: infer.py --chunked -c 9600 rolls a 48 000-sample buffer, infer_streaming.py
+    -c 24000 one of 35 520.  A row longer than 32 768 samples is shifted tile by tile inside the one launch; bit for bit stream.py:69-70's
+    roll + slice assignment, for one and for three streams, blocks from 1920 samples to all but one sample of the buffer."""
+    eng = gen.engine(DEV)
+    g = torch.Generator().manual_seed(n)
+    for S in (1, 3):
+        for m in (1920, 9600, n - 1):
+            buf = torch.randn(S, n, generator=g).to(DEV)
+            blk = torch.randn(S, m, generator=g).to(DEV)
+            want = torch.roll(buf, -m, dims=1)
+            want[:, -m:] = blk
+            got = eng.stream_push(buf.clone(), blk)
+            assert torch.equal(got, want), (S, n, m)
+
+
 def test_workspace_of_exactly_the_measured_peak_and_one_byte_less(gen):
     """Every entry measures its workspace with a walk that launches nothing (ws.dry) before its launching walk, and checks behind the second
     that it took no more (api.hip TVC_RUN).  tvc_workspace_bytes - 4096 is that peak: a conversion in exactly it equals one in the engine's

@@ -759,7 +759,9 @@ int tvc_sola_f32(tvc_ctx* ctx, void* stream, const float* y, float* sola_buf, co
 
 int tvc_stream_push_f32(tvc_ctx* ctx, void* stream, float* buf, const float* blocks, int S, int64_t n, int block) {
     if (!ctx) return TVC_ERR_ARG;
-    if (!buf || !blocks || S <= 0 || block <= 0 || n < block || n > 32768) return fail(ctx, TVC_ERR_ARG, "tvc_stream_push_f32: bad argument (block <= n <= 32768)");
+    // (the kernel indexes a row with 32-bit ints and rounds n up to whole 32 768-sample tiles)
+    if (!buf || !blocks || S <= 0 || block <= 0 || n < block || n > INT32_MAX - 32768)
+        return fail(ctx, TVC_ERR_ARG, "tvc_stream_push_f32: bad argument (block <= n <= 2^31 - 32769)");
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     return run_stream_push(ctx, (hipStream_t)stream, buf, blocks, S, (int)n, block);
 }

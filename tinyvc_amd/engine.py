@@ -520,12 +520,13 @@ class Engine:
         return wave
 
     def stream_push(self, buf, blocks):
-        """buf [S, n] <- (buf[:, m:], blocks [S, m]) in place, one launch (stream.py:69-70's roll + slice assignment)."""
+        """buf [S, n] <- (buf[:, m:], blocks [S, m]) in place, one launch for any buffer length n >= m (stream.py:69-70's roll + slice
+        assignment)."""
         _check_dev(buf, "buf", self.device)
         blocks = _prep(blocks, "blocks", self.device)
         S, n = buf.shape
         if blocks.shape[0] != S or not buf.is_contiguous() or buf.dtype != _F32:
-            raise ValueError("stream_push: buf [S, n] contiguous fp32, blocks [S, m]")
+            raise ValueError("stream_push: buf [S, n] contiguous fp32, blocks [S, m] with m <= n (n of any length)")
         self._ok(self.lib.tvc_stream_push_f32(self.ctx, self._stream(), _ptr(buf), _ptr(blocks), S, n, blocks.shape[1]), "tvc_stream_push_f32")
         return buf
 
