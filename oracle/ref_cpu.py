@@ -320,21 +320,40 @@ class StreamState:
         self.sola = torch.zeros(self.cross)
 
 
+def sola_tail(y, sola, fade_in, block, use_phase_vocoder=False, search=1920, delay=3840):
+    """The tail of reference module/infer/stream.py:74-95 for one stream, in the dtype of its inputs: lag search over
+    `search + 1` lags, cross-fade of the first `cross = len(sola)` samples, split into the block and the next buffer.
+    y [Ly], sola [cross], fade_in [cross] -> (out [block], new_sola [cross], shift, corr [search + 1]).
+
+    float32 runs the reference's own operations (the two F.conv1d): this is what stream_callback computes.  Any other
+    dtype (float64: the tests' truth) takes the correlation lag by lag, every window a contiguous row summed by the same
+    routine, so that identical windows give identical values and the first maximum is well defined."""
+    cross = sola.shape[0]
+    fade_out = 1 - fade_in
+    tmp = y[-block - cross - search - delay:-delay]
+    ci = tmp[:cross + search]
+    if y.dtype == torch.float32:
+        nom = F.conv1d(ci[None, None], sola[None, None, :])[0, 0]
+        den = torch.sqrt(F.conv1d(ci[None, None] ** 2, torch.ones(1, 1, cross)) + 1e-8)[0, 0]
+    else:
+        win = ci.unfold(0, cross, 1).contiguous()                 # [search + 1, cross]
+        nom = (win * sola).sum(-1)
+        den = torch.sqrt((win * win).sum(-1) + 1e-8)
+    corr = nom / den
+    shift = int(torch.argmax(corr))
+    tmp = tmp[shift:shift + block + cross].clone()
+    if use_phase_vocoder:
+        tmp[:cross] = phase_vocoder(sola, tmp[:cross], fade_out, fade_in)
+    else:
+        tmp[:cross] = tmp[:cross] * fade_in + sola * fade_out
+    return tmp[:-cross].clone(), tmp[-cross:].clone(), shift, corr
+
+
 def stream_callback(st, enc_sd, dec_sd, tgt, pitch_shift, block, angle, use_phase_vocoder=False):
     """reference module/infer/stream.py:68-96 -> (out block [1920], sola shift)."""
     with torch.inference_mode():
         st.input_wav = torch.roll(st.input_wav, -st.block)
         st.input_wav[-st.block:] = block
         y = convert(enc_sd, dec_sd, st.input_wav[None], tgt, pitch_shift, angle)[0]
-        tmp = y[-st.block - st.cross - st.search - st.delay:-st.delay]
-        ci = tmp[None, None, :st.cross + st.search]
-        nom = F.conv1d(ci, st.sola[None, None, :])
-        den = torch.sqrt(F.conv1d(ci ** 2, torch.ones(1, 1, st.cross)) + 1e-8)
-        shift = int(torch.argmax(nom[0, 0] / den[0, 0]))
-        tmp = tmp[shift:shift + st.block + st.cross].clone()
-        if use_phase_vocoder:
-            tmp[:st.cross] = phase_vocoder(st.sola, tmp[:st.cross], st.fade_out, st.fade_in)
-        else:
-            tmp[:st.cross] = tmp[:st.cross] * st.fade_in + st.sola * st.fade_out
-        st.sola = tmp[-st.cross:].clone()
-        return tmp[:-st.cross].clone(), shift
+        out, st.sola, shift, _corr = sola_tail(y, st.sola, st.fade_in, st.block, use_phase_vocoder, st.search, st.delay)
+        return out, shift

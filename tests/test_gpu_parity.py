@@ -274,7 +274,9 @@ def test_streaming(models, case, pv):
         _log(f"[parity] stream block {i}: shift {shift} (ref {int(g['shift'][i])})")
         assert shift == int(g["shift"][i])
         # end-to-end blocks carry the f0 conditioning of convert (measured <= 3.9e-4 rel = 5.5e-5 abs); the phase vocoder's first
-        # block cross-fades against an all-zero sola buffer (atan2 of empty bins): measured 2.3e-3
+        # block cross-fades against an all-zero sola buffer and is not comparable to the reference there: atan2 of an all-zero
+        # spectrum takes its sign from the signed zeros the FFT library leaves (the formula with pa = 0 is 2.8e-3 from torch's
+        # output; measured here 2.3e-3).  The vocoder's own accuracy gate is tests/test_gpu_sola.py's, against fp64.
         check(f"stream block {i}", out, g["out"][i], 1e-2 if (pv and i == 0) else 1e-3)
         assert pv and i == 0 or rms(out.cpu() - _t(g["out"][i])) <= 1e-4
 

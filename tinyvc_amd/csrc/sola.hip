@@ -54,10 +54,20 @@ static __device__ void phase_vocoder_block(const float* a, const float* b, const
     __syncthreads();
 }
 
+// The order of the lag arg-max, shared by every step of it (per thread, across lanes, across waves, across lag groups): is candidate
+// (ov, oi) ahead of (bv, bi)?  torch.argmax's rule - a NaN correlation is ahead of any number, among equals (two NaNs included) the
+// lower lag is - which is a total order, so the result does not depend on how the lags were split, and a thread that starts from
+// (-inf, kNoLag) ends with a lag in [0, SEARCH] as soon as it has seen one.
+constexpr int kNoLag = 0x7fffffff;
+static __device__ __forceinline__ bool lag_ahead(float ov, int oi, float bv, int bi) {
+    if (ov != ov) return bv == bv || oi < bi;
+    return bv == bv && (ov > bv || (ov == bv && oi < bi));
+}
+
 // Normalised cross-correlation over the SEARCH + 1 lags (the two F.conv1d of stream.py:77-78), split over kSolaGroups workgroups
 // per stream: one lag per thread, the same sums in the same order as the one-workgroup kernel below (bit-identical values), so
 // the search of 32 streams fills the chip instead of 32 CUs (173 us -> see DESIGN.md).  part[(st * G + g) * 2] = best value of
-// the group, [.. + 1] = its lag (as bits); ties keep the lowest lag.
+// the group, [.. + 1] = its lag (as bits); the order is lag_ahead's.
 static __global__ __launch_bounds__(256) void sola_corr_kernel(const float* __restrict__ y, const float* __restrict__ sola_buf,
                                                                float* __restrict__ part, long Ly, int block) {
     constexpr int LPG = (SEARCH + 1 + kSolaGroups - 1) / kSolaGroups;     // 241 lags per group
@@ -77,7 +87,7 @@ static __global__ __launch_bounds__(256) void sola_corr_kernel(const float* __re
     for (int i = tid; i < CROSS; i += 256) sb[i] = sola_buf[(long)st * CROSS + i];
     __syncthreads();
     float bv = -INFINITY;
-    int bi = 0x7fffffff;
+    int bi = kNoLag;
     const int lag = lag0 + tid;
     if (tid < LPG && lag <= SEARCH) {
         float nom = 0.f, den = 0.f;
@@ -105,7 +115,7 @@ static __global__ __launch_bounds__(256) void sola_corr_kernel(const float* __re
     for (int o = 32; o > 0; o >>= 1) {
         float ov = __shfl_xor(bv, o);
         int oi = __shfl_xor(bi, o);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        if (lag_ahead(ov, oi, bv, bi)) { bv = ov; bi = oi; }
     }
     if (lane == 0) { bestv[wave] = bv; besti[wave] = bi; }
     __syncthreads();
@@ -113,13 +123,15 @@ static __global__ __launch_bounds__(256) void sola_corr_kernel(const float* __re
         float v = bestv[0];
         int i = besti[0];
         for (int w = 1; w < 4; ++w)
-            if (bestv[w] > v || (bestv[w] == v && besti[w] < i)) { v = bestv[w]; i = besti[w]; }
+            if (lag_ahead(bestv[w], besti[w], v, i)) { v = bestv[w]; i = besti[w]; }
         part[(long)blockIdx.x * 2] = v;
         part[(long)blockIdx.x * 2 + 1] = __int_as_float(i);
     }
 }
 
 // one workgroup per stream; `part` != nullptr: the lag search was done by sola_corr_kernel, only its kSolaGroups candidates are compared here
+// (run_sola: while the scratch holds them, S <= kSolaPartFloats / 16 = 1024 streams); `part` == nullptr: the search runs here, lags strided by 256
+// over the threads - the same sums, and through lag_ahead the same lag (tests/test_gpu_sola.py compares the two row by row)
 static __global__ __launch_bounds__(256) void sola_kernel(const float* __restrict__ y, float* __restrict__ sola_buf,
                                                           const float* __restrict__ fade_in, float* __restrict__ out,
                                                           int32_t* __restrict__ shift_out, long Ly, int block, int use_pv,
@@ -149,7 +161,7 @@ static __global__ __launch_bounds__(256) void sola_kernel(const float* __restric
 
     // normalised cross-correlation over SEARCH+1 lags (two F.conv1d in stream.py:77-78)
     float bv = -INFINITY;
-    int bi = 0x7fffffff;
+    int bi = kNoLag;
     if (part) {
         if (tid < kSolaGroups) {
             bv = part[((long)st * kSolaGroups + tid) * 2];
@@ -163,14 +175,14 @@ static __global__ __launch_bounds__(256) void sola_kernel(const float* __restric
                 den += sq[lag + j];
             }
             float v = nom / sqrtf(den + 1e-8f);
-            if (v > bv) { bv = v; bi = lag; }   // ascending lags per thread: first maximum kept
+            if (lag_ahead(v, lag, bv, bi)) { bv = v; bi = lag; }
         }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         float ov = __shfl_xor(bv, o);
         int oi = __shfl_xor(bi, o);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        if (lag_ahead(ov, oi, bv, bi)) { bv = ov; bi = oi; }
     }
     if (lane == 0) { bestv[wave] = bv; besti[wave] = bi; }
     __syncthreads();
@@ -178,7 +190,7 @@ static __global__ __launch_bounds__(256) void sola_kernel(const float* __restric
         float v = bestv[0];
         int i = besti[0];
         for (int w = 1; w < 4; ++w)
-            if (bestv[w] > v || (bestv[w] == v && besti[w] < i)) { v = bestv[w]; i = besti[w]; }
+            if (lag_ahead(bestv[w], besti[w], v, i)) { v = bestv[w]; i = besti[w]; }
         s_shift = i;
         if (shift_out) shift_out[st] = i;
     }

@@ -6,6 +6,7 @@ scratch workspace; every computation is a call into libtinyvc_hip.so.
 import ctypes
 import math
 import threading
+import weakref
 
 import torch
 
@@ -42,6 +43,12 @@ def pitch_class_table():
     x = spec.PITCH_FMIN * (2 ** (ids / spec.PITCH_CPO))
     x[x <= spec.PITCH_FMIN] = 0
     return x.contiguous()
+
+
+def _forget_blob(engine_ref, ptr):
+    eng = engine_ref()
+    if eng is not None and getattr(eng, "ctx", None):
+        eng.lib.tvc_knn_forget(eng.ctx, ctypes.c_void_p(ptr))
 
 
 class Engine:
@@ -224,10 +231,18 @@ class Engine:
             rows = idx.t().contiguous()          # [N, 768] half, one vector per row
             blob = torch.empty(self.lib.tvc_knn_prepared_elems_f16(N), dtype=_F32, device=self.device)
             self._ok(self.lib.tvc_knn_prepare_index_f16(self.ctx, self._stream(), _ptr(rows), _ptr(blob), N), "tvc_knn_prepare_index_f16")
-            return blob, N
+            return self._owned(blob), N
         blob = torch.empty(self.lib.tvc_knn_prepared_elems(N), dtype=_F32, device=self.device)
         self._ok(self.lib.tvc_knn_prepare_index_f32(self.ctx, self._stream(), _ptr(idx.contiguous()), _ptr(blob), N), "tvc_knn_prepare_index_f32")
-        return blob, N
+        return self._owned(blob), N
+
+    def _owned(self, blob):
+        """The library remembers a prepared blob's N by device address (api.hip: blob_check) and asks for tvc_knn_forget before the
+        memory is reused: the allocator recycles addresses, and a blob copied to where a blob of another size once lived must not
+        inherit that record (it was refused as "prepared for N = 300, the call says N = 600").  The record goes when the tensor
+        does; dropping it early only costs the next use one header read."""
+        weakref.finalize(blob, _forget_blob, weakref.ref(self), blob.data_ptr()).atexit = False
+        return blob
 
     def knn_match(self, src, prepared, N, want_indices=False):
         src = _prep(src, "source", self.device)
