@@ -14,6 +14,11 @@ headers alone (a clip of n samples at 24 kHz contributes ceil(ceil(n / 480) / st
 length (tinyvc_amd/parallel.py lpt_split), each rank encodes its clips on cuda:LOCAL_RANK, and ONE gather (RCCL) brings the features to
 rank 0, which assembles them in the shuffled order, permutes, truncates and writes the file - the same bytes as the single-GPU run with
 the same `--seed`.
+
+`--batch-frames F` (single-process runs) builds the index in one pass on the device: the clips of the shuffled order go through the
+encoder in ragged calls of at most F frames (Engine.encode_ragged: every clip over its own length, bit-identical to its own call), the
+features stay on the device, and ONE gather selects the strided, permuted, truncated columns (feature_retrieval.index_columns) - the same
+bytes as the default clip-by-clip run with the same `--seed`, without a host round trip per clip.
 """
 import argparse
 import glob
@@ -25,6 +30,7 @@ import torch
 from tinyvc_amd import audio_io, parallel
 from tinyvc_amd.module import utils
 from tinyvc_amd.module.tinyvc import Encoder
+from tinyvc_amd.module.tinyvc.feature_retrieval import index_columns, index_from_columns
 
 SAMPLE_RATE = 24000
 
@@ -88,6 +94,41 @@ def sharded_features(cols, order, size, world, rank, encode, device, group=None)
     return feats
 
 
+def batched_index(enc, device, files, order, stride, size, gen, half, batch_frames):
+    """The default loop's index ([1, 768, size] on the CPU, the same bytes) with the clips encoded in ragged calls of at most `batch_frames`
+    frames (a longer clip is a call of its own) and the selection done by one gather on the device."""
+    eng = enc.engine(device)
+    feats, frames, total = [], [], 0
+    group, group_frames = [], 0
+
+    def flush():
+        if not group:
+            return
+        wf = torch.zeros(len(group), max(c.numel() for c in group), device=device)
+        for r, c in enumerate(group):
+            wf[r, :c.numel()] = c
+        feats.append(eng.encode_ragged(wf, [c.numel() for c in group])[0])
+        group.clear()
+
+    for i in order:
+        wf, sr = audio_io.load(files[i])
+        wf = utils.autopad_waveform(eng.resample(wf.to(device), sr, SAMPLE_RATE).mean(dim=0, keepdim=True))
+        t = wf.shape[1] // 480
+        if group and group_frames + t > batch_frames:
+            flush()
+            group_frames = 0
+        group.append(wf[0])
+        group_frames += t
+        frames.append(t)
+        total += -(-t // stride)
+        if total > size:
+            break
+    flush()
+    packed = feats[0] if len(feats) == 1 else torch.cat(feats, dim=1)
+    cols = index_columns(frames, stride, size, torch.randperm(total, generator=gen))
+    return index_from_columns(eng, packed, cols, half).cpu()
+
+
 def assemble(feats_in_order, size, gen, half):
     feats = torch.cat(feats_in_order, dim=2)
     perm = torch.randperm(feats.shape[2], generator=gen)
@@ -105,6 +146,8 @@ def main(argv=None):
     p.add_argument("--stride", default=4, type=int)
     p.add_argument("--seed", default=None, type=int, help="fix the shuffle (the reference does not seed it)")
     p.add_argument("--half", action="store_true", help="store the index in half precision (matched with the fp16 index storage: 2 B per element)")
+    p.add_argument("--batch-frames", default=0, type=int,
+                   help="encode the clips in ragged calls of at most this many frames and select the index on the device (0: clip by clip)")
     p.add_argument("--force-dist", action="store_true", help="run the WORLD_SIZE > 1 path (header-derived prefix, split, RCCL gather) even at world size 1")
     args = p.parse_args(argv)
 
@@ -125,14 +168,17 @@ def main(argv=None):
     if not sharded:
         gen = torch.Generator().manual_seed(args.seed) if args.seed is not None else None
         order = torch.randperm(len(files), generator=gen).tolist()      # DataLoader(shuffle=True) in the reference
-        feats, total = [], 0
-        for i in order:
-            z = encode_clip(enc, device, files[i], args.stride)
-            feats.append(z)
-            total += z.shape[2]
-            if total > args.size:
-                break
-        tgt = assemble(feats, args.size, gen, args.half)
+        if args.batch_frames > 0:
+            tgt = batched_index(enc, device, files, order, args.stride, args.size, gen, args.half, args.batch_frames)
+        else:
+            feats, total = [], 0
+            for i in order:
+                z = encode_clip(enc, device, files[i], args.stride)
+                feats.append(z)
+                total += z.shape[2]
+                if total > args.size:
+                    break
+            tgt = assemble(feats, args.size, gen, args.half)
     else:
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")

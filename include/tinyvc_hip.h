@@ -139,6 +139,18 @@ int tvc_knn_prepare_index_f32(tvc_ctx* ctx, void* stream, const float* index, fl
 int64_t tvc_knn_prepared_elems_f16(int64_t N);
 int tvc_knn_prepare_index_f16(tvc_ctx* ctx, void* stream, const void* rows_f16, float* prepared,
                               int64_t N);
+/* An index selected out of packed encoder features, prepared in one launch (reference extract_index.py:43-58: every stride-th frame of
+ * each clip, concatenated, permuted, truncated - here a column list): feats [768, S] fp32 (tvc_encode_ragged_f32's ssl, or any [768, S]
+ * tensor), cols a DEVICE array of N columns, each in [0, S) (a column outside is clamped into the tensor; the host's column plan refuses
+ * it first) -> `prepared`, byte for byte the blob tvc_knn_prepare_index_f32 makes of feats[:, cols] (tvc_knn_prepared_elems(N) floats), and
+ * optionally index_out [768, N] = feats[:, cols] itself (the tensor of index.pt; NULL = not wanted).  The _f16 form writes the blob
+ * tvc_knn_prepare_index_f16 makes of feats[:, cols] transposed and cast to half (tvc_knn_prepared_elems_f16(N) floats) and
+ * index_out_f16 [768, N] IEEE binary16.  The selected vectors never exist as a tensor of their own unless index_out asks for it.
+ * Asynchronous on `stream`, capturable; the blob is recorded like the other prepare calls'. */
+int tvc_knn_prepare_index_cols_f32(tvc_ctx* ctx, void* stream, const float* feats, int64_t S, const int64_t* cols, int64_t N,
+                                   float* prepared, float* index_out);
+int tvc_knn_prepare_index_cols_f16(tvc_ctx* ctx, void* stream, const float* feats, int64_t S, const int64_t* cols, int64_t N,
+                                   float* prepared, void* index_out_f16);
 
 /* The library remembers the N every blob was prepared with (by device address) and refuses calls that pass another N.  Call this
  * before the memory of a prepared blob is reused for anything else than a fresh tvc_knn_prepare_index_* (for instance a COPY of
@@ -252,6 +264,18 @@ int tvc_ctx_set_ragged_batch_frames(tvc_ctx* ctx, int max_frames);
 int tvc_convert_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens, const float* prepared_index,
                            int64_t N, float pitch_shift, const float* noise_angle, uint64_t seed, float* wave, int B, void* ws,
                            size_t ws_bytes);
+
+/* Generator.encode (reference module/infer/generator.py:19-23) over a RAGGED batch - the clips of a target speaker, which
+ * extract_index.py:47-52 encodes one by one: wav [B, Lmax] as in tvc_convert_ragged_f32 (lens a HOST array, lens[b] % 480 == 0,
+ * 960 < lens[b] <= Lmax) -> ssl [768, S] and f0 [S] with S = sum(lens[b] / 480), packed as ONE long utterance (csrc/ragged.h): utterance b
+ * occupies columns pre[b] .. pre[b] + lens[b] / 480 (pre = the exclusive prefix of the frame counts in the caller's row order), row stride S,
+ * however the call is cut into in-kernel batches (at most 80 000 frames, or tvc_ctx_set_ragged_batch_frames; no length classes: the
+ * encoder's kernels choose nothing by an utterance's length).  Utterance b's columns are bit-identical to tvc_stft_mag_f32 +
+ * tvc_encoder_f32 on it alone (B = 1): the spectrogram's |max| slot is the measured per-utterance maximum, as in those calls.
+ * Asynchronous on `stream`, capturable.  Workspace: tvc_workspace_bytes_encode_ragged. */
+int tvc_workspace_bytes_encode_ragged(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, size_t* out_bytes);
+int tvc_encode_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens, float* ssl, float* f0,
+                          int B, void* ws, size_t ws_bytes);
 
 /* one speaker index per utterance ----------------------------------------------------------- */
 /* The calls above with a TABLE of prepared indices instead of one: prepared[b] (a device blob) and N[b] are HOST arrays of B entries,

@@ -33,6 +33,8 @@ SIGNATURES = {
     "tvc_knn_prepared_elems": (c_int64, [c_int64]),
     "tvc_knn_prepared_elems_f16": (c_int64, [c_int64]),
     "tvc_knn_prepare_index_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64]),
+    "tvc_knn_prepare_index_cols_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "tvc_knn_prepare_index_cols_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "tvc_knn_forget": (c_int, [c_void_p, c_void_p]),
     "tvc_ragged_plan": (c_int, [c_int, c_int64, POINTER(c_int64), c_int, POINTER(c_int32), POINTER(c_int)]),
     "tvc_ctx_set_ragged_batch_frames": (c_int, [c_void_p, c_int]),
@@ -51,6 +53,8 @@ SIGNATURES = {
     "tvc_convert_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_uint64, c_void_p, c_int, c_int64, c_void_p, c_size_t]),
     "tvc_workspace_bytes_ragged": (c_int, [c_void_p, c_int, c_int64, POINTER(c_int64), c_int64, POINTER(c_size_t)]),
     "tvc_convert_ragged_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64), c_void_p, c_int64, c_float, c_void_p, c_uint64, c_void_p, c_int, c_void_p, c_size_t]),
+    "tvc_workspace_bytes_encode_ragged": (c_int, [c_void_p, c_int, c_int64, POINTER(c_int64), POINTER(c_size_t)]),
+    "tvc_encode_ragged_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64), c_void_p, c_void_p, c_int, c_void_p, c_size_t]),
     "tvc_knn_match_multi_f32": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_int64), c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t]),
     "tvc_workspace_bytes_multi": (c_int, [c_void_p, c_int, c_int64, POINTER(c_int64), POINTER(c_size_t)]),
     "tvc_convert_multi_f32": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_int64), c_float, POINTER(c_float), c_void_p, c_uint64,

@@ -397,6 +397,33 @@ int tvc_knn_prepare_index_f16(tvc_ctx* ctx, void* stream, const void* rows_f16, 
     return TVC_OK;
 }
 
+static int prepare_cols_check(tvc_ctx* ctx, const float* feats, int64_t S, const int64_t* cols, int64_t N, const float* prepared, const char* what) {
+    if (!ctx) return TVC_ERR_ARG;
+    if (!feats || !cols || !prepared || S <= 0 || N <= 0) return fail(ctx, TVC_ERR_ARG, "%s: bad argument", what);
+    if (N > 0x7fffffff - 128) return fail(ctx, TVC_ERR_ARG, "%s: N beyond 32-bit indexing", what);
+    return 0;
+}
+
+int tvc_knn_prepare_index_cols_f32(tvc_ctx* ctx, void* stream, const float* feats, int64_t S, const int64_t* cols, int64_t N, float* prepared,
+                                   float* index_out) {
+    TVC_CHECK(prepare_cols_check(ctx, feats, S, cols, N, prepared, "tvc_knn_prepare_index_cols_f32"));
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    blob_forget(prepared);
+    TVC_CHECK(run_prepare_index_cols(ctx, (hipStream_t)stream, feats, S, cols, N, prepared, index_out));
+    blob_record(prepared, N);
+    return TVC_OK;
+}
+
+int tvc_knn_prepare_index_cols_f16(tvc_ctx* ctx, void* stream, const float* feats, int64_t S, const int64_t* cols, int64_t N, float* prepared,
+                                   void* index_out_f16) {
+    TVC_CHECK(prepare_cols_check(ctx, feats, S, cols, N, prepared, "tvc_knn_prepare_index_cols_f16"));
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    blob_forget(prepared);
+    TVC_CHECK(run_prepare_index_cols_f16(ctx, (hipStream_t)stream, feats, S, cols, N, prepared, index_out_f16));
+    blob_record(prepared, N);
+    return TVC_OK;
+}
+
 int tvc_knn_match_f32(tvc_ctx* ctx, void* stream, const float* src, const float* prepared, int64_t N, float* out,
                       int64_t* idx_out, int B, int T, void* wsp, size_t ws_bytes) {
     if (!ctx) return TVC_ERR_ARG;
@@ -526,7 +553,7 @@ struct RagBatchPlan {
     std::vector<int> rows, frames;
     int Ttot = 0;
 };
-int ragged_split(tvc_ctx* ctx, int cap, int B, int64_t Lmax, const int64_t* lens, std::vector<RagBatchPlan>* batches) {
+int ragged_split(tvc_ctx* ctx, int cap, int B, int64_t Lmax, const int64_t* lens, std::vector<RagBatchPlan>* batches, bool classes = true) {
     std::vector<RagBatchPlan> open(4);          // the batch being filled, per class (cap: tvc_ctx_set_ragged_batch_frames / tvc_ragged_plan's argument, 0 = the default)
     const int max_frames = cap > 0 && cap < kRagMaxFrames ? cap : kRagMaxFrames;
     for (int b = 0; b < B; ++b) {
@@ -534,7 +561,7 @@ int ragged_split(tvc_ctx* ctx, int cap, int B, int64_t Lmax, const int64_t* lens
             return fail(ctx, TVC_ERR_ARG, "ragged batch: lens[%d] = %lld must be a multiple of 480 in (960, Lmax]", b, (long long)lens[b]);
         const int T = (int)(lens[b] / kHop);
         if (T > kRagMaxFrames) return fail(ctx, TVC_ERR_ARG, "ragged batch: lens[%d] = %lld is longer than a batch may be; convert it with tvc_convert_f32", b, (long long)lens[b]);
-        const int cls = (T >= kRagClassBounds[0]) + (T >= kRagClassBounds[1]) + (T >= kRagClassBounds[2]);
+        const int cls = classes ? (T >= kRagClassBounds[0]) + (T >= kRagClassBounds[1]) + (T >= kRagClassBounds[2]) : 0;      // (the encoder's kernels make no length-dependent choice: one class)
         RagBatchPlan& p = open[cls];
         if (p.Ttot + T > max_frames && !p.rows.empty()) {
             batches->push_back(p);
@@ -612,6 +639,105 @@ int tvc_convert_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t
     TVC_HIP(ctx, hipMemsetAsync(wave, 0, (size_t)B * Lmax * sizeof(float), s));
     Ws ws(wsp, bytes, false);
     TVC_CHECK(ragged_batches(ctx, s, ws, batches, wav, Lmax, prepared, N, pitch_shift, noise_angle, seed, wave));
+    return walks_agree(ctx, __func__, ws.peak, need.peak);
+}
+
+// ---- ragged encode ----------------------------------------------------------------------------------------------------------------
+// Generator.encode (generator.py:19-23) over utterances of different lengths, as extract_index.py:47-52 needs it for a folder of clips:
+// rag_setup, |STFT|, encoder with ctx->rag set - the first half of convert_impl, no index, no decoder.  The spectrogram's |max| slot is
+// the measured per-utterance maximum (run_encoder without a bound: run_amax_rows), as in the stage calls tvc_stft_mag_f32 + tvc_encoder_f32
+// that Generator.encode makes for one utterance: utterance b's columns are bit-identical to those calls at B = 1.  The length classes of
+// ragged_split exist for FilterNet's FiLM kernels; the encoder's kernels choose nothing by an utterance's length, so a call is cut by the
+// frame cap alone and its batches are runs of consecutive rows.
+namespace {
+// packed[c][gpre[row of b] + t'] = batch[c][pre[b] + t'] (c = 768: the f0 row): a later batch's columns into the call's packed outputs
+__global__ __launch_bounds__(256) void pack_batch_kernel(const float* __restrict__ ssl_b, const float* __restrict__ f0_b, float* __restrict__ ssl,
+                                                         float* __restrict__ f0, RagDev rg, const int* __restrict__ gpre, int Ttot, long S) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= Ttot) return;
+    const int b = rg.col2b[t];
+    const long dst = (long)gpre[rg.row[b]] + (t - rg.pre[b]);
+    const int c = blockIdx.y;
+    if (c < kSslDim) ssl[(long)c * S + dst] = ssl_b[(long)c * Ttot + t];
+    else f0[dst] = f0_b[t];
+}
+int encode_ragged_batches(tvc_ctx* ctx, hipStream_t s, Ws& ws, const std::vector<RagBatchPlan>& batches, const std::vector<int>& gpre, const float* wav,
+                          int64_t Lmax, float* ssl, float* f0, int64_t S) {
+    ws.release(0);
+    const bool direct = batches.size() == 1;      // one batch holds every row in the caller's order: its layout IS the packed one (row stride S)
+    int* d_gpre = nullptr;
+    if (!direct) {
+        d_gpre = ws.get<int>(gpre.size());
+        if (!ws.dry) TVC_CHECK(upload_ints(ctx, s, gpre, d_gpre));
+    }
+    const size_t m0 = ws.mark();
+    for (auto& p : batches) {
+        ws.release(m0);
+        RagHost h;
+        TVC_CHECK(rag_setup(ctx, s, ws, h, p.frames, p.rows, (int)(Lmax / kHop)));
+        float* spec = ws.get<float>((size_t)kBins * p.Ttot);
+        float* ssl_b = direct ? ssl : ws.get<float>((size_t)kSslDim * p.Ttot);
+        float* f0_b = direct ? f0 : ws.get<float>((size_t)p.Ttot);
+        ctx->rag = &h;
+        int rc = run_stft(ctx, s, ws, wav, spec, 1, (int64_t)p.Ttot * kHop);
+        if (!rc) rc = run_encoder(ctx, s, ws, spec, ssl_b, f0_b, nullptr, 1, p.Ttot);
+        if (!rc && !direct && !ws.dry) {
+            RagDev rg;
+            rc = rag_view(ctx, s, 1, 0, &rg, nullptr);
+            if (!rc) {
+                hipLaunchKernelGGL(pack_batch_kernel, dim3((unsigned)((p.Ttot + 255) / 256), kSslDim + 1), dim3(256), 0, s, ssl_b, f0_b, ssl, f0, rg, d_gpre, p.Ttot, (long)S);
+                rc = launch_check(ctx, "encode_ragged pack");
+            }
+        }
+        ctx->rag = nullptr;
+        TVC_CHECK(rc);
+    }
+    return 0;
+}
+// the call's plan: its batches, the packed column of every row's first frame, S
+int encode_ragged_plan(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, std::vector<RagBatchPlan>* batches, std::vector<int>* gpre, int64_t* S) {
+    TVC_CHECK(ragged_split(ctx, ctx->rag_batch_frames, B, Lmax, lens, batches, false));
+    gpre->assign((size_t)B, 0);
+    int64_t tot = 0;
+    for (int b = 0; b < B; ++b) {
+        (*gpre)[b] = (int)tot;
+        tot += lens[b] / kHop;
+        if (tot > 0x7fffffff) return fail(ctx, TVC_ERR_ARG, "ragged encode: more than 2^31 - 1 frames in one call");
+    }
+    *S = tot;
+    return 0;
+}
+}  // namespace
+
+int tvc_workspace_bytes_encode_ragged(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, size_t* out_bytes) {
+    TVC_CHECK(need_ready(ctx, NEED_NONE));
+    if (!out_bytes || !lens || B <= 0 || Lmax <= 0 || Lmax % kHop != 0) return fail(ctx, TVC_ERR_ARG, "tvc_workspace_bytes_encode_ragged: need B>0, Lmax%%480==0, lens[B]");
+    std::vector<RagBatchPlan> batches;
+    std::vector<int> gpre;
+    int64_t S = 0;
+    TVC_CHECK(encode_ragged_plan(ctx, B, Lmax, lens, &batches, &gpre, &S));
+    Ws ws(nullptr, 0, true);
+    TVC_CHECK(encode_ragged_batches(ctx, nullptr, ws, batches, gpre, kDryPtr, Lmax, kDryPtr, kDryPtr, S));
+    *out_bytes = ((ws.peak + 4095) & ~size_t(4095)) + 4096;
+    return TVC_OK;
+}
+
+int tvc_encode_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens, float* ssl, float* f0, int B, void* wsp,
+                          size_t ws_bytes) {
+    TVC_CHECK(need_ready(ctx, NEED_ENC));
+    if (!wav || !lens || !ssl || !f0 || B <= 0 || Lmax <= 0 || Lmax % kHop) return fail(ctx, TVC_ERR_ARG, "tvc_encode_ragged_f32: bad argument (Lmax must be a positive multiple of 480)");
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<RagBatchPlan> batches;
+    std::vector<int> gpre;
+    int64_t S = 0;
+    TVC_CHECK(encode_ragged_plan(ctx, B, Lmax, lens, &batches, &gpre, &S));
+    Ws need(nullptr, 0, true);
+    TVC_CHECK(encode_ragged_batches(ctx, s, need, batches, gpre, wav, Lmax, ssl, f0, S));
+    const size_t bytes = (need.peak + 4095) & ~size_t(4095);
+    if (bytes > ws_bytes) return fail(ctx, TVC_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", bytes, ws_bytes);
+    Ws ws(wsp, bytes, false);
+    TVC_CHECK(encode_ragged_batches(ctx, s, ws, batches, gpre, wav, Lmax, ssl, f0, S));
     return walks_agree(ctx, __func__, ws.peak, need.peak);
 }
 

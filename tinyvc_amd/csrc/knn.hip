@@ -263,6 +263,210 @@ int run_prepare_index_f16(tvc_ctx* ctx, hipStream_t s, const void* rows16, float
     return launch_check(ctx, "knn_prepare_index_f16");
 }
 
+// ---- an index gathered straight into a blob ---------------------------------------------------------------------------------
+// extract_index.py:43-58 selects index vectors out of the clips' features (every stride-th frame, permuted, truncated); here the
+// selection is a column list into packed features [768][S] and the selected vectors go straight into a prepared blob, byte for byte
+// the blob run_prepare_index / run_prepare_index_f16 make of feats[:, cols].  One workgroup per 128-vector image tile:
+//   * the column gather is element-granular (lanes along n read feats[k][cols[n]]: every lane its own cache line, served by L2 / the
+//     Infinity Cache - all tiles walk the channels in the same order), 32 independent loads per thread in flight;
+//   * a 64-channel chunk of the tile meets in LDS ([k][n], rows padded by one float: lanes along n and lanes along k are both
+//     conflict-free), and every store leaves with its lanes along the fast axis of its destination: raw rows in 256-byte runs,
+//     index_out along n, the images as whole 16-byte pieces (img_elem keeps the 8 j of one (n, step, lh) adjacent: 1 KiB per wave).
+// What byte identity pins: the norm's summation order (fp32 kind: ONE fmaf chain over k ascending per vector; fp16 kind: 64 lane-strided
+// chains, k = lane + 64 c, then the xor butterfly), raw / den as a division, the three-term bf16 split - restated below as they stand
+// in index_prepare_kernel / index_prepare_f16_kernel.
+constexpr int GP_KC = 64;             // channels per chunk: 4 K16 steps, one raw-row run of 256 bytes
+constexpr int GP_LD = 128 + 1;        // LDS row stride in floats
+static_assert(KD % GP_KC == 0 && GP_KC == 64, "the fp16 kind's lane-strided chains take one term per chunk");
+
+// a column outside [0, S) never leaves the tensor (the host's column plan refuses it first: feature_retrieval.py index_columns)
+__device__ __forceinline__ long gp_column(const int64_t* __restrict__ cols, long n, long N, long S) {
+    const long c = n < N ? (long)cols[n] : 0;
+    return c < 0 ? 0 : (c >= S ? S - 1 : c);
+}
+__device__ __forceinline__ unsigned gp_pack(unsigned short lo, unsigned short hi) { return (unsigned)lo | ((unsigned)hi << 16); }
+__device__ __forceinline__ void gp_amax_flush(float mx, float* red, float* __restrict__ slot) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+        if (m > 0.f) atomicMax(reinterpret_cast<unsigned*>(slot), __builtin_bit_cast(unsigned, m));      // as index_amax_kernel
+    }
+}
+
+// fp32 storage.  Pass 1: gather, norm chain, raw rows, index_out, |max|.  Pass 2: the tile's own rows (just written: L2-hot, contiguous)
+// come back through LDS and leave as the bf16x3 and fp16 images of v / den.
+static __global__ __launch_bounds__(256) void index_gather_prepare_kernel(const float* __restrict__ feats, long S, const int64_t* __restrict__ cols,
+                                                                          float* rows, uint4* __restrict__ img, float* __restrict__ inv,
+                                                                          uint4* __restrict__ img16, float* __restrict__ index_out,
+                                                                          float* __restrict__ slot, long N) {
+    __shared__ float tile[GP_KC * GP_LD];
+    __shared__ float den_s[128];
+    __shared__ float red[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long n0 = blockIdx.x * 128L;
+    const int gn = tid & 127, gh = tid >> 7;      // the gather: vector gn of the tile, channels 32 gh ... of the chunk
+    const long n = n0 + gn;
+    const bool live = n < N;
+    const float* src = feats + gp_column(cols, n, N, S);
+    float s = 0.f, mx = 0.f;
+    for (int k0 = 0; k0 < KD; k0 += GP_KC) {
+        float x[32];
+#pragma unroll
+        for (int i = 0; i < 32; ++i) x[i] = src[(long)(k0 + gh * 32 + i) * S];      // (a vector beyond N reads column 0 and drops it)
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+            const float v = live ? x[i] : 0.f;
+            tile[(gh * 32 + i) * GP_LD + gn] = v;
+            mx = fmaxf(mx, fabsf(v));
+            if (index_out && live) index_out[(long)(k0 + gh * 32 + i) * N + n] = v;
+        }
+        __syncthreads();
+        if (tid < 128) {      // thread t owns vector t's chain (gn == tid): k ascending, one accumulator
+#pragma unroll 16
+            for (int k = 0; k < GP_KC; ++k) {
+                const float v = tile[k * GP_LD + tid];
+                s = fmaf(v, v, s);
+            }
+        }
+#pragma unroll 8
+        for (int j = 0; j < 32; ++j) {      // raw rows: a wave writes channels k0 ... k0 + 63 of one vector
+            const int r = wave * 32 + j;
+            if (n0 + r < N) rows[(n0 + r) * KD + k0 + lane] = tile[lane * GP_LD + r];
+        }
+        __syncthreads();
+    }
+    gp_amax_flush(mx, red, slot);
+    if (tid < 128) {
+        const float den = live ? sqrtf(s) + 1e-6f : 1.f;
+        den_s[tid] = den;
+        inv[n] = live ? 1.f / den : 0.f;
+    }
+    __syncthreads();
+    const int nl = wave * 32 + (lane & 31), lh = lane >> 5;      // pass 2: wave = m-tile, lane = (lh, vector & 31) - the MFMA lane of the piece
+    const float den = den_s[nl];
+    for (int k0 = 0; k0 < KD; k0 += GP_KC) {
+#pragma unroll 8
+        for (int j = 0; j < 32; ++j) {
+            const int r = wave * 32 + j;
+            tile[lane * GP_LD + r] = n0 + r < N ? rows[(n0 + r) * KD + k0 + lane] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int st = 0; st < GP_KC / 16; ++st) {
+            unsigned short b1[8], b2[8], b3[8], hf[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float raw = tile[(st * 16 + lh * 8 + j) * GP_LD + nl];
+                float v = raw / den;
+                hf[j] = __half_as_ushort(__float2half(v));
+                __bf16 h1 = (__bf16)v;
+                float r = v - (float)h1;
+                __bf16 h2 = (__bf16)r;
+                float r2 = r - (float)h2;
+                __bf16 h3 = (__bf16)r2;
+                b1[j] = __builtin_bit_cast(unsigned short, h1);
+                b2[j] = __builtin_bit_cast(unsigned short, h2);
+                b3[j] = __builtin_bit_cast(unsigned short, h3);
+            }
+            const long piece = ((long)blockIdx.x * STEPS + (k0 >> 4) + st) * 4 + wave;      // img_elem / 8 = (piece * parts + part) * 64 + lane
+            img[(piece * 3 + 0) * 64 + lane] = make_uint4(gp_pack(b1[0], b1[1]), gp_pack(b1[2], b1[3]), gp_pack(b1[4], b1[5]), gp_pack(b1[6], b1[7]));
+            img[(piece * 3 + 1) * 64 + lane] = make_uint4(gp_pack(b2[0], b2[1]), gp_pack(b2[2], b2[3]), gp_pack(b2[4], b2[5]), gp_pack(b2[6], b2[7]));
+            img[(piece * 3 + 2) * 64 + lane] = make_uint4(gp_pack(b3[0], b3[1]), gp_pack(b3[2], b3[3]), gp_pack(b3[4], b3[5]), gp_pack(b3[6], b3[7]));
+            img16[piece * 64 + lane] = make_uint4(gp_pack(hf[0], hf[1]), gp_pack(hf[2], hf[3]), gp_pack(hf[4], hf[5]), gp_pack(hf[6], hf[7]));
+        }
+        __syncthreads();
+    }
+}
+
+// fp16 storage: no raw rows, one pass.  The chunk holds the fp16-rounded values (as floats); wave w keeps the 64 lane-strided chains of its
+// 32 vectors in registers (chunk c is term c of every chain) and folds them with the butterfly behind the last chunk.
+static __global__ __launch_bounds__(256) void index_gather_prepare_f16_kernel(const float* __restrict__ feats, long S, const int64_t* __restrict__ cols,
+                                                                              float* __restrict__ inv, uint4* __restrict__ img, float* __restrict__ invmax,
+                                                                              __half* __restrict__ index_out, float* __restrict__ slot, long N) {
+    __shared__ float tile[GP_KC * GP_LD];
+    __shared__ float red[4];
+    __shared__ float imx[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long n0 = blockIdx.x * 128L;
+    const int gn = tid & 127, gh = tid >> 7;
+    const long n = n0 + gn;
+    const bool live = n < N;
+    const float* src = feats + gp_column(cols, n, N, S);
+    const int nl = wave * 32 + (lane & 31), lh = lane >> 5;
+    float p[32];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) p[j] = 0.f;
+    float mx = 0.f;
+    for (int k0 = 0; k0 < KD; k0 += GP_KC) {
+        float x[32];
+#pragma unroll
+        for (int i = 0; i < 32; ++i) x[i] = src[(long)(k0 + gh * 32 + i) * S];
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+            const __half h = __float2half(live ? x[i] : 0.f);
+            const float v = __half2float(h);
+            tile[(gh * 32 + i) * GP_LD + gn] = v;
+            mx = fmaxf(mx, fabsf(v));
+            if (index_out && live) index_out[(long)(k0 + gh * 32 + i) * N + n] = h;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 32; ++j) {
+            const float v = tile[lane * GP_LD + wave * 32 + j];
+            p[j] = fmaf(v, v, p[j]);
+        }
+#pragma unroll
+        for (int st = 0; st < GP_KC / 16; ++st) {
+            unsigned short hf[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) hf[j] = __half_as_ushort(__float2half(tile[(st * 16 + lh * 8 + j) * GP_LD + nl]));      // exact: the values are halves
+            const long piece = ((long)blockIdx.x * STEPS + (k0 >> 4) + st) * 4 + wave;
+            img[piece * 64 + lane] = make_uint4(gp_pack(hf[0], hf[1]), gp_pack(hf[2], hf[3]), gp_pack(hf[4], hf[5]), gp_pack(hf[6], hf[7]));
+        }
+        __syncthreads();
+    }
+    gp_amax_flush(mx, red, slot);
+    float wmax = 0.f;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+        float s = p[j];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        const long r = n0 + wave * 32 + j;
+        const float iv = r < N ? 1.f / (sqrtf(s) + 1e-6f) : 0.f;
+        if (lane == 0) inv[r] = iv;
+        wmax = fmaxf(wmax, iv);
+    }
+    if (lane == 0) imx[wave] = wmax;
+    __syncthreads();
+    if (tid == 0) invmax[blockIdx.x] = fmaxf(fmaxf(fmaxf(fmaxf(0.f, imx[0]), imx[1]), imx[2]), imx[3]);      // the tile's largest inverse norm (index_invmax_kernel)
+}
+
+int run_prepare_index_cols(tvc_ctx* ctx, hipStream_t s, const float* feats, int64_t S, const int64_t* cols, int64_t N, float* prepared, float* index_out) {
+    const long Npad = npad128(N);
+    hipLaunchKernelGGL(blob_header_kernel, dim3(1), dim3(64), 0, s, prepared, KIND_F32, (long)N);
+    float* rows = prepared + HDR;
+    uint4* img = reinterpret_cast<uint4*>(rows + (size_t)N * KD);
+    float* inv = const_cast<float*>(blob_inv(prepared, KIND_F32, N, Npad));
+    uint4* img16 = const_cast<uint4*>(blob_img16(prepared, KIND_F32, N, Npad));
+    hipLaunchKernelGGL(index_gather_prepare_kernel, dim3((unsigned)(Npad / 128)), dim3(256), 0, s, feats, (long)S, cols, rows, img, inv, img16, index_out,
+                       prepared + 4, (long)N);
+    return launch_check(ctx, "knn_prepare_index_cols");
+}
+
+int run_prepare_index_cols_f16(tvc_ctx* ctx, hipStream_t s, const float* feats, int64_t S, const int64_t* cols, int64_t N, float* prepared, void* index_out_f16) {
+    const long Npad = npad128(N);
+    hipLaunchKernelGGL(blob_header_kernel, dim3(1), dim3(64), 0, s, prepared, KIND_F16, (long)N);
+    float* inv = prepared + HDR;
+    uint4* img = reinterpret_cast<uint4*>(inv + Npad);
+    hipLaunchKernelGGL(index_gather_prepare_f16_kernel, dim3((unsigned)(Npad / 128)), dim3(256), 0, s, feats, (long)S, cols, inv, img,
+                       const_cast<float*>(blob_invmax(prepared, Npad)), reinterpret_cast<__half*>(index_out_f16), prepared + 4, (long)N);
+    return launch_check(ctx, "knn_prepare_index_cols_f16");
+}
+
 // qn[b][k][t] = src[b][k][t] / (||src[b][:][t]|| + 1e-6).  One workgroup = 64 consecutive columns;
 // its 4 waves each sum a quarter of the 768 channels (lanes along time, coalesced), partial sums of
 // squares meet in LDS in a fixed order, then every wave rescales its quarter.

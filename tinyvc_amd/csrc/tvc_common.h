@@ -398,6 +398,10 @@ int run_f32_to_pcm16(tvc_ctx*, hipStream_t, const float* x, int16_t* pcm, int64_
 void frontdoor_release(tvc_ctx*);
 int run_prepare_index(tvc_ctx*, hipStream_t, const float* index, float* prepared, int64_t N);
 int run_prepare_index_f16(tvc_ctx*, hipStream_t, const void* rows_f16, float* prepared, int64_t N);
+// the blobs run_prepare_index / _f16 make of feats[:, cols] (feats [768][S], cols a DEVICE array of N columns), gathered in one launch;
+// index_out (optional): feats[:, cols] itself, [768][N] fp32 / half
+int run_prepare_index_cols(tvc_ctx*, hipStream_t, const float* feats, int64_t S, const int64_t* cols, int64_t N, float* prepared, float* index_out);
+int run_prepare_index_cols_f16(tvc_ctx*, hipStream_t, const float* feats, int64_t S, const int64_t* cols, int64_t N, float* prepared, void* index_out_f16);
 
 // fused FilterNet kernels (filter_up24s.hip, conv48s.hip)
 // (the amax_* arguments are the per-utterance |max| slots of the block-floating-point guard, split_fp16.h)

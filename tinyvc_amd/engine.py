@@ -236,6 +236,54 @@ class Engine:
         self._ok(self.lib.tvc_knn_prepare_index_f32(self.ctx, self._stream(), _ptr(idx.contiguous()), _ptr(blob), N), "tvc_knn_prepare_index_f32")
         return self._owned(blob), N
 
+    def knn_prepare_columns(self, feats, cols, half=False, want_index=True):
+        """feats [768, S] fp32 (packed encoder features), cols [N] int64 columns into it -> (prepared blob, N, index [1, 768, N] or None):
+        the blob knn_prepare makes of feats[:, cols] (of its .half() with half=True), gathered in one launch
+        (tvc_knn_prepare_index_cols_f32 / _f16); index = the selected vectors themselves, fp32 or fp16.  `cols` must lie in [0, S)
+        (feature_retrieval.index_columns checks its plan on the host)."""
+        feats = _prep(feats, "feats", self.device)
+        if feats.dim() != 2 or feats.shape[0] != spec.SSL_DIM:
+            raise ValueError(f"feats must be [768, S], got {tuple(feats.shape)}")
+        cols = cols.to(device=self.device, dtype=torch.int64).contiguous()
+        if cols.dim() != 1:
+            raise ValueError("cols must be a 1-D list of columns")
+        S, N = feats.shape[1], cols.numel()
+        if N < 1:
+            raise ValueError("cols selects no vector")
+        index = torch.empty(1, spec.SSL_DIM, N, dtype=torch.float16 if half else _F32, device=self.device) if want_index else None
+        if half:
+            blob = torch.empty(self.lib.tvc_knn_prepared_elems_f16(N), dtype=_F32, device=self.device)
+            self._ok(self.lib.tvc_knn_prepare_index_cols_f16(self.ctx, self._stream(), _ptr(feats), S, _ptr(cols), N, _ptr(blob), _ptr(index)),
+                     "tvc_knn_prepare_index_cols_f16")
+        else:
+            blob = torch.empty(self.lib.tvc_knn_prepared_elems(N), dtype=_F32, device=self.device)
+            self._ok(self.lib.tvc_knn_prepare_index_cols_f32(self.ctx, self._stream(), _ptr(feats), S, _ptr(cols), N, _ptr(blob), _ptr(index)),
+                     "tvc_knn_prepare_index_cols_f32")
+        return self._owned(blob), N, index
+
+    def encode_ragged(self, wav, lengths):
+        """wav [B, Lmax] (row b holds an utterance of lengths[b] samples, a multiple of 480, zero-padded behind it) -> (ssl [768, S],
+        f0 [S], pre [B + 1]): every utterance encoded over its OWN length in one call (tvc_encode_ragged_f32), packed as one long
+        utterance - utterance b owns columns pre[b] .. pre[b + 1], bit-identical to stft_mag + encoder on it alone."""
+        wav = _prep(wav, "wave", self.device)
+        B, Lmax = wav.shape
+        if Lmax % spec.HOP:
+            raise ValueError("the padded length must be a multiple of 480")
+        if len(lengths) != B:
+            raise ValueError(f"lengths: {len(lengths)} entries for {B} rows")
+        lens = (ctypes.c_int64 * B)(*[int(x) for x in lengths])
+        need = ctypes.c_size_t()
+        self._ok(self.lib.tvc_workspace_bytes_encode_ragged(self.ctx, B, Lmax, lens, ctypes.byref(need)), "tvc_workspace_bytes_encode_ragged")
+        ws = self._grow_ws(need.value)
+        pre = [0]
+        for n in lengths:
+            pre.append(pre[-1] + int(n) // spec.HOP)
+        ssl = torch.empty(spec.SSL_DIM, pre[-1], dtype=_F32, device=self.device)
+        f0 = torch.empty(pre[-1], dtype=_F32, device=self.device)
+        self._ok(self.lib.tvc_encode_ragged_f32(self.ctx, self._stream(), _ptr(wav), Lmax, lens, _ptr(ssl), _ptr(f0), B, _ptr(ws),
+                                                ctypes.c_size_t(ws.numel())), "tvc_encode_ragged_f32")
+        return ssl, f0, pre
+
     def _owned(self, blob):
         """The library remembers a prepared blob's N by device address (api.hip: blob_check) and asks for tvc_knn_forget before the
         memory is reused: the allocator recycles addresses, and a blob copied to where a blob of another size once lived must not

@@ -36,12 +36,30 @@ class Generator(HipModule):
         return sd
 
     @torch.no_grad()
-    def encode(self, wf):
-        """generator.py:19-23: wf [B, L] -> (features [B,768,T] usable as a kNN index, f0 [B,1,T])."""
+    def encode(self, wf, lengths=None):
+        """generator.py:19-23: wf [B, L] -> (features [B,768,T] usable as a kNN index, f0 [B,1,T]).
+        `lengths` (extension): a RAGGED batch - row b of wf holds a clip of lengths[b] samples, zero-padded behind it.  Every clip is
+        encoded over its own length (padded to a multiple of 480) in one call and equals its own `encode` bit for bit; the result is
+        (list of B [1, 768, T_b] views of ONE packed [768, sum T_b] tensor, list of B [1, 1, T_b])."""
+        if lengths is None:
+            wf = utils.autopad_waveform(self._input_device(wf))
+            eng = self.engine(wf.device)
+            ssl, f0, _ = eng.encoder(eng.stft_mag(wf))
+            return ssl, f0
+        ssl, f0, pre = self.encode_packed(wf, lengths)
+        return ([ssl[None, :, pre[b]:pre[b + 1]] for b in range(len(pre) - 1)],
+                [f0[None, None, pre[b]:pre[b + 1]] for b in range(len(pre) - 1)])
+
+    @torch.no_grad()
+    def encode_packed(self, wf, lengths):
+        """The ragged `encode` as it leaves the device: (features [768, S], f0 [S], pre [B + 1]) - clip b owns columns pre[b] .. pre[b + 1]
+        (Engine.encode_ragged); what build_index selects its columns from."""
         wf = utils.autopad_waveform(self._input_device(wf))
-        eng = self.engine(wf.device)
-        ssl, f0, _ = eng.encoder(eng.stft_mag(wf))
-        return ssl, f0
+        B, L = wf.shape
+        lens = [-(-int(n) // 480) * 480 for n in lengths]
+        if len(lens) != B or max(lens) > L or min(lens) <= 960:
+            raise ValueError("lengths: one entry per row, each in (960, L]")
+        return self.engine(wf.device).encode_ragged(wf, lens)
 
     @torch.no_grad()
     def convert(self, wf, tgt, pitch_shift, f0_estimation="default", device=None, noise_angle=None, lengths=None):

@@ -21,6 +21,54 @@ def prepare_reference(reference):
     return blob, n
 
 
+def index_columns(frames, stride, size, perm=None):
+    """The reference's index recipe (extract_index.py:43-58) as a column plan, on the host: clips of frames[b] frames lie back to back in
+    packed features [768, sum(frames)]; every `stride`-th frame of each clip in order, concatenated, index_select(perm), the first `size`
+    -> the int64 columns of the packed features that make up the index, in its order.  perm (optional): a permutation - any index list -
+    of the strided frames; size None = all of them.  Raises ValueError if a column would fall outside the packed features, before
+    anything touches the device."""
+    frames = [int(t) for t in frames]
+    stride = int(stride)
+    if stride < 1 or any(t < 1 for t in frames):
+        raise ValueError("index_columns: stride >= 1 and at least one frame per clip")
+    parts, off = [], 0
+    for t in frames:
+        parts.append(torch.arange(off, off + t, stride, dtype=torch.int64))
+        off += t
+    cols = torch.cat(parts) if parts else torch.empty(0, dtype=torch.int64)
+    if perm is not None:
+        perm = torch.as_tensor(perm).to("cpu", torch.int64).reshape(-1)
+        if perm.numel() and (int(perm.min()) < 0 or int(perm.max()) >= cols.numel()):
+            raise ValueError(f"index_columns: perm selects outside the {cols.numel()} strided frames")
+        cols = cols.index_select(0, perm)
+    if size is not None:
+        if int(size) < 0:
+            raise ValueError("index_columns: size must not be negative")
+        cols = cols[:int(size)]
+    if cols.numel() and (int(cols.min()) < 0 or int(cols.max()) >= off):
+        raise ValueError(f"index_columns: a column outside the {off} packed frames")
+    return cols.contiguous()
+
+
+@torch.no_grad()
+def build_index(generator, wf, lengths, stride=4, size=None, perm=None, half=False):
+    """A speaker index from a batch of target clips in one pass on the device (the reference's extract_index.py:43-58 for clips already
+    in memory): wf [B, L] with clip b in its first lengths[b] samples -> index [1, 768, N] (fp32, or fp16 with half=True), the tensor
+    `assemble` of extract_index.py builds from one `encode` per clip.  Ragged encode, column plan (index_columns), one gather that writes
+    the index AND its prepared blob: the blob rides on the returned tensor like prepare_reference's, so the first convert /
+    match_features against it prepares nothing."""
+    ssl, _f0, pre = generator.encode_packed(wf, lengths)
+    cols = index_columns([pre[b + 1] - pre[b] for b in range(len(pre) - 1)], stride, size, perm)
+    return index_from_columns(generator.engine(ssl.device), ssl, cols, half)
+
+
+def index_from_columns(eng, feats, cols, half=False):
+    """feats [768, S] on the device, cols (host or device int64) -> index [1, 768, N] carrying its prepared blob (Engine.knn_prepare_columns)."""
+    blob, n, index = eng.knn_prepare_columns(feats, cols, half=half, want_index=True)
+    index._tvc_prepared = (index._version, str(index.device), blob, n)
+    return index
+
+
 def check_references(tgt, B=None):
     """Shape check of a multi-index target, on the host (no engine, no device work): a [B, 768, N] tensor or a list of B [1, 768, N_b]
     tensors (fp32 or fp16).  Returns the number of indices; raises ValueError when the form is malformed or B does not match."""
