@@ -19,6 +19,11 @@ the same `--seed`.
 encoder in ragged calls of at most F frames (Engine.encode_ragged: every clip over its own length, bit-identical to its own call), the
 features stay on the device, and ONE gather selects the strided, permuted, truncated columns (feature_retrieval.index_columns) - the same
 bytes as the default clip-by-clip run with the same `--seed`, without a host round trip per clip.
+
+`--compact K` compacts the index built by any of these routes to K vectors by k-means on the device (feature_retrieval.compact_index:
+cosine assignment, raw-mean update, `--compact-iters` rounds, started from K vectors drawn from the same generator) instead of
+truncating further: `-size` then sets how much of the speaker's material the centroids summarise.  `--compact-snap` replaces every
+centroid by its nearest real frame.  Without `--compact` the file is what it always was.
 """
 import argparse
 import glob
@@ -30,7 +35,7 @@ import torch
 from tinyvc_amd import audio_io, parallel
 from tinyvc_amd.module import utils
 from tinyvc_amd.module.tinyvc import Encoder
-from tinyvc_amd.module.tinyvc.feature_retrieval import index_columns, index_from_columns
+from tinyvc_amd.module.tinyvc.feature_retrieval import compact_index, index_columns, index_from_columns
 
 SAMPLE_RATE = 24000
 
@@ -136,7 +141,31 @@ def assemble(feats_in_order, size, gen, half):
     return tgt.half() if half else tgt
 
 
-def main(argv=None):
+def compacted(tgt, device, k, iters, snap, gen, half):
+    """The index `tgt` ([1, 768, n] on the CPU, fp32) compacted to k centroids on the device; the start vectors come from `gen`."""
+    if k > tgt.shape[2]:
+        sys.exit(f"--compact {k}: the index holds only {tgt.shape[2]} vectors")
+    out = compact_index(tgt.to(device), k, iters=iters, generator=gen, snap=snap).cpu()
+    return out.half() if half else out
+
+
+def parse_args(argv=None):
+    """The command line; --compact is checked against -size here, before any model is loaded."""
+    p = build_parser()
+    args = p.parse_args(argv)
+    if args.compact is not None:
+        if args.compact < 4:
+            p.error("--compact: an index needs at least 4 vectors")
+        if args.compact > args.size:
+            p.error("--compact must not exceed -size (the vectors it compacts)")
+        if args.compact_iters < 1:
+            p.error("--compact-iters must be at least 1")
+    elif args.compact_snap:
+        p.error("--compact-snap needs --compact")
+    return args
+
+
+def build_parser():
     p = argparse.ArgumentParser(description="extract index")
     p.add_argument("--dataset-cache", default="dataset_cache")
     p.add_argument("-encp", "--encoder-path", default="models/encoder.pt")
@@ -149,8 +178,16 @@ def main(argv=None):
     p.add_argument("--batch-frames", default=0, type=int,
                    help="encode the clips in ragged calls of at most this many frames and select the index on the device (0: clip by clip)")
     p.add_argument("--force-dist", action="store_true", help="run the WORLD_SIZE > 1 path (header-derived prefix, split, RCCL gather) even at world size 1")
-    args = p.parse_args(argv)
+    p.add_argument("--compact", default=None, type=int, metavar="K", help="compact the index of -size vectors to K k-means centroids on the device")
+    p.add_argument("--compact-iters", default=8, type=int, help="k-means rounds of --compact")
+    p.add_argument("--compact-snap", action="store_true", help="replace every centroid of --compact by its nearest real frame")
+    return p
 
+
+def main(argv=None):
+    args = parse_args(argv)
+
+    build_half = args.half and args.compact is None      # --compact works on the fp32 vectors; --half casts its result
     world, rank, local_rank = parallel.dist_env()
     sharded = world > 1 or args.force_dist
     device = torch.device(args.device)
@@ -169,7 +206,7 @@ def main(argv=None):
         gen = torch.Generator().manual_seed(args.seed) if args.seed is not None else None
         order = torch.randperm(len(files), generator=gen).tolist()      # DataLoader(shuffle=True) in the reference
         if args.batch_frames > 0:
-            tgt = batched_index(enc, device, files, order, args.stride, args.size, gen, args.half, args.batch_frames)
+            tgt = batched_index(enc, device, files, order, args.stride, args.size, gen, build_half, args.batch_frames)
         else:
             feats, total = [], 0
             for i in order:
@@ -178,7 +215,7 @@ def main(argv=None):
                 total += z.shape[2]
                 if total > args.size:
                     break
-            tgt = assemble(feats, args.size, gen, args.half)
+            tgt = assemble(feats, args.size, gen, build_half)
     else:
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -200,7 +237,7 @@ def main(argv=None):
             eng = enc.engine(device) if device.type == "cuda" else None
             cols = [clip_columns(f, args.stride, eng) for f in files]
             feats = sharded_features(cols, order, args.size, world, rank, lambda i: encode_clip(enc, device, files[i], args.stride), device)
-            tgt = assemble(feats, args.size, gen, args.half) if rank == 0 else None
+            tgt = assemble(feats, args.size, gen, build_half) if rank == 0 else None
             dist.barrier()
         finally:
             if own_group:
@@ -209,6 +246,8 @@ def main(argv=None):
                 os.environ.pop("MASTER_PORT", None)
         if rank != 0:
             return 0
+    if args.compact is not None:
+        tgt = compacted(tgt, device, args.compact, args.compact_iters, args.compact_snap, gen, args.half)
     print(f"Extracted {tgt.shape[2]} vectors")
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     torch.save(tgt, args.output)

@@ -172,6 +172,39 @@ int tvc_knn_match_f32(tvc_ctx* ctx, void* stream, const float* src, const float*
 int tvc_knn_match_general_f32(tvc_ctx* ctx, void* stream, const float* src, const float* index, int64_t N, int k, int metric,
                               float* out, int64_t* idx_out, float* sim_out, int B, int T, void* ws, size_t ws_bytes);
 
+/* compacting an index -------------------------------------------------------------------------- */
+/* A smaller index by k-means instead of truncation.  The reference has no counterpart: its recipe (extract_index.py:43-58) permutes the
+ * strided frames and keeps the first `size` - a random subsample -; these calls complement it by keeping K centroids of ALL the vectors
+ * (what RVC's index training and so-vits-svc's cluster model do on the host).  Points are the N raw vectors of a prepared blob of either
+ * kind (for the fp16 kind: the fp16 values); centroids are an fp32 tensor [768, K], index.pt's layout.  4 <= K <= N, K <= 1 048 576.
+ *   - tvc_index_assign_f32 stands in for `argmax(cosine(points, centroids))`: assign[n] (and sim_out[n], nullable) = column 0 of what
+ *     tvc_knn_topk_f32 returns for src = the points as [1, 768, N] against `centroids_prepared` (an fp32-kind blob of the centroids) - the
+ *     same similarity, the same tie rule (lower index), bit for bit.  The points go through that search in chunks of at most
+ *     tvc_ctx_set_index_assign_chunk query columns (default 32 768; 0 restores it; a property of the context - no environment variable, no
+ *     process-wide state; results do not depend on it).  moved_out (nullable, [1]) += the entries of assign_inout that changed: start
+ *     assign at -1 and moved at 0 and the first call counts N.
+ *   - tvc_index_update_f32 stands in for `centroids[:, k] = points[assign == k].mean(0)`: sums in fp64 in ascending point index (a
+ *     cluster longer than 256 members in runs of 256, the runs' partial sums added in run order), mean = sum / count in fp64, rounded once
+ *     to fp32.  A cluster without members keeps its previous centroid bit for bit (counts_out[k] = 0; counts_out [K] nullable); an assign
+ *     value outside [0, K) belongs to no cluster.  No floating-point atomics: bit-identical from run to run.
+ *   - tvc_index_compact_f32 is the loop: centroids[:, k] = point init_cols[k] (a DEVICE int64 [K]; a column outside [0, N) is clamped),
+ *     then `iters` times (prepare the centroids, assign, update) - a fixed count, no convergence test, no host synchronisation - and one
+ *     last prepare into prepared_out (tvc_knn_prepared_elems(K) floats, recorded like the prepare calls' blobs; it also serves as the
+ *     loop's own centroid blob).  Outputs: centroids_out [768, K], prepared_out, and nullable assign_out [N] / counts_out [K] (what the last
+ *     update used) and moved_out [iters] (points that changed cluster in each iteration; moved_out[0] = N).
+ * Cosine assignment with a raw-mean update is the pair the match itself computes (a mean of raw vectors selected by cosine); it does not
+ * minimise one objective monotonically: moved_out is what reports convergence.
+ * Asynchronous on `stream`; not meant for stream capture.  Workspace for any of the three: tvc_workspace_bytes_index_compact. */
+int tvc_ctx_set_index_assign_chunk(tvc_ctx* ctx, int max_queries);
+int tvc_workspace_bytes_index_compact(tvc_ctx* ctx, int64_t N, int64_t K, size_t* out_bytes);
+int tvc_index_assign_f32(tvc_ctx* ctx, void* stream, const float* points_prepared, int64_t N, const float* centroids_prepared, int64_t K,
+                         int64_t* assign_inout, float* sim_out, int32_t* moved_out, void* ws, size_t ws_bytes);
+int tvc_index_update_f32(tvc_ctx* ctx, void* stream, const float* points_prepared, int64_t N, const int64_t* assign, int64_t K,
+                         float* centroids_inout, int32_t* counts_out, void* ws, size_t ws_bytes);
+int tvc_index_compact_f32(tvc_ctx* ctx, void* stream, const float* points_prepared, int64_t N, const int64_t* init_cols, int64_t K, int iters,
+                          float* centroids_out, float* prepared_out, int64_t* assign_out, int32_t* counts_out, int32_t* moved_out, void* ws,
+                          size_t ws_bytes);
+
 /* pitch shift ----------------------------------------------------------------------------- */
 /* Index-sharded variant of the match (a very large speaker index split over the GPUs of a node):
  * every rank holds a prepared shard and

@@ -838,6 +838,75 @@ int tvc_convert_ragged_multi_f32(tvc_ctx* ctx, void* stream, const float* wav, i
     return walks_agree(ctx, __func__, ws.peak, need.peak);
 }
 
+// ---- compacting an index: k-means over a prepared blob (index_compact.hip) -------------------------------------------------------
+static int compact_check(tvc_ctx* ctx, int64_t N, int64_t K, const char* what) {
+    if (K < 4 || K > N) return fail(ctx, TVC_ERR_ARG, "%s: need 4 <= K <= N (K = %lld, N = %lld)", what, (long long)K, (long long)N);
+    if (K > kIndexCompactMaxK) return fail(ctx, TVC_ERR_ARG, "%s: K = %lld is above the limit of %lld centroids", what, (long long)K, (long long)kIndexCompactMaxK);
+    if (N > 0x7fffff00L) return fail(ctx, TVC_ERR_ARG, "%s: N beyond 32-bit indexing", what);
+    return 0;
+}
+
+int tvc_ctx_set_index_assign_chunk(tvc_ctx* ctx, int max_queries) {
+    if (!ctx) return TVC_ERR_ARG;
+    if (max_queries < 0) return fail(ctx, TVC_ERR_ARG, "tvc_ctx_set_index_assign_chunk: the chunk is a count of query columns (0 = the default)");
+    ctx->index_assign_chunk = max_queries;
+    return TVC_OK;
+}
+
+int tvc_workspace_bytes_index_compact(tvc_ctx* ctx, int64_t N, int64_t K, size_t* out_bytes) {
+    if (!ctx) return TVC_ERR_ARG;
+    if (!out_bytes) return fail(ctx, TVC_ERR_ARG, "tvc_workspace_bytes_index_compact: out_bytes is NULL");
+    TVC_CHECK(compact_check(ctx, N, K, "tvc_workspace_bytes_index_compact"));
+    Ws ws(nullptr, 0, true);
+    TVC_CHECK(run_index_compact(ctx, nullptr, ws, kDryPtr, N, nullptr, K, 1, kDryPtr, kDryPtr, nullptr, nullptr, nullptr));
+    *out_bytes = ws.peak + 4096;
+    return TVC_OK;
+}
+
+int tvc_index_assign_f32(tvc_ctx* ctx, void* stream, const float* points_prepared, int64_t N, const float* centroids_prepared, int64_t K,
+                         int64_t* assign_inout, float* sim_out, int32_t* moved_out, void* wsp, size_t ws_bytes) {
+    if (!ctx) return TVC_ERR_ARG;
+    if (!points_prepared || !centroids_prepared || !assign_inout) return fail(ctx, TVC_ERR_ARG, "tvc_index_assign_f32: bad argument");
+    TVC_CHECK(compact_check(ctx, N, K, "tvc_index_assign_f32"));
+    hipStream_t s = (hipStream_t)stream;
+    TVC_CHECK(blob_check(ctx, s, points_prepared, N, "tvc_index_assign_f32 (points)"));
+    TVC_CHECK(blob_check(ctx, s, centroids_prepared, K, "tvc_index_assign_f32 (centroids)"));
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    TVC_RUN(run_index_assign(ctx, s, ws, points_prepared, N, centroids_prepared, K, assign_inout, sim_out, moved_out));
+}
+
+int tvc_index_update_f32(tvc_ctx* ctx, void* stream, const float* points_prepared, int64_t N, const int64_t* assign, int64_t K, float* centroids_inout,
+                         int32_t* counts_out, void* wsp, size_t ws_bytes) {
+    if (!ctx) return TVC_ERR_ARG;
+    if (!points_prepared || !assign || !centroids_inout) return fail(ctx, TVC_ERR_ARG, "tvc_index_update_f32: bad argument");
+    TVC_CHECK(compact_check(ctx, N, K, "tvc_index_update_f32"));
+    hipStream_t s = (hipStream_t)stream;
+    TVC_CHECK(blob_check(ctx, s, points_prepared, N, "tvc_index_update_f32"));
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    TVC_RUN(run_index_update(ctx, s, ws, points_prepared, N, assign, K, centroids_inout, counts_out));
+}
+
+int tvc_index_compact_f32(tvc_ctx* ctx, void* stream, const float* points_prepared, int64_t N, const int64_t* init_cols, int64_t K, int iters,
+                          float* centroids_out, float* prepared_out, int64_t* assign_out, int32_t* counts_out, int32_t* moved_out, void* wsp, size_t ws_bytes) {
+    if (!ctx) return TVC_ERR_ARG;
+    if (!points_prepared || !init_cols || !centroids_out || !prepared_out || iters < 1) return fail(ctx, TVC_ERR_ARG, "tvc_index_compact_f32: bad argument (iters >= 1)");
+    TVC_CHECK(compact_check(ctx, N, K, "tvc_index_compact_f32"));
+    hipStream_t s = (hipStream_t)stream;
+    TVC_CHECK(blob_check(ctx, s, points_prepared, N, "tvc_index_compact_f32"));
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    blob_forget(prepared_out);
+    {
+        Ws need(nullptr, 0, true);
+        TVC_CHECK(run_index_compact(ctx, s, need, points_prepared, N, init_cols, K, iters, centroids_out, prepared_out, assign_out, counts_out, moved_out));
+        if (need.peak > ws_bytes) return fail(ctx, TVC_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need.peak, ws_bytes);
+        Ws ws(wsp, ws_bytes, false);
+        TVC_CHECK(run_index_compact(ctx, s, ws, points_prepared, N, init_cols, K, iters, centroids_out, prepared_out, assign_out, counts_out, moved_out));
+        TVC_CHECK(walks_agree(ctx, __func__, ws.peak, need.peak));
+    }
+    blob_record(prepared_out, K);
+    return TVC_OK;
+}
+
 int tvc_profile_enable(tvc_ctx* ctx, int on) {
     if (!ctx) return TVC_ERR_ARG;
     ctx->profiling = on < 0 ? 0 : (on > 2 ? 1 : on);

@@ -22,6 +22,7 @@
 #include <cstring>
 #include <vector>
 
+#include "knn_blob.h"
 #include "ragged.h"
 #include "small_kernels.h"
 #include "split_fp16.h"
@@ -29,23 +30,6 @@
 
 namespace tvc {
 
-constexpr int KD = kSslDim;        // 768
-constexpr int STEPS = KD / 16;     // 48 K16 steps per index tile
-constexpr int HDR = 64;            // blob header, floats: [0] magic, [1] kind, [2] N (low 32 bits), [3] N (high), [4] |max| of the raw vectors (a float), [5] format version (tvc_common.h)
-constexpr int KIND_F32 = 0, KIND_F16 = 1;
-constexpr int BLOB_MAGIC = kBlobMagic;
-// fp32 kind:  header | rows fp32 [N][768] | bf16x3 image of v / den [Npad*768*3 bf16] | inv = 1 / den [Npad] | fp16 image of v / den [Npad*768]
-// fp16 kind:  header | inv [Npad] | fp16 image of the raw vectors [Npad*768] | largest inv of every 128-vector tile [Npad/128]
-// (both fp16 images in the 128-vector-tiled MFMA lane order, one part)
-__host__ __device__ inline const float* blob_inv(const float* blob, int kind, long N, long Npad) {
-    return kind == KIND_F16 ? blob + HDR : blob + HDR + (size_t)N * KD + (size_t)Npad * KD * 3 / 2;
-}
-__host__ __device__ inline const uint4* blob_img16(const float* blob, int kind, long N, long Npad) {
-    return reinterpret_cast<const uint4*>(blob_inv(blob, kind, N, Npad) + Npad);
-}
-__host__ __device__ inline const float* blob_invmax(const float* blob, long Npad) {      // fp16 kind only
-    return blob + HDR + Npad + (size_t)Npad * KD / 2;
-}
 constexpr int KNN_BLOCKS = 1024;   // target workgroup count (query tiles x index splits)
 
 static inline int64_t npad128(int64_t N) { return (N + 127) / 128 * 128; }
@@ -112,21 +96,6 @@ __device__ __forceinline__ KnnSeg seg_get(const KnnSegs& S, int i) {
     return g;
 }
 __device__ __forceinline__ long seg_npad(const KnnSeg& g) { return ((long)g.N + 127) / 128 * 128; }
-
-// element (vector n, channel k) of a 128-vector-tiled MFMA-ordered image with P parts per (m-tile, step): the index of
-// part 0's 8-value piece row; row = lane & 31, k = 16 step + 8 (lane >> 5) + j
-__device__ __forceinline__ long img_elem(long n, int k, int parts) {
-    const long tile = n >> 7;
-    const int mt = (int)(n & 127) >> 5, l31 = (int)(n & 31);
-    const int step = k >> 4, lh = (k >> 3) & 1, j = k & 7;
-    return ((((tile * STEPS + step) * 4 + mt) * parts) * 64 + (lh * 32 + l31)) * 8 + j;
-}
-
-// raw vector value (n, k) of either blob kind (the gathers)
-__device__ __forceinline__ float blob_row_value(const float* __restrict__ blob, int kind, long N, long Npad, long n, int k) {
-    if (kind == KIND_F16) return __half2float(reinterpret_cast<const __half*>(blob + HDR + Npad)[img_elem(n, k, 1)]);
-    return blob[HDR + n * KD + k];
-}
 
 static __global__ void blob_header_kernel(float* blob, int kind, long N) {
     int* h = reinterpret_cast<int*>(blob);

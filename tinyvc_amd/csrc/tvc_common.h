@@ -139,6 +139,7 @@ struct tvc_ctx {
     hipEvent_t ev_fork2 = nullptr, ev_join2 = nullptr, ev_amps = nullptr;      // the decoder's fork: FilterNet's input contraction beside SourceNet / dsp (decoder.hip run_decoder)
     tvc::RagHost* rag = nullptr;              // the ragged batch the drivers are currently running for (ragged.h); nullptr = equal lengths
     int rag_batch_frames = 0;                 // tvc_ctx_set_ragged_batch_frames: frames per in-kernel batch of THIS context's ragged calls (0 = the default)
+    int index_assign_chunk = 0;               // tvc_ctx_set_index_assign_chunk: query columns per search call of THIS context's index assignment (0 = the default)
     bool enc_ready = false, dec_ready = false;  // which checkpoint groups tvc_finalize_weights packed
     char enc_missing[160] = {0}, dec_missing[160] = {0};
     std::map<std::string, tvc::HostTensor> host;  // staged checkpoint tensors
@@ -402,6 +403,15 @@ int run_prepare_index_f16(tvc_ctx*, hipStream_t, const void* rows_f16, float* pr
 // index_out (optional): feats[:, cols] itself, [768][N] fp32 / half
 int run_prepare_index_cols(tvc_ctx*, hipStream_t, const float* feats, int64_t S, const int64_t* cols, int64_t N, float* prepared, float* index_out);
 int run_prepare_index_cols_f16(tvc_ctx*, hipStream_t, const float* feats, int64_t S, const int64_t* cols, int64_t N, float* prepared, void* index_out_f16);
+
+// k-means over the raw vectors of a prepared blob (index_compact.hip): assignment = column 0 of run_knn_topk with the points as queries, in
+// chunks of kIndexAssignChunk (or the context's) query columns; update = segmented fp64 mean without floating-point atomics
+constexpr int kIndexAssignChunk = 32768;
+constexpr int64_t kIndexCompactMaxK = 1 << 20;
+int run_index_assign(tvc_ctx*, hipStream_t, Ws&, const float* points, int64_t N, const float* cent_blob, int64_t K, int64_t* assign, float* sim_out, int32_t* moved);
+int run_index_update(tvc_ctx*, hipStream_t, Ws&, const float* points, int64_t N, const int64_t* assign, int64_t K, float* centroids, int32_t* counts_out);
+int run_index_compact(tvc_ctx*, hipStream_t, Ws&, const float* points, int64_t N, const int64_t* init_cols, int64_t K, int iters, float* centroids, float* prepared_out,
+                      int64_t* assign_out, int32_t* counts_out, int32_t* moved_out);
 
 // fused FilterNet kernels (filter_up24s.hip, conv48s.hip)
 // (the amax_* arguments are the per-utterance |max| slots of the block-floating-point guard, split_fp16.h)

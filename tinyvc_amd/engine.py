@@ -104,6 +104,10 @@ class Engine:
         """Frames per in-kernel batch of this engine's ragged calls (0 = the default, 80 000); results do not depend on it."""
         self._ok(self.lib.tvc_ctx_set_ragged_batch_frames(self.ctx, int(max_frames)), "tvc_ctx_set_ragged_batch_frames")
 
+    def set_index_assign_chunk(self, max_queries):
+        """Points per search call of this engine's index_assign / index_compact (0 = the default, 32 768); results do not depend on it."""
+        self._ok(self.lib.tvc_ctx_set_index_assign_chunk(self.ctx, int(max_queries)), "tvc_ctx_set_index_assign_chunk")
+
     def next_seed(self):
         self._seed = (self._seed * 6364136223846793005 + 1442695040888963407) & 0xFFFFFFFFFFFFFFFF
         return self._seed
@@ -439,6 +443,72 @@ class Engine:
         out = torch.empty(B, spec.SSL_DIM, T, dtype=_F32, device=self.device)
         self._ok(self.lib.tvc_knn_finish_f32(self.ctx, self._stream(), _ptr(slots), _ptr(out), B, T), "tvc_knn_finish_f32")
         return out
+
+    # ---- compacting an index: k-means over a prepared blob (tvc_index_*_f32) ----
+    def _compact_ws(self, N, K):
+        need = ctypes.c_size_t()
+        self._ok(self.lib.tvc_workspace_bytes_index_compact(self.ctx, int(N), int(K), ctypes.byref(need)), "tvc_workspace_bytes_index_compact")
+        ws = self._grow_ws(need.value)
+        return _ptr(ws), ctypes.c_size_t(ws.numel())
+
+    def index_assign(self, points_blob, N, cent_blob, K, assign=None):
+        """Nearest centroid (cosine) of every raw vector of `points_blob` (a blob of knn_prepare, either kind, N vectors) among the K vectors of
+        `cent_blob` (an fp32-kind blob) -> (assign [N] int64, sims [N] fp32, moved [1] int32): column 0 of knn_topk with the points as queries,
+        bit for bit.  assign (optional, [N] int64 on the device) is the previous assignment, updated in place; moved counts the entries that
+        changed (all N without a previous assignment)."""
+        N, K = int(N), int(K)
+        if assign is None:
+            assign = torch.full((N,), -1, dtype=torch.int64, device=self.device)
+        _check_dev(assign, "assign", self.device)
+        if assign.dtype != torch.int64 or tuple(assign.shape) != (N,) or not assign.is_contiguous():
+            raise ValueError("assign must be a contiguous int64 tensor of N entries")
+        sims = torch.empty(N, dtype=_F32, device=self.device)
+        moved = torch.zeros(1, dtype=torch.int32, device=self.device)
+        p, n = self._compact_ws(N, K)
+        self._ok(self.lib.tvc_index_assign_f32(self.ctx, self._stream(), _ptr(points_blob), N, _ptr(cent_blob), K, _ptr(assign), _ptr(sims), _ptr(moved), p, n),
+                 "tvc_index_assign_f32")
+        return assign, sims, moved
+
+    def index_update(self, points_blob, N, assign, centroids):
+        """centroids [768, K] fp32 (updated in place and returned): column k <- the mean of the raw vectors n of `points_blob` with
+        assign[n] == k (fp64 sums in ascending n, rounded once); a cluster without members keeps its column, entries of assign outside
+        [0, K) belong to no cluster -> (centroids, counts [K] int32)."""
+        N = int(N)
+        _check_dev(centroids, "centroids", self.device)
+        if centroids.dtype != _F32 or centroids.dim() != 2 or centroids.shape[0] != spec.SSL_DIM or not centroids.is_contiguous():
+            raise ValueError("centroids must be a contiguous fp32 [768, K] tensor")
+        K = centroids.shape[1]
+        assign = assign.to(device=self.device, dtype=torch.int64).contiguous()
+        if tuple(assign.shape) != (N,):
+            raise ValueError("assign must have N entries")
+        counts = torch.empty(K, dtype=torch.int32, device=self.device)
+        p, n = self._compact_ws(N, K)
+        self._ok(self.lib.tvc_index_update_f32(self.ctx, self._stream(), _ptr(points_blob), N, _ptr(assign), K, _ptr(centroids), _ptr(counts), p, n),
+                 "tvc_index_update_f32")
+        return centroids, counts
+
+    def index_compact(self, points_blob, N, init_cols, iters):
+        """k-means over the N raw vectors of `points_blob`: centroids start as the points init_cols [K] (int64), then `iters` rounds of
+        (prepare, index_assign, index_update) in one call without a host synchronisation (tvc_index_compact_f32) ->
+        (index [1, 768, K] fp32, its prepared blob, assign [N] int64, counts [K] int32, moved [iters] int32)."""
+        N, iters = int(N), int(iters)
+        init_cols = init_cols.to(device=self.device, dtype=torch.int64).contiguous()
+        if init_cols.dim() != 1:
+            raise ValueError("init_cols must be a 1-D list of point numbers")
+        K = init_cols.numel()
+        if not 4 <= K <= N:
+            raise ValueError(f"index_compact: need 4 <= K <= N, got K = {K}, N = {N}")
+        if iters < 1:
+            raise ValueError("index_compact: iters >= 1")
+        index = torch.empty(1, spec.SSL_DIM, K, dtype=_F32, device=self.device)
+        blob = torch.empty(self.lib.tvc_knn_prepared_elems(K), dtype=_F32, device=self.device)
+        assign = torch.empty(N, dtype=torch.int64, device=self.device)
+        counts = torch.empty(K, dtype=torch.int32, device=self.device)
+        moved = torch.empty(iters, dtype=torch.int32, device=self.device)
+        p, n = self._compact_ws(N, K)
+        self._ok(self.lib.tvc_index_compact_f32(self.ctx, self._stream(), _ptr(points_blob), N, _ptr(init_cols), K, iters, _ptr(index), _ptr(blob), _ptr(assign),
+                                                _ptr(counts), _ptr(moved), p, n), "tvc_index_compact_f32")
+        return index, self._owned(blob), assign, counts, moved
 
     def shift_frequency(self, f0, semitones):
         f0 = _prep(f0, "f0", self.device)

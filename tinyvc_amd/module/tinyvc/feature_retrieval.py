@@ -69,6 +69,35 @@ def index_from_columns(eng, feats, cols, half=False):
     return index
 
 
+@torch.no_grad()
+def compact_index(reference, size, iters=8, generator=None, init_cols=None, snap=False, return_info=False):
+    """A smaller index by k-means instead of truncation: reference [1, 768, N] (fp32 or fp16) -> [1, 768, size] fp32, the centroids of
+    `iters` rounds of (cosine assignment, raw-mean update) on the device (Engine.index_compact), started from the vectors init_cols
+    (default: torch.randperm(N, generator=generator)[:size]).  The reference's recipe (extract_index.py:43-58) reaches a size by dropping
+    vectors; this keeps the mean of every group of similar ones.  The prepared blob rides on the result like index_from_columns'.
+    snap=True replaces each centroid by its nearest vector of `reference` (cosine): the result then holds real frames of the speaker, not
+    averages.  return_info=True -> (index, {"assign", "counts", "moved"}): the last assignment [N], the cluster sizes [size] and the points
+    that changed cluster in each round [iters]."""
+    if not isinstance(reference, torch.Tensor) or reference.dim() != 3 or reference.shape[0] != 1 or reference.shape[1] != 768:
+        raise ValueError(f"compact_index: reference must be [1, 768, N], got {tuple(getattr(reference, 'shape', ()))}")
+    N, size = reference.shape[2], int(size)
+    if not 4 <= size <= N:
+        raise ValueError(f"compact_index: need 4 <= size <= N, got size = {size}, N = {N}")
+    if init_cols is None:
+        init_cols = torch.randperm(N, generator=generator)[:size]
+    init_cols = torch.as_tensor(init_cols).to(torch.int64).reshape(-1)
+    if init_cols.numel() != size or int(init_cols.min()) < 0 or int(init_cols.max()) >= N:
+        raise ValueError(f"compact_index: init_cols must be {size} point numbers in [0, {N})")
+    eng = default_engine(reference.device)
+    blob, n = prepare_reference(reference)
+    index, cblob, assign, counts, moved = eng.index_compact(blob, n, init_cols, iters)
+    if snap:
+        _sims, idx = eng.knn_topk(index, blob, n)
+        cblob, _k, index = eng.knn_prepare_columns(reference[0].float(), idx[0, :, 0], half=False, want_index=True)
+    index._tvc_prepared = (index._version, str(index.device), cblob, size)
+    return (index, {"assign": assign, "counts": counts, "moved": moved}) if return_info else index
+
+
 def check_references(tgt, B=None):
     """Shape check of a multi-index target, on the host (no engine, no device work): a [B, 768, N] tensor or a list of B [1, 768, N_b]
     tensors (fp32 or fp16).  Returns the number of indices; raises ValueError when the form is malformed or B does not match."""
