@@ -299,7 +299,7 @@ def test_stream_push_equals_roll_past_32768_samples(gen, n):
 
 def test_workspace_of_exactly_the_measured_peak_and_one_byte_less(gen):
     """Every entry measures its workspace with a walk that launches nothing (ws.dry) before its launching walk, and checks behind the second
-    that it took no more (api.hip TVC_RUN).  tvc_workspace_bytes - 4096 is that peak: a conversion in exactly it equals one in the engine's
+    that it took no more (api.hip run_walks).  tvc_workspace_bytes - 4096 is that peak: a conversion in exactly it equals one in the engine's
     own workspace bit for bit, and one byte less is refused with TVC_ERR_WORKSPACE before anything launches (the output keeps its NaN fill).
     The same for a ragged call with tvc_workspace_bytes_ragged - 4096."""
     import ctypes
@@ -341,3 +341,122 @@ def test_workspace_of_exactly_the_measured_peak_and_one_byte_less(gen):
             assert torch.equal(out, eng.convert_ragged(wr, [480 * f for f in frames], blob, n, 0.5, noise_angle=ar)), "a ragged call in exactly the measured workspace"
         else:
             assert out.isnan().all(), "a refused ragged call launched something"
+
+
+def test_exact_workspace_for_the_multi_ragged_encode_and_compact_entries(gen):
+    """The contract of the test above - a call in exactly the measured peak equals the engine's own call bit for bit, one byte less is
+    refused with TVC_ERR_WORKSPACE before anything launches (every output keeps its fill: NaN, or -7 in the integer tensors) - for the
+    other entries that walk twice: tvc_convert_multi_f32, tvc_knn_match_multi_f32, tvc_convert_ragged_multi_f32, tvc_encode_ragged_f32
+    (several batches, so the packing launch too) and tvc_index_compact_f32 (assign_out = NULL: the call its query measures).  The peak is the entry's tvc_workspace_bytes* - 4096;
+    tvc_knn_match_multi_f32 has no query of its own (the engine gives it a conversion's workspace), so its peak is read from the
+    refusal of a call without any workspace ("need <peak> bytes")."""
+    import ctypes
+    import re
+    from tinyvc_amd.engine import _ptr
+    eng = gen.engine(DEV)
+    lib, ctx = eng.lib, eng.ctx
+    nan = float("nan")
+
+    def exact_and_one_less(what, peak, fresh, call, check):
+        """call(outs, ws, nbytes) -> rc at `peak` bytes (then check(outs)) and at peak - 1 (then every out keeps its fill)"""
+        for extra, rc_want in ((0, 0), (-1, -4)):                      # -4: TVC_ERR_WORKSPACE
+            ws = torch.empty(peak + extra, dtype=torch.uint8, device=DEV)
+            outs = fresh()
+            rc = call(outs, _ptr(ws), ws.numel())
+            torch.cuda.synchronize()
+            assert rc == rc_want, (what, extra, rc, lib.tvc_last_error(ctx))
+            if rc == 0:
+                check(outs)
+            else:
+                for o in outs:
+                    assert (o.isnan() if o.is_floating_point() else o == -7).all(), f"{what}: a refused call launched something"
+
+    B, T = 2, 40
+    L = 480 * T
+    wf = synth.synth_wave(B, L, seed=51).to(DEV)
+    b1, n1 = eng.knn_prepare(synth.synth_index(300, seed=52).to(DEV))
+    b2, n2 = eng.knn_prepare(synth.synth_index(260, seed=53).to(DEV))
+    need = ctypes.c_size_t()
+
+    # ---- tvc_convert_multi_f32: two rows, two indices, one shift per row
+    blobs, ns, sh = (ctypes.c_void_p * 2)(b1.data_ptr(), b2.data_ptr()), (ctypes.c_int64 * 2)(n1, n2), (ctypes.c_float * 2)(0.5, -1.0)
+    angle = synth.synth_angle(B, T, 54).to(DEV)
+    want = eng.convert_multi(wf, [b1, b2], [n1, n2], [0.5, -1.0], noise_angle=angle)
+    assert lib.tvc_workspace_bytes_multi(ctx, B, L, ns, ctypes.byref(need)) == 0
+    multi_bytes = need.value
+
+    def check_wave(outs):
+        assert torch.equal(outs[0], want)
+    exact_and_one_less("convert_multi", multi_bytes - 4096, lambda: [torch.full((B, L), nan, device=DEV)],
+                       lambda o, p, nb: lib.tvc_convert_multi_f32(ctx, eng._stream(), _ptr(wf), blobs, ns, 0.0, sh, _ptr(angle), 0, _ptr(o[0]), B, L, p, nb), check_wave)
+
+    # ---- tvc_knn_match_multi_f32: the same table, indices wanted
+    src = torch.randn(B, 768, T, generator=torch.Generator().manual_seed(55)).to(DEV)
+    want_m, want_i = eng.knn_match_multi(src, [b1, b2], [n1, n2], want_indices=True)
+
+    def match(o, p, nb):
+        return lib.tvc_knn_match_multi_f32(ctx, eng._stream(), _ptr(src), blobs, ns, _ptr(o[0]), _ptr(o[1]), B, T, p, nb)
+    probe = [torch.full((B, 768, T), nan, device=DEV), torch.full((B, T, 4), -7, dtype=torch.int64, device=DEV)]
+    assert match(probe, None, 0) == -4
+    peak = int(re.search(rb"need (\d+) bytes", lib.tvc_last_error(ctx)).group(1))
+    assert 0 < peak <= multi_bytes - 4096, "the engine's workspace for this call covers it"
+
+    def check_match(outs):
+        assert torch.equal(outs[0], want_m) and torch.equal(outs[1], want_i)
+    exact_and_one_less("knn_match_multi", peak, lambda: [torch.full((B, 768, T), nan, device=DEV), torch.full((B, T, 4), -7, dtype=torch.int64, device=DEV)],
+                       match, check_match)
+
+    # ---- tvc_convert_ragged_multi_f32: two length classes = two batches; rows 0 and 2 share an index
+    frames = [40, 13, 7]
+    lengths = [480 * f for f in frames]
+    lens = (ctypes.c_int64 * 3)(*lengths)
+    wr = torch.zeros(3, L, device=DEV)
+    for b, f in enumerate(frames):
+        wr[b, :480 * f] = wf[b % B, :480 * f]
+    blobs3, ns3, sh3 = (ctypes.c_void_p * 3)(b1.data_ptr(), b2.data_ptr(), b1.data_ptr()), (ctypes.c_int64 * 3)(n1, n2, n1), (ctypes.c_float * 3)(0.5, -1.0, 2.0)
+    ar = synth.synth_angle(3, T, 56).to(DEV)
+    want_r = eng.convert_ragged_multi(wr, lengths, [b1, b2, b1], [n1, n2, n1], [0.5, -1.0, 2.0], noise_angle=ar)
+    assert lib.tvc_workspace_bytes_ragged_multi(ctx, 3, L, lens, ns3, ctypes.byref(need)) == 0
+
+    def check_ragged(outs):
+        assert torch.equal(outs[0], want_r)
+    exact_and_one_less("convert_ragged_multi", need.value - 4096, lambda: [torch.full((3, L), nan, device=DEV)],
+                       lambda o, p, nb: lib.tvc_convert_ragged_multi_f32(ctx, eng._stream(), _ptr(wr), L, lens, blobs3, ns3, 0.0, sh3, _ptr(ar), 0, _ptr(o[0]), 3, p, nb),
+                       check_ragged)
+
+    # ---- tvc_encode_ragged_f32 under a cap of 45 frames: batches [40] and [13, 7], packed by pack_batch_kernel
+    S = sum(frames)
+    try:
+        eng.set_ragged_batch_frames(45)
+        want_ssl, want_f0, _ = eng.encode_ragged(wr, lengths)
+        assert lib.tvc_workspace_bytes_encode_ragged(ctx, 3, L, lens, ctypes.byref(need)) == 0
+
+        def check_enc(outs):
+            assert torch.equal(outs[0], want_ssl) and torch.equal(outs[1], want_f0)
+        exact_and_one_less("encode_ragged", need.value - 4096, lambda: [torch.full((768, S), nan, device=DEV), torch.full((S,), nan, device=DEV)],
+                           lambda o, p, nb: lib.tvc_encode_ragged_f32(ctx, eng._stream(), _ptr(wr), L, lens, _ptr(o[0]), _ptr(o[1]), 3, p, nb), check_enc)
+    finally:
+        eng.set_ragged_batch_frames(0)
+
+    # ---- tvc_index_compact_f32: 300 points -> 8 centroids, two rounds; the accepted call records its blob for N = K
+    N, K, iters = n1, 8, 2
+    cols = (torch.arange(K, dtype=torch.int64) * 37).to(DEV)
+    w_index, w_blob, w_assign, w_counts, w_moved = eng.index_compact(b1, N, cols, iters)
+    q = src[:1].contiguous()
+    w_top = eng.knn_topk(q, w_blob, K)
+    assert lib.tvc_workspace_bytes_index_compact(ctx, N, K, ctypes.byref(need)) == 0
+
+    def fresh_compact():
+        return [torch.full((1, 768, K), nan, device=DEV), eng._owned(torch.full((lib.tvc_knn_prepared_elems(K),), nan, device=DEV)),
+                torch.full((K,), -7, dtype=torch.int32, device=DEV), torch.full((iters,), -7, dtype=torch.int32, device=DEV)]
+
+    def check_compact(outs):
+        index, blob, counts, moved = outs
+        assert torch.equal(index, w_index) and torch.equal(counts, w_counts) and torch.equal(moved, w_moved)
+        assert int(counts.sum()) == N and torch.equal(torch.bincount(w_assign, minlength=K).int(), counts)
+        top = eng.knn_topk(q, blob, K)                                 # (the blob's unwritten padding is whatever the buffer held: compared through a search)
+        assert torch.equal(top[0], w_top[0]) and torch.equal(top[1], w_top[1])
+    # assign_out = NULL: the assignment then lives in the workspace, which is the call the query measures (with assign_out it needs N * 8 bytes less)
+    exact_and_one_less("index_compact", need.value - 4096, fresh_compact,
+                       lambda o, p, nb: lib.tvc_index_compact_f32(ctx, eng._stream(), _ptr(b1), N, _ptr(cols), K, iters, _ptr(o[0]), _ptr(o[1]), None, _ptr(o[2]),
+                                                                  _ptr(o[3]), p, nb), check_compact)

@@ -1,7 +1,9 @@
-// libtinyvc_hip.so — context, workspace sizing and the extern "C" surface (checkpoint packing: pack.hip).
+// libtinyvc_hip.so — the extern "C" surface: context, prepared-blob registry, argument checks, and the two workspace walks every entry
+// makes (run_walks; measure for the tvc_workspace_bytes* queries).  An entry validates, describes its call and hands it to run_walks.
+// The one driver that lives here is convert_impl (the stage drivers chained); no kernel does - checkpoint packing: pack.hip, the
+// ragged batch planner and its loops: ragged.hip.
 #include <atomic>
 #include <cmath>
-#include <functional>
 #include <mutex>
 
 #include <cstdlib>
@@ -190,16 +192,13 @@ static int need_ready(tvc_ctx* ctx, int need) {
     return 0;
 }
 
-// One prepared index (and optionally one pitch shift) per row of a call (tvc_*_multi): host arrays indexed by the caller's row.
-struct RowIndex {
-    const float* const* blob;
-    const int64_t* N;
-    const float* shifts;       // nullptr: every row takes the call's pitch_shift
-};
+}  // extern "C": convert_impl is declared in tvc_common.h, the walk runners are templates
 
-static int convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* wav, const float* prepared,
-                        int64_t N, float pitch_shift, const float* angle,
-                        uint64_t seed, float* wave, int B, int64_t L, const RowIndex* rows = nullptr) {
+// Generator.convert: c.B rows of c.L samples each (tvc_common.h ConvertCall; a ragged batch comes as ONE row with ctx->rag set, ragged.hip)
+int tvc::convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const ConvertCall& c) {
+    const int B = c.B;
+    const int64_t L = c.L;
+    const ConvertIndex& ix = c.index;
     const int T = (int)(L / kHop);
     float* spec = ws.get<float>((size_t)B * kBins * T);
     float* energy = ws.get<float>((size_t)B * L);
@@ -216,28 +215,27 @@ static int convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* wav, c
     float* emax = ws.get<float>((size_t)5 * NB);
     float* spec_bound = emax + NB;
     float* enc_slots = spec_bound + NB;      // the encoder's three atomicMax slots: zeroed by the energy stage's pooled-maximum launch
-    const bool bounds = true;
     // one index per row: every utterance's matched-content bound is its own index's |max| (so its fp16-split scales, and its bits, are those
     // of its own B = 1 call), and its runs of query columns go to the search as segments; per-row pitch shifts travel like the lengths
-    float* rowmax = rows ? ws.get<float>((size_t)NB) : nullptr;
-    float* rshift = rows && rows->shifts ? ws.get<float>((size_t)NB) : nullptr;
+    float* rowmax = ix.per_row ? ws.get<float>((size_t)NB) : nullptr;
+    float* rshift = ix.per_row && c.shifts ? ws.get<float>((size_t)NB) : nullptr;
     std::vector<KnnSegIn> segs;
-    if (rows) {
+    if (ix.per_row) {
         for (int i = 0; i < NB; ++i) {
             const int r = ctx->rag ? ctx->rag->row[i] : i;
             const int c0 = ctx->rag ? ctx->rag->pre[i] : i * T, nc = ctx->rag ? ctx->rag->tb[i] : T;
-            segs.push_back(KnnSegIn{rows->blob[r], rows->N[r], c0, nc});
+            segs.push_back(KnnSegIn{ix.blobs[r], ix.Ns[r], c0, nc});
         }
     } else {
-        segs.push_back(KnnSegIn{prepared, N, 0, B * T});
+        segs.push_back(KnnSegIn{ix.blob, ix.N, 0, B * T});
     }
-    if (rows && !ws.dry) {
+    if (ix.per_row && !ws.dry) {
         std::vector<const float*> bl(NB);
         std::vector<int> sh(NB);
         for (int i = 0; i < NB; ++i) {
             const int r = ctx->rag ? ctx->rag->row[i] : i;
-            bl[i] = rows->blob[r];
-            if (rshift) std::memcpy(&sh[i], &rows->shifts[r], sizeof(int));
+            bl[i] = ix.blobs[r];
+            if (rshift) std::memcpy(&sh[i], &c.shifts[r], sizeof(int));
         }
         TVC_CHECK(run_knn_amax_rows(ctx, s, bl, rowmax));
         if (rshift) TVC_CHECK(upload_ints(ctx, s, sh, reinterpret_cast<int*>(rshift)));
@@ -245,17 +243,17 @@ static int convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* wav, c
     size_t m = ws.mark();
     {
         ProfScope ps(ctx, s, ws, "stft");
-        TVC_CHECK(run_stft(ctx, s, ws, wav, spec, B, L));
+        TVC_CHECK(run_stft(ctx, s, ws, c.wav, spec, B, L));
     }
     ws.release(m);
     {
         ProfScope ps(ctx, s, ws, "energy");
-        TVC_CHECK(run_energy(ctx, s, ws, wav, energy, B, L, bounds ? emax : nullptr, bounds ? spec_bound : nullptr, bounds ? enc_slots : nullptr, 3 * NB));
+        TVC_CHECK(run_energy(ctx, s, ws, c.wav, energy, B, L, emax, spec_bound, enc_slots, 3 * NB));
     }
     ws.release(m);
     {
         ProfScope ps(ctx, s, ws, "encoder");
-        TVC_CHECK(run_encoder(ctx, s, ws, spec, ssl, f0, nullptr, B, T, bounds ? spec_bound : nullptr, bounds ? enc_slots : nullptr, f0s, pitch_shift, rshift));
+        TVC_CHECK(run_encoder(ctx, s, ws, spec, ssl, f0, nullptr, B, T, spec_bound, enc_slots, f0s, c.shift, rshift));
     }
     ws.release(m);
     {
@@ -263,8 +261,8 @@ static int convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* wav, c
         TVC_CHECK(run_knn_segs(ctx, s, ws, ssl, segs.data(), (int)segs.size(), matched, nullptr, B, T));
     }
     ws.release(m);
-    TVC_CHECK(run_decoder(ctx, s, ws, matched, f0s, energy, angle, seed, wave, nullptr, nullptr, nullptr, B, T, ws.dry ? nullptr : (rows ? rowmax : knn_index_amax(prepared)),
-                          bounds ? emax : nullptr, rows ? 1 : 0));
+    TVC_CHECK(run_decoder(ctx, s, ws, matched, f0s, energy, c.angle, c.seed, c.wave, nullptr, nullptr, nullptr, B, T,
+                          ws.dry ? nullptr : (ix.per_row ? rowmax : knn_index_amax(ix.blob)), emax, ix.per_row ? 1 : 0));
     ws.release(m);
     return 0;
 }
@@ -277,29 +275,40 @@ static int walks_agree(tvc_ctx* ctx, const char* entry, size_t real_peak, size_t
     return real_peak <= measured ? TVC_OK : fail(ctx, TVC_ERR_WORKSPACE, "%s: the launching walk took %zu workspace bytes, the measuring walk %zu", entry, real_peak, measured);
 }
 
-int tvc_workspace_bytes(tvc_ctx* ctx, int B, int64_t L, int64_t N, size_t* out_bytes) {
-    TVC_CHECK(need_ready(ctx, NEED_NONE));
-    if (!out_bytes || B <= 0 || L <= 0 || L % kHop != 0 || N < 4) return fail(ctx, TVC_ERR_ARG, "tvc_workspace_bytes: need B>0, L%%480==0, N>=4");
+// Workspace is validated *before* launching: every entry walks its drivers twice, first with a Ws that only measures (ws.dry), then with the
+// caller's workspace.  Both walks take the same allocations (tvc_common.h Ws); the host check behind the second one states it.
+//   walk(Ws&) -> int        the entry's driver calls; called twice, so it must not change what it captures
+//   granule                 the measured peak counts in whole granules: 1, or 4 KiB pages for the ragged entries (kRagGranule)
+//   before_launch() -> int  (optional) runs once the workspace is known to suffice, in front of the launching walk
+// A refused call has launched nothing: the measuring walk launches nothing, and before_launch runs behind the size check.
+// (Function templates over the callables, no std::function: this is the host time of a B = 1 call.)
+static size_t whole_granules(size_t bytes, size_t granule) { return (bytes + granule - 1) / granule * granule; }
+template <class Walk, class Step>
+static int run_walks(tvc_ctx* ctx, const char* entry, void* wsp, size_t ws_bytes, size_t granule, Walk&& walk, Step&& before_launch) {
+    Ws need(nullptr, 0, true);
+    TVC_CHECK(walk(need));
+    const size_t bytes = whole_granules(need.peak, granule);
+    if (bytes > ws_bytes) return fail(ctx, TVC_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", bytes, ws_bytes);
+    TVC_CHECK(before_launch());
+    Ws ws(wsp, bytes, false);
+    TVC_CHECK(walk(ws));
+    return walks_agree(ctx, entry, ws.peak, need.peak);
+}
+template <class Walk>
+static int run_walks(tvc_ctx* ctx, const char* entry, void* wsp, size_t ws_bytes, size_t granule, Walk&& walk) {
+    return run_walks(ctx, entry, wsp, ws_bytes, granule, walk, [] { return 0; });
+}
+// the measuring walk alone, for the tvc_workspace_bytes* queries: the same granules, and 4096 bytes on top of the peak
+template <class Walk>
+static int measure(size_t granule, size_t* out_bytes, Walk&& walk) {
     Ws ws(nullptr, 0, true);
-    TVC_CHECK(convert_impl(ctx, nullptr, ws, kDryPtr, kDryPtr, N, 0.f, nullptr, 0, kDryPtr, B, L));
-    *out_bytes = ws.peak + 4096;
+    TVC_CHECK(walk(ws));
+    *out_bytes = whole_granules(ws.peak, granule) + 4096;
     return TVC_OK;
 }
+constexpr size_t kRagGranule = 4096;
 
-// Workspace is validated *before* launching: every entry walks `call` twice, first with a Ws that only measures (ws.dry), then with the
-// caller's workspace.  Both walks take the same allocations (tvc_common.h Ws); the host check behind the second one states it.
-#define TVC_RUN(call)                                                                                                           \
-    {                                                                                                                           \
-        Ws need(nullptr, 0, true);                                                                                              \
-        {                                                                                                                       \
-            Ws& ws = need;                                                                                                      \
-            TVC_CHECK(call);                                                                                                    \
-        }                                                                                                                       \
-        if (need.peak > ws_bytes) return fail(ctx, TVC_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need.peak, ws_bytes); \
-        Ws ws(wsp, ws_bytes, false);                                                                                            \
-        TVC_CHECK(call);                                                                                                        \
-        return walks_agree(ctx, __func__, ws.peak, need.peak);                                                                  \
-    }
+extern "C" {
 
 int tvc_stft_mag_f32(tvc_ctx* ctx, void* stream, const float* wav, float* spec, int B, int64_t L, void* wsp, size_t ws_bytes) {
     TVC_CHECK(need_ready(ctx, NEED_NONE));
@@ -307,7 +316,7 @@ int tvc_stft_mag_f32(tvc_ctx* ctx, void* stream, const float* wav, float* spec, 
     if (L < kNfft / 2 + 1) return fail(ctx, TVC_ERR_ARG, "tvc_stft_mag_f32: L must exceed 960 (reflect padding)");
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    TVC_RUN(run_stft(ctx, s, ws, wav, spec, B, L));
+    return run_walks(ctx, __func__, wsp, ws_bytes, 1, [&](Ws& ws) { return run_stft(ctx, s, ws, wav, spec, B, L); });
 }
 
 int64_t tvc_resample_out_len(int64_t n, int orig_freq, int new_freq) { return resample_out_len(n, orig_freq, new_freq); }
@@ -338,7 +347,7 @@ int tvc_energy_f32(tvc_ctx* ctx, void* stream, const float* wav, float* energy, 
     if (!wav || !energy || B <= 0 || L < 128) return fail(ctx, TVC_ERR_ARG, "tvc_energy_f32: bad argument");
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    TVC_RUN(run_energy(ctx, s, ws, wav, energy, B, L));
+    return run_walks(ctx, __func__, wsp, ws_bytes, 1, [&](Ws& ws) { return run_energy(ctx, s, ws, wav, energy, B, L); });
 }
 
 int tvc_encoder_f32(tvc_ctx* ctx, void* stream, const float* spec, float* ssl, float* f0, float* logits, int B, int T, void* wsp, size_t ws_bytes) {
@@ -346,7 +355,7 @@ int tvc_encoder_f32(tvc_ctx* ctx, void* stream, const float* spec, float* ssl, f
     if (!spec || !ssl || !f0 || B <= 0 || T <= 0) return fail(ctx, TVC_ERR_ARG, "tvc_encoder_f32: bad argument");
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    TVC_RUN(run_encoder(ctx, s, ws, spec, ssl, f0, logits, B, T));
+    return run_walks(ctx, __func__, wsp, ws_bytes, 1, [&](Ws& ws) { return run_encoder(ctx, s, ws, spec, ssl, f0, logits, B, T); });
 }
 
 int tvc_pitch_decode_f32(tvc_ctx* ctx, void* stream, const float* logits, float* f0, int B, int T) {
@@ -432,7 +441,7 @@ int tvc_knn_match_f32(tvc_ctx* ctx, void* stream, const float* src, const float*
     TVC_CHECK(blob_check(ctx, (hipStream_t)stream, prepared, N, "tvc_knn_match_f32"));
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    TVC_RUN(run_knn(ctx, s, ws, src, prepared, N, out, idx_out, B, T));
+    return run_walks(ctx, __func__, wsp, ws_bytes, 1, [&](Ws& ws) { return run_knn(ctx, s, ws, src, prepared, N, out, idx_out, B, T); });
 }
 
 int tvc_knn_match_general_f32(tvc_ctx* ctx, void* stream, const float* src, const float* index, int64_t N, int k, int metric, float* out,
@@ -445,7 +454,7 @@ int tvc_knn_match_general_f32(tvc_ctx* ctx, void* stream, const float* src, cons
     if (N > 0x7ffffffe || (long)B * T > 0x7fffffff) return fail(ctx, TVC_ERR_ARG, "tvc_knn_match_general_f32: sizes beyond 32-bit indexing");
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    TVC_RUN(run_knn_general(ctx, s, ws, src, index, N, k, metric, out, idx_out, sim_out, B, T));
+    return run_walks(ctx, __func__, wsp, ws_bytes, 1, [&](Ws& ws) { return run_knn_general(ctx, s, ws, src, index, N, k, metric, out, idx_out, sim_out, B, T); });
 }
 
 int tvc_knn_topk_f32(tvc_ctx* ctx, void* stream, const float* src, const float* prepared, int64_t N, float* sims_out,
@@ -456,7 +465,7 @@ int tvc_knn_topk_f32(tvc_ctx* ctx, void* stream, const float* src, const float* 
     TVC_CHECK(blob_check(ctx, (hipStream_t)stream, prepared, N, "tvc_knn_topk_f32"));
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    TVC_RUN(run_knn_topk(ctx, s, ws, src, prepared, N, sims_out, idx_out, B, T));
+    return run_walks(ctx, __func__, wsp, ws_bytes, 1, [&](Ws& ws) { return run_knn_topk(ctx, s, ws, src, prepared, N, sims_out, idx_out, B, T); });
 }
 
 int tvc_knn_gather_slots_f32(tvc_ctx* ctx, void* stream, const float* prepared, int64_t N, const int64_t* idx, float* slots,
@@ -497,7 +506,7 @@ int tvc_decoder_stages_f32(tvc_ctx* ctx, void* stream, const float* content, con
     if (wave || source) TVC_CHECK(draw_under_capture(ctx, (hipStream_t)stream, noise_angle, "tvc_decoder_f32"));
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    TVC_RUN(run_decoder(ctx, s, ws, content, f0, energy, noise_angle, seed, wave, amps, kernel, source, B, T));
+    return run_walks(ctx, __func__, wsp, ws_bytes, 1, [&](Ws& ws) { return run_decoder(ctx, s, ws, content, f0, energy, noise_angle, seed, wave, amps, kernel, source, B, T); });
 }
 
 int tvc_filter_net_f32(tvc_ctx* ctx, void* stream, const float* content, const float* f0, const float* energy, const float* source,
@@ -509,7 +518,7 @@ int tvc_filter_net_f32(tvc_ctx* ctx, void* stream, const float* content, const f
     FilterTaps taps;
     for (int i = 0; i < 5 && skips; ++i) taps.skips[i] = skips[i];
     for (int i = 0; i < 4 && ups; ++i) taps.ups[i] = ups[i];
-    TVC_RUN(run_filter(ctx, s, ws, content, f0, energy, source, wave, B, T, &taps));
+    return run_walks(ctx, __func__, wsp, ws_bytes, 1, [&](Ws& ws) { return run_filter(ctx, s, ws, content, f0, energy, source, wave, B, T, &taps); });
 }
 
 int tvc_dsp_f32(tvc_ctx* ctx, void* stream, const float* f0, const float* amps, const float* kernel, const float* noise_angle,
@@ -519,7 +528,7 @@ int tvc_dsp_f32(tvc_ctx* ctx, void* stream, const float* f0, const float* amps, 
     TVC_CHECK(draw_under_capture(ctx, (hipStream_t)stream, noise_angle, "tvc_dsp_f32"));
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    TVC_RUN(run_dsp(ctx, s, ws, f0, amps, kernel, noise_angle, seed, source, B, T));
+    return run_walks(ctx, __func__, wsp, ws_bytes, 1, [&](Ws& ws) { return run_dsp(ctx, s, ws, f0, amps, kernel, noise_angle, seed, source, B, T); });
 }
 
 int tvc_decoder_f32(tvc_ctx* ctx, void* stream, const float* content, const float* f0, const float* energy,
@@ -527,71 +536,121 @@ int tvc_decoder_f32(tvc_ctx* ctx, void* stream, const float* content, const floa
     return tvc_decoder_stages_f32(ctx, stream, content, f0, energy, noise_angle, seed, wave, nullptr, nullptr, nullptr, B, T, wsp, ws_bytes);
 }
 
+// ---- conversion: one index or one per row, rows of equal length or ragged --------------------------------------------------------------
+// A table of indices is checked whole before anything is enqueued: every entry non-null, N >= 4, and the blob_check of the single-index calls.
+static int rows_check(tvc_ctx* ctx, hipStream_t s, int B, const float* const* prepared, const int64_t* N, const char* what) {
+    if (!prepared || !N) return fail(ctx, TVC_ERR_ARG, "%s: prepared and N are host arrays of B entries", what);
+    for (int b = 0; b < B; ++b) {
+        if (!prepared[b]) return fail(ctx, TVC_ERR_ARG, "%s: prepared[%d] is NULL", what, b);
+        if (N[b] < 4) return fail(ctx, TVC_ERR_ARG, "%s: N[%d] = %lld: an index needs at least k=4 vectors", what, b, (long long)N[b]);
+    }
+    for (int b = 0; b < B; ++b) TVC_CHECK(blob_check(ctx, s, prepared[b], N[b], what));
+    return 0;
+}
+
+// The four tvc_convert*_f32 entries: the checks under the entry's own name `what`, then the two walks.  ragged: c.lens holds every row's
+// own length and c.L is Lmax; the call runs as the batches of ragged_split and the padded output is cleared once in front of them.
+static int convert_entry(tvc_ctx* ctx, void* stream, const ConvertCall& c, bool ragged, void* wsp, size_t ws_bytes, const char* what) {
+    TVC_CHECK(need_ready(ctx, NEED_ENC | NEED_DEC));
+    hipStream_t s = (hipStream_t)stream;
+    const ConvertIndex& ix = c.index;
+    if (!c.wav || !c.wave || (ragged && !c.lens) || (!ix.per_row && !ix.blob) || c.B <= 0 || c.L <= 0 || c.L % kHop)
+        return fail(ctx, TVC_ERR_ARG, "%s: bad argument (%s must be a positive multiple of 480)", what, ragged ? "Lmax" : "L");
+    if (!ragged && c.L < kNfft / 2 + 1) return fail(ctx, TVC_ERR_ARG, "%s: L must exceed 960 samples (STFT reflect padding, as torch.stft requires)", what);
+    if (ix.per_row) {
+        TVC_CHECK(rows_check(ctx, s, c.B, ix.blobs, ix.Ns, what));
+    } else {
+        if (ix.N < 4) return fail(ctx, TVC_ERR_ARG, "%s: index needs at least k=4 vectors", what);
+        TVC_CHECK(blob_check(ctx, s, ix.blob, ix.N, what));
+    }
+    TVC_CHECK(draw_under_capture(ctx, s, c.angle, what));
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ragged) return run_walks(ctx, what, wsp, ws_bytes, 1, [&](Ws& ws) { return convert_impl(ctx, s, ws, c); });
+    std::vector<RagBatchPlan> batches;
+    TVC_CHECK(ragged_split(ctx, ctx->rag_batch_frames, c.B, c.L, c.lens, &batches));
+    return run_walks(
+        ctx, what, wsp, ws_bytes, kRagGranule, [&](Ws& ws) { return convert_ragged_batches(ctx, s, ws, batches, c); },      // (the measuring walk is host time on the launch path)
+        [&] {      // the whole padded output is cleared once: every kernel writes its utterance's own samples only
+            TVC_HIP(ctx, hipMemsetAsync(c.wave, 0, (size_t)c.B * c.L * sizeof(float), s));
+            return 0;
+        });
+}
+
+// The tvc_workspace_bytes* query that goes with each of them: the same description with stand-in buffers, the measuring walk alone.  A
+// per-row index (ix.Ns; ix.blobs is not looked at) is planned with every row a segment of its own (distinct stand-in blobs) and a shift
+// table (it takes workspace; never read in this walk): a call whose rows share blobs, or without per-row shifts, needs less.
+// (No allocation depends on whether the call brings its own noise phases.)
+static int convert_query(tvc_ctx* ctx, int B, int64_t L, const int64_t* lens, bool ragged, const ConvertIndex& ix, size_t* out_bytes, const char* what) {
+    TVC_CHECK(need_ready(ctx, NEED_NONE));
+    if (!out_bytes || (ragged && !lens) || (ix.per_row ? !ix.Ns : ix.N < 4) || B <= 0 || L <= 0 || L % kHop != 0)
+        return fail(ctx, TVC_ERR_ARG, "%s: need B>0, %s%%480==0, %s%s", what, ragged ? "Lmax" : "L", ragged && ix.per_row ? "lens[B], " : "", ix.per_row ? "N[B]" : "N>=4");
+    for (int b = 0; ix.per_row && b < B; ++b)
+        if (ix.Ns[b] < 4) return fail(ctx, TVC_ERR_ARG, "%s: N[%d] < 4", what, b);
+    std::vector<const float*> blobs(ix.per_row ? (size_t)B : 0);
+    for (size_t b = 0; b < blobs.size(); ++b) blobs[b] = kDryPtr + 64 * b;
+    const float shift = 0.f;
+    ConvertCall c;
+    c.wav = c.wave = kDryPtr;
+    c.B = B;
+    c.L = L;
+    c.lens = lens;
+    c.index = ix.per_row ? ConvertIndex::table(blobs.data(), ix.Ns) : ConvertIndex::one(kDryPtr, ix.N);
+    c.shifts = ix.per_row ? &shift : nullptr;
+    if (!ragged) return measure(1, out_bytes, [&](Ws& ws) { return convert_impl(ctx, nullptr, ws, c); });
+    std::vector<RagBatchPlan> batches;
+    TVC_CHECK(ragged_split(ctx, ctx->rag_batch_frames, B, L, lens, &batches));
+    return measure(kRagGranule, out_bytes, [&](Ws& ws) { return convert_ragged_batches(ctx, nullptr, ws, batches, c); });
+}
+
+int tvc_workspace_bytes(tvc_ctx* ctx, int B, int64_t L, int64_t N, size_t* out_bytes) {
+    return convert_query(ctx, B, L, nullptr, false, ConvertIndex::one(nullptr, N), out_bytes, "tvc_workspace_bytes");
+}
+int tvc_workspace_bytes_ragged(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, int64_t N, size_t* out_bytes) {
+    return convert_query(ctx, B, Lmax, lens, true, ConvertIndex::one(nullptr, N), out_bytes, "tvc_workspace_bytes_ragged");
+}
+int tvc_workspace_bytes_multi(tvc_ctx* ctx, int B, int64_t L, const int64_t* N, size_t* out_bytes) {
+    return convert_query(ctx, B, L, nullptr, false, ConvertIndex::table(nullptr, N), out_bytes, "tvc_workspace_bytes_multi");
+}
+int tvc_workspace_bytes_ragged_multi(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, const int64_t* N, size_t* out_bytes) {
+    return convert_query(ctx, B, Lmax, lens, true, ConvertIndex::table(nullptr, N), out_bytes, "tvc_workspace_bytes_ragged_multi");
+}
+
 int tvc_convert_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* prepared, int64_t N,
                     float pitch_shift, const float* noise_angle, uint64_t seed, float* wave, int B, int64_t L,
                     void* wsp, size_t ws_bytes) {
-    TVC_CHECK(need_ready(ctx, NEED_ENC | NEED_DEC));
-    if (!wav || !prepared || !wave || B <= 0 || L <= 0 || L % kHop) return fail(ctx, TVC_ERR_ARG, "tvc_convert_f32: bad argument (L must be a positive multiple of 480)");
-    if (L < kNfft / 2 + 1) return fail(ctx, TVC_ERR_ARG, "tvc_convert_f32: L must exceed 960 samples (STFT reflect padding, as torch.stft requires)");
-    if (N < 4) return fail(ctx, TVC_ERR_ARG, "tvc_convert_f32: index needs at least k=4 vectors");
-    TVC_CHECK(blob_check(ctx, (hipStream_t)stream, prepared, N, "tvc_convert_f32"));
-    TVC_CHECK(draw_under_capture(ctx, (hipStream_t)stream, noise_angle, "tvc_convert_f32"));
-    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    const ConvertCall c{wav, wave, B, L, nullptr, ConvertIndex::one(prepared, N), pitch_shift, nullptr, noise_angle, seed};
+    return convert_entry(ctx, stream, c, false, wsp, ws_bytes, "tvc_convert_f32");
+}
+int tvc_convert_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens, const float* prepared, int64_t N,
+                           float pitch_shift, const float* noise_angle, uint64_t seed, float* wave, int B, void* wsp, size_t ws_bytes) {
+    const ConvertCall c{wav, wave, B, Lmax, lens, ConvertIndex::one(prepared, N), pitch_shift, nullptr, noise_angle, seed};
+    return convert_entry(ctx, stream, c, true, wsp, ws_bytes, "tvc_convert_ragged_f32");
+}
+int tvc_convert_multi_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, float pitch_shift,
+                          const float* pitch_shifts, const float* noise_angle, uint64_t seed, float* wave, int B, int64_t L, void* wsp, size_t ws_bytes) {
+    const ConvertCall c{wav, wave, B, L, nullptr, ConvertIndex::table(prepared, N), pitch_shift, pitch_shifts, noise_angle, seed};
+    return convert_entry(ctx, stream, c, false, wsp, ws_bytes, "tvc_convert_multi_f32");
+}
+int tvc_convert_ragged_multi_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens, const float* const* prepared,
+                                 const int64_t* N, float pitch_shift, const float* pitch_shifts, const float* noise_angle, uint64_t seed, float* wave,
+                                 int B, void* wsp, size_t ws_bytes) {
+    const ConvertCall c{wav, wave, B, Lmax, lens, ConvertIndex::table(prepared, N), pitch_shift, pitch_shifts, noise_angle, seed};
+    return convert_entry(ctx, stream, c, true, wsp, ws_bytes, "tvc_convert_ragged_multi_f32");
+}
+
+int tvc_knn_match_multi_f32(tvc_ctx* ctx, void* stream, const float* src, const float* const* prepared, const int64_t* N, float* out,
+                            int64_t* idx_out, int B, int T, void* wsp, size_t ws_bytes) {
+    if (!ctx) return TVC_ERR_ARG;
+    if (!src || !out || B <= 0 || T <= 0 || (int64_t)B * T > 0x7fffffff) return fail(ctx, TVC_ERR_ARG, "tvc_knn_match_multi_f32: bad argument");
     hipStream_t s = (hipStream_t)stream;
-    TVC_RUN(convert_impl(ctx, s, ws, wav, prepared, N, pitch_shift, noise_angle, seed, wave, B, L));
+    TVC_CHECK(rows_check(ctx, s, B, prepared, N, "tvc_knn_match_multi_f32"));
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<KnnSegIn> in((size_t)B);
+    for (int b = 0; b < B; ++b) in[b] = KnnSegIn{prepared[b], N[b], b * T, T};
+    return run_walks(ctx, __func__, wsp, ws_bytes, 1, [&](Ws& ws) { return run_knn_segs(ctx, s, ws, src, in.data(), B, out, idx_out, B, T); });
 }
 
-// ---- ragged batches ---------------------------------------------------------------------------------------------------------
-namespace {
-// Every utterance of a ragged call is converted inside the kernels (ragged.h), in batches of utterances that select the SAME kernels: which
-// FiLM kernel a FilterNet level runs depends on the utterance's own length there (film_s2 / the pre-split hand-over need one 256-column tile:
-// 2 T, 6 T, 24 T >= 256, decoder.hip film_conv), so the frame counts split into four classes at 11, 43 and 128 frames; inside a class every
-// utterance takes exactly the path its own B = 1 call takes and the result is bit-identical to it.
-constexpr int kRagClassBounds[3] = {11, 43, 128};
-constexpr int kRagMaxFrames = 80000;       // frames per in-kernel batch: 24 rows x 480 x 4 B x frames stays below the 32-bit byte offsets of the 24-channel kernels
-struct RagBatchPlan {
-    std::vector<int> rows, frames;
-    int Ttot = 0;
-};
-int ragged_split(tvc_ctx* ctx, int cap, int B, int64_t Lmax, const int64_t* lens, std::vector<RagBatchPlan>* batches, bool classes = true) {
-    std::vector<RagBatchPlan> open(4);          // the batch being filled, per class (cap: tvc_ctx_set_ragged_batch_frames / tvc_ragged_plan's argument, 0 = the default)
-    const int max_frames = cap > 0 && cap < kRagMaxFrames ? cap : kRagMaxFrames;
-    for (int b = 0; b < B; ++b) {
-        if (lens[b] <= 0 || lens[b] % kHop || lens[b] > Lmax || lens[b] < kNfft / 2 + 1)
-            return fail(ctx, TVC_ERR_ARG, "ragged batch: lens[%d] = %lld must be a multiple of 480 in (960, Lmax]", b, (long long)lens[b]);
-        const int T = (int)(lens[b] / kHop);
-        if (T > kRagMaxFrames) return fail(ctx, TVC_ERR_ARG, "ragged batch: lens[%d] = %lld is longer than a batch may be; convert it with tvc_convert_f32", b, (long long)lens[b]);
-        const int cls = classes ? (T >= kRagClassBounds[0]) + (T >= kRagClassBounds[1]) + (T >= kRagClassBounds[2]) : 0;      // (the encoder's kernels make no length-dependent choice: one class)
-        RagBatchPlan& p = open[cls];
-        if (p.Ttot + T > max_frames && !p.rows.empty()) {
-            batches->push_back(p);
-            p = RagBatchPlan();
-        }
-        p.rows.push_back(b);
-        p.frames.push_back(T);
-        p.Ttot += T;
-    }
-    for (int c = 3; c >= 0; --c)
-        if (!open[c].rows.empty()) batches->push_back(open[c]);
-    return 0;
-}
-// the batches of a call, one after the other on the caller's stream, each from the start of the same workspace region: [tables][convert
-// workspace].  The drivers run a batch as ONE utterance of Ttot frames (B = 1) with ctx->rag set.
-int ragged_batches(tvc_ctx* ctx, hipStream_t s, Ws& ws, const std::vector<RagBatchPlan>& batches, const float* wav, int64_t Lmax, const float* prepared,
-                   int64_t N, float pitch_shift, const float* angle, uint64_t seed, float* wave, const RowIndex* rows = nullptr) {
-    for (auto& p : batches) {
-        ws.release(0);
-        RagHost h;
-        TVC_CHECK(rag_setup(ctx, s, ws, h, p.frames, p.rows, (int)(Lmax / kHop)));
-        ctx->rag = &h;
-        const int rc = convert_impl(ctx, s, ws, wav, prepared, N, pitch_shift, angle, seed, wave, 1, (int64_t)p.Ttot * kHop, rows);
-        ctx->rag = nullptr;
-        TVC_CHECK(rc);
-    }
-    return 0;
-}
-}  // namespace
-
+// ---- ragged batches: the plan (ragged.hip) as callers see it, and the ragged encode ----------------------------------------------------
 int tvc_ctx_set_ragged_batch_frames(tvc_ctx* ctx, int max_frames) {
     if (!ctx) return TVC_ERR_ARG;
     if (max_frames < 0) return fail(ctx, TVC_ERR_ARG, "tvc_ctx_set_ragged_batch_frames: the cap is a frame count (0 = the default)");
@@ -609,106 +668,6 @@ int tvc_ragged_plan(int B, int64_t Lmax, const int64_t* lens, int max_frames, in
     return TVC_OK;
 }
 
-int tvc_workspace_bytes_ragged(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, int64_t N, size_t* out_bytes) {
-    TVC_CHECK(need_ready(ctx, NEED_NONE));
-    if (!out_bytes || !lens || B <= 0 || Lmax <= 0 || Lmax % kHop != 0 || N < 4) return fail(ctx, TVC_ERR_ARG, "tvc_workspace_bytes_ragged: need B>0, Lmax%%480==0, N>=4");
-    std::vector<RagBatchPlan> batches;
-    TVC_CHECK(ragged_split(ctx, ctx->rag_batch_frames, B, Lmax, lens, &batches));
-    Ws ws(nullptr, 0, true);      // (no allocation depends on whether the call brings its own noise phases)
-    TVC_CHECK(ragged_batches(ctx, nullptr, ws, batches, kDryPtr, Lmax, kDryPtr, N, 0.f, nullptr, 0, kDryPtr));
-    *out_bytes = ((ws.peak + 4095) & ~size_t(4095)) + 4096;
-    return TVC_OK;
-}
-
-int tvc_convert_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens, const float* prepared, int64_t N,
-                           float pitch_shift, const float* noise_angle, uint64_t seed, float* wave, int B, void* wsp, size_t ws_bytes) {
-    TVC_CHECK(need_ready(ctx, NEED_ENC | NEED_DEC));
-    if (!wav || !lens || !prepared || !wave || B <= 0 || Lmax <= 0 || Lmax % kHop) return fail(ctx, TVC_ERR_ARG, "tvc_convert_ragged_f32: bad argument (Lmax must be a positive multiple of 480)");
-    if (N < 4) return fail(ctx, TVC_ERR_ARG, "tvc_convert_ragged_f32: index needs at least k=4 vectors");
-    TVC_CHECK(blob_check(ctx, (hipStream_t)stream, prepared, N, "tvc_convert_ragged_f32"));
-    TVC_CHECK(draw_under_capture(ctx, (hipStream_t)stream, noise_angle, "tvc_convert_ragged_f32"));
-    TVC_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<RagBatchPlan> batches;
-    TVC_CHECK(ragged_split(ctx, ctx->rag_batch_frames, B, Lmax, lens, &batches));
-    Ws need(nullptr, 0, true);
-    TVC_CHECK(ragged_batches(ctx, s, need, batches, wav, Lmax, prepared, N, pitch_shift, noise_angle, seed, wave));      // host time on the launch path
-    const size_t bytes = (need.peak + 4095) & ~size_t(4095);      // (whole 4 KiB pages, as tvc_workspace_bytes_ragged promises)
-    if (bytes > ws_bytes) return fail(ctx, TVC_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", bytes, ws_bytes);
-    // the whole padded output is cleared once: every kernel writes its utterance's own samples only
-    TVC_HIP(ctx, hipMemsetAsync(wave, 0, (size_t)B * Lmax * sizeof(float), s));
-    Ws ws(wsp, bytes, false);
-    TVC_CHECK(ragged_batches(ctx, s, ws, batches, wav, Lmax, prepared, N, pitch_shift, noise_angle, seed, wave));
-    return walks_agree(ctx, __func__, ws.peak, need.peak);
-}
-
-// ---- ragged encode ----------------------------------------------------------------------------------------------------------------
-// Generator.encode (generator.py:19-23) over utterances of different lengths, as extract_index.py:47-52 needs it for a folder of clips:
-// rag_setup, |STFT|, encoder with ctx->rag set - the first half of convert_impl, no index, no decoder.  The spectrogram's |max| slot is
-// the measured per-utterance maximum (run_encoder without a bound: run_amax_rows), as in the stage calls tvc_stft_mag_f32 + tvc_encoder_f32
-// that Generator.encode makes for one utterance: utterance b's columns are bit-identical to those calls at B = 1.  The length classes of
-// ragged_split exist for FilterNet's FiLM kernels; the encoder's kernels choose nothing by an utterance's length, so a call is cut by the
-// frame cap alone and its batches are runs of consecutive rows.
-namespace {
-// packed[c][gpre[row of b] + t'] = batch[c][pre[b] + t'] (c = 768: the f0 row): a later batch's columns into the call's packed outputs
-__global__ __launch_bounds__(256) void pack_batch_kernel(const float* __restrict__ ssl_b, const float* __restrict__ f0_b, float* __restrict__ ssl,
-                                                         float* __restrict__ f0, RagDev rg, const int* __restrict__ gpre, int Ttot, long S) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= Ttot) return;
-    const int b = rg.col2b[t];
-    const long dst = (long)gpre[rg.row[b]] + (t - rg.pre[b]);
-    const int c = blockIdx.y;
-    if (c < kSslDim) ssl[(long)c * S + dst] = ssl_b[(long)c * Ttot + t];
-    else f0[dst] = f0_b[t];
-}
-int encode_ragged_batches(tvc_ctx* ctx, hipStream_t s, Ws& ws, const std::vector<RagBatchPlan>& batches, const std::vector<int>& gpre, const float* wav,
-                          int64_t Lmax, float* ssl, float* f0, int64_t S) {
-    ws.release(0);
-    const bool direct = batches.size() == 1;      // one batch holds every row in the caller's order: its layout IS the packed one (row stride S)
-    int* d_gpre = nullptr;
-    if (!direct) {
-        d_gpre = ws.get<int>(gpre.size());
-        if (!ws.dry) TVC_CHECK(upload_ints(ctx, s, gpre, d_gpre));
-    }
-    const size_t m0 = ws.mark();
-    for (auto& p : batches) {
-        ws.release(m0);
-        RagHost h;
-        TVC_CHECK(rag_setup(ctx, s, ws, h, p.frames, p.rows, (int)(Lmax / kHop)));
-        float* spec = ws.get<float>((size_t)kBins * p.Ttot);
-        float* ssl_b = direct ? ssl : ws.get<float>((size_t)kSslDim * p.Ttot);
-        float* f0_b = direct ? f0 : ws.get<float>((size_t)p.Ttot);
-        ctx->rag = &h;
-        int rc = run_stft(ctx, s, ws, wav, spec, 1, (int64_t)p.Ttot * kHop);
-        if (!rc) rc = run_encoder(ctx, s, ws, spec, ssl_b, f0_b, nullptr, 1, p.Ttot);
-        if (!rc && !direct && !ws.dry) {
-            RagDev rg;
-            rc = rag_view(ctx, s, 1, 0, &rg, nullptr);
-            if (!rc) {
-                hipLaunchKernelGGL(pack_batch_kernel, dim3((unsigned)((p.Ttot + 255) / 256), kSslDim + 1), dim3(256), 0, s, ssl_b, f0_b, ssl, f0, rg, d_gpre, p.Ttot, (long)S);
-                rc = launch_check(ctx, "encode_ragged pack");
-            }
-        }
-        ctx->rag = nullptr;
-        TVC_CHECK(rc);
-    }
-    return 0;
-}
-// the call's plan: its batches, the packed column of every row's first frame, S
-int encode_ragged_plan(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, std::vector<RagBatchPlan>* batches, std::vector<int>* gpre, int64_t* S) {
-    TVC_CHECK(ragged_split(ctx, ctx->rag_batch_frames, B, Lmax, lens, batches, false));
-    gpre->assign((size_t)B, 0);
-    int64_t tot = 0;
-    for (int b = 0; b < B; ++b) {
-        (*gpre)[b] = (int)tot;
-        tot += lens[b] / kHop;
-        if (tot > 0x7fffffff) return fail(ctx, TVC_ERR_ARG, "ragged encode: more than 2^31 - 1 frames in one call");
-    }
-    *S = tot;
-    return 0;
-}
-}  // namespace
-
 int tvc_workspace_bytes_encode_ragged(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, size_t* out_bytes) {
     TVC_CHECK(need_ready(ctx, NEED_NONE));
     if (!out_bytes || !lens || B <= 0 || Lmax <= 0 || Lmax % kHop != 0) return fail(ctx, TVC_ERR_ARG, "tvc_workspace_bytes_encode_ragged: need B>0, Lmax%%480==0, lens[B]");
@@ -716,10 +675,7 @@ int tvc_workspace_bytes_encode_ragged(tvc_ctx* ctx, int B, int64_t Lmax, const i
     std::vector<int> gpre;
     int64_t S = 0;
     TVC_CHECK(encode_ragged_plan(ctx, B, Lmax, lens, &batches, &gpre, &S));
-    Ws ws(nullptr, 0, true);
-    TVC_CHECK(encode_ragged_batches(ctx, nullptr, ws, batches, gpre, kDryPtr, Lmax, kDryPtr, kDryPtr, S));
-    *out_bytes = ((ws.peak + 4095) & ~size_t(4095)) + 4096;
-    return TVC_OK;
+    return measure(kRagGranule, out_bytes, [&](Ws& ws) { return encode_ragged_batches(ctx, nullptr, ws, batches, gpre, kDryPtr, Lmax, kDryPtr, kDryPtr, S); });
 }
 
 int tvc_encode_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens, float* ssl, float* f0, int B, void* wsp,
@@ -732,110 +688,7 @@ int tvc_encode_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t 
     std::vector<int> gpre;
     int64_t S = 0;
     TVC_CHECK(encode_ragged_plan(ctx, B, Lmax, lens, &batches, &gpre, &S));
-    Ws need(nullptr, 0, true);
-    TVC_CHECK(encode_ragged_batches(ctx, s, need, batches, gpre, wav, Lmax, ssl, f0, S));
-    const size_t bytes = (need.peak + 4095) & ~size_t(4095);
-    if (bytes > ws_bytes) return fail(ctx, TVC_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", bytes, ws_bytes);
-    Ws ws(wsp, bytes, false);
-    TVC_CHECK(encode_ragged_batches(ctx, s, ws, batches, gpre, wav, Lmax, ssl, f0, S));
-    return walks_agree(ctx, __func__, ws.peak, need.peak);
-}
-
-// ---- one prepared index per row ------------------------------------------------------------------------------------------------
-// The table is checked whole before anything is enqueued: every entry non-null, N >= 4, and the blob_check of the single-index calls.
-static int rows_check(tvc_ctx* ctx, hipStream_t s, int B, const float* const* prepared, const int64_t* N, const char* what) {
-    if (!prepared || !N) return fail(ctx, TVC_ERR_ARG, "%s: prepared and N are host arrays of B entries", what);
-    for (int b = 0; b < B; ++b) {
-        if (!prepared[b]) return fail(ctx, TVC_ERR_ARG, "%s: prepared[%d] is NULL", what, b);
-        if (N[b] < 4) return fail(ctx, TVC_ERR_ARG, "%s: N[%d] = %lld: an index needs at least k=4 vectors", what, b, (long long)N[b]);
-    }
-    for (int b = 0; b < B; ++b) TVC_CHECK(blob_check(ctx, s, prepared[b], N[b], what));
-    return 0;
-}
-// the workspace queries plan every row as a segment of its own (distinct stand-in blobs): a call whose rows share blobs needs less
-static std::vector<const float*> dry_blobs(int B) {
-    std::vector<const float*> v((size_t)B);
-    for (int b = 0; b < B; ++b) v[b] = kDryPtr + 64 * (size_t)b;
-    return v;
-}
-
-int tvc_knn_match_multi_f32(tvc_ctx* ctx, void* stream, const float* src, const float* const* prepared, const int64_t* N, float* out,
-                            int64_t* idx_out, int B, int T, void* wsp, size_t ws_bytes) {
-    if (!ctx) return TVC_ERR_ARG;
-    if (!src || !out || B <= 0 || T <= 0 || (int64_t)B * T > 0x7fffffff) return fail(ctx, TVC_ERR_ARG, "tvc_knn_match_multi_f32: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    TVC_CHECK(rows_check(ctx, s, B, prepared, N, "tvc_knn_match_multi_f32"));
-    TVC_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<KnnSegIn> in((size_t)B);
-    for (int b = 0; b < B; ++b) in[b] = KnnSegIn{prepared[b], N[b], b * T, T};
-    TVC_RUN(run_knn_segs(ctx, s, ws, src, in.data(), B, out, idx_out, B, T));
-}
-
-int tvc_workspace_bytes_multi(tvc_ctx* ctx, int B, int64_t L, const int64_t* N, size_t* out_bytes) {
-    TVC_CHECK(need_ready(ctx, NEED_NONE));
-    if (!out_bytes || !N || B <= 0 || L <= 0 || L % kHop != 0) return fail(ctx, TVC_ERR_ARG, "tvc_workspace_bytes_multi: need B>0, L%%480==0, N[B]");
-    for (int b = 0; b < B; ++b)
-        if (N[b] < 4) return fail(ctx, TVC_ERR_ARG, "tvc_workspace_bytes_multi: N[%d] < 4", b);
-    const std::vector<const float*> blobs = dry_blobs(B);
-    const float shift = 0.f;
-    const RowIndex rows{blobs.data(), N, &shift};      // (a shift table takes workspace: counted; never read in this walk)
-    Ws ws(nullptr, 0, true);
-    TVC_CHECK(convert_impl(ctx, nullptr, ws, kDryPtr, kDryPtr, N[0], 0.f, nullptr, 0, kDryPtr, B, L, &rows));
-    *out_bytes = ws.peak + 4096;
-    return TVC_OK;
-}
-
-int tvc_convert_multi_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, float pitch_shift,
-                          const float* pitch_shifts, const float* noise_angle, uint64_t seed, float* wave, int B, int64_t L, void* wsp, size_t ws_bytes) {
-    TVC_CHECK(need_ready(ctx, NEED_ENC | NEED_DEC));
-    if (!wav || !wave || B <= 0 || L <= 0 || L % kHop) return fail(ctx, TVC_ERR_ARG, "tvc_convert_multi_f32: bad argument (L must be a positive multiple of 480)");
-    if (L < kNfft / 2 + 1) return fail(ctx, TVC_ERR_ARG, "tvc_convert_multi_f32: L must exceed 960 samples (STFT reflect padding, as torch.stft requires)");
-    hipStream_t s = (hipStream_t)stream;
-    TVC_CHECK(rows_check(ctx, s, B, prepared, N, "tvc_convert_multi_f32"));
-    TVC_CHECK(draw_under_capture(ctx, s, noise_angle, "tvc_convert_multi_f32"));
-    TVC_HIP(ctx, hipSetDevice(ctx->device));
-    const RowIndex rows{prepared, N, pitch_shifts};
-    TVC_RUN(convert_impl(ctx, s, ws, wav, prepared[0], N[0], pitch_shift, noise_angle, seed, wave, B, L, &rows));
-}
-
-int tvc_workspace_bytes_ragged_multi(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, const int64_t* N, size_t* out_bytes) {
-    TVC_CHECK(need_ready(ctx, NEED_NONE));
-    if (!out_bytes || !lens || !N || B <= 0 || Lmax <= 0 || Lmax % kHop != 0)
-        return fail(ctx, TVC_ERR_ARG, "tvc_workspace_bytes_ragged_multi: need B>0, Lmax%%480==0, lens[B], N[B]");
-    for (int b = 0; b < B; ++b)
-        if (N[b] < 4) return fail(ctx, TVC_ERR_ARG, "tvc_workspace_bytes_ragged_multi: N[%d] < 4", b);
-    std::vector<RagBatchPlan> batches;
-    TVC_CHECK(ragged_split(ctx, ctx->rag_batch_frames, B, Lmax, lens, &batches));
-    const std::vector<const float*> blobs = dry_blobs(B);
-    const float shift = 0.f;
-    const RowIndex rows{blobs.data(), N, &shift};
-    Ws ws(nullptr, 0, true);
-    TVC_CHECK(ragged_batches(ctx, nullptr, ws, batches, kDryPtr, Lmax, kDryPtr, N[0], 0.f, nullptr, 0, kDryPtr, &rows));
-    *out_bytes = ((ws.peak + 4095) & ~size_t(4095)) + 4096;
-    return TVC_OK;
-}
-
-int tvc_convert_ragged_multi_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens, const float* const* prepared,
-                                 const int64_t* N, float pitch_shift, const float* pitch_shifts, const float* noise_angle, uint64_t seed, float* wave,
-                                 int B, void* wsp, size_t ws_bytes) {
-    TVC_CHECK(need_ready(ctx, NEED_ENC | NEED_DEC));
-    if (!wav || !lens || !wave || B <= 0 || Lmax <= 0 || Lmax % kHop)
-        return fail(ctx, TVC_ERR_ARG, "tvc_convert_ragged_multi_f32: bad argument (Lmax must be a positive multiple of 480)");
-    hipStream_t s = (hipStream_t)stream;
-    TVC_CHECK(rows_check(ctx, s, B, prepared, N, "tvc_convert_ragged_multi_f32"));
-    TVC_CHECK(draw_under_capture(ctx, s, noise_angle, "tvc_convert_ragged_multi_f32"));
-    TVC_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<RagBatchPlan> batches;
-    TVC_CHECK(ragged_split(ctx, ctx->rag_batch_frames, B, Lmax, lens, &batches));
-    const RowIndex rows{prepared, N, pitch_shifts};
-    Ws need(nullptr, 0, true);
-    TVC_CHECK(ragged_batches(ctx, s, need, batches, wav, Lmax, prepared[0], N[0], pitch_shift, noise_angle, seed, wave, &rows));
-    const size_t bytes = (need.peak + 4095) & ~size_t(4095);
-    if (bytes > ws_bytes) return fail(ctx, TVC_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", bytes, ws_bytes);
-    TVC_HIP(ctx, hipMemsetAsync(wave, 0, (size_t)B * Lmax * sizeof(float), s));
-    Ws ws(wsp, bytes, false);
-    TVC_CHECK(ragged_batches(ctx, s, ws, batches, wav, Lmax, prepared[0], N[0], pitch_shift, noise_angle, seed, wave, &rows));
-    return walks_agree(ctx, __func__, ws.peak, need.peak);
+    return run_walks(ctx, __func__, wsp, ws_bytes, kRagGranule, [&](Ws& ws) { return encode_ragged_batches(ctx, s, ws, batches, gpre, wav, Lmax, ssl, f0, S); });
 }
 
 // ---- compacting an index: k-means over a prepared blob (index_compact.hip) -------------------------------------------------------
@@ -857,10 +710,7 @@ int tvc_workspace_bytes_index_compact(tvc_ctx* ctx, int64_t N, int64_t K, size_t
     if (!ctx) return TVC_ERR_ARG;
     if (!out_bytes) return fail(ctx, TVC_ERR_ARG, "tvc_workspace_bytes_index_compact: out_bytes is NULL");
     TVC_CHECK(compact_check(ctx, N, K, "tvc_workspace_bytes_index_compact"));
-    Ws ws(nullptr, 0, true);
-    TVC_CHECK(run_index_compact(ctx, nullptr, ws, kDryPtr, N, nullptr, K, 1, kDryPtr, kDryPtr, nullptr, nullptr, nullptr));
-    *out_bytes = ws.peak + 4096;
-    return TVC_OK;
+    return measure(1, out_bytes, [&](Ws& ws) { return run_index_compact(ctx, nullptr, ws, kDryPtr, N, nullptr, K, 1, kDryPtr, kDryPtr, nullptr, nullptr, nullptr); });
 }
 
 int tvc_index_assign_f32(tvc_ctx* ctx, void* stream, const float* points_prepared, int64_t N, const float* centroids_prepared, int64_t K,
@@ -872,7 +722,7 @@ int tvc_index_assign_f32(tvc_ctx* ctx, void* stream, const float* points_prepare
     TVC_CHECK(blob_check(ctx, s, points_prepared, N, "tvc_index_assign_f32 (points)"));
     TVC_CHECK(blob_check(ctx, s, centroids_prepared, K, "tvc_index_assign_f32 (centroids)"));
     TVC_HIP(ctx, hipSetDevice(ctx->device));
-    TVC_RUN(run_index_assign(ctx, s, ws, points_prepared, N, centroids_prepared, K, assign_inout, sim_out, moved_out));
+    return run_walks(ctx, __func__, wsp, ws_bytes, 1, [&](Ws& ws) { return run_index_assign(ctx, s, ws, points_prepared, N, centroids_prepared, K, assign_inout, sim_out, moved_out); });
 }
 
 int tvc_index_update_f32(tvc_ctx* ctx, void* stream, const float* points_prepared, int64_t N, const int64_t* assign, int64_t K, float* centroids_inout,
@@ -883,7 +733,7 @@ int tvc_index_update_f32(tvc_ctx* ctx, void* stream, const float* points_prepare
     hipStream_t s = (hipStream_t)stream;
     TVC_CHECK(blob_check(ctx, s, points_prepared, N, "tvc_index_update_f32"));
     TVC_HIP(ctx, hipSetDevice(ctx->device));
-    TVC_RUN(run_index_update(ctx, s, ws, points_prepared, N, assign, K, centroids_inout, counts_out));
+    return run_walks(ctx, __func__, wsp, ws_bytes, 1, [&](Ws& ws) { return run_index_update(ctx, s, ws, points_prepared, N, assign, K, centroids_inout, counts_out); });
 }
 
 int tvc_index_compact_f32(tvc_ctx* ctx, void* stream, const float* points_prepared, int64_t N, const int64_t* init_cols, int64_t K, int iters,
@@ -895,14 +745,9 @@ int tvc_index_compact_f32(tvc_ctx* ctx, void* stream, const float* points_prepar
     TVC_CHECK(blob_check(ctx, s, points_prepared, N, "tvc_index_compact_f32"));
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     blob_forget(prepared_out);
-    {
-        Ws need(nullptr, 0, true);
-        TVC_CHECK(run_index_compact(ctx, s, need, points_prepared, N, init_cols, K, iters, centroids_out, prepared_out, assign_out, counts_out, moved_out));
-        if (need.peak > ws_bytes) return fail(ctx, TVC_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need.peak, ws_bytes);
-        Ws ws(wsp, ws_bytes, false);
-        TVC_CHECK(run_index_compact(ctx, s, ws, points_prepared, N, init_cols, K, iters, centroids_out, prepared_out, assign_out, counts_out, moved_out));
-        TVC_CHECK(walks_agree(ctx, __func__, ws.peak, need.peak));
-    }
+    TVC_CHECK(run_walks(ctx, __func__, wsp, ws_bytes, 1, [&](Ws& ws) {
+        return run_index_compact(ctx, s, ws, points_prepared, N, init_cols, K, iters, centroids_out, prepared_out, assign_out, counts_out, moved_out);
+    }));
     blob_record(prepared_out, K);
     return TVC_OK;
 }

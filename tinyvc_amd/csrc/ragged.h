@@ -13,6 +13,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <vector>
 
 struct tvc_ctx;
@@ -20,6 +21,7 @@ struct tvc_ctx;
 namespace tvc {
 
 struct Ws;
+struct ConvertCall;               // tvc_common.h
 
 struct RagDev {                   // device view handed to a kernel (tb == nullptr: equal lengths, the kernel's ordinary path)
     const int* tb = nullptr;      // [B] frames of utterance b
@@ -66,8 +68,37 @@ int rag_view(tvc_ctx* ctx, hipStream_t s, int mult, int bn, RagDev* out, int* nt
 int rag_tiles(tvc_ctx* ctx, hipStream_t s, int B, long len, int bn, RagDev* out, int* ntiles, const char* what, int mult = 0);
 
 // Shape-dependent kernel choices (decoder.hip: film_s2 needs one 256-column tile per utterance) look at the SHORTEST utterance of a ragged batch:
-// a batch only holds utterances that make the same choices (api.hip ragged_split), so this is every member's own decision.
+// a batch only holds utterances that make the same choices (ragged_split), so this is every member's own decision.
 int rag_min_len(const tvc_ctx* ctx, int len);
+
+// ---- the batches of a call ----------------------------------------------------------------------------------------------------
+// Every utterance of a ragged call is converted inside the kernels, in batches of utterances that select the SAME kernels: which
+// FiLM kernel a FilterNet level runs depends on the utterance's own length there (film_s2 / the pre-split hand-over need one 256-column tile:
+// 2 T, 6 T, 24 T >= 256, decoder.hip film_conv), so the frame counts split into four classes at 11, 43 and 128 frames; inside a class every
+// utterance takes exactly the path its own B = 1 call takes and the result is bit-identical to it.
+constexpr int kRagClassBounds[3] = {11, 43, 128};
+constexpr int kRagMaxFrames = 80000;       // frames per in-kernel batch: 24 rows x 480 x 4 B x frames stays below the 32-bit byte offsets of the 24-channel kernels
+struct RagBatchPlan {
+    std::vector<int> rows, frames;
+    int Ttot = 0;
+};
+// cap: tvc_ctx_set_ragged_batch_frames / tvc_ragged_plan's argument, 0 = the default; classes = false: one class, cut by the cap alone
+// (ctx may be nullptr: a refusal then has no message)
+int ragged_split(tvc_ctx* ctx, int cap, int B, int64_t Lmax, const int64_t* lens, std::vector<RagBatchPlan>* batches, bool classes = true);
+// the batches of the conversion c (c.lens set), one after the other on the caller's stream, each from the start of the same workspace
+// region: [tables][convert workspace].  convert_impl runs a batch as ONE utterance of Ttot frames (B = 1) with ctx->rag set.
+int convert_ragged_batches(tvc_ctx* ctx, hipStream_t s, Ws& ws, const std::vector<RagBatchPlan>& batches, const ConvertCall& c);
+
+// Generator.encode (generator.py:19-23) over utterances of different lengths, as extract_index.py:47-52 needs it for a folder of clips:
+// rag_setup, |STFT|, encoder with ctx->rag set - the first half of convert_impl, no index, no decoder.  The spectrogram's |max| slot is
+// the measured per-utterance maximum (run_encoder without a bound: run_amax_rows), as in the stage calls tvc_stft_mag_f32 + tvc_encoder_f32
+// that Generator.encode makes for one utterance: utterance b's columns are bit-identical to those calls at B = 1.  The length classes of
+// ragged_split exist for FilterNet's FiLM kernels; the encoder's kernels choose nothing by an utterance's length, so a call is cut by the
+// frame cap alone and its batches are runs of consecutive rows.
+// the call's plan: its batches, the packed column of every row's first frame, S = all frames
+int encode_ragged_plan(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, std::vector<RagBatchPlan>* batches, std::vector<int>* gpre, int64_t* S);
+int encode_ragged_batches(tvc_ctx* ctx, hipStream_t s, Ws& ws, const std::vector<RagBatchPlan>& batches, const std::vector<int>& gpre, const float* wav,
+                          int64_t Lmax, float* ssl, float* f0, int64_t S);
 
 // ---- device side -------------------------------------------------------------------------------------------------------------
 // utterance of column tile ct: ts[b] <= ct < ts[b + 1]; `hint` = the previous tile's utterance (a persistent walk only moves forward)

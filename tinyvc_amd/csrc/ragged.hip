@@ -1,6 +1,6 @@
 // Host side of ragged batches (ragged.h): the per-call tables (frames per utterance, their prefix, frame -> utterance, per-launch
 // column-tile prefixes) are built on the device from lengths that travel as kernel ARGUMENTS - asynchronous on the caller's stream,
-// no host staging buffer to keep alive, capturable.
+// no host staging buffer to keep alive, capturable.  Behind them, how a call is cut into batches and the loops that run them.
 #include "ragged.h"
 #include "tvc_common.h"
 
@@ -146,6 +146,111 @@ int rag_tiles(tvc_ctx* ctx, hipStream_t s, int B, long len, int bn, RagDev* out,
         if (!mult) mult = (int)(len / h->Ttot);
     }
     return rag_view(ctx, s, mult, bn, out, ntiles);
+}
+
+// ---- the batches of a call (ragged.h) ---------------------------------------------------------------------------------------------
+namespace {
+// the drivers called inside this scope run for the batch h (ctx->rag); whatever way the scope is left, the context forgets it
+struct RagScope {
+    tvc_ctx* ctx;
+    RagScope(tvc_ctx* c, RagHost* h) : ctx(c) { ctx->rag = h; }
+    ~RagScope() { ctx->rag = nullptr; }
+};
+}  // namespace
+
+int ragged_split(tvc_ctx* ctx, int cap, int B, int64_t Lmax, const int64_t* lens, std::vector<RagBatchPlan>* batches, bool classes) {
+    std::vector<RagBatchPlan> open(4);          // the batch being filled, per class
+    const int max_frames = cap > 0 && cap < kRagMaxFrames ? cap : kRagMaxFrames;
+    for (int b = 0; b < B; ++b) {
+        if (lens[b] <= 0 || lens[b] % kHop || lens[b] > Lmax || lens[b] < kNfft / 2 + 1)
+            return fail(ctx, TVC_ERR_ARG, "ragged batch: lens[%d] = %lld must be a multiple of 480 in (960, Lmax]", b, (long long)lens[b]);
+        const int T = (int)(lens[b] / kHop);
+        if (T > kRagMaxFrames) return fail(ctx, TVC_ERR_ARG, "ragged batch: lens[%d] = %lld is longer than a batch may be; convert it with tvc_convert_f32", b, (long long)lens[b]);
+        const int cls = classes ? (T >= kRagClassBounds[0]) + (T >= kRagClassBounds[1]) + (T >= kRagClassBounds[2]) : 0;      // (the encoder's kernels make no length-dependent choice: one class)
+        RagBatchPlan& p = open[cls];
+        if (p.Ttot + T > max_frames && !p.rows.empty()) {
+            batches->push_back(p);
+            p = RagBatchPlan();
+        }
+        p.rows.push_back(b);
+        p.frames.push_back(T);
+        p.Ttot += T;
+    }
+    for (int c = 3; c >= 0; --c)
+        if (!open[c].rows.empty()) batches->push_back(open[c]);
+    return 0;
+}
+
+int convert_ragged_batches(tvc_ctx* ctx, hipStream_t s, Ws& ws, const std::vector<RagBatchPlan>& batches, const ConvertCall& c) {
+    for (auto& p : batches) {
+        ws.release(0);
+        RagHost h;
+        TVC_CHECK(rag_setup(ctx, s, ws, h, p.frames, p.rows, (int)(c.L / kHop)));
+        ConvertCall one = c;      // the batch as one long utterance; the kernels find the rows of c.wav / c.wave through h.row
+        one.B = 1;
+        one.L = (int64_t)p.Ttot * kHop;
+        one.lens = nullptr;
+        RagScope in_batch(ctx, &h);
+        TVC_CHECK(convert_impl(ctx, s, ws, one));
+    }
+    return 0;
+}
+
+namespace {
+// packed[c][gpre[row of b] + t'] = batch[c][pre[b] + t'] (c = 768: the f0 row): a later batch's columns into the call's packed outputs
+__global__ __launch_bounds__(256) void pack_batch_kernel(const float* __restrict__ ssl_b, const float* __restrict__ f0_b, float* __restrict__ ssl,
+                                                         float* __restrict__ f0, RagDev rg, const int* __restrict__ gpre, int Ttot, long S) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= Ttot) return;
+    const int b = rg.col2b[t];
+    const long dst = (long)gpre[rg.row[b]] + (t - rg.pre[b]);
+    const int c = blockIdx.y;
+    if (c < kSslDim) ssl[(long)c * S + dst] = ssl_b[(long)c * Ttot + t];
+    else f0[dst] = f0_b[t];
+}
+}  // namespace
+
+int encode_ragged_batches(tvc_ctx* ctx, hipStream_t s, Ws& ws, const std::vector<RagBatchPlan>& batches, const std::vector<int>& gpre, const float* wav,
+                          int64_t Lmax, float* ssl, float* f0, int64_t S) {
+    ws.release(0);
+    const bool direct = batches.size() == 1;      // one batch holds every row in the caller's order: its layout IS the packed one (row stride S)
+    int* d_gpre = nullptr;
+    if (!direct) {
+        d_gpre = ws.get<int>(gpre.size());
+        if (!ws.dry) TVC_CHECK(upload_ints(ctx, s, gpre, d_gpre));
+    }
+    const size_t m0 = ws.mark();
+    for (auto& p : batches) {
+        ws.release(m0);
+        RagHost h;
+        TVC_CHECK(rag_setup(ctx, s, ws, h, p.frames, p.rows, (int)(Lmax / kHop)));
+        float* spec = ws.get<float>((size_t)kBins * p.Ttot);
+        float* ssl_b = direct ? ssl : ws.get<float>((size_t)kSslDim * p.Ttot);
+        float* f0_b = direct ? f0 : ws.get<float>((size_t)p.Ttot);
+        RagScope in_batch(ctx, &h);
+        TVC_CHECK(run_stft(ctx, s, ws, wav, spec, 1, (int64_t)p.Ttot * kHop));
+        TVC_CHECK(run_encoder(ctx, s, ws, spec, ssl_b, f0_b, nullptr, 1, p.Ttot));
+        if (!direct && !ws.dry) {
+            RagDev rg;
+            TVC_CHECK(rag_view(ctx, s, 1, 0, &rg, nullptr));
+            hipLaunchKernelGGL(pack_batch_kernel, dim3((unsigned)((p.Ttot + 255) / 256), kSslDim + 1), dim3(256), 0, s, ssl_b, f0_b, ssl, f0, rg, d_gpre, p.Ttot, (long)S);
+            TVC_CHECK(launch_check(ctx, "encode_ragged pack"));
+        }
+    }
+    return 0;
+}
+
+int encode_ragged_plan(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, std::vector<RagBatchPlan>* batches, std::vector<int>* gpre, int64_t* S) {
+    TVC_CHECK(ragged_split(ctx, ctx->rag_batch_frames, B, Lmax, lens, batches, false));
+    gpre->assign((size_t)B, 0);
+    int64_t tot = 0;
+    for (int b = 0; b < B; ++b) {
+        (*gpre)[b] = (int)tot;
+        tot += lens[b] / kHop;
+        if (tot > 0x7fffffff) return fail(ctx, TVC_ERR_ARG, "ragged encode: more than 2^31 - 1 frames in one call");
+    }
+    *S = tot;
+    return 0;
 }
 
 }  // namespace tvc

@@ -207,7 +207,7 @@ inline int fail(tvc_ctx* ctx, int code, const char* fmt, ...) {
         if (rc_ != 0) return rc_; \
     } while (0)
 
-// Bump allocator over the caller's workspace; in dry mode it only measures (api.hip TVC_RUN: every entry walks its driver dry, then for
+// Bump allocator over the caller's workspace; in dry mode it only measures (api.hip run_walks: every entry walks its driver dry, then for
 // real).  The drivers make the same get() calls in both walks - only launches, memsets, events and uploads look at `dry` -: equal peaks.
 struct Ws {
     char* base;
@@ -353,6 +353,33 @@ struct KnnSegIn {
     int col0, ncols;
 };
 int run_knn_segs(tvc_ctx*, hipStream_t, Ws&, const float* src, const KnnSegIn* in, int nin, float* out, int64_t* idx_out, int B, int T);
+
+// ---- one conversion, as the entries describe it to convert_impl (api.hip) and to the ragged batch loop (ragged.hip) -----------
+// What the rows of a call search: ONE prepared index, or host tables of one per row of the caller's batch (tvc_*_multi) - never both.
+struct ConvertIndex {
+    const float* blob = nullptr;               // one index for every row ...
+    int64_t N = 0;
+    const float* const* blobs = nullptr;       // ... or, per_row, blobs[r] / Ns[r] for the caller's row r (blob and N stay unset)
+    const int64_t* Ns = nullptr;
+    bool per_row = false;
+    static ConvertIndex one(const float* blob, int64_t N) { return {blob, N, nullptr, nullptr, false}; }
+    static ConvertIndex table(const float* const* blobs, const int64_t* Ns) { return {nullptr, 0, blobs, Ns, true}; }
+};
+struct ConvertCall {
+    const float* wav = nullptr;                // [B][L] in, row b zero-padded behind lens[b] samples
+    float* wave = nullptr;                     // [B][L] out
+    int B = 0;
+    int64_t L = 0;                             // samples per row (the Lmax of a ragged call)
+    const int64_t* lens = nullptr;             // host, one per row; nullptr: every row is L samples long
+    ConvertIndex index;
+    float shift = 0.f;                         // semitones of every row ...
+    const float* shifts = nullptr;             // ... or (host, with a per-row index only) one per row
+    const float* angle = nullptr;              // noise phases; nullptr: drawn from `seed`
+    uint64_t seed = 0;
+};
+// Generator.convert over c.B rows of c.L samples (c.lens is not looked at: a ragged call reaches this through convert_ragged_batches,
+// one batch at a time as ONE row with ctx->rag set, ragged.h)
+int convert_impl(tvc_ctx*, hipStream_t, Ws&, const ConvertCall& c);
 int run_knn_topk(tvc_ctx*, hipStream_t, Ws&, const float* src, const float* prepared, int64_t N,
                  float* sims_out, int64_t* idx_out, int B, int T);
 // match_features for any k <= 8 and metric (0 cos, 1 IP, 2 L2) on the RAW index [768][N] in plain fp32 (knn_general.hip)

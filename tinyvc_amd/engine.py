@@ -88,12 +88,22 @@ class Engine:
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def workspace(self, B, L, N):
-        need = ctypes.c_size_t()
-        self._ok(self.lib.tvc_workspace_bytes(self.ctx, int(B), int(L), int(max(N, 4)), ctypes.byref(need)), "tvc_workspace_bytes")
-        if self._ws is None or self._ws.numel() < need.value:
+    def _grow_ws(self, nbytes):
+        if self._ws is None or self._ws.numel() < nbytes:
             self._ws = None
-            self._ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def _query_ws(self, query, *args):
+        """Ask the tvc_workspace_bytes* function `query` what the call described by `args` needs and grow the workspace to it ->
+        (pointer, size): the last two arguments of the entry that query belongs to."""
+        need = ctypes.c_size_t()
+        self._ok(getattr(self.lib, query)(self.ctx, *args, ctypes.byref(need)), query)
+        ws = self._grow_ws(need.value)
+        return _ptr(ws), ctypes.c_size_t(ws.numel())
+
+    def workspace(self, B, L, N):
+        self._query_ws("tvc_workspace_bytes", int(B), int(L), int(max(N, 4)))
         return self._ws
 
     def _wsargs(self, B, L, N=4):
@@ -269,23 +279,15 @@ class Engine:
         """wav [B, Lmax] (row b holds an utterance of lengths[b] samples, a multiple of 480, zero-padded behind it) -> (ssl [768, S],
         f0 [S], pre [B + 1]): every utterance encoded over its OWN length in one call (tvc_encode_ragged_f32), packed as one long
         utterance - utterance b owns columns pre[b] .. pre[b + 1], bit-identical to stft_mag + encoder on it alone."""
-        wav = _prep(wav, "wave", self.device)
-        B, Lmax = wav.shape
-        if Lmax % spec.HOP:
-            raise ValueError("the padded length must be a multiple of 480")
-        if len(lengths) != B:
-            raise ValueError(f"lengths: {len(lengths)} entries for {B} rows")
-        lens = (ctypes.c_int64 * B)(*[int(x) for x in lengths])
-        need = ctypes.c_size_t()
-        self._ok(self.lib.tvc_workspace_bytes_encode_ragged(self.ctx, B, Lmax, lens, ctypes.byref(need)), "tvc_workspace_bytes_encode_ragged")
-        ws = self._grow_ws(need.value)
+        wav, B, Lmax = self._rows(wav, ragged=True)
+        lens = self._lens(lengths, B)
+        p, n = self._query_ws("tvc_workspace_bytes_encode_ragged", B, Lmax, lens)
         pre = [0]
-        for n in lengths:
-            pre.append(pre[-1] + int(n) // spec.HOP)
+        for length in lengths:
+            pre.append(pre[-1] + int(length) // spec.HOP)
         ssl = torch.empty(spec.SSL_DIM, pre[-1], dtype=_F32, device=self.device)
         f0 = torch.empty(pre[-1], dtype=_F32, device=self.device)
-        self._ok(self.lib.tvc_encode_ragged_f32(self.ctx, self._stream(), _ptr(wav), Lmax, lens, _ptr(ssl), _ptr(f0), B, _ptr(ws),
-                                                ctypes.c_size_t(ws.numel())), "tvc_encode_ragged_f32")
+        self._ok(self.lib.tvc_encode_ragged_f32(self.ctx, self._stream(), _ptr(wav), Lmax, lens, _ptr(ssl), _ptr(f0), B, p, n), "tvc_encode_ragged_f32")
         return ssl, f0, pre
 
     def _owned(self, blob):
@@ -333,11 +335,20 @@ class Engine:
             raise ValueError(f"pitch_shift: {len(sh)} shifts for {B} rows")
         return 0.0, (ctypes.c_float * B)(*sh)
 
-    def _grow_ws(self, nbytes):
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = None
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        return self._ws
+    @staticmethod
+    def _lens(lengths, B):
+        """one length per row -> int64 [B] on the host"""
+        if len(lengths) != B:
+            raise ValueError(f"lengths: {len(lengths)} entries for {B} rows")
+        return (ctypes.c_int64 * B)(*[int(x) for x in lengths])
+
+    def _rows(self, wav, ragged=False):
+        """what every convert* / encode_ragged does with its input first: wav [B, L] fp32 on this device, L in whole frames -> (wav, B, L)"""
+        wav = _prep(wav, "wave", self.device)
+        B, L = wav.shape
+        if L % spec.HOP:
+            raise ValueError("the padded length must be a multiple of 480" if ragged else "waveform length must be a multiple of 480 (autopad_waveform)")
+        return wav, B, L
 
     def knn_match_multi(self, src, prepared, Ns, want_indices=False):
         """src [B, 768, T]; row b searches prepared[b] (a blob of knn_prepare, Ns[b] vectors) -> matched [B, 768, T] (, indices [B, T, 4]):
@@ -349,48 +360,33 @@ class Engine:
         blobs, ns = self._table(prepared, Ns, B)
         out = torch.empty_like(src)
         idx = torch.empty(B, T, 4, dtype=torch.int64, device=self.device) if want_indices else None
-        need = ctypes.c_size_t()
-        self._ok(self.lib.tvc_workspace_bytes_multi(self.ctx, B, T * spec.HOP, ns, ctypes.byref(need)), "tvc_workspace_bytes_multi")
-        ws = self._grow_ws(need.value)
-        self._ok(self.lib.tvc_knn_match_multi_f32(self.ctx, self._stream(), _ptr(src), blobs, ns, _ptr(out), _ptr(idx), B, T, _ptr(ws),
-                                                  ctypes.c_size_t(ws.numel())), "tvc_knn_match_multi_f32")
+        p, n = self._query_ws("tvc_workspace_bytes_multi", B, T * spec.HOP, ns)
+        self._ok(self.lib.tvc_knn_match_multi_f32(self.ctx, self._stream(), _ptr(src), blobs, ns, _ptr(out), _ptr(idx), B, T, p, n), "tvc_knn_match_multi_f32")
         return (out, idx) if want_indices else out
 
     def convert_multi(self, wav, prepared, Ns, pitch_shift, noise_angle=None, out=None):
         """convert with one prepared index per row (and pitch_shift a float or one per row): tvc_convert_multi_f32."""
-        wav = _prep(wav, "wave", self.device)
-        B, L = wav.shape
-        if L % spec.HOP:
-            raise ValueError("waveform length must be a multiple of 480 (autopad_waveform)")
+        wav, B, L = self._rows(wav)
         blobs, ns = self._table(prepared, Ns, B)
         shift, shifts = self._shifts(pitch_shift, B)
         a, seed = self._angle(noise_angle, B, L // spec.HOP)
         wave = out if out is not None else torch.empty(B, L, dtype=_F32, device=self.device)
-        need = ctypes.c_size_t()
-        self._ok(self.lib.tvc_workspace_bytes_multi(self.ctx, B, L, ns, ctypes.byref(need)), "tvc_workspace_bytes_multi")
-        ws = self._grow_ws(need.value)
-        self._ok(self.lib.tvc_convert_multi_f32(self.ctx, self._stream(), _ptr(wav), blobs, ns, shift, shifts, _ptr(a), seed, _ptr(wave), B, L,
-                                                _ptr(ws), ctypes.c_size_t(ws.numel())), "tvc_convert_multi_f32")
+        p, n = self._query_ws("tvc_workspace_bytes_multi", B, L, ns)
+        self._ok(self.lib.tvc_convert_multi_f32(self.ctx, self._stream(), _ptr(wav), blobs, ns, shift, shifts, _ptr(a), seed, _ptr(wave), B, L, p, n),
+                 "tvc_convert_multi_f32")
         return wave
 
     def convert_ragged_multi(self, wav, lengths, prepared, Ns, pitch_shift, noise_angle=None):
         """convert_ragged with one prepared index per row (and pitch_shift a float or one per row): tvc_convert_ragged_multi_f32."""
-        wav = _prep(wav, "wave", self.device)
-        B, Lmax = wav.shape
-        if Lmax % spec.HOP:
-            raise ValueError("the padded length must be a multiple of 480")
-        if len(lengths) != B:
-            raise ValueError(f"lengths: {len(lengths)} entries for {B} rows")
+        wav, B, Lmax = self._rows(wav, ragged=True)
+        lens = self._lens(lengths, B)
         blobs, ns = self._table(prepared, Ns, B)
         shift, shifts = self._shifts(pitch_shift, B)
-        lens = (ctypes.c_int64 * B)(*[int(x) for x in lengths])
         a, seed = self._angle(noise_angle, B, Lmax // spec.HOP)
-        need = ctypes.c_size_t()
-        self._ok(self.lib.tvc_workspace_bytes_ragged_multi(self.ctx, B, Lmax, lens, ns, ctypes.byref(need)), "tvc_workspace_bytes_ragged_multi")
-        ws = self._grow_ws(need.value)
+        p, n = self._query_ws("tvc_workspace_bytes_ragged_multi", B, Lmax, lens, ns)
         wave = torch.empty(B, Lmax, dtype=_F32, device=self.device)
         self._ok(self.lib.tvc_convert_ragged_multi_f32(self.ctx, self._stream(), _ptr(wav), Lmax, lens, blobs, ns, shift, shifts, _ptr(a), seed,
-                                                       _ptr(wave), B, _ptr(ws), ctypes.c_size_t(ws.numel())), "tvc_convert_ragged_multi_f32")
+                                                       _ptr(wave), B, p, n), "tvc_convert_ragged_multi_f32")
         return wave
 
     # ---- index-sharded match (one prepared index shard per rank; merged by parallel.match_features_sharded) ----
@@ -446,10 +442,7 @@ class Engine:
 
     # ---- compacting an index: k-means over a prepared blob (tvc_index_*_f32) ----
     def _compact_ws(self, N, K):
-        need = ctypes.c_size_t()
-        self._ok(self.lib.tvc_workspace_bytes_index_compact(self.ctx, int(N), int(K), ctypes.byref(need)), "tvc_workspace_bytes_index_compact")
-        ws = self._grow_ws(need.value)
-        return _ptr(ws), ctypes.c_size_t(ws.numel())
+        return self._query_ws("tvc_workspace_bytes_index_compact", int(N), int(K))
 
     def index_assign(self, points_blob, N, cent_blob, K, assign=None):
         """Nearest centroid (cosine) of every raw vector of `points_blob` (a blob of knn_prepare, either kind, N vectors) among the K vectors of
@@ -623,10 +616,7 @@ class Engine:
         return source
 
     def convert(self, wav, prepared, N, pitch_shift, noise_angle=None, out=None):
-        wav = _prep(wav, "wave", self.device)
-        B, L = wav.shape
-        if L % spec.HOP:
-            raise ValueError("waveform length must be a multiple of 480 (autopad_waveform)")
+        wav, B, L = self._rows(wav)
         a, seed = self._angle(noise_angle, B, L // spec.HOP)
         wave = out if out is not None else torch.empty(B, L, dtype=_F32, device=self.device)
         p, n = self._wsargs(B, L, N)
@@ -636,20 +626,13 @@ class Engine:
     def convert_ragged(self, wav, lengths, prepared, N, pitch_shift, noise_angle=None):
         """wav [B, Lmax] (row b holds an utterance of lengths[b] samples, a multiple of 480, zero-padded behind it) -> [B, Lmax]:
         every utterance converted over its OWN length (tvc_convert_ragged_f32: per-utterance lengths inside the kernels)."""
-        wav = _prep(wav, "wave", self.device)
-        B, Lmax = wav.shape
-        if Lmax % spec.HOP:
-            raise ValueError("the padded length must be a multiple of 480")
-        lens = (ctypes.c_int64 * B)(*[int(x) for x in lengths])
+        wav, B, Lmax = self._rows(wav, ragged=True)
+        lens = self._lens(lengths, B)
         a, seed = self._angle(noise_angle, B, Lmax // spec.HOP)
-        need = ctypes.c_size_t()
-        self._ok(self.lib.tvc_workspace_bytes_ragged(self.ctx, B, Lmax, lens, int(max(N, 4)), ctypes.byref(need)), "tvc_workspace_bytes_ragged")
-        if self._ws is None or self._ws.numel() < need.value:
-            self._ws = None
-            self._ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        p, n = self._query_ws("tvc_workspace_bytes_ragged", B, Lmax, lens, int(max(N, 4)))
         wave = torch.empty(B, Lmax, dtype=_F32, device=self.device)
         self._ok(self.lib.tvc_convert_ragged_f32(self.ctx, self._stream(), _ptr(wav), Lmax, lens, _ptr(prepared), N, float(pitch_shift), _ptr(a), seed,
-                                                 _ptr(wave), B, _ptr(self._ws), ctypes.c_size_t(self._ws.numel())), "tvc_convert_ragged_f32")
+                                                 _ptr(wave), B, p, n), "tvc_convert_ragged_f32")
         return wave
 
     def stream_push(self, buf, blocks):
