@@ -339,6 +339,45 @@ int tvc_convert_ragged_multi_f32(tvc_ctx* ctx, void* stream, const float* wav, i
                                  const float* const* prepared, const int64_t* N, float pitch_shift, const float* pitch_shifts,
                                  const float* noise_angle, uint64_t seed, float* wave, int B, void* ws, size_t ws_bytes);
 
+/* a weighted blend of several speaker indices ------------------------------------------------ */
+/* The multi-index calls above with M prepared indices ("terms") per row and a weight for each: the usual voice morph of kNN-based conversion
+ * (an interpolation slider between two targets, a blend of several enrolments of one speaker, extrapolation away from a speaker with a
+ * negative weight).  The reference has no counterpart: its match_features(source, reference) takes one index per row
+ * (feature_retrieval.py:15-33); staged, a blend is one match per term and a tensor sum.  1 <= M <= TVC_BLEND_MAX.
+ *   - prepared / N: HOST arrays of B * M entries, row-major [B][M]: term m of row b is prepared[b * M + m], a blob of either kind with
+ *     N[b * M + m] >= 4 vectors.  Rows and terms may share blobs.
+ *   - weights: a DEVICE array of B * M floats, row-major [B][M], in the caller's row order.  The kernels read it when they run; the host
+ *     never does.  Weights may be negative or zero and are not normalised by the library; a zero-weight term is still searched (the host
+ *     cannot see the weights) and contributes +0; a non-finite weight gives non-finite output.
+ *   - every query column:  mu_m = (((r0 + r1) + r2) + r3) * 0.25f   (term m's four nearest raw rows: exactly what tvc_knn_match_f32 writes
+ *                                                                     for that blob)
+ *                          out  = w_0 * mu_0;  out = out + w_m * mu_m  for m = 1 .. M - 1
+ *     products and sums rounded separately (no fused multiply-add), in term order.  Each term's four rows are what the single-index search
+ *     returns for that (row, blob) - the two-stage search or the exact kernel by that blob's own size, with its own overflow fallback: the
+ *     segments of the multi-index calls are here the (term, row) runs, every pass of the search still ONE launch for the whole call (the
+ *     search cost grows about M-fold: M * B * T query columns).  The per-term matched tensors never exist in memory.
+ *   - the decoder's content bound of row b is sum_m |w[b][m]| * (|max| of term m's blob), computed on the device in term order.  With M = 1
+ *     and w = 1 a call is bit-identical to its multi-index sibling; with weights (1, 0) to the call against the first terms alone.
+ *   - idx_out (tvc_knn_match_blend_f32, nullable): [M][B][T][4] int64, term m's indices of row b.
+ *   - pitch_shift / pitch_shifts, noise_angle / seed, lens: as in the multi-index calls.
+ *   - every table entry is checked like theirs (non-null, N >= 4, the N it was prepared for), 1 <= M <= TVC_BLEND_MAX and weights non-null;
+ *     nothing is launched when any check fails (TVC_ERR_ARG).
+ *   - capture: the tables travel as kernel ARGUMENTS, the weights are read from the caller's device array at replay time - changing the
+ *     weights in place needs NO re-capture, changing the tables does.  The seeded-draw rule still holds.
+ * Workspace: tvc_workspace_bytes_blend / _ragged_blend (N: the host table of B * M sizes; they assume every entry is a blob of its own). */
+#define TVC_BLEND_MAX 4
+int tvc_knn_match_blend_f32(tvc_ctx* ctx, void* stream, const float* src, const float* const* prepared, const int64_t* N, int M,
+                            const float* weights, float* out, int64_t* idx_out, int B, int T, void* ws, size_t ws_bytes);
+int tvc_workspace_bytes_blend(tvc_ctx* ctx, int B, int64_t L, const int64_t* N, int M, size_t* out_bytes);
+int tvc_convert_blend_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M,
+                          const float* weights, float pitch_shift, const float* pitch_shifts, const float* noise_angle, uint64_t seed,
+                          float* wave, int B, int64_t L, void* ws, size_t ws_bytes);
+int tvc_workspace_bytes_ragged_blend(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, const int64_t* N, int M, size_t* out_bytes);
+int tvc_convert_ragged_blend_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens,
+                                 const float* const* prepared, const int64_t* N, int M, const float* weights, float pitch_shift,
+                                 const float* pitch_shifts, const float* noise_angle, uint64_t seed, float* wave, int B, void* ws,
+                                 size_t ws_bytes);
+
 /* streaming tail -------------------------------------------------------------------------- */
 /* StreamInfer.audio_callback after convert (reference module/infer/stream.py:74-95), batched over
  * S streams: y [S, Ly] converted buffers; sola_buf [S,1920] in/out; fade_in [1920] = the sin^2

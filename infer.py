@@ -3,13 +3,15 @@
 reference infer.py:17-29) driving the HIP path.
 
   python infer.py -i ./inputs/ -o ./outputs/ -encp models/encoder.pt -decp models/decoder.pt \\
-                  -t target.wav | -idx models/index.pt   [-p SEMITONES] [-d cuda]
+                  -t target.wav | -idx models/index.pt | --blend a.pt=0.7 b.pt=0.3   [-p SEMITONES] [-d cuda]
 
 Differences from the reference, all at the edges of the path: files are read/written with the
 package's own WAV I/O and resampler (torchaudio is not a dependency; ogg/mp3 need a codec and are
 skipped with a message); `-d` defaults to `cuda` and must be a GPU (there is no CPU path);
 the whole directory is converted in one call (a ragged batch: every file over its own length); resampling to 24 kHz runs on the GPU
-(tvc_resample_f32); an index.pt stored in half precision is matched with the fp16 index storage.
+(tvc_resample_f32); an index.pt stored in half precision is matched with the fp16 index storage; `--blend PATH=W [PATH=W ...]` (extension)
+converts toward a weighted blend of up to four index files in one call per batch (feature_retrieval.Blend; every rank of a launcher loads
+the blend like it loads the single index).
 
 Under a launcher (`python -m torch.distributed.run --nproc-per-node N infer.py ...`, WORLD_SIZE > 1) every rank converts ITS share of the
 directory on cuda:LOCAL_RANK and writes its own outputs: the files are split by length (longest-processing-time-first on padded samples,
@@ -35,7 +37,8 @@ import torch
 
 from tinyvc_amd import audio_io, parallel, spec
 from tinyvc_amd.module.infer import Generator
-from tinyvc_amd.module.tinyvc import Decoder, Encoder
+from tinyvc_amd.module.tinyvc import Blend, Decoder, Encoder
+from tinyvc_amd.module.tinyvc.feature_retrieval import add_blend_argument
 
 SAMPLE_RATE = 24000
 
@@ -49,6 +52,7 @@ def build_parser():
     p.add_argument("-f0-est", "--f0-estimation", default="default")
     p.add_argument("-idx", "--index", default="NONE")
     p.add_argument("-t", "--target", default="target.wav")
+    add_blend_argument(p)      # --blend PATH=W [PATH=W ...] -> args.blend = (paths, weights)
     p.add_argument("-d", "--device", default="cuda")
     p.add_argument("-p", "--pitch-shift", default=0.0, type=float)
     p.add_argument("-c", "--chunk-size", default=1920, type=int)
@@ -92,7 +96,10 @@ def load_generator(encoder_path, decoder_path, device):
 
 
 def load_target(gen, args, device):
-    """Speaker target: features of a target utterance, or a prebuilt index.pt [1, 768, N]."""
+    """Speaker target: features of a target utterance, a prebuilt index.pt [1, 768, N], or a weighted blend of several (--blend)."""
+    if args.blend is not None:      # a weighted blend of index files: every one loaded like -idx, the weights per term
+        paths, weights = args.blend
+        return Blend([torch.load(p_, map_location="cpu").to(device) for p_ in paths], weights)
     if args.index == "NONE":
         wf, sr = audio_io.load(args.target)
         wf = gen.engine(device).resample(wf.to(device), sr, SAMPLE_RATE)

@@ -8,6 +8,8 @@ playback loop.  GPU nodes have neither, so the same loop can be driven from file
   python infer_streaming.py -encp enc.pt -decp dec.pt -idx index.pt \\
          --input-wav in.wav --output-wav out.wav [--streams 32]
 
+`--blend PATH=W [PATH=W ...]` (extension) takes the place of `-idx` / `-t`: a weighted blend of up to four index files.
+
 `--streams S` feeds S copies of the input as S concurrent streams through one BatchedStreamInfer
 (one batched convert + one SOLA launch per block) and reports the p50 / p95 block latency against the
 real-time budget (chunk / 24 kHz = 80 ms for the default 1920-sample chunk).
@@ -21,7 +23,8 @@ import torch
 
 from tinyvc_amd import audio_io
 from tinyvc_amd.module.infer import BatchedStreamInfer, Generator
-from tinyvc_amd.module.tinyvc import Decoder, Encoder
+from tinyvc_amd.module.tinyvc import Blend, Decoder, Encoder
+from tinyvc_amd.module.tinyvc.feature_retrieval import add_blend_argument
 
 
 def build_parser():
@@ -34,6 +37,7 @@ def build_parser():
     p.add_argument("-idx", "--index", default="NONE")
     p.add_argument("-p", "--pitch-shift", default=0, type=float)
     p.add_argument("-t", "--target", default="target.wav")
+    add_blend_argument(p)      # --blend PATH=W [PATH=W ...] -> args.blend = (paths, weights)
     p.add_argument("-c", "--chunk", default=1920, type=int)
     p.add_argument("-e", "--extra", default=3840, type=int)
     p.add_argument("-d", "--device", default="cuda")
@@ -70,7 +74,10 @@ def main(argv=None):
     S = max(1, args.streams)
     stream = BatchedStreamInfer(gen, n_streams=S, pitch_shift=args.pitch_shift, block_size=args.chunk, device=device,
                                 extra_size=args.extra, f0_estimation=args.f0_estimation)
-    if args.index == "NONE":
+    if args.blend is not None:      # a weighted blend of index files in place of -idx / -t; every stream takes the same mix
+        paths, weights = args.blend
+        tgt = Blend([torch.load(p_, map_location="cpu").to(device) for p_ in paths], weights)
+    elif args.index == "NONE":
         wf, sr = audio_io.load(args.target)
         wf = gen.engine(device).resample(wf.to(device), sr, 24000)
         tgt, _ = gen.encode(wf.mean(dim=0, keepdim=True))

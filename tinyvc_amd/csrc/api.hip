@@ -216,28 +216,33 @@ int tvc::convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const ConvertCall& c)
     float* spec_bound = emax + NB;
     float* enc_slots = spec_bound + NB;      // the encoder's three atomicMax slots: zeroed by the energy stage's pooled-maximum launch
     // one index per row: every utterance's matched-content bound is its own index's |max| (so its fp16-split scales, and its bits, are those
-    // of its own B = 1 call), and its runs of query columns go to the search as segments; per-row pitch shifts travel like the lengths
+    // of its own B = 1 call), and its runs of query columns go to the search as segments; per-row pitch shifts travel like the lengths.
+    // A blend (ix.M terms per row): the (term, row) runs over ix.M x the columns, term-major, and the bound is sum_m |w_m| * |max|_m.
+    const int M = ix.M > 0 ? ix.M : 1;
     float* rowmax = ix.per_row ? ws.get<float>((size_t)NB) : nullptr;
     float* rshift = ix.per_row && c.shifts ? ws.get<float>((size_t)NB) : nullptr;
     std::vector<KnnSegIn> segs;
     if (ix.per_row) {
-        for (int i = 0; i < NB; ++i) {
-            const int r = ctx->rag ? ctx->rag->row[i] : i;
-            const int c0 = ctx->rag ? ctx->rag->pre[i] : i * T, nc = ctx->rag ? ctx->rag->tb[i] : T;
-            segs.push_back(KnnSegIn{ix.blobs[r], ix.Ns[r], c0, nc});
-        }
+        for (int m = 0; m < M; ++m)
+            for (int i = 0; i < NB; ++i) {
+                const int r = ctx->rag ? ctx->rag->row[i] : i;
+                const int c0 = ctx->rag ? ctx->rag->pre[i] : i * T, nc = ctx->rag ? ctx->rag->tb[i] : T;
+                segs.push_back(KnnSegIn{ix.blobs[(size_t)r * M + m], ix.Ns[(size_t)r * M + m], m * B * T + c0, nc});
+            }
     } else {
         segs.push_back(KnnSegIn{ix.blob, ix.N, 0, B * T});
     }
     if (ix.per_row && !ws.dry) {
-        std::vector<const float*> bl(NB);
-        std::vector<int> sh(NB);
+        std::vector<const float*> bl((size_t)NB * M);
+        std::vector<int> sh(NB), rows(NB);
         for (int i = 0; i < NB; ++i) {
             const int r = ctx->rag ? ctx->rag->row[i] : i;
-            bl[i] = ix.blobs[r];
+            rows[i] = r;
+            for (int m = 0; m < M; ++m) bl[(size_t)i * M + m] = ix.blobs[(size_t)r * M + m];
             if (rshift) std::memcpy(&sh[i], &c.shifts[r], sizeof(int));
         }
-        TVC_CHECK(run_knn_amax_rows(ctx, s, bl, rowmax));
+        if (ix.M > 0) TVC_CHECK(run_knn_blend_bound(ctx, s, bl, rows, M, ix.weights, rowmax));
+        else TVC_CHECK(run_knn_amax_rows(ctx, s, bl, rowmax));
         if (rshift) TVC_CHECK(upload_ints(ctx, s, sh, reinterpret_cast<int*>(rshift)));
     }
     size_t m = ws.mark();
@@ -258,7 +263,8 @@ int tvc::convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const ConvertCall& c)
     ws.release(m);
     {
         ProfScope ps(ctx, s, ws, "knn");
-        TVC_CHECK(run_knn_segs(ctx, s, ws, ssl, segs.data(), (int)segs.size(), matched, nullptr, B, T));
+        if (ix.M > 0) TVC_CHECK(run_knn_blend(ctx, s, ws, ssl, segs.data(), (int)segs.size(), ix.M, ix.weights, matched, nullptr, B, T));
+        else TVC_CHECK(run_knn_segs(ctx, s, ws, ssl, segs.data(), (int)segs.size(), matched, nullptr, B, T));
     }
     ws.release(m);
     TVC_CHECK(run_decoder(ctx, s, ws, matched, f0s, energy, c.angle, c.seed, c.wave, nullptr, nullptr, nullptr, B, T,
@@ -548,7 +554,15 @@ static int rows_check(tvc_ctx* ctx, hipStream_t s, int B, const float* const* pr
     return 0;
 }
 
-// The four tvc_convert*_f32 entries: the checks under the entry's own name `what`, then the two walks.  ragged: c.lens holds every row's
+// a blend's own arguments: 1 .. TVC_BLEND_MAX terms per row, the device weights, tables that 32-bit column numbers can address
+static int blend_check(tvc_ctx* ctx, int B, int M, const float* weights, const char* what) {
+    if (M < 1 || M > TVC_BLEND_MAX) return fail(ctx, TVC_ERR_ARG, "%s: M = %d terms per row; a blend takes 1 ... %d", what, M, TVC_BLEND_MAX);
+    if (!weights) return fail(ctx, TVC_ERR_ARG, "%s: weights is NULL (a device array of B * M floats)", what);
+    if (B <= 0 || (int64_t)B * M > 0x7fffffff) return fail(ctx, TVC_ERR_ARG, "%s: bad argument", what);
+    return 0;
+}
+
+// The tvc_convert*_f32 entries: the checks under the entry's own name `what`, then the two walks.  ragged: c.lens holds every row's
 // own length and c.L is Lmax; the call runs as the batches of ragged_split and the padded output is cleared once in front of them.
 static int convert_entry(tvc_ctx* ctx, void* stream, const ConvertCall& c, bool ragged, void* wsp, size_t ws_bytes, const char* what) {
     TVC_CHECK(need_ready(ctx, NEED_ENC | NEED_DEC));
@@ -557,12 +571,14 @@ static int convert_entry(tvc_ctx* ctx, void* stream, const ConvertCall& c, bool 
     if (!c.wav || !c.wave || (ragged && !c.lens) || (!ix.per_row && !ix.blob) || c.B <= 0 || c.L <= 0 || c.L % kHop)
         return fail(ctx, TVC_ERR_ARG, "%s: bad argument (%s must be a positive multiple of 480)", what, ragged ? "Lmax" : "L");
     if (!ragged && c.L < kNfft / 2 + 1) return fail(ctx, TVC_ERR_ARG, "%s: L must exceed 960 samples (STFT reflect padding, as torch.stft requires)", what);
+    if (ix.weights || ix.M) TVC_CHECK(blend_check(ctx, c.B, ix.M, ix.weights, what));
     if (ix.per_row) {
-        TVC_CHECK(rows_check(ctx, s, c.B, ix.blobs, ix.Ns, what));
+        TVC_CHECK(rows_check(ctx, s, c.B * (ix.M > 0 ? ix.M : 1), ix.blobs, ix.Ns, what));
     } else {
         if (ix.N < 4) return fail(ctx, TVC_ERR_ARG, "%s: index needs at least k=4 vectors", what);
         TVC_CHECK(blob_check(ctx, s, ix.blob, ix.N, what));
     }
+    if (ix.M > 0 && (int64_t)c.B * ix.M * (c.L / kHop) > 0x7fffffff) return fail(ctx, TVC_ERR_ARG, "%s: more than 2^31 - 1 query columns", what);
     TVC_CHECK(draw_under_capture(ctx, s, c.angle, what));
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     if (!ragged) return run_walks(ctx, what, wsp, ws_bytes, 1, [&](Ws& ws) { return convert_impl(ctx, s, ws, c); });
@@ -584,9 +600,12 @@ static int convert_query(tvc_ctx* ctx, int B, int64_t L, const int64_t* lens, bo
     TVC_CHECK(need_ready(ctx, NEED_NONE));
     if (!out_bytes || (ragged && !lens) || (ix.per_row ? !ix.Ns : ix.N < 4) || B <= 0 || L <= 0 || L % kHop != 0)
         return fail(ctx, TVC_ERR_ARG, "%s: need B>0, %s%%480==0, %s%s", what, ragged ? "Lmax" : "L", ragged && ix.per_row ? "lens[B], " : "", ix.per_row ? "N[B]" : "N>=4");
-    for (int b = 0; ix.per_row && b < B; ++b)
+    if (ix.M) TVC_CHECK(blend_check(ctx, B, ix.M, kDryPtr, what));
+    const int M = ix.M > 0 ? ix.M : 1;
+    if (!ragged && (int64_t)B * M * (L / kHop) > 0x7fffffff) return fail(ctx, TVC_ERR_ARG, "%s: more than 2^31 - 1 query columns", what);
+    for (int b = 0; ix.per_row && b < B * M; ++b)
         if (ix.Ns[b] < 4) return fail(ctx, TVC_ERR_ARG, "%s: N[%d] < 4", what, b);
-    std::vector<const float*> blobs(ix.per_row ? (size_t)B : 0);
+    std::vector<const float*> blobs(ix.per_row ? (size_t)B * M : 0);
     for (size_t b = 0; b < blobs.size(); ++b) blobs[b] = kDryPtr + 64 * b;
     const float shift = 0.f;
     ConvertCall c;
@@ -594,7 +613,7 @@ static int convert_query(tvc_ctx* ctx, int B, int64_t L, const int64_t* lens, bo
     c.B = B;
     c.L = L;
     c.lens = lens;
-    c.index = ix.per_row ? ConvertIndex::table(blobs.data(), ix.Ns) : ConvertIndex::one(kDryPtr, ix.N);
+    c.index = ix.M ? ConvertIndex::blend(blobs.data(), ix.Ns, ix.M, kDryPtr) : ix.per_row ? ConvertIndex::table(blobs.data(), ix.Ns) : ConvertIndex::one(kDryPtr, ix.N);
     c.shifts = ix.per_row ? &shift : nullptr;
     if (!ragged) return measure(1, out_bytes, [&](Ws& ws) { return convert_impl(ctx, nullptr, ws, c); });
     std::vector<RagBatchPlan> batches;
@@ -648,6 +667,49 @@ int tvc_knn_match_multi_f32(tvc_ctx* ctx, void* stream, const float* src, const 
     std::vector<KnnSegIn> in((size_t)B);
     for (int b = 0; b < B; ++b) in[b] = KnnSegIn{prepared[b], N[b], b * T, T};
     return run_walks(ctx, __func__, wsp, ws_bytes, 1, [&](Ws& ws) { return run_knn_segs(ctx, s, ws, src, in.data(), B, out, idx_out, B, T); });
+}
+
+// ---- a weighted blend of several indices per row ------------------------------------------------------------------------------------------
+int tvc_workspace_bytes_blend(tvc_ctx* ctx, int B, int64_t L, const int64_t* N, int M, size_t* out_bytes) {
+    if (!ctx) return TVC_ERR_ARG;
+    TVC_CHECK(blend_check(ctx, B, M, kDryPtr, "tvc_workspace_bytes_blend"));
+    return convert_query(ctx, B, L, nullptr, false, ConvertIndex::blend(nullptr, N, M, nullptr), out_bytes, "tvc_workspace_bytes_blend");
+}
+int tvc_workspace_bytes_ragged_blend(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, const int64_t* N, int M, size_t* out_bytes) {
+    if (!ctx) return TVC_ERR_ARG;
+    TVC_CHECK(blend_check(ctx, B, M, kDryPtr, "tvc_workspace_bytes_ragged_blend"));
+    return convert_query(ctx, B, Lmax, lens, true, ConvertIndex::blend(nullptr, N, M, nullptr), out_bytes, "tvc_workspace_bytes_ragged_blend");
+}
+int tvc_convert_blend_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M, const float* weights,
+                          float pitch_shift, const float* pitch_shifts, const float* noise_angle, uint64_t seed, float* wave, int B, int64_t L, void* wsp,
+                          size_t ws_bytes) {
+    if (!ctx) return TVC_ERR_ARG;
+    TVC_CHECK(blend_check(ctx, B, M, weights, "tvc_convert_blend_f32"));
+    const ConvertCall c{wav, wave, B, L, nullptr, ConvertIndex::blend(prepared, N, M, weights), pitch_shift, pitch_shifts, noise_angle, seed};
+    return convert_entry(ctx, stream, c, false, wsp, ws_bytes, "tvc_convert_blend_f32");
+}
+int tvc_convert_ragged_blend_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens, const float* const* prepared,
+                                 const int64_t* N, int M, const float* weights, float pitch_shift, const float* pitch_shifts, const float* noise_angle,
+                                 uint64_t seed, float* wave, int B, void* wsp, size_t ws_bytes) {
+    if (!ctx) return TVC_ERR_ARG;
+    TVC_CHECK(blend_check(ctx, B, M, weights, "tvc_convert_ragged_blend_f32"));
+    const ConvertCall c{wav, wave, B, Lmax, lens, ConvertIndex::blend(prepared, N, M, weights), pitch_shift, pitch_shifts, noise_angle, seed};
+    return convert_entry(ctx, stream, c, true, wsp, ws_bytes, "tvc_convert_ragged_blend_f32");
+}
+
+int tvc_knn_match_blend_f32(tvc_ctx* ctx, void* stream, const float* src, const float* const* prepared, const int64_t* N, int M, const float* weights,
+                            float* out, int64_t* idx_out, int B, int T, void* wsp, size_t ws_bytes) {
+    if (!ctx) return TVC_ERR_ARG;
+    if (!src || !out || B <= 0 || T <= 0) return fail(ctx, TVC_ERR_ARG, "tvc_knn_match_blend_f32: bad argument");
+    TVC_CHECK(blend_check(ctx, B, M, weights, "tvc_knn_match_blend_f32"));
+    if ((int64_t)B * M * T > 0x7fffffff) return fail(ctx, TVC_ERR_ARG, "tvc_knn_match_blend_f32: more than 2^31 - 1 query columns");
+    hipStream_t s = (hipStream_t)stream;
+    TVC_CHECK(rows_check(ctx, s, B * M, prepared, N, "tvc_knn_match_blend_f32"));
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<KnnSegIn> in;
+    for (int m = 0; m < M; ++m)
+        for (int b = 0; b < B; ++b) in.push_back(KnnSegIn{prepared[(size_t)b * M + m], N[(size_t)b * M + m], (m * B + b) * T, T});
+    return run_walks(ctx, __func__, wsp, ws_bytes, 1, [&](Ws& ws) { return run_knn_blend(ctx, s, ws, src, in.data(), (int)in.size(), M, weights, out, idx_out, B, T); });
 }
 
 // ---- ragged batches: the plan (ragged.hip) as callers see it, and the ragged encode ----------------------------------------------------

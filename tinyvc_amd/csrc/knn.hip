@@ -443,8 +443,10 @@ int run_prepare_index_cols_f16(tvc_ctx* ctx, hipStream_t s, const float* feats, 
 // (a segment's tiles are consecutive, its columns beyond its own count in its last tile are zero: the grid then runs over whole tiles);
 // cnt / flag (optional) = the two-stage search's per-query candidate counters and the segments' overflow flags, zeroed here;
 // col2seg (optional, several segments) = the segment of every column.
+// Bsrc = rows of src: row b of qn holds the queries of src row b % Bsrc (a blend call searches every source row once per term: B = terms x
+// Bsrc virtual rows; every other call has Bsrc == B).
 constexpr int QN_WAVES = 16;     // waves per 64-column group: each squares / scales KD / 16 = 48 channels (strided rows: the loop is a latency chain)
-static __global__ __launch_bounds__(QN_WAVES * 64) void query_normalize_kernel(const float* __restrict__ src, float* __restrict__ qn, int B, int T,
+static __global__ __launch_bounds__(QN_WAVES * 64) void query_normalize_kernel(const float* __restrict__ src, float* __restrict__ qn, int B, int Bsrc, int T,
                                                                      uint4* __restrict__ qh, int* __restrict__ cnt, int* __restrict__ flag,
                                                                      const KnnSegs segs, int* __restrict__ col2seg) {
     __shared__ float part[QN_WAVES][64];
@@ -473,7 +475,7 @@ static __global__ __launch_bounds__(QN_WAVES * 64) void query_normalize_kernel(c
     if (wave == 0 && ok && cnt) cnt[n] = 0;
     if (wave == 0 && ok && col2seg) col2seg[n] = sg;
     const int b = (int)(nn / T), t = (int)(nn - (long)b * T);
-    const float* p = src + (long)b * KD * T + t;
+    const float* p = src + (long)(b % Bsrc) * KD * T + t;
     float* q = qn + (long)b * KD * T + t;
     constexpr int KW = KD / QN_WAVES;
     const int k0 = wave * KW;
@@ -853,6 +855,141 @@ static __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const floa
         }
         __syncthreads();
     }
+}
+
+// ---- a weighted blend of several indices (tvc_*_blend_f32) -------------------------------------------------------------------
+// Every source row is searched once per term: term m of the call's ncols real columns is the virtual columns [m * ncols, (m + 1) * ncols)
+// of ONE search (virtual row m * B + b holds the queries of source row b: query_normalize_kernel's Bsrc), whose segments are the
+// (term, row) runs - each with its own path and overflow flag, exactly the single-index search of that (row, blob).  This kernel is the
+// blend's knn_merge_gather_kernel<true>: one workgroup = 32 REAL columns; threads (m, q) merge term m's lists of column q and write its
+// indices; the gather then walks the terms per query, four queries in flight per wave as there, and keeps
+//   out = w_0 * mu_0;  out = out + w_m * mu_m  (m = 1 .. M - 1),   mu_m = (((r0 + r1) + r2) + r3) * 0.25f
+// in registers - products and sums rounded separately (__fmul_rn / __fadd_rn), in term order - so the per-term matched tensors never exist
+// in memory.  One LDS transpose, stores along t.  weights [rows][M] is the caller's DEVICE array, read here: a captured graph replays with
+// whatever it holds then.  The weight row of a column is its batch row, or rowmap[col2b[column]] in a ragged batch (ragged.h).
+constexpr int BLEND_MAX = TVC_BLEND_MAX;
+static __global__ __launch_bounds__(256) void knn_merge_blend_gather_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
+                                                                            const KnnSegs segs, const int* __restrict__ col2seg, int ncols, int T,
+                                                                            int M, const float* __restrict__ weights, const int* __restrict__ col2b,
+                                                                            const int* __restrict__ rowmap, float* __restrict__ out,
+                                                                            int64_t* __restrict__ idx_out, const float* __restrict__ rv,
+                                                                            const int* __restrict__ ri, const int* __restrict__ flags) {
+    __shared__ int sel[BLEND_MAX][32][4];
+    __shared__ float tile[32][193];
+    __shared__ const float* sblob[BLEND_MAX][32];
+    __shared__ int skind[BLEND_MAX][32], sN[BLEND_MAX][32];
+    __shared__ float sw[BLEND_MAX][32];
+    const int tid = threadIdx.x;
+    const int n0 = blockIdx.x * 32;
+    if (tid < 32 * M) {
+        const int m = tid >> 5, q = tid & 31;
+        const int n = n0 + q;
+        const bool live = n < ncols;
+        const int nc = live ? n : ncols - 1;            // (a column past the end gathers row 0 of the last column's blobs: never stored)
+        const long vcols = (long)M * ncols;             // the search's columns: the lists' stride
+        const long vc = (long)m * ncols + nc;           // this term's virtual column
+        const int si = col2seg ? col2seg[vc] : 0;
+        const KnnSeg g = seg_get(segs, si);
+        const bool rescored = g.two && flags[si] == 0;
+        const float* cv = rescored ? rv : cand_v;
+        const int* ci = rescored ? ri : cand_i;
+        const int nsplit = rescored ? 1 : g.nsE;
+        const int N = g.N;
+        Top4 t4;
+        t4.init();
+        if (live) {
+            for (int s = 0; s < nsplit; ++s) {
+                const long o = ((long)s * vcols + vc) * 4;
+                for (int e = 0; e < 4; ++e) t4.insert(cv[o + e], ci[o + e]);
+            }
+            for (int e = 0; e < 4; ++e) t4.i[e] = (unsigned)t4.i[e] < (unsigned)N ? t4.i[e] : 0;   // never gather through a sentinel
+            if (idx_out)
+                for (int e = 0; e < 4; ++e) idx_out[vc * 4 + e] = (int64_t)t4.i[e];
+        }
+        for (int e = 0; e < 4; ++e) sel[m][q][e] = live ? t4.i[e] : 0;
+        sblob[m][q] = g.blob;
+        skind[m][q] = reinterpret_cast<const int*>(g.blob)[1];
+        sN[m][q] = N;
+        const int row = col2b ? rowmap[col2b[nc]] : nc / T;
+        sw[m][q] = weights[(long)row * M + m];
+    }
+    __syncthreads();
+    const int lane = tid & 63, wave = tid >> 6;
+    for (int kc = 0; kc < KD; kc += 192) {
+        for (int q0 = wave; q0 < 32; q0 += 16) {
+            float acc[4][3];
+#pragma unroll 1
+            for (int m = 0; m < M; ++m) {
+                float r[4][3][4];
+#pragma unroll
+                for (int qq = 0; qq < 4; ++qq) {
+                    const int q = q0 + 4 * qq;
+                    const float* blob = sblob[m][q];
+                    const int kind = skind[m][q], N = sN[m][q];
+                    const long Npad = ((long)N + 127) / 128 * 128;
+#pragma unroll
+                    for (int u = 0; u < 3; ++u)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) r[qq][u][e] = blob_row_value(blob, kind, N, Npad, sel[m][q][e], kc + lane + 64 * u);
+                }
+#pragma unroll
+                for (int qq = 0; qq < 4; ++qq) {
+                    const float w = sw[m][q0 + 4 * qq];
+#pragma unroll
+                    for (int u = 0; u < 3; ++u) {
+                        const float sum = __fadd_rn(__fadd_rn(__fadd_rn(r[qq][u][0], r[qq][u][1]), r[qq][u][2]), r[qq][u][3]);
+                        const float mu = sum * 0.25f;
+                        const float term = __fmul_rn(w, mu);
+                        acc[qq][u] = m == 0 ? term : __fadd_rn(acc[qq][u], term);
+                    }
+                }
+            }
+#pragma unroll
+            for (int qq = 0; qq < 4; ++qq)
+#pragma unroll
+                for (int u = 0; u < 3; ++u) tile[q0 + 4 * qq][lane + 64 * u] = acc[qq][u];
+        }
+        __syncthreads();
+        // scatter: lanes run along the 32 queries (time), 8 k-rows per pass
+        for (int kk = tid >> 5; kk < 192; kk += 8) {
+            const int q = tid & 31;
+            const int n = n0 + q;
+            if (n < ncols) {
+                const int b = n / T, t = n - b * T;
+                out[((long)b * KD + kc + kk) * T + t] = tile[q][kk];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// out[i] = sum_m |w[row[i]][m]| * (the |max| of blob (i, m)), in term order, products and sums rounded separately: the bound of row i's blended
+// content (|mu_m| <= its blob's |max|), the decoder's content bound of a blend call.  One workgroup; the blobs and the weight rows travel as
+// kernel arguments (like index_amax_rows_kernel), the weights are read from the caller's device array.
+constexpr int BB_ROWS = 64;
+struct BlendBoundChunk {
+    const float* p[BB_ROWS * BLEND_MAX];
+    int row[BB_ROWS];
+};
+static __global__ __launch_bounds__(BB_ROWS) void blend_bound_kernel(BlendBoundChunk c, const float* __restrict__ weights, int M, float* __restrict__ out, int n) {
+    const int i = threadIdx.x;
+    if (i >= n) return;
+    const float* w = weights + (long)c.row[i] * M;
+    float b = __fmul_rn(fabsf(w[0]), c.p[i * M][4]);
+    for (int m = 1; m < M; ++m) b = __fadd_rn(b, __fmul_rn(fabsf(w[m]), c.p[i * M + m][4]));
+    out[i] = b;
+}
+int run_knn_blend_bound(tvc_ctx* ctx, hipStream_t s, const std::vector<const float*>& blobs, const std::vector<int>& rows, int M, const float* weights, float* out) {
+    for (size_t o = 0; o < rows.size(); o += BB_ROWS) {
+        BlendBoundChunk c;
+        const int n = (int)(rows.size() - o < BB_ROWS ? rows.size() - o : BB_ROWS);
+        for (int i = 0; i < n; ++i) {
+            c.row[i] = rows[o + i];
+            for (int m = 0; m < M; ++m) c.p[i * M + m] = blobs[(o + i) * M + m];
+        }
+        hipLaunchKernelGGL(blend_bound_kernel, dim3(1), dim3(BB_ROWS), 0, s, c, weights, M, out + o, n);
+    }
+    return launch_check(ctx, "knn_blend_bound");
 }
 
 // ---- index-sharded search (one index shard per GPU): local top-4 with similarities, slot gather, finish ----
@@ -1487,7 +1624,8 @@ static int coarse_max_nsplit(int qtiles) { return (768 + qtiles - 1) / qtiles; }
 // query normalisation + the per-query top-4 lists; shared by the whole-index match and the index-sharded variant.
 // (The blob's kind lives in device memory - its header -, so the host cannot pick an instantiation: the kernels branch on it.)
 // The segment table of a several-segment call is uploaded as kernel arguments (ragged.h upload_ints): asynchronous, capturable.
-static int knn_candidates(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const KnnCall& c, int B, int T, KnnLists* L) {
+// (Bsrc: rows of src behind the B rows of queries - query_normalize_kernel; 0 = B)
+static int knn_candidates(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const KnnCall& c, int B, int T, KnnLists* L, int Bsrc = 0) {
     const int nseg = (int)c.seg.size();
     float* qn = ws.get<float>((size_t)B * KD * T);
     L->cv = ws.get<float>((size_t)c.ns_cv * c.ncols * 4);
@@ -1518,7 +1656,7 @@ static int knn_candidates(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src,
         TVC_CHECK(upload_ints(ctx, s, words, dtab));
     }
     const int nblk = c.two ? c.cq * 4 : (c.ncols + 63) / 64;      // the fp16 query image is written for whole 256-query tiles
-    hipLaunchKernelGGL(query_normalize_kernel, dim3(nblk), dim3(QN_WAVES * 64), 0, s, src, qn, B, T, qh, cnt, L->flag, L->segs, L->col2seg);
+    hipLaunchKernelGGL(query_normalize_kernel, dim3(nblk), dim3(QN_WAVES * 64), 0, s, src, qn, B, Bsrc > 0 ? Bsrc : B, T, qh, cnt, L->flag, L->segs, L->col2seg);
     if (c.two) {
         ProfScope ps(ctx, s, ws, "knn.coarse+rescore");
         TVC_CHECK((coarse_launch<0>(ctx, s, c, *L, qh, c4v, cnt, cand, candv)));
@@ -1566,6 +1704,23 @@ int run_knn_segs(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const Kn
         hipLaunchKernelGGL(knn_merge_gather_kernel<false>, dim3((c.ncols + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)nullptr, c.ncols, T,
                            out, idx_out, L.rv, L.ri, (const int*)L.flag);
     return launch_check(ctx, "knn_match");
+}
+
+// in[]: the (term, row) runs over the M * B * T virtual columns, term-major (term m's copy of real column n is column m * B * T + n); one
+// knn_candidates walk - every pass one launch, as run_knn_segs -, then the blend gather.  idx_out (nullable): [M][B][T][4].  A ragged batch
+// (ctx->rag: B = 1, T = all its frames) finds a column's weight row through the batch's tables.
+int run_knn_blend(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const KnnSegIn* in, int nin, int M, const float* weights, float* out,
+                  int64_t* idx_out, int B, int T) {
+    KnnCall c;
+    TVC_CHECK(knn_call_plan(ctx, in, nin, M * B * T, &c));
+    KnnLists L;
+    TVC_CHECK(knn_candidates(ctx, s, ws, src, c, M * B, T, &L, B));
+    if (ws.dry) return 0;
+    const RagHost* h = ctx->rag;
+    hipLaunchKernelGGL(knn_merge_blend_gather_kernel, dim3((B * T + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)L.col2seg, B * T, T, M, weights,
+                       h ? (const int*)h->d_col2b : (const int*)nullptr, h ? (const int*)h->d_row : (const int*)nullptr, out, idx_out, L.rv, L.ri,
+                       (const int*)L.flag);
+    return launch_check(ctx, "knn_match_blend");
 }
 
 int run_knn(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const float* prepared, int64_t N,

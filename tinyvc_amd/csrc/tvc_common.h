@@ -353,17 +353,29 @@ struct KnnSegIn {
     int col0, ncols;
 };
 int run_knn_segs(tvc_ctx*, hipStream_t, Ws&, const float* src, const KnnSegIn* in, int nin, float* out, int64_t* idx_out, int B, int T);
+// a weighted blend of M indices per row (knn.hip): in[] = the (term, row) runs over M * B * T VIRTUAL query columns, term-major - term m's
+// search of real column n is column m * B * T + n -, weights = the caller's device array [rows][M] (read by the kernels, never by the host),
+// out [B][768][T] = w_0 * mu_0 + ... in term order, idx_out (nullable) [M][B][T][4]
+int run_knn_blend(tvc_ctx*, hipStream_t, Ws&, const float* src, const KnnSegIn* in, int nin, int M, const float* weights, float* out, int64_t* idx_out,
+                  int B, int T);
+// out[i] = sum_m |weights[rows[i]][m]| * *knn_index_amax(blobs[i * M + m]): the bound of row i's blended content
+int run_knn_blend_bound(tvc_ctx*, hipStream_t, const std::vector<const float*>& blobs, const std::vector<int>& rows, int M, const float* weights, float* out);
 
 // ---- one conversion, as the entries describe it to convert_impl (api.hip) and to the ragged batch loop (ragged.hip) -----------
 // What the rows of a call search: ONE prepared index, or host tables of one per row of the caller's batch (tvc_*_multi) - never both.
+// The blend form (tvc_*_blend) is a per-row table with M terms per row: blobs / Ns are [rows][M] row-major, `weights` the device array
+// [rows][M] in the caller's row order.
 struct ConvertIndex {
     const float* blob = nullptr;               // one index for every row ...
     int64_t N = 0;
     const float* const* blobs = nullptr;       // ... or, per_row, blobs[r] / Ns[r] for the caller's row r (blob and N stay unset)
     const int64_t* Ns = nullptr;
     bool per_row = false;
-    static ConvertIndex one(const float* blob, int64_t N) { return {blob, N, nullptr, nullptr, false}; }
-    static ConvertIndex table(const float* const* blobs, const int64_t* Ns) { return {nullptr, 0, blobs, Ns, true}; }
+    int M = 0;                                 // blend: terms per row (0: no blend, one blob per row)
+    const float* weights = nullptr;            // blend: device, [rows][M]
+    static ConvertIndex one(const float* blob, int64_t N) { return {blob, N, nullptr, nullptr, false, 0, nullptr}; }
+    static ConvertIndex table(const float* const* blobs, const int64_t* Ns) { return {nullptr, 0, blobs, Ns, true, 0, nullptr}; }
+    static ConvertIndex blend(const float* const* blobs, const int64_t* Ns, int M, const float* weights) { return {nullptr, 0, blobs, Ns, true, M, weights}; }
 };
 struct ConvertCall {
     const float* wav = nullptr;                // [B][L] in, row b zero-padded behind lens[b] samples

@@ -389,6 +389,60 @@ class Engine:
                                                        _ptr(wave), B, p, n), "tvc_convert_ragged_multi_f32")
         return wave
 
+    # ---- a weighted blend of M prepared indices per row (tvc_*_blend) ----
+    def _blend_args(self, prepared, Ns, weights, B):
+        """(flat row-major [B * M] blob tensors and sizes, weights [B, M]) -> (void* [B * M], int64 [B * M], M).  The weights stay where they
+        are: a contiguous fp32 [B, M] tensor on this device that the kernels read when they run (so a captured graph follows in-place
+        changes) - anything else is refused here, never copied."""
+        _check_dev(weights, "weights", self.device)
+        if weights.dim() != 2 or weights.shape[0] != B or weights.dtype != _F32 or not weights.is_contiguous():
+            raise ValueError(f"weights must be a contiguous fp32 [B = {B}, M] tensor on the device, got {tuple(weights.shape)} {weights.dtype}")
+        M = weights.shape[1]
+        if not 1 <= M <= spec.BLEND_MAX:
+            raise ValueError(f"a blend takes 1 ... {spec.BLEND_MAX} terms per row, got {M}")
+        blobs, ns = self._table(prepared, Ns, B * M)
+        return blobs, ns, M
+
+    def knn_match_blend(self, src, prepared, Ns, weights, want_indices=False):
+        """src [B, 768, T]; term m of row b is prepared[b * M + m] (Ns likewise), weights [B, M] on the device -> matched [B, 768, T] =
+        w_0 * match_0 + w_1 * match_1 + ... in term order (, indices [M, B, T, 4]: each term's own search): tvc_knn_match_blend_f32."""
+        src = _prep(src, "source", self.device)
+        B, C, T = src.shape
+        if C != spec.SSL_DIM:
+            raise ValueError(f"source must have {spec.SSL_DIM} channels")
+        blobs, ns, M = self._blend_args(prepared, Ns, weights, B)
+        out = torch.empty_like(src)
+        idx = torch.empty(M, B, T, 4, dtype=torch.int64, device=self.device) if want_indices else None
+        p, n = self._query_ws("tvc_workspace_bytes_blend", B, T * spec.HOP, ns, M)
+        self._ok(self.lib.tvc_knn_match_blend_f32(self.ctx, self._stream(), _ptr(src), blobs, ns, M, _ptr(weights), _ptr(out), _ptr(idx), B, T, p, n),
+                 "tvc_knn_match_blend_f32")
+        return (out, idx) if want_indices else out
+
+    def convert_blend(self, wav, prepared, Ns, weights, pitch_shift, noise_angle=None, out=None):
+        """convert toward a weighted blend of M prepared indices per row (pitch_shift a float or one per row): tvc_convert_blend_f32."""
+        wav, B, L = self._rows(wav)
+        blobs, ns, M = self._blend_args(prepared, Ns, weights, B)
+        shift, shifts = self._shifts(pitch_shift, B)
+        a, seed = self._angle(noise_angle, B, L // spec.HOP)
+        wave = out if out is not None else torch.empty(B, L, dtype=_F32, device=self.device)
+        p, n = self._query_ws("tvc_workspace_bytes_blend", B, L, ns, M)
+        self._ok(self.lib.tvc_convert_blend_f32(self.ctx, self._stream(), _ptr(wav), blobs, ns, M, _ptr(weights), shift, shifts, _ptr(a), seed, _ptr(wave),
+                                                B, L, p, n), "tvc_convert_blend_f32")
+        return wave
+
+    def convert_ragged_blend(self, wav, lengths, prepared, Ns, weights, pitch_shift, noise_angle=None):
+        """convert_ragged toward a weighted blend of M prepared indices per row: tvc_convert_ragged_blend_f32."""
+        wav, B, Lmax = self._rows(wav, ragged=True)
+        lens = self._lens(lengths, B)
+        blobs, ns, M = self._blend_args(prepared, Ns, weights, B)
+        shift, shifts = self._shifts(pitch_shift, B)
+        a, seed = self._angle(noise_angle, B, Lmax // spec.HOP)
+        p, n = self._query_ws("tvc_workspace_bytes_ragged_blend", B, Lmax, lens, ns, M)
+        wave = torch.empty(B, Lmax, dtype=_F32, device=self.device)
+        self._ok(self.lib.tvc_convert_ragged_blend_f32(self.ctx, self._stream(), _ptr(wav), Lmax, lens, blobs, ns, M, _ptr(weights), shift, shifts, _ptr(a),
+                                                       seed, _ptr(wave), B, p, n), "tvc_convert_ragged_blend_f32")
+        return wave
+
     # ---- index-sharded match (one prepared index shard per rank; merged by parallel.match_features_sharded) ----
     METRICS = {"cos": 0, "IP": 1, "L2": 2}
 

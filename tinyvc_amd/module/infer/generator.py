@@ -5,7 +5,7 @@ import torch
 from .. import utils
 from .._base import HipModule
 from ..tinyvc import Decoder, Encoder
-from ..tinyvc.feature_retrieval import check_references, prepare_reference, prepare_references
+from ..tinyvc.feature_retrieval import Blend, check_blend, check_references, prepare_reference, prepare_references
 
 
 def _per_row_shift(pitch_shift, B):
@@ -73,8 +73,13 @@ class Generator(HipModule):
         to a common length would change the results); row b of the result holds it, zeros behind.
         One index per row: tgt [B, 768, N] (the reference's form) or a list of B [1, 768, N_b] tensors (extension: fp32 or fp16,
         any N_b), equal or ragged batches, in one call (tvc_convert_multi_f32 / tvc_convert_ragged_multi_f32: row b equals its own
-        B = 1 conversion against tgt[b]).  `pitch_shift` (extension): a float, or a sequence / 1-D tensor of one shift per row."""
+        B = 1 conversion against tgt[b]).  `pitch_shift` (extension): a float, or a sequence / 1-D tensor of one shift per row.
+        A weighted blend of indices (extension): tgt = feature_retrieval.Blend(terms, weights) converts every frame toward
+        w_0 * match_0 + w_1 * match_1 + ... in ONE call (tvc_convert_blend_f32 / tvc_convert_ragged_blend_f32), equal or ragged batches,
+        scalar or per-row shifts; the weights are read on the device when the kernels run."""
         B = wf.shape[0] if wf.dim() == 2 else 1
+        if isinstance(tgt, Blend):
+            return self._convert_blend(wf, tgt, pitch_shift, noise_angle, lengths, B)
         multi = isinstance(tgt, (list, tuple)) or (isinstance(tgt, torch.Tensor) and tgt.dim() == 3 and tgt.shape[0] != 1)
         if multi:
             check_references(tgt, B)           # malformed tables / shift lists are refused before any engine or device work
@@ -107,3 +112,22 @@ class Generator(HipModule):
         if lens is not None:
             return eng.convert_ragged_multi(wf, lens, blobs, ns, shift, noise_angle)
         return eng.convert_multi(wf, blobs, ns, shift, noise_angle)
+
+    def _convert_blend(self, wf, blend, pitch_shift, noise_angle, lengths, B):
+        check_blend(blend.terms, blend._given, B)      # malformed blends / shift lists are refused before any engine or device work
+        shifts = _per_row_shift(pitch_shift, B)
+        wf = utils.autopad_waveform(self._input_device(wf))
+        eng = self.engine(wf.device)
+        B, L = wf.shape
+        if noise_angle is not None:
+            noise_angle = self._input_device(noise_angle)
+        lens = None
+        if lengths is not None:
+            lens = [-(-int(n) // 480) * 480 for n in lengths]
+            if len(lens) != B or max(lens) > L or min(lens) <= 960:
+                raise ValueError("lengths: one entry per row, each in (960, L]")
+        blobs, ns, w = blend.resolve(B, wf.device, self._input_device)
+        shift = shifts if shifts is not None else float(pitch_shift)
+        if lens is not None:
+            return eng.convert_ragged_blend(wf, lens, blobs, ns, w, shift, noise_angle)
+        return eng.convert_blend(wf, blobs, ns, w, shift, noise_angle)

@@ -5,6 +5,7 @@ the lag arg-max kept on the device."""
 import numpy as np
 import torch
 
+from ..tinyvc.feature_retrieval import Blend
 from .generator import Generator
 
 
@@ -16,7 +17,8 @@ def _fade_windows(crossfade_size, device):
 
 class BatchedStreamInfer:
     """`target`: one index for every stream ([1, 768, N]) or one per stream ([S, 768, N], or a list of S [1, 768, N_s] tensors), prepared
-    once and cached on those tensors; `pitch_shift`: a float or one per stream."""
+    once and cached on those tensors - or a feature_retrieval.Blend of several (its weights are read on the device when a block runs:
+    `blend.weights.copy_(...)` between blocks moves the mix without a new graph capture); `pitch_shift`: a float or one per stream."""
 
     def __init__(self, generator: Generator, n_streams=1, target=None, pitch_shift=0., device=None,
                  block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False):
@@ -69,12 +71,16 @@ class BatchedStreamInfer:
         eng = self.generator.engine(self.device)          # re-packs the weights first if a parameter changed
         ws, tgt = eng._ws, self.target
         tgts = tgt if isinstance(tgt, (list, tuple)) else [tgt]      # one index per stream: every blob's tensor
+        wkey = 0
+        if isinstance(tgt, Blend):      # every term's tensors, and WHERE the weights live - not their version or values: the kernels read them at replay
+            tgts = tgt.term_tensors()
+            wkey = tgt.resolve(self.n_streams, self.device, self.generator._input_device)[2].data_ptr()
         ps = self.pitch_shift
         if isinstance(ps, torch.Tensor):
             ps = ps.detach().cpu().reshape(-1).tolist()
         shifts = tuple(float(x) for x in ps) if hasattr(ps, "__len__") else float(ps)
         return (eng.weights_key, ws.data_ptr() if ws is not None else 0, ws.numel() if ws is not None else 0,
-                tuple((id(t), t._version, t.data_ptr()) for t in tgts), shifts, bool(self.use_phase_vocoder))
+                tuple((id(t), t._version, t.data_ptr()) for t in tgts), wkey, shifts, bool(self.use_phase_vocoder))
 
     @torch.no_grad()
     def audio_callback(self, blocks, noise_angle=None):

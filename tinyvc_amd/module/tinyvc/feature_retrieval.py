@@ -2,6 +2,7 @@
 top-k kernel of csrc/knn.hip."""
 import torch
 
+from ... import spec
 from ...engine import default_engine
 
 
@@ -120,6 +121,162 @@ def check_references(tgt, B=None):
     if B is not None and n != B:
         raise ValueError(f"{n} target indices for a batch of {B}")
     return n
+
+
+BLEND_MAX = spec.BLEND_MAX      # terms per row (TVC_BLEND_MAX)
+
+
+def _term_rows(term, m):
+    """rows a blend term speaks for: None = one shared index for every row ([1, 768, N]), else B"""
+    if not isinstance(term, (torch.Tensor, list, tuple)):
+        raise ValueError(f"blend term {m}: a [1 or B, 768, N] tensor or a list of [1, 768, N_b] tensors, got {type(term).__name__}")
+    n = check_references(term)
+    if isinstance(term, torch.Tensor):
+        if term.dtype not in (torch.float32, torch.float16):
+            raise ValueError(f"blend term {m} must be fp32 or fp16, got {term.dtype}")
+        return None if n == 1 else n
+    return n
+
+
+def check_blend(terms, weights, B=None):
+    """Shape check of a blend, on the host (no engine, no device work; beside check_references): `terms` = 1 ... 4 targets, each in any form
+    `convert` takes as tgt (a shared [1, 768, N], a [B, 768, N] tensor or a list of B [1, 768, N_b], fp32 or fp16); `weights` = M floats, B rows
+    of M floats, or a tensor [M] or [B, M].  Returns (M, rows) - rows = the batch the blend is made for, None when every term is shared and the weights are
+    per term (it then fits any batch); raises ValueError when the form is malformed or the row counts disagree (with each other or with B)."""
+    if not isinstance(terms, (list, tuple)):
+        raise ValueError(f"blend terms: a list of targets, got {type(terms).__name__}")
+    M = len(terms)
+    if not 1 <= M <= BLEND_MAX:
+        raise ValueError(f"a blend takes 1 ... {BLEND_MAX} terms, got {M}")
+    rows = B
+    for m, t in enumerate(terms):
+        n = _term_rows(t, m)
+        if n is not None:
+            if rows is not None and n != rows:
+                raise ValueError(f"blend term {m} holds {n} indices for a batch of {rows}")
+            rows = n
+    if not isinstance(weights, torch.Tensor):      # floats, or nested rows of floats
+        try:
+            weights = torch.as_tensor(weights, dtype=torch.float32)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"blend weights: {M} floats, or a tensor [M] or [B, M], got {type(weights).__name__}") from None
+    if weights.dim() == 1:
+        ok = weights.shape[0] == M
+    else:
+        ok = weights.dim() == 2 and weights.shape[1] == M and (rows is None or weights.shape[0] == rows)
+        if ok:
+            rows = weights.shape[0]
+    if not ok:
+        raise ValueError(f"blend weights: [M = {M}] or [B{'' if rows is None else ' = ' + str(rows)}, M = {M}], got {tuple(weights.shape)}")
+    if not weights.dtype.is_floating_point:
+        raise ValueError(f"blend weights must be floating point, got {weights.dtype}")
+    return M, rows
+
+
+class Blend:
+    """A weighted blend of speaker indices as a conversion target: out = w_0 * match(src, terms[0]) + w_1 * match(src, terms[1]) + ...
+    (the kNN-VC voice morph; weights may be negative or zero and are not normalised).  `terms` and `weights` as check_blend takes them.
+    A weights tensor that is already on the device, fp32, contiguous and [B, M] is used IN PLACE: the kernels read it when they run, so
+    `blend.weights.copy_(...)` takes effect on the next call - and on the next replay of a captured stream graph, without a new capture.
+    Anything else is expanded once into a device tensor the object owns (`.weights`; made at construction when the rows and the device are
+    known, else at the first use).  The terms' prepared blobs ride on the caller's tensors (prepare_reference / prepare_references): nothing
+    is prepared twice.  `terms` is a plain list: replacing an entry takes effect on the next call."""
+
+    def __init__(self, terms, weights):
+        self.M, self.rows = check_blend(terms, weights)
+        self.terms = list(terms)
+        self._given = weights
+        self.weights = None
+        live = (isinstance(weights, torch.Tensor) and weights.dim() == 2 and weights.device.type == "cuda" and weights.dtype == torch.float32
+                and weights.is_contiguous())
+        if live:
+            self.weights = weights
+        elif self.rows is not None:
+            first = self.terms[0][0] if isinstance(self.terms[0], (list, tuple)) else self.terms[0]
+            dev = weights.device if isinstance(weights, torch.Tensor) and weights.device.type == "cuda" else first.device
+            if dev.type == "cuda":
+                self.weights = self._expand(self.rows, dev)
+
+    def _expand(self, B, device):
+        w = torch.as_tensor(self._given, dtype=torch.float32).detach().to("cpu")
+        if w.dim() == 1:
+            w = w[None].expand(B, self.M)
+        return w.contiguous().to(device)
+
+    def term_tensors(self):
+        """every index tensor the blend holds, in term order (what a captured graph keys on)"""
+        out = []
+        for t in self.terms:
+            out.extend(t if isinstance(t, (list, tuple)) else [t])
+        return out
+
+    def resolve(self, B, device, to_device=None):
+        """-> (blobs [B * M], Ns [B * M], weights [B, M] on `device`): the row-major tables of a batch of B rows.  Host checks first;
+        `to_device` (optional) maps every index tensor to the device (Generator._input_device)."""
+        check_blend(self.terms, self._given, B)
+        device = torch.device(device)
+        w = self.weights
+        if w is None or w.shape[0] != B or w.device != device:
+            if w is not None and w is self._given:
+                raise ValueError(f"blend weights live on {w.device}, the batch on {device}")
+            w = self.weights = self._expand(B, device)
+        move = to_device if to_device is not None else (lambda t: t)
+        cols = []
+        for t in self.terms:
+            if isinstance(t, (list, tuple)):
+                cols.append(prepare_references([move(x) for x in t]))
+            elif t.shape[0] == 1:
+                blob, n = prepare_reference(move(t))
+                cols.append(([blob] * B, [n] * B))
+            else:
+                cols.append(prepare_references(move(t)))
+        blobs = [cols[m][0][b] for b in range(B) for m in range(self.M)]
+        ns = [cols[m][1][b] for b in range(B) for m in range(self.M)]
+        return blobs, ns, w
+
+
+def parse_blend(items):
+    """The entry scripts' `--blend PATH=W [PATH=W ...]`: 1 ... 4 index files and their weights -> (paths, weights).  ValueError for a
+    missing or malformed weight, an empty path or too many entries."""
+    items = list(items)
+    if not 1 <= len(items) <= BLEND_MAX:
+        raise ValueError(f"1 ... {BLEND_MAX} PATH=WEIGHT entries, got {len(items)}")
+    paths, weights = [], []
+    for it in items:
+        path, sep, w = str(it).rpartition("=")
+        if not sep or not path:
+            raise ValueError(f"{it!r}: expected PATH=WEIGHT")
+        try:
+            weights.append(float(w))
+        except ValueError:
+            raise ValueError(f"{it!r}: the weight {w!r} is not a number") from None
+        paths.append(path)
+    return paths, weights
+
+
+def add_blend_argument(parser):
+    """`--blend PATH=W [PATH=W ...]` for an entry script's argparse parser: args.blend = (paths, weights) or None; a malformed list is
+    refused at parse time (parse_blend)."""
+    import argparse
+
+    class BlendArg(argparse.Action):
+        def __call__(self, parser_, namespace, values, option_string=None):
+            try:
+                setattr(namespace, self.dest, parse_blend(values))
+            except ValueError as e:
+                parser_.error(f"--blend: {e}")
+
+    parser.add_argument("--blend", nargs="+", metavar="PATH=W", default=None, action=BlendArg,
+                        help="convert toward a weighted blend of up to four index files (index.pt=WEIGHT ...) instead of -idx / -t")
+
+
+@torch.no_grad()
+def match_features_blend(source, blend, return_indices=False):
+    """source [B, 768, T], blend = Blend(terms, weights) -> [B, 768, T] = sum_m w[b][m] * match_features(source[b], term m's index of row b)
+    in term order, one call (tvc_knn_match_blend_f32; k = 4, 'cos'); return_indices: also [M, B, T, 4], each term's own search."""
+    eng = default_engine(source.device)
+    blobs, ns, w = blend.resolve(source.shape[0], source.device)
+    return eng.knn_match_blend(source, blobs, ns, w, want_indices=return_indices)
 
 
 def prepare_references(tgt):

@@ -26,6 +26,7 @@ SRC_LAYERS = 3
 NUM_HARMONICS = 14             # oscillator emits NUM_HARMONICS + 1 sinusoids
 FILTER_CHANNELS = (384, 192, 96, 48, 24)
 FILTER_FACTORS = (2, 3, 4, 4, 5)
+BLEND_MAX = 4                  # terms of a weighted blend of speaker indices (TVC_BLEND_MAX)
 
 
 def _conv(d, name, cout, cin, k, groups=1):
