@@ -53,6 +53,33 @@ def rel_rms(a, ref):
     return rms(torch.as_tensor(a).double() - torch.as_tensor(ref).double()) / max(rms(ref), 1e-30)
 
 
+def window_starts(n, width=32):
+    """First columns of the windows `window_errors` measures on a length-n axis: `width` columns every `width // 2`, plus one window
+    that ends on the last column; one window over everything when n <= width."""
+    if n <= width:
+        return [0]
+    starts = list(range(0, n - width + 1, max(width // 2, 1)))
+    if starts[-1] != n - width:
+        starts.append(n - width)
+    return starts
+
+
+def window_errors(x, truth, width=32):
+    """[B, C, len] against an fp64 `truth` -> [B, windows] (fp64): per row b and window (window_starts), the rms over (C, window) of
+    x - truth divided by the rms of truth[b] over the WHOLE row.  A whole-tensor relative rms dilutes an error confined to the last columns
+    of a tile by sqrt(columns / len) (1e-4 in two of 3096 columns reads 2.5e-6); here those columns sit in a full-width window of their own."""
+    truth = torch.as_tensor(truth)
+    assert truth.dtype == torch.float64 and truth.dim() == 3 and tuple(x.shape) == tuple(truth.shape)
+    d = torch.as_tensor(x).double() - truth
+    B, C, n = truth.shape
+    cs = torch.cat([torch.zeros(B, 1, dtype=torch.float64), (d * d).sum(dim=1).cumsum(dim=1)], dim=1)      # [B, n + 1]
+    st = torch.tensor(window_starts(n, width))
+    w = min(width, n)
+    num = torch.sqrt((cs[:, st + w] - cs[:, st]).clamp_min(0.0) / (C * w))
+    den = torch.sqrt((truth * truth).mean(dim=(1, 2))).clamp_min(1e-30)
+    return num / den[:, None]
+
+
 def stage(g, name):
     """(tensor, time stride) of a stored stage output.  Round-1 fixtures keep the encoder-side tensors whole and
     decimate the full-rate ones by `decim`; the headline-length fixtures (convert_cfg*) store `<name>_d` with its own
