@@ -24,6 +24,10 @@ bytes as the default clip-by-clip run with the same `--seed`, without a host rou
 cosine assignment, raw-mean update, `--compact-iters` rounds, started from K vectors drawn from the same generator) instead of
 truncating further: `-size` then sets how much of the speaker's material the centroids summarise.  `--compact-snap` replaces every
 centroid by its nearest real frame.  Without `--compact` the file is what it always was.
+
+Beside the index every route writes `<output>.f0.pt`: {"median_hz", "voiced"}, the speaker's pitch register - the lower median of the voiced
+f0 of every frame of the clips the index was drawn from (feature_retrieval.pitch_register, on the device) - which `infer.py --auto-pitch`
+and `infer_streaming.py --auto-pitch-from` aim at.  `index.pt` itself keeps the reference's format byte for byte.
 """
 import argparse
 import glob
@@ -35,17 +39,20 @@ import torch
 from tinyvc_amd import audio_io, parallel
 from tinyvc_amd.module import utils
 from tinyvc_amd.module.tinyvc import Encoder
-from tinyvc_amd.module.tinyvc.feature_retrieval import compact_index, index_columns, index_from_columns
+from tinyvc_amd.module.tinyvc.feature_retrieval import compact_index, index_columns, index_from_columns, pitch_register, save_register, sidecar_path
 
 SAMPLE_RATE = 24000
 
 
-def encode_clip(enc, device, path, stride):
-    """[1, 768, ceil(T / stride)] on the CPU: the encoder's features of one clip, every `stride`-th frame (extract_index.py:47-52)."""
+def encode_clip(enc, device, path, stride, f0_out=None):
+    """[1, 768, ceil(T / stride)] on the CPU: the encoder's features of one clip, every `stride`-th frame (extract_index.py:47-52).
+    f0_out (a list): the clip's f0 [T], all frames, is appended to it and stays on the device."""
     wf, sr = audio_io.load(path)
     wf = enc.engine(device).resample(wf.to(device), sr, SAMPLE_RATE).mean(dim=0, keepdim=True)
     spec = utils.spectrogram(utils.autopad_waveform(wf), enc.n_fft, enc.hop_size)
-    z, _f0 = enc.infer(spec)
+    z, f0 = enc.infer(spec)
+    if f0_out is not None:
+        f0_out.append(f0.reshape(-1))
     return z.cpu()[:, :, ::stride]
 
 
@@ -99,7 +106,38 @@ def sharded_features(cols, order, size, world, rank, encode, device, group=None)
     return feats
 
 
-def batched_index(enc, device, files, order, stride, size, gen, half, batch_frames):
+def register_of(f0_parts):
+    """the pitch register of every frame in f0_parts (device tensors) as one row"""
+    f0 = f0_parts[0] if len(f0_parts) == 1 else torch.cat(f0_parts)
+    return pitch_register(f0, [f0.numel()])
+
+
+def gathered_register(f0_parts, world, rank, device, group=None):
+    """The sharded run's register: every rank's f0 gathered on rank 0 (a median does not care for the order) and measured there as one row;
+    None on the other ranks, and on rank 0 when the gathered f0 does not fit (the sidecar is then left out)."""
+    import torch.distributed as dist
+    local = torch.cat(f0_parts) if f0_parts else torch.zeros(0, device=device)
+    n = torch.tensor([local.numel()], dtype=torch.int64, device=device)
+    sizes = [torch.zeros_like(n) for _ in range(world)]
+    dist.all_gather(sizes, n, group=group)
+    sizes = [int(x.item()) for x in sizes]
+    try:
+        buf = torch.zeros(max(max(sizes), 1), device=device)
+        buf[:local.numel()] = local
+        parts = [torch.empty_like(buf) for _ in range(world)] if rank == 0 else None
+    except torch.cuda.OutOfMemoryError:
+        buf = parts = None
+    ok = torch.tensor([0 if buf is None else 1], dtype=torch.int64, device=device)
+    dist.all_reduce(ok, op=dist.ReduceOp.MIN, group=group)
+    if int(ok.item()) == 0:
+        return None
+    dist.gather(buf, parts, dst=0, group=group)
+    if rank != 0:
+        return None
+    return register_of([parts[r][:sizes[r]] for r in range(world)])
+
+
+def batched_index(enc, device, files, order, stride, size, gen, half, batch_frames, f0_out=None):
     """The default loop's index ([1, 768, size] on the CPU, the same bytes) with the clips encoded in ragged calls of at most `batch_frames`
     frames (a longer clip is a call of its own) and the selection done by one gather on the device."""
     eng = enc.engine(device)
@@ -112,7 +150,10 @@ def batched_index(enc, device, files, order, stride, size, gen, half, batch_fram
         wf = torch.zeros(len(group), max(c.numel() for c in group), device=device)
         for r, c in enumerate(group):
             wf[r, :c.numel()] = c
-        feats.append(eng.encode_ragged(wf, [c.numel() for c in group])[0])
+        ssl, f0, _pre = eng.encode_ragged(wf, [c.numel() for c in group])
+        feats.append(ssl)
+        if f0_out is not None:
+            f0_out.append(f0)
         group.clear()
 
     for i in order:
@@ -205,17 +246,19 @@ def main(argv=None):
     if not sharded:
         gen = torch.Generator().manual_seed(args.seed) if args.seed is not None else None
         order = torch.randperm(len(files), generator=gen).tolist()      # DataLoader(shuffle=True) in the reference
+        f0s = []
         if args.batch_frames > 0:
-            tgt = batched_index(enc, device, files, order, args.stride, args.size, gen, build_half, args.batch_frames)
+            tgt = batched_index(enc, device, files, order, args.stride, args.size, gen, build_half, args.batch_frames, f0s)
         else:
             feats, total = [], 0
             for i in order:
-                z = encode_clip(enc, device, files[i], args.stride)
+                z = encode_clip(enc, device, files[i], args.stride, f0s)
                 feats.append(z)
                 total += z.shape[2]
                 if total > args.size:
                     break
             tgt = assemble(feats, args.size, gen, build_half)
+        register = register_of(f0s)
     else:
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -236,8 +279,10 @@ def main(argv=None):
             order = torch.randperm(len(files), generator=gen).tolist()
             eng = enc.engine(device) if device.type == "cuda" else None
             cols = [clip_columns(f, args.stride, eng) for f in files]
-            feats = sharded_features(cols, order, args.size, world, rank, lambda i: encode_clip(enc, device, files[i], args.stride), device)
+            f0s = []
+            feats = sharded_features(cols, order, args.size, world, rank, lambda i: encode_clip(enc, device, files[i], args.stride, f0s), device)
             tgt = assemble(feats, args.size, gen, build_half) if rank == 0 else None
+            register = gathered_register(f0s, world, rank, device) if device.type == "cuda" else None
             dist.barrier()
         finally:
             if own_group:
@@ -251,6 +296,11 @@ def main(argv=None):
     print(f"Extracted {tgt.shape[2]} vectors")
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     torch.save(tgt, args.output)
+    if register is not None:
+        save_register(args.output, register)
+        print(f"Pitch register {float(register.median_hz[0]):.1f} Hz over {int(register.voiced[0])} voiced frames -> {sidecar_path(args.output)}")
+    else:
+        print(f"The clips' f0 could not be gathered on rank 0: no {sidecar_path(args.output)} written")
     return 0
 
 

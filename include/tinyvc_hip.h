@@ -378,6 +378,42 @@ int tvc_convert_ragged_blend_f32(tvc_ctx* ctx, void* stream, const float* wav, i
                                  const float* pitch_shifts, const float* noise_angle, uint64_t seed, float* wave, int B, void* ws,
                                  size_t ws_bytes);
 
+/* automatic pitch: the target speaker's register, matched on the device ------------------------ */
+/* The kNN match replaces timbre only: every frame of the source's f0 reaches the decoder as it is, shifted by a number of semitones the
+ * caller has to guess.  "Auto pitch" moves the source's median f0 onto the target's.  The source's f0 exists only inside the fused call,
+ * behind the encoder, so the shift is found there, by one launch, without a host synchronisation (capturable).
+ *   - register of a row of f0: the LOWER median of its voiced frames, torch.median(row[row > 0]) - the element of rank (n_voiced - 1) / 2
+ *     among the values > 0; zeros, negatives and NaN are unvoiced.  An order statistic of fp32 values (a radix select over the bit
+ *     pattern, one workgroup per row): exact and bit-defined, no floating-point sum, independent of grid and order.  A row without a voiced
+ *     frame reports median 0 and voiced 0.
+ *   - shift[b] = offset[b] + 12 * log2(target_f0[b] / median[b]), evaluated in fp64 and rounded once to fp32; offset[b] = pitch_shifts[b],
+ *     or pitch_shift when pitch_shifts is NULL (HOST values: they travel as kernel arguments).  shift[b] = offset[b] exactly when the row has
+ *     no voiced frame, target_f0[b] <= 0 or NaN, or target_f0 is NULL.
+ *   - f0_shifted[n] = tvc_shift_frequency_f32(f0[n], shift[b]) for every column n of row b, same arithmetic, same launch.
+ * tvc_pitch_match_f32, the stage call: f0 (device) holds the rows as runs of columns, row b = [row_start[b], row_start[b + 1]) with row_start
+ * a HOST array of rows + 1 ascending column numbers below 2^31 (an equal batch [B][T]: b * T; a packed ragged encode: its prefix; one long row:
+ * {0, S}; an empty row is unvoiced).  target_f0 (device, rows floats in Hz) may be NULL: the call then only measures.  Outputs (device, each
+ * may be NULL, not all): median_out [rows], voiced_out [rows] int32, shift_out [rows], f0_shifted (f0's layout; columns outside every row
+ * are not written).  Rows of 28 frames and of millions go through the same kernel; no workspace.
+ * tvc_convert_auto_f32 / tvc_convert_ragged_auto_f32: the table form of the blend entries - prepared / N are HOST arrays [B][M], weights the
+ * DEVICE array [B][M], or NULL with M = 1: the multi-index call - with target_f0 (device, B registers in Hz, read when the kernels run: a
+ * captured graph follows in-place changes) and shift_out (device, B floats, nullable: the shifts applied).  pitch_shift / pitch_shifts become
+ * the offset on top of the automatic shift.  Row b is bit-identical to the multi-index / blend call given shift_out[b] as its host shift.
+ * Everything else - checks, lens, noise_angle / seed, capture - as in those calls.  Workspace: tvc_workspace_bytes_auto / _ragged_auto
+ * (N: the host table of B * M sizes). */
+int tvc_pitch_match_f32(tvc_ctx* ctx, void* stream, const float* f0, const int64_t* row_start, int rows, const float* target_f0,
+                        float pitch_shift, const float* pitch_shifts, float* median_out, int32_t* voiced_out, float* shift_out,
+                        float* f0_shifted);
+int tvc_workspace_bytes_auto(tvc_ctx* ctx, int B, int64_t L, const int64_t* N, int M, size_t* out_bytes);
+int tvc_convert_auto_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M,
+                         const float* weights, const float* target_f0, float pitch_shift, const float* pitch_shifts, float* shift_out,
+                         const float* noise_angle, uint64_t seed, float* wave, int B, int64_t L, void* ws, size_t ws_bytes);
+int tvc_workspace_bytes_ragged_auto(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, const int64_t* N, int M, size_t* out_bytes);
+int tvc_convert_ragged_auto_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens,
+                                const float* const* prepared, const int64_t* N, int M, const float* weights, const float* target_f0,
+                                float pitch_shift, const float* pitch_shifts, float* shift_out, const float* noise_angle, uint64_t seed,
+                                float* wave, int B, void* ws, size_t ws_bytes);
+
 /* streaming tail -------------------------------------------------------------------------- */
 /* StreamInfer.audio_callback after convert (reference module/infer/stream.py:74-95), batched over
  * S streams: y [S, Ly] converted buffers; sola_buf [S,1920] in/out; fade_in [1920] = the sin^2

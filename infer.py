@@ -38,7 +38,7 @@ import torch
 from tinyvc_amd import audio_io, parallel, spec
 from tinyvc_amd.module.infer import Generator
 from tinyvc_amd.module.tinyvc import Blend, Decoder, Encoder
-from tinyvc_amd.module.tinyvc.feature_retrieval import add_blend_argument
+from tinyvc_amd.module.tinyvc.feature_retrieval import add_auto_pitch_argument, add_blend_argument, attach_register, pitch_register
 
 SAMPLE_RATE = 24000
 
@@ -55,6 +55,7 @@ def build_parser():
     add_blend_argument(p)      # --blend PATH=W [PATH=W ...] -> args.blend = (paths, weights)
     p.add_argument("-d", "--device", default="cuda")
     p.add_argument("-p", "--pitch-shift", default=0.0, type=float)
+    add_auto_pitch_argument(p)      # --auto-pitch: every file's median f0 onto the target's register; -p stays, as the offset
     p.add_argument("-c", "--chunk-size", default=1920, type=int)
     p.add_argument("-b", "--buffer-size", default=4, type=int)
     p.add_argument("-nc", "--no-chunking", default=False, type=bool)
@@ -103,9 +104,11 @@ def load_target(gen, args, device):
     if args.index == "NONE":
         wf, sr = audio_io.load(args.target)
         wf = gen.engine(device).resample(wf.to(device), sr, SAMPLE_RATE)
-        tgt, _f0 = gen.encode(wf.mean(dim=0, keepdim=True) if wf.shape[0] > 1 else wf)
+        tgt, f0 = gen.encode(wf.mean(dim=0, keepdim=True) if wf.shape[0] > 1 else wf)
+        tgt.pitch_register = pitch_register(f0)      # the target recording's own register, from the encode that runs anyway
         return tgt
-    return torch.load(args.index, map_location="cpu").to(device)     # fp32 [1,768,N], or half: fp16 index storage
+    # fp32 [1,768,N], or half: fp16 index storage; the register of <index>.f0.pt rides on the tensor when the file exists
+    return attach_register(torch.load(args.index, map_location="cpu").to(device), args.index)
 
 
 SOLA_MAX_LATENCY = 1920 + 1920 + 3840     # cross-fade + search range + last delay: a block's output lags its input by this minus the SOLA lag (stream.py:76-83)
@@ -159,6 +162,15 @@ def main(argv=None, world=None, rank=None, local_rank=None):
         torch.cuda.set_device(device)
     gen = load_generator(args.encoder_path, args.decoder_path, device)
     tgt = load_target(gen, args, device)
+    auto = None
+    if args.auto_pitch:
+        if args.blend is not None:
+            sys.exit("infer.py: --auto-pitch with --blend: a blend has no register of its own (its weights are the caller's); use -p")
+        if args.chunked and not args.no_chunking:
+            sys.exit("infer.py: --auto-pitch converts files whole; with --chunked use -p (a stream's register: infer_streaming.py --auto-pitch-from)")
+        if getattr(tgt, "pitch_register", None) is None:
+            sys.exit(f"infer.py: --auto-pitch: no pitch register beside {args.index} (extract_index.py writes <index>.f0.pt)")
+        auto = True
     os.makedirs(args.outputs, exist_ok=True)
 
     paths = []
@@ -227,9 +239,9 @@ def main(argv=None, world=None, rank=None, local_rank=None):
                     f = -(-lengths[i] // 480)
                     angle[r, :, :f] = file_angle(gen, device, args.seed, jobs[i][0], f)[0]
             if len(set(lens)) == 1:
-                out = gen.convert(batch[:, :lens[0]], tgt, args.pitch_shift, noise_angle=angle).cpu()
+                out = gen.convert(batch[:, :lens[0]], tgt, args.pitch_shift, noise_angle=angle, auto_pitch=auto).cpu()
             else:
-                out = gen.convert(batch, tgt, args.pitch_shift, noise_angle=angle, lengths=lens).cpu()
+                out = gen.convert(batch, tgt, args.pitch_shift, noise_angle=angle, lengths=lens, auto_pitch=auto).cpu()
             for r, i in enumerate(rows):
                 outs[i] = out[r, :-(-lengths[i] // 480) * 480]
             del batch, out

@@ -10,6 +10,10 @@ playback loop.  GPU nodes have neither, so the same loop can be driven from file
 
 `--blend PATH=W [PATH=W ...]` (extension) takes the place of `-idx` / `-t`: a weighted blend of up to four index files.
 
+`--auto-pitch-from calib.wav` (extension) measures the speaker's pitch register ONCE from a calibration recording (the lower median of its
+voiced f0, on the device) and fixes the session's pitch shift at -p + 12 log2(target register / speaker register); the target's register
+comes from the index's `.f0.pt` sidecar (extract_index.py) or from the `-t` recording.  The shift does not move during the session.
+
 `--streams S` feeds S copies of the input as S concurrent streams through one BatchedStreamInfer
 (one batched convert + one SOLA launch per block) and reports the p50 / p95 block latency against the
 real-time budget (chunk / 24 kHz = 80 ms for the default 1920-sample chunk).
@@ -24,7 +28,7 @@ import torch
 from tinyvc_amd import audio_io
 from tinyvc_amd.module.infer import BatchedStreamInfer, Generator
 from tinyvc_amd.module.tinyvc import Blend, Decoder, Encoder
-from tinyvc_amd.module.tinyvc.feature_retrieval import add_blend_argument
+from tinyvc_amd.module.tinyvc.feature_retrieval import add_blend_argument, attach_register, pitch_register, semitones_between
 
 
 def build_parser():
@@ -37,6 +41,8 @@ def build_parser():
     p.add_argument("-idx", "--index", default="NONE")
     p.add_argument("-p", "--pitch-shift", default=0, type=float)
     p.add_argument("-t", "--target", default="target.wav")
+    p.add_argument("--auto-pitch-from", default=None, metavar="WAV",
+                   help="measure the speaker's median f0 once from this recording and fix the session's shift at -p + the semitones onto the target's register")
     add_blend_argument(p)      # --blend PATH=W [PATH=W ...] -> args.blend = (paths, weights)
     p.add_argument("-c", "--chunk", default=1920, type=int)
     p.add_argument("-e", "--extra", default=3840, type=int)
@@ -72,17 +78,33 @@ def main(argv=None):
     dec.load_state_dict(torch.load(args.decoder_path, map_location="cpu"))
     gen = Generator(enc.eval(), dec.eval()).to(device)
     S = max(1, args.streams)
-    stream = BatchedStreamInfer(gen, n_streams=S, pitch_shift=args.pitch_shift, block_size=args.chunk, device=device,
-                                extra_size=args.extra, f0_estimation=args.f0_estimation)
+    if args.auto_pitch_from is not None and args.blend is not None:
+        sys.exit("infer_streaming.py: --auto-pitch-from with --blend: a blend has no register of its own; use -p")
     if args.blend is not None:      # a weighted blend of index files in place of -idx / -t; every stream takes the same mix
         paths, weights = args.blend
         tgt = Blend([torch.load(p_, map_location="cpu").to(device) for p_ in paths], weights)
     elif args.index == "NONE":
         wf, sr = audio_io.load(args.target)
         wf = gen.engine(device).resample(wf.to(device), sr, 24000)
-        tgt, _ = gen.encode(wf.mean(dim=0, keepdim=True))
+        tgt, f0 = gen.encode(wf.mean(dim=0, keepdim=True))
+        tgt.pitch_register = pitch_register(f0)
     else:
-        tgt = torch.load(args.index, map_location="cpu").to(device)
+        tgt = attach_register(torch.load(args.index, map_location="cpu").to(device), args.index)
+    pitch_shift = args.pitch_shift
+    if args.auto_pitch_from is not None:      # one measurement, one host read, before the session starts
+        reg = getattr(tgt, "pitch_register", None)
+        if reg is None:
+            sys.exit(f"infer_streaming.py: --auto-pitch-from: no pitch register beside {args.index} (extract_index.py writes <index>.f0.pt)")
+        wf, sr = audio_io.load(args.auto_pitch_from)
+        wf = gen.engine(device).resample(wf.to(device), sr, 24000)
+        own = pitch_register(gen.encode(wf.mean(dim=0, keepdim=True))[1])
+        if int(own.voiced[0]) == 0:
+            sys.exit(f"infer_streaming.py: --auto-pitch-from: no voiced frame in {args.auto_pitch_from}")
+        auto = semitones_between(float(own.median_hz[0]), float(reg.median_hz[0]))
+        pitch_shift += auto
+        print(f"Pitch register {float(own.median_hz[0]):.1f} Hz -> {float(reg.median_hz[0]):.1f} Hz: {auto:+.2f} semitones, session shift {pitch_shift:+.2f}")
+    stream = BatchedStreamInfer(gen, n_streams=S, pitch_shift=pitch_shift, block_size=args.chunk, device=device,
+                                extra_size=args.extra, f0_estimation=args.f0_estimation)
     stream.target = tgt
     stream.init_buffer()
 

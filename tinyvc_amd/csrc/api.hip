@@ -220,7 +220,8 @@ int tvc::convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const ConvertCall& c)
     // A blend (ix.M terms per row): the (term, row) runs over ix.M x the columns, term-major, and the bound is sum_m |w_m| * |max|_m.
     const int M = ix.M > 0 ? ix.M : 1;
     float* rowmax = ix.per_row ? ws.get<float>((size_t)NB) : nullptr;
-    float* rshift = ix.per_row && c.shifts ? ws.get<float>((size_t)NB) : nullptr;
+    const bool auto_pitch = c.target_f0 != nullptr;      // the shifts come from the f0 this call decodes (run_pitch_match behind the encoder)
+    float* rshift = ix.per_row && c.shifts && !auto_pitch ? ws.get<float>((size_t)NB) : nullptr;
     std::vector<KnnSegIn> segs;
     if (ix.per_row) {
         for (int m = 0; m < M; ++m)
@@ -258,7 +259,15 @@ int tvc::convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const ConvertCall& c)
     ws.release(m);
     {
         ProfScope ps(ctx, s, ws, "encoder");
-        TVC_CHECK(run_encoder(ctx, s, ws, spec, ssl, f0, nullptr, B, T, spec_bound, enc_slots, f0s, c.shift, rshift));
+        TVC_CHECK(run_encoder(ctx, s, ws, spec, ssl, f0, nullptr, B, T, spec_bound, enc_slots, auto_pitch ? nullptr : f0s, c.shift, rshift));
+        if (auto_pitch && !ws.dry) {      // one workgroup per utterance: its register, its shift (offset = the host value), its shifted f0
+            std::vector<PitchRow> rows((size_t)NB);
+            for (int i = 0; i < NB; ++i) {
+                const int r = ctx->rag ? ctx->rag->row[i] : i;
+                rows[i] = PitchRow{ctx->rag ? ctx->rag->pre[i] : i * T, ctx->rag ? ctx->rag->tb[i] : T, r, c.shifts ? c.shifts[r] : c.shift};
+            }
+            TVC_CHECK(run_pitch_match(ctx, s, f0, rows, c.target_f0, nullptr, nullptr, c.shift_out, f0s));
+        }
     }
     ws.release(m);
     {
@@ -596,7 +605,8 @@ static int convert_entry(tvc_ctx* ctx, void* stream, const ConvertCall& c, bool 
 // per-row index (ix.Ns; ix.blobs is not looked at) is planned with every row a segment of its own (distinct stand-in blobs) and a shift
 // table (it takes workspace; never read in this walk): a call whose rows share blobs, or without per-row shifts, needs less.
 // (No allocation depends on whether the call brings its own noise phases.)
-static int convert_query(tvc_ctx* ctx, int B, int64_t L, const int64_t* lens, bool ragged, const ConvertIndex& ix, size_t* out_bytes, const char* what) {
+static int convert_query(tvc_ctx* ctx, int B, int64_t L, const int64_t* lens, bool ragged, const ConvertIndex& ix, size_t* out_bytes, const char* what,
+                         bool auto_pitch = false) {
     TVC_CHECK(need_ready(ctx, NEED_NONE));
     if (!out_bytes || (ragged && !lens) || (ix.per_row ? !ix.Ns : ix.N < 4) || B <= 0 || L <= 0 || L % kHop != 0)
         return fail(ctx, TVC_ERR_ARG, "%s: need B>0, %s%%480==0, %s%s", what, ragged ? "Lmax" : "L", ragged && ix.per_row ? "lens[B], " : "", ix.per_row ? "N[B]" : "N>=4");
@@ -615,6 +625,7 @@ static int convert_query(tvc_ctx* ctx, int B, int64_t L, const int64_t* lens, bo
     c.lens = lens;
     c.index = ix.M ? ConvertIndex::blend(blobs.data(), ix.Ns, ix.M, kDryPtr) : ix.per_row ? ConvertIndex::table(blobs.data(), ix.Ns) : ConvertIndex::one(kDryPtr, ix.N);
     c.shifts = ix.per_row ? &shift : nullptr;
+    c.target_f0 = auto_pitch ? kDryPtr : nullptr;
     if (!ragged) return measure(1, out_bytes, [&](Ws& ws) { return convert_impl(ctx, nullptr, ws, c); });
     std::vector<RagBatchPlan> batches;
     TVC_CHECK(ragged_split(ctx, ctx->rag_batch_frames, B, L, lens, &batches));
@@ -695,6 +706,70 @@ int tvc_convert_ragged_blend_f32(tvc_ctx* ctx, void* stream, const float* wav, i
     TVC_CHECK(blend_check(ctx, B, M, weights, "tvc_convert_ragged_blend_f32"));
     const ConvertCall c{wav, wave, B, Lmax, lens, ConvertIndex::blend(prepared, N, M, weights), pitch_shift, pitch_shifts, noise_angle, seed};
     return convert_entry(ctx, stream, c, true, wsp, ws_bytes, "tvc_convert_ragged_blend_f32");
+}
+
+// ---- automatic pitch: the shift that moves a row's register onto its target's, found on the device ------------------------------------------
+int tvc_pitch_match_f32(tvc_ctx* ctx, void* stream, const float* f0, const int64_t* row_start, int rows, const float* target_f0, float pitch_shift,
+                        const float* pitch_shifts, float* median_out, int32_t* voiced_out, float* shift_out, float* f0_shifted) {
+    if (!ctx) return TVC_ERR_ARG;
+    if (!f0 || !row_start || rows <= 0 || (!median_out && !voiced_out && !shift_out && !f0_shifted)) return fail(ctx, TVC_ERR_ARG, "tvc_pitch_match_f32: bad argument");
+    if (row_start[0] < 0 || row_start[rows] > 0x7fffffff) return fail(ctx, TVC_ERR_ARG, "tvc_pitch_match_f32: row_start beyond 32-bit indexing");
+    std::vector<PitchRow> pr((size_t)rows);
+    for (int b = 0; b < rows; ++b) {
+        if (row_start[b + 1] < row_start[b]) return fail(ctx, TVC_ERR_ARG, "tvc_pitch_match_f32: row_start[%d] > row_start[%d] (rows + 1 ascending column numbers)", b, b + 1);
+        pr[b] = PitchRow{(int)row_start[b], (int)(row_start[b + 1] - row_start[b]), b, pitch_shifts ? pitch_shifts[b] : pitch_shift};
+    }
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    return run_pitch_match(ctx, (hipStream_t)stream, f0, pr, target_f0, median_out, voiced_out, shift_out, f0_shifted);
+}
+
+// the table form of the blend entries: weights == NULL is the multi-index call and takes M = 1
+static int auto_index(tvc_ctx* ctx, int B, const float* const* prepared, const int64_t* N, int M, const float* weights, ConvertIndex* ix, const char* what) {
+    if (!ctx) return TVC_ERR_ARG;
+    if (!weights) {
+        if (M != 1) return fail(ctx, TVC_ERR_ARG, "%s: weights = NULL is one index per row: M must be 1, got %d", what, M);
+        *ix = ConvertIndex::table(prepared, N);
+        return 0;
+    }
+    TVC_CHECK(blend_check(ctx, B, M, weights, what));
+    *ix = ConvertIndex::blend(prepared, N, M, weights);
+    return 0;
+}
+// M = 1 may come with weights (a one-term blend) or without (the multi-index call): the query covers both
+static int auto_query(tvc_ctx* ctx, int B, int64_t L, const int64_t* lens, bool ragged, const int64_t* N, int M, size_t* out_bytes, const char* what) {
+    if (!ctx) return TVC_ERR_ARG;
+    TVC_CHECK(blend_check(ctx, B, M, kDryPtr, what));
+    TVC_CHECK(convert_query(ctx, B, L, lens, ragged, ConvertIndex::blend(nullptr, N, M, nullptr), out_bytes, what, true));
+    if (M == 1) {
+        size_t table = 0;
+        TVC_CHECK(convert_query(ctx, B, L, lens, ragged, ConvertIndex::table(nullptr, N), &table, what, true));
+        if (table > *out_bytes) *out_bytes = table;
+    }
+    return TVC_OK;
+}
+int tvc_workspace_bytes_auto(tvc_ctx* ctx, int B, int64_t L, const int64_t* N, int M, size_t* out_bytes) {
+    return auto_query(ctx, B, L, nullptr, false, N, M, out_bytes, "tvc_workspace_bytes_auto");
+}
+int tvc_workspace_bytes_ragged_auto(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, const int64_t* N, int M, size_t* out_bytes) {
+    return auto_query(ctx, B, Lmax, lens, true, N, M, out_bytes, "tvc_workspace_bytes_ragged_auto");
+}
+int tvc_convert_auto_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M, const float* weights,
+                         const float* target_f0, float pitch_shift, const float* pitch_shifts, float* shift_out, const float* noise_angle, uint64_t seed,
+                         float* wave, int B, int64_t L, void* wsp, size_t ws_bytes) {
+    ConvertIndex ix;
+    TVC_CHECK(auto_index(ctx, B, prepared, N, M, weights, &ix, "tvc_convert_auto_f32"));
+    if (!target_f0) return fail(ctx, TVC_ERR_ARG, "tvc_convert_auto_f32: target_f0 is NULL (a device array of B registers in Hz)");
+    const ConvertCall c{wav, wave, B, L, nullptr, ix, pitch_shift, pitch_shifts, noise_angle, seed, target_f0, shift_out};
+    return convert_entry(ctx, stream, c, false, wsp, ws_bytes, "tvc_convert_auto_f32");
+}
+int tvc_convert_ragged_auto_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens, const float* const* prepared,
+                                const int64_t* N, int M, const float* weights, const float* target_f0, float pitch_shift, const float* pitch_shifts,
+                                float* shift_out, const float* noise_angle, uint64_t seed, float* wave, int B, void* wsp, size_t ws_bytes) {
+    ConvertIndex ix;
+    TVC_CHECK(auto_index(ctx, B, prepared, N, M, weights, &ix, "tvc_convert_ragged_auto_f32"));
+    if (!target_f0) return fail(ctx, TVC_ERR_ARG, "tvc_convert_ragged_auto_f32: target_f0 is NULL (a device array of B registers in Hz)");
+    const ConvertCall c{wav, wave, B, Lmax, lens, ix, pitch_shift, pitch_shifts, noise_angle, seed, target_f0, shift_out};
+    return convert_entry(ctx, stream, c, true, wsp, ws_bytes, "tvc_convert_ragged_auto_f32");
 }
 
 int tvc_knn_match_blend_f32(tvc_ctx* ctx, void* stream, const float* src, const float* const* prepared, const int64_t* N, int M, const float* weights,

@@ -1,5 +1,5 @@
 // Front end: |STFT| (spectrogram.py:8-15), energy envelope (energy_estimation.py:9-14),
-// semitone shift (pitch_shift.py:5-15).
+// semitone shift (pitch_shift.py:5-15), the row-wise pitch register and the automatic shift onto a target's (no reference counterpart).
 #include "small_kernels.h"
 #include "tvc_common.h"
 
@@ -195,6 +195,137 @@ int run_uniform_to_angle(tvc_ctx* ctx, hipStream_t s, float* u, int64_t n) {
 int run_shift(tvc_ctx* ctx, hipStream_t s, const float* f0, float* out, int64_t n, float semitones) {
     hipLaunchKernelGGL(shift_kernel, dim3(grid_for(n)), dim3(256), 0, s, f0, out, (long)n, semitones);
     return launch_check(ctx, "shift_frequency");
+}
+
+// ---- pitch register and automatic shift ------------------------------------------------------------
+// The register of a row of f0 = the LOWER median of its voiced frames, torch.median(row[row > 0]): the element of rank (nv - 1) / 2 among
+// the nv values > 0 (zeros, negatives and NaN are unvoiced).  An order statistic: exact, no floating-point sum, independent of the grid.
+// Positive floats order like their bit patterns, so it is a radix select over bits 30 .. 0 (the sign of a voiced value is 0): four passes
+// over the digits [30:23] (the exponent), [22:15], [14:7], [6:0], each a histogram of the values that share the digits selected so far,
+// then a scan that finds the digit holding the wanted rank.  One 256-thread workgroup per row; rows come as runs of columns (start,
+// length) in the kernel's ARGUMENTS, like the offsets (host values of the call: asynchronous, capturable).
+// f0 lives in 20 Hz .. a few kHz: a row's values share their top bits, the exponent pass meets 2 - 4 distinct digits and a pass over equal
+// values one.  So every wave keeps its own histogram and first peels the two most advanced digits of its 64 values with a ballot (one add of
+// the population count by the first lane that holds the digit); only what is left goes to the LDS atomics one by one.  Integer atomics
+// on LDS only.
+//   shift[b] = offset[b] + 12 log2(target[b] / median[b])   evaluated in fp64, rounded once (like shift_frequency_one's transcendentals);
+//   shift[b] = offset[b] exactly when the row has no voiced frame, target[b] <= 0 or NaN, or there is no target (measuring only).
+// The same workgroup then walks its row again: f0s[n] = shift_frequency_one(f0[n], shift[b]).  The median of a row without a voiced
+// frame is reported as 0.
+constexpr int kPmRows = 256;      // rows per launch: their descriptions are kernel arguments (3 KiB of the 4 KiB a launch may carry)
+struct PitchRowChunk {
+    int start[kPmRows], len[kPmRows], idx[kPmRows];      // columns [start, start + len) of f0; idx = the row's slot in target / the outputs
+    float offset[kPmRows];
+};
+
+static __global__ __launch_bounds__(256) void pitch_match_kernel(const float* __restrict__ f0, PitchRowChunk rows, const float* __restrict__ target,
+                                                                 float* __restrict__ median_out, int* __restrict__ voiced_out, float* __restrict__ shift_out,
+                                                                 float* __restrict__ f0s) {
+    __shared__ unsigned hist[4][256];
+    __shared__ unsigned wsum[4];
+    __shared__ unsigned sel_digit, sel_rank;
+    __shared__ float sh_shift;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = blockIdx.x;
+    const long n = rows.len[r];
+    const float* p = f0 + rows.start[r];
+    unsigned prefix = 0, rank = 0, nv = 0;
+#pragma unroll 1
+    for (int pass = 0; pass < 4; ++pass) {
+        const int lo = pass == 3 ? 0 : 23 - 8 * pass;            // 23, 15, 7, 0
+        const int width = pass == 3 ? 7 : 8;
+        for (int w = 0; w < 4; ++w) hist[w][tid] = 0;
+        __syncthreads();
+        for (long base = 0; base < n; base += 256 * 4) {
+            float v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const long i = base + u * 256 + tid;
+                v[u] = i < n ? p[i] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const unsigned bits = __float_as_uint(v[u]);
+                bool live = v[u] > 0.f && (pass == 0 || (bits >> (lo + width)) == prefix);
+                const unsigned digit = (bits >> lo) & ((1u << width) - 1u);
+#pragma unroll
+                for (int round = 0; round < 2; ++round) {
+                    const unsigned long long act = __ballot(live);
+                    if (!act) break;
+                    const int first = __ffsll((long long)act) - 1;
+                    const unsigned d0 = (unsigned)__shfl((int)digit, first);
+                    const unsigned long long same = __ballot(live && digit == d0);
+                    if (lane == first) atomicAdd(&hist[wave][d0], (unsigned)__popcll(same));
+                    if (digit == d0) live = false;
+                }
+                if (live) atomicAdd(&hist[wave][digit], 1u);
+            }
+        }
+        __syncthreads();
+        // exclusive scan of the 256 bins (thread = bin): the bin that holds `rank`
+        const unsigned c = hist[0][tid] + hist[1][tid] + hist[2][tid] + hist[3][tid];
+        unsigned inc = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned t = (unsigned)__shfl_up((int)inc, o);
+            if (lane >= o) inc += t;
+        }
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        unsigned before = 0, total = 0;
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) before += wsum[w];
+            total += wsum[w];
+        }
+        if (pass == 0) {
+            nv = total;
+            rank = nv ? (nv - 1) / 2 : 0;
+        }
+        if (total == 0) break;      // (pass 0 only: no voiced frame; uniform over the workgroup)
+        const unsigned excl = before + inc - c;
+        if (c && excl <= rank && rank < excl + c) {
+            sel_digit = (unsigned)tid;
+            sel_rank = rank - excl;
+        }
+        __syncthreads();
+        prefix = (prefix << width) | sel_digit;
+        rank = sel_rank;
+    }
+    if (tid == 0) {
+        const float med = nv ? __uint_as_float(prefix) : 0.f;
+        const int slot = rows.idx[r];
+        const float off = rows.offset[r];
+        float sh = off;
+        if (target && nv) {
+            const float tg = target[slot];
+            if (tg > 0.f) sh = (float)((double)off + 12.0 * log2((double)tg / (double)med));
+        }
+        if (median_out) median_out[slot] = med;
+        if (voiced_out) voiced_out[slot] = (int)nv;
+        if (shift_out) shift_out[slot] = sh;
+        sh_shift = sh;
+    }
+    if (!f0s) return;
+    __syncthreads();
+    const float sh = sh_shift;
+    float* q = f0s + rows.start[r];
+    for (long i = tid; i < n; i += 256) q[i] = shift_frequency_one(p[i], sh);
+}
+
+int run_pitch_match(tvc_ctx* ctx, hipStream_t s, const float* f0, const std::vector<PitchRow>& rows, const float* target, float* median_out, int* voiced_out,
+                    float* shift_out, float* f0s) {
+    for (size_t o = 0; o < rows.size(); o += kPmRows) {
+        PitchRowChunk c{};
+        const int n = (int)(rows.size() - o < (size_t)kPmRows ? rows.size() - o : (size_t)kPmRows);
+        for (int i = 0; i < n; ++i) {
+            c.start[i] = rows[o + i].start;
+            c.len[i] = rows[o + i].len;
+            c.idx[i] = rows[o + i].idx;
+            c.offset[i] = rows[o + i].offset;
+        }
+        hipLaunchKernelGGL(pitch_match_kernel, dim3(n), dim3(256), 0, s, f0, c, target, median_out, voiced_out, shift_out, f0s);
+    }
+    return launch_check(ctx, "pitch_match");
 }
 
 }  // namespace tvc

@@ -388,6 +388,11 @@ struct ConvertCall {
     const float* shifts = nullptr;             // ... or (host, with a per-row index only) one per row
     const float* angle = nullptr;              // noise phases; nullptr: drawn from `seed`
     uint64_t seed = 0;
+    // automatic pitch (tvc_convert_auto_f32): target_f0 (device, one register in Hz per caller's row) makes shift / shifts the OFFSET on top
+    // of 12 log2(target_f0[r] / the row's own register), found on the device between the encoder and the decoder (run_pitch_match);
+    // shift_out (device, nullable) receives the applied shifts, one per caller's row
+    const float* target_f0 = nullptr;
+    float* shift_out = nullptr;
 };
 // Generator.convert over c.B rows of c.L samples (c.lens is not looked at: a ragged call reaches this through convert_ragged_batches,
 // one batch at a time as ONE row with ctx->rag set, ragged.h)
@@ -400,6 +405,17 @@ int run_knn_general(tvc_ctx*, hipStream_t, Ws&, const float* src, const float* i
 int run_knn_slots(tvc_ctx*, hipStream_t, const float* prepared, int64_t N, const int64_t* idx, float* slots, int64_t nslots);
 int run_knn_finish(tvc_ctx*, hipStream_t, const float* slots, float* out, int B, int T);
 int run_shift(tvc_ctx*, hipStream_t, const float* f0, float* out, int64_t n, float semitones);
+// The pitch register of rows of f0 and the shift that moves it onto a target's (frontend.hip pitch_match_kernel): row i = columns
+// [start, start + len) of f0, its slot `idx` in target / median_out / voiced_out / shift_out, its host offset in semitones.
+//   median = the lower median of the row's values > 0 (0 without one), voiced = their count,
+//   shift  = offset + 12 log2(target[idx] / median)   (offset alone: no voiced frame, target[idx] <= 0 or NaN, target == nullptr),
+//   f0s[start + t] = shift_frequency(f0[start + t], shift).   Every output is optional.  One launch per 256 rows, no workspace.
+struct PitchRow {
+    int start, len, idx;
+    float offset;
+};
+int run_pitch_match(tvc_ctx*, hipStream_t, const float* f0, const std::vector<PitchRow>& rows, const float* target, float* median_out, int* voiced_out,
+                    float* shift_out, float* f0s);
 int run_uniform_to_angle(tvc_ctx*, hipStream_t, float* u, int64_t n);
 // content_bound (optional): an upper bound of |content| (the prepared index's |max| when content came out of the kNN match): ONE float, or
 // with content_bound_stride = 1 one per utterance (a match against one index per utterance);

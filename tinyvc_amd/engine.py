@@ -443,6 +443,77 @@ class Engine:
                                                        seed, _ptr(wave), B, p, n), "tvc_convert_ragged_blend_f32")
         return wave
 
+    # ---- automatic pitch: the shift that moves a row's register onto its target's (tvc_pitch_match_f32, tvc_*_auto) ----
+    def _target_f0(self, target_f0, B):
+        """the target registers of a call: a contiguous fp32 [B] tensor on this device, used in place (the kernels read it when they run)"""
+        _check_dev(target_f0, "target_f0", self.device)
+        if target_f0.dtype != _F32 or target_f0.dim() != 1 or target_f0.shape[0] != B or not target_f0.is_contiguous():
+            raise ValueError(f"target_f0 must be a contiguous fp32 [B = {B}] tensor on the device, got {tuple(target_f0.shape)} {target_f0.dtype}")
+        return target_f0
+
+    def pitch_match(self, f0, row_start=None, target_f0=None, pitch_shift=0.0, want_shifted=False):
+        """The pitch register of rows of f0, and the shift onto a target's: f0 [B, 1, T] / [B, T] (every row a run of T columns), or any
+        contiguous f0 with row_start = rows + 1 ascending column numbers (row b = [row_start[b], row_start[b + 1]) of the flattened f0) ->
+        (median [rows] fp32 - the lower median of the values > 0, 0 without one -, voiced [rows] int32, shift [rows] fp32 =
+        pitch_shift (a float or one per row) + 12 log2(target_f0 / median), f0 shifted by it or None).  target_f0 (optional): a
+        contiguous fp32 [rows] device tensor in Hz; without it the call measures and shift is the offset."""
+        f0 = _prep(f0, "f0", self.device)
+        if row_start is None:
+            if f0.dim() < 2:
+                raise ValueError("pitch_match: f0 [B, 1, T] or [B, T], or row_start for a packed f0")
+            rows, T = f0.shape[0], f0.numel() // max(f0.shape[0], 1)
+            row_start = [b * T for b in range(rows + 1)]
+        row_start = [int(x) for x in row_start]
+        rows = len(row_start) - 1
+        if rows < 1 or row_start[0] < 0 or row_start[-1] > f0.numel() or any(a > b for a, b in zip(row_start, row_start[1:])):
+            raise ValueError(f"pitch_match: row_start must be rows + 1 ascending column numbers within the {f0.numel()} values of f0")
+        shift, shifts = self._shifts(pitch_shift, rows)
+        tgt = self._target_f0(target_f0, rows) if target_f0 is not None else None
+        med = torch.empty(rows, dtype=_F32, device=self.device)
+        voiced = torch.empty(rows, dtype=torch.int32, device=self.device)
+        sh = torch.empty(rows, dtype=_F32, device=self.device)
+        out = torch.zeros_like(f0) if want_shifted else None
+        self._ok(self.lib.tvc_pitch_match_f32(self.ctx, self._stream(), _ptr(f0), (ctypes.c_int64 * (rows + 1))(*row_start), rows, _ptr(tgt), shift, shifts,
+                                              _ptr(med), _ptr(voiced), _ptr(sh), _ptr(out)), "tvc_pitch_match_f32")
+        return med, voiced, sh, out
+
+    def _auto_index(self, prepared, Ns, weights, B):
+        if weights is None:
+            blobs, ns = self._table(prepared, Ns, B)
+            return blobs, ns, 1
+        return self._blend_args(prepared, Ns, weights, B)
+
+    def convert_auto(self, wav, prepared, Ns, target_f0, pitch_shift=0.0, weights=None, noise_angle=None, out=None, shift_out=None):
+        """convert_multi (weights None: one prepared index per row) or convert_blend (weights [B, M] on the device, prepared / Ns [B * M]) with the
+        shift found on the device: row b is shifted by pitch_shift (a float or one per row, now the offset) + 12 log2(target_f0[b] / the
+        lower median of the row's own voiced f0) -> (wave [B, L], shifts [B] on the device): tvc_convert_auto_f32."""
+        wav, B, L = self._rows(wav)
+        blobs, ns, M = self._auto_index(prepared, Ns, weights, B)
+        tgt = self._target_f0(target_f0, B)
+        shift, shifts = self._shifts(pitch_shift, B)
+        a, seed = self._angle(noise_angle, B, L // spec.HOP)
+        wave = out if out is not None else torch.empty(B, L, dtype=_F32, device=self.device)
+        sh = shift_out if shift_out is not None else torch.empty(B, dtype=_F32, device=self.device)
+        p, n = self._query_ws("tvc_workspace_bytes_auto", B, L, ns, M)
+        self._ok(self.lib.tvc_convert_auto_f32(self.ctx, self._stream(), _ptr(wav), blobs, ns, M, _ptr(weights), _ptr(tgt), shift, shifts, _ptr(sh), _ptr(a), seed,
+                                               _ptr(wave), B, L, p, n), "tvc_convert_auto_f32")
+        return wave, sh
+
+    def convert_ragged_auto(self, wav, lengths, prepared, Ns, target_f0, pitch_shift=0.0, weights=None, noise_angle=None):
+        """convert_auto over a ragged batch (every utterance's register is the median over its OWN frames): tvc_convert_ragged_auto_f32."""
+        wav, B, Lmax = self._rows(wav, ragged=True)
+        lens = self._lens(lengths, B)
+        blobs, ns, M = self._auto_index(prepared, Ns, weights, B)
+        tgt = self._target_f0(target_f0, B)
+        shift, shifts = self._shifts(pitch_shift, B)
+        a, seed = self._angle(noise_angle, B, Lmax // spec.HOP)
+        p, n = self._query_ws("tvc_workspace_bytes_ragged_auto", B, Lmax, lens, ns, M)
+        wave = torch.empty(B, Lmax, dtype=_F32, device=self.device)
+        sh = torch.empty(B, dtype=_F32, device=self.device)
+        self._ok(self.lib.tvc_convert_ragged_auto_f32(self.ctx, self._stream(), _ptr(wav), Lmax, lens, blobs, ns, M, _ptr(weights), _ptr(tgt), shift, shifts,
+                                                      _ptr(sh), _ptr(a), seed, _ptr(wave), B, p, n), "tvc_convert_ragged_auto_f32")
+        return wave, sh
+
     # ---- index-sharded match (one prepared index shard per rank; merged by parallel.match_features_sharded) ----
     METRICS = {"cos": 0, "IP": 1, "L2": 2}
 

@@ -5,7 +5,8 @@ import torch
 from .. import utils
 from .._base import HipModule
 from ..tinyvc import Decoder, Encoder
-from ..tinyvc.feature_retrieval import Blend, check_blend, check_references, prepare_reference, prepare_references
+from ..tinyvc.feature_retrieval import (Blend, check_blend, check_references, prepare_reference, prepare_references, resolve_auto_pitch,
+                                        target_registers)
 
 
 def _per_row_shift(pitch_shift, B):
@@ -62,7 +63,8 @@ class Generator(HipModule):
         return self.engine(wf.device).encode_ragged(wf, lens)
 
     @torch.no_grad()
-    def convert(self, wf, tgt, pitch_shift, f0_estimation="default", device=None, noise_angle=None, lengths=None):
+    def convert(self, wf, tgt, pitch_shift, f0_estimation="default", device=None, noise_angle=None, lengths=None, auto_pitch=None,
+                return_shift=False):
         """generator.py:26-34: wf [B, L], tgt [1 or B, 768, N] -> converted waveform [B, L'] (L' = L
         padded to a multiple of 480).  `f0_estimation` / `device` are accepted and ignored exactly as
         in the reference.  `noise_angle` [B,961,T] (extension) injects the decoder's noise phases;
@@ -76,8 +78,18 @@ class Generator(HipModule):
         B = 1 conversion against tgt[b]).  `pitch_shift` (extension): a float, or a sequence / 1-D tensor of one shift per row.
         A weighted blend of indices (extension): tgt = feature_retrieval.Blend(terms, weights) converts every frame toward
         w_0 * match_0 + w_1 * match_1 + ... in ONE call (tvc_convert_blend_f32 / tvc_convert_ragged_blend_f32), equal or ragged batches,
-        scalar or per-row shifts; the weights are read on the device when the kernels run."""
+        scalar or per-row shifts; the weights are read on the device when the kernels run.
+        `auto_pitch` (extension): move every row's median f0 onto the target's register, on the device inside the same call
+        (tvc_convert_auto_f32 / tvc_convert_ragged_auto_f32: no second encoder pass, no host synchronisation) - a register in Hz (a float, or
+        a [B] / [1] device tensor, read when the kernels run), or True = the register riding on each target tensor (`pitch_register`:
+        build_index and the entry scripts' loaders attach it).  True is refused (ValueError, before any engine work) for a target without a
+        register and for a Blend, which takes an explicit register.  `pitch_shift` then is the offset on top of the automatic shift.
+        `return_shift=True` -> (wave, shifts [B] on the device: the semitones applied to each row)."""
         B = wf.shape[0] if wf.dim() == 2 else 1
+        if auto_pitch is not None and auto_pitch is not False:
+            return self._convert_auto(wf, tgt, pitch_shift, noise_angle, lengths, B, auto_pitch, return_shift)
+        if return_shift:
+            raise ValueError("return_shift needs auto_pitch: without it the shifts are the caller's own pitch_shift")
         if isinstance(tgt, Blend):
             return self._convert_blend(wf, tgt, pitch_shift, noise_angle, lengths, B)
         multi = isinstance(tgt, (list, tuple)) or (isinstance(tgt, torch.Tensor) and tgt.dim() == 3 and tgt.shape[0] != 1)
@@ -131,3 +143,40 @@ class Generator(HipModule):
         if lens is not None:
             return eng.convert_ragged_blend(wf, lens, blobs, ns, w, shift, noise_angle)
         return eng.convert_blend(wf, blobs, ns, w, shift, noise_angle)
+
+    def _convert_auto(self, wf, tgt, pitch_shift, noise_angle, lengths, B, auto_pitch, return_shift):
+        """convert with the shift found on the device: every form of tgt, as the table form of the blend entries (M = 1 without weights)"""
+        blend = isinstance(tgt, Blend)
+        multi = not blend and (isinstance(tgt, (list, tuple)) or (isinstance(tgt, torch.Tensor) and tgt.dim() == 3 and tgt.shape[0] != 1))
+        # malformed targets, registers and shift lists are refused before any engine or device work
+        if blend:
+            check_blend(tgt.terms, tgt._given, B)
+        elif multi:
+            check_references(tgt, B)
+        regs = resolve_auto_pitch(auto_pitch, tgt, B)
+        shifts = _per_row_shift(pitch_shift, B)
+        wf = utils.autopad_waveform(self._input_device(wf))
+        eng = self.engine(wf.device)
+        B, L = wf.shape
+        if noise_angle is not None:
+            noise_angle = self._input_device(noise_angle)
+        lens = None
+        if lengths is not None:
+            lens = [-(-int(n) // 480) * 480 for n in lengths]
+            if len(lens) != B or max(lens) > L or min(lens) <= 960:
+                raise ValueError("lengths: one entry per row, each in (960, L]")
+        w = None
+        if blend:
+            blobs, ns, w = tgt.resolve(B, wf.device, self._input_device)
+        elif multi:
+            blobs, ns = prepare_references([self._input_device(t) for t in tgt] if isinstance(tgt, (list, tuple)) else self._input_device(tgt))
+        else:
+            blob, n = prepare_reference(self._input_device(tgt))
+            blobs, ns = [blob] * B, [n] * B
+        f0t = target_registers(regs, B, wf.device)
+        shift = shifts if shifts is not None else float(pitch_shift)
+        if lens is not None:
+            wave, sh = eng.convert_ragged_auto(wf, lens, blobs, ns, f0t, shift, w, noise_angle)
+        else:
+            wave, sh = eng.convert_auto(wf, blobs, ns, f0t, shift, w, noise_angle)
+        return (wave, sh) if return_shift else wave

@@ -1,5 +1,9 @@
 """kNN-VC feature matching (reference module/tinyvc/feature_retrieval.py:15-33) on the streamed
 top-k kernel of csrc/knn.hip."""
+import collections
+import math
+import os
+
 import torch
 
 from ... import spec
@@ -58,9 +62,12 @@ def build_index(generator, wf, lengths, stride=4, size=None, perm=None, half=Fal
     `assemble` of extract_index.py builds from one `encode` per clip.  Ragged encode, column plan (index_columns), one gather that writes
     the index AND its prepared blob: the blob rides on the returned tensor like prepare_reference's, so the first convert /
     match_features against it prepares nothing."""
-    ssl, _f0, pre = generator.encode_packed(wf, lengths)
+    ssl, f0, pre = generator.encode_packed(wf, lengths)
     cols = index_columns([pre[b + 1] - pre[b] for b in range(len(pre) - 1)], stride, size, perm)
-    return index_from_columns(generator.engine(ssl.device), ssl, cols, half)
+    index = index_from_columns(generator.engine(ssl.device), ssl, cols, half)
+    # the speaker's pitch register over ALL frames of the clips (not the strided selection): what convert(auto_pitch=True) aims at
+    index.pitch_register = pitch_register(f0, [f0.numel()])
+    return index
 
 
 def index_from_columns(eng, feats, cols, half=False):
@@ -97,6 +104,119 @@ def compact_index(reference, size, iters=8, generator=None, init_cols=None, snap
         cblob, _k, index = eng.knn_prepare_columns(reference[0].float(), idx[0, :, 0], half=False, want_index=True)
     index._tvc_prepared = (index._version, str(index.device), cblob, size)
     return (index, {"assign": assign, "counts": counts, "moved": moved}) if return_info else index
+
+
+# ---- pitch registers: the other half of a target (convert(auto_pitch=...)) -------------------------------------------------------------
+PitchRegister = collections.namedtuple("PitchRegister", ["median_hz", "voiced"])      # device tensors [rows]: fp32 Hz, int32 voiced frames
+
+
+@torch.no_grad()
+def pitch_register(f0, lengths=None):
+    """The pitch register of rows of f0 on the device (Engine.pitch_match): the lower median of each row's voiced frames,
+    torch.median(row[row > 0]) bit for bit, and their count -> PitchRegister(median_hz [rows] fp32 - 0 for a row without a voiced frame -,
+    voiced [rows] int32).  f0 [B, 1, T] / [B, T]: one register per row.  lengths (frames): f0 is packed (encode_packed's [S]), row b
+    owns the lengths[b] values behind those of the rows before it; lengths = [S] is the register of everything."""
+    eng = default_engine(f0.device)
+    row_start = None
+    if lengths is not None:
+        row_start = [0]
+        for n in lengths:
+            row_start.append(row_start[-1] + int(n))
+    med, voiced, _sh, _ = eng.pitch_match(f0, row_start)
+    return PitchRegister(med, voiced)
+
+
+def semitones_between(src_hz, tgt_hz):
+    """12 * log2(tgt_hz / src_hz) in fp64 on the host: the automatic shift of tvc_pitch_match_f32 without its offset.  Floats -> a float;
+    sequences / tensors -> a list.  A pair with src_hz <= 0 or tgt_hz <= 0 (no register) or NaN gives 0.0, as on the device."""
+    def one(a, b):
+        a, b = float(a), float(b)
+        return 12.0 * math.log2(b / a) if a > 0.0 and b > 0.0 else 0.0
+
+    def seq(x):
+        if isinstance(x, torch.Tensor):
+            return x.detach().to("cpu", torch.float64).reshape(-1).tolist()
+        return list(x) if hasattr(x, "__len__") else None
+
+    a, b = seq(src_hz), seq(tgt_hz)
+    if a is None and b is None:
+        return one(src_hz, tgt_hz)
+    n = len(a) if a is not None else len(b)
+    a = a if a is not None else [src_hz] * n
+    b = b if b is not None else [tgt_hz] * n
+    if len(a) != len(b):
+        raise ValueError(f"semitones_between: {len(a)} source registers against {len(b)} targets")
+    return [one(x, y) for x, y in zip(a, b)]
+
+
+def sidecar_path(index_path):
+    """where the register of the index file `index_path` lives: <index_path>.f0.pt"""
+    return str(index_path) + ".f0.pt"
+
+
+def save_register(index_path, register):
+    """writes {"median_hz": float, "voiced": int} beside the index file (the index file itself keeps the reference's format)"""
+    torch.save({"median_hz": float(register.median_hz.reshape(-1)[0]), "voiced": int(register.voiced.reshape(-1)[0])}, sidecar_path(index_path))
+
+
+def attach_register(index, index_path):
+    """index.pitch_register <- the sidecar of `index_path` when there is one (tensors on the index's device); returns index"""
+    path = sidecar_path(index_path)
+    if os.path.exists(path):
+        d = torch.load(path, map_location="cpu")
+        index.pitch_register = PitchRegister(torch.tensor([float(d["median_hz"])], dtype=torch.float32, device=index.device),
+                                             torch.tensor([int(d["voiced"])], dtype=torch.int32, device=index.device))
+    return index
+
+
+def _registers_of(tgt):
+    """the [rows] median tensors that ride on a target (a tensor or a list of tensors), or ValueError naming the one without"""
+    items = list(tgt) if isinstance(tgt, (list, tuple)) else [tgt]
+    out = []
+    for i, t in enumerate(items):
+        reg = getattr(t, "pitch_register", None)
+        if reg is None:
+            raise ValueError(f"auto_pitch=True: target{f' {i}' if len(items) > 1 else ''} carries no pitch register (build_index and the entry scripts' "
+                             "loaders attach one; else pass auto_pitch in Hz)")
+        out.append(reg.median_hz.reshape(-1))
+    return out
+
+
+def resolve_auto_pitch(auto_pitch, tgt, B):
+    """convert's auto_pitch -> what becomes the [B] device tensor of target registers, checked on the host (no engine, no device work):
+    a float in Hz, a [B] or [1] tensor, or True = the registers riding on the target tensor(s).  Returns a float or a list of tensors
+    whose concatenation has 1 or B entries; raises ValueError otherwise."""
+    if auto_pitch is True:
+        if isinstance(tgt, Blend):
+            raise ValueError("auto_pitch=True with a Blend: its weights live on the device, so the blend's register is the caller's to give (auto_pitch in Hz)")
+        regs = _registers_of(tgt)
+        n = sum(r.numel() for r in regs)
+        if n not in (1, B):
+            raise ValueError(f"auto_pitch=True: {n} target registers for a batch of {B}")
+        return regs
+    if isinstance(auto_pitch, torch.Tensor):
+        if auto_pitch.dim() > 1 or auto_pitch.numel() not in (1, B):
+            raise ValueError(f"auto_pitch: a tensor of 1 or B = {B} registers in Hz, got {tuple(auto_pitch.shape)}")
+        return [auto_pitch.reshape(-1)]
+    if isinstance(auto_pitch, bool) or not isinstance(auto_pitch, (int, float)):
+        raise ValueError(f"auto_pitch: a register in Hz (float or [B] / [1] tensor) or True, got {auto_pitch!r}")
+    return float(auto_pitch)
+
+
+def target_registers(resolved, B, device):
+    """resolve_auto_pitch's result as the contiguous fp32 [B] device tensor the engine takes (a [B] fp32 device tensor passes through as it
+    is: the kernels read it when they run)"""
+    if isinstance(resolved, float):
+        return torch.full((B,), resolved, dtype=torch.float32, device=device)
+    t = resolved[0] if len(resolved) == 1 else torch.cat([r.to(device) for r in resolved])
+    t = t.to(device=device, dtype=torch.float32)
+    return (t.expand(B) if t.numel() == 1 else t).contiguous()
+
+
+def add_auto_pitch_argument(parser):
+    """`--auto-pitch` for infer.py's parser: shift every file so that its median f0 lands on the target's (-p stays, as the offset)."""
+    parser.add_argument("--auto-pitch", action="store_true",
+                        help="move every file's median f0 onto the target speaker's (from the index's .f0.pt sidecar, or the -t recording); -p is added on top")
 
 
 def check_references(tgt, B=None):
