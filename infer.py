@@ -65,12 +65,17 @@ def build_parser():
     return p
 
 
-def file_angle(gen, device, seed, path, frames):
-    """[1, 961, frames] noise phases of one file under --seed: the reference's own draw (decoder.py:78: torch.rand * 2 pi - pi) from a device
-    generator seeded by (seed, crc32 of the file's base name) - the same phases whichever call, row or rank converts the file."""
+def file_generator(device, seed, path):
+    """--seed: a device generator seeded by (seed, crc32 of the file's base name) alone"""
     g = torch.Generator(device=device)
     g.manual_seed((int(seed) * 0x9E3779B1 + zlib.crc32(os.path.basename(path).encode())) & 0x7FFFFFFFFFFFFFFF)
-    return gen.engine(device).noise_angle_from_uniform(torch.rand(1, spec.FFT_BIN, frames, device=device, generator=g))
+    return g
+
+
+def file_angle(gen, device, seed, path, frames):
+    """[1, 961, frames] noise phases of one file under --seed: the reference's own draw (decoder.py:78: torch.rand * 2 pi - pi) from a device
+    generator of the file's own (file_generator) - the same phases whichever call, row or rank converts the file."""
+    return gen.engine(device).noise_angle_from_uniform(torch.rand(1, spec.FFT_BIN, frames, device=device, generator=file_generator(device, seed, path)))
 
 
 def my_share(paths, world, rank):
@@ -204,11 +209,7 @@ def main(argv=None, world=None, rank=None, local_rank=None):
             batch = torch.cat([jobs[i][1][:, :length] for i in rows], dim=0)
             angles = None
             if args.seed is not None:      # one generator per file, drawn from block after block: a stream's phases do not depend on its neighbours
-                gens = []
-                for i in rows:
-                    g = torch.Generator(device=device)
-                    g.manual_seed((int(args.seed) * 0x9E3779B1 + zlib.crc32(os.path.basename(jobs[i][0]).encode())) & 0x7FFFFFFFFFFFFFFF)
-                    gens.append(g)
+                gens = [file_generator(device, args.seed, jobs[i][0]) for i in rows]
                 tb = max(args.chunk_size + 1920 + 1920 + 2 * 3840, args.chunk_size + args.buffer_size * args.chunk_size) // 480      # frames of a stream's rolling buffer (BatchedStreamInfer.input_size, stream.py:52-53)
                 angles = lambda _i: gen.engine(device).noise_angle_from_uniform(      # noqa: E731
                     torch.cat([torch.rand(1, spec.FFT_BIN, tb, device=device, generator=g) for g in gens], dim=0))

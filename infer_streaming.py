@@ -26,9 +26,9 @@ import numpy as np
 import torch
 
 from tinyvc_amd import audio_io
-from tinyvc_amd.module.infer import BatchedStreamInfer, Generator
-from tinyvc_amd.module.tinyvc import Blend, Decoder, Encoder
-from tinyvc_amd.module.tinyvc.feature_retrieval import add_blend_argument, attach_register, pitch_register, semitones_between
+from infer import load_generator, load_target
+from tinyvc_amd.module.infer import BatchedStreamInfer
+from tinyvc_amd.module.tinyvc.feature_retrieval import add_blend_argument, pitch_register, semitones_between
 
 
 def build_parser():
@@ -73,23 +73,11 @@ def main(argv=None):
     device = torch.device(args.device)
     if device.type != "cuda":
         sys.exit("infer_streaming.py: this build runs on an AMD GPU only; pass -d cuda")
-    enc, dec = Encoder(), Decoder()
-    enc.load_state_dict(torch.load(args.encoder_path, map_location="cpu"))
-    dec.load_state_dict(torch.load(args.decoder_path, map_location="cpu"))
-    gen = Generator(enc.eval(), dec.eval()).to(device)
+    gen = load_generator(args.encoder_path, args.decoder_path, device)
     S = max(1, args.streams)
     if args.auto_pitch_from is not None and args.blend is not None:
         sys.exit("infer_streaming.py: --auto-pitch-from with --blend: a blend has no register of its own; use -p")
-    if args.blend is not None:      # a weighted blend of index files in place of -idx / -t; every stream takes the same mix
-        paths, weights = args.blend
-        tgt = Blend([torch.load(p_, map_location="cpu").to(device) for p_ in paths], weights)
-    elif args.index == "NONE":
-        wf, sr = audio_io.load(args.target)
-        wf = gen.engine(device).resample(wf.to(device), sr, 24000)
-        tgt, f0 = gen.encode(wf.mean(dim=0, keepdim=True))
-        tgt.pitch_register = pitch_register(f0)
-    else:
-        tgt = attach_register(torch.load(args.index, map_location="cpu").to(device), args.index)
+    tgt = load_target(gen, args, device)      # --blend (every stream takes the same mix), -idx or -t: as infer.py loads them
     pitch_shift = args.pitch_shift
     if args.auto_pitch_from is not None:      # one measurement, one host read, before the session starts
         reg = getattr(tgt, "pitch_register", None)

@@ -19,6 +19,10 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _floats(xs):
+    return (ctypes.c_float * len(xs))(*xs) if xs is not None else None
+
+
 def _check_dev(t, name, device):
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor")
@@ -35,6 +39,41 @@ def _prep(t, name, device):
     if t.dtype != _F32:
         t = t.float()
     return t.contiguous()
+
+
+def pitch_shifts(pitch_shift, B):
+    """convert's pitch_shift, parsed on the host (no device work): a float / 0-d tensor -> (pitch_shift, None); a sequence / 1-D tensor of one
+    shift per row -> (0.0, [B floats]).  ValueError for any other form or length."""
+    if isinstance(pitch_shift, torch.Tensor):
+        if pitch_shift.dim() == 0:
+            return float(pitch_shift), None
+        if pitch_shift.dim() != 1:
+            raise ValueError("pitch_shift: a float or a 1-D sequence of one shift per row")
+        pitch_shift = pitch_shift.detach().cpu().tolist()
+    if not hasattr(pitch_shift, "__len__"):
+        return float(pitch_shift), None
+    sh = [float(x) for x in pitch_shift]
+    if len(sh) != B:
+        raise ValueError(f"pitch_shift: {len(sh)} shifts for a batch of {B}")
+    return 0.0, sh
+
+
+# the C names of a conversion / a match: (how the index is given, ragged) -> (tvc_workspace_bytes* query, entry).  Nothing else decides them.
+_CONVERT = {
+    ("shared", False): ("tvc_workspace_bytes", "tvc_convert_f32"),
+    ("shared", True): ("tvc_workspace_bytes_ragged", "tvc_convert_ragged_f32"),
+    ("table", False): ("tvc_workspace_bytes_multi", "tvc_convert_multi_f32"),
+    ("table", True): ("tvc_workspace_bytes_ragged_multi", "tvc_convert_ragged_multi_f32"),
+    ("blend", False): ("tvc_workspace_bytes_blend", "tvc_convert_blend_f32"),
+    ("blend", True): ("tvc_workspace_bytes_ragged_blend", "tvc_convert_ragged_blend_f32"),
+    ("auto", False): ("tvc_workspace_bytes_auto", "tvc_convert_auto_f32"),
+    ("auto", True): ("tvc_workspace_bytes_ragged_auto", "tvc_convert_ragged_auto_f32"),
+}
+_MATCH = {
+    "shared": ("tvc_workspace_bytes", "tvc_knn_match_f32"),
+    "table": ("tvc_workspace_bytes_multi", "tvc_knn_match_multi_f32"),
+    "blend": ("tvc_workspace_bytes_blend", "tvc_knn_match_blend_f32"),
+}
 
 
 def pitch_class_table():
@@ -298,18 +337,7 @@ class Engine:
         weakref.finalize(blob, _forget_blob, weakref.ref(self), blob.data_ptr()).atexit = False
         return blob
 
-    def knn_match(self, src, prepared, N, want_indices=False):
-        src = _prep(src, "source", self.device)
-        B, C, T = src.shape
-        if C != spec.SSL_DIM:
-            raise ValueError(f"source must have {spec.SSL_DIM} channels")
-        out = torch.empty_like(src)
-        idx = torch.empty(B, T, 4, dtype=torch.int64, device=self.device) if want_indices else None
-        p, n = self._wsargs(B, T * spec.HOP, N)
-        self._ok(self.lib.tvc_knn_match_f32(self.ctx, self._stream(), _ptr(src), _ptr(prepared), N, _ptr(out), _ptr(idx), B, T, p, n), "tvc_knn_match_f32")
-        return (out, idx) if want_indices else out
-
-    # ---- one prepared index per row (tvc_*_multi) ----
+    # ---- the index of a call: shared (one blob), table (one per row), blend (M weighted per row), auto (table or blend + target registers) ----
     def _table(self, prepared, Ns, B):
         """(blob tensors, Ns) of B rows -> host arrays (void* [B], int64 [B]); the blobs must be 1-D float tensors on this device."""
         prepared, Ns = list(prepared), [int(n) for n in Ns]
@@ -319,21 +347,40 @@ class Engine:
             _check_dev(t, f"prepared[{b}]", self.device)
         return (ctypes.c_void_p * B)(*[t.data_ptr() for t in prepared]), (ctypes.c_int64 * B)(*Ns)
 
-    @staticmethod
-    def _shifts(pitch_shift, B):
-        """float -> (pitch_shift, NULL); a sequence / 1-D tensor of B floats -> (0, float [B])."""
-        if isinstance(pitch_shift, torch.Tensor):
-            if pitch_shift.dim() == 0:
-                return float(pitch_shift), None
-            pitch_shift = pitch_shift.detach().cpu().reshape(-1).tolist() if pitch_shift.dim() == 1 else None
-            if pitch_shift is None:
-                raise ValueError("pitch_shift: a float or a 1-D sequence of one shift per row")
-        if not hasattr(pitch_shift, "__len__"):
-            return float(pitch_shift), None
-        sh = [float(x) for x in pitch_shift]
-        if len(sh) != B:
-            raise ValueError(f"pitch_shift: {len(sh)} shifts for {B} rows")
-        return 0.0, (ctypes.c_float * B)(*sh)
+    def _blend_args(self, prepared, Ns, weights, B):
+        """(flat row-major [B * M] blob tensors and sizes, weights [B, M]) -> (void* [B * M], int64 [B * M], M).  The weights stay where they
+        are: a contiguous fp32 [B, M] tensor on this device that the kernels read when they run (so a captured graph follows in-place
+        changes) - anything else is refused here, never copied."""
+        _check_dev(weights, "weights", self.device)
+        if weights.dim() != 2 or weights.shape[0] != B or weights.dtype != _F32 or not weights.is_contiguous():
+            raise ValueError(f"weights must be a contiguous fp32 [B = {B}, M] tensor on the device, got {tuple(weights.shape)} {weights.dtype}")
+        M = weights.shape[1]
+        if not 1 <= M <= spec.BLEND_MAX:
+            raise ValueError(f"a blend takes 1 ... {spec.BLEND_MAX} terms per row, got {M}")
+        blobs, ns = self._table(prepared, Ns, B * M)
+        return blobs, ns, M
+
+    def _target_f0(self, target_f0, B):
+        """the target registers of a call: a contiguous fp32 [B] tensor on this device, used in place (the kernels read it when they run)"""
+        _check_dev(target_f0, "target_f0", self.device)
+        if target_f0.dtype != _F32 or target_f0.dim() != 1 or target_f0.shape[0] != B or not target_f0.is_contiguous():
+            raise ValueError(f"target_f0 must be a contiguous fp32 [B = {B}] tensor on the device, got {tuple(target_f0.shape)} {target_f0.dtype}")
+        return target_f0
+
+    def _index_args(self, form, prepared, Ns, weights, B):
+        """The index of a call, checked on the host -> (what the entry takes for it, what its workspace query takes for it).  shared:
+        (prepared, Ns) = one blob and its N; table: one blob and N per row; blend: weights [B, M] on the device, prepared / Ns row-major
+        [B * M]; auto: the blend form, or with weights None the table form as M = 1."""
+        if form == "shared":
+            return (_ptr(prepared), Ns), (int(max(Ns, 4)),)
+        if form == "table":
+            blobs, ns = self._table(prepared, Ns, B)
+            return (blobs, ns), (ns,)
+        if form == "auto" and weights is None:
+            blobs, ns = self._table(prepared, Ns, B)
+            return (blobs, ns, 1, None), (ns, 1)
+        blobs, ns, M = self._blend_args(prepared, Ns, weights, B)
+        return (blobs, ns, M, _ptr(weights)), (ns, M)
 
     @staticmethod
     def _lens(lengths, B):
@@ -350,107 +397,98 @@ class Engine:
             raise ValueError("the padded length must be a multiple of 480" if ragged else "waveform length must be a multiple of 480 (autopad_waveform)")
         return wav, B, L
 
-    def knn_match_multi(self, src, prepared, Ns, want_indices=False):
-        """src [B, 768, T]; row b searches prepared[b] (a blob of knn_prepare, Ns[b] vectors) -> matched [B, 768, T] (, indices [B, T, 4]):
-        one call, every row equal to its own knn_match."""
+    # ---- kNN match: one driver, the public forms forward to it ----
+    def _match(self, form, src, prepared, Ns, weights=None, want_indices=False):
+        """src [B, 768, T] matched against the index (`form`, prepared, Ns, weights: _index_args) -> matched [B, 768, T] (, indices [B, T, 4];
+        [M, B, T, 4] for a blend: each term's own search)."""
         src = _prep(src, "source", self.device)
         B, C, T = src.shape
         if C != spec.SSL_DIM:
             raise ValueError(f"source must have {spec.SSL_DIM} channels")
-        blobs, ns = self._table(prepared, Ns, B)
+        index, sized = self._index_args(form, prepared, Ns, weights, B)
         out = torch.empty_like(src)
-        idx = torch.empty(B, T, 4, dtype=torch.int64, device=self.device) if want_indices else None
-        p, n = self._query_ws("tvc_workspace_bytes_multi", B, T * spec.HOP, ns)
-        self._ok(self.lib.tvc_knn_match_multi_f32(self.ctx, self._stream(), _ptr(src), blobs, ns, _ptr(out), _ptr(idx), B, T, p, n), "tvc_knn_match_multi_f32")
+        terms = sized[1:]      # (M,) for a blend, else ()
+        idx = torch.empty(*terms, B, T, 4, dtype=torch.int64, device=self.device) if want_indices else None
+        query, entry = _MATCH[form]
+        p, n = self._query_ws(query, B, T * spec.HOP, *sized)
+        self._ok(getattr(self.lib, entry)(self.ctx, self._stream(), _ptr(src), *index, _ptr(out), _ptr(idx), B, T, p, n), entry)
         return (out, idx) if want_indices else out
 
-    def convert_multi(self, wav, prepared, Ns, pitch_shift, noise_angle=None, out=None):
-        """convert with one prepared index per row (and pitch_shift a float or one per row): tvc_convert_multi_f32."""
-        wav, B, L = self._rows(wav)
-        blobs, ns = self._table(prepared, Ns, B)
-        shift, shifts = self._shifts(pitch_shift, B)
-        a, seed = self._angle(noise_angle, B, L // spec.HOP)
-        wave = out if out is not None else torch.empty(B, L, dtype=_F32, device=self.device)
-        p, n = self._query_ws("tvc_workspace_bytes_multi", B, L, ns)
-        self._ok(self.lib.tvc_convert_multi_f32(self.ctx, self._stream(), _ptr(wav), blobs, ns, shift, shifts, _ptr(a), seed, _ptr(wave), B, L, p, n),
-                 "tvc_convert_multi_f32")
-        return wave
+    def knn_match(self, src, prepared, N, want_indices=False):
+        return self._match("shared", src, prepared, N, None, want_indices)
 
-    def convert_ragged_multi(self, wav, lengths, prepared, Ns, pitch_shift, noise_angle=None):
-        """convert_ragged with one prepared index per row (and pitch_shift a float or one per row): tvc_convert_ragged_multi_f32."""
-        wav, B, Lmax = self._rows(wav, ragged=True)
-        lens = self._lens(lengths, B)
-        blobs, ns = self._table(prepared, Ns, B)
-        shift, shifts = self._shifts(pitch_shift, B)
-        a, seed = self._angle(noise_angle, B, Lmax // spec.HOP)
-        p, n = self._query_ws("tvc_workspace_bytes_ragged_multi", B, Lmax, lens, ns)
-        wave = torch.empty(B, Lmax, dtype=_F32, device=self.device)
-        self._ok(self.lib.tvc_convert_ragged_multi_f32(self.ctx, self._stream(), _ptr(wav), Lmax, lens, blobs, ns, shift, shifts, _ptr(a), seed,
-                                                       _ptr(wave), B, p, n), "tvc_convert_ragged_multi_f32")
-        return wave
-
-    # ---- a weighted blend of M prepared indices per row (tvc_*_blend) ----
-    def _blend_args(self, prepared, Ns, weights, B):
-        """(flat row-major [B * M] blob tensors and sizes, weights [B, M]) -> (void* [B * M], int64 [B * M], M).  The weights stay where they
-        are: a contiguous fp32 [B, M] tensor on this device that the kernels read when they run (so a captured graph follows in-place
-        changes) - anything else is refused here, never copied."""
-        _check_dev(weights, "weights", self.device)
-        if weights.dim() != 2 or weights.shape[0] != B or weights.dtype != _F32 or not weights.is_contiguous():
-            raise ValueError(f"weights must be a contiguous fp32 [B = {B}, M] tensor on the device, got {tuple(weights.shape)} {weights.dtype}")
-        M = weights.shape[1]
-        if not 1 <= M <= spec.BLEND_MAX:
-            raise ValueError(f"a blend takes 1 ... {spec.BLEND_MAX} terms per row, got {M}")
-        blobs, ns = self._table(prepared, Ns, B * M)
-        return blobs, ns, M
+    def knn_match_multi(self, src, prepared, Ns, want_indices=False):
+        """src [B, 768, T]; row b searches prepared[b] (a blob of knn_prepare, Ns[b] vectors) -> matched [B, 768, T] (, indices [B, T, 4]):
+        one call, every row equal to its own knn_match."""
+        return self._match("table", src, prepared, Ns, None, want_indices)
 
     def knn_match_blend(self, src, prepared, Ns, weights, want_indices=False):
         """src [B, 768, T]; term m of row b is prepared[b * M + m] (Ns likewise), weights [B, M] on the device -> matched [B, 768, T] =
         w_0 * match_0 + w_1 * match_1 + ... in term order (, indices [M, B, T, 4]: each term's own search): tvc_knn_match_blend_f32."""
-        src = _prep(src, "source", self.device)
-        B, C, T = src.shape
-        if C != spec.SSL_DIM:
-            raise ValueError(f"source must have {spec.SSL_DIM} channels")
-        blobs, ns, M = self._blend_args(prepared, Ns, weights, B)
-        out = torch.empty_like(src)
-        idx = torch.empty(M, B, T, 4, dtype=torch.int64, device=self.device) if want_indices else None
-        p, n = self._query_ws("tvc_workspace_bytes_blend", B, T * spec.HOP, ns, M)
-        self._ok(self.lib.tvc_knn_match_blend_f32(self.ctx, self._stream(), _ptr(src), blobs, ns, M, _ptr(weights), _ptr(out), _ptr(idx), B, T, p, n),
-                 "tvc_knn_match_blend_f32")
-        return (out, idx) if want_indices else out
+        return self._match("blend", src, prepared, Ns, weights, want_indices)
+
+    # ---- convert: one driver, the eight public forms forward to it ----
+    def _convert(self, form, wav, prepared, Ns, pitch_shift, noise_angle=None, lengths=None, weights=None, target_f0=None, out=None, shift_out=None):
+        """wav [B, L] converted toward the index (`form`, prepared, Ns, weights: _index_args) -> wave [B, L]; form "auto" -> (wave, shifts [B]).
+        lengths: a ragged batch (row b holds an utterance of lengths[b] samples, a multiple of 480, zero-padded behind it; every utterance
+        is converted over its OWN length).  pitch_shift: a float, or one per row for every form but "shared".  Every host check comes
+        first, then the noise draw (which advances torch's generator), then device work: a refused call leaves no trace."""
+        ragged = lengths is not None
+        wav, B, L = self._rows(wav, ragged)
+        lens = (self._lens(lengths, B),) if ragged else ()
+        index, sized = self._index_args(form, prepared, Ns, weights, B)
+        if form == "auto":
+            index += (_ptr(self._target_f0(target_f0, B)),)
+        shift, shifts = pitch_shifts(pitch_shift, B)
+        if form == "shared" and shifts is not None:
+            raise ValueError("pitch_shift: one shared index takes one shift (a shift per row takes an index per row)")
+        shift_args = (shift,) if form == "shared" else (shift, _floats(shifts))
+        a, seed = self._angle(noise_angle, B, L // spec.HOP)
+        wave = out if out is not None else torch.empty(B, L, dtype=_F32, device=self.device)
+        if form == "auto":
+            sh = shift_out if shift_out is not None else torch.empty(B, dtype=_F32, device=self.device)
+            shift_args += (_ptr(sh),)
+        query, entry = _CONVERT[form, ragged]
+        p, n = self._query_ws(query, B, L, *lens, *sized)
+        head, tail = ((_ptr(wav), L, *lens), (B, p, n)) if ragged else ((_ptr(wav),), (B, L, p, n))
+        self._ok(getattr(self.lib, entry)(self.ctx, self._stream(), *head, *index, *shift_args, _ptr(a), seed, _ptr(wave), *tail), entry)
+        return (wave, sh) if form == "auto" else wave
+
+    def convert(self, wav, prepared, N, pitch_shift, noise_angle=None, out=None):
+        return self._convert("shared", wav, prepared, N, pitch_shift, noise_angle, out=out)
+
+    def convert_ragged(self, wav, lengths, prepared, N, pitch_shift, noise_angle=None):
+        """wav [B, Lmax] (row b holds an utterance of lengths[b] samples, a multiple of 480, zero-padded behind it) -> [B, Lmax]:
+        every utterance converted over its OWN length (tvc_convert_ragged_f32: per-utterance lengths inside the kernels)."""
+        return self._convert("shared", wav, prepared, N, pitch_shift, noise_angle, lengths)
+
+    def convert_multi(self, wav, prepared, Ns, pitch_shift, noise_angle=None, out=None):
+        """convert with one prepared index per row (and pitch_shift a float or one per row): tvc_convert_multi_f32."""
+        return self._convert("table", wav, prepared, Ns, pitch_shift, noise_angle, out=out)
+
+    def convert_ragged_multi(self, wav, lengths, prepared, Ns, pitch_shift, noise_angle=None):
+        """convert_ragged with one prepared index per row (and pitch_shift a float or one per row): tvc_convert_ragged_multi_f32."""
+        return self._convert("table", wav, prepared, Ns, pitch_shift, noise_angle, lengths)
 
     def convert_blend(self, wav, prepared, Ns, weights, pitch_shift, noise_angle=None, out=None):
         """convert toward a weighted blend of M prepared indices per row (pitch_shift a float or one per row): tvc_convert_blend_f32."""
-        wav, B, L = self._rows(wav)
-        blobs, ns, M = self._blend_args(prepared, Ns, weights, B)
-        shift, shifts = self._shifts(pitch_shift, B)
-        a, seed = self._angle(noise_angle, B, L // spec.HOP)
-        wave = out if out is not None else torch.empty(B, L, dtype=_F32, device=self.device)
-        p, n = self._query_ws("tvc_workspace_bytes_blend", B, L, ns, M)
-        self._ok(self.lib.tvc_convert_blend_f32(self.ctx, self._stream(), _ptr(wav), blobs, ns, M, _ptr(weights), shift, shifts, _ptr(a), seed, _ptr(wave),
-                                                B, L, p, n), "tvc_convert_blend_f32")
-        return wave
+        return self._convert("blend", wav, prepared, Ns, pitch_shift, noise_angle, weights=weights, out=out)
 
     def convert_ragged_blend(self, wav, lengths, prepared, Ns, weights, pitch_shift, noise_angle=None):
         """convert_ragged toward a weighted blend of M prepared indices per row: tvc_convert_ragged_blend_f32."""
-        wav, B, Lmax = self._rows(wav, ragged=True)
-        lens = self._lens(lengths, B)
-        blobs, ns, M = self._blend_args(prepared, Ns, weights, B)
-        shift, shifts = self._shifts(pitch_shift, B)
-        a, seed = self._angle(noise_angle, B, Lmax // spec.HOP)
-        p, n = self._query_ws("tvc_workspace_bytes_ragged_blend", B, Lmax, lens, ns, M)
-        wave = torch.empty(B, Lmax, dtype=_F32, device=self.device)
-        self._ok(self.lib.tvc_convert_ragged_blend_f32(self.ctx, self._stream(), _ptr(wav), Lmax, lens, blobs, ns, M, _ptr(weights), shift, shifts, _ptr(a),
-                                                       seed, _ptr(wave), B, p, n), "tvc_convert_ragged_blend_f32")
-        return wave
+        return self._convert("blend", wav, prepared, Ns, pitch_shift, noise_angle, lengths, weights)
 
-    # ---- automatic pitch: the shift that moves a row's register onto its target's (tvc_pitch_match_f32, tvc_*_auto) ----
-    def _target_f0(self, target_f0, B):
-        """the target registers of a call: a contiguous fp32 [B] tensor on this device, used in place (the kernels read it when they run)"""
-        _check_dev(target_f0, "target_f0", self.device)
-        if target_f0.dtype != _F32 or target_f0.dim() != 1 or target_f0.shape[0] != B or not target_f0.is_contiguous():
-            raise ValueError(f"target_f0 must be a contiguous fp32 [B = {B}] tensor on the device, got {tuple(target_f0.shape)} {target_f0.dtype}")
-        return target_f0
+    def convert_auto(self, wav, prepared, Ns, target_f0, pitch_shift=0.0, weights=None, noise_angle=None, out=None, shift_out=None):
+        """convert_multi (weights None: one prepared index per row) or convert_blend (weights [B, M] on the device, prepared / Ns [B * M]) with the
+        shift found on the device: row b is shifted by pitch_shift (a float or one per row, now the offset) + 12 log2(target_f0[b] / the
+        lower median of the row's own voiced f0) -> (wave [B, L], shifts [B] on the device): tvc_convert_auto_f32."""
+        return self._convert("auto", wav, prepared, Ns, pitch_shift, noise_angle, None, weights, target_f0, out, shift_out)
 
+    def convert_ragged_auto(self, wav, lengths, prepared, Ns, target_f0, pitch_shift=0.0, weights=None, noise_angle=None):
+        """convert_auto over a ragged batch (every utterance's register is the median over its OWN frames): tvc_convert_ragged_auto_f32."""
+        return self._convert("auto", wav, prepared, Ns, pitch_shift, noise_angle, lengths, weights, target_f0)
+
+    # ---- the pitch register of rows of f0, and the shift onto a target's (tvc_pitch_match_f32) ----
     def pitch_match(self, f0, row_start=None, target_f0=None, pitch_shift=0.0, want_shifted=False):
         """The pitch register of rows of f0, and the shift onto a target's: f0 [B, 1, T] / [B, T] (every row a run of T columns), or any
         contiguous f0 with row_start = rows + 1 ascending column numbers (row b = [row_start[b], row_start[b + 1]) of the flattened f0) ->
@@ -467,52 +505,15 @@ class Engine:
         rows = len(row_start) - 1
         if rows < 1 or row_start[0] < 0 or row_start[-1] > f0.numel() or any(a > b for a, b in zip(row_start, row_start[1:])):
             raise ValueError(f"pitch_match: row_start must be rows + 1 ascending column numbers within the {f0.numel()} values of f0")
-        shift, shifts = self._shifts(pitch_shift, rows)
+        shift, shifts = pitch_shifts(pitch_shift, rows)
         tgt = self._target_f0(target_f0, rows) if target_f0 is not None else None
         med = torch.empty(rows, dtype=_F32, device=self.device)
         voiced = torch.empty(rows, dtype=torch.int32, device=self.device)
         sh = torch.empty(rows, dtype=_F32, device=self.device)
         out = torch.zeros_like(f0) if want_shifted else None
-        self._ok(self.lib.tvc_pitch_match_f32(self.ctx, self._stream(), _ptr(f0), (ctypes.c_int64 * (rows + 1))(*row_start), rows, _ptr(tgt), shift, shifts,
+        self._ok(self.lib.tvc_pitch_match_f32(self.ctx, self._stream(), _ptr(f0), (ctypes.c_int64 * (rows + 1))(*row_start), rows, _ptr(tgt), shift, _floats(shifts),
                                               _ptr(med), _ptr(voiced), _ptr(sh), _ptr(out)), "tvc_pitch_match_f32")
         return med, voiced, sh, out
-
-    def _auto_index(self, prepared, Ns, weights, B):
-        if weights is None:
-            blobs, ns = self._table(prepared, Ns, B)
-            return blobs, ns, 1
-        return self._blend_args(prepared, Ns, weights, B)
-
-    def convert_auto(self, wav, prepared, Ns, target_f0, pitch_shift=0.0, weights=None, noise_angle=None, out=None, shift_out=None):
-        """convert_multi (weights None: one prepared index per row) or convert_blend (weights [B, M] on the device, prepared / Ns [B * M]) with the
-        shift found on the device: row b is shifted by pitch_shift (a float or one per row, now the offset) + 12 log2(target_f0[b] / the
-        lower median of the row's own voiced f0) -> (wave [B, L], shifts [B] on the device): tvc_convert_auto_f32."""
-        wav, B, L = self._rows(wav)
-        blobs, ns, M = self._auto_index(prepared, Ns, weights, B)
-        tgt = self._target_f0(target_f0, B)
-        shift, shifts = self._shifts(pitch_shift, B)
-        a, seed = self._angle(noise_angle, B, L // spec.HOP)
-        wave = out if out is not None else torch.empty(B, L, dtype=_F32, device=self.device)
-        sh = shift_out if shift_out is not None else torch.empty(B, dtype=_F32, device=self.device)
-        p, n = self._query_ws("tvc_workspace_bytes_auto", B, L, ns, M)
-        self._ok(self.lib.tvc_convert_auto_f32(self.ctx, self._stream(), _ptr(wav), blobs, ns, M, _ptr(weights), _ptr(tgt), shift, shifts, _ptr(sh), _ptr(a), seed,
-                                               _ptr(wave), B, L, p, n), "tvc_convert_auto_f32")
-        return wave, sh
-
-    def convert_ragged_auto(self, wav, lengths, prepared, Ns, target_f0, pitch_shift=0.0, weights=None, noise_angle=None):
-        """convert_auto over a ragged batch (every utterance's register is the median over its OWN frames): tvc_convert_ragged_auto_f32."""
-        wav, B, Lmax = self._rows(wav, ragged=True)
-        lens = self._lens(lengths, B)
-        blobs, ns, M = self._auto_index(prepared, Ns, weights, B)
-        tgt = self._target_f0(target_f0, B)
-        shift, shifts = self._shifts(pitch_shift, B)
-        a, seed = self._angle(noise_angle, B, Lmax // spec.HOP)
-        p, n = self._query_ws("tvc_workspace_bytes_ragged_auto", B, Lmax, lens, ns, M)
-        wave = torch.empty(B, Lmax, dtype=_F32, device=self.device)
-        sh = torch.empty(B, dtype=_F32, device=self.device)
-        self._ok(self.lib.tvc_convert_ragged_auto_f32(self.ctx, self._stream(), _ptr(wav), Lmax, lens, blobs, ns, M, _ptr(weights), _ptr(tgt), shift, shifts,
-                                                      _ptr(sh), _ptr(a), seed, _ptr(wave), B, p, n), "tvc_convert_ragged_auto_f32")
-        return wave, sh
 
     # ---- index-sharded match (one prepared index shard per rank; merged by parallel.match_features_sharded) ----
     METRICS = {"cos": 0, "IP": 1, "L2": 2}
@@ -739,26 +740,6 @@ class Engine:
         p, n = self._wsargs(B, T * spec.HOP)
         self._ok(self.lib.tvc_dsp_f32(self.ctx, self._stream(), _ptr(f0), _ptr(amps), _ptr(kernel), _ptr(a), seed, _ptr(source), B, T, p, n), "tvc_dsp_f32")
         return source
-
-    def convert(self, wav, prepared, N, pitch_shift, noise_angle=None, out=None):
-        wav, B, L = self._rows(wav)
-        a, seed = self._angle(noise_angle, B, L // spec.HOP)
-        wave = out if out is not None else torch.empty(B, L, dtype=_F32, device=self.device)
-        p, n = self._wsargs(B, L, N)
-        self._ok(self.lib.tvc_convert_f32(self.ctx, self._stream(), _ptr(wav), _ptr(prepared), N, float(pitch_shift), _ptr(a), seed, _ptr(wave), B, L, p, n), "tvc_convert_f32")
-        return wave
-
-    def convert_ragged(self, wav, lengths, prepared, N, pitch_shift, noise_angle=None):
-        """wav [B, Lmax] (row b holds an utterance of lengths[b] samples, a multiple of 480, zero-padded behind it) -> [B, Lmax]:
-        every utterance converted over its OWN length (tvc_convert_ragged_f32: per-utterance lengths inside the kernels)."""
-        wav, B, Lmax = self._rows(wav, ragged=True)
-        lens = self._lens(lengths, B)
-        a, seed = self._angle(noise_angle, B, Lmax // spec.HOP)
-        p, n = self._query_ws("tvc_workspace_bytes_ragged", B, Lmax, lens, int(max(N, 4)))
-        wave = torch.empty(B, Lmax, dtype=_F32, device=self.device)
-        self._ok(self.lib.tvc_convert_ragged_f32(self.ctx, self._stream(), _ptr(wav), Lmax, lens, _ptr(prepared), N, float(pitch_shift), _ptr(a), seed,
-                                                 _ptr(wave), B, p, n), "tvc_convert_ragged_f32")
-        return wave
 
     def stream_push(self, buf, blocks):
         """buf [S, n] <- (buf[:, m:], blocks [S, m]) in place, one launch for any buffer length n >= m (stream.py:69-70's roll + slice

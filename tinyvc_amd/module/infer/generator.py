@@ -1,28 +1,21 @@
-"""Generator = encoder -> kNN match -> pitch shift -> decoder (reference module/infer/generator.py:12-34),
-one tvc_convert_f32 call per batch."""
+"""Generator = encoder -> kNN match -> pitch shift -> decoder (reference module/infer/generator.py:12-34): whatever form the target takes,
+`convert` is one host path that ends in one call of the tvc_convert*_f32 entry that form belongs to (Engine._convert)."""
 import torch
 
 from .. import utils
+from ...engine import pitch_shifts
 from .._base import HipModule
 from ..tinyvc import Decoder, Encoder
-from ..tinyvc.feature_retrieval import (Blend, check_blend, check_references, prepare_reference, prepare_references, resolve_auto_pitch,
+from ..tinyvc.feature_retrieval import (check_blend, check_references, prepare_reference, prepare_references, resolve_auto_pitch, target_form,
                                         target_registers)
 
 
-def _per_row_shift(pitch_shift, B):
-    """None for a scalar shift; else the list of B floats (a sequence or 1-D tensor), checked on the host."""
-    if isinstance(pitch_shift, torch.Tensor):
-        if pitch_shift.dim() == 0:
-            return None
-        if pitch_shift.dim() != 1:
-            raise ValueError("pitch_shift: a float or a 1-D sequence of one shift per row")
-        pitch_shift = pitch_shift.detach().cpu().tolist()
-    if not hasattr(pitch_shift, "__len__"):
-        return None
-    sh = [float(x) for x in pitch_shift]
-    if len(sh) != B:
-        raise ValueError(f"pitch_shift: {len(sh)} shifts for a batch of {B}")
-    return sh
+def _padded_lengths(lengths, B, L):
+    """a ragged batch's lengths, each rounded up to whole frames: one per row, each in (960, L]"""
+    lens = [-(-int(n) // 480) * 480 for n in lengths]
+    if len(lens) != B or max(lens) > L or min(lens) <= 960:
+        raise ValueError("lengths: one entry per row, each in (960, L]")
+    return lens
 
 
 class Generator(HipModule):
@@ -57,10 +50,7 @@ class Generator(HipModule):
         (Engine.encode_ragged); what build_index selects its columns from."""
         wf = utils.autopad_waveform(self._input_device(wf))
         B, L = wf.shape
-        lens = [-(-int(n) // 480) * 480 for n in lengths]
-        if len(lens) != B or max(lens) > L or min(lens) <= 960:
-            raise ValueError("lengths: one entry per row, each in (960, L]")
-        return self.engine(wf.device).encode_ragged(wf, lens)
+        return self.engine(wf.device).encode_ragged(wf, _padded_lengths(lengths, B, L))
 
     @torch.no_grad()
     def convert(self, wf, tgt, pitch_shift, f0_estimation="default", device=None, noise_angle=None, lengths=None, auto_pitch=None,
@@ -85,98 +75,38 @@ class Generator(HipModule):
         build_index and the entry scripts' loaders attach it).  True is refused (ValueError, before any engine work) for a target without a
         register and for a Blend, which takes an explicit register.  `pitch_shift` then is the offset on top of the automatic shift.
         `return_shift=True` -> (wave, shifts [B] on the device: the semitones applied to each row)."""
+        # 1. classify the target once; malformed targets, registers and shift lists are refused before any engine or device work
         B = wf.shape[0] if wf.dim() == 2 else 1
-        if auto_pitch is not None and auto_pitch is not False:
-            return self._convert_auto(wf, tgt, pitch_shift, noise_angle, lengths, B, auto_pitch, return_shift)
-        if return_shift:
+        auto = auto_pitch is not None and auto_pitch is not False
+        if return_shift and not auto:
             raise ValueError("return_shift needs auto_pitch: without it the shifts are the caller's own pitch_shift")
-        if isinstance(tgt, Blend):
-            return self._convert_blend(wf, tgt, pitch_shift, noise_angle, lengths, B)
-        multi = isinstance(tgt, (list, tuple)) or (isinstance(tgt, torch.Tensor) and tgt.dim() == 3 and tgt.shape[0] != 1)
-        if multi:
-            check_references(tgt, B)           # malformed tables / shift lists are refused before any engine or device work
-        shifts = _per_row_shift(pitch_shift, B)
-        wf = utils.autopad_waveform(self._input_device(wf))
-        eng = self.engine(wf.device)
-        B, L = wf.shape
-        if noise_angle is not None:
-            noise_angle = self._input_device(noise_angle)
-        if multi:
-            tgt = [self._input_device(t) for t in tgt] if isinstance(tgt, (list, tuple)) else self._input_device(tgt)
-        else:
-            tgt = self._input_device(tgt)
-        lens = None
-        if lengths is not None:
-            lens = [-(-int(n) // 480) * 480 for n in lengths]
-            if len(lens) != B or max(lens) > L or min(lens) <= 960:
-                raise ValueError("lengths: one entry per row, each in (960, L]")
-        if not multi and shifts is None:
-            blob, n = prepare_reference(tgt)
-            if lens is not None:
-                return eng.convert_ragged(wf, lens, blob, n, pitch_shift, noise_angle)
-            return eng.convert(wf, blob, n, pitch_shift, noise_angle)
-        if multi:
-            blobs, ns = prepare_references(tgt)
-        else:                                   # one shared index, a shift per row: the shared blob in every row (one segment)
-            blob, n = prepare_reference(tgt)
-            blobs, ns = [blob] * B, [n] * B
-        shift = shifts if shifts is not None else float(pitch_shift)
-        if lens is not None:
-            return eng.convert_ragged_multi(wf, lens, blobs, ns, shift, noise_angle)
-        return eng.convert_multi(wf, blobs, ns, shift, noise_angle)
-
-    def _convert_blend(self, wf, blend, pitch_shift, noise_angle, lengths, B):
-        check_blend(blend.terms, blend._given, B)      # malformed blends / shift lists are refused before any engine or device work
-        shifts = _per_row_shift(pitch_shift, B)
-        wf = utils.autopad_waveform(self._input_device(wf))
-        eng = self.engine(wf.device)
-        B, L = wf.shape
-        if noise_angle is not None:
-            noise_angle = self._input_device(noise_angle)
-        lens = None
-        if lengths is not None:
-            lens = [-(-int(n) // 480) * 480 for n in lengths]
-            if len(lens) != B or max(lens) > L or min(lens) <= 960:
-                raise ValueError("lengths: one entry per row, each in (960, L]")
-        blobs, ns, w = blend.resolve(B, wf.device, self._input_device)
-        shift = shifts if shifts is not None else float(pitch_shift)
-        if lens is not None:
-            return eng.convert_ragged_blend(wf, lens, blobs, ns, w, shift, noise_angle)
-        return eng.convert_blend(wf, blobs, ns, w, shift, noise_angle)
-
-    def _convert_auto(self, wf, tgt, pitch_shift, noise_angle, lengths, B, auto_pitch, return_shift):
-        """convert with the shift found on the device: every form of tgt, as the table form of the blend entries (M = 1 without weights)"""
-        blend = isinstance(tgt, Blend)
-        multi = not blend and (isinstance(tgt, (list, tuple)) or (isinstance(tgt, torch.Tensor) and tgt.dim() == 3 and tgt.shape[0] != 1))
-        # malformed targets, registers and shift lists are refused before any engine or device work
-        if blend:
+        form = target_form(tgt)[0]
+        if form == "blend":
             check_blend(tgt.terms, tgt._given, B)
-        elif multi:
+        elif form == "table":
             check_references(tgt, B)
-        regs = resolve_auto_pitch(auto_pitch, tgt, B)
-        shifts = _per_row_shift(pitch_shift, B)
+        regs = resolve_auto_pitch(auto_pitch, tgt, B) if auto else None
+        shift, shifts = pitch_shifts(pitch_shift, B)
+        # 2. the inputs, on the device
         wf = utils.autopad_waveform(self._input_device(wf))
         eng = self.engine(wf.device)
         B, L = wf.shape
         if noise_angle is not None:
             noise_angle = self._input_device(noise_angle)
-        lens = None
-        if lengths is not None:
-            lens = [-(-int(n) // 480) * 480 for n in lengths]
-            if len(lens) != B or max(lens) > L or min(lens) <= 960:
-                raise ValueError("lengths: one entry per row, each in (960, L]")
+        lens = _padded_lengths(lengths, B, L) if lengths is not None else None
+        # 3. the target as prepared blobs: (blob, n) of a shared index, or the tables of B rows (x M terms and their weights for a blend)
         w = None
-        if blend:
+        if form == "blend":
             blobs, ns, w = tgt.resolve(B, wf.device, self._input_device)
-        elif multi:
+        elif form == "table":
             blobs, ns = prepare_references([self._input_device(t) for t in tgt] if isinstance(tgt, (list, tuple)) else self._input_device(tgt))
         else:
-            blob, n = prepare_reference(self._input_device(tgt))
-            blobs, ns = [blob] * B, [n] * B
-        f0t = target_registers(regs, B, wf.device)
-        shift = shifts if shifts is not None else float(pitch_shift)
-        if lens is not None:
-            wave, sh = eng.convert_ragged_auto(wf, lens, blobs, ns, f0t, shift, w, noise_angle)
-        else:
-            wave, sh = eng.convert_auto(wf, blobs, ns, f0t, shift, w, noise_angle)
+            blobs, ns = prepare_reference(self._input_device(tgt))
+            if auto or shifts is not None:      # a shift per row (given, or found on the device): the shared blob in every row (one segment)
+                form, blobs, ns = "table", [blobs] * B, [ns] * B
+        # 4. one engine call
+        pitch = shift if shifts is None else shifts
+        if not auto:
+            return eng._convert(form, wf, blobs, ns, pitch, noise_angle, lens, w)
+        wave, sh = eng._convert("auto", wf, blobs, ns, pitch, noise_angle, lens, w, target_registers(regs, B, wf.device))
         return (wave, sh) if return_shift else wave

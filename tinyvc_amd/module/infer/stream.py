@@ -5,7 +5,8 @@ the lag arg-max kept on the device."""
 import numpy as np
 import torch
 
-from ..tinyvc.feature_retrieval import Blend
+from ...engine import pitch_shifts
+from ..tinyvc.feature_retrieval import target_form
 from .generator import Generator
 
 
@@ -69,16 +70,13 @@ class BatchedStreamInfer:
         freed - when a parameter changes), the engine's scratch workspace (re-allocated when another call needs a bigger
         one), the prepared index riding on `target`, plus the scalars captured by value."""
         eng = self.generator.engine(self.device)          # re-packs the weights first if a parameter changed
-        ws, tgt = eng._ws, self.target
-        tgts = tgt if isinstance(tgt, (list, tuple)) else [tgt]      # one index per stream: every blob's tensor
+        ws = eng._ws
+        form, tgts = target_form(self.target)      # every blob's tensor
         wkey = 0
-        if isinstance(tgt, Blend):      # every term's tensors, and WHERE the weights live - not their version or values: the kernels read them at replay
-            tgts = tgt.term_tensors()
-            wkey = tgt.resolve(self.n_streams, self.device, self.generator._input_device)[2].data_ptr()
-        ps = self.pitch_shift
-        if isinstance(ps, torch.Tensor):
-            ps = ps.detach().cpu().reshape(-1).tolist()
-        shifts = tuple(float(x) for x in ps) if hasattr(ps, "__len__") else float(ps)
+        if form == "blend":      # WHERE the weights live - not their version or values: the kernels read them at replay
+            wkey = self.target.resolve(self.n_streams, self.device, self.generator._input_device)[2].data_ptr()
+        shift, shifts = pitch_shifts(self.pitch_shift, self.n_streams)
+        shifts = shift if shifts is None else tuple(shifts)
         return (eng.weights_key, ws.data_ptr() if ws is not None else 0, ws.numel() if ws is not None else 0,
                 tuple((id(t), t._version, t.data_ptr()) for t in tgts), wkey, shifts, bool(self.use_phase_vocoder))
 

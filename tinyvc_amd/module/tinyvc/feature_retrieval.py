@@ -219,6 +219,18 @@ def add_auto_pitch_argument(parser):
                         help="move every file's median f0 onto the target speaker's (from the index's .f0.pt sidecar, or the -t recording); -p is added on top")
 
 
+def target_form(tgt):
+    """How convert reads its target -> ("blend" | "table" | "shared", the index tensors it consists of): a Blend; one index per row (a list /
+    tuple of tensors, or a 3-D tensor of more than one row); else one index shared by every row (not shape-checked on the host)."""
+    if isinstance(tgt, Blend):
+        return "blend", tgt.term_tensors()
+    if isinstance(tgt, (list, tuple)):
+        return "table", list(tgt)
+    if isinstance(tgt, torch.Tensor) and tgt.dim() == 3 and tgt.shape[0] != 1:
+        return "table", [tgt]
+    return "shared", [tgt]
+
+
 def check_references(tgt, B=None):
     """Shape check of a multi-index target, on the host (no engine, no device work): a [B, 768, N] tensor or a list of B [1, 768, N_b]
     tensors (fp32 or fp16).  Returns the number of indices; raises ValueError when the form is malformed or B does not match."""
