@@ -8,6 +8,7 @@
 
 #include <cstdlib>
 
+#include "knn_blob.h"
 #include "tvc_common.h"
 
 using namespace tvc;
@@ -45,14 +46,14 @@ static int blob_check(tvc_ctx* ctx, hipStream_t s, const void* p, int64_t N, con
     }
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return 0;
-    int h[6] = {0, 0, 0, 0, 0, 0};
+    int h[BLOB_WORDS] = {};
     if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(s) != hipSuccess || hipMemcpy(h, p, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess)
         return fail(ctx, TVC_ERR_HIP, "%s: cannot read the prepared index's header", what);
-    const int64_t n = ((int64_t)(unsigned)h[3] << 32) | (unsigned)h[2];
-    if (h[0] != tvc::kBlobMagic || (h[1] != 0 && h[1] != 1))
+    const int64_t n = ((int64_t)(unsigned)h[BLOB_W_N_HI] << 32) | (unsigned)h[BLOB_W_N_LO];
+    if (h[BLOB_W_MAGIC] != BLOB_MAGIC || (h[BLOB_W_KIND] != KIND_F32 && h[BLOB_W_KIND] != KIND_F16))
         return fail(ctx, TVC_ERR_ARG, "%s: `prepared` is not a blob of tvc_knn_prepare_index_f32 / _f16", what);
-    if (h[5] != tvc::kBlobVersion)
-        return fail(ctx, TVC_ERR_ARG, "%s: the prepared index has format version %d, this library writes and reads version %d: prepare it again", what, h[5], tvc::kBlobVersion);
+    if (h[BLOB_W_VERSION] != tvc::kBlobVersion)
+        return fail(ctx, TVC_ERR_ARG, "%s: the prepared index has format version %d, this library writes and reads version %d: prepare it again", what, h[BLOB_W_VERSION], tvc::kBlobVersion);
     if (n != N) return fail(ctx, TVC_ERR_ARG, "%s: this blob was prepared for N = %lld index vectors, the call says N = %lld", what, (long long)n, (long long)N);
     blob_record(p, N);
     return 0;
@@ -277,7 +278,7 @@ int tvc::convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const ConvertCall& c)
     }
     ws.release(m);
     TVC_CHECK(run_decoder(ctx, s, ws, matched, f0s, energy, c.angle, c.seed, c.wave, nullptr, nullptr, nullptr, B, T,
-                          ws.dry ? nullptr : (ix.per_row ? rowmax : knn_index_amax(ix.blob)), emax, ix.per_row ? 1 : 0));
+                          ws.dry ? nullptr : (ix.per_row ? rowmax : blob_amax(ix.blob)), emax, ix.per_row ? 1 : 0));
     ws.release(m);
     return 0;
 }
@@ -381,18 +382,11 @@ int tvc_pitch_decode_f32(tvc_ctx* ctx, void* stream, const float* logits, float*
 }
 
 int64_t tvc_knn_prepared_elems(int64_t N) {
-    if (N <= 0) return 0;
-    int64_t npad = (N + 127) / 128 * 128;
-    // header + raw rows [N][768] + split image of the normalised vectors (3 bf16 per value = 1.5 floats)
-    // + inverse norms [Npad] + fp16 image of the normalised vectors (the coarse pass's operand, half a float per value)
-    return 64 + N * (int64_t)kSslDim + (int64_t)kSslDim * npad * 3 / 2 + npad + (int64_t)kSslDim * npad / 2;
+    return N <= 0 ? 0 : blob_elems(KIND_F32, N);
 }
 
 int64_t tvc_knn_prepared_elems_f16(int64_t N) {
-    if (N <= 0) return 0;
-    int64_t npad = (N + 127) / 128 * 128;
-    // header + inverse norms [Npad] + fp16 image (half a float per value) + the largest inverse norm of every 128-vector tile
-    return 64 + npad + (int64_t)kSslDim * npad / 2 + npad / 128;
+    return N <= 0 ? 0 : blob_elems(KIND_F16, N);
 }
 
 int tvc_knn_prepare_index_f32(tvc_ctx* ctx, void* stream, const float* index, float* prepared, int64_t N) {

@@ -29,8 +29,6 @@ constexpr int IC_SCAN_PER = 16;        // elements per thread of the scan kernel
 constexpr int IC_SCAN_TILE = 256 * IC_SCAN_PER;
 constexpr long IC_HIST_MAX = 1L << 24; // histogram entries (clusters x chunks) the chunk count is chosen to stay under
 
-__device__ __forceinline__ long ic_npad(long N) { return (N + 127) / 128 * 128; }
-
 // ---- staging: raw rows -> columns ------------------------------------------------------------------------------------------------
 // dst[c * dstride + q] = row(n0 + q)[c] for q < ncols: rows of a blob of either kind (rows == nullptr), or plain fp32 rows [.][768].
 // A 64-row x 64-channel tile meets in LDS as [c][r] (rows padded by one float): fp32 rows are read with lanes along c (256-byte runs),
@@ -41,9 +39,9 @@ __global__ __launch_bounds__(256) void ic_stage_kernel(const float* __restrict__
     __shared__ float tile[64][65];
     const int t = threadIdx.x;
     const int q0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
-    const int kind = rows ? KIND_F32 : reinterpret_cast<const int*>(blob)[1];
+    const int kind = rows ? KIND_F32 : blob_kind(blob);
     if (kind == KIND_F16) {
-        const uint4* __restrict__ img = reinterpret_cast<const uint4*>(blob + HDR + ic_npad(N));
+        const uint4* __restrict__ img = blob_img16(blob, KIND_F16, N, blob_npad(N));
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int pt = i * 256 + t, r = pt & 63, pc = pt >> 6;          // 8 pieces of 8 channels per row of the tile
@@ -59,7 +57,8 @@ __global__ __launch_bounds__(256) void ic_stage_kernel(const float* __restrict__
             }
         }
     } else {
-        const float* __restrict__ base = rows ? rows : blob + HDR;
+        const float* own = blob_rows(blob);      // (taken unconditionally: the choice below stays a select)
+        const float* __restrict__ base = rows ? rows : own;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int e = i * 256 + t, r = e >> 6, c = e & 63;
@@ -81,9 +80,9 @@ __global__ __launch_bounds__(256) void ic_init_kernel(const float* __restrict__ 
     if (k >= K) return;
     long n = cols[k];
     n = n < 0 ? 0 : (n >= N ? N - 1 : n);
-    const int kind = reinterpret_cast<const int*>(blob)[1];
+    const int kind = blob_kind(blob);
     const int c = blockIdx.y;
-    cent[(long)c * K + k] = blob_row_value(blob, kind, N, ic_npad(N), n, c);
+    cent[(long)c * K + k] = blob_row_value(blob, kind, N, blob_npad(N), n, c);
 }
 
 // column 0 of a chunk's top-4 lists -> assign / sim; the entries that changed are counted with one integer atomic per wave
@@ -266,9 +265,9 @@ __global__ __launch_bounds__(256) void ic_mean_kernel(const float* __restrict__ 
     const int m1 = first[k] + (cnt < (r + 1) * IC_RUN ? cnt : (r + 1) * IC_RUN);
     const bool single = cnt <= IC_RUN;
     const double dn = (double)cnt;
-    const int kind = reinterpret_cast<const int*>(blob)[1];
+    const int kind = blob_kind(blob);
     if (kind == KIND_F16) {
-        const uint4* __restrict__ img = reinterpret_cast<const uint4*>(blob + HDR + ic_npad(N));
+        const uint4* __restrict__ img = blob_img16(blob, KIND_F16, N, blob_npad(N));
         const bool two = lane < 32;
         double acc[16];
 #pragma unroll
@@ -319,7 +318,7 @@ __global__ __launch_bounds__(256) void ic_mean_kernel(const float* __restrict__ 
             }
         }
     } else {
-        const float4* __restrict__ rows = reinterpret_cast<const float4*>(blob + HDR);
+        const float4* __restrict__ rows = reinterpret_cast<const float4*>(blob_rows(blob));
         double acc[12];
 #pragma unroll
         for (int i = 0; i < 12; ++i) acc[i] = 0.0;

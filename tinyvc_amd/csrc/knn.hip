@@ -5,6 +5,8 @@
 // (index vectors are the M axis, queries the N axis, so the 16 accumulator registers of a lane are 16 index vectors
 // against ONE query: the reduction is lane-local).  The index is split across workgroups for occupancy; a second kernel
 // merges the per-split candidates, emits int64 indices and gathers + averages the 4 raw index vectors.
+// This file is the search: query normalisation, the exact top-4 kernel, the two-stage coarse + rescore search and the host plan
+// (knn_search.h).  Prepared blobs are written by knn_prepare.hip (layout: knn_blob.h); the lists become results in knn_gather.hip.
 //
 // Similarities run on the split-precision path (conv3s.h): bf16 part-products, fp32 accumulation, error below an fp32
 // FMA chain's.  Two index storages share the kernels (the prepared blob is self-describing, so every entry point - and a
@@ -17,424 +19,14 @@
 //           bf16 parts, split while a tile is staged into LDS; five part-products per product; the similarity is
 //           dot(q_hat, r) * inv_norm; the gather reads the same image.
 // Tie-break: equal similarities -> lower index first (torch.topk leaves it unspecified).
-#include <hip/hip_fp16.h>
-
-#include <cstring>
-#include <vector>
-
 #include "knn_blob.h"
-#include "ragged.h"
-#include "small_kernels.h"
+#include "knn_search.h"
 #include "split_fp16.h"
 #include "tvc_common.h"
 
 namespace tvc {
 
 constexpr int KNN_BLOCKS = 1024;   // target workgroup count (query tiles x index splits)
-
-static inline int64_t npad128(int64_t N) { return (N + 127) / 128 * 128; }
-
-// ---- segments: one call, several prepared indices -------------------------------------------------------------------------
-// A segment is a maximal run of consecutive query columns that search the same blob (tvc_*_multi: one speaker index per row; a
-// ragged sub-batch's rows in its own order).  Query tiles (KNN_QT = C_QT = 256) never cross a segment; every pass is ONE launch
-// over the concatenated (segment, query tile, split) work units of the segments that take it, a workgroup finds its segment in the
-// unit prefix u[], and the per-query kernels (rescore, merge + gather) look it up in col2seg[].  Each segment has its own overflow
-// flag, so it takes exactly the path its own B = 1 call takes.  A call with one blob is one segment - the table then travels by
-// value in the kernel arguments (KnnSegs::one) and nothing is uploaded: the single-index launch sequence is the degenerate case.
-struct KnnSeg {
-    const float* blob;
-    int N, col0, ncols;        // query columns [col0, col0 + ncols) of the call
-    int two;                   // two-stage search (N >= KNN_COARSE_MIN); else the exact kernel only
-    int sample, t2;            // 256-vector tiles covered by coarse pass A / pass B
-    int nsA, tpsA, nsB, tpsB;  // coarse splits
-    int nsE, tpsE;             // exact kernel splits
-    int u[4];                  // first work unit of pass A, pass B and the exact kernel; [3]: first 256-query tile
-};
-static_assert(sizeof(KnnSeg) % sizeof(int) == 0, "uploaded as ints");
-struct KnnSegs {               // kernel argument
-    const KnnSeg* d;           // device table (n > 1)
-    int n;
-    KnnSeg one;                // the table when n == 1
-};
-// last segment whose key (u[F]; F == 4: col0) is <= v - segments without units of a launch share their successor's prefix and are skipped
-template <int F>
-__device__ __forceinline__ int seg_find(const KnnSegs& S, int v) {
-    if (S.n == 1) return 0;
-    int lo = 0, hi = S.n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        const int key = F == 4 ? S.d[mid].col0 : S.d[mid].u[F];
-        if (key <= v) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-// field by field: a select between the kernel-argument copy and the device table (selecting the whole struct put it on the stack)
-__device__ __forceinline__ KnnSeg seg_get(const KnnSegs& S, int i) {
-    KnnSeg g;
-    const bool one = S.n == 1;
-    const KnnSeg* __restrict__ d = S.d + (one ? 0 : i);
-#define TVC_SEG_FIELD(f) g.f = one ? S.one.f : d->f
-    TVC_SEG_FIELD(blob);
-    TVC_SEG_FIELD(N);
-    TVC_SEG_FIELD(col0);
-    TVC_SEG_FIELD(ncols);
-    TVC_SEG_FIELD(two);
-    TVC_SEG_FIELD(sample);
-    TVC_SEG_FIELD(t2);
-    TVC_SEG_FIELD(nsA);
-    TVC_SEG_FIELD(tpsA);
-    TVC_SEG_FIELD(nsB);
-    TVC_SEG_FIELD(tpsB);
-    TVC_SEG_FIELD(nsE);
-    TVC_SEG_FIELD(tpsE);
-    TVC_SEG_FIELD(u[0]);
-    TVC_SEG_FIELD(u[1]);
-    TVC_SEG_FIELD(u[2]);
-    TVC_SEG_FIELD(u[3]);
-#undef TVC_SEG_FIELD
-    return g;
-}
-__device__ __forceinline__ long seg_npad(const KnnSeg& g) { return ((long)g.N + 127) / 128 * 128; }
-
-static __global__ void blob_header_kernel(float* blob, int kind, long N) {
-    int* h = reinterpret_cast<int*>(blob);
-    if (threadIdx.x < HDR) h[threadIdx.x] = 0;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        h[0] = BLOB_MAGIC;
-        h[1] = kind;
-        h[2] = (int)(N & 0xffffffffL);
-        h[3] = (int)(N >> 32);
-        h[5] = kBlobVersion;
-    }
-}
-
-// fp32 storage.  index [768][N] (the [1,768,N] tensor of index.pt) -> raw rows + the bf16x3 image of v / (||v|| + 1e-6)
-// (feature_retrieval.py:25 recomputes that normalisation on every call).  One thread per vector; reads run along n.
-static __global__ void index_prepare_kernel(const float* __restrict__ index, float* __restrict__ rows,
-                                            unsigned short* __restrict__ img, float* __restrict__ inv, __half* __restrict__ img16,
-                                            long N, long Npad) {
-    long n = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    if (n >= Npad) return;
-    float den = 1.f;
-    if (n < N) {
-        float s = 0.f;
-        for (int k = 0; k < KD; ++k) {
-            float v = index[(long)k * N + n];
-            s = fmaf(v, v, s);
-        }
-        den = sqrtf(s) + 1e-6f;
-    }
-    inv[n] = n < N ? 1.f / den : 0.f;
-    for (int k = 0; k < KD; ++k) {
-        float raw = n < N ? index[(long)k * N + n] : 0.f;
-        if (n < N) rows[n * KD + k] = raw;
-        float v = raw / den;
-        img16[img_elem(n, k, 1)] = __float2half(v);      // the coarse pass's operand (knn_coarse_kernel)
-        __bf16 h1 = (__bf16)v;
-        float r = v - (float)h1;
-        __bf16 h2 = (__bf16)r;
-        float r2 = r - (float)h2;
-        __bf16 h3 = (__bf16)r2;
-        const long base = img_elem(n, k, 3);
-        img[base] = __builtin_bit_cast(unsigned short, h1);
-        img[base + 512] = __builtin_bit_cast(unsigned short, h2);
-        img[base + 1024] = __builtin_bit_cast(unsigned short, h3);
-    }
-}
-
-// fp16 storage.  rows16 [N][768] IEEE half (row-major: one vector per row) -> inverse norms + the fp16 image.
-// One wavefront per vector: lanes run along k (coalesced 128-byte reads), the norm is a fixed-order wave reduction.
-static __global__ __launch_bounds__(256) void index_prepare_f16_kernel(const __half* __restrict__ rows16, float* __restrict__ inv,
-                                                                       __half* __restrict__ img, long N, long Npad) {
-    const int lane = threadIdx.x & 63;
-    const long n = (blockIdx.x * (long)blockDim.x + threadIdx.x) >> 6;
-    if (n >= Npad) return;
-    float s = 0.f;
-    for (int k = lane; k < KD; k += 64) {
-        const __half h = n < N ? rows16[n * KD + k] : __float2half(0.f);
-        const float v = __half2float(h);
-        s = fmaf(v, v, s);
-        img[img_elem(n, k, 1)] = h;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) inv[n] = n < N ? 1.f / (sqrtf(s) + 1e-6f) : 0.f;
-}
-
-// header[4] = the largest |value| of the index: `matched` (the mean of four of its rows) is bounded by it, so the conversion takes the
-// |max| slot of the decoder's content input from here instead of a pass over the tensor (block-floating-point guard, split_fp16.h)
-template <class T>
-static __global__ __launch_bounds__(256) void index_amax_kernel(const T* __restrict__ p, long n, float* __restrict__ slot) {
-    __shared__ float red[4];
-    float mx = 0.f;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) mx = fmaxf(mx, fabsf((float)p[i]));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-        if (m > 0.f) atomicMax(reinterpret_cast<unsigned*>(slot), __builtin_bit_cast(unsigned, m));      // non-negative floats order like their bits; NaN never enters
-    }
-}
-const float* knn_index_amax(const float* prepared) { return prepared + 4; }
-
-// out[i] = the |max| of blob i (one index per utterance: each utterance's content bound is its own index's): the pointers travel as kernel
-// arguments, like ragged.h's upload_ints
-struct BlobChunk {
-    const float* p[480];
-};
-static __global__ void index_amax_rows_kernel(BlobChunk c, float* __restrict__ out, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = c.p[i][4];
-}
-int run_knn_amax_rows(tvc_ctx* ctx, hipStream_t s, const std::vector<const float*>& blobs, float* out) {
-    for (size_t o = 0; o < blobs.size(); o += 480) {
-        BlobChunk c;
-        const int n = (int)(blobs.size() - o < 480 ? blobs.size() - o : 480);
-        for (int i = 0; i < n; ++i) c.p[i] = blobs[o + i];
-        hipLaunchKernelGGL(index_amax_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, s, c, out + o, n);
-    }
-    return launch_check(ctx, "knn_amax_rows");
-}
-
-int run_prepare_index(tvc_ctx* ctx, hipStream_t s, const float* index, float* prepared, int64_t N) {
-    const long Npad = npad128(N);
-    hipLaunchKernelGGL(blob_header_kernel, dim3(1), dim3(64), 0, s, prepared, KIND_F32, (long)N);
-    float* rows = prepared + HDR;
-    unsigned short* img = reinterpret_cast<unsigned short*>(rows + (size_t)N * KD);
-    float* inv = const_cast<float*>(blob_inv(prepared, KIND_F32, N, Npad));
-    __half* img16 = reinterpret_cast<__half*>(const_cast<uint4*>(blob_img16(prepared, KIND_F32, N, Npad)));
-    hipLaunchKernelGGL(index_prepare_kernel, dim3((unsigned)((Npad + 255) / 256)), dim3(256), 0, s, index, rows, img, inv, img16, (long)N, Npad);
-    hipLaunchKernelGGL(index_amax_kernel<float>, dim3(64), dim3(256), 0, s, index, (long)N * KD, prepared + 4);
-    return launch_check(ctx, "knn_prepare_index");
-}
-
-static __global__ void index_invmax_kernel(const float* __restrict__ inv, float* __restrict__ invmax, long ntiles) {
-    const long t = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    if (t >= ntiles) return;
-    float m = 0.f;
-    for (int i = 0; i < 128; ++i) m = fmaxf(m, inv[t * 128 + i]);
-    invmax[t] = m;
-}
-
-int run_prepare_index_f16(tvc_ctx* ctx, hipStream_t s, const void* rows16, float* prepared, int64_t N) {
-    const long Npad = npad128(N);
-    hipLaunchKernelGGL(blob_header_kernel, dim3(1), dim3(64), 0, s, prepared, KIND_F16, (long)N);
-    float* inv = prepared + HDR;
-    __half* img = reinterpret_cast<__half*>(inv + Npad);
-    hipLaunchKernelGGL(index_prepare_f16_kernel, dim3((unsigned)((Npad * 64 + 255) / 256)), dim3(256), 0, s,
-                       reinterpret_cast<const __half*>(rows16), inv, img, (long)N, Npad);
-    hipLaunchKernelGGL(index_invmax_kernel, dim3((unsigned)((Npad / 128 + 255) / 256)), dim3(256), 0, s, inv, const_cast<float*>(blob_invmax(prepared, Npad)), Npad / 128);
-    hipLaunchKernelGGL(index_amax_kernel<__half>, dim3(64), dim3(256), 0, s, reinterpret_cast<const __half*>(rows16), (long)N * KD, prepared + 4);
-    return launch_check(ctx, "knn_prepare_index_f16");
-}
-
-// ---- an index gathered straight into a blob ---------------------------------------------------------------------------------
-// extract_index.py:43-58 selects index vectors out of the clips' features (every stride-th frame, permuted, truncated); here the
-// selection is a column list into packed features [768][S] and the selected vectors go straight into a prepared blob, byte for byte
-// the blob run_prepare_index / run_prepare_index_f16 make of feats[:, cols].  One workgroup per 128-vector image tile:
-//   * the column gather is element-granular (lanes along n read feats[k][cols[n]]: every lane its own cache line, served by L2 / the
-//     Infinity Cache - all tiles walk the channels in the same order), 32 independent loads per thread in flight;
-//   * a 64-channel chunk of the tile meets in LDS ([k][n], rows padded by one float: lanes along n and lanes along k are both
-//     conflict-free), and every store leaves with its lanes along the fast axis of its destination: raw rows in 256-byte runs,
-//     index_out along n, the images as whole 16-byte pieces (img_elem keeps the 8 j of one (n, step, lh) adjacent: 1 KiB per wave).
-// What byte identity pins: the norm's summation order (fp32 kind: ONE fmaf chain over k ascending per vector; fp16 kind: 64 lane-strided
-// chains, k = lane + 64 c, then the xor butterfly), raw / den as a division, the three-term bf16 split - restated below as they stand
-// in index_prepare_kernel / index_prepare_f16_kernel.
-constexpr int GP_KC = 64;             // channels per chunk: 4 K16 steps, one raw-row run of 256 bytes
-constexpr int GP_LD = 128 + 1;        // LDS row stride in floats
-static_assert(KD % GP_KC == 0 && GP_KC == 64, "the fp16 kind's lane-strided chains take one term per chunk");
-
-// a column outside [0, S) never leaves the tensor (the host's column plan refuses it first: feature_retrieval.py index_columns)
-__device__ __forceinline__ long gp_column(const int64_t* __restrict__ cols, long n, long N, long S) {
-    const long c = n < N ? (long)cols[n] : 0;
-    return c < 0 ? 0 : (c >= S ? S - 1 : c);
-}
-__device__ __forceinline__ unsigned gp_pack(unsigned short lo, unsigned short hi) { return (unsigned)lo | ((unsigned)hi << 16); }
-__device__ __forceinline__ void gp_amax_flush(float mx, float* red, float* __restrict__ slot) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-        if (m > 0.f) atomicMax(reinterpret_cast<unsigned*>(slot), __builtin_bit_cast(unsigned, m));      // as index_amax_kernel
-    }
-}
-
-// fp32 storage.  Pass 1: gather, norm chain, raw rows, index_out, |max|.  Pass 2: the tile's own rows (just written: L2-hot, contiguous)
-// come back through LDS and leave as the bf16x3 and fp16 images of v / den.
-static __global__ __launch_bounds__(256) void index_gather_prepare_kernel(const float* __restrict__ feats, long S, const int64_t* __restrict__ cols,
-                                                                          float* rows, uint4* __restrict__ img, float* __restrict__ inv,
-                                                                          uint4* __restrict__ img16, float* __restrict__ index_out,
-                                                                          float* __restrict__ slot, long N) {
-    __shared__ float tile[GP_KC * GP_LD];
-    __shared__ float den_s[128];
-    __shared__ float red[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long n0 = blockIdx.x * 128L;
-    const int gn = tid & 127, gh = tid >> 7;      // the gather: vector gn of the tile, channels 32 gh ... of the chunk
-    const long n = n0 + gn;
-    const bool live = n < N;
-    const float* src = feats + gp_column(cols, n, N, S);
-    float s = 0.f, mx = 0.f;
-    for (int k0 = 0; k0 < KD; k0 += GP_KC) {
-        float x[32];
-#pragma unroll
-        for (int i = 0; i < 32; ++i) x[i] = src[(long)(k0 + gh * 32 + i) * S];      // (a vector beyond N reads column 0 and drops it)
-#pragma unroll
-        for (int i = 0; i < 32; ++i) {
-            const float v = live ? x[i] : 0.f;
-            tile[(gh * 32 + i) * GP_LD + gn] = v;
-            mx = fmaxf(mx, fabsf(v));
-            if (index_out && live) index_out[(long)(k0 + gh * 32 + i) * N + n] = v;
-        }
-        __syncthreads();
-        if (tid < 128) {      // thread t owns vector t's chain (gn == tid): k ascending, one accumulator
-#pragma unroll 16
-            for (int k = 0; k < GP_KC; ++k) {
-                const float v = tile[k * GP_LD + tid];
-                s = fmaf(v, v, s);
-            }
-        }
-#pragma unroll 8
-        for (int j = 0; j < 32; ++j) {      // raw rows: a wave writes channels k0 ... k0 + 63 of one vector
-            const int r = wave * 32 + j;
-            if (n0 + r < N) rows[(n0 + r) * KD + k0 + lane] = tile[lane * GP_LD + r];
-        }
-        __syncthreads();
-    }
-    gp_amax_flush(mx, red, slot);
-    if (tid < 128) {
-        const float den = live ? sqrtf(s) + 1e-6f : 1.f;
-        den_s[tid] = den;
-        inv[n] = live ? 1.f / den : 0.f;
-    }
-    __syncthreads();
-    const int nl = wave * 32 + (lane & 31), lh = lane >> 5;      // pass 2: wave = m-tile, lane = (lh, vector & 31) - the MFMA lane of the piece
-    const float den = den_s[nl];
-    for (int k0 = 0; k0 < KD; k0 += GP_KC) {
-#pragma unroll 8
-        for (int j = 0; j < 32; ++j) {
-            const int r = wave * 32 + j;
-            tile[lane * GP_LD + r] = n0 + r < N ? rows[(n0 + r) * KD + k0 + lane] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int st = 0; st < GP_KC / 16; ++st) {
-            unsigned short b1[8], b2[8], b3[8], hf[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float raw = tile[(st * 16 + lh * 8 + j) * GP_LD + nl];
-                float v = raw / den;
-                hf[j] = __half_as_ushort(__float2half(v));
-                __bf16 h1 = (__bf16)v;
-                float r = v - (float)h1;
-                __bf16 h2 = (__bf16)r;
-                float r2 = r - (float)h2;
-                __bf16 h3 = (__bf16)r2;
-                b1[j] = __builtin_bit_cast(unsigned short, h1);
-                b2[j] = __builtin_bit_cast(unsigned short, h2);
-                b3[j] = __builtin_bit_cast(unsigned short, h3);
-            }
-            const long piece = ((long)blockIdx.x * STEPS + (k0 >> 4) + st) * 4 + wave;      // img_elem / 8 = (piece * parts + part) * 64 + lane
-            img[(piece * 3 + 0) * 64 + lane] = make_uint4(gp_pack(b1[0], b1[1]), gp_pack(b1[2], b1[3]), gp_pack(b1[4], b1[5]), gp_pack(b1[6], b1[7]));
-            img[(piece * 3 + 1) * 64 + lane] = make_uint4(gp_pack(b2[0], b2[1]), gp_pack(b2[2], b2[3]), gp_pack(b2[4], b2[5]), gp_pack(b2[6], b2[7]));
-            img[(piece * 3 + 2) * 64 + lane] = make_uint4(gp_pack(b3[0], b3[1]), gp_pack(b3[2], b3[3]), gp_pack(b3[4], b3[5]), gp_pack(b3[6], b3[7]));
-            img16[piece * 64 + lane] = make_uint4(gp_pack(hf[0], hf[1]), gp_pack(hf[2], hf[3]), gp_pack(hf[4], hf[5]), gp_pack(hf[6], hf[7]));
-        }
-        __syncthreads();
-    }
-}
-
-// fp16 storage: no raw rows, one pass.  The chunk holds the fp16-rounded values (as floats); wave w keeps the 64 lane-strided chains of its
-// 32 vectors in registers (chunk c is term c of every chain) and folds them with the butterfly behind the last chunk.
-static __global__ __launch_bounds__(256) void index_gather_prepare_f16_kernel(const float* __restrict__ feats, long S, const int64_t* __restrict__ cols,
-                                                                              float* __restrict__ inv, uint4* __restrict__ img, float* __restrict__ invmax,
-                                                                              __half* __restrict__ index_out, float* __restrict__ slot, long N) {
-    __shared__ float tile[GP_KC * GP_LD];
-    __shared__ float red[4];
-    __shared__ float imx[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long n0 = blockIdx.x * 128L;
-    const int gn = tid & 127, gh = tid >> 7;
-    const long n = n0 + gn;
-    const bool live = n < N;
-    const float* src = feats + gp_column(cols, n, N, S);
-    const int nl = wave * 32 + (lane & 31), lh = lane >> 5;
-    float p[32];
-#pragma unroll
-    for (int j = 0; j < 32; ++j) p[j] = 0.f;
-    float mx = 0.f;
-    for (int k0 = 0; k0 < KD; k0 += GP_KC) {
-        float x[32];
-#pragma unroll
-        for (int i = 0; i < 32; ++i) x[i] = src[(long)(k0 + gh * 32 + i) * S];
-#pragma unroll
-        for (int i = 0; i < 32; ++i) {
-            const __half h = __float2half(live ? x[i] : 0.f);
-            const float v = __half2float(h);
-            tile[(gh * 32 + i) * GP_LD + gn] = v;
-            mx = fmaxf(mx, fabsf(v));
-            if (index_out && live) index_out[(long)(k0 + gh * 32 + i) * N + n] = h;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 32; ++j) {
-            const float v = tile[lane * GP_LD + wave * 32 + j];
-            p[j] = fmaf(v, v, p[j]);
-        }
-#pragma unroll
-        for (int st = 0; st < GP_KC / 16; ++st) {
-            unsigned short hf[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) hf[j] = __half_as_ushort(__float2half(tile[(st * 16 + lh * 8 + j) * GP_LD + nl]));      // exact: the values are halves
-            const long piece = ((long)blockIdx.x * STEPS + (k0 >> 4) + st) * 4 + wave;
-            img[piece * 64 + lane] = make_uint4(gp_pack(hf[0], hf[1]), gp_pack(hf[2], hf[3]), gp_pack(hf[4], hf[5]), gp_pack(hf[6], hf[7]));
-        }
-        __syncthreads();
-    }
-    gp_amax_flush(mx, red, slot);
-    float wmax = 0.f;
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        float s = p[j];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        const long r = n0 + wave * 32 + j;
-        const float iv = r < N ? 1.f / (sqrtf(s) + 1e-6f) : 0.f;
-        if (lane == 0) inv[r] = iv;
-        wmax = fmaxf(wmax, iv);
-    }
-    if (lane == 0) imx[wave] = wmax;
-    __syncthreads();
-    if (tid == 0) invmax[blockIdx.x] = fmaxf(fmaxf(fmaxf(fmaxf(0.f, imx[0]), imx[1]), imx[2]), imx[3]);      // the tile's largest inverse norm (index_invmax_kernel)
-}
-
-int run_prepare_index_cols(tvc_ctx* ctx, hipStream_t s, const float* feats, int64_t S, const int64_t* cols, int64_t N, float* prepared, float* index_out) {
-    const long Npad = npad128(N);
-    hipLaunchKernelGGL(blob_header_kernel, dim3(1), dim3(64), 0, s, prepared, KIND_F32, (long)N);
-    float* rows = prepared + HDR;
-    uint4* img = reinterpret_cast<uint4*>(rows + (size_t)N * KD);
-    float* inv = const_cast<float*>(blob_inv(prepared, KIND_F32, N, Npad));
-    uint4* img16 = const_cast<uint4*>(blob_img16(prepared, KIND_F32, N, Npad));
-    hipLaunchKernelGGL(index_gather_prepare_kernel, dim3((unsigned)(Npad / 128)), dim3(256), 0, s, feats, (long)S, cols, rows, img, inv, img16, index_out,
-                       prepared + 4, (long)N);
-    return launch_check(ctx, "knn_prepare_index_cols");
-}
-
-int run_prepare_index_cols_f16(tvc_ctx* ctx, hipStream_t s, const float* feats, int64_t S, const int64_t* cols, int64_t N, float* prepared, void* index_out_f16) {
-    const long Npad = npad128(N);
-    hipLaunchKernelGGL(blob_header_kernel, dim3(1), dim3(64), 0, s, prepared, KIND_F16, (long)N);
-    float* inv = prepared + HDR;
-    uint4* img = reinterpret_cast<uint4*>(inv + Npad);
-    hipLaunchKernelGGL(index_gather_prepare_f16_kernel, dim3((unsigned)(Npad / 128)), dim3(256), 0, s, feats, (long)S, cols, inv, img,
-                       const_cast<float*>(blob_invmax(prepared, Npad)), reinterpret_cast<__half*>(index_out_f16), prepared + 4, (long)N);
-    return launch_check(ctx, "knn_prepare_index_cols_f16");
-}
 
 // qn[b][k][t] = src[b][k][t] / (||src[b][:][t]|| + 1e-6).  One workgroup = 64 consecutive columns;
 // its 4 waves each sum a quarter of the 768 channels (lanes along time, coalesced), partial sums of
@@ -514,32 +106,6 @@ static __global__ __launch_bounds__(QN_WAVES * 64) void query_normalize_kernel(c
     }
 }
 
-// torch.topk orders NaN above every number; a query column with NaN / Inf samples upstream makes every similarity NaN.
-// Mapping NaN to +inf keeps that order (ties -> lowest index, so such a column selects rows 0..3 like any all-equal
-// column) and, more to the point, keeps the 0x7fffffff list sentinel from ever reaching the row gather.
-__device__ __forceinline__ float nan_max(float x) { return x != x ? INFINITY : x; }
-
-struct Top4 {
-    float v[4];
-    int i[4];
-    __device__ __forceinline__ void init() {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            v[j] = -INFINITY;
-            i[j] = 0x7fffffff;
-        }
-    }
-    // strict ordering: higher value first, then lower index
-    __device__ __forceinline__ static bool better(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
-    __device__ __forceinline__ void insert(float x, int ix) {
-        if (!better(x, ix, v[3], i[3])) return;
-        if (better(x, ix, v[0], i[0])) { v[3] = v[2]; i[3] = i[2]; v[2] = v[1]; i[2] = i[1]; v[1] = v[0]; i[1] = i[0]; v[0] = x; i[0] = ix; }
-        else if (better(x, ix, v[1], i[1])) { v[3] = v[2]; i[3] = i[2]; v[2] = v[1]; i[2] = i[1]; v[1] = x; i[1] = ix; }
-        else if (better(x, ix, v[2], i[2])) { v[3] = v[2]; i[3] = i[2]; v[2] = x; i[2] = ix; }
-        else { v[3] = x; i[3] = ix; }
-    }
-};
-
 // The exact kernel's own split: three bf16 parts per fp32 operand (x = x1 + x2 + x3, residuals exact), six part-products per
 // product on v_mfma_f32_32x32x16_bf16.  (The conv / GEMM kernels moved to the two-term fp16 split of conv3s.h; this kernel only runs
 // for N < 4096 and as the in-call fallback of the two-stage search, whose coarse passes are single fp16 products.)
@@ -598,8 +164,8 @@ __device__ __forceinline__ void knn_topk_body(const float* __restrict__ blob, lo
     constexpr int GP = F16 ? 4 : 12;                   // 1 KiB pieces per (tile, step) in the global image
     uint4* As = smem;
     uint4* Xs = smem + 2 * KNN_A_U4;
-    const uint4* img = F16 ? reinterpret_cast<const uint4*>(blob + HDR + Npad) : reinterpret_cast<const uint4*>(blob + HDR + (size_t)N * KD);
-    const float* inv = blob + HDR;                     // fp16 storage only
+    const uint4* img = F16 ? blob_img16(blob, KIND_F16, N, Npad) : blob_img3(blob, N);
+    const float* inv = blob_inv(blob, KIND_F16, N, Npad);      // fp16 storage only
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 2, wn = wave & 3;
@@ -764,300 +330,10 @@ static __global__ __launch_bounds__(512) void knn_topk_split_kernel(const KnnSeg
     const int si = seg_find<2>(segs, blockIdx.x);
     const KnnSeg g = seg_get(segs, si);
     if (g.two && flags[si] == 0) return;                         // the segment's two-stage search succeeded: nothing to do (uniform)
-    const int kind = reinterpret_cast<const int*>(g.blob)[1];    // uniform: which storage this prepared index uses
+    const int kind = blob_kind(g.blob);                          // uniform: which storage this prepared index uses
     const int unit = blockIdx.x - g.u[2];
-    if (kind == KIND_F16) knn_topk_body<true>(g.blob, seg_npad(g), g.N, qn, g.ncols, g.col0, cstride, T, unit, g.nsE, g.tpsE, cand_v, cand_i, smem);
-    else knn_topk_body<false>(g.blob, seg_npad(g), g.N, qn, g.ncols, g.col0, cstride, T, unit, g.nsE, g.tpsE, cand_v, cand_i, smem);
-}
-
-// One workgroup = 32 consecutive query columns: merge split candidates -> top-4, write indices,
-// gather the 4 raw rows per query (coalesced along the feature axis), average, and write
-// out[b][k][t] through an LDS transpose so stores run along t.  Every query takes its segment's blob and lists (col2seg: several
-// segments; the 32 columns may straddle a segment boundary).  MULTI = false: one segment, whose blob the gather reads as a uniform value.
-template <bool MULTI>
-static __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
-                                                                      const KnnSegs segs, const int* __restrict__ col2seg, int ncols, int T,
-                                                                      float* __restrict__ out, int64_t* __restrict__ idx_out,
-                                                                      const float* __restrict__ rv, const int* __restrict__ ri,
-                                                                      const int* __restrict__ flags) {
-    __shared__ int sel[32][4];
-    __shared__ float tile[32][193];
-    __shared__ const float* sblob[32];
-    __shared__ int skind[32], sN[32];
-    const int tid = threadIdx.x;
-    const int n0 = blockIdx.x * 32;
-    if (tid < 32) {
-        int n = n0 + tid;
-        const int nc = n < ncols ? n : ncols - 1;      // (a column past the end gathers row 0 of the last column's blob: never stored)
-        const int si = MULTI ? col2seg[nc] : 0;
-        const KnnSeg g = seg_get(segs, si);
-        const bool rescored = g.two && flags[si] == 0;  // the two-stage search's rescored lists (one "split") are the result
-        const float* cv = rescored ? rv : cand_v;
-        const int* ci = rescored ? ri : cand_i;
-        const int nsplit = rescored ? 1 : g.nsE;
-        const int N = g.N;
-        Top4 t4;
-        t4.init();
-        if (n < ncols) {
-            for (int s = 0; s < nsplit; ++s) {
-                long o = ((long)s * ncols + n) * 4;
-                for (int e = 0; e < 4; ++e) t4.insert(cv[o + e], ci[o + e]);
-            }
-            for (int e = 0; e < 4; ++e) t4.i[e] = (unsigned)t4.i[e] < (unsigned)N ? t4.i[e] : 0;   // never gather through a sentinel
-            if (idx_out)
-                for (int e = 0; e < 4; ++e) idx_out[(long)n * 4 + e] = (int64_t)t4.i[e];
-        }
-        for (int e = 0; e < 4; ++e) sel[tid][e] = n < ncols ? t4.i[e] : 0;
-        if (MULTI) {
-            sblob[tid] = g.blob;
-            skind[tid] = reinterpret_cast<const int*>(g.blob)[1];
-            sN[tid] = N;
-        }
-    }
-    __syncthreads();
-    const int lane = tid & 63, wave = tid >> 6;
-    const float* const blob0 = segs.one.blob;
-    const int kind0 = MULTI ? 0 : reinterpret_cast<const int*>(blob0)[1], N0 = segs.one.N;
-    for (int kc = 0; kc < KD; kc += 192) {
-        // gather: wave handles queries wave, wave+4, ...; lanes run along k (3 x 64 = 192)
-        // (four queries' 48 loads in flight per lane: one query at a time was eight serial round trips per wave and chunk - 48 us per
-        // launch whatever the batch, a chain of latencies)
-        for (int q0 = wave; q0 < 32; q0 += 16) {
-            float r[4][3][4];
-#pragma unroll
-            for (int qq = 0; qq < 4; ++qq) {
-                const int q = q0 + 4 * qq;
-                const float* blob = MULTI ? sblob[q] : blob0;
-                const int kind = MULTI ? skind[q] : kind0, N = MULTI ? sN[q] : N0;
-                const long Npad = ((long)N + 127) / 128 * 128;
-#pragma unroll
-                for (int u = 0; u < 3; ++u)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) r[qq][u][e] = blob_row_value(blob, kind, N, Npad, sel[q][e], kc + lane + 64 * u);
-            }
-#pragma unroll
-            for (int qq = 0; qq < 4; ++qq)
-#pragma unroll
-                for (int u = 0; u < 3; ++u) {
-                    const float sum = __fadd_rn(__fadd_rn(__fadd_rn(r[qq][u][0], r[qq][u][1]), r[qq][u][2]), r[qq][u][3]);
-                    tile[q0 + 4 * qq][lane + 64 * u] = sum * 0.25f;
-                }
-        }
-        __syncthreads();
-        // scatter: lanes run along the 32 queries (time), 8 k-rows per pass
-        for (int kk = tid >> 5; kk < 192; kk += 8) {
-            int q = tid & 31;
-            int n = n0 + q;
-            if (n < ncols) {
-                int b = n / T, t = n - b * T;
-                out[((long)b * KD + kc + kk) * T + t] = tile[q][kk];
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// ---- a weighted blend of several indices (tvc_*_blend_f32) -------------------------------------------------------------------
-// Every source row is searched once per term: term m of the call's ncols real columns is the virtual columns [m * ncols, (m + 1) * ncols)
-// of ONE search (virtual row m * B + b holds the queries of source row b: query_normalize_kernel's Bsrc), whose segments are the
-// (term, row) runs - each with its own path and overflow flag, exactly the single-index search of that (row, blob).  This kernel is the
-// blend's knn_merge_gather_kernel<true>: one workgroup = 32 REAL columns; threads (m, q) merge term m's lists of column q and write its
-// indices; the gather then walks the terms per query, four queries in flight per wave as there, and keeps
-//   out = w_0 * mu_0;  out = out + w_m * mu_m  (m = 1 .. M - 1),   mu_m = (((r0 + r1) + r2) + r3) * 0.25f
-// in registers - products and sums rounded separately (__fmul_rn / __fadd_rn), in term order - so the per-term matched tensors never exist
-// in memory.  One LDS transpose, stores along t.  weights [rows][M] is the caller's DEVICE array, read here: a captured graph replays with
-// whatever it holds then.  The weight row of a column is its batch row, or rowmap[col2b[column]] in a ragged batch (ragged.h).
-constexpr int BLEND_MAX = TVC_BLEND_MAX;
-static __global__ __launch_bounds__(256) void knn_merge_blend_gather_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
-                                                                            const KnnSegs segs, const int* __restrict__ col2seg, int ncols, int T,
-                                                                            int M, const float* __restrict__ weights, const int* __restrict__ col2b,
-                                                                            const int* __restrict__ rowmap, float* __restrict__ out,
-                                                                            int64_t* __restrict__ idx_out, const float* __restrict__ rv,
-                                                                            const int* __restrict__ ri, const int* __restrict__ flags) {
-    __shared__ int sel[BLEND_MAX][32][4];
-    __shared__ float tile[32][193];
-    __shared__ const float* sblob[BLEND_MAX][32];
-    __shared__ int skind[BLEND_MAX][32], sN[BLEND_MAX][32];
-    __shared__ float sw[BLEND_MAX][32];
-    const int tid = threadIdx.x;
-    const int n0 = blockIdx.x * 32;
-    if (tid < 32 * M) {
-        const int m = tid >> 5, q = tid & 31;
-        const int n = n0 + q;
-        const bool live = n < ncols;
-        const int nc = live ? n : ncols - 1;            // (a column past the end gathers row 0 of the last column's blobs: never stored)
-        const long vcols = (long)M * ncols;             // the search's columns: the lists' stride
-        const long vc = (long)m * ncols + nc;           // this term's virtual column
-        const int si = col2seg ? col2seg[vc] : 0;
-        const KnnSeg g = seg_get(segs, si);
-        const bool rescored = g.two && flags[si] == 0;
-        const float* cv = rescored ? rv : cand_v;
-        const int* ci = rescored ? ri : cand_i;
-        const int nsplit = rescored ? 1 : g.nsE;
-        const int N = g.N;
-        Top4 t4;
-        t4.init();
-        if (live) {
-            for (int s = 0; s < nsplit; ++s) {
-                const long o = ((long)s * vcols + vc) * 4;
-                for (int e = 0; e < 4; ++e) t4.insert(cv[o + e], ci[o + e]);
-            }
-            for (int e = 0; e < 4; ++e) t4.i[e] = (unsigned)t4.i[e] < (unsigned)N ? t4.i[e] : 0;   // never gather through a sentinel
-            if (idx_out)
-                for (int e = 0; e < 4; ++e) idx_out[vc * 4 + e] = (int64_t)t4.i[e];
-        }
-        for (int e = 0; e < 4; ++e) sel[m][q][e] = live ? t4.i[e] : 0;
-        sblob[m][q] = g.blob;
-        skind[m][q] = reinterpret_cast<const int*>(g.blob)[1];
-        sN[m][q] = N;
-        const int row = col2b ? rowmap[col2b[nc]] : nc / T;
-        sw[m][q] = weights[(long)row * M + m];
-    }
-    __syncthreads();
-    const int lane = tid & 63, wave = tid >> 6;
-    for (int kc = 0; kc < KD; kc += 192) {
-        for (int q0 = wave; q0 < 32; q0 += 16) {
-            float acc[4][3];
-#pragma unroll 1
-            for (int m = 0; m < M; ++m) {
-                float r[4][3][4];
-#pragma unroll
-                for (int qq = 0; qq < 4; ++qq) {
-                    const int q = q0 + 4 * qq;
-                    const float* blob = sblob[m][q];
-                    const int kind = skind[m][q], N = sN[m][q];
-                    const long Npad = ((long)N + 127) / 128 * 128;
-#pragma unroll
-                    for (int u = 0; u < 3; ++u)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) r[qq][u][e] = blob_row_value(blob, kind, N, Npad, sel[m][q][e], kc + lane + 64 * u);
-                }
-#pragma unroll
-                for (int qq = 0; qq < 4; ++qq) {
-                    const float w = sw[m][q0 + 4 * qq];
-#pragma unroll
-                    for (int u = 0; u < 3; ++u) {
-                        const float sum = __fadd_rn(__fadd_rn(__fadd_rn(r[qq][u][0], r[qq][u][1]), r[qq][u][2]), r[qq][u][3]);
-                        const float mu = sum * 0.25f;
-                        const float term = __fmul_rn(w, mu);
-                        acc[qq][u] = m == 0 ? term : __fadd_rn(acc[qq][u], term);
-                    }
-                }
-            }
-#pragma unroll
-            for (int qq = 0; qq < 4; ++qq)
-#pragma unroll
-                for (int u = 0; u < 3; ++u) tile[q0 + 4 * qq][lane + 64 * u] = acc[qq][u];
-        }
-        __syncthreads();
-        // scatter: lanes run along the 32 queries (time), 8 k-rows per pass
-        for (int kk = tid >> 5; kk < 192; kk += 8) {
-            const int q = tid & 31;
-            const int n = n0 + q;
-            if (n < ncols) {
-                const int b = n / T, t = n - b * T;
-                out[((long)b * KD + kc + kk) * T + t] = tile[q][kk];
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// out[i] = sum_m |w[row[i]][m]| * (the |max| of blob (i, m)), in term order, products and sums rounded separately: the bound of row i's blended
-// content (|mu_m| <= its blob's |max|), the decoder's content bound of a blend call.  One workgroup; the blobs and the weight rows travel as
-// kernel arguments (like index_amax_rows_kernel), the weights are read from the caller's device array.
-constexpr int BB_ROWS = 64;
-struct BlendBoundChunk {
-    const float* p[BB_ROWS * BLEND_MAX];
-    int row[BB_ROWS];
-};
-static __global__ __launch_bounds__(BB_ROWS) void blend_bound_kernel(BlendBoundChunk c, const float* __restrict__ weights, int M, float* __restrict__ out, int n) {
-    const int i = threadIdx.x;
-    if (i >= n) return;
-    const float* w = weights + (long)c.row[i] * M;
-    float b = __fmul_rn(fabsf(w[0]), c.p[i * M][4]);
-    for (int m = 1; m < M; ++m) b = __fadd_rn(b, __fmul_rn(fabsf(w[m]), c.p[i * M + m][4]));
-    out[i] = b;
-}
-int run_knn_blend_bound(tvc_ctx* ctx, hipStream_t s, const std::vector<const float*>& blobs, const std::vector<int>& rows, int M, const float* weights, float* out) {
-    for (size_t o = 0; o < rows.size(); o += BB_ROWS) {
-        BlendBoundChunk c;
-        const int n = (int)(rows.size() - o < BB_ROWS ? rows.size() - o : BB_ROWS);
-        for (int i = 0; i < n; ++i) {
-            c.row[i] = rows[o + i];
-            for (int m = 0; m < M; ++m) c.p[i * M + m] = blobs[(o + i) * M + m];
-        }
-        hipLaunchKernelGGL(blend_bound_kernel, dim3(1), dim3(BB_ROWS), 0, s, c, weights, M, out + o, n);
-    }
-    return launch_check(ctx, "knn_blend_bound");
-}
-
-// ---- index-sharded search (one index shard per GPU): local top-4 with similarities, slot gather, finish ----
-// merge the split candidates of every query -> this shard's top-4 (similarity, local index)
-static __global__ __launch_bounds__(256) void knn_merge_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i, int nsplit, int ncols,
-                                                               float* __restrict__ sims_out, int64_t* __restrict__ idx_out,
-                                                               const float* __restrict__ rv, const int* __restrict__ ri, const int* __restrict__ flag) {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= ncols) return;
-    if (flag && *flag == 0) {
-        cand_v = rv;
-        cand_i = ri;
-        nsplit = 1;
-    }
-    Top4 t4;
-    t4.init();
-    for (int sp = 0; sp < nsplit; ++sp) {
-        long o = ((long)sp * ncols + n) * 4;
-        for (int e = 0; e < 4; ++e) t4.insert(cand_v[o + e], cand_i[o + e]);
-    }
-    for (int e = 0; e < 4; ++e) {
-        sims_out[(long)n * 4 + e] = t4.v[e];
-        idx_out[(long)n * 4 + e] = (int64_t)t4.i[e];
-    }
-}
-// slots[n][e][:] = raw row idx[n][e] of this shard, or zeros where idx < 0 (the row lives on another rank)
-static __global__ __launch_bounds__(192) void knn_slot_gather_kernel(const float* __restrict__ blob, const int64_t* __restrict__ idx, long nslots,
-                                                                     long N, long Npad, float* __restrict__ slots) {
-    const long sl = blockIdx.x;
-    if (sl >= nslots) return;
-    const int kind = reinterpret_cast<const int*>(blob)[1];
-    const int64_t i = idx[sl];
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (i >= 0 && i < N) {
-        const int k = 4 * threadIdx.x;
-        v = make_float4(blob_row_value(blob, kind, N, Npad, i, k), blob_row_value(blob, kind, N, Npad, i, k + 1),
-                        blob_row_value(blob, kind, N, Npad, i, k + 2), blob_row_value(blob, kind, N, Npad, i, k + 3));
-    }
-    reinterpret_cast<float4*>(slots + sl * KD)[threadIdx.x] = v;
-}
-// out[b][k][t] = (((s0 + s1) + s2) + s3) * 0.25 from slots [B*T][4][768] (the same order as the single-GPU gather),
-// transposed through LDS so reads run along k and stores along t
-static __global__ __launch_bounds__(256) void knn_finish_kernel(const float* __restrict__ slots, int ncols, int T, float* __restrict__ out) {
-    __shared__ float tile[32][193];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n0 = blockIdx.x * 32;
-    for (int kc = 0; kc < KD; kc += 192) {
-        for (int q = wave; q < 32; q += 4) {
-            const int n = n0 + q < ncols ? n0 + q : ncols - 1;
-            const float* r0 = slots + ((long)n * 4) * KD + kc;
-#pragma unroll
-            for (int u = 0; u < 3; ++u) {
-                int k = lane + 64 * u;
-                float sum = __fadd_rn(__fadd_rn(__fadd_rn(r0[k], r0[KD + k]), r0[2 * KD + k]), r0[3 * KD + k]);
-                tile[q][k] = sum * 0.25f;
-            }
-        }
-        __syncthreads();
-        for (int kk = tid >> 5; kk < 192; kk += 8) {
-            int q = tid & 31;
-            int n = n0 + q;
-            if (n < ncols) {
-                int b = n / T, t = n - b * T;
-                out[((long)b * KD + kc + kk) * T + t] = tile[q][kk];
-            }
-        }
-        __syncthreads();
-    }
+    if (kind == KIND_F16) knn_topk_body<true>(g.blob, blob_npad(g.N), g.N, qn, g.ncols, g.col0, cstride, T, unit, g.nsE, g.tpsE, cand_v, cand_i, smem);
+    else knn_topk_body<false>(g.blob, blob_npad(g.N), g.N, qn, g.ncols, g.col0, cstride, T, unit, g.nsE, g.tpsE, cand_v, cand_i, smem);
 }
 
 // =================================================================================================
@@ -1322,10 +598,10 @@ static __global__ __launch_bounds__(512) void knn_coarse_kernel(const KnnSegs se
     int* ct = cnt + g.col0;
     int* cd = cand + (long)g.col0 * C_CAP;
     float* cdv = candv + (long)g.col0 * C_CAP;
-    if (reinterpret_cast<const int*>(g.blob)[1] == KIND_F16)
-        knn_coarse_body<true, MODE>(g.blob, seg_npad(g), g.N, q, g.ncols, cstride, unit, nsplit, tps, cover, c4, g.nsA, ct, cd, cdv, flags + si);
+    if (blob_kind(g.blob) == KIND_F16)
+        knn_coarse_body<true, MODE>(g.blob, blob_npad(g.N), g.N, q, g.ncols, cstride, unit, nsplit, tps, cover, c4, g.nsA, ct, cd, cdv, flags + si);
     else
-        knn_coarse_body<false, MODE>(g.blob, seg_npad(g), g.N, q, g.ncols, cstride, unit, nsplit, tps, cover, c4, g.nsA, ct, cd, cdv, flags + si);
+        knn_coarse_body<false, MODE>(g.blob, blob_npad(g.N), g.N, q, g.ncols, cstride, unit, nsplit, tps, cover, c4, g.nsA, ct, cd, cdv, flags + si);
 }
 
 // One wavefront per query: exact similarity of every candidate = (fp32 FMA chain of q_hat against the raw vector, lanes
@@ -1344,8 +620,8 @@ static __global__ __launch_bounds__(256) void knn_rescore_kernel(const KnnSegs s
     if (!g.two) return;
     const float* __restrict__ blob = g.blob;
     const int N = g.N;
-    const long Npad = seg_npad(g);
-    const int kind = reinterpret_cast<const int*>(blob)[1];
+    const long Npad = blob_npad(g.N);
+    const int kind = blob_kind(blob);
     const float* inv = blob_inv(blob, kind, N, Npad);
     const int b = n / T, t = n - b * T;
     const float* qp = qn + (long)b * KD * T + t;
@@ -1466,7 +742,7 @@ static __global__ __launch_bounds__(256) void knn_rescore_kernel(const KnnSegs s
         float qv[12];
 #pragma unroll
         for (int u = 0; u < 12; ++u) qv[u] = qp[(long)(lane + 64 * u) * T];
-        const float* rows = blob + HDR;
+        const float* rows = blob_rows(blob);
         for (int base = 0, ch = 0; base < nc; base += 64, ++ch) {
             const int mine = ch == 0 ? rowl[0] : (ch == 1 ? rowl[1] : (ch == 2 ? rowl[2] : rowl[3]));
             const float cvv = ch == 0 ? cvl[0] : (ch == 1 ? cvl[1] : (ch == 2 ? cvl[2] : cvl[3]));
@@ -1531,17 +807,9 @@ static void split_plan(int blocks, int qtiles, int cover, int* ns, int* tps) {
     *ns = (cover + *tps - 1) / *tps;
 }
 
-struct KnnCall {                 // one call's segments and launch geometry
-    std::vector<KnnSeg> seg;
-    int ncols = 0, cq = 0;       // query columns; 256-query tiles (each segment's own)
-    int units[3] = {0, 0, 0};    // workgroups of pass A, pass B, the exact kernel
-    int ns_cv = 1;               // splits the exact kernel's lists are sized for
-    bool two = false;            // some segment searches in two stages
-};
-
 // Segments from the callers' runs (in column order): adjacent runs of the same blob merge.  Every split count follows from the call's
 // total query tiles, so a one-segment call plans exactly what the single-index search always planned.
-static int knn_call_plan(tvc_ctx* ctx, const KnnSegIn* in, int nin, int ncols, KnnCall* c) {
+int knn_call_plan(tvc_ctx* ctx, const KnnSegIn* in, int nin, int ncols, KnnCall* c) {
     static_assert(KNN_QT == C_QT, "one query tiling for both searches");
     c->ncols = ncols;
     for (int i = 0; i < nin; ++i) {
@@ -1563,7 +831,7 @@ static int knn_call_plan(tvc_ctx* ctx, const KnnSegIn* in, int nin, int ncols, K
     int mt_max = 1;
     int tile = 0;
     for (auto& g : c->seg) {
-        const long Npad = npad128(g.N);
+        const long Npad = blob_npad(g.N);
         const int mtiles = (int)(Npad / 128);
         const int qt = (g.ncols + C_QT - 1) / C_QT;
         mt_max = mtiles > mt_max ? mtiles : mt_max;
@@ -1601,16 +869,6 @@ static int knn_call_plan(tvc_ctx* ctx, const KnnSegIn* in, int nin, int ncols, K
     return 0;
 }
 
-struct KnnLists {        // where the merge kernels find the per-query top-4 lists
-    float* cv = nullptr;    // exact kernel: [nsplit][ncols][4]
-    int* ci = nullptr;
-    float* rv = nullptr;    // two-stage search: [ncols][4]
-    int* ri = nullptr;
-    int* flag = nullptr;    // per segment: 0 = its two-stage lists are valid; nullptr = no segment searches in two stages
-    int* col2seg = nullptr; // [ncols] (several segments)
-    KnnSegs segs{};
-};
-
 template <int MODE>
 static int coarse_launch(tvc_ctx* ctx, hipStream_t s, const KnnCall& c, const KnnLists& L, const uint4* qh, float* c4v, int* cnt, int* cand, float* candv) {
     TVC_CHECK(lds_optin<knn_coarse_kernel<MODE>>(ctx, C_LDS, "knn coarse"));
@@ -1625,7 +883,7 @@ static int coarse_max_nsplit(int qtiles) { return (768 + qtiles - 1) / qtiles; }
 // (The blob's kind lives in device memory - its header -, so the host cannot pick an instantiation: the kernels branch on it.)
 // The segment table of a several-segment call is uploaded as kernel arguments (ragged.h upload_ints): asynchronous, capturable.
 // (Bsrc: rows of src behind the B rows of queries - query_normalize_kernel; 0 = B)
-static int knn_candidates(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const KnnCall& c, int B, int T, KnnLists* L, int Bsrc = 0) {
+int knn_candidates(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const KnnCall& c, int B, int T, KnnLists* L, int Bsrc) {
     const int nseg = (int)c.seg.size();
     float* qn = ws.get<float>((size_t)B * KD * T);
     L->cv = ws.get<float>((size_t)c.ns_cv * c.ncols * 4);
@@ -1666,67 +924,6 @@ static int knn_candidates(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src,
     ProfScope ps(ctx, s, ws, "knn.exact");       // ~0 when the two-stage search succeeded (the kernel exits on the flag)
     hipLaunchKernelGGL(knn_topk_split_kernel, dim3((unsigned)c.units[2]), dim3(512), 0, s, L->segs, qn, c.ncols, T, L->cv, L->ci, (const int*)L->flag);
     return 0;
-}
-
-int run_knn_topk(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const float* prepared, int64_t N,
-                 float* sims_out, int64_t* idx_out, int B, int T) {
-    const KnnSegIn one{prepared, N, 0, B * T};
-    KnnCall c;
-    TVC_CHECK(knn_call_plan(ctx, &one, 1, B * T, &c));
-    KnnLists L;
-    TVC_CHECK(knn_candidates(ctx, s, ws, src, c, B, T, &L));
-    if (ws.dry) return 0;
-    hipLaunchKernelGGL(knn_merge_kernel, dim3((c.ncols + 255) / 256), dim3(256), 0, s, L.cv, L.ci, c.seg[0].nsE, c.ncols, sims_out, idx_out, L.rv, L.ri, L.flag);
-    return launch_check(ctx, "knn_topk");
-}
-
-int run_knn_slots(tvc_ctx* ctx, hipStream_t s, const float* prepared, int64_t N, const int64_t* idx, float* slots, int64_t nslots) {
-    hipLaunchKernelGGL(knn_slot_gather_kernel, dim3((unsigned)nslots), dim3(192), 0, s, prepared, idx, (long)nslots, (long)N, (long)npad128(N), slots);
-    return launch_check(ctx, "knn_slots");
-}
-
-int run_knn_finish(tvc_ctx* ctx, hipStream_t s, const float* slots, float* out, int B, int T) {
-    const int ncols = B * T;
-    hipLaunchKernelGGL(knn_finish_kernel, dim3((ncols + 31) / 32), dim3(256), 0, s, slots, ncols, T, out);
-    return launch_check(ctx, "knn_finish");
-}
-
-int run_knn_segs(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const KnnSegIn* in, int nin, float* out, int64_t* idx_out, int B, int T) {
-    KnnCall c;
-    TVC_CHECK(knn_call_plan(ctx, in, nin, B * T, &c));
-    KnnLists L;
-    TVC_CHECK(knn_candidates(ctx, s, ws, src, c, B, T, &L));
-    if (ws.dry) return 0;
-    if (L.col2seg)
-        hipLaunchKernelGGL(knn_merge_gather_kernel<true>, dim3((c.ncols + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)L.col2seg, c.ncols, T,
-                           out, idx_out, L.rv, L.ri, (const int*)L.flag);
-    else
-        hipLaunchKernelGGL(knn_merge_gather_kernel<false>, dim3((c.ncols + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)nullptr, c.ncols, T,
-                           out, idx_out, L.rv, L.ri, (const int*)L.flag);
-    return launch_check(ctx, "knn_match");
-}
-
-// in[]: the (term, row) runs over the M * B * T virtual columns, term-major (term m's copy of real column n is column m * B * T + n); one
-// knn_candidates walk - every pass one launch, as run_knn_segs -, then the blend gather.  idx_out (nullable): [M][B][T][4].  A ragged batch
-// (ctx->rag: B = 1, T = all its frames) finds a column's weight row through the batch's tables.
-int run_knn_blend(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const KnnSegIn* in, int nin, int M, const float* weights, float* out,
-                  int64_t* idx_out, int B, int T) {
-    KnnCall c;
-    TVC_CHECK(knn_call_plan(ctx, in, nin, M * B * T, &c));
-    KnnLists L;
-    TVC_CHECK(knn_candidates(ctx, s, ws, src, c, M * B, T, &L, B));
-    if (ws.dry) return 0;
-    const RagHost* h = ctx->rag;
-    hipLaunchKernelGGL(knn_merge_blend_gather_kernel, dim3((B * T + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)L.col2seg, B * T, T, M, weights,
-                       h ? (const int*)h->d_col2b : (const int*)nullptr, h ? (const int*)h->d_row : (const int*)nullptr, out, idx_out, L.rv, L.ri,
-                       (const int*)L.flag);
-    return launch_check(ctx, "knn_match_blend");
-}
-
-int run_knn(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const float* prepared, int64_t N,
-            float* out, int64_t* idx_out, int B, int T) {
-    const KnnSegIn one{prepared, N, 0, B * T};
-    return run_knn_segs(ctx, s, ws, src, &one, 1, out, idx_out, B, T);
 }
 
 }  // namespace tvc

@@ -1,0 +1,349 @@
+// From the search's top-4 lists (knn.hip, knn_search.h) to results: the merge + gather of the whole-index match (one index, one per
+// row, a weighted blend), the index-sharded route's three steps (merge, slot gather, finish) and the |max| bounds of `matched`.
+// Every route averages the four rows with mean4 and stores through store_tile_along_t: equal lists give equal bits on all of them.
+#include "knn_blob.h"
+#include "knn_search.h"
+#include "tvc_common.h"
+
+namespace tvc {
+
+// ---- what the kernels below share ----------------------------------------------------------------------------------------------
+// the `nsplit` x 4 list entries of query column `col` of a search over `stride` columns -> one top-4 (sentinels as they are)
+__device__ __forceinline__ Top4 merge_lists(const float* __restrict__ cv, const int* __restrict__ ci, int nsplit, long stride, long col) {
+    Top4 t4;
+    t4.init();
+    for (int s = 0; s < nsplit; ++s) {
+        const long o = (s * stride + col) * 4;
+        for (int e = 0; e < 4; ++e) t4.insert(cv[o + e], ci[o + e]);
+    }
+    return t4;
+}
+// sel[4] = the rows column `col` of segment g (number si) gathers: its rescored lists (one "split") where the segment's two-stage search
+// succeeded, else the exact kernel's g.nsE splits, merged; never a sentinel; also written to idx_out[col] (nullable).  A column that is not
+// live (past the end of the call) reads nothing and selects row 0.
+__device__ __forceinline__ void merged_top4(const KnnSeg& g, int si, const int* __restrict__ flags, const float* __restrict__ cand_v,
+                                            const int* __restrict__ cand_i, const float* __restrict__ rv, const int* __restrict__ ri, long stride,
+                                            long col, bool live, int64_t* __restrict__ idx_out, int* sel) {
+    const bool rescored = g.two && flags[si] == 0;
+    Top4 t4;
+    t4.init();
+    if (live) {
+        t4 = merge_lists(rescored ? rv : cand_v, rescored ? ri : cand_i, rescored ? 1 : g.nsE, stride, col);
+        for (int e = 0; e < 4; ++e) t4.i[e] = (unsigned)t4.i[e] < (unsigned)g.N ? t4.i[e] : 0;   // never gather through a sentinel
+        if (idx_out)
+            for (int e = 0; e < 4; ++e) idx_out[col * 4 + e] = (int64_t)t4.i[e];
+    }
+    for (int e = 0; e < 4; ++e) sel[e] = live ? t4.i[e] : 0;
+}
+// r[qq][u][e] = channel k + 64 u of row sel[q][e] of query q = q0 + 4 qq's blob (src(q)): four queries' 48 loads in flight per lane (one
+// query at a time was eight serial round trips per wave and chunk - 48 us per launch whatever the batch, a chain of latencies)
+struct RowSrc { const float* blob; int kind, N; };
+template <class Src>
+__device__ __forceinline__ void gather4x3(float (&r)[4][3][4], int q0, Src src, const int (*sel)[4], int k) {
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) {
+        const int q = q0 + 4 * qq;
+        const RowSrc b = src(q);
+        const long Npad = blob_npad(b.N);
+#pragma unroll
+        for (int u = 0; u < 3; ++u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) r[qq][u][e] = blob_row_value(b.blob, b.kind, b.N, Npad, sel[q][e], k + 64 * u);
+    }
+}
+// the mean of the four rows, in the one order every route keeps: (((r0 + r1) + r2) + r3) * 0.25
+__device__ __forceinline__ float mean4(float r0, float r1, float r2, float r3) {
+    return __fadd_rn(__fadd_rn(__fadd_rn(r0, r1), r2), r3) * 0.25f;
+}
+// tile[q][kk] = channel kc + kk of column n0 + q -> out[b][kc + kk][t]: lanes run along the 32 queries (time), 8 k-rows per pass
+__device__ __forceinline__ void store_tile_along_t(const float (&tile)[32][193], float* __restrict__ out, int n0, int ncols, int T, int kc) {
+    for (int kk = threadIdx.x >> 5; kk < 192; kk += 8) {
+        const int q = threadIdx.x & 31;
+        const int n = n0 + q;
+        if (n < ncols) {
+            const int b = n / T, t = n - b * T;
+            out[((long)b * KD + kc + kk) * T + t] = tile[q][kk];
+        }
+    }
+}
+
+// One workgroup = 32 consecutive query columns: merge split candidates -> top-4, write indices,
+// gather the 4 raw rows per query (coalesced along the feature axis), average, and write
+// out[b][k][t] through an LDS transpose so stores run along t.  Every query takes its segment's blob and lists (col2seg: several
+// segments; the 32 columns may straddle a segment boundary).  MULTI = false: one segment, whose blob the gather reads as a uniform value.
+template <bool MULTI>
+static __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
+                                                                      const KnnSegs segs, const int* __restrict__ col2seg, int ncols, int T,
+                                                                      float* __restrict__ out, int64_t* __restrict__ idx_out,
+                                                                      const float* __restrict__ rv, const int* __restrict__ ri,
+                                                                      const int* __restrict__ flags) {
+    __shared__ int sel[32][4];
+    __shared__ float tile[32][193];
+    __shared__ const float* sblob[32];
+    __shared__ int skind[32], sN[32];
+    const int tid = threadIdx.x;
+    const int n0 = blockIdx.x * 32;
+    if (tid < 32) {
+        const int n = n0 + tid;
+        const int nc = n < ncols ? n : ncols - 1;      // (a column past the end gathers row 0 of the last column's blob: never stored)
+        const int si = MULTI ? col2seg[nc] : 0;
+        const KnnSeg g = seg_get(segs, si);
+        merged_top4(g, si, flags, cand_v, cand_i, rv, ri, ncols, n, n < ncols, idx_out, sel[tid]);
+        if (MULTI) {
+            sblob[tid] = g.blob;
+            skind[tid] = blob_kind(g.blob);
+            sN[tid] = g.N;
+        }
+    }
+    __syncthreads();
+    const int lane = tid & 63, wave = tid >> 6;
+    const RowSrc one{segs.one.blob, MULTI ? 0 : blob_kind(segs.one.blob), segs.one.N};      // MULTI = false: uniform values, no table read
+    for (int kc = 0; kc < KD; kc += 192) {
+        // gather: wave handles queries wave, wave+4, ...; lanes run along k (3 x 64 = 192)
+        for (int q0 = wave; q0 < 32; q0 += 16) {
+            float r[4][3][4];
+            if (MULTI) gather4x3(r, q0, [&](int q) { return RowSrc{sblob[q], skind[q], sN[q]}; }, sel, kc + lane);
+            else gather4x3(r, q0, [&](int) { return one; }, sel, kc + lane);
+#pragma unroll
+            for (int qq = 0; qq < 4; ++qq)
+#pragma unroll
+                for (int u = 0; u < 3; ++u) tile[q0 + 4 * qq][lane + 64 * u] = mean4(r[qq][u][0], r[qq][u][1], r[qq][u][2], r[qq][u][3]);
+        }
+        __syncthreads();
+        store_tile_along_t(tile, out, n0, ncols, T, kc);
+        __syncthreads();
+    }
+}
+
+// ---- a weighted blend of several indices (tvc_*_blend_f32) -------------------------------------------------------------------
+// Every source row is searched once per term: term m of the call's ncols real columns is the virtual columns [m * ncols, (m + 1) * ncols)
+// of ONE search (virtual row m * B + b holds the queries of source row b: query_normalize_kernel's Bsrc), whose segments are the
+// (term, row) runs - each with its own path and overflow flag, exactly the single-index search of that (row, blob).  This kernel is the
+// blend's knn_merge_gather_kernel<true>: one workgroup = 32 REAL columns; threads (m, q) merge term m's lists of column q and write its
+// indices; the gather then walks the terms per query, four queries in flight per wave as there, and keeps
+//   out = w_0 * mu_0;  out = out + w_m * mu_m  (m = 1 .. M - 1),   mu_m = (((r0 + r1) + r2) + r3) * 0.25f
+// in registers - products and sums rounded separately (__fmul_rn / __fadd_rn), in term order - so the per-term matched tensors never exist
+// in memory.  One LDS transpose, stores along t.  weights [rows][M] is the caller's DEVICE array, read here: a captured graph replays with
+// whatever it holds then.  The weight row of a column is its batch row, or rowmap[col2b[column]] in a ragged batch (ragged.h).
+constexpr int BLEND_MAX = TVC_BLEND_MAX;
+static __global__ __launch_bounds__(256) void knn_merge_blend_gather_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
+                                                                            const KnnSegs segs, const int* __restrict__ col2seg, int ncols, int T,
+                                                                            int M, const float* __restrict__ weights, const int* __restrict__ col2b,
+                                                                            const int* __restrict__ rowmap, float* __restrict__ out,
+                                                                            int64_t* __restrict__ idx_out, const float* __restrict__ rv,
+                                                                            const int* __restrict__ ri, const int* __restrict__ flags) {
+    __shared__ int sel[BLEND_MAX][32][4];
+    __shared__ float tile[32][193];
+    __shared__ const float* sblob[BLEND_MAX][32];
+    __shared__ int skind[BLEND_MAX][32], sN[BLEND_MAX][32];
+    __shared__ float sw[BLEND_MAX][32];
+    const int tid = threadIdx.x;
+    const int n0 = blockIdx.x * 32;
+    if (tid < 32 * M) {
+        const int m = tid >> 5, q = tid & 31;
+        const int n = n0 + q;
+        const bool live = n < ncols;
+        const int nc = live ? n : ncols - 1;            // (a column past the end gathers row 0 of the last column's blobs: never stored)
+        const long vcols = (long)M * ncols;             // the search's columns: the lists' stride
+        const long vc = (long)m * ncols + nc;           // this term's virtual column
+        const int si = col2seg ? col2seg[vc] : 0;
+        const KnnSeg g = seg_get(segs, si);
+        merged_top4(g, si, flags, cand_v, cand_i, rv, ri, vcols, vc, live, idx_out, sel[m][q]);
+        sblob[m][q] = g.blob;
+        skind[m][q] = blob_kind(g.blob);
+        sN[m][q] = g.N;
+        const int row = col2b ? rowmap[col2b[nc]] : nc / T;
+        sw[m][q] = weights[(long)row * M + m];
+    }
+    __syncthreads();
+    const int lane = tid & 63, wave = tid >> 6;
+    for (int kc = 0; kc < KD; kc += 192) {
+        for (int q0 = wave; q0 < 32; q0 += 16) {
+            float acc[4][3];
+#pragma unroll 1
+            for (int m = 0; m < M; ++m) {
+                float r[4][3][4];
+                gather4x3(r, q0, [&](int q) { return RowSrc{sblob[m][q], skind[m][q], sN[m][q]}; }, sel[m], kc + lane);
+#pragma unroll
+                for (int qq = 0; qq < 4; ++qq) {
+                    const float w = sw[m][q0 + 4 * qq];
+#pragma unroll
+                    for (int u = 0; u < 3; ++u) {
+                        const float term = __fmul_rn(w, mean4(r[qq][u][0], r[qq][u][1], r[qq][u][2], r[qq][u][3]));
+                        acc[qq][u] = m == 0 ? term : __fadd_rn(acc[qq][u], term);
+                    }
+                }
+            }
+#pragma unroll
+            for (int qq = 0; qq < 4; ++qq)
+#pragma unroll
+                for (int u = 0; u < 3; ++u) tile[q0 + 4 * qq][lane + 64 * u] = acc[qq][u];
+        }
+        __syncthreads();
+        store_tile_along_t(tile, out, n0, ncols, T, kc);
+        __syncthreads();
+    }
+}
+
+// out[i] = sum_m |w[row[i]][m]| * (the |max| of blob (i, m)), in term order, products and sums rounded separately: the bound of row i's blended
+// content (|mu_m| <= its blob's |max|), the decoder's content bound of a blend call.  One workgroup; the blobs and the weight rows travel as
+// kernel arguments (like index_amax_rows_kernel), the weights are read from the caller's device array.
+constexpr int BB_ROWS = 64;
+struct BlendBoundChunk {
+    const float* p[BB_ROWS * BLEND_MAX];
+    int row[BB_ROWS];
+};
+static __global__ __launch_bounds__(BB_ROWS) void blend_bound_kernel(BlendBoundChunk c, const float* __restrict__ weights, int M, float* __restrict__ out, int n) {
+    const int i = threadIdx.x;
+    if (i >= n) return;
+    const float* w = weights + (long)c.row[i] * M;
+    float b = __fmul_rn(fabsf(w[0]), *blob_amax(c.p[i * M]));
+    for (int m = 1; m < M; ++m) b = __fadd_rn(b, __fmul_rn(fabsf(w[m]), *blob_amax(c.p[i * M + m])));
+    out[i] = b;
+}
+int run_knn_blend_bound(tvc_ctx* ctx, hipStream_t s, const std::vector<const float*>& blobs, const std::vector<int>& rows, int M, const float* weights, float* out) {
+    for (size_t o = 0; o < rows.size(); o += BB_ROWS) {
+        BlendBoundChunk c;
+        const int n = (int)(rows.size() - o < BB_ROWS ? rows.size() - o : BB_ROWS);
+        for (int i = 0; i < n; ++i) {
+            c.row[i] = rows[o + i];
+            for (int m = 0; m < M; ++m) c.p[i * M + m] = blobs[(o + i) * M + m];
+        }
+        hipLaunchKernelGGL(blend_bound_kernel, dim3(1), dim3(BB_ROWS), 0, s, c, weights, M, out + o, n);
+    }
+    return launch_check(ctx, "knn_blend_bound");
+}
+
+// out[i] = the |max| of blob i (one index per utterance: each utterance's content bound is its own index's): the pointers travel as kernel
+// arguments, like ragged.h's upload_ints
+struct BlobChunk {
+    const float* p[480];
+};
+static __global__ void index_amax_rows_kernel(BlobChunk c, float* __restrict__ out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = *blob_amax(c.p[i]);
+}
+int run_knn_amax_rows(tvc_ctx* ctx, hipStream_t s, const std::vector<const float*>& blobs, float* out) {
+    for (size_t o = 0; o < blobs.size(); o += 480) {
+        BlobChunk c;
+        const int n = (int)(blobs.size() - o < 480 ? blobs.size() - o : 480);
+        for (int i = 0; i < n; ++i) c.p[i] = blobs[o + i];
+        hipLaunchKernelGGL(index_amax_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, s, c, out + o, n);
+    }
+    return launch_check(ctx, "knn_amax_rows");
+}
+
+// ---- index-sharded search (one index shard per GPU): local top-4 with similarities, slot gather, finish ----
+// merge the split candidates of every query -> this shard's top-4 (similarity, local index)
+static __global__ __launch_bounds__(256) void knn_merge_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i, int nsplit, int ncols,
+                                                               float* __restrict__ sims_out, int64_t* __restrict__ idx_out,
+                                                               const float* __restrict__ rv, const int* __restrict__ ri, const int* __restrict__ flag) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= ncols) return;
+    if (flag && *flag == 0) {
+        cand_v = rv;
+        cand_i = ri;
+        nsplit = 1;
+    }
+    const Top4 t4 = merge_lists(cand_v, cand_i, nsplit, ncols, n);      // sentinels as they are: the caller merges across shards
+    for (int e = 0; e < 4; ++e) {
+        sims_out[(long)n * 4 + e] = t4.v[e];
+        idx_out[(long)n * 4 + e] = (int64_t)t4.i[e];
+    }
+}
+// slots[n][e][:] = raw row idx[n][e] of this shard, or zeros where idx < 0 (the row lives on another rank)
+static __global__ __launch_bounds__(192) void knn_slot_gather_kernel(const float* __restrict__ blob, const int64_t* __restrict__ idx, long nslots,
+                                                                     long N, long Npad, float* __restrict__ slots) {
+    const long sl = blockIdx.x;
+    if (sl >= nslots) return;
+    const int kind = blob_kind(blob);
+    const int64_t i = idx[sl];
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (i >= 0 && i < N) {
+        const int k = 4 * threadIdx.x;
+        v = make_float4(blob_row_value(blob, kind, N, Npad, i, k), blob_row_value(blob, kind, N, Npad, i, k + 1),
+                        blob_row_value(blob, kind, N, Npad, i, k + 2), blob_row_value(blob, kind, N, Npad, i, k + 3));
+    }
+    reinterpret_cast<float4*>(slots + sl * KD)[threadIdx.x] = v;
+}
+// out[b][k][t] = (((s0 + s1) + s2) + s3) * 0.25 from slots [B*T][4][768] (the same order as the single-GPU gather),
+// transposed through LDS so reads run along k and stores along t
+static __global__ __launch_bounds__(256) void knn_finish_kernel(const float* __restrict__ slots, int ncols, int T, float* __restrict__ out) {
+    __shared__ float tile[32][193];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n0 = blockIdx.x * 32;
+    for (int kc = 0; kc < KD; kc += 192) {
+        for (int q = wave; q < 32; q += 4) {
+            const int n = n0 + q < ncols ? n0 + q : ncols - 1;
+            const float* r0 = slots + ((long)n * 4) * KD + kc;
+#pragma unroll
+            for (int u = 0; u < 3; ++u) {
+                const int k = lane + 64 * u;
+                tile[q][k] = mean4(r0[k], r0[KD + k], r0[2 * KD + k], r0[3 * KD + k]);
+            }
+        }
+        __syncthreads();
+        store_tile_along_t(tile, out, n0, ncols, T, kc);
+        __syncthreads();
+    }
+}
+
+int run_knn_topk(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const float* prepared, int64_t N,
+                 float* sims_out, int64_t* idx_out, int B, int T) {
+    const KnnSegIn one{prepared, N, 0, B * T};
+    KnnCall c;
+    TVC_CHECK(knn_call_plan(ctx, &one, 1, B * T, &c));
+    KnnLists L;
+    TVC_CHECK(knn_candidates(ctx, s, ws, src, c, B, T, &L));
+    if (ws.dry) return 0;
+    hipLaunchKernelGGL(knn_merge_kernel, dim3((c.ncols + 255) / 256), dim3(256), 0, s, L.cv, L.ci, c.seg[0].nsE, c.ncols, sims_out, idx_out, L.rv, L.ri, L.flag);
+    return launch_check(ctx, "knn_topk");
+}
+
+int run_knn_slots(tvc_ctx* ctx, hipStream_t s, const float* prepared, int64_t N, const int64_t* idx, float* slots, int64_t nslots) {
+    hipLaunchKernelGGL(knn_slot_gather_kernel, dim3((unsigned)nslots), dim3(192), 0, s, prepared, idx, (long)nslots, (long)N, blob_npad(N), slots);
+    return launch_check(ctx, "knn_slots");
+}
+
+int run_knn_finish(tvc_ctx* ctx, hipStream_t s, const float* slots, float* out, int B, int T) {
+    const int ncols = B * T;
+    hipLaunchKernelGGL(knn_finish_kernel, dim3((ncols + 31) / 32), dim3(256), 0, s, slots, ncols, T, out);
+    return launch_check(ctx, "knn_finish");
+}
+
+int run_knn_segs(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const KnnSegIn* in, int nin, float* out, int64_t* idx_out, int B, int T) {
+    KnnCall c;
+    TVC_CHECK(knn_call_plan(ctx, in, nin, B * T, &c));
+    KnnLists L;
+    TVC_CHECK(knn_candidates(ctx, s, ws, src, c, B, T, &L));
+    if (ws.dry) return 0;
+    const auto kernel = L.col2seg ? knn_merge_gather_kernel<true> : knn_merge_gather_kernel<false>;      // several segments : one (no table read)
+    hipLaunchKernelGGL(kernel, dim3((c.ncols + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)L.col2seg, c.ncols, T, out, idx_out, L.rv, L.ri,
+                       (const int*)L.flag);
+    return launch_check(ctx, "knn_match");
+}
+
+// in[]: the (term, row) runs over the M * B * T virtual columns, term-major (term m's copy of real column n is column m * B * T + n); one
+// knn_candidates walk - every pass one launch, as run_knn_segs -, then the blend gather.  idx_out (nullable): [M][B][T][4].  A ragged batch
+// (ctx->rag: B = 1, T = all its frames) finds a column's weight row through the batch's tables.
+int run_knn_blend(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const KnnSegIn* in, int nin, int M, const float* weights, float* out,
+                  int64_t* idx_out, int B, int T) {
+    KnnCall c;
+    TVC_CHECK(knn_call_plan(ctx, in, nin, M * B * T, &c));
+    KnnLists L;
+    TVC_CHECK(knn_candidates(ctx, s, ws, src, c, M * B, T, &L, B));
+    if (ws.dry) return 0;
+    const RagHost* h = ctx->rag;
+    hipLaunchKernelGGL(knn_merge_blend_gather_kernel, dim3((B * T + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)L.col2seg, B * T, T, M, weights,
+                       h ? (const int*)h->d_col2b : (const int*)nullptr, h ? (const int*)h->d_row : (const int*)nullptr, out, idx_out, L.rv, L.ri,
+                       (const int*)L.flag);
+    return launch_check(ctx, "knn_match_blend");
+}
+
+int run_knn(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const float* prepared, int64_t N,
+            float* out, int64_t* idx_out, int B, int T) {
+    const KnnSegIn one{prepared, N, 0, B * T};
+    return run_knn_segs(ctx, s, ws, src, &one, 1, out, idx_out, B, T);
+}
+
+}  // namespace tvc

@@ -1,6 +1,6 @@
 // match_features with the reference's FULL signature (module/tinyvc/feature_retrieval.py:15-33): k = 1 ... 8 nearest index vectors under
-// metrics 'cos' / 'IP' / 'L2', the mean of the k raw vectors.  The inference path only ever asks for k = 4, 'cos' - that is knn.hip's
-// prepared-index search on the matrix pipe; this file serves every other argument on the RAW index [768][N] in plain fp32: no prepared
+// metrics 'cos' / 'IP' / 'L2', the mean of the k raw vectors.  The inference path only ever asks for k = 4, 'cos' - that is the
+// prepared-index search on the matrix pipe (knn_prepare.hip, knn.hip, knn_gather.hip); this file serves every other argument on the RAW index [768][N] in plain fp32: no prepared
 // blob, no split precision, no assumption about the vectors' range (inner products and distances of un-normalised vectors are not bounded
 // the way cosines are).  It is not a hot path - HBM- and fma-bound, a few milliseconds for the headline shapes - and is written for
 // clarity: exact fp32 similarities in one fixed summation order, a lane-local top-k, one merge per query.

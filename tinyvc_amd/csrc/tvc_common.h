@@ -325,18 +325,16 @@ int run_noise_ifft(tvc_ctx*, hipStream_t, const float* kern, const float* angle,
 // emax (optional, equal-length batches only): per-utterance max of the pooled |x| = max |wav| of the utterance, written (not accumulated)
 int run_energy(tvc_ctx*, hipStream_t, Ws&, const float* wav, float* energy, int B, int64_t L, float* emax = nullptr, float* spec_bound = nullptr,
                float* zero = nullptr, int nz = 0);      // (emax given: the pooled-maximum launch also zeroes zero[0 .. nz))
-const float* knn_index_amax(const float* prepared);
-int run_knn_amax_rows(tvc_ctx*, hipStream_t, const std::vector<const float*>& blobs, float* out);      // out[i] = *knn_index_amax(blobs[i])
+int run_knn_amax_rows(tvc_ctx*, hipStream_t, const std::vector<const float*>& blobs, float* out);      // out[i] = *blob_amax(blobs[i]) (knn_gather.hip)
 // out[b] = a * in[b * in_stride] + c for b < n: a |max| slot from the slot of the tensor it is a bounded function of (frontend.hip)
 int run_slot_affine(tvc_ctx*, hipStream_t, float* out, const float* in, int in_stride, float a, float c, int n);
 int run_slot_prep(tvc_ctx*, hipStream_t, float* zero, int nz, float* o1, const float* in1, int s1, float a1, float c1, float* o2, const float* in2, int s2, float a2,
                   float c2, float* o3, float a3, float c3, int n);
-// prepared kNN blob (knn.hip): header word 0 = magic, word 5 = format version.  Version 2 (round 5): word 4 holds the raw vectors' |max| (a float), which
+// prepared kNN blob (knn_blob.h; written by knn_prepare.hip): header word 0 = magic, word 5 = format version.  Version 2 (round 5): word 4 holds the raw vectors' |max| (a float), which
 // the decoder takes as the bound of `matched` - a blob of another version has 0 there (= "no scaling": the fp16 range guard silently off) and is refused.
 constexpr int kBlobMagic = 0x54564B4E, kBlobVersion = 2;
 constexpr int kFilterSlotX = 2;       // ... and the one of its input contraction's output (S_X)
 constexpr int kFilterSlots = 41;      // run_filter's |max| slots per utterance (decoder.hip S_COUNT)
-      // device pointer to the prepared index's |max| (one float)
 // spec_bound (optional): per-utterance upper bounds of |spec| (the slot of the input contraction); nullptr = one pass over spec measures it
 int run_encoder(tvc_ctx*, hipStream_t, Ws&, const float* spec, float* ssl, float* f0,
                 float* logits, int B, int T, const float* spec_bound = nullptr, float* zeroed_slots = nullptr,      // zeroed_slots: 3 x utterances floats already zeroed on this stream
@@ -345,7 +343,7 @@ int run_encoder(tvc_ctx*, hipStream_t, Ws&, const float* spec, float* ssl, float
 int run_pitch_decode(tvc_ctx*, hipStream_t, const float* logits, float* f0, int B, int T);
 int run_knn(tvc_ctx*, hipStream_t, Ws&, const float* src, const float* prepared, int64_t N,
             float* out, int64_t* idx_out, int B, int T);
-// several prepared indices in one call (knn.hip segments): in[] = runs of query columns [col0, col0 + ncols) of the [B][768][T] queries
+// several prepared indices in one call (knn_gather.hip; knn_search.h segments): in[] = runs of query columns [col0, col0 + ncols) of the [B][768][T] queries
 // that search `blob` (prepared for N vectors), in column order, covering all B * T columns; adjacent runs of one blob are one segment
 struct KnnSegIn {
     const float* blob;
@@ -353,12 +351,12 @@ struct KnnSegIn {
     int col0, ncols;
 };
 int run_knn_segs(tvc_ctx*, hipStream_t, Ws&, const float* src, const KnnSegIn* in, int nin, float* out, int64_t* idx_out, int B, int T);
-// a weighted blend of M indices per row (knn.hip): in[] = the (term, row) runs over M * B * T VIRTUAL query columns, term-major - term m's
+// a weighted blend of M indices per row (knn_gather.hip): in[] = the (term, row) runs over M * B * T VIRTUAL query columns, term-major - term m's
 // search of real column n is column m * B * T + n -, weights = the caller's device array [rows][M] (read by the kernels, never by the host),
 // out [B][768][T] = w_0 * mu_0 + ... in term order, idx_out (nullable) [M][B][T][4]
 int run_knn_blend(tvc_ctx*, hipStream_t, Ws&, const float* src, const KnnSegIn* in, int nin, int M, const float* weights, float* out, int64_t* idx_out,
                   int B, int T);
-// out[i] = sum_m |weights[rows[i]][m]| * *knn_index_amax(blobs[i * M + m]): the bound of row i's blended content
+// out[i] = sum_m |weights[rows[i]][m]| * *blob_amax(blobs[i * M + m]): the bound of row i's blended content
 int run_knn_blend_bound(tvc_ctx*, hipStream_t, const std::vector<const float*>& blobs, const std::vector<int>& rows, int M, const float* weights, float* out);
 
 // ---- one conversion, as the entries describe it to convert_impl (api.hip) and to the ragged batch loop (ragged.hip) -----------
