@@ -414,6 +414,41 @@ int tvc_convert_ragged_auto_f32(tvc_ctx* ctx, void* stream, const float* wav, in
                                 float pitch_shift, const float* pitch_shifts, float* shift_out, const float* noise_angle, uint64_t seed,
                                 float* wave, int B, void* ws, size_t ws_bytes);
 
+/* automatic pitch in streams: a per-stream pitch tracker on the device -------------------------- */
+/* A streaming block's window is 28 frames, so its own median jumps from block to block: a stream's register is a statistic over its
+ * HISTORY, kept on the device (thousands of streams in one call, one captured graph per block, no host synchronisation).
+ * State, device tensors owned by the caller, one set per set of S streams that advance in lock step:
+ *   ring [S][W] fp32  - the last W voiced f0 values of each stream, as a ring; unwritten slots are 0.0, so a row's live entries are
+ *                       exactly its entries > 0.  1 <= W <= TVC_PITCH_TRACK_MAX_WINDOW (a row fits LDS: one code path).
+ *   count [S] int64   - voiced frames appended since the last reset: the write cursor is count % W, the fill min(count, W)
+ *   auto_shift [S] fp32 - the automatic part of the shift applied in the latest block
+ * All zero = a fresh stream.  One block, one launch of one 256-thread workgroup per stream, no workspace, no floating-point atomics; the
+ * host values T, start, n (0 <= n <= 256, start + n <= T), W, min_voiced >= 1, slew >= 0 (+inf allowed) and the offsets travel as kernel
+ * arguments (baked into a capture); f0, target_f0 and the state are read when the kernel runs.  For every stream s:
+ *   1. x_k = f0[s][start + k], k = 0 .. n - 1; a frame is voiced iff x_k > 0 (zero, negatives and NaN are not: tvc_pitch_match_f32's rule)
+ *   2. the voiced x_k go into the ring in ascending k at ring[s][(count + j) % W], j = 0, 1, ..; then count += nv.  The result equals
+ *      appending them one at a time: with nv > W only the last W survive.
+ *   3. fill = min(count, W); median = the lower median of the fill live entries (rank (fill - 1) / 2; torch.median bit for bit; 0 when empty)
+ *   4. wanted = (fill >= min_voiced && target_f0[s] > 0) ? (float)(12 * log2((double)target_f0[s] / (double)median)) : 0.f
+ *   5. a = auto_shift[s], d = wanted - a (fp32): if !(|d| > slew) a = wanted (it lands exactly) else a = a + copysignf(slew, d);
+ *      auto_shift[s] = a.  slew is in semitones per call; +inf never limits, 0 never moves.
+ *   6. shift[s] = offset[s] + a, one fp32 add; offset[s] = pitch_shifts[s], or pitch_shift when pitch_shifts is NULL (HOST values)
+ *   7. f0_shifted[s][t] = tvc_shift_frequency_f32(f0[s][t], shift[s]) for all T columns, in the same launch.
+ * tvc_pitch_track_f32, the stage call over a caller's f0 [S][T] (device).  Outputs (device, each may be NULL): median_out [S], count_out [S]
+ * int64 (= count), shift_out [S], f0_shifted [S][T].  Every argument is checked before any device work.
+ * tvc_convert_track_f32: tvc_convert_auto_f32 (equal lengths; one index per row, or a blend with weights) with the tracker in the place of
+ * the per-call register: B = S streams, T = L / 480, and row b's shift is step 6's.  target_f0, shift_out, noise and capture rules as in
+ * tvc_convert_auto_f32; row b is bit-identical to the multi-index / blend call given shift_out[b] as its host shift.  Workspace:
+ * tvc_workspace_bytes_auto (the tracker takes none).  There is no ragged form: streams advance in lock step. */
+#define TVC_PITCH_TRACK_MAX_WINDOW 8192
+int tvc_pitch_track_f32(tvc_ctx* ctx, void* stream, const float* f0, int S, int T, int start, int n, const float* target_f0,
+                        float pitch_shift, const float* pitch_shifts, int W, int min_voiced, float slew, float* ring, int64_t* count,
+                        float* auto_shift, float* median_out, int64_t* count_out, float* shift_out, float* f0_shifted);
+int tvc_convert_track_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M,
+                          const float* weights, const float* target_f0, int start, int n, int W, int min_voiced, float slew, float* ring,
+                          int64_t* count, float* auto_shift, float pitch_shift, const float* pitch_shifts, float* shift_out,
+                          const float* noise_angle, uint64_t seed, float* wave, int B, int64_t L, void* ws, size_t ws_bytes);
+
 /* streaming tail -------------------------------------------------------------------------- */
 /* StreamInfer.audio_callback after convert (reference module/infer/stream.py:74-95), batched over
  * S streams: y [S, Ly] converted buffers; sola_buf [S,1920] in/out; fade_in [1920] = the sin^2

@@ -261,7 +261,9 @@ int tvc::convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const ConvertCall& c)
     {
         ProfScope ps(ctx, s, ws, "encoder");
         TVC_CHECK(run_encoder(ctx, s, ws, spec, ssl, f0, nullptr, B, T, spec_bound, enc_slots, auto_pitch ? nullptr : f0s, c.shift, rshift));
-        if (auto_pitch && !ws.dry) {      // one workgroup per utterance: its register, its shift (offset = the host value), its shifted f0
+        if (c.track && !ws.dry) {      // one workgroup per stream: its history's register, the slew-limited shift, its shifted f0 (no workspace)
+            TVC_CHECK(run_pitch_track(ctx, s, f0, B, T, *c.track, c.target_f0, c.shift, c.shifts, nullptr, nullptr, c.shift_out, f0s));
+        } else if (auto_pitch && !ws.dry) {      // one workgroup per utterance: its register, its shift (offset = the host value), its shifted f0
             std::vector<PitchRow> rows((size_t)NB);
             for (int i = 0; i < NB; ++i) {
                 const int r = ctx->rag ? ctx->rag->row[i] : i;
@@ -764,6 +766,43 @@ int tvc_convert_ragged_auto_f32(tvc_ctx* ctx, void* stream, const float* wav, in
     if (!target_f0) return fail(ctx, TVC_ERR_ARG, "tvc_convert_ragged_auto_f32: target_f0 is NULL (a device array of B registers in Hz)");
     const ConvertCall c{wav, wave, B, Lmax, lens, ix, pitch_shift, pitch_shifts, noise_angle, seed, target_f0, shift_out};
     return convert_entry(ctx, stream, c, true, wsp, ws_bytes, "tvc_convert_ragged_auto_f32");
+}
+
+// ---- automatic pitch in streams: the register is the stream's history (a ring per stream on the device) ---------------------------------------
+// every host value of a tracker call, checked under the entry's own name before any device work
+static int track_check(tvc_ctx* ctx, int S, int T, const PitchTrackState& t, const float* target_f0, const char* what) {
+    if (S <= 0 || T <= 0) return fail(ctx, TVC_ERR_ARG, "%s: S = %d streams of T = %d frames", what, S, T);
+    if (!target_f0) return fail(ctx, TVC_ERR_ARG, "%s: target_f0 is NULL (a device array of S registers in Hz)", what);
+    if (!t.ring || !t.count || !t.autos) return fail(ctx, TVC_ERR_ARG, "%s: the tracker state (ring [S][W], count [S], auto [S]) has a NULL pointer", what);
+    if (t.W < 1 || t.W > TVC_PITCH_TRACK_MAX_WINDOW) return fail(ctx, TVC_ERR_ARG, "%s: W = %d; a ring holds 1 ... %d frames", what, t.W, TVC_PITCH_TRACK_MAX_WINDOW);
+    if (t.n < 0 || t.n > 256) return fail(ctx, TVC_ERR_ARG, "%s: n = %d new frames; a block brings 0 ... 256", what, t.n);
+    if (t.start < 0 || (int64_t)t.start + t.n > T) return fail(ctx, TVC_ERR_ARG, "%s: columns [%d, %d + %d) do not lie within T = %d", what, t.start, t.start, t.n, T);
+    if (t.min_voiced < 1) return fail(ctx, TVC_ERR_ARG, "%s: min_voiced = %d; at least 1", what, t.min_voiced);
+    if (!(t.slew >= 0.f)) return fail(ctx, TVC_ERR_ARG, "%s: slew must be >= 0 semitones per call (+inf: no limit)", what);
+    return 0;
+}
+int tvc_pitch_track_f32(tvc_ctx* ctx, void* stream, const float* f0, int S, int T, int start, int n, const float* target_f0, float pitch_shift,
+                        const float* pitch_shifts, int W, int min_voiced, float slew, float* ring, int64_t* count, float* auto_shift, float* median_out,
+                        int64_t* count_out, float* shift_out, float* f0_shifted) {
+    if (!ctx) return TVC_ERR_ARG;
+    if (!f0) return fail(ctx, TVC_ERR_ARG, "tvc_pitch_track_f32: f0 is NULL");
+    const PitchTrackState t{start, n, W, min_voiced, slew, ring, count, auto_shift};
+    TVC_CHECK(track_check(ctx, S, T, t, target_f0, "tvc_pitch_track_f32"));
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    return run_pitch_track(ctx, (hipStream_t)stream, f0, S, T, t, target_f0, pitch_shift, pitch_shifts, median_out, count_out, shift_out, f0_shifted);
+}
+int tvc_convert_track_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M, const float* weights,
+                          const float* target_f0, int start, int n, int W, int min_voiced, float slew, float* ring, int64_t* count, float* auto_shift,
+                          float pitch_shift, const float* pitch_shifts, float* shift_out, const float* noise_angle, uint64_t seed, float* wave, int B,
+                          int64_t L, void* wsp, size_t ws_bytes) {
+    ConvertIndex ix;
+    TVC_CHECK(auto_index(ctx, B, prepared, N, M, weights, &ix, "tvc_convert_track_f32"));
+    const PitchTrackState t{start, n, W, min_voiced, slew, ring, count, auto_shift};
+    if (L <= 0 || L / kHop > 0x7fffffff) return fail(ctx, TVC_ERR_ARG, "tvc_convert_track_f32: bad argument (L must be a positive multiple of 480)");
+    TVC_CHECK(track_check(ctx, B, (int)(L / kHop), t, target_f0, "tvc_convert_track_f32"));
+    ConvertCall c{wav, wave, B, L, nullptr, ix, pitch_shift, pitch_shifts, noise_angle, seed, target_f0, shift_out};
+    c.track = &t;
+    return convert_entry(ctx, stream, c, false, wsp, ws_bytes, "tvc_convert_track_f32");
 }
 
 int tvc_knn_match_blend_f32(tvc_ctx* ctx, void* stream, const float* src, const float* const* prepared, const int64_t* N, int M, const float* weights,

@@ -218,23 +218,22 @@ struct PitchRowChunk {
     float offset[kPmRows];
 };
 
-static __global__ __launch_bounds__(256) void pitch_match_kernel(const float* __restrict__ f0, PitchRowChunk rows, const float* __restrict__ target,
-                                                                 float* __restrict__ median_out, int* __restrict__ voiced_out, float* __restrict__ shift_out,
-                                                                 float* __restrict__ f0s) {
-    __shared__ unsigned hist[4][256];
-    __shared__ unsigned wsum[4];
-    __shared__ unsigned sel_digit, sel_rank;
-    __shared__ float sh_shift;
+// The select itself, shared by pitch_match_kernel (a row in global memory) and pitch_track_kernel (a ring staged in LDS): the bit pattern of
+// the lower median of the values > 0 among p[0 .. n), and their number in *nv_out (0: no voiced value, the result is 0).  Called by all
+// 256 threads of the workgroup; the result is uniform over it.
+struct PitchSelectLds {
+    unsigned hist[4][256];
+    unsigned wsum[4];
+    unsigned sel_digit, sel_rank;
+};
+static __device__ __forceinline__ unsigned pitch_select(const float* __restrict__ p, long n, PitchSelectLds& lds, unsigned* nv_out) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = blockIdx.x;
-    const long n = rows.len[r];
-    const float* p = f0 + rows.start[r];
     unsigned prefix = 0, rank = 0, nv = 0;
 #pragma unroll 1
     for (int pass = 0; pass < 4; ++pass) {
         const int lo = pass == 3 ? 0 : 23 - 8 * pass;            // 23, 15, 7, 0
         const int width = pass == 3 ? 7 : 8;
-        for (int w = 0; w < 4; ++w) hist[w][tid] = 0;
+        for (int w = 0; w < 4; ++w) lds.hist[w][tid] = 0;
         __syncthreads();
         for (long base = 0; base < n; base += 256 * 4) {
             float v[4];
@@ -255,27 +254,27 @@ static __global__ __launch_bounds__(256) void pitch_match_kernel(const float* __
                     const int first = __ffsll((long long)act) - 1;
                     const unsigned d0 = (unsigned)__shfl((int)digit, first);
                     const unsigned long long same = __ballot(live && digit == d0);
-                    if (lane == first) atomicAdd(&hist[wave][d0], (unsigned)__popcll(same));
+                    if (lane == first) atomicAdd(&lds.hist[wave][d0], (unsigned)__popcll(same));
                     if (digit == d0) live = false;
                 }
-                if (live) atomicAdd(&hist[wave][digit], 1u);
+                if (live) atomicAdd(&lds.hist[wave][digit], 1u);
             }
         }
         __syncthreads();
         // exclusive scan of the 256 bins (thread = bin): the bin that holds `rank`
-        const unsigned c = hist[0][tid] + hist[1][tid] + hist[2][tid] + hist[3][tid];
+        const unsigned c = lds.hist[0][tid] + lds.hist[1][tid] + lds.hist[2][tid] + lds.hist[3][tid];
         unsigned inc = c;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
             const unsigned t = (unsigned)__shfl_up((int)inc, o);
             if (lane >= o) inc += t;
         }
-        if (lane == 63) wsum[wave] = inc;
+        if (lane == 63) lds.wsum[wave] = inc;
         __syncthreads();
         unsigned before = 0, total = 0;
         for (int w = 0; w < 4; ++w) {
-            if (w < wave) before += wsum[w];
-            total += wsum[w];
+            if (w < wave) before += lds.wsum[w];
+            total += lds.wsum[w];
         }
         if (pass == 0) {
             nv = total;
@@ -284,13 +283,28 @@ static __global__ __launch_bounds__(256) void pitch_match_kernel(const float* __
         if (total == 0) break;      // (pass 0 only: no voiced frame; uniform over the workgroup)
         const unsigned excl = before + inc - c;
         if (c && excl <= rank && rank < excl + c) {
-            sel_digit = (unsigned)tid;
-            sel_rank = rank - excl;
+            lds.sel_digit = (unsigned)tid;
+            lds.sel_rank = rank - excl;
         }
         __syncthreads();
-        prefix = (prefix << width) | sel_digit;
-        rank = sel_rank;
+        prefix = (prefix << width) | lds.sel_digit;
+        rank = lds.sel_rank;
     }
+    *nv_out = nv;
+    return nv ? prefix : 0u;
+}
+
+static __global__ __launch_bounds__(256) void pitch_match_kernel(const float* __restrict__ f0, PitchRowChunk rows, const float* __restrict__ target,
+                                                                 float* __restrict__ median_out, int* __restrict__ voiced_out, float* __restrict__ shift_out,
+                                                                 float* __restrict__ f0s) {
+    __shared__ PitchSelectLds sel;
+    __shared__ float sh_shift;
+    const int tid = threadIdx.x;
+    const int r = blockIdx.x;
+    const long n = rows.len[r];
+    const float* p = f0 + rows.start[r];
+    unsigned nv;
+    const unsigned prefix = pitch_select(p, n, sel, &nv);
     if (tid == 0) {
         const float med = nv ? __uint_as_float(prefix) : 0.f;
         const int slot = rows.idx[r];
@@ -326,6 +340,99 @@ int run_pitch_match(tvc_ctx* ctx, hipStream_t s, const float* f0, const std::vec
         hipLaunchKernelGGL(pitch_match_kernel, dim3(n), dim3(256), 0, s, f0, c, target, median_out, voiced_out, shift_out, f0s);
     }
     return launch_check(ctx, "pitch_match");
+}
+
+// ---- the pitch register of a STREAM: a ring of its last W voiced f0 values, and a slew-limited shift onto the target's ---------------------
+// A block's window is 28 frames: its own median jumps from block to block.  A stream's register is the lower median over its history, kept on
+// the device (thousands of streams, one captured graph per block, no host synchronisation): per stream a ring [W] of the last W voiced
+// values (unwritten slots 0.0, so the live entries are the entries > 0), count = the voiced frames appended since the last reset (write
+// cursor count % W, fill min(count, W)) and `auto` = the automatic part of the latest shift.  One 256-thread workgroup per stream:
+//   1. x_k = f0[s][start + k], k < n <= 256 (one per thread); voiced iff x_k > 0, pitch_match's rule
+//   2. the voiced x_k in ascending k go to ring[(count + j) % W], j their rank among the voiced: a ballot prefix per wave plus the wave
+//      offsets.  Equal to appending one at a time: of nv > W values only the last W are written (so no slot is written twice); count += nv.
+//      The row is staged in LDS once, the append goes to LDS and to global memory, the select reads LDS: one global read of the row.
+//   3. median = pitch_select over the staged row (rank (fill - 1) / 2 of its fill live entries)
+//   4. wanted = fill >= min_voiced && target > 0 ? (float)(12 log2((double)target / (double)median)) : 0
+//   5. d = wanted - auto;  |d| > slew ? auto += copysign(slew, d) : auto = wanted (it lands exactly; slew = +inf always lands, 0 never moves)
+//   6. shift = offset + auto (one fp32 add), 7. f0s[s][:] = shift_frequency_one(f0[s][:], shift) over all T columns.
+// W <= 8192: a row is at most 32 KiB of (dynamic) LDS, one code path.  Host values (T, start, n, W, min_voiced, slew, the offsets) are kernel
+// arguments, baked into a capture like pitch_match's row descriptions; target, the ring, count and auto are read when the kernel runs.
+// Integer arithmetic and order statistics only up to step 3: no floating-point sum, no floating-point atomic.
+constexpr int kPtRows = 512;      // streams per launch when every stream has its own offset (2 KiB of kernel arguments); one launch otherwise
+struct PitchTrackOffsets {
+    float v[kPtRows];
+};
+
+static __global__ __launch_bounds__(256) void pitch_track_kernel(const float* __restrict__ f0, int T, int start, int n, int W, int min_voiced, float slew,
+                                                                 float offset, PitchTrackOffsets offsets, int per_row, int s0, const float* __restrict__ target,
+                                                                 float* __restrict__ ring, long long* __restrict__ count, float* __restrict__ autos,
+                                                                 float* __restrict__ median_out, long long* __restrict__ count_out,
+                                                                 float* __restrict__ shift_out, float* __restrict__ f0s) {
+    extern __shared__ float row[];      // [W]
+    __shared__ PitchSelectLds sel;
+    __shared__ unsigned wave_voiced[4];
+    __shared__ float sh_shift;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long s = s0 + (long)blockIdx.x;
+    const float* p = f0 + s * T;
+    float* rg = ring + s * W;
+    const long long cnt = count[s];
+    const int cursor = (int)(((cnt % W) + W) % W);      // (within the row even for a count the caller corrupted)
+    for (int i = tid; i < W; i += 256) row[i] = rg[i];
+    const float x = tid < n ? p[start + tid] : 0.f;
+    const bool voiced = x > 0.f;
+    const unsigned long long vb = __ballot(voiced);
+    if (lane == 0) wave_voiced[wave] = (unsigned)__popcll(vb);
+    __syncthreads();      // the staged row and the waves' counts
+    int j = __popcll(vb & ((1ull << lane) - 1ull)), nv = 0;
+    for (int w = 0; w < 4; ++w) {
+        if (w < wave) j += (int)wave_voiced[w];
+        nv += (int)wave_voiced[w];
+    }
+    if (voiced && nv - j <= W) {      // one of the last W: slot (cursor + j) % W, distinct over the writers
+        const int slot = (cursor + j) % W;
+        row[slot] = x;
+        rg[slot] = x;
+    }
+    const long long now = cnt + nv;
+    const int fill = now < (long long)W ? (int)now : W;
+    __syncthreads();
+    unsigned live;
+    const unsigned bits = pitch_select(row, W, sel, &live);
+    if (tid == 0) {
+        const float med = __uint_as_float(bits);
+        const float tg = target[s];
+        float wanted = 0.f;
+        if (live && fill >= min_voiced && tg > 0.f) wanted = (float)(12.0 * log2((double)tg / (double)med));
+        float a = autos[s];
+        const float d = __fsub_rn(wanted, a);
+        a = fabsf(d) > slew ? __fadd_rn(a, copysignf(slew, d)) : wanted;
+        const float sh = __fadd_rn(per_row ? offsets.v[blockIdx.x] : offset, a);
+        count[s] = now;
+        autos[s] = a;
+        if (median_out) median_out[s] = med;
+        if (count_out) count_out[s] = now;
+        if (shift_out) shift_out[s] = sh;
+        sh_shift = sh;
+    }
+    if (!f0s) return;
+    __syncthreads();
+    const float sh = sh_shift;
+    float* q = f0s + s * T;
+    for (int i = tid; i < T; i += 256) q[i] = shift_frequency_one(p[i], sh);
+}
+
+int run_pitch_track(tvc_ctx* ctx, hipStream_t s, const float* f0, int S, int T, const PitchTrackState& t, const float* target, float offset,
+                    const float* offsets, float* median_out, int64_t* count_out, float* shift_out, float* f0s) {
+    const size_t lds = (size_t)t.W * sizeof(float);
+    PitchTrackOffsets o{};
+    for (int s0 = 0; s0 < S; s0 += offsets ? kPtRows : S) {
+        const int rows = offsets ? (S - s0 < kPtRows ? S - s0 : kPtRows) : S;
+        if (offsets) std::memcpy(o.v, offsets + s0, (size_t)rows * sizeof(float));
+        hipLaunchKernelGGL(pitch_track_kernel, dim3(rows), dim3(256), lds, s, f0, T, t.start, t.n, t.W, t.min_voiced, t.slew, offset, o, offsets ? 1 : 0, s0,
+                           target, t.ring, reinterpret_cast<long long*>(t.count), t.autos, median_out, reinterpret_cast<long long*>(count_out), shift_out, f0s);
+    }
+    return launch_check(ctx, "pitch_track");
 }
 
 }  // namespace tvc

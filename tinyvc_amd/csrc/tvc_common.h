@@ -375,6 +375,16 @@ struct ConvertIndex {
     static ConvertIndex table(const float* const* blobs, const int64_t* Ns) { return {nullptr, 0, blobs, Ns, true, 0, nullptr}; }
     static ConvertIndex blend(const float* const* blobs, const int64_t* Ns, int M, const float* weights) { return {nullptr, 0, blobs, Ns, true, M, weights}; }
 };
+// A stream set's pitch tracker (frontend.hip pitch_track_kernel): the device state - ring [S][W] fp32, count [S] int64, autos [S] fp32 - and
+// the host values of one block: the new frames are columns [start, start + n) of every row, n <= 256; 1 <= W <= 8192; min_voiced >= 1;
+// slew >= 0 semitones per call (+inf: none)
+struct PitchTrackState {
+    int start = 0, n = 0, W = 0, min_voiced = 1;
+    float slew = 0.f;
+    float* ring = nullptr;
+    int64_t* count = nullptr;
+    float* autos = nullptr;
+};
 struct ConvertCall {
     const float* wav = nullptr;                // [B][L] in, row b zero-padded behind lens[b] samples
     float* wave = nullptr;                     // [B][L] out
@@ -391,6 +401,9 @@ struct ConvertCall {
     // shift_out (device, nullable) receives the applied shifts, one per caller's row
     const float* target_f0 = nullptr;
     float* shift_out = nullptr;
+    // tvc_convert_track_f32 (equal lengths only): the register is the stream's history, not the call's own rows - run_pitch_track takes
+    // run_pitch_match's place
+    const PitchTrackState* track = nullptr;
 };
 // Generator.convert over c.B rows of c.L samples (c.lens is not looked at: a ragged call reaches this through convert_ragged_batches,
 // one batch at a time as ONE row with ctx->rag set, ragged.h)
@@ -414,6 +427,12 @@ struct PitchRow {
 };
 int run_pitch_match(tvc_ctx*, hipStream_t, const float* f0, const std::vector<PitchRow>& rows, const float* target, float* median_out, int* voiced_out,
                     float* shift_out, float* f0s);
+// One block of S streams in lock step, f0 [S][T] (frontend.hip pitch_track_kernel): append the voiced frames among columns [t.start,
+// t.start + t.n) to each stream's ring, take the lower median of the ring, move t.autos toward 12 log2(target / median) by at most t.slew,
+// shift = offset (offsets[s] when given, host values) + autos, f0s = shift_frequency(f0, shift) over all T columns.  median_out, count_out,
+// shift_out and f0s are optional.  One launch (one per 512 streams with per-stream offsets), no workspace.
+int run_pitch_track(tvc_ctx*, hipStream_t, const float* f0, int S, int T, const PitchTrackState& t, const float* target, float offset,
+                    const float* offsets, float* median_out, int64_t* count_out, float* shift_out, float* f0s);
 int run_uniform_to_angle(tvc_ctx*, hipStream_t, float* u, int64_t n);
 // content_bound (optional): an upper bound of |content| (the prepared index's |max| when content came out of the kNN match): ONE float, or
 // with content_bound_stride = 1 one per utterance (a match against one index per utterance);

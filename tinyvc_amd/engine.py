@@ -68,6 +68,7 @@ _CONVERT = {
     ("blend", True): ("tvc_workspace_bytes_ragged_blend", "tvc_convert_ragged_blend_f32"),
     ("auto", False): ("tvc_workspace_bytes_auto", "tvc_convert_auto_f32"),
     ("auto", True): ("tvc_workspace_bytes_ragged_auto", "tvc_convert_ragged_auto_f32"),
+    ("track", False): ("tvc_workspace_bytes_auto", "tvc_convert_track_f32"),      # streams advance in lock step: no ragged form
 }
 _MATCH = {
     "shared": ("tvc_workspace_bytes", "tvc_knn_match_f32"),
@@ -376,7 +377,7 @@ class Engine:
         if form == "table":
             blobs, ns = self._table(prepared, Ns, B)
             return (blobs, ns), (ns,)
-        if form == "auto" and weights is None:
+        if form in ("auto", "track") and weights is None:
             blobs, ns = self._table(prepared, Ns, B)
             return (blobs, ns, 1, None), (ns, 1)
         blobs, ns, M = self._blend_args(prepared, Ns, weights, B)
@@ -428,8 +429,22 @@ class Engine:
         return self._match("blend", src, prepared, Ns, weights, want_indices)
 
     # ---- convert: one driver, the eight public forms forward to it ----
-    def _convert(self, form, wav, prepared, Ns, pitch_shift, noise_angle=None, lengths=None, weights=None, target_f0=None, out=None, shift_out=None):
-        """wav [B, L] converted toward the index (`form`, prepared, Ns, weights: _index_args) -> wave [B, L]; form "auto" -> (wave, shifts [B]).
+    def _track_args(self, track, S, T):
+        """a PitchTrack's share of a call over S streams of T frames, checked on the host: (start, n, W, min_voiced, slew, ring, count, auto)"""
+        if track.n_streams != S:
+            raise ValueError(f"track: a tracker of {track.n_streams} streams for {S} rows")
+        start, n = track.columns(T)
+        W = track.window_frames
+        for t, name, shape, dtype in ((track.ring, "track.ring", (S, W), _F32), (track.count, "track.count", (S,), torch.int64), (track.auto, "track.auto", (S,), _F32)):
+            _check_dev(t, name, self.device)
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():      # the kernel indexes the state by (S, W): never past it
+                raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape}, got {tuple(t.shape)} {t.dtype}")
+        return (start, n, track.window_frames, track.min_voiced, track.slew, _ptr(track.ring), _ptr(track.count), _ptr(track.auto))
+
+    def _convert(self, form, wav, prepared, Ns, pitch_shift, noise_angle=None, lengths=None, weights=None, target_f0=None, out=None, shift_out=None,
+                 track=None):
+        """wav [B, L] converted toward the index (`form`, prepared, Ns, weights: _index_args) -> wave [B, L]; form "auto" / "track" ->
+        (wave, shifts [B]).  "track": "auto" with the register taken from `track` (a PitchTrack: the streams' history), equal lengths only.
         lengths: a ragged batch (row b holds an utterance of lengths[b] samples, a multiple of 480, zero-padded behind it; every utterance
         is converted over its OWN length).  pitch_shift: a float, or one per row for every form but "shared".  Every host check comes
         first, then the noise draw (which advances torch's generator), then device work: a refused call leaves no trace."""
@@ -437,22 +452,27 @@ class Engine:
         wav, B, L = self._rows(wav, ragged)
         lens = (self._lens(lengths, B),) if ragged else ()
         index, sized = self._index_args(form, prepared, Ns, weights, B)
-        if form == "auto":
+        if ragged and form == "track":
+            raise ValueError("track: streams advance in lock step, there is no ragged form")
+        found = form in ("auto", "track")      # the shifts are found on the device: pitch_shift is the offset, the applied shifts come back
+        if found:
             index += (_ptr(self._target_f0(target_f0, B)),)
+        if form == "track":
+            index += self._track_args(track, B, L // spec.HOP)
         shift, shifts = pitch_shifts(pitch_shift, B)
         if form == "shared" and shifts is not None:
             raise ValueError("pitch_shift: one shared index takes one shift (a shift per row takes an index per row)")
         shift_args = (shift,) if form == "shared" else (shift, _floats(shifts))
         a, seed = self._angle(noise_angle, B, L // spec.HOP)
         wave = out if out is not None else torch.empty(B, L, dtype=_F32, device=self.device)
-        if form == "auto":
+        if found:
             sh = shift_out if shift_out is not None else torch.empty(B, dtype=_F32, device=self.device)
             shift_args += (_ptr(sh),)
         query, entry = _CONVERT[form, ragged]
         p, n = self._query_ws(query, B, L, *lens, *sized)
         head, tail = ((_ptr(wav), L, *lens), (B, p, n)) if ragged else ((_ptr(wav),), (B, L, p, n))
         self._ok(getattr(self.lib, entry)(self.ctx, self._stream(), *head, *index, *shift_args, _ptr(a), seed, _ptr(wave), *tail), entry)
-        return (wave, sh) if form == "auto" else wave
+        return (wave, sh) if found else wave
 
     def convert(self, wav, prepared, N, pitch_shift, noise_angle=None, out=None):
         return self._convert("shared", wav, prepared, N, pitch_shift, noise_angle, out=out)
@@ -514,6 +534,27 @@ class Engine:
         self._ok(self.lib.tvc_pitch_match_f32(self.ctx, self._stream(), _ptr(f0), (ctypes.c_int64 * (rows + 1))(*row_start), rows, _ptr(tgt), shift, _floats(shifts),
                                               _ptr(med), _ptr(voiced), _ptr(sh), _ptr(out)), "tvc_pitch_match_f32")
         return med, voiced, sh, out
+
+    def pitch_track(self, f0, track, target_f0, pitch_shift=0.0, want_shifted=False):
+        """One block of a PitchTrack over a caller's f0 [S, 1, T] / [S, T] (tvc_pitch_track_f32): the voiced frames among the tracked columns
+        (track.columns(T)) enter each stream's ring, `track.auto` moves toward 12 log2(target_f0 / the ring's lower median) ->
+        (median [S] fp32, count [S] int64, shift [S] fp32 = pitch_shift (a float or one per stream) + track.auto, f0 shifted by it or None).
+        target_f0: a contiguous fp32 [S] device tensor in Hz.  The state in `track` is updated in place."""
+        f0 = _prep(f0, "f0", self.device)
+        if f0.dim() < 2:
+            raise ValueError("pitch_track: f0 [S, 1, T] or [S, T]")
+        S, T = f0.shape[0], f0.numel() // max(f0.shape[0], 1)
+        targs = self._track_args(track, S, T)
+        shift, shifts = pitch_shifts(pitch_shift, S)
+        tgt = self._target_f0(target_f0, S)
+        med = torch.empty(S, dtype=_F32, device=self.device)
+        cnt = torch.empty(S, dtype=torch.int64, device=self.device)
+        sh = torch.empty(S, dtype=_F32, device=self.device)
+        out = torch.empty_like(f0) if want_shifted else None
+        start, n, W, min_voiced, slew, ring, count, auto = targs
+        self._ok(self.lib.tvc_pitch_track_f32(self.ctx, self._stream(), _ptr(f0), S, T, start, n, _ptr(tgt), shift, _floats(shifts), W, min_voiced, slew,
+                                              ring, count, auto, _ptr(med), _ptr(cnt), _ptr(sh), _ptr(out)), "tvc_pitch_track_f32")
+        return med, cnt, sh, out
 
     # ---- index-sharded match (one prepared index shard per rank; merged by parallel.match_features_sharded) ----
     METRICS = {"cos": 0, "IP": 1, "L2": 2}

@@ -54,7 +54,7 @@ class Generator(HipModule):
 
     @torch.no_grad()
     def convert(self, wf, tgt, pitch_shift, f0_estimation="default", device=None, noise_angle=None, lengths=None, auto_pitch=None,
-                return_shift=False):
+                return_shift=False, track=None):
         """generator.py:26-34: wf [B, L], tgt [1 or B, 768, N] -> converted waveform [B, L'] (L' = L
         padded to a multiple of 480).  `f0_estimation` / `device` are accepted and ignored exactly as
         in the reference.  `noise_angle` [B,961,T] (extension) injects the decoder's noise phases;
@@ -74,7 +74,10 @@ class Generator(HipModule):
         a [B] / [1] device tensor, read when the kernels run), or True = the register riding on each target tensor (`pitch_register`:
         build_index and the entry scripts' loaders attach it).  True is refused (ValueError, before any engine work) for a target without a
         register and for a Blend, which takes an explicit register.  `pitch_shift` then is the offset on top of the automatic shift.
-        `return_shift=True` -> (wave, shifts [B] on the device: the semitones applied to each row)."""
+        `return_shift=True` -> (wave, shifts [B] on the device: the semitones applied to each row).
+        `track` (extension, with auto_pitch): a feature_retrieval.PitchTrack of B streams - the register each row is moved FROM is then the
+        lower median of the stream's history (the tracker's ring on the device, fed by columns [T - lag_frames - new_frames, T - lag_frames)
+        of this call's f0), slew-limited, instead of the median of the call's own rows (tvc_convert_track_f32; equal lengths only)."""
         # 1. classify the target once; malformed targets, registers and shift lists are refused before any engine or device work
         B = wf.shape[0] if wf.dim() == 2 else 1
         auto = auto_pitch is not None and auto_pitch is not False
@@ -86,6 +89,14 @@ class Generator(HipModule):
         elif form == "table":
             check_references(tgt, B)
         regs = resolve_auto_pitch(auto_pitch, tgt, B) if auto else None
+        if track is not None:
+            if not auto:
+                raise ValueError("track needs auto_pitch: the tracker finds the register the automatic shift starts from")
+            if lengths is not None:
+                raise ValueError("track with lengths: streams advance in lock step, there is no ragged form")
+            if track.n_streams != B:
+                raise ValueError(f"track: a tracker of {track.n_streams} streams for a batch of {B}")
+            track.columns(-(-wf.shape[-1] // 480))      # the tracked columns must lie within the (padded) call's frames
         shift, shifts = pitch_shifts(pitch_shift, B)
         # 2. the inputs, on the device
         wf = utils.autopad_waveform(self._input_device(wf))
@@ -108,5 +119,6 @@ class Generator(HipModule):
         pitch = shift if shifts is None else shifts
         if not auto:
             return eng._convert(form, wf, blobs, ns, pitch, noise_angle, lens, w)
-        wave, sh = eng._convert("auto", wf, blobs, ns, pitch, noise_angle, lens, w, target_registers(regs, B, wf.device))
+        wave, sh = eng._convert("auto" if track is None else "track", wf, blobs, ns, pitch, noise_angle, lens, w, target_registers(regs, B, wf.device),
+                                track=track)
         return (wave, sh) if return_shift else wave

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from ...engine import pitch_shifts
-from ..tinyvc.feature_retrieval import target_form
+from ..tinyvc.feature_retrieval import PitchTrack, resolve_auto_pitch, target_form
 from .generator import Generator
 
 
@@ -19,10 +19,22 @@ def _fade_windows(crossfade_size, device):
 class BatchedStreamInfer:
     """`target`: one index for every stream ([1, 768, N]) or one per stream ([S, 768, N], or a list of S [1, 768, N_s] tensors), prepared
     once and cached on those tensors - or a feature_retrieval.Blend of several (its weights are read on the device when a block runs:
-    `blend.weights.copy_(...)` between blocks moves the mix without a new graph capture); `pitch_shift`: a float or one per stream."""
+    `blend.weights.copy_(...)` between blocks moves the mix without a new graph capture); `pitch_shift`: a float or one per stream.
+    `auto_pitch` (convert's: True, a register in Hz, or a [S] / [1] device tensor that is read when a block runs): every block moves each
+    stream's register - the lower median of its last voiced frames, tracked on the device by `pitch_track` (a feature_retrieval.PitchTrack;
+    built in init_buffer when not given: the block's own frames, last_dilay_size before the end of the buffer, are the new ones) - onto
+    the target's; `pitch_shift` is the offset on top and `last_pitch_shift` [S] the shift the latest block applied, on the device."""
 
     def __init__(self, generator: Generator, n_streams=1, target=None, pitch_shift=0., device=None,
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False):
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, auto_pitch=None, pitch_track=None):
+        self.auto_pitch = auto_pitch if auto_pitch is not False else None
+        self.pitch_track = pitch_track
+        self._own_track = pitch_track is None
+        if pitch_track is not None and self.auto_pitch is None:
+            raise ValueError("pitch_track needs auto_pitch: the tracker finds the register the automatic shift starts from")
+        if self.auto_pitch is not None and block_size % 480:
+            raise ValueError(f"auto_pitch: block_size = {block_size} is not a whole number of 480-sample frames")
+        self.last_pitch_shift = None
         self.generator = generator
         self.n_streams = n_streams
         self.target = target
@@ -50,6 +62,10 @@ class BatchedStreamInfer:
         self.sola_buffer = torch.zeros(self.n_streams, self.crossfade_size, device=self.device)
         self._graph = None
         self._calls = 0
+        if self.auto_pitch is not None:
+            if self._own_track:      # the block's own frames: they have their full right context and are the audio about to be played
+                self.pitch_track = PitchTrack(self.n_streams, self.block_size // 480, self.last_dilay_size // 480, device=self.device)
+            self.pitch_track.reset()
 
     def _step(self, blocks, noise_angle):
         # torch.roll + slice assignment of the reference (stream.py:69-70), in place on a fixed buffer, one launch
@@ -59,16 +75,24 @@ class BatchedStreamInfer:
             # generator is graph-safe (its offset advances per replay), so the graph path keeps the reference's torch.rand draw
             from ..tinyvc import Decoder
             noise_angle = Decoder.draw_noise_angle(self.n_streams, self.input_size // 480, self.device)
-        y = self.generator.convert(self.input_wav, self.target, self.pitch_shift, device=self.device,
-                                   f0_estimation=self.f0_estimation, noise_angle=noise_angle)
+        pshift = None
+        if self.auto_pitch is None:
+            y = self.generator.convert(self.input_wav, self.target, self.pitch_shift, device=self.device,
+                                       f0_estimation=self.f0_estimation, noise_angle=noise_angle)
+        else:
+            y, pshift = self.generator.convert(self.input_wav, self.target, self.pitch_shift, device=self.device, f0_estimation=self.f0_estimation,
+                                               noise_angle=noise_angle, auto_pitch=self.auto_pitch, return_shift=True, track=self.pitch_track)
         eng = self.generator.engine(self.device)
         return eng.sola(y, self.sola_buffer, self.fade_in_window, self.block_size,
-                        self.use_phase_vocoder, want_shift=True)
+                        self.use_phase_vocoder, want_shift=True) + (pshift,)
 
     def _graph_key(self):
         """Everything a captured step bakes in as raw device pointers: the packed weights (re-packed - and the old arena
         freed - when a parameter changes), the engine's scratch workspace (re-allocated when another call needs a bigger
-        one), the prepared index riding on `target`, plus the scalars captured by value."""
+        one), the prepared index riding on `target`, plus the scalars captured by value.  With auto_pitch also the
+        tracker's three state tensors (where they live) and its host parameters, and WHERE the target registers live - not their values,
+        nor the ring's or `auto`'s: the kernels read those at replay, so a reset(), registers.copy_(...) or a stream's history advancing
+        keeps the graph."""
         eng = self.generator.engine(self.device)          # re-packs the weights first if a parameter changed
         ws = eng._ws
         form, tgts = target_form(self.target)      # every blob's tensor
@@ -77,8 +101,14 @@ class BatchedStreamInfer:
             wkey = self.target.resolve(self.n_streams, self.device, self.generator._input_device)[2].data_ptr()
         shift, shifts = pitch_shifts(self.pitch_shift, self.n_streams)
         shifts = shift if shifts is None else tuple(shifts)
+        tkey = ()
+        if self.auto_pitch is not None:
+            regs = resolve_auto_pitch(self.auto_pitch, self.target, self.n_streams)
+            tr = self.pitch_track
+            tkey = (regs if isinstance(regs, float) else tuple(r.data_ptr() for r in regs), tr.ring.data_ptr(), tr.count.data_ptr(), tr.auto.data_ptr(),
+                    tr.params())
         return (eng.weights_key, ws.data_ptr() if ws is not None else 0, ws.numel() if ws is not None else 0,
-                tuple((id(t), t._version, t.data_ptr()) for t in tgts), wkey, shifts, bool(self.use_phase_vocoder))
+                tuple((id(t), t._version, t.data_ptr()) for t in tgts), wkey, shifts, bool(self.use_phase_vocoder)) + tkey
 
     @torch.no_grad()
     def audio_callback(self, blocks, noise_angle=None):
@@ -86,8 +116,7 @@ class BatchedStreamInfer:
         blocks = blocks.to(self.device)
         self._calls += 1
         if not self.use_graph or self._calls <= 2:
-            out, shift = self._step(blocks, noise_angle)
-            self.last_shift = shift
+            out, self.last_shift, self.last_pitch_shift = self._step(blocks, noise_angle)
             return out
         key = self._graph_key()
         if self._graph is not None and key != self._graph[0]:
@@ -110,15 +139,14 @@ class BatchedStreamInfer:
             graphs[inject] = (g, res)
             if self._graph_key() != key:      # the capture itself grew the workspace: what it recorded is already stale
                 self._graph = None
-                out, shift = self._step(blocks, noise_angle)
-                self.last_shift = shift
+                out, self.last_shift, self.last_pitch_shift = self._step(blocks, noise_angle)
                 return out
         self._g_in.copy_(blocks)
         if inject:
             self._g_angle.copy_(noise_angle)
-        g, (g_out, g_shift) = graphs[inject]
+        g, (g_out, g_shift, g_pshift) = graphs[inject]
         g.replay()
-        self.last_shift = g_shift
+        self.last_shift, self.last_pitch_shift = g_shift, g_pshift
         return g_out.clone()
 
 
@@ -126,11 +154,11 @@ class StreamInfer(BatchedStreamInfer):
     """Single stream with the reference's constructor and 1-D buffers (stream.py:31-57)."""
 
     def __init__(self, generator: Generator, target=None, pitch_shift=0., device=torch.device("cpu"),
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False):
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, auto_pitch=None, pitch_track=None):
         dev = torch.device(device)
         if dev.type != "cuda":
             dev = generator._module_device()     # the reference defaults to CPU; there is no CPU path here
-        super().__init__(generator, 1, target, pitch_shift, dev, block_size, extra_size, use_phase_vocoder, f0_estimation, use_graph)
+        super().__init__(generator, 1, target, pitch_shift, dev, block_size, extra_size, use_phase_vocoder, f0_estimation, use_graph, auto_pitch, pitch_track)
 
     @torch.no_grad()
     def audio_callback(self, block, noise_angle=None):

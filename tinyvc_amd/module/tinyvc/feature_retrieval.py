@@ -213,6 +213,66 @@ def target_registers(resolved, B, device):
     return (t.expand(B) if t.numel() == 1 else t).contiguous()
 
 
+class PitchTrack:
+    """The pitch tracker of a set of streams that advance in lock step (tvc_pitch_track_f32 / tvc_convert_track_f32): the register a
+    stream's automatic shift aims FROM is the lower median of its last `window_frames` voiced f0 values, kept on the device.
+      ring [S, W] fp32   the last W voiced f0 values of each stream (a ring; unwritten slots are 0.0)
+      count [S] int64    voiced frames appended since the last reset (write cursor count % W, fill min(count, W))
+      auto [S] fp32      the automatic part of the shift applied in the latest block
+    Per block the kernel appends the voiced frames among the `new_frames` columns that end `lag_frames` before the end of f0, and moves
+    `auto` toward 12 log2(target / median) by at most `slew` semitones (per block; inf = at once).  Before `min_voiced` values are in the
+    ring the automatic shift is 0.  Every argument is checked before anything is allocated (ValueError)."""
+
+    def __init__(self, n_streams, new_frames, lag_frames=0, window_frames=1500, min_voiced=25, slew=float("inf"), device=None):
+        def whole(x, name, lo, hi=None):
+            if isinstance(x, bool) or not isinstance(x, int) or x < lo or (hi is not None and x > hi):
+                raise ValueError(f"PitchTrack: {name} must be an integer {'>= ' + str(lo) if hi is None else 'in ' + str(lo) + ' ... ' + str(hi)}, got {x!r}")
+            return x
+        self.n_streams = whole(n_streams, "n_streams", 1)
+        self.new_frames = whole(new_frames, "new_frames", 0, spec.PITCH_TRACK_MAX_NEW)
+        self.lag_frames = whole(lag_frames, "lag_frames", 0)
+        self.window_frames = whole(window_frames, "window_frames", 1, spec.PITCH_TRACK_MAX_WINDOW)
+        self.min_voiced = whole(min_voiced, "min_voiced", 1, 0x7fffffff)
+        if isinstance(slew, bool) or not isinstance(slew, (int, float)) or not float(slew) >= 0.0:
+            raise ValueError(f"PitchTrack: slew must be >= 0 semitones per block (inf: no limit), got {slew!r}")
+        self.slew = float(slew)
+        device = torch.device(device if device is not None else "cuda")
+        if device.type == "cuda" and not torch.cuda.is_available():
+            raise ValueError("PitchTrack: the state lives on the GPU and there is none here (device='cpu' builds a tracker no engine will take)")
+        self.device = device
+        self.ring = torch.zeros(self.n_streams, self.window_frames, dtype=torch.float32, device=device)
+        self.count = torch.zeros(self.n_streams, dtype=torch.int64, device=device)
+        self.auto = torch.zeros(self.n_streams, dtype=torch.float32, device=device)
+
+    def columns(self, T):
+        """the tracked columns [start, start + new_frames) of an f0 of T frames; ValueError when they do not fit"""
+        start = T - self.lag_frames - self.new_frames
+        if start < 0:
+            raise ValueError(f"track: {self.new_frames} new frames ending {self.lag_frames} before the end do not fit T = {T} frames")
+        return start, self.new_frames
+
+    def params(self):
+        """the host values a captured block bakes in"""
+        return (self.new_frames, self.lag_frames, self.window_frames, self.min_voiced, self.slew)
+
+    def reset(self, streams=None):
+        """Forget the history of every stream, or of the listed ones: in-place ops on the state tensors, so it works between replays of a
+        captured graph (which reads them when it runs)."""
+        if streams is None:
+            self.ring.zero_()
+            self.count.zero_()
+            self.auto.zero_()
+            return
+        idx = torch.as_tensor(list(streams), dtype=torch.int64, device=self.device)
+        self.ring.index_fill_(0, idx, 0.0)
+        self.count.index_fill_(0, idx, 0)
+        self.auto.index_fill_(0, idx, 0.0)
+
+    def register(self):
+        """the streams' registers as they stand: PitchRegister(median_hz [S], voiced [S] = the fill)"""
+        return pitch_register(self.ring)
+
+
 def add_auto_pitch_argument(parser):
     """`--auto-pitch` for infer.py's parser: shift every file so that its median f0 lands on the target's (-p stays, as the offset)."""
     parser.add_argument("--auto-pitch", action="store_true",

@@ -27,6 +27,8 @@ NUM_HARMONICS = 14             # oscillator emits NUM_HARMONICS + 1 sinusoids
 FILTER_CHANNELS = (384, 192, 96, 48, 24)
 FILTER_FACTORS = (2, 3, 4, 4, 5)
 BLEND_MAX = 4                  # terms of a weighted blend of speaker indices (TVC_BLEND_MAX)
+PITCH_TRACK_MAX_WINDOW = 8192  # frames in a stream's pitch ring (TVC_PITCH_TRACK_MAX_WINDOW): a row of 32 KiB fits LDS
+PITCH_TRACK_MAX_NEW = 256      # new frames per block: one per thread of the tracker's workgroup
 
 
 def _conv(d, name, cout, cin, k, groups=1):
