@@ -315,29 +315,50 @@ __global__ __launch_bounds__(FS2T<NWV_>::NTHR) __attribute__((amdgpu_waves_per_e
             asm volatile("" : "+v"(el));
             const int e31 = el & 31, eh = el >> 5;
             const float ix = norm_from_amax(XPRE ? presplit_bound(a.pre_w, a.pre_b, a.amax_x, cb) : sload_f32(a.amax_x + cb)).inv, ic_ = norm_from_amax(sload_f32(a.amax_c + cb)).inv;
+            // (1) the FiLM combine of ALL m-tiles first: it reads LDS tables only, and it frees the 96 sc / sh registers for (2)
 #pragma unroll
             for (int i = 0; i < WM; ++i) {
-            const int row0 = (cmb * MTB + wm * WM + i) * 32;
-            const float kc = Tb[FilmU::TAB_SCALE * 384 + row0] * ix, ks = Tb[FilmU::TAB_SSC * 384 + row0] * ic_, kh = Tb[FilmU::TAB_SSH * 384 + row0] * ic_;      // one m-tile: one scale each
+                const int row0 = (cmb * MTB + wm * WM + i) * 32;
+                const float kc = Tb[FilmU::TAB_SCALE * 384 + row0] * ix, ks = Tb[FilmU::TAB_SSC * 384 + row0] * ic_, kh = Tb[FilmU::TAB_SSH * 384 + row0] * ic_;      // one m-tile: one scale each
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int rr = row0 + 8 * g + 4 * eh;
-                const float4 b0 = *reinterpret_cast<const float4*>(Tb + FilmU::TAB_BIAS * 384 + rr);
-                const float4 b1 = *reinterpret_cast<const float4*>(Tb + FilmU::TAB_BSC * 384 + rr);
-                const float4 b2 = *reinterpret_cast<const float4*>(Tb + FilmU::TAB_BSH * 384 + rr);
-                const float bm[4] = {b0.x, b0.y, b0.z, b0.w}, bs[4] = {b1.x, b1.y, b1.z, b1.w}, bh[4] = {b2.x, b2.y, b2.z, b2.w};
+                for (int g = 0; g < 4; ++g) {
+                    const int rr = row0 + 8 * g + 4 * eh;
+                    const float4 b0 = *reinterpret_cast<const float4*>(Tb + FilmU::TAB_BIAS * 384 + rr);
+                    const float4 b1 = *reinterpret_cast<const float4*>(Tb + FilmU::TAB_BSC * 384 + rr);
+                    const float4 b2 = *reinterpret_cast<const float4*>(Tb + FilmU::TAB_BSH * 384 + rr);
+                    const float bm[4] = {b0.x, b0.y, b0.z, b0.w}, bs[4] = {b1.x, b1.y, b1.z, b1.w}, bh[4] = {b2.x, b2.y, b2.z, b2.w};
 #pragma unroll
-                for (int q = 0; q < 4; ++q)
+                    for (int q = 0; q < 4; ++q)
 #pragma unroll
-                    for (int j = 0; j < WN; ++j) {
-                        const int r = 4 * g + q;
-                        const float h = fmaf(hi[i][j][r], kc, bm[q]), s = fmaf(sc[i][j][r], ks, bs[q]), t = fmaf(sh[i][j][r], kh, bh[q]);
-                        hi[i][j][r] = __fadd_rn(__fmul_rn(h, s), t);         // h * scale + shift, rounded like the reference's two tensor ops
-                        sc[i][j][r] = 0.f;
-                        sh[i][j][r] = 0.f;
-                    }
+                        for (int j = 0; j < WN; ++j) {
+                            const int r = 4 * g + q;
+                            const float h = fmaf(hi[i][j][r], kc, bm[q]), s = fmaf(sc[i][j][r], ks, bs[q]), t = fmaf(sh[i][j][r], kh, bh[q]);
+                            hi[i][j][r] = __fadd_rn(__fmul_rn(h, s), t);         // h * scale + shift, rounded like the reference's two tensor ops
+                            sc[i][j][r] = 0.f;
+                            sh[i][j][r] = 0.f;
+                        }
+                    // (four rows' results pinned behind their table reads: with all three m-tiles in one block the scheduler otherwise hoists
+                    // the table values of every group above the arithmetic - DESIGN.md section 4, round-6 findings (a))
+#pragma unroll
+                    for (int j = 0; j < WN; ++j) asm volatile("" : "+v"(hi[i][j]) : : "memory");
+                }
             }
-            float* yb = RAG ? a.y + (long)row0 * rs + coff : a.y + ((long)cb * C + row0) * rs;                // uniform; a lane adds its 32-bit offset
+            // (2) the residual of the whole 96-row column as ONE batch of loads (48 values per lane, 96 for the interpolated half) into
+            // the freed registers, then the adds, then the stores: one global round trip per tile end.  Taken m-tile by m-tile - load,
+            // wait, add, store - it was three: the stores to y may alias the next m-tile's loads from res as far as the compiler can
+            // tell, so it hoisted none of them, and each wait also waits for the staging loads issue_load() has just requested (vmcnt
+            // retires in order).  res and y are never the same buffer (decoder.hip conv_film_half): read and written through
+            // __restrict__ locals, and every load stands in front of every store.  A column's index math (and its lerp_coord) is shared
+            // by all its rows - one uniform base, the rows in the lanes' 32-bit offsets: a base per row cost 77-91 scalar registers spilled
+            // into vector lanes -; the per-element arithmetic and its order are unchanged.
+            // Not built, because no instantiation has the registers (250-256 of 256 inside the step): requesting rows a slab EARLIER, in
+            // front of the tile's last issue_load() - one m-tile's 16 rows, direct case: 1 ... 34 registers spilled in all six kernels -,
+            // and requesting them chunk by chunk between the m-tiles' combines as sc / sh come free (73 ... 138 spilled: the 16-register
+            // tuples do not line up).  A chunk that travels early would save nothing anyway while the others take the round trip here.
+            const float* __restrict__ resp = a.res;
+            float* __restrict__ yp = a.y;
+            const int mrow = (cmb * MTB + wm * WM) * 32;
+            float* yb = RAG ? yp + (long)mrow * rs + coff : yp + ((long)cb * C + mrow) * rs;                // uniform; a lane adds its 32-bit offset
 #pragma unroll
             for (int j = 0; j < WN; ++j) {
                 const int t = ct0 + (wn * WN + j) * 32 + e31;
@@ -346,38 +367,52 @@ __global__ __launch_bounds__(FS2T<NWV_>::NTHR) __attribute__((amdgpu_waves_per_e
                 const unsigned off = 4u * (unsigned)(4 * eh * rs + tc);
                 if (a.res_lin > 0) {       // the residual is F.interpolate of the low-rate tensor, evaluated here
                     const Lerp lc = lerp_coord(tc, a.res_scale, RAG ? len / rf : a.res_lin);
-                    const float* rb = RAG ? a.res + (long)row0 * a.res_lin + coff / rf : a.res + ((long)cb * C + row0) * a.res_lin;
+                    const float* rb = RAG ? resp + (long)mrow * a.res_lin + coff / rf : resp + ((long)cb * C + mrow) * a.res_lin;
                     const unsigned o0 = 4u * (unsigned)(4 * eh * a.res_lin + lc.i0), o1 = 4u * (unsigned)(4 * eh * a.res_lin + lc.i1);
+                    f32x16 x0[WM], x1[WM];
 #pragma unroll
-                    for (int h8 = 0; h8 < 2; ++h8) {
-                        float x0[8], x1[8];
+                    for (int i = 0; i < WM; ++i)
 #pragma unroll
-                        for (int r = 0; r < 8; ++r) {
-                            const float* rr = rb + (long)(16 * h8 + (r & 3) + 8 * (r >> 2)) * a.res_lin;
-                            x0[r] = ldg_so(rr, o0);
-                            x1[r] = ldg_so(rr, o1);
+                        for (int r = 0; r < 16; ++r) {
+                            const unsigned ro = (unsigned)(32 * i + (r & 3) + 8 * (r >> 2)) * 4u * (unsigned)a.res_lin;
+                            x0[i][r] = ldg_so(rb, o0 + ro);
+                            x1[i][r] = ldg_so(rb, o1 + ro);
                         }
+                    // (the batch pinned: left alone, the scheduler pairs every load with its add - a wait per row)
 #pragma unroll
-                        for (int r = 0; r < 8; ++r) hi[i][j][8 * h8 + r] = __fadd_rn(hi[i][j][8 * h8 + r], lerp_eval(lc, x0[r], x1[r]));
-                    }
+                    for (int i = 0; i < WM; ++i) asm volatile("" : "+v"(x0[i]), "+v"(x1[i]) : : "memory");
+#pragma unroll
+                    for (int i = 0; i < WM; ++i)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) hi[i][j][r] = __fadd_rn(hi[i][j][r], lerp_eval(lc, x0[i][r], x1[i][r]));
                 } else {
-                    const float* rb = RAG ? a.res + (long)row0 * rs + coff : a.res + ((long)cb * C + row0) * rs;
-                    float rv[16];
+                    const float* rb = RAG ? resp + (long)mrow * rs + coff : resp + ((long)cb * C + mrow) * rs;
+                    f32x16 rv[WM];
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) rv[r] = ldg_so(rb + (long)((r & 3) + 8 * (r >> 2)) * rs, off);
+                    for (int i = 0; i < WM; ++i)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) hi[i][j][r] = __fadd_rn(hi[i][j][r], rv[r]);
+                        for (int r = 0; r < 16; ++r) rv[i][r] = ldg_so(rb, off + (unsigned)(32 * i + (r & 3) + 8 * (r >> 2)) * 4u * (unsigned)rs);
+#pragma unroll
+                    for (int i = 0; i < WM; ++i) asm volatile("" : "+v"(rv[i]) : : "memory");
+#pragma unroll
+                    for (int i = 0; i < WM; ++i)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) hi[i][j][r] = __fadd_rn(hi[i][j][r], rv[i][r]);
+                }
+                if (live) {
+#pragma unroll
+                    for (int i = 0; i < WM; ++i)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const float e = hi[i][j][r];
+                            stg_so(yb, off + (unsigned)(32 * i + (r & 3) + 8 * (r >> 2)) * 4u * (unsigned)rs, e);
+                            mx_run = fmaxf(mx_run, fabsf(e));
+                        }
                 }
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float e = hi[i][j][r];
-                    if (live) {
-                        stg_so(yb + (long)((r & 3) + 8 * (r >> 2)) * rs, off, e);
-                        mx_run = fmaxf(mx_run, fabsf(e));
-                    }
-                    hi[i][j][r] = 0.f;
-                }
-            }
+                for (int i = 0; i < WM; ++i)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) hi[i][j][r] = 0.f;
             }
             const int done_b = cb;
             ++cv;
