@@ -466,6 +466,36 @@ int tvc_sola_f32(tvc_ctx* ctx, void* stream, const float* y, float* sola_buf, co
  * than 32 768 samples is shifted in 32 768-sample tiles inside the same launch (capturable like every other call). */
 int tvc_stream_push_f32(tvc_ctx* ctx, void* stream, float* buf, const float* blocks, int S, int64_t n, int block);
 
+/* The streaming door (extension): tvc_resample_f32 block by block, for S streams whose clients run at another rate than the model's
+ * 24 kHz, fused with the int16 conversions and gain above.  Each stream carries `hist` fp32 input samples of filter history on the
+ * device (state [S][hist], zeros at the start of a stream; zero a row to restart that stream).
+ *
+ * Definition: for every prefix of a stream, the blocks emitted so far are the first samples of tvc_resample_f32 applied to
+ * (G * orig zeros ++ the prefix), bit for bit - the same filter table, the same ascending fmaf chain per output.
+ *
+ * Geometry (host only: no context, no device; g = gcd(in_freq, out_freq), orig = in_freq / g, new = out_freq / g, width and
+ * taps = 2 * width + orig as tvc_resample_f32's table has them):
+ *   a block is n_in input samples with n_in % orig == 0 and gives exactly n_out = n_in / orig * new outputs;
+ *   G = ceil(width / orig) whole output groups of look-ahead;  hist = G * orig + width;  delay = G * new output samples of latency,
+ *   the least for which every emitted output has all its `taps` inputs (48000 -> 24000: hist 27, delay 7; 44100 -> 24000: orig 147,
+ *   new 80, G 1, hist 159, delay 80 = 3.3 ms - one whole 147:80 group, and the same again on the way back out).
+ * tvc_stream_resample_geometry returns TVC_ERR_ARG for a non-positive rate or n_in, for n_in % orig != 0, and for a block whose
+ * hist + n_in floats exceed TVC_STREAM_RESAMPLE_LDS_FLOATS: the kernel stages a stream's history and block in LDS, one workgroup per
+ * stream, and 64 KiB is what a workgroup gets.  Equal rates are legal: hist = delay = 0, n_out = n_in.
+ *
+ * tvc_stream_resample: in [S][n_in] (int16 when in_is_pcm16, else fp32) -> out [S][n_out] (int16 when out_is_pcm16, else fp32); state is
+ * read and advanced in place (NULL allowed at equal rates).  One side at most is int16; gain_db is that side's gain (tvc_pcm16_to_f32's
+ * arithmetic before the filter, tvc_f32_to_pcm16's after it - wrap-around included) and must be 0 between fp32 and fp32.  Equal rates
+ * run the plain conversions (a device copy for fp32 to fp32).  The rates, n_in and the gain are kernel arguments, baked into a stream
+ * capture; the samples and the state are read when the kernel runs, so a captured block replays as the streams advance or restart.
+ * No workspace.  The first use of a rate pair by a context builds its filter table synchronously: tvc_stream_resample_prepare does that
+ * ahead of time, and tvc_stream_resample refuses with TVC_ERR_STATE inside a capture when it has not been done. */
+#define TVC_STREAM_RESAMPLE_LDS_FLOATS 16384
+int tvc_stream_resample_geometry(int in_freq, int out_freq, int64_t n_in, int64_t* n_out, int* hist, int* delay);
+int tvc_stream_resample_prepare(tvc_ctx* ctx, int in_freq, int out_freq);
+int tvc_stream_resample(tvc_ctx* ctx, void* stream, const void* in, int in_is_pcm16, void* out, int out_is_pcm16, float* state, int S,
+                        int64_t n_in, int in_freq, int out_freq, float gain_db);
+
 /* measurement ----------------------------------------------------------------------------- */
 /* on = 1: every stage (and every FilterNet block) is bracketed by a hipEvent pair on the launch stream (19 pairs per
  * convert, ~0.1 ms of a 8.4 ms step); on = 2: only the `filter_net` region (the roofline's kernel group); on = 0: off.

@@ -18,11 +18,18 @@ comes from the index's `.f0.pt` sidecar (extract_index.py) or from the `-t` reco
 seconds of voiced f0, tracked on the device - is moved onto the target's, no faster than `--auto-pitch-slew` semitones per second and only
 once `--auto-pitch-warmup` seconds of voiced speech have been heard; `-p` is added on top.  No calibration recording, no host read per block.
 
+`--resample` (extension) runs the audio device - or the file - at `-sr` for real: `-c` counts samples at that rate, every block is resampled
+to the model's 24 kHz on the way in and back to `-sr` on the way out by a stateful resampler on the device (StreamDoor: the filter history
+is carried per stream, so there is no transient at block edges), and `-ig` / `-og` are applied there.  The model block is c * 24000 / sr and
+must be an integer made of whole resampling groups (44.1 kHz: multiples of 147 samples, e.g. -c 3528).  Without the flag `-sr` only opens the
+device at that rate and the samples are taken for 24 kHz, as in the reference.
+
 `--streams S` feeds S copies of the input as S concurrent streams through one BatchedStreamInfer
 (one batched convert + one SOLA launch per block) and reports the p50 / p95 block latency against the
 real-time budget (chunk / 24 kHz = 80 ms for the default 1920-sample chunk).
 """
 import argparse
+import math
 import sys
 import time
 
@@ -31,7 +38,8 @@ import torch
 
 from tinyvc_amd import audio_io
 from infer import load_generator, load_target
-from tinyvc_amd.module.infer import BatchedStreamInfer
+from tinyvc_amd.engine import stream_resample_geometry
+from tinyvc_amd.module.infer import BatchedStreamInfer, StreamDoor
 from tinyvc_amd.module.tinyvc.feature_retrieval import PitchTrack, add_blend_argument, pitch_register, semitones_between
 
 FRAMES_PER_SECOND = 50      # 24 kHz / 480 samples
@@ -63,6 +71,9 @@ def build_parser():
     p.add_argument("-ig", "--input-gain", default=0, type=float)
     p.add_argument("-og", "--output-gain", default=0, type=float)
     p.add_argument("-f0-est", "--f0-estimation", default="default", choices=["default", "fcpe", "dio", "harvest"])
+    p.add_argument("--resample", action="store_true",
+                   help="run the device (or file) at -sr and resample every block to the model's 24 kHz and back on the GPU; -c counts samples at -sr, "
+                        "-ig / -og are applied by the same kernels")
     # file-driven operation (no audio devices on a GPU node)
     p.add_argument("--input-wav", default=None, help="read the microphone signal from this WAV instead of a device")
     p.add_argument("--output-wav", default=None, help="write the converted stream here")
@@ -80,31 +91,54 @@ def int16_blocks_from_wav(path, sample_rate, chunk, engine):
     return [pcm[i * chunk:(i + 1) * chunk] for i in range(n)]
 
 
-def check_auto_pitch(args):
-    """--auto-pitch against the other flags, before anything is loaded: sys.exit with a message, or the PitchTrack keywords (None without
+def check_resample(args):
+    """--resample against -sr and -c, before anything is loaded: sys.exit with a message, or the model's block length at 24 kHz (None without
     the flag)"""
+    if not args.resample:
+        return None
+    sr, c = args.sample_rate, args.chunk
+    if sr <= 0 or c <= 0:
+        sys.exit("infer_streaming.py: --resample: -sr and -c must be positive")
+    orig = sr // math.gcd(sr, 24000)
+    if c % orig:
+        near = " or ".join(str(n) for n in (c // orig * orig, (c // orig + 1) * orig) if n > 0)
+        sys.exit(f"infer_streaming.py: --resample: -c {c} at -sr {sr} is not a multiple of {orig}, the samples of one resampling group "
+                 f"({sr} -> 24000 Hz); the nearest sizes that work: {near}")
+    try:
+        block, _, _ = stream_resample_geometry(sr, 24000, c)
+        stream_resample_geometry(24000, sr, block)
+    except ValueError as e:
+        sys.exit(f"infer_streaming.py: --resample: {e}")
+    return block
+
+
+def check_auto_pitch(args, block=None):
+    """--auto-pitch against the other flags, before anything is loaded: sys.exit with a message, or the PitchTrack keywords (None without
+    the flag).  `block`: the model's block length when it is not -c (--resample)"""
     if not args.auto_pitch:
         return None
+    chunk = args.chunk if block is None else block
     if args.auto_pitch_from is not None:
         sys.exit("infer_streaming.py: --auto-pitch with --auto-pitch-from: the live tracker needs no calibration recording; pick one")
     if args.blend is not None:
         sys.exit("infer_streaming.py: --auto-pitch with --blend: a blend has no register of its own; use -p")
-    if args.chunk <= 0 or args.chunk % 480:
+    if chunk <= 0 or chunk % 480:
         sys.exit(f"infer_streaming.py: --auto-pitch: -c {args.chunk} is not a whole number of 480-sample frames")
-    if args.chunk // 480 > 256:
+    if chunk // 480 > 256:
         sys.exit(f"infer_streaming.py: --auto-pitch: -c {args.chunk} is more than 256 frames per block")
     window = int(round(args.auto_pitch_window * FRAMES_PER_SECOND))
     if not 1 <= window <= 8192:
         sys.exit("infer_streaming.py: --auto-pitch-window: between 0.02 and 163.84 seconds")
     if not args.auto_pitch_warmup >= 0 or not args.auto_pitch_slew >= 0:
         sys.exit("infer_streaming.py: --auto-pitch-warmup and --auto-pitch-slew must be >= 0")
-    slew = args.auto_pitch_slew * args.chunk / 24000 if args.auto_pitch_slew > 0 else float("inf")      # semitones per block
-    return dict(new_frames=args.chunk // 480, window_frames=window, min_voiced=max(1, int(round(args.auto_pitch_warmup * FRAMES_PER_SECOND))), slew=slew)
+    slew = args.auto_pitch_slew * chunk / 24000 if args.auto_pitch_slew > 0 else float("inf")      # semitones per block
+    return dict(new_frames=chunk // 480, window_frames=window, min_voiced=max(1, int(round(args.auto_pitch_warmup * FRAMES_PER_SECOND))), slew=slew)
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    track_kw = check_auto_pitch(args)
+    block = check_resample(args)
+    track_kw = check_auto_pitch(args, block)
     device = torch.device(args.device)
     if device.type != "cuda":
         sys.exit("infer_streaming.py: this build runs on an AMD GPU only; pass -d cuda")
@@ -131,17 +165,23 @@ def main(argv=None):
         if getattr(tgt, "pitch_register", None) is None:
             sys.exit(f"infer_streaming.py: --auto-pitch: no pitch register beside {args.index} (extract_index.py writes <index>.f0.pt)")
         track = PitchTrack(S, lag_frames=3840 // 480, device=device, **track_kw)      # the frames of the block about to be played (last_dilay_size)
-    stream = BatchedStreamInfer(gen, n_streams=S, pitch_shift=pitch_shift, block_size=args.chunk, device=device,
-                                extra_size=args.extra, f0_estimation=args.f0_estimation, auto_pitch=True if track is not None else None, pitch_track=track)
+    # the int16 conversions and gains belong to the door; without --resample it stands between equal rates - the samples are taken for
+    # 24 kHz whatever -sr says, as in the reference - and is those conversions alone
+    rate = args.sample_rate if block is not None else 24000
+    door = StreamDoor(S, rate, rate, block if block is not None else args.chunk, args.input_gain, args.output_gain, device=device)
+    if block is not None:
+        print(f"Resampling {rate} Hz <-> 24000 Hz on the device: {args.chunk}-sample blocks are {block} at the model's rate; "
+              f"the two filters add {door.latency_seconds * 1e3:.2f} ms of latency")
+    stream = BatchedStreamInfer(gen, n_streams=S, pitch_shift=pitch_shift, block_size=door.block_size, device=device, extra_size=args.extra,
+                                f0_estimation=args.f0_estimation, door=door, auto_pitch=True if track is not None else None, pitch_track=track)
     stream.target = tgt
     stream.init_buffer()
 
     def process(chunk_i16):
-        """One pass of the reference's loop body (infer_streaming.py:84-94) for S streams."""
-        eng = gen.engine(device)
-        x = eng.pcm16_to_f32(torch.from_numpy(np.ascontiguousarray(chunk_i16)).to(device), args.input_gain)      # / 32768, gain: on the GPU
-        y = stream.audio_callback(x.expand(S, -1) if x.dim() == 1 else x)
-        return eng.f32_to_pcm16(y, args.output_gain).cpu().numpy()                                                # gain, * 32768, int16: on the GPU
+        """One pass of the reference's loop body (infer_streaming.py:84-94) for S streams: / 32768 and gain, the block, gain and * 32768 to
+        int16 - with --resample also both resamplers -, all on the GPU"""
+        pcm = torch.from_numpy(np.ascontiguousarray(chunk_i16)).to(device)
+        return stream.audio_callback_pcm(pcm.expand(S, -1) if pcm.dim() == 1 else pcm).cpu().numpy()
 
     if args.input_wav is None:
         try:

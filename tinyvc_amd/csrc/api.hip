@@ -976,4 +976,28 @@ int tvc_stream_push_f32(tvc_ctx* ctx, void* stream, float* buf, const float* blo
     return run_stream_push(ctx, (hipStream_t)stream, buf, blocks, S, (int)n, block);
 }
 
+int tvc_stream_resample_geometry(int in_freq, int out_freq, int64_t n_in, int64_t* n_out, int* hist, int* delay) {
+    if (!n_out || !hist || !delay) return TVC_ERR_ARG;
+    return stream_resample_geometry(in_freq, out_freq, n_in, n_out, hist, delay);
+}
+
+int tvc_stream_resample_prepare(tvc_ctx* ctx, int in_freq, int out_freq) {
+    if (!ctx) return TVC_ERR_ARG;
+    if (in_freq <= 0 || out_freq <= 0) return fail(ctx, TVC_ERR_ARG, "tvc_stream_resample_prepare: rates must be positive");
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    return stream_resample_prepare(ctx, in_freq, out_freq);
+}
+
+int tvc_stream_resample(tvc_ctx* ctx, void* stream, const void* in, int in_is_pcm16, void* out, int out_is_pcm16, float* state, int S, int64_t n_in,
+                        int in_freq, int out_freq, float gain_db) {
+    if (!ctx) return TVC_ERR_ARG;
+    if (!in || !out || S <= 0 || n_in <= 0 || in_freq <= 0 || out_freq <= 0 || (!state && in_freq != out_freq))
+        return fail(ctx, TVC_ERR_ARG, "tvc_stream_resample: bad argument (state may be NULL only at equal rates)");
+    if (in_is_pcm16 && out_is_pcm16) return fail(ctx, TVC_ERR_ARG, "tvc_stream_resample: one side is fp32 (a door stands between int16 and the model)");
+    if (!in_is_pcm16 && !out_is_pcm16 && gain_db != 0.f)
+        return fail(ctx, TVC_ERR_ARG, "tvc_stream_resample: gain_db belongs to the int16 conversion; fp32 to fp32 takes 0");
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    return run_stream_resample(ctx, (hipStream_t)stream, in, in_is_pcm16 != 0, out, out_is_pcm16 != 0, state, S, n_in, in_freq, out_freq, gain_db);
+}
+
 }  // extern "C"

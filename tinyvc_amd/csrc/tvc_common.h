@@ -466,6 +466,10 @@ int run_sola(tvc_ctx*, hipStream_t, const float* y, float* sola_buf, const float
 int run_stream_push(tvc_ctx* ctx, hipStream_t s, float* buf, const float* blocks, int S, int n, int m);
 int64_t resample_out_len(int64_t n, int orig_freq, int new_freq);
 int run_resample(tvc_ctx*, hipStream_t, const float* x, float* y, int rows, int64_t n, int orig_freq, int new_freq);
+int stream_resample_geometry(int in_freq, int out_freq, int64_t n_in, int64_t* n_out, int* hist, int* delay);
+int stream_resample_prepare(tvc_ctx*, int in_freq, int out_freq);
+int run_stream_resample(tvc_ctx*, hipStream_t, const void* in, bool in16, void* out, bool out16, float* state, int S, int64_t n_in, int in_freq,
+                        int out_freq, float gain_db);
 int run_pcm16_to_f32(tvc_ctx*, hipStream_t, const int16_t* pcm, float* y, int64_t n, float gain_db);
 int run_f32_to_pcm16(tvc_ctx*, hipStream_t, const float* x, int16_t* pcm, int64_t n, float gain_db);
 void frontdoor_release(tvc_ctx*);

@@ -77,6 +77,26 @@ _MATCH = {
 }
 
 
+STREAM_RESAMPLE_LDS_FLOATS = 16384      # TVC_STREAM_RESAMPLE_LDS_FLOATS of tinyvc_hip.h: a stream's history + block, staged in 64 KiB of LDS
+
+
+def stream_resample_geometry(in_freq, out_freq, n_in, lib=None):
+    """tvc_stream_resample_geometry (no context, no device) -> (n_out, hist, delay) for blocks of n_in samples at in_freq, resampled to out_freq.
+    ValueError, with the reason, for what the library refuses."""
+    in_freq, out_freq, n_in = int(in_freq), int(out_freq), int(n_in)
+    lib = lib if lib is not None else _lib.load_library()
+    n_out, hist, delay = ctypes.c_int64(), ctypes.c_int(), ctypes.c_int()
+    if lib.tvc_stream_resample_geometry(in_freq, out_freq, n_in, ctypes.byref(n_out), ctypes.byref(hist), ctypes.byref(delay)) != 0:
+        if in_freq <= 0 or out_freq <= 0 or n_in <= 0:
+            raise ValueError(f"stream resample: rates and block length must be positive, got {in_freq} -> {out_freq} Hz, n_in = {n_in}")
+        orig = in_freq // math.gcd(in_freq, out_freq)
+        if n_in % orig:
+            raise ValueError(f"stream resample: {in_freq} -> {out_freq} Hz takes blocks of whole {orig}-sample groups; n_in = {n_in} is not one")
+        raise ValueError(f"stream resample: a block of {n_in} samples at {in_freq} -> {out_freq} Hz and its history do not fit the kernel's LDS budget of "
+                         f"{STREAM_RESAMPLE_LDS_FLOATS} floats (64 KiB per stream)")
+    return n_out.value, hist.value, delay.value
+
+
 def pitch_class_table():
     """PitchEstimator.id2freq over ids 0..511 (reference encoder.py:48-54), on the host."""
     ids = torch.arange(spec.PITCH_CLASSES).to(torch.float)
@@ -242,6 +262,34 @@ class Engine:
         if x.numel():
             self._ok(self.lib.tvc_f32_to_pcm16(self.ctx, self._stream(), _ptr(x), _ptr(pcm), x.numel(), float(gain_db)), "tvc_f32_to_pcm16")
         return pcm
+
+    def stream_resample_geometry(self, in_freq, out_freq, n_in):
+        """The streaming door's geometry for blocks of `n_in` samples (tvc_stream_resample_geometry: host only) -> (n_out, hist, delay)."""
+        return stream_resample_geometry(in_freq, out_freq, n_in, self.lib)
+
+    def stream_resample_prepare(self, in_freq, out_freq):
+        """Build this engine's filter table for a rate pair now (its first use allocates: not inside a graph capture)."""
+        self._ok(self.lib.tvc_stream_resample_prepare(self.ctx, int(in_freq), int(out_freq)), "tvc_stream_resample_prepare")
+
+    def stream_resample(self, x, state, in_freq, out_freq, gain_db=0.0, out_pcm16=False):
+        """One block of S streams through the streaming resampler: x [S, n_in] (int16 PCM or fp32) -> [S, n_out] (int16 with out_pcm16,
+        else fp32); state [S, hist] fp32 is the streams' filter history, advanced in place (None at equal rates).  gain_db goes with the
+        int16 side.  The blocks of a stream, concatenated, are resample(G * orig zeros ++ its input) from the start, bit for bit."""
+        _check_dev(x, "x", self.device)
+        in16 = x.dtype == torch.int16
+        if x.dim() != 2 or not (in16 or x.dtype == _F32):
+            raise ValueError("stream_resample: x is [S, n_in], int16 or fp32")
+        x = x.contiguous()
+        S, n_in = x.shape
+        n_out, hist, _ = self.stream_resample_geometry(in_freq, out_freq, n_in)
+        if hist:
+            _check_dev(state, "state", self.device)
+            if tuple(state.shape) != (S, hist) or state.dtype != _F32 or not state.is_contiguous():
+                raise ValueError(f"stream_resample: state must be contiguous fp32 [{S}, {hist}] for {in_freq} -> {out_freq} Hz, got {tuple(state.shape)}")
+        y = torch.empty(S, n_out, dtype=torch.int16 if out_pcm16 else _F32, device=self.device)
+        self._ok(self.lib.tvc_stream_resample(self.ctx, self._stream(), _ptr(x), int(in16), _ptr(y), int(bool(out_pcm16)), _ptr(state) if hist else None,
+                                              S, n_in, int(in_freq), int(out_freq), float(gain_db)), "tvc_stream_resample")
+        return y
 
     def encoder(self, spec_t, want_logits=False):
         x = _prep(spec_t, "spec", self.device)

@@ -1,4 +1,4 @@
 from .generator import Generator
-from .stream import StreamInfer, BatchedStreamInfer
+from .stream import StreamInfer, BatchedStreamInfer, StreamDoor
 
-__all__ = ["Generator", "StreamInfer", "BatchedStreamInfer"]
+__all__ = ["Generator", "StreamInfer", "BatchedStreamInfer", "StreamDoor"]

@@ -1,11 +1,14 @@
 """Real-time wrapper: rolling input buffer, full convert per block, SOLA alignment and cross-fade
 (reference module/infer/stream.py:30-96).  `StreamInfer` is the reference's single-stream class;
 `BatchedStreamInfer` runs S independent streams through one batched convert + one SOLA launch with
-the lag arg-max kept on the device."""
+the lag arg-max kept on the device.  `StreamDoor` (extension) puts a stateful resampler, fused with the int16 conversions and gain, on both
+sides of the block: clients send and receive int16 at their own rates."""
+import math
+
 import numpy as np
 import torch
 
-from ...engine import pitch_shifts
+from ...engine import pitch_shifts, stream_resample_geometry
 from ..tinyvc.feature_retrieval import PitchTrack, resolve_auto_pitch, target_form
 from .generator import Generator
 
@@ -16,6 +19,79 @@ def _fade_windows(crossfade_size, device):
     return fade_in.to(device), (1 - fade_in).to(device)
 
 
+MODEL_RATE = 24000
+
+
+class StreamDoor:
+    """The two resamplers of a set of streams that advance in lock step (tvc_stream_resample): clients send int16 at `in_rate` and receive
+    int16 at `out_rate` (default: in_rate); the model runs `block_size` samples at 24 kHz in between.
+      chunk_in, chunk_out      the client-side block lengths: block_size * in_rate / 24000 and block_size * out_rate / 24000
+      in_state [S, hist_in]    each stream's filter history on the way in (client samples after the int16 conversion and input_gain)
+      out_state [S, hist_out]  and on the way out (24 kHz samples), fp32 on the device; zeros = the start of a stream
+      latency_seconds          delay_in / 24000 + delay_out / out_rate: what the two filters' look-ahead adds
+    A stream's blocks are, bit for bit, what the offline resampler gives for the whole signal with G * orig zeros in front (see
+    tinyvc_hip.h).  `input_gain` / `output_gain` in dB, applied with the int16 conversions.  Every argument is checked before anything is
+    allocated (ValueError): a block_size either rate cannot serve in whole groups is refused with the nearest sizes that work."""
+
+    def __init__(self, n_streams, in_rate, out_rate=None, block_size=1920, input_gain=0.0, output_gain=0.0, device=None):
+        out_rate = in_rate if out_rate is None else out_rate
+        for x, name in ((n_streams, "n_streams"), (in_rate, "in_rate"), (out_rate, "out_rate"), (block_size, "block_size")):
+            if isinstance(x, bool) or not isinstance(x, int) or x < 1:
+                raise ValueError(f"StreamDoor: {name} must be an integer >= 1, got {x!r}")
+        for x, name in ((input_gain, "input_gain"), (output_gain, "output_gain")):
+            if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x):
+                raise ValueError(f"StreamDoor: {name} must be a finite number of dB, got {x!r}")
+        # the 24 kHz side of each rate pair comes in groups of 24000 / gcd samples: the block must be whole groups of both
+        step = math.lcm(MODEL_RATE // math.gcd(in_rate, MODEL_RATE), MODEL_RATE // math.gcd(out_rate, MODEL_RATE))
+        if block_size % step:
+            near = [n for n in (block_size // step * step, (block_size // step + 1) * step) if n > 0]
+            raise ValueError(f"StreamDoor: block_size = {block_size} at 24000 Hz is not a whole number of resampling groups for {in_rate} Hz in / "
+                             f"{out_rate} Hz out (multiples of {step}); the nearest sizes that work: {' or '.join(str(n) for n in near)}")
+        self.n_streams, self.in_rate, self.out_rate, self.block_size = n_streams, in_rate, out_rate, block_size
+        self.input_gain, self.output_gain = float(input_gain), float(output_gain)
+        self.chunk_in = block_size * in_rate // MODEL_RATE
+        self.chunk_out = block_size * out_rate // MODEL_RATE
+        n24, self.hist_in, self.delay_in = stream_resample_geometry(in_rate, MODEL_RATE, self.chunk_in)
+        nout, self.hist_out, self.delay_out = stream_resample_geometry(MODEL_RATE, out_rate, block_size)
+        assert (n24, nout) == (block_size, self.chunk_out)
+        self.latency_seconds = self.delay_in / MODEL_RATE + self.delay_out / out_rate
+        device = torch.device(device if device is not None else "cuda")
+        if device.type != "cuda" or not torch.cuda.is_available():
+            raise ValueError(f"StreamDoor: the state lives on the GPU, where the door's kernel runs; got device {str(device)!r}"
+                             + ("" if torch.cuda.is_available() else " and there is no GPU here"))
+        self.device = device
+        self.in_state = torch.zeros(n_streams, self.hist_in, dtype=torch.float32, device=device)
+        self.out_state = torch.zeros(n_streams, self.hist_out, dtype=torch.float32, device=device)
+
+    def params(self):
+        """the host values a captured block bakes in"""
+        return (self.in_rate, self.out_rate, self.block_size, self.input_gain, self.output_gain)
+
+    def prepare(self, engine):
+        """build `engine`'s filter tables for both rate pairs now: their first use allocates, which a graph capture cannot record"""
+        engine.stream_resample_prepare(self.in_rate, MODEL_RATE)
+        engine.stream_resample_prepare(MODEL_RATE, self.out_rate)
+
+    def reset(self, streams=None):
+        """Forget the filter history of every stream, or of the listed ones: in-place ops on the state tensors, so it works between replays
+        of a captured graph (which reads them when it runs)."""
+        if streams is None:
+            self.in_state.zero_()
+            self.out_state.zero_()
+            return
+        idx = torch.as_tensor(list(streams), dtype=torch.int64, device=self.device)
+        self.in_state.index_fill_(0, idx, 0.0)
+        self.out_state.index_fill_(0, idx, 0.0)
+
+    def push(self, engine, pcm):
+        """client int16 [S, chunk_in] -> fp32 [S, block_size] at 24 kHz (input_gain applied), advancing in_state"""
+        return engine.stream_resample(pcm, self.in_state, self.in_rate, MODEL_RATE, self.input_gain)
+
+    def pull(self, engine, y):
+        """fp32 [S, block_size] at 24 kHz -> client int16 [S, chunk_out] (output_gain applied), advancing out_state"""
+        return engine.stream_resample(y, self.out_state, MODEL_RATE, self.out_rate, self.output_gain, out_pcm16=True)
+
+
 class BatchedStreamInfer:
     """`target`: one index for every stream ([1, 768, N]) or one per stream ([S, 768, N], or a list of S [1, 768, N_s] tensors), prepared
     once and cached on those tensors - or a feature_retrieval.Blend of several (its weights are read on the device when a block runs:
@@ -23,10 +99,15 @@ class BatchedStreamInfer:
     `auto_pitch` (convert's: True, a register in Hz, or a [S] / [1] device tensor that is read when a block runs): every block moves each
     stream's register - the lower median of its last voiced frames, tracked on the device by `pitch_track` (a feature_retrieval.PitchTrack;
     built in init_buffer when not given: the block's own frames, last_dilay_size before the end of the buffer, are the new ones) - onto
-    the target's; `pitch_shift` is the offset on top and `last_pitch_shift` [S] the shift the latest block applied, on the device."""
+    the target's; `pitch_shift` is the offset on top and `last_pitch_shift` [S] the shift the latest block applied, on the device.
+    `door` (a StreamDoor of the same n_streams and block_size): audio_callback_pcm takes the clients' int16 blocks at the door's rates."""
 
     def __init__(self, generator: Generator, n_streams=1, target=None, pitch_shift=0., device=None,
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, auto_pitch=None, pitch_track=None):
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, door=None, auto_pitch=None,
+                 pitch_track=None):
+        if door is not None and (door.n_streams, door.block_size) != (n_streams, block_size):
+            raise ValueError(f"door: built for {door.n_streams} streams of {door.block_size}-sample blocks, the streams are {n_streams} of {block_size}")
+        self.door = door
         self.auto_pitch = auto_pitch if auto_pitch is not False else None
         self.pitch_track = pitch_track
         self._own_track = pitch_track is None
@@ -66,6 +147,9 @@ class BatchedStreamInfer:
             if self._own_track:      # the block's own frames: they have their full right context and are the audio about to be played
                 self.pitch_track = PitchTrack(self.n_streams, self.block_size // 480, self.last_dilay_size // 480, device=self.device)
             self.pitch_track.reset()
+        if self.door is not None:
+            self.door.prepare(self.generator.engine(self.device))
+            self.door.reset()
 
     def _step(self, blocks, noise_angle):
         # torch.roll + slice assignment of the reference (stream.py:69-70), in place on a fixed buffer, one launch
@@ -86,13 +170,19 @@ class BatchedStreamInfer:
         return eng.sola(y, self.sola_buffer, self.fade_in_window, self.block_size,
                         self.use_phase_vocoder, want_shift=True) + (pshift,)
 
+    def _step_pcm(self, pcm, noise_angle):
+        # the whole block from client int16 to client int16: door in, _step, door out
+        eng = self.generator.engine(self.device)
+        out, shift, pshift = self._step(self.door.push(eng, pcm), noise_angle)
+        return self.door.pull(eng, out), shift, pshift
+
     def _graph_key(self):
         """Everything a captured step bakes in as raw device pointers: the packed weights (re-packed - and the old arena
         freed - when a parameter changes), the engine's scratch workspace (re-allocated when another call needs a bigger
         one), the prepared index riding on `target`, plus the scalars captured by value.  With auto_pitch also the
         tracker's three state tensors (where they live) and its host parameters, and WHERE the target registers live - not their values,
         nor the ring's or `auto`'s: the kernels read those at replay, so a reset(), registers.copy_(...) or a stream's history advancing
-        keeps the graph."""
+        keeps the graph.  With a door, likewise: where its two state tensors live and its host parameters (rates, block, gains)."""
         eng = self.generator.engine(self.device)          # re-packs the weights first if a parameter changed
         ws = eng._ws
         form, tgts = target_form(self.target)      # every blob's tensor
@@ -107,16 +197,34 @@ class BatchedStreamInfer:
             tr = self.pitch_track
             tkey = (regs if isinstance(regs, float) else tuple(r.data_ptr() for r in regs), tr.ring.data_ptr(), tr.count.data_ptr(), tr.auto.data_ptr(),
                     tr.params())
+        if self.door is not None:
+            tkey += (self.door.in_state.data_ptr(), self.door.out_state.data_ptr(), self.door.params())
         return (eng.weights_key, ws.data_ptr() if ws is not None else 0, ws.numel() if ws is not None else 0,
                 tuple((id(t), t._version, t.data_ptr()) for t in tgts), wkey, shifts, bool(self.use_phase_vocoder)) + tkey
 
     @torch.no_grad()
     def audio_callback(self, blocks, noise_angle=None):
         """blocks [S, block_size] -> converted blocks [S, block_size]."""
+        return self._callback(blocks, noise_angle, False)
+
+    @torch.no_grad()
+    def audio_callback_pcm(self, pcm, noise_angle=None):
+        """The clients' blocks through the door: pcm [S, door.chunk_in] int16 at door.in_rate -> int16 [S, door.chunk_out] at door.out_rate.
+        Door in (int16 -> fp32, input gain, resample to 24 kHz), the block of audio_callback, door out (resample, output gain, int16); with
+        use_graph all of it is one captured graph."""
+        if self.door is None:
+            raise ValueError("audio_callback_pcm needs a door: BatchedStreamInfer(..., door=StreamDoor(n_streams, in_rate, ...))")
+        if pcm.dtype != torch.int16 or tuple(pcm.shape) != (self.n_streams, self.door.chunk_in):
+            raise ValueError(f"audio_callback_pcm: int16 [{self.n_streams}, {self.door.chunk_in}] blocks at {self.door.in_rate} Hz, got "
+                             f"{pcm.dtype} {tuple(pcm.shape)}")
+        return self._callback(pcm, noise_angle, True)
+
+    def _callback(self, blocks, noise_angle, pcm):
+        step = self._step_pcm if pcm else self._step
         blocks = blocks.to(self.device)
         self._calls += 1
         if not self.use_graph or self._calls <= 2:
-            out, self.last_shift, self.last_pitch_shift = self._step(blocks, noise_angle)
+            out, self.last_shift, self.last_pitch_shift = step(blocks, noise_angle)
             return out
         key = self._graph_key()
         if self._graph is not None and key != self._graph[0]:
@@ -124,27 +232,30 @@ class BatchedStreamInfer:
         if self._graph is None:
             self._graph = (key, {})
             self._g_in = torch.zeros(self.n_streams, self.block_size, device=self.device)
+            self._g_pcm = torch.zeros(self.n_streams, self.door.chunk_in, dtype=torch.int16, device=self.device) if self.door is not None else None
             self._g_angle = torch.zeros(self.n_streams, 961, self.input_size // 480, device=self.device)
         inject = noise_angle is not None      # injected phases replay from a static buffer; otherwise the draw is part of the graph
+        g_in = self._g_pcm if pcm else self._g_in
+        slot = ("pcm", inject) if pcm else inject
         graphs = self._graph[1]
-        if inject not in graphs:
-            self._g_in.copy_(blocks)
+        if slot not in graphs:
+            g_in.copy_(blocks)
             if inject:
                 self._g_angle.copy_(noise_angle)
-            # capture changes no state: the buffer roll, convert and SOLA are recorded, not run
+            # capture changes no state: the buffer roll, convert and SOLA (and the door's two launches) are recorded, not run
             torch.cuda.synchronize(self.device)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                res = self._step(self._g_in, self._g_angle if inject else None)
-            graphs[inject] = (g, res)
+                res = step(g_in, self._g_angle if inject else None)
+            graphs[slot] = (g, res)
             if self._graph_key() != key:      # the capture itself grew the workspace: what it recorded is already stale
                 self._graph = None
-                out, self.last_shift, self.last_pitch_shift = self._step(blocks, noise_angle)
+                out, self.last_shift, self.last_pitch_shift = step(blocks, noise_angle)
                 return out
-        self._g_in.copy_(blocks)
+        g_in.copy_(blocks)
         if inject:
             self._g_angle.copy_(noise_angle)
-        g, (g_out, g_shift, g_pshift) = graphs[inject]
+        g, (g_out, g_shift, g_pshift) = graphs[slot]
         g.replay()
         self.last_shift, self.last_pitch_shift = g_shift, g_pshift
         return g_out.clone()
@@ -154,13 +265,19 @@ class StreamInfer(BatchedStreamInfer):
     """Single stream with the reference's constructor and 1-D buffers (stream.py:31-57)."""
 
     def __init__(self, generator: Generator, target=None, pitch_shift=0., device=torch.device("cpu"),
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, auto_pitch=None, pitch_track=None):
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, door=None, auto_pitch=None,
+                 pitch_track=None):
         dev = torch.device(device)
         if dev.type != "cuda":
             dev = generator._module_device()     # the reference defaults to CPU; there is no CPU path here
-        super().__init__(generator, 1, target, pitch_shift, dev, block_size, extra_size, use_phase_vocoder, f0_estimation, use_graph, auto_pitch, pitch_track)
+        super().__init__(generator, 1, target, pitch_shift, dev, block_size, extra_size, use_phase_vocoder, f0_estimation, use_graph, door, auto_pitch, pitch_track)
 
     @torch.no_grad()
     def audio_callback(self, block, noise_angle=None):
         """block [block_size] -> converted block [block_size] (stream.py:68-96)."""
         return super().audio_callback(block[None], noise_angle)[0]
+
+    @torch.no_grad()
+    def audio_callback_pcm(self, pcm, noise_angle=None):
+        """pcm [door.chunk_in] int16 -> int16 [door.chunk_out]."""
+        return super().audio_callback_pcm(pcm[None], noise_angle)[0]
