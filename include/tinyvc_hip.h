@@ -460,6 +460,21 @@ int tvc_sola_f32(tvc_ctx* ctx, void* stream, const float* y, float* sola_buf, co
                  float* out, int32_t* shift_out, int S, int64_t Ly, int block,
                  int use_phase_vocoder);
 
+/* The same tail with the geometry chosen by the caller: sola_buf [S][cross], fade_in [cross], temp = y[Ly - (block + cross + search + delay) :
+ * Ly - delay], the lag is searched over 0 .. search.  tvc_sola_f32 is the (1920, 1920, 3840) call of it.  The first sample of the block a
+ * stream emits lags the first sample of its newest input block by cross + search + delay - shift samples, shift in [0, search].
+ *
+ * tvc_sola_geometry (host only: no context, no device) holds the limits: 4 <= cross <= 1920 and cross % 4 == 0; 0 <= search <= 1920
+ * (0 = one lag: a plain cross-fade); delay >= 0; 1 <= block <= 2^30.  Anything else returns TVC_ERR_ARG; otherwise min_ly = block + cross +
+ * search + delay (the shortest y), latency_min = cross + delay and latency_max = cross + search + delay, in samples (out pointers are
+ * nullable).  tvc_sola_geometry_message gives the reason of a refusal ("" for a legal geometry), valid until the thread's next call.
+ * tvc_sola_geom_f32 refuses the same geometries and Ly < min_ly with that reason in tvc_last_error (a short Ly names the minimum).
+ * Capturable like tvc_sola_f32: the geometry is baked into a capture, the samples and the buffer are read when the kernel runs. */
+int tvc_sola_geometry(int block, int cross, int search, int delay, int64_t* min_ly, int* latency_min, int* latency_max);
+const char* tvc_sola_geometry_message(int block, int cross, int search, int delay);
+int tvc_sola_geom_f32(tvc_ctx* ctx, void* stream, const float* y, float* sola_buf, const float* fade_in, float* out, int32_t* shift_out, int S,
+                      int64_t Ly, int block, int cross, int search, int delay, int use_phase_vocoder);
+
 /* StreamInfer.audio_callback before convert (reference module/infer/stream.py:69-70: `input_wav = torch.roll(input_wav, -block)`,
  * `input_wav[-block:] = block`), batched over S streams, in place and in one launch: buf [S, n] rolling input buffers,
  * blocks [S, block] the new blocks; afterwards buf[s] = (old buf[s][block:], blocks[s]).  Any block <= n < 2^31 - 32 768; a row longer

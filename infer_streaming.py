@@ -24,6 +24,11 @@ is carried per stream, so there is no transient at block edges), and `-ig` / `-o
 must be an integer made of whole resampling groups (44.1 kHz: multiples of 147 samples, e.g. -c 3528).  Without the flag `-sr` only opens the
 device at that rate and the samples are taken for 24 kHz, as in the reference.
 
+`--crossfade N --sola-search N --lookahead N` (extension) set the SOLA geometry the reference hard-codes (1920, 1920, 3840), in samples at
+the model's 24 kHz.  A block's first sample is played crossfade + lookahead .. crossfade + sola-search + lookahead samples after the first
+sample of the newest block came in (240 .. 320 ms at the defaults), plus the block itself: the latency is these three numbers, not compute.
+Look-ahead is the right context the converter sees behind the block it emits; a shorter one trades that context for latency.
+
 `--streams S` feeds S copies of the input as S concurrent streams through one BatchedStreamInfer
 (one batched convert + one SOLA launch per block) and reports the p50 / p95 block latency against the
 real-time budget (chunk / 24 kHz = 80 ms for the default 1920-sample chunk).
@@ -38,8 +43,9 @@ import torch
 
 from tinyvc_amd import audio_io
 from infer import load_generator, load_target
-from tinyvc_amd.engine import stream_resample_geometry
+from tinyvc_amd.engine import sola_geometry, stream_resample_geometry
 from tinyvc_amd.module.infer import BatchedStreamInfer, StreamDoor
+from tinyvc_amd.module.infer.stream import check_window
 from tinyvc_amd.module.tinyvc.feature_retrieval import PitchTrack, add_blend_argument, pitch_register, semitones_between
 
 FRAMES_PER_SECOND = 50      # 24 kHz / 480 samples
@@ -74,6 +80,11 @@ def build_parser():
     p.add_argument("--resample", action="store_true",
                    help="run the device (or file) at -sr and resample every block to the model's 24 kHz and back on the GPU; -c counts samples at -sr, "
                         "-ig / -og are applied by the same kernels")
+    p.add_argument("--crossfade", default=1920, type=int, metavar="N", help="SOLA cross-fade length in 24 kHz samples: a multiple of 4 in 4 .. 1920")
+    p.add_argument("--sola-search", default=1920, type=int, metavar="N", help="SOLA lag search range in 24 kHz samples: 0 .. 1920 (0 = a plain cross-fade)")
+    p.add_argument("--lookahead", default=3840, type=int, metavar="N",
+                   help="24 kHz samples of converted audio behind the emitted block (the reference's last_dilay_size): right context for the converter, "
+                        "paid for in latency; with --auto-pitch a multiple of 480")
     # file-driven operation (no audio devices on a GPU node)
     p.add_argument("--input-wav", default=None, help="read the microphone signal from this WAV instead of a device")
     p.add_argument("--output-wav", default=None, help="write the converted stream here")
@@ -112,6 +123,20 @@ def check_resample(args):
     return block
 
 
+def check_geometry(args, block=None):
+    """--crossfade / --sola-search / --lookahead against the block (and -e, --auto-pitch; stream.check_window's rules), before anything is
+    loaded: sys.exit with a message, or (latency_min, latency_max) in 24 kHz samples.  `block`: the model's block length when it is not -c (--resample)"""
+    chunk = args.chunk if block is None else block
+    try:
+        _, pad = check_window(chunk, args.extra, args.crossfade, args.sola_search, args.lookahead, bool(args.auto_pitch))
+        _, lo, hi = sola_geometry(chunk, args.crossfade, args.sola_search, args.lookahead)
+    except ValueError as e:
+        sys.exit(f"infer_streaming.py: --crossfade {args.crossfade} --sola-search {args.sola_search} --lookahead {args.lookahead} -e {args.extra} with blocks of "
+                 f"{chunk}: {e}")
+    lo, hi = lo - pad, hi - pad      # a window that is not whole frames is padded behind its end: that much of the look-ahead is padding
+    return lo, hi
+
+
 def check_auto_pitch(args, block=None):
     """--auto-pitch against the other flags, before anything is loaded: sys.exit with a message, or the PitchTrack keywords (None without
     the flag).  `block`: the model's block length when it is not -c (--resample)"""
@@ -139,6 +164,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     block = check_resample(args)
     track_kw = check_auto_pitch(args, block)
+    check_geometry(args, block)
     device = torch.device(args.device)
     if device.type != "cuda":
         sys.exit("infer_streaming.py: this build runs on an AMD GPU only; pass -d cuda")
@@ -164,7 +190,7 @@ def main(argv=None):
     if track_kw is not None:
         if getattr(tgt, "pitch_register", None) is None:
             sys.exit(f"infer_streaming.py: --auto-pitch: no pitch register beside {args.index} (extract_index.py writes <index>.f0.pt)")
-        track = PitchTrack(S, lag_frames=3840 // 480, device=device, **track_kw)      # the frames of the block about to be played (last_dilay_size)
+        track = PitchTrack(S, lag_frames=args.lookahead // 480, device=device, **track_kw)      # the frames of the block about to be played (last_dilay_size)
     # the int16 conversions and gains belong to the door; without --resample it stands between equal rates - the samples are taken for
     # 24 kHz whatever -sr says, as in the reference - and is those conversions alone
     rate = args.sample_rate if block is not None else 24000
@@ -173,7 +199,11 @@ def main(argv=None):
         print(f"Resampling {rate} Hz <-> 24000 Hz on the device: {args.chunk}-sample blocks are {block} at the model's rate; "
               f"the two filters add {door.latency_seconds * 1e3:.2f} ms of latency")
     stream = BatchedStreamInfer(gen, n_streams=S, pitch_shift=pitch_shift, block_size=door.block_size, device=device, extra_size=args.extra,
-                                f0_estimation=args.f0_estimation, door=door, auto_pitch=True if track is not None else None, pitch_track=track)
+                                f0_estimation=args.f0_estimation, door=door, auto_pitch=True if track is not None else None, pitch_track=track,
+                                crossfade_size=args.crossfade, sola_search_size=args.sola_search, last_delay_size=args.lookahead)
+    lo, hi = stream.latency_seconds
+    print(f"Latency {lo * 1e3:.1f} to {hi * 1e3:.1f} ms (cross-fade {args.crossfade} + look-ahead {args.lookahead} + lag 0 .. {args.sola_search} samples at 24 kHz"
+          f"{', and the resampling filters' if block is not None else ''}) plus the {door.block_size / 24000 * 1e3:.0f} ms block")
     stream.target = tgt
     stream.init_buffer()
 

@@ -90,6 +90,9 @@ SIGNATURES = {
     "tvc_index_compact_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_size_t]),
     "tvc_sola_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int]),
+    "tvc_sola_geom_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_int]),
+    "tvc_sola_geometry": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int), POINTER(c_int)]),
+    "tvc_sola_geometry_message": (c_char_p, [c_int, c_int, c_int, c_int]),
     "tvc_stream_push_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int]),
     "tvc_stream_resample_geometry": (c_int, [c_int, c_int, c_int64, POINTER(c_int64), POINTER(c_int), POINTER(c_int)]),
     "tvc_stream_resample_prepare": (c_int, [c_void_p, c_int, c_int]),

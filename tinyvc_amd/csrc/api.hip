@@ -961,10 +961,33 @@ int tvc_profile_read(tvc_ctx* ctx, char* buf, size_t buf_bytes) {
 int tvc_sola_f32(tvc_ctx* ctx, void* stream, const float* y, float* sola_buf, const float* fade_in, float* out,
                  int32_t* shift_out, int S, int64_t Ly, int block, int use_phase_vocoder) {
     if (!ctx) return TVC_ERR_ARG;
-    if (!y || !sola_buf || !fade_in || !out || S <= 0 || block <= 0 || Ly < block + kSolaCross + kSolaSearch + kSolaDelay)
+    if (!y || !sola_buf || !fade_in || !out || S <= 0 || block <= 0 || block > kSolaMaxBlock || Ly < (int64_t)block + kSolaCross + kSolaSearch + kSolaDelay)
         return fail(ctx, TVC_ERR_ARG, "tvc_sola_f32: bad argument (Ly must cover block+1920+1920+3840)");
     TVC_HIP(ctx, hipSetDevice(ctx->device));
-    return run_sola(ctx, (hipStream_t)stream, y, sola_buf, fade_in, out, shift_out, S, Ly, block, use_phase_vocoder);
+    return run_sola(ctx, (hipStream_t)stream, y, sola_buf, fade_in, out, shift_out, S, Ly, block, kSolaCross, kSolaSearch, kSolaDelay, use_phase_vocoder);
+}
+
+int tvc_sola_geometry(int block, int cross, int search, int delay, int64_t* min_ly, int* latency_min, int* latency_max) {
+    return sola_geometry(block, cross, search, delay, min_ly, latency_min, latency_max, nullptr, 0);
+}
+
+const char* tvc_sola_geometry_message(int block, int cross, int search, int delay) {
+    static thread_local char why[96];
+    sola_geometry(block, cross, search, delay, nullptr, nullptr, nullptr, why, sizeof(why));
+    return why;
+}
+
+int tvc_sola_geom_f32(tvc_ctx* ctx, void* stream, const float* y, float* sola_buf, const float* fade_in, float* out, int32_t* shift_out, int S,
+                      int64_t Ly, int block, int cross, int search, int delay, int use_phase_vocoder) {
+    if (!ctx) return TVC_ERR_ARG;
+    char why[96];
+    int64_t min_ly = 0;
+    if (sola_geometry(block, cross, search, delay, &min_ly, nullptr, nullptr, why, sizeof(why)) != 0) return fail(ctx, TVC_ERR_ARG, "tvc_sola_geom_f32: %s", why);
+    if (!y || !sola_buf || !fade_in || !out || S <= 0) return fail(ctx, TVC_ERR_ARG, "tvc_sola_geom_f32: bad argument (a NULL pointer or S <= 0)");
+    if (Ly < min_ly)
+        return fail(ctx, TVC_ERR_ARG, "tvc_sola_geom_f32: Ly = %ld is shorter than block + cross + search + delay = %ld", (long)Ly, (long)min_ly);
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    return run_sola(ctx, (hipStream_t)stream, y, sola_buf, fade_in, out, shift_out, S, Ly, block, cross, search, delay, use_phase_vocoder);
 }
 
 int tvc_stream_push_f32(tvc_ctx* ctx, void* stream, float* buf, const float* blocks, int S, int64_t n, int block) {

@@ -26,7 +26,8 @@ constexpr int kPitchCh = 128;
 constexpr int kPitchClasses = 512;
 constexpr int kSrcCh = 128;
 constexpr int kHarm = 15;  // num_harmonics + 1 sinusoids
-constexpr int kSolaCross = 1920, kSolaSearch = 1920, kSolaDelay = 3840;
+constexpr int kSolaCross = 1920, kSolaSearch = 1920, kSolaDelay = 3840;   // the reference's SOLA geometry (stream.py:48-50): the default, and the caps of cross and search
+constexpr int kSolaMaxBlock = 1 << 30;
 constexpr int kSolaGroups = 8, kSolaPartFloats = 16384;   // lag groups (workgroups) per stream of the correlation search; its scratch in the context's constant arena
 
 // A conv / 1x1 weight packed for the split-precision MFMA kernels (conv3s.h): the two-part fp16 image A6 (K16 steps x MT6 = Mpad / 32
@@ -461,8 +462,10 @@ struct DspFork {
 // csum: the oscillator's frame sums [B][15][T] (doubles); nullptr = run_dsp takes its own from ws
 int run_dsp(tvc_ctx*, hipStream_t, Ws&, const float* f0, const float* amps, const float* kern, const float* angle, uint64_t seed, float* source, int B, int T,
             float* smax = nullptr, double* csum = nullptr, const DspFork* fk = nullptr);
+// the legal SOLA geometries, in one place (sola.hip): 0, or TVC_ERR_ARG with the reason in `why`; every out pointer is nullable
+int sola_geometry(int block, int cross, int search, int delay, int64_t* min_ly, int* latency_min, int* latency_max, char* why, size_t why_bytes);
 int run_sola(tvc_ctx*, hipStream_t, const float* y, float* sola_buf, const float* fade_in, float* out, int32_t* shift_out,
-             int S, int64_t Ly, int block, int use_pv);
+             int S, int64_t Ly, int block, int cross, int search, int delay, int use_pv);
 int run_stream_push(tvc_ctx* ctx, hipStream_t s, float* buf, const float* blocks, int S, int n, int m);
 int64_t resample_out_len(int64_t n, int orig_freq, int new_freq);
 int run_resample(tvc_ctx*, hipStream_t, const float* x, float* y, int rows, int64_t n, int orig_freq, int new_freq);

@@ -5,6 +5,7 @@ scratch workspace; every computation is a call into libtinyvc_hip.so.
 """
 import ctypes
 import math
+import numbers
 import threading
 import weakref
 
@@ -95,6 +96,24 @@ def stream_resample_geometry(in_freq, out_freq, n_in, lib=None):
         raise ValueError(f"stream resample: a block of {n_in} samples at {in_freq} -> {out_freq} Hz and its history do not fit the kernel's LDS budget of "
                          f"{STREAM_RESAMPLE_LDS_FLOATS} floats (64 KiB per stream)")
     return n_out.value, hist.value, delay.value
+
+
+SOLA_CROSS, SOLA_SEARCH, SOLA_DELAY = 1920, 1920, 3840      # the reference's SOLA geometry (stream.py:48-50): the defaults, and the caps of the first two
+
+
+def sola_geometry(block, cross=SOLA_CROSS, search=SOLA_SEARCH, delay=SOLA_DELAY, lib=None):
+    """tvc_sola_geometry (no context, no device) -> (min_ly, latency_min, latency_max) of a streaming tail with `block`-sample blocks: the
+    shortest converted buffer it takes, and the range of cross + search + delay - shift, in 24 kHz samples.  ValueError, with the library's
+    reason, for a geometry the kernels do not take."""
+    for x, name in ((block, "block"), (cross, "cross"), (search, "search"), (delay, "delay")):
+        if isinstance(x, bool) or not isinstance(x, numbers.Integral) or abs(x) >= 2 ** 31:
+            raise ValueError(f"sola geometry: {name} must be an integer, got {x!r}")
+    block, cross, search, delay = int(block), int(cross), int(search), int(delay)
+    lib = lib if lib is not None else _lib.load_library()
+    min_ly, lo, hi = ctypes.c_int64(), ctypes.c_int(), ctypes.c_int()
+    if lib.tvc_sola_geometry(block, cross, search, delay, ctypes.byref(min_ly), ctypes.byref(lo), ctypes.byref(hi)) != 0:
+        raise ValueError(f"sola geometry: {lib.tvc_sola_geometry_message(block, cross, search, delay).decode()}")
+    return min_ly.value, lo.value, hi.value
 
 
 def pitch_class_table():
@@ -841,17 +860,33 @@ class Engine:
         self._ok(self.lib.tvc_stream_push_f32(self.ctx, self._stream(), _ptr(buf), _ptr(blocks), S, n, blocks.shape[1]), "tvc_stream_push_f32")
         return buf
 
-    def sola(self, y, sola_buf, fade_in, block, use_phase_vocoder=False, want_shift=False):
-        """y [S, Ly]; sola_buf [S, 1920] updated in place; returns out [S, block] (and shifts)."""
+    def sola(self, y, sola_buf, fade_in, block, use_phase_vocoder=False, want_shift=False, crossfade=None, search=None, delay=None):
+        """y [S, Ly]; sola_buf [S, crossfade] updated in place; fade_in [crossfade]; returns out [S, block] (and shifts).  The geometry
+        (tvc_sola_geom_f32; None = the reference's 1920 / 1920 / 3840) is checked by the library, the two tensors against it here: the
+        kernels read `crossfade` floats of each."""
         y = _prep(y, "y", self.device)
         _check_dev(sola_buf, "sola_buffer", self.device)
         fade_in = _prep(fade_in, "fade_in_window", self.device)
         if not sola_buf.is_contiguous() or sola_buf.dtype != _F32:
             raise ValueError("sola_buffer must be contiguous fp32")
+        default = crossfade is None and search is None and delay is None
+        cross, search, delay = (d if x is None else x for x, d in ((crossfade, SOLA_CROSS), (search, SOLA_SEARCH), (delay, SOLA_DELAY)))
+        for x, name in ((cross, "crossfade"), (search, "search"), (delay, "delay")):      # as sola_geometry: 240.9 is not 240
+            if isinstance(x, bool) or not isinstance(x, numbers.Integral) or abs(x) >= 2 ** 31:
+                raise ValueError(f"sola: {name} must be an integer, got {x!r}")
+        cross, search, delay = int(cross), int(search), int(delay)
         S, Ly = y.shape
-        out = torch.empty(S, block, dtype=_F32, device=self.device)
+        if tuple(sola_buf.shape) != (S, cross) or fade_in.numel() != cross:
+            raise ValueError(f"sola: crossfade = {cross} takes sola_buffer [{S}, {cross}] and a fade_in_window of {cross} entries, got "
+                             f"{tuple(sola_buf.shape)} and {fade_in.numel()}")
+        out = torch.empty(S, max(int(block), 0), dtype=_F32, device=self.device)
         shift = torch.empty(S, dtype=torch.int32, device=self.device) if want_shift else None
-        self._ok(self.lib.tvc_sola_f32(self.ctx, self._stream(), _ptr(y), _ptr(sola_buf), _ptr(fade_in), _ptr(out), _ptr(shift), S, Ly, int(block), int(bool(use_phase_vocoder))), "tvc_sola_f32")
+        if default:      # tvc_sola_f32 is the (1920, 1920, 3840) call of the same implementation and keeps its own error text
+            self._ok(self.lib.tvc_sola_f32(self.ctx, self._stream(), _ptr(y), _ptr(sola_buf), _ptr(fade_in), _ptr(out), _ptr(shift), S, Ly, int(block),
+                                           int(bool(use_phase_vocoder))), "tvc_sola_f32")
+        else:
+            self._ok(self.lib.tvc_sola_geom_f32(self.ctx, self._stream(), _ptr(y), _ptr(sola_buf), _ptr(fade_in), _ptr(out), _ptr(shift), S, Ly, int(block),
+                                                cross, search, delay, int(bool(use_phase_vocoder))), "tvc_sola_geom_f32")
         return (out, shift) if want_shift else out
 
 

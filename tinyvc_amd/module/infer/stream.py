@@ -1,22 +1,55 @@
 """Real-time wrapper: rolling input buffer, full convert per block, SOLA alignment and cross-fade
 (reference module/infer/stream.py:30-96).  `StreamInfer` is the reference's single-stream class;
 `BatchedStreamInfer` runs S independent streams through one batched convert + one SOLA launch with
-the lag arg-max kept on the device.  `StreamDoor` (extension) puts a stateful resampler, fused with the int16 conversions and gain, on both
+the lag arg-max kept on the device.  The tail's geometry (extension: the reference hard-codes it, stream.py:48-50) is a constructor
+argument - crossfade_size, sola_search_size, last_delay_size -: a block's first sample leaves crossfade + search + delay - shift samples
+after the first sample of the newest input block came in (shift in [0, search], chosen per block), so the three sizes are the latency a
+listener hears beyond the block itself; look-ahead (last_delay_size) is the right context the converter sees behind the emitted block.  `StreamDoor` (extension) puts a stateful resampler, fused with the int16 conversions and gain, on both
 sides of the block: clients send and receive int16 at their own rates."""
 import math
 
 import numpy as np
 import torch
 
-from ...engine import pitch_shifts, stream_resample_geometry
+from ...engine import SOLA_CROSS, SOLA_DELAY, SOLA_SEARCH, pitch_shifts, sola_geometry, stream_resample_geometry
 from ..tinyvc.feature_retrieval import PitchTrack, resolve_auto_pitch, target_form
 from .generator import Generator
 
 
 def _fade_windows(crossfade_size, device):
-    # stream.py:61-62, computed on the host exactly as the reference does, then uploaded
-    fade_in = torch.sin(np.pi * torch.arange(0, 1, 1 / crossfade_size) / 2) ** 2
+    # stream.py:61-62, computed on the host exactly as the reference does, then uploaded.  The window is the FIRST crossfade_size entries
+    # of the reference's expression: with a floating-point step arange(0, 1, 1 / n) has n + 1 entries for some n (196, 392, 412, ...)
+    fade_in = torch.sin(np.pi * torch.arange(0, 1, 1 / crossfade_size)[:crossfade_size] / 2) ** 2
+    assert fade_in.numel() == crossfade_size
     return fade_in.to(device), (1 - fade_in).to(device)
+
+
+MIN_INPUT = 960      # the front end reflect-pads a window by 960 samples on either side: it takes windows longer than that
+FRAME = 480
+
+
+def check_window(block_size, extra_size, crossfade_size, sola_search_size, last_delay_size, auto_pitch):
+    """The geometry of a stream against everything that can be said on the host (ValueError) -> (input_size, pad).  convert zero-pads a
+    window at its END to whole 480-sample frames and returns the padded length, and the tail counts from the end of what convert returns: a
+    window of input_size samples that is not whole frames puts pad = -input_size % 480 samples of converted padding behind the signal, so the
+    tail's look-ahead over the SIGNAL is last_delay_size - pad.  It must not be negative: the emitted block and the next SOLA buffer would
+    be cut partly from the conversion of the padding."""
+    sola_geometry(block_size, crossfade_size, sola_search_size, last_delay_size)      # ValueError with the library's reason
+    input_size = max(block_size + crossfade_size + sola_search_size + 2 * last_delay_size, block_size + extra_size)
+    if input_size <= MIN_INPUT:
+        raise ValueError(f"the stream's window of {input_size} samples (the larger of block + crossfade + search + 2 * delay and block + extra_size) "
+                         f"is too short for the front end, which reflect-pads {MIN_INPUT} samples on either side: raise extra_size to more than "
+                         f"{MIN_INPUT - block_size}")
+    pad = -input_size % FRAME
+    if pad > last_delay_size:
+        whole = (input_size + pad) - block_size
+        raise ValueError(f"the stream's window of {input_size} samples is converted as {input_size + pad} (whole {FRAME}-sample frames, zeros at the end): "
+                         f"{pad} samples of padding behind a look-ahead of last_delay_size = {last_delay_size} would put converted padding into the "
+                         f"emitted block; extra_size = {whole} makes the window whole frames")
+    if auto_pitch and last_delay_size % FRAME:
+        raise ValueError(f"auto_pitch: last_delay_size = {last_delay_size} is not a whole number of 480-sample frames (the tracker's new frames "
+                         f"end that far before the end of the window)")
+    return input_size, pad
 
 
 MODEL_RATE = 24000
@@ -100,11 +133,18 @@ class BatchedStreamInfer:
     stream's register - the lower median of its last voiced frames, tracked on the device by `pitch_track` (a feature_retrieval.PitchTrack;
     built in init_buffer when not given: the block's own frames, last_dilay_size before the end of the buffer, are the new ones) - onto
     the target's; `pitch_shift` is the offset on top and `last_pitch_shift` [S] the shift the latest block applied, on the device.
-    `door` (a StreamDoor of the same n_streams and block_size): audio_callback_pcm takes the clients' int16 blocks at the door's rates."""
+    `door` (a StreamDoor of the same n_streams and block_size): audio_callback_pcm takes the clients' int16 blocks at the door's rates.
+    `crossfade_size`, `sola_search_size`, `last_delay_size` (kept as the attribute `last_dilay_size`, the reference's spelling): the tail's
+    geometry in 24 kHz samples, within engine.sola_geometry's limits; `latency_samples` / `latency_seconds` give the resulting range.  The
+    attributes are plain, as in the reference: one changed after construction takes effect at the next init_buffer(), which checks them again
+    and recomputes input_size; until then every block is refused (ValueError), never run against buffers, a window or a tracker lag that no
+    longer match.  A window that is not whole 480-sample frames is padded by convert at its end (`pad_size`): the latency is that much
+    shorter than the three sizes say, and a look-ahead shorter than the pad is refused."""
 
     def __init__(self, generator: Generator, n_streams=1, target=None, pitch_shift=0., device=None,
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, door=None, auto_pitch=None,
-                 pitch_track=None):
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, door=None,
+                 crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
+        check_window(block_size, extra_size, crossfade_size, sola_search_size, last_delay_size, auto_pitch is not None and auto_pitch is not False)
         if door is not None and (door.n_streams, door.block_size) != (n_streams, block_size):
             raise ValueError(f"door: built for {door.n_streams} streams of {door.block_size}-sample blocks, the streams are {n_streams} of {block_size}")
         self.door = door
@@ -123,9 +163,9 @@ class BatchedStreamInfer:
         self.device = torch.device(device) if device is not None else generator._module_device()
         self.block_size = block_size
         self.extra_size = extra_size
-        self.sola_search_size = 1920
-        self.last_dilay_size = 3840          # (sic) the reference's attribute name, stream.py:49
-        self.crossfade_size = 1920
+        self.sola_search_size = sola_search_size
+        self.last_dilay_size = last_delay_size          # (sic) the reference's attribute name, stream.py:49
+        self.crossfade_size = crossfade_size
         self.use_phase_vocoder = use_phase_vocoder
         self.f0_estimation = f0_estimation
         self.input_size = max(self.block_size + self.crossfade_size + self.sola_search_size + 2 * self.last_dilay_size,
@@ -137,7 +177,33 @@ class BatchedStreamInfer:
         self._graph = None
         self._calls = 0
 
+    @property
+    def latency_samples(self):
+        """(min, max) 24 kHz samples between the first sample of the newest input block and the first sample of the block emitted for it:
+        crossfade + delay .. crossfade + search + delay, by the lag the search picks, LESS the pad of a window that is not whole 480-sample
+        frames (`pad_size`: convert pads the window at its end, the tail counts from the end of the padded conversion, so that much of the
+        look-ahead is padding and the block leaves that much earlier); the door's two filters come on top in latency_seconds"""
+        _, lo, hi = sola_geometry(self.block_size, self.crossfade_size, self.sola_search_size, self.last_dilay_size)
+        return lo - self.pad_size, hi - self.pad_size
+
+    @property
+    def pad_size(self):
+        """samples of zero padding convert puts behind the window to make it whole frames"""
+        return -self.input_size % FRAME
+
+    @property
+    def latency_seconds(self):
+        """latency_samples in seconds, plus the door's latency_seconds when there is a door; the time to collect a block is not included"""
+        extra = self.door.latency_seconds if self.door is not None else 0.0
+        lo, hi = self.latency_samples
+        return lo / MODEL_RATE + extra, hi / MODEL_RATE + extra
+
     def init_buffer(self):
+        # the attributes as they stand now (plain attributes, as in the reference): checked as in the constructor, the window follows them,
+        # and _step holds every later block against what was seen here
+        self.input_size, _ = check_window(self.block_size, self.extra_size, self.crossfade_size, self.sola_search_size, self.last_dilay_size,
+                                           self.auto_pitch is not None)
+        self._geometry = self._attributes()
         self.fade_in_window, self.fade_out_window = _fade_windows(self.crossfade_size, self.device)
         self.input_wav = torch.zeros(self.n_streams, self.input_size, device=self.device)
         self.sola_buffer = torch.zeros(self.n_streams, self.crossfade_size, device=self.device)
@@ -151,6 +217,9 @@ class BatchedStreamInfer:
             self.door.prepare(self.generator.engine(self.device))
             self.door.reset()
 
+    def _attributes(self):
+        return (self.block_size, self.crossfade_size, self.sola_search_size, self.last_dilay_size, self.input_size)
+
     def _step(self, blocks, noise_angle):
         # torch.roll + slice assignment of the reference (stream.py:69-70), in place on a fixed buffer, one launch
         self.generator.engine(self.device).stream_push(self.input_wav, blocks)
@@ -158,7 +227,7 @@ class BatchedStreamInfer:
             # a captured step bakes kernel arguments in: the library's seeded draw would replay ONE seed for every block.  torch's
             # generator is graph-safe (its offset advances per replay), so the graph path keeps the reference's torch.rand draw
             from ..tinyvc import Decoder
-            noise_angle = Decoder.draw_noise_angle(self.n_streams, self.input_size // 480, self.device)
+            noise_angle = Decoder.draw_noise_angle(self.n_streams, -(-self.input_size // 480), self.device)      # (convert pads the window to whole frames)
         pshift = None
         if self.auto_pitch is None:
             y = self.generator.convert(self.input_wav, self.target, self.pitch_shift, device=self.device,
@@ -167,8 +236,8 @@ class BatchedStreamInfer:
             y, pshift = self.generator.convert(self.input_wav, self.target, self.pitch_shift, device=self.device, f0_estimation=self.f0_estimation,
                                                noise_angle=noise_angle, auto_pitch=self.auto_pitch, return_shift=True, track=self.pitch_track)
         eng = self.generator.engine(self.device)
-        return eng.sola(y, self.sola_buffer, self.fade_in_window, self.block_size,
-                        self.use_phase_vocoder, want_shift=True) + (pshift,)
+        return eng.sola(y, self.sola_buffer, self.fade_in_window, self.block_size, self.use_phase_vocoder, want_shift=True,
+                        crossfade=self.crossfade_size, search=self.sola_search_size, delay=self.last_dilay_size) + (pshift,)
 
     def _step_pcm(self, pcm, noise_angle):
         # the whole block from client int16 to client int16: door in, _step, door out
@@ -182,7 +251,8 @@ class BatchedStreamInfer:
         one), the prepared index riding on `target`, plus the scalars captured by value.  With auto_pitch also the
         tracker's three state tensors (where they live) and its host parameters, and WHERE the target registers live - not their values,
         nor the ring's or `auto`'s: the kernels read those at replay, so a reset(), registers.copy_(...) or a stream's history advancing
-        keeps the graph.  With a door, likewise: where its two state tensors live and its host parameters (rates, block, gains)."""
+        keeps the graph.  With a door, likewise: where its two state tensors live and its host parameters (rates, block, gains).  The tail's
+        geometry is baked into its two launches, so it is part of the key."""
         eng = self.generator.engine(self.device)          # re-packs the weights first if a parameter changed
         ws = eng._ws
         form, tgts = target_form(self.target)      # every blob's tensor
@@ -200,7 +270,8 @@ class BatchedStreamInfer:
         if self.door is not None:
             tkey += (self.door.in_state.data_ptr(), self.door.out_state.data_ptr(), self.door.params())
         return (eng.weights_key, ws.data_ptr() if ws is not None else 0, ws.numel() if ws is not None else 0,
-                tuple((id(t), t._version, t.data_ptr()) for t in tgts), wkey, shifts, bool(self.use_phase_vocoder)) + tkey
+                tuple((id(t), t._version, t.data_ptr()) for t in tgts), wkey, shifts, bool(self.use_phase_vocoder),
+                (self.crossfade_size, self.sola_search_size, self.last_dilay_size)) + tkey
 
     @torch.no_grad()
     def audio_callback(self, blocks, noise_angle=None):
@@ -220,6 +291,9 @@ class BatchedStreamInfer:
         return self._callback(pcm, noise_angle, True)
 
     def _callback(self, blocks, noise_angle, pcm):
+        if self._attributes() != getattr(self, "_geometry", None):      # before anything runs or is captured
+            raise ValueError(f"block_size / crossfade_size / sola_search_size / last_dilay_size / input_size are {self._attributes()}, init_buffer() saw "
+                             f"{getattr(self, '_geometry', None)}: the buffers, the window and the tracker's lag follow them only there - call init_buffer()")
         step = self._step_pcm if pcm else self._step
         blocks = blocks.to(self.device)
         self._calls += 1
@@ -233,7 +307,7 @@ class BatchedStreamInfer:
             self._graph = (key, {})
             self._g_in = torch.zeros(self.n_streams, self.block_size, device=self.device)
             self._g_pcm = torch.zeros(self.n_streams, self.door.chunk_in, dtype=torch.int16, device=self.device) if self.door is not None else None
-            self._g_angle = torch.zeros(self.n_streams, 961, self.input_size // 480, device=self.device)
+            self._g_angle = torch.zeros(self.n_streams, 961, -(-self.input_size // 480), device=self.device)
         inject = noise_angle is not None      # injected phases replay from a static buffer; otherwise the draw is part of the graph
         g_in = self._g_pcm if pcm else self._g_in
         slot = ("pcm", inject) if pcm else inject
@@ -265,12 +339,13 @@ class StreamInfer(BatchedStreamInfer):
     """Single stream with the reference's constructor and 1-D buffers (stream.py:31-57)."""
 
     def __init__(self, generator: Generator, target=None, pitch_shift=0., device=torch.device("cpu"),
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, door=None, auto_pitch=None,
-                 pitch_track=None):
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, door=None,
+                 crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         dev = torch.device(device)
         if dev.type != "cuda":
             dev = generator._module_device()     # the reference defaults to CPU; there is no CPU path here
-        super().__init__(generator, 1, target, pitch_shift, dev, block_size, extra_size, use_phase_vocoder, f0_estimation, use_graph, door, auto_pitch, pitch_track)
+        super().__init__(generator, 1, target, pitch_shift, dev, block_size, extra_size, use_phase_vocoder, f0_estimation, use_graph, door,
+                         crossfade_size, sola_search_size, last_delay_size, auto_pitch, pitch_track)
 
     @torch.no_grad()
     def audio_callback(self, block, noise_angle=None):
