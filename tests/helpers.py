@@ -96,3 +96,236 @@ def stage(g, name):
     else:
         st = dm
     return torch.from_numpy(np.asarray(g[name + "_d"])), st
+
+
+# ---- front end, pitch decode and DSP edge cases (test_gpu_front_dsp_edges.py, test_front_dsp_metric_host.py) ----------------------------
+def frame_bin_errors(x, truth):
+    """[B, 961, T] against an fp64 `truth` -> (per frame [B, T], per bin [B, 961]), fp64.  Per frame t: the rms over bins of x - truth divided by
+    the rms of the WHOLE row.  Per bin k: the rms over frames of x - truth divided by the rms over frames of truth at that bin - the bin's own
+    scale, so a bin far below the row's loudest (bin 960 of a low-passed signal) is not hidden by them."""
+    truth = torch.as_tensor(truth)
+    assert truth.dtype == torch.float64 and truth.dim() == 3 and tuple(x.shape) == tuple(truth.shape)
+    d2 = (torch.as_tensor(x).double() - truth) ** 2
+    row = torch.sqrt((truth * truth).mean(dim=(1, 2))).clamp_min(1e-300)
+    per_frame = torch.sqrt(d2.mean(dim=1)) / row[:, None]
+    per_bin = torch.sqrt(d2.mean(dim=2)) / torch.sqrt((truth * truth).mean(dim=2)).clamp_min(1e-300)
+    return per_frame, per_bin
+
+
+def frame_element_errors(x, truth, frame=480):
+    """[B, L] against an fp64 `truth` -> (per frame [B, L / frame], per element [B, L]), both relative to the row's rms.  Samples where the
+    truth is NaN count nowhere: not in the row's rms, not in a frame's mean (a frame of NaNs reads 0), and their element error is 0."""
+    truth = torch.as_tensor(truth)
+    assert truth.dtype == torch.float64 and truth.dim() == 2 and tuple(x.shape) == tuple(truth.shape) and truth.shape[1] % frame == 0
+    ok = ~torch.isnan(truth)
+    t0 = torch.where(ok, truth, torch.zeros_like(truth))
+    d = torch.where(ok, torch.as_tensor(x).double() - t0, torch.zeros_like(truth))
+    n_row = ok.sum(dim=1).clamp_min(1)
+    row = torch.sqrt((t0 * t0).sum(dim=1) / n_row).clamp_min(1e-300)
+    B = truth.shape[0]
+    n_fr = ok.view(B, -1, frame).sum(dim=2).clamp_min(1)
+    per_frame = torch.sqrt((d * d).view(B, -1, frame).sum(dim=2) / n_fr) / row[:, None]
+    return per_frame, d.abs() / row[:, None]
+
+
+def decidable_samples(inc, margin):
+    """The oscillator's decidable samples.  inc: the oracle's fp32 phase increments of one (utterance, harmonic), 1-D.  The oracle's phase is
+    P = their sequential fp64 sum, rounded to fp32 (I).  Where P lies more than `margin` (cycles; a number or one per sample) from both
+    rounding midpoints of I, every summation order whose drift stays within the margin gives the same I, hence the same sample up to the
+    sine's last bit -> (decidable [n] bool, P fp64, I fp32)."""
+    P = np.cumsum(np.asarray(inc, dtype=np.float32).reshape(-1).astype(np.float64))
+    I = P.astype(np.float32)
+    lo = (I.astype(np.float64) + np.nextafter(I, np.float32(-np.inf)).astype(np.float64)) / 2
+    hi = (I.astype(np.float64) + np.nextafter(I, np.float32(np.inf)).astype(np.float64)) / 2
+    return np.minimum(P - lo, hi - P) > margin, P, I
+
+
+def summation_order_margin(P):
+    """The margin of decidable_samples for short utterances: 4 (i + 1) 2^-53 P_i.  Any order of adding i + 1 positive fp64 terms lies within
+    (i + 1) 2^-53 P_i of the sequential sum (every partial sum is at most P_i, every addition rounds by at most 2^-53 of it); the factor 4
+    covers the oracle's own sequential roundings and the kernels' three-level scan together."""
+    P = np.asarray(P, dtype=np.float64)
+    return 4.0 * np.arange(1, P.shape[0] + 1, dtype=np.float64) * 2.0 ** -53 * P
+
+
+def sums_exact_in_any_order(inc):
+    """True where NO fp64 addition of these fp32 increments can round, in whatever order and grouping they are added: all of them are whole
+    multiples of q = the lowest set bit among them, so is every partial sum, and a multiple of q below 2^53 q is an fp64 number.  The drift
+    between two summation orders is then 0, not (i + 1) 2^-53 P_i.  It matters at these lengths: under a constant f0 the phase is
+    P_i = (i + 1) c exactly, which IS a rounding midpoint of fp32 for a few per cent of the i (3 c has 25 or 26 significant bits) - and both
+    sides round that tie to even.  A margin rule alone would call those samples, and every sample of an unvoiced tail that stands on one,
+    non-decidable."""
+    bits = np.asarray(inc, dtype=np.float32).reshape(-1).view(np.uint32).astype(np.int64)
+    exp, man = (bits >> 23) & 0xFF, bits & 0x7FFFFF
+    nz = (exp | man) != 0
+    if not nz.any():
+        return True
+    man = np.where(exp > 0, man | 0x800000, man)[nz]
+    e = np.maximum(exp[nz], 1) - 150                                          # value = man * 2^e
+    low = e + np.log2((man & -man).astype(np.float64)).astype(np.int64)       # exponent of the lowest set bit
+    total = float(np.asarray(inc, dtype=np.float64).sum())
+    return total < 2.0 ** (53 + int(low.min()))
+
+
+def decidable_short(inc):
+    """decidable_samples for the short utterances of test_gpu_front_dsp_edges.py: every sample where the sums are exact in any order,
+    else those further than summation_order_margin from a rounding midpoint -> (decidable, P, I)."""
+    _d, P, _I = decidable_samples(inc, 0.0)
+    dec, P, I = decidable_samples(inc, summation_order_margin(P))
+    if sums_exact_in_any_order(inc):
+        dec = np.ones_like(dec)
+    return dec, P, I
+
+
+def decode_lower_id_first(logits):
+    """PitchEstimator.decode restated with the kernels' tie rule (ties go to the lower class id): a stable descending sort, its first four
+    entries, softmax, the class frequencies 20 * 2^(id / 48) with the oracle's '<= 20 Hz -> 0' rule, the output gate.  Every operation after
+    the sort is the oracle's own (oracle.ref_cpu.pitch_decode), in its order and in the dtype of `logits` -> (f0 [B, 1, T], the value in
+    front of the output gate [B, 1, T], the four class ids [B, 4, T], tie_free [B, T]: the first five sorted logits strictly decrease)."""
+    import torch.nn.functional as F
+    srt = torch.sort(logits, dim=1, descending=True, stable=True)
+    top, ids = srt.values[:, :4], srt.indices[:, :4]
+    p = F.softmax(top, dim=1)
+    fr = 20.0 * (2 ** (ids.to(logits.dtype) / 48))
+    fr = torch.where(fr <= 20.0, torch.zeros_like(fr), fr)
+    raw = (p * fr).sum(dim=1, keepdim=True)
+    f0 = torch.where(raw <= 20.0, torch.zeros_like(raw), raw)
+    tie_free = (srt.values[:, :4] > srt.values[:, 1:5]).all(dim=1)
+    return f0, raw, ids, tie_free
+
+
+# the inputs of those two files, a function of the shape alone (both files, and both machines, build the same tensors)
+STFT_SHAPES = [(1, 3), (2, 4), (1, 7), (2, 8), (3, 9), (2, 12), (1, 17)]
+# the per-bin gate's factor over the oracle's worst bin: 2, except where a case is listed with its measured figures and the reason
+# (module docstring of test_gpu_front_dsp_edges.py, item 1); never above 4
+STFT_BIN_FACTOR = {(1, 3, "synth"): 4.0}
+ENERGY_LENGTHS = [128, 129, 191, 192, 193, 1437, 1438, 1439, 1440, 61920, 61921]
+DECODE_SHAPES = [(1, 1), (3, 21), (1, 64), (5, 13), (3, 43)]                  # B * T = 1, 63, 64, 65, 129
+DSP_SHAPES = [(1, 1), (2, 2), (1, 3), (3, 5), (2, 9), (1, 17)]
+F0_PATTERNS = ["unvoiced_first", "unvoiced_last", "voiced_first_only", "voiced_last_only", "exactly_20", "just_above_20", "all_zero", "800_hz"]
+
+
+def stft_edge_wave(kind, B, T):
+    """[B, 480 T].  'synth': synth.synth_wave (its first 1200 samples are silent).  'spikes': white noise with large isolated samples at
+    0, 1, L - 2 and L - 1, all four different, so that a reflection off by one sample changes the three frames that reflect."""
+    L = 480 * T
+    if kind == "synth":
+        return synth.synth_wave(B, L, seed=3000 + T)
+    g = torch.Generator().manual_seed(3100 + T)
+    wf = 0.1 * torch.randn(B, L, generator=g)
+    wf[:, 0], wf[:, 1], wf[:, L - 2], wf[:, L - 1] = 1.5, -2.0, 1.75, -1.25
+    return wf
+
+
+def energy_edge_wave(B, L):
+    g = torch.Generator().manual_seed(5000 + L)
+    wf = 0.3 * torch.randn(B, L, generator=g)
+    wf[:, 0] = -0.8
+    wf[:, L - 1] = 1.0 + 0.1 * torch.arange(B)
+    return wf
+
+
+def _decode_columns():
+    """name -> f(generator) -> [512] logits of one column"""
+    ids = torch.arange(512.0)
+
+    def prior(g):      # the synthetic checkpoint's prior: a parabola centred on class 150
+        return -2.0 * ((ids - 150.0) / 30.0) ** 2 + torch.randn(512, generator=g)
+
+    def low(g):
+        return -30.0 + torch.randn(512, generator=g)
+
+    def put(col, pairs):
+        for i, v in pairs:
+            col[i] = v
+        return col
+
+    def class0(g):     # class 0 (0 Hz) wins on part of the frames, as in the checkpoint
+        c = prior(g)
+        c[0] = c.max() + 1.0 + torch.rand(1, generator=g)[0]
+        return c
+
+    def best_511(g):
+        c = prior(g)
+        c[511] = c.max() + 2.0
+        return c
+
+    return {
+        "prior": prior,
+        "prior_class0": class0,
+        "tie_top_31_32": lambda g: put(low(g), [(31, 5.0), (32, 5.0), (100, 3.0), (200, 2.5)]),            # waves 0 | 1, both inside the top four
+        "tie_top_5_500": lambda g: put(low(g), [(500, 4.0), (5, 4.0), (250, 3.5), (251, 1.0)]),             # waves 0 | 15
+        "tie_4th_31_32": lambda g: put(low(g), [(100, 5.0), (200, 4.0), (300, 3.0), (32, 2.0), (31, 2.0)]),  # 31 is in, 32 is out
+        "tie_4th_5_500": lambda g: put(low(g), [(150, 5.0), (160, 4.5), (170, 4.0), (500, 3.25), (5, 3.25)]),
+        "tie_4th_three_way": lambda g: put(low(g), [(10, 3.0), (20, 2.5), (30, 2.0), (447, 1.0), (64, 1.0), (63, 1.0)]),      # waves 13 | 2 | 1: 63 is in
+        "all_equal": lambda g: torch.full((512,), 1.25),                                                    # classes 0 .. 3: 15.4 Hz, below the gate
+        "four_waves": lambda g: put(low(g), [(10, 4.0), (170, 3.5), (300, 3.0), (511, 2.5)]),               # waves 0, 5, 9, 15
+        "class0_alone": lambda g: put(-200.0 + torch.randn(512, generator=g), [(0, 10.0)]),                 # exactly 0
+        "best_511": best_511,
+        "two_finite": lambda g: put(torch.full((512,), float("-inf")), [(40, 1.0), (41, 0.5)]),
+        "two_finite_tied": lambda g: put(torch.full((512,), float("-inf")), [(480, 0.3), (7, 0.3)]),
+    }
+
+
+DECODE_SPECIALS = [k for k in _decode_columns() if not k.startswith("prior")]
+
+
+def decode_edge_logits(B, T, rot=0):
+    """([B, 512, T] fp32 logits, the column kinds in column order n = b T + t).  The first and the last len(DECODE_SPECIALS) columns are the
+    constructed ones, rotated by `rot` - the last workgroup's few columns (n = 64, n = 128) get them too -, the columns between are
+    prior-shaped random ones, every third with class 0 in front."""
+    cols, n, K = _decode_columns(), B * T, len(DECODE_SPECIALS)
+    g = torch.Generator().manual_seed(6000 + 7 * n + rot)
+    out, kinds = torch.empty(n, 512), []
+    for c in range(n):
+        if c < K or c >= n - K:
+            kind = DECODE_SPECIALS[(c + rot) % K]
+        else:
+            kind = "prior_class0" if c % 3 == 0 else "prior"
+        kinds.append(kind)
+        out[c] = cols[kind](g)
+    return out.view(B, T, 512).transpose(1, 2).contiguous(), kinds
+
+
+def dsp_edge_inputs(B, T):
+    """(amps [B, 15, T], kernel [B, 961, T], phases [B, 961, T] in [-pi, pi))"""
+    g = torch.Generator().manual_seed(4000 + T)
+    amps = 0.05 + 2.0 * torch.rand(B, 15, T, generator=g)
+    kern = 0.05 + torch.rand(B, 961, T, generator=g)
+    return amps, kern, synth.synth_angle(B, T, 4100 + T)
+
+
+def dsp_edge_f0(pattern, B, T):
+    """[B, 1, T] f0 as pitch_decode emits it (0 = unvoiced, else above 20 Hz), and the gate's own edge: exactly 20.0 is unvoiced, the next
+    float is voiced."""
+    g = torch.Generator().manual_seed(4200 + T)
+    base = 60.0 + 440.0 * torch.rand(B, 1, T, generator=g)
+    f0 = base.clone()
+    if pattern == "unvoiced_first":
+        f0[..., 0] = 0.0
+    elif pattern == "unvoiced_last":
+        f0[..., -1] = 0.0
+    elif pattern == "voiced_first_only":
+        f0 = torch.zeros_like(base)
+        f0[..., 0] = base[..., 0]
+    elif pattern == "voiced_last_only":
+        f0 = torch.zeros_like(base)
+        f0[..., -1] = base[..., -1]
+    elif pattern == "exactly_20":
+        f0[..., ::2] = 20.0
+    elif pattern == "just_above_20":
+        f0[..., ::2] = float(np.nextafter(np.float32(20.0), np.float32(np.inf)))
+    elif pattern == "all_zero":
+        f0 = torch.zeros_like(base)
+    elif pattern == "800_hz":
+        f0 = torch.full_like(base, 800.0)
+    else:
+        raise ValueError(pattern)
+    return f0
+
+
+def harmonic_increments(f0):
+    """The oracle's phase increments, op for op (oracle.ref_cpu.oscillate_harmonics): [B, 15, 480 T] fp32."""
+    import torch.nn.functional as F
+    mul = (torch.arange(15) + 1).view(1, -1, 1)
+    return (F.interpolate(f0, f0.shape[2] * 480, mode="linear") * mul) / 24000

@@ -9,7 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import rel_rms, rms, state_dicts
+from helpers import decidable_samples, rel_rms, rms, state_dicts
 from oracle import ref_cpu as R
 from tinyvc_amd import synth
 
@@ -82,13 +82,9 @@ def test_oscillator_and_noise_at_five_minutes_against_the_oracle():
         amp_i = F.interpolate(amps[b:b + 1], scale_factor=R.HOP, mode="linear")[0]
         for m in range(R.NUM_HARMONICS + 1):
             inc = (fs * (m + 1)) / R.SAMPLE_RATE
-            P = np.cumsum(inc.reshape(-1).numpy().astype(np.float64))
-            I = P.astype(np.float32)
+            decidable, _P, I = decidable_samples(inc.reshape(-1).numpy(), 1e-7)
             if m in (0, R.NUM_HARMONICS):                                      # the model of the oracle's cumsum: fp64 sequential, rounded once
                 assert np.array_equal(torch.cumsum(inc, dim=2).reshape(-1).numpy(), I)
-            lo = (I.astype(np.float64) + np.nextafter(I, np.float32(-np.inf)).astype(np.float64)) / 2
-            hi = (I.astype(np.float64) + np.nextafter(I, np.float32(np.inf)).astype(np.float64)) / 2
-            decidable = np.minimum(P - lo, hi - P) > 1e-7
             amp = amp_i[m].numpy()
             diff = np.abs(got[m].numpy().astype(np.float64) - ref[m].numpy().astype(np.float64))
             bad = diff > 2.0 ** -21 * np.abs(amp) + 1e-30
