@@ -165,7 +165,7 @@ int tvc_knn_match_f32(tvc_ctx* ctx, void* stream, const float* src, const float*
 
 /* match_features with the reference's full signature (module/tinyvc/feature_retrieval.py:15-33): the k = 1 ... 8 nearest index vectors of
  * every source frame under metric 0 = 'cos', 1 = 'IP' (inner product), 2 = 'L2' (negative Euclidean distance), out = the mean of the k RAW
- * vectors (alpha blending is the caller's one-liner).  src [B,768,T]; index [768,N] = the raw [1,768,N] tensor of index.pt (no prepared
+ * vectors (alpha blending is the caller's one-liner here; the inference path has it inside the call: tvc_*_alpha_f32).  src [B,768,T]; index [768,N] = the raw [1,768,N] tensor of index.pt (no prepared
  * blob: this is not the inference path - that asks for k = 4, 'cos' and runs tvc_knn_match_f32 - but every other argument the reference
  * accepts, in plain fp32 on the raw vectors); out [B,768,T]; idx_out [B,T,k] int64 and sim_out [B,T,k] (nullable) = torch.topk's indices
  * and values in rank order, equal similarities by lower index.  N >= k.  Workspace: B * T * k * 8 bytes + 4096 when idx_out is NULL. */
@@ -448,6 +448,46 @@ int tvc_convert_track_f32(tvc_ctx* ctx, void* stream, const float* wav, const fl
                           const float* weights, const float* target_f0, int start, int n, int W, int min_voiced, float slew, float* ring,
                           int64_t* count, float* auto_shift, float pitch_shift, const float* pitch_shifts, float* shift_out,
                           const float* noise_angle, uint64_t seed, float* wave, int B, int64_t L, void* ws, size_t ws_bytes);
+
+/* alpha: a share of the source's own content features ------------------------------------------- */
+/* The reference's match_features(source, reference, k=4, alpha=0.0) ends in `result * (1 - alpha) + input_data * alpha`
+ * (feature_retrieval.py:33): the share of the source's own features that survives the match (RVC's "index rate" is its complement).  In the
+ * fused conversion the encoder's output and the matched tensor exist only inside the call, so the blend happens there, per row:
+ *   - alpha: a DEVICE array of B floats in the caller's row order, read when the kernels run (the host never reads it): a captured graph
+ *     follows an in-place change without a new capture.  Neither clamped nor normalised: any finite value is legal, values below 0 or above 1
+ *     extrapolate, a non-finite value gives non-finite output.  alpha == NULL is legal and IS the sibling call: the same launches, the same
+ *     bits (tvc_knn_match_multi_f32 / _blend_f32; tvc_convert_multi / _blend / _auto / _track_f32 and their ragged forms).
+ *   - every element of a query column of row b, with a = alpha[b], mu = what the alpha-less call writes there (the mean of the four rows, or
+ *     the accumulated blend) and src = the same element of the tensor that was searched:
+ *         keep = 1 - a;   out = mu * keep + src * a
+ *     three separate fp32 roundings after the subtraction, no fused multiply-add: the bits of torch's eager `mu * (1 - a_t) + src * a_t`.
+ *     The indices found do not depend on alpha.  One launch: the alpha forms of the merge + gather kernels read src where they store.
+ *   - the decoder's content bound of row b becomes |keep| * (the alpha-less call's bound: the blob's |max|, or the blend bound) + |a| * (the
+ *     measured |max| of utterance b's own encoder output; per utterance in a ragged batch), products and sum rounded separately.  At a = 0
+ *     it is the alpha-less bound exactly: such a row has the scales, and the bits, of the alpha-less call.
+ *   - per-row contract: row b is bit-identical to its own B = 1 call with alpha[b].
+ * tvc_knn_match_alpha_f32, the stage call: the table form - prepared / N HOST arrays [B][M], weights the DEVICE array [B][M], or NULL with
+ * M = 1 (one index per row) -, out [B,768,T] (another buffer than src), idx_out (nullable) [M][B][T][4] as the blend call's.
+ * tvc_convert_alpha_f32: tvc_convert_track_f32's arguments plus alpha (behind weights).  ring == NULL: no tracker (start, n, W, min_voiced,
+ * slew, count, auto_shift are not looked at) - tvc_convert_auto_f32's behaviour; target_f0 == NULL as well: plain host shifts (shift_out is
+ * not written) - tvc_convert_multi_f32's / _blend_f32's.  tvc_convert_ragged_alpha_f32: tvc_convert_ragged_auto_f32's arguments plus alpha,
+ * target_f0 nullable in the same way.  Every host check runs before any device work, as in the siblings; all three are capturable under
+ * their rules.  Workspace: tvc_workspace_bytes_alpha / _ragged_alpha (N: the host table of B * M sizes; enough with or without target_f0,
+ * a tracker or alpha). */
+int tvc_knn_match_alpha_f32(tvc_ctx* ctx, void* stream, const float* src, const float* const* prepared, const int64_t* N, int M,
+                            const float* weights, const float* alpha, float* out, int64_t* idx_out, int B, int T, void* ws,
+                            size_t ws_bytes);
+int tvc_workspace_bytes_alpha(tvc_ctx* ctx, int B, int64_t L, const int64_t* N, int M, size_t* out_bytes);
+int tvc_convert_alpha_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M,
+                          const float* weights, const float* alpha, const float* target_f0, int start, int n, int W, int min_voiced,
+                          float slew, float* ring, int64_t* count, float* auto_shift, float pitch_shift, const float* pitch_shifts,
+                          float* shift_out, const float* noise_angle, uint64_t seed, float* wave, int B, int64_t L, void* ws,
+                          size_t ws_bytes);
+int tvc_workspace_bytes_ragged_alpha(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, const int64_t* N, int M, size_t* out_bytes);
+int tvc_convert_ragged_alpha_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens,
+                                 const float* const* prepared, const int64_t* N, int M, const float* weights, const float* alpha,
+                                 const float* target_f0, float pitch_shift, const float* pitch_shifts, float* shift_out,
+                                 const float* noise_angle, uint64_t seed, float* wave, int B, void* ws, size_t ws_bytes);
 
 /* streaming tail -------------------------------------------------------------------------- */
 /* StreamInfer.audio_callback after convert (reference module/infer/stream.py:74-95), batched over

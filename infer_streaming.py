@@ -46,7 +46,8 @@ from infer import load_generator, load_target
 from tinyvc_amd.engine import sola_geometry, stream_resample_geometry
 from tinyvc_amd.module.infer import BatchedStreamInfer, StreamDoor
 from tinyvc_amd.module.infer.stream import check_window
-from tinyvc_amd.module.tinyvc.feature_retrieval import PitchTrack, add_blend_argument, pitch_register, semitones_between
+from tinyvc_amd.module.tinyvc.feature_retrieval import (PitchTrack, add_alpha_argument, add_blend_argument, alpha_keywords, pitch_register,
+                                                        semitones_between)
 
 FRAMES_PER_SECOND = 50      # 24 kHz / 480 samples
 
@@ -70,6 +71,7 @@ def build_parser():
     p.add_argument("--auto-pitch-warmup", default=0.5, type=float, metavar="SECONDS", help="voiced speech heard before the automatic shift starts")
     p.add_argument("--auto-pitch-slew", default=6.0, type=float, metavar="SEMITONES_PER_SECOND", help="how fast the automatic shift may move; 0 = unlimited")
     add_blend_argument(p)      # --blend PATH=W [PATH=W ...] -> args.blend = (paths, weights)
+    add_alpha_argument(p)      # --alpha A: keep that share of every stream's own content features in the match (stream.alpha, live on the device)
     p.add_argument("-c", "--chunk", default=1920, type=int)
     p.add_argument("-e", "--extra", default=3840, type=int)
     p.add_argument("-d", "--device", default="cuda")
@@ -198,9 +200,10 @@ def main(argv=None):
     if block is not None:
         print(f"Resampling {rate} Hz <-> 24000 Hz on the device: {args.chunk}-sample blocks are {block} at the model's rate; "
               f"the two filters add {door.latency_seconds * 1e3:.2f} ms of latency")
+    alpha_kw = alpha_keywords(args, "infer_streaming.py")      # {} without --alpha: the stream is then built as it has always been
     stream = BatchedStreamInfer(gen, n_streams=S, pitch_shift=pitch_shift, block_size=door.block_size, device=device, extra_size=args.extra,
                                 f0_estimation=args.f0_estimation, door=door, auto_pitch=True if track is not None else None, pitch_track=track,
-                                crossfade_size=args.crossfade, sola_search_size=args.sola_search, last_delay_size=args.lookahead)
+                                crossfade_size=args.crossfade, sola_search_size=args.sola_search, last_delay_size=args.lookahead, **alpha_kw)
     lo, hi = stream.latency_seconds
     print(f"Latency {lo * 1e3:.1f} to {hi * 1e3:.1f} ms (cross-fade {args.crossfade} + look-ahead {args.lookahead} + lag 0 .. {args.sola_search} samples at 24 kHz"
           f"{', and the resampling filters' if block is not None else ''}) plus the {door.block_size / 24000 * 1e3:.0f} ms block")

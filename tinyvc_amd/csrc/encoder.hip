@@ -467,4 +467,8 @@ int run_encoder(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* spec, float* s
     return launch_check(ctx, "encoder");
 }
 
+// slot[utterance] = the |max| of its own ssl (slot zeroed on this stream): the source's part of an alpha call's content bound.  One pass
+// over ssl (run_amax_rows; a ragged batch per utterance through its tables).
+int run_ssl_amax(tvc_ctx* ctx, hipStream_t s, const float* ssl, int B, int T, float* slot) { return run_amax_rows(ctx, s, ssl, B, kSslDim, T, slot); }
+
 }  // namespace tvc

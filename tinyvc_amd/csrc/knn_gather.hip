@@ -1,5 +1,6 @@
 // From the search's top-4 lists (knn.hip, knn_search.h) to results: the merge + gather of the whole-index match (one index, one per
-// row, a weighted blend), the index-sharded route's three steps (merge, slot gather, finish) and the |max| bounds of `matched`.
+// row, a weighted blend; each also in its alpha form, which keeps a share of the source), the index-sharded route's three steps (merge, slot
+// gather, finish) and the |max| bounds of `matched`.
 // Every route averages the four rows with mean4 and stores through store_tile_along_t: equal lists give equal bits on all of them.
 #include "knn_blob.h"
 #include "knn_search.h"
@@ -67,22 +68,58 @@ __device__ __forceinline__ void store_tile_along_t(const float (&tile)[32][193],
     }
 }
 
+// The alpha forms (tvc_*_alpha_f32) keep a share of the source's own features: a = alpha[row of the column] (the caller's DEVICE array, read
+// here: a captured graph replays with whatever it holds then), and every element leaves as
+//   out = mu * (1 - a) + src * a      (__fsub_rn, two __fmul_rn, __fadd_rn: torch's eager mu * (1 - a_t) + src * a_t on fp32 tensors)
+// with mu what the alpha-less kernel stores there.  src has out's layout, so it is read in the store phase at the address of the store (lanes
+// along t); a tile's 32 columns may straddle rows with different alpha.  The row of a column: its batch row, or rowmap[col2b[column]] in a
+// ragged batch (ragged.h) - the blend kernel's weight row.
+struct AlphaIn {
+    const float* alpha;      // [rows]
+    const float* src;        // [B][768][T]: the queries that were searched (another buffer than `out`)
+    const int* col2b;        // ragged batch: column -> utterance, utterance -> caller's row; else nullptr
+    const int* rowmap;
+};
+__device__ __forceinline__ float alpha_of_column(const AlphaIn& al, int nc, int T) { return al.alpha[al.col2b ? al.rowmap[al.col2b[nc]] : nc / T]; }
+// store_tile_along_t with the source's share a of this thread's column mixed in
+__device__ __forceinline__ void store_tile_along_t_alpha(const float (&tile)[32][193], float* __restrict__ out, const AlphaIn& al, float a, int n0,
+                                                         int ncols, int T, int kc) {
+    const float* __restrict__ src = al.src;
+    const float keep = __fsub_rn(1.f, a);
+    for (int kk = threadIdx.x >> 5; kk < 192; kk += 8) {
+        const int q = threadIdx.x & 31;
+        const int n = n0 + q;
+        if (n < ncols) {
+            const int b = n / T, t = n - b * T;
+            const long o = ((long)b * KD + kc + kk) * T + t;
+            out[o] = __fadd_rn(__fmul_rn(tile[q][kk], keep), __fmul_rn(src[o], a));
+        }
+    }
+}
+
 // One workgroup = 32 consecutive query columns: merge split candidates -> top-4, write indices,
 // gather the 4 raw rows per query (coalesced along the feature axis), average, and write
 // out[b][k][t] through an LDS transpose so stores run along t.  Every query takes its segment's blob and lists (col2seg: several
 // segments; the 32 columns may straddle a segment boundary).  MULTI = false: one segment, whose blob the gather reads as a uniform value.
-template <bool MULTI>
+// A... = AlphaIn: the alpha form (an instantiation with one more argument); empty: the kernel as it has always been, argument for argument.
+template <bool MULTI, class... A>
 static __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
                                                                       const KnnSegs segs, const int* __restrict__ col2seg, int ncols, int T,
                                                                       float* __restrict__ out, int64_t* __restrict__ idx_out,
                                                                       const float* __restrict__ rv, const int* __restrict__ ri,
-                                                                      const int* __restrict__ flags) {
+                                                                      const int* __restrict__ flags, const A... al) {
+    constexpr bool ALPHA = sizeof...(A) > 0;
     __shared__ int sel[32][4];
     __shared__ float tile[32][193];
     __shared__ const float* sblob[32];
     __shared__ int skind[32], sN[32];
     const int tid = threadIdx.x;
     const int n0 = blockIdx.x * 32;
+    float a = 0.f;
+    if constexpr (ALPHA) {      // this thread's column in the store phase (a column past the end reads the last column's row: never stored)
+        const int n = n0 + (tid & 31);
+        a = alpha_of_column(al..., n < ncols ? n : ncols - 1, T);
+    }
     if (tid < 32) {
         const int n = n0 + tid;
         const int nc = n < ncols ? n : ncols - 1;      // (a column past the end gathers row 0 of the last column's blob: never stored)
@@ -110,7 +147,8 @@ static __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const floa
                 for (int u = 0; u < 3; ++u) tile[q0 + 4 * qq][lane + 64 * u] = mean4(r[qq][u][0], r[qq][u][1], r[qq][u][2], r[qq][u][3]);
         }
         __syncthreads();
-        store_tile_along_t(tile, out, n0, ncols, T, kc);
+        if constexpr (ALPHA) store_tile_along_t_alpha(tile, out, al..., a, n0, ncols, T, kc);
+        else store_tile_along_t(tile, out, n0, ncols, T, kc);
         __syncthreads();
     }
 }
@@ -125,13 +163,16 @@ static __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const floa
 // in registers - products and sums rounded separately (__fmul_rn / __fadd_rn), in term order - so the per-term matched tensors never exist
 // in memory.  One LDS transpose, stores along t.  weights [rows][M] is the caller's DEVICE array, read here: a captured graph replays with
 // whatever it holds then.  The weight row of a column is its batch row, or rowmap[col2b[column]] in a ragged batch (ragged.h).
+// A... = AlphaIn: the alpha form, as above - the accumulated blend is the mu of its definition, alpha's row the weights'.
 constexpr int BLEND_MAX = TVC_BLEND_MAX;
+template <class... A>
 static __global__ __launch_bounds__(256) void knn_merge_blend_gather_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
                                                                             const KnnSegs segs, const int* __restrict__ col2seg, int ncols, int T,
                                                                             int M, const float* __restrict__ weights, const int* __restrict__ col2b,
                                                                             const int* __restrict__ rowmap, float* __restrict__ out,
                                                                             int64_t* __restrict__ idx_out, const float* __restrict__ rv,
-                                                                            const int* __restrict__ ri, const int* __restrict__ flags) {
+                                                                            const int* __restrict__ ri, const int* __restrict__ flags, const A... al) {
+    constexpr bool ALPHA = sizeof...(A) > 0;
     __shared__ int sel[BLEND_MAX][32][4];
     __shared__ float tile[32][193];
     __shared__ const float* sblob[BLEND_MAX][32];
@@ -139,6 +180,11 @@ static __global__ __launch_bounds__(256) void knn_merge_blend_gather_kernel(cons
     __shared__ float sw[BLEND_MAX][32];
     const int tid = threadIdx.x;
     const int n0 = blockIdx.x * 32;
+    float a = 0.f;
+    if constexpr (ALPHA) {      // this thread's column in the store phase
+        const int n = n0 + (tid & 31);
+        a = alpha_of_column(al..., n < ncols ? n : ncols - 1, T);
+    }
     if (tid < 32 * M) {
         const int m = tid >> 5, q = tid & 31;
         const int n = n0 + q;
@@ -180,9 +226,28 @@ static __global__ __launch_bounds__(256) void knn_merge_blend_gather_kernel(cons
                 for (int u = 0; u < 3; ++u) tile[q0 + 4 * qq][lane + 64 * u] = acc[qq][u];
         }
         __syncthreads();
-        store_tile_along_t(tile, out, n0, ncols, T, kc);
+        if constexpr (ALPHA) store_tile_along_t_alpha(tile, out, al..., a, n0, ncols, T, kc);
+        else store_tile_along_t(tile, out, n0, ncols, T, kc);
         __syncthreads();
     }
+}
+
+// out[i] = |1 - a| * idx_bound[i * stride] + |a| * srcmax[i], a = alpha[row[i]] (row == nullptr: i), products and sum rounded separately: the
+// bound of utterance i's content in an alpha call (|mu| <= the alpha-less call's bound, |src| <= the measured |max| of its own ssl), the
+// decoder's content bound there.  At a = 0 it is idx_bound exactly: such a row keeps the alpha-less call's scales.
+static __global__ __launch_bounds__(256) void alpha_bound_kernel(const float* __restrict__ alpha, const int* __restrict__ row,
+                                                                 const float* __restrict__ idx_bound, int stride, const float* __restrict__ srcmax,
+                                                                 float* __restrict__ out, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float a = alpha[row ? row[i] : i];
+    out[i] = __fadd_rn(__fmul_rn(fabsf(__fsub_rn(1.f, a)), idx_bound[(long)i * stride]), __fmul_rn(fabsf(a), srcmax[i]));
+}
+int run_knn_alpha_bound(tvc_ctx* ctx, hipStream_t s, const float* alpha, const float* idx_bound, int stride, const float* srcmax, float* out, int n) {
+    const RagHost* h = ctx->rag;
+    hipLaunchKernelGGL(alpha_bound_kernel, dim3((n + 255) / 256), dim3(256), 0, s, alpha, h ? (const int*)h->d_row : (const int*)nullptr, idx_bound, stride, srcmax,
+                       out, n);
+    return launch_check(ctx, "knn_alpha_bound");
 }
 
 // out[i] = sum_m |w[row[i]][m]| * (the |max| of blob (i, m)), in term order, products and sums rounded separately: the bound of row i's blended
@@ -311,12 +376,21 @@ int run_knn_finish(tvc_ctx* ctx, hipStream_t s, const float* slots, float* out, 
     return launch_check(ctx, "knn_finish");
 }
 
-int run_knn_segs(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const KnnSegIn* in, int nin, float* out, int64_t* idx_out, int B, int T) {
+int run_knn_segs(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const KnnSegIn* in, int nin, float* out, int64_t* idx_out, int B, int T,
+                 const float* alpha) {
     KnnCall c;
     TVC_CHECK(knn_call_plan(ctx, in, nin, B * T, &c));
     KnnLists L;
     TVC_CHECK(knn_candidates(ctx, s, ws, src, c, B, T, &L));
     if (ws.dry) return 0;
+    if (alpha) {      // the alpha form: the same lists, the source's share mixed in at the store (a ragged batch finds alpha's row through its tables)
+        const RagHost* h = ctx->rag;
+        const AlphaIn al{alpha, src, h ? (const int*)h->d_col2b : (const int*)nullptr, h ? (const int*)h->d_row : (const int*)nullptr};
+        const auto akernel = L.col2seg ? knn_merge_gather_kernel<true, AlphaIn> : knn_merge_gather_kernel<false, AlphaIn>;
+        hipLaunchKernelGGL(akernel, dim3((c.ncols + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)L.col2seg, c.ncols, T, out, idx_out, L.rv, L.ri,
+                           (const int*)L.flag, al);
+        return launch_check(ctx, "knn_match_alpha");
+    }
     const auto kernel = L.col2seg ? knn_merge_gather_kernel<true> : knn_merge_gather_kernel<false>;      // several segments : one (no table read)
     hipLaunchKernelGGL(kernel, dim3((c.ncols + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)L.col2seg, c.ncols, T, out, idx_out, L.rv, L.ri,
                        (const int*)L.flag);
@@ -327,14 +401,22 @@ int run_knn_segs(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const Kn
 // knn_candidates walk - every pass one launch, as run_knn_segs -, then the blend gather.  idx_out (nullable): [M][B][T][4].  A ragged batch
 // (ctx->rag: B = 1, T = all its frames) finds a column's weight row through the batch's tables.
 int run_knn_blend(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const KnnSegIn* in, int nin, int M, const float* weights, float* out,
-                  int64_t* idx_out, int B, int T) {
+                  int64_t* idx_out, int B, int T, const float* alpha) {
     KnnCall c;
     TVC_CHECK(knn_call_plan(ctx, in, nin, M * B * T, &c));
     KnnLists L;
     TVC_CHECK(knn_candidates(ctx, s, ws, src, c, M * B, T, &L, B));
     if (ws.dry) return 0;
     const RagHost* h = ctx->rag;
-    hipLaunchKernelGGL(knn_merge_blend_gather_kernel, dim3((B * T + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)L.col2seg, B * T, T, M, weights,
+    if (alpha) {
+        const int* col2b = h ? (const int*)h->d_col2b : nullptr;
+        const int* rowmap = h ? (const int*)h->d_row : nullptr;
+        const AlphaIn al{alpha, src, col2b, rowmap};
+        hipLaunchKernelGGL(knn_merge_blend_gather_kernel<AlphaIn>, dim3((B * T + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)L.col2seg, B * T, T, M,
+                           weights, col2b, rowmap, out, idx_out, L.rv, L.ri, (const int*)L.flag, al);
+        return launch_check(ctx, "knn_match_blend_alpha");
+    }
+    hipLaunchKernelGGL(knn_merge_blend_gather_kernel<>, dim3((B * T + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)L.col2seg, B * T, T, M, weights,
                        h ? (const int*)h->d_col2b : (const int*)nullptr, h ? (const int*)h->d_row : (const int*)nullptr, out, idx_out, L.rv, L.ri,
                        (const int*)L.flag);
     return launch_check(ctx, "knn_match_blend");

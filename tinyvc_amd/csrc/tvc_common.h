@@ -351,14 +351,21 @@ struct KnnSegIn {
     int64_t N;
     int col0, ncols;
 };
-int run_knn_segs(tvc_ctx*, hipStream_t, Ws&, const float* src, const KnnSegIn* in, int nin, float* out, int64_t* idx_out, int B, int T);
+// alpha (optional, both drivers): the caller's DEVICE array [rows] of the source's own share - out = mu * (1 - a) + src * a with mu the alpha-less
+// result (knn_gather.hip); nullptr launches exactly what the call without it launches
+int run_knn_segs(tvc_ctx*, hipStream_t, Ws&, const float* src, const KnnSegIn* in, int nin, float* out, int64_t* idx_out, int B, int T,
+                 const float* alpha = nullptr);
 // a weighted blend of M indices per row (knn_gather.hip): in[] = the (term, row) runs over M * B * T VIRTUAL query columns, term-major - term m's
 // search of real column n is column m * B * T + n -, weights = the caller's device array [rows][M] (read by the kernels, never by the host),
 // out [B][768][T] = w_0 * mu_0 + ... in term order, idx_out (nullable) [M][B][T][4]
 int run_knn_blend(tvc_ctx*, hipStream_t, Ws&, const float* src, const KnnSegIn* in, int nin, int M, const float* weights, float* out, int64_t* idx_out,
-                  int B, int T);
+                  int B, int T, const float* alpha = nullptr);
 // out[i] = sum_m |weights[rows[i]][m]| * *blob_amax(blobs[i * M + m]): the bound of row i's blended content
 int run_knn_blend_bound(tvc_ctx*, hipStream_t, const std::vector<const float*>& blobs, const std::vector<int>& rows, int M, const float* weights, float* out);
+// the content bound of an alpha call: out[i] = |1 - a| * idx_bound[i * stride] + |a| * srcmax[i] for utterance i < n, a = alpha[its row]
+int run_knn_alpha_bound(tvc_ctx*, hipStream_t, const float* alpha, const float* idx_bound, int stride, const float* srcmax, float* out, int n);
+// slot[utterance] = max |ssl| of that utterance (slot already zeroed on this stream; encoder.hip)
+int run_ssl_amax(tvc_ctx*, hipStream_t, const float* ssl, int B, int T, float* slot);
 
 // ---- one conversion, as the entries describe it to convert_impl (api.hip) and to the ragged batch loop (ragged.hip) -----------
 // What the rows of a call search: ONE prepared index, or host tables of one per row of the caller's batch (tvc_*_multi) - never both.
@@ -405,6 +412,9 @@ struct ConvertCall {
     // tvc_convert_track_f32 (equal lengths only): the register is the stream's history, not the call's own rows - run_pitch_track takes
     // run_pitch_match's place
     const PitchTrackState* track = nullptr;
+    // tvc_convert_*alpha_f32: alpha (device, one fp32 per caller's row, read when the kernels run) keeps that share of the row's own content
+    // features - matched = mu * (1 - a) + ssl * a - and the decoder's content bound becomes |1 - a| * (the index's) + |a| * max |ssl|
+    const float* alpha = nullptr;
 };
 // Generator.convert over c.B rows of c.L samples (c.lens is not looked at: a ragged call reaches this through convert_ragged_batches,
 // one batch at a time as ONE row with ctx->rag set, ragged.h)

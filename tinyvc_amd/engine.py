@@ -70,11 +70,14 @@ _CONVERT = {
     ("auto", False): ("tvc_workspace_bytes_auto", "tvc_convert_auto_f32"),
     ("auto", True): ("tvc_workspace_bytes_ragged_auto", "tvc_convert_ragged_auto_f32"),
     ("track", False): ("tvc_workspace_bytes_auto", "tvc_convert_track_f32"),      # streams advance in lock step: no ragged form
+    ("alpha", False): ("tvc_workspace_bytes_alpha", "tvc_convert_alpha_f32"),      # any table / blend call, with or without auto pitch and a tracker, + alpha
+    ("alpha", True): ("tvc_workspace_bytes_ragged_alpha", "tvc_convert_ragged_alpha_f32"),
 }
 _MATCH = {
     "shared": ("tvc_workspace_bytes", "tvc_knn_match_f32"),
     "table": ("tvc_workspace_bytes_multi", "tvc_knn_match_multi_f32"),
     "blend": ("tvc_workspace_bytes_blend", "tvc_knn_match_blend_f32"),
+    "alpha": ("tvc_workspace_bytes_alpha", "tvc_knn_match_alpha_f32"),
 }
 
 
@@ -435,16 +438,26 @@ class Engine:
             raise ValueError(f"target_f0 must be a contiguous fp32 [B = {B}] tensor on the device, got {tuple(target_f0.shape)} {target_f0.dtype}")
         return target_f0
 
+    def _alpha(self, alpha, B):
+        """the source's share of every row: a contiguous fp32 [B] tensor on this device, used in place (the kernels read it when they run) -
+        anything else is refused here, never copied"""
+        if not isinstance(alpha, torch.Tensor):
+            raise TypeError(f"alpha must be a torch.Tensor on the device (a contiguous fp32 [B = {B}]), got {type(alpha).__name__}")
+        _check_dev(alpha, "alpha", self.device)
+        if alpha.dtype != _F32 or alpha.dim() != 1 or alpha.shape[0] != B or not alpha.is_contiguous():
+            raise ValueError(f"alpha must be a contiguous fp32 [B = {B}] tensor on the device, got {tuple(alpha.shape)} {alpha.dtype}")
+        return alpha
+
     def _index_args(self, form, prepared, Ns, weights, B):
         """The index of a call, checked on the host -> (what the entry takes for it, what its workspace query takes for it).  shared:
         (prepared, Ns) = one blob and its N; table: one blob and N per row; blend: weights [B, M] on the device, prepared / Ns row-major
-        [B * M]; auto: the blend form, or with weights None the table form as M = 1."""
+        [B * M]; auto, track, alpha: the blend form, or with weights None the table form as M = 1."""
         if form == "shared":
             return (_ptr(prepared), Ns), (int(max(Ns, 4)),)
         if form == "table":
             blobs, ns = self._table(prepared, Ns, B)
             return (blobs, ns), (ns,)
-        if form in ("auto", "track") and weights is None:
+        if form in ("auto", "track", "alpha") and weights is None:
             blobs, ns = self._table(prepared, Ns, B)
             return (blobs, ns, 1, None), (ns, 1)
         blobs, ns, M = self._blend_args(prepared, Ns, weights, B)
@@ -466,14 +479,17 @@ class Engine:
         return wav, B, L
 
     # ---- kNN match: one driver, the public forms forward to it ----
-    def _match(self, form, src, prepared, Ns, weights=None, want_indices=False):
+    def _match(self, form, src, prepared, Ns, weights=None, want_indices=False, alpha=None):
         """src [B, 768, T] matched against the index (`form`, prepared, Ns, weights: _index_args) -> matched [B, 768, T] (, indices [B, T, 4];
-        [M, B, T, 4] for a blend: each term's own search)."""
+        [M, B, T, 4] for a blend: each term's own search).  form "alpha": the table (weights None) or blend form, and out = matched *
+        (1 - alpha[b]) + src * alpha[b] (alpha: _alpha; indices always [M, B, T, 4])."""
         src = _prep(src, "source", self.device)
         B, C, T = src.shape
         if C != spec.SSL_DIM:
             raise ValueError(f"source must have {spec.SSL_DIM} channels")
         index, sized = self._index_args(form, prepared, Ns, weights, B)
+        if form == "alpha":
+            index += (_ptr(self._alpha(alpha, B)),)
         out = torch.empty_like(src)
         terms = sized[1:]      # (M,) for a blend, else ()
         idx = torch.empty(*terms, B, T, 4, dtype=torch.int64, device=self.device) if want_indices else None
@@ -495,6 +511,12 @@ class Engine:
         w_0 * match_0 + w_1 * match_1 + ... in term order (, indices [M, B, T, 4]: each term's own search): tvc_knn_match_blend_f32."""
         return self._match("blend", src, prepared, Ns, weights, want_indices)
 
+    def knn_match_alpha(self, src, prepared, Ns, alpha, weights=None, want_indices=False):
+        """knn_match_multi (weights None: prepared / Ns one per row) or knn_match_blend (weights [B, M]) keeping a share of the source:
+        out = matched * (1 - alpha[b]) + src * alpha[b], three separate fp32 roundings, alpha a contiguous fp32 [B] device tensor read when
+        the kernel runs (, indices [M, B, T, 4], M = 1 without weights: what the alpha-less call finds): tvc_knn_match_alpha_f32."""
+        return self._match("alpha", src, prepared, Ns, weights, want_indices, alpha)
+
     # ---- convert: one driver, the eight public forms forward to it ----
     def _track_args(self, track, S, T):
         """a PitchTrack's share of a call over S streams of T frames, checked on the host: (start, n, W, min_voiced, slew, ring, count, auto)"""
@@ -509,9 +531,11 @@ class Engine:
         return (start, n, track.window_frames, track.min_voiced, track.slew, _ptr(track.ring), _ptr(track.count), _ptr(track.auto))
 
     def _convert(self, form, wav, prepared, Ns, pitch_shift, noise_angle=None, lengths=None, weights=None, target_f0=None, out=None, shift_out=None,
-                 track=None):
+                 track=None, alpha=None):
         """wav [B, L] converted toward the index (`form`, prepared, Ns, weights: _index_args) -> wave [B, L]; form "auto" / "track" ->
         (wave, shifts [B]).  "track": "auto" with the register taken from `track` (a PitchTrack: the streams' history), equal lengths only.
+        "alpha": the table / blend call keeping the share alpha[b] of row b's own content features (alpha: _alpha); with target_f0 it is the
+        "auto" call (-> (wave, shifts)), with `track` as well the "track" call.
         lengths: a ragged batch (row b holds an utterance of lengths[b] samples, a multiple of 480, zero-padded behind it; every utterance
         is converted over its OWN length).  pitch_shift: a float, or one per row for every form but "shared".  Every host check comes
         first, then the noise draw (which advances torch's generator), then device work: a refused call leaves no trace."""
@@ -519,10 +543,17 @@ class Engine:
         wav, B, L = self._rows(wav, ragged)
         lens = (self._lens(lengths, B),) if ragged else ()
         index, sized = self._index_args(form, prepared, Ns, weights, B)
-        if ragged and form == "track":
+        if ragged and (form == "track" or track is not None):
             raise ValueError("track: streams advance in lock step, there is no ragged form")
         found = form in ("auto", "track")      # the shifts are found on the device: pitch_shift is the offset, the applied shifts come back
-        if found:
+        if form == "alpha":      # the table / blend call with or without target registers (and, equal lengths, a tracker), plus the source's share
+            found = target_f0 is not None
+            if track is not None and not found:
+                raise ValueError("track needs target_f0: the tracker finds the register the automatic shift starts from")
+            index += (_ptr(self._alpha(alpha, B)), _ptr(self._target_f0(target_f0, B)) if found else None)
+            if not ragged:
+                index += self._track_args(track, B, L // spec.HOP) if track is not None else (0, 0, 0, 0, 0.0, None, None, None)
+        elif found:
             index += (_ptr(self._target_f0(target_f0, B)),)
         if form == "track":
             index += self._track_args(track, B, L // spec.HOP)
@@ -535,6 +566,8 @@ class Engine:
         if found:
             sh = shift_out if shift_out is not None else torch.empty(B, dtype=_F32, device=self.device)
             shift_args += (_ptr(sh),)
+        elif form == "alpha":
+            shift_args += (None,)
         query, entry = _CONVERT[form, ragged]
         p, n = self._query_ws(query, B, L, *lens, *sized)
         head, tail = ((_ptr(wav), L, *lens), (B, p, n)) if ragged else ((_ptr(wav),), (B, L, p, n))

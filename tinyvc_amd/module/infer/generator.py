@@ -6,8 +6,8 @@ from .. import utils
 from ...engine import pitch_shifts
 from .._base import HipModule
 from ..tinyvc import Decoder, Encoder
-from ..tinyvc.feature_retrieval import (check_blend, check_references, prepare_reference, prepare_references, resolve_auto_pitch, target_form,
-                                        target_registers)
+from ..tinyvc.feature_retrieval import (alpha_rows, check_blend, check_references, prepare_reference, prepare_references, resolve_alpha,
+                                        resolve_auto_pitch, target_form, target_registers)
 
 
 def _padded_lengths(lengths, B, L):
@@ -54,7 +54,7 @@ class Generator(HipModule):
 
     @torch.no_grad()
     def convert(self, wf, tgt, pitch_shift, f0_estimation="default", device=None, noise_angle=None, lengths=None, auto_pitch=None,
-                return_shift=False, track=None):
+                return_shift=False, track=None, alpha=None):
         """generator.py:26-34: wf [B, L], tgt [1 or B, 768, N] -> converted waveform [B, L'] (L' = L
         padded to a multiple of 480).  `f0_estimation` / `device` are accepted and ignored exactly as
         in the reference.  `noise_angle` [B,961,T] (extension) injects the decoder's noise phases;
@@ -77,7 +77,11 @@ class Generator(HipModule):
         `return_shift=True` -> (wave, shifts [B] on the device: the semitones applied to each row).
         `track` (extension, with auto_pitch): a feature_retrieval.PitchTrack of B streams - the register each row is moved FROM is then the
         lower median of the stream's history (the tracker's ring on the device, fed by columns [T - lag_frames - new_frames, T - lag_frames)
-        of this call's f0), slew-limited, instead of the median of the call's own rows (tvc_convert_track_f32; equal lengths only)."""
+        of this call's f0), slew-limited, instead of the median of the call's own rows (tvc_convert_track_f32; equal lengths only).
+        `alpha` (extension; the reference's match_features(..., alpha), which its convert never passes): keep that share of every row's own
+        content features - matched * (1 - alpha) + features * alpha, inside the same call (tvc_convert_alpha_f32 /
+        tvc_convert_ragged_alpha_f32) - a float, a list of B floats, or an fp32 [B] / [1] device tensor ([B]: used in place, read when the
+        kernels run).  Every target form, equal and ragged batches, with auto_pitch and track.  None (the default) is the call without it."""
         # 1. classify the target once; malformed targets, registers and shift lists are refused before any engine or device work
         B = wf.shape[0] if wf.dim() == 2 else 1
         auto = auto_pitch is not None and auto_pitch is not False
@@ -98,6 +102,7 @@ class Generator(HipModule):
                 raise ValueError(f"track: a tracker of {track.n_streams} streams for a batch of {B}")
             track.columns(-(-wf.shape[-1] // 480))      # the tracked columns must lie within the (padded) call's frames
         shift, shifts = pitch_shifts(pitch_shift, B)
+        share = resolve_alpha(alpha, B) if alpha is not None else None
         # 2. the inputs, on the device
         wf = utils.autopad_waveform(self._input_device(wf))
         eng = self.engine(wf.device)
@@ -113,10 +118,14 @@ class Generator(HipModule):
             blobs, ns = prepare_references([self._input_device(t) for t in tgt] if isinstance(tgt, (list, tuple)) else self._input_device(tgt))
         else:
             blobs, ns = prepare_reference(self._input_device(tgt))
-            if auto or shifts is not None:      # a shift per row (given, or found on the device): the shared blob in every row (one segment)
+            if auto or shifts is not None or share is not None:      # a value per row (given, or found on the device): the shared blob in every row (one segment)
                 form, blobs, ns = "table", [blobs] * B, [ns] * B
         # 4. one engine call
         pitch = shift if shifts is None else shifts
+        if share is not None:      # the alpha entry covers every case below: plain shifts, target registers, a tracker
+            res = eng._convert("alpha", wf, blobs, ns, pitch, noise_angle, lens, w, target_registers(regs, B, wf.device) if auto else None, track=track,
+                               alpha=alpha_rows(share, B, wf.device))
+            return res if return_shift or not auto else res[0]
         if not auto:
             return eng._convert(form, wf, blobs, ns, pitch, noise_angle, lens, w)
         wave, sh = eng._convert("auto" if track is None else "track", wf, blobs, ns, pitch, noise_angle, lens, w, target_registers(regs, B, wf.device),

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from ...engine import SOLA_CROSS, SOLA_DELAY, SOLA_SEARCH, pitch_shifts, sola_geometry, stream_resample_geometry
-from ..tinyvc.feature_retrieval import PitchTrack, resolve_auto_pitch, target_form
+from ..tinyvc.feature_retrieval import PitchTrack, alpha_rows, resolve_alpha, resolve_auto_pitch, target_form
 from .generator import Generator
 
 
@@ -133,6 +133,9 @@ class BatchedStreamInfer:
     stream's register - the lower median of its last voiced frames, tracked on the device by `pitch_track` (a feature_retrieval.PitchTrack;
     built in init_buffer when not given: the block's own frames, last_dilay_size before the end of the buffer, are the new ones) - onto
     the target's; `pitch_shift` is the offset on top and `last_pitch_shift` [S] the shift the latest block applied, on the device.
+    `alpha` (convert's: a float, one per stream, or a [S] / [1] fp32 device tensor): the share of each stream's own content features kept in
+    the match, held as `self.alpha`, a [S] device tensor read when a block runs - `stream.alpha.fill_(...)` / `copy_(...)` between blocks
+    moves it without a new graph capture; None (the default) is the plain match.
     `door` (a StreamDoor of the same n_streams and block_size): audio_callback_pcm takes the clients' int16 blocks at the door's rates.
     `crossfade_size`, `sola_search_size`, `last_delay_size` (kept as the attribute `last_dilay_size`, the reference's spelling): the tail's
     geometry in 24 kHz samples, within engine.sola_geometry's limits; `latency_samples` / `latency_seconds` give the resulting range.  The
@@ -142,9 +145,10 @@ class BatchedStreamInfer:
     shorter than the three sizes say, and a look-ahead shorter than the pad is refused."""
 
     def __init__(self, generator: Generator, n_streams=1, target=None, pitch_shift=0., device=None,
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, door=None,
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         check_window(block_size, extra_size, crossfade_size, sola_search_size, last_delay_size, auto_pitch is not None and auto_pitch is not False)
+        share = resolve_alpha(alpha, n_streams) if alpha is not None else None      # refused here, before anything is allocated
         if door is not None and (door.n_streams, door.block_size) != (n_streams, block_size):
             raise ValueError(f"door: built for {door.n_streams} streams of {door.block_size}-sample blocks, the streams are {n_streams} of {block_size}")
         self.door = door
@@ -161,6 +165,8 @@ class BatchedStreamInfer:
         self.target = target
         self.pitch_shift = pitch_shift
         self.device = torch.device(device) if device is not None else generator._module_device()
+        # the streams' shares of their own content features: a [S] device tensor every block reads when it runs, or None (the plain match)
+        self.alpha = alpha_rows(share, n_streams, self.device) if share is not None else None
         self.block_size = block_size
         self.extra_size = extra_size
         self.sola_search_size = sola_search_size
@@ -231,10 +237,11 @@ class BatchedStreamInfer:
         pshift = None
         if self.auto_pitch is None:
             y = self.generator.convert(self.input_wav, self.target, self.pitch_shift, device=self.device,
-                                       f0_estimation=self.f0_estimation, noise_angle=noise_angle)
+                                       f0_estimation=self.f0_estimation, noise_angle=noise_angle, alpha=self.alpha)
         else:
             y, pshift = self.generator.convert(self.input_wav, self.target, self.pitch_shift, device=self.device, f0_estimation=self.f0_estimation,
-                                               noise_angle=noise_angle, auto_pitch=self.auto_pitch, return_shift=True, track=self.pitch_track)
+                                               noise_angle=noise_angle, auto_pitch=self.auto_pitch, return_shift=True, track=self.pitch_track,
+                                               alpha=self.alpha)
         eng = self.generator.engine(self.device)
         return eng.sola(y, self.sola_buffer, self.fade_in_window, self.block_size, self.use_phase_vocoder, want_shift=True,
                         crossfade=self.crossfade_size, search=self.sola_search_size, delay=self.last_dilay_size) + (pshift,)
@@ -269,6 +276,8 @@ class BatchedStreamInfer:
                     tr.params())
         if self.door is not None:
             tkey += (self.door.in_state.data_ptr(), self.door.out_state.data_ptr(), self.door.params())
+        if self.alpha is not None:      # WHERE the shares live, not their values: alpha.fill_(...) / copy_(...) keeps the graph
+            tkey += (("alpha", self.alpha.data_ptr()),)
         return (eng.weights_key, ws.data_ptr() if ws is not None else 0, ws.numel() if ws is not None else 0,
                 tuple((id(t), t._version, t.data_ptr()) for t in tgts), wkey, shifts, bool(self.use_phase_vocoder),
                 (self.crossfade_size, self.sola_search_size, self.last_dilay_size)) + tkey
@@ -339,12 +348,12 @@ class StreamInfer(BatchedStreamInfer):
     """Single stream with the reference's constructor and 1-D buffers (stream.py:31-57)."""
 
     def __init__(self, generator: Generator, target=None, pitch_shift=0., device=torch.device("cpu"),
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, door=None,
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         dev = torch.device(device)
         if dev.type != "cuda":
             dev = generator._module_device()     # the reference defaults to CPU; there is no CPU path here
-        super().__init__(generator, 1, target, pitch_shift, dev, block_size, extra_size, use_phase_vocoder, f0_estimation, use_graph, door,
+        super().__init__(generator, 1, target, pitch_shift, dev, block_size, extra_size, use_phase_vocoder, f0_estimation, use_graph, alpha, door,
                          crossfade_size, sola_search_size, last_delay_size, auto_pitch, pitch_track)
 
     @torch.no_grad()

@@ -3,6 +3,7 @@ top-k kernel of csrc/knn.hip."""
 import collections
 import math
 import os
+import sys
 
 import torch
 
@@ -211,6 +212,60 @@ def target_registers(resolved, B, device):
     t = resolved[0] if len(resolved) == 1 else torch.cat([r.to(device) for r in resolved])
     t = t.to(device=device, dtype=torch.float32)
     return (t.expand(B) if t.numel() == 1 else t).contiguous()
+
+
+def resolve_alpha(alpha, B):
+    """convert's alpha - the share of a row's own content features that survives the match (the reference's match_features(..., alpha);
+    RVC's index rate is 1 - alpha) - checked on the host (no engine, no device work): a float, a sequence of B (or 1) floats, or a 1-D fp32
+    tensor of B or 1 entries ON THE DEVICE (the kernels read it when they run).  Returns a list of B floats, or the tensor; raises
+    ValueError naming alpha otherwise.  Values are neither clamped nor normalised: below 0 and above 1 extrapolate."""
+    if isinstance(alpha, torch.Tensor):
+        if alpha.dim() != 1 or alpha.numel() not in (1, B):
+            raise ValueError(f"alpha: a tensor of 1 or B = {B} shares, got shape {tuple(alpha.shape)}")
+        if alpha.dtype != torch.float32:
+            raise ValueError(f"alpha: an fp32 tensor (it is read in place by the kernels, never converted), got {alpha.dtype}")
+        if alpha.device.type != "cuda":
+            raise ValueError(f"alpha: a tensor lives on the GPU, where the kernels read it when they run; got one on {alpha.device} (pass floats instead)")
+        return alpha
+    if isinstance(alpha, (list, tuple)):
+        vals = list(alpha)
+        if len(vals) not in (1, B):
+            raise ValueError(f"alpha: {len(vals)} shares for a batch of {B}")
+    else:
+        vals = [alpha]
+    for x in vals:
+        if isinstance(x, bool) or not isinstance(x, (int, float)):
+            raise ValueError(f"alpha: a float, a sequence of one float per row or an fp32 [B] / [1] device tensor, got {alpha!r}")
+    return [float(x) for x in vals] * (B if len(vals) == 1 else 1)
+
+
+def alpha_rows(resolved, B, device):
+    """resolve_alpha's result as the contiguous fp32 [B] device tensor the engine takes (a [B] tensor on `device` passes through as it is,
+    so in-place changes reach a captured graph; a [1] tensor is expanded to a new [B] one)"""
+    if isinstance(resolved, torch.Tensor):
+        device = torch.device(device)
+        if resolved.device.type != device.type or (device.index is not None and resolved.device.index != device.index):
+            raise ValueError(f"alpha: the tensor is on {resolved.device}, the conversion runs on {device}")
+        return (resolved.expand(B) if resolved.numel() != B else resolved).contiguous()
+    return torch.tensor(resolved, dtype=torch.float32, device=device)
+
+
+def add_alpha_argument(parser):
+    """`--alpha A` for the entry scripts' parsers: absent (None) is the call without alpha"""
+    parser.add_argument("--alpha", type=float, default=None,
+                        help="keep this share of the source's own content features in the match (the reference's match_features alpha; RVC's "
+                             "index rate is 1 - alpha); default: absent, the plain match")
+
+
+def alpha_keywords(args, script):
+    """what `--alpha` adds to the script's convert / stream call: nothing when it is absent (the call is today's), else {"alpha": A} and one
+    printed line; a non-finite value ends the script"""
+    if args.alpha is None:
+        return {}
+    if not math.isfinite(args.alpha):
+        sys.exit(f"{script}: --alpha must be a finite number")
+    print(f"Keeping {args.alpha:g} of the source's own content features (alpha; index rate {1 - args.alpha:g})")
+    return {"alpha": float(args.alpha)}
 
 
 class PitchTrack:
