@@ -551,6 +551,36 @@ int tvc_stream_resample_prepare(tvc_ctx* ctx, int in_freq, int out_freq);
 int tvc_stream_resample(tvc_ctx* ctx, void* stream, const void* in, int in_is_pcm16, void* out, int out_is_pcm16, float* state, int S,
                         int64_t n_in, int in_freq, int out_freq, float gain_db);
 
+/* The streams' noise gate (extension): one launch behind the tail, one workgroup per stream.  For stream s: x = its input window
+ * [n] (x [S][n]), y = the block the tail emitted ([S][block]), a = base + shift[s] (shift: the tail's shift_out, NULL = 0), so that
+ * x[a + j] is the input sample y[j] was converted from (for a stream: base = Ly - block - cross - search - delay); an index outside
+ * [0, n) reads as 0.  With nsub = block / sub sub-frames and `look` sub-frames of look-ahead:
+ *   p[i] = mean(x[a + i*sub .. a + (i+1)*sub)^2), i < nsub + look (fp32);  T_open = 10^(threshold_db[s] / 10), T_close = T_open *
+ *   10^(-hysteresis_db / 10) (-inf dB -> 0: always open);  for i = 0 .. nsub - 1 in order, carrying (open, hold, g) from block to block:
+ *     d = max(p[i] .. p[i + look])                       (a NaN d is below both thresholds)
+ *     d >= T_open: open = 1, hold = H;  else open and d >= T_close: hold = H;  else open: hold > 0 ? hold -= 1 : open = 0
+ *     tgt = open ? 1 : floor (= 10^(range_db / 20), -inf -> 0);  g_prev = g;
+ *     g = tgt > g ? min(tgt, g + 1.0f / attack) : max(tgt, g - 1.0f / release)      (fp32: one add, one clamp)
+ *     out[i*sub + j] = y[i*sub + j] * (g_prev + (g - g_prev) * ((j + 1) / (float)sub)),  j < sub
+ *   level_db[s] = 10 log10(max(mean(p[0 .. nsub)), 1e-20))      (nullable)
+ * Where g_prev == g the multiplier is exactly g: an open gate changes no bit, a closed one at range_db = -inf emits zeros.  H (`hold`),
+ * attack and release count sub-frames.  threshold_db [S] and the state - open [S] int32, hold_state [S] int32, gain [S] fp32; a stream
+ * starts at (1, 0, 1.0) - live on the device and are read when the kernel runs (the state is advanced in place), so a captured launch
+ * replays as they move; everything else is baked in.  out may be y.  No workspace.
+ *
+ * tvc_stream_gate_geometry (host only: no context, no device) holds the limits: 4 <= sub <= 65536, sub % 4 == 0, block >= 1 a multiple
+ * of sub; look >= 0 and block / sub + look <= 4096 (the powers sit in LDS); 0 <= hold <= 2^20; 1 <= attack, release <= 2^20.  Anything
+ * else returns TVC_ERR_ARG; otherwise nsub = block / sub and look_samples = look * sub (out pointers are nullable).
+ * tvc_stream_gate_geometry_message gives the reason of a refusal ("" for a legal geometry), valid until the thread's next call.
+ * tvc_stream_gate_f32 refuses the same geometries with that reason in tvc_last_error, and: a NULL x, y, out, threshold_db or state
+ * pointer, S <= 0, n outside 1 .. 2^40, |base| > 2^40, a hysteresis_db that is negative or not finite, a range_db that is positive or
+ * NaN - all with TVC_ERR_ARG before anything is launched. */
+int tvc_stream_gate_geometry(int block, int sub, int look, int hold, int attack, int release, int* nsub, int* look_samples);
+const char* tvc_stream_gate_geometry_message(int block, int sub, int look, int hold, int attack, int release);
+int tvc_stream_gate_f32(tvc_ctx* ctx, void* stream, const float* x, int64_t n, int64_t base, const int32_t* shift, const float* y, float* out, int S,
+                        int block, int sub, int look, int hold, int attack, int release, float hysteresis_db, float range_db,
+                        const float* threshold_db, int32_t* open, int32_t* hold_state, float* gain, float* level_db);
+
 /* measurement ----------------------------------------------------------------------------- */
 /* on = 1: every stage (and every FilterNet block) is bracketed by a hipEvent pair on the launch stream (19 pairs per
  * convert, ~0.1 ms of a 8.4 ms step); on = 2: only the `filter_net` region (the roofline's kernel group); on = 0: off.

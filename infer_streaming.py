@@ -29,6 +29,12 @@ the model's 24 kHz.  A block's first sample is played crossfade + lookahead .. c
 sample of the newest block came in (240 .. 320 ms at the defaults), plus the block itself: the latency is these three numbers, not compute.
 Look-ahead is the right context the converter sees behind the block it emits; a shorter one trades that context for latency.
 
+`--gate DB` (extension) puts a noise gate behind SOLA, on the device: a stream whose input falls below DB (mean power of a 10 ms sub-frame, dB
+re full scale) for longer than `--gate-hold` fades to `--gate-range` (default: silence) over `--gate-release`, and opens again over
+`--gate-attack` as soon as a sub-frame within `--gate-lookahead` of the one being played reaches DB; it stays open down to DB minus
+`--gate-hysteresis`.  The gate reads the input window the converter already holds, aligned with the played block by SOLA's own lag, so the
+look-ahead costs no latency.  Times are in milliseconds, rounded to whole 10 ms sub-frames.  The defaults are guesses: nobody has listened yet.
+
 `--streams S` feeds S copies of the input as S concurrent streams through one BatchedStreamInfer
 (one batched convert + one SOLA launch per block) and reports the p50 / p95 block latency against the
 real-time budget (chunk / 24 kHz = 80 ms for the default 1920-sample chunk).
@@ -43,13 +49,15 @@ import torch
 
 from tinyvc_amd import audio_io
 from infer import load_generator, load_target
-from tinyvc_amd.engine import sola_geometry, stream_resample_geometry
-from tinyvc_amd.module.infer import BatchedStreamInfer, StreamDoor
-from tinyvc_amd.module.infer.stream import check_window
+from tinyvc_amd.engine import sola_geometry, stream_gate_geometry, stream_resample_geometry
+from tinyvc_amd.module.infer import BatchedStreamInfer, StreamDoor, StreamGate
+from tinyvc_amd.module.infer.stream import check_gate_lookahead, check_window
 from tinyvc_amd.module.tinyvc.feature_retrieval import (PitchTrack, add_alpha_argument, add_blend_argument, alpha_keywords, pitch_register,
                                                         semitones_between)
 
 FRAMES_PER_SECOND = 50      # 24 kHz / 480 samples
+GATE_SUB_FRAME = 240        # the gate's sub-frame: 10 ms at 24 kHz
+GATE_MS = dict(hold=200.0, attack=10.0, release=100.0, lookahead=20.0)      # the defaults of --gate-hold / -attack / -release / -lookahead
 
 
 def build_parser():
@@ -87,6 +95,17 @@ def build_parser():
     p.add_argument("--lookahead", default=3840, type=int, metavar="N",
                    help="24 kHz samples of converted audio behind the emitted block (the reference's last_dilay_size): right context for the converter, "
                         "paid for in latency; with --auto-pitch a multiple of 480")
+    p.add_argument("--gate", default=None, type=float, metavar="DB",
+                   help="noise gate on the device behind SOLA: streams whose input stays below DB (dB re full scale, per 10 ms sub-frame) fade out; "
+                        "--gate=-inf is an always-open gate.  Absent: no gate.  The defaults of the six flags below are guesses: nobody has listened yet")
+    p.add_argument("--gate-hysteresis", default=None, type=float, metavar="DB", help="an open gate stays open down to --gate minus this (default 6)")
+    p.add_argument("--gate-range", default=None, type=float, metavar="DB", help="gain of a closed gate, <= 0 (default -inf: silence)")
+    p.add_argument("--gate-hold", default=None, type=float, metavar="MS", help=f"how long the gate outlasts the last loud sub-frame (default {GATE_MS['hold']:g})")
+    p.add_argument("--gate-attack", default=None, type=float, metavar="MS", help=f"fade-in time, at least one sub-frame (default {GATE_MS['attack']:g})")
+    p.add_argument("--gate-release", default=None, type=float, metavar="MS", help=f"fade-out time, at least one sub-frame (default {GATE_MS['release']:g})")
+    p.add_argument("--gate-lookahead", default=None, type=float, metavar="MS",
+                   help=f"how far ahead of the played sample the gate looks in the input it already holds: no added latency, at most "
+                        f"--crossfade + --lookahead samples (default {GATE_MS['lookahead']:g})")
     # file-driven operation (no audio devices on a GPU node)
     p.add_argument("--input-wav", default=None, help="read the microphone signal from this WAV instead of a device")
     p.add_argument("--output-wav", default=None, help="write the converted stream here")
@@ -162,11 +181,52 @@ def check_auto_pitch(args, block=None):
     return dict(new_frames=chunk // 480, window_frames=window, min_voiced=max(1, int(round(args.auto_pitch_warmup * FRAMES_PER_SECOND))), slew=slew)
 
 
+def gate_sub_frames(ms):
+    """milliseconds -> whole 10 ms sub-frames, rounded to the nearest"""
+    return int(round(ms * 24.0 / GATE_SUB_FRAME))
+
+
+def check_gate(args, block=None):
+    """--gate and its six companions against each other and the stream's geometry, before anything is loaded: sys.exit with a message, or the
+    StreamGate keywords (None without --gate).  `block`: the model's block length when it is not -c (--resample)"""
+    extra = [f"--gate-{k}" for k in ("hysteresis", "range", "hold", "attack", "release", "lookahead") if getattr(args, f"gate_{k}") is not None]
+    if args.gate is None:
+        if extra:
+            sys.exit(f"infer_streaming.py: {' '.join(extra)} without --gate DB: there is no gate to set")
+        return None
+    chunk = args.chunk if block is None else block
+    hyst = 6.0 if args.gate_hysteresis is None else args.gate_hysteresis
+    rng = -math.inf if args.gate_range is None else args.gate_range
+    if math.isnan(args.gate):
+        sys.exit("infer_streaming.py: --gate: a threshold in dB (--gate=-inf: always open)")
+    if not (hyst >= 0 and math.isfinite(hyst)):
+        sys.exit(f"infer_streaming.py: --gate-hysteresis {hyst}: a finite number of dB >= 0")
+    if not rng <= 0:
+        sys.exit(f"infer_streaming.py: --gate-range {rng}: a gain in dB <= 0 (-inf: silence)")
+    ms = {k: (GATE_MS[k] if getattr(args, f"gate_{k}") is None else getattr(args, f"gate_{k}")) for k in GATE_MS}
+    for k, v in ms.items():
+        if not (v >= 0 and math.isfinite(v)):
+            sys.exit(f"infer_streaming.py: --gate-{k} {v}: a finite number of milliseconds >= 0")
+    if chunk <= 0 or chunk % GATE_SUB_FRAME:
+        sys.exit(f"infer_streaming.py: --gate: blocks of {chunk} samples at 24 kHz are not whole {GATE_SUB_FRAME}-sample (10 ms) sub-frames")
+    n = {k: gate_sub_frames(v) for k, v in ms.items()}
+    n["attack"], n["release"] = max(1, n["attack"]), max(1, n["release"])      # a fade takes at least one sub-frame
+    try:
+        stream_gate_geometry(chunk, GATE_SUB_FRAME, n["lookahead"], n["hold"], n["attack"], n["release"])
+        _, pad = check_window(chunk, args.extra, args.crossfade, args.sola_search, args.lookahead, bool(args.auto_pitch))
+        check_gate_lookahead(n["lookahead"] * GATE_SUB_FRAME, args.crossfade, args.lookahead, pad)
+    except ValueError as e:
+        sys.exit(f"infer_streaming.py: --gate: {e}")
+    return dict(threshold_db=args.gate, hysteresis_db=hyst, range_db=rng, sub_frame=GATE_SUB_FRAME, hold_size=n["hold"] * GATE_SUB_FRAME,
+                attack_size=n["attack"] * GATE_SUB_FRAME, release_size=n["release"] * GATE_SUB_FRAME, lookahead_size=n["lookahead"] * GATE_SUB_FRAME)
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     block = check_resample(args)
     track_kw = check_auto_pitch(args, block)
     check_geometry(args, block)
+    gate_kw = check_gate(args, block)
     device = torch.device(args.device)
     if device.type != "cuda":
         sys.exit("infer_streaming.py: this build runs on an AMD GPU only; pass -d cuda")
@@ -201,9 +261,16 @@ def main(argv=None):
         print(f"Resampling {rate} Hz <-> 24000 Hz on the device: {args.chunk}-sample blocks are {block} at the model's rate; "
               f"the two filters add {door.latency_seconds * 1e3:.2f} ms of latency")
     alpha_kw = alpha_keywords(args, "infer_streaming.py")      # {} without --alpha: the stream is then built as it has always been
+    gate = None
+    if gate_kw is not None:
+        gate = StreamGate(S, door.block_size, device=device, **gate_kw)
+        to_ms = 1000.0 / 24000
+        print(f"Noise gate at {gate_kw['threshold_db']:g} dB (hysteresis {gate.hysteresis_db:g} dB, range {gate.range_db:g} dB): hold {gate.hold_size * to_ms:g} ms, "
+              f"attack {gate.attack_size * to_ms:g} ms, release {gate.release_size * to_ms:g} ms, look-ahead {gate.lookahead_size * to_ms:g} ms "
+              f"in {GATE_SUB_FRAME * to_ms:g} ms sub-frames")
     stream = BatchedStreamInfer(gen, n_streams=S, pitch_shift=pitch_shift, block_size=door.block_size, device=device, extra_size=args.extra,
                                 f0_estimation=args.f0_estimation, door=door, auto_pitch=True if track is not None else None, pitch_track=track,
-                                crossfade_size=args.crossfade, sola_search_size=args.sola_search, last_delay_size=args.lookahead, **alpha_kw)
+                                crossfade_size=args.crossfade, sola_search_size=args.sola_search, last_delay_size=args.lookahead, gate=gate, **alpha_kw)
     lo, hi = stream.latency_seconds
     print(f"Latency {lo * 1e3:.1f} to {hi * 1e3:.1f} ms (cross-fade {args.crossfade} + look-ahead {args.lookahead} + lag 0 .. {args.sola_search} samples at 24 kHz"
           f"{', and the resampling filters' if block is not None else ''}) plus the {door.block_size / 24000 * 1e3:.0f} ms block")
@@ -235,12 +302,15 @@ def main(argv=None):
 
     blocks = int16_blocks_from_wav(args.input_wav, args.sample_rate, args.chunk, gen.engine(device))
     outs, lat = [], []
+    ended_open = torch.zeros(S, dtype=torch.int64, device=device) if gate is not None else None
     for blk in blocks:
         torch.cuda.synchronize(device)
         t0 = time.perf_counter()
         o = process(blk)
         lat.append(time.perf_counter() - t0)      # includes the device -> host copy of the block, like the reference loop
         outs.append(o[0])
+        if gate is not None:
+            ended_open += gate.open      # counted on the device, read once at the end
     if args.output_wav:
         pcm = np.concatenate(outs).astype(np.float32) / 32768
         audio_io.save(args.output_wav, torch.from_numpy(pcm)[None], args.sample_rate)
@@ -248,6 +318,9 @@ def main(argv=None):
         reg = track.register()
         for s_, (hz, n, sh) in enumerate(zip(reg.median_hz.tolist(), reg.voiced.tolist(), stream.last_pitch_shift.tolist())):
             print(f"stream {s_}: register {hz:.1f} Hz over {n} voiced frames, shift {sh:+.2f} semitones")
+    if gate is not None and blocks:
+        for s_, n_open in enumerate(ended_open.tolist()):
+            print(f"stream {s_}: gate open at the end of {n_open} of {len(blocks)} blocks ({100.0 * n_open / len(blocks):.0f} %)")
     if len(lat) > 3:
         l = np.sort(np.array(lat[3:])) * 1e3
         budget = args.chunk / args.sample_rate * 1e3

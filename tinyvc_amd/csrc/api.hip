@@ -1079,6 +1079,39 @@ int tvc_stream_push_f32(tvc_ctx* ctx, void* stream, float* buf, const float* blo
     return run_stream_push(ctx, (hipStream_t)stream, buf, blocks, S, (int)n, block);
 }
 
+int tvc_stream_gate_geometry(int block, int sub, int look, int hold, int attack, int release, int* nsub, int* look_samples) {
+    return stream_gate_geometry(block, sub, look, hold, attack, release, nsub, look_samples, nullptr, 0);
+}
+
+const char* tvc_stream_gate_geometry_message(int block, int sub, int look, int hold, int attack, int release) {
+    static thread_local char why[96];
+    stream_gate_geometry(block, sub, look, hold, attack, release, nullptr, nullptr, why, sizeof(why));
+    return why;
+}
+
+int tvc_stream_gate_f32(tvc_ctx* ctx, void* stream, const float* x, int64_t n, int64_t base, const int32_t* shift, const float* y, float* out, int S,
+                        int block, int sub, int look, int hold, int attack, int release, float hysteresis_db, float range_db,
+                        const float* threshold_db, int32_t* open, int32_t* hold_state, float* gain, float* level_db) {
+    if (!ctx) return TVC_ERR_ARG;
+    char why[96];
+    if (stream_gate_geometry(block, sub, look, hold, attack, release, nullptr, nullptr, why, sizeof(why)) != 0)
+        return fail(ctx, TVC_ERR_ARG, "tvc_stream_gate_f32: %s", why);
+    if (!x || !y || !out || !threshold_db || !open || !hold_state || !gain || S <= 0)
+        return fail(ctx, TVC_ERR_ARG, "tvc_stream_gate_f32: bad argument (a NULL pointer or S <= 0)");
+    constexpr int64_t kSpan = (int64_t)1 << 40;      // a + i stays far inside 64 bits for any int32 shift
+    if (n < 1 || n > kSpan || base < -kSpan || base > kSpan)
+        return fail(ctx, TVC_ERR_ARG, "tvc_stream_gate_f32: n = %ld is outside 1 .. 2^40 or |base| = |%ld| is above 2^40", (long)n, (long)base);
+    if (!(hysteresis_db >= 0.f) || std::isinf(hysteresis_db))
+        return fail(ctx, TVC_ERR_ARG, "tvc_stream_gate_f32: hysteresis_db = %g is not a finite number >= 0", (double)hysteresis_db);
+    if (!(range_db <= 0.f)) return fail(ctx, TVC_ERR_ARG, "tvc_stream_gate_f32: range_db = %g is not <= 0 (-inf: a closed gate emits zeros)", (double)range_db);
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    StreamGate g;
+    g.block = block; g.sub = sub; g.look = look; g.hold = hold; g.attack = attack; g.release = release;
+    g.hysteresis_db = hysteresis_db; g.range_db = range_db;
+    g.threshold_db = threshold_db; g.open = open; g.hold_state = hold_state; g.gain = gain; g.level_db = level_db;
+    return run_stream_gate(ctx, (hipStream_t)stream, x, n, base, shift, y, out, S, g);
+}
+
 int tvc_stream_resample_geometry(int in_freq, int out_freq, int64_t n_in, int64_t* n_out, int* hist, int* delay) {
     if (!n_out || !hist || !delay) return TVC_ERR_ARG;
     return stream_resample_geometry(in_freq, out_freq, n_in, n_out, hist, delay);

@@ -477,6 +477,21 @@ int sola_geometry(int block, int cross, int search, int delay, int64_t* min_ly, 
 int run_sola(tvc_ctx*, hipStream_t, const float* y, float* sola_buf, const float* fade_in, float* out, int32_t* shift_out,
              int S, int64_t Ly, int block, int cross, int search, int delay, int use_pv);
 int run_stream_push(tvc_ctx* ctx, hipStream_t s, float* buf, const float* blocks, int S, int n, int m);
+// the noise gate behind the tail (gate.hip).  kGateMaxSub: the sub-frame powers of a block and its look-ahead that a workgroup keeps in LDS
+constexpr int kGateMaxSub = 4096, kGateMaxSubFrame = 1 << 16, kGateMaxCount = 1 << 20;
+struct StreamGate {
+    int block, sub, look, hold, attack, release;      // samples, samples, and counts of sub-frames
+    float hysteresis_db, range_db;
+    const float* threshold_db;      // [S] device, read when the kernel runs
+    int32_t* open;                  // [S] device state, read and advanced in place: open, hold, gain
+    int32_t* hold_state;
+    float* gain;
+    float* level_db;                // [S] device, optional: the block's input level
+};
+// the legal gate geometries, in one place (gate.hip): 0, or TVC_ERR_ARG with the reason in `why`; every out pointer is nullable
+int stream_gate_geometry(int block, int sub, int look, int hold, int attack, int release, int* nsub, int* look_samples, char* why, size_t why_bytes);
+// (the caller has checked the geometry; x [S][n], y and out [S][block], out may be y; shift [S] optional)
+int run_stream_gate(tvc_ctx*, hipStream_t, const float* x, int64_t n, int64_t base, const int32_t* shift, const float* y, float* out, int S, const StreamGate& g);
 int64_t resample_out_len(int64_t n, int orig_freq, int new_freq);
 int run_resample(tvc_ctx*, hipStream_t, const float* x, float* y, int rows, int64_t n, int orig_freq, int new_freq);
 int stream_resample_geometry(int in_freq, int out_freq, int64_t n_in, int64_t* n_out, int* hist, int* delay);

@@ -119,6 +119,21 @@ def sola_geometry(block, cross=SOLA_CROSS, search=SOLA_SEARCH, delay=SOLA_DELAY,
     return min_ly.value, lo.value, hi.value
 
 
+def stream_gate_geometry(block, sub, look=0, hold=0, attack=1, release=1, lib=None):
+    """tvc_stream_gate_geometry (no context, no device) -> (nsub, look_samples) of a noise gate over `block`-sample blocks in sub-frames of
+    `sub` samples; look, hold, attack and release count sub-frames.  ValueError, with the library's reason, for what the kernel does not take."""
+    vals = (block, sub, look, hold, attack, release)
+    for x, name in zip(vals, ("block", "sub", "look", "hold", "attack", "release")):
+        if isinstance(x, bool) or not isinstance(x, numbers.Integral) or abs(x) >= 2 ** 31:
+            raise ValueError(f"stream gate geometry: {name} must be an integer, got {x!r}")
+    vals = tuple(int(v) for v in vals)
+    lib = lib if lib is not None else _lib.load_library()
+    nsub, look_samples = ctypes.c_int(), ctypes.c_int()
+    if lib.tvc_stream_gate_geometry(*vals, ctypes.byref(nsub), ctypes.byref(look_samples)) != 0:
+        raise ValueError(f"stream gate geometry: {lib.tvc_stream_gate_geometry_message(*vals).decode()}")
+    return nsub.value, look_samples.value
+
+
 def pitch_class_table():
     """PitchEstimator.id2freq over ids 0..511 (reference encoder.py:48-54), on the host."""
     ids = torch.arange(spec.PITCH_CLASSES).to(torch.float)
@@ -921,6 +936,41 @@ class Engine:
             self._ok(self.lib.tvc_sola_geom_f32(self.ctx, self._stream(), _ptr(y), _ptr(sola_buf), _ptr(fade_in), _ptr(out), _ptr(shift), S, Ly, int(block),
                                                 cross, search, delay, int(bool(use_phase_vocoder))), "tvc_sola_geom_f32")
         return (out, shift) if want_shift else out
+
+    def stream_gate(self, x, y, shift, gate, base, out=None):
+        """The noise gate behind the tail (tvc_stream_gate_f32): x [S, n] the streams' input windows, y [S, block] the emitted blocks,
+        shift [S] int32 the tail's lags (None = 0), `gate` a module.infer.StreamGate (thresholds and state on the device, advanced in place),
+        base + shift[s] the index in x[s] of the input sample y[s, 0] was converted from.  Returns the gated blocks: a new tensor, or `out`
+        (which may be y)."""
+        for t, name in ((x, "x"), (y, "y")):
+            _check_dev(t, name, self.device)
+            if t.dim() != 2 or t.dtype != _F32 or not t.is_contiguous():
+                raise ValueError(f"stream_gate: {name} must be contiguous fp32 [S, n], got {t.dtype} {tuple(t.shape)}")
+        S, n = x.shape
+        if tuple(y.shape) != (S, gate.block_size) or gate.n_streams != S:
+            raise ValueError(f"stream_gate: a gate for {gate.n_streams} streams of {gate.block_size}-sample blocks, x is {tuple(x.shape)} and y {tuple(y.shape)}")
+        if shift is not None:
+            _check_dev(shift, "shift", self.device)
+            if shift.dtype != torch.int32 or tuple(shift.shape) != (S,) or not shift.is_contiguous():
+                raise ValueError(f"stream_gate: shift must be contiguous int32 [{S}], got {shift.dtype} {tuple(shift.shape)}")
+        if isinstance(base, bool) or not isinstance(base, numbers.Integral):
+            raise ValueError(f"stream_gate: base must be an integer, got {base!r}")
+        for t, name, dt in ((gate.threshold_db, "threshold_db", _F32), (gate.open, "open", torch.int32), (gate.hold, "hold", torch.int32),
+                            (gate.gain, "gain", _F32), (gate.level_db, "level_db", _F32)):
+            _check_dev(t, f"gate.{name}", self.device)
+            if t.dtype != dt or tuple(t.shape) != (S,) or not t.is_contiguous():
+                raise ValueError(f"stream_gate: gate.{name} must be contiguous {dt} [{S}], got {t.dtype} {tuple(t.shape)}")
+        if out is None:
+            out = torch.empty_like(y)
+        else:
+            _check_dev(out, "out", self.device)
+            if out.dtype != _F32 or out.shape != y.shape or not out.is_contiguous():
+                raise ValueError(f"stream_gate: out must be contiguous fp32 {tuple(y.shape)}, got {out.dtype} {tuple(out.shape)}")
+        sub, look, hold, attack, release, hysteresis_db, range_db = gate.params()[2:]
+        self._ok(self.lib.tvc_stream_gate_f32(self.ctx, self._stream(), _ptr(x), n, int(base), _ptr(shift), _ptr(y), _ptr(out), S, gate.block_size, sub, look,
+                                              hold, attack, release, hysteresis_db, range_db, _ptr(gate.threshold_db), _ptr(gate.open), _ptr(gate.hold),
+                                              _ptr(gate.gain), _ptr(gate.level_db)), "tvc_stream_gate_f32")
+        return out
 
 
 # ---------------------------------------------------------------------- shared weightless engines

@@ -5,13 +5,14 @@ the lag arg-max kept on the device.  The tail's geometry (extension: the referen
 argument - crossfade_size, sola_search_size, last_delay_size -: a block's first sample leaves crossfade + search + delay - shift samples
 after the first sample of the newest input block came in (shift in [0, search], chosen per block), so the three sizes are the latency a
 listener hears beyond the block itself; look-ahead (last_delay_size) is the right context the converter sees behind the emitted block.  `StreamDoor` (extension) puts a stateful resampler, fused with the int16 conversions and gain, on both
-sides of the block: clients send and receive int16 at their own rates."""
+sides of the block: clients send and receive int16 at their own rates.  `StreamGate` (extension) is a per-stream noise gate on the device,
+one launch behind SOLA: it follows the input window's power under the emitted block and looks ahead in what the window already holds."""
 import math
 
 import numpy as np
 import torch
 
-from ...engine import SOLA_CROSS, SOLA_DELAY, SOLA_SEARCH, pitch_shifts, sola_geometry, stream_resample_geometry
+from ...engine import SOLA_CROSS, SOLA_DELAY, SOLA_SEARCH, pitch_shifts, sola_geometry, stream_gate_geometry, stream_resample_geometry
 from ..tinyvc.feature_retrieval import PitchTrack, alpha_rows, resolve_alpha, resolve_auto_pitch, target_form
 from .generator import Generator
 
@@ -125,6 +126,91 @@ class StreamDoor:
         return engine.stream_resample(y, self.out_state, MODEL_RATE, self.out_rate, self.output_gain, out_pcm16=True)
 
 
+def check_gate_lookahead(lookahead_size, crossfade_size, last_delay_size, pad_size):
+    """The gate's look-ahead against the window (ValueError): behind the input samples of an emitted block the window holds crossfade + search +
+    delay - shift more, of which the last pad_size belong to a frame the converter padded; at the largest lag that leaves crossfade_size +
+    last_delay_size - pad_size input samples the gate may look at without running past the window's end."""
+    room = crossfade_size + last_delay_size - pad_size
+    if lookahead_size > room:
+        raise ValueError(f"gate: lookahead_size = {lookahead_size} is more than the {room} input samples the window holds behind an emitted block "
+                         f"(crossfade_size {crossfade_size} + last_delay_size {last_delay_size} - pad_size {pad_size})")
+    return room
+
+
+class StreamGate:
+    """The noise gate of a set of streams that advance in lock step (tvc_stream_gate_f32; its definition is in tinyvc_hip.h): behind SOLA,
+    every emitted block is multiplied by a gain that follows the power of the INPUT samples it was converted from, sub-frame by sub-frame,
+    and of `lookahead_size` samples of input behind them, which the rolling window already holds - so the gate opens ahead of an onset at no
+    added latency.  It never feeds back: the SOLA buffer and the window stay ungated, and closed streams are still converted.
+      threshold_db [S]   fp32 on the device, read when a block runs: a sub-frame at or above it (mean power, dB re full scale) opens the gate;
+                         `gate.threshold_db.fill_(...)` / `copy_(...)` moves it between blocks; -inf = always open, the ungated stream bit for bit
+      hysteresis_db      the gate stays open down to threshold - hysteresis
+      hold_size, attack_size, release_size, lookahead_size
+                         24 kHz samples, whole sub-frames: how long an open gate outlasts the last loud sub-frame, how long the gain takes
+                         from 0 to 1 and from 1 to 0 (at least one sub-frame each), how far the gate looks ahead
+      range_db           the gain of a closed gate (<= 0; -inf, the default: silence)
+      gain [S] fp32, open [S] int32, hold [S] int32      the state the next block starts from; level_db [S]: the last block's input level
+    The defaults are guesses: nobody has listened to them yet.  Every argument is checked before anything is allocated (ValueError)."""
+
+    def __init__(self, n_streams, block_size, threshold_db=-50.0, hysteresis_db=6.0, hold_size=4800, attack_size=240, release_size=2400,
+                 lookahead_size=480, sub_frame=240, range_db=-math.inf, device=None):
+        for x, name in ((n_streams, "n_streams"), (block_size, "block_size"), (sub_frame, "sub_frame")):
+            if isinstance(x, bool) or not isinstance(x, int) or x < 1:
+                raise ValueError(f"StreamGate: {name} must be an integer >= 1, got {x!r}")
+        for x, name, least in ((hold_size, "hold_size", 0), (attack_size, "attack_size", 1), (release_size, "release_size", 1),
+                               (lookahead_size, "lookahead_size", 0)):
+            if isinstance(x, bool) or not isinstance(x, int) or x < 0 or x % sub_frame or x // sub_frame < least:
+                raise ValueError(f"StreamGate: {name} must be a whole number of {sub_frame}-sample sub-frames, at least {least}; got {x!r}")
+        thr = [threshold_db] if isinstance(threshold_db, (int, float)) and not isinstance(threshold_db, bool) else threshold_db
+        if isinstance(thr, torch.Tensor):
+            thr = thr.detach().cpu().tolist() if thr.dim() == 1 else None
+        if not isinstance(thr, (list, tuple)) or len(thr) not in (1, n_streams) or not all(
+                isinstance(t, (int, float)) and not isinstance(t, bool) and not math.isnan(t) for t in thr):
+            raise ValueError(f"StreamGate: threshold_db must be a number of dB (-inf: always open) or one per stream ({n_streams}), got {threshold_db!r}")
+        if isinstance(hysteresis_db, bool) or not isinstance(hysteresis_db, (int, float)) or not math.isfinite(hysteresis_db) or hysteresis_db < 0:
+            raise ValueError(f"StreamGate: hysteresis_db must be a finite number of dB >= 0, got {hysteresis_db!r}")
+        if isinstance(range_db, bool) or not isinstance(range_db, (int, float)) or not range_db <= 0:
+            raise ValueError(f"StreamGate: range_db must be a number of dB <= 0 (-inf: a closed gate is silent), got {range_db!r}")
+        self.look, self.hold_count, self.attack, self.release = (v // sub_frame for v in (lookahead_size, hold_size, attack_size, release_size))
+        try:
+            stream_gate_geometry(block_size, sub_frame, self.look, self.hold_count, self.attack, self.release)
+        except ValueError as e:
+            raise ValueError(f"StreamGate: {e}") from None
+        self.n_streams, self.block_size, self.sub_frame = n_streams, block_size, sub_frame
+        self.hold_size, self.attack_size, self.release_size, self.lookahead_size = hold_size, attack_size, release_size, lookahead_size
+        self.hysteresis_db, self.range_db = float(hysteresis_db), float(range_db)
+        device = torch.device(device if device is not None else "cuda")
+        if device.type != "cuda" or not torch.cuda.is_available():
+            raise ValueError(f"StreamGate: the thresholds and the state live on the GPU, where the gate's kernel runs; got device {str(device)!r}"
+                             + ("" if torch.cuda.is_available() else " and there is no GPU here"))
+        self.device = device
+        self.threshold_db = torch.tensor([float(t) for t in thr] * (n_streams // len(thr)), dtype=torch.float32, device=device)
+        self.gain = torch.ones(n_streams, dtype=torch.float32, device=device)
+        self.open = torch.ones(n_streams, dtype=torch.int32, device=device)
+        self.hold = torch.zeros(n_streams, dtype=torch.int32, device=device)
+        self.level_db = torch.full((n_streams,), -200.0, dtype=torch.float32, device=device)
+
+    def params(self):
+        """the host values a captured block bakes in: (n_streams, block_size, sub_frame, look, hold, attack, release - counts of sub-frames -,
+        hysteresis_db, range_db)"""
+        return (self.n_streams, self.block_size, self.sub_frame, self.look, self.hold_count, self.attack, self.release, self.hysteresis_db, self.range_db)
+
+    def reset(self, streams=None):
+        """Put every stream, or the listed ones, back at the start: open, no hold left, gain 1 (a silent start then closes over release_size).
+        In-place ops on the state tensors, so it works between replays of a captured graph, which reads them when it runs."""
+        if streams is None:
+            self.open.fill_(1)
+            self.hold.zero_()
+            self.gain.fill_(1.0)
+            self.level_db.fill_(-200.0)
+            return
+        idx = torch.as_tensor(list(streams), dtype=torch.int64, device=self.device)
+        self.open.index_fill_(0, idx, 1)
+        self.hold.index_fill_(0, idx, 0)
+        self.gain.index_fill_(0, idx, 1.0)
+        self.level_db.index_fill_(0, idx, -200.0)
+
+
 class BatchedStreamInfer:
     """`target`: one index for every stream ([1, 768, N]) or one per stream ([S, 768, N], or a list of S [1, 768, N_s] tensors), prepared
     once and cached on those tensors - or a feature_retrieval.Blend of several (its weights are read on the device when a block runs:
@@ -137,6 +223,10 @@ class BatchedStreamInfer:
     the match, held as `self.alpha`, a [S] device tensor read when a block runs - `stream.alpha.fill_(...)` / `copy_(...)` between blocks
     moves it without a new graph capture; None (the default) is the plain match.
     `door` (a StreamDoor of the same n_streams and block_size): audio_callback_pcm takes the clients' int16 blocks at the door's rates.
+    `gate` (a StreamGate of the same n_streams and block_size): every emitted block goes through the noise gate, one launch behind SOLA (and
+    in front of the door), driven by the input window and `last_shift` on the device; the SOLA buffer and the window stay ungated.
+    `gate.threshold_db.fill_(...)` / `copy_(...)` and `gate.reset(...)` between blocks keep a captured graph; None (the default) is the
+    ungated stream, launch for launch.
     `crossfade_size`, `sola_search_size`, `last_delay_size` (kept as the attribute `last_dilay_size`, the reference's spelling): the tail's
     geometry in 24 kHz samples, within engine.sola_geometry's limits; `latency_samples` / `latency_seconds` give the resulting range.  The
     attributes are plain, as in the reference: one changed after construction takes effect at the next init_buffer(), which checks them again
@@ -145,13 +235,16 @@ class BatchedStreamInfer:
     shorter than the three sizes say, and a look-ahead shorter than the pad is refused."""
 
     def __init__(self, generator: Generator, n_streams=1, target=None, pitch_shift=0., device=None,
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, door=None,
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, gate=None, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         check_window(block_size, extra_size, crossfade_size, sola_search_size, last_delay_size, auto_pitch is not None and auto_pitch is not False)
         share = resolve_alpha(alpha, n_streams) if alpha is not None else None      # refused here, before anything is allocated
         if door is not None and (door.n_streams, door.block_size) != (n_streams, block_size):
             raise ValueError(f"door: built for {door.n_streams} streams of {door.block_size}-sample blocks, the streams are {n_streams} of {block_size}")
         self.door = door
+        if gate is not None and (gate.n_streams, gate.block_size) != (n_streams, block_size):
+            raise ValueError(f"gate: built for {gate.n_streams} streams of {gate.block_size}-sample blocks, the streams are {n_streams} of {block_size}")
+        self.gate = gate
         self.auto_pitch = auto_pitch if auto_pitch is not False else None
         self.pitch_track = pitch_track
         self._own_track = pitch_track is None
@@ -209,6 +302,11 @@ class BatchedStreamInfer:
         # and _step holds every later block against what was seen here
         self.input_size, _ = check_window(self.block_size, self.extra_size, self.crossfade_size, self.sola_search_size, self.last_dilay_size,
                                            self.auto_pitch is not None)
+        if self.gate is not None:      # (before anything is allocated) the gate against the attributes as they stand now
+            if (self.gate.n_streams, self.gate.block_size) != (self.n_streams, self.block_size):
+                raise ValueError(f"gate: built for {self.gate.n_streams} streams of {self.gate.block_size}-sample blocks, the streams are "
+                                 f"{self.n_streams} of {self.block_size}")
+            check_gate_lookahead(self.gate.lookahead_size, self.crossfade_size, self.last_dilay_size, self.pad_size)
         self._geometry = self._attributes()
         self.fade_in_window, self.fade_out_window = _fade_windows(self.crossfade_size, self.device)
         self.input_wav = torch.zeros(self.n_streams, self.input_size, device=self.device)
@@ -222,6 +320,8 @@ class BatchedStreamInfer:
         if self.door is not None:
             self.door.prepare(self.generator.engine(self.device))
             self.door.reset()
+        if self.gate is not None:
+            self.gate.reset()
 
     def _attributes(self):
         return (self.block_size, self.crossfade_size, self.sola_search_size, self.last_dilay_size, self.input_size)
@@ -243,11 +343,16 @@ class BatchedStreamInfer:
                                                noise_angle=noise_angle, auto_pitch=self.auto_pitch, return_shift=True, track=self.pitch_track,
                                                alpha=self.alpha)
         eng = self.generator.engine(self.device)
-        return eng.sola(y, self.sola_buffer, self.fade_in_window, self.block_size, self.use_phase_vocoder, want_shift=True,
-                        crossfade=self.crossfade_size, search=self.sola_search_size, delay=self.last_dilay_size) + (pshift,)
+        out, shift = eng.sola(y, self.sola_buffer, self.fade_in_window, self.block_size, self.use_phase_vocoder, want_shift=True,
+                              crossfade=self.crossfade_size, search=self.sola_search_size, delay=self.last_dilay_size)
+        if self.gate is not None:
+            # y[Ly - block - crossfade - search - delay + shift + j] became out[j], and convert keeps the window's time axis (padding at the end)
+            base = y.shape[1] - self.block_size - self.crossfade_size - self.sola_search_size - self.last_dilay_size
+            eng.stream_gate(self.input_wav, out, shift, self.gate, base, out=out)
+        return out, shift, pshift
 
     def _step_pcm(self, pcm, noise_angle):
-        # the whole block from client int16 to client int16: door in, _step, door out
+        # the whole block from client int16 to client int16: door in, _step (convert, SOLA, gate), door out
         eng = self.generator.engine(self.device)
         out, shift, pshift = self._step(self.door.push(eng, pcm), noise_angle)
         return self.door.pull(eng, out), shift, pshift
@@ -258,7 +363,7 @@ class BatchedStreamInfer:
         one), the prepared index riding on `target`, plus the scalars captured by value.  With auto_pitch also the
         tracker's three state tensors (where they live) and its host parameters, and WHERE the target registers live - not their values,
         nor the ring's or `auto`'s: the kernels read those at replay, so a reset(), registers.copy_(...) or a stream's history advancing
-        keeps the graph.  With a door, likewise: where its two state tensors live and its host parameters (rates, block, gains).  The tail's
+        keeps the graph.  With a door, likewise: where its two state tensors live and its host parameters (rates, block, gains); with a gate, where its five tensors live and its params().  The tail's
         geometry is baked into its two launches, so it is part of the key."""
         eng = self.generator.engine(self.device)          # re-packs the weights first if a parameter changed
         ws = eng._ws
@@ -276,6 +381,9 @@ class BatchedStreamInfer:
                     tr.params())
         if self.door is not None:
             tkey += (self.door.in_state.data_ptr(), self.door.out_state.data_ptr(), self.door.params())
+        if self.gate is not None:      # WHERE the thresholds and the state live, and the gate's host parameters - never their values
+            gt = self.gate
+            tkey += (("gate", gt.threshold_db.data_ptr(), gt.open.data_ptr(), gt.hold.data_ptr(), gt.gain.data_ptr(), gt.level_db.data_ptr(), gt.params()),)
         if self.alpha is not None:      # WHERE the shares live, not their values: alpha.fill_(...) / copy_(...) keeps the graph
             tkey += (("alpha", self.alpha.data_ptr()),)
         return (eng.weights_key, ws.data_ptr() if ws is not None else 0, ws.numel() if ws is not None else 0,
@@ -348,12 +456,12 @@ class StreamInfer(BatchedStreamInfer):
     """Single stream with the reference's constructor and 1-D buffers (stream.py:31-57)."""
 
     def __init__(self, generator: Generator, target=None, pitch_shift=0., device=torch.device("cpu"),
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, door=None,
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, gate=None, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         dev = torch.device(device)
         if dev.type != "cuda":
             dev = generator._module_device()     # the reference defaults to CPU; there is no CPU path here
-        super().__init__(generator, 1, target, pitch_shift, dev, block_size, extra_size, use_phase_vocoder, f0_estimation, use_graph, alpha, door,
+        super().__init__(generator, 1, target, pitch_shift, dev, block_size, extra_size, use_phase_vocoder, f0_estimation, use_graph, alpha, gate, door,
                          crossfade_size, sola_search_size, last_delay_size, auto_pitch, pitch_track)
 
     @torch.no_grad()
