@@ -581,6 +581,44 @@ int tvc_stream_gate_f32(tvc_ctx* ctx, void* stream, const float* x, int64_t n, i
                         int block, int sub, int look, int hold, int attack, int release, float hysteresis_db, float range_db,
                         const float* threshold_db, int32_t* open, int32_t* hold_state, float* gain, float* level_db);
 
+/* The streams' spectral suppressor (extension): one launch in front of tvc_stream_push_f32, one workgroup per stream, a stateful short-time
+ * spectral gain on the 24 kHz block x [S][block] before it enters the rolling window.  Frames of NF = 640 samples at a hop of `hop` (160 or
+ * 320), analysis and synthesis window w[n] = sqrt(0.5 - 0.5 cos(2 pi n / 640)) (tabulated in fp64, rounded once), synthesis scale
+ * 2 hop / 640 (the overlap-add of w^2 is then exactly 1); block % hop == 0; the output is the processed input delayed by D = 640 - hop.
+ * State per stream, on the device, advanced in place; a stream starts with all of it zero:
+ *   hist [S][D] raw input tail, ola [S][D] overlap-add tail, smooth [S][321] smoothed power per bin, noise [S][321] noise power per bin,
+ *   frames [S] int32 frames counted so far (saturating at 2^30).
+ * reduction_db [S] fp32 on the device is read when the kernel runs: floor = 10^(-max(reduction_db, 0) / 20).  a_s, a_n, clamp, beta (fp32)
+ * and warm (int) are baked in; NMIN = TVC_STREAM_DENOISE_NMIN, tiny = 1e-30f.  For frame m of the stream, in order, with
+ * f = (hist ++ x)[m hop .. m hop + 640):
+ *   1. all 640 samples of f are +-0: the frame adds nothing to the overlap-add and leaves smooth, noise and frames as they are (a muted
+ *      microphone neither counts as warm-up nor drags the estimate to zero);
+ *   2. otherwise X = rfft(w f) (321 bins), P = re^2 + im^2, and per bin
+ *        smooth = a_s smooth + (1 - a_s) P
+ *        frames < warm:  noise = noise + (P - noise) / (frames + 1)           (a running mean)
+ *        otherwise:      noise = a_n noise + (1 - a_n) min(P, max(clamp noise, NMIN))
+ *        G = max(floor, 1 - beta noise / max(smooth, tiny));  Y = G X;   then frames += 1;
+ *   3. irfft(Y) w (2 hop / 640) is added into the overlap-add accumulator in ascending frame order: an output sample is the carried ola
+ *      plus at most 640 / hop contributions, added in that order;
+ *   4. hop finished samples leave.
+ * noise_db [S] (nullable) = 10 log10(max(sum_k m_k noise[k] / (640 * 320), 1e-20)) after the block, m_k = 1 for k = 0 and 320, else 2: the
+ * estimate in dB re full scale per sample.  Every rule is continuous in the data (the branches are min / max and two integer tests).
+ * Output and state do not depend, bit for bit, on how a stream is cut into blocks, on S or on the other streams; reduction_db == 0 gives
+ * G == 1 (the delayed input within the transforms' rounding; the state still advances); a stream of zeros emits zeros and keeps its state.
+ * out may be x.  No workspace.
+ *
+ * tvc_stream_denoise_geometry (host only: no context, no device) holds the limits: hop is 160 or 320, block >= hop a multiple of hop,
+ * block / hop <= 4096.  Anything else returns TVC_ERR_ARG; otherwise frames = block / hop and delay = 640 - hop (out pointers are nullable).
+ * tvc_stream_denoise_geometry_message gives the reason of a refusal ("" for a legal geometry), valid until the thread's next call.
+ * tvc_stream_denoise_f32 refuses the same geometries with that reason in tvc_last_error, and: a NULL pointer (noise_db is exempt), S <= 0,
+ * a_s or a_n outside [0, 1), clamp < 1, beta < 0, warm < 0, any scalar that is not finite - all with TVC_ERR_ARG before anything is launched. */
+#define TVC_STREAM_DENOISE_NMIN 1e-12f
+int tvc_stream_denoise_geometry(int block, int hop, int* frames, int* delay);
+const char* tvc_stream_denoise_geometry_message(int block, int hop);
+int tvc_stream_denoise_f32(tvc_ctx* ctx, void* stream, const float* x, float* out, int S, int block, int hop, float a_s, float a_n, float clamp,
+                           float beta, int warm, const float* reduction_db, float* hist, float* ola, float* smooth, float* noise, int32_t* frames,
+                           float* noise_db);
+
 /* measurement ----------------------------------------------------------------------------- */
 /* on = 1: every stage (and every FilterNet block) is bracketed by a hipEvent pair on the launch stream (19 pairs per
  * convert, ~0.1 ms of a 8.4 ms step); on = 2: only the `filter_net` region (the roofline's kernel group); on = 0: off.

@@ -35,6 +35,12 @@ re full scale) for longer than `--gate-hold` fades to `--gate-range` (default: s
 `--gate-hysteresis`.  The gate reads the input window the converter already holds, aligned with the played block by SOLA's own lag, so the
 look-ahead costs no latency.  Times are in milliseconds, rounded to whole 10 ms sub-frames.  The defaults are guesses: nobody has listened yet.
 
+`--denoise DB` (extension) puts a spectral suppressor in front of the converter, on the device: steady noise under the speech (fan, room,
+laptop microphone) is estimated per frequency bin - from the first `--denoise-warmup` of sound, then adapting over `--denoise-adapt` - and
+every bin is turned down by up to DB where the estimate explains its power (`--denoise-strength`: the over-subtraction factor;
+`--denoise-smooth`: the time constant of the power the gain follows).  The converter, the pitch tracker and the gate then see the cleaned
+signal.  It costs 640 - `--denoise-hop` samples of latency (20 ms at hop 160, 13.3 ms at 320).  The defaults are guesses: nobody has listened yet.
+
 `--streams S` feeds S copies of the input as S concurrent streams through one BatchedStreamInfer
 (one batched convert + one SOLA launch per block) and reports the p50 / p95 block latency against the
 real-time budget (chunk / 24 kHz = 80 ms for the default 1920-sample chunk).
@@ -49,14 +55,15 @@ import torch
 
 from tinyvc_amd import audio_io
 from infer import load_generator, load_target
-from tinyvc_amd.engine import sola_geometry, stream_gate_geometry, stream_resample_geometry
-from tinyvc_amd.module.infer import BatchedStreamInfer, StreamDoor, StreamGate
-from tinyvc_amd.module.infer.stream import check_gate_lookahead, check_window
+from tinyvc_amd.engine import sola_geometry, stream_denoise_geometry, stream_gate_geometry, stream_resample_geometry
+from tinyvc_amd.module.infer import BatchedStreamInfer, StreamDenoise, StreamDoor, StreamGate
+from tinyvc_amd.module.infer.stream import check_gate_lookahead, check_window, denoise_constants
 from tinyvc_amd.module.tinyvc.feature_retrieval import (PitchTrack, add_alpha_argument, add_blend_argument, alpha_keywords, pitch_register,
                                                         semitones_between)
 
 FRAMES_PER_SECOND = 50      # 24 kHz / 480 samples
 GATE_SUB_FRAME = 240        # the gate's sub-frame: 10 ms at 24 kHz
+DENOISE_DEFAULTS = dict(hop=160, strength=2.0, adapt_s=1.0, smooth_ms=40.0, warmup_ms=200.0)      # of --denoise-hop / -strength / -adapt / -smooth / -warmup
 GATE_MS = dict(hold=200.0, attack=10.0, release=100.0, lookahead=20.0)      # the defaults of --gate-hold / -attack / -release / -lookahead
 
 
@@ -106,6 +113,17 @@ def build_parser():
     p.add_argument("--gate-lookahead", default=None, type=float, metavar="MS",
                    help=f"how far ahead of the played sample the gate looks in the input it already holds: no added latency, at most "
                         f"--crossfade + --lookahead samples (default {GATE_MS['lookahead']:g})")
+    p.add_argument("--denoise", default=None, type=float, metavar="DB",
+                   help="spectral noise suppressor on the device in front of the converter: every frequency bin is turned down by up to DB where the "
+                        "noise estimate explains its power (0: the delayed input).  Absent: no suppressor.  It adds 640 - --denoise-hop samples of "
+                        "latency.  The defaults of the five flags below are guesses: nobody has listened yet")
+    p.add_argument("--denoise-hop", default=None, type=int, choices=[160, 320], help="hop of the 640-sample frames: 20 ms or 13.3 ms of delay (default 160)")
+    p.add_argument("--denoise-strength", default=None, type=float, metavar="X", help=f"over-subtraction factor, >= 0 (default {DENOISE_DEFAULTS['strength']:g})")
+    p.add_argument("--denoise-adapt", default=None, type=float, metavar="S", help=f"time constant of the noise estimate in seconds (default {DENOISE_DEFAULTS['adapt_s']:g})")
+    p.add_argument("--denoise-smooth", default=None, type=float, metavar="MS",
+                   help=f"time constant of the smoothed power the gain follows, in milliseconds (default {DENOISE_DEFAULTS['smooth_ms']:g})")
+    p.add_argument("--denoise-warmup", default=None, type=float, metavar="MS",
+                   help=f"the first this many milliseconds of sound in a stream are taken for noise (default {DENOISE_DEFAULTS['warmup_ms']:g})")
     # file-driven operation (no audio devices on a GPU node)
     p.add_argument("--input-wav", default=None, help="read the microphone signal from this WAV instead of a device")
     p.add_argument("--output-wav", default=None, help="write the converted stream here")
@@ -221,12 +239,37 @@ def check_gate(args, block=None):
                 attack_size=n["attack"] * GATE_SUB_FRAME, release_size=n["release"] * GATE_SUB_FRAME, lookahead_size=n["lookahead"] * GATE_SUB_FRAME)
 
 
+def check_denoise(args, block=None):
+    """--denoise and its five companions against each other and the block, before anything is loaded: sys.exit with a message, or the
+    StreamDenoise keywords (None without --denoise).  `block`: the model's block length when it is not -c (--resample)"""
+    flags = dict(hop="hop", strength="strength", adapt="adapt_s", smooth="smooth_ms", warmup="warmup_ms")
+    extra = [f"--denoise-{k}" for k in flags if getattr(args, f"denoise_{k}") is not None]
+    if args.denoise is None:
+        if extra:
+            sys.exit(f"infer_streaming.py: {' '.join(extra)} without --denoise DB: there is no suppressor to set")
+        return None
+    chunk = args.chunk if block is None else block
+    if math.isnan(args.denoise):
+        sys.exit("infer_streaming.py: --denoise: a reduction in dB (0: the delayed input)")
+    kw = {name: (DENOISE_DEFAULTS[name] if getattr(args, f"denoise_{k}") is None else getattr(args, f"denoise_{k}")) for k, name in flags.items()}
+    for k, name in flags.items():
+        if not (kw[name] >= 0 and math.isfinite(kw[name])):
+            sys.exit(f"infer_streaming.py: --denoise-{k} {kw[name]}: a finite number >= 0")
+    try:
+        stream_denoise_geometry(chunk, kw["hop"])
+        denoise_constants(clamp=2.0, **kw)
+    except ValueError as e:
+        sys.exit(f"infer_streaming.py: --denoise: {e}")
+    return dict(reduction_db=args.denoise, **kw)
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     block = check_resample(args)
     track_kw = check_auto_pitch(args, block)
     check_geometry(args, block)
     gate_kw = check_gate(args, block)
+    denoise_kw = check_denoise(args, block)
     device = torch.device(args.device)
     if device.type != "cuda":
         sys.exit("infer_streaming.py: this build runs on an AMD GPU only; pass -d cuda")
@@ -268,11 +311,18 @@ def main(argv=None):
         print(f"Noise gate at {gate_kw['threshold_db']:g} dB (hysteresis {gate.hysteresis_db:g} dB, range {gate.range_db:g} dB): hold {gate.hold_size * to_ms:g} ms, "
               f"attack {gate.attack_size * to_ms:g} ms, release {gate.release_size * to_ms:g} ms, look-ahead {gate.lookahead_size * to_ms:g} ms "
               f"in {GATE_SUB_FRAME * to_ms:g} ms sub-frames")
+    denoise = None
+    if denoise_kw is not None:
+        denoise = StreamDenoise(S, door.block_size, device=device, **denoise_kw)
+        print(f"Noise suppressor: up to {denoise_kw['reduction_db']:g} dB per bin (strength {denoise.strength:g}, smoothing {denoise.smooth_ms:g} ms, adaptation "
+              f"{denoise.adapt_s:g} s, warm-up {denoise.warmup_ms:g} ms) in 640-sample frames at a hop of {denoise.hop}: "
+              f"{denoise.delay_size / 24000 * 1e3:.1f} ms of delay")
     stream = BatchedStreamInfer(gen, n_streams=S, pitch_shift=pitch_shift, block_size=door.block_size, device=device, extra_size=args.extra,
                                 f0_estimation=args.f0_estimation, door=door, auto_pitch=True if track is not None else None, pitch_track=track,
-                                crossfade_size=args.crossfade, sola_search_size=args.sola_search, last_delay_size=args.lookahead, gate=gate, **alpha_kw)
+                                crossfade_size=args.crossfade, sola_search_size=args.sola_search, last_delay_size=args.lookahead, gate=gate, denoise=denoise, **alpha_kw)
     lo, hi = stream.latency_seconds
-    print(f"Latency {lo * 1e3:.1f} to {hi * 1e3:.1f} ms (cross-fade {args.crossfade} + look-ahead {args.lookahead} + lag 0 .. {args.sola_search} samples at 24 kHz"
+    delay = f" + the suppressor's {denoise.delay_size}" if denoise is not None else ""
+    print(f"Latency {lo * 1e3:.1f} to {hi * 1e3:.1f} ms (cross-fade {args.crossfade} + look-ahead {args.lookahead} + lag 0 .. {args.sola_search}{delay} samples at 24 kHz"
           f"{', and the resampling filters' if block is not None else ''}) plus the {door.block_size / 24000 * 1e3:.0f} ms block")
     stream.target = tgt
     stream.init_buffer()
@@ -321,6 +371,9 @@ def main(argv=None):
     if gate is not None and blocks:
         for s_, n_open in enumerate(ended_open.tolist()):
             print(f"stream {s_}: gate open at the end of {n_open} of {len(blocks)} blocks ({100.0 * n_open / len(blocks):.0f} %)")
+    if denoise is not None and blocks:
+        for s_, db in enumerate(denoise.noise_db.tolist()):
+            print(f"stream {s_}: noise estimate {db:.1f} dB re full scale")
     if len(lat) > 3:
         l = np.sort(np.array(lat[3:])) * 1e3
         budget = args.chunk / args.sample_rate * 1e3

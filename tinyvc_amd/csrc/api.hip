@@ -1112,6 +1112,37 @@ int tvc_stream_gate_f32(tvc_ctx* ctx, void* stream, const float* x, int64_t n, i
     return run_stream_gate(ctx, (hipStream_t)stream, x, n, base, shift, y, out, S, g);
 }
 
+int tvc_stream_denoise_geometry(int block, int hop, int* frames, int* delay) { return stream_denoise_geometry(block, hop, frames, delay, nullptr, 0); }
+
+const char* tvc_stream_denoise_geometry_message(int block, int hop) {
+    static thread_local char why[96];
+    stream_denoise_geometry(block, hop, nullptr, nullptr, why, sizeof(why));
+    return why;
+}
+
+int tvc_stream_denoise_f32(tvc_ctx* ctx, void* stream, const float* x, float* out, int S, int block, int hop, float a_s, float a_n, float clamp,
+                           float beta, int warm, const float* reduction_db, float* hist, float* ola, float* smooth, float* noise, int32_t* frames,
+                           float* noise_db) {
+    if (!ctx) return TVC_ERR_ARG;
+    char why[96];
+    if (stream_denoise_geometry(block, hop, nullptr, nullptr, why, sizeof(why)) != 0) return fail(ctx, TVC_ERR_ARG, "tvc_stream_denoise_f32: %s", why);
+    if (!x || !out || !reduction_db || !hist || !ola || !smooth || !noise || !frames || S <= 0)
+        return fail(ctx, TVC_ERR_ARG, "tvc_stream_denoise_f32: bad argument (a NULL pointer or S <= 0)");
+    if (!std::isfinite(a_s) || !std::isfinite(a_n) || !std::isfinite(clamp) || !std::isfinite(beta))
+        return fail(ctx, TVC_ERR_ARG, "tvc_stream_denoise_f32: a_s = %g, a_n = %g, clamp = %g, beta = %g: not all finite", (double)a_s, (double)a_n, (double)clamp,
+                    (double)beta);
+    if (a_s < 0.f || a_s >= 1.f || a_n < 0.f || a_n >= 1.f)
+        return fail(ctx, TVC_ERR_ARG, "tvc_stream_denoise_f32: a_s = %g or a_n = %g is outside [0, 1)", (double)a_s, (double)a_n);
+    if (clamp < 1.f) return fail(ctx, TVC_ERR_ARG, "tvc_stream_denoise_f32: clamp = %g is below 1", (double)clamp);
+    if (beta < 0.f) return fail(ctx, TVC_ERR_ARG, "tvc_stream_denoise_f32: beta = %g is negative", (double)beta);
+    if (warm < 0) return fail(ctx, TVC_ERR_ARG, "tvc_stream_denoise_f32: warm = %d is negative", warm);
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    StreamDenoise d;
+    d.block = block; d.hop = hop; d.a_s = a_s; d.a_n = a_n; d.clamp = clamp; d.beta = beta; d.warm = warm;
+    d.reduction_db = reduction_db; d.hist = hist; d.ola = ola; d.smooth = smooth; d.noise = noise; d.frames = frames; d.noise_db = noise_db;
+    return run_stream_denoise(ctx, (hipStream_t)stream, x, out, S, d);
+}
+
 int tvc_stream_resample_geometry(int in_freq, int out_freq, int64_t n_in, int64_t* n_out, int* hist, int* delay) {
     if (!n_out || !hist || !delay) return TVC_ERR_ARG;
     return stream_resample_geometry(in_freq, out_freq, n_in, n_out, hist, delay);

@@ -9,8 +9,10 @@
 // 8 waves = 8 consecutive frames of one utterance per workgroup, so the [961][T] spectrogram is written / read in
 // 32-byte runs along time through an LDS transpose.  ~0.1 MFLOP per frame instead of the 3.7 MFLOP of the half-size
 // real-DFT GEMMs this replaces (frontend.hip, decoder.hip keep those behind -DTVC_FFT=0).
+// The wave-level pieces (the small DFTs, fft960_wave, bitrev6) live in fft_wave.h, which denoise.hip shares.
 // Twiddles come from fp64-computed tables (pack.hip pack_constants): tw960[j] = (cos, sin)(2 pi j / 960),
 // tw1920[k] = (cos, sin)(2 pi k / 1920), hann[n] = 0.5 - 0.5 cos(2 pi n / 1920).
+#include "fft_wave.h"
 #include "small_kernels.h"
 #include "tvc_common.h"
 
@@ -21,80 +23,6 @@ namespace {
 constexpr int kM = 960;          // complex FFT size
 constexpr int kFW = 8;           // frames (waves) per workgroup
 
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-// a * (c + i SIGN s)
-template <int SIGN>
-__device__ __forceinline__ float2 cmul_tw(float2 a, float2 w) {
-    const float s = SIGN < 0 ? -w.y : w.y;
-    return make_float2(fmaf(a.x, w.x, -a.y * s), fmaf(a.x, s, a.y * w.x));
-}
-// multiply by SIGN * i
-template <int SIGN>
-__device__ __forceinline__ float2 mul_i(float2 a) { return SIGN < 0 ? make_float2(a.y, -a.x) : make_float2(-a.y, a.x); }
-
-// 3-point DFT in place: y[k] = sum_n x[n] e^(SIGN 2 pi i n k / 3)
-template <int SIGN>
-__device__ __forceinline__ void dft3(float2& a, float2& b, float2& c) {
-    const float s = 0.86602540378443864676f;
-    const float2 t = cadd(b, c), d = csub(b, c);
-    const float2 m = make_float2(fmaf(-0.5f, t.x, a.x), fmaf(-0.5f, t.y, a.y));
-    const float2 js = mul_i<SIGN>(make_float2(s * d.x, s * d.y));     // SIGN i s (b - c)
-    a = cadd(a, t);
-    b = cadd(m, js);
-    c = csub(m, js);
-}
-// 5-point DFT in place
-template <int SIGN>
-__device__ __forceinline__ void dft5(float2& x0, float2& x1, float2& x2, float2& x3, float2& x4) {
-    const float c1 = 0.30901699437494742410f, c2 = -0.80901699437494742410f;    // cos(2 pi / 5), cos(4 pi / 5)
-    const float s1 = 0.95105651629515357212f, s2 = 0.58778525229247312917f;     // sin(2 pi / 5), sin(4 pi / 5)
-    const float2 t1 = cadd(x1, x4), t2 = cadd(x2, x3), t3 = csub(x1, x4), t4 = csub(x2, x3);
-    const float2 m1 = make_float2(fmaf(c1, t1.x, fmaf(c2, t2.x, x0.x)), fmaf(c1, t1.y, fmaf(c2, t2.y, x0.y)));
-    const float2 m2 = make_float2(fmaf(c2, t1.x, fmaf(c1, t2.x, x0.x)), fmaf(c2, t1.y, fmaf(c1, t2.y, x0.y)));
-    const float2 u1 = mul_i<SIGN>(make_float2(fmaf(s1, t3.x, s2 * t4.x), fmaf(s1, t3.y, s2 * t4.y)));   // SIGN i (s1 t3 + s2 t4)
-    const float2 u2 = mul_i<SIGN>(make_float2(fmaf(s2, t3.x, -s1 * t4.x), fmaf(s2, t3.y, -s1 * t4.y)));  // SIGN i (s2 t3 - s1 t4)
-    x0 = cadd(x0, cadd(t1, t2));
-    x1 = cadd(m1, u1);
-    x4 = csub(m1, u1);
-    x2 = cadd(m2, u2);
-    x3 = csub(m2, u2);
-}
-
-// register slot of output index k2 of the 15-point DFT below
-__device__ __forceinline__ constexpr int slot15(int k2) { return 5 * (k2 % 3) + k2 / 3; }
-
-// Complex FFT of 960 points held by one wavefront.  In: v[n2] = z[64 n2 + lane].  Out: v[slot15(k2)] = Z[15 bitrev6(lane) + k2]
-// with Z[k] = sum_m z[m] e^(SIGN 2 pi i m k / 960) (unnormalised).
-template <int SIGN>
-__device__ __forceinline__ void fft960_wave(float2 (&v)[15], int lane, const float2* __restrict__ tw960) {
-    // 15-point DFT over n2 = 5 na + nb -> k2 = ka + 3 kb
-#pragma unroll
-    for (int nb = 0; nb < 5; ++nb) dft3<SIGN>(v[nb], v[5 + nb], v[10 + nb]);          // v[5 ka + nb]
-#pragma unroll
-    for (int ka = 1; ka < 3; ++ka)
-#pragma unroll
-        for (int nb = 1; nb < 5; ++nb) v[5 * ka + nb] = cmul_tw<SIGN>(v[5 * ka + nb], tw960[64 * nb * ka]);   // W_15^(nb ka)
-#pragma unroll
-    for (int ka = 0; ka < 3; ++ka) dft5<SIGN>(v[5 * ka], v[5 * ka + 1], v[5 * ka + 2], v[5 * ka + 3], v[5 * ka + 4]);   // v[5 ka + kb]
-    // twiddle W_960^(n1 k2), n1 = lane
-#pragma unroll
-    for (int k2 = 1; k2 < 15; ++k2) v[slot15(k2)] = cmul_tw<SIGN>(v[slot15(k2)], tw960[lane * k2]);
-    // 64-point DIF FFT across the lanes
-#pragma unroll
-    for (int h = 32; h >= 1; h >>= 1) {
-        const bool lower = (lane & h) != 0;
-        const float2 w = tw960[(480 / h) * (lane & (h - 1))];                          // W_(2h)^(lane mod h)
-#pragma unroll
-        for (int i = 0; i < 15; ++i) {
-            const float2 p = make_float2(__shfl_xor(v[i].x, h), __shfl_xor(v[i].y, h));
-            const float2 sum = cadd(v[i], p), dif = csub(p, v[i]);                      // lower lanes: partner is the upper element
-            v[i] = lower ? (h > 1 ? cmul_tw<SIGN>(dif, w) : dif) : sum;
-        }
-    }
-}
-
-__device__ __forceinline__ int bitrev6(int l) { return (int)(__brev((unsigned)l) >> 26); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // spec[b][k][t] = | sum_n hann[n] x_b[(t + 1) * 480 - 960 + n (reflected)] e^(-2 pi i k n / 1920) |, k = 0..960, t = 0..T-1

@@ -415,7 +415,8 @@ struct Packer {
 }  // namespace
 
 // Tables of the wave-level 1920-point FFTs (fft.hip), computed in fp64: (cos, sin)(2 pi j / 960), (cos, sin)(2 pi k / 1920),
-// periodic Hann window.
+// periodic Hann window.  Behind them the tables of the streams' spectral suppressor (denoise.hip), fp64-made too: the square-root Hann
+// window of its 640-sample frames, (cos, sin)(2 pi j / 320) and (cos, sin)(2 pi k / 640).
 void pack_constants(tvc_ctx* ctx, ArenaBuilder* ab) {
     const int N = kNfft;
     const double two_pi = 6.283185307179586476925286766559;
@@ -433,6 +434,20 @@ void pack_constants(tvc_ctx* ctx, ArenaBuilder* ab) {
     ab->put(&ctx->fft_tw1920, t1920);
     ab->put(&ctx->fft_hann, hann);
     ab->put(&ctx->sola_part, std::vector<float>(kSolaPartFloats, 0.f));   // device scratch, not a table (sola.hip)
+    const int F = kDenoiseFrame;
+    std::vector<float> win(F), t320(2 * (F / 2)), t640(2 * (F / 2 + 1));
+    for (int n = 0; n < F; ++n) win[n] = (float)std::sqrt(0.5 - 0.5 * std::cos(two_pi * n / F));
+    for (int j = 0; j < F / 2; ++j) {
+        t320[2 * j] = (float)std::cos(two_pi * j / (F / 2));
+        t320[2 * j + 1] = (float)std::sin(two_pi * j / (F / 2));
+    }
+    for (int k = 0; k <= F / 2; ++k) {
+        t640[2 * k] = (float)std::cos(two_pi * k / F);
+        t640[2 * k + 1] = (float)std::sin(two_pi * k / F);
+    }
+    ab->put(&ctx->dn_win, win);
+    ab->put(&ctx->dn_tw320, t320);
+    ab->put(&ctx->dn_tw640, t640);
 }
 
 void pack_checkpoint(tvc_ctx* ctx, ArenaBuilder* ab, std::string* missing_enc, std::string* missing_dec) {

@@ -156,6 +156,9 @@ struct tvc_ctx {
     const float* fft_hann = nullptr;
     const float* pitch_freq = nullptr;  // [512]
     const float* sola_part = nullptr;   // scratch of the split SOLA search: (best value, best lag) per (stream, lag group); kSolaPartFloats floats
+    const float* dn_win = nullptr;      // denoise.hip tables: sqrt-Hann window [640], (cos, sin)(2 pi j / 320) [320], (cos, sin)(2 pi k / 640) [321]
+    const float* dn_tw320 = nullptr;
+    const float* dn_tw640 = nullptr;
 
     // encoder
     tvc::PackedW enc_in;  // ssl(384) and pitch(128) input 1x1 stacked: M = 512
@@ -492,6 +495,24 @@ struct StreamGate {
 int stream_gate_geometry(int block, int sub, int look, int hold, int attack, int release, int* nsub, int* look_samples, char* why, size_t why_bytes);
 // (the caller has checked the geometry; x [S][n], y and out [S][block], out may be y; shift [S] optional)
 int run_stream_gate(tvc_ctx*, hipStream_t, const float* x, int64_t n, int64_t base, const int32_t* shift, const float* y, float* out, int S, const StreamGate& g);
+// the spectral suppressor in front of the window (denoise.hip).  Frames of kDenoiseFrame samples at a hop of 160 or 320
+constexpr int kDenoiseFrame = 640, kDenoiseBins = kDenoiseFrame / 2 + 1, kDenoiseMaxFrames = 4096;
+struct StreamDenoise {
+    int block, hop;                        // samples
+    float a_s, a_n, clamp, beta;           // smoothing of the power, adaptation and clamp of the noise estimate, over-subtraction
+    int warm;                              // frames the noise estimate is a running mean over
+    const float* reduction_db;             // [S] device, read when the kernel runs
+    float* hist;                           // [S][640 - hop] device state, read and advanced in place: raw input tail, overlap-add tail,
+    float* ola;                            //   smoothed power and noise power per bin [S][321], frames counted
+    float* smooth;
+    float* noise;
+    int32_t* frames;
+    float* noise_db;                       // [S] device, optional: the noise estimate in dB re full scale per sample
+};
+// the legal suppressor geometries, in one place (denoise.hip): 0, or TVC_ERR_ARG with the reason in `why`; every out pointer is nullable
+int stream_denoise_geometry(int block, int hop, int* frames, int* delay, char* why, size_t why_bytes);
+// (the caller has checked the geometry and the scalars; x and out [S][block], out may be x)
+int run_stream_denoise(tvc_ctx*, hipStream_t, const float* x, float* out, int S, const StreamDenoise& d);
 int64_t resample_out_len(int64_t n, int orig_freq, int new_freq);
 int run_resample(tvc_ctx*, hipStream_t, const float* x, float* y, int rows, int64_t n, int orig_freq, int new_freq);
 int stream_resample_geometry(int in_freq, int out_freq, int64_t n_in, int64_t* n_out, int* hist, int* delay);

@@ -134,6 +134,21 @@ def stream_gate_geometry(block, sub, look=0, hold=0, attack=1, release=1, lib=No
     return nsub.value, look_samples.value
 
 
+def stream_denoise_geometry(block, hop=160, lib=None):
+    """tvc_stream_denoise_geometry (no context, no device) -> (frames, delay) of a spectral suppressor over `block`-sample blocks at a hop of
+    `hop` samples: frames per block and the samples of delay it adds (640 - hop).  ValueError, with the library's reason, for what the
+    kernel does not take."""
+    for x, name in ((block, "block"), (hop, "hop")):
+        if isinstance(x, bool) or not isinstance(x, numbers.Integral) or abs(x) >= 2 ** 31:
+            raise ValueError(f"stream denoise geometry: {name} must be an integer, got {x!r}")
+    block, hop = int(block), int(hop)
+    lib = lib if lib is not None else _lib.load_library()
+    frames, delay = ctypes.c_int(), ctypes.c_int()
+    if lib.tvc_stream_denoise_geometry(block, hop, ctypes.byref(frames), ctypes.byref(delay)) != 0:
+        raise ValueError(f"stream denoise geometry: {lib.tvc_stream_denoise_geometry_message(block, hop).decode()}")
+    return frames.value, delay.value
+
+
 def pitch_class_table():
     """PitchEstimator.id2freq over ids 0..511 (reference encoder.py:48-54), on the host."""
     ids = torch.arange(spec.PITCH_CLASSES).to(torch.float)
@@ -970,6 +985,35 @@ class Engine:
         self._ok(self.lib.tvc_stream_gate_f32(self.ctx, self._stream(), _ptr(x), n, int(base), _ptr(shift), _ptr(y), _ptr(out), S, gate.block_size, sub, look,
                                               hold, attack, release, hysteresis_db, range_db, _ptr(gate.threshold_db), _ptr(gate.open), _ptr(gate.hold),
                                               _ptr(gate.gain), _ptr(gate.level_db)), "tvc_stream_gate_f32")
+        return out
+
+    def stream_denoise(self, blocks, denoise, out=None):
+        """The spectral suppressor in front of the window (tvc_stream_denoise_f32): blocks [S, block] the streams' new 24 kHz samples,
+        `denoise` a module.infer.StreamDenoise (reduction and state on the device, advanced in place).  Returns the suppressed blocks,
+        delayed by denoise.delay_size samples: a new tensor, or `out` (which may be blocks)."""
+        _check_dev(blocks, "blocks", self.device)
+        if blocks.dim() != 2 or blocks.dtype != _F32 or not blocks.is_contiguous():
+            raise ValueError(f"stream_denoise: blocks must be contiguous fp32 [S, block], got {blocks.dtype} {tuple(blocks.shape)}")
+        S = blocks.shape[0]
+        if tuple(blocks.shape) != (denoise.n_streams, denoise.block_size):
+            raise ValueError(f"stream_denoise: a suppressor for {denoise.n_streams} streams of {denoise.block_size}-sample blocks, blocks is {tuple(blocks.shape)}")
+        D = denoise.delay_size
+        for t, name, dt, shape in ((denoise.reduction_db, "reduction_db", _F32, (S,)), (denoise.hist, "hist", _F32, (S, D)), (denoise.ola, "ola", _F32, (S, D)),
+                                   (denoise.smooth, "smooth", _F32, (S, 321)), (denoise.noise, "noise", _F32, (S, 321)),
+                                   (denoise.frames, "frames", torch.int32, (S,)), (denoise.noise_db, "noise_db", _F32, (S,))):
+            _check_dev(t, f"denoise.{name}", self.device)
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"stream_denoise: denoise.{name} must be contiguous {dt} {list(shape)}, got {t.dtype} {tuple(t.shape)}")
+        if out is None:
+            out = torch.empty_like(blocks)
+        else:
+            _check_dev(out, "out", self.device)
+            if out.dtype != _F32 or out.shape != blocks.shape or not out.is_contiguous():
+                raise ValueError(f"stream_denoise: out must be contiguous fp32 {tuple(blocks.shape)}, got {out.dtype} {tuple(out.shape)}")
+        hop, a_s, a_n, clamp, beta, warm = denoise.params()[2:]
+        self._ok(self.lib.tvc_stream_denoise_f32(self.ctx, self._stream(), _ptr(blocks), _ptr(out), S, denoise.block_size, hop, a_s, a_n, clamp, beta, warm,
+                                                 _ptr(denoise.reduction_db), _ptr(denoise.hist), _ptr(denoise.ola), _ptr(denoise.smooth), _ptr(denoise.noise),
+                                                 _ptr(denoise.frames), _ptr(denoise.noise_db)), "tvc_stream_denoise_f32")
         return out
 
 

@@ -6,13 +6,16 @@ argument - crossfade_size, sola_search_size, last_delay_size -: a block's first 
 after the first sample of the newest input block came in (shift in [0, search], chosen per block), so the three sizes are the latency a
 listener hears beyond the block itself; look-ahead (last_delay_size) is the right context the converter sees behind the emitted block.  `StreamDoor` (extension) puts a stateful resampler, fused with the int16 conversions and gain, on both
 sides of the block: clients send and receive int16 at their own rates.  `StreamGate` (extension) is a per-stream noise gate on the device,
-one launch behind SOLA: it follows the input window's power under the emitted block and looks ahead in what the window already holds."""
+one launch behind SOLA: it follows the input window's power under the emitted block and looks ahead in what the window already holds.
+`StreamDenoise` (extension) is a per-stream spectral suppressor on the device, one launch in front of the window: noise under speech is
+turned down before the converter, the pitch tracker and the gate see it."""
 import math
 
 import numpy as np
 import torch
 
-from ...engine import SOLA_CROSS, SOLA_DELAY, SOLA_SEARCH, pitch_shifts, sola_geometry, stream_gate_geometry, stream_resample_geometry
+from ...engine import (SOLA_CROSS, SOLA_DELAY, SOLA_SEARCH, pitch_shifts, sola_geometry, stream_denoise_geometry, stream_gate_geometry,
+                       stream_resample_geometry)
 from ..tinyvc.feature_retrieval import PitchTrack, alpha_rows, resolve_alpha, resolve_auto_pitch, target_form
 from .generator import Generator
 
@@ -211,6 +214,103 @@ class StreamGate:
         self.level_db.index_fill_(0, idx, -200.0)
 
 
+DENOISE_FRAME = 640
+DENOISE_BINS = DENOISE_FRAME // 2 + 1
+
+
+def _f32(x):
+    with np.errstate(over="ignore"):      # too large for fp32 is inf, which the callers refuse
+        return float(np.float32(x))
+
+
+def denoise_constants(hop, strength, smooth_ms, adapt_s, clamp, warmup_ms):
+    """The suppressor's baked constants from its settings (ValueError) -> (a_s, a_n, clamp, beta, warm): the two recurrence coefficients
+    a = exp(-hop / (24000 * time constant)), computed in double and rounded to fp32 once (0 for a time constant of 0), clamp and beta =
+    strength as fp32 values, and the warm-up in frames, round(warmup * 24000 / hop).  This is the one place they are computed."""
+    for x, name, least in ((strength, "strength", 0.0), (smooth_ms, "smooth_ms", 0.0), (adapt_s, "adapt_s", 0.0), (clamp, "clamp", 1.0),
+                           (warmup_ms, "warmup_ms", 0.0)):
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or x < least:
+            raise ValueError(f"StreamDenoise: {name} must be a finite number >= {least:g}, got {x!r}")
+    a_s = _f32(math.exp(-hop / (MODEL_RATE * smooth_ms * 1e-3))) if smooth_ms > 0 else 0.0
+    a_n = _f32(math.exp(-hop / (MODEL_RATE * adapt_s))) if adapt_s > 0 else 0.0
+    if a_s >= 1.0 or a_n >= 1.0:
+        raise ValueError(f"StreamDenoise: smooth_ms = {smooth_ms!r} or adapt_s = {adapt_s!r} is so long that its fp32 coefficient is 1: nothing would move")
+    beta, clamp = _f32(strength), _f32(clamp)
+    if not math.isfinite(beta) or not math.isfinite(clamp):
+        raise ValueError(f"StreamDenoise: strength = {strength!r} or clamp = {clamp!r} is not a finite fp32 number")
+    warm = int(round(warmup_ms * 1e-3 * MODEL_RATE / hop))
+    if warm >= 2 ** 30:
+        raise ValueError(f"StreamDenoise: warmup_ms = {warmup_ms!r} is more than 2^30 frames")
+    return a_s, a_n, clamp, beta, warm
+
+
+class StreamDenoise:
+    """The spectral suppressor of a set of streams that advance in lock step (tvc_stream_denoise_f32; its definition is in tinyvc_hip.h): in
+    front of the rolling window every 24 kHz block goes through a short-time spectral gain - 640-sample frames under a square-root Hann
+    window at a hop of `hop` samples, a noise estimate per bin, G = max(floor, 1 - strength * noise / smoothed power), overlap-add - so the
+    window, and with it the converter, the pitch tracker and the gate, see the suppressed signal `delay_size` = 640 - hop samples late.
+      reduction_db [S]   fp32 on the device, read when a block runs: the most a bin is turned down by (floor = 10^(-reduction_db / 20); 0 or
+                         less: the delayed input); `denoise.reduction_db.fill_(...)` / `copy_(...)` moves it between blocks
+      hop                160 or 320 samples: 20 ms or 13.3 ms of delay, four or two frames over every sample
+      strength           the over-subtraction factor beta
+      smooth_ms          time constant of the smoothed power the gain is computed from
+      adapt_s            time constant of the noise estimate once the warm-up is over; it follows a bin up by at most `clamp` times itself
+                         per frame, so speech moves it slowly and a lasting change of the noise is followed
+      warmup_ms          the first frames of a stream that are not all zeros are taken for noise: a running mean over that long
+      hist, ola [S, delay_size], smooth, noise [S, 321], frames [S] int32      the state the next block starts from
+      noise_db [S]       the noise estimate after the last block, dB re full scale per sample: a guide for a gate's threshold
+    The defaults are guesses: nobody has listened to them yet.  Every argument is checked before anything is allocated (ValueError)."""
+
+    def __init__(self, n_streams, block_size, reduction_db=12.0, hop=160, strength=2.0, smooth_ms=40.0, adapt_s=1.0, clamp=2.0, warmup_ms=200.0,
+                 device=None):
+        for x, name in ((n_streams, "n_streams"), (block_size, "block_size"), (hop, "hop")):
+            if isinstance(x, bool) or not isinstance(x, int) or x < 1:
+                raise ValueError(f"StreamDenoise: {name} must be an integer >= 1, got {x!r}")
+        red = [reduction_db] if isinstance(reduction_db, (int, float)) and not isinstance(reduction_db, bool) else reduction_db
+        if isinstance(red, torch.Tensor):
+            red = red.detach().cpu().tolist() if red.dim() == 1 else None
+        if not isinstance(red, (list, tuple)) or len(red) not in (1, n_streams) or not all(
+                isinstance(t, (int, float)) and not isinstance(t, bool) and not math.isnan(t) for t in red):
+            raise ValueError(f"StreamDenoise: reduction_db must be a number of dB (0: no suppression) or one per stream ({n_streams}), got {reduction_db!r}")
+        try:
+            _, self.delay_size = stream_denoise_geometry(block_size, hop)
+        except ValueError as e:
+            raise ValueError(f"StreamDenoise: {e}") from None
+        self.a_s, self.a_n, self.clamp, self.beta, self.warm = denoise_constants(hop, strength, smooth_ms, adapt_s, clamp, warmup_ms)
+        self.n_streams, self.block_size, self.hop = n_streams, block_size, hop
+        self.strength, self.smooth_ms, self.adapt_s, self.warmup_ms = float(strength), float(smooth_ms), float(adapt_s), float(warmup_ms)
+        device = torch.device(device if device is not None else "cuda")
+        if device.type != "cuda" or not torch.cuda.is_available():
+            raise ValueError(f"StreamDenoise: the reduction and the state live on the GPU, where the suppressor's kernel runs; got device {str(device)!r}"
+                             + ("" if torch.cuda.is_available() else " and there is no GPU here"))
+        self.device = device
+        self.reduction_db = torch.tensor([float(t) for t in red] * (n_streams // len(red)), dtype=torch.float32, device=device)
+        self.hist = torch.zeros(n_streams, self.delay_size, dtype=torch.float32, device=device)
+        self.ola = torch.zeros(n_streams, self.delay_size, dtype=torch.float32, device=device)
+        self.smooth = torch.zeros(n_streams, DENOISE_BINS, dtype=torch.float32, device=device)
+        self.noise = torch.zeros(n_streams, DENOISE_BINS, dtype=torch.float32, device=device)
+        self.frames = torch.zeros(n_streams, dtype=torch.int32, device=device)
+        self.noise_db = torch.full((n_streams,), -200.0, dtype=torch.float32, device=device)
+
+    def params(self):
+        """the host values a captured block bakes in: (n_streams, block_size, hop, a_s, a_n, clamp, beta, warm)"""
+        return (self.n_streams, self.block_size, self.hop, self.a_s, self.a_n, self.clamp, self.beta, self.warm)
+
+    def reset(self, streams=None):
+        """Put every stream, or the listed ones, back at the start: empty tails, no estimate, no frame counted - so the warm-up runs again.
+        In-place ops on the state tensors, so it works between replays of a captured graph, which reads them when it runs."""
+        state = (self.hist, self.ola, self.smooth, self.noise, self.frames)
+        if streams is None:
+            for t in state:
+                t.zero_()
+            self.noise_db.fill_(-200.0)
+            return
+        idx = torch.as_tensor(list(streams), dtype=torch.int64, device=self.device)
+        for t in state:
+            t.index_fill_(0, idx, 0)
+        self.noise_db.index_fill_(0, idx, -200.0)
+
+
 class BatchedStreamInfer:
     """`target`: one index for every stream ([1, 768, N]) or one per stream ([S, 768, N], or a list of S [1, 768, N_s] tensors), prepared
     once and cached on those tensors - or a feature_retrieval.Blend of several (its weights are read on the device when a block runs:
@@ -227,6 +327,10 @@ class BatchedStreamInfer:
     in front of the door), driven by the input window and `last_shift` on the device; the SOLA buffer and the window stay ungated.
     `gate.threshold_db.fill_(...)` / `copy_(...)` and `gate.reset(...)` between blocks keep a captured graph; None (the default) is the
     ungated stream, launch for launch.
+    `denoise` (a StreamDenoise of the same n_streams and block_size): every block goes through the spectral suppressor, one launch in front of
+    the window (behind the door's input side), so the converter, the pitch tracker and the gate see the suppressed signal; it adds
+    `denoise.delay_size` samples of latency.  `denoise.reduction_db.fill_(...)` / `copy_(...)` and `denoise.reset(...)` between blocks keep a
+    captured graph; None (the default) is the stream without it, launch for launch.
     `crossfade_size`, `sola_search_size`, `last_delay_size` (kept as the attribute `last_dilay_size`, the reference's spelling): the tail's
     geometry in 24 kHz samples, within engine.sola_geometry's limits; `latency_samples` / `latency_seconds` give the resulting range.  The
     attributes are plain, as in the reference: one changed after construction takes effect at the next init_buffer(), which checks them again
@@ -235,7 +339,7 @@ class BatchedStreamInfer:
     shorter than the three sizes say, and a look-ahead shorter than the pad is refused."""
 
     def __init__(self, generator: Generator, n_streams=1, target=None, pitch_shift=0., device=None,
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, gate=None, door=None,
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, denoise=None, gate=None, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         check_window(block_size, extra_size, crossfade_size, sola_search_size, last_delay_size, auto_pitch is not None and auto_pitch is not False)
         share = resolve_alpha(alpha, n_streams) if alpha is not None else None      # refused here, before anything is allocated
@@ -245,6 +349,9 @@ class BatchedStreamInfer:
         if gate is not None and (gate.n_streams, gate.block_size) != (n_streams, block_size):
             raise ValueError(f"gate: built for {gate.n_streams} streams of {gate.block_size}-sample blocks, the streams are {n_streams} of {block_size}")
         self.gate = gate
+        if denoise is not None and (denoise.n_streams, denoise.block_size) != (n_streams, block_size):
+            raise ValueError(f"denoise: built for {denoise.n_streams} streams of {denoise.block_size}-sample blocks, the streams are {n_streams} of {block_size}")
+        self.denoise = denoise
         self.auto_pitch = auto_pitch if auto_pitch is not False else None
         self.pitch_track = pitch_track
         self._own_track = pitch_track is None
@@ -281,9 +388,11 @@ class BatchedStreamInfer:
         """(min, max) 24 kHz samples between the first sample of the newest input block and the first sample of the block emitted for it:
         crossfade + delay .. crossfade + search + delay, by the lag the search picks, LESS the pad of a window that is not whole 480-sample
         frames (`pad_size`: convert pads the window at its end, the tail counts from the end of the padded conversion, so that much of the
-        look-ahead is padding and the block leaves that much earlier); the door's two filters come on top in latency_seconds"""
+        look-ahead is padding and the block leaves that much earlier), PLUS the suppressor's delay_size when there is one; the door's two
+        filters come on top in latency_seconds"""
         _, lo, hi = sola_geometry(self.block_size, self.crossfade_size, self.sola_search_size, self.last_dilay_size)
-        return lo - self.pad_size, hi - self.pad_size
+        extra = self.denoise.delay_size if self.denoise is not None else 0
+        return lo - self.pad_size + extra, hi - self.pad_size + extra
 
     @property
     def pad_size(self):
@@ -307,6 +416,9 @@ class BatchedStreamInfer:
                 raise ValueError(f"gate: built for {self.gate.n_streams} streams of {self.gate.block_size}-sample blocks, the streams are "
                                  f"{self.n_streams} of {self.block_size}")
             check_gate_lookahead(self.gate.lookahead_size, self.crossfade_size, self.last_dilay_size, self.pad_size)
+        if self.denoise is not None and (self.denoise.n_streams, self.denoise.block_size) != (self.n_streams, self.block_size):
+            raise ValueError(f"denoise: built for {self.denoise.n_streams} streams of {self.denoise.block_size}-sample blocks, the streams are "
+                             f"{self.n_streams} of {self.block_size}")
         self._geometry = self._attributes()
         self.fade_in_window, self.fade_out_window = _fade_windows(self.crossfade_size, self.device)
         self.input_wav = torch.zeros(self.n_streams, self.input_size, device=self.device)
@@ -322,12 +434,16 @@ class BatchedStreamInfer:
             self.door.reset()
         if self.gate is not None:
             self.gate.reset()
+        if self.denoise is not None:
+            self.denoise.reset()
 
     def _attributes(self):
         return (self.block_size, self.crossfade_size, self.sola_search_size, self.last_dilay_size, self.input_size)
 
     def _step(self, blocks, noise_angle):
         # torch.roll + slice assignment of the reference (stream.py:69-70), in place on a fixed buffer, one launch
+        if self.denoise is not None:      # in front of everything else: the window holds the suppressed signal, denoise.delay_size samples late
+            blocks = self.generator.engine(self.device).stream_denoise(blocks.contiguous(), self.denoise)
         self.generator.engine(self.device).stream_push(self.input_wav, blocks)
         if noise_angle is None and self.use_graph:
             # a captured step bakes kernel arguments in: the library's seeded draw would replay ONE seed for every block.  torch's
@@ -363,7 +479,7 @@ class BatchedStreamInfer:
         one), the prepared index riding on `target`, plus the scalars captured by value.  With auto_pitch also the
         tracker's three state tensors (where they live) and its host parameters, and WHERE the target registers live - not their values,
         nor the ring's or `auto`'s: the kernels read those at replay, so a reset(), registers.copy_(...) or a stream's history advancing
-        keeps the graph.  With a door, likewise: where its two state tensors live and its host parameters (rates, block, gains); with a gate, where its five tensors live and its params().  The tail's
+        keeps the graph.  With a door, likewise: where its two state tensors live and its host parameters (rates, block, gains); with a gate, where its five tensors live and its params(); with a suppressor (denoise), where its seven tensors live and its params().  The tail's
         geometry is baked into its two launches, so it is part of the key."""
         eng = self.generator.engine(self.device)          # re-packs the weights first if a parameter changed
         ws = eng._ws
@@ -384,6 +500,9 @@ class BatchedStreamInfer:
         if self.gate is not None:      # WHERE the thresholds and the state live, and the gate's host parameters - never their values
             gt = self.gate
             tkey += (("gate", gt.threshold_db.data_ptr(), gt.open.data_ptr(), gt.hold.data_ptr(), gt.gain.data_ptr(), gt.level_db.data_ptr(), gt.params()),)
+        if self.denoise is not None:      # WHERE the reduction and the state live, and the suppressor's host parameters - never their values
+            dn = self.denoise
+            tkey += (("denoise",) + tuple(t.data_ptr() for t in (dn.reduction_db, dn.hist, dn.ola, dn.smooth, dn.noise, dn.frames, dn.noise_db)) + (dn.params(),),)
         if self.alpha is not None:      # WHERE the shares live, not their values: alpha.fill_(...) / copy_(...) keeps the graph
             tkey += (("alpha", self.alpha.data_ptr()),)
         return (eng.weights_key, ws.data_ptr() if ws is not None else 0, ws.numel() if ws is not None else 0,
@@ -456,12 +575,12 @@ class StreamInfer(BatchedStreamInfer):
     """Single stream with the reference's constructor and 1-D buffers (stream.py:31-57)."""
 
     def __init__(self, generator: Generator, target=None, pitch_shift=0., device=torch.device("cpu"),
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, gate=None, door=None,
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, denoise=None, gate=None, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         dev = torch.device(device)
         if dev.type != "cuda":
             dev = generator._module_device()     # the reference defaults to CPU; there is no CPU path here
-        super().__init__(generator, 1, target, pitch_shift, dev, block_size, extra_size, use_phase_vocoder, f0_estimation, use_graph, alpha, gate, door,
+        super().__init__(generator, 1, target, pitch_shift, dev, block_size, extra_size, use_phase_vocoder, f0_estimation, use_graph, alpha, denoise, gate, door,
                          crossfade_size, sola_search_size, last_delay_size, auto_pitch, pitch_track)
 
     @torch.no_grad()
