@@ -7,11 +7,13 @@ import ctypes
 import math
 import numbers
 import threading
+import types
 import weakref
 
 import torch
 
 from . import _lib, spec
+from .stream_state import DENOISE_STATE, GATE_STATE, TRACK_STATE, Field, checked
 
 _F32 = torch.float32
 
@@ -40,6 +42,13 @@ def _prep(t, name, device):
     if t.dtype != _F32:
         t = t.float()
     return t.contiguous()
+
+
+def integer(x, what, name):
+    """x as the int a C int argument takes; ValueError for a bool, anything that is no integer (240.9 is not 240) or one beyond 32 bits"""
+    if isinstance(x, bool) or not isinstance(x, numbers.Integral) or abs(x) >= 2 ** 31:
+        raise ValueError(f"{what}: {name} must be an integer, got {x!r}")
+    return int(x)
 
 
 def pitch_shifts(pitch_shift, B):
@@ -81,6 +90,7 @@ _MATCH = {
 }
 
 
+_RESAMPLE_STATE = (Field("state", _F32, "hist", 0.0),)      # what stream_resample takes of a door: one side's history
 STREAM_RESAMPLE_LDS_FLOATS = 16384      # TVC_STREAM_RESAMPLE_LDS_FLOATS of tinyvc_hip.h: a stream's history + block, staged in 64 KiB of LDS
 
 
@@ -108,10 +118,7 @@ def sola_geometry(block, cross=SOLA_CROSS, search=SOLA_SEARCH, delay=SOLA_DELAY,
     """tvc_sola_geometry (no context, no device) -> (min_ly, latency_min, latency_max) of a streaming tail with `block`-sample blocks: the
     shortest converted buffer it takes, and the range of cross + search + delay - shift, in 24 kHz samples.  ValueError, with the library's
     reason, for a geometry the kernels do not take."""
-    for x, name in ((block, "block"), (cross, "cross"), (search, "search"), (delay, "delay")):
-        if isinstance(x, bool) or not isinstance(x, numbers.Integral) or abs(x) >= 2 ** 31:
-            raise ValueError(f"sola geometry: {name} must be an integer, got {x!r}")
-    block, cross, search, delay = int(block), int(cross), int(search), int(delay)
+    block, cross, search, delay = (integer(x, "sola geometry", name) for x, name in ((block, "block"), (cross, "cross"), (search, "search"), (delay, "delay")))
     lib = lib if lib is not None else _lib.load_library()
     min_ly, lo, hi = ctypes.c_int64(), ctypes.c_int(), ctypes.c_int()
     if lib.tvc_sola_geometry(block, cross, search, delay, ctypes.byref(min_ly), ctypes.byref(lo), ctypes.byref(hi)) != 0:
@@ -122,11 +129,8 @@ def sola_geometry(block, cross=SOLA_CROSS, search=SOLA_SEARCH, delay=SOLA_DELAY,
 def stream_gate_geometry(block, sub, look=0, hold=0, attack=1, release=1, lib=None):
     """tvc_stream_gate_geometry (no context, no device) -> (nsub, look_samples) of a noise gate over `block`-sample blocks in sub-frames of
     `sub` samples; look, hold, attack and release count sub-frames.  ValueError, with the library's reason, for what the kernel does not take."""
-    vals = (block, sub, look, hold, attack, release)
-    for x, name in zip(vals, ("block", "sub", "look", "hold", "attack", "release")):
-        if isinstance(x, bool) or not isinstance(x, numbers.Integral) or abs(x) >= 2 ** 31:
-            raise ValueError(f"stream gate geometry: {name} must be an integer, got {x!r}")
-    vals = tuple(int(v) for v in vals)
+    vals = tuple(integer(x, "stream gate geometry", name)
+                 for x, name in zip((block, sub, look, hold, attack, release), ("block", "sub", "look", "hold", "attack", "release")))
     lib = lib if lib is not None else _lib.load_library()
     nsub, look_samples = ctypes.c_int(), ctypes.c_int()
     if lib.tvc_stream_gate_geometry(*vals, ctypes.byref(nsub), ctypes.byref(look_samples)) != 0:
@@ -138,10 +142,7 @@ def stream_denoise_geometry(block, hop=160, lib=None):
     """tvc_stream_denoise_geometry (no context, no device) -> (frames, delay) of a spectral suppressor over `block`-sample blocks at a hop of
     `hop` samples: frames per block and the samples of delay it adds (640 - hop).  ValueError, with the library's reason, for what the
     kernel does not take."""
-    for x, name in ((block, "block"), (hop, "hop")):
-        if isinstance(x, bool) or not isinstance(x, numbers.Integral) or abs(x) >= 2 ** 31:
-            raise ValueError(f"stream denoise geometry: {name} must be an integer, got {x!r}")
-    block, hop = int(block), int(hop)
+    block, hop = integer(block, "stream denoise geometry", "block"), integer(hop, "stream denoise geometry", "hop")
     lib = lib if lib is not None else _lib.load_library()
     frames, delay = ctypes.c_int(), ctypes.c_int()
     if lib.tvc_stream_denoise_geometry(block, hop, ctypes.byref(frames), ctypes.byref(delay)) != 0:
@@ -334,10 +335,8 @@ class Engine:
         x = x.contiguous()
         S, n_in = x.shape
         n_out, hist, _ = self.stream_resample_geometry(in_freq, out_freq, n_in)
-        if hist:
-            _check_dev(state, "state", self.device)
-            if tuple(state.shape) != (S, hist) or state.dtype != _F32 or not state.is_contiguous():
-                raise ValueError(f"stream_resample: state must be contiguous fp32 [{S}, {hist}] for {in_freq} -> {out_freq} Hz, got {tuple(state.shape)}")
+        if hist:      # one side of a door: the field of DOOR_STATE for this rate pair
+            checked(types.SimpleNamespace(state=state, hist=hist), _RESAMPLE_STATE, S, self.device, f"stream_resample ({in_freq} -> {out_freq} Hz): ")
         y = torch.empty(S, n_out, dtype=torch.int16 if out_pcm16 else _F32, device=self.device)
         self._ok(self.lib.tvc_stream_resample(self.ctx, self._stream(), _ptr(x), int(in16), _ptr(y), int(bool(out_pcm16)), _ptr(state) if hist else None,
                                               S, n_in, int(in_freq), int(out_freq), float(gain_db)), "tvc_stream_resample")
@@ -461,22 +460,15 @@ class Engine:
         blobs, ns = self._table(prepared, Ns, B * M)
         return blobs, ns, M
 
-    def _target_f0(self, target_f0, B):
-        """the target registers of a call: a contiguous fp32 [B] tensor on this device, used in place (the kernels read it when they run)"""
-        _check_dev(target_f0, "target_f0", self.device)
-        if target_f0.dtype != _F32 or target_f0.dim() != 1 or target_f0.shape[0] != B or not target_f0.is_contiguous():
-            raise ValueError(f"target_f0 must be a contiguous fp32 [B = {B}] tensor on the device, got {tuple(target_f0.shape)} {target_f0.dtype}")
-        return target_f0
-
-    def _alpha(self, alpha, B):
-        """the source's share of every row: a contiguous fp32 [B] tensor on this device, used in place (the kernels read it when they run) -
-        anything else is refused here, never copied"""
-        if not isinstance(alpha, torch.Tensor):
-            raise TypeError(f"alpha must be a torch.Tensor on the device (a contiguous fp32 [B = {B}]), got {type(alpha).__name__}")
-        _check_dev(alpha, "alpha", self.device)
-        if alpha.dtype != _F32 or alpha.dim() != 1 or alpha.shape[0] != B or not alpha.is_contiguous():
-            raise ValueError(f"alpha must be a contiguous fp32 [B = {B}] tensor on the device, got {tuple(alpha.shape)} {alpha.dtype}")
-        return alpha
+    def _per_row(self, t, name, B):
+        """a value per row of a call (`name`: target_f0, the target registers; alpha, the source's share): a contiguous fp32 [B] tensor on
+        this device, used in place (the kernels read it when they run) - anything else is refused here, never copied"""
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor on the device (a contiguous fp32 [B = {B}]), got {type(t).__name__}")
+        _check_dev(t, name, self.device)
+        if t.dtype != _F32 or t.dim() != 1 or t.shape[0] != B or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous fp32 [B = {B}] tensor on the device, got {tuple(t.shape)} {t.dtype}")
+        return t
 
     def _index_args(self, form, prepared, Ns, weights, B):
         """The index of a call, checked on the host -> (what the entry takes for it, what its workspace query takes for it).  shared:
@@ -512,14 +504,14 @@ class Engine:
     def _match(self, form, src, prepared, Ns, weights=None, want_indices=False, alpha=None):
         """src [B, 768, T] matched against the index (`form`, prepared, Ns, weights: _index_args) -> matched [B, 768, T] (, indices [B, T, 4];
         [M, B, T, 4] for a blend: each term's own search).  form "alpha": the table (weights None) or blend form, and out = matched *
-        (1 - alpha[b]) + src * alpha[b] (alpha: _alpha; indices always [M, B, T, 4])."""
+        (1 - alpha[b]) + src * alpha[b] (alpha: _per_row; indices always [M, B, T, 4])."""
         src = _prep(src, "source", self.device)
         B, C, T = src.shape
         if C != spec.SSL_DIM:
             raise ValueError(f"source must have {spec.SSL_DIM} channels")
         index, sized = self._index_args(form, prepared, Ns, weights, B)
         if form == "alpha":
-            index += (_ptr(self._alpha(alpha, B)),)
+            index += (_ptr(self._per_row(alpha, "alpha", B)),)
         out = torch.empty_like(src)
         terms = sized[1:]      # (M,) for a blend, else ()
         idx = torch.empty(*terms, B, T, 4, dtype=torch.int64, device=self.device) if want_indices else None
@@ -553,18 +545,14 @@ class Engine:
         if track.n_streams != S:
             raise ValueError(f"track: a tracker of {track.n_streams} streams for {S} rows")
         start, n = track.columns(T)
-        W = track.window_frames
-        for t, name, shape, dtype in ((track.ring, "track.ring", (S, W), _F32), (track.count, "track.count", (S,), torch.int64), (track.auto, "track.auto", (S,), _F32)):
-            _check_dev(t, name, self.device)
-            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():      # the kernel indexes the state by (S, W): never past it
-                raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape}, got {tuple(t.shape)} {t.dtype}")
-        return (start, n, track.window_frames, track.min_voiced, track.slew, _ptr(track.ring), _ptr(track.count), _ptr(track.auto))
+        state = checked(track, TRACK_STATE, S, self.device, "track.")      # the kernel indexes the state by (S, W): never past it
+        return (start, n, track.window_frames, track.min_voiced, track.slew, *map(_ptr, state))
 
     def _convert(self, form, wav, prepared, Ns, pitch_shift, noise_angle=None, lengths=None, weights=None, target_f0=None, out=None, shift_out=None,
                  track=None, alpha=None):
         """wav [B, L] converted toward the index (`form`, prepared, Ns, weights: _index_args) -> wave [B, L]; form "auto" / "track" ->
         (wave, shifts [B]).  "track": "auto" with the register taken from `track` (a PitchTrack: the streams' history), equal lengths only.
-        "alpha": the table / blend call keeping the share alpha[b] of row b's own content features (alpha: _alpha); with target_f0 it is the
+        "alpha": the table / blend call keeping the share alpha[b] of row b's own content features (alpha: _per_row); with target_f0 it is the
         "auto" call (-> (wave, shifts)), with `track` as well the "track" call.
         lengths: a ragged batch (row b holds an utterance of lengths[b] samples, a multiple of 480, zero-padded behind it; every utterance
         is converted over its OWN length).  pitch_shift: a float, or one per row for every form but "shared".  Every host check comes
@@ -580,11 +568,11 @@ class Engine:
             found = target_f0 is not None
             if track is not None and not found:
                 raise ValueError("track needs target_f0: the tracker finds the register the automatic shift starts from")
-            index += (_ptr(self._alpha(alpha, B)), _ptr(self._target_f0(target_f0, B)) if found else None)
+            index += (_ptr(self._per_row(alpha, "alpha", B)), _ptr(self._per_row(target_f0, "target_f0", B)) if found else None)
             if not ragged:
                 index += self._track_args(track, B, L // spec.HOP) if track is not None else (0, 0, 0, 0, 0.0, None, None, None)
         elif found:
-            index += (_ptr(self._target_f0(target_f0, B)),)
+            index += (_ptr(self._per_row(target_f0, "target_f0", B)),)
         if form == "track":
             index += self._track_args(track, B, L // spec.HOP)
         shift, shifts = pitch_shifts(pitch_shift, B)
@@ -656,7 +644,7 @@ class Engine:
         if rows < 1 or row_start[0] < 0 or row_start[-1] > f0.numel() or any(a > b for a, b in zip(row_start, row_start[1:])):
             raise ValueError(f"pitch_match: row_start must be rows + 1 ascending column numbers within the {f0.numel()} values of f0")
         shift, shifts = pitch_shifts(pitch_shift, rows)
-        tgt = self._target_f0(target_f0, rows) if target_f0 is not None else None
+        tgt = self._per_row(target_f0, "target_f0", rows) if target_f0 is not None else None
         med = torch.empty(rows, dtype=_F32, device=self.device)
         voiced = torch.empty(rows, dtype=torch.int32, device=self.device)
         sh = torch.empty(rows, dtype=_F32, device=self.device)
@@ -676,7 +664,7 @@ class Engine:
         S, T = f0.shape[0], f0.numel() // max(f0.shape[0], 1)
         targs = self._track_args(track, S, T)
         shift, shifts = pitch_shifts(pitch_shift, S)
-        tgt = self._target_f0(target_f0, S)
+        tgt = self._per_row(target_f0, "target_f0", S)
         med = torch.empty(S, dtype=_F32, device=self.device)
         cnt = torch.empty(S, dtype=torch.int64, device=self.device)
         sh = torch.empty(S, dtype=_F32, device=self.device)
@@ -934,10 +922,7 @@ class Engine:
             raise ValueError("sola_buffer must be contiguous fp32")
         default = crossfade is None and search is None and delay is None
         cross, search, delay = (d if x is None else x for x, d in ((crossfade, SOLA_CROSS), (search, SOLA_SEARCH), (delay, SOLA_DELAY)))
-        for x, name in ((cross, "crossfade"), (search, "search"), (delay, "delay")):      # as sola_geometry: 240.9 is not 240
-            if isinstance(x, bool) or not isinstance(x, numbers.Integral) or abs(x) >= 2 ** 31:
-                raise ValueError(f"sola: {name} must be an integer, got {x!r}")
-        cross, search, delay = int(cross), int(search), int(delay)
+        cross, search, delay = (integer(x, "sola", name) for x, name in ((cross, "crossfade"), (search, "search"), (delay, "delay")))      # as sola_geometry
         S, Ly = y.shape
         if tuple(sola_buf.shape) != (S, cross) or fade_in.numel() != cross:
             raise ValueError(f"sola: crossfade = {cross} takes sola_buffer [{S}, {cross}] and a fade_in_window of {cross} entries, got "
@@ -970,11 +955,7 @@ class Engine:
                 raise ValueError(f"stream_gate: shift must be contiguous int32 [{S}], got {shift.dtype} {tuple(shift.shape)}")
         if isinstance(base, bool) or not isinstance(base, numbers.Integral):
             raise ValueError(f"stream_gate: base must be an integer, got {base!r}")
-        for t, name, dt in ((gate.threshold_db, "threshold_db", _F32), (gate.open, "open", torch.int32), (gate.hold, "hold", torch.int32),
-                            (gate.gain, "gain", _F32), (gate.level_db, "level_db", _F32)):
-            _check_dev(t, f"gate.{name}", self.device)
-            if t.dtype != dt or tuple(t.shape) != (S,) or not t.is_contiguous():
-                raise ValueError(f"stream_gate: gate.{name} must be contiguous {dt} [{S}], got {t.dtype} {tuple(t.shape)}")
+        state = checked(gate, GATE_STATE, S, self.device, "stream_gate: gate.")
         if out is None:
             out = torch.empty_like(y)
         else:
@@ -983,8 +964,7 @@ class Engine:
                 raise ValueError(f"stream_gate: out must be contiguous fp32 {tuple(y.shape)}, got {out.dtype} {tuple(out.shape)}")
         sub, look, hold, attack, release, hysteresis_db, range_db = gate.params()[2:]
         self._ok(self.lib.tvc_stream_gate_f32(self.ctx, self._stream(), _ptr(x), n, int(base), _ptr(shift), _ptr(y), _ptr(out), S, gate.block_size, sub, look,
-                                              hold, attack, release, hysteresis_db, range_db, _ptr(gate.threshold_db), _ptr(gate.open), _ptr(gate.hold),
-                                              _ptr(gate.gain), _ptr(gate.level_db)), "tvc_stream_gate_f32")
+                                              hold, attack, release, hysteresis_db, range_db, *map(_ptr, state)), "tvc_stream_gate_f32")
         return out
 
     def stream_denoise(self, blocks, denoise, out=None):
@@ -997,13 +977,7 @@ class Engine:
         S = blocks.shape[0]
         if tuple(blocks.shape) != (denoise.n_streams, denoise.block_size):
             raise ValueError(f"stream_denoise: a suppressor for {denoise.n_streams} streams of {denoise.block_size}-sample blocks, blocks is {tuple(blocks.shape)}")
-        D = denoise.delay_size
-        for t, name, dt, shape in ((denoise.reduction_db, "reduction_db", _F32, (S,)), (denoise.hist, "hist", _F32, (S, D)), (denoise.ola, "ola", _F32, (S, D)),
-                                   (denoise.smooth, "smooth", _F32, (S, 321)), (denoise.noise, "noise", _F32, (S, 321)),
-                                   (denoise.frames, "frames", torch.int32, (S,)), (denoise.noise_db, "noise_db", _F32, (S,))):
-            _check_dev(t, f"denoise.{name}", self.device)
-            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError(f"stream_denoise: denoise.{name} must be contiguous {dt} {list(shape)}, got {t.dtype} {tuple(t.shape)}")
+        state = checked(denoise, DENOISE_STATE, S, self.device, "stream_denoise: denoise.")
         if out is None:
             out = torch.empty_like(blocks)
         else:
@@ -1012,8 +986,7 @@ class Engine:
                 raise ValueError(f"stream_denoise: out must be contiguous fp32 {tuple(blocks.shape)}, got {out.dtype} {tuple(out.shape)}")
         hop, a_s, a_n, clamp, beta, warm = denoise.params()[2:]
         self._ok(self.lib.tvc_stream_denoise_f32(self.ctx, self._stream(), _ptr(blocks), _ptr(out), S, denoise.block_size, hop, a_s, a_n, clamp, beta, warm,
-                                                 _ptr(denoise.reduction_db), _ptr(denoise.hist), _ptr(denoise.ola), _ptr(denoise.smooth), _ptr(denoise.noise),
-                                                 _ptr(denoise.frames), _ptr(denoise.noise_db)), "tvc_stream_denoise_f32")
+                                                 *map(_ptr, state)), "tvc_stream_denoise_f32")
         return out
 
 

@@ -16,7 +16,8 @@ import torch
 
 from ...engine import (SOLA_CROSS, SOLA_DELAY, SOLA_SEARCH, pitch_shifts, sola_geometry, stream_denoise_geometry, stream_gate_geometry,
                        stream_resample_geometry)
-from ..tinyvc.feature_retrieval import PitchTrack, alpha_rows, resolve_alpha, resolve_auto_pitch, target_form
+from ...stream_state import DENOISE_STATE, DOOR_STATE, GATE_STATE, TRACK_STATE, addresses, allocate, reset
+from ..tinyvc.feature_retrieval import PitchTrack, alpha_rows, gpu_device, resolve_alpha, resolve_auto_pitch, target_form
 from .generator import Generator
 
 
@@ -92,13 +93,8 @@ class StreamDoor:
         nout, self.hist_out, self.delay_out = stream_resample_geometry(MODEL_RATE, out_rate, block_size)
         assert (n24, nout) == (block_size, self.chunk_out)
         self.latency_seconds = self.delay_in / MODEL_RATE + self.delay_out / out_rate
-        device = torch.device(device if device is not None else "cuda")
-        if device.type != "cuda" or not torch.cuda.is_available():
-            raise ValueError(f"StreamDoor: the state lives on the GPU, where the door's kernel runs; got device {str(device)!r}"
-                             + ("" if torch.cuda.is_available() else " and there is no GPU here"))
-        self.device = device
-        self.in_state = torch.zeros(n_streams, self.hist_in, dtype=torch.float32, device=device)
-        self.out_state = torch.zeros(n_streams, self.hist_out, dtype=torch.float32, device=device)
+        self.device = gpu_device(device, "StreamDoor: the state lives on the GPU, where the door's kernel runs")
+        allocate(self, DOOR_STATE, self.device)
 
     def params(self):
         """the host values a captured block bakes in"""
@@ -112,13 +108,7 @@ class StreamDoor:
     def reset(self, streams=None):
         """Forget the filter history of every stream, or of the listed ones: in-place ops on the state tensors, so it works between replays
         of a captured graph (which reads them when it runs)."""
-        if streams is None:
-            self.in_state.zero_()
-            self.out_state.zero_()
-            return
-        idx = torch.as_tensor(list(streams), dtype=torch.int64, device=self.device)
-        self.in_state.index_fill_(0, idx, 0.0)
-        self.out_state.index_fill_(0, idx, 0.0)
+        reset(self, DOOR_STATE, streams)
 
     def push(self, engine, pcm):
         """client int16 [S, chunk_in] -> fp32 [S, block_size] at 24 kHz (input_gain applied), advancing in_state"""
@@ -138,6 +128,18 @@ def check_gate_lookahead(lookahead_size, crossfade_size, last_delay_size, pad_si
         raise ValueError(f"gate: lookahead_size = {lookahead_size} is more than the {room} input samples the window holds behind an emitted block "
                          f"(crossfade_size {crossfade_size} + last_delay_size {last_delay_size} - pad_size {pad_size})")
     return room
+
+
+def _db_rows(x, n_streams, refusal):
+    """a live per-stream parameter in dB as given - a number, one per stream, or a 1-D tensor - -> n_streams floats; ValueError(refusal) for
+    anything else, NaN included"""
+    vals = [x] if isinstance(x, (int, float)) and not isinstance(x, bool) else x
+    if isinstance(vals, torch.Tensor):
+        vals = vals.detach().cpu().tolist() if vals.dim() == 1 else None
+    if not isinstance(vals, (list, tuple)) or len(vals) not in (1, n_streams) or not all(
+            isinstance(t, (int, float)) and not isinstance(t, bool) and not math.isnan(t) for t in vals):
+        raise ValueError(refusal)
+    return [float(t) for t in vals] * (n_streams // len(vals))
 
 
 class StreamGate:
@@ -164,12 +166,8 @@ class StreamGate:
                                (lookahead_size, "lookahead_size", 0)):
             if isinstance(x, bool) or not isinstance(x, int) or x < 0 or x % sub_frame or x // sub_frame < least:
                 raise ValueError(f"StreamGate: {name} must be a whole number of {sub_frame}-sample sub-frames, at least {least}; got {x!r}")
-        thr = [threshold_db] if isinstance(threshold_db, (int, float)) and not isinstance(threshold_db, bool) else threshold_db
-        if isinstance(thr, torch.Tensor):
-            thr = thr.detach().cpu().tolist() if thr.dim() == 1 else None
-        if not isinstance(thr, (list, tuple)) or len(thr) not in (1, n_streams) or not all(
-                isinstance(t, (int, float)) and not isinstance(t, bool) and not math.isnan(t) for t in thr):
-            raise ValueError(f"StreamGate: threshold_db must be a number of dB (-inf: always open) or one per stream ({n_streams}), got {threshold_db!r}")
+        thr = _db_rows(threshold_db, n_streams,
+                       f"StreamGate: threshold_db must be a number of dB (-inf: always open) or one per stream ({n_streams}), got {threshold_db!r}")
         if isinstance(hysteresis_db, bool) or not isinstance(hysteresis_db, (int, float)) or not math.isfinite(hysteresis_db) or hysteresis_db < 0:
             raise ValueError(f"StreamGate: hysteresis_db must be a finite number of dB >= 0, got {hysteresis_db!r}")
         if isinstance(range_db, bool) or not isinstance(range_db, (int, float)) or not range_db <= 0:
@@ -182,16 +180,9 @@ class StreamGate:
         self.n_streams, self.block_size, self.sub_frame = n_streams, block_size, sub_frame
         self.hold_size, self.attack_size, self.release_size, self.lookahead_size = hold_size, attack_size, release_size, lookahead_size
         self.hysteresis_db, self.range_db = float(hysteresis_db), float(range_db)
-        device = torch.device(device if device is not None else "cuda")
-        if device.type != "cuda" or not torch.cuda.is_available():
-            raise ValueError(f"StreamGate: the thresholds and the state live on the GPU, where the gate's kernel runs; got device {str(device)!r}"
-                             + ("" if torch.cuda.is_available() else " and there is no GPU here"))
-        self.device = device
-        self.threshold_db = torch.tensor([float(t) for t in thr] * (n_streams // len(thr)), dtype=torch.float32, device=device)
-        self.gain = torch.ones(n_streams, dtype=torch.float32, device=device)
-        self.open = torch.ones(n_streams, dtype=torch.int32, device=device)
-        self.hold = torch.zeros(n_streams, dtype=torch.int32, device=device)
-        self.level_db = torch.full((n_streams,), -200.0, dtype=torch.float32, device=device)
+        self.device = gpu_device(device, "StreamGate: the thresholds and the state live on the GPU, where the gate's kernel runs")
+        self.threshold_db = torch.tensor(thr, dtype=torch.float32, device=self.device)
+        allocate(self, GATE_STATE, self.device)
 
     def params(self):
         """the host values a captured block bakes in: (n_streams, block_size, sub_frame, look, hold, attack, release - counts of sub-frames -,
@@ -201,21 +192,7 @@ class StreamGate:
     def reset(self, streams=None):
         """Put every stream, or the listed ones, back at the start: open, no hold left, gain 1 (a silent start then closes over release_size).
         In-place ops on the state tensors, so it works between replays of a captured graph, which reads them when it runs."""
-        if streams is None:
-            self.open.fill_(1)
-            self.hold.zero_()
-            self.gain.fill_(1.0)
-            self.level_db.fill_(-200.0)
-            return
-        idx = torch.as_tensor(list(streams), dtype=torch.int64, device=self.device)
-        self.open.index_fill_(0, idx, 1)
-        self.hold.index_fill_(0, idx, 0)
-        self.gain.index_fill_(0, idx, 1.0)
-        self.level_db.index_fill_(0, idx, -200.0)
-
-
-DENOISE_FRAME = 640
-DENOISE_BINS = DENOISE_FRAME // 2 + 1
+        reset(self, GATE_STATE, streams)
 
 
 def _f32(x):
@@ -266,12 +243,8 @@ class StreamDenoise:
         for x, name in ((n_streams, "n_streams"), (block_size, "block_size"), (hop, "hop")):
             if isinstance(x, bool) or not isinstance(x, int) or x < 1:
                 raise ValueError(f"StreamDenoise: {name} must be an integer >= 1, got {x!r}")
-        red = [reduction_db] if isinstance(reduction_db, (int, float)) and not isinstance(reduction_db, bool) else reduction_db
-        if isinstance(red, torch.Tensor):
-            red = red.detach().cpu().tolist() if red.dim() == 1 else None
-        if not isinstance(red, (list, tuple)) or len(red) not in (1, n_streams) or not all(
-                isinstance(t, (int, float)) and not isinstance(t, bool) and not math.isnan(t) for t in red):
-            raise ValueError(f"StreamDenoise: reduction_db must be a number of dB (0: no suppression) or one per stream ({n_streams}), got {reduction_db!r}")
+        red = _db_rows(reduction_db, n_streams,
+                       f"StreamDenoise: reduction_db must be a number of dB (0: no suppression) or one per stream ({n_streams}), got {reduction_db!r}")
         try:
             _, self.delay_size = stream_denoise_geometry(block_size, hop)
         except ValueError as e:
@@ -279,18 +252,9 @@ class StreamDenoise:
         self.a_s, self.a_n, self.clamp, self.beta, self.warm = denoise_constants(hop, strength, smooth_ms, adapt_s, clamp, warmup_ms)
         self.n_streams, self.block_size, self.hop = n_streams, block_size, hop
         self.strength, self.smooth_ms, self.adapt_s, self.warmup_ms = float(strength), float(smooth_ms), float(adapt_s), float(warmup_ms)
-        device = torch.device(device if device is not None else "cuda")
-        if device.type != "cuda" or not torch.cuda.is_available():
-            raise ValueError(f"StreamDenoise: the reduction and the state live on the GPU, where the suppressor's kernel runs; got device {str(device)!r}"
-                             + ("" if torch.cuda.is_available() else " and there is no GPU here"))
-        self.device = device
-        self.reduction_db = torch.tensor([float(t) for t in red] * (n_streams // len(red)), dtype=torch.float32, device=device)
-        self.hist = torch.zeros(n_streams, self.delay_size, dtype=torch.float32, device=device)
-        self.ola = torch.zeros(n_streams, self.delay_size, dtype=torch.float32, device=device)
-        self.smooth = torch.zeros(n_streams, DENOISE_BINS, dtype=torch.float32, device=device)
-        self.noise = torch.zeros(n_streams, DENOISE_BINS, dtype=torch.float32, device=device)
-        self.frames = torch.zeros(n_streams, dtype=torch.int32, device=device)
-        self.noise_db = torch.full((n_streams,), -200.0, dtype=torch.float32, device=device)
+        self.device = gpu_device(device, "StreamDenoise: the reduction and the state live on the GPU, where the suppressor's kernel runs")
+        self.reduction_db = torch.tensor(red, dtype=torch.float32, device=self.device)
+        allocate(self, DENOISE_STATE, self.device)
 
     def params(self):
         """the host values a captured block bakes in: (n_streams, block_size, hop, a_s, a_n, clamp, beta, warm)"""
@@ -299,16 +263,7 @@ class StreamDenoise:
     def reset(self, streams=None):
         """Put every stream, or the listed ones, back at the start: empty tails, no estimate, no frame counted - so the warm-up runs again.
         In-place ops on the state tensors, so it works between replays of a captured graph, which reads them when it runs."""
-        state = (self.hist, self.ola, self.smooth, self.noise, self.frames)
-        if streams is None:
-            for t in state:
-                t.zero_()
-            self.noise_db.fill_(-200.0)
-            return
-        idx = torch.as_tensor(list(streams), dtype=torch.int64, device=self.device)
-        for t in state:
-            t.index_fill_(0, idx, 0)
-        self.noise_db.index_fill_(0, idx, -200.0)
+        reset(self, DENOISE_STATE, streams)
 
 
 class BatchedStreamInfer:
@@ -341,17 +296,11 @@ class BatchedStreamInfer:
     def __init__(self, generator: Generator, n_streams=1, target=None, pitch_shift=0., device=None,
                  block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, denoise=None, gate=None, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
-        check_window(block_size, extra_size, crossfade_size, sola_search_size, last_delay_size, auto_pitch is not None and auto_pitch is not False)
+        self.input_size, _ = check_window(block_size, extra_size, crossfade_size, sola_search_size, last_delay_size,
+                                           auto_pitch is not None and auto_pitch is not False)
         share = resolve_alpha(alpha, n_streams) if alpha is not None else None      # refused here, before anything is allocated
-        if door is not None and (door.n_streams, door.block_size) != (n_streams, block_size):
-            raise ValueError(f"door: built for {door.n_streams} streams of {door.block_size}-sample blocks, the streams are {n_streams} of {block_size}")
-        self.door = door
-        if gate is not None and (gate.n_streams, gate.block_size) != (n_streams, block_size):
-            raise ValueError(f"gate: built for {gate.n_streams} streams of {gate.block_size}-sample blocks, the streams are {n_streams} of {block_size}")
-        self.gate = gate
-        if denoise is not None and (denoise.n_streams, denoise.block_size) != (n_streams, block_size):
-            raise ValueError(f"denoise: built for {denoise.n_streams} streams of {denoise.block_size}-sample blocks, the streams are {n_streams} of {block_size}")
-        self.denoise = denoise
+        self.n_streams, self.block_size = n_streams, block_size
+        self.door, self.gate, self.denoise = (self._fits(name, stage) for name, stage in (("door", door), ("gate", gate), ("denoise", denoise)))
         self.auto_pitch = auto_pitch if auto_pitch is not False else None
         self.pitch_track = pitch_track
         self._own_track = pitch_track is None
@@ -361,21 +310,17 @@ class BatchedStreamInfer:
             raise ValueError(f"auto_pitch: block_size = {block_size} is not a whole number of 480-sample frames")
         self.last_pitch_shift = None
         self.generator = generator
-        self.n_streams = n_streams
         self.target = target
         self.pitch_shift = pitch_shift
         self.device = torch.device(device) if device is not None else generator._module_device()
         # the streams' shares of their own content features: a [S] device tensor every block reads when it runs, or None (the plain match)
         self.alpha = alpha_rows(share, n_streams, self.device) if share is not None else None
-        self.block_size = block_size
         self.extra_size = extra_size
         self.sola_search_size = sola_search_size
         self.last_dilay_size = last_delay_size          # (sic) the reference's attribute name, stream.py:49
         self.crossfade_size = crossfade_size
         self.use_phase_vocoder = use_phase_vocoder
         self.f0_estimation = f0_estimation
-        self.input_size = max(self.block_size + self.crossfade_size + self.sola_search_size + 2 * self.last_dilay_size,
-                              self.block_size + self.extra_size)
         self.last_shift = None
         # use_graph: after two eager warm-up blocks the whole per-block pipeline (buffer roll, noise draw,
         # convert, SOLA) is captured once into a HIP graph and replayed per block: ~170 launches become one.
@@ -406,36 +351,40 @@ class BatchedStreamInfer:
         lo, hi = self.latency_samples
         return lo / MODEL_RATE + extra, hi / MODEL_RATE + extra
 
+    def _fits(self, name, stage):
+        """`stage` (a door, a gate, a suppressor, or None) when it was built for these streams; ValueError otherwise"""
+        if stage is not None and (stage.n_streams, stage.block_size) != (self.n_streams, self.block_size):
+            raise ValueError(f"{name}: built for {stage.n_streams} streams of {stage.block_size}-sample blocks, the streams are "
+                             f"{self.n_streams} of {self.block_size}")
+        return stage
+
+    def _stages(self):
+        """the stages of these streams that keep state on the device, in block order: (name, stage, its table in stream_state)"""
+        every = (("track", self.pitch_track if self.auto_pitch is not None else None, TRACK_STATE), ("door", self.door, DOOR_STATE),
+                 ("denoise", self.denoise, DENOISE_STATE), ("gate", self.gate, GATE_STATE))
+        return [s for s in every if s[1] is not None]
+
     def init_buffer(self):
         # the attributes as they stand now (plain attributes, as in the reference): checked as in the constructor, the window follows them,
         # and _step holds every later block against what was seen here
         self.input_size, _ = check_window(self.block_size, self.extra_size, self.crossfade_size, self.sola_search_size, self.last_dilay_size,
                                            self.auto_pitch is not None)
-        if self.gate is not None:      # (before anything is allocated) the gate against the attributes as they stand now
-            if (self.gate.n_streams, self.gate.block_size) != (self.n_streams, self.block_size):
-                raise ValueError(f"gate: built for {self.gate.n_streams} streams of {self.gate.block_size}-sample blocks, the streams are "
-                                 f"{self.n_streams} of {self.block_size}")
+        for name in ("door", "gate", "denoise"):      # (before anything is allocated) the stages against the attributes as they stand now
+            self._fits(name, getattr(self, name))
+        if self.gate is not None:
             check_gate_lookahead(self.gate.lookahead_size, self.crossfade_size, self.last_dilay_size, self.pad_size)
-        if self.denoise is not None and (self.denoise.n_streams, self.denoise.block_size) != (self.n_streams, self.block_size):
-            raise ValueError(f"denoise: built for {self.denoise.n_streams} streams of {self.denoise.block_size}-sample blocks, the streams are "
-                             f"{self.n_streams} of {self.block_size}")
         self._geometry = self._attributes()
         self.fade_in_window, self.fade_out_window = _fade_windows(self.crossfade_size, self.device)
         self.input_wav = torch.zeros(self.n_streams, self.input_size, device=self.device)
         self.sola_buffer = torch.zeros(self.n_streams, self.crossfade_size, device=self.device)
         self._graph = None
         self._calls = 0
-        if self.auto_pitch is not None:
-            if self._own_track:      # the block's own frames: they have their full right context and are the audio about to be played
-                self.pitch_track = PitchTrack(self.n_streams, self.block_size // 480, self.last_dilay_size // 480, device=self.device)
-            self.pitch_track.reset()
+        if self.auto_pitch is not None and self._own_track:      # the block's own frames: they have their full right context and are the audio about to be played
+            self.pitch_track = PitchTrack(self.n_streams, self.block_size // 480, self.last_dilay_size // 480, device=self.device)
         if self.door is not None:
             self.door.prepare(self.generator.engine(self.device))
-            self.door.reset()
-        if self.gate is not None:
-            self.gate.reset()
-        if self.denoise is not None:
-            self.denoise.reset()
+        for _, stage, _ in self._stages():
+            stage.reset()
 
     def _attributes(self):
         return (self.block_size, self.crossfade_size, self.sola_search_size, self.last_dilay_size, self.input_size)
@@ -476,11 +425,12 @@ class BatchedStreamInfer:
     def _graph_key(self):
         """Everything a captured step bakes in as raw device pointers: the packed weights (re-packed - and the old arena
         freed - when a parameter changes), the engine's scratch workspace (re-allocated when another call needs a bigger
-        one), the prepared index riding on `target`, plus the scalars captured by value.  With auto_pitch also the
-        tracker's three state tensors (where they live) and its host parameters, and WHERE the target registers live - not their values,
-        nor the ring's or `auto`'s: the kernels read those at replay, so a reset(), registers.copy_(...) or a stream's history advancing
-        keeps the graph.  With a door, likewise: where its two state tensors live and its host parameters (rates, block, gains); with a gate, where its five tensors live and its params(); with a suppressor (denoise), where its seven tensors live and its params().  The tail's
-        geometry is baked into its two launches, so it is part of the key."""
+        one), the prepared index riding on `target`, plus the scalars captured by value.  Every stage present - the
+        tracker, the door, the suppressor (denoise), the gate - adds (its name, WHERE the tensors of its table in stream_state live, its
+        params()): the table lists every tensor whose pointer reaches the library, so none can be passed on and left out here.  With
+        auto_pitch also WHERE the target registers live, with alpha where the shares live.  Never a value: the kernels read those at replay,
+        so a reset(), registers.copy_(...), threshold_db.fill_(...) or a stream's history advancing keeps the graph.  The tail's geometry is
+        baked into its two launches, so it is part of the key."""
         eng = self.generator.engine(self.device)          # re-packs the weights first if a parameter changed
         ws = eng._ws
         form, tgts = target_form(self.target)      # every blob's tensor
@@ -489,20 +439,10 @@ class BatchedStreamInfer:
             wkey = self.target.resolve(self.n_streams, self.device, self.generator._input_device)[2].data_ptr()
         shift, shifts = pitch_shifts(self.pitch_shift, self.n_streams)
         shifts = shift if shifts is None else tuple(shifts)
-        tkey = ()
+        tkey = tuple((name, addresses(stage, table), stage.params()) for name, stage, table in self._stages())
         if self.auto_pitch is not None:
             regs = resolve_auto_pitch(self.auto_pitch, self.target, self.n_streams)
-            tr = self.pitch_track
-            tkey = (regs if isinstance(regs, float) else tuple(r.data_ptr() for r in regs), tr.ring.data_ptr(), tr.count.data_ptr(), tr.auto.data_ptr(),
-                    tr.params())
-        if self.door is not None:
-            tkey += (self.door.in_state.data_ptr(), self.door.out_state.data_ptr(), self.door.params())
-        if self.gate is not None:      # WHERE the thresholds and the state live, and the gate's host parameters - never their values
-            gt = self.gate
-            tkey += (("gate", gt.threshold_db.data_ptr(), gt.open.data_ptr(), gt.hold.data_ptr(), gt.gain.data_ptr(), gt.level_db.data_ptr(), gt.params()),)
-        if self.denoise is not None:      # WHERE the reduction and the state live, and the suppressor's host parameters - never their values
-            dn = self.denoise
-            tkey += (("denoise",) + tuple(t.data_ptr() for t in (dn.reduction_db, dn.hist, dn.ola, dn.smooth, dn.noise, dn.frames, dn.noise_db)) + (dn.params(),),)
+            tkey += (("target_f0", regs if isinstance(regs, float) else tuple(r.data_ptr() for r in regs)),)
         if self.alpha is not None:      # WHERE the shares live, not their values: alpha.fill_(...) / copy_(...) keeps the graph
             tkey += (("alpha", self.alpha.data_ptr()),)
         return (eng.weights_key, ws.data_ptr() if ws is not None else 0, ws.numel() if ws is not None else 0,
@@ -580,8 +520,10 @@ class StreamInfer(BatchedStreamInfer):
         dev = torch.device(device)
         if dev.type != "cuda":
             dev = generator._module_device()     # the reference defaults to CPU; there is no CPU path here
-        super().__init__(generator, 1, target, pitch_shift, dev, block_size, extra_size, use_phase_vocoder, f0_estimation, use_graph, alpha, denoise, gate, door,
-                         crossfade_size, sola_search_size, last_delay_size, auto_pitch, pitch_track)
+        super().__init__(generator, n_streams=1, target=target, pitch_shift=pitch_shift, device=dev, block_size=block_size, extra_size=extra_size,
+                         use_phase_vocoder=use_phase_vocoder, f0_estimation=f0_estimation, use_graph=use_graph, alpha=alpha, denoise=denoise, gate=gate,
+                         door=door, crossfade_size=crossfade_size, sola_search_size=sola_search_size, last_delay_size=last_delay_size,
+                         auto_pitch=auto_pitch, pitch_track=pitch_track)
 
     @torch.no_grad()
     def audio_callback(self, block, noise_angle=None):

@@ -7,7 +7,7 @@ import sys
 
 import torch
 
-from ... import spec
+from ... import spec, stream_state
 from ...engine import default_engine
 
 
@@ -268,6 +268,15 @@ def alpha_keywords(args, script):
     return {"alpha": float(args.alpha)}
 
 
+def gpu_device(device, sentence, cpu_ok=False):
+    """where a stream stage's state lives: `device` (None: "cuda") as a torch.device, refused (ValueError: `sentence` - the stage's own words -
+    and what was given) before anything is allocated when it is not a GPU that is there; cpu_ok: a CPU device passes"""
+    device = torch.device(device if device is not None else "cuda")
+    if not (torch.cuda.is_available() if device.type == "cuda" else cpu_ok):
+        raise ValueError(f"{sentence}; got device {str(device)!r}" + ("" if torch.cuda.is_available() else " and there is no GPU here"))
+    return device
+
+
 class PitchTrack:
     """The pitch tracker of a set of streams that advance in lock step (tvc_pitch_track_f32 / tvc_convert_track_f32): the register a
     stream's automatic shift aims FROM is the lower median of its last `window_frames` voiced f0 values, kept on the device.
@@ -291,13 +300,8 @@ class PitchTrack:
         if isinstance(slew, bool) or not isinstance(slew, (int, float)) or not float(slew) >= 0.0:
             raise ValueError(f"PitchTrack: slew must be >= 0 semitones per block (inf: no limit), got {slew!r}")
         self.slew = float(slew)
-        device = torch.device(device if device is not None else "cuda")
-        if device.type == "cuda" and not torch.cuda.is_available():
-            raise ValueError("PitchTrack: the state lives on the GPU and there is none here (device='cpu' builds a tracker no engine will take)")
-        self.device = device
-        self.ring = torch.zeros(self.n_streams, self.window_frames, dtype=torch.float32, device=device)
-        self.count = torch.zeros(self.n_streams, dtype=torch.int64, device=device)
-        self.auto = torch.zeros(self.n_streams, dtype=torch.float32, device=device)
+        self.device = gpu_device(device, "PitchTrack: the state lives on the GPU (device='cpu' builds a tracker no engine will take)", cpu_ok=True)
+        stream_state.allocate(self, stream_state.TRACK_STATE, self.device)
 
     def columns(self, T):
         """the tracked columns [start, start + new_frames) of an f0 of T frames; ValueError when they do not fit"""
@@ -313,15 +317,7 @@ class PitchTrack:
     def reset(self, streams=None):
         """Forget the history of every stream, or of the listed ones: in-place ops on the state tensors, so it works between replays of a
         captured graph (which reads them when it runs)."""
-        if streams is None:
-            self.ring.zero_()
-            self.count.zero_()
-            self.auto.zero_()
-            return
-        idx = torch.as_tensor(list(streams), dtype=torch.int64, device=self.device)
-        self.ring.index_fill_(0, idx, 0.0)
-        self.count.index_fill_(0, idx, 0)
-        self.auto.index_fill_(0, idx, 0.0)
+        stream_state.reset(self, stream_state.TRACK_STATE, streams)
 
     def register(self):
         """the streams' registers as they stand: PitchRegister(median_hz [S], voiced [S] = the fill)"""
