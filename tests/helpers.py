@@ -329,3 +329,179 @@ def harmonic_increments(f0):
     import torch.nn.functional as F
     mul = (torch.arange(15) + 1).view(1, -1, 1)
     return (F.interpolate(f0, f0.shape[2] * 480, mode="linear") * mul) / 24000
+
+
+# ---- window and row gates at tile edges (test_gpu_tile_edges.py, test_gpu_contraction_edges.py, test_contraction_metric_host.py) ---------
+FLOOR = 3e-6
+
+
+def _group(name):
+    return name.split("[")[0]
+
+
+def _gate_case(case, gpu, truth, ref, extra=""):
+    """gpu / truth / ref: {name: [rows, C, len]} (gpu on the host).  Logs the case's `[edge]` line; returns (failures, {name: [rows] gates})."""
+    fails, gates, ermax, groups = [], {}, {}, {}
+    worst = None                                      # (e / gate, e, gate, name, row, column)
+    for name, t in truth.items():
+        g = gpu[name].cpu()
+        assert torch.isfinite(g).all(), f"{case} {name}: non-finite"
+        eg, er = window_errors(g, t), window_errors(ref[name], t)
+        gate = (2.0 * er.max(dim=1).values).clamp_min(FLOOR)
+        gates[name], ermax[name] = gate, er.max(dim=1).values
+        st = window_starts(t.shape[2])
+        a, b = groups.get(_group(name), (0.0, 0.0))
+        groups[_group(name)] = (max(a, float(eg.max())), max(b, float(er.max())))
+        ratio = eg / gate[:, None]
+        r, w = divmod(int(ratio.argmax()), ratio.shape[1])
+        if worst is None or float(ratio[r, w]) > worst[0]:
+            worst = (float(ratio[r, w]), float(eg[r, w]), float(gate[r]), name, r, st[w])
+        for r, w in (ratio > 1.0).nonzero().tolist()[:4]:
+            fails.append(f"{name} row {r} columns [{st[w]}, {st[w] + min(32, t.shape[2])}) of {t.shape[2]}: {float(eg[r, w]):.2e} > gate {float(gate[r]):.2e}")
+    _x, e, gt, name, r, col = worst
+    print(f"[edge] {case}: worst window GPU {e:.2e} (gate {gt:.2e}, oracle fp32 worst {float(ermax[name][r]):.2e}) "
+          f"at {name} row {r} column {col} of {truth[name].shape[2]}; whole tensor {rel_rms(gpu[name].cpu(), truth[name]):.2e}; worst GPU / oracle window per group: "
+          + ", ".join(f"{k} {a:.2e} / {b:.2e}" for k, (a, b) in groups.items()) + extra)
+    return fails, gates
+
+
+def _bump_trips(gpu, truth, gates, name):
+    """The gate's own sensitivity: + 1e-4 x rms on the last two columns of block `name`, on the host; does a window exceed its gate?"""
+    t = truth[name]
+    bumped = gpu[name].cpu().double().clone()
+    bumped[..., -2:] += 1e-4 * torch.sqrt((t * t).mean(dim=(1, 2)))[:, None, None]
+    return bool((window_errors(bumped, t) > gates[name][:, None]).any())
+
+
+def row_errors(x, truth):
+    """[B, C, len] against an fp64 `truth` -> [B, C] (fp64): per utterance b and output row c, the rms over time of x - truth divided by the rms
+    of truth[b] over the WHOLE utterance - window_errors with rows for columns.  Not the row's own rms: ELU + 1 outputs go down to 5e-6 where
+    the pre-activation is very negative, and there the fp32 oracle itself reads 5e-3 on the row's scale (1e-7 in the utterance's units)."""
+    return window_errors(torch.as_tensor(x).transpose(1, 2), torch.as_tensor(truth).transpose(1, 2), width=1)
+
+
+# SourceNet (B, T): see the table in test_gpu_contraction_edges.py; the two cases that also carry the planted errors on the GPU
+SOURCE_SHAPES = [(1, 1), (1, 3), (3, 32), (3, 33), (3, 43), (2, 64), (2, 65), (1, 127), (1, 128), (1, 129), (1, 1024), (1, 1025)]
+SOURCE_BUMP_SHAPES = [(3, 43), (1, 129)]
+
+
+def sourcenet_edge_inputs(B, T, seed=None):
+    """(content [B, 768, T], f0 [B, 1, T], energy [B, 1, 480 T]) for SourceNet.  f0: every third frame exactly 0 and the last frame -5.0 - the
+    relu and log(1e-6) branches of the f0 conditioning.  energy: each frame's maximum planted alternately on sample 0 and on sample 479 of
+    the frame - the first and the last load of the frame-maximum kernel; every other sample is below 1."""
+    g = torch.Generator().manual_seed(7000 + 131 * B + T if seed is None else seed)
+    content = 0.5 * torch.randn(B, 768, T, generator=g)
+    f0 = 80.0 + 200.0 * torch.rand(B, 1, T, generator=g)
+    f0[..., ::3] = 0.0
+    f0[..., -1] = -5.0
+    energy = torch.rand(B, 1, 480 * T, generator=g)
+    peak = 1.0 + 0.5 * torch.rand(B, T, generator=g)
+    fr = energy.view(B, T, 480)
+    fr[:, 0::2, 0] = peak[:, 0::2]
+    fr[:, 1::2, 479] = peak[:, 1::2]
+    return content, f0, energy
+
+
+CONVNEXT_LAYERS = {"ssl_feature_estimator": 6, "pitch_estimator": 4, "source_net": 3}          # trunk -> its ConvNeXt layers (mid_layers.i)
+
+
+def convnext_prefixes(trunks, which="all"):
+    """The state-dict prefixes of the ConvNeXt layers of `trunks`; which = 'all', or 'second': every second layer (mid_layers.1, .3, .5)."""
+    return [f"{t}.mid_layers.{i}" for t in trunks for i in range(CONVNEXT_LAYERS[t]) if which == "all" or i % 2 == 1]
+
+
+def rescaled_ln(sd, prefixes, k=12):
+    """A copy of `sd` with norm.gamma and norm.beta x 2^k and c2.weight x 2^-k for the named ConvNeXt layers: the same function exactly
+    (powers of two; LayerNorm's output and every product of the 1x1 behind it scale without rounding), but the layer's LayerNorm bound
+    (ln_bound) grows by 2^k."""
+    out = dict(sd)
+    for p in prefixes:
+        out[p + ".norm.gamma"] = sd[p + ".norm.gamma"] * 2.0 ** k
+        out[p + ".norm.beta"] = sd[p + ".norm.beta"] * 2.0 ** k
+        out[p + ".c2.weight"] = sd[p + ".c2.weight"] * 2.0 ** -k
+    return out
+
+
+def ln_bound(sd, prefix):
+    """pack.hip's bound on a ConvNeXt layer's LayerNorm output, restated in fp32: sqrt(C) max|gamma| + max|beta|.  At 32768 and above the
+    fused ConvNeXt launches refuse the layer and the five unfused launches run it, with a |max| slot on the first 1x1's input."""
+    g, b = sd[prefix + ".norm.gamma"].float(), sd[prefix + ".norm.beta"].float()
+    return float(np.float32(np.sqrt(np.float32(g.numel()))) * np.float32(g.abs().max()) + np.float32(b.abs().max()))
+
+
+def gemm_s2_width(ncols, mblocks, ncu):
+    """gemm_s2_try's column-tile width rule restated (the width in units of 32 columns, 2 .. 6): the fewest rounds of the chip's persistent
+    workgroups (one per CU, a multiple of 8) times (width + 64 columns of staging); the narrower tile on a tie.  Used to CHOOSE and ASSERT
+    test shapes only."""
+    slots = ncu // 8 * 8
+    best, best_cost = None, None
+    for nwv in range(2, 7):
+        tiles = -(-ncols // (nwv * 32)) * mblocks
+        cost = -(-tiles // slots) * (nwv * 32 + 64)
+        if best_cost is None or cost < best_cost:
+            best, best_cost = nwv, cost
+    return best
+
+
+SSL_OUT_MBLOCKS, PIT_OUT_MBLOCKS = 6, 4                          # 768 and 512 output rows in blocks of 128
+WIDE_SHAPES_256 = [(3, 897), (17, 241), (3, 1814), (2, 3361)]    # (B, T): ssl_out widths 3, 4, 5, 6 on 256 CUs, tails of 3, 1, 2, 2 columns
+
+
+def wide_tile_shapes(ncu, span=400):
+    """[(B, T)] x 4: for ssl_out widths 3, 4, 5, 6 on a chip of `ncu` CUs, the T nearest to WIDE_SHAPES_256's at which B T selects that width and
+    leaves a tail of 1 .. 3 columns behind the last full tile; None where no T within `span` does."""
+    out = []
+    for want, (B, T0) in zip((3, 4, 5, 6), WIDE_SHAPES_256):
+        pick = None
+        for d in range(span + 1):
+            for T in ((T0,) if d == 0 else (T0 - d, T0 + d)):
+                if pick is None and T >= 3 and gemm_s2_width(B * T, SSL_OUT_MBLOCKS, ncu) == want and 1 <= (B * T) % (32 * want) <= 3:
+                    pick = (B, T)
+        out.append(pick)
+    return out
+
+
+def edge_gate(e_ref):
+    """The rule of the tile-edge files for one case, tensor and metric: max(3e-6, 2 x the oracle's own worst figure)."""
+    return max(FLOOR, 2.0 * float(e_ref.max()))
+
+
+_METRICS = (("window", window_errors, window_starts), ("row", row_errors, None))
+
+
+def gate_windows_and_rows(case, x, truth, ref, extra="", log=True):
+    """x / truth / ref: {name: [B, C, len]}.  Every tensor under both metrics - 32-column windows and output rows - against
+    edge_gate(the oracle's fp32 figures of this case, tensor and metric).  Logs the case's `[edge]` line -> (failures, {(name, metric): gate})."""
+    fails, gates, parts = [], {}, []
+    for name, t in truth.items():
+        g = torch.as_tensor(x[name]).cpu()
+        assert torch.isfinite(g).all(), f"{case} {name}: non-finite"
+        for metric, fn, starts in _METRICS:
+            eg, er = fn(g, t), fn(ref[name], t)
+            gate = gates[name, metric] = edge_gate(er)
+            b, i = divmod(int(eg.argmax()), eg.shape[1])
+            where = f"row {i}" if starts is None else f"column {starts(t.shape[2])[i]} of {t.shape[2]}"
+            parts.append(f"{name} per {metric} GPU {float(eg.max()):.2e} (utterance {b} {where}) / oracle fp32 {float(er.max()):.2e} / gate {gate:.2e}")
+            for b, i in (eg > gate).nonzero().tolist()[:4]:
+                where = f"row {i}" if starts is None else f"columns from {starts(t.shape[2])[i]} of {t.shape[2]}"
+                fails.append(f"{name} utterance {b} {where}: {float(eg[b, i]):.2e} > gate {gate:.2e}")
+    if log:
+        print(f"[edge] {case}: " + "; ".join(parts) + "; whole tensor " + ", ".join(f"{k} {rel_rms(torch.as_tensor(x[k]).cpu(), t):.2e}" for k, t in truth.items()) + extra)
+    return fails, gates
+
+
+def planted_errors_trip(x, truth, gates):
+    """The gates' own sensitivity, on the host -> the planted errors that did NOT trip their gate (want: none).  `kernel` row 960 and
+    `amps` row 14 x (1 + 1e-4) against the row gate; + 1e-4 x the utterance's rms on the last two columns of each tensor against the window gate."""
+    missed = []
+    for name, row in (("kernel", 960), ("amps", 14)):
+        b = torch.as_tensor(x[name]).cpu().double().clone()
+        b[:, row] *= 1.0 + 1e-4
+        if not bool((row_errors(b, truth[name])[:, row] > gates[name, "row"]).all()):
+            missed.append(f"{name} row {row} x (1 + 1e-4)")
+    for name, t in truth.items():
+        b = torch.as_tensor(x[name]).cpu().double().clone()
+        b[..., -2:] += 1e-4 * torch.sqrt((t * t).mean(dim=(1, 2)))[:, None, None]
+        if not bool((window_errors(b, t)[:, -1] > gates[name, "window"]).all()):
+            missed.append(f"{name} last two columns + 1e-4 x rms")
+    return missed

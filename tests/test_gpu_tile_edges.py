@@ -26,13 +26,12 @@ one GPU block by 1e-4 of its rms ON THE HOST and requires the gate to trip."""
 import pytest
 import torch
 
-from helpers import oracle_one_thread, rel_rms, state_dicts, window_errors, window_starts
+from helpers import _bump_trips, _gate_case, oracle_one_thread, rel_rms, state_dicts
 from oracle import ref_cpu as R
 from tinyvc_amd import synth
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-FLOOR = 3e-6
 
 
 @pytest.fixture(scope="module")
@@ -56,44 +55,6 @@ def _sd64():
         _SD64["e"] = {k: v.double() for k, v in enc_sd.items()}
         _SD64["d"] = {k: v.double() for k, v in dec_sd.items()}
     return _SD64["e"], _SD64["d"]
-
-
-def _group(name):
-    return name.split("[")[0]
-
-
-def _gate_case(case, gpu, truth, ref, extra=""):
-    """gpu / truth / ref: {name: [rows, C, len]} (gpu on the host).  Logs the case's `[edge]` line; returns (failures, {name: [rows] gates})."""
-    fails, gates, ermax, groups = [], {}, {}, {}
-    worst = None                                      # (e / gate, e, gate, name, row, column)
-    for name, t in truth.items():
-        g = gpu[name].cpu()
-        assert torch.isfinite(g).all(), f"{case} {name}: non-finite"
-        eg, er = window_errors(g, t), window_errors(ref[name], t)
-        gate = (2.0 * er.max(dim=1).values).clamp_min(FLOOR)
-        gates[name], ermax[name] = gate, er.max(dim=1).values
-        st = window_starts(t.shape[2])
-        a, b = groups.get(_group(name), (0.0, 0.0))
-        groups[_group(name)] = (max(a, float(eg.max())), max(b, float(er.max())))
-        ratio = eg / gate[:, None]
-        r, w = divmod(int(ratio.argmax()), ratio.shape[1])
-        if worst is None or float(ratio[r, w]) > worst[0]:
-            worst = (float(ratio[r, w]), float(eg[r, w]), float(gate[r]), name, r, st[w])
-        for r, w in (ratio > 1.0).nonzero().tolist()[:4]:
-            fails.append(f"{name} row {r} columns [{st[w]}, {st[w] + min(32, t.shape[2])}) of {t.shape[2]}: {float(eg[r, w]):.2e} > gate {float(gate[r]):.2e}")
-    _x, e, gt, name, r, col = worst
-    print(f"[edge] {case}: worst window GPU {e:.2e} (gate {gt:.2e}, oracle fp32 worst {float(ermax[name][r]):.2e}) "
-          f"at {name} row {r} column {col} of {truth[name].shape[2]}; whole tensor {rel_rms(gpu[name].cpu(), truth[name]):.2e}; worst GPU / oracle window per group: "
-          + ", ".join(f"{k} {a:.2e} / {b:.2e}" for k, (a, b) in groups.items()) + extra)
-    return fails, gates
-
-
-def _bump_trips(gpu, truth, gates, name):
-    """The gate's own sensitivity: + 1e-4 x rms on the last two columns of block `name`, on the host; does a window exceed its gate?"""
-    t = truth[name]
-    bumped = gpu[name].cpu().double().clone()
-    bumped[..., -2:] += 1e-4 * torch.sqrt((t * t).mean(dim=(1, 2)))[:, None, None]
-    return bool((window_errors(bumped, t) > gates[name][:, None]).any())
 
 
 # ------------------------------------------------------------------------------------------------ FilterNet
