@@ -15,6 +15,7 @@ path has no CPU fallback.
 
 Shapes follow the reference: waveforms [B, L] @24 kHz, feature maps [B, C, T], T = L / 480.
 """
+import contextlib
 import math
 
 import torch
@@ -34,6 +35,67 @@ def _fp(x):
     """fp32 like the reference - except that an fp64 tensor stays fp64: evaluating this file on `.double()` weights and inputs
     gives the path's fp64 value, the fixed truth tests/test_gpu_truth.py measures both fp32 implementations against."""
     return x if x.dtype == torch.float64 else x.float()
+
+
+# --------------------------------------------------------------------------- linear interpolation
+_FP32_POSITIONS = False
+
+
+@contextlib.contextmanager
+def fp32_positions():
+    """Inside this block an fp64 tensor is interpolated at the source positions ATen computes for fp32 tensors (lerp_positions), with the
+    blend still in fp64.  The path's fp64 value then differs from the reference's fp32 arithmetic by rounding alone: plain fp64
+    F.interpolate also moves every position by up to one fp32 ulp of `src` (2^-8 of a sample at column 48 000), a difference of
+    definition that grows with the length.  fp32 tensors are not affected."""
+    global _FP32_POSITIONS
+    saved, _FP32_POSITIONS = _FP32_POSITIONS, True
+    try:
+        yield
+    finally:
+        _FP32_POSITIONS = saved
+
+
+def lerp_positions(n_in, n_out, scale, fused=True):
+    """ATen's linear source positions (align_corners=False) for an fp32 tensor, as tinyvc_amd/csrc/small_kernels.h:lerp_coord restates them:
+    src = fp32 fma(scale, dst + 0.5, -0.5) clamped at 0, i0 = min(floor(src), n_in - 1), i1 = min(i0 + 1, n_in - 1), lambda = src - i0 and
+    w0 = 1 - lambda in fp32 -> (i0, i1 int64 [n_out], w0, lambda fp32 [n_out]).  `scale` is the fp32 ratio (interp_scale).  The fma is
+    taken in fp64: the product of two fp32 numbers is exact there, and so is the sum wherever it is not negative (a negative one is
+    clamped to 0), so rounding it to fp32 is the fma's single rounding.  fused=False rounds the product to fp32 first - NOT what ATen
+    does; tests/test_wave_truth_host.py uses it to show that its bound tells the two apart."""
+    scale = torch.tensor(scale, dtype=torch.float32)
+    dst = torch.arange(n_out, dtype=torch.float32) + 0.5
+    if fused:
+        src = (scale.double() * dst.double() - 0.5).float()
+    else:
+        src = scale * dst - 0.5
+    src = src.clamp_min(0.0)
+    f = torch.floor(src).clamp_max(float(n_in - 1))
+    lam = (src - f).clamp(0.0, 1.0)
+    i0 = f.long()
+    return i0, (i0 + 1).clamp_max(n_in - 1), 1.0 - lam, lam
+
+
+def interp_scale(n_in, size=None, scale_factor=None):
+    """ATen's conventions -> (n_out, the fp32 ratio): `size` given: float32(n_in) / float32(n_out); `scale_factor` given:
+    n_out = floor(n_in * scale_factor) and float32(1 / scale_factor), both taken in fp64 first."""
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32)
+    if size is not None:
+        return int(size), float(f32(float(n_in)) / f32(float(size)))
+    return int(math.floor(float(n_in) * scale_factor)), float(f32(1.0 / scale_factor))
+
+
+def interp_fp32_positions(x, size=None, scale_factor=None, fused=True):
+    """F.interpolate(x, mode='linear') of [B, C, n] restated on lerp_positions; the blend w0 x0 + lambda x1 runs in x's own dtype."""
+    n_out, scale = interp_scale(x.shape[2], size, scale_factor)
+    i0, i1, w0, lam = lerp_positions(x.shape[2], n_out, scale, fused)
+    return w0.to(x.dtype) * x[..., i0] + lam.to(x.dtype) * x[..., i1]
+
+
+def _interp(x, size=None, scale_factor=None):
+    """Every linear interpolation of this file: F.interpolate, except for an fp64 tensor under fp32_positions()."""
+    if _FP32_POSITIONS and x.dtype == torch.float64:
+        return interp_fp32_positions(x, size, scale_factor)
+    return F.interpolate(x, size=size, scale_factor=scale_factor, mode="linear")
 
 
 # --------------------------------------------------------------------------- front end (a1-a3)
@@ -58,7 +120,7 @@ def estimate_energy(wf):
     """reference module/utils/energy_estimation.py:9-14 — max|x| over 128-sample windows every 64
     samples (pad 32), linearly interpolated back to L -> [B, 1, L]."""
     e = F.max_pool1d(wf.abs().unsqueeze(1), 128, 64, 32)
-    return F.interpolate(e, wf.shape[1], mode="linear")
+    return _interp(e, size=wf.shape[1])
 
 
 # --------------------------------------------------------------------------- ConvNeXt-v2 (a4-a6)
@@ -185,8 +247,8 @@ def oscillate_harmonics(f0, num_harmonics=NUM_HARMONICS, fmin=20.0):
     T = f0.shape[2]
     L = T * HOP
     mul = (torch.arange(num_harmonics + 1) + 1).view(1, -1, 1)
-    fs = F.interpolate(f0, L, mode="linear") * mul
-    uv = F.interpolate((f0 > fmin).to(f0.dtype), L, mode="linear")
+    fs = _interp(f0, size=L) * mul
+    uv = _interp((f0 > fmin).to(f0.dtype), size=L)
     cyc = torch.cumsum(fs / SAMPLE_RATE, dim=2)
     return torch.sin(2 * math.pi * (cyc % 1)) * uv
 
@@ -201,7 +263,7 @@ def oscillate_noise(kernel, angle):
 
 def dsp(f0, amps, kernel, angle):
     """reference module/tinyvc/decoder.py:259-266 -> source [B, 16, L]."""
-    harm = oscillate_harmonics(f0) * F.interpolate(amps, scale_factor=HOP, mode="linear")
+    harm = oscillate_harmonics(f0) * _interp(amps, scale_factor=HOP)
     return torch.cat([harm, oscillate_noise(kernel, angle)], dim=1)
 
 
@@ -211,7 +273,7 @@ def _lrelu(x):
 
 def filter_downsample(sd, p, x, factor):
     """reference module/tinyvc/decoder.py:147-157."""
-    x = F.interpolate(x, scale_factor=1.0 / factor, mode="linear")
+    x = _interp(x, scale_factor=1.0 / factor)
     res = F.conv1d(x, sd[p + ".down_res.weight"], sd[p + ".down_res.bias"])
     h = x
     for name, d in (("c1", 1), ("c2", 2), ("c3", 4)):
@@ -221,7 +283,7 @@ def filter_downsample(sd, p, x, factor):
 
 def filter_upsample(sd, p, x, c, factor):
     """reference module/tinyvc/decoder.py:173-190."""
-    x = F.interpolate(x, scale_factor=factor, mode="linear")
+    x = _interp(x, scale_factor=factor)
     for (ca, da), (cb, db), film in ((("c1", 1), ("c2", 3), "film1"), (("c3", 9), ("c4", 27), "film2")):
         h = conv1d_rep(_lrelu(x), sd[f"{p}.{ca}.weight"], sd[f"{p}.{ca}.bias"], da)
         h = conv1d_rep(_lrelu(h), sd[f"{p}.{cb}.weight"], sd[f"{p}.{cb}.bias"], db)

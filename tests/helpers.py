@@ -373,6 +373,56 @@ def _bump_trips(gpu, truth, gates, name):
     return bool((window_errors(bumped, t) > gates[name][:, None]).any())
 
 
+# FilterNet cases of test_gpu_tile_edges.py (a) and (b); test_wave_truth_host.py proves their truth and gates with the oracle alone
+FILTER_EDGE_LENGTHS = [1, 3, 9, 12, 25, 26, 28, 37, 43, 65, 127, 128, 129, 136, 512]       # (a): B = 1; the seam table is in the GPU file
+WIDE_FILM_SHAPES = [(64, 100), (256, 5)]                                                   # (b): (B, T), rows 0, 1, B / 2, B - 1
+_SD64 = {}
+
+
+def sd64():
+    """(encoder, decoder) state_dicts(0) in fp64"""
+    if not _SD64:
+        enc_sd, dec_sd = state_dicts(0)
+        _SD64["e"] = {k: v.double() for k, v in enc_sd.items()}
+        _SD64["d"] = {k: v.double() for k, v in dec_sd.items()}
+    return _SD64["e"], _SD64["d"]
+
+
+def filter_edge_inputs(B, T):
+    """test_filter_net_blocks_out_of_range's recipe at scale 1, seed 1000 + T -> (content, f0, energy, source)."""
+    g = torch.Generator().manual_seed(1000 + T)
+    L = 480 * T
+    content = torch.randn(B, 768, T, generator=g) * 0.5
+    f0 = 80.0 + 200.0 * torch.rand(B, 1, T, generator=g)
+    source = torch.randn(B, 16, L, generator=g) * 0.3
+    energy = torch.rand(B, 1, L, generator=g)
+    return content, f0, energy, source
+
+
+def filter_named(wave, skips, ups):
+    """filter_net's (waveform, skips, ups) -> the ten compared tensors by name; ups[4] is not among them: the waveform is its only view."""
+    d = {f"downs[{i}]": s for i, s in enumerate(skips)}
+    d.update({f"ups[{i}]": u for i, u in enumerate(ups[:4])})
+    d["wave"] = wave if wave.dim() == 3 else wave[:, None, :]
+    return d
+
+
+def filter_edge_oracle(inputs, fp32_positions=True):
+    """(truth, yardstick) of the ten compared tensors for the given rows.  Truth: the oracle in fp64 at the source positions ATen computes
+    for fp32 tensors (oracle.ref_cpu.fp32_positions); fp32_positions=False: at fp64 positions, the truth of test_gpu_truth.py.  Yardstick:
+    the oracle in fp32 on one thread."""
+    import contextlib
+
+    from oracle import ref_cpu as R
+    _e64, d64 = sd64()
+    _enc_sd, dec_sd = state_dicts(0)
+    with R.fp32_positions() if fp32_positions else contextlib.nullcontext():
+        truth = filter_named(*R.filter_net(d64, *[x.double() for x in inputs], return_blocks=True))
+    with oracle_one_thread():
+        ref = filter_named(*R.filter_net(dec_sd, *inputs, return_blocks=True))
+    return truth, ref
+
+
 def row_errors(x, truth):
     """[B, C, len] against an fp64 `truth` -> [B, C] (fp64): per utterance b and output row c, the rms over time of x - truth divided by the rms
     of truth[b] over the WHOLE utterance - window_errors with rows for columns.  Not the row's own rms: ELU + 1 outputs go down to 5e-6 where
