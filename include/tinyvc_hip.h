@@ -489,7 +489,55 @@ int tvc_convert_ragged_alpha_f32(tvc_ctx* ctx, void* stream, const float* wav, i
                                  const float* target_f0, float pitch_shift, const float* pitch_shifts, float* shift_out,
                                  const float* noise_angle, uint64_t seed, float* wave, int B, void* ws, size_t ws_bytes);
 
-/* streaming tail -------------------------------------------------------------------------- */
+/* protect: a per-frame share of the source from the call's own f0 -------------------------------- */
+/* A per-row alpha keeps the source's features on every frame alike.  RVC's `protect` keeps more of them on UNVOICED frames only - consonants,
+ * breaths, silence, where the kNN match has least to offer - and leaves voiced frames fully converted.  Here it is a second per-row value
+ * beside alpha.  Definition, over ONE utterance of T frames (a ragged batch: the utterance's own T_b frames; a stream: the window's frames):
+ *   - voicing flag u[t] = f0[t] > 0 ? 1 : 0, f0 the f0 this call's encoder decodes, before any shift (the stage calls: the caller's f0); NaN
+ *     and negative values count as unvoiced.
+ *   - voicing weight v[t] = (u[t-1] + 2 u[t] + u[t+1]) / 4 with u[-1] = u[0] and u[T] = u[T-1]: neighbours never cross into another
+ *     utterance, row or stream.  w[t] = 1 - v[t] takes only the values {0, .25, .5, .75, 1}, all exact in fp32.
+ *   - with a = alpha[row] (alpha == NULL: 0) and p = protect[row], the frame's share is a_t = a + (1 - a) * (p * w[t]) - torch's eager
+ *     expression on fp32 tensors, every operation rounded separately (one subtraction, two products, one sum; no fused multiply-add).
+ *   - every element of the frame's query column is then stored as out = mu * (1 - a_t) + src * a_t, rounded exactly as the alpha form rounds.
+ * So: on a fully unvoiced frame (w = 1) the match keeps the share (1 - a)(1 - p) - RVC's composition of index rate and protect with
+ * p = 1 - (RVC's protect value), as a = 1 - (RVC's index rate); p = 0 is the alpha call bit for bit (and with alpha NULL or 0 the plain
+ * call's bits); a fully voiced neighbourhood (w = 0) is untouched by p; a = 0, p = 1, w = 1 stores the source's bits; the indices do not
+ * depend on p.  protect is meant for [0, 1]; like alpha it is neither clamped nor normalised and any finite value is computed as defined.
+ * The 3-tap weight is a guess at a useful smoothing, not a tuned one: nobody has listened to any setting.
+ * The decoder's content bound stays per utterance: with a_u = a + (1 - a) * p (the same roundings; every a_t lies between a and a_u because
+ * rounding is monotonic) it is max(|1 - a|, |1 - a_u|) * (the index's bound) + max(|a|, |a_u|) * (the measured |max| of the utterance's own
+ * encoder output), products and sum rounded separately - at p = 0 the alpha call's bound exactly, so such rows keep its scales and bits.
+ * alpha and protect are DEVICE arrays of one fp32 per caller's row, read when the kernels run (a captured graph follows in-place changes).
+ * tvc_convert_protect_f32 / tvc_convert_ragged_protect_f32: the alpha entries' arguments plus `protect` behind alpha.  protect == NULL is the
+ * alpha call, launch for launch (and with alpha NULL too its sibling); alpha == NULL with protect set means a = 0.  Table and blend forms,
+ * target_f0 and the tracker as there.  One more launch (one thread per query column writes a_t into B * T floats of workspace) in front of
+ * the search, and the per-column instantiation of the merge + gather kernels.  Workspace: tvc_workspace_bytes_protect / _ragged_protect
+ * (enough with or without alpha, protect, target_f0 and a tracker).  Per-row contract: row b is bit-identical to its own B = 1 call.
+ * tvc_knn_match_protect_f32, the stage call: tvc_knn_match_alpha_f32 with f0 [B][T] (device, behind src; needed when protect is set) and
+ * protect behind alpha.
+ * tvc_frame_share_f32: the a_t kernel alone over packed rows, row i = columns [row_start[i], row_start[i] + row_count[i]) of f0 and of
+ * share_out (HOST arrays of `rows` entries, below 2^31; an empty row writes nothing; columns outside every row are not written); alpha
+ * (nullable = 0) and protect are device arrays of `rows` floats.  No workspace. */
+int tvc_workspace_bytes_protect(tvc_ctx* ctx, int B, int64_t L, const int64_t* N, int M, size_t* out_bytes);
+int tvc_convert_protect_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M,
+                            const float* weights, const float* alpha, const float* protect, const float* target_f0, int start, int n, int W,
+                            int min_voiced, float slew, float* ring, int64_t* count, float* auto_shift, float pitch_shift,
+                            const float* pitch_shifts, float* shift_out, const float* noise_angle, uint64_t seed, float* wave, int B,
+                            int64_t L, void* ws, size_t ws_bytes);
+int tvc_workspace_bytes_ragged_protect(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, const int64_t* N, int M, size_t* out_bytes);
+int tvc_convert_ragged_protect_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens,
+                                   const float* const* prepared, const int64_t* N, int M, const float* weights, const float* alpha,
+                                   const float* protect, const float* target_f0, float pitch_shift, const float* pitch_shifts,
+                                   float* shift_out, const float* noise_angle, uint64_t seed, float* wave, int B, void* ws,
+                                   size_t ws_bytes);
+int tvc_knn_match_protect_f32(tvc_ctx* ctx, void* stream, const float* src, const float* f0, const float* const* prepared,
+                              const int64_t* N, int M, const float* weights, const float* alpha, const float* protect, float* out,
+                              int64_t* idx_out, int B, int T, void* ws, size_t ws_bytes);
+int tvc_frame_share_f32(tvc_ctx* ctx, void* stream, const float* f0, const int64_t* row_start, const int64_t* row_count, int rows,
+                        const float* alpha, const float* protect, float* share_out);
+
+/* streaming tail-------------------------------------------------------------------------- */
 /* StreamInfer.audio_callback after convert (reference module/infer/stream.py:74-95), batched over
  * S streams: y [S, Ly] converted buffers; sola_buf [S,1920] in/out; fade_in [1920] = the sin^2
  * window init_buffer builds (stream.py:61; fade_out = 1 - fade_in); out [S, block];

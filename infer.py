@@ -57,7 +57,7 @@ def build_parser():
     p.add_argument("-d", "--device", default="cuda")
     p.add_argument("-p", "--pitch-shift", default=0.0, type=float)
     add_auto_pitch_argument(p)      # --auto-pitch: every file's median f0 onto the target's register; -p stays, as the offset
-    add_alpha_argument(p)           # --alpha A: keep that share of every file's own content features in the match
+    add_alpha_argument(p)           # --alpha A: keep that share of every file's own content features in the match; --protect P: more on unvoiced frames
     p.add_argument("-c", "--chunk-size", default=1920, type=int)
     p.add_argument("-b", "--buffer-size", default=4, type=int)
     p.add_argument("-nc", "--no-chunking", default=False, type=bool)
@@ -132,7 +132,7 @@ def convert_chunked(gen, batch, tgt, pitch_shift, chunk_size, buffer_blocks, use
     `noise_angles(i)` -> [B, 961, T] injects the decoder's noise phases of block i (parity runs against the oracle's
     `stream_callback`; default: drawn on the device per block, as the reference's `torch.rand` is).
     `return_blocks`: also return the untrimmed block outputs [B, nblk, chunk_size] and the SOLA lags [nblk, B].
-    `stream_kw`: further BatchedStreamInfer keywords (alpha)."""
+    `stream_kw`: further BatchedStreamInfer keywords (alpha, protect)."""
     from tinyvc_amd.module.infer import BatchedStreamInfer
     B, L = batch.shape
     st = BatchedStreamInfer(gen, n_streams=B, target=tgt, pitch_shift=pitch_shift, device=batch.device, block_size=chunk_size,
@@ -179,7 +179,7 @@ def main(argv=None, world=None, rank=None, local_rank=None):
         if getattr(tgt, "pitch_register", None) is None:
             sys.exit(f"infer.py: --auto-pitch: no pitch register beside {args.index} (extract_index.py writes <index>.f0.pt)")
         auto = True
-    alpha_kw = alpha_keywords(args, "infer.py")      # {} without --alpha: every call below is then the call it has always been
+    alpha_kw = alpha_keywords(args, "infer.py")      # {} without --alpha / --protect: every call below is then the call it has always been
     os.makedirs(args.outputs, exist_ok=True)
 
     paths = []

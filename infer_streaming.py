@@ -86,7 +86,7 @@ def build_parser():
     p.add_argument("--auto-pitch-warmup", default=0.5, type=float, metavar="SECONDS", help="voiced speech heard before the automatic shift starts")
     p.add_argument("--auto-pitch-slew", default=6.0, type=float, metavar="SEMITONES_PER_SECOND", help="how fast the automatic shift may move; 0 = unlimited")
     add_blend_argument(p)      # --blend PATH=W [PATH=W ...] -> args.blend = (paths, weights)
-    add_alpha_argument(p)      # --alpha A: keep that share of every stream's own content features in the match (stream.alpha, live on the device)
+    add_alpha_argument(p)      # --alpha A: keep that share of every stream's own content features in the match (stream.alpha, live on the device); --protect P (stream.protect)
     p.add_argument("-c", "--chunk", default=1920, type=int)
     p.add_argument("-e", "--extra", default=3840, type=int)
     p.add_argument("-d", "--device", default="cuda")
@@ -303,7 +303,7 @@ def main(argv=None):
     if block is not None:
         print(f"Resampling {rate} Hz <-> 24000 Hz on the device: {args.chunk}-sample blocks are {block} at the model's rate; "
               f"the two filters add {door.latency_seconds * 1e3:.2f} ms of latency")
-    alpha_kw = alpha_keywords(args, "infer_streaming.py")      # {} without --alpha: the stream is then built as it has always been
+    alpha_kw = alpha_keywords(args, "infer_streaming.py")      # {} without --alpha / --protect: the stream is then built as it has always been
     gate = None
     if gate_kw is not None:
         gate = StreamGate(S, door.block_size, device=device, **gate_kw)

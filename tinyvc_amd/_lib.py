@@ -92,6 +92,17 @@ SIGNATURES = {
     "tvc_workspace_bytes_ragged_alpha": (c_int, [c_void_p, c_int, c_int64, POINTER(c_int64), POINTER(c_int64), c_int, POINTER(c_size_t)]),
     "tvc_convert_ragged_alpha_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64), POINTER(c_void_p), POINTER(c_int64), c_int, c_void_p,
                                              c_void_p, c_void_p, c_float, POINTER(c_float), c_void_p, c_void_p, c_uint64, c_void_p, c_int, c_void_p, c_size_t]),
+    "tvc_workspace_bytes_protect": (c_int, [c_void_p, c_int, c_int64, POINTER(c_int64), c_int, POINTER(c_size_t)]),
+    "tvc_convert_protect_f32": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_int64), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                        c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_float, POINTER(c_float), c_void_p, c_void_p, c_uint64,
+                                        c_void_p, c_int, c_int64, c_void_p, c_size_t]),
+    "tvc_workspace_bytes_ragged_protect": (c_int, [c_void_p, c_int, c_int64, POINTER(c_int64), POINTER(c_int64), c_int, POINTER(c_size_t)]),
+    "tvc_convert_ragged_protect_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64), POINTER(c_void_p), POINTER(c_int64), c_int, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_float, POINTER(c_float), c_void_p, c_void_p, c_uint64, c_void_p, c_int, c_void_p,
+                                               c_size_t]),
+    "tvc_knn_match_protect_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_int64), c_int, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t]),
+    "tvc_frame_share_f32": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int64), c_int, c_void_p, c_void_p, c_void_p]),
     "tvc_ctx_set_index_assign_chunk":(c_int, [c_void_p, c_int]),
     "tvc_workspace_bytes_index_compact": (c_int, [c_void_p, c_int64, c_int64, POINTER(c_size_t)]),
     "tvc_index_assign_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),

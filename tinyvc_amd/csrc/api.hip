@@ -215,12 +215,16 @@ int tvc::convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const ConvertCall& c)
     const int NB = ctx->rag ? ctx->rag->B : B;
     // An alpha call (c.alpha) mixes the share a of ssl into `matched`: its bound takes the measured |max| of the utterance's own ssl - one more
     // atomicMax slot per utterance behind the encoder's, zeroed with them - and becomes |1 - a| * (the index's bound) + |a| * that maximum.
-    const int nslots = c.alpha ? 4 : 3;
+    // A protect call (c.protect; c.alpha may be null = 0) is an alpha call whose share is per frame: share[column] = a + (1 - a) * (p * w) from the
+    // f0 decoded here (run_frame_share behind the encoder), and its bound takes the larger factors of a and a + (1 - a) * p.
+    const bool mixed = c.alpha || c.protect;
+    const int nslots = mixed ? 4 : 3;
     float* emax = ws.get<float>((size_t)(2 + nslots) * NB);
     float* spec_bound = emax + NB;
     float* enc_slots = spec_bound + NB;      // the encoder's three atomicMax slots: zeroed by the energy stage's pooled-maximum launch
-    float* srcmax = c.alpha ? enc_slots + 3 * NB : nullptr;
-    float* abound = c.alpha ? ws.get<float>((size_t)NB) : nullptr;
+    float* srcmax = mixed ? enc_slots + 3 * NB : nullptr;
+    float* abound = mixed ? ws.get<float>((size_t)NB) : nullptr;
+    float* share = c.protect ? ws.get<float>((size_t)B * T) : nullptr;
     // one index per row: every utterance's matched-content bound is its own index's |max| (so its fp16-split scales, and its bits, are those
     // of its own B = 1 call), and its runs of query columns go to the search as segments; per-row pitch shifts travel like the lengths.
     // A blend (ix.M terms per row): the (term, row) runs over ix.M x the columns, term-major, and the bound is sum_m |w_m| * |max|_m.
@@ -276,21 +280,22 @@ int tvc::convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const ConvertCall& c)
             }
             TVC_CHECK(run_pitch_match(ctx, s, f0, rows, c.target_f0, nullptr, nullptr, c.shift_out, f0s));
         }
+        if (c.protect && !ws.dry) TVC_CHECK(run_frame_share(ctx, s, f0, c.alpha, c.protect, share, B, T));      // from f0 itself, before any shift
     }
     ws.release(m);
     {
         ProfScope ps(ctx, s, ws, "knn");
-        if (ix.M > 0) TVC_CHECK(run_knn_blend(ctx, s, ws, ssl, segs.data(), (int)segs.size(), ix.M, ix.weights, matched, nullptr, B, T, c.alpha));
-        else TVC_CHECK(run_knn_segs(ctx, s, ws, ssl, segs.data(), (int)segs.size(), matched, nullptr, B, T, c.alpha));
+        if (ix.M > 0) TVC_CHECK(run_knn_blend(ctx, s, ws, ssl, segs.data(), (int)segs.size(), ix.M, ix.weights, matched, nullptr, B, T, c.alpha, share));
+        else TVC_CHECK(run_knn_segs(ctx, s, ws, ssl, segs.data(), (int)segs.size(), matched, nullptr, B, T, c.alpha, share));
     }
     ws.release(m);
     const float* idx_bound = ws.dry ? nullptr : (ix.per_row ? rowmax : blob_amax(ix.blob));
-    if (c.alpha && !ws.dry) {
+    if (mixed && !ws.dry) {
         TVC_CHECK(run_ssl_amax(ctx, s, ssl, B, T, srcmax));
-        TVC_CHECK(run_knn_alpha_bound(ctx, s, c.alpha, idx_bound, ix.per_row ? 1 : 0, srcmax, abound, NB));
+        TVC_CHECK(run_knn_alpha_bound(ctx, s, c.alpha, idx_bound, ix.per_row ? 1 : 0, srcmax, abound, NB, c.protect));
     }
-    TVC_CHECK(run_decoder(ctx, s, ws, matched, f0s, energy, c.angle, c.seed, c.wave, nullptr, nullptr, nullptr, B, T, c.alpha && !ws.dry ? abound : idx_bound, emax,
-                          c.alpha || ix.per_row ? 1 : 0));
+    TVC_CHECK(run_decoder(ctx, s, ws, matched, f0s, energy, c.angle, c.seed, c.wave, nullptr, nullptr, nullptr, B, T, mixed && !ws.dry ? abound : idx_bound, emax,
+                          mixed || ix.per_row ? 1 : 0));
     ws.release(m);
     return 0;
 }
@@ -612,7 +617,7 @@ static int convert_entry(tvc_ctx* ctx, void* stream, const ConvertCall& c, bool 
 // table (it takes workspace; never read in this walk): a call whose rows share blobs, or without per-row shifts, needs less.
 // (No allocation depends on whether the call brings its own noise phases.)
 static int convert_query(tvc_ctx* ctx, int B, int64_t L, const int64_t* lens, bool ragged, const ConvertIndex& ix, size_t* out_bytes, const char* what,
-                         bool auto_pitch = false, bool alpha = false) {
+                         bool auto_pitch = false, bool alpha = false, bool protect = false) {
     TVC_CHECK(need_ready(ctx, NEED_NONE));
     if (!out_bytes || (ragged && !lens) || (ix.per_row ? !ix.Ns : ix.N < 4) || B <= 0 || L <= 0 || L % kHop != 0)
         return fail(ctx, TVC_ERR_ARG, "%s: need B>0, %s%%480==0, %s%s", what, ragged ? "Lmax" : "L", ragged && ix.per_row ? "lens[B], " : "", ix.per_row ? "N[B]" : "N>=4");
@@ -633,6 +638,7 @@ static int convert_query(tvc_ctx* ctx, int B, int64_t L, const int64_t* lens, bo
     c.shifts = ix.per_row ? &shift : nullptr;
     c.target_f0 = auto_pitch ? kDryPtr : nullptr;
     c.alpha = alpha ? kDryPtr : nullptr;
+    c.protect = protect ? kDryPtr : nullptr;
     if (!ragged) return measure(1, out_bytes, [&](Ws& ws) { return convert_impl(ctx, nullptr, ws, c); });
     std::vector<RagBatchPlan> batches;
     TVC_CHECK(ragged_split(ctx, ctx->rag_batch_frames, B, L, lens, &batches));
@@ -675,9 +681,16 @@ int tvc_convert_ragged_multi_f32(tvc_ctx* ctx, void* stream, const float* wav, i
     return convert_entry(ctx, stream, c, true, wsp, ws_bytes, "tvc_convert_ragged_multi_f32");
 }
 
-// the match against one index per row, under the entry's own name `what`; alpha (nullable): the alpha form of the same call
+// the stage calls' share per column: with protect set, B * T floats of workspace (both walks) filled from the caller's f0 [B][T] in front of the search
+static int match_share(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* f0, const float* alpha, const float* protect, int B, int T, float** share) {
+    *share = protect ? ws.get<float>((size_t)B * T) : nullptr;
+    if (protect && !ws.dry) TVC_CHECK(run_frame_share(ctx, s, f0, alpha, protect, *share, B, T));
+    return 0;
+}
+// the match against one index per row, under the entry's own name `what`; alpha (nullable): the alpha form of the same call; protect
+// (nullable, with f0): its protect form
 static int match_table(tvc_ctx* ctx, void* stream, const float* src, const float* const* prepared, const int64_t* N, const float* alpha, float* out,
-                       int64_t* idx_out, int B, int T, void* wsp, size_t ws_bytes, const char* what) {
+                       int64_t* idx_out, int B, int T, void* wsp, size_t ws_bytes, const char* what, const float* f0 = nullptr, const float* protect = nullptr) {
     if (!ctx) return TVC_ERR_ARG;
     if (!src || !out || B <= 0 || T <= 0 || (int64_t)B * T > 0x7fffffff) return fail(ctx, TVC_ERR_ARG, "%s: bad argument", what);
     hipStream_t s = (hipStream_t)stream;
@@ -685,7 +698,11 @@ static int match_table(tvc_ctx* ctx, void* stream, const float* src, const float
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<KnnSegIn> in((size_t)B);
     for (int b = 0; b < B; ++b) in[b] = KnnSegIn{prepared[b], N[b], b * T, T};
-    return run_walks(ctx, what, wsp, ws_bytes, 1, [&](Ws& ws) { return run_knn_segs(ctx, s, ws, src, in.data(), B, out, idx_out, B, T, alpha); });
+    return run_walks(ctx, what, wsp, ws_bytes, 1, [&](Ws& ws) {
+        float* share;
+        TVC_CHECK(match_share(ctx, s, ws, f0, alpha, protect, B, T, &share));
+        return run_knn_segs(ctx, s, ws, src, in.data(), B, out, idx_out, B, T, alpha, share);
+    });
 }
 int tvc_knn_match_multi_f32(tvc_ctx* ctx, void* stream, const float* src, const float* const* prepared, const int64_t* N, float* out,
                             int64_t* idx_out, int B, int T, void* wsp, size_t ws_bytes) {
@@ -821,9 +838,10 @@ int tvc_convert_track_f32(tvc_ctx* ctx, void* stream, const float* wav, const fl
     return convert_entry(ctx, stream, c, false, wsp, ws_bytes, "tvc_convert_track_f32");
 }
 
-// the match against a blend, under the entry's own name `what`; alpha (nullable): the alpha form of the same call
+// the match against a blend, under the entry's own name `what`; alpha (nullable): the alpha form of the same call; protect (nullable, with f0): its protect form
 static int match_blend(tvc_ctx* ctx, void* stream, const float* src, const float* const* prepared, const int64_t* N, int M, const float* weights,
-                       const float* alpha, float* out, int64_t* idx_out, int B, int T, void* wsp, size_t ws_bytes, const char* what) {
+                       const float* alpha, float* out, int64_t* idx_out, int B, int T, void* wsp, size_t ws_bytes, const char* what, const float* f0 = nullptr,
+                       const float* protect = nullptr) {
     if (!ctx) return TVC_ERR_ARG;
     if (!src || !out || B <= 0 || T <= 0) return fail(ctx, TVC_ERR_ARG, "%s: bad argument", what);
     TVC_CHECK(blend_check(ctx, B, M, weights, what));
@@ -834,7 +852,11 @@ static int match_blend(tvc_ctx* ctx, void* stream, const float* src, const float
     std::vector<KnnSegIn> in;
     for (int m = 0; m < M; ++m)
         for (int b = 0; b < B; ++b) in.push_back(KnnSegIn{prepared[(size_t)b * M + m], N[(size_t)b * M + m], (m * B + b) * T, T});
-    return run_walks(ctx, what, wsp, ws_bytes, 1, [&](Ws& ws) { return run_knn_blend(ctx, s, ws, src, in.data(), (int)in.size(), M, weights, out, idx_out, B, T, alpha); });
+    return run_walks(ctx, what, wsp, ws_bytes, 1, [&](Ws& ws) {
+        float* share;
+        TVC_CHECK(match_share(ctx, s, ws, f0, alpha, protect, B, T, &share));
+        return run_knn_blend(ctx, s, ws, src, in.data(), (int)in.size(), M, weights, out, idx_out, B, T, alpha, share);
+    });
 }
 int tvc_knn_match_blend_f32(tvc_ctx* ctx, void* stream, const float* src, const float* const* prepared, const int64_t* N, int M, const float* weights,
                             float* out, int64_t* idx_out, int B, int T, void* wsp, size_t ws_bytes) {
@@ -844,7 +866,8 @@ int tvc_knn_match_blend_f32(tvc_ctx* ctx, void* stream, const float* src, const 
 // ---- alpha: a share of the source's own content features kept in the match (the reference's match_features(..., alpha)) ---------------------
 // The table form of the auto entries plus `alpha` (device, one fp32 per row); alpha == NULL is the sibling call.  One ConvertCall field and one
 // argument of the kNN drivers: no second path.
-static int alpha_query(tvc_ctx* ctx, int B, int64_t L, const int64_t* lens, bool ragged, const int64_t* N, int M, size_t* out_bytes, const char* what) {
+static int alpha_query(tvc_ctx* ctx, int B, int64_t L, const int64_t* lens, bool ragged, const int64_t* N, int M, size_t* out_bytes, const char* what,
+                       bool protect = false) {
     if (!ctx) return TVC_ERR_ARG;
     TVC_CHECK(blend_check(ctx, B, M, kDryPtr, what));
     size_t most = 0;
@@ -852,7 +875,7 @@ static int alpha_query(tvc_ctx* ctx, int B, int64_t L, const int64_t* lens, bool
         for (int table = 0; table < (M == 1 ? 2 : 1); ++table) {
             size_t bytes = 0;
             TVC_CHECK(convert_query(ctx, B, L, lens, ragged, table ? ConvertIndex::table(nullptr, N) : ConvertIndex::blend(nullptr, N, M, nullptr), &bytes, what,
-                                    auto_pitch != 0, true));
+                                    auto_pitch != 0, true, protect));
             if (bytes > most) most = bytes;
         }
     *out_bytes = most;
@@ -864,40 +887,106 @@ int tvc_workspace_bytes_alpha(tvc_ctx* ctx, int B, int64_t L, const int64_t* N, 
 int tvc_workspace_bytes_ragged_alpha(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, const int64_t* N, int M, size_t* out_bytes) {
     return alpha_query(ctx, B, Lmax, lens, true, N, M, out_bytes, "tvc_workspace_bytes_ragged_alpha");
 }
+// the alpha and the protect entries share their bodies: protect == nullptr is the alpha call, under the entry's own name `what`
+static int convert_alpha(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M, const float* weights,
+                         const float* alpha, const float* protect, const float* target_f0, int start, int n, int W, int min_voiced, float slew, float* ring,
+                         int64_t* count, float* auto_shift, float pitch_shift, const float* pitch_shifts, float* shift_out, const float* noise_angle,
+                         uint64_t seed, float* wave, int B, int64_t L, void* wsp, size_t ws_bytes, const char* what) {
+    ConvertIndex ix;
+    TVC_CHECK(auto_index(ctx, B, prepared, N, M, weights, &ix, what));
+    ConvertCall c{wav, wave, B, L, nullptr, ix, pitch_shift, pitch_shifts, noise_angle, seed, target_f0, target_f0 ? shift_out : nullptr};
+    c.alpha = alpha;
+    c.protect = protect;
+    const PitchTrackState t{start, n, W, min_voiced, slew, ring, count, auto_shift};
+    if (ring) {      // a tracker: tvc_convert_track_f32's checks
+        if (L <= 0 || L / kHop > 0x7fffffff) return fail(ctx, TVC_ERR_ARG, "%s: bad argument (L must be a positive multiple of 480)", what);
+        TVC_CHECK(track_check(ctx, B, (int)(L / kHop), t, target_f0, what));
+        c.track = &t;
+    }
+    return convert_entry(ctx, stream, c, false, wsp, ws_bytes, what);
+}
+static int convert_ragged_alpha(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens, const float* const* prepared,
+                                const int64_t* N, int M, const float* weights, const float* alpha, const float* protect, const float* target_f0,
+                                float pitch_shift, const float* pitch_shifts, float* shift_out, const float* noise_angle, uint64_t seed, float* wave, int B,
+                                void* wsp, size_t ws_bytes, const char* what) {
+    ConvertIndex ix;
+    TVC_CHECK(auto_index(ctx, B, prepared, N, M, weights, &ix, what));
+    ConvertCall c{wav, wave, B, Lmax, lens, ix, pitch_shift, pitch_shifts, noise_angle, seed, target_f0, target_f0 ? shift_out : nullptr};
+    c.alpha = alpha;
+    c.protect = protect;
+    return convert_entry(ctx, stream, c, true, wsp, ws_bytes, what);
+}
+static int match_alpha(tvc_ctx* ctx, void* stream, const float* src, const float* f0, const float* const* prepared, const int64_t* N, int M,
+                       const float* weights, const float* alpha, const float* protect, float* out, int64_t* idx_out, int B, int T, void* wsp, size_t ws_bytes,
+                       const char* what) {
+    if (!ctx) return TVC_ERR_ARG;
+    if ((alpha || protect) && src && src == out)
+        return fail(ctx, TVC_ERR_ARG, "%s: out must be another buffer than src (the source's share is read while out is written)", what);
+    if (protect && !f0) return fail(ctx, TVC_ERR_ARG, "%s: protect needs f0 (device, [B][T]: the voicing comes from it)", what);
+    if (weights) return match_blend(ctx, stream, src, prepared, N, M, weights, alpha, out, idx_out, B, T, wsp, ws_bytes, what, f0, protect);
+    if (M != 1) return fail(ctx, TVC_ERR_ARG, "%s: weights = NULL is one index per row: M must be 1, got %d", what, M);
+    return match_table(ctx, stream, src, prepared, N, alpha, out, idx_out, B, T, wsp, ws_bytes, what, f0, protect);
+}
 int tvc_convert_alpha_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M, const float* weights,
                           const float* alpha, const float* target_f0, int start, int n, int W, int min_voiced, float slew, float* ring, int64_t* count,
                           float* auto_shift, float pitch_shift, const float* pitch_shifts, float* shift_out, const float* noise_angle, uint64_t seed,
                           float* wave, int B, int64_t L, void* wsp, size_t ws_bytes) {
-    ConvertIndex ix;
-    TVC_CHECK(auto_index(ctx, B, prepared, N, M, weights, &ix, "tvc_convert_alpha_f32"));
-    ConvertCall c{wav, wave, B, L, nullptr, ix, pitch_shift, pitch_shifts, noise_angle, seed, target_f0, target_f0 ? shift_out : nullptr};
-    c.alpha = alpha;
-    const PitchTrackState t{start, n, W, min_voiced, slew, ring, count, auto_shift};
-    if (ring) {      // a tracker: tvc_convert_track_f32's checks
-        if (L <= 0 || L / kHop > 0x7fffffff) return fail(ctx, TVC_ERR_ARG, "tvc_convert_alpha_f32: bad argument (L must be a positive multiple of 480)");
-        TVC_CHECK(track_check(ctx, B, (int)(L / kHop), t, target_f0, "tvc_convert_alpha_f32"));
-        c.track = &t;
-    }
-    return convert_entry(ctx, stream, c, false, wsp, ws_bytes, "tvc_convert_alpha_f32");
+    return convert_alpha(ctx, stream, wav, prepared, N, M, weights, alpha, nullptr, target_f0, start, n, W, min_voiced, slew, ring, count, auto_shift, pitch_shift,
+                         pitch_shifts, shift_out, noise_angle, seed, wave, B, L, wsp, ws_bytes, "tvc_convert_alpha_f32");
 }
 int tvc_convert_ragged_alpha_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens, const float* const* prepared,
                                  const int64_t* N, int M, const float* weights, const float* alpha, const float* target_f0, float pitch_shift,
                                  const float* pitch_shifts, float* shift_out, const float* noise_angle, uint64_t seed, float* wave, int B, void* wsp,
                                  size_t ws_bytes) {
-    ConvertIndex ix;
-    TVC_CHECK(auto_index(ctx, B, prepared, N, M, weights, &ix, "tvc_convert_ragged_alpha_f32"));
-    ConvertCall c{wav, wave, B, Lmax, lens, ix, pitch_shift, pitch_shifts, noise_angle, seed, target_f0, target_f0 ? shift_out : nullptr};
-    c.alpha = alpha;
-    return convert_entry(ctx, stream, c, true, wsp, ws_bytes, "tvc_convert_ragged_alpha_f32");
+    return convert_ragged_alpha(ctx, stream, wav, Lmax, lens, prepared, N, M, weights, alpha, nullptr, target_f0, pitch_shift, pitch_shifts, shift_out, noise_angle,
+                                seed, wave, B, wsp, ws_bytes, "tvc_convert_ragged_alpha_f32");
 }
 int tvc_knn_match_alpha_f32(tvc_ctx* ctx, void* stream, const float* src, const float* const* prepared, const int64_t* N, int M, const float* weights,
                             const float* alpha, float* out, int64_t* idx_out, int B, int T, void* wsp, size_t ws_bytes) {
-    const char* what = "tvc_knn_match_alpha_f32";
+    return match_alpha(ctx, stream, src, nullptr, prepared, N, M, weights, alpha, nullptr, out, idx_out, B, T, wsp, ws_bytes, "tvc_knn_match_alpha_f32");
+}
+
+// ---- protect: the alpha entries with a per-frame share - more of the source on the unvoiced frames of the f0 the call decodes --------------
+// `protect` (device, one fp32 per row) behind alpha; protect == NULL is the alpha call, launch for launch; alpha == NULL with protect set: a = 0.
+int tvc_workspace_bytes_protect(tvc_ctx* ctx, int B, int64_t L, const int64_t* N, int M, size_t* out_bytes) {
+    return alpha_query(ctx, B, L, nullptr, false, N, M, out_bytes, "tvc_workspace_bytes_protect", true);
+}
+int tvc_workspace_bytes_ragged_protect(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, const int64_t* N, int M, size_t* out_bytes) {
+    return alpha_query(ctx, B, Lmax, lens, true, N, M, out_bytes, "tvc_workspace_bytes_ragged_protect", true);
+}
+int tvc_convert_protect_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M, const float* weights,
+                            const float* alpha, const float* protect, const float* target_f0, int start, int n, int W, int min_voiced, float slew,
+                            float* ring, int64_t* count, float* auto_shift, float pitch_shift, const float* pitch_shifts, float* shift_out,
+                            const float* noise_angle, uint64_t seed, float* wave, int B, int64_t L, void* wsp, size_t ws_bytes) {
+    return convert_alpha(ctx, stream, wav, prepared, N, M, weights, alpha, protect, target_f0, start, n, W, min_voiced, slew, ring, count, auto_shift, pitch_shift,
+                         pitch_shifts, shift_out, noise_angle, seed, wave, B, L, wsp, ws_bytes, "tvc_convert_protect_f32");
+}
+int tvc_convert_ragged_protect_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens, const float* const* prepared,
+                                   const int64_t* N, int M, const float* weights, const float* alpha, const float* protect, const float* target_f0,
+                                   float pitch_shift, const float* pitch_shifts, float* shift_out, const float* noise_angle, uint64_t seed, float* wave,
+                                   int B, void* wsp, size_t ws_bytes) {
+    return convert_ragged_alpha(ctx, stream, wav, Lmax, lens, prepared, N, M, weights, alpha, protect, target_f0, pitch_shift, pitch_shifts, shift_out, noise_angle,
+                                seed, wave, B, wsp, ws_bytes, "tvc_convert_ragged_protect_f32");
+}
+int tvc_knn_match_protect_f32(tvc_ctx* ctx, void* stream, const float* src, const float* f0, const float* const* prepared, const int64_t* N, int M,
+                              const float* weights, const float* alpha, const float* protect, float* out, int64_t* idx_out, int B, int T, void* wsp,
+                              size_t ws_bytes) {
+    return match_alpha(ctx, stream, src, f0, prepared, N, M, weights, alpha, protect, out, idx_out, B, T, wsp, ws_bytes, "tvc_knn_match_protect_f32");
+}
+int tvc_frame_share_f32(tvc_ctx* ctx, void* stream, const float* f0, const int64_t* row_start, const int64_t* row_count, int rows, const float* alpha,
+                        const float* protect, float* share_out) {
+    const char* what = "tvc_frame_share_f32";
     if (!ctx) return TVC_ERR_ARG;
-    if (alpha && src && src == out) return fail(ctx, TVC_ERR_ARG, "%s: out must be another buffer than src (the source's share is read while out is written)", what);
-    if (weights) return match_blend(ctx, stream, src, prepared, N, M, weights, alpha, out, idx_out, B, T, wsp, ws_bytes, what);
-    if (M != 1) return fail(ctx, TVC_ERR_ARG, "%s: weights = NULL is one index per row: M must be 1, got %d", what, M);
-    return match_table(ctx, stream, src, prepared, N, alpha, out, idx_out, B, T, wsp, ws_bytes, what);
+    if (!f0 || !row_start || !row_count || rows <= 0 || !protect || !share_out || f0 == share_out) return fail(ctx, TVC_ERR_ARG, "%s: bad argument", what);
+    std::vector<int> start((size_t)rows), len((size_t)rows);
+    for (int b = 0; b < rows; ++b) {
+        if (row_start[b] < 0 || row_count[b] < 0 || row_start[b] + row_count[b] > 0x7fffffff)
+            return fail(ctx, TVC_ERR_ARG, "%s: row %d = [%lld, +%lld) beyond 32-bit indexing", what, b, (long long)row_start[b], (long long)row_count[b]);
+        start[b] = (int)row_start[b];
+        len[b] = (int)row_count[b];
+    }
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    return run_frame_share_rows(ctx, (hipStream_t)stream, f0, start, len, alpha, protect, share_out);
 }
 
 // ---- ragged batches: the plan (ragged.hip) as callers see it, and the ragged encode ----------------------------------------------------

@@ -81,8 +81,16 @@ struct AlphaIn {
     const int* rowmap;
 };
 __device__ __forceinline__ float alpha_of_column(const AlphaIn& al, int nc, int T) { return al.alpha[al.col2b ? al.rowmap[al.col2b[nc]] : nc / T]; }
-// store_tile_along_t with the source's share a of this thread's column mixed in
-__device__ __forceinline__ void store_tile_along_t_alpha(const float (&tile)[32][193], float* __restrict__ out, const AlphaIn& al, float a, int n0,
+// The protect forms (tvc_*_protect_f32) give every query COLUMN its own share: a = share[column], the a_t that frame_share_kernel below wrote
+// from the call's f0 in front of the search.  The same store phase, and no col2b / rowmap lookup: one more instantiation of the two kernels.
+struct ShareIn {
+    const float* share;      // [ncols]
+    const float* src;        // [B][768][T], as AlphaIn's
+};
+__device__ __forceinline__ float alpha_of_column(const ShareIn& sh, int nc, int) { return sh.share[nc]; }
+// store_tile_along_t with the source's share a of this thread's column mixed in (AI: AlphaIn or ShareIn)
+template <class AI>
+__device__ __forceinline__ void store_tile_along_t_alpha(const float (&tile)[32][193], float* __restrict__ out, const AI& al, float a, int n0,
                                                          int ncols, int T, int kc) {
     const float* __restrict__ src = al.src;
     const float keep = __fsub_rn(1.f, a);
@@ -101,7 +109,8 @@ __device__ __forceinline__ void store_tile_along_t_alpha(const float (&tile)[32]
 // gather the 4 raw rows per query (coalesced along the feature axis), average, and write
 // out[b][k][t] through an LDS transpose so stores run along t.  Every query takes its segment's blob and lists (col2seg: several
 // segments; the 32 columns may straddle a segment boundary).  MULTI = false: one segment, whose blob the gather reads as a uniform value.
-// A... = AlphaIn: the alpha form (an instantiation with one more argument); empty: the kernel as it has always been, argument for argument.
+// A... = AlphaIn: the alpha form (an instantiation with one more argument), ShareIn: the protect form; empty: the kernel as it has always been,
+// argument for argument.
 template <bool MULTI, class... A>
 static __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
                                                                       const KnnSegs segs, const int* __restrict__ col2seg, int ncols, int T,
@@ -163,7 +172,7 @@ static __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const floa
 // in registers - products and sums rounded separately (__fmul_rn / __fadd_rn), in term order - so the per-term matched tensors never exist
 // in memory.  One LDS transpose, stores along t.  weights [rows][M] is the caller's DEVICE array, read here: a captured graph replays with
 // whatever it holds then.  The weight row of a column is its batch row, or rowmap[col2b[column]] in a ragged batch (ragged.h).
-// A... = AlphaIn: the alpha form, as above - the accumulated blend is the mu of its definition, alpha's row the weights'.
+// A... = AlphaIn: the alpha form, as above - the accumulated blend is the mu of its definition, alpha's row the weights'; ShareIn: the protect form.
 constexpr int BLEND_MAX = TVC_BLEND_MAX;
 template <class... A>
 static __global__ __launch_bounds__(256) void knn_merge_blend_gather_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
@@ -243,11 +252,95 @@ static __global__ __launch_bounds__(256) void alpha_bound_kernel(const float* __
     const float a = alpha[row ? row[i] : i];
     out[i] = __fadd_rn(__fmul_rn(fabsf(__fsub_rn(1.f, a)), idx_bound[(long)i * stride]), __fmul_rn(fabsf(a), srcmax[i]));
 }
-int run_knn_alpha_bound(tvc_ctx* ctx, hipStream_t s, const float* alpha, const float* idx_bound, int stride, const float* srcmax, float* out, int n) {
+// a + (1 - a) * (p * w), every operation rounded on its own: the share of a frame of unvoiced weight w under alpha a and protect p
+__device__ __forceinline__ float share_of_frame(float a, float p, float w) { return __fadd_rn(a, __fmul_rn(__fsub_rn(1.f, a), __fmul_rn(p, w))); }
+// The protect form (alpha nullable: a = 0): a frame's share a_t lies between a (w = 0) and a_u = a + (1 - a) * p (w = 1) - rounding is monotonic -,
+// so out[i] = max(|1 - a|, |1 - a_u|) * idx_bound + max(|a|, |a_u|) * srcmax; at p = 0, a_u == a and it is the kernel above's value exactly.
+static __global__ __launch_bounds__(256) void protect_bound_kernel(const float* __restrict__ alpha, const float* __restrict__ protect,
+                                                                   const int* __restrict__ row, const float* __restrict__ idx_bound, int stride,
+                                                                   const float* __restrict__ srcmax, float* __restrict__ out, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int r = row ? row[i] : i;
+    const float a = alpha ? alpha[r] : 0.f;
+    const float au = share_of_frame(a, protect[r], 1.f);
+    out[i] = __fadd_rn(__fmul_rn(fmaxf(fabsf(__fsub_rn(1.f, a)), fabsf(__fsub_rn(1.f, au))), idx_bound[(long)i * stride]),
+                       __fmul_rn(fmaxf(fabsf(a), fabsf(au)), srcmax[i]));
+}
+int run_knn_alpha_bound(tvc_ctx* ctx, hipStream_t s, const float* alpha, const float* idx_bound, int stride, const float* srcmax, float* out, int n,
+                        const float* protect) {
     const RagHost* h = ctx->rag;
-    hipLaunchKernelGGL(alpha_bound_kernel, dim3((n + 255) / 256), dim3(256), 0, s, alpha, h ? (const int*)h->d_row : (const int*)nullptr, idx_bound, stride, srcmax,
-                       out, n);
+    const int* row = h ? (const int*)h->d_row : (const int*)nullptr;
+    if (protect) {
+        hipLaunchKernelGGL(protect_bound_kernel, dim3((n + 255) / 256), dim3(256), 0, s, alpha, protect, row, idx_bound, stride, srcmax, out, n);
+        return launch_check(ctx, "knn_protect_bound");
+    }
+    hipLaunchKernelGGL(alpha_bound_kernel, dim3((n + 255) / 256), dim3(256), 0, s, alpha, row, idx_bound, stride, srcmax, out, n);
     return launch_check(ctx, "knn_alpha_bound");
+}
+
+// ---- protect: a per-frame source share from the call's own f0 (tvc_*_protect_f32, tvc_frame_share_f32) -----------------------------------
+// Frame t of an utterance of len frames at f0[0 .. len): u[t] = f0[t] > 0 (NaN and negatives: unvoiced), the voicing weight
+// v[t] = (u[t-1] + 2 u[t] + u[t+1]) / 4 with u[-1] = u[0], u[len] = u[len-1] - neighbours never leave the utterance -, w = 1 - v one of
+// {0, .25, .5, .75, 1} (exact), and the frame keeps a_t = a + (1 - a) * (p * w) of the source: torch's eager expression on fp32 tensors, every
+// operation rounded on its own.  p = 0: a_t == a, bit for bit (a + 0 or a + (-0)).
+__device__ __forceinline__ float frame_share_one(const float* __restrict__ f0, int len, int t, float a, float p) {
+    const int tl = t > 0 ? t - 1 : 0, tr = t + 1 < len ? t + 1 : len - 1;
+    const int voiced = (f0[tl] > 0.f ? 1 : 0) + (f0[t] > 0.f ? 2 : 0) + (f0[tr] > 0.f ? 1 : 0);
+    return share_of_frame(a, p, (float)(4 - voiced) * 0.25f);
+}
+// one thread per query column n of a conversion: share[n] = a_t of its frame.  Its utterance: row n / T, columns [row * T, row * T + T) - or,
+// in a ragged batch (col2b set: ragged.h's tables), utterance u = col2b[n], columns [pre[u], pre[u] + tb[u]), the caller's row rowmap[u].
+static __global__ __launch_bounds__(256) void frame_share_kernel(const float* __restrict__ f0, const float* __restrict__ alpha,
+                                                                 const float* __restrict__ protect, const int* __restrict__ col2b,
+                                                                 const int* __restrict__ pre, const int* __restrict__ tb, const int* __restrict__ rowmap,
+                                                                 int ncols, int T, float* __restrict__ share) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= ncols) return;
+    int row = n / T, start = row * T, len = T;
+    if (col2b) {
+        const int u = col2b[n];
+        row = rowmap[u];
+        start = pre[u];
+        len = tb[u];
+    }
+    share[n] = frame_share_one(f0 + start, len, n - start, alpha ? alpha[row] : 0.f, protect[row]);
+}
+int run_frame_share(tvc_ctx* ctx, hipStream_t s, const float* f0, const float* alpha, const float* protect, float* share, int B, int T) {
+    const RagHost* h = ctx->rag;
+    const int ncols = B * T;
+    hipLaunchKernelGGL(frame_share_kernel, dim3((ncols + 255) / 256), dim3(256), 0, s, f0, alpha, protect, h ? (const int*)h->d_col2b : (const int*)nullptr,
+                       h ? (const int*)h->d_pre : (const int*)nullptr, h ? (const int*)h->d_tb : (const int*)nullptr, h ? (const int*)h->d_row : (const int*)nullptr,
+                       ncols, T, share);
+    return launch_check(ctx, "frame_share");
+}
+// the same over caller's rows: row i = columns [start[i], start[i] + len[i]) of f0 and share, the rows travel as kernel arguments (blockIdx.y)
+constexpr int FS_ROWS = 256;
+struct FrameShareRows {
+    int start[FS_ROWS], len[FS_ROWS];
+};
+static __global__ __launch_bounds__(256) void frame_share_rows_kernel(FrameShareRows r, int row0, const float* __restrict__ f0, const float* __restrict__ alpha,
+                                                                      const float* __restrict__ protect, float* __restrict__ share) {
+    const int i = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= r.len[i]) return;
+    const long start = r.start[i];
+    share[start + t] = frame_share_one(f0 + start, r.len[i], t, alpha ? alpha[row0 + i] : 0.f, protect[row0 + i]);
+}
+int run_frame_share_rows(tvc_ctx* ctx, hipStream_t s, const float* f0, const std::vector<int>& start, const std::vector<int>& len, const float* alpha,
+                         const float* protect, float* share) {
+    for (size_t o = 0; o < start.size(); o += FS_ROWS) {
+        FrameShareRows r;
+        const int n = (int)(start.size() - o < FS_ROWS ? start.size() - o : FS_ROWS);
+        int longest = 0;
+        for (int i = 0; i < n; ++i) {
+            r.start[i] = start[o + i];
+            r.len[i] = len[o + i];
+            if (len[o + i] > longest) longest = len[o + i];
+        }
+        if (longest == 0) continue;
+        hipLaunchKernelGGL(frame_share_rows_kernel, dim3((longest + 255) / 256, n), dim3(256), 0, s, r, (int)o, f0, alpha, protect, share);
+    }
+    return launch_check(ctx, "frame_share_rows");
 }
 
 // out[i] = sum_m |w[row[i]][m]| * (the |max| of blob (i, m)), in term order, products and sums rounded separately: the bound of row i's blended
@@ -377,12 +470,19 @@ int run_knn_finish(tvc_ctx* ctx, hipStream_t s, const float* slots, float* out, 
 }
 
 int run_knn_segs(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const KnnSegIn* in, int nin, float* out, int64_t* idx_out, int B, int T,
-                 const float* alpha) {
+                 const float* alpha, const float* share) {
     KnnCall c;
     TVC_CHECK(knn_call_plan(ctx, in, nin, B * T, &c));
     KnnLists L;
     TVC_CHECK(knn_candidates(ctx, s, ws, src, c, B, T, &L));
     if (ws.dry) return 0;
+    if (share) {      // the protect form: a share per column (run_frame_share), which has alpha in it
+        const ShareIn sh{share, src};
+        const auto skernel = L.col2seg ? knn_merge_gather_kernel<true, ShareIn> : knn_merge_gather_kernel<false, ShareIn>;
+        hipLaunchKernelGGL(skernel, dim3((c.ncols + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)L.col2seg, c.ncols, T, out, idx_out, L.rv, L.ri,
+                           (const int*)L.flag, sh);
+        return launch_check(ctx, "knn_match_protect");
+    }
     if (alpha) {      // the alpha form: the same lists, the source's share mixed in at the store (a ragged batch finds alpha's row through its tables)
         const RagHost* h = ctx->rag;
         const AlphaIn al{alpha, src, h ? (const int*)h->d_col2b : (const int*)nullptr, h ? (const int*)h->d_row : (const int*)nullptr};
@@ -401,13 +501,20 @@ int run_knn_segs(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const Kn
 // knn_candidates walk - every pass one launch, as run_knn_segs -, then the blend gather.  idx_out (nullable): [M][B][T][4].  A ragged batch
 // (ctx->rag: B = 1, T = all its frames) finds a column's weight row through the batch's tables.
 int run_knn_blend(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const KnnSegIn* in, int nin, int M, const float* weights, float* out,
-                  int64_t* idx_out, int B, int T, const float* alpha) {
+                  int64_t* idx_out, int B, int T, const float* alpha, const float* share) {
     KnnCall c;
     TVC_CHECK(knn_call_plan(ctx, in, nin, M * B * T, &c));
     KnnLists L;
     TVC_CHECK(knn_candidates(ctx, s, ws, src, c, M * B, T, &L, B));
     if (ws.dry) return 0;
     const RagHost* h = ctx->rag;
+    if (share) {
+        const ShareIn sh{share, src};
+        hipLaunchKernelGGL(knn_merge_blend_gather_kernel<ShareIn>, dim3((B * T + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)L.col2seg, B * T, T, M,
+                           weights, h ? (const int*)h->d_col2b : (const int*)nullptr, h ? (const int*)h->d_row : (const int*)nullptr, out, idx_out, L.rv, L.ri,
+                           (const int*)L.flag, sh);
+        return launch_check(ctx, "knn_match_blend_protect");
+    }
     if (alpha) {
         const int* col2b = h ? (const int*)h->d_col2b : nullptr;
         const int* rowmap = h ? (const int*)h->d_row : nullptr;

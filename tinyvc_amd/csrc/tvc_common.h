@@ -355,18 +355,28 @@ struct KnnSegIn {
     int col0, ncols;
 };
 // alpha (optional, both drivers): the caller's DEVICE array [rows] of the source's own share - out = mu * (1 - a) + src * a with mu the alpha-less
-// result (knn_gather.hip); nullptr launches exactly what the call without it launches
+// result (knn_gather.hip); nullptr launches exactly what the call without it launches.  share (optional, both drivers; takes alpha's place): a
+// DEVICE array of one share per query COLUMN (run_frame_share's, which has alpha in it) - the protect form of the same store
 int run_knn_segs(tvc_ctx*, hipStream_t, Ws&, const float* src, const KnnSegIn* in, int nin, float* out, int64_t* idx_out, int B, int T,
-                 const float* alpha = nullptr);
+                 const float* alpha = nullptr, const float* share = nullptr);
 // a weighted blend of M indices per row (knn_gather.hip): in[] = the (term, row) runs over M * B * T VIRTUAL query columns, term-major - term m's
 // search of real column n is column m * B * T + n -, weights = the caller's device array [rows][M] (read by the kernels, never by the host),
 // out [B][768][T] = w_0 * mu_0 + ... in term order, idx_out (nullable) [M][B][T][4]
 int run_knn_blend(tvc_ctx*, hipStream_t, Ws&, const float* src, const KnnSegIn* in, int nin, int M, const float* weights, float* out, int64_t* idx_out,
-                  int B, int T, const float* alpha = nullptr);
+                  int B, int T, const float* alpha = nullptr, const float* share = nullptr);
 // out[i] = sum_m |weights[rows[i]][m]| * *blob_amax(blobs[i * M + m]): the bound of row i's blended content
 int run_knn_blend_bound(tvc_ctx*, hipStream_t, const std::vector<const float*>& blobs, const std::vector<int>& rows, int M, const float* weights, float* out);
 // the content bound of an alpha call: out[i] = |1 - a| * idx_bound[i * stride] + |a| * srcmax[i] for utterance i < n, a = alpha[its row]
-int run_knn_alpha_bound(tvc_ctx*, hipStream_t, const float* alpha, const float* idx_bound, int stride, const float* srcmax, float* out, int n);
+// protect (optional; alpha then nullable = 0): with a_u = a + (1 - a) * protect[row], max(|1 - a|, |1 - a_u|) and max(|a|, |a_u|) take the factors' places
+int run_knn_alpha_bound(tvc_ctx*, hipStream_t, const float* alpha, const float* idx_bound, int stride, const float* srcmax, float* out, int n,
+                        const float* protect = nullptr);
+// share[n] = the source's share of query column n of a conversion of B rows of T frames (a ragged batch: ctx->rag, B = 1) from its f0 [B][T]:
+// a + (1 - a) * (p * w[n]), a = alpha[row] (nullptr: 0), p = protect[row], w the unvoiced weight of the frame within its own utterance
+// (knn_gather.hip frame_share_kernel; include/tinyvc_hip.h has the definition)
+int run_frame_share(tvc_ctx*, hipStream_t, const float* f0, const float* alpha, const float* protect, float* share, int B, int T);
+// the same over caller's rows i = columns [start[i], start[i] + len[i]) of f0 and share, alpha / protect one per row
+int run_frame_share_rows(tvc_ctx*, hipStream_t, const float* f0, const std::vector<int>& start, const std::vector<int>& len, const float* alpha,
+                         const float* protect, float* share);
 // slot[utterance] = max |ssl| of that utterance (slot already zeroed on this stream; encoder.hip)
 int run_ssl_amax(tvc_ctx*, hipStream_t, const float* ssl, int B, int T, float* slot);
 
@@ -418,6 +428,9 @@ struct ConvertCall {
     // tvc_convert_*alpha_f32: alpha (device, one fp32 per caller's row, read when the kernels run) keeps that share of the row's own content
     // features - matched = mu * (1 - a) + ssl * a - and the decoder's content bound becomes |1 - a| * (the index's) + |a| * max |ssl|
     const float* alpha = nullptr;
+    // tvc_convert_*protect_f32: protect (device, one fp32 per caller's row; alpha may then be nullptr = 0) raises the share on unvoiced frames of
+    // the f0 this call decodes - a_t = a + (1 - a) * (p * w[t]), one per query column (run_frame_share) in the place of the row's alpha
+    const float* protect = nullptr;
 };
 // Generator.convert over c.B rows of c.L samples (c.lens is not looked at: a ragged call reaches this through convert_ragged_batches,
 // one batch at a time as ONE row with ctx->rag set, ragged.h)

@@ -88,6 +88,19 @@ _MATCH = {
     "blend": ("tvc_workspace_bytes_blend", "tvc_knn_match_blend_f32"),
     "alpha": ("tvc_workspace_bytes_alpha", "tvc_knn_match_alpha_f32"),
 }
+# form "protect": the alpha rows' calls with `protect` behind alpha (and f0 behind the stage call's src) - (ragged,) for a conversion, "match"
+_PROTECT = {
+    False: ("tvc_workspace_bytes_protect", "tvc_convert_protect_f32"),
+    True: ("tvc_workspace_bytes_ragged_protect", "tvc_convert_ragged_protect_f32"),
+    "match": ("tvc_workspace_bytes_protect", "tvc_knn_match_protect_f32"),
+}
+
+
+def _names(form, ragged=None):
+    """(workspace query, entry) of a conversion (`ragged` a bool) or a match (None) from the tables above"""
+    if form == "protect":
+        return _PROTECT["match" if ragged is None else ragged]
+    return _MATCH[form] if ragged is None else _CONVERT[form, ragged]
 
 
 _RESAMPLE_STATE = (Field("state", _F32, "hist", 0.0),)      # what stream_resample takes of a door: one side's history
@@ -461,7 +474,7 @@ class Engine:
         return blobs, ns, M
 
     def _per_row(self, t, name, B):
-        """a value per row of a call (`name`: target_f0, the target registers; alpha, the source's share): a contiguous fp32 [B] tensor on
+        """a value per row of a call (`name`: target_f0, the target registers; alpha, the source's share; protect, its rise on unvoiced frames): a contiguous fp32 [B] tensor on
         this device, used in place (the kernels read it when they run) - anything else is refused here, never copied"""
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name} must be a torch.Tensor on the device (a contiguous fp32 [B = {B}]), got {type(t).__name__}")
@@ -473,13 +486,13 @@ class Engine:
     def _index_args(self, form, prepared, Ns, weights, B):
         """The index of a call, checked on the host -> (what the entry takes for it, what its workspace query takes for it).  shared:
         (prepared, Ns) = one blob and its N; table: one blob and N per row; blend: weights [B, M] on the device, prepared / Ns row-major
-        [B * M]; auto, track, alpha: the blend form, or with weights None the table form as M = 1."""
+        [B * M]; auto, track, alpha, protect: the blend form, or with weights None the table form as M = 1."""
         if form == "shared":
             return (_ptr(prepared), Ns), (int(max(Ns, 4)),)
         if form == "table":
             blobs, ns = self._table(prepared, Ns, B)
             return (blobs, ns), (ns,)
-        if form in ("auto", "track", "alpha") and weights is None:
+        if form in ("auto", "track", "alpha", "protect") and weights is None:
             blobs, ns = self._table(prepared, Ns, B)
             return (blobs, ns, 1, None), (ns, 1)
         blobs, ns, M = self._blend_args(prepared, Ns, weights, B)
@@ -501,23 +514,31 @@ class Engine:
         return wav, B, L
 
     # ---- kNN match: one driver, the public forms forward to it ----
-    def _match(self, form, src, prepared, Ns, weights=None, want_indices=False, alpha=None):
+    def _match(self, form, src, prepared, Ns, weights=None, want_indices=False, alpha=None, f0=None, protect=None):
         """src [B, 768, T] matched against the index (`form`, prepared, Ns, weights: _index_args) -> matched [B, 768, T] (, indices [B, T, 4];
         [M, B, T, 4] for a blend: each term's own search).  form "alpha": the table (weights None) or blend form, and out = matched *
-        (1 - alpha[b]) + src * alpha[b] (alpha: _per_row; indices always [M, B, T, 4])."""
+        (1 - alpha[b]) + src * alpha[b] (alpha: _per_row; indices always [M, B, T, 4]).  form "protect": the alpha form with the frame's share
+        a_t = a + (1 - a) * (protect[b] * w[t]) in alpha's place, w from f0 [B, 1, T] / [B, T] (alpha None: a = 0)."""
         src = _prep(src, "source", self.device)
         B, C, T = src.shape
         if C != spec.SSL_DIM:
             raise ValueError(f"source must have {spec.SSL_DIM} channels")
         index, sized = self._index_args(form, prepared, Ns, weights, B)
+        head = (_ptr(src),)
         if form == "alpha":
             index += (_ptr(self._per_row(alpha, "alpha", B)),)
+        elif form == "protect":
+            f0 = _prep(f0, "f0", self.device)
+            if f0.numel() != B * T or f0.shape[0] != B:
+                raise ValueError(f"f0 must hold one value per frame, [B = {B}, 1, T = {T}] or [B, T], got {tuple(f0.shape)}")
+            index += (_ptr(self._per_row(alpha, "alpha", B)) if alpha is not None else None, _ptr(self._per_row(protect, "protect", B)))
+            head += (_ptr(f0),)
         out = torch.empty_like(src)
         terms = sized[1:]      # (M,) for a blend, else ()
         idx = torch.empty(*terms, B, T, 4, dtype=torch.int64, device=self.device) if want_indices else None
-        query, entry = _MATCH[form]
+        query, entry = _names(form)
         p, n = self._query_ws(query, B, T * spec.HOP, *sized)
-        self._ok(getattr(self.lib, entry)(self.ctx, self._stream(), _ptr(src), *index, _ptr(out), _ptr(idx), B, T, p, n), entry)
+        self._ok(getattr(self.lib, entry)(self.ctx, self._stream(), *head, *index, _ptr(out), _ptr(idx), B, T, p, n), entry)
         return (out, idx) if want_indices else out
 
     def knn_match(self, src, prepared, N, want_indices=False):
@@ -539,6 +560,29 @@ class Engine:
         the kernel runs (, indices [M, B, T, 4], M = 1 without weights: what the alpha-less call finds): tvc_knn_match_alpha_f32."""
         return self._match("alpha", src, prepared, Ns, weights, want_indices, alpha)
 
+    def knn_match_protect(self, src, f0, prepared, Ns, alpha, protect, weights=None, want_indices=False):
+        """knn_match_alpha with a share per FRAME: a_t = a + (1 - a) * (protect[b] * w[t]), w[t] = 1 - (u[t-1] + 2 u[t] + u[t+1]) / 4 the
+        unvoiced weight of frame t from f0 [B, 1, T] / [B, T] (u = f0 > 0, edges repeated, rows apart), alpha / protect contiguous fp32 [B]
+        device tensors read when the kernels run (alpha None: a = 0): tvc_knn_match_protect_f32."""
+        return self._match("protect", src, prepared, Ns, weights, want_indices, alpha, f0, protect)
+
+    def frame_share(self, f0_packed, start, counts, alpha, protect):
+        """The per-frame share alone (tvc_frame_share_f32): f0_packed any contiguous fp32 device tensor, row i = its flattened values
+        [start[i], start[i] + counts[i]); alpha (or None = 0) / protect contiguous fp32 [rows] device tensors -> a tensor like f0_packed
+        holding a_t at every row's columns and zeros elsewhere."""
+        f0 = _prep(f0_packed, "f0", self.device)
+        start, counts = [int(x) for x in start], [int(x) for x in counts]
+        rows = len(start)
+        if rows < 1 or len(counts) != rows or any(a < 0 or c < 0 or a + c > f0.numel() for a, c in zip(start, counts)):
+            raise ValueError(f"frame_share: start and counts must be equally many rows within the {f0.numel()} values of f0")
+        al = self._per_row(alpha, "alpha", rows) if alpha is not None else None
+        pr = self._per_row(protect, "protect", rows)
+        out = torch.zeros_like(f0)
+        I64 = ctypes.c_int64 * rows
+        self._ok(self.lib.tvc_frame_share_f32(self.ctx, self._stream(), _ptr(f0), I64(*start), I64(*counts), rows, _ptr(al), _ptr(pr), _ptr(out)),
+                 "tvc_frame_share_f32")
+        return out
+
     # ---- convert: one driver, the eight public forms forward to it ----
     def _track_args(self, track, S, T):
         """a PitchTrack's share of a call over S streams of T frames, checked on the host: (start, n, W, min_voiced, slew, ring, count, auto)"""
@@ -549,11 +593,12 @@ class Engine:
         return (start, n, track.window_frames, track.min_voiced, track.slew, *map(_ptr, state))
 
     def _convert(self, form, wav, prepared, Ns, pitch_shift, noise_angle=None, lengths=None, weights=None, target_f0=None, out=None, shift_out=None,
-                 track=None, alpha=None):
+                 track=None, alpha=None, protect=None):
         """wav [B, L] converted toward the index (`form`, prepared, Ns, weights: _index_args) -> wave [B, L]; form "auto" / "track" ->
         (wave, shifts [B]).  "track": "auto" with the register taken from `track` (a PitchTrack: the streams' history), equal lengths only.
         "alpha": the table / blend call keeping the share alpha[b] of row b's own content features (alpha: _per_row); with target_f0 it is the
-        "auto" call (-> (wave, shifts)), with `track` as well the "track" call.
+        "auto" call (-> (wave, shifts)), with `track` as well the "track" call.  "protect": the "alpha" call with protect[b] (_per_row) behind
+        alpha, which may then be None (a = 0): the share rises to a + (1 - a) * protect[b] on the unvoiced frames of the f0 the call decodes.
         lengths: a ragged batch (row b holds an utterance of lengths[b] samples, a multiple of 480, zero-padded behind it; every utterance
         is converted over its OWN length).  pitch_shift: a float, or one per row for every form but "shared".  Every host check comes
         first, then the noise draw (which advances torch's generator), then device work: a refused call leaves no trace."""
@@ -564,11 +609,15 @@ class Engine:
         if ragged and (form == "track" or track is not None):
             raise ValueError("track: streams advance in lock step, there is no ragged form")
         found = form in ("auto", "track")      # the shifts are found on the device: pitch_shift is the offset, the applied shifts come back
-        if form == "alpha":      # the table / blend call with or without target registers (and, equal lengths, a tracker), plus the source's share
+        if form in ("alpha", "protect"):      # the table / blend call with or without target registers (and, equal lengths, a tracker), plus the source's share
             found = target_f0 is not None
             if track is not None and not found:
                 raise ValueError("track needs target_f0: the tracker finds the register the automatic shift starts from")
-            index += (_ptr(self._per_row(alpha, "alpha", B)), _ptr(self._per_row(target_f0, "target_f0", B)) if found else None)
+            if form == "alpha":
+                index += (_ptr(self._per_row(alpha, "alpha", B)),)
+            else:
+                index += (_ptr(self._per_row(alpha, "alpha", B)) if alpha is not None else None, _ptr(self._per_row(protect, "protect", B)))
+            index += (_ptr(self._per_row(target_f0, "target_f0", B)) if found else None,)
             if not ragged:
                 index += self._track_args(track, B, L // spec.HOP) if track is not None else (0, 0, 0, 0, 0.0, None, None, None)
         elif found:
@@ -584,9 +633,9 @@ class Engine:
         if found:
             sh = shift_out if shift_out is not None else torch.empty(B, dtype=_F32, device=self.device)
             shift_args += (_ptr(sh),)
-        elif form == "alpha":
+        elif form in ("alpha", "protect"):
             shift_args += (None,)
-        query, entry = _CONVERT[form, ragged]
+        query, entry = _names(form, ragged)
         p, n = self._query_ws(query, B, L, *lens, *sized)
         head, tail = ((_ptr(wav), L, *lens), (B, p, n)) if ragged else ((_ptr(wav),), (B, L, p, n))
         self._ok(getattr(self.lib, entry)(self.ctx, self._stream(), *head, *index, *shift_args, _ptr(a), seed, _ptr(wave), *tail), entry)

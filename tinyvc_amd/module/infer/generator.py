@@ -6,8 +6,8 @@ from .. import utils
 from ...engine import pitch_shifts
 from .._base import HipModule
 from ..tinyvc import Decoder, Encoder
-from ..tinyvc.feature_retrieval import (alpha_rows, check_blend, check_references, prepare_reference, prepare_references, resolve_alpha,
-                                        resolve_auto_pitch, target_form, target_registers)
+from ..tinyvc.feature_retrieval import (alpha_rows, check_blend, check_references, prepare_reference, prepare_references, protect_rows,
+                                        resolve_alpha, resolve_auto_pitch, resolve_protect, target_form, target_registers)
 
 
 def _padded_lengths(lengths, B, L):
@@ -54,7 +54,7 @@ class Generator(HipModule):
 
     @torch.no_grad()
     def convert(self, wf, tgt, pitch_shift, f0_estimation="default", device=None, noise_angle=None, lengths=None, auto_pitch=None,
-                return_shift=False, track=None, alpha=None):
+                return_shift=False, track=None, alpha=None, protect=None):
         """generator.py:26-34: wf [B, L], tgt [1 or B, 768, N] -> converted waveform [B, L'] (L' = L
         padded to a multiple of 480).  `f0_estimation` / `device` are accepted and ignored exactly as
         in the reference.  `noise_angle` [B,961,T] (extension) injects the decoder's noise phases;
@@ -81,7 +81,13 @@ class Generator(HipModule):
         `alpha` (extension; the reference's match_features(..., alpha), which its convert never passes): keep that share of every row's own
         content features - matched * (1 - alpha) + features * alpha, inside the same call (tvc_convert_alpha_f32 /
         tvc_convert_ragged_alpha_f32) - a float, a list of B floats, or an fp32 [B] / [1] device tensor ([B]: used in place, read when the
-        kernels run).  Every target form, equal and ragged batches, with auto_pitch and track.  None (the default) is the call without it."""
+        kernels run).  Every target form, equal and ragged batches, with auto_pitch and track.  None (the default) is the call without it.
+        `protect` (extension; RVC's protect, as 1 - its value): raise that share on UNVOICED frames only - frame t keeps
+        a_t = alpha + (1 - alpha) * (protect * w[t]) of its own features, w[t] = 1 - (u[t-1] + 2 u[t] + u[t+1]) / 4 from the voicing u = f0 > 0
+        of the f0 this call decodes (before any shift; neighbours stay inside the utterance), so voiced frames keep alpha and a fully unvoiced
+        frame alpha + (1 - alpha) * protect (tvc_convert_protect_f32 / tvc_convert_ragged_protect_f32).  alpha's forms (a float, B floats, an
+        fp32 [B] / [1] device tensor), with or without alpha (None: 0), every target form, equal and ragged, auto_pitch and track; 0 is the
+        alpha call bit for bit, None (the default) the call without it.  The 3-tap weight is an untuned guess: nobody has listened."""
         # 1. classify the target once; malformed targets, registers and shift lists are refused before any engine or device work
         B = wf.shape[0] if wf.dim() == 2 else 1
         auto = auto_pitch is not None and auto_pitch is not False
@@ -103,6 +109,7 @@ class Generator(HipModule):
             track.columns(-(-wf.shape[-1] // 480))      # the tracked columns must lie within the (padded) call's frames
         shift, shifts = pitch_shifts(pitch_shift, B)
         share = resolve_alpha(alpha, B) if alpha is not None else None
+        guard = resolve_protect(protect, B) if protect is not None else None
         # 2. the inputs, on the device
         wf = utils.autopad_waveform(self._input_device(wf))
         eng = self.engine(wf.device)
@@ -118,13 +125,16 @@ class Generator(HipModule):
             blobs, ns = prepare_references([self._input_device(t) for t in tgt] if isinstance(tgt, (list, tuple)) else self._input_device(tgt))
         else:
             blobs, ns = prepare_reference(self._input_device(tgt))
-            if auto or shifts is not None or share is not None:      # a value per row (given, or found on the device): the shared blob in every row (one segment)
+            if auto or shifts is not None or share is not None or guard is not None:      # a value per row (given, or found on the device): the shared blob in every row (one segment)
                 form, blobs, ns = "table", [blobs] * B, [ns] * B
         # 4. one engine call
         pitch = shift if shifts is None else shifts
-        if share is not None:      # the alpha entry covers every case below: plain shifts, target registers, a tracker
-            res = eng._convert("alpha", wf, blobs, ns, pitch, noise_angle, lens, w, target_registers(regs, B, wf.device) if auto else None, track=track,
-                               alpha=alpha_rows(share, B, wf.device))
+        if share is not None or guard is not None:      # the alpha / protect entry covers every case below: plain shifts, target registers, a tracker
+            rows = {"alpha": alpha_rows(share, B, wf.device) if share is not None else None}
+            if guard is not None:
+                rows["protect"] = protect_rows(guard, B, wf.device)
+            res = eng._convert("alpha" if guard is None else "protect", wf, blobs, ns, pitch, noise_angle, lens, w,
+                               target_registers(regs, B, wf.device) if auto else None, track=track, **rows)
             return res if return_shift or not auto else res[0]
         if not auto:
             return eng._convert(form, wf, blobs, ns, pitch, noise_angle, lens, w)

@@ -17,7 +17,8 @@ import torch
 from ...engine import (SOLA_CROSS, SOLA_DELAY, SOLA_SEARCH, pitch_shifts, sola_geometry, stream_denoise_geometry, stream_gate_geometry,
                        stream_resample_geometry)
 from ...stream_state import DENOISE_STATE, DOOR_STATE, GATE_STATE, TRACK_STATE, addresses, allocate, reset
-from ..tinyvc.feature_retrieval import PitchTrack, alpha_rows, gpu_device, resolve_alpha, resolve_auto_pitch, target_form
+from ..tinyvc.feature_retrieval import (PitchTrack, alpha_rows, gpu_device, protect_rows, resolve_alpha, resolve_auto_pitch, resolve_protect,
+                                        target_form)
 from .generator import Generator
 
 
@@ -277,6 +278,9 @@ class BatchedStreamInfer:
     `alpha` (convert's: a float, one per stream, or a [S] / [1] fp32 device tensor): the share of each stream's own content features kept in
     the match, held as `self.alpha`, a [S] device tensor read when a block runs - `stream.alpha.fill_(...)` / `copy_(...)` between blocks
     moves it without a new graph capture; None (the default) is the plain match.
+    `protect` (convert's, in alpha's forms; the keyword behind alpha): how far that share rises on the unvoiced frames of each window's own f0, held as
+    `self.protect`, a [S] device tensor like `self.alpha` (`stream.protect.fill_(...)` / `copy_(...)` replay the same graph); with or without
+    alpha; None (the default) is the stream as it was.
     `door` (a StreamDoor of the same n_streams and block_size): audio_callback_pcm takes the clients' int16 blocks at the door's rates.
     `gate` (a StreamGate of the same n_streams and block_size): every emitted block goes through the noise gate, one launch behind SOLA (and
     in front of the door), driven by the input window and `last_shift` on the device; the SOLA buffer and the window stay ungated.
@@ -294,11 +298,12 @@ class BatchedStreamInfer:
     shorter than the three sizes say, and a look-ahead shorter than the pad is refused."""
 
     def __init__(self, generator: Generator, n_streams=1, target=None, pitch_shift=0., device=None,
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, denoise=None, gate=None, door=None,
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, denoise=None, gate=None, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         self.input_size, _ = check_window(block_size, extra_size, crossfade_size, sola_search_size, last_delay_size,
                                            auto_pitch is not None and auto_pitch is not False)
         share = resolve_alpha(alpha, n_streams) if alpha is not None else None      # refused here, before anything is allocated
+        guard = resolve_protect(protect, n_streams) if protect is not None else None
         self.n_streams, self.block_size = n_streams, block_size
         self.door, self.gate, self.denoise = (self._fits(name, stage) for name, stage in (("door", door), ("gate", gate), ("denoise", denoise)))
         self.auto_pitch = auto_pitch if auto_pitch is not False else None
@@ -315,6 +320,7 @@ class BatchedStreamInfer:
         self.device = torch.device(device) if device is not None else generator._module_device()
         # the streams' shares of their own content features: a [S] device tensor every block reads when it runs, or None (the plain match)
         self.alpha = alpha_rows(share, n_streams, self.device) if share is not None else None
+        self.protect = protect_rows(guard, n_streams, self.device) if guard is not None else None      # ... and their rise on unvoiced frames, likewise
         self.extra_size = extra_size
         self.sola_search_size = sola_search_size
         self.last_dilay_size = last_delay_size          # (sic) the reference's attribute name, stream.py:49
@@ -402,11 +408,11 @@ class BatchedStreamInfer:
         pshift = None
         if self.auto_pitch is None:
             y = self.generator.convert(self.input_wav, self.target, self.pitch_shift, device=self.device,
-                                       f0_estimation=self.f0_estimation, noise_angle=noise_angle, alpha=self.alpha)
+                                       f0_estimation=self.f0_estimation, noise_angle=noise_angle, alpha=self.alpha, protect=self.protect)
         else:
             y, pshift = self.generator.convert(self.input_wav, self.target, self.pitch_shift, device=self.device, f0_estimation=self.f0_estimation,
                                                noise_angle=noise_angle, auto_pitch=self.auto_pitch, return_shift=True, track=self.pitch_track,
-                                               alpha=self.alpha)
+                                               alpha=self.alpha, protect=self.protect)
         eng = self.generator.engine(self.device)
         out, shift = eng.sola(y, self.sola_buffer, self.fade_in_window, self.block_size, self.use_phase_vocoder, want_shift=True,
                               crossfade=self.crossfade_size, search=self.sola_search_size, delay=self.last_dilay_size)
@@ -428,7 +434,7 @@ class BatchedStreamInfer:
         one), the prepared index riding on `target`, plus the scalars captured by value.  Every stage present - the
         tracker, the door, the suppressor (denoise), the gate - adds (its name, WHERE the tensors of its table in stream_state live, its
         params()): the table lists every tensor whose pointer reaches the library, so none can be passed on and left out here.  With
-        auto_pitch also WHERE the target registers live, with alpha where the shares live.  Never a value: the kernels read those at replay,
+        auto_pitch also WHERE the target registers live, with alpha / protect where the shares live.  Never a value: the kernels read those at replay,
         so a reset(), registers.copy_(...), threshold_db.fill_(...) or a stream's history advancing keeps the graph.  The tail's geometry is
         baked into its two launches, so it is part of the key."""
         eng = self.generator.engine(self.device)          # re-packs the weights first if a parameter changed
@@ -445,6 +451,8 @@ class BatchedStreamInfer:
             tkey += (("target_f0", regs if isinstance(regs, float) else tuple(r.data_ptr() for r in regs)),)
         if self.alpha is not None:      # WHERE the shares live, not their values: alpha.fill_(...) / copy_(...) keeps the graph
             tkey += (("alpha", self.alpha.data_ptr()),)
+        if self.protect is not None:
+            tkey += (("protect", self.protect.data_ptr()),)
         return (eng.weights_key, ws.data_ptr() if ws is not None else 0, ws.numel() if ws is not None else 0,
                 tuple((id(t), t._version, t.data_ptr()) for t in tgts), wkey, shifts, bool(self.use_phase_vocoder),
                 (self.crossfade_size, self.sola_search_size, self.last_dilay_size)) + tkey
@@ -515,13 +523,13 @@ class StreamInfer(BatchedStreamInfer):
     """Single stream with the reference's constructor and 1-D buffers (stream.py:31-57)."""
 
     def __init__(self, generator: Generator, target=None, pitch_shift=0., device=torch.device("cpu"),
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, denoise=None, gate=None, door=None,
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, denoise=None, gate=None, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         dev = torch.device(device)
         if dev.type != "cuda":
             dev = generator._module_device()     # the reference defaults to CPU; there is no CPU path here
         super().__init__(generator, n_streams=1, target=target, pitch_shift=pitch_shift, device=dev, block_size=block_size, extra_size=extra_size,
-                         use_phase_vocoder=use_phase_vocoder, f0_estimation=f0_estimation, use_graph=use_graph, alpha=alpha, denoise=denoise, gate=gate,
+                         use_phase_vocoder=use_phase_vocoder, f0_estimation=f0_estimation, use_graph=use_graph, alpha=alpha, protect=protect, denoise=denoise, gate=gate,
                          door=door, crossfade_size=crossfade_size, sola_search_size=sola_search_size, last_delay_size=last_delay_size,
                          auto_pitch=auto_pitch, pitch_track=pitch_track)
 

@@ -214,58 +214,81 @@ def target_registers(resolved, B, device):
     return (t.expand(B) if t.numel() == 1 else t).contiguous()
 
 
-def resolve_alpha(alpha, B):
+def resolve_alpha(alpha, B, name="alpha"):
     """convert's alpha - the share of a row's own content features that survives the match (the reference's match_features(..., alpha);
     RVC's index rate is 1 - alpha) - checked on the host (no engine, no device work): a float, a sequence of B (or 1) floats, or a 1-D fp32
     tensor of B or 1 entries ON THE DEVICE (the kernels read it when they run).  Returns a list of B floats, or the tensor; raises
-    ValueError naming alpha otherwise.  Values are neither clamped nor normalised: below 0 and above 1 extrapolate."""
+    ValueError naming alpha otherwise.  Values are neither clamped nor normalised: below 0 and above 1 extrapolate.
+    `name`: the other per-row value of this form, "protect" (resolve_protect), under its own name in every message."""
     if isinstance(alpha, torch.Tensor):
         if alpha.dim() != 1 or alpha.numel() not in (1, B):
-            raise ValueError(f"alpha: a tensor of 1 or B = {B} shares, got shape {tuple(alpha.shape)}")
+            raise ValueError(f"{name}: a tensor of 1 or B = {B} shares, got shape {tuple(alpha.shape)}")
         if alpha.dtype != torch.float32:
-            raise ValueError(f"alpha: an fp32 tensor (it is read in place by the kernels, never converted), got {alpha.dtype}")
+            raise ValueError(f"{name}: an fp32 tensor (it is read in place by the kernels, never converted), got {alpha.dtype}")
         if alpha.device.type != "cuda":
-            raise ValueError(f"alpha: a tensor lives on the GPU, where the kernels read it when they run; got one on {alpha.device} (pass floats instead)")
+            raise ValueError(f"{name}: a tensor lives on the GPU, where the kernels read it when they run; got one on {alpha.device} (pass floats instead)")
         return alpha
     if isinstance(alpha, (list, tuple)):
         vals = list(alpha)
         if len(vals) not in (1, B):
-            raise ValueError(f"alpha: {len(vals)} shares for a batch of {B}")
+            raise ValueError(f"{name}: {len(vals)} shares for a batch of {B}")
     else:
         vals = [alpha]
     for x in vals:
         if isinstance(x, bool) or not isinstance(x, (int, float)):
-            raise ValueError(f"alpha: a float, a sequence of one float per row or an fp32 [B] / [1] device tensor, got {alpha!r}")
+            raise ValueError(f"{name}: a float, a sequence of one float per row or an fp32 [B] / [1] device tensor, got {alpha!r}")
     return [float(x) for x in vals] * (B if len(vals) == 1 else 1)
 
 
-def alpha_rows(resolved, B, device):
+def alpha_rows(resolved, B, device, name="alpha"):
     """resolve_alpha's result as the contiguous fp32 [B] device tensor the engine takes (a [B] tensor on `device` passes through as it is,
     so in-place changes reach a captured graph; a [1] tensor is expanded to a new [B] one)"""
     if isinstance(resolved, torch.Tensor):
         device = torch.device(device)
         if resolved.device.type != device.type or (device.index is not None and resolved.device.index != device.index):
-            raise ValueError(f"alpha: the tensor is on {resolved.device}, the conversion runs on {device}")
+            raise ValueError(f"{name}: the tensor is on {resolved.device}, the conversion runs on {device}")
         return (resolved.expand(B) if resolved.numel() != B else resolved).contiguous()
     return torch.tensor(resolved, dtype=torch.float32, device=device)
 
 
+def resolve_protect(protect, B):
+    """convert's protect - how far the source's share rises on UNVOICED frames: frame t keeps a_t = a + (1 - a) * (protect * w[t]) of the row's
+    own content features, w[t] in {0, .25, .5, .75, 1} the unvoiced weight of the frame and its two neighbours in the f0 the call decodes
+    (include/tinyvc_hip.h; 1 - RVC's protect value) - in alpha's forms, by alpha's code, refused under its own name"""
+    return resolve_alpha(protect, B, "protect")
+
+
+def protect_rows(resolved, B, device):
+    return alpha_rows(resolved, B, device, "protect")
+
+
 def add_alpha_argument(parser):
-    """`--alpha A` for the entry scripts' parsers: absent (None) is the call without alpha"""
+    """`--alpha A` and `--protect P` for the entry scripts' parsers: absent (None) is the call without them"""
     parser.add_argument("--alpha", type=float, default=None,
                         help="keep this share of the source's own content features in the match (the reference's match_features alpha; RVC's "
                              "index rate is 1 - alpha); default: absent, the plain match")
+    parser.add_argument("--protect", type=float, default=None,
+                        help="raise that share on unvoiced frames (consonants, breaths, silence) to alpha + (1 - alpha) * P, by the f0 the "
+                             "conversion decodes; voiced frames keep alpha.  1 - RVC's protect value; meant for 0 .. 1.  An untuned guess: nobody "
+                             "has listened.  default: absent, the same share on every frame")
 
 
 def alpha_keywords(args, script):
-    """what `--alpha` adds to the script's convert / stream call: nothing when it is absent (the call is today's), else {"alpha": A} and one
-    printed line; a non-finite value ends the script"""
-    if args.alpha is None:
-        return {}
-    if not math.isfinite(args.alpha):
-        sys.exit(f"{script}: --alpha must be a finite number")
-    print(f"Keeping {args.alpha:g} of the source's own content features (alpha; index rate {1 - args.alpha:g})")
-    return {"alpha": float(args.alpha)}
+    """what `--alpha` / `--protect` add to the script's convert / stream call: nothing when they are absent (the call is today's), else
+    {"alpha": A} / {"protect": P} and one printed line each; a non-finite value ends the script"""
+    kw = {}
+    if args.alpha is not None:
+        if not math.isfinite(args.alpha):
+            sys.exit(f"{script}: --alpha must be a finite number")
+        print(f"Keeping {args.alpha:g} of the source's own content features (alpha; index rate {1 - args.alpha:g})")
+        kw["alpha"] = float(args.alpha)
+    protect = getattr(args, "protect", None)
+    if protect is not None:
+        if not math.isfinite(protect):
+            sys.exit(f"{script}: --protect must be a finite number")
+        print(f"Protecting unvoiced frames: their share of the source's own features rises by {protect:g} of what the match would take (protect)")
+        kw["protect"] = float(protect)
+    return kw
 
 
 def gpu_device(device, sentence, cpu_ok=False):
