@@ -667,6 +667,60 @@ int tvc_stream_denoise_f32(tvc_ctx* ctx, void* stream, const float* x, float* ou
                            float beta, int warm, const float* reduction_db, float* hist, float* ola, float* smooth, float* noise, int32_t* frames,
                            float* noise_db);
 
+/* The loudness envelope match (extension; RVC's rms_mix_rate, as 1 - its value): the converted signal follows the loudness envelope of
+ * the signal it was converted from, by a share e in [0, 1].  x is the input at the model's rate on the output's time axis, y the converted
+ * output; both are cut into sub-frames of `sub` samples (a multiple of 4; 240 = 10 ms).
+ *   Powers     Ps[i], Po[i] = the mean power of sub-frame i of x and of y, accumulated in fp64 (an fp32 square is exact in fp64, so the
+ *              order of the reduction does not matter at fp32 precision).
+ *   Envelope   Es[i] = the mean of Ps over a window of sub-frames, summed in ascending index order in fp64 and divided by the number of
+ *              sub-frames actually present; Eo[i] likewise from Po.
+ *   Gain       q = max(Es, floor) / max(Eo, floor), floor = 10^(floor_db / 10);  r = exp2(0.5 * e * log2(q)), all in fp64;  r is clamped
+ *              to [10^(-cut_db / 20), 10^(boost_db / 20)] and rounded to fp32 once: the gain g[i] of sub-frame i.
+ *   Special    a window that holds a NaN or infinite power gives g[i] = 1 exactly.  e is read from device memory when the kernel runs:
+ *              values outside [0, 1] are clamped, NaN is 0, and e == 0 gives g[i] = 1.0f exactly - the samples keep their bits.
+ *   Ramp       the gate's: with g0 the gain at the previous sub-frame edge and g1 = g[i], sample j of sub-frame i is multiplied by
+ *              g0 + (g1 - g0) * ((j + 1) / (float)sub), every operation rounded on its own in fp32.  The very first sub-frame of an
+ *              utterance or a stream is flat at its own gain (g0 = g1).
+ * Defaults (guesses: nobody has listened): floor_db = -60, boost_db = 12, cut_db = 40, smooth = 2 sub-frames each side.
+ *
+ * tvc_loudness_match_f32 (offline): x, y, out [B][L], share [B] fp32 on the device.  The window is centred - sub-frames i - smooth ..
+ * i + smooth, truncated to the row's own sub-frames.  lengths (nullable): int64 [B] on the HOST, as in the ragged conversions; they travel
+ * as kernel arguments (no copy, no workspace: asynchronous, and baked into a capture) - row b owns its first lengths[b] samples (clamped
+ * to 0 .. L, whole sub-frames of them); the window never crosses that length and the samples behind it are copied unchanged.  gains (nullable): [B][L / sub + 1] fp32, the gain at every sub-frame edge - edge 0 and edge 1 hold g[0], edge
+ * i + 1 holds g[i], edges behind a row's length hold 1.  One launch (one per 384 rows of a larger batch), no workspace, 64-bit indices: the grid is rows x tiles of `tile`
+ * sub-frames (tvc_loudness_geometry reports the constant), and each workgroup recomputes the powers of its halo of 2 * smooth + 1
+ * sub-frames.  out may be y: the call is then one workgroup per row, which walks the row's tiles in order (another workgroup's halo would
+ * be read while this one scales it), with the same bits.  Any other overlap of out with x or y is refused; x, y and out are 16-byte aligned.
+ *
+ * tvc_stream_loudness_f32 (streams): one launch behind the tail, one workgroup per stream, with the gate's addressing - x [S][n] the input
+ * windows, y [S][block] the emitted blocks, x[base + shift[s] + j] is the input sample y[j] was converted from (shift NULL = 0; an index
+ * outside [0, n) reads 0).  The window trails: the last W = 2 * smooth + 1 sub-frames up to and including the current one, fewer at the
+ * start of a stream.  State per stream, on the device, advanced in place: src_ring, out_ring [S][W] fp64 (the last powers, slot = sub-frame
+ * index % W, summed oldest to newest), frames [S] int64 (sub-frames seen), gain [S] fp32 (the last edge gain); a stream starts at zeros,
+ * 0 and 1.0.  A stream is therefore the offline gain sequence `smooth` sub-frames late - in the interior the two agree bit for bit - and
+ * its result does not depend, bit for bit, on how it is cut into blocks, on S or on the other streams.  The state advances when e == 0
+ * too.  gain_db [S] (nullable): the last edge gain in dB.  gains (nullable): [S][block / sub + 1], the block's edge gains (edge 0: the
+ * carried gain).  out may be y (any other overlap of out with x or y is refused); y and out are 16-byte aligned.  No workspace.
+ *
+ * tvc_loudness_geometry (host only: no context, no device) holds the limits: 4 <= sub <= 65536, sub % 4 == 0, 1 <= length <= 2^40 a
+ * multiple of sub, 0 <= smooth <= 32; tvc_stream_loudness_geometry the same for a stream's block, and at most 4096 sub-frames per block
+ * (the gate's cap, so that both stages take the same blocks; no resource of the kernel depends on it).
+ * Anything else returns TVC_ERR_ARG; otherwise nsub = length / sub, window = 2 * smooth + 1 and tile (out pointers are nullable).  The
+ * _message entries give the reason of a refusal ("" for a legal geometry), valid until the thread's next call.  The two device entries
+ * refuse the same geometries with that reason in tvc_last_error, and: a NULL pointer (lengths, shift, gain_db and gains are exempt), B or
+ * S <= 0, a floor_db that is not finite (or whose 10^(floor_db / 10) is not a positive double), a boost_db or cut_db that is negative or
+ * not finite (or whose gain is not a positive finite fp32 number), n outside 1 .. 2^40, |base| > 2^40 - all with TVC_ERR_ARG before
+ * anything is launched. */
+int tvc_loudness_geometry(int64_t length, int sub, int smooth, int64_t* nsub, int* window, int* tile);
+const char* tvc_loudness_geometry_message(int64_t length, int sub, int smooth);
+int tvc_stream_loudness_geometry(int block, int sub, int smooth, int* nsub, int* window);
+const char* tvc_stream_loudness_geometry_message(int block, int sub, int smooth);
+int tvc_loudness_match_f32(tvc_ctx* ctx, void* stream, const float* x, const float* y, float* out, int B, int64_t L, const int64_t* lengths,
+                           const float* share, int sub, int smooth, float floor_db, float boost_db, float cut_db, float* gains);
+int tvc_stream_loudness_f32(tvc_ctx* ctx, void* stream, const float* x, int64_t n, int64_t base, const int32_t* shift, const float* y, float* out, int S,
+                            int block, int sub, int smooth, float floor_db, float boost_db, float cut_db, const float* share, double* src_ring,
+                            double* out_ring, int64_t* frames, float* gain, float* gain_db, float* gains);
+
 /* measurement ----------------------------------------------------------------------------- */
 /* on = 1: every stage (and every FilterNet block) is bracketed by a hipEvent pair on the launch stream (19 pairs per
  * convert, ~0.1 ms of a 8.4 ms step); on = 2: only the `filter_net` region (the roofline's kernel group); on = 0: off.

@@ -36,10 +36,11 @@ import zlib
 import torch
 
 from tinyvc_amd import audio_io, parallel, spec
+from tinyvc_amd.engine import loudness_geometry
 from tinyvc_amd.module.infer import Generator
 from tinyvc_amd.module.tinyvc import Blend, Decoder, Encoder
-from tinyvc_amd.module.tinyvc.feature_retrieval import (add_alpha_argument, add_auto_pitch_argument, add_blend_argument, alpha_keywords, attach_register,
-                                                        pitch_register)
+from tinyvc_amd.module.tinyvc.feature_retrieval import (add_alpha_argument, add_auto_pitch_argument, add_blend_argument, add_loudness_argument, alpha_keywords,
+                                                        attach_register, loudness_keywords, pitch_register)
 
 SAMPLE_RATE = 24000
 
@@ -57,6 +58,7 @@ def build_parser():
     p.add_argument("-d", "--device", default="cuda")
     p.add_argument("-p", "--pitch-shift", default=0.0, type=float)
     add_auto_pitch_argument(p)      # --auto-pitch: every file's median f0 onto the target's register; -p stays, as the offset
+    add_loudness_argument(p)        # --loudness E: follow that share of every file's own loudness envelope
     add_alpha_argument(p)           # --alpha A: keep that share of every file's own content features in the match; --protect P: more on unvoiced frames
     p.add_argument("-c", "--chunk-size", default=1920, type=int)
     p.add_argument("-b", "--buffer-size", default=4, type=int)
@@ -132,9 +134,12 @@ def convert_chunked(gen, batch, tgt, pitch_shift, chunk_size, buffer_blocks, use
     `noise_angles(i)` -> [B, 961, T] injects the decoder's noise phases of block i (parity runs against the oracle's
     `stream_callback`; default: drawn on the device per block, as the reference's `torch.rand` is).
     `return_blocks`: also return the untrimmed block outputs [B, nblk, chunk_size] and the SOLA lags [nblk, B].
-    `stream_kw`: further BatchedStreamInfer keywords (alpha, protect)."""
-    from tinyvc_amd.module.infer import BatchedStreamInfer
+    `stream_kw`: further BatchedStreamInfer keywords (alpha, protect, loudness: a share of the source's loudness envelope - a StreamLoudness
+    stage for these streams is built from it here)."""
+    from tinyvc_amd.module.infer import BatchedStreamInfer, StreamLoudness
     B, L = batch.shape
+    if stream_kw.get("loudness") is not None and not isinstance(stream_kw["loudness"], StreamLoudness):
+        stream_kw["loudness"] = StreamLoudness(B, chunk_size, share=stream_kw["loudness"], device=batch.device)
     st = BatchedStreamInfer(gen, n_streams=B, target=tgt, pitch_shift=pitch_shift, device=batch.device, block_size=chunk_size,
                             extra_size=buffer_blocks * chunk_size, use_phase_vocoder=use_phase_vocoder, use_graph=True, **stream_kw)
     st.init_buffer()
@@ -180,6 +185,12 @@ def main(argv=None, world=None, rank=None, local_rank=None):
             sys.exit(f"infer.py: --auto-pitch: no pitch register beside {args.index} (extract_index.py writes <index>.f0.pt)")
         auto = True
     alpha_kw = alpha_keywords(args, "infer.py")      # {} without --alpha / --protect: every call below is then the call it has always been
+    alpha_kw.update(loudness_keywords(args, "infer.py"))      # likewise --loudness
+    if "loudness" in alpha_kw and args.chunked and not args.no_chunking:      # a stream's stage works on whole 10 ms sub-frames of a block
+        try:
+            loudness_geometry(args.chunk_size, stream_block=True)
+        except ValueError as e:
+            sys.exit(f"infer.py: --loudness with --chunked: {e}")
     os.makedirs(args.outputs, exist_ok=True)
 
     paths = []

@@ -41,6 +41,12 @@ every bin is turned down by up to DB where the estimate explains its power (`--d
 `--denoise-smooth`: the time constant of the power the gain follows).  The converter, the pitch tracker and the gate then see the cleaned
 signal.  It costs 640 - `--denoise-hop` samples of latency (20 ms at hop 160, 13.3 ms at 320).  The defaults are guesses: nobody has listened yet.
 
+`--loudness E` (extension; 1 - RVC's rms_mix_rate) makes every stream follow that share of its speaker's loudness envelope, on the device
+behind SOLA and in front of the gate: each 10 ms sub-frame of a played block is scaled by (Es / Eo)^(E / 2), Es and Eo the mean powers of
+the input the block was converted from and of the block itself over the last `--loudness-window`; powers below `--loudness-floor` count as
+it, and a sub-frame is never turned up by more than `--loudness-boost` or down by more than `--loudness-cut`.  It adds no latency.  The
+defaults are guesses: nobody has listened yet.
+
 `--streams S` feeds S copies of the input as S concurrent streams through one BatchedStreamInfer
 (one batched convert + one SOLA launch per block) and reports the p50 / p95 block latency against the
 real-time budget (chunk / 24 kHz = 80 ms for the default 1920-sample chunk).
@@ -55,8 +61,8 @@ import torch
 
 from tinyvc_amd import audio_io
 from infer import load_generator, load_target
-from tinyvc_amd.engine import sola_geometry, stream_denoise_geometry, stream_gate_geometry, stream_resample_geometry
-from tinyvc_amd.module.infer import BatchedStreamInfer, StreamDenoise, StreamDoor, StreamGate
+from tinyvc_amd.engine import loudness_geometry, loudness_levels, sola_geometry, stream_denoise_geometry, stream_gate_geometry, stream_resample_geometry
+from tinyvc_amd.module.infer import BatchedStreamInfer, StreamDenoise, StreamDoor, StreamGate, StreamLoudness
 from tinyvc_amd.module.infer.stream import check_gate_lookahead, check_window, denoise_constants
 from tinyvc_amd.module.tinyvc.feature_retrieval import (PitchTrack, add_alpha_argument, add_blend_argument, alpha_keywords, pitch_register,
                                                         semitones_between)
@@ -64,6 +70,7 @@ from tinyvc_amd.module.tinyvc.feature_retrieval import (PitchTrack, add_alpha_ar
 FRAMES_PER_SECOND = 50      # 24 kHz / 480 samples
 GATE_SUB_FRAME = 240        # the gate's sub-frame: 10 ms at 24 kHz
 DENOISE_DEFAULTS = dict(hop=160, strength=2.0, adapt_s=1.0, smooth_ms=40.0, warmup_ms=200.0)      # of --denoise-hop / -strength / -adapt / -smooth / -warmup
+LOUDNESS_DEFAULTS = dict(window=50.0, floor=-60.0, boost=12.0, cut=40.0)      # of --loudness-window (ms) / -floor / -boost / -cut (dB)
 GATE_MS = dict(hold=200.0, attack=10.0, release=100.0, lookahead=20.0)      # the defaults of --gate-hold / -attack / -release / -lookahead
 
 
@@ -124,6 +131,16 @@ def build_parser():
                    help=f"time constant of the smoothed power the gain follows, in milliseconds (default {DENOISE_DEFAULTS['smooth_ms']:g})")
     p.add_argument("--denoise-warmup", default=None, type=float, metavar="MS",
                    help=f"the first this many milliseconds of sound in a stream are taken for noise (default {DENOISE_DEFAULTS['warmup_ms']:g})")
+    p.add_argument("--loudness", default=None, type=float, metavar="E",
+                   help="make every stream follow this share (0 .. 1) of its speaker's loudness envelope, on the device behind SOLA and in front of the "
+                        "gate (1 - RVC's rms_mix_rate; stage.share, live on the device).  Absent: the level the decoder gives.  The defaults of the "
+                        "four flags below are guesses: nobody has listened yet")
+    p.add_argument("--loudness-window", default=None, type=float, metavar="MS",
+                   help=f"length of the trailing window both envelopes are taken over: an odd number of 10 ms sub-frames, at most 65 (default {LOUDNESS_DEFAULTS['window']:g})")
+    p.add_argument("--loudness-floor", default=None, type=float, metavar="DB",
+                   help=f"powers below this (dB re full scale) count as it: silence is not amplified (default {LOUDNESS_DEFAULTS['floor']:g})")
+    p.add_argument("--loudness-boost", default=None, type=float, metavar="DB", help=f"the most a sub-frame is turned up by, >= 0 (default {LOUDNESS_DEFAULTS['boost']:g})")
+    p.add_argument("--loudness-cut", default=None, type=float, metavar="DB", help=f"the most a sub-frame is turned down by, >= 0 (default {LOUDNESS_DEFAULTS['cut']:g})")
     # file-driven operation (no audio devices on a GPU node)
     p.add_argument("--input-wav", default=None, help="read the microphone signal from this WAV instead of a device")
     p.add_argument("--output-wav", default=None, help="write the converted stream here")
@@ -263,6 +280,29 @@ def check_denoise(args, block=None):
     return dict(reduction_db=args.denoise, **kw)
 
 
+def check_loudness(args, block=None):
+    """--loudness and its four companions against each other and the block, before anything is loaded: sys.exit with a message, or the
+    StreamLoudness keywords (None without --loudness).  `block`: the model's block length when it is not -c (--resample)"""
+    extra = [f"--loudness-{k}" for k in LOUDNESS_DEFAULTS if getattr(args, f"loudness_{k}") is not None]
+    if args.loudness is None:
+        if extra:
+            sys.exit(f"infer_streaming.py: {' '.join(extra)} without --loudness E: there is no stage to set")
+        return None
+    if not 0.0 <= args.loudness <= 1.0:      # (NaN fails both)
+        sys.exit("infer_streaming.py: --loudness: a share in 0 .. 1")
+    v = {k: (d if getattr(args, f"loudness_{k}") is None else getattr(args, f"loudness_{k}")) for k, d in LOUDNESS_DEFAULTS.items()}
+    window = v["window"] * 24.0 / GATE_SUB_FRAME
+    if not math.isfinite(window) or window != int(window) or int(window) % 2 != 1:
+        sys.exit(f"infer_streaming.py: --loudness-window {v['window']:g}: an odd number of {GATE_SUB_FRAME / 24.0:g} ms sub-frames")
+    chunk = args.chunk if block is None else block
+    try:
+        loudness_geometry(chunk, GATE_SUB_FRAME, (int(window) - 1) // 2, stream_block=True)
+        loudness_levels(v["floor"], v["boost"], v["cut"], "--loudness")
+    except ValueError as e:
+        sys.exit(f"infer_streaming.py: --loudness: {e}")
+    return dict(share=args.loudness, sub_frame=GATE_SUB_FRAME, smooth=(int(window) - 1) // 2, floor_db=v["floor"], boost_db=v["boost"], cut_db=v["cut"])
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     block = check_resample(args)
@@ -270,6 +310,7 @@ def main(argv=None):
     check_geometry(args, block)
     gate_kw = check_gate(args, block)
     denoise_kw = check_denoise(args, block)
+    loudness_kw = check_loudness(args, block)
     device = torch.device(args.device)
     if device.type != "cuda":
         sys.exit("infer_streaming.py: this build runs on an AMD GPU only; pass -d cuda")
@@ -317,6 +358,10 @@ def main(argv=None):
         print(f"Noise suppressor: up to {denoise_kw['reduction_db']:g} dB per bin (strength {denoise.strength:g}, smoothing {denoise.smooth_ms:g} ms, adaptation "
               f"{denoise.adapt_s:g} s, warm-up {denoise.warmup_ms:g} ms) in 640-sample frames at a hop of {denoise.hop}: "
               f"{denoise.delay_size / 24000 * 1e3:.1f} ms of delay")
+    if loudness_kw is not None:      # (absent: the stream is built as it has always been)
+        alpha_kw["loudness"] = stage = StreamLoudness(S, door.block_size, device=device, **loudness_kw)
+        print(f"Following {loudness_kw['share']:g} of the speaker's loudness envelope: {stage.window * GATE_SUB_FRAME / 24:g} ms window, floor {stage.floor_db:g} dB, "
+              f"at most +{stage.boost_db:g} / -{stage.cut_db:g} dB")
     stream = BatchedStreamInfer(gen, n_streams=S, pitch_shift=pitch_shift, block_size=door.block_size, device=device, extra_size=args.extra,
                                 f0_estimation=args.f0_estimation, door=door, auto_pitch=True if track is not None else None, pitch_track=track,
                                 crossfade_size=args.crossfade, sola_search_size=args.sola_search, last_delay_size=args.lookahead, gate=gate, denoise=denoise, **alpha_kw)

@@ -1201,6 +1201,76 @@ int tvc_stream_gate_f32(tvc_ctx* ctx, void* stream, const float* x, int64_t n, i
     return run_stream_gate(ctx, (hipStream_t)stream, x, n, base, shift, y, out, S, g);
 }
 
+int tvc_loudness_geometry(int64_t length, int sub, int smooth, int64_t* nsub, int* window, int* tile) {
+    return loudness_geometry(length, sub, smooth, false, nsub, window, tile, nullptr, 0);
+}
+
+const char* tvc_loudness_geometry_message(int64_t length, int sub, int smooth) {
+    static thread_local char why[96];
+    loudness_geometry(length, sub, smooth, false, nullptr, nullptr, nullptr, why, sizeof(why));
+    return why;
+}
+
+int tvc_stream_loudness_geometry(int block, int sub, int smooth, int* nsub, int* window) {
+    int64_t n = 0;
+    const int rc = loudness_geometry(block, sub, smooth, true, &n, window, nullptr, nullptr, 0);
+    if (rc == 0 && nsub) *nsub = (int)n;
+    return rc;
+}
+
+const char* tvc_stream_loudness_geometry_message(int block, int sub, int smooth) {
+    static thread_local char why[96];
+    loudness_geometry(block, sub, smooth, true, nullptr, nullptr, nullptr, why, sizeof(why));
+    return why;
+}
+
+int tvc_loudness_match_f32(tvc_ctx* ctx, void* stream, const float* x, const float* y, float* out, int B, int64_t L, const int64_t* lengths, const float* share,
+                           int sub, int smooth, float floor_db, float boost_db, float cut_db, float* gains) {
+    if (!ctx) return TVC_ERR_ARG;
+    char why[96];
+    if (loudness_geometry(L, sub, smooth, false, nullptr, nullptr, nullptr, why, sizeof(why)) != 0) return fail(ctx, TVC_ERR_ARG, "tvc_loudness_match_f32: %s", why);
+    if (!x || !y || !out || !share || B <= 0) return fail(ctx, TVC_ERR_ARG, "tvc_loudness_match_f32: bad argument (a NULL pointer or B <= 0)");
+    LoudnessConst c;
+    if (loudness_constants(floor_db, boost_db, cut_db, &c, why, sizeof(why)) != 0) return fail(ctx, TVC_ERR_ARG, "tvc_loudness_match_f32: %s", why);
+    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)out) & 15)
+        return fail(ctx, TVC_ERR_ARG, "tvc_loudness_match_f32: x, y and out must be 16-byte aligned (the rows are read and written 16 bytes at a time)");
+    const int64_t tiles = (L / sub + kLoudnessTile - 1) / kLoudnessTile;
+    if (tiles * std::min(B, kLoudnessLenRows) > INT32_MAX) return fail(ctx, TVC_ERR_ARG, "tvc_loudness_match_f32: %d rows of %ld tiles are more than 2^31 - 1 workgroups", std::min(B, kLoudnessLenRows), (long)tiles);
+    // out is y, or lies apart from it: a workgroup reads its neighbours' sub-frames of y, which a partly overlapping out would be changing.  x likewise
+    const uintptr_t bytes = (uintptr_t)B * (uintptr_t)L * sizeof(float), o = (uintptr_t)out;
+    auto overlaps = [&](const float* p) { return o < (uintptr_t)p + bytes && (uintptr_t)p < o + bytes; };
+    if ((out != y && overlaps(y)) || overlaps(x))
+        return fail(ctx, TVC_ERR_ARG, "tvc_loudness_match_f32: out overlaps x, or y without being y");
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    return run_loudness_match(ctx, (hipStream_t)stream, x, y, out, B, L, lengths, share, sub, smooth, c, gains);
+}
+
+int tvc_stream_loudness_f32(tvc_ctx* ctx, void* stream, const float* x, int64_t n, int64_t base, const int32_t* shift, const float* y, float* out, int S,
+                            int block, int sub, int smooth, float floor_db, float boost_db, float cut_db, const float* share, double* src_ring,
+                            double* out_ring, int64_t* frames, float* gain, float* gain_db, float* gains) {
+    if (!ctx) return TVC_ERR_ARG;
+    char why[96];
+    if (loudness_geometry(block, sub, smooth, true, nullptr, nullptr, nullptr, why, sizeof(why)) != 0) return fail(ctx, TVC_ERR_ARG, "tvc_stream_loudness_f32: %s", why);
+    if (!x || !y || !out || !share || !src_ring || !out_ring || !frames || !gain || S <= 0)
+        return fail(ctx, TVC_ERR_ARG, "tvc_stream_loudness_f32: bad argument (a NULL pointer or S <= 0)");
+    constexpr int64_t kSpan = (int64_t)1 << 40;      // a + i stays far inside 64 bits for any int32 shift
+    if (n < 1 || n > kSpan || base < -kSpan || base > kSpan)
+        return fail(ctx, TVC_ERR_ARG, "tvc_stream_loudness_f32: n = %ld is outside 1 .. 2^40 or |base| = |%ld| is above 2^40", (long)n, (long)base);
+    LoudnessConst c;
+    if (loudness_constants(floor_db, boost_db, cut_db, &c, why, sizeof(why)) != 0) return fail(ctx, TVC_ERR_ARG, "tvc_stream_loudness_f32: %s", why);
+    if (((uintptr_t)y | (uintptr_t)out) & 15)
+        return fail(ctx, TVC_ERR_ARG, "tvc_stream_loudness_f32: y and out must be 16-byte aligned (the blocks are read and written 16 bytes at a time)");
+    // out is y, or lies apart from it; and apart from the windows, which the next block's conversion reads
+    const uintptr_t obytes = (uintptr_t)S * (uintptr_t)block * sizeof(float), xbytes = (uintptr_t)S * (uintptr_t)n * sizeof(float), o = (uintptr_t)out;
+    if ((out != y && o < (uintptr_t)y + obytes && (uintptr_t)y < o + obytes) || (o < (uintptr_t)x + xbytes && (uintptr_t)x < o + obytes))
+        return fail(ctx, TVC_ERR_ARG, "tvc_stream_loudness_f32: out overlaps x, or y without being y");
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    StreamLoudness g;
+    g.block = block; g.sub = sub; g.smooth = smooth;
+    g.share = share; g.src_ring = src_ring; g.out_ring = out_ring; g.frames = frames; g.gain = gain; g.gain_db = gain_db;
+    return run_stream_loudness(ctx, (hipStream_t)stream, x, n, base, shift, y, out, S, g, c, gains);
+}
+
 int tvc_stream_denoise_geometry(int block, int hop, int* frames, int* delay) { return stream_denoise_geometry(block, hop, frames, delay, nullptr, 0); }
 
 const char* tvc_stream_denoise_geometry_message(int block, int hop) {

@@ -508,6 +508,40 @@ struct StreamGate {
 int stream_gate_geometry(int block, int sub, int look, int hold, int attack, int release, int* nsub, int* look_samples, char* why, size_t why_bytes);
 // (the caller has checked the geometry; x [S][n], y and out [S][block], out may be y; shift [S] optional)
 int run_stream_gate(tvc_ctx*, hipStream_t, const float* x, int64_t n, int64_t base, const int32_t* shift, const float* y, float* out, int S, const StreamGate& g);
+// the loudness envelope match (loudness.hip).  kLoudnessTile: the sub-frames one workgroup of the offline form owns (tvc_loudness_geometry
+// reports it); kLoudnessChunk: the sub-frames of a stream block whose powers a workgroup keeps in LDS at a time
+constexpr int kLoudnessTile = 64, kLoudnessChunk = 512, kLoudnessMaxSmooth = 32, kLoudnessMaxSubFrame = 1 << 16;
+// the cap on a stream block's sub-frames is the gate's, kept so that the two stages take the same blocks: the kernel walks a block in chunks
+// of kLoudnessChunk sub-frames, so nothing of it is sized by this number
+constexpr int kLoudnessMaxBlockSub = 4096;
+constexpr int64_t kLoudnessMaxLength = (int64_t)1 << 40;
+// a ragged batch's row lengths as kernel arguments: the rows of one launch of the offline form (3 KiB of the 4 KiB a launch may pass)
+constexpr int kLoudnessLenRows = 384;
+struct LoudnessLens {
+    int64_t v[kLoudnessLenRows];
+};
+struct LoudnessConst {
+    double floor, lo, hi;      // 10^(floor_db / 10), 10^(-cut_db / 20), 10^(boost_db / 20)
+};
+struct StreamLoudness {
+    int block, sub, smooth;         // samples, samples, sub-frames each side (the window trails: 2 * smooth + 1 sub-frames)
+    const float* share;             // [S] device, read when the kernel runs
+    double* src_ring;               // [S][2 * smooth + 1] device state, read and advanced in place: the last powers of the input and of the output,
+    double* out_ring;               //   slot = sub-frame index % window
+    int64_t* frames;                // [S] sub-frames seen
+    float* gain;                    // [S] the last edge gain
+    float* gain_db;                 // [S] device, optional: the same in dB
+};
+// the legal geometries, in one place (loudness.hip): 0, or TVC_ERR_ARG with the reason in `why`; every out pointer is nullable.  stream_block:
+// `length` is a stream's block
+int loudness_geometry(int64_t length, int sub, int smooth, bool stream_block, int64_t* nsub, int* window, int* tile, char* why, size_t why_bytes);
+// the three dB settings as the kernels take them: 0, or TVC_ERR_ARG with the reason in `why`
+int loudness_constants(float floor_db, float boost_db, float cut_db, LoudnessConst* c, char* why, size_t why_bytes);
+// (the caller has checked the geometry, the alignment and that out is y or does not overlap it; lengths [B] HOST, optional; gains optional)
+int run_loudness_match(tvc_ctx*, hipStream_t, const float* x, const float* y, float* out, int B, int64_t L, const int64_t* lengths, const float* share, int sub,
+                       int smooth, const LoudnessConst& c, float* gains);
+int run_stream_loudness(tvc_ctx*, hipStream_t, const float* x, int64_t n, int64_t base, const int32_t* shift, const float* y, float* out, int S,
+                        const StreamLoudness& g, const LoudnessConst& c, float* gains);
 // the spectral suppressor in front of the window (denoise.hip).  Frames of kDenoiseFrame samples at a hop of 160 or 320
 constexpr int kDenoiseFrame = 640, kDenoiseBins = kDenoiseFrame / 2 + 1, kDenoiseMaxFrames = 4096;
 struct StreamDenoise {

@@ -13,7 +13,7 @@ import weakref
 import torch
 
 from . import _lib, spec
-from .stream_state import DENOISE_STATE, GATE_STATE, TRACK_STATE, Field, checked
+from .stream_state import DENOISE_STATE, GATE_STATE, LOUDNESS_STATE, TRACK_STATE, Field, checked
 
 _F32 = torch.float32
 
@@ -161,6 +161,46 @@ def stream_denoise_geometry(block, hop=160, lib=None):
     if lib.tvc_stream_denoise_geometry(block, hop, ctypes.byref(frames), ctypes.byref(delay)) != 0:
         raise ValueError(f"stream denoise geometry: {lib.tvc_stream_denoise_geometry_message(block, hop).decode()}")
     return frames.value, delay.value
+
+
+def loudness_geometry(length, sub=240, smooth=2, stream_block=False, lib=None):
+    """tvc_loudness_geometry (no context, no device) -> (nsub, window, tile) of a loudness match over `length` samples in sub-frames of `sub`
+    samples with `smooth` sub-frames each side: sub-frames, window = 2 * smooth + 1, and the sub-frames a workgroup of the offline form owns.
+    stream_block: `length` is a stream's block (tvc_stream_loudness_geometry: at most 4096 sub-frames; tile is None).  ValueError, with the
+    library's reason, for what the kernels do not take."""
+    if isinstance(length, bool) or not isinstance(length, numbers.Integral) or abs(length) >= (2 ** 31 if stream_block else 2 ** 63):
+        raise ValueError(f"loudness geometry: length must be an integer, got {length!r}")
+    vals = (int(length), integer(sub, "loudness geometry", "sub"), integer(smooth, "loudness geometry", "smooth"))
+    lib = lib if lib is not None else _lib.load_library()
+    nsub, window, tile = (ctypes.c_int if stream_block else ctypes.c_int64)(), ctypes.c_int(), ctypes.c_int()
+    if stream_block:
+        if lib.tvc_stream_loudness_geometry(*vals, ctypes.byref(nsub), ctypes.byref(window)) != 0:
+            raise ValueError(f"loudness geometry: {lib.tvc_stream_loudness_geometry_message(*vals).decode()}")
+        return nsub.value, window.value, None
+    if lib.tvc_loudness_geometry(*vals, ctypes.byref(nsub), ctypes.byref(window), ctypes.byref(tile)) != 0:
+        raise ValueError(f"loudness geometry: {lib.tvc_loudness_geometry_message(*vals).decode()}")
+    return nsub.value, window.value, tile.value
+
+
+def loudness_levels(floor_db=-60.0, boost_db=12.0, cut_db=40.0, what="loudness"):
+    """the three dB settings of a loudness match as the fp32 values the library takes; ValueError for what it refuses: a floor that is not
+    finite, a boost or cut that is negative or not finite (they are the most the gain may raise or lower a sub-frame by)"""
+    vals = []
+    for x, name, least in ((floor_db, "floor_db", None), (boost_db, "boost_db", 0.0), (cut_db, "cut_db", 0.0)):
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or (least is not None and x < least):
+            raise ValueError(f"{what}: {name} must be a finite number of dB" + ("" if least is None else " >= 0") + f", got {x!r}")
+        v = ctypes.c_float(x).value
+        if not math.isfinite(v) or abs(v) > 600.0:      # 10^(+-30) as an fp32 gain, 10^(+-60) as a power: far inside what the library takes
+            raise ValueError(f"{what}: {name} = {x!r} dB is outside -600 .. 600")
+        vals.append(v)
+    return tuple(vals)
+
+
+def loudness_in_place(rows, device):
+    """whether a loudness match of `rows` rows should run in place: an in-place call is one workgroup per row (a tile's halo lies in tiles
+    another workgroup would be scaling), so it pays once the rows alone fill the device's compute units; below that a call into a tensor of
+    its own, rows x tiles workgroups, is faster (64 x 4 s: 35 us against 154 us; one five-minute row: profiles/loudness_probe.json)"""
+    return rows >= torch.cuda.get_device_properties(device).multi_processor_count
 
 
 def pitch_class_table():
@@ -1015,6 +1055,78 @@ class Engine:
         self._ok(self.lib.tvc_stream_gate_f32(self.ctx, self._stream(), _ptr(x), n, int(base), _ptr(shift), _ptr(y), _ptr(out), S, gate.block_size, sub, look,
                                               hold, attack, release, hysteresis_db, range_db, *map(_ptr, state)), "tvc_stream_gate_f32")
         return out
+
+    def loudness_match(self, x, y, share, lengths=None, settings=None, out=None, want_gains=False):
+        """The loudness envelope match (tvc_loudness_match_f32; its definition is in tinyvc_hip.h): x [B, L] the input on the output's time
+        axis, y [B, L] the converted waves, share [B] fp32 on the device (read when the kernel runs), `lengths` a ragged batch's row lengths
+        (a sequence on the host: they travel as kernel arguments, so the call stays asynchronous and capturable), `settings` anything with
+        sub_frame, smooth, floor_db, boost_db and cut_db (a feature_retrieval.LoudnessMatch; None: the defaults).  Returns the matched waves
+        - a new tensor, or `out`, which may be y (one workgroup per row then: see loudness_in_place) - and with want_gains the gain at every
+        sub-frame edge, [B, L / sub_frame + 1]."""
+        for t, name in ((x, "x"), (y, "y")):
+            _check_dev(t, name, self.device)
+            if t.dim() != 2 or t.dtype != _F32 or not t.is_contiguous():
+                raise ValueError(f"loudness_match: {name} must be contiguous fp32 [B, L], got {t.dtype} {tuple(t.shape)}")
+        B, L = y.shape
+        if x.shape != y.shape:
+            raise ValueError(f"loudness_match: x {tuple(x.shape)} and y {tuple(y.shape)} must have one shape")
+        _check_dev(share, "share", self.device)
+        if share.dtype != _F32 or tuple(share.shape) != (B,) or not share.is_contiguous():
+            raise ValueError(f"loudness_match: share must be contiguous fp32 [{B}], got {share.dtype} {tuple(share.shape)}")
+        sub, smooth, floor_db, boost_db, cut_db = ((240, 2, -60.0, 12.0, 40.0) if settings is None else
+                                                   (settings.sub_frame, settings.smooth, settings.floor_db, settings.boost_db, settings.cut_db))
+        nsub = loudness_geometry(L, sub, smooth, lib=self.lib)[0]
+        floor_db, boost_db, cut_db = loudness_levels(floor_db, boost_db, cut_db, "loudness_match")
+        lens = None
+        if lengths is not None:
+            vals = lengths.tolist() if isinstance(lengths, torch.Tensor) and lengths.device.type == "cpu" else lengths
+            if isinstance(vals, torch.Tensor) or len(vals) != B or any(isinstance(n, bool) or not isinstance(n, numbers.Integral) for n in vals):
+                raise ValueError(f"loudness_match: lengths: a host sequence of one integer per row ({B}), got {lengths!r}")
+            if min(vals) < 0 or max(vals) > L or any(n % sub for n in vals):
+                raise ValueError(f"loudness_match: lengths: one entry per row, each a whole number of {sub}-sample sub-frames in 0 .. {L}")
+            lens = (ctypes.c_int64 * B)(*[int(n) for n in vals])
+        if out is None:
+            out = torch.empty_like(y)
+        else:
+            _check_dev(out, "out", self.device)
+            if out.dtype != _F32 or out.shape != y.shape or not out.is_contiguous():
+                raise ValueError(f"loudness_match: out must be contiguous fp32 {tuple(y.shape)}, got {out.dtype} {tuple(out.shape)}")
+        gains = torch.empty(B, nsub + 1, dtype=_F32, device=self.device) if want_gains else None
+        self._ok(self.lib.tvc_loudness_match_f32(self.ctx, self._stream(), _ptr(x), _ptr(y), _ptr(out), B, L, lens, _ptr(share), sub, smooth, floor_db,
+                                                 boost_db, cut_db, _ptr(gains)), "tvc_loudness_match_f32")
+        return (out, gains) if want_gains else out
+
+    def stream_loudness(self, x, y, shift, stage, base, out=None, want_gains=False):
+        """The loudness envelope match behind the tail (tvc_stream_loudness_f32), with stream_gate's addressing: x [S, n] the streams' input
+        windows, y [S, block] the emitted blocks, shift [S] int32 the tail's lags (None = 0), base + shift[s] the index in x[s] of the input
+        sample y[s, 0] was converted from; `stage` a module.infer.StreamLoudness (share and state on the device, advanced in place).  Returns
+        the matched blocks - a new tensor, or `out` (which may be y) - and with want_gains the block's edge gains [S, block / sub_frame + 1]."""
+        for t, name in ((x, "x"), (y, "y")):
+            _check_dev(t, name, self.device)
+            if t.dim() != 2 or t.dtype != _F32 or not t.is_contiguous():
+                raise ValueError(f"stream_loudness: {name} must be contiguous fp32 [S, n], got {t.dtype} {tuple(t.shape)}")
+        S, n = x.shape
+        if tuple(y.shape) != (S, stage.block_size) or stage.n_streams != S:
+            raise ValueError(f"stream_loudness: a stage for {stage.n_streams} streams of {stage.block_size}-sample blocks, x is {tuple(x.shape)} and y "
+                             f"{tuple(y.shape)}")
+        if shift is not None:
+            _check_dev(shift, "shift", self.device)
+            if shift.dtype != torch.int32 or tuple(shift.shape) != (S,) or not shift.is_contiguous():
+                raise ValueError(f"stream_loudness: shift must be contiguous int32 [{S}], got {shift.dtype} {tuple(shift.shape)}")
+        if isinstance(base, bool) or not isinstance(base, numbers.Integral):
+            raise ValueError(f"stream_loudness: base must be an integer, got {base!r}")
+        state = checked(stage, LOUDNESS_STATE, S, self.device, "stream_loudness: loudness.")
+        if out is None:
+            out = torch.empty_like(y)
+        else:
+            _check_dev(out, "out", self.device)
+            if out.dtype != _F32 or out.shape != y.shape or not out.is_contiguous():
+                raise ValueError(f"stream_loudness: out must be contiguous fp32 {tuple(y.shape)}, got {out.dtype} {tuple(out.shape)}")
+        sub, smooth, floor_db, boost_db, cut_db = stage.params()[2:]
+        gains = torch.empty(S, stage.block_size // sub + 1, dtype=_F32, device=self.device) if want_gains else None
+        self._ok(self.lib.tvc_stream_loudness_f32(self.ctx, self._stream(), _ptr(x), n, int(base), _ptr(shift), _ptr(y), _ptr(out), S, stage.block_size, sub,
+                                                  smooth, floor_db, boost_db, cut_db, *map(_ptr, state), _ptr(gains)), "tvc_stream_loudness_f32")
+        return (out, gains) if want_gains else out
 
     def stream_denoise(self, blocks, denoise, out=None):
         """The spectral suppressor in front of the window (tvc_stream_denoise_f32): blocks [S, block] the streams' new 24 kHz samples,

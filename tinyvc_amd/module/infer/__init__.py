@@ -1,4 +1,4 @@
 from .generator import Generator
-from .stream import StreamInfer, BatchedStreamInfer, StreamDoor, StreamGate, StreamDenoise
+from .stream import StreamInfer, BatchedStreamInfer, StreamDoor, StreamGate, StreamDenoise, StreamLoudness
 
-__all__ = ["Generator", "StreamInfer", "BatchedStreamInfer", "StreamDoor", "StreamGate", "StreamDenoise"]
+__all__ = ["Generator", "StreamInfer", "BatchedStreamInfer", "StreamDoor", "StreamGate", "StreamDenoise", "StreamLoudness"]

@@ -3,11 +3,11 @@
 import torch
 
 from .. import utils
-from ...engine import pitch_shifts
+from ...engine import loudness_in_place, pitch_shifts
 from .._base import HipModule
 from ..tinyvc import Decoder, Encoder
-from ..tinyvc.feature_retrieval import (alpha_rows, check_blend, check_references, prepare_reference, prepare_references, protect_rows,
-                                        resolve_alpha, resolve_auto_pitch, resolve_protect, target_form, target_registers)
+from ..tinyvc.feature_retrieval import (alpha_rows, check_blend, check_references, loudness_rows, prepare_reference, prepare_references, protect_rows,
+                                        resolve_alpha, resolve_auto_pitch, resolve_loudness, resolve_protect, target_form, target_registers)
 
 
 def _padded_lengths(lengths, B, L):
@@ -54,7 +54,7 @@ class Generator(HipModule):
 
     @torch.no_grad()
     def convert(self, wf, tgt, pitch_shift, f0_estimation="default", device=None, noise_angle=None, lengths=None, auto_pitch=None,
-                return_shift=False, track=None, alpha=None, protect=None):
+                return_shift=False, track=None, alpha=None, protect=None, loudness=None):
         """generator.py:26-34: wf [B, L], tgt [1 or B, 768, N] -> converted waveform [B, L'] (L' = L
         padded to a multiple of 480).  `f0_estimation` / `device` are accepted and ignored exactly as
         in the reference.  `noise_angle` [B,961,T] (extension) injects the decoder's noise phases;
@@ -87,7 +87,16 @@ class Generator(HipModule):
         of the f0 this call decodes (before any shift; neighbours stay inside the utterance), so voiced frames keep alpha and a fully unvoiced
         frame alpha + (1 - alpha) * protect (tvc_convert_protect_f32 / tvc_convert_ragged_protect_f32).  alpha's forms (a float, B floats, an
         fp32 [B] / [1] device tensor), with or without alpha (None: 0), every target form, equal and ragged, auto_pitch and track; 0 is the
-        alpha call bit for bit, None (the default) the call without it.  The 3-tap weight is an untuned guess: nobody has listened."""
+        alpha call bit for bit, None (the default) the call without it.  The 3-tap weight is an untuned guess: nobody has listened.
+        `loudness` (extension; RVC's rms_mix_rate, as 1 - its value): make the converted wave follow that share of the loudness envelope of
+        its source.  Every 10 ms the wave is scaled by (Es / Eo)^(share / 2), Es and Eo the mean powers of the padded input and of the wave
+        over 50 ms: one more launch behind the conversion (tvc_loudness_match_f32), with no host synchronisation and capturable, equal and
+        ragged batches alike (a ragged row's envelope never crosses its own padded length; the lengths travel as kernel arguments).  It runs
+        in place on the wave when the batch has a row for every compute unit, and into a tensor of its own below that
+        (engine.loudness_in_place).  A share in alpha's forms (a float in [0, 1], B of them, or an fp32 [B] / [1] device tensor, which the
+        kernel clamps), or a feature_retrieval.LoudnessMatch with the settings (sub_frame must divide 480).  Every target form, with alpha,
+        protect, auto_pitch, track and return_shift; 0 is the call without it bit for bit, None (the default) launch for launch.  The
+        settings' defaults are guesses: nobody has listened."""
         # 1. classify the target once; malformed targets, registers and shift lists are refused before any engine or device work
         B = wf.shape[0] if wf.dim() == 2 else 1
         auto = auto_pitch is not None and auto_pitch is not False
@@ -110,6 +119,9 @@ class Generator(HipModule):
         shift, shifts = pitch_shifts(pitch_shift, B)
         share = resolve_alpha(alpha, B) if alpha is not None else None
         guard = resolve_protect(protect, B) if protect is not None else None
+        level = resolve_loudness(loudness, B) if loudness is not None else None
+        if level is not None and 480 % level[0].sub_frame:
+            raise ValueError(f"loudness: sub_frame = {level[0].sub_frame} does not divide the 480-sample frames a call is padded to")
         # 2. the inputs, on the device
         wf = utils.autopad_waveform(self._input_device(wf))
         eng = self.engine(wf.device)
@@ -135,9 +147,17 @@ class Generator(HipModule):
                 rows["protect"] = protect_rows(guard, B, wf.device)
             res = eng._convert("alpha" if guard is None else "protect", wf, blobs, ns, pitch, noise_angle, lens, w,
                                target_registers(regs, B, wf.device) if auto else None, track=track, **rows)
-            return res if return_shift or not auto else res[0]
-        if not auto:
-            return eng._convert(form, wf, blobs, ns, pitch, noise_angle, lens, w)
-        wave, sh = eng._convert("auto" if track is None else "track", wf, blobs, ns, pitch, noise_angle, lens, w, target_registers(regs, B, wf.device),
-                                track=track)
-        return (wave, sh) if return_shift else wave
+            res = res if return_shift or not auto else res[0]
+        elif not auto:
+            res = eng._convert(form, wf, blobs, ns, pitch, noise_angle, lens, w)
+        else:
+            wave, sh = eng._convert("auto" if track is None else "track", wf, blobs, ns, pitch, noise_angle, lens, w, target_registers(regs, B, wf.device),
+                                    track=track)
+            res = (wave, sh) if return_shift else wave
+        # 5. with loudness, one launch behind it: the padded input and the wave (in place where that is the faster form)
+        if level is not None:
+            wave = res[0] if isinstance(res, tuple) else res
+            wave = eng.loudness_match(wf, wave, loudness_rows(level[1], B, wf.device), lengths=lens, settings=level[0],
+                                      out=wave if loudness_in_place(B, wf.device) else None)
+            res = (wave,) + tuple(res[1:]) if isinstance(res, tuple) else wave
+        return res

@@ -8,15 +8,16 @@ listener hears beyond the block itself; look-ahead (last_delay_size) is the righ
 sides of the block: clients send and receive int16 at their own rates.  `StreamGate` (extension) is a per-stream noise gate on the device,
 one launch behind SOLA: it follows the input window's power under the emitted block and looks ahead in what the window already holds.
 `StreamDenoise` (extension) is a per-stream spectral suppressor on the device, one launch in front of the window: noise under speech is
-turned down before the converter, the pitch tracker and the gate see it."""
+turned down before the converter, the pitch tracker and the gate see it.  `StreamLoudness` (extension) makes every emitted block follow the
+loudness envelope of the input it was converted from, one launch behind SOLA and in front of the gate."""
 import math
 
 import numpy as np
 import torch
 
-from ...engine import (SOLA_CROSS, SOLA_DELAY, SOLA_SEARCH, pitch_shifts, sola_geometry, stream_denoise_geometry, stream_gate_geometry,
-                       stream_resample_geometry)
-from ...stream_state import DENOISE_STATE, DOOR_STATE, GATE_STATE, TRACK_STATE, addresses, allocate, reset
+from ...engine import (SOLA_CROSS, SOLA_DELAY, SOLA_SEARCH, loudness_geometry, loudness_levels, pitch_shifts, sola_geometry, stream_denoise_geometry,
+                       stream_gate_geometry, stream_resample_geometry)
+from ...stream_state import DENOISE_STATE, DOOR_STATE, GATE_STATE, LOUDNESS_STATE, TRACK_STATE, addresses, allocate, reset
 from ..tinyvc.feature_retrieval import (PitchTrack, alpha_rows, gpu_device, protect_rows, resolve_alpha, resolve_auto_pitch, resolve_protect,
                                         target_form)
 from .generator import Generator
@@ -267,6 +268,48 @@ class StreamDenoise:
         reset(self, DENOISE_STATE, streams)
 
 
+class StreamLoudness:
+    """The loudness envelope match of a set of streams that advance in lock step (tvc_stream_loudness_f32; its definition is in
+    tinyvc_hip.h; 1 - RVC's rms_mix_rate): behind SOLA, every emitted block is scaled, sub-frame by sub-frame, by (Es / Eo)^(share / 2) -
+    Es the mean power of the INPUT samples the block was converted from, Eo that of the block itself, each over the last 2 * smooth + 1
+    sub-frames of the stream - so a speaker who drops to a murmur comes back as a murmur.  The gain trails the offline one
+    (convert's loudness) by `smooth` sub-frames.  It never feeds back: the SOLA buffer and the window stay as they are.
+      share [S]          fp32 on the device, read when a block runs and clamped to [0, 1] there: `stage.share.fill_(...)` / `copy_(...)` moves
+                         it between blocks; 0 = the stream without the stage, bit for bit (the envelopes are still followed, so a share
+                         raised later starts warm)
+      sub_frame, smooth  24 kHz samples (a multiple of 4 that divides block_size) and sub-frames each side (0 .. 32); `window` = 2 * smooth + 1
+      floor_db           powers below it (dB re full scale) count as it: silence is not amplified
+      boost_db, cut_db   the most a sub-frame is turned up and down by (>= 0)
+      src_ring, out_ring [S, window] fp64, frames [S] int64, gain [S] fp32      the state the next block starts from; gain_db [S]: the last gain in dB
+    The defaults are guesses: nobody has listened to them yet.  Every argument is checked before anything is allocated (ValueError)."""
+
+    def __init__(self, n_streams, block_size, share=1.0, sub_frame=240, smooth=2, floor_db=-60.0, boost_db=12.0, cut_db=40.0, device=None):
+        for x, name in ((n_streams, "n_streams"), (block_size, "block_size")):
+            if isinstance(x, bool) or not isinstance(x, int) or x < 1:
+                raise ValueError(f"StreamLoudness: {name} must be an integer >= 1, got {x!r}")
+        rows = _db_rows(share, n_streams, f"StreamLoudness: share must be a number in [0, 1] or one per stream ({n_streams}), got {share!r}")
+        if not all(0.0 <= v <= 1.0 for v in rows):
+            raise ValueError(f"StreamLoudness: share must be a number in [0, 1] or one per stream ({n_streams}), got {share!r}")
+        try:
+            _, self.window, _ = loudness_geometry(block_size, sub_frame, smooth, stream_block=True)
+        except ValueError as e:
+            raise ValueError(f"StreamLoudness: {e}") from None
+        self.floor_db, self.boost_db, self.cut_db = loudness_levels(floor_db, boost_db, cut_db, "StreamLoudness")
+        self.n_streams, self.block_size, self.sub_frame, self.smooth = n_streams, block_size, int(sub_frame), int(smooth)
+        self.device = gpu_device(device, "StreamLoudness: the share and the state live on the GPU, where the stage's kernel runs")
+        self.share = torch.tensor(rows, dtype=torch.float32, device=self.device)
+        allocate(self, LOUDNESS_STATE, self.device)
+
+    def params(self):
+        """the host values a captured block bakes in: (n_streams, block_size, sub_frame, smooth, floor_db, boost_db, cut_db)"""
+        return (self.n_streams, self.block_size, self.sub_frame, self.smooth, self.floor_db, self.boost_db, self.cut_db)
+
+    def reset(self, streams=None):
+        """Put every stream, or the listed ones, back at the start: empty envelopes, no sub-frame seen, gain 1 (the next block's first
+        sub-frame is flat at its own gain).  In-place ops on the state tensors, so it works between replays of a captured graph."""
+        reset(self, LOUDNESS_STATE, streams)
+
+
 class BatchedStreamInfer:
     """`target`: one index for every stream ([1, 768, N]) or one per stream ([S, 768, N], or a list of S [1, 768, N_s] tensors), prepared
     once and cached on those tensors - or a feature_retrieval.Blend of several (its weights are read on the device when a block runs:
@@ -290,6 +333,10 @@ class BatchedStreamInfer:
     the window (behind the door's input side), so the converter, the pitch tracker and the gate see the suppressed signal; it adds
     `denoise.delay_size` samples of latency.  `denoise.reduction_db.fill_(...)` / `copy_(...)` and `denoise.reset(...)` between blocks keep a
     captured graph; None (the default) is the stream without it, launch for launch.
+    `loudness` (a StreamLoudness of the same n_streams and block_size): every emitted block follows the loudness envelope of the input it was
+    converted from, one launch behind SOLA and in front of the gate (and the door), driven by the input window and `last_shift` on the
+    device; the SOLA buffer and the window stay as they are.  `loudness.share.fill_(...)` / `copy_(...)` and `loudness.reset(...)` between
+    blocks keep a captured graph; None (the default) is the stream without it, launch for launch.
     `crossfade_size`, `sola_search_size`, `last_delay_size` (kept as the attribute `last_dilay_size`, the reference's spelling): the tail's
     geometry in 24 kHz samples, within engine.sola_geometry's limits; `latency_samples` / `latency_seconds` give the resulting range.  The
     attributes are plain, as in the reference: one changed after construction takes effect at the next init_buffer(), which checks them again
@@ -298,14 +345,15 @@ class BatchedStreamInfer:
     shorter than the three sizes say, and a look-ahead shorter than the pad is refused."""
 
     def __init__(self, generator: Generator, n_streams=1, target=None, pitch_shift=0., device=None,
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, denoise=None, gate=None, door=None,
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, denoise=None, loudness=None, gate=None, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         self.input_size, _ = check_window(block_size, extra_size, crossfade_size, sola_search_size, last_delay_size,
                                            auto_pitch is not None and auto_pitch is not False)
         share = resolve_alpha(alpha, n_streams) if alpha is not None else None      # refused here, before anything is allocated
         guard = resolve_protect(protect, n_streams) if protect is not None else None
         self.n_streams, self.block_size = n_streams, block_size
-        self.door, self.gate, self.denoise = (self._fits(name, stage) for name, stage in (("door", door), ("gate", gate), ("denoise", denoise)))
+        self.door, self.gate, self.denoise, self.loudness = (self._fits(name, stage) for name, stage in
+                                                             (("door", door), ("gate", gate), ("denoise", denoise), ("loudness", loudness)))
         self.auto_pitch = auto_pitch if auto_pitch is not False else None
         self.pitch_track = pitch_track
         self._own_track = pitch_track is None
@@ -358,7 +406,7 @@ class BatchedStreamInfer:
         return lo / MODEL_RATE + extra, hi / MODEL_RATE + extra
 
     def _fits(self, name, stage):
-        """`stage` (a door, a gate, a suppressor, or None) when it was built for these streams; ValueError otherwise"""
+        """`stage` (a door, a gate, a suppressor, a loudness match, or None) when it was built for these streams; ValueError otherwise"""
         if stage is not None and (stage.n_streams, stage.block_size) != (self.n_streams, self.block_size):
             raise ValueError(f"{name}: built for {stage.n_streams} streams of {stage.block_size}-sample blocks, the streams are "
                              f"{self.n_streams} of {self.block_size}")
@@ -367,7 +415,7 @@ class BatchedStreamInfer:
     def _stages(self):
         """the stages of these streams that keep state on the device, in block order: (name, stage, its table in stream_state)"""
         every = (("track", self.pitch_track if self.auto_pitch is not None else None, TRACK_STATE), ("door", self.door, DOOR_STATE),
-                 ("denoise", self.denoise, DENOISE_STATE), ("gate", self.gate, GATE_STATE))
+                 ("denoise", self.denoise, DENOISE_STATE), ("loudness", self.loudness, LOUDNESS_STATE), ("gate", self.gate, GATE_STATE))
         return [s for s in every if s[1] is not None]
 
     def init_buffer(self):
@@ -375,7 +423,7 @@ class BatchedStreamInfer:
         # and _step holds every later block against what was seen here
         self.input_size, _ = check_window(self.block_size, self.extra_size, self.crossfade_size, self.sola_search_size, self.last_dilay_size,
                                            self.auto_pitch is not None)
-        for name in ("door", "gate", "denoise"):      # (before anything is allocated) the stages against the attributes as they stand now
+        for name in ("door", "gate", "denoise", "loudness"):      # (before anything is allocated) the stages against the attributes as they stand now
             self._fits(name, getattr(self, name))
         if self.gate is not None:
             check_gate_lookahead(self.gate.lookahead_size, self.crossfade_size, self.last_dilay_size, self.pad_size)
@@ -416,14 +464,16 @@ class BatchedStreamInfer:
         eng = self.generator.engine(self.device)
         out, shift = eng.sola(y, self.sola_buffer, self.fade_in_window, self.block_size, self.use_phase_vocoder, want_shift=True,
                               crossfade=self.crossfade_size, search=self.sola_search_size, delay=self.last_dilay_size)
+        # y[Ly - block - crossfade - search - delay + shift + j] became out[j], and convert keeps the window's time axis (padding at the end)
+        base = y.shape[1] - self.block_size - self.crossfade_size - self.sola_search_size - self.last_dilay_size
+        if self.loudness is not None:      # in front of the gate: the gate's fades stay what they are
+            eng.stream_loudness(self.input_wav, out, shift, self.loudness, base, out=out)
         if self.gate is not None:
-            # y[Ly - block - crossfade - search - delay + shift + j] became out[j], and convert keeps the window's time axis (padding at the end)
-            base = y.shape[1] - self.block_size - self.crossfade_size - self.sola_search_size - self.last_dilay_size
             eng.stream_gate(self.input_wav, out, shift, self.gate, base, out=out)
         return out, shift, pshift
 
     def _step_pcm(self, pcm, noise_angle):
-        # the whole block from client int16 to client int16: door in, _step (convert, SOLA, gate), door out
+        # the whole block from client int16 to client int16: door in, _step (convert, SOLA, loudness, gate), door out
         eng = self.generator.engine(self.device)
         out, shift, pshift = self._step(self.door.push(eng, pcm), noise_angle)
         return self.door.pull(eng, out), shift, pshift
@@ -432,7 +482,7 @@ class BatchedStreamInfer:
         """Everything a captured step bakes in as raw device pointers: the packed weights (re-packed - and the old arena
         freed - when a parameter changes), the engine's scratch workspace (re-allocated when another call needs a bigger
         one), the prepared index riding on `target`, plus the scalars captured by value.  Every stage present - the
-        tracker, the door, the suppressor (denoise), the gate - adds (its name, WHERE the tensors of its table in stream_state live, its
+        tracker, the door, the suppressor (denoise), the loudness match, the gate - adds (its name, WHERE the tensors of its table in stream_state live, its
         params()): the table lists every tensor whose pointer reaches the library, so none can be passed on and left out here.  With
         auto_pitch also WHERE the target registers live, with alpha / protect where the shares live.  Never a value: the kernels read those at replay,
         so a reset(), registers.copy_(...), threshold_db.fill_(...) or a stream's history advancing keeps the graph.  The tail's geometry is
@@ -523,7 +573,7 @@ class StreamInfer(BatchedStreamInfer):
     """Single stream with the reference's constructor and 1-D buffers (stream.py:31-57)."""
 
     def __init__(self, generator: Generator, target=None, pitch_shift=0., device=torch.device("cpu"),
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, denoise=None, gate=None, door=None,
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, denoise=None, loudness=None, gate=None, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         dev = torch.device(device)
         if dev.type != "cuda":
@@ -531,7 +581,7 @@ class StreamInfer(BatchedStreamInfer):
         super().__init__(generator, n_streams=1, target=target, pitch_shift=pitch_shift, device=dev, block_size=block_size, extra_size=extra_size,
                          use_phase_vocoder=use_phase_vocoder, f0_estimation=f0_estimation, use_graph=use_graph, alpha=alpha, protect=protect, denoise=denoise, gate=gate,
                          door=door, crossfade_size=crossfade_size, sola_search_size=sola_search_size, last_delay_size=last_delay_size,
-                         auto_pitch=auto_pitch, pitch_track=pitch_track)
+                         auto_pitch=auto_pitch, pitch_track=pitch_track, loudness=loudness)
 
     @torch.no_grad()
     def audio_callback(self, block, noise_angle=None):

@@ -8,7 +8,7 @@ import sys
 import torch
 
 from ... import spec, stream_state
-from ...engine import default_engine
+from ...engine import default_engine, integer, loudness_geometry, loudness_levels
 
 
 def prepare_reference(reference):
@@ -260,6 +260,62 @@ def resolve_protect(protect, B):
 
 def protect_rows(resolved, B, device):
     return alpha_rows(resolved, B, device, "protect")
+
+
+class LoudnessMatch:
+    """convert's loudness - how far the converted wave follows the loudness envelope of its source (tvc_loudness_match_f32; the definition is
+    in include/tinyvc_hip.h; 1 - RVC's rms_mix_rate): every `sub_frame` samples the output is scaled by (Es / Eo)^(share / 2), Es and Eo the
+    mean powers of input and output over 2 * smooth + 1 sub-frames, never below `floor_db` (dB re full scale: silence is not amplified),
+    never by more than `boost_db` up or `cut_db` down, ramped from sub-frame to sub-frame.
+      share      alpha's forms: a float, B floats, or an fp32 [B] / [1] device tensor ([B]: used in place, read when the kernel runs, where
+                 values outside [0, 1] are clamped); 0 leaves every bit
+      sub_frame  24 kHz samples, a multiple of 4 (convert: a divisor of 480); smooth: sub-frames each side, 0 .. 32
+    The defaults are guesses: nobody has listened to them yet.  The settings are checked here and the share in resolve_loudness
+    (ValueError), before any engine work."""
+
+    def __init__(self, share, sub_frame=240, smooth=2, floor_db=-60.0, boost_db=12.0, cut_db=40.0):
+        try:
+            sub_frame = integer(sub_frame, "loudness geometry", "sub")
+            loudness_geometry(sub_frame, sub_frame, smooth)      # one sub-frame: the limits of sub_frame and smooth themselves
+        except ValueError as e:
+            raise ValueError(f"loudness: {e}") from None
+        self.floor_db, self.boost_db, self.cut_db = loudness_levels(floor_db, boost_db, cut_db)
+        self.share, self.sub_frame, self.smooth = share, int(sub_frame), int(smooth)
+
+
+def resolve_loudness(loudness, B):
+    """convert's loudness as given - a LoudnessMatch, or a bare share (LoudnessMatch(share)) - checked on the host (no engine, no device work)
+    -> (settings, share): the LoudnessMatch and its share as a list of B floats or the device tensor.  The share takes alpha's forms by
+    alpha's code; floats outside [0, 1] and NaN are refused (a tensor is read, and clamped, on the device).  ValueError naming loudness."""
+    settings = loudness if isinstance(loudness, LoudnessMatch) else LoudnessMatch(loudness)
+    share = resolve_alpha(settings.share, B, "loudness")
+    if not isinstance(share, torch.Tensor) and not all(0.0 <= x <= 1.0 for x in share):
+        raise ValueError(f"loudness: a share of the source's envelope in [0, 1], got {settings.share!r}")
+    return settings, share
+
+
+def loudness_rows(resolved, B, device):
+    return alpha_rows(resolved, B, device, "loudness")
+
+
+def add_loudness_argument(parser):
+    """`--loudness E` for the entry scripts' parsers: absent (None) is the call without it"""
+    parser.add_argument("--loudness", type=float, default=None, metavar="E",
+                        help="make the converted voice follow this share (0 .. 1) of the source's loudness envelope, 10 ms sub-frames smoothed over "
+                             "50 ms (1 - RVC's rms_mix_rate).  The defaults behind it are guesses: nobody has listened.  default: absent, the level "
+                             "the decoder gives")
+
+
+def loudness_keywords(args, script):
+    """what `--loudness` adds to the script's convert call: nothing when it is absent (the call is today's), else {"loudness": E} and one
+    printed line; a value outside [0, 1] ends the script"""
+    e = getattr(args, "loudness", None)
+    if e is None:
+        return {}
+    if not 0.0 <= e <= 1.0:      # (NaN fails both)
+        sys.exit(f"{script}: --loudness must be a share in 0 .. 1")
+    print(f"Following {e:g} of the source's loudness envelope (loudness; rms mix rate {1 - e:g})")
+    return {"loudness": float(e)}
 
 
 def add_alpha_argument(parser):
