@@ -721,6 +721,63 @@ int tvc_stream_loudness_f32(tvc_ctx* ctx, void* stream, const float* x, int64_t 
                             int block, int sub, int smooth, float floor_db, float boost_db, float cut_db, const float* share, double* src_ring,
                             double* out_ring, int64_t* frames, float* gain, float* gain_db, float* gains);
 
+/* The look-ahead peak limiter (extension; the stage every real-time voice chain ends in): nothing it emits lies above a ceiling, exactly.
+ * y is the signal to limit, cut into sub-frames of `sub` samples (a multiple of 4; 24 = 1 ms, which is the look-ahead and the attack).
+ *   c          = ceiling[row or stream], a linear fp32 amplitude read from device memory when the kernel runs; NaN, <= 0 and +inf mean off
+ *              and are treated as +inf.
+ *   drive      an fp32 factor baked in: (float)10^(drive_db / 20), computed in double on the host and rounded once.
+ *   R          = release, in sub-frames, 1 <= R <= 4096;  d = 1.0f / (float)R, one fp32 division.
+ * Every operation below is a separate fp32 rounding (__fmul_rn, __fadd_rn, __fdiv_rn, ...), as in the loudness match's ramp.
+ *   v[n]  = y[n] * drive
+ *   p[k]  = max over sub-frame k of |v|        (NaN samples ignored; p[-1] = 0; p[K] = 0 behind the last sub-frame of a row)
+ *   m[k]  = max(p[k-1], p[k])                  for edge k = the start of sub-frame k, k = 0 .. K
+ *   r[k]  = m[k] > c ? c / m[k] : 1.0f         (m = inf -> 0)
+ *   e[k]  = min(r[k], min(1.0f, e[k-1] + d))   e[-1] = 1          (instant fall, linear rise: the gate's rule)
+ *   out[k*sub + j] = clampc( v[k*sub + j] * (e[k] + (e[k+1] - e[k]) * ((j + 1) / (float)sub)) )      the gate's ramp
+ *   clampc(t) = t > c ? c : (t < -c ? -c : t)                      (NaN passes; with c = inf nothing happens)
+ * Both edge gains of sub-frame k are at most c / p[k] and the ramp stays between them up to rounding, so |out| <= c up to a few ulp; clampc
+ * makes the bound exact and only ever moves a sample by that rounding.  Wherever e[k] == e[k+1] == 1 and drive == 1 the samples keep their
+ * bits.  A NaN sample comes out NaN and moves no gain; an infinite one drives its two edges to 0 and comes out NaN.
+ * f(e) = min(1, e + d) is monotone and f^(R+1)(0) == 1.0f exactly for every legal R, so e[k] depends on r[k - R .. k] only: a recurrence
+ * restarted from e = 1 at R + 1 edges back gives the same bits.  The offline kernel's tile grid rests on this.
+ * Defaults (guesses: nobody has listened): sub = 24, release = 100 sub-frames (100 ms), ceiling -1 dBFS, drive 0 dB.
+ *
+ * tvc_limit_f32 (offline): y, out [B][L], ceiling [B] fp32 on the device.  lengths (nullable): int64 [B] on the HOST, travelling as kernel
+ * arguments as in tvc_loudness_match_f32 - row b owns its first lengths[b] samples (clamped to 0 .. L, whole sub-frames of them), p is 0
+ * behind those sub-frames and the samples behind them are copied unchanged.  gains (nullable): [B][L / sub + 1] fp32, the edge gains
+ * e[0 .. K]; edges behind a row's last one hold 1.  One launch (one per 384 rows of a larger batch) on a grid of rows x tiles of `tile`
+ * sub-frames, no workspace, no host synchronisation, 64-bit indices.  Per tile a workgroup takes the peaks of its sub-frames, of the R + 2
+ * before them and of the one after, runs the recurrence with every thread owning a few edges behind a warm-up of R + 1, and applies the
+ * ramp; only peaks and gains sit in LDS (tile + R + 3 floats).  out must not overlap y - an in-place call is refused: another tile's halo
+ * would be read while it is being scaled.  y and out are 16-byte aligned.
+ *
+ * tvc_stream_limit_f32 (streams): y, out [S][block], one launch, one workgroup per stream, which walks the block in chunks of `chunk`
+ * sub-frames, so no resource depends on the block.  Sub-frame k can only leave once p[k+1] is known: the stage delays by exactly `sub`
+ * samples.  State per stream, on the device, advanced in place: tail [S][sub] fp32 (the driven samples of the sub-frame not yet emitted),
+ * peak [S] (its peak), gain [S] (e at its start); a stream starts at zeros, 0 and 1.0.  A stream's blocks, concatenated, are `sub` zeros
+ * followed by the offline result of the whole signal, bit for bit, however the stream is cut into blocks, whatever S is and whatever the
+ * neighbours do.  reduction_db [S] (nullable): 20 log10 of the smallest edge gain of the block, the carried one included (a meter).
+ * gains (nullable): [S][block / sub + 1], the block's edge gains (edge 0: the carried gain).  out must not overlap y; y, out and tail are
+ * 16-byte aligned.  Everything but ceiling and the state is baked into a capture.  No workspace.
+ *
+ * tvc_limiter_geometry (host only: no context, no device) holds the limits: 4 <= sub <= 65536, sub % 4 == 0, 1 <= length <= 2^40 a multiple
+ * of sub, 1 <= release <= 4096; tvc_stream_limiter_geometry the same for a stream's block of one sub-frame .. 2^30 samples.  Anything else
+ * returns TVC_ERR_ARG; otherwise nsub = length / sub, delay = sub and tile / chunk (out pointers are nullable).  The _message entries give
+ * the reason of a refusal ("" for a legal geometry), valid until the thread's next call.  The two device entries refuse the same
+ * geometries with that reason in tvc_last_error, and: a NULL pointer (lengths, reduction_db and gains are exempt), B or S <= 0, a drive_db
+ * that is not finite or whose factor is not a positive finite fp32 number - all with TVC_ERR_ARG before anything is launched.
+ *
+ * Two limits of the guarantee: the door's int16 conversion still wraps a sample above 32767 / 32768, so a ceiling above that bounds
+ * nothing there; and a resampling door interpolates between samples and may overshoot the ceiling: -1 dB is margin, not proof. */
+int tvc_limiter_geometry(int64_t length, int sub, int release, int64_t* nsub, int* delay, int* tile);
+const char* tvc_limiter_geometry_message(int64_t length, int sub, int release);
+int tvc_stream_limiter_geometry(int block, int sub, int release, int* nsub, int* delay, int* chunk);
+const char* tvc_stream_limiter_geometry_message(int block, int sub, int release);
+int tvc_limit_f32(tvc_ctx* ctx, void* stream, const float* y, float* out, int B, int64_t L, const int64_t* lengths, const float* ceiling, int sub, int release,
+                  float drive_db, float* gains);
+int tvc_stream_limit_f32(tvc_ctx* ctx, void* stream, const float* y, float* out, int S, int block, int sub, int release, float drive_db, const float* ceiling,
+                         float* tail, float* peak, float* gain, float* reduction_db, float* gains);
+
 /* measurement ----------------------------------------------------------------------------- */
 /* on = 1: every stage (and every FilterNet block) is bracketed by a hipEvent pair on the launch stream (19 pairs per
  * convert, ~0.1 ms of a 8.4 ms step); on = 2: only the `filter_net` region (the roofline's kernel group); on = 0: off.

@@ -36,11 +36,11 @@ import zlib
 import torch
 
 from tinyvc_amd import audio_io, parallel, spec
-from tinyvc_amd.engine import loudness_geometry
+from tinyvc_amd.engine import limiter_geometry, loudness_geometry
 from tinyvc_amd.module.infer import Generator
 from tinyvc_amd.module.tinyvc import Blend, Decoder, Encoder
-from tinyvc_amd.module.tinyvc.feature_retrieval import (add_alpha_argument, add_auto_pitch_argument, add_blend_argument, add_loudness_argument, alpha_keywords,
-                                                        attach_register, loudness_keywords, pitch_register)
+from tinyvc_amd.module.tinyvc.feature_retrieval import (add_alpha_argument, add_auto_pitch_argument, add_blend_argument, add_limit_argument, add_loudness_argument,
+                                                        alpha_keywords, attach_register, limit_keywords, loudness_keywords, pitch_register)
 
 SAMPLE_RATE = 24000
 
@@ -59,6 +59,7 @@ def build_parser():
     p.add_argument("-p", "--pitch-shift", default=0.0, type=float)
     add_auto_pitch_argument(p)      # --auto-pitch: every file's median f0 onto the target's register; -p stays, as the offset
     add_loudness_argument(p)        # --loudness E: follow that share of every file's own loudness envelope
+    add_limit_argument(p)           # --limit [DB]: a look-ahead peak limiter behind everything else: no sample above the ceiling
     add_alpha_argument(p)           # --alpha A: keep that share of every file's own content features in the match; --protect P: more on unvoiced frames
     p.add_argument("-c", "--chunk-size", default=1920, type=int)
     p.add_argument("-b", "--buffer-size", default=4, type=int)
@@ -135,15 +136,21 @@ def convert_chunked(gen, batch, tgt, pitch_shift, chunk_size, buffer_blocks, use
     `stream_callback`; default: drawn on the device per block, as the reference's `torch.rand` is).
     `return_blocks`: also return the untrimmed block outputs [B, nblk, chunk_size] and the SOLA lags [nblk, B].
     `stream_kw`: further BatchedStreamInfer keywords (alpha, protect, loudness: a share of the source's loudness envelope - a StreamLoudness
-    stage for these streams is built from it here)."""
-    from tinyvc_amd.module.infer import BatchedStreamInfer, StreamLoudness
+    stage for these streams is built from it here; limit: a ceiling in dBFS - a StreamLimiter likewise, passed on as `limiter`, whose
+    delay_size joins the trim)."""
+    from tinyvc_amd.module.infer import BatchedStreamInfer, StreamLimiter, StreamLoudness
     B, L = batch.shape
+    delay = 0
+    if stream_kw.get("limit") is not None:
+        limit = stream_kw.pop("limit")
+        stream_kw["limiter"] = limit if isinstance(limit, StreamLimiter) else StreamLimiter(B, chunk_size, ceiling_db=limit, device=batch.device)
+        delay = stream_kw["limiter"].delay_size
     if stream_kw.get("loudness") is not None and not isinstance(stream_kw["loudness"], StreamLoudness):
         stream_kw["loudness"] = StreamLoudness(B, chunk_size, share=stream_kw["loudness"], device=batch.device)
     st = BatchedStreamInfer(gen, n_streams=B, target=tgt, pitch_shift=pitch_shift, device=batch.device, block_size=chunk_size,
                             extra_size=buffer_blocks * chunk_size, use_phase_vocoder=use_phase_vocoder, use_graph=True, **stream_kw)
     st.init_buffer()
-    nblk = -(-(L + SOLA_MAX_LATENCY) // chunk_size)
+    nblk = -(-(L + SOLA_MAX_LATENCY + delay) // chunk_size)
     padded = torch.zeros(B, nblk * chunk_size, device=batch.device)
     padded[:, :L] = batch
     outs, lags = [], []
@@ -154,7 +161,7 @@ def convert_chunked(gen, batch, tgt, pitch_shift, chunk_size, buffer_blocks, use
     stream = torch.cat(outs, dim=1)
     nsig = max(1, -(-L // chunk_size))                               # blocks that carry signal (the flush blocks' lags are noise)
     latency = (SOLA_MAX_LATENCY - lags[:nsig].float().median(dim=0).values.round().long()).clamp(0, SOLA_MAX_LATENCY).tolist()
-    out = torch.stack([stream[b, latency[b]:latency[b] + L] for b in range(B)], dim=0)
+    out = torch.stack([stream[b, latency[b] + delay:latency[b] + delay + L] for b in range(B)], dim=0)
     if return_blocks:
         return out, torch.stack(outs, dim=1), lags
     return out
@@ -191,6 +198,12 @@ def main(argv=None, world=None, rank=None, local_rank=None):
             loudness_geometry(args.chunk_size, stream_block=True)
         except ValueError as e:
             sys.exit(f"infer.py: --loudness with --chunked: {e}")
+    alpha_kw.update(limit_keywords(args, "infer.py"))         # likewise --limit
+    if "limit" in alpha_kw and args.chunked and not args.no_chunking:      # a stream's stage works on whole 1 ms sub-frames of a block
+        try:
+            limiter_geometry(args.chunk_size, stream_block=True)
+        except ValueError as e:
+            sys.exit(f"infer.py: --limit with --chunked: {e}")
     os.makedirs(args.outputs, exist_ok=True)
 
     paths = []

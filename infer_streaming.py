@@ -47,6 +47,13 @@ the input the block was converted from and of the block itself over the last `--
 it, and a sub-frame is never turned up by more than `--loudness-boost` or down by more than `--loudness-cut`.  It adds no latency.  The
 defaults are guesses: nobody has listened yet.
 
+`--limit [DB]` (extension; bare: -1) ends every stream in a look-ahead peak limiter on the device, behind the gate and in front of the int16
+conversion: no sample leaves above DB dBFS - exactly -, where without it a sample of 1.0 or more wraps to a full-scale click.  The gain
+falls at once, 1 ms ahead of a peak, and rises linearly over `--limit-release`.  `-og` then becomes the limiter's drive: the gain is applied
+in front of the limiter, not behind it.  It costs 1 ms of latency.  DB is at most -0.001 (above 32767 / 32768 the conversion wraps); with
+--resample the filter on the way out can overshoot the ceiling between samples: -1 dB is margin, not proof.  The defaults are guesses:
+nobody has listened yet.
+
 `--streams S` feeds S copies of the input as S concurrent streams through one BatchedStreamInfer
 (one batched convert + one SOLA launch per block) and reports the p50 / p95 block latency against the
 real-time budget (chunk / 24 kHz = 80 ms for the default 1920-sample chunk).
@@ -61,9 +68,9 @@ import torch
 
 from tinyvc_amd import audio_io
 from infer import load_generator, load_target
-from tinyvc_amd.engine import loudness_geometry, loudness_levels, sola_geometry, stream_denoise_geometry, stream_gate_geometry, stream_resample_geometry
-from tinyvc_amd.module.infer import BatchedStreamInfer, StreamDenoise, StreamDoor, StreamGate, StreamLoudness
-from tinyvc_amd.module.infer.stream import check_gate_lookahead, check_window, denoise_constants
+from tinyvc_amd.engine import limiter_drive, limiter_geometry, loudness_geometry, loudness_levels, sola_geometry, stream_denoise_geometry, stream_gate_geometry, stream_resample_geometry
+from tinyvc_amd.module.infer import BatchedStreamInfer, StreamDenoise, StreamDoor, StreamGate, StreamLimiter, StreamLoudness
+from tinyvc_amd.module.infer.stream import DOOR_CEILING_DB, check_gate_lookahead, check_window, denoise_constants
 from tinyvc_amd.module.tinyvc.feature_retrieval import (PitchTrack, add_alpha_argument, add_blend_argument, alpha_keywords, pitch_register,
                                                         semitones_between)
 
@@ -71,6 +78,8 @@ FRAMES_PER_SECOND = 50      # 24 kHz / 480 samples
 GATE_SUB_FRAME = 240        # the gate's sub-frame: 10 ms at 24 kHz
 DENOISE_DEFAULTS = dict(hop=160, strength=2.0, adapt_s=1.0, smooth_ms=40.0, warmup_ms=200.0)      # of --denoise-hop / -strength / -adapt / -smooth / -warmup
 LOUDNESS_DEFAULTS = dict(window=50.0, floor=-60.0, boost=12.0, cut=40.0)      # of --loudness-window (ms) / -floor / -boost / -cut (dB)
+LIMIT_SUB_FRAME = 24        # the limiter's sub-frame, its look-ahead and delay: 1 ms at 24 kHz
+LIMIT_RELEASE_MS = 100.0    # the default of --limit-release
 GATE_MS = dict(hold=200.0, attack=10.0, release=100.0, lookahead=20.0)      # the defaults of --gate-hold / -attack / -release / -lookahead
 
 
@@ -141,6 +150,12 @@ def build_parser():
                    help=f"powers below this (dB re full scale) count as it: silence is not amplified (default {LOUDNESS_DEFAULTS['floor']:g})")
     p.add_argument("--loudness-boost", default=None, type=float, metavar="DB", help=f"the most a sub-frame is turned up by, >= 0 (default {LOUDNESS_DEFAULTS['boost']:g})")
     p.add_argument("--loudness-cut", default=None, type=float, metavar="DB", help=f"the most a sub-frame is turned down by, >= 0 (default {LOUDNESS_DEFAULTS['cut']:g})")
+    p.add_argument("--limit", default=None, type=float, nargs="?", const=-1.0, metavar="DB",
+                   help="end every stream in a look-ahead peak limiter on the device: no sample leaves above this ceiling (dBFS, at most -0.001; bare: -1), "
+                        "where without it a sample of 1.0 or more wraps in the int16 conversion.  -og becomes the limiter's drive, in front of it; 1 ms of "
+                        "latency (stage.ceiling, live on the device).  The defaults are guesses: nobody has listened yet")
+    p.add_argument("--limit-release", default=None, type=float, metavar="MS",
+                   help=f"the time a fully reduced gain takes back to 1: whole milliseconds, 1 .. 4096 (default {LIMIT_RELEASE_MS:g})")
     # file-driven operation (no audio devices on a GPU node)
     p.add_argument("--input-wav", default=None, help="read the microphone signal from this WAV instead of a device")
     p.add_argument("--output-wav", default=None, help="write the converted stream here")
@@ -303,6 +318,28 @@ def check_loudness(args, block=None):
     return dict(share=args.loudness, sub_frame=GATE_SUB_FRAME, smooth=(int(window) - 1) // 2, floor_db=v["floor"], boost_db=v["boost"], cut_db=v["cut"])
 
 
+def check_limit(args, block=None):
+    """--limit and --limit-release against each other, -og and the block, before anything is loaded: sys.exit with a message, or the
+    StreamLimiter keywords (None without --limit) - -og travels in them as drive_db, and the door then gets an output gain of 0.
+    `block`: the model's block length when it is not -c (--resample)"""
+    if args.limit is None:
+        if args.limit_release is not None:
+            sys.exit("infer_streaming.py: --limit-release without --limit [DB]: there is no stage to set")
+        return None
+    if not args.limit <= DOOR_CEILING_DB or args.limit < -600.0:      # (NaN fails the first)
+        sys.exit(f"infer_streaming.py: --limit: a ceiling in dBFS of at most {DOOR_CEILING_DB:g} (above 32767 / 32768 the int16 conversion wraps)")
+    ms = LIMIT_RELEASE_MS if args.limit_release is None else args.limit_release
+    release = ms * 24.0 / LIMIT_SUB_FRAME
+    if not math.isfinite(release) or release != int(release):
+        sys.exit(f"infer_streaming.py: --limit-release {ms:g}: a whole number of {LIMIT_SUB_FRAME / 24.0:g} ms sub-frames")
+    try:
+        limiter_geometry(args.chunk if block is None else block, LIMIT_SUB_FRAME, int(release), stream_block=True)
+        drive = limiter_drive(args.output_gain, "-og")
+    except ValueError as e:
+        sys.exit(f"infer_streaming.py: --limit: {e}")
+    return dict(ceiling_db=args.limit, sub_frame=LIMIT_SUB_FRAME, release_size=int(release) * LIMIT_SUB_FRAME, drive_db=drive)
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     block = check_resample(args)
@@ -311,6 +348,7 @@ def main(argv=None):
     gate_kw = check_gate(args, block)
     denoise_kw = check_denoise(args, block)
     loudness_kw = check_loudness(args, block)
+    limit_kw = check_limit(args, block)
     device = torch.device(args.device)
     if device.type != "cuda":
         sys.exit("infer_streaming.py: this build runs on an AMD GPU only; pass -d cuda")
@@ -340,7 +378,8 @@ def main(argv=None):
     # the int16 conversions and gains belong to the door; without --resample it stands between equal rates - the samples are taken for
     # 24 kHz whatever -sr says, as in the reference - and is those conversions alone
     rate = args.sample_rate if block is not None else 24000
-    door = StreamDoor(S, rate, rate, block if block is not None else args.chunk, args.input_gain, args.output_gain, device=device)
+    # (with --limit -og is the limiter's drive, in front of it: a gain behind the limiter would lift its ceiling)
+    door = StreamDoor(S, rate, rate, block if block is not None else args.chunk, args.input_gain, args.output_gain if limit_kw is None else 0.0, device=device)
     if block is not None:
         print(f"Resampling {rate} Hz <-> 24000 Hz on the device: {args.chunk}-sample blocks are {block} at the model's rate; "
               f"the two filters add {door.latency_seconds * 1e3:.2f} ms of latency")
@@ -362,11 +401,17 @@ def main(argv=None):
         alpha_kw["loudness"] = stage = StreamLoudness(S, door.block_size, device=device, **loudness_kw)
         print(f"Following {loudness_kw['share']:g} of the speaker's loudness envelope: {stage.window * GATE_SUB_FRAME / 24:g} ms window, floor {stage.floor_db:g} dB, "
               f"at most +{stage.boost_db:g} / -{stage.cut_db:g} dB")
+    if limit_kw is not None:      # (absent: the stream is built as it has always been)
+        alpha_kw["limiter"] = stage = StreamLimiter(S, door.block_size, device=device, **limit_kw)
+        print(f"Peak limiter at {limit_kw['ceiling_db']:g} dBFS: drive {stage.drive_db:g} dB (-og), look-ahead and attack {stage.sub_frame / 24:g} ms, release "
+              f"{stage.release_size / 24:g} ms")
     stream = BatchedStreamInfer(gen, n_streams=S, pitch_shift=pitch_shift, block_size=door.block_size, device=device, extra_size=args.extra,
                                 f0_estimation=args.f0_estimation, door=door, auto_pitch=True if track is not None else None, pitch_track=track,
                                 crossfade_size=args.crossfade, sola_search_size=args.sola_search, last_delay_size=args.lookahead, gate=gate, denoise=denoise, **alpha_kw)
     lo, hi = stream.latency_seconds
     delay = f" + the suppressor's {denoise.delay_size}" if denoise is not None else ""
+    if limit_kw is not None:
+        delay += f" + the limiter's {stage.delay_size} (1 ms)"
     print(f"Latency {lo * 1e3:.1f} to {hi * 1e3:.1f} ms (cross-fade {args.crossfade} + look-ahead {args.lookahead} + lag 0 .. {args.sola_search}{delay} samples at 24 kHz"
           f"{', and the resampling filters' if block is not None else ''}) plus the {door.block_size / 24000 * 1e3:.0f} ms block")
     stream.target = tgt

@@ -133,6 +133,13 @@ SIGNATURES = {
                                        c_float, c_void_p]),
     "tvc_stream_loudness_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
                                         c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tvc_limiter_geometry": (c_int, [c_int64, c_int, c_int, POINTER(c_int64), POINTER(c_int), POINTER(c_int)]),
+    "tvc_limiter_geometry_message": (c_char_p, [c_int64, c_int, c_int]),
+    "tvc_stream_limiter_geometry": (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "tvc_stream_limiter_geometry_message": (c_char_p, [c_int, c_int, c_int]),
+    "tvc_limit_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, POINTER(c_int64), c_void_p, c_int, c_int, c_float, c_void_p]),
+    "tvc_stream_limit_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p]),
     "tvc_profile_enable": (c_int, [c_void_p, c_int]),
     "tvc_profile_read": (c_int, [c_void_p, ctypes.c_char_p, c_size_t]),
 }

@@ -1271,6 +1271,69 @@ int tvc_stream_loudness_f32(tvc_ctx* ctx, void* stream, const float* x, int64_t 
     return run_stream_loudness(ctx, (hipStream_t)stream, x, n, base, shift, y, out, S, g, c, gains);
 }
 
+int tvc_limiter_geometry(int64_t length, int sub, int release, int64_t* nsub, int* delay, int* tile) {
+    return limiter_geometry(length, sub, release, false, nsub, delay, tile, nullptr, 0);
+}
+
+const char* tvc_limiter_geometry_message(int64_t length, int sub, int release) {
+    static thread_local char why[96];
+    limiter_geometry(length, sub, release, false, nullptr, nullptr, nullptr, why, sizeof(why));
+    return why;
+}
+
+int tvc_stream_limiter_geometry(int block, int sub, int release, int* nsub, int* delay, int* chunk) {
+    int64_t n = 0;
+    const int rc = limiter_geometry(block, sub, release, true, &n, delay, chunk, nullptr, 0);
+    if (rc == 0 && nsub) *nsub = (int)n;
+    return rc;
+}
+
+const char* tvc_stream_limiter_geometry_message(int block, int sub, int release) {
+    static thread_local char why[96];
+    limiter_geometry(block, sub, release, true, nullptr, nullptr, nullptr, why, sizeof(why));
+    return why;
+}
+
+int tvc_limit_f32(tvc_ctx* ctx, void* stream, const float* y, float* out, int B, int64_t L, const int64_t* lengths, const float* ceiling, int sub, int release,
+                  float drive_db, float* gains) {
+    if (!ctx) return TVC_ERR_ARG;
+    char why[96];
+    if (limiter_geometry(L, sub, release, false, nullptr, nullptr, nullptr, why, sizeof(why)) != 0) return fail(ctx, TVC_ERR_ARG, "tvc_limit_f32: %s", why);
+    if (!y || !out || !ceiling || B <= 0) return fail(ctx, TVC_ERR_ARG, "tvc_limit_f32: bad argument (a NULL pointer or B <= 0)");
+    float drive = 1.f;
+    if (limiter_drive(drive_db, &drive, why, sizeof(why)) != 0) return fail(ctx, TVC_ERR_ARG, "tvc_limit_f32: %s", why);
+    if (((uintptr_t)y | (uintptr_t)out) & 15)
+        return fail(ctx, TVC_ERR_ARG, "tvc_limit_f32: y and out must be 16-byte aligned (the rows are read and written 16 bytes at a time)");
+    const int64_t tiles = (L / sub + kLimiterTile - 1) / kLimiterTile;
+    if (tiles * std::min(B, kLoudnessLenRows) > INT32_MAX)
+        return fail(ctx, TVC_ERR_ARG, "tvc_limit_f32: %d rows of %ld tiles are more than 2^31 - 1 workgroups", std::min(B, kLoudnessLenRows), (long)tiles);
+    // a workgroup reads the sub-frames of y in its neighbours' tiles, which an overlapping out would be changing: in place is refused too
+    const uintptr_t bytes = (uintptr_t)B * (uintptr_t)L * sizeof(float), o = (uintptr_t)out;
+    if (o < (uintptr_t)y + bytes && (uintptr_t)y < o + bytes) return fail(ctx, TVC_ERR_ARG, "tvc_limit_f32: out overlaps y (another tile's halo would be read while it is being scaled)");
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    return run_limit(ctx, (hipStream_t)stream, y, out, B, L, lengths, ceiling, sub, release, drive, gains);
+}
+
+int tvc_stream_limit_f32(tvc_ctx* ctx, void* stream, const float* y, float* out, int S, int block, int sub, int release, float drive_db, const float* ceiling,
+                         float* tail, float* peak, float* gain, float* reduction_db, float* gains) {
+    if (!ctx) return TVC_ERR_ARG;
+    char why[96];
+    if (limiter_geometry(block, sub, release, true, nullptr, nullptr, nullptr, why, sizeof(why)) != 0) return fail(ctx, TVC_ERR_ARG, "tvc_stream_limit_f32: %s", why);
+    if (!y || !out || !ceiling || !tail || !peak || !gain || S <= 0) return fail(ctx, TVC_ERR_ARG, "tvc_stream_limit_f32: bad argument (a NULL pointer or S <= 0)");
+    float drive = 1.f;
+    if (limiter_drive(drive_db, &drive, why, sizeof(why)) != 0) return fail(ctx, TVC_ERR_ARG, "tvc_stream_limit_f32: %s", why);
+    if (((uintptr_t)y | (uintptr_t)out | (uintptr_t)tail) & 15)
+        return fail(ctx, TVC_ERR_ARG, "tvc_stream_limit_f32: y, out and tail must be 16-byte aligned (they are read and written 16 bytes at a time)");
+    // an output sub-frame is the input sub-frame before it: an overlapping out would change samples that are still to be read
+    const uintptr_t bytes = (uintptr_t)S * (uintptr_t)block * sizeof(float), o = (uintptr_t)out;
+    if (o < (uintptr_t)y + bytes && (uintptr_t)y < o + bytes) return fail(ctx, TVC_ERR_ARG, "tvc_stream_limit_f32: out overlaps y");
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    StreamLimiter g;
+    g.block = block; g.sub = sub;
+    g.ceiling = ceiling; g.tail = tail; g.peak = peak; g.gain = gain; g.reduction_db = reduction_db;
+    return run_stream_limit(ctx, (hipStream_t)stream, y, out, S, g, release, drive, gains);
+}
+
 int tvc_stream_denoise_geometry(int block, int hop, int* frames, int* delay) { return stream_denoise_geometry(block, hop, frames, delay, nullptr, 0); }
 
 const char* tvc_stream_denoise_geometry_message(int block, int hop) {

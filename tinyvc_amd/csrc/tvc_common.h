@@ -542,6 +542,29 @@ int run_loudness_match(tvc_ctx*, hipStream_t, const float* x, const float* y, fl
                        int smooth, const LoudnessConst& c, float* gains);
 int run_stream_loudness(tvc_ctx*, hipStream_t, const float* x, int64_t n, int64_t base, const int32_t* shift, const float* y, float* out, int S,
                         const StreamLoudness& g, const LoudnessConst& c, float* gains);
+// the look-ahead peak limiter (limiter.hip).  kLimiterTile: the sub-frames one workgroup of the offline form owns (tvc_limiter_geometry reports
+// it); kLimiterEdges: the consecutive edges of a tile one of its 256 threads owns; kLimiterChunk: the sub-frames of a stream block whose
+// peaks and gains a workgroup keeps in LDS at a time (tvc_stream_limiter_geometry reports it)
+constexpr int kLimiterTile = 512, kLimiterEdges = (kLimiterTile + 1 + 255) / 256, kLimiterChunk = 512, kLimiterMaxRelease = 4096, kLimiterMaxSubFrame = 1 << 16;
+constexpr int kLimiterMaxBlock = 1 << 30;
+constexpr int64_t kLimiterMaxLength = (int64_t)1 << 40;
+struct StreamLimiter {
+    int block, sub;                 // samples, samples
+    const float* ceiling;           // [S] device, read when the kernel runs: linear; NaN, <= 0 and +inf are off
+    float* tail;                    // [S][sub] device state, read and advanced in place: the driven samples of the sub-frame not yet emitted,
+    float* peak;                    // [S] that sub-frame's peak,
+    float* gain;                    // [S] e at that sub-frame's start
+    float* reduction_db;            // [S] device, optional: 20 log10 of the block's smallest edge gain
+};
+// the legal geometries, in one place (limiter.hip): 0, or TVC_ERR_ARG with the reason in `why`; every out pointer is nullable.  stream_block:
+// `length` is a stream's block, and `tile` the chunk
+int limiter_geometry(int64_t length, int sub, int release, bool stream_block, int64_t* nsub, int* delay, int* tile, char* why, size_t why_bytes);
+// drive_db as the factor the kernels take: 0, or TVC_ERR_ARG with the reason in `why`
+int limiter_drive(float drive_db, float* drive, char* why, size_t why_bytes);
+// (the caller has checked the geometry, the alignment and that out lies apart from y; lengths [B] HOST, optional; gains optional)
+int run_limit(tvc_ctx*, hipStream_t, const float* y, float* out, int B, int64_t L, const int64_t* lengths, const float* ceiling, int sub, int release, float drive,
+              float* gains);
+int run_stream_limit(tvc_ctx*, hipStream_t, const float* y, float* out, int S, const StreamLimiter& g, int release, float drive, float* gains);
 // the spectral suppressor in front of the window (denoise.hip).  Frames of kDenoiseFrame samples at a hop of 160 or 320
 constexpr int kDenoiseFrame = 640, kDenoiseBins = kDenoiseFrame / 2 + 1, kDenoiseMaxFrames = 4096;
 struct StreamDenoise {

@@ -13,7 +13,7 @@ import weakref
 import torch
 
 from . import _lib, spec
-from .stream_state import DENOISE_STATE, GATE_STATE, LOUDNESS_STATE, TRACK_STATE, Field, checked
+from .stream_state import DENOISE_STATE, GATE_STATE, LIMITER_STATE, LOUDNESS_STATE, TRACK_STATE, Field, checked
 
 _F32 = torch.float32
 
@@ -201,6 +201,33 @@ def loudness_in_place(rows, device):
     another workgroup would be scaling), so it pays once the rows alone fill the device's compute units; below that a call into a tensor of
     its own, rows x tiles workgroups, is faster (64 x 4 s: 35 us against 154 us; one five-minute row: profiles/loudness_probe.json)"""
     return rows >= torch.cuda.get_device_properties(device).multi_processor_count
+
+
+def limiter_geometry(length, sub=24, release=100, stream_block=False, lib=None):
+    """tvc_limiter_geometry (no context, no device) -> (nsub, delay, tile) of a peak limiter over `length` samples in sub-frames of `sub`
+    samples with a release of `release` sub-frames: sub-frames, the delay of the stream form in samples (= sub), and the sub-frames a
+    workgroup of the offline form owns.  stream_block: `length` is a stream's block (tvc_stream_limiter_geometry; the third value is then
+    the chunk of sub-frames the stream kernel walks a block in).  ValueError, with the library's reason, for what the kernels do not take."""
+    if isinstance(length, bool) or not isinstance(length, numbers.Integral) or abs(length) >= (2 ** 31 if stream_block else 2 ** 63):
+        raise ValueError(f"limiter geometry: length must be an integer, got {length!r}")
+    vals = (int(length), integer(sub, "limiter geometry", "sub"), integer(release, "limiter geometry", "release"))
+    lib = lib if lib is not None else _lib.load_library()
+    nsub, delay, tile = (ctypes.c_int if stream_block else ctypes.c_int64)(), ctypes.c_int(), ctypes.c_int()
+    name = "tvc_stream_limiter_geometry" if stream_block else "tvc_limiter_geometry"
+    if getattr(lib, name)(*vals, ctypes.byref(nsub), ctypes.byref(delay), ctypes.byref(tile)) != 0:
+        raise ValueError(f"limiter geometry: {getattr(lib, name + '_message')(*vals).decode()}")
+    return nsub.value, delay.value, tile.value
+
+
+def limiter_drive(drive_db=0.0, what="limiter"):
+    """a limiter's drive_db as the fp32 value the library takes; ValueError for a drive that is not a finite number of dB within +-600 (the
+    library itself refuses only a factor 10^(drive_db / 20) that is not a positive finite fp32 number)"""
+    if isinstance(drive_db, bool) or not isinstance(drive_db, (int, float)) or not math.isfinite(drive_db):
+        raise ValueError(f"{what}: drive_db must be a finite number of dB, got {drive_db!r}")
+    v = ctypes.c_float(drive_db).value
+    if not math.isfinite(v) or abs(v) > 600.0:      # 10^(+-30) as an fp32 factor: far inside what the library takes
+        raise ValueError(f"{what}: drive_db = {drive_db!r} dB is outside -600 .. 600")
+    return v
 
 
 def pitch_class_table():
@@ -1126,6 +1153,52 @@ class Engine:
         gains = torch.empty(S, stage.block_size // sub + 1, dtype=_F32, device=self.device) if want_gains else None
         self._ok(self.lib.tvc_stream_loudness_f32(self.ctx, self._stream(), _ptr(x), n, int(base), _ptr(shift), _ptr(y), _ptr(out), S, stage.block_size, sub,
                                                   smooth, floor_db, boost_db, cut_db, *map(_ptr, state), _ptr(gains)), "tvc_stream_loudness_f32")
+        return (out, gains) if want_gains else out
+
+    def limit(self, y, ceiling, lengths=None, settings=None, want_gains=False):
+        """The look-ahead peak limiter (tvc_limit_f32; its definition is in tinyvc_hip.h): y [B, L] the waves, ceiling [B] fp32 on the device,
+        linear amplitudes read when the kernel runs (NaN, <= 0 and inf: off), `lengths` a ragged batch's row lengths (a sequence on the
+        host: they travel as kernel arguments, so the call stays asynchronous and capturable), `settings` anything with sub_frame, release
+        (sub-frames) and drive_db (a feature_retrieval.Limiter; None: the defaults).  Returns the limited waves, always a new tensor - no
+        sample of a row's own length lies above its ceiling -, and with want_gains the gain at every sub-frame edge, [B, L / sub_frame + 1]."""
+        _check_dev(y, "y", self.device)
+        if y.dim() != 2 or y.dtype != _F32 or not y.is_contiguous():
+            raise ValueError(f"limit: y must be contiguous fp32 [B, L], got {y.dtype} {tuple(y.shape)}")
+        B, L = y.shape
+        _check_dev(ceiling, "ceiling", self.device)
+        if ceiling.dtype != _F32 or tuple(ceiling.shape) != (B,) or not ceiling.is_contiguous():
+            raise ValueError(f"limit: ceiling must be contiguous fp32 [{B}], got {ceiling.dtype} {tuple(ceiling.shape)}")
+        sub, release, drive_db = (24, 100, 0.0) if settings is None else (settings.sub_frame, settings.release, settings.drive_db)
+        nsub = limiter_geometry(L, sub, release, lib=self.lib)[0]
+        drive_db = limiter_drive(drive_db, "limit")
+        lens = None
+        if lengths is not None:
+            vals = lengths.tolist() if isinstance(lengths, torch.Tensor) and lengths.device.type == "cpu" else lengths
+            if isinstance(vals, torch.Tensor) or len(vals) != B or any(isinstance(n, bool) or not isinstance(n, numbers.Integral) for n in vals):
+                raise ValueError(f"limit: lengths: a host sequence of one integer per row ({B}), got {lengths!r}")
+            lens = (ctypes.c_int64 * B)(*[int(n) for n in vals])      # (the kernel clamps them to 0 .. L and to whole sub-frames)
+        out = torch.empty_like(y)
+        gains = torch.empty(B, nsub + 1, dtype=_F32, device=self.device) if want_gains else None
+        self._ok(self.lib.tvc_limit_f32(self.ctx, self._stream(), _ptr(y), _ptr(out), B, L, lens, _ptr(ceiling), sub, release, drive_db, _ptr(gains)),
+                 "tvc_limit_f32")
+        return (out, gains) if want_gains else out
+
+    def stream_limit(self, y, stage, want_gains=False):
+        """The peak limiter at the end of a stream's block (tvc_stream_limit_f32): y [S, block] the blocks, `stage` a module.infer.StreamLimiter
+        (ceiling and state on the device, advanced in place).  Returns the limited blocks, a new tensor `stage.sub_frame` samples behind y -
+        the sub-frame held back is the stage's look-ahead -, and with want_gains the block's edge gains [S, block / sub_frame + 1]."""
+        _check_dev(y, "y", self.device)
+        if y.dim() != 2 or y.dtype != _F32 or not y.is_contiguous():
+            raise ValueError(f"stream_limit: y must be contiguous fp32 [S, block], got {y.dtype} {tuple(y.shape)}")
+        S = y.shape[0]
+        if tuple(y.shape) != (stage.n_streams, stage.block_size):
+            raise ValueError(f"stream_limit: a stage for {stage.n_streams} streams of {stage.block_size}-sample blocks, y is {tuple(y.shape)}")
+        state = checked(stage, LIMITER_STATE, S, self.device, "stream_limit: limiter.")
+        sub, release, drive_db = stage.params()[2:]
+        out = torch.empty_like(y)
+        gains = torch.empty(S, stage.block_size // sub + 1, dtype=_F32, device=self.device) if want_gains else None
+        self._ok(self.lib.tvc_stream_limit_f32(self.ctx, self._stream(), _ptr(y), _ptr(out), S, stage.block_size, sub, release, drive_db, *map(_ptr, state),
+                                               _ptr(gains)), "tvc_stream_limit_f32")
         return (out, gains) if want_gains else out
 
     def stream_denoise(self, blocks, denoise, out=None):

@@ -6,8 +6,9 @@ from .. import utils
 from ...engine import loudness_in_place, pitch_shifts
 from .._base import HipModule
 from ..tinyvc import Decoder, Encoder
-from ..tinyvc.feature_retrieval import (alpha_rows, check_blend, check_references, loudness_rows, prepare_reference, prepare_references, protect_rows,
-                                        resolve_alpha, resolve_auto_pitch, resolve_loudness, resolve_protect, target_form, target_registers)
+from ..tinyvc.feature_retrieval import (alpha_rows, check_blend, check_references, limit_rows, loudness_rows, prepare_reference, prepare_references,
+                                        protect_rows, resolve_alpha, resolve_auto_pitch, resolve_limit, resolve_loudness, resolve_protect, target_form,
+                                        target_registers)
 
 
 def _padded_lengths(lengths, B, L):
@@ -54,7 +55,7 @@ class Generator(HipModule):
 
     @torch.no_grad()
     def convert(self, wf, tgt, pitch_shift, f0_estimation="default", device=None, noise_angle=None, lengths=None, auto_pitch=None,
-                return_shift=False, track=None, alpha=None, protect=None, loudness=None):
+                return_shift=False, track=None, alpha=None, protect=None, loudness=None, limit=None):
         """generator.py:26-34: wf [B, L], tgt [1 or B, 768, N] -> converted waveform [B, L'] (L' = L
         padded to a multiple of 480).  `f0_estimation` / `device` are accepted and ignored exactly as
         in the reference.  `noise_angle` [B,961,T] (extension) injects the decoder's noise phases;
@@ -96,7 +97,12 @@ class Generator(HipModule):
         (engine.loudness_in_place).  A share in alpha's forms (a float in [0, 1], B of them, or an fp32 [B] / [1] device tensor, which the
         kernel clamps), or a feature_retrieval.LoudnessMatch with the settings (sub_frame must divide 480).  Every target form, with alpha,
         protect, auto_pitch, track and return_shift; 0 is the call without it bit for bit, None (the default) launch for launch.  The
-        settings' defaults are guesses: nobody has listened."""
+        settings' defaults are guesses: nobody has listened.
+        `limit` (extension): a look-ahead peak limiter behind everything else, loudness included: no sample of a row's own (padded) length
+        leaves above the ceiling, exactly.  One more launch (tvc_limit_f32) into a tensor of its own, with no host synchronisation and
+        capturable, equal and ragged batches alike.  A ceiling in dBFS (a number, or B of them; inf: off), an fp32 [B] / [1] device tensor
+        of LINEAR ceilings, or a feature_retrieval.Limiter with the settings (sub_frame must divide 480).  Every target form, with every
+        other keyword; None (the default) is the call without it, launch for launch.  The settings' defaults are guesses: nobody has listened."""
         # 1. classify the target once; malformed targets, registers and shift lists are refused before any engine or device work
         B = wf.shape[0] if wf.dim() == 2 else 1
         auto = auto_pitch is not None and auto_pitch is not False
@@ -122,6 +128,9 @@ class Generator(HipModule):
         level = resolve_loudness(loudness, B) if loudness is not None else None
         if level is not None and 480 % level[0].sub_frame:
             raise ValueError(f"loudness: sub_frame = {level[0].sub_frame} does not divide the 480-sample frames a call is padded to")
+        bound = resolve_limit(limit, B) if limit is not None else None
+        if bound is not None and 480 % bound[0].sub_frame:
+            raise ValueError(f"limit: sub_frame = {bound[0].sub_frame} does not divide the 480-sample frames a call is padded to")
         # 2. the inputs, on the device
         wf = utils.autopad_waveform(self._input_device(wf))
         eng = self.engine(wf.device)
@@ -159,5 +168,10 @@ class Generator(HipModule):
             wave = res[0] if isinstance(res, tuple) else res
             wave = eng.loudness_match(wf, wave, loudness_rows(level[1], B, wf.device), lengths=lens, settings=level[0],
                                       out=wave if loudness_in_place(B, wf.device) else None)
+            res = (wave,) + tuple(res[1:]) if isinstance(res, tuple) else wave
+        # 6. with limit, one launch behind that, into a tensor of its own (a tile reads its neighbours' samples: never in place)
+        if bound is not None:
+            wave = res[0] if isinstance(res, tuple) else res
+            wave = eng.limit(wave, limit_rows(bound[1], B, wf.device), lengths=lens, settings=bound[0])
             res = (wave,) + tuple(res[1:]) if isinstance(res, tuple) else wave
         return res

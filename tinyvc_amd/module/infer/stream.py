@@ -9,7 +9,8 @@ sides of the block: clients send and receive int16 at their own rates.  `StreamG
 one launch behind SOLA: it follows the input window's power under the emitted block and looks ahead in what the window already holds.
 `StreamDenoise` (extension) is a per-stream spectral suppressor on the device, one launch in front of the window: noise under speech is
 turned down before the converter, the pitch tracker and the gate see it.  `StreamLoudness` (extension) makes every emitted block follow the
-loudness envelope of the input it was converted from, one launch behind SOLA and in front of the gate."""
+loudness envelope of the input it was converted from, one launch behind SOLA and in front of the gate.  `StreamLimiter` (extension) is a
+look-ahead peak limiter, the last launch in front of the door's output side: no sample leaves above a stream's ceiling."""
 import math
 
 import numpy as np
@@ -17,9 +18,9 @@ import torch
 
 from ...engine import (SOLA_CROSS, SOLA_DELAY, SOLA_SEARCH, loudness_geometry, loudness_levels, pitch_shifts, sola_geometry, stream_denoise_geometry,
                        stream_gate_geometry, stream_resample_geometry)
-from ...stream_state import DENOISE_STATE, DOOR_STATE, GATE_STATE, LOUDNESS_STATE, TRACK_STATE, addresses, allocate, reset
-from ..tinyvc.feature_retrieval import (PitchTrack, alpha_rows, gpu_device, protect_rows, resolve_alpha, resolve_auto_pitch, resolve_protect,
-                                        target_form)
+from ...stream_state import DENOISE_STATE, DOOR_STATE, GATE_STATE, LIMITER_STATE, LOUDNESS_STATE, TRACK_STATE, addresses, allocate, reset
+from ..tinyvc.feature_retrieval import (PitchTrack, alpha_rows, gpu_device, limit_ceiling, limiter_settings, protect_rows, resolve_alpha,
+                                        resolve_auto_pitch, resolve_protect, target_form)
 from .generator import Generator
 
 
@@ -310,6 +311,66 @@ class StreamLoudness:
         reset(self, LOUDNESS_STATE, streams)
 
 
+DOOR_CEILING_DB = -0.001      # the highest ceiling a limiter in front of a door may take: the int16 conversion wraps above 32767 / 32768 (-0.000265 dB)
+
+
+class StreamLimiter:
+    """The look-ahead peak limiter of a set of streams that advance in lock step (tvc_stream_limit_f32; its definition is in tinyvc_hip.h):
+    the last stage of a block, behind the gate and in front of the door's output side.  A gain that falls at once, one sub-frame ahead of a
+    peak, and rises linearly over release_size keeps every sample at or below the stream's ceiling - exactly, not as a tuning claim.  The
+    stage holds one sub-frame back: it delays by `delay_size` = sub_frame samples.
+      ceiling [S]     fp32 on the device, a LINEAR amplitude read when a block runs (NaN, <= 0 and inf: off); `set_ceiling_db(x, streams)`
+                      converts dBFS on the host and copies, `stage.ceiling.fill_(...)` / `copy_(...)` takes linear values as they are
+      ceiling_db      the start: a number of dBFS or one per stream (inf: off)
+      sub_frame, release_size   24 kHz samples: the look-ahead and attack (a multiple of 4 that divides block_size; 24 = 1 ms), and the
+                      time a gain of 0 takes back to 1 (1 .. 4096 whole sub-frames)
+      drive_db        a gain in front of the limiter
+      tail [S, sub_frame], peak [S], gain [S] fp32     the state the next block starts from; reduction_db [S]: the last block's deepest gain in dB
+    Two limits of the guarantee.  A ceiling above 32767 / 32768 still wraps in a door's int16 conversion: streams with a door refuse a
+    ceiling_db above -0.001 dB (`max_ceiling_db`, which set_ceiling_db holds too; a linear value written into `ceiling` directly is the
+    caller's).  And a resampling door interpolates between samples and can overshoot the ceiling: the -1 dB default is margin, not proof.
+    The defaults are guesses: nobody has listened to them yet.  Every argument is checked before anything is allocated (ValueError)."""
+
+    def __init__(self, n_streams, block_size, ceiling_db=-1.0, sub_frame=24, release_size=2400, drive_db=0.0, device=None):
+        for x, name in ((n_streams, "n_streams"), (block_size, "block_size")):
+            if isinstance(x, bool) or not isinstance(x, int) or x < 1:
+                raise ValueError(f"StreamLimiter: {name} must be an integer >= 1, got {x!r}")
+        self.max_ceiling_db = None
+        rows_db, rows = self._ceilings(ceiling_db, n_streams)
+        self.sub_frame, self.release, self.drive_db = limiter_settings(sub_frame, release_size, drive_db, "StreamLimiter", block_size)
+        self.n_streams, self.block_size, self.release_size, self.delay_size = n_streams, block_size, int(release_size), self.sub_frame
+        self.device = gpu_device(device, "StreamLimiter: the ceilings and the state live on the GPU, where the stage's kernel runs")
+        self.ceiling = torch.tensor(rows, dtype=torch.float32, device=self.device)
+        self.ceiling_db = rows_db      # what the host last set, per stream: a value written into `ceiling` directly is not seen here
+        allocate(self, LIMITER_STATE, self.device)
+
+    def _ceilings(self, x, n):
+        """ceilings in dBFS as given - a number or n of them - -> (n values in dB, the same as linear amplitudes); ValueError"""
+        rows_db = _db_rows(x, n, f"StreamLimiter: ceiling_db must be a number of dBFS (inf: no limit) or one per stream ({n}), got {x!r}")
+        if self.max_ceiling_db is not None and max(rows_db) > self.max_ceiling_db:
+            raise ValueError(f"StreamLimiter: ceiling_db = {max(rows_db):g} is above {self.max_ceiling_db:g}: these streams end in a door, whose int16 "
+                             "conversion wraps every sample above 32767 / 32768")
+        return rows_db, [limit_ceiling(v, "StreamLimiter") for v in rows_db]
+
+    def set_ceiling_db(self, x, streams=None):
+        """Move the ceiling of every stream, or of the listed ones, to x dBFS (a number, or one per stream moved): converted to linear on the
+        host, in double, and copied in place, so it works between replays of a captured graph."""
+        idx = list(range(self.n_streams)) if streams is None else [int(i) for i in streams]
+        rows_db, rows = self._ceilings(x, len(idx))
+        self.ceiling.index_copy_(0, torch.as_tensor(idx, dtype=torch.int64, device=self.device), torch.tensor(rows, dtype=torch.float32, device=self.device))
+        for i, v in zip(idx, rows_db):
+            self.ceiling_db[i] = v
+
+    def params(self):
+        """the host values a captured block bakes in: (n_streams, block_size, sub_frame, release in sub-frames, drive_db)"""
+        return (self.n_streams, self.block_size, self.sub_frame, self.release, self.drive_db)
+
+    def reset(self, streams=None):
+        """Put every stream, or the listed ones, back at the start: nothing held back, gain 1.  The ceilings stay.  In-place ops on the
+        state tensors, so it works between replays of a captured graph."""
+        reset(self, LIMITER_STATE, streams)
+
+
 class BatchedStreamInfer:
     """`target`: one index for every stream ([1, 768, N]) or one per stream ([S, 768, N], or a list of S [1, 768, N_s] tensors), prepared
     once and cached on those tensors - or a feature_retrieval.Blend of several (its weights are read on the device when a block runs:
@@ -337,6 +398,10 @@ class BatchedStreamInfer:
     converted from, one launch behind SOLA and in front of the gate (and the door), driven by the input window and `last_shift` on the
     device; the SOLA buffer and the window stay as they are.  `loudness.share.fill_(...)` / `copy_(...)` and `loudness.reset(...)` between
     blocks keep a captured graph; None (the default) is the stream without it, launch for launch.
+    `limiter` (a StreamLimiter of the same n_streams and block_size): a look-ahead peak limiter, the last launch of a block - behind the gate,
+    in front of the door's output side -, so that nothing leaves above a stream's ceiling; it adds `limiter.delay_size` samples of latency,
+    and with a door it takes no ceiling above -0.001 dBFS.  `limiter.ceiling.fill_(...)`, `limiter.set_ceiling_db(...)` and
+    `limiter.reset(...)` between blocks keep a captured graph; None (the default) is the stream without it, launch for launch.
     `crossfade_size`, `sola_search_size`, `last_delay_size` (kept as the attribute `last_dilay_size`, the reference's spelling): the tail's
     geometry in 24 kHz samples, within engine.sola_geometry's limits; `latency_samples` / `latency_seconds` give the resulting range.  The
     attributes are plain, as in the reference: one changed after construction takes effect at the next init_buffer(), which checks them again
@@ -345,15 +410,16 @@ class BatchedStreamInfer:
     shorter than the three sizes say, and a look-ahead shorter than the pad is refused."""
 
     def __init__(self, generator: Generator, n_streams=1, target=None, pitch_shift=0., device=None,
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, denoise=None, loudness=None, gate=None, door=None,
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, denoise=None, loudness=None, gate=None, limiter=None, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         self.input_size, _ = check_window(block_size, extra_size, crossfade_size, sola_search_size, last_delay_size,
                                            auto_pitch is not None and auto_pitch is not False)
         share = resolve_alpha(alpha, n_streams) if alpha is not None else None      # refused here, before anything is allocated
         guard = resolve_protect(protect, n_streams) if protect is not None else None
         self.n_streams, self.block_size = n_streams, block_size
-        self.door, self.gate, self.denoise, self.loudness = (self._fits(name, stage) for name, stage in
-                                                             (("door", door), ("gate", gate), ("denoise", denoise), ("loudness", loudness)))
+        self.door, self.gate, self.denoise, self.loudness, self.limiter = (self._fits(name, stage) for name, stage in (
+            ("door", door), ("gate", gate), ("denoise", denoise), ("loudness", loudness), ("limiter", limiter)))
+        self._bound_ceiling()
         self.auto_pitch = auto_pitch if auto_pitch is not False else None
         self.pitch_track = pitch_track
         self._own_track = pitch_track is None
@@ -388,9 +454,9 @@ class BatchedStreamInfer:
         crossfade + delay .. crossfade + search + delay, by the lag the search picks, LESS the pad of a window that is not whole 480-sample
         frames (`pad_size`: convert pads the window at its end, the tail counts from the end of the padded conversion, so that much of the
         look-ahead is padding and the block leaves that much earlier), PLUS the suppressor's delay_size when there is one; the door's two
-        filters come on top in latency_seconds"""
+        and the limiter's; the door's two filters come on top in latency_seconds"""
         _, lo, hi = sola_geometry(self.block_size, self.crossfade_size, self.sola_search_size, self.last_dilay_size)
-        extra = self.denoise.delay_size if self.denoise is not None else 0
+        extra = sum(stage.delay_size for stage in (self.denoise, self.limiter) if stage is not None)
         return lo - self.pad_size + extra, hi - self.pad_size + extra
 
     @property
@@ -406,16 +472,25 @@ class BatchedStreamInfer:
         return lo / MODEL_RATE + extra, hi / MODEL_RATE + extra
 
     def _fits(self, name, stage):
-        """`stage` (a door, a gate, a suppressor, a loudness match, or None) when it was built for these streams; ValueError otherwise"""
+        """`stage` (a door, a gate, a suppressor, a loudness match, a limiter, or None) when it was built for these streams; ValueError otherwise"""
         if stage is not None and (stage.n_streams, stage.block_size) != (self.n_streams, self.block_size):
             raise ValueError(f"{name}: built for {stage.n_streams} streams of {stage.block_size}-sample blocks, the streams are "
                              f"{self.n_streams} of {self.block_size}")
         return stage
 
+    def _bound_ceiling(self):
+        """a limiter in front of a door: its ceilings stay at or below DOOR_CEILING_DB, now and in set_ceiling_db (ValueError)"""
+        if self.limiter is not None and self.door is not None:
+            if max(self.limiter.ceiling_db) > DOOR_CEILING_DB:
+                raise ValueError(f"limiter: ceiling_db = {max(self.limiter.ceiling_db):g} is above {DOOR_CEILING_DB:g}: the door's int16 conversion wraps every "
+                                 "sample above 32767 / 32768, so such a ceiling bounds nothing")
+            self.limiter.max_ceiling_db = DOOR_CEILING_DB
+
     def _stages(self):
         """the stages of these streams that keep state on the device, in block order: (name, stage, its table in stream_state)"""
         every = (("track", self.pitch_track if self.auto_pitch is not None else None, TRACK_STATE), ("door", self.door, DOOR_STATE),
-                 ("denoise", self.denoise, DENOISE_STATE), ("loudness", self.loudness, LOUDNESS_STATE), ("gate", self.gate, GATE_STATE))
+                 ("denoise", self.denoise, DENOISE_STATE), ("loudness", self.loudness, LOUDNESS_STATE), ("gate", self.gate, GATE_STATE),
+                 ("limiter", self.limiter, LIMITER_STATE))
         return [s for s in every if s[1] is not None]
 
     def init_buffer(self):
@@ -423,8 +498,9 @@ class BatchedStreamInfer:
         # and _step holds every later block against what was seen here
         self.input_size, _ = check_window(self.block_size, self.extra_size, self.crossfade_size, self.sola_search_size, self.last_dilay_size,
                                            self.auto_pitch is not None)
-        for name in ("door", "gate", "denoise", "loudness"):      # (before anything is allocated) the stages against the attributes as they stand now
+        for name in ("door", "gate", "denoise", "loudness", "limiter"):      # (before anything is allocated) the stages against the attributes as they stand now
             self._fits(name, getattr(self, name))
+        self._bound_ceiling()
         if self.gate is not None:
             check_gate_lookahead(self.gate.lookahead_size, self.crossfade_size, self.last_dilay_size, self.pad_size)
         self._geometry = self._attributes()
@@ -470,10 +546,12 @@ class BatchedStreamInfer:
             eng.stream_loudness(self.input_wav, out, shift, self.loudness, base, out=out)
         if self.gate is not None:
             eng.stream_gate(self.input_wav, out, shift, self.gate, base, out=out)
+        if self.limiter is not None:      # last: whatever the stages before it did to the level, nothing leaves above the ceiling
+            out = eng.stream_limit(out, self.limiter)
         return out, shift, pshift
 
     def _step_pcm(self, pcm, noise_angle):
-        # the whole block from client int16 to client int16: door in, _step (convert, SOLA, loudness, gate), door out
+        # the whole block from client int16 to client int16: door in, _step (convert, SOLA, loudness, gate, limiter), door out
         eng = self.generator.engine(self.device)
         out, shift, pshift = self._step(self.door.push(eng, pcm), noise_angle)
         return self.door.pull(eng, out), shift, pshift
@@ -482,7 +560,7 @@ class BatchedStreamInfer:
         """Everything a captured step bakes in as raw device pointers: the packed weights (re-packed - and the old arena
         freed - when a parameter changes), the engine's scratch workspace (re-allocated when another call needs a bigger
         one), the prepared index riding on `target`, plus the scalars captured by value.  Every stage present - the
-        tracker, the door, the suppressor (denoise), the loudness match, the gate - adds (its name, WHERE the tensors of its table in stream_state live, its
+        tracker, the door, the suppressor (denoise), the loudness match, the gate, the limiter - adds (its name, WHERE the tensors of its table in stream_state live, its
         params()): the table lists every tensor whose pointer reaches the library, so none can be passed on and left out here.  With
         auto_pitch also WHERE the target registers live, with alpha / protect where the shares live.  Never a value: the kernels read those at replay,
         so a reset(), registers.copy_(...), threshold_db.fill_(...) or a stream's history advancing keeps the graph.  The tail's geometry is
@@ -573,14 +651,14 @@ class StreamInfer(BatchedStreamInfer):
     """Single stream with the reference's constructor and 1-D buffers (stream.py:31-57)."""
 
     def __init__(self, generator: Generator, target=None, pitch_shift=0., device=torch.device("cpu"),
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, denoise=None, loudness=None, gate=None, door=None,
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, denoise=None, loudness=None, gate=None, limiter=None, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         dev = torch.device(device)
         if dev.type != "cuda":
             dev = generator._module_device()     # the reference defaults to CPU; there is no CPU path here
         super().__init__(generator, n_streams=1, target=target, pitch_shift=pitch_shift, device=dev, block_size=block_size, extra_size=extra_size,
                          use_phase_vocoder=use_phase_vocoder, f0_estimation=f0_estimation, use_graph=use_graph, alpha=alpha, protect=protect, denoise=denoise, gate=gate,
-                         door=door, crossfade_size=crossfade_size, sola_search_size=sola_search_size, last_delay_size=last_delay_size,
+                         limiter=limiter, door=door, crossfade_size=crossfade_size, sola_search_size=sola_search_size, last_delay_size=last_delay_size,
                          auto_pitch=auto_pitch, pitch_track=pitch_track, loudness=loudness)
 
     @torch.no_grad()

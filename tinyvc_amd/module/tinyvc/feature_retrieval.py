@@ -8,7 +8,7 @@ import sys
 import torch
 
 from ... import spec, stream_state
-from ...engine import default_engine, integer, loudness_geometry, loudness_levels
+from ...engine import default_engine, integer, limiter_drive, limiter_geometry, loudness_geometry, loudness_levels
 
 
 def prepare_reference(reference):
@@ -316,6 +316,82 @@ def loudness_keywords(args, script):
         sys.exit(f"{script}: --loudness must be a share in 0 .. 1")
     print(f"Following {e:g} of the source's loudness envelope (loudness; rms mix rate {1 - e:g})")
     return {"loudness": float(e)}
+
+
+def limit_ceiling(db, what="limit"):
+    """a ceiling in dBFS as the linear amplitude the limiter's kernels read: 10^(db / 20), the one place it is computed - in double, on
+    the host; the device never takes a power of ten of it.  +inf is off (inf).  ValueError for anything that is no number of dB in
+    -600 .. 600 or +inf."""
+    if isinstance(db, bool) or not isinstance(db, (int, float)) or not (db == math.inf or -600.0 <= db <= 600.0):
+        raise ValueError(f"{what}: a ceiling is a number of dBFS in -600 .. 600, or inf for none; got {db!r}")
+    return math.inf if db == math.inf else 10.0 ** (float(db) / 20.0)
+
+
+class Limiter:
+    """convert's limit - the look-ahead peak limiter behind everything else (tvc_limit_f32; the definition is in include/tinyvc_hip.h): no
+    sample of the result lies above the ceiling, exactly.  The gain falls at once, one sub-frame ahead of a peak, and rises linearly.
+      ceiling_db    dBFS: a number, B numbers (inf: off), or an fp32 [B] / [1] device tensor of LINEAR ceilings ([B]: used in place, read
+                    when the kernel runs; NaN, <= 0 and inf are off)
+      sub_frame     24 kHz samples, a multiple of 4 (convert: a divisor of 480): the look-ahead and the attack; 24 = 1 ms
+      release_size  24 kHz samples, 1 .. 4096 whole sub-frames: the time a gain of 0 takes back to 1
+      drive_db      a gain in front of the limiter
+    The defaults are guesses: nobody has listened to them yet.  The settings are checked here and the ceiling in resolve_limit
+    (ValueError), before any engine work."""
+
+    def __init__(self, ceiling_db=-1.0, sub_frame=24, release_size=2400, drive_db=0.0):
+        self.sub_frame, self.release, self.drive_db = limiter_settings(sub_frame, release_size, drive_db, "limit")
+        self.ceiling_db, self.release_size = ceiling_db, int(release_size)
+
+
+def limiter_settings(sub_frame, release_size, drive_db, what, block_size=None):
+    """a limiter's host settings, checked by the library's own rule -> (sub_frame, release in sub-frames, drive_db as fp32); `block_size`:
+    a stream's block.  ValueError naming `what`."""
+    try:
+        sub_frame, release_size = integer(sub_frame, "limiter geometry", "sub"), integer(release_size, "limiter geometry", "release_size")
+        limiter_geometry(sub_frame, sub_frame, 1)      # the limits of sub_frame itself
+        if release_size % sub_frame:
+            raise ValueError(f"release_size = {release_size} is not a whole number of {sub_frame}-sample sub-frames")
+        limiter_geometry(sub_frame if block_size is None else block_size, sub_frame, release_size // sub_frame, stream_block=block_size is not None)
+    except ValueError as e:
+        raise ValueError(f"{what}: {e}") from None
+    return sub_frame, release_size // sub_frame, limiter_drive(drive_db, what)
+
+
+def resolve_limit(limit, B):
+    """convert's limit as given - a Limiter, or a bare ceiling (Limiter(ceiling)) - checked on the host (no engine, no device work) ->
+    (settings, ceiling): the Limiter and its ceiling as a list of B LINEAR floats or the device tensor (linear already).  The ceiling takes
+    alpha's forms by alpha's code; the dB to linear conversion happens here, once.  ValueError naming limit."""
+    settings = limit if isinstance(limit, Limiter) else Limiter(limit)
+    ceiling = resolve_alpha(settings.ceiling_db, B, "limit")
+    if not isinstance(ceiling, torch.Tensor):
+        ceiling = [limit_ceiling(x) for x in ceiling]
+    return settings, ceiling
+
+
+def limit_rows(resolved, B, device):
+    return alpha_rows(resolved, B, device, "limit")
+
+
+def add_limit_argument(parser):
+    """`--limit [DB]` for the entry scripts' parsers: absent (None) is the run without it, bare is -1 dBFS"""
+    parser.add_argument("--limit", type=float, nargs="?", const=-1.0, default=None, metavar="DB",
+                        help="hold every output sample at or below this ceiling (dBFS; bare: -1) with a look-ahead peak limiter on the device, "
+                             "1 ms ahead of a peak, behind everything else.  The defaults behind it are guesses: nobody has listened.  default: "
+                             "absent, the output is not bounded")
+
+
+def limit_keywords(args, script):
+    """what `--limit` adds to the script's convert call: nothing when it is absent (the call is today's), else {"limit": DB} and one
+    printed line; a value that is no ceiling ends the script"""
+    db = getattr(args, "limit", None)
+    if db is None:
+        return {}
+    try:
+        c = limit_ceiling(db, "--limit")
+    except ValueError as e:
+        sys.exit(f"{script}: {e}")
+    print(f"Limiting peaks to {db:g} dBFS ({c:.6g} of full scale; 1 ms look-ahead)")
+    return {"limit": float(db)}
 
 
 def add_alpha_argument(parser):

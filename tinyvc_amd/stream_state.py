@@ -20,6 +20,8 @@ GATE_STATE = (Field("threshold_db", _F32, (), None), Field("open", _I32, (), 1),
 TRACK_STATE = (Field("ring", _F32, "window_frames", 0.0), Field("count", torch.int64, (), 0), Field("auto", _F32, (), 0.0))
 LOUDNESS_STATE = (Field("share", _F32, (), None), Field("src_ring", torch.float64, "window", 0.0), Field("out_ring", torch.float64, "window", 0.0),
                   Field("frames", torch.int64, (), 0), Field("gain", _F32, (), 1.0), Field("gain_db", _F32, (), 0.0))
+LIMITER_STATE = (Field("ceiling", _F32, (), None), Field("tail", _F32, "sub_frame", 0.0), Field("peak", _F32, (), 0.0), Field("gain", _F32, (), 1.0),
+                 Field("reduction_db", _F32, (), 0.0))
 
 
 def _shape(stage, field, S):
