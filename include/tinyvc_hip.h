@@ -537,6 +537,74 @@ int tvc_knn_match_protect_f32(tvc_ctx* ctx, void* stream, const float* src, cons
 int tvc_frame_share_f32(tvc_ctx* ctx, void* stream, const float* f0, const int64_t* row_start, const int64_t* row_count, int rows,
                         const float* alpha, const float* protect, float* share_out);
 
+/* the pitch path: a Viterbi decode of the pitch logits ------------------------------------------------------------------------ */
+/* tvc_pitch_decode_f32 decodes every frame on its own: the four largest logits need not be neighbours (mass split between a class and the
+ * class an octave above leaves at 1.5 times the pitch), class 0 (unvoiced, 0 Hz) in the four drags a frame down, and nothing ties frame t to
+ * frame t - 1.  The pitch path is the decode every neural pitch tracker offers for this (CREPE's viterbi): the best sequence of classes under
+ * a cost for moving.  It takes the per-frame decode's place when a call asks for it; without it every call is what it was.
+ * It runs over ONE utterance of T frames (a ragged batch: the utterance's own T_b frames; a stream: the window's frames) and never crosses
+ * rows.  Settings, a HOST struct (the values travel as kernel arguments and are baked into a capture):
+ *   step >= 0, finite        cost per class of distance inside the band
+ *   band W, 0 .. 32          classes a voiced frame may move at `step` each (48 classes are one octave)
+ *   jump >= W * step         cost of any longer move between voiced classes; +inf is allowed
+ *   voicing >= 0             cost of a move between class 0 and a voiced class; +inf is allowed
+ *   refine r, 0 .. 4         the frequency is a local expectation over the classes within r of the path's
+ * Everything is fp32 and every operation is rounded on its own (no fused multiply-add).  x = the logit of class j at frame t:
+ *   - emission e_t[j] = x clamped to [-1e30, 1e30], NaN -> -1e30: everything stays finite.
+ *   - cost(i, j) = 0 for i = j = 0; voicing when exactly one of i, j is 0; (float)|i - j| * step when both are >= 1 and |i - j| <= W; jump when
+ *     both are >= 1 and further apart.
+ *   - u_0[j] = e_0[j].  For every t: m_t = max_j u_t[j], s_t[j] = u_t[j] - m_t (the normalisation keeps a five-minute row at full precision).
+ *   - t >= 1: cand(i -> j) = s_{t-1}[i] - cost(i, j); best_t[j] = max_i cand; bp_t[j] = the LOWEST i that attains it; u_t[j] = best_t[j] + e_t[j].
+ *   - path[T-1] = the lowest argmax of s_{T-1}; path[t-1] = bp_t[path[t]].
+ *   - frequency, c = path[t]: c = 0 gives f0[t] = 0.  Otherwise, over the window j in [max(1, c - r), min(511, c + r)]: d_j = e_t[j] - (the
+ *     window's maximum) - the clamped emission, so the frequency is finite too -, w_j = (float)exp((double)d_j) (tvc_pitch_decode_f32's exp),
+ *     den = the sum of w_j in ascending j, f0[t] = sum_j (w_j / den) * freq[j] in ascending j - quotient, product and sum rounded separately -,
+ *     then tvc_pitch_decode_f32's `<= 20 -> 0` gate.  r = 0 gives freq[c] exactly.
+ *   - step = jump = voicing = 0 is the per-frame argmax, lowest class on equal logits.
+ * jump >= W * step is what lets the kernel take the far candidates from ONE per-frame reduction - the maximum, and its lowest class, of
+ * s[i] - jump over the voiced classes: rounding is monotone, so a class inside the band never does better by the jump route, and the
+ * lowest-class rule survives when the two results are combined as `min` on equal values (tests/helpers_pitch_path.py holds both forms equal).
+ * TVC_PITCH_PATH_DEFAULT: step 0.5, band 12, jump 12, voicing 3, refine 2 - 48 classes per octave and 20 ms frames make the band 3 semitones
+ * per frame.  THESE ARE GUESSES: nobody has listened to any setting.
+ * Kernel: one workgroup of 512 threads per utterance, two barriers per frame, uint16 back-pointers [columns][512] in workspace, the walk back
+ * and the frequencies in the same launch; no floating-point atomics, no host synchronisation; rows of 1 frame and of 15 000 take one path.
+ * tvc_pitch_path_f32, the stage call: row i = columns [row_start[i], row_start[i] + row_count[i]) (HOST arrays of `rows` entries, ascending
+ * and apart, ends below 2^31; an empty row writes nothing; columns outside every row are not written).  class_stride S: class j of column n
+ * lies at logits[(n / S) * 512 * S + j * S + n % S] - an equal batch [B][512][T] has S = T, a packed ragged [512][Ttot] has S = Ttot - and no
+ * row straddles a multiple of S.  pitch_shift, or pitch_shifts (HOST, one per row), is the shift of f0_shifted.  Outputs (device, each may
+ * be NULL, not all): f0 and f0_shifted (one per column), path_out (int32, one per column), score_out [rows][512] = s_{T-1} (an empty row's is
+ * not written).  Workspace: tvc_workspace_bytes_pitch_path (1 KiB per column up to the last row's end).
+ * tvc_convert_path_f32 / tvc_convert_ragged_path_f32: the protect entries' arguments plus `path` behind protect.  path == NULL is the protect
+ * call, launch for launch and bit for bit.  With it the call keeps the encoder's logits, runs the path kernel directly behind the encoder (one
+ * launch per 256 utterances) and everything that reads f0 - the voicing weight of protect, the automatic shift, a tracker, the shift, the
+ * decoder - reads the path's.  Workspace: tvc_workspace_bytes_path / _ragged_path (enough with or without any of the optional arguments). */
+typedef struct tvc_pitch_path {
+    float step;
+    int32_t band;
+    float jump;
+    float voicing;
+    int32_t refine;
+} tvc_pitch_path;
+#define TVC_PITCH_PATH_DEFAULT {0.5f, 12, 12.0f, 3.0f, 2}
+#define TVC_PITCH_PATH_MAX_BAND 32
+#define TVC_PITCH_PATH_MAX_REFINE 4
+int tvc_workspace_bytes_pitch_path(tvc_ctx* ctx, const int64_t* row_start, const int64_t* row_count, int rows, size_t* out_bytes);
+int tvc_pitch_path_f32(tvc_ctx* ctx, void* stream, const float* logits, const int64_t* row_start, const int64_t* row_count, int rows,
+                       int64_t class_stride, const tvc_pitch_path* path, float pitch_shift, const float* pitch_shifts, float* f0,
+                       float* f0_shifted, int32_t* path_out, float* score_out, void* ws, size_t ws_bytes);
+int tvc_workspace_bytes_path(tvc_ctx* ctx, int B, int64_t L, const int64_t* N, int M, size_t* out_bytes);
+int tvc_convert_path_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M,
+                         const float* weights, const float* alpha, const float* protect, const tvc_pitch_path* path, const float* target_f0,
+                         int start, int n, int W, int min_voiced, float slew, float* ring, int64_t* count, float* auto_shift,
+                         float pitch_shift, const float* pitch_shifts, float* shift_out, const float* noise_angle, uint64_t seed,
+                         float* wave, int B, int64_t L, void* ws, size_t ws_bytes);
+int tvc_workspace_bytes_ragged_path(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, const int64_t* N, int M, size_t* out_bytes);
+int tvc_convert_ragged_path_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens,
+                                const float* const* prepared, const int64_t* N, int M, const float* weights, const float* alpha,
+                                const float* protect, const tvc_pitch_path* path, const float* target_f0, float pitch_shift,
+                                const float* pitch_shifts, float* shift_out, const float* noise_angle, uint64_t seed, float* wave, int B,
+                                void* ws, size_t ws_bytes);
+
 /* streaming tail-------------------------------------------------------------------------- */
 /* StreamInfer.audio_callback after convert (reference module/infer/stream.py:74-95), batched over
  * S streams: y [S, Ly] converted buffers; sola_buf [S,1920] in/out; fade_in [1920] = the sin^2

@@ -39,8 +39,9 @@ from tinyvc_amd import audio_io, parallel, spec
 from tinyvc_amd.engine import limiter_geometry, loudness_geometry
 from tinyvc_amd.module.infer import Generator
 from tinyvc_amd.module.tinyvc import Blend, Decoder, Encoder
-from tinyvc_amd.module.tinyvc.feature_retrieval import (add_alpha_argument, add_auto_pitch_argument, add_blend_argument, add_limit_argument, add_loudness_argument,
-                                                        alpha_keywords, attach_register, limit_keywords, loudness_keywords, pitch_register)
+from tinyvc_amd.module.tinyvc.feature_retrieval import (PitchPath, add_alpha_argument, add_auto_pitch_argument, add_blend_argument, add_f0_arguments,
+                                                        add_limit_argument, add_loudness_argument, alpha_keywords, attach_register, f0_keywords,
+                                                        limit_keywords, loudness_keywords, pitch_register)
 
 SAMPLE_RATE = 24000
 
@@ -51,7 +52,7 @@ def build_parser():
     p.add_argument("-o", "--outputs", default="./outputs/")
     p.add_argument("-encp", "--encoder-path", default="./models/encoder.pt")
     p.add_argument("-decp", "--decoder-path", default="./models/decoder.pt")
-    p.add_argument("-f0-est", "--f0-estimation", default="default")
+    add_f0_arguments(p)             # -f0-est NAME: `viterbi` decodes pitch as one path (--f0-step --f0-band --f0-jump --f0-voicing --f0-refine); any other name is ignored
     p.add_argument("-idx", "--index", default="NONE")
     p.add_argument("-t", "--target", default="target.wav")
     add_blend_argument(p)      # --blend PATH=W [PATH=W ...] -> args.blend = (paths, weights)
@@ -192,6 +193,9 @@ def main(argv=None, world=None, rank=None, local_rank=None):
             sys.exit(f"infer.py: --auto-pitch: no pitch register beside {args.index} (extract_index.py writes <index>.f0.pt)")
         auto = True
     alpha_kw = alpha_keywords(args, "infer.py")      # {} without --alpha / --protect: every call below is then the call it has always been
+    f0_est = f0_keywords(args, "infer.py")
+    if isinstance(f0_est, PitchPath):      # likewise -f0-est viterbi; every other name stays out of the calls, as it always has
+        alpha_kw["f0_estimation"] = f0_est
     alpha_kw.update(loudness_keywords(args, "infer.py"))      # likewise --loudness
     if "loudness" in alpha_kw and args.chunked and not args.no_chunking:      # a stream's stage works on whole 10 ms sub-frames of a block
         try:

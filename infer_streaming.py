@@ -71,8 +71,8 @@ from infer import load_generator, load_target
 from tinyvc_amd.engine import limiter_drive, limiter_geometry, loudness_geometry, loudness_levels, sola_geometry, stream_denoise_geometry, stream_gate_geometry, stream_resample_geometry
 from tinyvc_amd.module.infer import BatchedStreamInfer, StreamDenoise, StreamDoor, StreamGate, StreamLimiter, StreamLoudness
 from tinyvc_amd.module.infer.stream import DOOR_CEILING_DB, check_gate_lookahead, check_window, denoise_constants
-from tinyvc_amd.module.tinyvc.feature_retrieval import (PitchTrack, add_alpha_argument, add_blend_argument, alpha_keywords, pitch_register,
-                                                        semitones_between)
+from tinyvc_amd.module.tinyvc.feature_retrieval import (PitchTrack, add_alpha_argument, add_blend_argument, add_f0_arguments, alpha_keywords, f0_keywords,
+                                                        pitch_register, semitones_between)
 
 FRAMES_PER_SECOND = 50      # 24 kHz / 480 samples
 GATE_SUB_FRAME = 240        # the gate's sub-frame: 10 ms at 24 kHz
@@ -109,7 +109,7 @@ def build_parser():
     p.add_argument("-sr", "--sample-rate", default=24000, type=int)
     p.add_argument("-ig", "--input-gain", default=0, type=float)
     p.add_argument("-og", "--output-gain", default=0, type=float)
-    p.add_argument("-f0-est", "--f0-estimation", default="default", choices=["default", "fcpe", "dio", "harvest"])
+    add_f0_arguments(p, choices=["default", "fcpe", "dio", "harvest", "viterbi"])      # viterbi: each window's pitch as one path (--f0-step .. --f0-refine)
     p.add_argument("--resample", action="store_true",
                    help="run the device (or file) at -sr and resample every block to the model's 24 kHz and back on the GPU; -c counts samples at -sr, "
                         "-ig / -og are applied by the same kernels")
@@ -406,7 +406,7 @@ def main(argv=None):
         print(f"Peak limiter at {limit_kw['ceiling_db']:g} dBFS: drive {stage.drive_db:g} dB (-og), look-ahead and attack {stage.sub_frame / 24:g} ms, release "
               f"{stage.release_size / 24:g} ms")
     stream = BatchedStreamInfer(gen, n_streams=S, pitch_shift=pitch_shift, block_size=door.block_size, device=device, extra_size=args.extra,
-                                f0_estimation=args.f0_estimation, door=door, auto_pitch=True if track is not None else None, pitch_track=track,
+                                f0_estimation=f0_keywords(args, "infer_streaming.py"), door=door, auto_pitch=True if track is not None else None, pitch_track=track,
                                 crossfade_size=args.crossfade, sola_search_size=args.sola_search, last_delay_size=args.lookahead, gate=gate, denoise=denoise, **alpha_kw)
     lo, hi = stream.latency_seconds
     delay = f" + the suppressor's {denoise.delay_size}" if denoise is not None else ""

@@ -12,6 +12,12 @@ LIB_PATH = os.environ.get("TVC_LIB_PATH") or os.path.join(_HERE, "libtinyvc_hip.
 
 _lib = None
 
+
+class PitchPathSettings(ctypes.Structure):
+    """tvc_pitch_path of include/tinyvc_hip.h: the host settings of the pitch path"""
+    _fields_ = [("step", c_float), ("band", c_int32), ("jump", c_float), ("voicing", c_float), ("refine", c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/tinyvc_hip.h one to one
 SIGNATURES = {
     "tvc_version": (c_int, []),
@@ -103,6 +109,17 @@ SIGNATURES = {
     "tvc_knn_match_protect_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_int64), c_int, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t]),
     "tvc_frame_share_f32": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int64), c_int, c_void_p, c_void_p, c_void_p]),
+    "tvc_workspace_bytes_pitch_path": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64), c_int, POINTER(c_size_t)]),
+    "tvc_pitch_path_f32": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int64), c_int, c_int64, POINTER(PitchPathSettings), c_float,
+                                   POINTER(c_float), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "tvc_workspace_bytes_path": (c_int, [c_void_p, c_int, c_int64, POINTER(c_int64), c_int, POINTER(c_size_t)]),
+    "tvc_convert_path_f32": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_int64), c_int, c_void_p, c_void_p, c_void_p,
+                                     POINTER(PitchPathSettings), c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_float,
+                                     POINTER(c_float), c_void_p, c_void_p, c_uint64, c_void_p, c_int, c_int64, c_void_p, c_size_t]),
+    "tvc_workspace_bytes_ragged_path": (c_int, [c_void_p, c_int, c_int64, POINTER(c_int64), POINTER(c_int64), c_int, POINTER(c_size_t)]),
+    "tvc_convert_ragged_path_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64), POINTER(c_void_p), POINTER(c_int64), c_int, c_void_p,
+                                            c_void_p, c_void_p, POINTER(PitchPathSettings), c_void_p, c_float, POINTER(c_float), c_void_p, c_void_p, c_uint64,
+                                            c_void_p, c_int, c_void_p, c_size_t]),
     "tvc_ctx_set_index_assign_chunk":(c_int, [c_void_p, c_int]),
     "tvc_workspace_bytes_index_compact": (c_int, [c_void_p, c_int64, c_int64, POINTER(c_size_t)]),
     "tvc_index_assign_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),

@@ -269,7 +269,20 @@ int tvc::convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const ConvertCall& c)
     ws.release(m);
     {
         ProfScope ps(ctx, s, ws, "encoder");
-        TVC_CHECK(run_encoder(ctx, s, ws, spec, ssl, f0, nullptr, B, T, spec_bound, enc_slots, auto_pitch ? nullptr : f0s, c.shift, rshift));
+        // A path call (c.path) keeps the logits and decodes them again over each utterance as a whole (run_pitch_path: one workgroup per
+        // utterance, its back-pointers in workspace that goes back with the encoder's): f0, and f0s unless a register decides the shift, are
+        // the path's from here on - the tracker, the register, protect's voicing weight and the decoder read nothing else.
+        float* lgt = c.path ? ws.get<float>((size_t)B * kPitchClasses * T) : nullptr;
+        uint16_t* bp = c.path ? ws.get<uint16_t>((size_t)B * T * kPitchClasses) : nullptr;
+        TVC_CHECK(run_encoder(ctx, s, ws, spec, ssl, f0, lgt, B, T, spec_bound, enc_slots, auto_pitch || c.path ? nullptr : f0s, c.shift, rshift));
+        if (c.path && !ws.dry) {
+            std::vector<PitchPathRow> rows((size_t)NB);
+            for (int i = 0; i < NB; ++i) {
+                const int r = ctx->rag ? ctx->rag->row[i] : i;
+                rows[i] = PitchPathRow{ctx->rag ? ctx->rag->pre[i] : i * T, ctx->rag ? ctx->rag->tb[i] : T, ix.per_row && c.shifts ? c.shifts[r] : c.shift};
+            }
+            TVC_CHECK(run_pitch_path(ctx, s, lgt, T, rows, *c.path, bp, f0, auto_pitch ? nullptr : f0s, nullptr, nullptr));
+        }
         if (c.track && !ws.dry) {      // one workgroup per stream: its history's register, the slew-limited shift, its shifted f0 (no workspace)
             TVC_CHECK(run_pitch_track(ctx, s, f0, B, T, *c.track, c.target_f0, c.shift, c.shifts, nullptr, nullptr, c.shift_out, f0s));
         } else if (auto_pitch && !ws.dry) {      // one workgroup per utterance: its register, its shift (offset = the host value), its shifted f0
@@ -617,7 +630,7 @@ static int convert_entry(tvc_ctx* ctx, void* stream, const ConvertCall& c, bool 
 // table (it takes workspace; never read in this walk): a call whose rows share blobs, or without per-row shifts, needs less.
 // (No allocation depends on whether the call brings its own noise phases.)
 static int convert_query(tvc_ctx* ctx, int B, int64_t L, const int64_t* lens, bool ragged, const ConvertIndex& ix, size_t* out_bytes, const char* what,
-                         bool auto_pitch = false, bool alpha = false, bool protect = false) {
+                         bool auto_pitch = false, bool alpha = false, bool protect = false, bool path = false) {
     TVC_CHECK(need_ready(ctx, NEED_NONE));
     if (!out_bytes || (ragged && !lens) || (ix.per_row ? !ix.Ns : ix.N < 4) || B <= 0 || L <= 0 || L % kHop != 0)
         return fail(ctx, TVC_ERR_ARG, "%s: need B>0, %s%%480==0, %s%s", what, ragged ? "Lmax" : "L", ragged && ix.per_row ? "lens[B], " : "", ix.per_row ? "N[B]" : "N>=4");
@@ -639,6 +652,8 @@ static int convert_query(tvc_ctx* ctx, int B, int64_t L, const int64_t* lens, bo
     c.target_f0 = auto_pitch ? kDryPtr : nullptr;
     c.alpha = alpha ? kDryPtr : nullptr;
     c.protect = protect ? kDryPtr : nullptr;
+    const tvc_pitch_path any_path = TVC_PITCH_PATH_DEFAULT;      // the settings take no part in the sizes
+    c.path = path ? &any_path : nullptr;
     if (!ragged) return measure(1, out_bytes, [&](Ws& ws) { return convert_impl(ctx, nullptr, ws, c); });
     std::vector<RagBatchPlan> batches;
     TVC_CHECK(ragged_split(ctx, ctx->rag_batch_frames, B, L, lens, &batches));
@@ -867,7 +882,7 @@ int tvc_knn_match_blend_f32(tvc_ctx* ctx, void* stream, const float* src, const 
 // The table form of the auto entries plus `alpha` (device, one fp32 per row); alpha == NULL is the sibling call.  One ConvertCall field and one
 // argument of the kNN drivers: no second path.
 static int alpha_query(tvc_ctx* ctx, int B, int64_t L, const int64_t* lens, bool ragged, const int64_t* N, int M, size_t* out_bytes, const char* what,
-                       bool protect = false) {
+                       bool protect = false, bool path = false) {
     if (!ctx) return TVC_ERR_ARG;
     TVC_CHECK(blend_check(ctx, B, M, kDryPtr, what));
     size_t most = 0;
@@ -875,7 +890,7 @@ static int alpha_query(tvc_ctx* ctx, int B, int64_t L, const int64_t* lens, bool
         for (int table = 0; table < (M == 1 ? 2 : 1); ++table) {
             size_t bytes = 0;
             TVC_CHECK(convert_query(ctx, B, L, lens, ragged, table ? ConvertIndex::table(nullptr, N) : ConvertIndex::blend(nullptr, N, M, nullptr), &bytes, what,
-                                    auto_pitch != 0, true, protect));
+                                    auto_pitch != 0, true, protect, path));
             if (bytes > most) most = bytes;
         }
     *out_bytes = most;
@@ -887,16 +902,26 @@ int tvc_workspace_bytes_alpha(tvc_ctx* ctx, int B, int64_t L, const int64_t* N, 
 int tvc_workspace_bytes_ragged_alpha(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, const int64_t* N, int M, size_t* out_bytes) {
     return alpha_query(ctx, B, Lmax, lens, true, N, M, out_bytes, "tvc_workspace_bytes_ragged_alpha");
 }
-// the alpha and the protect entries share their bodies: protect == nullptr is the alpha call, under the entry's own name `what`
+// a call's path settings (nullable: no path), refused under the entry's own name `what` before any device work
+static int path_check(tvc_ctx* ctx, const tvc_pitch_path* path, const char* what) {
+    char why[96];
+    if (path && pitch_path_check(*path, why, sizeof(why)) != 0) return fail(ctx, TVC_ERR_ARG, "%s: path: %s", what, why);
+    return 0;
+}
+// the alpha, the protect and the path entries share their bodies: protect == nullptr is the alpha call, path == nullptr the protect call, under
+// the entry's own name `what`
 static int convert_alpha(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M, const float* weights,
                          const float* alpha, const float* protect, const float* target_f0, int start, int n, int W, int min_voiced, float slew, float* ring,
                          int64_t* count, float* auto_shift, float pitch_shift, const float* pitch_shifts, float* shift_out, const float* noise_angle,
-                         uint64_t seed, float* wave, int B, int64_t L, void* wsp, size_t ws_bytes, const char* what) {
+                         uint64_t seed, float* wave, int B, int64_t L, void* wsp, size_t ws_bytes, const char* what, const tvc_pitch_path* path = nullptr) {
+    if (!ctx) return TVC_ERR_ARG;
+    TVC_CHECK(path_check(ctx, path, what));
     ConvertIndex ix;
     TVC_CHECK(auto_index(ctx, B, prepared, N, M, weights, &ix, what));
     ConvertCall c{wav, wave, B, L, nullptr, ix, pitch_shift, pitch_shifts, noise_angle, seed, target_f0, target_f0 ? shift_out : nullptr};
     c.alpha = alpha;
     c.protect = protect;
+    c.path = path;
     const PitchTrackState t{start, n, W, min_voiced, slew, ring, count, auto_shift};
     if (ring) {      // a tracker: tvc_convert_track_f32's checks
         if (L <= 0 || L / kHop > 0x7fffffff) return fail(ctx, TVC_ERR_ARG, "%s: bad argument (L must be a positive multiple of 480)", what);
@@ -908,12 +933,15 @@ static int convert_alpha(tvc_ctx* ctx, void* stream, const float* wav, const flo
 static int convert_ragged_alpha(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens, const float* const* prepared,
                                 const int64_t* N, int M, const float* weights, const float* alpha, const float* protect, const float* target_f0,
                                 float pitch_shift, const float* pitch_shifts, float* shift_out, const float* noise_angle, uint64_t seed, float* wave, int B,
-                                void* wsp, size_t ws_bytes, const char* what) {
+                                void* wsp, size_t ws_bytes, const char* what, const tvc_pitch_path* path = nullptr) {
+    if (!ctx) return TVC_ERR_ARG;
+    TVC_CHECK(path_check(ctx, path, what));
     ConvertIndex ix;
     TVC_CHECK(auto_index(ctx, B, prepared, N, M, weights, &ix, what));
     ConvertCall c{wav, wave, B, Lmax, lens, ix, pitch_shift, pitch_shifts, noise_angle, seed, target_f0, target_f0 ? shift_out : nullptr};
     c.alpha = alpha;
     c.protect = protect;
+    c.path = path;
     return convert_entry(ctx, stream, c, true, wsp, ws_bytes, what);
 }
 static int match_alpha(tvc_ctx* ctx, void* stream, const float* src, const float* f0, const float* const* prepared, const int64_t* N, int M,
@@ -972,6 +1000,71 @@ int tvc_knn_match_protect_f32(tvc_ctx* ctx, void* stream, const float* src, cons
                               const float* weights, const float* alpha, const float* protect, float* out, int64_t* idx_out, int B, int T, void* wsp,
                               size_t ws_bytes) {
     return match_alpha(ctx, stream, src, f0, prepared, N, M, weights, alpha, protect, out, idx_out, B, T, wsp, ws_bytes, "tvc_knn_match_protect_f32");
+}
+
+// ---- the pitch path: the protect entries with the Viterbi decode of the call's own logits in the per-frame decode's place ------------------
+// `path` (host settings) behind protect; path == NULL is the protect call, launch for launch.
+int tvc_workspace_bytes_path(tvc_ctx* ctx, int B, int64_t L, const int64_t* N, int M, size_t* out_bytes) {
+    return alpha_query(ctx, B, L, nullptr, false, N, M, out_bytes, "tvc_workspace_bytes_path", true, true);
+}
+int tvc_workspace_bytes_ragged_path(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, const int64_t* N, int M, size_t* out_bytes) {
+    return alpha_query(ctx, B, Lmax, lens, true, N, M, out_bytes, "tvc_workspace_bytes_ragged_path", true, true);
+}
+int tvc_convert_path_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M, const float* weights,
+                         const float* alpha, const float* protect, const tvc_pitch_path* path, const float* target_f0, int start, int n, int W,
+                         int min_voiced, float slew, float* ring, int64_t* count, float* auto_shift, float pitch_shift, const float* pitch_shifts,
+                         float* shift_out, const float* noise_angle, uint64_t seed, float* wave, int B, int64_t L, void* wsp, size_t ws_bytes) {
+    return convert_alpha(ctx, stream, wav, prepared, N, M, weights, alpha, protect, target_f0, start, n, W, min_voiced, slew, ring, count, auto_shift, pitch_shift,
+                         pitch_shifts, shift_out, noise_angle, seed, wave, B, L, wsp, ws_bytes, "tvc_convert_path_f32", path);
+}
+int tvc_convert_ragged_path_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens, const float* const* prepared,
+                                const int64_t* N, int M, const float* weights, const float* alpha, const float* protect, const tvc_pitch_path* path,
+                                const float* target_f0, float pitch_shift, const float* pitch_shifts, float* shift_out, const float* noise_angle,
+                                uint64_t seed, float* wave, int B, void* wsp, size_t ws_bytes) {
+    return convert_ragged_alpha(ctx, stream, wav, Lmax, lens, prepared, N, M, weights, alpha, protect, target_f0, pitch_shift, pitch_shifts, shift_out, noise_angle,
+                                seed, wave, B, wsp, ws_bytes, "tvc_convert_ragged_path_f32", path);
+}
+// the stage call's rows, checked on the host: ascending, apart, inside 32-bit indexing and inside one run of class_stride columns each
+static int path_rows(tvc_ctx* ctx, const int64_t* row_start, const int64_t* row_count, int rows, int64_t S, int64_t* span, const char* what) {
+    if (!row_start || !row_count || rows <= 0) return fail(ctx, TVC_ERR_ARG, "%s: bad argument (row_start, row_count and rows > 0)", what);
+    int64_t end = 0;
+    for (int b = 0; b < rows; ++b) {
+        if (row_start[b] < end || row_count[b] < 0 || row_start[b] + row_count[b] > 0x7fffffff)
+            return fail(ctx, TVC_ERR_ARG, "%s: row %d = [%lld, +%lld) must begin at or behind the row before it and end below 2^31", what, b, (long long)row_start[b],
+                        (long long)row_count[b]);
+        if (S > 0 && row_count[b] > 0 && row_start[b] / S != (row_start[b] + row_count[b] - 1) / S)
+            return fail(ctx, TVC_ERR_ARG, "%s: row %d = [%lld, +%lld) straddles a multiple of class_stride = %lld", what, b, (long long)row_start[b],
+                        (long long)row_count[b], (long long)S);
+        end = row_start[b] + row_count[b];
+    }
+    *span = end;
+    return 0;
+}
+int tvc_workspace_bytes_pitch_path(tvc_ctx* ctx, const int64_t* row_start, const int64_t* row_count, int rows, size_t* out_bytes) {
+    if (!ctx) return TVC_ERR_ARG;
+    int64_t span = 0;
+    if (!out_bytes) return fail(ctx, TVC_ERR_ARG, "tvc_workspace_bytes_pitch_path: bad argument");
+    TVC_CHECK(path_rows(ctx, row_start, row_count, rows, 0, &span, "tvc_workspace_bytes_pitch_path"));
+    return measure(1, out_bytes, [&](Ws& ws) { ws.get<uint16_t>(pitch_path_ws_bytes(span) / sizeof(uint16_t)); return 0; });
+}
+int tvc_pitch_path_f32(tvc_ctx* ctx, void* stream, const float* logits, const int64_t* row_start, const int64_t* row_count, int rows, int64_t class_stride,
+                       const tvc_pitch_path* path, float pitch_shift, const float* pitch_shifts, float* f0, float* f0_shifted, int32_t* path_out,
+                       float* score_out, void* wsp, size_t ws_bytes) {
+    const char* what = "tvc_pitch_path_f32";
+    if (!ctx) return TVC_ERR_ARG;
+    if (!logits || !path || class_stride <= 0 || class_stride > 0x7fffffff || (!f0 && !f0_shifted && !path_out && !score_out))
+        return fail(ctx, TVC_ERR_ARG, "%s: bad argument (logits, path, 0 < class_stride < 2^31 and at least one output)", what);
+    TVC_CHECK(path_check(ctx, path, what));
+    int64_t span = 0;
+    TVC_CHECK(path_rows(ctx, row_start, row_count, rows, class_stride, &span, what));
+    std::vector<PitchPathRow> rw((size_t)rows);
+    for (int b = 0; b < rows; ++b) rw[b] = PitchPathRow{(int)row_start[b], (int)row_count[b], pitch_shifts ? pitch_shifts[b] : pitch_shift};
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    return run_walks(ctx, what, wsp, ws_bytes, 1, [&](Ws& ws) {
+        uint16_t* bp = ws.get<uint16_t>(pitch_path_ws_bytes(span) / sizeof(uint16_t));
+        if (ws.dry) return 0;
+        return run_pitch_path(ctx, (hipStream_t)stream, logits, (long)class_stride, rw, *path, bp, f0, f0_shifted, path_out, score_out);
+    });
 }
 int tvc_frame_share_f32(tvc_ctx* ctx, void* stream, const float* f0, const int64_t* row_start, const int64_t* row_count, int rows, const float* alpha,
                         const float* protect, float* share_out) {

@@ -431,6 +431,9 @@ struct ConvertCall {
     // tvc_convert_*protect_f32: protect (device, one fp32 per caller's row; alpha may then be nullptr = 0) raises the share on unvoiced frames of
     // the f0 this call decodes - a_t = a + (1 - a) * (p * w[t]), one per query column (run_frame_share) in the place of the row's alpha
     const float* protect = nullptr;
+    // tvc_convert_*path_f32: path (host settings) puts the Viterbi decode of the call's own logits (run_pitch_path, directly behind the encoder) in
+    // the place of the per-frame decode: protect's voicing weight, the automatic shift, a tracker, the shift and the decoder read its f0
+    const tvc_pitch_path* path = nullptr;
 };
 // Generator.convert over c.B rows of c.L samples (c.lens is not looked at: a ragged call reaches this through convert_ragged_batches,
 // one batch at a time as ONE row with ctx->rag set, ragged.h)
@@ -460,6 +463,19 @@ int run_pitch_match(tvc_ctx*, hipStream_t, const float* f0, const std::vector<Pi
 // shift_out and f0s are optional.  One launch (one per 512 streams with per-stream offsets), no workspace.
 int run_pitch_track(tvc_ctx*, hipStream_t, const float* f0, int S, int T, const PitchTrackState& t, const float* target, float offset,
                     const float* offsets, float* median_out, int64_t* count_out, float* shift_out, float* f0s);
+// The pitch path (pitch_path.hip; include/tinyvc_hip.h has the definition): a Viterbi decode of rows of logits.  Row i = columns [start, start +
+// len) with `shift` the semitones of its f0s; class k of column n lies at logits[(n / S) * 512 * S + k * S + n % S] and no row straddles a
+// multiple of S; bp = 512 uint16 per column up to the last row's end (pitch_path_ws_bytes); f0, f0s, path_out, score_out [rows][512] optional.
+// One launch per 256 rows.  The caller has checked the settings (pitch_path_check: 0, or TVC_ERR_ARG with the reason in `why`).
+constexpr int kPitchPathMaxBand = TVC_PITCH_PATH_MAX_BAND, kPitchPathMaxRefine = TVC_PITCH_PATH_MAX_REFINE;
+struct PitchPathRow {
+    int start, len;
+    float shift;
+};
+size_t pitch_path_ws_bytes(int64_t columns);
+int pitch_path_check(const tvc_pitch_path& p, char* why, size_t why_bytes);
+int run_pitch_path(tvc_ctx*, hipStream_t, const float* logits, long S, const std::vector<PitchPathRow>& rows, const tvc_pitch_path& p, uint16_t* bp, float* f0,
+                   float* f0s, int* path_out, float* score_out);
 int run_uniform_to_angle(tvc_ctx*, hipStream_t, float* u, int64_t n);
 // content_bound (optional): an upper bound of |content| (the prepared index's |max| when content came out of the kNN match): ONE float, or
 // with content_bound_stride = 1 one per utterance (a match against one index per utterance);

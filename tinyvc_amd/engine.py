@@ -96,8 +96,17 @@ _PROTECT = {
 }
 
 
+# form "path": the protect rows' conversions with the pitch path's settings behind protect - (ragged,)
+_PATH = {
+    False: ("tvc_workspace_bytes_path", "tvc_convert_path_f32"),
+    True: ("tvc_workspace_bytes_ragged_path", "tvc_convert_ragged_path_f32"),
+}
+
+
 def _names(form, ragged=None):
     """(workspace query, entry) of a conversion (`ragged` a bool) or a match (None) from the tables above"""
+    if form == "path":
+        return _PATH[ragged]
     if form == "protect":
         return _PROTECT["match" if ragged is None else ragged]
     return _MATCH[form] if ragged is None else _CONVERT[form, ragged]
@@ -553,13 +562,13 @@ class Engine:
     def _index_args(self, form, prepared, Ns, weights, B):
         """The index of a call, checked on the host -> (what the entry takes for it, what its workspace query takes for it).  shared:
         (prepared, Ns) = one blob and its N; table: one blob and N per row; blend: weights [B, M] on the device, prepared / Ns row-major
-        [B * M]; auto, track, alpha, protect: the blend form, or with weights None the table form as M = 1."""
+        [B * M]; auto, track, alpha, protect, path: the blend form, or with weights None the table form as M = 1."""
         if form == "shared":
             return (_ptr(prepared), Ns), (int(max(Ns, 4)),)
         if form == "table":
             blobs, ns = self._table(prepared, Ns, B)
             return (blobs, ns), (ns,)
-        if form in ("auto", "track", "alpha", "protect") and weights is None:
+        if form in ("auto", "track", "alpha", "protect", "path") and weights is None:
             blobs, ns = self._table(prepared, Ns, B)
             return (blobs, ns, 1, None), (ns, 1)
         blobs, ns, M = self._blend_args(prepared, Ns, weights, B)
@@ -660,12 +669,14 @@ class Engine:
         return (start, n, track.window_frames, track.min_voiced, track.slew, *map(_ptr, state))
 
     def _convert(self, form, wav, prepared, Ns, pitch_shift, noise_angle=None, lengths=None, weights=None, target_f0=None, out=None, shift_out=None,
-                 track=None, alpha=None, protect=None):
+                 track=None, alpha=None, protect=None, path=None):
         """wav [B, L] converted toward the index (`form`, prepared, Ns, weights: _index_args) -> wave [B, L]; form "auto" / "track" ->
         (wave, shifts [B]).  "track": "auto" with the register taken from `track` (a PitchTrack: the streams' history), equal lengths only.
         "alpha": the table / blend call keeping the share alpha[b] of row b's own content features (alpha: _per_row); with target_f0 it is the
         "auto" call (-> (wave, shifts)), with `track` as well the "track" call.  "protect": the "alpha" call with protect[b] (_per_row) behind
         alpha, which may then be None (a = 0): the share rises to a + (1 - a) * protect[b] on the unvoiced frames of the f0 the call decodes.
+        "path": the "protect" call (alpha and protect may both be None) with `path`, a PitchPath, behind protect: f0 is the Viterbi decode of the
+        call's own logits over each utterance, and everything behind the encoder reads that one.
         lengths: a ragged batch (row b holds an utterance of lengths[b] samples, a multiple of 480, zero-padded behind it; every utterance
         is converted over its OWN length).  pitch_shift: a float, or one per row for every form but "shared".  Every host check comes
         first, then the noise draw (which advances torch's generator), then device work: a refused call leaves no trace."""
@@ -676,14 +687,17 @@ class Engine:
         if ragged and (form == "track" or track is not None):
             raise ValueError("track: streams advance in lock step, there is no ragged form")
         found = form in ("auto", "track")      # the shifts are found on the device: pitch_shift is the offset, the applied shifts come back
-        if form in ("alpha", "protect"):      # the table / blend call with or without target registers (and, equal lengths, a tracker), plus the source's share
+        if form in ("alpha", "protect", "path"):      # the table / blend call with or without target registers (and, equal lengths, a tracker), plus the source's share
             found = target_f0 is not None
             if track is not None and not found:
                 raise ValueError("track needs target_f0: the tracker finds the register the automatic shift starts from")
             if form == "alpha":
                 index += (_ptr(self._per_row(alpha, "alpha", B)),)
-            else:
+            elif form == "protect":
                 index += (_ptr(self._per_row(alpha, "alpha", B)) if alpha is not None else None, _ptr(self._per_row(protect, "protect", B)))
+            else:
+                index += (_ptr(self._per_row(alpha, "alpha", B)) if alpha is not None else None,
+                          _ptr(self._per_row(protect, "protect", B)) if protect is not None else None, ctypes.byref(path.settings()))
             index += (_ptr(self._per_row(target_f0, "target_f0", B)) if found else None,)
             if not ragged:
                 index += self._track_args(track, B, L // spec.HOP) if track is not None else (0, 0, 0, 0, 0.0, None, None, None)
@@ -700,7 +714,7 @@ class Engine:
         if found:
             sh = shift_out if shift_out is not None else torch.empty(B, dtype=_F32, device=self.device)
             shift_args += (_ptr(sh),)
-        elif form in ("alpha", "protect"):
+        elif form in ("alpha", "protect", "path"):
             shift_args += (None,)
         query, entry = _names(form, ragged)
         p, n = self._query_ws(query, B, L, *lens, *sized)
@@ -741,6 +755,39 @@ class Engine:
     def convert_ragged_auto(self, wav, lengths, prepared, Ns, target_f0, pitch_shift=0.0, weights=None, noise_angle=None):
         """convert_auto over a ragged batch (every utterance's register is the median over its OWN frames): tvc_convert_ragged_auto_f32."""
         return self._convert("auto", wav, prepared, Ns, pitch_shift, noise_angle, lengths, weights, target_f0)
+
+    # ---- the pitch path: a Viterbi decode of rows of logits (tvc_pitch_path_f32) ----
+    def pitch_path(self, logits, settings, row_start=None, pitch_shift=0.0, want_shifted=False):
+        """The pitch path of rows of logits (include/tinyvc_hip.h has the definition; `settings` a PitchPath): logits [B, 512, T] (every row
+        a run of T columns), or a packed [512, Ttot] / [1, 512, Ttot] with row_start = rows + 1 ascending column numbers (row b =
+        columns [row_start[b], row_start[b + 1])) -> (f0 [B, 1, T] or [1, 1, Ttot] fp32, path int32 of f0's shape, scores [rows, 512] = the
+        last frame's normalised scores[, f0 shifted by pitch_shift - a float or one per row - when want_shifted]).  Columns outside every
+        row are 0."""
+        lg = _prep(logits, "logits", self.device)
+        if lg.dim() == 2:
+            lg = lg[None]
+        if lg.dim() != 3 or lg.shape[1] != spec.PITCH_CLASSES or lg.shape[2] < 1:
+            raise ValueError(f"pitch_path: logits [B, {spec.PITCH_CLASSES}, T] or a packed [{spec.PITCH_CLASSES}, Ttot], got {tuple(lg.shape)}")
+        B, _, T = lg.shape
+        if row_start is None:
+            row_start = [b * T for b in range(B + 1)]
+        elif B != 1:
+            raise ValueError("pitch_path: row_start goes with a packed [512, Ttot]")
+        row_start = [int(x) for x in row_start]
+        rows = len(row_start) - 1
+        if rows < 1 or row_start[0] < 0 or row_start[-1] > B * T or any(a > b for a, b in zip(row_start, row_start[1:])):
+            raise ValueError(f"pitch_path: row_start must be rows + 1 ascending column numbers within the {B * T} columns of logits")
+        shift, shifts = pitch_shifts(pitch_shift, rows)
+        I64 = ctypes.c_int64 * rows
+        start, count = I64(*row_start[:-1]), I64(*(b - a for a, b in zip(row_start, row_start[1:])))
+        f0 = torch.zeros(B, 1, T, dtype=_F32, device=self.device)
+        path = torch.zeros(B, 1, T, dtype=torch.int32, device=self.device)
+        scores = torch.zeros(rows, spec.PITCH_CLASSES, dtype=_F32, device=self.device)
+        out = torch.zeros_like(f0) if want_shifted else None
+        p, n = self._query_ws("tvc_workspace_bytes_pitch_path", start, count, rows)
+        self._ok(self.lib.tvc_pitch_path_f32(self.ctx, self._stream(), _ptr(lg), start, count, rows, T, ctypes.byref(settings.settings()), shift, _floats(shifts),
+                                             _ptr(f0), _ptr(out), _ptr(path), _ptr(scores), p, n), "tvc_pitch_path_f32")
+        return (f0, path, scores, out) if want_shifted else (f0, path, scores)
 
     # ---- the pitch register of rows of f0, and the shift onto a target's (tvc_pitch_match_f32) ----
     def pitch_match(self, f0, row_start=None, target_f0=None, pitch_shift=0.0, want_shifted=False):

@@ -7,8 +7,8 @@ from ...engine import loudness_in_place, pitch_shifts
 from .._base import HipModule
 from ..tinyvc import Decoder, Encoder
 from ..tinyvc.feature_retrieval import (alpha_rows, check_blend, check_references, limit_rows, loudness_rows, prepare_reference, prepare_references,
-                                        protect_rows, resolve_alpha, resolve_auto_pitch, resolve_limit, resolve_loudness, resolve_protect, target_form,
-                                        target_registers)
+                                        protect_rows, resolve_alpha, resolve_auto_pitch, resolve_f0_estimation, resolve_limit, resolve_loudness,
+                                        resolve_protect, target_form, target_registers)
 
 
 def _padded_lengths(lengths, B, L):
@@ -58,7 +58,11 @@ class Generator(HipModule):
                 return_shift=False, track=None, alpha=None, protect=None, loudness=None, limit=None):
         """generator.py:26-34: wf [B, L], tgt [1 or B, 768, N] -> converted waveform [B, L'] (L' = L
         padded to a multiple of 480).  `f0_estimation` / `device` are accepted and ignored exactly as
-        in the reference.  `noise_angle` [B,961,T] (extension) injects the decoder's noise phases;
+        in the reference - but for `f0_estimation='viterbi'` or a feature_retrieval.PitchPath (extension): f0 is then the pitch path, a
+        Viterbi decode of the call's own pitch logits over each utterance as a whole (a ragged batch: each utterance's own frames) in the place
+        of the per-frame top-4 expectation, inside the same call (tvc_convert_path_f32 / tvc_convert_ragged_path_f32: one more launch directly
+        behind the encoder), and protect's voicing, auto_pitch, track, the shift and the decoder read that f0.  Every target form, equal and
+        ragged, with every other keyword.  'viterbi' is PitchPath() with its defaults, which are guesses: nobody has listened.  `noise_angle` [B,961,T] (extension) injects the decoder's noise phases;
         by default the library draws them itself (seeded from torch's generator: Decoder.draw_noise_angle).
         `lengths` (extension): a RAGGED batch - row b of wf holds an utterance of lengths[b] samples, zero-padded behind it.
         Every utterance is converted over its own length (padded to a multiple of 480), exactly as if it were converted
@@ -125,6 +129,7 @@ class Generator(HipModule):
         shift, shifts = pitch_shifts(pitch_shift, B)
         share = resolve_alpha(alpha, B) if alpha is not None else None
         guard = resolve_protect(protect, B) if protect is not None else None
+        path = resolve_f0_estimation(f0_estimation)      # 'viterbi' or a PitchPath; every other name is None: the call it has always been
         level = resolve_loudness(loudness, B) if loudness is not None else None
         if level is not None and 480 % level[0].sub_frame:
             raise ValueError(f"loudness: sub_frame = {level[0].sub_frame} does not divide the 480-sample frames a call is padded to")
@@ -146,15 +151,17 @@ class Generator(HipModule):
             blobs, ns = prepare_references([self._input_device(t) for t in tgt] if isinstance(tgt, (list, tuple)) else self._input_device(tgt))
         else:
             blobs, ns = prepare_reference(self._input_device(tgt))
-            if auto or shifts is not None or share is not None or guard is not None:      # a value per row (given, or found on the device): the shared blob in every row (one segment)
+            if auto or shifts is not None or share is not None or guard is not None or path is not None:      # a value per row (given, or found on the device): the shared blob in every row (one segment)
                 form, blobs, ns = "table", [blobs] * B, [ns] * B
         # 4. one engine call
         pitch = shift if shifts is None else shifts
-        if share is not None or guard is not None:      # the alpha / protect entry covers every case below: plain shifts, target registers, a tracker
+        if share is not None or guard is not None or path is not None:      # the alpha / protect / path entry covers every case below: plain shifts, target registers, a tracker
             rows = {"alpha": alpha_rows(share, B, wf.device) if share is not None else None}
             if guard is not None:
                 rows["protect"] = protect_rows(guard, B, wf.device)
-            res = eng._convert("alpha" if guard is None else "protect", wf, blobs, ns, pitch, noise_angle, lens, w,
+            if path is not None:
+                rows["path"] = path
+            res = eng._convert("path" if path is not None else "alpha" if guard is None else "protect", wf, blobs, ns, pitch, noise_angle, lens, w,
                                target_registers(regs, B, wf.device) if auto else None, track=track, **rows)
             res = res if return_shift or not auto else res[0]
         elif not auto:

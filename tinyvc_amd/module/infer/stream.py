@@ -20,7 +20,7 @@ from ...engine import (SOLA_CROSS, SOLA_DELAY, SOLA_SEARCH, loudness_geometry, l
                        stream_gate_geometry, stream_resample_geometry)
 from ...stream_state import DENOISE_STATE, DOOR_STATE, GATE_STATE, LIMITER_STATE, LOUDNESS_STATE, TRACK_STATE, addresses, allocate, reset
 from ..tinyvc.feature_retrieval import (PitchTrack, alpha_rows, gpu_device, limit_ceiling, limiter_settings, protect_rows, resolve_alpha,
-                                        resolve_auto_pitch, resolve_protect, target_form)
+                                        resolve_auto_pitch, resolve_f0_estimation, resolve_protect, target_form)
 from .generator import Generator
 
 
@@ -385,6 +385,9 @@ class BatchedStreamInfer:
     `protect` (convert's, in alpha's forms; the keyword behind alpha): how far that share rises on the unvoiced frames of each window's own f0, held as
     `self.protect`, a [S] device tensor like `self.alpha` (`stream.protect.fill_(...)` / `copy_(...)` replay the same graph); with or without
     alpha; None (the default) is the stream as it was.
+    `f0_estimation` (convert's): 'viterbi' or a feature_retrieval.PitchPath decodes every window's pitch as one path over its own frames
+    (each window afresh: no state travels from block to block, the window's left context is what steadies the emitted frames); held as
+    `self.f0_estimation`, and its settings - host values baked into the launch - are part of the graph key.  Every other name is ignored.
     `door` (a StreamDoor of the same n_streams and block_size): audio_callback_pcm takes the clients' int16 blocks at the door's rates.
     `gate` (a StreamGate of the same n_streams and block_size): every emitted block goes through the noise gate, one launch behind SOLA (and
     in front of the door), driven by the input window and `last_shift` on the device; the SOLA buffer and the window stay ungated.
@@ -581,6 +584,9 @@ class BatchedStreamInfer:
             tkey += (("alpha", self.alpha.data_ptr()),)
         if self.protect is not None:
             tkey += (("protect", self.protect.data_ptr()),)
+        path = resolve_f0_estimation(self.f0_estimation)
+        if path is not None:      # the pitch path's settings ARE values: host numbers baked into the launch, so another PitchPath is another graph
+            tkey += (("f0_estimation", path.params()),)
         return (eng.weights_key, ws.data_ptr() if ws is not None else 0, ws.numel() if ws is not None else 0,
                 tuple((id(t), t._version, t.data_ptr()) for t in tgts), wkey, shifts, bool(self.use_phase_vocoder),
                 (self.crossfade_size, self.sola_search_size, self.last_dilay_size)) + tkey

@@ -1,6 +1,7 @@
 """kNN-VC feature matching (reference module/tinyvc/feature_retrieval.py:15-33) on the streamed
 top-k kernel of csrc/knn.hip."""
 import collections
+import ctypes
 import math
 import os
 import sys
@@ -8,6 +9,7 @@ import sys
 import torch
 
 from ... import spec, stream_state
+from ..._lib import PitchPathSettings
 from ...engine import default_engine, integer, limiter_drive, limiter_geometry, loudness_geometry, loudness_levels
 
 
@@ -392,6 +394,92 @@ def limit_keywords(args, script):
         sys.exit(f"{script}: {e}")
     print(f"Limiting peaks to {db:g} dBFS ({c:.6g} of full scale; 1 ms look-ahead)")
     return {"limit": float(db)}
+
+
+def _f32(x):
+    return ctypes.c_float(x).value
+
+
+class PitchPath:
+    """convert's f0_estimation='viterbi' - the pitch path, a Viterbi decode of the call's own pitch logits over each utterance as a whole in
+    the place of the per-frame top-4 expectation (tvc_pitch_path_f32 and the *_path_f32 conversions; the definition is in
+    include/tinyvc_hip.h).  Host values, baked into a captured graph:
+      step      cost per class of distance inside the band (>= 0, finite)
+      band      classes a voiced frame may move at `step` each, 0 .. 32 (48 classes are one octave, a frame is 20 ms)
+      jump      cost of any longer move between voiced classes (>= band * step; inf allowed)
+      voicing   cost of a move between unvoiced (class 0) and voiced (>= 0; inf allowed)
+      refine    the frequency is a local expectation over the classes within `refine` of the path's, 0 .. 4 (0: the class frequency itself)
+    The defaults are guesses: nobody has listened to them yet.  Checked here (ValueError), by the library's own rule on the fp32 values,
+    before any engine work."""
+    MAX_BAND, MAX_REFINE = 32, 4
+
+    def __init__(self, step=0.5, band=12, jump=12.0, voicing=3.0, refine=2):
+        for name, x in (("step", step), ("jump", jump), ("voicing", voicing)):
+            if isinstance(x, bool) or not isinstance(x, (int, float)) or math.isnan(x):
+                raise ValueError(f"f0_estimation: {name} must be a number, got {x!r}")
+        band, refine = integer(band, "f0_estimation", "band"), integer(refine, "f0_estimation", "refine")
+        step, jump, voicing = _f32(step), _f32(jump), _f32(voicing)
+        if not (0.0 <= step < math.inf):
+            raise ValueError(f"f0_estimation: step must be finite and >= 0, got {step!r}")
+        if not 0 <= band <= self.MAX_BAND:
+            raise ValueError(f"f0_estimation: band must lie in 0 .. {self.MAX_BAND}, got {band}")
+        if not jump >= _f32(band * step):
+            raise ValueError(f"f0_estimation: jump must be >= band * step = {_f32(band * step):g} (inf is allowed), got {jump!r}")
+        if not voicing >= 0.0:
+            raise ValueError(f"f0_estimation: voicing must be >= 0 (inf is allowed), got {voicing!r}")
+        if not 0 <= refine <= self.MAX_REFINE:
+            raise ValueError(f"f0_estimation: refine must lie in 0 .. {self.MAX_REFINE}, got {refine}")
+        self.step, self.band, self.jump, self.voicing, self.refine = step, band, jump, voicing, refine
+
+    def params(self):
+        """the five settings as a tuple: what a captured graph has baked in"""
+        return (self.step, self.band, self.jump, self.voicing, self.refine)
+
+    def settings(self):
+        """the tvc_pitch_path struct the library takes"""
+        return PitchPathSettings(*self.params())
+
+    def __repr__(self):
+        return "PitchPath(step={}, band={}, jump={}, voicing={}, refine={})".format(*self.params())
+
+
+def resolve_f0_estimation(f0_estimation):
+    """convert's f0_estimation: 'viterbi' -> PitchPath() with the defaults, a PitchPath -> itself, anything else (the reference's 'default',
+    'fcpe', 'dio', 'harvest', ...) -> None: accepted and ignored exactly as in the reference"""
+    if isinstance(f0_estimation, PitchPath):
+        return f0_estimation
+    return PitchPath() if isinstance(f0_estimation, str) and f0_estimation == "viterbi" else None
+
+
+def add_f0_arguments(parser, choices=None):
+    """`-f0-est` and the pitch path's five settings for the entry scripts' parsers.  `choices`: the script's own list of accepted names"""
+    kw = {"choices": choices} if choices is not None else {}
+    parser.add_argument("-f0-est", "--f0-estimation", default="default",
+                        help="viterbi: decode the pitch logits as one path over each utterance (a stream: each window) instead of frame by "
+                             "frame; every other name is accepted and ignored, as in the reference", **kw)
+    for flag, typ, what in (("--f0-step", float, "cost per class of distance inside the band (default 0.5)"),
+                            ("--f0-band", int, "classes a voiced frame may move at that cost, 0 .. 32; 48 are one octave (default 12)"),
+                            ("--f0-jump", float, "cost of any longer move between voiced classes, >= band * step (default 12)"),
+                            ("--f0-voicing", float, "cost of a move between unvoiced and voiced (default 3)"),
+                            ("--f0-refine", int, "classes on each side of the path's that share the frequency, 0 .. 4 (default 2)")):
+        parser.add_argument(flag, type=typ, default=None, help=f"-f0-est viterbi: {what}.  The defaults are guesses: nobody has listened")
+
+
+def f0_keywords(args, script):
+    """what `-f0-est` and the --f0-* settings make of the script's f0_estimation keyword: the name as it was given, or with `viterbi` a
+    PitchPath and one printed line; a setting without `-f0-est viterbi`, or a refused one, ends the script"""
+    given = {k: getattr(args, "f0_" + k, None) for k in ("step", "band", "jump", "voicing", "refine")}
+    given = {k: v for k, v in given.items() if v is not None}
+    if args.f0_estimation != "viterbi":
+        if given:
+            sys.exit(f"{script}: --f0-{next(iter(given))} belongs to -f0-est viterbi")
+        return args.f0_estimation
+    try:
+        path = PitchPath(**given)
+    except ValueError as e:
+        sys.exit(f"{script}: {e}")
+    print(f"Decoding pitch as a path: {path!r} (untuned defaults: nobody has listened)")
+    return path
 
 
 def add_alpha_argument(parser):
