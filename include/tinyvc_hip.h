@@ -13,9 +13,11 @@
  *   - `stream` is a hipStream_t passed as void* (torch.cuda.current_stream().cuda_stream); all
  *     work is enqueued asynchronously on it; nothing here synchronises the device (one exception: the first use of a prepared
  *     index this process did not prepare itself reads its 24-byte header, see tvc_knn_prepare_index_f32).  Outside a stream
- *     capture the encoder forks its pitch estimator, and the decoder its harmonic oscillator and FilterNet's input contraction,
- *     onto a context-owned side stream and joins them back onto `stream` with events before the call returns - an error return
- *     included -, so `stream` order is all a caller ever sees; equal and ragged batches alike.  While `stream` is being captured
+ *     capture the encoder forks its pitch estimator, and the decoder its harmonic oscillator and FilterNet's content-only front
+ *     (the input contraction and Upsample 0's first conv), onto a context-owned side stream and joins them back onto `stream`
+ *     with events before the call returns - an error return included -, so `stream` order is all a caller ever sees; equal and
+ *     ragged batches alike.  The decoder's branch is joined twice: the harmonic rows in front of FilterNet's first launch, the
+ *     front - which may still run beside FilterNet's first launches - in front of Upsample 0's FiLM launch.  While `stream` is being captured
  *     everything stays on `stream` (one chain replays faster than a fork inside a graph: DESIGN.md section 4).  Results do not
  *     depend on it;
  *   - stream capture: every call may be captured into a HIP graph, with two rules.  Kernel arguments are baked into the graph,

@@ -105,7 +105,8 @@ int tvc_ctx_create(int hip_device, tvc_ctx** out) {
         hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_fork2, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_join2, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_amps, hipEventDisableTiming) != hipSuccess) {
+        hipEventCreateWithFlags(&c->ev_amps, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_src, hipEventDisableTiming) != hipSuccess) {
         tvc_ctx_destroy(c);
         return TVC_ERR_HIP;
     }
@@ -126,6 +127,7 @@ void tvc_ctx_destroy(tvc_ctx* ctx) {
     if (ctx->ev_fork2) (void)hipEventDestroy(ctx->ev_fork2);
     if (ctx->ev_join2) (void)hipEventDestroy(ctx->ev_join2);
     if (ctx->ev_amps) (void)hipEventDestroy(ctx->ev_amps);
+    if (ctx->ev_src) (void)hipEventDestroy(ctx->ev_src);
     if (ctx->side) (void)hipStreamDestroy(ctx->side);
     frontdoor_release(ctx);
     if (ctx->arena) (void)hipFree(ctx->arena);

@@ -316,26 +316,47 @@ static int film_conv(tvc_ctx* ctx, hipStream_t s, const PackedW& w, const Packed
 // utterance's shape only - h crosses HBM as the second conv's READY operand: conv_s2's epilogue writes split(lrelu(h) * 2^k) as two fp16
 // planes (the bytes of the fp32 tensor), k from the analytic bound hb_w |x|max + hb_b >= |h|, and film_s2 stages it by copy: the
 // lrelu / scale / split of every staged element - repeated by each of the C / 96 row blocks that read it - is done once, by the producer.
-static int conv_film_half(tvc_ctx* ctx, hipStream_t s, const PackedW& ca, const PackedW& cb, const PackedW& fw, const FilmU& fu, const float* x, int lin, float lscale,
-                          int da, int db, float* h, const float* cond, int B, int C, int len, float* out, const float* bsc, const float* bsh, const float* res,
-                          int res_lin, float res_scale, const float* ma_in, float* mh, const float* mcond, float* mout) {
-    const bool pre = rag_min_len(ctx, len) >= FS2::BN && fu.img && fu.C == C && fu.hb_w > 0.f && C % 96 == 0 && C <= 384 && ma_in && mcond && res && db >= 1 && db <= FS2::MAXD &&
+// The half is two steps, so that the first conv can be launched early and on another stream than the FiLM conv (Upsample 0's c1 reads the
+// input contraction's output only: run_filter): half_first launches ca and reports in *pre how it wrote h; half_film launches cb for that form.
+static int half_first(tvc_ctx* ctx, hipStream_t s, const PackedW& ca, const FilmU& fu, const float* x, int lin, float lscale, int da, int db, float* h, int B, int C, int len,
+                      const float* res, int res_lin, const float* ma_in, float* mh, const float* mcond, bool* pre) {
+    *pre = false;
+    const bool can = rag_min_len(ctx, len) >= FS2::BN && fu.img && fu.C == C && fu.hb_w > 0.f && C % 96 == 0 && C <= 384 && ma_in && mcond && res && db >= 1 && db <= FS2::MAXD &&
                      (long)C * len * 4 < (1L << 32) && (res_lin <= 0 || (long)C * res_lin * 4 < (1L << 32));
-    if (pre) {
+    if (can) {
         int rc = 0;
         const BfpSlots in{ma_in, nullptr, nullptr};
         const bool ok = lin > 0 ? conv_s2_try<true, true>(&rc, ctx, s, ca, x, B, C, len, da, h, in, lin, lscale, fu.hb_w, fu.hb_b)
                                 : conv_s2_try<false, true>(&rc, ctx, s, ca, x, B, C, len, da, h, in, 0, 0.f, fu.hb_w, fu.hb_b);
         if (ok) {
-            TVC_CHECK(rc);
-            if (!film_s2_try(&rc, ctx, s, fu, h, cond, B, C, len, db, out, res, res_lin, res_scale, BfpSlots{ma_in, mcond, mout}, true, fu.hb_w, fu.hb_b))
-                return fail(ctx, TVC_ERR_STATE, "filter_net: the FiLM conv refused the pre-split operand its producer wrote");
+            *pre = rc == 0;
             return rc;
         }
     }
-    TVC_CHECK(plain_conv(ctx, s, ca, x, B, C, len, da, h, BfpSlots{ma_in, nullptr, mh}, lin, lscale));
+    return plain_conv(ctx, s, ca, x, B, C, len, da, h, BfpSlots{ma_in, nullptr, mh}, lin, lscale);
+}
+
+static int half_film(tvc_ctx* ctx, hipStream_t s, const PackedW& cb, const PackedW& fw, const FilmU& fu, int db, const float* h, const float* cond, int B, int C, int len,
+                     float* out, const float* bsc, const float* bsh, const float* res, int res_lin, float res_scale, const float* ma_in, const float* mh, const float* mcond,
+                     float* mout, bool pre) {
+    if (pre) {
+        int rc = 0;
+        if (!film_s2_try(&rc, ctx, s, fu, h, cond, B, C, len, db, out, res, res_lin, res_scale, BfpSlots{ma_in, mcond, mout}, true, fu.hb_w, fu.hb_b))
+            return fail(ctx, TVC_ERR_STATE, "filter_net: the FiLM conv refused the pre-split operand its producer wrote");
+        return rc;
+    }
     return film_conv(ctx, s, cb, fw, fu, h, cond, B, C, len, db, out, bsc, bsh, res, res_lin, res_scale, BfpSlots{mh, mcond, mout});
 }
+
+static int conv_film_half(tvc_ctx* ctx, hipStream_t s, const PackedW& ca, const PackedW& cb, const PackedW& fw, const FilmU& fu, const float* x, int lin, float lscale,
+                          int da, int db, float* h, const float* cond, int B, int C, int len, float* out, const float* bsc, const float* bsh, const float* res,
+                          int res_lin, float res_scale, const float* ma_in, float* mh, const float* mcond, float* mout) {
+    bool pre = false;
+    TVC_CHECK(half_first(ctx, s, ca, fu, x, lin, lscale, da, db, h, B, C, len, res, res_lin, ma_in, mh, mcond, &pre));
+    return half_film(ctx, s, cb, fw, fu, db, h, cond, B, C, len, out, bsc, bsh, res, res_lin, res_scale, ma_in, mh, mcond, mout, pre);
+}
+
+constexpr int kHalfDil[2][2] = {{1, 3}, {9, 27}};      // dilations of an Upsample block's halves: (c1, c2), (c3, c4)
 
 // [B][C / 8][l][8] (G8) -> [B][C][l]
 static __global__ void g8_to_planar_kernel(const float* __restrict__ x, float* __restrict__ y, long B, long l, int C) {
@@ -357,13 +378,20 @@ static int filter_input_gemm(tvc_ctx* ctx, hipStream_t s, const float* content, 
 
 int run_filter(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* content, const float* f0,
                const float* energy, const float* source, float* wave, int B, int T, const FilterTaps* taps, const float* cmax, const float* smax, float* zeroed_slots, bool x_slot_set,
-               float* x_pre, bool x_pre_filled) {
+               const FilterFront* front) {
     const long L = (long)T * kHop;
     static const int ch[5] = {384, 192, 96, 48, 24};
     const long len_dn[5] = {L, L / 5, L / 20, L / 80, L / 240};   // skip i lives at len_dn[i]
     float* skip[5];
     for (int i = 0; i < 5; ++i) skip[i] = ws.get<float>((size_t)B * ch[4 - i] * len_dn[i]);
-    float* x = x_pre ? x_pre : ws.get<float>((size_t)B * ch[0] * T);
+    float* x = front ? front->x0 : ws.get<float>((size_t)B * ch[0] * T);
+    // Upsample 0's c1 reads x0 and its slot only - nothing of the down path -, so its output h0 lives from in front of the down loop to the end of
+    // Upsample 0: with the caller's fork open, c1 runs on the side stream beside the noise branch's tail and FilterNet's first launches, and s joins it in front of the level's FiLM launch
+    const UpW& u0 = ctx->ups[0];
+    const int lo0 = T * u0.factor;
+    float* h0 = front ? front->h0 : ws.get<float>((size_t)B * u0.cin * lo0);
+    SideFork* fk = front && front->fk && front->fk->forked() ? front->fk : nullptr;
+    bool pre0 = false;      // how c1 wrote h0 (half_first)
     // Downsample i's input = interpolate(skip[i-1], 1/f), written by the conv that produces skip[i-1]
     float* xi_pre[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     for (int i = 1; i <= 4; ++i) xi_pre[i] = ws.get<float>((size_t)B * ctx->downs[i - 1].cin * len_dn[i]);
@@ -378,6 +406,11 @@ int run_filter(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* content, const 
     static_assert(S_COUNT == kFilterSlots && S_X == kFilterSlotX, "tvc_common.h kFilterSlots / kFilterSlotX");
     float* slots = zeroed_slots ? zeroed_slots : ws.get<float>((size_t)S_COUNT * NB);
     auto slot = [&](int i) { return slots + (size_t)i * NB; };
+    // Upsample 0's c1 on stream st (the FiLM conv's slot and the residual are named for the hand-over's decision only: neither is read)
+    auto up0_first = [&](hipStream_t st) {
+        return half_first(ctx, st, u0.c1, u0.fu1, x, T, (float)(1.0 / (double)u0.factor), kHalfDil[0][0], kHalfDil[0][1], h0, B, u0.cin, lo0, x, T, slot(S_X), slot(S_UHA),
+                          slot(S_SKIP0 + 4), &pre0);
+    };
 
     if (!ws.dry) {
         ProfScope ps(ctx, s, ws, "filter.in+down0");
@@ -391,9 +424,17 @@ int run_filter(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* content, const 
             TVC_CHECK(run_amax_rows(ctx, s, energy, B, 1, L, slot(S_SRC)));
             smax = slot(S_SRC);
         }
-        if (!x_pre_filled) TVC_CHECK(filter_input_gemm(ctx, s, content, f0, x, B, T, cmax));      // (filled: the caller ran it on its side stream and joined)
+        if (fk && !(zeroed_slots && x_slot_set)) return fail(ctx, TVC_ERR_STATE, "filter_net: a forked front needs its slots prepared in front of the fork");
+        if (!fk) TVC_CHECK(filter_input_gemm(ctx, s, content, f0, x, B, T, cmax));      // (forked: the caller has launched it on the side stream)
         // x0's |max| slot: the functor finishes the elements, so the slot is the bound bw |content|max + bb instead of a pass over x0
         if (!(zeroed_slots && x_slot_set)) TVC_CHECK(run_slot_affine(ctx, s, slot(S_X), cmax, 1, ctx->flt_in_bw, ctx->flt_in_bb, NB));
+        if (fk) {      // c1 behind the harmonic synthesis on the side stream: beside the noise branch's tail and whatever of FilterNet's first launches it reaches
+            {
+                ProfScope ps(ctx, fk->side, ws, "filter_net.input@side");      // FilterNet's work outside its region on the launch stream: bench.py adds it to the roofline's duration
+                TVC_CHECK(up0_first(fk->side));
+            }
+            TVC_CHECK(fk->end());
+        }
         // skips[0] is read as FiLM cond only (ups[4]): it is written as the two halves' ready operand; the fp32 tensor exists for the parity tap alone
         TVC_CHECK(run_down0_split(ctx, s, ctx->flt_down0s, source, energy, skip[0], taps ? taps->skips[0] : nullptr, xi_pre[1], B, (int)L, smax, slot(S_SKIP0)));
     }
@@ -449,7 +490,7 @@ int run_filter(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* content, const 
         const float* mcond = slot(S_SKIP0 + 4 - i);
         size_t mk = ws.mark();
         float* xu = ws.get<float>((size_t)B * C * lo);
-        float* h = ws.get<float>((size_t)B * C * lo);
+        float* h = i == 0 ? h0 : ws.get<float>((size_t)B * C * lo);
         float* x1 = ws.get<float>((size_t)B * C * lo);
         if (!ws.dry && C == 24) {
             // last level: Upsample block + output_layer in two launches, waveform written directly
@@ -465,7 +506,7 @@ int run_filter(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* content, const 
                 const PackedW& fw = half ? u.film2 : u.film1;      // stacked [to_scale ; to_shift] rows, each group padded to whole 32-row tiles
                 const float* bsc = fw.bias;                        // its bias row: [b_scale (C) ; b_shift (C)]
                 const float* bsh = fw.bias + C;
-                const int da = half ? 9 : 1, db = half ? 27 : 3;
+                const int da = kHalfDil[half][0], db = kHalfDil[half][1];
                 float* xout = half ? xu : x1;   // first half: x1 = FiLM1(c2(c1(xf))) + xf; second half: xu = FiLM2(c4(c3(x1))) + x1
                 const float* ma_in = half ? slot(S_UX1 + i) : mx_in;             // input of the half's first conv
                 float* mh = slot((half ? S_UHB : S_UHA) + i);                    // its output h
@@ -478,6 +519,10 @@ int run_filter(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* content, const 
                         // c4 + FiLM2 + residual + c5 (48 -> 24) in one launch: the level's output (and its |max|) is written directly
                         TVC_CHECK(run_conv48s(ctx, s, cb, h, &fw, bsc, bsh, cond, x1, nullptr, B, lo, db, mh, mcond, slot(S_LEV + i), &u.c5, xlev[i]));
                     }
+                } else if (half == 0 && i == 0) {   // c1 on s here, or already on the side stream: joined in front of the first launch that reads h0
+                    if (fk) TVC_CHECK(fk->join());
+                    else TVC_CHECK(up0_first(s));
+                    TVC_CHECK(half_film(ctx, s, cb, fw, u.fu1, db, h, cond, B, C, lo, xout, bsc, bsh, x, lin, lscale, ma_in, mh, mcond, mout, pre0));
                 } else if (half == 0) {
                     TVC_CHECK(conv_film_half(ctx, s, ca, cb, fw, u.fu1, x, lin, lscale, da, db, h, cond, B, C, lo, xout, bsc, bsh, x, lin, lscale, ma_in, mh, mcond, mout));
                 } else {
@@ -531,8 +576,10 @@ int run_decoder(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* content, const
     float* smax = cmax + NB;
     float* xmax = smax + NB;
     float* fslots = xmax + NB;
-    // FilterNet's input contraction's output and the oscillator's frame sums
+    // FilterNet's input contraction's output, Upsample 0's c1 output (both written on the side stream while SourceNet's and dsp's temporaries
+    // are live: outside the region the stages share) and the oscillator's frame sums
     float* x0 = ws.get<float>((size_t)B * 384 * T);
+    float* h0 = ws.get<float>((size_t)B * ctx->ups[0].cin * T * ctx->ups[0].factor);
     double* csum = ws.get<double>((size_t)B * kHarm * T);
     if (!ws.dry) {
         TVC_CHECK(run_slot_prep(ctx, s, cmax, (3 + kFilterSlots) * NB, content_bound ? cmax : nullptr, content_bound, content_bound_stride, 1.f, 0.f, energy_bound ? smax : nullptr,
@@ -540,16 +587,27 @@ int run_decoder(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* content, const
                                 NB));      // (the dsp kernels raise smax to cat[source, energy]'s; the third: FilterNet's x0 slot from |content|max)
         if (!content_bound) TVC_CHECK(run_amax_rows(ctx, s, content, B, kSslDim, T, cmax));
         if (!energy_bound) TVC_CHECK(run_amax_rows(ctx, s, energy, B, 1, L, smax));
+        // what the side stream's FilterNet launches read besides content and f0, complete on s in front of the fork: x0's slot ...
+        if (!content_bound && wave) TVC_CHECK(run_slot_affine(ctx, s, fslots + (size_t)kFilterSlotX * NB, cmax, 1, ctx->flt_in_bw, ctx->flt_in_bb, NB));
+        if (wave && ctx->rag) {      // ... and, of a ragged batch, the column-tile table of c1's launch (built on the stream of its first use: ragged.h)
+            RagDev rd;
+            TVC_CHECK(rag_tiles(ctx, s, B, (long)T * ctx->ups[0].factor, CS2::BN, &rd, nullptr, "filter_net front"));
+        }
     }
-    // FilterNet's input contraction (768 -> 384 at the frame rate: 48 us at the bench shape) reads nothing SourceNet or dsp produce: with the
-    // waveform asked for, it runs on the context's side stream behind the oscillator's frame sums (f0 only), beside SourceNet; the harmonic
-    // synthesis (vector-ALU-bound) follows there beside to_kernel and the noise FFTs on s; the join follows dsp.  Ragged batches too: the side
-    // stream's kernels read the batch's base tables only (built on s in front of the fork), no column-tile table.
+    // One fork, two joins.  With the waveform asked for, the context's side stream carries, in this order: the oscillator's frame sums (f0 only)
+    // and FilterNet's input contraction (768 -> 384 at the frame rate; content, f0 and cmax only), beside SourceNet; the harmonic synthesis
+    // (vector-ALU-bound) behind the amplitudes' GEMM, beside to_kernel and the noise FFTs on s - s waits for the harmonic rows behind dsp, in
+    // front of FilterNet's first launch -; Upsample 0's c1, which reads the contraction's output only, beside the noise branch's tail and
+    // FilterNet's first launches - s waits for it in front of Upsample 0's FiLM launch (run_filter), and in fk's destructor on every earlier
+    // return.  Measured against the two other placements of the pair (both behind the synthesis; both behind downs[0]'s launch): DESIGN.md
+    // section 4.  Ragged batches too: the side stream's kernels read the batch's base tables and the one column-tile table above, all built
+    // on s in front of the fork.
     SideFork fk(ctx, s);
-    if (wave) TVC_CHECK(fk.fork(ws, ctx->ev_fork2, ctx->ev_join2));      // content, f0 and cmax are complete on s
+    if (wave) TVC_CHECK(fk.fork(ws, ctx->ev_fork2, ctx->ev_join2));      // content, f0, cmax and the slots are complete on s
+    const FilterFront front{&fk, x0, h0};
     if (fk.forked()) {
         TVC_CHECK(run_harm_sums(ctx, fk.side, f0, csum, B, T));
-        ProfScope ps(ctx, fk.side, ws, "filter_net.input@side");      // FilterNet's work outside its region on the launch stream: bench.py adds it to the roofline's duration
+        ProfScope ps(ctx, fk.side, ws, "filter_net.input@side");      // (a second scope of this name, around c1, is run_filter's: the profile sums them)
         TVC_CHECK(filter_input_gemm(ctx, fk.side, content, f0, x0, B, T, cmax));
     }
     size_t mk = ws.mark();
@@ -563,12 +621,12 @@ int run_decoder(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* content, const
         ProfScope ps(ctx, s, ws, "dsp");
         const DspFork df{fk.side, ctx->ev_amps};
         TVC_CHECK(run_dsp(ctx, s, ws, f0, amps, kern, angle, seed, source, B, T, smax, csum, fk.forked() ? &df : nullptr));
-        TVC_CHECK(fk.join());      // the side stream's whole chain (harmonics, FilterNet's input contraction) is behind s from here
+        TVC_CHECK(fk.join_so_far(ctx->ev_src));      // the first join: the harmonic rows (and the input contraction in front of them) are behind s from here
     }
     ws.release(mk);
     if (!wave) return 0;                 // ... or for Decoder.dsp's output (decoder.py:259-266) without the FilterNet pass
     ProfScope ps(ctx, s, ws, "filter_net");
-    TVC_CHECK(run_filter(ctx, s, ws, content, f0, energy, source, wave, B, T, nullptr, cmax, smax, fslots, content_bound != nullptr, x0, fk.forked()));
+    TVC_CHECK(run_filter(ctx, s, ws, content, f0, energy, source, wave, B, T, nullptr, cmax, smax, fslots, true, &front));      // (the second join is run_filter's)
     ws.release(mk);
     return 0;
 }

@@ -137,7 +137,8 @@ struct tvc_ctx {
     std::vector<hipEvent_t> event_pool;       // recycled hipEvents: no hipEventCreate on the hot path
     hipStream_t side = nullptr;               // fork/join stream: the pitch estimator runs beside the SSL chain
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_fork2 = nullptr, ev_join2 = nullptr, ev_amps = nullptr;      // the decoder's fork: FilterNet's input contraction beside SourceNet / dsp (decoder.hip run_decoder)
+    hipEvent_t ev_fork2 = nullptr, ev_join2 = nullptr, ev_amps = nullptr;      // the decoder's fork: the oscillator beside SourceNet / dsp, FilterNet's content-only front beside SourceNet and the noise branch's tail (decoder.hip run_decoder)
+    hipEvent_t ev_src = nullptr;              // ... its first join: the harmonic rows of `source` are written (the launch stream waits for it in front of FilterNet)
     tvc::RagHost* rag = nullptr;              // the ragged batch the drivers are currently running for (ragged.h); nullptr = equal lengths
     int rag_batch_frames = 0;                 // tvc_ctx_set_ragged_batch_frames: frames per in-kernel batch of THIS context's ragged calls (0 = the default)
     int index_assign_chunk = 0;               // tvc_ctx_set_index_assign_chunk: query columns per search call of THIS context's index assignment (0 = the default)
@@ -259,10 +260,11 @@ struct ProfScope {
     }
 };
 
-// A branch on the context's side stream (run_encoder's pitch chain, run_decoder's oscillator and FilterNet input contraction).  fork() forks
+// A branch on the context's side stream (run_encoder's pitch chain, run_decoder's oscillator and FilterNet's content-only front).  fork() forks
 // only when the side stream and both events exist, ws.dry is false and `s` is not being captured; `side` = the branch's
-// stream (`s` unforked).  end() records `ev_join` behind the branch; join() makes `s` wait for it (recording it first if end() has not run),
-// and so does the destructor if join() has not run: an error return leaves `s` behind every side launch (they write into the workspace).
+// stream (`s` unforked).  join_so_far(ev) puts `s` behind the side launches made so far and leaves the branch open.  end() records `ev_join`
+// behind the branch; join() makes `s` wait for it (recording it first if end() has not run), and so does the destructor if join() has not
+// run: an error return leaves `s` behind every side launch (they write into the workspace), whichever of the joins it came before.
 struct SideFork {
     tvc_ctx* ctx;
     hipStream_t s, side;
@@ -277,6 +279,12 @@ struct SideFork {
         TVC_HIP(ctx, hipStreamWaitEvent(ctx->side, ev_fork, 0));
         side = ctx->side;
         ev_join = join;
+        return 0;
+    }
+    int join_so_far(hipEvent_t ev) {
+        if (!forked()) return 0;
+        TVC_HIP(ctx, hipEventRecord(ev, side));
+        TVC_HIP(ctx, hipStreamWaitEvent(s, ev, 0));
         return 0;
     }
     int end() {
@@ -490,11 +498,19 @@ struct FilterTaps {   // optional copies of FilterNet's block outputs (tvc_filte
 };
 // cmax / smax / the trailing float* of run_dsp: per-utterance |max| slots of content / cat[source, energy] (block-floating-point
 // guard of the fp16 split, split_fp16.h); nullptr = the stage computes (or keeps) its own
+// FilterNet's content-only front - the input contraction x0 and Upsample 0's c1 output h0, which read content, f0 and cmax only - as
+// run_decoder hands it to run_filter: the two buffers (live for the whole call, outside the region run_filter allocates from), and the
+// caller's fork.  With the fork open, the caller has launched the contraction on fk->side; run_filter launches c1 behind it there, beside
+// its own first launches, and joins fk in front of Upsample 0's FiLM launch, the first that reads h0; an earlier return leaves the join to fk's
+// destructor.  Unforked, run_filter runs both on `s`, in the chain's order.
+struct FilterFront {
+    SideFork* fk;         // the caller's fork
+    float *x0, *h0;       // [B][384][T], [B][384][2 T]
+};
 int run_filter(tvc_ctx*, hipStream_t, Ws&, const float* content, const float* f0, const float* energy,
                const float* source, float* wave, int B, int T, const FilterTaps* taps = nullptr, const float* cmax = nullptr, const float* smax = nullptr,
-               float* zeroed_slots = nullptr, bool x_slot_set = false, float* x_pre = nullptr, bool x_pre_filled = false);      // zeroed_slots: kFilterSlots x utterances floats the caller has already zeroed on this
-                                                                             // stream; x_slot_set: ... and has set slot kFilterSlotX to flt_in_bw |content|max + flt_in_bb; x_pre: the buffer of the input
-                                                                             // contraction's output; x_pre_filled: ... which already holds it, ordered in front of `s` (run_decoder's fork)
+               float* zeroed_slots = nullptr, bool x_slot_set = false, const FilterFront* front = nullptr);      // zeroed_slots: kFilterSlots x utterances floats the caller has already zeroed on this
+                                                                             // stream; x_slot_set: ... and has set slot kFilterSlotX to flt_in_bw |content|max + flt_in_bb (a forked front needs both)
 // run_decoder's fork (decoder.hip): the harmonic synthesis on `side` beside SourceNet's to_kernel GEMM and the noise branch; csum's frame sums
 // are already scanned there, amps_ready is recorded on the launch stream behind the amplitudes' GEMM.  The caller joins `side` itself.
 struct DspFork {
