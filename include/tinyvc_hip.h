@@ -579,7 +579,30 @@ int tvc_frame_share_f32(tvc_ctx* ctx, void* stream, const float* f0, const int64
  * tvc_convert_path_f32 / tvc_convert_ragged_path_f32: the protect entries' arguments plus `path` behind protect.  path == NULL is the protect
  * call, launch for launch and bit for bit.  With it the call keeps the encoder's logits, runs the path kernel directly behind the encoder (one
  * launch per 256 utterances) and everything that reads f0 - the voicing weight of protect, the automatic shift, a tracker, the shift, the
- * decoder - reads the path's.  Workspace: tvc_workspace_bytes_path / _ragged_path (enough with or without any of the optional arguments). */
+ * decoder - reads the path's.  Workspace: tvc_workspace_bytes_path / _ragged_path (enough with or without any of the optional arguments).
+ * THE CARRY: the path's state from one stream block to the next.  Two optional per-row device arrays of 512 fp32, `prior` (read) and
+ * `carry_out` (written), and a host integer carry_frame = h >= 1.
+ *   - prior: p_j = prior[j] where prior[j] <= 0 (-inf included); every other value - NaN, a positive value, +inf - counts as 0; if after that
+ *     every p_j is -inf, all p_j are 0 (a reset).  u_0[j] = p_j + e_0[j], one rounded fp32 add; everything else of the definition is unchanged.
+ *     prior == NULL is u_0 = e_0, the call as it was; a prior of zeros gives the same classes, back-pointers and f0, and scores equal by value.
+ *   - carry: carry_out[j] = best_h[j], the best-predecessor value of frame h before e_h[j] is added.  It is computed from s_{h-1}, so its
+ *     maximum is exactly 0.0; it is never NaN or positive, and -inf only under infinite costs.  Every non-empty row must have more than h
+ *     frames (TVC_ERR_ARG with the reason otherwise).  prior and carry_out may be the same array: thread j reads its element at frame 0 and
+ *     writes it at frame h.
+ *   - in a stream whose window advances by h = block_size / 480 frames, each window's best_h is the next window's prior at its frame 0, the
+ *     same instant: the exact forward recursion of an online Viterbi.  Decoded window by window over slices of ONE logits tensor, scores,
+ *     back-pointers and path equal the decode of the whole prefix (tests/helpers_pitch_carry.py).  In a stream every window has logits of its
+ *     own, so the chain accumulates the emissions of each window's oldest h frames; the state is a prior, not the decode of any one tensor.
+ *   - MEMORY SAFETY, the one rule: no state, whatever a caller wrote into it, may leave a frame of the kernel without a class whose s == 0.
+ *     The sanitised prior holds a finite value <= 0 and the emissions are finite, so m_0 is finite and the rule holds from frame 0 on as it
+ *     does without a prior; no score is NaN, and every back-pointer is a class.  Independently of it the walk back never starts from the
+ *     "none" value 512: it falls back to class 0.
+ * tvc_pitch_path_carry_f32: tvc_pitch_path_f32's arguments with carry_frame, prior, carry_out behind path; the arrays are [rows][512], either
+ * may be NULL, carry_frame is ignored when carry_out is NULL, and carry_out counts as an output.  Both NULL is tvc_pitch_path_f32.
+ * tvc_convert_carry_f32: tvc_convert_path_f32's arguments with carry_frame, carry behind path; carry is [B][512] on the device, read and written
+ * in place (needs path; L / 480 must be more than carry_frame).  carry == NULL is the path call, launch for launch and bit for bit.  There is
+ * no ragged form: streams advance in lock step.  Both workspace queries are the path's.  The carried calls launch a variant of the kernel
+ * that adds one barrier at frame 0 and one 4-byte store per thread at frame h; no new workspace, no atomics, capturable. */
 typedef struct tvc_pitch_path {
     float step;
     int32_t band;
@@ -600,6 +623,15 @@ int tvc_convert_path_f32(tvc_ctx* ctx, void* stream, const float* wav, const flo
                          int start, int n, int W, int min_voiced, float slew, float* ring, int64_t* count, float* auto_shift,
                          float pitch_shift, const float* pitch_shifts, float* shift_out, const float* noise_angle, uint64_t seed,
                          float* wave, int B, int64_t L, void* ws, size_t ws_bytes);
+int tvc_pitch_path_carry_f32(tvc_ctx* ctx, void* stream, const float* logits, const int64_t* row_start, const int64_t* row_count, int rows,
+                             int64_t class_stride, const tvc_pitch_path* path, int carry_frame, const float* prior, float* carry_out,
+                             float pitch_shift, const float* pitch_shifts, float* f0, float* f0_shifted, int32_t* path_out, float* score_out,
+                             void* ws, size_t ws_bytes);
+int tvc_convert_carry_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M,
+                          const float* weights, const float* alpha, const float* protect, const tvc_pitch_path* path, int carry_frame,
+                          float* carry, const float* target_f0, int start, int n, int W, int min_voiced, float slew, float* ring,
+                          int64_t* count, float* auto_shift, float pitch_shift, const float* pitch_shifts, float* shift_out,
+                          const float* noise_angle, uint64_t seed, float* wave, int B, int64_t L, void* ws, size_t ws_bytes);
 int tvc_workspace_bytes_ragged_path(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, const int64_t* N, int M, size_t* out_bytes);
 int tvc_convert_ragged_path_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens,
                                 const float* const* prepared, const int64_t* N, int M, const float* weights, const float* alpha,

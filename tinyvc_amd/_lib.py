@@ -116,6 +116,11 @@ SIGNATURES = {
     "tvc_convert_path_f32": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_int64), c_int, c_void_p, c_void_p, c_void_p,
                                      POINTER(PitchPathSettings), c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_float,
                                      POINTER(c_float), c_void_p, c_void_p, c_uint64, c_void_p, c_int, c_int64, c_void_p, c_size_t]),
+    "tvc_pitch_path_carry_f32": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int64), c_int, c_int64, POINTER(PitchPathSettings), c_int,
+                                         c_void_p, c_void_p, c_float, POINTER(c_float), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "tvc_convert_carry_f32": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_int64), c_int, c_void_p, c_void_p, c_void_p,
+                                      POINTER(PitchPathSettings), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                      c_float, POINTER(c_float), c_void_p, c_void_p, c_uint64, c_void_p, c_int, c_int64, c_void_p, c_size_t]),
     "tvc_workspace_bytes_ragged_path": (c_int, [c_void_p, c_int, c_int64, POINTER(c_int64), POINTER(c_int64), c_int, POINTER(c_size_t)]),
     "tvc_convert_ragged_path_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64), POINTER(c_void_p), POINTER(c_int64), c_int, c_void_p,
                                             c_void_p, c_void_p, POINTER(PitchPathSettings), c_void_p, c_float, POINTER(c_float), c_void_p, c_void_p, c_uint64,

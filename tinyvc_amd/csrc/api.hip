@@ -283,7 +283,7 @@ int tvc::convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const ConvertCall& c)
                 const int r = ctx->rag ? ctx->rag->row[i] : i;
                 rows[i] = PitchPathRow{ctx->rag ? ctx->rag->pre[i] : i * T, ctx->rag ? ctx->rag->tb[i] : T, ix.per_row && c.shifts ? c.shifts[r] : c.shift};
             }
-            TVC_CHECK(run_pitch_path(ctx, s, lgt, T, rows, *c.path, bp, f0, auto_pitch ? nullptr : f0s, nullptr, nullptr));
+            TVC_CHECK(run_pitch_path(ctx, s, lgt, T, rows, *c.path, bp, f0, auto_pitch ? nullptr : f0s, nullptr, nullptr, c.carry_frame, c.carry, c.carry));
         }
         if (c.track && !ws.dry) {      // one workgroup per stream: its history's register, the slew-limited shift, its shifted f0 (no workspace)
             TVC_CHECK(run_pitch_track(ctx, s, f0, B, T, *c.track, c.target_f0, c.shift, c.shifts, nullptr, nullptr, c.shift_out, f0s));
@@ -915,15 +915,23 @@ static int path_check(tvc_ctx* ctx, const tvc_pitch_path* path, const char* what
 static int convert_alpha(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M, const float* weights,
                          const float* alpha, const float* protect, const float* target_f0, int start, int n, int W, int min_voiced, float slew, float* ring,
                          int64_t* count, float* auto_shift, float pitch_shift, const float* pitch_shifts, float* shift_out, const float* noise_angle,
-                         uint64_t seed, float* wave, int B, int64_t L, void* wsp, size_t ws_bytes, const char* what, const tvc_pitch_path* path = nullptr) {
+                         uint64_t seed, float* wave, int B, int64_t L, void* wsp, size_t ws_bytes, const char* what, const tvc_pitch_path* path = nullptr,
+                         int carry_frame = 0, float* carry = nullptr) {
     if (!ctx) return TVC_ERR_ARG;
     TVC_CHECK(path_check(ctx, path, what));
+    if (carry) {      // the path's state from block to block: refused here, before any device work
+        if (!path) return fail(ctx, TVC_ERR_ARG, "%s: carry needs path (the state is the pitch path's)", what);
+        if (carry_frame < 1 || L / kHop <= carry_frame)
+            return fail(ctx, TVC_ERR_ARG, "%s: carry_frame = %d must be >= 1 and below the window's %lld frames", what, carry_frame, (long long)(L / kHop));
+    }
     ConvertIndex ix;
     TVC_CHECK(auto_index(ctx, B, prepared, N, M, weights, &ix, what));
     ConvertCall c{wav, wave, B, L, nullptr, ix, pitch_shift, pitch_shifts, noise_angle, seed, target_f0, target_f0 ? shift_out : nullptr};
     c.alpha = alpha;
     c.protect = protect;
     c.path = path;
+    c.carry_frame = carry ? carry_frame : 0;
+    c.carry = carry;
     const PitchTrackState t{start, n, W, min_voiced, slew, ring, count, auto_shift};
     if (ring) {      // a tracker: tvc_convert_track_f32's checks
         if (L <= 0 || L / kHop > 0x7fffffff) return fail(ctx, TVC_ERR_ARG, "%s: bad argument (L must be a positive multiple of 480)", what);
@@ -1026,6 +1034,16 @@ int tvc_convert_ragged_path_f32(tvc_ctx* ctx, void* stream, const float* wav, in
     return convert_ragged_alpha(ctx, stream, wav, Lmax, lens, prepared, N, M, weights, alpha, protect, target_f0, pitch_shift, pitch_shifts, shift_out, noise_angle,
                                 seed, wave, B, wsp, ws_bytes, "tvc_convert_ragged_path_f32", path);
 }
+// the carry: the path entry with the path's state [B][512] on the device, read at frame 0 and written at frame carry_frame, in place.  Equal
+// lengths only (streams advance in lock step); carry == NULL is the path call, launch for launch.  Workspace: tvc_workspace_bytes_path.
+int tvc_convert_carry_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M, const float* weights,
+                          const float* alpha, const float* protect, const tvc_pitch_path* path, int carry_frame, float* carry, const float* target_f0,
+                          int start, int n, int W, int min_voiced, float slew, float* ring, int64_t* count, float* auto_shift, float pitch_shift,
+                          const float* pitch_shifts, float* shift_out, const float* noise_angle, uint64_t seed, float* wave, int B, int64_t L, void* wsp,
+                          size_t ws_bytes) {
+    return convert_alpha(ctx, stream, wav, prepared, N, M, weights, alpha, protect, target_f0, start, n, W, min_voiced, slew, ring, count, auto_shift, pitch_shift,
+                         pitch_shifts, shift_out, noise_angle, seed, wave, B, L, wsp, ws_bytes, "tvc_convert_carry_f32", path, carry_frame, carry);
+}
 // the stage call's rows, checked on the host: ascending, apart, inside 32-bit indexing and inside one run of class_stride columns each
 static int path_rows(tvc_ctx* ctx, const int64_t* row_start, const int64_t* row_count, int rows, int64_t S, int64_t* span, const char* what) {
     if (!row_start || !row_count || rows <= 0) return fail(ctx, TVC_ERR_ARG, "%s: bad argument (row_start, row_count and rows > 0)", what);
@@ -1049,24 +1067,44 @@ int tvc_workspace_bytes_pitch_path(tvc_ctx* ctx, const int64_t* row_start, const
     TVC_CHECK(path_rows(ctx, row_start, row_count, rows, 0, &span, "tvc_workspace_bytes_pitch_path"));
     return measure(1, out_bytes, [&](Ws& ws) { ws.get<uint16_t>(pitch_path_ws_bytes(span) / sizeof(uint16_t)); return 0; });
 }
-int tvc_pitch_path_f32(tvc_ctx* ctx, void* stream, const float* logits, const int64_t* row_start, const int64_t* row_count, int rows, int64_t class_stride,
-                       const tvc_pitch_path* path, float pitch_shift, const float* pitch_shifts, float* f0, float* f0_shifted, int32_t* path_out,
-                       float* score_out, void* wsp, size_t ws_bytes) {
-    const char* what = "tvc_pitch_path_f32";
+// the stage call and its carried form share their body: prior == carry_out == nullptr is the call as it was, under the entry's own name `what`
+static int pitch_path_entry(tvc_ctx* ctx, void* stream, const float* logits, const int64_t* row_start, const int64_t* row_count, int rows, int64_t class_stride,
+                            const tvc_pitch_path* path, int carry_frame, const float* prior, float* carry_out, float pitch_shift, const float* pitch_shifts,
+                            float* f0, float* f0_shifted, int32_t* path_out, float* score_out, void* wsp, size_t ws_bytes, const char* what) {
     if (!ctx) return TVC_ERR_ARG;
-    if (!logits || !path || class_stride <= 0 || class_stride > 0x7fffffff || (!f0 && !f0_shifted && !path_out && !score_out))
+    if (!logits || !path || class_stride <= 0 || class_stride > 0x7fffffff || (!f0 && !f0_shifted && !path_out && !score_out && !carry_out))
         return fail(ctx, TVC_ERR_ARG, "%s: bad argument (logits, path, 0 < class_stride < 2^31 and at least one output)", what);
     TVC_CHECK(path_check(ctx, path, what));
     int64_t span = 0;
     TVC_CHECK(path_rows(ctx, row_start, row_count, rows, class_stride, &span, what));
+    if (carry_out) {      // frame h must exist in every row that runs
+        if (carry_frame < 1) return fail(ctx, TVC_ERR_ARG, "%s: carry_frame = %d must be >= 1", what, carry_frame);
+        for (int b = 0; b < rows; ++b)
+            if (row_count[b] > 0 && row_count[b] <= carry_frame)
+                return fail(ctx, TVC_ERR_ARG, "%s: row %d has %lld frames: carry_out takes frame carry_frame = %d, so every non-empty row needs more", what, b,
+                            (long long)row_count[b], carry_frame);
+    }
     std::vector<PitchPathRow> rw((size_t)rows);
     for (int b = 0; b < rows; ++b) rw[b] = PitchPathRow{(int)row_start[b], (int)row_count[b], pitch_shifts ? pitch_shifts[b] : pitch_shift};
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     return run_walks(ctx, what, wsp, ws_bytes, 1, [&](Ws& ws) {
         uint16_t* bp = ws.get<uint16_t>(pitch_path_ws_bytes(span) / sizeof(uint16_t));
         if (ws.dry) return 0;
-        return run_pitch_path(ctx, (hipStream_t)stream, logits, (long)class_stride, rw, *path, bp, f0, f0_shifted, path_out, score_out);
+        return run_pitch_path(ctx, (hipStream_t)stream, logits, (long)class_stride, rw, *path, bp, f0, f0_shifted, path_out, score_out, carry_frame, prior,
+                              carry_out);
     });
+}
+int tvc_pitch_path_f32(tvc_ctx* ctx, void* stream, const float* logits, const int64_t* row_start, const int64_t* row_count, int rows, int64_t class_stride,
+                       const tvc_pitch_path* path, float pitch_shift, const float* pitch_shifts, float* f0, float* f0_shifted, int32_t* path_out,
+                       float* score_out, void* wsp, size_t ws_bytes) {
+    return pitch_path_entry(ctx, stream, logits, row_start, row_count, rows, class_stride, path, 0, nullptr, nullptr, pitch_shift, pitch_shifts, f0, f0_shifted,
+                            path_out, score_out, wsp, ws_bytes, "tvc_pitch_path_f32");
+}
+int tvc_pitch_path_carry_f32(tvc_ctx* ctx, void* stream, const float* logits, const int64_t* row_start, const int64_t* row_count, int rows,
+                             int64_t class_stride, const tvc_pitch_path* path, int carry_frame, const float* prior, float* carry_out, float pitch_shift,
+                             const float* pitch_shifts, float* f0, float* f0_shifted, int32_t* path_out, float* score_out, void* wsp, size_t ws_bytes) {
+    return pitch_path_entry(ctx, stream, logits, row_start, row_count, rows, class_stride, path, carry_frame, prior, carry_out, pitch_shift, pitch_shifts, f0,
+                            f0_shifted, path_out, score_out, wsp, ws_bytes, "tvc_pitch_path_carry_f32");
 }
 int tvc_frame_share_f32(tvc_ctx* ctx, void* stream, const float* f0, const int64_t* row_start, const int64_t* row_count, int rows, const float* alpha,
                         const float* protect, float* share_out) {

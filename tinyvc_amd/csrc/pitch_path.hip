@@ -15,6 +15,13 @@
 // Then the same workgroup walks back: 32 frames of back-pointers at a time return to LDS with 16-byte loads, thread 0 follows them there
 // (a dependent LDS read per frame, where the walk through memory was a dependent miss per frame), and one thread per frame writes the
 // class, f0 and the shifted f0.  No atomics on floats, no host synchronisation: the launch is capturable.
+// The carry (tvc_pitch_path_carry_f32, tvc_convert_carry_f32) is a compile-time variant, pitch_path_kernel<true>: thread j adds the sanitised
+// prior[row][j] to its first emission (one __syncthreads_or for the all -inf rule) and stores best_h[j], the best-predecessor value of frame h
+// before e_h[j] is added, into carry_out[row][j] - the same thread reads and writes its element, so the two may be one array.  The calls
+// without a carry launch pitch_path_kernel<false>, whose code is what it was.
+// MEMORY SAFETY (the rule of tinyvc_hip.h): every frame leaves with a class whose s == 0.  The emissions are finite; a prior enters only
+// through pp_prior below, which lets nothing but values <= 0 through and resets a state without a finite one - so m_t is finite, no score is
+// NaN or positive, every ballot has a lane and every back-pointer is a class below 512.
 #include <cmath>
 #include <cstdint>
 
@@ -40,8 +47,17 @@ struct PitchPathOut {
     int* path;
     float* score;
 };
+// the carried variant's share: prior / out [rows][512] (either may be nullptr, both may be one array), frame = h >= 1 (looked at with out only)
+struct PitchPathCarryArgs {
+    const float* prior;
+    float* out;
+    int frame;
+};
 
 __device__ __forceinline__ float pp_emission(float x) { return x != x ? -kPpClamp : fminf(fmaxf(x, -kPpClamp), kPpClamp); }
+// a carried state as the recursion takes it, whatever a caller wrote there: values <= 0 (-inf included) as they are, everything else - NaN,
+// positive values, +inf - counts as 0.  The caller (all 512 threads) turns a state that is -inf throughout into zeros.
+__device__ __forceinline__ float pp_prior(float p) { return p <= 0.f ? p : 0.f; }
 
 // f0 of class c at a frame whose logits are p[class * S]: freq[c] weighted over the classes within r of c (definition: tinyvc_hip.h)
 __device__ __forceinline__ float pp_frequency(const float* __restrict__ p, long S, const float* __restrict__ freq, int c, int r) {
@@ -70,9 +86,10 @@ __device__ __forceinline__ float pp_frequency(const float* __restrict__ p, long 
     return acc <= 20.f ? 0.f : acc;
 }
 
+template <bool CARRY>
 static __global__ __launch_bounds__(kPitchClasses) void pitch_path_kernel(PitchPathRows rows, int row0, const float* __restrict__ logits, long S,
                                                                           const float* __restrict__ freq, float step, int W, float jump, float voicing,
-                                                                          int refine, uint16_t* __restrict__ bp, PitchPathOut out) {
+                                                                          int refine, uint16_t* __restrict__ bp, PitchPathOut out, PitchPathCarryArgs carry) {
     __shared__ float sc[kPpPad + kPitchClasses + kPpPad];      // s_t of the voiced classes; class 0's slot and the pads hold -inf
     __shared__ float s0;                                       // s_t[0]
     __shared__ float pm[kPpWaves];                             // the waves' maxima of u_t over the voiced classes,
@@ -96,6 +113,13 @@ static __global__ __launch_bounds__(kPitchClasses) void pitch_path_kernel(PitchP
 #pragma unroll
     for (int k = 0; k < 4; ++k) e[k] = 1 + k < T ? pp_emission(mine[1 + k]) : 0.f;
     float u = pp_emission(mine[0]), s = 0.f;
+    if constexpr (CARRY) {
+        if (carry.prior) {      // uniform over the workgroup: every thread meets the barrier
+            float p = pp_prior(carry.prior[(long)(row0 + blockIdx.x) * kPitchClasses + j]);
+            if (!__syncthreads_or(p != -INFINITY)) p = 0.f;      // -inf throughout: a reset
+            u = __fadd_rn(p, u);
+        }
+    }
     for (int tb = 0; tb < T; tb += 4) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -155,6 +179,9 @@ static __global__ __launch_bounds__(kPitchClasses) void pitch_path_kernel(PitchP
                 if (fv > best || (fv == best && fi < from)) { best = fv; from = fi; }
             }
             bpr[(long)(t + 1) * kPitchClasses + j] = (uint16_t)from;
+            if constexpr (CARRY) {
+                if (carry.out && t + 1 == carry.frame) carry.out[(long)(row0 + blockIdx.x) * kPitchClasses + j] = best;
+            }
             u = __fadd_rn(best, e[k]);
             if (t + 5 < T) e[k] = pp_emission(mine[t + 5]);
         }
@@ -172,6 +199,9 @@ static __global__ __launch_bounds__(kPitchClasses) void pitch_path_kernel(PitchP
         if (out.f0s) out.f0s[c0 + t] = shift_frequency_one(fv, shift);
     };
     int c = last;      // thread 0 keeps path[hi]
+    if constexpr (CARRY) {
+        if (c >= kPitchClasses) c = 0;      // never reached under the rule above; the walk back indexes LDS by c, so it does not rest on it
+    }
     if (j == 0) emit(T - 1, c);
     for (int hi = T - 1; hi > 0;) {
         const int n = hi < kPpChunk ? hi : kPpChunk;      // back-pointers of frames hi - n + 1 .. hi give the classes of frames hi - n .. hi - 1
@@ -207,9 +237,11 @@ int pitch_path_check(const tvc_pitch_path& p, char* why, size_t why_bytes) {
 }
 
 int run_pitch_path(tvc_ctx* ctx, hipStream_t s, const float* logits, long S, const std::vector<PitchPathRow>& rows, const tvc_pitch_path& p, uint16_t* bp,
-                   float* f0, float* f0s, int* path_out, float* score_out) {
+                   float* f0, float* f0s, int* path_out, float* score_out, int carry_frame, const float* prior, float* carry_out) {
     if (!ctx->pitch_freq) return fail(ctx, TVC_ERR_STATE, "pitch table not uploaded (tvc_set_pitch_table + tvc_finalize_weights)");
     const PitchPathOut out{f0, f0s, path_out, score_out};
+    const PitchPathCarryArgs carry{prior, carry_out, carry_out ? carry_frame : 0};
+    const auto kernel = prior || carry_out ? pitch_path_kernel<true> : pitch_path_kernel<false>;
     for (size_t o = 0; o < rows.size(); o += PP_ROWS) {
         PitchPathRows r;
         const int n = (int)(rows.size() - o < PP_ROWS ? rows.size() - o : PP_ROWS);
@@ -218,8 +250,8 @@ int run_pitch_path(tvc_ctx* ctx, hipStream_t s, const float* logits, long S, con
             r.len[i] = rows[o + i].len;
             r.shift[i] = rows[o + i].shift;
         }
-        hipLaunchKernelGGL(pitch_path_kernel, dim3(n), dim3(kPitchClasses), 0, s, r, (int)o, logits, S, ctx->pitch_freq, p.step, p.band, p.jump, p.voicing, p.refine,
-                           bp, out);
+        hipLaunchKernelGGL(kernel, dim3(n), dim3(kPitchClasses), 0, s, r, (int)o, logits, S, ctx->pitch_freq, p.step, p.band, p.jump, p.voicing, p.refine, bp,
+                           out, carry);
     }
     return launch_check(ctx, "pitch_path");
 }

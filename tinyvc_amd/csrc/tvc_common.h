@@ -442,6 +442,10 @@ struct ConvertCall {
     // tvc_convert_*path_f32: path (host settings) puts the Viterbi decode of the call's own logits (run_pitch_path, directly behind the encoder) in
     // the place of the per-frame decode: protect's voicing weight, the automatic shift, a tracker, the shift and the decoder read its f0
     const tvc_pitch_path* path = nullptr;
+    // tvc_convert_carry_f32 (equal lengths only, with path): carry (device, [B][512], read and written in place) is the path's state from one
+    // stream block to the next - row b starts from carry[b] and leaves the best-predecessor values of frame carry_frame there
+    int carry_frame = 0;
+    float* carry = nullptr;
 };
 // Generator.convert over c.B rows of c.L samples (c.lens is not looked at: a ragged call reaches this through convert_ragged_batches,
 // one batch at a time as ONE row with ctx->rag set, ragged.h)
@@ -475,6 +479,9 @@ int run_pitch_track(tvc_ctx*, hipStream_t, const float* f0, int S, int T, const 
 // len) with `shift` the semitones of its f0s; class k of column n lies at logits[(n / S) * 512 * S + k * S + n % S] and no row straddles a
 // multiple of S; bp = 512 uint16 per column up to the last row's end (pitch_path_ws_bytes); f0, f0s, path_out, score_out [rows][512] optional.
 // One launch per 256 rows.  The caller has checked the settings (pitch_path_check: 0, or TVC_ERR_ARG with the reason in `why`).
+// The carry: prior / carry_out (device, [rows][512], nullable, may be one array) and carry_frame = h - row i starts from the sanitised
+// prior[i] and leaves best_h in carry_out[i]; the caller has checked that every non-empty row has more than h >= 1 frames (a row without
+// frame h stores nothing).  Both nullptr is the call as it was, and launches the kernel it launched.
 constexpr int kPitchPathMaxBand = TVC_PITCH_PATH_MAX_BAND, kPitchPathMaxRefine = TVC_PITCH_PATH_MAX_REFINE;
 struct PitchPathRow {
     int start, len;
@@ -483,7 +490,7 @@ struct PitchPathRow {
 size_t pitch_path_ws_bytes(int64_t columns);
 int pitch_path_check(const tvc_pitch_path& p, char* why, size_t why_bytes);
 int run_pitch_path(tvc_ctx*, hipStream_t, const float* logits, long S, const std::vector<PitchPathRow>& rows, const tvc_pitch_path& p, uint16_t* bp, float* f0,
-                   float* f0s, int* path_out, float* score_out);
+                   float* f0s, int* path_out, float* score_out, int carry_frame = 0, const float* prior = nullptr, float* carry_out = nullptr);
 int run_uniform_to_angle(tvc_ctx*, hipStream_t, float* u, int64_t n);
 // content_bound (optional): an upper bound of |content| (the prepared index's |max| when content came out of the kNN match): ONE float, or
 // with content_bound_stride = 1 one per utterance (a match against one index per utterance);

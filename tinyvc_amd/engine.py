@@ -13,7 +13,7 @@ import weakref
 import torch
 
 from . import _lib, spec
-from .stream_state import DENOISE_STATE, GATE_STATE, LIMITER_STATE, LOUDNESS_STATE, TRACK_STATE, Field, checked
+from .stream_state import CARRY_STATE, DENOISE_STATE, GATE_STATE, LIMITER_STATE, LOUDNESS_STATE, TRACK_STATE, Field, checked
 
 _F32 = torch.float32
 
@@ -100,6 +100,7 @@ _PROTECT = {
 _PATH = {
     False: ("tvc_workspace_bytes_path", "tvc_convert_path_f32"),
     True: ("tvc_workspace_bytes_ragged_path", "tvc_convert_ragged_path_f32"),
+    "carry": ("tvc_workspace_bytes_path", "tvc_convert_carry_f32"),      # the path's state from block to block: streams advance in lock step, no ragged form
 }
 
 
@@ -668,15 +669,26 @@ class Engine:
         state = checked(track, TRACK_STATE, S, self.device, "track.")      # the kernel indexes the state by (S, W): never past it
         return (start, n, track.window_frames, track.min_voiced, track.slew, *map(_ptr, state))
 
+    def _carry_args(self, carry, S, T):
+        """a PitchCarry's share of a call over S streams of T frames, checked on the host: (carry_frame, scores)"""
+        if carry.n_streams != S:
+            raise ValueError(f"carry: a carry of {carry.n_streams} streams for {S} rows")
+        if T <= carry.hop_frames:
+            raise ValueError(f"carry: hop_frames = {carry.hop_frames} must be below the call's T = {T} frames (frame hop_frames is the next window's first)")
+        state = checked(carry, CARRY_STATE, S, self.device, "carry.")      # the kernel indexes the state by (S, 512): never past it
+        return (carry.hop_frames, *map(_ptr, state))
+
     def _convert(self, form, wav, prepared, Ns, pitch_shift, noise_angle=None, lengths=None, weights=None, target_f0=None, out=None, shift_out=None,
-                 track=None, alpha=None, protect=None, path=None):
+                 track=None, alpha=None, protect=None, path=None, carry=None):
         """wav [B, L] converted toward the index (`form`, prepared, Ns, weights: _index_args) -> wave [B, L]; form "auto" / "track" ->
         (wave, shifts [B]).  "track": "auto" with the register taken from `track` (a PitchTrack: the streams' history), equal lengths only.
         "alpha": the table / blend call keeping the share alpha[b] of row b's own content features (alpha: _per_row); with target_f0 it is the
         "auto" call (-> (wave, shifts)), with `track` as well the "track" call.  "protect": the "alpha" call with protect[b] (_per_row) behind
         alpha, which may then be None (a = 0): the share rises to a + (1 - a) * protect[b] on the unvoiced frames of the f0 the call decodes.
         "path": the "protect" call (alpha and protect may both be None) with `path`, a PitchPath, behind protect: f0 is the Viterbi decode of the
-        call's own logits over each utterance, and everything behind the encoder reads that one.
+        call's own logits over each utterance, and everything behind the encoder reads that one.  `carry` (with "path", equal lengths only): a
+        PitchCarry of B streams - row b's decode starts from carry.scores[b] and leaves the best-predecessor values of frame carry.hop_frames
+        there, in place (tvc_convert_carry_f32).
         lengths: a ragged batch (row b holds an utterance of lengths[b] samples, a multiple of 480, zero-padded behind it; every utterance
         is converted over its OWN length).  pitch_shift: a float, or one per row for every form but "shared".  Every host check comes
         first, then the noise draw (which advances torch's generator), then device work: a refused call leaves no trace."""
@@ -686,6 +698,8 @@ class Engine:
         index, sized = self._index_args(form, prepared, Ns, weights, B)
         if ragged and (form == "track" or track is not None):
             raise ValueError("track: streams advance in lock step, there is no ragged form")
+        if carry is not None and (form != "path" or ragged):
+            raise ValueError("carry: the pitch path's state - it goes with form \"path\", and streams advance in lock step: there is no ragged form")
         found = form in ("auto", "track")      # the shifts are found on the device: pitch_shift is the offset, the applied shifts come back
         if form in ("alpha", "protect", "path"):      # the table / blend call with or without target registers (and, equal lengths, a tracker), plus the source's share
             found = target_f0 is not None
@@ -698,6 +712,8 @@ class Engine:
             else:
                 index += (_ptr(self._per_row(alpha, "alpha", B)) if alpha is not None else None,
                           _ptr(self._per_row(protect, "protect", B)) if protect is not None else None, ctypes.byref(path.settings()))
+                if carry is not None:
+                    index += self._carry_args(carry, B, L // spec.HOP)
             index += (_ptr(self._per_row(target_f0, "target_f0", B)) if found else None,)
             if not ragged:
                 index += self._track_args(track, B, L // spec.HOP) if track is not None else (0, 0, 0, 0, 0.0, None, None, None)
@@ -716,7 +732,7 @@ class Engine:
             shift_args += (_ptr(sh),)
         elif form in ("alpha", "protect", "path"):
             shift_args += (None,)
-        query, entry = _names(form, ragged)
+        query, entry = _names(form, "carry" if carry is not None else ragged)
         p, n = self._query_ws(query, B, L, *lens, *sized)
         head, tail = ((_ptr(wav), L, *lens), (B, p, n)) if ragged else ((_ptr(wav),), (B, L, p, n))
         self._ok(getattr(self.lib, entry)(self.ctx, self._stream(), *head, *index, *shift_args, _ptr(a), seed, _ptr(wave), *tail), entry)
@@ -757,12 +773,21 @@ class Engine:
         return self._convert("auto", wav, prepared, Ns, pitch_shift, noise_angle, lengths, weights, target_f0)
 
     # ---- the pitch path: a Viterbi decode of rows of logits (tvc_pitch_path_f32) ----
-    def pitch_path(self, logits, settings, row_start=None, pitch_shift=0.0, want_shifted=False):
+    def _carry_rows(self, t, name, rows):
+        """prior / carry_out of pitch_path as the kernel indexes it: a contiguous fp32 [rows, 512] tensor on the device, used in place"""
+        _check_dev(t, name, self.device)
+        if t.dtype != _F32 or tuple(t.shape) != (rows, spec.PITCH_CLASSES) or not t.is_contiguous():
+            raise ValueError(f"pitch_path: {name} must be a contiguous fp32 [rows = {rows}, {spec.PITCH_CLASSES}] tensor, got {t.dtype} {tuple(t.shape)}")
+        return t
+
+    def pitch_path(self, logits, settings, row_start=None, pitch_shift=0.0, want_shifted=False, prior=None, carry_out=None, carry_frame=0):
         """The pitch path of rows of logits (include/tinyvc_hip.h has the definition; `settings` a PitchPath): logits [B, 512, T] (every row
         a run of T columns), or a packed [512, Ttot] / [1, 512, Ttot] with row_start = rows + 1 ascending column numbers (row b =
         columns [row_start[b], row_start[b + 1])) -> (f0 [B, 1, T] or [1, 1, Ttot] fp32, path int32 of f0's shape, scores [rows, 512] = the
         last frame's normalised scores[, f0 shifted by pitch_shift - a float or one per row - when want_shifted]).  Columns outside every
-        row are 0."""
+        row are 0.  The carry (tvc_pitch_path_carry_f32): `prior` [rows, 512] is added, sanitised, to each row's first emissions, and
+        `carry_out` [rows, 512] receives the best-predecessor values of frame `carry_frame` >= 1, which every non-empty row must have;
+        contiguous fp32 device tensors used in place, either alone, or one tensor as both.  Neither is the call as it was."""
         lg = _prep(logits, "logits", self.device)
         if lg.dim() == 2:
             lg = lg[None]
@@ -780,13 +805,21 @@ class Engine:
         shift, shifts = pitch_shifts(pitch_shift, rows)
         I64 = ctypes.c_int64 * rows
         start, count = I64(*row_start[:-1]), I64(*(b - a for a, b in zip(row_start, row_start[1:])))
+        carried = ()
+        if prior is not None or carry_out is not None:
+            h = integer(carry_frame, "pitch_path", "carry_frame") if carry_out is not None else 0
+            if carry_out is not None and (h < 1 or any(0 < n <= h for n in count)):
+                raise ValueError(f"pitch_path: carry_frame = {h} must be >= 1 and every non-empty row must have more frames (rows of {sorted(set(count))})")
+            carried = (h, _ptr(self._carry_rows(prior, "prior", rows)) if prior is not None else None,
+                       _ptr(self._carry_rows(carry_out, "carry_out", rows)) if carry_out is not None else None)
         f0 = torch.zeros(B, 1, T, dtype=_F32, device=self.device)
         path = torch.zeros(B, 1, T, dtype=torch.int32, device=self.device)
         scores = torch.zeros(rows, spec.PITCH_CLASSES, dtype=_F32, device=self.device)
         out = torch.zeros_like(f0) if want_shifted else None
         p, n = self._query_ws("tvc_workspace_bytes_pitch_path", start, count, rows)
-        self._ok(self.lib.tvc_pitch_path_f32(self.ctx, self._stream(), _ptr(lg), start, count, rows, T, ctypes.byref(settings.settings()), shift, _floats(shifts),
-                                             _ptr(f0), _ptr(out), _ptr(path), _ptr(scores), p, n), "tvc_pitch_path_f32")
+        entry = "tvc_pitch_path_carry_f32" if carried else "tvc_pitch_path_f32"
+        self._ok(getattr(self.lib, entry)(self.ctx, self._stream(), _ptr(lg), start, count, rows, T, ctypes.byref(settings.settings()), *carried, shift,
+                                          _floats(shifts), _ptr(f0), _ptr(out), _ptr(path), _ptr(scores), p, n), entry)
         return (f0, path, scores, out) if want_shifted else (f0, path, scores)
 
     # ---- the pitch register of rows of f0, and the shift onto a target's (tvc_pitch_match_f32) ----

@@ -55,7 +55,7 @@ class Generator(HipModule):
 
     @torch.no_grad()
     def convert(self, wf, tgt, pitch_shift, f0_estimation="default", device=None, noise_angle=None, lengths=None, auto_pitch=None,
-                return_shift=False, track=None, alpha=None, protect=None, loudness=None, limit=None):
+                return_shift=False, track=None, alpha=None, protect=None, loudness=None, limit=None, carry=None):
         """generator.py:26-34: wf [B, L], tgt [1 or B, 768, N] -> converted waveform [B, L'] (L' = L
         padded to a multiple of 480).  `f0_estimation` / `device` are accepted and ignored exactly as
         in the reference - but for `f0_estimation='viterbi'` or a feature_retrieval.PitchPath (extension): f0 is then the pitch path, a
@@ -106,7 +106,11 @@ class Generator(HipModule):
         leaves above the ceiling, exactly.  One more launch (tvc_limit_f32) into a tensor of its own, with no host synchronisation and
         capturable, equal and ragged batches alike.  A ceiling in dBFS (a number, or B of them; inf: off), an fp32 [B] / [1] device tensor
         of LINEAR ceilings, or a feature_retrieval.Limiter with the settings (sub_frame must divide 480).  Every target form, with every
-        other keyword; None (the default) is the call without it, launch for launch.  The settings' defaults are guesses: nobody has listened."""
+        other keyword; None (the default) is the call without it, launch for launch.  The settings' defaults are guesses: nobody has listened.
+        `carry` (extension, with a pitch path): a feature_retrieval.PitchCarry of B streams - row b's path starts from the scores the stream's
+        last window left for this window's first frame, and leaves those of frame carry.hop_frames for the next (tvc_convert_carry_f32: the
+        state is read and written in place, on the device, inside the same launch).  Equal batches only; ValueError without a pitch path, with
+        `lengths=`, and for a carry of another size.  None (the default) is the call without it, launch for launch."""
         # 1. classify the target once; malformed targets, registers and shift lists are refused before any engine or device work
         B = wf.shape[0] if wf.dim() == 2 else 1
         auto = auto_pitch is not None and auto_pitch is not False
@@ -130,6 +134,15 @@ class Generator(HipModule):
         share = resolve_alpha(alpha, B) if alpha is not None else None
         guard = resolve_protect(protect, B) if protect is not None else None
         path = resolve_f0_estimation(f0_estimation)      # 'viterbi' or a PitchPath; every other name is None: the call it has always been
+        if carry is not None:
+            if path is None:
+                raise ValueError("carry needs f0_estimation='viterbi' or a PitchPath: the state it carries is the pitch path's")
+            if lengths is not None:
+                raise ValueError("carry with lengths: streams advance in lock step, there is no ragged form")
+            if carry.n_streams != B:
+                raise ValueError(f"carry: a carry of {carry.n_streams} streams for a batch of {B}")
+            if -(-wf.shape[-1] // 480) <= carry.hop_frames:
+                raise ValueError(f"carry: hop_frames = {carry.hop_frames} must be below the call's {-(-wf.shape[-1] // 480)} frames")
         level = resolve_loudness(loudness, B) if loudness is not None else None
         if level is not None and 480 % level[0].sub_frame:
             raise ValueError(f"loudness: sub_frame = {level[0].sub_frame} does not divide the 480-sample frames a call is padded to")
@@ -161,6 +174,8 @@ class Generator(HipModule):
                 rows["protect"] = protect_rows(guard, B, wf.device)
             if path is not None:
                 rows["path"] = path
+            if carry is not None:
+                rows["carry"] = carry
             res = eng._convert("path" if path is not None else "alpha" if guard is None else "protect", wf, blobs, ns, pitch, noise_angle, lens, w,
                                target_registers(regs, B, wf.device) if auto else None, track=track, **rows)
             res = res if return_shift or not auto else res[0]

@@ -18,8 +18,8 @@ import torch
 
 from ...engine import (SOLA_CROSS, SOLA_DELAY, SOLA_SEARCH, loudness_geometry, loudness_levels, pitch_shifts, sola_geometry, stream_denoise_geometry,
                        stream_gate_geometry, stream_resample_geometry)
-from ...stream_state import DENOISE_STATE, DOOR_STATE, GATE_STATE, LIMITER_STATE, LOUDNESS_STATE, TRACK_STATE, addresses, allocate, reset
-from ..tinyvc.feature_retrieval import (PitchTrack, alpha_rows, gpu_device, limit_ceiling, limiter_settings, protect_rows, resolve_alpha,
+from ...stream_state import CARRY_STATE, DENOISE_STATE, DOOR_STATE, GATE_STATE, LIMITER_STATE, LOUDNESS_STATE, TRACK_STATE, addresses, allocate, reset
+from ..tinyvc.feature_retrieval import (PitchCarry, PitchTrack, alpha_rows, check_f0_carry, gpu_device, limit_ceiling, limiter_settings, protect_rows, resolve_alpha,
                                         resolve_auto_pitch, resolve_f0_estimation, resolve_protect, target_form)
 from .generator import Generator
 
@@ -386,8 +386,14 @@ class BatchedStreamInfer:
     `self.protect`, a [S] device tensor like `self.alpha` (`stream.protect.fill_(...)` / `copy_(...)` replay the same graph); with or without
     alpha; None (the default) is the stream as it was.
     `f0_estimation` (convert's): 'viterbi' or a feature_retrieval.PitchPath decodes every window's pitch as one path over its own frames
-    (each window afresh: no state travels from block to block, the window's left context is what steadies the emitted frames); held as
+    (each window afresh unless f0_carry is set; the window's left context is what steadies the emitted frames); held as
     `self.f0_estimation`, and its settings - host values baked into the launch - are part of the graph key.  Every other name is ignored.
+    `f0_carry` (with a pitch path; block_size in whole 480-sample frames): True carries the path's scores from block to block - the window
+    advances by block_size / 480 frames, so the best-predecessor values of that frame of one window are the prior of the next window's
+    first frame, the forward recursion of an online Viterbi - in `pitch_carry`, a feature_retrieval.PitchCarry built in init_buffer (or the
+    one given here); `stream.pitch_carry.reset([i])` between blocks starts stream i's path afresh and keeps a captured graph.  False (the
+    default) is the stream as it was, launch for launch.  Every window has logits of its own, so the carried scores are a prior, not the
+    decode of any one tensor; nobody has listened.
     `door` (a StreamDoor of the same n_streams and block_size): audio_callback_pcm takes the clients' int16 blocks at the door's rates.
     `gate` (a StreamGate of the same n_streams and block_size): every emitted block goes through the noise gate, one launch behind SOLA (and
     in front of the door), driven by the input window and `last_shift` on the device; the SOLA buffer and the window stay ungated.
@@ -413,10 +419,12 @@ class BatchedStreamInfer:
     shorter than the three sizes say, and a look-ahead shorter than the pad is refused."""
 
     def __init__(self, generator: Generator, n_streams=1, target=None, pitch_shift=0., device=None,
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, denoise=None, loudness=None, gate=None, limiter=None, door=None,
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, denoise=None, loudness=None, gate=None, limiter=None, f0_carry=False, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         self.input_size, _ = check_window(block_size, extra_size, crossfade_size, sola_search_size, last_delay_size,
                                            auto_pitch is not None and auto_pitch is not False)
+        self.f0_carry = check_f0_carry(f0_carry, f0_estimation, block_size, n_streams)      # refused here, before anything is allocated
+        self.pitch_carry = self.f0_carry if isinstance(self.f0_carry, PitchCarry) else None
         share = resolve_alpha(alpha, n_streams) if alpha is not None else None      # refused here, before anything is allocated
         guard = resolve_protect(protect, n_streams) if protect is not None else None
         self.n_streams, self.block_size = n_streams, block_size
@@ -492,8 +500,8 @@ class BatchedStreamInfer:
     def _stages(self):
         """the stages of these streams that keep state on the device, in block order: (name, stage, its table in stream_state)"""
         every = (("track", self.pitch_track if self.auto_pitch is not None else None, TRACK_STATE), ("door", self.door, DOOR_STATE),
-                 ("denoise", self.denoise, DENOISE_STATE), ("loudness", self.loudness, LOUDNESS_STATE), ("gate", self.gate, GATE_STATE),
-                 ("limiter", self.limiter, LIMITER_STATE))
+                 ("denoise", self.denoise, DENOISE_STATE), ("carry", self.pitch_carry, CARRY_STATE), ("loudness", self.loudness, LOUDNESS_STATE),
+                 ("gate", self.gate, GATE_STATE), ("limiter", self.limiter, LIMITER_STATE))
         return [s for s in every if s[1] is not None]
 
     def init_buffer(self):
@@ -504,6 +512,7 @@ class BatchedStreamInfer:
         for name in ("door", "gate", "denoise", "loudness", "limiter"):      # (before anything is allocated) the stages against the attributes as they stand now
             self._fits(name, getattr(self, name))
         self._bound_ceiling()
+        self.f0_carry = check_f0_carry(self.f0_carry, self.f0_estimation, self.block_size, self.n_streams)
         if self.gate is not None:
             check_gate_lookahead(self.gate.lookahead_size, self.crossfade_size, self.last_dilay_size, self.pad_size)
         self._geometry = self._attributes()
@@ -514,6 +523,10 @@ class BatchedStreamInfer:
         self._calls = 0
         if self.auto_pitch is not None and self._own_track:      # the block's own frames: they have their full right context and are the audio about to be played
             self.pitch_track = PitchTrack(self.n_streams, self.block_size // 480, self.last_dilay_size // 480, device=self.device)
+        if self.f0_carry is True:      # the window advances by the block's frames: that frame of this window is the next one's first
+            self.pitch_carry = PitchCarry(self.n_streams, self.block_size // FRAME, device=self.device)
+        else:
+            self.pitch_carry = self.f0_carry
         if self.door is not None:
             self.door.prepare(self.generator.engine(self.device))
         for _, stage, _ in self._stages():
@@ -535,11 +548,12 @@ class BatchedStreamInfer:
         pshift = None
         if self.auto_pitch is None:
             y = self.generator.convert(self.input_wav, self.target, self.pitch_shift, device=self.device,
-                                       f0_estimation=self.f0_estimation, noise_angle=noise_angle, alpha=self.alpha, protect=self.protect)
+                                       f0_estimation=self.f0_estimation, noise_angle=noise_angle, alpha=self.alpha, protect=self.protect,
+                                       carry=self.pitch_carry)
         else:
             y, pshift = self.generator.convert(self.input_wav, self.target, self.pitch_shift, device=self.device, f0_estimation=self.f0_estimation,
                                                noise_angle=noise_angle, auto_pitch=self.auto_pitch, return_shift=True, track=self.pitch_track,
-                                               alpha=self.alpha, protect=self.protect)
+                                               alpha=self.alpha, protect=self.protect, carry=self.pitch_carry)
         eng = self.generator.engine(self.device)
         out, shift = eng.sola(y, self.sola_buffer, self.fade_in_window, self.block_size, self.use_phase_vocoder, want_shift=True,
                               crossfade=self.crossfade_size, search=self.sola_search_size, delay=self.last_dilay_size)
@@ -563,7 +577,7 @@ class BatchedStreamInfer:
         """Everything a captured step bakes in as raw device pointers: the packed weights (re-packed - and the old arena
         freed - when a parameter changes), the engine's scratch workspace (re-allocated when another call needs a bigger
         one), the prepared index riding on `target`, plus the scalars captured by value.  Every stage present - the
-        tracker, the door, the suppressor (denoise), the loudness match, the gate, the limiter - adds (its name, WHERE the tensors of its table in stream_state live, its
+        tracker, the door, the suppressor (denoise), the pitch path's carry, the loudness match, the gate, the limiter - adds (its name, WHERE the tensors of its table in stream_state live, its
         params()): the table lists every tensor whose pointer reaches the library, so none can be passed on and left out here.  With
         auto_pitch also WHERE the target registers live, with alpha / protect where the shares live.  Never a value: the kernels read those at replay,
         so a reset(), registers.copy_(...), threshold_db.fill_(...) or a stream's history advancing keeps the graph.  The tail's geometry is
@@ -657,7 +671,7 @@ class StreamInfer(BatchedStreamInfer):
     """Single stream with the reference's constructor and 1-D buffers (stream.py:31-57)."""
 
     def __init__(self, generator: Generator, target=None, pitch_shift=0., device=torch.device("cpu"),
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, denoise=None, loudness=None, gate=None, limiter=None, door=None,
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, denoise=None, loudness=None, gate=None, limiter=None, f0_carry=False, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         dev = torch.device(device)
         if dev.type != "cuda":
@@ -665,7 +679,7 @@ class StreamInfer(BatchedStreamInfer):
         super().__init__(generator, n_streams=1, target=target, pitch_shift=pitch_shift, device=dev, block_size=block_size, extra_size=extra_size,
                          use_phase_vocoder=use_phase_vocoder, f0_estimation=f0_estimation, use_graph=use_graph, alpha=alpha, protect=protect, denoise=denoise, gate=gate,
                          limiter=limiter, door=door, crossfade_size=crossfade_size, sola_search_size=sola_search_size, last_delay_size=last_delay_size,
-                         auto_pitch=auto_pitch, pitch_track=pitch_track, loudness=loudness)
+                         auto_pitch=auto_pitch, pitch_track=pitch_track, loudness=loudness, f0_carry=f0_carry)
 
     @torch.no_grad()
     def audio_callback(self, block, noise_angle=None):

@@ -443,6 +443,52 @@ class PitchPath:
         return "PitchPath(step={}, band={}, jump={}, voicing={}, refine={})".format(*self.params())
 
 
+class PitchCarry:
+    """The pitch path's state of a set of streams that advance in lock step (tvc_pitch_path_carry_f32 / tvc_convert_carry_f32; the
+    definition is in include/tinyvc_hip.h): a stream's window advances by `hop_frames` = block_size / 480 frames per block, so frame
+    hop_frames of one window is frame 0 of the next - the same instant.
+      scores [S, 512] fp32   the best-predecessor values of that frame (maximum exactly 0; zeros: a fresh path), on the device
+    Every block the path kernel adds a stream's scores to its window's first emissions and leaves the new ones in their place: the forward
+    recursion of an online Viterbi, so a window no longer starts from a flat prior.  The scores are a prior whose spread the costs bound
+    (no class lies further than about max(jump, voicing) behind the best), not the decode of any single logits tensor: every window has
+    logits of its own.  Whatever is written into `scores`, the kernel takes values <= 0 only and counts the rest as 0.  Every argument is
+    checked before anything is allocated (ValueError)."""
+
+    def __init__(self, n_streams, hop_frames, device=None):
+        for x, name in ((n_streams, "n_streams"), (hop_frames, "hop_frames")):
+            if isinstance(x, bool) or not isinstance(x, int) or x < 1 or x > 0x7fffffff:
+                raise ValueError(f"PitchCarry: {name} must be an integer >= 1, got {x!r}")
+        self.n_streams, self.hop_frames = n_streams, hop_frames
+        self.device = gpu_device(device, "PitchCarry: the state lives on the GPU (device='cpu' builds a carry no engine will take)", cpu_ok=True)
+        stream_state.allocate(self, stream_state.CARRY_STATE, self.device)
+
+    def params(self):
+        """the host values a captured block bakes in"""
+        return (self.hop_frames,)
+
+    def reset(self, streams=None):
+        """Start the path of every stream, or of the listed ones, afresh: in-place ops on the state tensor, so it works between replays of a
+        captured graph (which reads it when it runs)."""
+        stream_state.reset(self, stream_state.CARRY_STATE, streams)
+
+
+def check_f0_carry(f0_carry, f0_estimation, block_size, n_streams):
+    """a stream's f0_carry against everything that can be said on the host (ValueError, before anything is allocated) -> None (no carry),
+    True (build one in init_buffer) or the PitchCarry given"""
+    if f0_carry is None or f0_carry is False:
+        return None
+    if f0_carry is not True and not isinstance(f0_carry, PitchCarry):
+        raise ValueError(f"f0_carry: True, False or a feature_retrieval.PitchCarry, got {type(f0_carry).__name__}")
+    if resolve_f0_estimation(f0_estimation) is None:
+        raise ValueError("f0_carry needs f0_estimation='viterbi' or a PitchPath: the state it carries is the pitch path's")
+    if block_size % 480:
+        raise ValueError(f"f0_carry: block_size = {block_size} is not a whole number of 480-sample frames (the window must advance by whole frames)")
+    if f0_carry is not True and (f0_carry.n_streams, f0_carry.hop_frames) != (n_streams, block_size // 480):
+        raise ValueError(f"f0_carry: a carry of {f0_carry.n_streams} streams advancing {f0_carry.hop_frames} frames, the streams are {n_streams} "
+                         f"advancing {block_size // 480}")
+    return f0_carry
+
+
 def resolve_f0_estimation(f0_estimation):
     """convert's f0_estimation: 'viterbi' -> PitchPath() with the defaults, a PitchPath -> itself, anything else (the reference's 'default',
     'fcpe', 'dio', 'harvest', ...) -> None: accepted and ignored exactly as in the reference"""
@@ -463,6 +509,24 @@ def add_f0_arguments(parser, choices=None):
                             ("--f0-voicing", float, "cost of a move between unvoiced and voiced (default 3)"),
                             ("--f0-refine", int, "classes on each side of the path's that share the frequency, 0 .. 4 (default 2)")):
         parser.add_argument(flag, type=typ, default=None, help=f"-f0-est viterbi: {what}.  The defaults are guesses: nobody has listened")
+
+
+def add_f0_carry_argument(parser):
+    """`--f0-carry` for the entry scripts that stream"""
+    parser.add_argument("--f0-carry", action="store_true",
+                        help="-f0-est viterbi in a stream: carry the path's scores from block to block (an online Viterbi) instead of decoding "
+                             "every window from a flat start; block_size must be whole 480-sample frames.  Nobody has listened")
+
+
+def f0_carry_keywords(args, script):
+    """what `--f0-carry` adds to the script's stream keywords: nothing when absent, else {"f0_carry": True} and one printed line; the flag
+    without `-f0-est viterbi` ends the script"""
+    if not getattr(args, "f0_carry", False):
+        return {}
+    if args.f0_estimation != "viterbi":
+        sys.exit(f"{script}: --f0-carry belongs to -f0-est viterbi")
+    print("Carrying the pitch path's scores from block to block (nobody has listened)")
+    return {"f0_carry": True}
 
 
 def f0_keywords(args, script):
