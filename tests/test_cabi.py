@@ -1,5 +1,6 @@
 """The C ABI boundary, without a GPU: libtinyvc_hip.so loads, exports every prototype declared in
 include/tinyvc_hip.h, and the ctypes table in tinyvc_amd/_lib.py mirrors the header one to one."""
+import ctypes
 import os
 import re
 
@@ -36,6 +37,52 @@ def test_ctypes_table_matches_header(lib):
     assert set(decl) == set(_lib.SIGNATURES), set(decl) ^ set(_lib.SIGNATURES)
     for name, args in decl.items():
         assert len(args) == len(_lib.SIGNATURES[name][1]), f"{name}: header has {len(args)} parameters"
+
+
+def test_prototypes_carry_the_headers_parameter_names():
+    """every function's parameters are declared under the header's names, in the header's order: a pointer swapped with its neighbour no
+    longer passes; and SIGNATURES, which load_library declares, is nothing but PROTOTYPES without the names"""
+    decl = header_functions()
+    assert set(decl) == set(_lib.PROTOTYPES)
+    for name, args in decl.items():
+        names = [re.findall(r"[A-Za-z_]\w*", a)[-1] for a in args]
+        assert [n for n, _t in _lib.PROTOTYPES[name][1]] == names, name
+    assert _lib.SIGNATURES == {name: (res, [t for _n, t in params]) for name, (res, params) in _lib.PROTOTYPES.items()}
+
+
+# the conversion ladder: the 16 conversions, their 14 workspace queries, the 5 matches
+LADDER = sorted(n for n in _lib.PROTOTYPES if re.fullmatch(
+    r"tvc_convert\w*_f32|tvc_knn_match(_multi|_blend|_alpha|_protect)?_f32|tvc_workspace_bytes(_ragged)?(_multi|_blend|_auto|_alpha|_protect|_path)?", n))
+
+
+def test_the_ladder_is_whole():
+    assert [sum(n.startswith(p) for n in LADDER) for p in ("tvc_convert", "tvc_workspace_bytes", "tvc_knn_match")] == [16, 14, 5]
+
+
+@pytest.mark.parametrize("entry", LADDER)
+def test_arguments_orders_values_by_name(entry):
+    """_lib.arguments: the entry's declared names, each with a sentinel of its own, come back in the header's order whatever else the dict
+    holds at its "off" value; a declared name without a value raises, and so does a value the entry has no parameter for"""
+    names = [re.findall(r"[A-Za-z_]\w*", a)[-1] for a in header_functions()[entry]]
+    everything = {n for e in LADDER for n, _t in _lib.PROTOTYPES[e][1]}
+    named = {n: off for n, off in zip(sorted(everything - set(names)), [None, 0, 0.0] * len(everything))}
+    named.update((n, object()) for n in names)
+    assert _lib.arguments(entry, named) == tuple(named[n] for n in names)
+    assert _lib.arguments(entry, {n: named[n] for n in names}) == tuple(named[n] for n in names)
+    for n in names:
+        with pytest.raises(TypeError, match=f"`{n}`"):
+            _lib.arguments(entry, {k: v for k, v in named.items() if k != n})
+    for n in sorted(everything - set(names)):
+        for on in (1, 0.5, object()):
+            with pytest.raises(TypeError, match=f"`{n}`"):
+                _lib.arguments(entry, dict(named, **{n: on}))
+
+
+def test_arguments_refuses_alpha_at_the_multi_entry():
+    named = dict.fromkeys((n for n, _t in _lib.PROTOTYPES["tvc_convert_multi_f32"][1]), 1)
+    assert len(_lib.arguments("tvc_convert_multi_f32", dict(named, alpha=None))) == len(named)
+    with pytest.raises(TypeError, match="tvc_convert_multi_f32 has no parameter `alpha`"):
+        _lib.arguments("tvc_convert_multi_f32", dict(named, alpha=ctypes.c_void_p(4096)))
 
 
 def test_version_and_null_safety(lib):

@@ -299,7 +299,7 @@ def test_stream_push_equals_roll_past_32768_samples(gen, n):
 
 def test_workspace_of_exactly_the_measured_peak_and_one_byte_less(gen):
     """Every entry measures its workspace with a walk that launches nothing (ws.dry) before its launching walk, and checks behind the second
-    that it took no more (api.hip run_walks).  tvc_workspace_bytes - 4096 is that peak: a conversion in exactly it equals one in the engine's
+    that it took no more (api.h run_walks).  tvc_workspace_bytes - 4096 is that peak: a conversion in exactly it equals one in the engine's
     own workspace bit for bit, and one byte less is refused with TVC_ERR_WORKSPACE before anything launches (the output keeps its NaN fill).
     The same for a ragged call with tvc_workspace_bytes_ragged - 4096."""
     import ctypes

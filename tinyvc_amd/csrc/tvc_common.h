@@ -212,7 +212,7 @@ inline int fail(tvc_ctx* ctx, int code, const char* fmt, ...) {
         if (rc_ != 0) return rc_; \
     } while (0)
 
-// Bump allocator over the caller's workspace; in dry mode it only measures (api.hip run_walks: every entry walks its driver dry, then for
+// Bump allocator over the caller's workspace; in dry mode it only measures (api.h run_walks: every entry walks its driver dry, then for
 // real).  The drivers make the same get() calls in both walks - only launches, memsets, events and uploads look at `dry` -: equal peaks.
 struct Ws {
     char* base;
@@ -388,7 +388,7 @@ int run_frame_share_rows(tvc_ctx*, hipStream_t, const float* f0, const std::vect
 // slot[utterance] = max |ssl| of that utterance (slot already zeroed on this stream; encoder.hip)
 int run_ssl_amax(tvc_ctx*, hipStream_t, const float* ssl, int B, int T, float* slot);
 
-// ---- one conversion, as the entries describe it to convert_impl (api.hip) and to the ragged batch loop (ragged.hip) -----------
+// ---- one conversion, as the entries describe it to convert_impl (api_convert.hip) and to the ragged batch loop (ragged.hip) -----------
 // What the rows of a call search: ONE prepared index, or host tables of one per row of the caller's batch (tvc_*_multi) - never both.
 // The blend form (tvc_*_blend) is a per-row table with M terms per row: blobs / Ns are [rows][M] row-major, `weights` the device array
 // [rows][M] in the caller's row order.

@@ -3,6 +3,7 @@
 PyTorch is used here for device memory (tensors in, tensors out), the current HIP stream and the
 scratch workspace; every computation is a call into libtinyvc_hip.so.
 """
+import collections
 import ctypes
 import math
 import numbers
@@ -113,7 +114,14 @@ def _names(form, ragged=None):
     return _MATCH[form] if ragged is None else _CONVERT[form, ragged]
 
 
-_RESAMPLE_STATE = (Field("state", _F32, "hist", 0.0),)      # what stream_resample takes of a door: one side's history
+# a tracker's and a carry's share of a call, and every optional parameter of a conversion at its "off" value: the C parameters' names
+_TrackArgs = collections.namedtuple("_TrackArgs", "start n W min_voiced slew ring count auto_shift")
+_CarryArgs = collections.namedtuple("_CarryArgs", "carry_frame carry")
+_FEATURES_OFF = dict(lens=None, M=0, weights=None, alpha=None, protect=None, path=None, target_f0=None, shift_out=None,
+                     **_CarryArgs(0, None)._asdict(), **_TrackArgs(0, 0, 0, 0, 0.0, None, None, None)._asdict())
+
+
+_RESAMPLE_STATE =(Field("state", _F32, "hist", 0.0),)      # what stream_resample takes of a door: one side's history
 STREAM_RESAMPLE_LDS_FLOATS = 16384      # TVC_STREAM_RESAMPLE_LDS_FLOATS of tinyvc_hip.h: a stream's history + block, staged in 64 KiB of LDS
 
 
@@ -297,11 +305,13 @@ class Engine:
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return self._ws
 
-    def _query_ws(self, query, *args):
-        """Ask the tvc_workspace_bytes* function `query` what the call described by `args` needs and grow the workspace to it ->
-        (pointer, size): the last two arguments of the entry that query belongs to."""
+    def _query_ws(self, query, *args, **named):
+        """Ask the tvc_workspace_bytes* function `query` what the call described by `args` (in its order), or by `named` (under its
+        parameters' names: _lib.arguments), needs and grow the workspace to it -> (pointer, size): the last two arguments of the entry
+        that query belongs to."""
         need = ctypes.c_size_t()
-        self._ok(getattr(self.lib, query)(self.ctx, *args, ctypes.byref(need)), query)
+        args = _lib.arguments(query, dict(named, ctx=self.ctx, out_bytes=ctypes.byref(need))) if named else (self.ctx, *args, ctypes.byref(need))
+        self._ok(getattr(self.lib, query)(*args), query)
         ws = self._grow_ws(need.value)
         return _ptr(ws), ctypes.c_size_t(ws.numel())
 
@@ -561,19 +571,20 @@ class Engine:
         return t
 
     def _index_args(self, form, prepared, Ns, weights, B):
-        """The index of a call, checked on the host -> (what the entry takes for it, what its workspace query takes for it).  shared:
-        (prepared, Ns) = one blob and its N; table: one blob and N per row; blend: weights [B, M] on the device, prepared / Ns row-major
-        [B * M]; auto, track, alpha, protect, path: the blend form, or with weights None the table form as M = 1."""
+        """The index of a call, checked on the host -> (what the entry takes for it, what its workspace query takes for it), each under
+        the C parameters' names.  shared: (prepared, Ns) = one blob and its N; table: one blob and N per row; blend: weights [B, M] on the
+        device, prepared / Ns row-major [B * M]; auto, track, alpha, protect, path: the blend form, or with weights None the table form
+        as M = 1."""
         if form == "shared":
-            return (_ptr(prepared), Ns), (int(max(Ns, 4)),)
+            return dict(prepared=_ptr(prepared), N=Ns), dict(N=int(max(Ns, 4)))
         if form == "table":
             blobs, ns = self._table(prepared, Ns, B)
-            return (blobs, ns), (ns,)
+            return dict(prepared=blobs, N=ns), dict(N=ns)
         if form in ("auto", "track", "alpha", "protect", "path") and weights is None:
             blobs, ns = self._table(prepared, Ns, B)
-            return (blobs, ns, 1, None), (ns, 1)
+            return dict(prepared=blobs, N=ns, M=1, weights=None), dict(N=ns, M=1)
         blobs, ns, M = self._blend_args(prepared, Ns, weights, B)
-        return (blobs, ns, M, _ptr(weights)), (ns, M)
+        return dict(prepared=blobs, N=ns, M=M, weights=_ptr(weights)), dict(N=ns, M=M)
 
     @staticmethod
     def _lens(lengths, B):
@@ -600,22 +611,24 @@ class Engine:
         B, C, T = src.shape
         if C != spec.SSL_DIM:
             raise ValueError(f"source must have {spec.SSL_DIM} channels")
-        index, sized = self._index_args(form, prepared, Ns, weights, B)
-        head = (_ptr(src),)
+        named, sized = self._index_args(form, prepared, Ns, weights, B)
+        named.update(src=_ptr(src), B=B, T=T)
         if form == "alpha":
-            index += (_ptr(self._per_row(alpha, "alpha", B)),)
+            named["alpha"] = _ptr(self._per_row(alpha, "alpha", B))
         elif form == "protect":
             f0 = _prep(f0, "f0", self.device)
             if f0.numel() != B * T or f0.shape[0] != B:
                 raise ValueError(f"f0 must hold one value per frame, [B = {B}, 1, T = {T}] or [B, T], got {tuple(f0.shape)}")
-            index += (_ptr(self._per_row(alpha, "alpha", B)) if alpha is not None else None, _ptr(self._per_row(protect, "protect", B)))
-            head += (_ptr(f0),)
+            named["alpha"] = _ptr(self._per_row(alpha, "alpha", B)) if alpha is not None else None
+            named["protect"] = _ptr(self._per_row(protect, "protect", B))
+            named["f0"] = _ptr(f0)
         out = torch.empty_like(src)
-        terms = sized[1:]      # (M,) for a blend, else ()
+        terms = (sized["M"],) if "M" in sized else ()      # a blend's terms
         idx = torch.empty(*terms, B, T, 4, dtype=torch.int64, device=self.device) if want_indices else None
         query, entry = _names(form)
-        p, n = self._query_ws(query, B, T * spec.HOP, *sized)
-        self._ok(getattr(self.lib, entry)(self.ctx, self._stream(), *head, *index, _ptr(out), _ptr(idx), B, T, p, n), entry)
+        named["ws"], named["ws_bytes"] = self._query_ws(query, B=B, L=T * spec.HOP, **sized)
+        named.update(ctx=self.ctx, stream=self._stream(), out=_ptr(out), idx_out=_ptr(idx))
+        self._ok(getattr(self.lib, entry)(*_lib.arguments(entry, named)), entry)
         return (out, idx) if want_indices else out
 
     def knn_match(self, src, prepared, N, want_indices=False):
@@ -662,21 +675,21 @@ class Engine:
 
     # ---- convert: one driver, the eight public forms forward to it ----
     def _track_args(self, track, S, T):
-        """a PitchTrack's share of a call over S streams of T frames, checked on the host: (start, n, W, min_voiced, slew, ring, count, auto)"""
+        """a PitchTrack's share of a call over S streams of T frames, checked on the host, under the C parameters' names (and in their order)"""
         if track.n_streams != S:
             raise ValueError(f"track: a tracker of {track.n_streams} streams for {S} rows")
         start, n = track.columns(T)
         state = checked(track, TRACK_STATE, S, self.device, "track.")      # the kernel indexes the state by (S, W): never past it
-        return (start, n, track.window_frames, track.min_voiced, track.slew, *map(_ptr, state))
+        return _TrackArgs(start, n, track.window_frames, track.min_voiced, track.slew, *map(_ptr, state))
 
     def _carry_args(self, carry, S, T):
-        """a PitchCarry's share of a call over S streams of T frames, checked on the host: (carry_frame, scores)"""
+        """a PitchCarry's share of a call over S streams of T frames, checked on the host, under the C parameters' names"""
         if carry.n_streams != S:
             raise ValueError(f"carry: a carry of {carry.n_streams} streams for {S} rows")
         if T <= carry.hop_frames:
             raise ValueError(f"carry: hop_frames = {carry.hop_frames} must be below the call's T = {T} frames (frame hop_frames is the next window's first)")
         state = checked(carry, CARRY_STATE, S, self.device, "carry.")      # the kernel indexes the state by (S, 512): never past it
-        return (carry.hop_frames, *map(_ptr, state))
+        return _CarryArgs(carry.hop_frames, *map(_ptr, state))
 
     def _convert(self, form, wav, prepared, Ns, pitch_shift, noise_angle=None, lengths=None, weights=None, target_f0=None, out=None, shift_out=None,
                  track=None, alpha=None, protect=None, path=None, carry=None):
@@ -691,51 +704,55 @@ class Engine:
         there, in place (tvc_convert_carry_f32).
         lengths: a ragged batch (row b holds an utterance of lengths[b] samples, a multiple of 480, zero-padded behind it; every utterance
         is converted over its OWN length).  pitch_shift: a float, or one per row for every form but "shared".  Every host check comes
-        first, then the noise draw (which advances torch's generator), then device work: a refused call leaves no trace."""
+        first, then the noise draw (which advances torch's generator), then device work: a refused call leaves no trace.
+        Every value is computed once, under the name of the C parameter it is for (a feature the call lacks keeps its "off" value); the
+        entry takes the ones it declares (_lib.arguments)."""
         ragged = lengths is not None
         wav, B, L = self._rows(wav, ragged)
-        lens = (self._lens(lengths, B),) if ragged else ()
+        T = L // spec.HOP
+        named = dict(_FEATURES_OFF, wav=_ptr(wav), B=B)
+        named["Lmax" if ragged else "L"] = L
+        if ragged:
+            named["lens"] = self._lens(lengths, B)
         index, sized = self._index_args(form, prepared, Ns, weights, B)
+        named.update(index)
+        if form == "shared":
+            named["prepared_index"] = named.pop("prepared")      # the conversion's name for the stage call's `prepared`
         if ragged and (form == "track" or track is not None):
             raise ValueError("track: streams advance in lock step, there is no ragged form")
         if carry is not None and (form != "path" or ragged):
             raise ValueError("carry: the pitch path's state - it goes with form \"path\", and streams advance in lock step: there is no ragged form")
         found = form in ("auto", "track")      # the shifts are found on the device: pitch_shift is the offset, the applied shifts come back
-        if form in ("alpha", "protect", "path"):      # the table / blend call with or without target registers (and, equal lengths, a tracker), plus the source's share
+        shares = form in ("alpha", "protect", "path")      # the table / blend call with or without target registers (and, equal lengths, a tracker), plus the source's share
+        if shares:
             found = target_f0 is not None
             if track is not None and not found:
                 raise ValueError("track needs target_f0: the tracker finds the register the automatic shift starts from")
-            if form == "alpha":
-                index += (_ptr(self._per_row(alpha, "alpha", B)),)
-            elif form == "protect":
-                index += (_ptr(self._per_row(alpha, "alpha", B)) if alpha is not None else None, _ptr(self._per_row(protect, "protect", B)))
-            else:
-                index += (_ptr(self._per_row(alpha, "alpha", B)) if alpha is not None else None,
-                          _ptr(self._per_row(protect, "protect", B)) if protect is not None else None, ctypes.byref(path.settings()))
+            if form == "alpha" or alpha is not None:
+                named["alpha"] = _ptr(self._per_row(alpha, "alpha", B))
+            if form == "protect" or (form == "path" and protect is not None):
+                named["protect"] = _ptr(self._per_row(protect, "protect", B))
+            if form == "path":
+                named["path"] = ctypes.byref(path.settings())
                 if carry is not None:
-                    index += self._carry_args(carry, B, L // spec.HOP)
-            index += (_ptr(self._per_row(target_f0, "target_f0", B)) if found else None,)
-            if not ragged:
-                index += self._track_args(track, B, L // spec.HOP) if track is not None else (0, 0, 0, 0, 0.0, None, None, None)
-        elif found:
-            index += (_ptr(self._per_row(target_f0, "target_f0", B)),)
-        if form == "track":
-            index += self._track_args(track, B, L // spec.HOP)
-        shift, shifts = pitch_shifts(pitch_shift, B)
+                    named.update(self._carry_args(carry, B, T)._asdict())
+        if found:
+            named["target_f0"] = _ptr(self._per_row(target_f0, "target_f0", B))
+        if form == "track" or (shares and track is not None):
+            named.update(self._track_args(track, B, T)._asdict())
+        named["pitch_shift"], shifts = pitch_shifts(pitch_shift, B)
         if form == "shared" and shifts is not None:
             raise ValueError("pitch_shift: one shared index takes one shift (a shift per row takes an index per row)")
-        shift_args = (shift,) if form == "shared" else (shift, _floats(shifts))
-        a, seed = self._angle(noise_angle, B, L // spec.HOP)
+        named["pitch_shifts"] = _floats(shifts)
+        a, named["seed"] = self._angle(noise_angle, B, T)
         wave = out if out is not None else torch.empty(B, L, dtype=_F32, device=self.device)
         if found:
             sh = shift_out if shift_out is not None else torch.empty(B, dtype=_F32, device=self.device)
-            shift_args += (_ptr(sh),)
-        elif form in ("alpha", "protect", "path"):
-            shift_args += (None,)
+            named["shift_out"] = _ptr(sh)
         query, entry = _names(form, "carry" if carry is not None else ragged)
-        p, n = self._query_ws(query, B, L, *lens, *sized)
-        head, tail = ((_ptr(wav), L, *lens), (B, p, n)) if ragged else ((_ptr(wav),), (B, L, p, n))
-        self._ok(getattr(self.lib, entry)(self.ctx, self._stream(), *head, *index, *shift_args, _ptr(a), seed, _ptr(wave), *tail), entry)
+        named["ws"], named["ws_bytes"] = self._query_ws(query, B=B, lens=named["lens"], **{"Lmax" if ragged else "L": L}, **sized)
+        named.update(ctx=self.ctx, stream=self._stream(), noise_angle=_ptr(a), wave=_ptr(wave))
+        self._ok(getattr(self.lib, entry)(*_lib.arguments(entry, named)), entry)
         return (wave, sh) if found else wave
 
     def convert(self, wav, prepared, N, pitch_shift, noise_angle=None, out=None):

@@ -2,8 +2,12 @@
     TVC_LIB_PATH=$PWD/libA.so python tools/ab_equal.py dump /tmp/a.npz
     TVC_LIB_PATH=$PWD/libB.so python tools/ab_equal.py dump /tmp/b.npz
     python tools/ab_equal.py cmp /tmp/a.npz /tmp/b.npz
+or of two commits: copy this file into a checkout of the other one and dump there (it uses the public API only).
 Dumps encoder (ssl, logits, f0), decoder and whole-path outputs at the shapes that pick different kernels / tilings: the bench batch,
-one utterance, a streaming block (32 x 28 frames), odd lengths, a 2000-frame utterance and a ragged batch."""
+one utterance, a streaming block (32 x 28 frames), odd lengths, a 2000-frame utterance and a ragged batch; then the conversion ladder
+(dump_ladder): one conversion per tvc_convert*_f32 entry, the matches, the workspace queries' sizes, and the (rc, tvc_last_error) of
+calls that a host check refuses."""
+import ctypes
 import os
 import sys
 
@@ -13,6 +17,143 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+# the parameters of the entries the refused calls go to, between (ctx, stream) and (ws, ws_bytes), in the header's order
+ORDER = {
+    "tvc_convert_blend_f32": "wav prepared N M weights pitch_shift pitch_shifts noise_angle seed wave B L",
+    "tvc_convert_auto_f32": "wav prepared N M weights target_f0 pitch_shift pitch_shifts shift_out noise_angle seed wave B L",
+    "tvc_convert_track_f32": "wav prepared N M weights target_f0 start n W min_voiced slew ring count auto_shift pitch_shift pitch_shifts shift_out noise_angle seed "
+                             "wave B L",
+    "tvc_convert_alpha_f32": "wav prepared N M weights alpha target_f0 start n W min_voiced slew ring count auto_shift pitch_shift pitch_shifts shift_out noise_angle "
+                             "seed wave B L",
+    "tvc_convert_carry_f32": "wav prepared N M weights alpha protect path carry_frame carry target_f0 start n W min_voiced slew ring count auto_shift pitch_shift "
+                             "pitch_shifts shift_out noise_angle seed wave B L",
+    "tvc_convert_ragged_path_f32": "wav Lmax lens prepared N M weights alpha protect path target_f0 pitch_shift pitch_shifts shift_out noise_angle seed wave B",
+    "tvc_knn_match_alpha_f32": "src prepared N M weights alpha out idx_out B T",
+    "tvc_knn_match_protect_f32": "src f0 prepared N M weights alpha protect out idx_out B T",
+}
+QUERIES = ["", "_multi", "_blend", "_auto", "_alpha", "_protect", "_path"]
+
+
+def dump_ladder(out, gen, dev):
+    """B = 2 rows of 20 frames (ragged: 20 and 13), indices of 64 and 300 vectors, explicit noise phases, a shift per row: every rung equal
+    and ragged, the upper ones with and without target registers, the tracker and the carry over two consecutive blocks with their state."""
+    from tinyvc_amd import synth
+    from tinyvc_amd._lib import PitchPathSettings
+    from tinyvc_amd.module.tinyvc.feature_retrieval import Blend, PitchCarry, PitchPath, PitchTrack, prepare_reference, prepare_references
+    B, L, T, HZ = 2, 9600, 20, 150.0
+    lengths, shifts, al, pr = [9600, 6000], [1.0, -2.0], [0.25, 0.6], [0.5, 0.9]
+    wf = synth.synth_wave(B, L, seed=91)
+    wf[1, lengths[1]:] = 0
+    wf, wf2 = wf.to(dev), synth.synth_wave(B, L, seed=97).to(dev)
+    angle = synth.synth_angle(B, T, 94).to(dev)
+    a, b = synth.synth_index(64, seed=92).to(dev), synth.synth_index(300, seed=93).to(dev)
+    blend = Blend([a, b], [0.7, 0.3])
+
+    def put(tag, res):
+        for i, t in enumerate(res if isinstance(res, tuple) else (res,)):
+            out["ladder_%s_%d" % (tag, i)] = t.cpu().numpy()
+
+    for rag, lens in (("equal", None), ("ragged", lengths)):
+        kw = dict(noise_angle=angle, lengths=lens)
+        put("shared_" + rag, gen.convert(wf, a, 1.0, **kw))
+        put("multi_" + rag, gen.convert(wf, [a, b], shifts, **kw))
+        put("blend_" + rag, gen.convert(wf, blend, shifts, **kw))
+        for hz in (None, HZ):
+            kw = dict(noise_angle=angle, lengths=lens, auto_pitch=hz, return_shift=hz is not None)
+            tag = "_%s_%s" % (rag, "target" if hz else "plain")
+            if hz:
+                put("auto" + tag, gen.convert(wf, [a, b], shifts, **kw))
+                put("auto_blend" + tag, gen.convert(wf, blend, shifts, **kw))
+            put("alpha" + tag, gen.convert(wf, [a, b], shifts, alpha=al, **kw))
+            put("alpha_blend" + tag, gen.convert(wf, blend, shifts, alpha=al, **kw))
+            put("protect" + tag, gen.convert(wf, [a, b], shifts, alpha=al, protect=pr, **kw))
+            put("protect_alone" + tag, gen.convert(wf, blend, 1.0, protect=pr, **kw))
+            put("path" + tag, gen.convert(wf, [a, b], shifts, f0_estimation="viterbi", **kw))
+            put("path_all" + tag, gen.convert(wf, blend, shifts, f0_estimation=PitchPath(step=0.4, band=8), alpha=al, protect=pr, **kw))
+    # two consecutive blocks: the tracker on every rung that takes one, the carry with and without target registers and beside a tracker
+    rungs = {"track": {}, "alpha_track": dict(alpha=al), "protect_track": dict(alpha=al, protect=pr), "path_track": dict(f0_estimation="viterbi"),
+             "carry_plain": dict(f0_estimation="viterbi", carry=True), "carry_target": dict(f0_estimation="viterbi", carry=True),
+             "carry_track": dict(f0_estimation="viterbi", carry=True, alpha=al, protect=pr)}
+    for name, kw in rungs.items():
+        kw = dict(kw, noise_angle=angle)
+        if name != "carry_plain":
+            kw.update(auto_pitch=HZ, return_shift=True)
+        if name.endswith("track"):
+            kw["track"] = PitchTrack(B, 4, lag_frames=2, window_frames=16, min_voiced=2, slew=0.5, device=dev)
+        if kw.get("carry"):
+            kw["carry"] = PitchCarry(B, 4, device=dev)
+        for blk, w in enumerate((wf, wf2)):
+            put("%s_block%d" % (name, blk), gen.convert(w, [a, b], shifts, **kw))
+            if "track" in kw:
+                put("%s_block%d_state" % (name, blk), (kw["track"].ring, kw["track"].count, kw["track"].auto))
+            if kw.get("carry"):
+                put("%s_block%d_scores" % (name, blk), kw["carry"].scores)
+    # the five matches, with indices
+    eng = gen.engine(torch.device(dev))
+    g = torch.Generator().manual_seed(95)
+    src = torch.randn(B, 768, T, generator=g).to(dev)
+    f0 = (torch.rand(B, T, generator=g) * 200 * (torch.rand(B, T, generator=g) > 0.4)).to(dev)
+    alpha, protect = torch.tensor(al, device=dev), torch.tensor(pr, device=dev)
+    blob, n = prepare_reference(a)
+    blobs, ns = prepare_references([a, b])
+    bblobs, bns, bw = blend.resolve(B, torch.device(dev))
+    put("match_shared", eng.knn_match(src, blob, n, True))
+    put("match_multi", eng.knn_match_multi(src, blobs, ns, True))
+    put("match_blend", eng.knn_match_blend(src, bblobs, bns, bw, True))
+    put("match_alpha", eng.knn_match_alpha(src, blobs, ns, alpha, None, True))
+    put("match_alpha_blend", eng.knn_match_alpha(src, bblobs, bns, alpha, bw, True))
+    put("match_protect", eng.knn_match_protect(src, f0, blobs, ns, alpha, protect, None, True))
+    put("match_protect_blend", eng.knn_match_protect(src, f0, bblobs, bns, None, protect, bw, True))
+    # what the workspace queries answer for these shapes
+    lib, ctx = eng.lib, eng.ctx
+    N2, N4, lens = (ctypes.c_int64 * 2)(64, 300), (ctypes.c_int64 * 4)(64, 300, 64, 300), (ctypes.c_int64 * 2)(*lengths)
+    need = ctypes.c_size_t()
+    for q in QUERIES:
+        for ragged in (False, True):
+            for M in ((None,) if q in ("", "_multi") else (1, 2)):
+                name = "tvc_workspace_bytes%s%s" % ("_ragged" if ragged else "", q)
+                args = (B, L) + ((lens,) if ragged else ()) + ((64,) if q == "" else (N2,) if M is None else (N4, M))
+                need.value = 0
+                rc = getattr(lib, name)(ctx, *args, ctypes.byref(need))
+                out["query_%s_M%s" % (name, M)] = np.array([rc, need.value], dtype=np.int64)
+    # calls that a host check refuses before any device work.  Every argument is valid but the ones a case changes, and the workspace is
+    # (NULL, 0 bytes): even a call that passed every check would be refused for its workspace and launch nothing.
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    keep = [torch.empty(B, L, device=dev), torch.empty(B, 512, device=dev), torch.full((B,), HZ, device=dev), torch.zeros(B, 16, device=dev),
+            torch.zeros(B, dtype=torch.int64, device=dev), torch.zeros(B, device=dev), torch.empty(B, device=dev), torch.empty_like(src)]
+    path, bad_path = PitchPath().settings(), PitchPathSettings(0.5, -1, 12.0, 3.0, 2)
+    valid = dict(wav=p(wf), prepared=(ctypes.c_void_p * 2)(*[t.data_ptr() for t in blobs]), N=N2, M=1, weights=None, alpha=p(alpha), protect=p(protect),
+                 path=ctypes.byref(path), carry_frame=4, carry=p(keep[1]), target_f0=p(keep[2]), start=14, n=4, W=16, min_voiced=2, slew=0.5, ring=p(keep[3]),
+                 count=p(keep[4]), auto_shift=p(keep[5]), pitch_shift=0.0, pitch_shifts=None, shift_out=p(keep[6]), noise_angle=p(angle), seed=0,
+                 wave=p(keep[0]), B=B, L=L, Lmax=L, lens=lens, src=p(src), f0=p(f0), out=p(keep[7]), idx_out=None, T=T)
+    st = ctypes.c_void_p(torch.cuda.current_stream(torch.device(dev)).cuda_stream)
+
+    def refused(tag, entry, **change):
+        v = dict(valid, **change)
+        rc = getattr(lib, entry)(ctx, st, *[v[k] for k in ORDER[entry].split()], None, 0)
+        text = "%d %s" % (rc, lib.tvc_last_error(ctx).decode())
+        print("refused", tag, entry, text)
+        out["refused_" + tag] = np.frombuffer(text.encode(), dtype=np.uint8)
+
+    refused("weights_null_M2", "tvc_convert_auto_f32", M=2)
+    refused("M0_with_weights", "tvc_convert_blend_f32", M=0, weights=p(bw))
+    refused("auto_without_target", "tvc_convert_auto_f32", target_f0=None)
+    refused("carry_without_path", "tvc_convert_carry_f32", path=None)
+    refused("carry_frame_0", "tvc_convert_carry_f32", carry_frame=0)
+    refused("tracker_W0", "tvc_convert_track_f32", W=0)
+    refused("tracker_without_target", "tvc_convert_alpha_f32", target_f0=None)
+    refused("match_src_is_out", "tvc_knn_match_alpha_f32", out=p(src))
+    refused("protect_without_f0", "tvc_knn_match_protect_f32", f0=None)
+    # two faults at once: the first check in the entry's order answers
+    refused("carry_without_path_and_M2", "tvc_convert_carry_f32", path=None, M=2)
+    refused("M2_and_no_target", "tvc_convert_auto_f32", M=2, target_f0=None)
+    refused("no_target_and_no_wav", "tvc_convert_auto_f32", target_f0=None, wav=None)
+    refused("src_is_out_and_M2", "tvc_knn_match_alpha_f32", out=p(src), M=2)
+    refused("bad_path_and_no_lens", "tvc_convert_ragged_path_f32", path=ctypes.byref(bad_path), lens=None)
+    refused("L0_and_tracker_W0", "tvc_convert_track_f32", L=0, W=0)
+    refused("tracker_n_and_short_L", "tvc_convert_alpha_f32", n=300, L=480)
+    del keep
 
 
 def dump(path):
@@ -59,6 +200,7 @@ def dump(path):
     out["wave_ragged"] = y.cpu().numpy()
     torch.manual_seed(99)
     out["wave_ragged_default_draw"] = gen.convert(wf.to(dev), tgt, -1.5, lengths=lens).cpu().numpy()
+    dump_ladder(out, gen, dev)
     np.savez(path, **out)
     print("dumped", len(out), "tensors to", path)
 
@@ -69,13 +211,18 @@ if __name__ == "__main__":
     else:
         a, b = np.load(sys.argv[2]), np.load(sys.argv[3])
         bad = 0
-        for k in a.files:
-            same = a[k].shape == b[k].shape and np.array_equal(a[k], b[k], equal_nan=True)
-            if not same:
+        for k in sorted(set(a.files) | set(b.files)):
+            if k not in a.files or k not in b.files:
+                bad += 1
+                print("ONLY ", k, "in", sys.argv[2] if k in a.files else sys.argv[3])
+            elif a[k].shape == b[k].shape and np.array_equal(a[k], b[k], equal_nan=True):
+                print("equal", k, a[k].shape)
+            elif k.startswith("refused_") or a[k].shape != b[k].shape:
+                bad += 1
+                print("DIFF ", k, a[k].shape, b[k].shape, *([bytes(a[k]).decode(), "|", bytes(b[k]).decode()] if k.startswith("refused_") else []))
+            else:
                 bad += 1
                 d = np.abs(a[k].astype(np.float64) - b[k].astype(np.float64))
                 print("DIFF ", k, a[k].shape, "max", d.max(), "count", int((d > 0).sum()), "nan", int(np.isnan(b[k]).sum()))
-            else:
-                print("equal", k, a[k].shape)
         print("ALL EQUAL" if not bad else "%d tensors differ" % bad)
         sys.exit(1 if bad else 0)
