@@ -639,6 +639,75 @@ int tvc_convert_ragged_path_f32(tvc_ctx* ctx, void* stream, const float* wav, in
                                 const float* pitch_shifts, float* shift_out, const float* noise_angle, uint64_t seed, float* wave, int B,
                                 void* ws, size_t ws_bytes);
 
+/* pitch correction: snap f0 to a table of allowed notes ------------------------------------------------------------------------ */
+/* The f0 the decoder's oscillator reads exists only inside the fused call, so this is where it can be put in tune.  A note is chosen with
+ * hysteresis (a pitch hovering between two notes does not flutter), the correction is smoothed by a retune coefficient (vibrato passes
+ * while the note's centre moves), and a strength says how much of it is applied.  Off unless a call asks for it.
+ * Everything is fp32 and every operation is rounded on its own: mul, add, sub and div below are single correctly rounded operations, sqrt
+ * is correctly rounded, compares, min and max are exact.  No transcendentals: tests/helpers_pitch_snap.py holds the definition bit for bit.
+ * It runs over ONE row of T frames (an utterance; an utterance's own frames in a ragged batch; a stream's window) and never crosses rows.
+ * Its input x[t] is the f0 the decoder would have read - behind the path, the register, the tracker and every shift; protect's voicing
+ * weight and the tracker keep reading the unshifted f0.
+ * Inputs:
+ *   notes     fp32 [TVC_PITCH_SNAP_NOTES = 128] on the device, read when the kernel runs: the allowed frequencies in Hz, ascending, padded
+ *             with +inf
+ *   strength  fp32 on the device, one per row, or NULL = 1; the kernel clamps it to [0, 1], NaN counts as 0; read when the kernel runs
+ *   tvc_pitch_snap, a HOST struct: hysteresis = h, a frequency ratio in [1, 2^(1/12)]; retune = g in (0, 1], the per-frame coefficient of
+ *             a one-pole smoother; 32 <= f_min <= f_max, both finite.  Anything else: TVC_ERR_ARG with the reason.
+ *   state (streams; optional): note int32 and ratio fp32, one per row, and a host integer carry_frame = hop >= 1
+ * Table: K is the largest k <= 128 such that notes[0 .. k-1] are finite, notes[0] > 0 and the entries are strictly ascending.  The kernel
+ *   finds K itself: a table a caller scribbled into can give wrong pitches, never an index outside 0 .. K-1.  K = 0 makes every frame "out".
+ *   b[i] = sqrt(mul(notes[i], notes[i+1])) for i < K-1;  near(x) = the number of i with b[i] <= x;
+ *   lo[0] = 0, lo[i] = div(b[i-1], h);  hi[i] = mul(b[i], h), hi[K-1] = +inf.
+ * State (q, c): (-1, anything) without a prior.  A prior (note, ratio) counts only if 0 <= note < K and 2/3f <= ratio <= 1.5f (2/3f is fp32
+ *   0x3F2AAAAB; a NaN fails the compare); otherwise q = -1.
+ * Frame t, x = x[t]:
+ *   out:      if f_min <= x && x <= f_max is false - 0 = unvoiced, negatives, NaN, values out of range - out[t] = x with the same bits,
+ *             q = -1, note_out[t] = -1.
+ *   in range: n = q if q >= 0 && lo[q] < x && x < hi[q], else n = near(x);  r = div(notes[n], x);
+ *             c = r if q < 0 (a note starts in tune), otherwise c = add(c, mul(g, sub(r, c)));  then c = min(max(c, 2/3f), 1.5f);  q = n;
+ *             out[t] = mul(x, add(1, mul(s, sub(c, 1))));  note_out[t] = n.
+ *   safety:   with f_min >= 32 and the clamp, out >= 32 * 2/3 > 20: correction never pushes a voiced frame under the decoder's 20 Hz
+ *             voicing gate, whatever the table holds.
+ * Carry: behind frame carry_frame - 1 the row's (q, c) is stored to the state, c as 1.0 where q = -1; every non-empty row needs at least
+ *   carry_frame frames; prior and carry may be (and in these entries are) the same arrays.  Windows advanced by hop frames over slices of
+ *   ONE f0 tensor equal the run over the whole prefix, by construction.  In a real stream every window decodes an f0 of its own, so the
+ *   state is a prior, as with the pitch carry.
+ * Identities: s = 0 returns the input bits; a table of one note maps every in-range frame toward it; g = 1, h = 1 is the memoryless
+ *   nearest-note snap.
+ * Kernel: one wavefront per row, four rows per workgroup, the table in LDS; no workspace, no atomics, no host synchronisation; capturable;
+ *   out may be f0.  Equal rows back to back take one launch, any other row table one per 256 rows.
+ * tvc_pitch_snap_f32, the stage call: rows as tvc_pitch_path_f32's (HOST arrays, ascending and apart, ends below 2^31; an empty row writes
+ *   nothing; columns outside every row are not written).  note and ratio are both NULL or both given (carry_frame is ignored when NULL);
+ *   note_out (int32 per column) may be NULL.
+ * tvc_tuned_convert_f32: tvc_convert_carry_f32's arguments plus snap, notes, strength [B], snap_carry_frame, snap_note [B], snap_ratio [B]
+ *   behind carry.  tvc_tuned_convert_ragged_f32: tvc_convert_ragged_path_f32's plus snap, notes, strength behind path (no state: streams
+ *   advance in lock step).  snap == NULL is the carry call / the ragged path call, launch for launch and bit for bit; path, alpha, protect
+ *   and the registers all stay optional.  The one new launch sits directly in front of the decoder, in place on the shifted f0.
+ *   Workspace: tvc_workspace_bytes_path / _ragged_path (the stage needs none).
+ * The Python defaults built on this (feature_retrieval.PitchSnap) are guesses: nobody has listened. */
+typedef struct tvc_pitch_snap {
+    float hysteresis;
+    float retune;
+    float f_min;
+    float f_max;
+} tvc_pitch_snap;
+#define TVC_PITCH_SNAP_NOTES 128
+int tvc_pitch_snap_f32(tvc_ctx* ctx, void* stream, const float* f0, const int64_t* row_start, const int64_t* row_count, int rows,
+                       const tvc_pitch_snap* snap, const float* notes, const float* strength, int carry_frame, int32_t* note, float* ratio,
+                       float* out, int32_t* note_out);
+int tvc_tuned_convert_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M,
+                          const float* weights, const float* alpha, const float* protect, const tvc_pitch_path* path, int carry_frame,
+                          float* carry, const tvc_pitch_snap* snap, const float* notes, const float* strength, int snap_carry_frame,
+                          int32_t* snap_note, float* snap_ratio, const float* target_f0, int start, int n, int W, int min_voiced, float slew,
+                          float* ring, int64_t* count, float* auto_shift, float pitch_shift, const float* pitch_shifts, float* shift_out,
+                          const float* noise_angle, uint64_t seed, float* wave, int B, int64_t L, void* ws, size_t ws_bytes);
+int tvc_tuned_convert_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens,
+                                 const float* const* prepared, const int64_t* N, int M, const float* weights, const float* alpha,
+                                 const float* protect, const tvc_pitch_path* path, const tvc_pitch_snap* snap, const float* notes,
+                                 const float* strength, const float* target_f0, float pitch_shift, const float* pitch_shifts,
+                                 float* shift_out, const float* noise_angle, uint64_t seed, float* wave, int B, void* ws, size_t ws_bytes);
+
 /* streaming tail-------------------------------------------------------------------------- */
 /* StreamInfer.audio_callback after convert (reference module/infer/stream.py:74-95), batched over
  * S streams: y [S, Ly] converted buffers; sola_buf [S,1920] in/out; fade_in [1920] = the sin^2

@@ -40,7 +40,7 @@ from tinyvc_amd.engine import limiter_geometry, loudness_geometry
 from tinyvc_amd.module.infer import Generator
 from tinyvc_amd.module.tinyvc import Blend, Decoder, Encoder
 from tinyvc_amd.module.tinyvc.feature_retrieval import (PitchPath, add_alpha_argument, add_auto_pitch_argument, add_blend_argument, add_f0_arguments,
-                                                        add_f0_carry_argument, f0_carry_keywords,
+                                                        add_f0_carry_argument, add_tune_arguments, f0_carry_keywords, tune_keywords,
                                                         add_limit_argument, add_loudness_argument, alpha_keywords, attach_register, f0_keywords,
                                                         limit_keywords, loudness_keywords, pitch_register)
 
@@ -54,6 +54,7 @@ def build_parser():
     p.add_argument("-encp", "--encoder-path", default="./models/encoder.pt")
     p.add_argument("-decp", "--decoder-path", default="./models/decoder.pt")
     add_f0_carry_argument(p)        # --f0-carry: with --chunked and -f0-est viterbi, the path's scores travel from block to block
+    add_tune_arguments(p)           # --tune "KEY SCALE" (--tune-notes --tune-a4 --tune-retune --tune-strength --tune-hysteresis): pitch correction, also with --chunked
     add_f0_arguments(p)             # -f0-est NAME: `viterbi` decodes pitch as one path (--f0-step --f0-band --f0-jump --f0-voicing --f0-refine); any other name is ignored
     p.add_argument("-idx", "--index", default="NONE")
     p.add_argument("-t", "--target", default="target.wav")
@@ -138,7 +139,7 @@ def convert_chunked(gen, batch, tgt, pitch_shift, chunk_size, buffer_blocks, use
     `noise_angles(i)` -> [B, 961, T] injects the decoder's noise phases of block i (parity runs against the oracle's
     `stream_callback`; default: drawn on the device per block, as the reference's `torch.rand` is).
     `return_blocks`: also return the untrimmed block outputs [B, nblk, chunk_size] and the SOLA lags [nblk, B].
-    `stream_kw`: further BatchedStreamInfer keywords (f0_estimation, f0_carry, alpha, protect, loudness: a share of the source's loudness envelope - a StreamLoudness
+    `stream_kw`: further BatchedStreamInfer keywords (f0_estimation, f0_carry, tune, alpha, protect, loudness: a share of the source's loudness envelope - a StreamLoudness
     stage for these streams is built from it here; limit: a ceiling in dBFS - a StreamLimiter likewise, passed on as `limiter`, whose
     delay_size joins the trim)."""
     from tinyvc_amd.module.infer import BatchedStreamInfer, StreamLimiter, StreamLoudness
@@ -205,6 +206,10 @@ def main(argv=None, world=None, rank=None, local_rank=None):
         if args.chunk_size % 480:
             sys.exit(f"infer.py: --f0-carry: the chunk size {args.chunk_size} is not a whole number of 480-sample frames")
         alpha_kw.update(carry_kw)
+    tune_kw = tune_keywords(args, "infer.py")      # likewise --tune: convert's keyword and a stream's
+    if tune_kw and args.chunked and not args.no_chunking and args.chunk_size % 480:
+        sys.exit(f"infer.py: --tune with --chunked: the chunk size {args.chunk_size} is not a whole number of 480-sample frames")
+    alpha_kw.update(tune_kw)
     alpha_kw.update(loudness_keywords(args, "infer.py"))      # likewise --loudness
     if "loudness" in alpha_kw and args.chunked and not args.no_chunking:      # a stream's stage works on whole 10 ms sub-frames of a block
         try:

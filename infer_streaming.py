@@ -72,7 +72,7 @@ from tinyvc_amd.engine import limiter_drive, limiter_geometry, loudness_geometry
 from tinyvc_amd.module.infer import BatchedStreamInfer, StreamDenoise, StreamDoor, StreamGate, StreamLimiter, StreamLoudness
 from tinyvc_amd.module.infer.stream import DOOR_CEILING_DB, check_gate_lookahead, check_window, denoise_constants
 from tinyvc_amd.module.tinyvc.feature_retrieval import (PitchTrack, add_alpha_argument, add_blend_argument, add_f0_arguments, alpha_keywords, f0_keywords,
-                                                        add_f0_carry_argument, f0_carry_keywords,
+                                                        add_f0_carry_argument, add_tune_arguments, f0_carry_keywords, tune_keywords,
                                                         pitch_register, semitones_between)
 
 FRAMES_PER_SECOND = 50      # 24 kHz / 480 samples
@@ -111,6 +111,7 @@ def build_parser():
     p.add_argument("-ig", "--input-gain", default=0, type=float)
     p.add_argument("-og", "--output-gain", default=0, type=float)
     add_f0_carry_argument(p)      # --f0-carry: with -f0-est viterbi, the path's scores travel from block to block
+    add_tune_arguments(p)         # --tune "KEY SCALE" and its settings: pitch correction on the f0 every window's decoder reads
     add_f0_arguments(p, choices=["default", "fcpe", "dio", "harvest", "viterbi"])      # viterbi: each window's pitch as one path (--f0-step .. --f0-refine)
     p.add_argument("--resample", action="store_true",
                    help="run the device (or file) at -sr and resample every block to the model's 24 kHz and back on the GPU; -c counts samples at -sr, "
@@ -411,6 +412,10 @@ def main(argv=None):
     if carry_kw and door.block_size % 480:
         sys.exit(f"infer_streaming.py: --f0-carry: the block of {door.block_size} samples at 24 kHz is not a whole number of 480-sample frames")
     alpha_kw.update(carry_kw)
+    tune_kw = tune_keywords(args, "infer_streaming.py")
+    if tune_kw and door.block_size % 480:
+        sys.exit(f"infer_streaming.py: --tune: the block of {door.block_size} samples at 24 kHz is not a whole number of 480-sample frames")
+    alpha_kw.update(tune_kw)
     stream = BatchedStreamInfer(gen, n_streams=S, pitch_shift=pitch_shift, block_size=door.block_size, device=device, extra_size=args.extra,
                                 f0_estimation=f0_keywords(args, "infer_streaming.py"), door=door, auto_pitch=True if track is not None else None, pitch_track=track,
                                 crossfade_size=args.crossfade, sola_search_size=args.sola_search, last_delay_size=args.lookahead, gate=gate, denoise=denoise, **alpha_kw)

@@ -18,8 +18,14 @@ class PitchPathSettings(ctypes.Structure):
     _fields_ = [("step", c_float), ("band", c_int32), ("jump", c_float), ("voicing", c_float), ("refine", c_int32)]
 
 
+class PitchSnapSettings(ctypes.Structure):
+    """tvc_pitch_snap of include/tinyvc_hip.h: the host settings of the pitch correction"""
+    _fields_ = [("hysteresis", c_float), ("retune", c_float), ("f_min", c_float), ("f_max", c_float)]
+
+
 PTR, INT, I64, F32, U64, SIZE, STR = c_void_p, c_int, c_int64, c_float, c_uint64, c_size_t, c_char_p
 PTRS, INTS, I64S, F32S, SIZES, PATH = POINTER(c_void_p), POINTER(c_int), POINTER(c_int64), POINTER(c_float), POINTER(c_size_t), POINTER(PitchPathSettings)
+SNAP_SETTINGS = POINTER(PitchSnapSettings)
 
 
 def _fn(restype, *groups, **params):
@@ -38,6 +44,8 @@ SHARED = dict(prepared_index=PTR, N=I64)      # one index for every row; the sta
 TABLE = dict(prepared=PTRS, N=I64S)           # host tables, one entry per row
 BLEND = dict(TABLE, M=INT, weights=PTR)       # ... M per row, and the device weights (NULL with M = 1: the table call)
 ALPHA, PROTECT, PITCH_PATH, CARRY, TARGET = dict(alpha=PTR), dict(protect=PTR), dict(path=PATH), dict(carry_frame=INT, carry=PTR), dict(target_f0=PTR)
+SNAP = dict(snap=SNAP_SETTINGS, notes=PTR, strength=PTR)      # the pitch correction: host settings, the table and the strengths on the device
+SNAP_STATE = dict(snap_carry_frame=INT, snap_note=PTR, snap_ratio=PTR)
 TRACK = dict(start=INT, n=INT, W=INT, min_voiced=INT, slew=F32, ring=PTR, count=PTR, auto_shift=PTR)
 SHIFT = dict(pitch_shift=F32)
 SHIFTS = dict(SHIFT, pitch_shifts=F32S)
@@ -128,6 +136,9 @@ PROTOTYPES = {
     "tvc_convert_path_f32": _convert(EQUAL, BLEND, ALPHA, PROTECT, PITCH_PATH, TARGET, TRACK, SHIFTS_OUT),
     "tvc_convert_ragged_path_f32": _convert(RAGGED, BLEND, ALPHA, PROTECT, PITCH_PATH, TARGET, SHIFTS_OUT),
     "tvc_convert_carry_f32": _convert(EQUAL, BLEND, ALPHA, PROTECT, PITCH_PATH, CARRY, TARGET, TRACK, SHIFTS_OUT),
+    # the tuned entries: the carry call / the ragged path call with the correction in front of the decoder (not rungs of the ladder: snap == NULL is the sibling)
+    "tvc_tuned_convert_f32": _convert(EQUAL, BLEND, ALPHA, PROTECT, PITCH_PATH, CARRY, SNAP, SNAP_STATE, TARGET, TRACK, SHIFTS_OUT),
+    "tvc_tuned_convert_ragged_f32": _convert(RAGGED, BLEND, ALPHA, PROTECT, PITCH_PATH, SNAP, TARGET, SHIFTS_OUT),
     "tvc_knn_match_f32": _fn(INT, CALL, dict(src=PTR, prepared=PTR, N=I64), MATCH),
     "tvc_knn_match_multi_f32": _fn(INT, CALL, dict(src=PTR), TABLE, MATCH),
     "tvc_knn_match_blend_f32": _fn(INT, CALL, dict(src=PTR), BLEND, MATCH),
@@ -143,6 +154,7 @@ PROTOTYPES = {
                               path_out=PTR, score_out=PTR, **WS),
     "tvc_pitch_path_carry_f32": _fn(INT, CALL, dict(logits=PTR, row_start=I64S, row_count=I64S, rows=INT, class_stride=I64), PITCH_PATH,
                                     dict(carry_frame=INT, prior=PTR, carry_out=PTR), SHIFTS, f0=PTR, f0_shifted=PTR, path_out=PTR, score_out=PTR, **WS),
+    "tvc_pitch_snap_f32": _fn(INT, CALL, dict(f0=PTR, row_start=I64S, row_count=I64S, rows=INT), SNAP, carry_frame=INT, note=PTR, ratio=PTR, out=PTR, note_out=PTR),
     # ---- index compaction
     "tvc_ctx_set_index_assign_chunk": _fn(INT, ctx=PTR, max_queries=INT),
     "tvc_workspace_bytes_index_compact": _fn(INT, ctx=PTR, N=I64, K=I64, out_bytes=SIZES),

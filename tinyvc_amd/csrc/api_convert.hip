@@ -117,6 +117,11 @@ int tvc::convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const ConvertCall& c)
         TVC_CHECK(run_ssl_amax(ctx, s, ssl, B, T, srcmax));
         TVC_CHECK(run_knn_alpha_bound(ctx, s, c.alpha, idx_bound, ix.per_row ? 1 : 0, srcmax, abound, NB, c.protect));
     }
+    if (c.snap && !ws.dry) {      // pitch correction: one wavefront per utterance over the f0 the decoder is about to read, in place (no workspace)
+        std::vector<SnapRow> rows((size_t)NB);
+        for (int i = 0; i < NB; ++i) rows[i] = SnapRow{ctx->rag ? ctx->rag->pre[i] : i * T, ctx->rag ? ctx->rag->tb[i] : T, ctx->rag ? ctx->rag->row[i] : i};
+        TVC_CHECK(run_pitch_snap(ctx, s, f0s, rows, *c.snap, c.notes, c.strength, c.snap_carry_frame, c.snap_note, c.snap_ratio, f0s, nullptr));
+    }
     TVC_CHECK(run_decoder(ctx, s, ws, matched, f0s, energy, c.angle, c.seed, c.wave, nullptr, nullptr, nullptr, B, T, mixed && !ws.dry ? abound : idx_bound, emax,
                           mixed || ix.per_row ? 1 : 0));
     ws.release(m);
@@ -256,6 +261,13 @@ static int path_check(tvc_ctx* ctx, const tvc_pitch_path* path, const char* what
     return 0;
 }
 
+// a call's correction settings (nullable: none), likewise
+static int snap_check(tvc_ctx* ctx, const tvc_pitch_snap* snap, const char* what) {
+    char why[128];
+    if (snap && pitch_snap_check(*snap, why, sizeof(why)) != 0) return fail(ctx, TVC_ERR_ARG, "%s: snap: %s", what, why);
+    return 0;
+}
+
 // The per-row index as a caller gives it - host tables of B * M blobs and sizes, the device weights - and what the entry asks of it
 struct IndexAsGiven {
     const float* const* prepared = nullptr;
@@ -279,6 +291,19 @@ static int convert_checked(tvc_ctx* ctx, void* stream, ConvertCall c, const Inde
     } else {
         c.carry_frame = 0;
     }
+    TVC_CHECK(snap_check(ctx, c.snap, what));
+    if (c.snap) {      // the correction: its table, and its state from block to block
+        if (!c.notes) return fail(ctx, TVC_ERR_ARG, "%s: snap needs notes (a device array of %d fp32)", what, TVC_PITCH_SNAP_NOTES);
+        if (!c.snap_note != !c.snap_ratio) return fail(ctx, TVC_ERR_ARG, "%s: snap_note and snap_ratio are both NULL or both given", what);
+        if (c.snap_note && (c.snap_carry_frame < 1 || c.L / kHop < c.snap_carry_frame))
+            return fail(ctx, TVC_ERR_ARG, "%s: snap_carry_frame = %d must be >= 1 and at most the window's %lld frames", what, c.snap_carry_frame,
+                        (long long)(c.L / kHop));
+    } else {
+        c.notes = c.strength = nullptr;
+        c.snap_note = nullptr;
+        c.snap_ratio = nullptr;
+    }
+    if (!c.snap_note) c.snap_carry_frame = 0;
     if (given && (given->weights || given->weights_required)) {
         TVC_CHECK(blend_check(ctx, c.B, given->M, given->weights, what));
         c.index = ConvertIndex::blend(given->prepared, given->N, given->M, given->weights);
@@ -512,6 +537,34 @@ int tvc_convert_carry_f32(tvc_ctx* ctx, void* stream, const float* wav, const fl
     return convert_checked(ctx, stream, c, &g, ring ? &t : nullptr, false, wsp, ws_bytes, "tvc_convert_carry_f32");
 }
 
+// ---- pitch correction: the carry entry and the ragged path entry with the snap stage in front of the decoder ---------------------------------
+// snap (host settings), notes, strength and - equal lengths only - the state behind carry / path; snap == NULL is the sibling call, launch
+// for launch.  Workspace: tvc_workspace_bytes_path / _ragged_path.
+int tvc_tuned_convert_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M, const float* weights,
+                          const float* alpha, const float* protect, const tvc_pitch_path* path, int carry_frame, float* carry, const tvc_pitch_snap* snap,
+                          const float* notes, const float* strength, int snap_carry_frame, int32_t* snap_note, float* snap_ratio, const float* target_f0,
+                          int start, int n, int W, int min_voiced, float slew, float* ring, int64_t* count, float* auto_shift, float pitch_shift,
+                          const float* pitch_shifts, float* shift_out, const float* noise_angle, uint64_t seed, float* wave, int B, int64_t L, void* wsp,
+                          size_t ws_bytes) {
+    ConvertCall c; c.wav = wav; c.wave = wave; c.B = B; c.L = L; c.shift = pitch_shift; c.shifts = pitch_shifts; c.angle = noise_angle; c.seed = seed;
+    c.alpha = alpha; c.protect = protect; c.path = path; c.carry_frame = carry_frame; c.carry = carry; c.target_f0 = target_f0; c.shift_out = target_f0 ? shift_out : nullptr;
+    c.snap = snap; c.notes = notes; c.strength = strength; c.snap_carry_frame = snap_carry_frame; c.snap_note = snap_note; c.snap_ratio = snap_ratio;
+    IndexAsGiven g; g.prepared = prepared; g.N = N; g.M = M; g.weights = weights;
+    PitchTrackState t; t.start = start; t.n = n; t.W = W; t.min_voiced = min_voiced; t.slew = slew; t.ring = ring; t.count = count; t.autos = auto_shift;
+    return convert_checked(ctx, stream, c, &g, ring ? &t : nullptr, false, wsp, ws_bytes, "tvc_tuned_convert_f32");
+}
+int tvc_tuned_convert_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens, const float* const* prepared,
+                                 const int64_t* N, int M, const float* weights, const float* alpha, const float* protect, const tvc_pitch_path* path,
+                                 const tvc_pitch_snap* snap, const float* notes, const float* strength, const float* target_f0, float pitch_shift,
+                                 const float* pitch_shifts, float* shift_out, const float* noise_angle, uint64_t seed, float* wave, int B, void* wsp,
+                                 size_t ws_bytes) {
+    ConvertCall c; c.wav = wav; c.wave = wave; c.B = B; c.L = Lmax; c.lens = lens; c.shift = pitch_shift; c.shifts = pitch_shifts; c.angle = noise_angle; c.seed = seed;
+    c.alpha = alpha; c.protect = protect; c.path = path; c.target_f0 = target_f0; c.shift_out = target_f0 ? shift_out : nullptr;
+    c.snap = snap; c.notes = notes; c.strength = strength;
+    IndexAsGiven g; g.prepared = prepared; g.N = N; g.M = M; g.weights = weights;
+    return convert_checked(ctx, stream, c, &g, nullptr, true, wsp, ws_bytes, "tvc_tuned_convert_ragged_f32");
+}
+
 // ---- the matches against one index per row or a blend: the kNN stage of the entries above on the caller's own features ---------------------
 // One match by field name.  alpha (nullable): the alpha form of the same call; protect (nullable, with f0): its protect form.
 struct MatchCall {
@@ -686,6 +739,27 @@ int tvc_pitch_path_carry_f32(tvc_ctx* ctx, void* stream, const float* logits, co
     c.carry_frame = carry_frame; c.prior = prior; c.carry_out = carry_out;
     c.pitch_shift = pitch_shift; c.pitch_shifts = pitch_shifts; c.f0 = f0; c.f0_shifted = f0_shifted; c.path_out = path_out; c.score_out = score_out;
     return pitch_path_entry(ctx, stream, c, wsp, ws_bytes, "tvc_pitch_path_carry_f32");
+}
+int tvc_pitch_snap_f32(tvc_ctx* ctx, void* stream, const float* f0, const int64_t* row_start, const int64_t* row_count, int rows, const tvc_pitch_snap* snap,
+                       const float* notes, const float* strength, int carry_frame, int32_t* note, float* ratio, float* out, int32_t* note_out) {
+    const char* what = "tvc_pitch_snap_f32";
+    if (!ctx) return TVC_ERR_ARG;
+    if (!f0 || !snap || !notes || !out) return fail(ctx, TVC_ERR_ARG, "%s: bad argument (f0, snap, notes and out)", what);
+    if (!note != !ratio) return fail(ctx, TVC_ERR_ARG, "%s: note and ratio are both NULL or both given", what);
+    TVC_CHECK(snap_check(ctx, snap, what));
+    int64_t span = 0;
+    TVC_CHECK(path_rows(ctx, row_start, row_count, rows, 0, &span, what));
+    if (note) {      // frame h - 1 must exist in every row that runs
+        if (carry_frame < 1) return fail(ctx, TVC_ERR_ARG, "%s: carry_frame = %d must be >= 1", what, carry_frame);
+        for (int b = 0; b < rows; ++b)
+            if (row_count[b] > 0 && row_count[b] < carry_frame)
+                return fail(ctx, TVC_ERR_ARG, "%s: row %d has %lld frames: the state is stored behind frame carry_frame - 1 = %d, so every non-empty row needs "
+                            "at least carry_frame", what, b, (long long)row_count[b], carry_frame - 1);
+    }
+    std::vector<SnapRow> rw((size_t)rows);
+    for (int b = 0; b < rows; ++b) rw[b] = SnapRow{(int)row_start[b], (int)row_count[b], b};
+    TVC_HIP(ctx, hipSetDevice(ctx->device));
+    return run_pitch_snap(ctx, (hipStream_t)stream, f0, rw, *snap, notes, strength, note ? carry_frame : 0, note, ratio, out, note_out);
 }
 int tvc_frame_share_f32(tvc_ctx* ctx, void* stream, const float* f0, const int64_t* row_start, const int64_t* row_count, int rows, const float* alpha,
                         const float* protect, float* share_out) {

@@ -446,6 +446,15 @@ struct ConvertCall {
     // stream block to the next - row b starts from carry[b] and leaves the best-predecessor values of frame carry_frame there
     int carry_frame = 0;
     float* carry = nullptr;
+    // tvc_tuned_convert*_f32: snap (host settings) puts the pitch correction (run_pitch_snap, directly in front of the decoder, in place) on the
+    // shifted f0 - notes (device, [128]) and strength (device, one fp32 per caller's row, nullable = 1) are read when the kernel runs; the
+    // state snap_note / snap_ratio (device, one per row, both or neither, equal lengths only) is read at frame 0 and written behind frame
+    // snap_carry_frame - 1
+    const tvc_pitch_snap* snap = nullptr;
+    const float *notes = nullptr, *strength = nullptr;
+    int snap_carry_frame = 0;
+    int32_t* snap_note = nullptr;
+    float* snap_ratio = nullptr;
 };
 // Generator.convert over c.B rows of c.L samples (c.lens is not looked at: a ragged call reaches this through convert_ragged_batches,
 // one batch at a time as ONE row with ctx->rag set, ragged.h)
@@ -491,6 +500,18 @@ size_t pitch_path_ws_bytes(int64_t columns);
 int pitch_path_check(const tvc_pitch_path& p, char* why, size_t why_bytes);
 int run_pitch_path(tvc_ctx*, hipStream_t, const float* logits, long S, const std::vector<PitchPathRow>& rows, const tvc_pitch_path& p, uint16_t* bp, float* f0,
                    float* f0s, int* path_out, float* score_out, int carry_frame = 0, const float* prior = nullptr, float* carry_out = nullptr);
+// Pitch correction (pitch_snap.hip; include/tinyvc_hip.h has the definition): row i = columns [start, start + len) of f0 and of out (which
+// may be f0), idx = its slot in strength (nullable) and in the state note / ratio (both or neither; stored behind frame carry_frame - 1, which
+// the caller has checked every non-empty row to have).  note_out optional.  One launch for equal rows back to back, else one per 256
+// rows; no workspace.  The caller has checked the settings (pitch_snap_check: 0, or TVC_ERR_ARG with the reason in `why`).
+constexpr int SNAP_ROWS = 256;
+constexpr float kSnapMaxHysteresis = 1.0594631f;      // (float)2^(1/12)
+struct SnapRow {
+    int start, len, idx;
+};
+int pitch_snap_check(const tvc_pitch_snap& p, char* why, size_t why_bytes);
+int run_pitch_snap(tvc_ctx*, hipStream_t, const float* f0, const std::vector<SnapRow>& rows, const tvc_pitch_snap& p, const float* notes, const float* strength,
+                   int carry_frame, int32_t* note, float* ratio, float* out, int32_t* note_out);
 int run_uniform_to_angle(tvc_ctx*, hipStream_t, float* u, int64_t n);
 // content_bound (optional): an upper bound of |content| (the prepared index's |max| when content came out of the kNN match): ONE float, or
 // with content_bound_stride = 1 one per utterance (a match against one index per utterance);

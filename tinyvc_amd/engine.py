@@ -14,7 +14,7 @@ import weakref
 import torch
 
 from . import _lib, spec
-from .stream_state import CARRY_STATE, DENOISE_STATE, GATE_STATE, LIMITER_STATE, LOUDNESS_STATE, TRACK_STATE, Field, checked
+from .stream_state import CARRY_STATE, DENOISE_STATE, GATE_STATE, LIMITER_STATE, LOUDNESS_STATE, SNAP_STATE, TRACK_STATE, Field, checked
 
 _F32 = torch.float32
 
@@ -105,8 +105,18 @@ _PATH = {
 }
 
 
+# form "tuned": the carry call / the ragged path call with the pitch correction in front of the decoder; everything behind the index is
+# optional there, the carry included - (ragged,)
+_TUNED = {
+    False: ("tvc_workspace_bytes_path", "tvc_tuned_convert_f32"),
+    True: ("tvc_workspace_bytes_ragged_path", "tvc_tuned_convert_ragged_f32"),
+}
+
+
 def _names(form, ragged=None):
     """(workspace query, entry) of a conversion (`ragged` a bool) or a match (None) from the tables above"""
+    if form == "tuned":
+        return _TUNED[ragged]
     if form == "path":
         return _PATH[ragged]
     if form == "protect":
@@ -117,8 +127,9 @@ def _names(form, ragged=None):
 # a tracker's and a carry's share of a call, and every optional parameter of a conversion at its "off" value: the C parameters' names
 _TrackArgs = collections.namedtuple("_TrackArgs", "start n W min_voiced slew ring count auto_shift")
 _CarryArgs = collections.namedtuple("_CarryArgs", "carry_frame carry")
+_SnapArgs = collections.namedtuple("_SnapArgs", "snap notes strength snap_carry_frame snap_note snap_ratio")
 _FEATURES_OFF = dict(lens=None, M=0, weights=None, alpha=None, protect=None, path=None, target_f0=None, shift_out=None,
-                     **_CarryArgs(0, None)._asdict(), **_TrackArgs(0, 0, 0, 0, 0.0, None, None, None)._asdict())
+                     **_CarryArgs(0, None)._asdict(), **_SnapArgs(None, None, None, 0, None, None)._asdict(), **_TrackArgs(0, 0, 0, 0, 0.0, None, None, None)._asdict())
 
 
 _RESAMPLE_STATE =(Field("state", _F32, "hist", 0.0),)      # what stream_resample takes of a door: one side's history
@@ -580,7 +591,7 @@ class Engine:
         if form == "table":
             blobs, ns = self._table(prepared, Ns, B)
             return dict(prepared=blobs, N=ns), dict(N=ns)
-        if form in ("auto", "track", "alpha", "protect", "path") and weights is None:
+        if form in ("auto", "track", "alpha", "protect", "path", "tuned") and weights is None:
             blobs, ns = self._table(prepared, Ns, B)
             return dict(prepared=blobs, N=ns, M=1, weights=None), dict(N=ns, M=1)
         blobs, ns, M = self._blend_args(prepared, Ns, weights, B)
@@ -691,8 +702,29 @@ class Engine:
         state = checked(carry, CARRY_STATE, S, self.device, "carry.")      # the kernel indexes the state by (S, 512): never past it
         return _CarryArgs(carry.hop_frames, *map(_ptr, state))
 
+    def _snap_tensors(self, tune, rows, what):
+        """a PitchSnap's table and strengths as the kernel reads them, bound to this device and `rows` rows and checked: (notes, strength)"""
+        tune.bind(self.device, rows)
+        for t, name, shape in ((tune.notes, "notes", (128,)), (tune.strength, "strength", (rows,))):
+            _check_dev(t, f"{what}.{name}", self.device)
+            if t.dtype != _F32 or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{what}.{name} must be a contiguous fp32 {list(shape)} tensor, got {t.dtype} {tuple(t.shape)}")
+        return tune.notes, tune.strength
+
+    def _snap_args(self, tune, tune_carry, B, T):
+        """a PitchSnap's (and its SnapCarry's) share of a call over B rows of at most T frames, checked on the host, under the C parameters' names"""
+        notes, strength = self._snap_tensors(tune, B, "tune")
+        state = (0, None, None)
+        if tune_carry is not None:
+            if tune_carry.n_streams != B:
+                raise ValueError(f"tune_carry: a carry of {tune_carry.n_streams} streams for {B} rows")
+            if T < tune_carry.hop_frames:
+                raise ValueError(f"tune_carry: hop_frames = {tune_carry.hop_frames} must be at most the call's T = {T} frames")
+            state = (tune_carry.hop_frames, *map(_ptr, checked(tune_carry, SNAP_STATE, B, self.device, "tune_carry.")))      # the kernel indexes the state by row: never past it
+        return _SnapArgs(ctypes.byref(tune.settings()), _ptr(notes), _ptr(strength), *state)
+
     def _convert(self, form, wav, prepared, Ns, pitch_shift, noise_angle=None, lengths=None, weights=None, target_f0=None, out=None, shift_out=None,
-                 track=None, alpha=None, protect=None, path=None, carry=None):
+                 track=None, alpha=None, protect=None, path=None, carry=None, tune=None, tune_carry=None):
         """wav [B, L] converted toward the index (`form`, prepared, Ns, weights: _index_args) -> wave [B, L]; form "auto" / "track" ->
         (wave, shifts [B]).  "track": "auto" with the register taken from `track` (a PitchTrack: the streams' history), equal lengths only.
         "alpha": the table / blend call keeping the share alpha[b] of row b's own content features (alpha: _per_row); with target_f0 it is the
@@ -701,7 +733,10 @@ class Engine:
         "path": the "protect" call (alpha and protect may both be None) with `path`, a PitchPath, behind protect: f0 is the Viterbi decode of the
         call's own logits over each utterance, and everything behind the encoder reads that one.  `carry` (with "path", equal lengths only): a
         PitchCarry of B streams - row b's decode starts from carry.scores[b] and leaves the best-predecessor values of frame carry.hop_frames
-        there, in place (tvc_convert_carry_f32).
+        there, in place (tvc_convert_carry_f32).  "tuned": the "path" call with alpha, protect, path and carry ALL optional and `tune`, a
+        PitchSnap, behind them: the f0 the decoder reads is snapped to tune.notes in place, one launch in front of the decoder
+        (tvc_tuned_convert_f32 / tvc_tuned_convert_ragged_f32); `tune_carry` (equal lengths only): a SnapCarry of B streams, read at frame 0 and
+        written behind frame tune_carry.hop_frames - 1.
         lengths: a ragged batch (row b holds an utterance of lengths[b] samples, a multiple of 480, zero-padded behind it; every utterance
         is converted over its OWN length).  pitch_shift: a float, or one per row for every form but "shared".  Every host check comes
         first, then the noise draw (which advances torch's generator), then device work: a refused call leaves no trace.
@@ -720,22 +755,26 @@ class Engine:
             named["prepared_index"] = named.pop("prepared")      # the conversion's name for the stage call's `prepared`
         if ragged and (form == "track" or track is not None):
             raise ValueError("track: streams advance in lock step, there is no ragged form")
-        if carry is not None and (form != "path" or ragged):
+        if carry is not None and (form not in ("path", "tuned") or path is None or ragged):
             raise ValueError("carry: the pitch path's state - it goes with form \"path\", and streams advance in lock step: there is no ragged form")
         found = form in ("auto", "track")      # the shifts are found on the device: pitch_shift is the offset, the applied shifts come back
-        shares = form in ("alpha", "protect", "path")      # the table / blend call with or without target registers (and, equal lengths, a tracker), plus the source's share
+        if (tune is None) != (form != "tuned") or (tune_carry is not None and (tune is None or ragged)):
+            raise ValueError("tune goes with form \"tuned\" (and tune_carry with tune; streams advance in lock step: there is no ragged form)")
+        shares = form in ("alpha", "protect", "path", "tuned")      # the table / blend call with or without target registers (and, equal lengths, a tracker), plus the source's share
         if shares:
             found = target_f0 is not None
             if track is not None and not found:
                 raise ValueError("track needs target_f0: the tracker finds the register the automatic shift starts from")
             if form == "alpha" or alpha is not None:
                 named["alpha"] = _ptr(self._per_row(alpha, "alpha", B))
-            if form == "protect" or (form == "path" and protect is not None):
+            if form == "protect" or (form in ("path", "tuned") and protect is not None):
                 named["protect"] = _ptr(self._per_row(protect, "protect", B))
-            if form == "path":
+            if form == "path" or (form == "tuned" and path is not None):
                 named["path"] = ctypes.byref(path.settings())
                 if carry is not None:
                     named.update(self._carry_args(carry, B, T)._asdict())
+            if form == "tuned":
+                named.update(self._snap_args(tune, tune_carry, B, T)._asdict())
         if found:
             named["target_f0"] = _ptr(self._per_row(target_f0, "target_f0", B))
         if form == "track" or (shares and track is not None):
@@ -749,7 +788,7 @@ class Engine:
         if found:
             sh = shift_out if shift_out is not None else torch.empty(B, dtype=_F32, device=self.device)
             named["shift_out"] = _ptr(sh)
-        query, entry = _names(form, "carry" if carry is not None else ragged)
+        query, entry = _names(form, "carry" if carry is not None and form == "path" else ragged)
         named["ws"], named["ws_bytes"] = self._query_ws(query, B=B, lens=named["lens"], **{"Lmax" if ragged else "L": L}, **sized)
         named.update(ctx=self.ctx, stream=self._stream(), noise_angle=_ptr(a), wave=_ptr(wave))
         self._ok(getattr(self.lib, entry)(*_lib.arguments(entry, named)), entry)
@@ -838,6 +877,46 @@ class Engine:
         self._ok(getattr(self.lib, entry)(self.ctx, self._stream(), _ptr(lg), start, count, rows, T, ctypes.byref(settings.settings()), *carried, shift,
                                           _floats(shifts), _ptr(f0), _ptr(out), _ptr(path), _ptr(scores), p, n), entry)
         return (f0, path, scores, out) if want_shifted else (f0, path, scores)
+
+    # ---- pitch correction: rows of f0 snapped to a table of notes (tvc_pitch_snap_f32) ----
+    def pitch_snap(self, f0, tune, row_start=None, row_count=None, carry=None, in_place=False):
+        """The pitch correction of rows of f0 (include/tinyvc_hip.h has the definition; `tune` a PitchSnap, whose notes [128] and strength
+        [rows] are read on the device when the kernel runs): f0 [B, 1, T] / [B, T] (every row a run of T columns), or any contiguous f0 with
+        row_start (and row_count; default: up to the next row's start, row_start then has rows + 1 entries) naming the rows' columns in the
+        flattened f0 -> (out like f0 - f0 itself with in_place -, note_out int32 like f0: the note of every frame, -1 for a frame that passed
+        untouched).  Columns outside every row keep f0's value and note -1.  `carry`: a SnapCarry of `rows` streams, read at every row's
+        first frame and written behind frame carry.hop_frames - 1, which every non-empty row must have."""
+        f0 = _prep(f0, "f0", self.device)
+        if row_start is None:
+            if f0.dim() < 2:
+                raise ValueError("pitch_snap: f0 [B, 1, T] or [B, T], or row_start for a packed f0")
+            rows, T = f0.shape[0], f0.numel() // max(f0.shape[0], 1)
+            row_start, row_count = [b * T for b in range(rows)], [T] * rows
+        row_start = [int(x) for x in row_start]
+        if row_count is None:
+            row_start, row_count = row_start[:-1], [b - a for a, b in zip(row_start, row_start[1:])]
+        row_count = [int(x) for x in row_count]
+        rows, end = len(row_start), 0
+        if rows < 1 or len(row_count) != rows:
+            raise ValueError("pitch_snap: row_start and row_count must name the same rows, at least one")
+        for a, n in zip(row_start, row_count):
+            if a < end or n < 0 or a + n > f0.numel():
+                raise ValueError(f"pitch_snap: the rows must be ascending and apart within the {f0.numel()} values of f0")
+            end = a + n
+        notes, strength = self._snap_tensors(tune, rows, "tune")
+        state = (0, None, None)
+        if carry is not None:
+            if carry.n_streams != rows:
+                raise ValueError(f"pitch_snap: a carry of {carry.n_streams} streams for {rows} rows")
+            if any(0 < n < carry.hop_frames for n in row_count):
+                raise ValueError(f"pitch_snap: every non-empty row needs at least carry.hop_frames = {carry.hop_frames} frames (rows of {sorted(set(row_count))})")
+            state = (carry.hop_frames, *map(_ptr, checked(carry, SNAP_STATE, rows, self.device, "carry.")))
+        out = f0 if in_place else f0.clone()
+        note_out = torch.full(f0.shape, -1, dtype=torch.int32, device=self.device)
+        I64 = ctypes.c_int64 * rows
+        self._ok(self.lib.tvc_pitch_snap_f32(self.ctx, self._stream(), _ptr(f0), I64(*row_start), I64(*row_count), rows, ctypes.byref(tune.settings()), _ptr(notes),
+                                             _ptr(strength), *state, _ptr(out), _ptr(note_out)), "tvc_pitch_snap_f32")
+        return out, note_out
 
     # ---- the pitch register of rows of f0, and the shift onto a target's (tvc_pitch_match_f32) ----
     def pitch_match(self, f0, row_start=None, target_f0=None, pitch_shift=0.0, want_shifted=False):

@@ -6,7 +6,7 @@ from .. import utils
 from ...engine import loudness_in_place, pitch_shifts
 from .._base import HipModule
 from ..tinyvc import Decoder, Encoder
-from ..tinyvc.feature_retrieval import (alpha_rows, check_blend, check_references, limit_rows, loudness_rows, prepare_reference, prepare_references,
+from ..tinyvc.feature_retrieval import (alpha_rows, check_blend, check_references, check_tune_carry, resolve_tune, limit_rows, loudness_rows, prepare_reference, prepare_references,
                                         protect_rows, resolve_alpha, resolve_auto_pitch, resolve_f0_estimation, resolve_limit, resolve_loudness,
                                         resolve_protect, target_form, target_registers)
 
@@ -55,7 +55,7 @@ class Generator(HipModule):
 
     @torch.no_grad()
     def convert(self, wf, tgt, pitch_shift, f0_estimation="default", device=None, noise_angle=None, lengths=None, auto_pitch=None,
-                return_shift=False, track=None, alpha=None, protect=None, loudness=None, limit=None, carry=None):
+                return_shift=False, track=None, alpha=None, protect=None, loudness=None, limit=None, carry=None, tune=None, tune_carry=None):
         """generator.py:26-34: wf [B, L], tgt [1 or B, 768, N] -> converted waveform [B, L'] (L' = L
         padded to a multiple of 480).  `f0_estimation` / `device` are accepted and ignored exactly as
         in the reference - but for `f0_estimation='viterbi'` or a feature_retrieval.PitchPath (extension): f0 is then the pitch path, a
@@ -110,7 +110,16 @@ class Generator(HipModule):
         `carry` (extension, with a pitch path): a feature_retrieval.PitchCarry of B streams - row b's path starts from the scores the stream's
         last window left for this window's first frame, and leaves those of frame carry.hop_frames for the next (tvc_convert_carry_f32: the
         state is read and written in place, on the device, inside the same launch).  Equal batches only; ValueError without a pitch path, with
-        `lengths=`, and for a carry of another size.  None (the default) is the call without it, launch for launch."""
+        `lengths=`, and for a carry of another size.  None (the default) is the call without it, launch for launch.
+        `tune` (extension): pitch correction - the f0 the decoder's oscillator reads, behind the path, the register, the tracker and every
+        shift, is snapped to a table of allowed notes: the note is chosen with hysteresis, the correction is smoothed by a retune time and a
+        strength says how much of it is applied (one more launch directly in front of the decoder, in place, no workspace:
+        tvc_tuned_convert_f32 / tvc_tuned_convert_ragged_f32; the definition is in include/tinyvc_hip.h and is exact: fp32, bit for bit what
+        tests/helpers_pitch_snap.py computes).  A feature_retrieval.PitchSnap, or a string such as "A minor" / "chromatic" (PitchSnap's
+        defaults).  Every target form, equal and ragged batches, with every other keyword; protect's voicing and the tracker keep reading the
+        unshifted f0.  A strength of 0 is the call without it bit for bit, None (the default) launch for launch.  `tune_carry` (equal batches
+        only): a feature_retrieval.SnapCarry of B streams - the note and the smoothed ratio travel from one window to the next, in place.
+        The defaults are guesses: nobody has listened."""
         # 1. classify the target once; malformed targets, registers and shift lists are refused before any engine or device work
         B = wf.shape[0] if wf.dim() == 2 else 1
         auto = auto_pitch is not None and auto_pitch is not False
@@ -143,6 +152,10 @@ class Generator(HipModule):
                 raise ValueError(f"carry: a carry of {carry.n_streams} streams for a batch of {B}")
             if -(-wf.shape[-1] // 480) <= carry.hop_frames:
                 raise ValueError(f"carry: hop_frames = {carry.hop_frames} must be below the call's {-(-wf.shape[-1] // 480)} frames")
+        tune = resolve_tune(tune)
+        if tune_carry is not None and lengths is not None:
+            raise ValueError("tune_carry with lengths: streams advance in lock step, there is no ragged form")
+        check_tune_carry(tune_carry, tune, B, -(-wf.shape[-1] // 480))
         level = resolve_loudness(loudness, B) if loudness is not None else None
         if level is not None and 480 % level[0].sub_frame:
             raise ValueError(f"loudness: sub_frame = {level[0].sub_frame} does not divide the 480-sample frames a call is padded to")
@@ -164,11 +177,11 @@ class Generator(HipModule):
             blobs, ns = prepare_references([self._input_device(t) for t in tgt] if isinstance(tgt, (list, tuple)) else self._input_device(tgt))
         else:
             blobs, ns = prepare_reference(self._input_device(tgt))
-            if auto or shifts is not None or share is not None or guard is not None or path is not None:      # a value per row (given, or found on the device): the shared blob in every row (one segment)
+            if auto or shifts is not None or share is not None or guard is not None or path is not None or tune is not None:      # a value per row (given, or found on the device): the shared blob in every row (one segment)
                 form, blobs, ns = "table", [blobs] * B, [ns] * B
         # 4. one engine call
         pitch = shift if shifts is None else shifts
-        if share is not None or guard is not None or path is not None:      # the alpha / protect / path entry covers every case below: plain shifts, target registers, a tracker
+        if share is not None or guard is not None or path is not None or tune is not None:      # the alpha / protect / path / tuned entry covers every case below: plain shifts, target registers, a tracker
             rows = {"alpha": alpha_rows(share, B, wf.device) if share is not None else None}
             if guard is not None:
                 rows["protect"] = protect_rows(guard, B, wf.device)
@@ -176,7 +189,9 @@ class Generator(HipModule):
                 rows["path"] = path
             if carry is not None:
                 rows["carry"] = carry
-            res = eng._convert("path" if path is not None else "alpha" if guard is None else "protect", wf, blobs, ns, pitch, noise_angle, lens, w,
+            if tune is not None:
+                rows["tune"], rows["tune_carry"] = tune, tune_carry
+            res = eng._convert("tuned" if tune is not None else "path" if path is not None else "alpha" if guard is None else "protect", wf, blobs, ns, pitch, noise_angle, lens, w,
                                target_registers(regs, B, wf.device) if auto else None, track=track, **rows)
             res = res if return_shift or not auto else res[0]
         elif not auto:

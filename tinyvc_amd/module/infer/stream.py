@@ -18,8 +18,8 @@ import torch
 
 from ...engine import (SOLA_CROSS, SOLA_DELAY, SOLA_SEARCH, loudness_geometry, loudness_levels, pitch_shifts, sola_geometry, stream_denoise_geometry,
                        stream_gate_geometry, stream_resample_geometry)
-from ...stream_state import CARRY_STATE, DENOISE_STATE, DOOR_STATE, GATE_STATE, LIMITER_STATE, LOUDNESS_STATE, TRACK_STATE, addresses, allocate, reset
-from ..tinyvc.feature_retrieval import (PitchCarry, PitchTrack, alpha_rows, check_f0_carry, gpu_device, limit_ceiling, limiter_settings, protect_rows, resolve_alpha,
+from ...stream_state import CARRY_STATE, SNAP_STATE, DENOISE_STATE, DOOR_STATE, GATE_STATE, LIMITER_STATE, LOUDNESS_STATE, TRACK_STATE, addresses, allocate, reset
+from ..tinyvc.feature_retrieval import (PitchCarry, PitchTrack, SnapCarry, alpha_rows, check_f0_carry, check_stream_tune, gpu_device, limit_ceiling, limiter_settings, protect_rows, resolve_alpha,
                                         resolve_auto_pitch, resolve_f0_estimation, resolve_protect, target_form)
 from .generator import Generator
 
@@ -394,6 +394,13 @@ class BatchedStreamInfer:
     one given here); `stream.pitch_carry.reset([i])` between blocks starts stream i's path afresh and keeps a captured graph.  False (the
     default) is the stream as it was, launch for launch.  Every window has logits of its own, so the carried scores are a prior, not the
     decode of any one tensor; nobody has listened.
+    `tune` (block_size in whole 480-sample frames; refused with the reason otherwise): pitch correction, convert's `tune` - a
+    feature_retrieval.PitchSnap or a string such as "A minor" - on the f0 every window's decoder reads; held as `self.tune`, with the note and
+    the smoothed ratio of every stream travelling from window to window in `self.tune_carry`, a feature_retrieval.SnapCarry built in
+    init_buffer.  `stream.tune.notes.copy_(...)`, `stream.tune.strength.fill_(...)`, `stream.tune.set_scale(...)` within the same range and
+    `stream.tune_carry.reset([i])` between blocks replay the same captured graph; the host settings (hysteresis, retune, the range) and the
+    addresses are part of the graph key.  Every window decodes an f0 of its own, so the state is a prior, not the run over one tensor.
+    None (the default) is the stream as it was, launch for launch.  The defaults are guesses: nobody has listened.
     `door` (a StreamDoor of the same n_streams and block_size): audio_callback_pcm takes the clients' int16 blocks at the door's rates.
     `gate` (a StreamGate of the same n_streams and block_size): every emitted block goes through the noise gate, one launch behind SOLA (and
     in front of the door), driven by the input window and `last_shift` on the device; the SOLA buffer and the window stay ungated.
@@ -419,12 +426,14 @@ class BatchedStreamInfer:
     shorter than the three sizes say, and a look-ahead shorter than the pad is refused."""
 
     def __init__(self, generator: Generator, n_streams=1, target=None, pitch_shift=0., device=None,
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, denoise=None, loudness=None, gate=None, limiter=None, f0_carry=False, door=None,
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, denoise=None, loudness=None, gate=None, limiter=None, f0_carry=False, tune=None, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         self.input_size, _ = check_window(block_size, extra_size, crossfade_size, sola_search_size, last_delay_size,
                                            auto_pitch is not None and auto_pitch is not False)
         self.f0_carry = check_f0_carry(f0_carry, f0_estimation, block_size, n_streams)      # refused here, before anything is allocated
         self.pitch_carry = self.f0_carry if isinstance(self.f0_carry, PitchCarry) else None
+        self.tune = check_stream_tune(tune, block_size)
+        self.tune_carry = None
         share = resolve_alpha(alpha, n_streams) if alpha is not None else None      # refused here, before anything is allocated
         guard = resolve_protect(protect, n_streams) if protect is not None else None
         self.n_streams, self.block_size = n_streams, block_size
@@ -500,7 +509,8 @@ class BatchedStreamInfer:
     def _stages(self):
         """the stages of these streams that keep state on the device, in block order: (name, stage, its table in stream_state)"""
         every = (("track", self.pitch_track if self.auto_pitch is not None else None, TRACK_STATE), ("door", self.door, DOOR_STATE),
-                 ("denoise", self.denoise, DENOISE_STATE), ("carry", self.pitch_carry, CARRY_STATE), ("loudness", self.loudness, LOUDNESS_STATE),
+                 ("denoise", self.denoise, DENOISE_STATE), ("carry", self.pitch_carry, CARRY_STATE), ("tune_carry", self.tune_carry if self.tune is not None else None, SNAP_STATE),
+                 ("loudness", self.loudness, LOUDNESS_STATE),
                  ("gate", self.gate, GATE_STATE), ("limiter", self.limiter, LIMITER_STATE))
         return [s for s in every if s[1] is not None]
 
@@ -513,6 +523,7 @@ class BatchedStreamInfer:
             self._fits(name, getattr(self, name))
         self._bound_ceiling()
         self.f0_carry = check_f0_carry(self.f0_carry, self.f0_estimation, self.block_size, self.n_streams)
+        self.tune = check_stream_tune(self.tune, self.block_size)
         if self.gate is not None:
             check_gate_lookahead(self.gate.lookahead_size, self.crossfade_size, self.last_dilay_size, self.pad_size)
         self._geometry = self._attributes()
@@ -527,6 +538,10 @@ class BatchedStreamInfer:
             self.pitch_carry = PitchCarry(self.n_streams, self.block_size // FRAME, device=self.device)
         else:
             self.pitch_carry = self.f0_carry
+        # the correction's state: what it holds behind the block's last new frame of one window is where frame 0 of the next starts
+        self.tune_carry = SnapCarry(self.n_streams, self.block_size // FRAME, device=self.device) if self.tune is not None else None
+        if self.tune is not None:
+            self.tune.bind(self.device, self.n_streams)      # the table and the strengths: tensors every block reads when it runs
         if self.door is not None:
             self.door.prepare(self.generator.engine(self.device))
         for _, stage, _ in self._stages():
@@ -534,6 +549,10 @@ class BatchedStreamInfer:
 
     def _attributes(self):
         return (self.block_size, self.crossfade_size, self.sola_search_size, self.last_dilay_size, self.input_size)
+
+    def _tune_kw(self):
+        """convert's keywords of the pitch correction: none without `tune`, so the call is the one it was"""
+        return {"tune": self.tune, "tune_carry": self.tune_carry} if self.tune is not None else {}
 
     def _step(self, blocks, noise_angle):
         # torch.roll + slice assignment of the reference (stream.py:69-70), in place on a fixed buffer, one launch
@@ -549,11 +568,11 @@ class BatchedStreamInfer:
         if self.auto_pitch is None:
             y = self.generator.convert(self.input_wav, self.target, self.pitch_shift, device=self.device,
                                        f0_estimation=self.f0_estimation, noise_angle=noise_angle, alpha=self.alpha, protect=self.protect,
-                                       carry=self.pitch_carry)
+                                       carry=self.pitch_carry, **self._tune_kw())
         else:
             y, pshift = self.generator.convert(self.input_wav, self.target, self.pitch_shift, device=self.device, f0_estimation=self.f0_estimation,
                                                noise_angle=noise_angle, auto_pitch=self.auto_pitch, return_shift=True, track=self.pitch_track,
-                                               alpha=self.alpha, protect=self.protect, carry=self.pitch_carry)
+                                               alpha=self.alpha, protect=self.protect, carry=self.pitch_carry, **self._tune_kw())
         eng = self.generator.engine(self.device)
         out, shift = eng.sola(y, self.sola_buffer, self.fade_in_window, self.block_size, self.use_phase_vocoder, want_shift=True,
                               crossfade=self.crossfade_size, search=self.sola_search_size, delay=self.last_dilay_size)
@@ -577,7 +596,7 @@ class BatchedStreamInfer:
         """Everything a captured step bakes in as raw device pointers: the packed weights (re-packed - and the old arena
         freed - when a parameter changes), the engine's scratch workspace (re-allocated when another call needs a bigger
         one), the prepared index riding on `target`, plus the scalars captured by value.  Every stage present - the
-        tracker, the door, the suppressor (denoise), the pitch path's carry, the loudness match, the gate, the limiter - adds (its name, WHERE the tensors of its table in stream_state live, its
+        tracker, the door, the suppressor (denoise), the pitch path's carry, the pitch correction's state, the loudness match, the gate, the limiter - adds (its name, WHERE the tensors of its table in stream_state live, its
         params()): the table lists every tensor whose pointer reaches the library, so none can be passed on and left out here.  With
         auto_pitch also WHERE the target registers live, with alpha / protect where the shares live.  Never a value: the kernels read those at replay,
         so a reset(), registers.copy_(...), threshold_db.fill_(...) or a stream's history advancing keeps the graph.  The tail's geometry is
@@ -601,6 +620,8 @@ class BatchedStreamInfer:
         path = resolve_f0_estimation(self.f0_estimation)
         if path is not None:      # the pitch path's settings ARE values: host numbers baked into the launch, so another PitchPath is another graph
             tkey += (("f0_estimation", path.params()),)
+        if self.tune is not None:      # the correction's host settings are values; its table and strengths are read at replay: WHERE they live
+            tkey += (("tune", self.tune.params(), self.tune.notes.data_ptr(), self.tune.strength.data_ptr()),)
         return (eng.weights_key, ws.data_ptr() if ws is not None else 0, ws.numel() if ws is not None else 0,
                 tuple((id(t), t._version, t.data_ptr()) for t in tgts), wkey, shifts, bool(self.use_phase_vocoder),
                 (self.crossfade_size, self.sola_search_size, self.last_dilay_size)) + tkey
@@ -671,7 +692,7 @@ class StreamInfer(BatchedStreamInfer):
     """Single stream with the reference's constructor and 1-D buffers (stream.py:31-57)."""
 
     def __init__(self, generator: Generator, target=None, pitch_shift=0., device=torch.device("cpu"),
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, denoise=None, loudness=None, gate=None, limiter=None, f0_carry=False, door=None,
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, denoise=None, loudness=None, gate=None, limiter=None, f0_carry=False, tune=None, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         dev = torch.device(device)
         if dev.type != "cuda":
@@ -679,7 +700,7 @@ class StreamInfer(BatchedStreamInfer):
         super().__init__(generator, n_streams=1, target=target, pitch_shift=pitch_shift, device=dev, block_size=block_size, extra_size=extra_size,
                          use_phase_vocoder=use_phase_vocoder, f0_estimation=f0_estimation, use_graph=use_graph, alpha=alpha, protect=protect, denoise=denoise, gate=gate,
                          limiter=limiter, door=door, crossfade_size=crossfade_size, sola_search_size=sola_search_size, last_delay_size=last_delay_size,
-                         auto_pitch=auto_pitch, pitch_track=pitch_track, loudness=loudness, f0_carry=f0_carry)
+                         auto_pitch=auto_pitch, pitch_track=pitch_track, loudness=loudness, f0_carry=f0_carry, tune=tune)
 
     @torch.no_grad()
     def audio_callback(self, block, noise_angle=None):

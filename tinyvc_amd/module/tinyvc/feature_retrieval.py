@@ -9,7 +9,7 @@ import sys
 import torch
 
 from ... import spec, stream_state
-from ..._lib import PitchPathSettings
+from ..._lib import PitchPathSettings, PitchSnapSettings
 from ...engine import default_engine, integer, limiter_drive, limiter_geometry, loudness_geometry, loudness_levels
 
 
@@ -487,6 +487,231 @@ def check_f0_carry(f0_carry, f0_estimation, block_size, n_streams):
         raise ValueError(f"f0_carry: a carry of {f0_carry.n_streams} streams advancing {f0_carry.hop_frames} frames, the streams are {n_streams} "
                          f"advancing {block_size // 480}")
     return f0_carry
+
+
+SNAP_NOTES = 128      # TVC_PITCH_SNAP_NOTES
+SCALES = {"chromatic": tuple(range(12)), "major": (0, 2, 4, 5, 7, 9, 11), "minor": (0, 2, 3, 5, 7, 8, 10), "pentatonic": (0, 2, 4, 7, 9)}
+KEYS = {"C": 0, "C#": 1, "Db": 1, "D": 2, "D#": 3, "Eb": 3, "E": 4, "F": 5, "F#": 6, "Gb": 6, "G": 7, "G#": 8, "Ab": 8, "A": 9, "A#": 10, "Bb": 10, "B": 11}
+
+
+def note_table(key="C", scale="major", notes=None, a4=440.0, low=24, high=96):
+    """The table of allowed notes, on the host: MIDI low .. high filtered by the scale (or `notes`, an explicit list of MIDI numbers), each
+    a4 * 2^((m - 69) / 12) in fp64 rounded to fp32 -> (a list of SNAP_NOTES floats, ascending, padded with inf; the number of notes).
+    ValueError for anything it cannot build."""
+    if isinstance(a4, bool) or not isinstance(a4, (int, float)) or not (0.0 < a4 < math.inf):
+        raise ValueError(f"tune: a4 must be a positive finite number of Hz, got {a4!r}")
+    if notes is not None:
+        midi = list(notes) if isinstance(notes, (list, tuple, range)) else None
+        if not midi or any(isinstance(m, bool) or not isinstance(m, int) or not 0 <= m <= 127 for m in midi):
+            raise ValueError(f"tune: notes must be a non-empty list of MIDI numbers 0 .. 127, got {notes!r}")
+        midi = sorted(set(midi))
+    else:
+        if key not in KEYS:
+            raise ValueError(f"tune: key must be one of {', '.join(KEYS)}, got {key!r}")
+        if scale not in SCALES:
+            raise ValueError(f"tune: scale must be one of {', '.join(SCALES)}, got {scale!r}")
+        for x, name in ((low, "low"), (high, "high")):
+            if isinstance(x, bool) or not isinstance(x, int) or not 0 <= x <= 127:
+                raise ValueError(f"tune: {name} must be a MIDI number 0 .. 127, got {x!r}")
+        degrees = {(KEYS[key] + d) % 12 for d in SCALES[scale]}
+        midi = [m for m in range(low, high + 1) if m % 12 in degrees]
+        if not midi:
+            raise ValueError(f"tune: no note of {key} {scale} lies in MIDI {low} .. {high}")
+    if len(midi) > SNAP_NOTES:
+        raise ValueError(f"tune: {len(midi)} notes; the table holds {SNAP_NOTES}")
+    hz = [_f32(float(a4) * 2.0 ** ((m - 69) / 12.0)) for m in midi]
+    if not (hz[0] > 0.0 and hz[-1] < math.inf and all(a < b for a, b in zip(hz, hz[1:]))):
+        raise ValueError(f"tune: a4 = {a4!r} gives notes that are not positive, finite and ascending in fp32")
+    return hz + [math.inf] * (SNAP_NOTES - len(hz)), len(hz)
+
+
+def parse_tune(text):
+    """'A minor', 'chromatic', 'F#' -> (key, scale): a key (default C) and a scale (default major), in that order"""
+    words = text.split() if isinstance(text, str) else []
+    if len(words) == 1 and words[0] in SCALES:
+        return "C", words[0]
+    if len(words) == 1 and words[0] in KEYS:
+        return words[0], "major"
+    if len(words) == 2 and words[0] in KEYS and words[1] in SCALES:
+        return words[0], words[1]
+    raise ValueError(f"tune: 'KEY SCALE' with KEY one of {', '.join(KEYS)} and SCALE one of {', '.join(SCALES)} (either alone will do), got {text!r}")
+
+
+class PitchSnap:
+    """Pitch correction (convert's and the streams' `tune`; tvc_pitch_snap_f32 and the tvc_tuned_convert* entries; the definition is in
+    include/tinyvc_hip.h): the f0 the decoder reads is snapped to a table of allowed notes.
+      key, scale         the table is MIDI low .. high filtered by the scale (chromatic, major, minor, pentatonic) in that key;
+      notes              ... or an explicit list of MIDI numbers;  a4: the pitch of MIDI 69 in Hz.  At most 128 notes.
+      retune_ms          the time constant of the correction's one-pole smoother: g = 1 - exp(-20 / retune_ms) per 20 ms frame, 0 ms is g = 1
+                         (vibrato passes while the note's centre moves; 0 flattens it)
+      strength           how much of the correction is applied, 0 .. 1: a number, or one per row
+      hysteresis_cents   a pitch leaves its note only that far beyond the bound to the next, 0 .. 100 (h = 2^(cents / 1200))
+    f_min is the lowest note a semitone down (not below 32 Hz), f_max the highest a semitone up: frames outside pass untouched.
+    `notes` and `strength` are tensors the kernel reads when it runs (on the device once the snap is bound to its rows: convert and
+    init_buffer do that): `snap.notes.copy_(...)`, `snap.strength.fill_(...)` and `set_scale(...)` take effect in place, under a captured
+    graph too.  The kernel finds the table's size itself, so whatever is written there gives pitches, never a fault.  h, g, f_min and
+    f_max are host values, baked into a capture.  Every argument is checked here (ValueError) before any engine work.
+    THE DEFAULTS ARE GUESSES: nobody has listened."""
+
+    def __init__(self, key="C", scale="major", notes=None, a4=440.0, low=24, high=96, retune_ms=60.0, strength=1.0, hysteresis_cents=25.0, device=None):
+        table, n = note_table(key, scale, notes, a4, low, high)
+        for x, name in ((retune_ms, "retune_ms"), (hysteresis_cents, "hysteresis_cents")):
+            if isinstance(x, bool) or not isinstance(x, (int, float)) or not (0.0 <= x < math.inf):
+                raise ValueError(f"tune: {name} must be a finite number >= 0, got {x!r}")
+        if hysteresis_cents > 100.0:
+            raise ValueError(f"tune: hysteresis_cents must lie in 0 .. 100 (a semitone), got {hysteresis_cents!r}")
+        rows = list(strength) if isinstance(strength, (list, tuple)) else [strength]
+        if not rows or any(isinstance(s, bool) or not isinstance(s, (int, float)) or not 0.0 <= s <= 1.0 for s in rows):
+            raise ValueError(f"tune: strength must be a number in 0 .. 1, or a list of them (one per row), got {strength!r}")
+        self.retune = _f32(1.0 if retune_ms == 0 else 1.0 - math.exp(-20.0 / retune_ms))
+        self.hysteresis = _f32(2.0 ** (hysteresis_cents / 1200.0))
+        if not 0.0 < self.retune <= 1.0:
+            raise ValueError(f"tune: retune_ms = {retune_ms!r} gives a coefficient of {self.retune!r} per frame; it must lie in (0, 1]")
+        self.retune_ms, self.hysteresis_cents = float(retune_ms), float(hysteresis_cents)
+        self._strength = [float(s) for s in rows] if isinstance(strength, (list, tuple)) else float(strength)
+        self._range(table, n)
+        self.notes = torch.tensor(table, dtype=torch.float32)
+        self.strength = torch.tensor(rows, dtype=torch.float32)
+        if device is not None:
+            self.notes = self.notes.to(gpu_device(device, "PitchSnap: the table lives on the GPU"))
+
+    def _range(self, table, n):
+        semitone = 2.0 ** (1.0 / 12.0)
+        f_min, f_max = _f32(max(table[0] / semitone, 32.0)), _f32(table[n - 1] * semitone)
+        if not (32.0 <= f_min <= f_max < math.inf):
+            raise ValueError(f"tune: the table's range {f_min!r} .. {f_max!r} Hz: the highest note a semitone up must be finite and at least 32 Hz")
+        self.f_min, self.f_max, self.n_notes = f_min, f_max, n
+
+    def set_scale(self, key="C", scale="major", notes=None, a4=440.0, low=24, high=96):
+        """Rebuild the table in place (the tensor a captured graph reads stays where it is).  f_min and f_max follow the new table: they
+        are host values, so a stream whose range changed captures again."""
+        table, n = note_table(key, scale, notes, a4, low, high)
+        self._range(table, n)
+        self.notes.copy_(torch.tensor(table, dtype=torch.float32))
+
+    def bind(self, device, rows):
+        """put the table and the strengths (one per row) on `device`: once, and again only for another device or number of rows"""
+        if self.notes.device != device:
+            self.notes = self.notes.to(device)
+        if self.strength.device != device or self.strength.shape[0] != rows:
+            given = self._strength
+            if isinstance(given, list) and len(given) != rows:
+                raise ValueError(f"tune: {len(given)} strengths for {rows} rows")
+            self.strength = torch.tensor(given if isinstance(given, list) else [given] * rows, dtype=torch.float32, device=device)
+        return self
+
+    def params(self):
+        """the host values a captured block bakes in"""
+        return (self.hysteresis, self.retune, self.f_min, self.f_max)
+
+    def settings(self):
+        """the tvc_pitch_snap struct the library takes"""
+        return PitchSnapSettings(*self.params())
+
+    def __repr__(self):
+        return f"PitchSnap({self.n_notes} notes, retune_ms={self.retune_ms:g}, hysteresis_cents={self.hysteresis_cents:g}, {self.f_min:g} .. {self.f_max:g} Hz)"
+
+
+class SnapCarry:
+    """The pitch correction's state of a set of streams that advance in lock step (tvc_tuned_convert_f32): a window advances by
+    `hop_frames` = block_size / 480 frames per block, so what the correction holds behind frame hop_frames - 1 of one window is where
+    frame 0 of the next starts.
+      note  [S] int32   the note the stream is on (-1: none - unvoiced, out of range, fresh)
+      ratio [S] fp32    the smoothed correction ratio there (1.0 with note -1)
+    Whatever is written into them, the kernel takes a note only inside its table and a ratio only inside [2/3, 1.5].  Every window decodes an
+    f0 of its own, so the state is a prior, not the run over any one tensor.  Every argument is checked before anything is allocated
+    (ValueError)."""
+
+    def __init__(self, n_streams, hop_frames, device=None):
+        for x, name in ((n_streams, "n_streams"), (hop_frames, "hop_frames")):
+            if isinstance(x, bool) or not isinstance(x, int) or x < 1 or x > 0x7fffffff:
+                raise ValueError(f"SnapCarry: {name} must be an integer >= 1, got {x!r}")
+        self.n_streams, self.hop_frames = n_streams, hop_frames
+        self.device = gpu_device(device, "SnapCarry: the state lives on the GPU (device='cpu' builds a carry no engine will take)", cpu_ok=True)
+        stream_state.allocate(self, stream_state.SNAP_STATE, self.device)
+
+    def params(self):
+        """the host values a captured block bakes in"""
+        return (self.hop_frames,)
+
+    def reset(self, streams=None):
+        """Start every stream, or the listed ones, without a note: in-place ops on the state tensors, so it works between replays of a
+        captured graph (which reads them when it runs)."""
+        stream_state.reset(self, stream_state.SNAP_STATE, streams)
+
+
+def resolve_tune(tune):
+    """convert's and the streams' `tune`: None -> None, a PitchSnap -> itself, 'A minor' / 'chromatic' -> PitchSnap(key, scale) with the
+    defaults; ValueError for anything else, before any engine work"""
+    if tune is None or isinstance(tune, PitchSnap):
+        return tune
+    if isinstance(tune, str):
+        return PitchSnap(*parse_tune(tune))
+    raise ValueError(f"tune: a feature_retrieval.PitchSnap or a string such as 'A minor', got {type(tune).__name__}")
+
+
+def check_tune_carry(tune_carry, tune, B, frames):
+    """convert's tune_carry (a SnapCarry or None) against the call, on the host"""
+    if tune_carry is None:
+        return None
+    if not isinstance(tune_carry, SnapCarry):
+        raise ValueError(f"tune_carry: a feature_retrieval.SnapCarry, got {type(tune_carry).__name__}")
+    if tune is None:
+        raise ValueError("tune_carry needs tune: the state it carries is the pitch correction's")
+    if tune_carry.n_streams != B:
+        raise ValueError(f"tune_carry: a carry of {tune_carry.n_streams} streams for a batch of {B}")
+    if frames < tune_carry.hop_frames:
+        raise ValueError(f"tune_carry: hop_frames = {tune_carry.hop_frames} must be at most the call's {frames} frames")
+    return tune_carry
+
+
+def check_stream_tune(tune, block_size):
+    """a stream's `tune` on the host (ValueError, before anything is allocated) -> None or the PitchSnap"""
+    tune = resolve_tune(tune)
+    if tune is not None and block_size % 480:
+        raise ValueError(f"tune: block_size = {block_size} is not a whole number of 480-sample frames (the correction's state travels from "
+                         "window to window, so the window must advance by whole frames)")
+    return tune
+
+
+def add_tune_arguments(parser):
+    """`--tune "KEY SCALE"` and the correction's settings for the entry scripts' parsers: absent is the call without it"""
+    parser.add_argument("--tune", default=None, metavar='"KEY SCALE"',
+                        help="pitch correction: snap the pitch the decoder plays to the notes of a scale, e.g. \"A minor\", \"C major\", chromatic "
+                             f"(keys {' '.join(KEYS)}; scales {' '.join(SCALES)}).  The defaults are guesses: nobody has listened")
+    parser.add_argument("--tune-notes", default=None, metavar="M,M,...", help="... or to an explicit list of MIDI note numbers (69 = A4)")
+    for flag, what in (("--tune-a4", "the pitch of A4 in Hz (default 440)"), ("--tune-retune", "retune time in ms; 0 snaps at once and flattens vibrato (default 60)"),
+                       ("--tune-strength", "share of the correction that is applied, 0 .. 1 (default 1)"),
+                       ("--tune-hysteresis", "cents a pitch must pass the bound between two notes before it changes note, 0 .. 100 (default 25)")):
+        parser.add_argument(flag, type=float, default=None, help=f"--tune: {what}.  Nobody has listened")
+
+
+def tune_keywords(args, script):
+    """what `--tune` and its settings add to the script's convert / stream keywords: nothing when absent, else {"tune": a PitchSnap} and
+    one printed line; a setting without `--tune` / `--tune-notes`, or a refused one, ends the script"""
+    flags = {"a4": "a4", "retune_ms": "retune", "strength": "strength", "hysteresis_cents": "hysteresis"}      # PitchSnap's keyword -> the flag's tail
+    given = {k: getattr(args, "tune_" + a, None) for k, a in flags.items()}
+    given = {k: v for k, v in given.items() if v is not None}
+    tune, notes = getattr(args, "tune", None), getattr(args, "tune_notes", None)
+    if tune is None and notes is None:
+        if given:
+            sys.exit(f"{script}: --tune-{flags[next(iter(given))]} belongs to --tune")
+        return {}
+    try:
+        if notes is not None:
+            if tune is not None:
+                raise ValueError("tune: --tune and --tune-notes are two ways to give the table; give one")
+            try:
+                given["notes"] = [int(m) for m in notes.split(",")]
+            except ValueError:
+                raise ValueError(f"tune: --tune-notes takes MIDI numbers separated by commas, got {notes!r}") from None
+        else:
+            given["key"], given["scale"] = parse_tune(tune)
+        snap = PitchSnap(**given)
+    except ValueError as e:
+        sys.exit(f"{script}: {e}")
+    print(f"Correcting pitch: {snap!r} (untuned defaults: nobody has listened)")
+    return {"tune": snap}
 
 
 def resolve_f0_estimation(f0_estimation):

@@ -19,6 +19,7 @@ GATE_STATE = (Field("threshold_db", _F32, (), None), Field("open", _I32, (), 1),
               Field("level_db", _F32, (), -200.0))
 TRACK_STATE = (Field("ring", _F32, "window_frames", 0.0), Field("count", torch.int64, (), 0), Field("auto", _F32, (), 0.0))
 CARRY_STATE = (Field("scores", _F32, 512, 0.0),)      # the pitch path's best-predecessor values at the next window's first frame; zeros: a fresh path
+SNAP_STATE = (Field("note", _I32, (), -1), Field("ratio", _F32, (), 1.0))      # the pitch correction's note and smoothed ratio at the next window's first frame; -1: no note
 LOUDNESS_STATE = (Field("share", _F32, (), None), Field("src_ring", torch.float64, "window", 0.0), Field("out_ring", torch.float64, "window", 0.0),
                   Field("frames", torch.int64, (), 0), Field("gain", _F32, (), 1.0), Field("gain_db", _F32, (), 0.0))
 LIMITER_STATE = (Field("ceiling", _F32, (), None), Field("tail", _F32, "sub_frame", 0.0), Field("peak", _F32, (), 0.0), Field("gain", _F32, (), 1.0),
