@@ -708,6 +708,61 @@ int tvc_tuned_convert_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav, i
                                  const float* strength, const float* target_f0, float pitch_shift, const float* pitch_shifts,
                                  float* shift_out, const float* noise_angle, uint64_t seed, float* wave, int B, void* ws, size_t ws_bytes);
 
+/* ---- weighted neighbours: a k of 1 .. 4 and a similarity width per row (the reference's match_features(..., k), and a weight it lacks) ----
+ * Every other conversion entry averages the four nearest index rows with equal weight.  These entries average the k nearest, each weighted by
+ * how close its similarity lies to the nearest row's.  Per query column of caller's row r:
+ *   s_0 >= s_1 >= s_2 >= s_3 and i_0 .. i_3: the column's merged top-4, exactly what every entry selects (NaN counted as +inf, a sentinel
+ *     mapped to row 0) - the indices depend on neither array: the top-k under the lists' strict order is a prefix of the top-4;
+ *   k = min(max(neighbours[r], 1), 4), neighbours a DEVICE array of one int32 per caller's row; width[r] a DEVICE array of one fp32 per
+ *     caller's row, in cosine units.  Both are read when the kernel runs: a captured graph replays with whatever they hold then.
+ * Weights: w_0 = 1;  for 1 <= e < k:  g = s_0 - s_e (one fp32 subtraction), t = g / width (__fdiv_rn), w_e = (t > 0) ? fmaxf(0, 1 - t) : 1;
+ *   for e >= k: w_e = 0.  The rule is total: NaN or inf similarities, inf / inf, 0 / 0 (a tie under width 0), a NaN or negative width all give
+ *   w_e = 1; width = +inf gives 1 for every e < k; width = 0 keeps the nearest row and its exact ties.  Every w_e lies in [0, 1] and W >= 1:
+ *   whatever a caller writes into the two arrays gives features, never a fault and never a division by zero.
+ * Matched value of every element of the column, r_e the element of row i_e:  acc = r_0;  for e = 1 .. k - 1 in order, where w_e != 0:
+ *   acc = acc + w_e * r_e (product and sum rounded separately, no FMA; a neighbour of weight 0 takes no part);  W = ((w_0 + w_1) + w_2) + w_3;
+ *   mu = acc / W (__fdiv_rn).  tests/helpers_match_weight.py restates it in numpy, operation by operation.
+ * Consequences: k = 4 with width = +inf is every other entry's mean bit for bit (x / 4 == x * 0.25f); k = 1, and width = 0 without ties,
+ *   store the nearest row's own bits; k = 2 with width = +inf is (r_0 + r_1) * 0.5f.
+ * neighbours == NULL means 4, width == NULL means +inf; both NULL is the call as it was, launch for launch.
+ * alpha / protect: mu above is the mu of their definitions.  A blend: every term's mu_m is formed this way, with the row's k and width and
+ *   the term's own similarities, before w_m * mu_m is accumulated.  A ragged batch finds the row as alpha does.  An index still needs N >= 4:
+ *   the search keeps four.
+ * Range guard: mu is a convex combination of index rows, so the decoder's content bound (the blob's |max|, the blend's sum, alpha's and
+ *   protect's formulas) stays as it is; the guard scales by powers of two with three orders of magnitude of headroom, so the few ulps of
+ *   rounding in acc / W do not matter.
+ * tvc_knn_match_weighted_f32, the stage call: tvc_knn_match_protect_f32's arguments plus neighbours and width behind protect, and sims_out
+ *   (nullable, [M][B][T][4] fp32, beside idx_out): the similarities exactly as the lists held them when the weights were formed - cosines of
+ *   the query and the selected rows, accurate to the fp32 accumulation of a 768-term product of unit vectors (770 * 2^-24), and the one
+ *   measure of how well an index covers a speaker that the library can give.  With neighbours, width and sims_out all NULL it is the protect call.
+ * tvc_weighted_convert_f32 / tvc_weighted_convert_ragged_f32: the tuned entries' arguments plus neighbours and width behind protect.  No
+ *   workspace of their own: tvc_workspace_bytes_path / _ragged_path.  Capturable under the siblings' rules; every host check runs before
+ *   any device work; the one kernel that changes is the merge + gather, in its weighted instantiation - no new pass, no host synchronisation.
+ * Per row: row b equals its own B = 1 call bit for bit whenever its segment of the search takes the path its own call takes.  A (query, row)
+ *   similarity's bits do not depend on splits, tiles or the segments' order - the rescore is one fixed-order fp32 chain per pair, the exact
+ *   kernel one fixed-order accumulator per pair - but the two kernels round differently, and rows that share ONE blob in adjacent columns
+ *   are one segment with one overflow flag: a dense neighbourhood in one row (more than the candidate cap) then sends its neighbours' rows
+ *   to the exact kernel too.  The indices are the same either way; the similarities, and so the weights, then agree to 770 * 2^-24 only.
+ *   Rows with blobs of their own are segments of their own and keep the bit-for-bit contract.
+ * No default width is suggested: nobody has listened. */
+int tvc_knn_match_weighted_f32(tvc_ctx* ctx, void* stream, const float* src, const float* f0, const float* const* prepared,
+                               const int64_t* N, int M, const float* weights, const float* alpha, const float* protect,
+                               const int32_t* neighbours, const float* width, float* out, int64_t* idx_out, float* sims_out, int B, int T,
+                               void* ws, size_t ws_bytes);
+int tvc_weighted_convert_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M,
+                             const float* weights, const float* alpha, const float* protect, const int32_t* neighbours, const float* width,
+                             const tvc_pitch_path* path, int carry_frame, float* carry, const tvc_pitch_snap* snap, const float* notes,
+                             const float* strength, int snap_carry_frame, int32_t* snap_note, float* snap_ratio, const float* target_f0,
+                             int start, int n, int W, int min_voiced, float slew, float* ring, int64_t* count, float* auto_shift,
+                             float pitch_shift, const float* pitch_shifts, float* shift_out, const float* noise_angle, uint64_t seed,
+                             float* wave, int B, int64_t L, void* ws, size_t ws_bytes);
+int tvc_weighted_convert_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens,
+                                    const float* const* prepared, const int64_t* N, int M, const float* weights, const float* alpha,
+                                    const float* protect, const int32_t* neighbours, const float* width, const tvc_pitch_path* path,
+                                    const tvc_pitch_snap* snap, const float* notes, const float* strength, const float* target_f0,
+                                    float pitch_shift, const float* pitch_shifts, float* shift_out, const float* noise_angle, uint64_t seed,
+                                    float* wave, int B, void* ws, size_t ws_bytes);
+
 /* streaming tail-------------------------------------------------------------------------- */
 /* StreamInfer.audio_callback after convert (reference module/infer/stream.py:74-95), batched over
  * S streams: y [S, Ly] converted buffers; sola_buf [S,1920] in/out; fade_in [1920] = the sin^2

@@ -108,8 +108,12 @@ int tvc::convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const ConvertCall& c)
     ws.release(m);
     {
         ProfScope ps(ctx, s, ws, "knn");
-        if (ix.M > 0) TVC_CHECK(run_knn_blend(ctx, s, ws, ssl, segs.data(), (int)segs.size(), ix.M, ix.weights, matched, nullptr, B, T, c.alpha, share));
-        else TVC_CHECK(run_knn_segs(ctx, s, ws, ssl, segs.data(), (int)segs.size(), matched, nullptr, B, T, c.alpha, share));
+        // a weighted call (c.neighbours / c.width): the same search, the weighted instantiation of the merge + gather.  Its mu is a convex
+        // combination of the same index rows, so every content bound below stays what it is without it.
+        const KnnWeight weight{c.neighbours, c.width, nullptr};
+        const KnnWeight* wt = c.neighbours || c.width ? &weight : nullptr;
+        if (ix.M > 0) TVC_CHECK(run_knn_blend(ctx, s, ws, ssl, segs.data(), (int)segs.size(), ix.M, ix.weights, matched, nullptr, B, T, c.alpha, share, wt));
+        else TVC_CHECK(run_knn_segs(ctx, s, ws, ssl, segs.data(), (int)segs.size(), matched, nullptr, B, T, c.alpha, share, wt));
     }
     ws.release(m);
     const float* idx_bound = ws.dry ? nullptr : (ix.per_row ? rowmax : blob_amax(ix.blob));
@@ -565,6 +569,36 @@ int tvc_tuned_convert_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav, i
     return convert_checked(ctx, stream, c, &g, nullptr, true, wsp, ws_bytes, "tvc_tuned_convert_ragged_f32");
 }
 
+// ---- weighted neighbours: the tuned entries with a k of 1 .. 4 and a similarity width per row in the match ----------------------------------
+// `neighbours` (device, one int32 per row) and `width` (device, one fp32 per row) behind protect, either nullable (4, +inf); both NULL is the
+// tuned call, launch for launch.  One more instantiation of the merge + gather: no workspace of its own (tvc_workspace_bytes_path / _ragged_path).
+int tvc_weighted_convert_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M, const float* weights,
+                             const float* alpha, const float* protect, const int32_t* neighbours, const float* width, const tvc_pitch_path* path,
+                             int carry_frame, float* carry, const tvc_pitch_snap* snap, const float* notes, const float* strength, int snap_carry_frame,
+                             int32_t* snap_note, float* snap_ratio, const float* target_f0, int start, int n, int W, int min_voiced, float slew, float* ring,
+                             int64_t* count, float* auto_shift, float pitch_shift, const float* pitch_shifts, float* shift_out, const float* noise_angle,
+                             uint64_t seed, float* wave, int B, int64_t L, void* wsp, size_t ws_bytes) {
+    ConvertCall c; c.wav = wav; c.wave = wave; c.B = B; c.L = L; c.shift = pitch_shift; c.shifts = pitch_shifts; c.angle = noise_angle; c.seed = seed;
+    c.alpha = alpha; c.protect = protect; c.path = path; c.carry_frame = carry_frame; c.carry = carry; c.target_f0 = target_f0; c.shift_out = target_f0 ? shift_out : nullptr;
+    c.snap = snap; c.notes = notes; c.strength = strength; c.snap_carry_frame = snap_carry_frame; c.snap_note = snap_note; c.snap_ratio = snap_ratio;
+    c.neighbours = neighbours; c.width = width;
+    IndexAsGiven g; g.prepared = prepared; g.N = N; g.M = M; g.weights = weights;
+    PitchTrackState t; t.start = start; t.n = n; t.W = W; t.min_voiced = min_voiced; t.slew = slew; t.ring = ring; t.count = count; t.autos = auto_shift;
+    return convert_checked(ctx, stream, c, &g, ring ? &t : nullptr, false, wsp, ws_bytes, "tvc_weighted_convert_f32");
+}
+int tvc_weighted_convert_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens, const float* const* prepared,
+                                    const int64_t* N, int M, const float* weights, const float* alpha, const float* protect, const int32_t* neighbours,
+                                    const float* width, const tvc_pitch_path* path, const tvc_pitch_snap* snap, const float* notes, const float* strength,
+                                    const float* target_f0, float pitch_shift, const float* pitch_shifts, float* shift_out, const float* noise_angle,
+                                    uint64_t seed, float* wave, int B, void* wsp, size_t ws_bytes) {
+    ConvertCall c; c.wav = wav; c.wave = wave; c.B = B; c.L = Lmax; c.lens = lens; c.shift = pitch_shift; c.shifts = pitch_shifts; c.angle = noise_angle; c.seed = seed;
+    c.alpha = alpha; c.protect = protect; c.path = path; c.target_f0 = target_f0; c.shift_out = target_f0 ? shift_out : nullptr;
+    c.snap = snap; c.notes = notes; c.strength = strength;
+    c.neighbours = neighbours; c.width = width;
+    IndexAsGiven g; g.prepared = prepared; g.N = N; g.M = M; g.weights = weights;
+    return convert_checked(ctx, stream, c, &g, nullptr, true, wsp, ws_bytes, "tvc_weighted_convert_ragged_f32");
+}
+
 // ---- the matches against one index per row or a blend: the kNN stage of the entries above on the caller's own features ---------------------
 // One match by field name.  alpha (nullable): the alpha form of the same call; protect (nullable, with f0): its protect form.
 struct MatchCall {
@@ -572,6 +606,7 @@ struct MatchCall {
     const float* f0 = nullptr;                 // [B][T], the protect form's voicing
     IndexAsGiven index;
     const float *alpha = nullptr, *protect = nullptr;
+    KnnWeight weight;                          // the weighted form: neighbours, width, sims_out - all nullable, all null: not weighted
     float* out = nullptr;
     int64_t* idx_out = nullptr;      // nullable
     int B = 0, T = 0;
@@ -608,11 +643,12 @@ static int match_checked(tvc_ctx* ctx, void* stream, const MatchCall& c, void* w
     TVC_CHECK(rows_check(ctx, s, B * ix.M, ix.prepared, ix.N, what));
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     const std::vector<KnnSegIn> in = term_row_segments(ix, B, T);
+    const KnnWeight* wt = c.weight.neighbours || c.weight.width || c.weight.sims_out ? &c.weight : nullptr;
     return run_walks(ctx, what, wsp, ws_bytes, 1, [&](Ws& ws) {
         float* share;
         TVC_CHECK(match_share(ctx, s, ws, c, &share));
-        if (blend) return run_knn_blend(ctx, s, ws, c.src, in.data(), (int)in.size(), ix.M, ix.weights, c.out, c.idx_out, B, T, c.alpha, share);
-        return run_knn_segs(ctx, s, ws, c.src, in.data(), B, c.out, c.idx_out, B, T, c.alpha, share);
+        if (blend) return run_knn_blend(ctx, s, ws, c.src, in.data(), (int)in.size(), ix.M, ix.weights, c.out, c.idx_out, B, T, c.alpha, share, wt);
+        return run_knn_segs(ctx, s, ws, c.src, in.data(), B, c.out, c.idx_out, B, T, c.alpha, share, wt);
     });
 }
 int tvc_knn_match_multi_f32(tvc_ctx* ctx, void* stream, const float* src, const float* const* prepared, const int64_t* N, float* out,
@@ -639,6 +675,14 @@ int tvc_knn_match_protect_f32(tvc_ctx* ctx, void* stream, const float* src, cons
     MatchCall c; c.src = src; c.f0 = f0; c.alpha = alpha; c.protect = protect; c.out = out; c.idx_out = idx_out; c.B = B; c.T = T;
     c.index.prepared = prepared; c.index.N = N; c.index.M = M; c.index.weights = weights;
     return match_checked(ctx, stream, c, wsp, ws_bytes, "tvc_knn_match_protect_f32");
+}
+int tvc_knn_match_weighted_f32(tvc_ctx* ctx, void* stream, const float* src, const float* f0, const float* const* prepared, const int64_t* N, int M,
+                               const float* weights, const float* alpha, const float* protect, const int32_t* neighbours, const float* width, float* out,
+                               int64_t* idx_out, float* sims_out, int B, int T, void* wsp, size_t ws_bytes) {
+    MatchCall c; c.src = src; c.f0 = f0; c.alpha = alpha; c.protect = protect; c.out = out; c.idx_out = idx_out; c.B = B; c.T = T;
+    c.weight.neighbours = neighbours; c.weight.width = width; c.weight.sims_out = sims_out;
+    c.index.prepared = prepared; c.index.N = N; c.index.M = M; c.index.weights = weights;
+    return match_checked(ctx, stream, c, wsp, ws_bytes, "tvc_knn_match_weighted_f32");
 }
 
 // ---- the pitch stage calls: the register match, the tracker, the path and the per-frame share on the caller's own f0 / logits -------------

@@ -1,7 +1,10 @@
 // From the search's top-4 lists (knn.hip, knn_search.h) to results: the merge + gather of the whole-index match (one index, one per
 // row, a weighted blend; each also in its alpha form, which keeps a share of the source), the index-sharded route's three steps (merge, slot
 // gather, finish) and the |max| bounds of `matched`.
-// Every route averages the four rows with mean4 and stores through store_tile_along_t: equal lists give equal bits on all of them.
+// Every route averages the four rows with mean4 and stores through store_tile_along_t: equal lists give equal bits on all of them.  The
+// weighted forms of the two merge + gather kernels (WeightIn) put weighted_mean4 - the k nearest, weighted by their similarities - in its place.
+#include <type_traits>
+
 #include "knn_blob.h"
 #include "knn_search.h"
 #include "tvc_common.h"
@@ -21,10 +24,12 @@ __device__ __forceinline__ Top4 merge_lists(const float* __restrict__ cv, const 
 }
 // sel[4] = the rows column `col` of segment g (number si) gathers: its rescored lists (one "split") where the segment's two-stage search
 // succeeded, else the exact kernel's g.nsE splits, merged; never a sentinel; also written to idx_out[col] (nullable).  A column that is not
-// live (past the end of the call) reads nothing and selects row 0.
+// live (past the end of the call) reads nothing and selects row 0.  sims (nullable, the weighted forms): the four similarities as the merged
+// list holds them (NaN arrived as +inf, a sentinel's is -inf; a column that is not live: zeros), also written to sims_out[col] (nullable).
 __device__ __forceinline__ void merged_top4(const KnnSeg& g, int si, const int* __restrict__ flags, const float* __restrict__ cand_v,
                                             const int* __restrict__ cand_i, const float* __restrict__ rv, const int* __restrict__ ri, long stride,
-                                            long col, bool live, int64_t* __restrict__ idx_out, int* sel) {
+                                            long col, bool live, int64_t* __restrict__ idx_out, int* sel, float* sims = nullptr,
+                                            float* __restrict__ sims_out = nullptr) {
     const bool rescored = g.two && flags[si] == 0;
     Top4 t4;
     t4.init();
@@ -33,8 +38,12 @@ __device__ __forceinline__ void merged_top4(const KnnSeg& g, int si, const int* 
         for (int e = 0; e < 4; ++e) t4.i[e] = (unsigned)t4.i[e] < (unsigned)g.N ? t4.i[e] : 0;   // never gather through a sentinel
         if (idx_out)
             for (int e = 0; e < 4; ++e) idx_out[col * 4 + e] = (int64_t)t4.i[e];
+        if (sims_out)
+            for (int e = 0; e < 4; ++e) sims_out[col * 4 + e] = t4.v[e];
     }
     for (int e = 0; e < 4; ++e) sel[e] = live ? t4.i[e] : 0;
+    if (sims)
+        for (int e = 0; e < 4; ++e) sims[e] = live ? t4.v[e] : 0.f;
 }
 // r[qq][u][e] = channel k + 64 u of row sel[q][e] of query q = q0 + 4 qq's blob (src(q)): four queries' 48 loads in flight per lane (one
 // query at a time was eight serial round trips per wave and chunk - 48 us per launch whatever the batch, a chain of latencies)
@@ -88,6 +97,51 @@ struct ShareIn {
     const float* src;        // [B][768][T], as AlphaIn's
 };
 __device__ __forceinline__ float alpha_of_column(const ShareIn& sh, int nc, int) { return sh.share[nc]; }
+// The weighted forms (tvc_*weighted*_f32; the definition is in include/tinyvc_hip.h) take the mean over the k nearest of the four rows, each
+// weighted by how close its similarity lies to the nearest's: k = neighbours[row] clamped to 1 .. 4, the width = width[row] in cosine units,
+// both the caller's DEVICE arrays, read here (a captured graph replays with whatever they hold then).  Either may be null: 4, +inf.  The row
+// of a column is alpha's.  sims_out (nullable): the merged lists' similarities, beside idx_out.
+struct WeightIn {
+    const int* neighbours;   // [rows]
+    const float* width;      // [rows]
+    const int* col2b;        // ragged batch: column -> utterance, utterance -> caller's row; else nullptr
+    const int* rowmap;
+    float* sims_out;         // [M][B][T][4]
+};
+// a weighted instantiation's one more argument: the weights' inputs and, behind them, the store form's (Mix: AlphaIn, ShareIn or NoMix)
+struct NoMix {};
+template <class Mix>
+struct Weighted {
+    WeightIn w;
+    Mix mix;
+};
+template <class... A> struct Forms { static constexpr bool weighted = false, mixed = sizeof...(A) > 0; };
+template <class Mix> struct Forms<Weighted<Mix>> { static constexpr bool weighted = true, mixed = !std::is_same<Mix, NoMix>::value; };
+template <class AI> __device__ __forceinline__ const AI& mix_of(const AI& al) { return al; }
+template <class Mix> __device__ __forceinline__ const Mix& mix_of(const Weighted<Mix>& x) { return x.mix; }
+// w[0 .. 3] = the four weights of a column and w[4] = their sum W from its merged similarities s[0] >= ... >= s[3]: w_0 = 1, w_e = 1 - (s_0 - s_e) /
+// width clamped to [0, 1] for e < k - and 1 wherever that quotient is not a positive number (NaN, a tie under width 0, a negative width) -, 0 from
+// k on.  Every operation is rounded on its own; W >= 1 whatever the two arrays hold.
+__device__ __forceinline__ void match_weights(const WeightIn& wi, int row, const float* s, float* w) {
+    int k = wi.neighbours ? wi.neighbours[row] : 4;
+    k = k < 1 ? 1 : (k > 4 ? 4 : k);
+    const float width = wi.width ? wi.width[row] : INFINITY;
+    w[0] = 1.f;
+    for (int e = 1; e < 4; ++e) {
+        const float t = __fdiv_rn(__fsub_rn(s[0], s[e]), width);
+        w[e] = e < k ? (t > 0.f ? fmaxf(0.f, __fsub_rn(1.f, t)) : 1.f) : 0.f;
+    }
+    w[4] = __fadd_rn(__fadd_rn(__fadd_rn(w[0], w[1]), w[2]), w[3]);
+}
+// the weighted mean of the four rows: r0, then + w_e * r_e in order where w_e != 0 (a neighbour of weight 0 takes no part, whatever it holds),
+// product and sum rounded separately, over W.  w = {1, 1, 1, 1, 4} is mean4 bit for bit (x / 4 == x * 0.25f), {1, 0, 0, 0, 1} r0's own bits.
+__device__ __forceinline__ float weighted_mean4(float r0, float r1, float r2, float r3, const float* w) {
+    float acc = r0;
+    acc = w[1] != 0.f ? __fadd_rn(acc, __fmul_rn(w[1], r1)) : acc;
+    acc = w[2] != 0.f ? __fadd_rn(acc, __fmul_rn(w[2], r2)) : acc;
+    acc = w[3] != 0.f ? __fadd_rn(acc, __fmul_rn(w[3], r3)) : acc;
+    return __fdiv_rn(acc, w[4]);
+}
 // store_tile_along_t with the source's share a of this thread's column mixed in (AI: AlphaIn or ShareIn)
 template <class AI>
 __device__ __forceinline__ void store_tile_along_t_alpha(const float (&tile)[32][193], float* __restrict__ out, const AI& al, float a, int n0,
@@ -110,31 +164,40 @@ __device__ __forceinline__ void store_tile_along_t_alpha(const float (&tile)[32]
 // out[b][k][t] through an LDS transpose so stores run along t.  Every query takes its segment's blob and lists (col2seg: several
 // segments; the 32 columns may straddle a segment boundary).  MULTI = false: one segment, whose blob the gather reads as a uniform value.
 // A... = AlphaIn: the alpha form (an instantiation with one more argument), ShareIn: the protect form; empty: the kernel as it has always been,
-// argument for argument.
+// argument for argument.  Weighted<Mix>: the weighted form of any of the three - the merge threads leave each column's weights in LDS beside
+// sel, and the gather, its loads as they are, divides the weighted sum by theirs.
 template <bool MULTI, class... A>
 static __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
                                                                       const KnnSegs segs, const int* __restrict__ col2seg, int ncols, int T,
                                                                       float* __restrict__ out, int64_t* __restrict__ idx_out,
                                                                       const float* __restrict__ rv, const int* __restrict__ ri,
                                                                       const int* __restrict__ flags, const A... al) {
-    constexpr bool ALPHA = sizeof...(A) > 0;
+    constexpr bool ALPHA = Forms<A...>::mixed, WEIGHTED = Forms<A...>::weighted;
     __shared__ int sel[32][4];
     __shared__ float tile[32][193];
     __shared__ const float* sblob[32];
     __shared__ int skind[32], sN[32];
+    __shared__ float sw[WEIGHTED ? 32 : 1][5];      // the weighted forms: a column's four weights and their sum
     const int tid = threadIdx.x;
     const int n0 = blockIdx.x * 32;
     float a = 0.f;
     if constexpr (ALPHA) {      // this thread's column in the store phase (a column past the end reads the last column's row: never stored)
         const int n = n0 + (tid & 31);
-        a = alpha_of_column(al..., n < ncols ? n : ncols - 1, T);
+        a = alpha_of_column(mix_of(al...), n < ncols ? n : ncols - 1, T);
     }
     if (tid < 32) {
         const int n = n0 + tid;
         const int nc = n < ncols ? n : ncols - 1;      // (a column past the end gathers row 0 of the last column's blob: never stored)
         const int si = MULTI ? col2seg[nc] : 0;
         const KnnSeg g = seg_get(segs, si);
-        merged_top4(g, si, flags, cand_v, cand_i, rv, ri, ncols, n, n < ncols, idx_out, sel[tid]);
+        if constexpr (WEIGHTED) {
+            const WeightIn& wi = (al.w, ...);
+            float sims[4];
+            merged_top4(g, si, flags, cand_v, cand_i, rv, ri, ncols, n, n < ncols, idx_out, sel[tid], sims, wi.sims_out);
+            match_weights(wi, wi.col2b ? wi.rowmap[wi.col2b[nc]] : nc / T, sims, sw[tid]);
+        } else {
+            merged_top4(g, si, flags, cand_v, cand_i, rv, ri, ncols, n, n < ncols, idx_out, sel[tid]);
+        }
         if (MULTI) {
             sblob[tid] = g.blob;
             skind[tid] = blob_kind(g.blob);
@@ -153,10 +216,13 @@ static __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const floa
 #pragma unroll
             for (int qq = 0; qq < 4; ++qq)
 #pragma unroll
-                for (int u = 0; u < 3; ++u) tile[q0 + 4 * qq][lane + 64 * u] = mean4(r[qq][u][0], r[qq][u][1], r[qq][u][2], r[qq][u][3]);
+                for (int u = 0; u < 3; ++u) {
+                    if constexpr (WEIGHTED) tile[q0 + 4 * qq][lane + 64 * u] = weighted_mean4(r[qq][u][0], r[qq][u][1], r[qq][u][2], r[qq][u][3], sw[q0 + 4 * qq]);
+                    else tile[q0 + 4 * qq][lane + 64 * u] = mean4(r[qq][u][0], r[qq][u][1], r[qq][u][2], r[qq][u][3]);
+                }
         }
         __syncthreads();
-        if constexpr (ALPHA) store_tile_along_t_alpha(tile, out, al..., a, n0, ncols, T, kc);
+        if constexpr (ALPHA) store_tile_along_t_alpha(tile, out, mix_of(al...), a, n0, ncols, T, kc);
         else store_tile_along_t(tile, out, n0, ncols, T, kc);
         __syncthreads();
     }
@@ -181,18 +247,19 @@ static __global__ __launch_bounds__(256) void knn_merge_blend_gather_kernel(cons
                                                                             const int* __restrict__ rowmap, float* __restrict__ out,
                                                                             int64_t* __restrict__ idx_out, const float* __restrict__ rv,
                                                                             const int* __restrict__ ri, const int* __restrict__ flags, const A... al) {
-    constexpr bool ALPHA = sizeof...(A) > 0;
+    constexpr bool ALPHA = Forms<A...>::mixed, WEIGHTED = Forms<A...>::weighted;
     __shared__ int sel[BLEND_MAX][32][4];
     __shared__ float tile[32][193];
     __shared__ const float* sblob[BLEND_MAX][32];
     __shared__ int skind[BLEND_MAX][32], sN[BLEND_MAX][32];
     __shared__ float sw[BLEND_MAX][32];
+    __shared__ float snw[WEIGHTED ? BLEND_MAX : 1][WEIGHTED ? 32 : 1][5];      // the weighted forms: a (term, column)'s four weights and their sum
     const int tid = threadIdx.x;
     const int n0 = blockIdx.x * 32;
     float a = 0.f;
     if constexpr (ALPHA) {      // this thread's column in the store phase
         const int n = n0 + (tid & 31);
-        a = alpha_of_column(al..., n < ncols ? n : ncols - 1, T);
+        a = alpha_of_column(mix_of(al...), n < ncols ? n : ncols - 1, T);
     }
     if (tid < 32 * M) {
         const int m = tid >> 5, q = tid & 31;
@@ -203,12 +270,15 @@ static __global__ __launch_bounds__(256) void knn_merge_blend_gather_kernel(cons
         const long vc = (long)m * ncols + nc;           // this term's virtual column
         const int si = col2seg ? col2seg[vc] : 0;
         const KnnSeg g = seg_get(segs, si);
-        merged_top4(g, si, flags, cand_v, cand_i, rv, ri, vcols, vc, live, idx_out, sel[m][q]);
+        [[maybe_unused]] float sims[4];
+        if constexpr (WEIGHTED) merged_top4(g, si, flags, cand_v, cand_i, rv, ri, vcols, vc, live, idx_out, sel[m][q], sims, (al.w, ...).sims_out);
+        else merged_top4(g, si, flags, cand_v, cand_i, rv, ri, vcols, vc, live, idx_out, sel[m][q]);
         sblob[m][q] = g.blob;
         skind[m][q] = blob_kind(g.blob);
         sN[m][q] = g.N;
         const int row = col2b ? rowmap[col2b[nc]] : nc / T;
         sw[m][q] = weights[(long)row * M + m];
+        if constexpr (WEIGHTED) match_weights((al.w, ...), row, sims, snw[m][q]);      // every term's mu_m: the row's k and width, the term's own similarities
     }
     __syncthreads();
     const int lane = tid & 63, wave = tid >> 6;
@@ -224,7 +294,10 @@ static __global__ __launch_bounds__(256) void knn_merge_blend_gather_kernel(cons
                     const float w = sw[m][q0 + 4 * qq];
 #pragma unroll
                     for (int u = 0; u < 3; ++u) {
-                        const float term = __fmul_rn(w, mean4(r[qq][u][0], r[qq][u][1], r[qq][u][2], r[qq][u][3]));
+                        float mu;
+                        if constexpr (WEIGHTED) mu = weighted_mean4(r[qq][u][0], r[qq][u][1], r[qq][u][2], r[qq][u][3], snw[m][q0 + 4 * qq]);
+                        else mu = mean4(r[qq][u][0], r[qq][u][1], r[qq][u][2], r[qq][u][3]);
+                        const float term = __fmul_rn(w, mu);
                         acc[qq][u] = m == 0 ? term : __fadd_rn(acc[qq][u], term);
                     }
                 }
@@ -235,7 +308,7 @@ static __global__ __launch_bounds__(256) void knn_merge_blend_gather_kernel(cons
                 for (int u = 0; u < 3; ++u) tile[q0 + 4 * qq][lane + 64 * u] = acc[qq][u];
         }
         __syncthreads();
-        if constexpr (ALPHA) store_tile_along_t_alpha(tile, out, al..., a, n0, ncols, T, kc);
+        if constexpr (ALPHA) store_tile_along_t_alpha(tile, out, mix_of(al...), a, n0, ncols, T, kc);
         else store_tile_along_t(tile, out, n0, ncols, T, kc);
         __syncthreads();
     }
@@ -469,13 +542,41 @@ int run_knn_finish(tvc_ctx* ctx, hipStream_t s, const float* slots, float* out, 
     return launch_check(ctx, "knn_finish");
 }
 
+// the weighted forms' launch: the same grid and lists with Weighted<Mix> as the one more argument (Mix: the store form's AlphaIn / ShareIn / NoMix)
+static WeightIn weight_in(const tvc_ctx* ctx, const KnnWeight& wt) {
+    const RagHost* h = ctx->rag;
+    return WeightIn{wt.neighbours, wt.width, h ? (const int*)h->d_col2b : (const int*)nullptr, h ? (const int*)h->d_row : (const int*)nullptr, wt.sims_out};
+}
+template <class Mix>
+static int launch_weighted(tvc_ctx* ctx, hipStream_t s, const KnnCall& c, const KnnLists& L, int T, float* out, int64_t* idx_out, const KnnWeight& wt, const Mix& mix) {
+    const Weighted<Mix> x{weight_in(ctx, wt), mix};
+    const auto kernel = L.col2seg ? knn_merge_gather_kernel<true, Weighted<Mix>> : knn_merge_gather_kernel<false, Weighted<Mix>>;
+    hipLaunchKernelGGL(kernel, dim3((c.ncols + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)L.col2seg, c.ncols, T, out, idx_out, L.rv, L.ri,
+                       (const int*)L.flag, x);
+    return launch_check(ctx, "knn_match_weighted");
+}
+template <class Mix>
+static int launch_weighted_blend(tvc_ctx* ctx, hipStream_t s, const KnnLists& L, int B, int T, int M, const float* weights, float* out, int64_t* idx_out,
+                                 const KnnWeight& wt, const Mix& mix) {
+    const Weighted<Mix> x{weight_in(ctx, wt), mix};
+    hipLaunchKernelGGL(knn_merge_blend_gather_kernel<Weighted<Mix>>, dim3((B * T + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)L.col2seg, B * T, T, M,
+                       weights, x.w.col2b, x.w.rowmap, out, idx_out, L.rv, L.ri, (const int*)L.flag, x);
+    return launch_check(ctx, "knn_match_blend_weighted");
+}
+
 int run_knn_segs(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const KnnSegIn* in, int nin, float* out, int64_t* idx_out, int B, int T,
-                 const float* alpha, const float* share) {
+                 const float* alpha, const float* share, const KnnWeight* wt) {
     KnnCall c;
     TVC_CHECK(knn_call_plan(ctx, in, nin, B * T, &c));
     KnnLists L;
     TVC_CHECK(knn_candidates(ctx, s, ws, src, c, B, T, &L));
     if (ws.dry) return 0;
+    if (wt) {      // the weighted forms: the same lists, the four rows weighted by their similarities; the store form as below
+        const RagHost* h = ctx->rag;
+        if (share) return launch_weighted(ctx, s, c, L, T, out, idx_out, *wt, ShareIn{share, src});
+        if (alpha) return launch_weighted(ctx, s, c, L, T, out, idx_out, *wt, AlphaIn{alpha, src, h ? (const int*)h->d_col2b : (const int*)nullptr, h ? (const int*)h->d_row : (const int*)nullptr});
+        return launch_weighted(ctx, s, c, L, T, out, idx_out, *wt, NoMix{});
+    }
     if (share) {      // the protect form: a share per column (run_frame_share), which has alpha in it
         const ShareIn sh{share, src};
         const auto skernel = L.col2seg ? knn_merge_gather_kernel<true, ShareIn> : knn_merge_gather_kernel<false, ShareIn>;
@@ -501,13 +602,18 @@ int run_knn_segs(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const Kn
 // knn_candidates walk - every pass one launch, as run_knn_segs -, then the blend gather.  idx_out (nullable): [M][B][T][4].  A ragged batch
 // (ctx->rag: B = 1, T = all its frames) finds a column's weight row through the batch's tables.
 int run_knn_blend(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const KnnSegIn* in, int nin, int M, const float* weights, float* out,
-                  int64_t* idx_out, int B, int T, const float* alpha, const float* share) {
+                  int64_t* idx_out, int B, int T, const float* alpha, const float* share, const KnnWeight* wt) {
     KnnCall c;
     TVC_CHECK(knn_call_plan(ctx, in, nin, M * B * T, &c));
     KnnLists L;
     TVC_CHECK(knn_candidates(ctx, s, ws, src, c, M * B, T, &L, B));
     if (ws.dry) return 0;
     const RagHost* h = ctx->rag;
+    if (wt) {
+        if (share) return launch_weighted_blend(ctx, s, L, B, T, M, weights, out, idx_out, *wt, ShareIn{share, src});
+        if (alpha) return launch_weighted_blend(ctx, s, L, B, T, M, weights, out, idx_out, *wt, AlphaIn{alpha, src, h ? (const int*)h->d_col2b : (const int*)nullptr, h ? (const int*)h->d_row : (const int*)nullptr});
+        return launch_weighted_blend(ctx, s, L, B, T, M, weights, out, idx_out, *wt, NoMix{});
+    }
     if (share) {
         const ShareIn sh{share, src};
         hipLaunchKernelGGL(knn_merge_blend_gather_kernel<ShareIn>, dim3((B * T + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)L.col2seg, B * T, T, M,

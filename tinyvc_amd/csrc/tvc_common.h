@@ -365,13 +365,21 @@ struct KnnSegIn {
 // alpha (optional, both drivers): the caller's DEVICE array [rows] of the source's own share - out = mu * (1 - a) + src * a with mu the alpha-less
 // result (knn_gather.hip); nullptr launches exactly what the call without it launches.  share (optional, both drivers; takes alpha's place): a
 // DEVICE array of one share per query COLUMN (run_frame_share's, which has alpha in it) - the protect form of the same store
+// wt (optional, both drivers; with or without alpha / share): the weighted form of the same launch - the mean over the neighbours[row] nearest
+// of the four rows, weighted by their similarities under width[row] (DEVICE arrays of one value per caller's row, either nullable = 4 / +inf;
+// a ragged batch finds the row through its tables, as alpha), sims_out (nullable) [M][B][T][4] the merged lists' similarities beside idx_out
+struct KnnWeight {
+    const int* neighbours = nullptr;
+    const float* width = nullptr;
+    float* sims_out = nullptr;
+};
 int run_knn_segs(tvc_ctx*, hipStream_t, Ws&, const float* src, const KnnSegIn* in, int nin, float* out, int64_t* idx_out, int B, int T,
-                 const float* alpha = nullptr, const float* share = nullptr);
+                 const float* alpha = nullptr, const float* share = nullptr, const KnnWeight* wt = nullptr);
 // a weighted blend of M indices per row (knn_gather.hip): in[] = the (term, row) runs over M * B * T VIRTUAL query columns, term-major - term m's
 // search of real column n is column m * B * T + n -, weights = the caller's device array [rows][M] (read by the kernels, never by the host),
 // out [B][768][T] = w_0 * mu_0 + ... in term order, idx_out (nullable) [M][B][T][4]
 int run_knn_blend(tvc_ctx*, hipStream_t, Ws&, const float* src, const KnnSegIn* in, int nin, int M, const float* weights, float* out, int64_t* idx_out,
-                  int B, int T, const float* alpha = nullptr, const float* share = nullptr);
+                  int B, int T, const float* alpha = nullptr, const float* share = nullptr, const KnnWeight* wt = nullptr);
 // out[i] = sum_m |weights[rows[i]][m]| * *blob_amax(blobs[i * M + m]): the bound of row i's blended content
 int run_knn_blend_bound(tvc_ctx*, hipStream_t, const std::vector<const float*>& blobs, const std::vector<int>& rows, int M, const float* weights, float* out);
 // the content bound of an alpha call: out[i] = |1 - a| * idx_bound[i * stride] + |a| * srcmax[i] for utterance i < n, a = alpha[its row]
@@ -439,6 +447,11 @@ struct ConvertCall {
     // tvc_convert_*protect_f32: protect (device, one fp32 per caller's row; alpha may then be nullptr = 0) raises the share on unvoiced frames of
     // the f0 this call decodes - a_t = a + (1 - a) * (p * w[t]), one per query column (run_frame_share) in the place of the row's alpha
     const float* protect = nullptr;
+    // tvc_weighted_convert*_f32: neighbours (device, one int32 per caller's row) and width (device, one fp32 per caller's row), either nullable:
+    // the match is the mean over the row's k nearest of the four rows, weighted by their similarities (knn_gather.hip WeightIn) - the mu of alpha's
+    // and protect's definitions, every term's mu_m of a blend.  A convex combination of index rows: the content bounds stay as they are.
+    const int* neighbours = nullptr;
+    const float* width = nullptr;
     // tvc_convert_*path_f32: path (host settings) puts the Viterbi decode of the call's own logits (run_pitch_path, directly behind the encoder) in
     // the place of the per-frame decode: protect's voicing weight, the automatic shift, a tracker, the shift and the decoder read its f0
     const tvc_pitch_path* path = nullptr;

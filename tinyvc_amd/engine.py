@@ -113,8 +113,19 @@ _TUNED = {
 }
 
 
+# form "weighted": the tuned rows' conversions / the protect match with neighbours and width behind protect; everything behind the index is
+# optional, as there - (ragged,) for a conversion, "match".  No query of its own: the weights take no workspace.
+_WEIGHTED = {
+    False: ("tvc_workspace_bytes_path", "tvc_weighted_convert_f32"),
+    True: ("tvc_workspace_bytes_ragged_path", "tvc_weighted_convert_ragged_f32"),
+    "match": ("tvc_workspace_bytes_protect", "tvc_knn_match_weighted_f32"),
+}
+
+
 def _names(form, ragged=None):
     """(workspace query, entry) of a conversion (`ragged` a bool) or a match (None) from the tables above"""
+    if form == "weighted":
+        return _WEIGHTED["match" if ragged is None else ragged]
     if form == "tuned":
         return _TUNED[ragged]
     if form == "path":
@@ -128,7 +139,7 @@ def _names(form, ragged=None):
 _TrackArgs = collections.namedtuple("_TrackArgs", "start n W min_voiced slew ring count auto_shift")
 _CarryArgs = collections.namedtuple("_CarryArgs", "carry_frame carry")
 _SnapArgs = collections.namedtuple("_SnapArgs", "snap notes strength snap_carry_frame snap_note snap_ratio")
-_FEATURES_OFF = dict(lens=None, M=0, weights=None, alpha=None, protect=None, path=None, target_f0=None, shift_out=None,
+_FEATURES_OFF = dict(lens=None, M=0, weights=None, alpha=None, protect=None, neighbours=None, width=None, path=None, target_f0=None, shift_out=None,
                      **_CarryArgs(0, None)._asdict(), **_SnapArgs(None, None, None, 0, None, None)._asdict(), **_TrackArgs(0, 0, 0, 0, 0.0, None, None, None)._asdict())
 
 
@@ -581,6 +592,20 @@ class Engine:
             raise ValueError(f"{name} must be a contiguous fp32 [B = {B}] tensor on the device, got {tuple(t.shape)} {t.dtype}")
         return t
 
+    def _neighbours(self, t, B):
+        """k per row of a weighted call: a contiguous int32 [B] tensor on this device, used in place (the kernel clamps it to 1 .. 4 when it runs)"""
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"neighbours must be a torch.Tensor on the device (a contiguous int32 [B = {B}]), got {type(t).__name__}")
+        _check_dev(t, "neighbours", self.device)
+        if t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] != B or not t.is_contiguous():
+            raise ValueError(f"neighbours must be a contiguous int32 [B = {B}] tensor on the device, got {tuple(t.shape)} {t.dtype}")
+        return t
+
+    def _weight_args(self, neighbours, width, B):
+        """the weighted match's share of a call under the C parameters' names: either may be None (4 neighbours, an infinite width)"""
+        return dict(neighbours=_ptr(self._neighbours(neighbours, B)) if neighbours is not None else None,
+                    width=_ptr(self._per_row(width, "width", B)) if width is not None else None)
+
     def _index_args(self, form, prepared, Ns, weights, B):
         """The index of a call, checked on the host -> (what the entry takes for it, what its workspace query takes for it), each under
         the C parameters' names.  shared: (prepared, Ns) = one blob and its N; table: one blob and N per row; blend: weights [B, M] on the
@@ -591,7 +616,7 @@ class Engine:
         if form == "table":
             blobs, ns = self._table(prepared, Ns, B)
             return dict(prepared=blobs, N=ns), dict(N=ns)
-        if form in ("auto", "track", "alpha", "protect", "path", "tuned") and weights is None:
+        if form in ("auto", "track", "alpha", "protect", "path", "tuned", "weighted") and weights is None:
             blobs, ns = self._table(prepared, Ns, B)
             return dict(prepared=blobs, N=ns, M=1, weights=None), dict(N=ns, M=1)
         blobs, ns, M = self._blend_args(prepared, Ns, weights, B)
@@ -613,11 +638,13 @@ class Engine:
         return wav, B, L
 
     # ---- kNN match: one driver, the public forms forward to it ----
-    def _match(self, form, src, prepared, Ns, weights=None, want_indices=False, alpha=None, f0=None, protect=None):
+    def _match(self, form, src, prepared, Ns, weights=None, want_indices=False, alpha=None, f0=None, protect=None, neighbours=None, width=None,
+               want_similarities=False):
         """src [B, 768, T] matched against the index (`form`, prepared, Ns, weights: _index_args) -> matched [B, 768, T] (, indices [B, T, 4];
         [M, B, T, 4] for a blend: each term's own search).  form "alpha": the table (weights None) or blend form, and out = matched *
         (1 - alpha[b]) + src * alpha[b] (alpha: _per_row; indices always [M, B, T, 4]).  form "protect": the alpha form with the frame's share
-        a_t = a + (1 - a) * (protect[b] * w[t]) in alpha's place, w from f0 [B, 1, T] / [B, T] (alpha None: a = 0)."""
+        a_t = a + (1 - a) * (protect[b] * w[t]) in alpha's place, w from f0 [B, 1, T] / [B, T] (alpha None: a = 0).  form "weighted": the
+        protect form with alpha, protect and f0 all optional and neighbours / width (_weight_args) behind them (, similarities [M, B, T, 4])."""
         src = _prep(src, "source", self.device)
         B, C, T = src.shape
         if C != spec.SSL_DIM:
@@ -633,14 +660,27 @@ class Engine:
             named["alpha"] = _ptr(self._per_row(alpha, "alpha", B)) if alpha is not None else None
             named["protect"] = _ptr(self._per_row(protect, "protect", B))
             named["f0"] = _ptr(f0)
+        elif form == "weighted":
+            if protect is not None:
+                f0 = _prep(f0, "f0", self.device)
+                if f0.numel() != B * T or f0.shape[0] != B:
+                    raise ValueError(f"f0 must hold one value per frame, [B = {B}, 1, T = {T}] or [B, T], got {tuple(f0.shape)}")
+            named["alpha"] = _ptr(self._per_row(alpha, "alpha", B)) if alpha is not None else None
+            named["protect"] = _ptr(self._per_row(protect, "protect", B)) if protect is not None else None
+            named["f0"] = _ptr(f0) if protect is not None else None
+            named.update(self._weight_args(neighbours, width, B))
         out = torch.empty_like(src)
         terms = (sized["M"],) if "M" in sized else ()      # a blend's terms
         idx = torch.empty(*terms, B, T, 4, dtype=torch.int64, device=self.device) if want_indices else None
+        sims = torch.empty(*terms, B, T, 4, dtype=_F32, device=self.device) if want_similarities else None
         query, entry = _names(form)
         named["ws"], named["ws_bytes"] = self._query_ws(query, B=B, L=T * spec.HOP, **sized)
         named.update(ctx=self.ctx, stream=self._stream(), out=_ptr(out), idx_out=_ptr(idx))
+        if form == "weighted":
+            named["sims_out"] = _ptr(sims)
         self._ok(getattr(self.lib, entry)(*_lib.arguments(entry, named)), entry)
-        return (out, idx) if want_indices else out
+        res = (out,) + ((idx,) if want_indices else ()) + ((sims,) if want_similarities else ())
+        return res if len(res) > 1 else out
 
     def knn_match(self, src, prepared, N, want_indices=False):
         return self._match("shared", src, prepared, N, None, want_indices)
@@ -666,6 +706,15 @@ class Engine:
         unvoiced weight of frame t from f0 [B, 1, T] / [B, T] (u = f0 > 0, edges repeated, rows apart), alpha / protect contiguous fp32 [B]
         device tensors read when the kernels run (alpha None: a = 0): tvc_knn_match_protect_f32."""
         return self._match("protect", src, prepared, Ns, weights, want_indices, alpha, f0, protect)
+
+    def knn_match_weighted(self, src, prepared, Ns, neighbours=None, width=None, weights=None, alpha=None, f0=None, protect=None, want_indices=False,
+                           want_similarities=False):
+        """knn_match_multi / _blend / _alpha / _protect (weights, alpha, protect and its f0 all optional) with the mean over the k nearest of
+        the four rows, each weighted by w_e = clamp(1 - (s_0 - s_e) / width, 0, 1): neighbours a contiguous int32 [B] device tensor (k,
+        clamped to 1 .. 4; None: 4), width a contiguous fp32 [B] device tensor in cosine units (None: +inf), both read when the kernel runs
+        (, indices [M, B, T, 4], similarities [M, B, T, 4]: what the lists held when the weights were formed): tvc_knn_match_weighted_f32;
+        the definition is in include/tinyvc_hip.h."""
+        return self._match("weighted", src, prepared, Ns, weights, want_indices, alpha, f0, protect, neighbours, width, want_similarities)
 
     def frame_share(self, f0_packed, start, counts, alpha, protect):
         """The per-frame share alone (tvc_frame_share_f32): f0_packed any contiguous fp32 device tensor, row i = its flattened values
@@ -724,7 +773,7 @@ class Engine:
         return _SnapArgs(ctypes.byref(tune.settings()), _ptr(notes), _ptr(strength), *state)
 
     def _convert(self, form, wav, prepared, Ns, pitch_shift, noise_angle=None, lengths=None, weights=None, target_f0=None, out=None, shift_out=None,
-                 track=None, alpha=None, protect=None, path=None, carry=None, tune=None, tune_carry=None):
+                 track=None, alpha=None, protect=None, path=None, carry=None, tune=None, tune_carry=None, neighbours=None, width=None):
         """wav [B, L] converted toward the index (`form`, prepared, Ns, weights: _index_args) -> wave [B, L]; form "auto" / "track" ->
         (wave, shifts [B]).  "track": "auto" with the register taken from `track` (a PitchTrack: the streams' history), equal lengths only.
         "alpha": the table / blend call keeping the share alpha[b] of row b's own content features (alpha: _per_row); with target_f0 it is the
@@ -736,7 +785,9 @@ class Engine:
         there, in place (tvc_convert_carry_f32).  "tuned": the "path" call with alpha, protect, path and carry ALL optional and `tune`, a
         PitchSnap, behind them: the f0 the decoder reads is snapped to tune.notes in place, one launch in front of the decoder
         (tvc_tuned_convert_f32 / tvc_tuned_convert_ragged_f32); `tune_carry` (equal lengths only): a SnapCarry of B streams, read at frame 0 and
-        written behind frame tune_carry.hop_frames - 1.
+        written behind frame tune_carry.hop_frames - 1.  "weighted": the "tuned" call with `tune` optional too and neighbours / width
+        (_weight_args: k and the similarity width per row, either may be None) behind protect: the match is the weighted mean over the k
+        nearest rows (tvc_weighted_convert_f32 / tvc_weighted_convert_ragged_f32; the workspace is the tuned call's).
         lengths: a ragged batch (row b holds an utterance of lengths[b] samples, a multiple of 480, zero-padded behind it; every utterance
         is converted over its OWN length).  pitch_shift: a float, or one per row for every form but "shared".  Every host check comes
         first, then the noise draw (which advances torch's generator), then device work: a refused call leaves no trace.
@@ -755,25 +806,27 @@ class Engine:
             named["prepared_index"] = named.pop("prepared")      # the conversion's name for the stage call's `prepared`
         if ragged and (form == "track" or track is not None):
             raise ValueError("track: streams advance in lock step, there is no ragged form")
-        if carry is not None and (form not in ("path", "tuned") or path is None or ragged):
+        if carry is not None and (form not in ("path", "tuned", "weighted") or path is None or ragged):
             raise ValueError("carry: the pitch path's state - it goes with form \"path\", and streams advance in lock step: there is no ragged form")
         found = form in ("auto", "track")      # the shifts are found on the device: pitch_shift is the offset, the applied shifts come back
-        if (tune is None) != (form != "tuned") or (tune_carry is not None and (tune is None or ragged)):
+        if (form != "weighted" and (tune is None) != (form != "tuned")) or (tune_carry is not None and (tune is None or ragged)):
             raise ValueError("tune goes with form \"tuned\" (and tune_carry with tune; streams advance in lock step: there is no ragged form)")
-        shares = form in ("alpha", "protect", "path", "tuned")      # the table / blend call with or without target registers (and, equal lengths, a tracker), plus the source's share
+        shares = form in ("alpha", "protect", "path", "tuned", "weighted")      # the table / blend call with or without target registers (and, equal lengths, a tracker), plus the source's share
         if shares:
             found = target_f0 is not None
             if track is not None and not found:
                 raise ValueError("track needs target_f0: the tracker finds the register the automatic shift starts from")
             if form == "alpha" or alpha is not None:
                 named["alpha"] = _ptr(self._per_row(alpha, "alpha", B))
-            if form == "protect" or (form in ("path", "tuned") and protect is not None):
+            if form == "protect" or (form in ("path", "tuned", "weighted") and protect is not None):
                 named["protect"] = _ptr(self._per_row(protect, "protect", B))
-            if form == "path" or (form == "tuned" and path is not None):
+            if form == "weighted":
+                named.update(self._weight_args(neighbours, width, B))
+            if form == "path" or (form in ("tuned", "weighted") and path is not None):
                 named["path"] = ctypes.byref(path.settings())
                 if carry is not None:
                     named.update(self._carry_args(carry, B, T)._asdict())
-            if form == "tuned":
+            if form == "tuned" or (form == "weighted" and tune is not None):
                 named.update(self._snap_args(tune, tune_carry, B, T)._asdict())
         if found:
             named["target_f0"] = _ptr(self._per_row(target_f0, "target_f0", B))

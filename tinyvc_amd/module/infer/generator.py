@@ -6,7 +6,7 @@ from .. import utils
 from ...engine import loudness_in_place, pitch_shifts
 from .._base import HipModule
 from ..tinyvc import Decoder, Encoder
-from ..tinyvc.feature_retrieval import (alpha_rows, check_blend, check_references, check_tune_carry, resolve_tune, limit_rows, loudness_rows, prepare_reference, prepare_references,
+from ..tinyvc.feature_retrieval import (alpha_rows, match_k_rows, match_width_rows, resolve_match_k, resolve_match_width, check_blend, check_references, check_tune_carry, resolve_tune, limit_rows, loudness_rows, prepare_reference, prepare_references,
                                         protect_rows, resolve_alpha, resolve_auto_pitch, resolve_f0_estimation, resolve_limit, resolve_loudness,
                                         resolve_protect, target_form, target_registers)
 
@@ -55,7 +55,8 @@ class Generator(HipModule):
 
     @torch.no_grad()
     def convert(self, wf, tgt, pitch_shift, f0_estimation="default", device=None, noise_angle=None, lengths=None, auto_pitch=None,
-                return_shift=False, track=None, alpha=None, protect=None, loudness=None, limit=None, carry=None, tune=None, tune_carry=None):
+                return_shift=False, track=None, alpha=None, protect=None, loudness=None, limit=None, carry=None, tune=None, tune_carry=None, k=None,
+                match_width=None):
         """generator.py:26-34: wf [B, L], tgt [1 or B, 768, N] -> converted waveform [B, L'] (L' = L
         padded to a multiple of 480).  `f0_estimation` / `device` are accepted and ignored exactly as
         in the reference - but for `f0_estimation='viterbi'` or a feature_retrieval.PitchPath (extension): f0 is then the pitch path, a
@@ -119,7 +120,17 @@ class Generator(HipModule):
         defaults).  Every target form, equal and ragged batches, with every other keyword; protect's voicing and the tracker keep reading the
         unshifted f0.  A strength of 0 is the call without it bit for bit, None (the default) launch for launch.  `tune_carry` (equal batches
         only): a feature_retrieval.SnapCarry of B streams - the note and the smoothed ratio travel from one window to the next, in place.
-        The defaults are guesses: nobody has listened."""
+        The defaults are guesses: nobody has listened.
+        `k` / `match_width` (extension; k is the reference's match_features(..., k), which its convert never passes): every frame becomes the
+        mean over its k nearest index rows (1 .. 4: the fused search keeps four), neighbour e weighted by clamp(1 - (s_0 - s_e) /
+        match_width, 0, 1) with s the cosine similarities the search already holds - one more instantiation of the merge + gather kernel,
+        no new launch, no workspace (tvc_weighted_convert_f32 / tvc_weighted_convert_ragged_f32; the definition is in
+        include/tinyvc_hip.h and is exact: bit for bit what tests/helpers_match_weight.py computes from the call's own similarities).  k: an
+        int, B of them, or an int32 [B] / [1] device tensor; match_width: a float >= 0 in cosine units (inf: equal weights, 0: the nearest
+        row alone), B of them, or an fp32 [B] / [1] device tensor.  [B] tensors are used in place and read when the kernel runs, which
+        clamps k and treats a NaN or negative width as inf; host values outside the ranges are refused before any engine work.  Every
+        target form (a Blend: every term's match), equal and ragged batches, with every other keyword.  k = 4 with match_width = inf is
+        the call without them bit for bit, None for both (the default) launch for launch.  No width is suggested: nobody has listened."""
         # 1. classify the target once; malformed targets, registers and shift lists are refused before any engine or device work
         B = wf.shape[0] if wf.dim() == 2 else 1
         auto = auto_pitch is not None and auto_pitch is not False
@@ -152,6 +163,9 @@ class Generator(HipModule):
                 raise ValueError(f"carry: a carry of {carry.n_streams} streams for a batch of {B}")
             if -(-wf.shape[-1] // 480) <= carry.hop_frames:
                 raise ValueError(f"carry: hop_frames = {carry.hop_frames} must be below the call's {-(-wf.shape[-1] // 480)} frames")
+        near = resolve_match_k(k, B) if k is not None else None
+        wide = resolve_match_width(match_width, B) if match_width is not None else None
+        weighted = near is not None or wide is not None
         tune = resolve_tune(tune)
         if tune_carry is not None and lengths is not None:
             raise ValueError("tune_carry with lengths: streams advance in lock step, there is no ragged form")
@@ -177,11 +191,11 @@ class Generator(HipModule):
             blobs, ns = prepare_references([self._input_device(t) for t in tgt] if isinstance(tgt, (list, tuple)) else self._input_device(tgt))
         else:
             blobs, ns = prepare_reference(self._input_device(tgt))
-            if auto or shifts is not None or share is not None or guard is not None or path is not None or tune is not None:      # a value per row (given, or found on the device): the shared blob in every row (one segment)
+            if auto or shifts is not None or share is not None or guard is not None or path is not None or tune is not None or weighted:      # a value per row (given, or found on the device): the shared blob in every row (one segment)
                 form, blobs, ns = "table", [blobs] * B, [ns] * B
         # 4. one engine call
         pitch = shift if shifts is None else shifts
-        if share is not None or guard is not None or path is not None or tune is not None:      # the alpha / protect / path / tuned entry covers every case below: plain shifts, target registers, a tracker
+        if share is not None or guard is not None or path is not None or tune is not None or weighted:      # the alpha / protect / path / tuned / weighted entry covers every case below: plain shifts, target registers, a tracker
             rows = {"alpha": alpha_rows(share, B, wf.device) if share is not None else None}
             if guard is not None:
                 rows["protect"] = protect_rows(guard, B, wf.device)
@@ -191,7 +205,10 @@ class Generator(HipModule):
                 rows["carry"] = carry
             if tune is not None:
                 rows["tune"], rows["tune_carry"] = tune, tune_carry
-            res = eng._convert("tuned" if tune is not None else "path" if path is not None else "alpha" if guard is None else "protect", wf, blobs, ns, pitch, noise_angle, lens, w,
+            if weighted:
+                rows["neighbours"] = match_k_rows(near, B, wf.device) if near is not None else None
+                rows["width"] = match_width_rows(wide, B, wf.device) if wide is not None else None
+            res = eng._convert("weighted" if weighted else "tuned" if tune is not None else "path" if path is not None else "alpha" if guard is None else "protect", wf, blobs, ns, pitch, noise_angle, lens, w,
                                target_registers(regs, B, wf.device) if auto else None, track=track, **rows)
             res = res if return_shift or not auto else res[0]
         elif not auto:

@@ -19,7 +19,7 @@ import torch
 from ...engine import (SOLA_CROSS, SOLA_DELAY, SOLA_SEARCH, loudness_geometry, loudness_levels, pitch_shifts, sola_geometry, stream_denoise_geometry,
                        stream_gate_geometry, stream_resample_geometry)
 from ...stream_state import CARRY_STATE, SNAP_STATE, DENOISE_STATE, DOOR_STATE, GATE_STATE, LIMITER_STATE, LOUDNESS_STATE, TRACK_STATE, addresses, allocate, reset
-from ..tinyvc.feature_retrieval import (PitchCarry, PitchTrack, SnapCarry, alpha_rows, check_f0_carry, check_stream_tune, gpu_device, limit_ceiling, limiter_settings, protect_rows, resolve_alpha,
+from ..tinyvc.feature_retrieval import (PitchCarry, PitchTrack, SnapCarry, alpha_rows, match_k_rows, match_width_rows, resolve_match_k, resolve_match_width, check_f0_carry, check_stream_tune, gpu_device, limit_ceiling, limiter_settings, protect_rows, resolve_alpha,
                                         resolve_auto_pitch, resolve_f0_estimation, resolve_protect, target_form)
 from .generator import Generator
 
@@ -385,6 +385,10 @@ class BatchedStreamInfer:
     `protect` (convert's, in alpha's forms; the keyword behind alpha): how far that share rises on the unvoiced frames of each window's own f0, held as
     `self.protect`, a [S] device tensor like `self.alpha` (`stream.protect.fill_(...)` / `copy_(...)` replay the same graph); with or without
     alpha; None (the default) is the stream as it was.
+    `k` / `match_width` (convert's: an int in 1 .. 4 / a width >= 0 in cosine units, one per stream, or an int32 / fp32 [S] / [1] device
+    tensor): the weighted match - every frame the mean over its k nearest index rows, weighted by their similarities -, held as `self.k`
+    and `self.match_width`, [S] device tensors read when a block runs: `stream.k.fill_(1)` / `stream.match_width.fill_(...)` between blocks
+    replay the same captured graph (their addresses are part of the graph key).  None for both (the default) is the stream as it was.
     `f0_estimation` (convert's): 'viterbi' or a feature_retrieval.PitchPath decodes every window's pitch as one path over its own frames
     (each window afresh unless f0_carry is set; the window's left context is what steadies the emitted frames); held as
     `self.f0_estimation`, and its settings - host values baked into the launch - are part of the graph key.  Every other name is ignored.
@@ -426,7 +430,7 @@ class BatchedStreamInfer:
     shorter than the three sizes say, and a look-ahead shorter than the pad is refused."""
 
     def __init__(self, generator: Generator, n_streams=1, target=None, pitch_shift=0., device=None,
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, denoise=None, loudness=None, gate=None, limiter=None, f0_carry=False, tune=None, door=None,
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, k=None, match_width=None, denoise=None, loudness=None, gate=None, limiter=None, f0_carry=False, tune=None, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         self.input_size, _ = check_window(block_size, extra_size, crossfade_size, sola_search_size, last_delay_size,
                                            auto_pitch is not None and auto_pitch is not False)
@@ -436,6 +440,8 @@ class BatchedStreamInfer:
         self.tune_carry = None
         share = resolve_alpha(alpha, n_streams) if alpha is not None else None      # refused here, before anything is allocated
         guard = resolve_protect(protect, n_streams) if protect is not None else None
+        near = resolve_match_k(k, n_streams) if k is not None else None
+        wide = resolve_match_width(match_width, n_streams) if match_width is not None else None
         self.n_streams, self.block_size = n_streams, block_size
         self.door, self.gate, self.denoise, self.loudness, self.limiter = (self._fits(name, stage) for name, stage in (
             ("door", door), ("gate", gate), ("denoise", denoise), ("loudness", loudness), ("limiter", limiter)))
@@ -455,6 +461,9 @@ class BatchedStreamInfer:
         # the streams' shares of their own content features: a [S] device tensor every block reads when it runs, or None (the plain match)
         self.alpha = alpha_rows(share, n_streams, self.device) if share is not None else None
         self.protect = protect_rows(guard, n_streams, self.device) if guard is not None else None      # ... and their rise on unvoiced frames, likewise
+        # the weighted match: k and the similarity width of every stream, [S] device tensors read when a block runs, or None (four rows, equal weights)
+        self.k = match_k_rows(near, n_streams, self.device) if near is not None else None
+        self.match_width = match_width_rows(wide, n_streams, self.device) if wide is not None else None
         self.extra_size = extra_size
         self.sola_search_size = sola_search_size
         self.last_dilay_size = last_delay_size          # (sic) the reference's attribute name, stream.py:49
@@ -568,11 +577,12 @@ class BatchedStreamInfer:
         if self.auto_pitch is None:
             y = self.generator.convert(self.input_wav, self.target, self.pitch_shift, device=self.device,
                                        f0_estimation=self.f0_estimation, noise_angle=noise_angle, alpha=self.alpha, protect=self.protect,
-                                       carry=self.pitch_carry, **self._tune_kw())
+                                       carry=self.pitch_carry, k=self.k, match_width=self.match_width, **self._tune_kw())
         else:
             y, pshift = self.generator.convert(self.input_wav, self.target, self.pitch_shift, device=self.device, f0_estimation=self.f0_estimation,
                                                noise_angle=noise_angle, auto_pitch=self.auto_pitch, return_shift=True, track=self.pitch_track,
-                                               alpha=self.alpha, protect=self.protect, carry=self.pitch_carry, **self._tune_kw())
+                                               alpha=self.alpha, protect=self.protect, carry=self.pitch_carry, k=self.k, match_width=self.match_width,
+                                               **self._tune_kw())
         eng = self.generator.engine(self.device)
         out, shift = eng.sola(y, self.sola_buffer, self.fade_in_window, self.block_size, self.use_phase_vocoder, want_shift=True,
                               crossfade=self.crossfade_size, search=self.sola_search_size, delay=self.last_dilay_size)
@@ -617,6 +627,10 @@ class BatchedStreamInfer:
             tkey += (("alpha", self.alpha.data_ptr()),)
         if self.protect is not None:
             tkey += (("protect", self.protect.data_ptr()),)
+        if self.k is not None:      # likewise: k.fill_(...) / match_width.fill_(...) keep the graph
+            tkey += (("k", self.k.data_ptr()),)
+        if self.match_width is not None:
+            tkey += (("match_width", self.match_width.data_ptr()),)
         path = resolve_f0_estimation(self.f0_estimation)
         if path is not None:      # the pitch path's settings ARE values: host numbers baked into the launch, so another PitchPath is another graph
             tkey += (("f0_estimation", path.params()),)
@@ -692,7 +706,7 @@ class StreamInfer(BatchedStreamInfer):
     """Single stream with the reference's constructor and 1-D buffers (stream.py:31-57)."""
 
     def __init__(self, generator: Generator, target=None, pitch_shift=0., device=torch.device("cpu"),
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, denoise=None, loudness=None, gate=None, limiter=None, f0_carry=False, tune=None, door=None,
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, k=None, match_width=None, denoise=None, loudness=None, gate=None, limiter=None, f0_carry=False, tune=None, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         dev = torch.device(device)
         if dev.type != "cuda":
@@ -700,7 +714,7 @@ class StreamInfer(BatchedStreamInfer):
         super().__init__(generator, n_streams=1, target=target, pitch_shift=pitch_shift, device=dev, block_size=block_size, extra_size=extra_size,
                          use_phase_vocoder=use_phase_vocoder, f0_estimation=f0_estimation, use_graph=use_graph, alpha=alpha, protect=protect, denoise=denoise, gate=gate,
                          limiter=limiter, door=door, crossfade_size=crossfade_size, sola_search_size=sola_search_size, last_delay_size=last_delay_size,
-                         auto_pitch=auto_pitch, pitch_track=pitch_track, loudness=loudness, f0_carry=f0_carry, tune=tune)
+                         auto_pitch=auto_pitch, pitch_track=pitch_track, loudness=loudness, f0_carry=f0_carry, tune=tune, k=k, match_width=match_width)
 
     @torch.no_grad()
     def audio_callback(self, block, noise_angle=None):

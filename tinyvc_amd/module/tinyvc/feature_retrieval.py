@@ -264,6 +264,53 @@ def protect_rows(resolved, B, device):
     return alpha_rows(resolved, B, device, "protect")
 
 
+def resolve_match_k(k, B):
+    """convert's k - how many of the four nearest index rows a frame averages (the reference's match_features(..., k); the fused match keeps
+    four, so 1 .. 4) - checked on the host: an int in 1 .. 4, a sequence of B (or 1) of them, or a 1-D int32 tensor of B or 1 entries ON THE
+    DEVICE, taken as it is (the kernel clamps it to 1 .. 4 when it runs).  Returns a list of B ints, or the tensor; ValueError naming k
+    otherwise."""
+    if isinstance(k, torch.Tensor):
+        if k.dim() != 1 or k.numel() not in (1, B):
+            raise ValueError(f"k: a tensor of 1 or B = {B} entries, got shape {tuple(k.shape)}")
+        if k.dtype != torch.int32:
+            raise ValueError(f"k: an int32 tensor (it is read in place by the kernels, never converted), got {k.dtype}")
+        if k.device.type != "cuda":
+            raise ValueError(f"k: a tensor lives on the GPU, where the kernels read it when they run; got one on {k.device} (pass ints instead)")
+        return k
+    vals = list(k) if isinstance(k, (list, tuple)) else [k]
+    if len(vals) not in (1, B):
+        raise ValueError(f"k: {len(vals)} values for a batch of {B}")
+    for x in vals:
+        if isinstance(x, bool) or not isinstance(x, int) or not 1 <= x <= 4:
+            raise ValueError(f"k: an int in 1 .. 4 (the fused match keeps four neighbours; match_features serves any k), one per row or an int32 [B] / [1] device "
+                             f"tensor, got {k!r}")
+    return [int(x) for x in vals] * (B if len(vals) == 1 else 1)
+
+
+def match_k_rows(resolved, B, device):
+    """resolve_match_k's result as the contiguous int32 [B] device tensor the engine takes (a [B] tensor passes through as it is)"""
+    if isinstance(resolved, torch.Tensor):
+        return alpha_rows(resolved, B, device, "k")
+    return torch.tensor(resolved, dtype=torch.int32, device=device)
+
+
+def resolve_match_width(width, B):
+    """convert's match_width - the similarity width of the weighted match, in cosine units: neighbour e of a frame weighs
+    clamp(1 - (s_0 - s_e) / width, 0, 1), s the cosine similarities (include/tinyvc_hip.h) - in alpha's forms: a float >= 0 (inf: equal
+    weights; 0: the nearest row and its exact ties), B of them, or an fp32 [B] / [1] device tensor, taken as it is.  A negative or NaN host
+    value is refused under its own name."""
+    res = resolve_alpha(width, B, "match_width")
+    if not isinstance(res, torch.Tensor):
+        for x in res:
+            if not x >= 0.0:
+                raise ValueError(f"match_width: a width in cosine units is >= 0 (inf: equal weights), got {x!r}")
+    return res
+
+
+def match_width_rows(resolved, B, device):
+    return alpha_rows(resolved, B, device, "match_width")
+
+
 class LoudnessMatch:
     """convert's loudness - how far the converted wave follows the loudness envelope of its source (tvc_loudness_match_f32; the definition is
     in include/tinyvc_hip.h; 1 - RVC's rms_mix_rate): every `sub_frame` samples the output is scaled by (Es / Eo)^(share / 2), Es and Eo the
@@ -797,6 +844,33 @@ def alpha_keywords(args, script):
             sys.exit(f"{script}: --protect must be a finite number")
         print(f"Protecting unvoiced frames: their share of the source's own features rises by {protect:g} of what the match would take (protect)")
         kw["protect"] = float(protect)
+    return kw
+
+
+def add_match_weight_argument(parser):
+    """`-k K` and `--match-width W` for the entry scripts' parsers: absent (None) is the call without them"""
+    parser.add_argument("-k", "--neighbours", dest="k", type=int, default=None,
+                        help="average the K nearest index rows of every frame (1 .. 4; the reference's match_features k); default: absent, "
+                             "the four nearest with equal weight")
+    parser.add_argument("--match-width", type=float, default=None,
+                        help="weight neighbour e by clamp(1 - (s_0 - s_e) / W, 0, 1), s the cosine similarities: W in cosine units, >= 0 "
+                             "(inf: equal weights, 0: the nearest row alone).  No value is suggested: nobody has listened.  default: absent")
+
+
+def match_weight_keywords(args, script):
+    """what `-k` / `--match-width` add to the script's convert / stream call: nothing when they are absent (the call is today's), else
+    {"k": K} / {"match_width": W} and one printed line; a value outside its range ends the script"""
+    kw = {}
+    if args.k is not None:
+        if not 1 <= args.k <= 4:
+            sys.exit(f"{script}: -k must be 1 .. 4 (the fused match keeps four neighbours)")
+        kw["k"] = int(args.k)
+    if args.match_width is not None:
+        if not args.match_width >= 0:
+            sys.exit(f"{script}: --match-width must be >= 0 (cosine units; inf: equal weights)")
+        kw["match_width"] = float(args.match_width)
+    if kw:
+        print(f"Weighted match: the {kw.get('k', 4)} nearest rows of every frame, similarity width {kw.get('match_width', math.inf):g}")
     return kw
 
 
