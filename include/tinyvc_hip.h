@@ -763,6 +763,70 @@ int tvc_weighted_convert_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav
                                     float pitch_shift, const float* pitch_shifts, float* shift_out, const float* noise_angle, uint64_t seed,
                                     float* wave, int B, void* ws, size_t ws_bytes);
 
+/* ---- match along a path: a continuity weight between neighbouring frames (unit selection's join cost; no reference counterpart) ----
+ * The weighted entries choose per frame: the weights form around neighbour 0, whatever the frame before chose.  Where two index rows are
+ * almost equally near a stretch of frames, the anchor of a sharp match (k = 1, a small width) alternates between them every 20 ms.  These
+ * entries choose the anchor as a SEQUENCE: a neighbour gains by its similarity to the query (s, which the search holds) and by its
+ * similarity to the neighbour chosen for the frame before (the affinity a).  Per utterance - a row's T frames, or in a ragged batch the
+ * frames [pre[u], pre[u] + tb[u]) of utterance u - and, in a blend, per term: a path never leaves its utterance, its row, its term or its
+ * stream.  Frames t = 0 .. len - 1; k = the row's clamped neighbours (NULL: 4); s_t[e], i_t[e] the column's merged top-4, exactly what every
+ * entry selects; c = join[r], a DEVICE fp32 per caller's row, read when the kernels run.  Every step below is one fp32 rounding, no FMA.
+ * THE TOTAL RULE (the kernels' memory safety rests on it): a similarity or an affinity that is not finite counts as 0; a c that is NaN or
+ *   negative counts as 0, a c of +inf as the largest finite float (FLT_MAX); and sat(x) = fminf(fmaxf(x, -FLT_MAX), FLT_MAX) - NaN gives
+ *   -FLT_MAX - is applied where the rules below say so (it changes nothing while |values| stay below FLT_MAX).  Then every state of every
+ *   frame has a finite score <= 0 with a maximum of exactly 0, and - independently of that - a back-pointer is the d < k of a comparison
+ *   chain that starts at d = 0 and the last anchor the e < k of one that starts at e = 0: whatever the arrays hold, every anchor lies in
+ *   0 .. k - 1.
+ * Affinity, t >= 1 and d, e < 4:  a_t[d][e] = (dot(row i_{t-1}[d], row i_t[e]) * inv[i_{t-1}[d]]) * inv[i_t[e]] over the segment's own blob,
+ *   inv = 1 / (|v| + 1e-6) as every prepared blob holds it.  The dot in ONE order: with p_k the rounded product of channel k, partial sum
+ *   P_l = ((p_l + p_{l+64}) + ..) + p_{l+704} for l = 0 .. 63 (ascending), then six rounds Q_l <- Q_l + Q_{l xor m} for m = 32, 16, 8, 4, 2, 1;
+ *   dot = Q_0.  Its bits depend on no tile, split, batch size or k.  The dot carries 18 roundings (a product, 11 + 6 sums) where one chain of 768 carries
+ *   768; with the two inv factors a is held to the 770 * 2^-24 of sims_out against dot / ((|u| + 1e-6) (|v| + 1e-6)) in fp64.  Frame 0 of an utterance has none (affinity_out: zeros).
+ * Scores:  D_0[e] = s_0[e];  for t >= 1, e < k:  D_t[e] = sat(s_t[e] + max_{d<k} (D_{t-1}[d] + sat(c * a_t[d][e]))) - the max is exact, ties
+ *   go to the lowest d, and the back-pointer records it.  After every frame, 0 included: D_t[e] = sat(D_t[e] - max_{e<k} D_t[e]), one
+ *   subtraction - scores stay near 0 at 15 000 frames, where accumulated sums would lose the 1e-3 differences between similarities.
+ * Anchor:  p(len - 1) = argmax_{e<k} D, the lowest e on ties;  p(t - 1) = the back-pointer of state p(t) of frame t.
+ * Weights around the anchor p:  w_p = 1;  for e < k, e != p:  g = |s_p - s_e|, t = g / width (__fdiv_rn), w_e = (t > 0) ? fmaxf(0, 1 - t) : 1
+ *   (the RAW similarities, as the weighted entries');  w_e = 0 from k on.
+ * Mean:  the terms w_e * r_e with w_e != 0 are added in ascending e, the first of them starting the sum (product and sum rounded on their
+ *   own; a weight of exactly 1 contributes r_e's own bits);  W = ((w_0 + w_1) + w_2) + w_3 >= 1;  mu = acc / W (__fdiv_rn).
+ *   tests/helpers_match_join.py restates all of it in numpy fp32, operation by operation.
+ * Consequences: c = 0 on finite similarities gives anchor 0 on every frame and the weighted call bit for bit; width = +inf makes the path
+ *   irrelevant (the same bits for any c); width = 0 without ties stores the path's row's own bits - unit selection; k = 1 has no choice to
+ *   make; mu stays a convex combination of index rows, so the decoder's range guard and every content bound stay as they are;
+ *   join == NULL is the weighted call, launch for launch.
+ * Kernels: no search kernel changes and the indices depend on nothing new.  Three launches take the weighted gather's place: merge +
+ *   affinity (the merged lists, idx_out and sims_out; the 16 affinities per column), the path (one wavefront per (term, utterance), the walk
+ *   back in the same launch) and the joined form of the merge + gather, which reads the anchor where it forms the weights.  No host
+ *   synchronisation: capturable.  Workspace of their own (101 bytes per query column and term), from the call's one walk.
+ * tvc_knn_match_joined_f32: tvc_knn_match_weighted_f32's arguments plus join behind width and, behind sims_out, anchor_out (nullable, int32
+ *   [M][B][T]) and affinity_out (nullable, fp32 [M][B][T][4][4], [d][e]; frame 0's sixteen are zeros).  anchor_out / affinity_out without
+ *   join are refused.  Workspace: tvc_workspace_bytes_match_joined (B rows of L = 480 T samples).
+ * tvc_joined_convert_f32 / tvc_joined_convert_ragged_f32: the weighted entries' arguments plus join behind width.  Workspace:
+ *   tvc_workspace_bytes_joined / _ragged_joined.  Every host check runs before any device work.
+ * A stream decodes a path per window; carrying the scores from window to window is out of scope, as are the sharded route and a default:
+ *   nobody has listened. */
+int tvc_workspace_bytes_joined(tvc_ctx* ctx, int B, int64_t L, const int64_t* N, int M, size_t* out_bytes);
+int tvc_workspace_bytes_ragged_joined(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, const int64_t* N, int M, size_t* out_bytes);
+int tvc_workspace_bytes_match_joined(tvc_ctx* ctx, int B, int64_t L, const int64_t* N, int M, size_t* out_bytes);
+int tvc_knn_match_joined_f32(tvc_ctx* ctx, void* stream, const float* src, const float* f0, const float* const* prepared, const int64_t* N,
+                             int M, const float* weights, const float* alpha, const float* protect, const int32_t* neighbours,
+                             const float* width, const float* join, float* out, int64_t* idx_out, float* sims_out, int32_t* anchor_out,
+                             float* affinity_out, int B, int T, void* ws, size_t ws_bytes);
+int tvc_joined_convert_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M,
+                           const float* weights, const float* alpha, const float* protect, const int32_t* neighbours, const float* width,
+                           const float* join, const tvc_pitch_path* path, int carry_frame, float* carry, const tvc_pitch_snap* snap,
+                           const float* notes, const float* strength, int snap_carry_frame, int32_t* snap_note, float* snap_ratio,
+                           const float* target_f0, int start, int n, int W, int min_voiced, float slew, float* ring, int64_t* count,
+                           float* auto_shift, float pitch_shift, const float* pitch_shifts, float* shift_out, const float* noise_angle,
+                           uint64_t seed, float* wave, int B, int64_t L, void* ws, size_t ws_bytes);
+int tvc_joined_convert_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens,
+                                  const float* const* prepared, const int64_t* N, int M, const float* weights, const float* alpha,
+                                  const float* protect, const int32_t* neighbours, const float* width, const float* join,
+                                  const tvc_pitch_path* path, const tvc_pitch_snap* snap, const float* notes, const float* strength,
+                                  const float* target_f0, float pitch_shift, const float* pitch_shifts, float* shift_out,
+                                  const float* noise_angle, uint64_t seed, float* wave, int B, void* ws, size_t ws_bytes);
+
 /* streaming tail-------------------------------------------------------------------------- */
 /* StreamInfer.audio_callback after convert (reference module/infer/stream.py:74-95), batched over
  * S streams: y [S, Ly] converted buffers; sola_buf [S,1920] in/out; fade_in [1920] = the sin^2

@@ -39,7 +39,7 @@ from tinyvc_amd import audio_io, parallel, spec
 from tinyvc_amd.engine import limiter_geometry, loudness_geometry
 from tinyvc_amd.module.infer import Generator
 from tinyvc_amd.module.tinyvc import Blend, Decoder, Encoder
-from tinyvc_amd.module.tinyvc.feature_retrieval import (PitchPath, add_alpha_argument, add_match_weight_argument, match_weight_keywords, add_auto_pitch_argument, add_blend_argument, add_f0_arguments,
+from tinyvc_amd.module.tinyvc.feature_retrieval import (PitchPath, add_alpha_argument, add_match_weight_argument, match_weight_keywords, add_continuity_argument, continuity_keywords, add_auto_pitch_argument, add_blend_argument, add_f0_arguments,
                                                         add_f0_carry_argument, add_tune_arguments, f0_carry_keywords, tune_keywords,
                                                         add_limit_argument, add_loudness_argument, alpha_keywords, attach_register, f0_keywords,
                                                         limit_keywords, loudness_keywords, pitch_register)
@@ -66,6 +66,7 @@ def build_parser():
     add_limit_argument(p)           # --limit [DB]: a look-ahead peak limiter behind everything else: no sample above the ceiling
     add_alpha_argument(p)           # --alpha A: keep that share of every file's own content features in the match; --protect P: more on unvoiced frames
     add_match_weight_argument(p)    # -k K --match-width W: the K nearest index rows of every frame, weighted by their similarities
+    add_continuity_argument(p)      # --continuity C: choose the anchor of the weighted match along a path over each file
     p.add_argument("-c", "--chunk-size", default=1920, type=int)
     p.add_argument("-b", "--buffer-size", default=4, type=int)
     p.add_argument("-nc", "--no-chunking", default=False, type=bool)
@@ -140,7 +141,7 @@ def convert_chunked(gen, batch, tgt, pitch_shift, chunk_size, buffer_blocks, use
     `noise_angles(i)` -> [B, 961, T] injects the decoder's noise phases of block i (parity runs against the oracle's
     `stream_callback`; default: drawn on the device per block, as the reference's `torch.rand` is).
     `return_blocks`: also return the untrimmed block outputs [B, nblk, chunk_size] and the SOLA lags [nblk, B].
-    `stream_kw`: further BatchedStreamInfer keywords (f0_estimation, f0_carry, tune, alpha, protect, k, match_width, loudness: a share of the source's loudness envelope - a StreamLoudness
+    `stream_kw`: further BatchedStreamInfer keywords (f0_estimation, f0_carry, tune, alpha, protect, k, match_width, continuity, loudness: a share of the source's loudness envelope - a StreamLoudness
     stage for these streams is built from it here; limit: a ceiling in dBFS - a StreamLimiter likewise, passed on as `limiter`, whose
     delay_size joins the trim)."""
     from tinyvc_amd.module.infer import BatchedStreamInfer, StreamLimiter, StreamLoudness
@@ -198,6 +199,7 @@ def main(argv=None, world=None, rank=None, local_rank=None):
         auto = True
     alpha_kw = alpha_keywords(args, "infer.py")      # {} without --alpha / --protect: every call below is then the call it has always been
     alpha_kw.update(match_weight_keywords(args, "infer.py"))      # likewise -k / --match-width: convert's keywords and a stream's
+    alpha_kw.update(continuity_keywords(args, "infer.py", alpha_kw))      # likewise --continuity
     f0_est = f0_keywords(args, "infer.py")
     if isinstance(f0_est, PitchPath):      # likewise -f0-est viterbi; every other name stays out of the calls, as it always has
         alpha_kw["f0_estimation"] = f0_est

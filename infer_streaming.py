@@ -71,7 +71,7 @@ from infer import load_generator, load_target
 from tinyvc_amd.engine import limiter_drive, limiter_geometry, loudness_geometry, loudness_levels, sola_geometry, stream_denoise_geometry, stream_gate_geometry, stream_resample_geometry
 from tinyvc_amd.module.infer import BatchedStreamInfer, StreamDenoise, StreamDoor, StreamGate, StreamLimiter, StreamLoudness
 from tinyvc_amd.module.infer.stream import DOOR_CEILING_DB, check_gate_lookahead, check_window, denoise_constants
-from tinyvc_amd.module.tinyvc.feature_retrieval import (PitchTrack, add_alpha_argument, add_match_weight_argument, match_weight_keywords, add_blend_argument, add_f0_arguments, alpha_keywords, f0_keywords,
+from tinyvc_amd.module.tinyvc.feature_retrieval import (PitchTrack, add_alpha_argument, add_match_weight_argument, match_weight_keywords, add_continuity_argument, continuity_keywords, add_blend_argument, add_f0_arguments, alpha_keywords, f0_keywords,
                                                         add_f0_carry_argument, add_tune_arguments, f0_carry_keywords, tune_keywords,
                                                         pitch_register, semitones_between)
 
@@ -105,6 +105,7 @@ def build_parser():
     add_blend_argument(p)      # --blend PATH=W [PATH=W ...] -> args.blend = (paths, weights)
     add_alpha_argument(p)      # --alpha A: keep that share of every stream's own content features in the match (stream.alpha, live on the device); --protect P (stream.protect)
     add_match_weight_argument(p)      # -k K --match-width W: the weighted match (stream.k / stream.match_width, live on the device)
+    add_continuity_argument(p)      # --continuity C: the match along a path (stream.continuity, live on the device); every window a path of its own
     p.add_argument("-c", "--chunk", default=1920, type=int)
     p.add_argument("-e", "--extra", default=3840, type=int)
     p.add_argument("-d", "--device", default="cuda")
@@ -389,6 +390,7 @@ def main(argv=None):
               f"the two filters add {door.latency_seconds * 1e3:.2f} ms of latency")
     alpha_kw = alpha_keywords(args, "infer_streaming.py")      # {} without --alpha / --protect: the stream is then built as it has always been
     alpha_kw.update(match_weight_keywords(args, "infer_streaming.py"))      # likewise -k / --match-width
+    alpha_kw.update(continuity_keywords(args, "infer_streaming.py", alpha_kw))      # likewise --continuity
     gate = None
     if gate_kw is not None:
         gate = StreamGate(S, door.block_size, device=device, **gate_kw)

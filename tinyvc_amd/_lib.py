@@ -45,6 +45,7 @@ TABLE = dict(prepared=PTRS, N=I64S)           # host tables, one entry per row
 BLEND = dict(TABLE, M=INT, weights=PTR)       # ... M per row, and the device weights (NULL with M = 1: the table call)
 ALPHA, PROTECT, PITCH_PATH, CARRY, TARGET = dict(alpha=PTR), dict(protect=PTR), dict(path=PATH), dict(carry_frame=INT, carry=PTR), dict(target_f0=PTR)
 WEIGHTED = dict(neighbours=PTR, width=PTR)      # the weighted match: k (int32) and the similarity width (fp32) per row, on the device
+JOINED = dict(WEIGHTED, join=PTR)               # ... and the continuity weight (fp32) per row of the match along a path, on the device
 SNAP = dict(snap=SNAP_SETTINGS, notes=PTR, strength=PTR)      # the pitch correction: host settings, the table and the strengths on the device
 SNAP_STATE = dict(snap_carry_frame=INT, snap_note=PTR, snap_ratio=PTR)
 TRACK = dict(start=INT, n=INT, W=INT, min_voiced=INT, slew=F32, ring=PTR, count=PTR, auto_shift=PTR)
@@ -145,6 +146,14 @@ PROTOTYPES = {
     "tvc_weighted_convert_ragged_f32": _convert(RAGGED, BLEND, ALPHA, PROTECT, WEIGHTED, PITCH_PATH, SNAP, TARGET, SHIFTS_OUT),
     "tvc_knn_match_weighted_f32": _fn(INT, CALL, dict(src=PTR, f0=PTR), BLEND, ALPHA, PROTECT, WEIGHTED,
                                       dict(out=PTR, idx_out=PTR, sims_out=PTR, B=INT, T=INT, **WS)),
+    # the joined entries: the weighted entries with the continuity weight behind width (NULL: the sibling), the path's outputs behind sims_out
+    "tvc_workspace_bytes_joined": _query(Q_EQUAL, **_BLEND_Q),
+    "tvc_workspace_bytes_ragged_joined": _query(Q_RAGGED, **_BLEND_Q),
+    "tvc_workspace_bytes_match_joined": _query(Q_EQUAL, **_BLEND_Q),
+    "tvc_joined_convert_f32": _convert(EQUAL, BLEND, ALPHA, PROTECT, JOINED, PITCH_PATH, CARRY, SNAP, SNAP_STATE, TARGET, TRACK, SHIFTS_OUT),
+    "tvc_joined_convert_ragged_f32": _convert(RAGGED, BLEND, ALPHA, PROTECT, JOINED, PITCH_PATH, SNAP, TARGET, SHIFTS_OUT),
+    "tvc_knn_match_joined_f32": _fn(INT, CALL, dict(src=PTR, f0=PTR), BLEND, ALPHA, PROTECT, JOINED,
+                                    dict(out=PTR, idx_out=PTR, sims_out=PTR, anchor_out=PTR, affinity_out=PTR, B=INT, T=INT, **WS)),
     "tvc_knn_match_f32": _fn(INT, CALL, dict(src=PTR, prepared=PTR, N=I64), MATCH),
     "tvc_knn_match_multi_f32": _fn(INT, CALL, dict(src=PTR), TABLE, MATCH),
     "tvc_knn_match_blend_f32": _fn(INT, CALL, dict(src=PTR), BLEND, MATCH),

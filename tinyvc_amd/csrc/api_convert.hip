@@ -112,8 +112,12 @@ int tvc::convert_impl(tvc_ctx* ctx, hipStream_t s, Ws& ws, const ConvertCall& c)
         // combination of the same index rows, so every content bound below stays what it is without it.
         const KnnWeight weight{c.neighbours, c.width, nullptr};
         const KnnWeight* wt = c.neighbours || c.width ? &weight : nullptr;
-        if (ix.M > 0) TVC_CHECK(run_knn_blend(ctx, s, ws, ssl, segs.data(), (int)segs.size(), ix.M, ix.weights, matched, nullptr, B, T, c.alpha, share, wt));
-        else TVC_CHECK(run_knn_segs(ctx, s, ws, ssl, segs.data(), (int)segs.size(), matched, nullptr, B, T, c.alpha, share, wt));
+        // a joined call (c.join): the weights form around the neighbour a path over each utterance chose - two launches and workspace of their
+        // own in front of the gather (both walks), the same convex combination behind it
+        const KnnJoin join{c.join, nullptr, nullptr};
+        const KnnJoin* jn = c.join ? &join : nullptr;
+        if (ix.M > 0) TVC_CHECK(run_knn_blend(ctx, s, ws, ssl, segs.data(), (int)segs.size(), ix.M, ix.weights, matched, nullptr, B, T, c.alpha, share, wt, jn));
+        else TVC_CHECK(run_knn_segs(ctx, s, ws, ssl, segs.data(), (int)segs.size(), matched, nullptr, B, T, c.alpha, share, wt, jn));
     }
     ws.release(m);
     const float* idx_bound = ws.dry ? nullptr : (ix.per_row ? rowmax : blob_amax(ix.blob));
@@ -191,7 +195,7 @@ struct ConvertQuery {
     const int64_t* lens = nullptr;
     bool ragged = false;
     ConvertIndex index;                        // N, or Ns and M: the blobs and weights are not looked at
-    bool auto_pitch = false, alpha = false, protect = false, path = false;
+    bool auto_pitch = false, alpha = false, protect = false, path = false, join = false;
 };
 // The tvc_workspace_bytes* query that goes with each entry: the same description with stand-in buffers, the measuring walk alone.  A
 // per-row index (ix.Ns; ix.blobs is not looked at) is planned with every row a segment of its own (distinct stand-in blobs) and a shift
@@ -220,6 +224,7 @@ static int convert_query(tvc_ctx* ctx, const ConvertQuery& q, size_t* out_bytes,
     c.target_f0 = q.auto_pitch ? kDryPtr : nullptr;
     c.alpha = q.alpha ? kDryPtr : nullptr;
     c.protect = q.protect ? kDryPtr : nullptr;
+    c.join = q.join ? kDryPtr : nullptr;
     const tvc_pitch_path any_path = TVC_PITCH_PATH_DEFAULT;      // the settings take no part in the sizes
     c.path = q.path ? &any_path : nullptr;
     if (!q.ragged) return measure(1, out_bytes, [&](Ws& ws) { return convert_impl(ctx, nullptr, ws, c); });
@@ -599,6 +604,44 @@ int tvc_weighted_convert_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav
     return convert_checked(ctx, stream, c, &g, nullptr, true, wsp, ws_bytes, "tvc_weighted_convert_ragged_f32");
 }
 
+// ---- match along a path: the weighted entries with a continuity weight per row ------------------------------------------------------------------
+// `join` (device, one fp32 per row) behind width; join == NULL is the weighted call, launch for launch.  The path takes workspace of its own:
+// tvc_workspace_bytes_joined / _ragged_joined (the path queries with it).
+int tvc_workspace_bytes_joined(tvc_ctx* ctx, int B, int64_t L, const int64_t* N, int M, size_t* out_bytes) {
+    ConvertQuery q; q.B = B; q.L = L; q.index = ConvertIndex::blend(nullptr, N, M, nullptr); q.alpha = q.protect = q.path = q.join = true;
+    return ladder_query(ctx, q, true, out_bytes, "tvc_workspace_bytes_joined");
+}
+int tvc_workspace_bytes_ragged_joined(tvc_ctx* ctx, int B, int64_t Lmax, const int64_t* lens, const int64_t* N, int M, size_t* out_bytes) {
+    ConvertQuery q; q.B = B; q.L = Lmax; q.lens = lens; q.ragged = true; q.index = ConvertIndex::blend(nullptr, N, M, nullptr); q.alpha = q.protect = q.path = q.join = true;
+    return ladder_query(ctx, q, true, out_bytes, "tvc_workspace_bytes_ragged_joined");
+}
+int tvc_joined_convert_f32(tvc_ctx* ctx, void* stream, const float* wav, const float* const* prepared, const int64_t* N, int M, const float* weights,
+                           const float* alpha, const float* protect, const int32_t* neighbours, const float* width, const float* join,
+                           const tvc_pitch_path* path, int carry_frame, float* carry, const tvc_pitch_snap* snap, const float* notes, const float* strength,
+                           int snap_carry_frame, int32_t* snap_note, float* snap_ratio, const float* target_f0, int start, int n, int W, int min_voiced,
+                           float slew, float* ring, int64_t* count, float* auto_shift, float pitch_shift, const float* pitch_shifts, float* shift_out,
+                           const float* noise_angle, uint64_t seed, float* wave, int B, int64_t L, void* wsp, size_t ws_bytes) {
+    ConvertCall c; c.wav = wav; c.wave = wave; c.B = B; c.L = L; c.shift = pitch_shift; c.shifts = pitch_shifts; c.angle = noise_angle; c.seed = seed;
+    c.alpha = alpha; c.protect = protect; c.path = path; c.carry_frame = carry_frame; c.carry = carry; c.target_f0 = target_f0; c.shift_out = target_f0 ? shift_out : nullptr;
+    c.snap = snap; c.notes = notes; c.strength = strength; c.snap_carry_frame = snap_carry_frame; c.snap_note = snap_note; c.snap_ratio = snap_ratio;
+    c.neighbours = neighbours; c.width = width; c.join = join;
+    IndexAsGiven g; g.prepared = prepared; g.N = N; g.M = M; g.weights = weights;
+    PitchTrackState t; t.start = start; t.n = n; t.W = W; t.min_voiced = min_voiced; t.slew = slew; t.ring = ring; t.count = count; t.autos = auto_shift;
+    return convert_checked(ctx, stream, c, &g, ring ? &t : nullptr, false, wsp, ws_bytes, "tvc_joined_convert_f32");
+}
+int tvc_joined_convert_ragged_f32(tvc_ctx* ctx, void* stream, const float* wav, int64_t Lmax, const int64_t* lens, const float* const* prepared,
+                                  const int64_t* N, int M, const float* weights, const float* alpha, const float* protect, const int32_t* neighbours,
+                                  const float* width, const float* join, const tvc_pitch_path* path, const tvc_pitch_snap* snap, const float* notes,
+                                  const float* strength, const float* target_f0, float pitch_shift, const float* pitch_shifts, float* shift_out,
+                                  const float* noise_angle, uint64_t seed, float* wave, int B, void* wsp, size_t ws_bytes) {
+    ConvertCall c; c.wav = wav; c.wave = wave; c.B = B; c.L = Lmax; c.lens = lens; c.shift = pitch_shift; c.shifts = pitch_shifts; c.angle = noise_angle; c.seed = seed;
+    c.alpha = alpha; c.protect = protect; c.path = path; c.target_f0 = target_f0; c.shift_out = target_f0 ? shift_out : nullptr;
+    c.snap = snap; c.notes = notes; c.strength = strength;
+    c.neighbours = neighbours; c.width = width; c.join = join;
+    IndexAsGiven g; g.prepared = prepared; g.N = N; g.M = M; g.weights = weights;
+    return convert_checked(ctx, stream, c, &g, nullptr, true, wsp, ws_bytes, "tvc_joined_convert_ragged_f32");
+}
+
 // ---- the matches against one index per row or a blend: the kNN stage of the entries above on the caller's own features ---------------------
 // One match by field name.  alpha (nullable): the alpha form of the same call; protect (nullable, with f0): its protect form.
 struct MatchCall {
@@ -607,6 +650,7 @@ struct MatchCall {
     IndexAsGiven index;
     const float *alpha = nullptr, *protect = nullptr;
     KnnWeight weight;                          // the weighted form: neighbours, width, sims_out - all nullable, all null: not weighted
+    KnnJoin join;                              // the joined form: join (null: not joined), anchor_out, affinity_out
     float* out = nullptr;
     int64_t* idx_out = nullptr;      // nullable
     int B = 0, T = 0;
@@ -624,6 +668,15 @@ static int match_share(tvc_ctx* ctx, hipStream_t s, Ws& ws, const MatchCall& c, 
     if (c.protect && !ws.dry) TVC_CHECK(run_frame_share(ctx, s, c.f0, c.alpha, c.protect, *share, c.B, c.T));
     return 0;
 }
+// one walk of a match: the share, then the search and its gather
+static int match_walk(tvc_ctx* ctx, hipStream_t s, Ws& ws, const MatchCall& c, const std::vector<KnnSegIn>& in, bool blend) {
+    const KnnWeight* wt = c.weight.neighbours || c.weight.width || c.weight.sims_out ? &c.weight : nullptr;
+    const KnnJoin* jn = c.join.join ? &c.join : nullptr;
+    float* share;
+    TVC_CHECK(match_share(ctx, s, ws, c, &share));
+    if (blend) return run_knn_blend(ctx, s, ws, c.src, in.data(), (int)in.size(), c.index.M, c.index.weights, c.out, c.idx_out, c.B, c.T, c.alpha, share, wt, jn);
+    return run_knn_segs(ctx, s, ws, c.src, in.data(), c.B, c.out, c.idx_out, c.B, c.T, c.alpha, share, wt, jn);
+}
 // every match entry's checks and its two walks, under the entry's own name `what`
 static int match_checked(tvc_ctx* ctx, void* stream, const MatchCall& c, void* wsp, size_t ws_bytes, const char* what) {
     if (!ctx) return TVC_ERR_ARG;
@@ -632,6 +685,8 @@ static int match_checked(tvc_ctx* ctx, void* stream, const MatchCall& c, void* w
     if ((c.alpha || c.protect) && c.src && c.src == c.out)
         return fail(ctx, TVC_ERR_ARG, "%s: out must be another buffer than src (the source's share is read while out is written)", what);
     if (c.protect && !c.f0) return fail(ctx, TVC_ERR_ARG, "%s: protect needs f0 (device, [B][T]: the voicing comes from it)", what);
+    if (!c.join.join && (c.join.anchor_out || c.join.affinity_out))
+        return fail(ctx, TVC_ERR_ARG, "%s: anchor_out and affinity_out are the path's: they need join (device, one fp32 per row)", what);
     const bool blend = ix.weights || ix.weights_required;
     if (!blend && ix.M != 1) return fail(ctx, TVC_ERR_ARG, "%s: weights = NULL is one index per row: M must be 1, got %d", what, ix.M);
     if (!c.src || !c.out || B <= 0 || T <= 0 || (!blend && (int64_t)B * T > 0x7fffffff)) return fail(ctx, TVC_ERR_ARG, "%s: bad argument", what);
@@ -643,13 +698,7 @@ static int match_checked(tvc_ctx* ctx, void* stream, const MatchCall& c, void* w
     TVC_CHECK(rows_check(ctx, s, B * ix.M, ix.prepared, ix.N, what));
     TVC_HIP(ctx, hipSetDevice(ctx->device));
     const std::vector<KnnSegIn> in = term_row_segments(ix, B, T);
-    const KnnWeight* wt = c.weight.neighbours || c.weight.width || c.weight.sims_out ? &c.weight : nullptr;
-    return run_walks(ctx, what, wsp, ws_bytes, 1, [&](Ws& ws) {
-        float* share;
-        TVC_CHECK(match_share(ctx, s, ws, c, &share));
-        if (blend) return run_knn_blend(ctx, s, ws, c.src, in.data(), (int)in.size(), ix.M, ix.weights, c.out, c.idx_out, B, T, c.alpha, share, wt);
-        return run_knn_segs(ctx, s, ws, c.src, in.data(), B, c.out, c.idx_out, B, T, c.alpha, share, wt);
-    });
+    return run_walks(ctx, what, wsp, ws_bytes, 1, [&](Ws& ws) { return match_walk(ctx, s, ws, c, in, blend); });
 }
 int tvc_knn_match_multi_f32(tvc_ctx* ctx, void* stream, const float* src, const float* const* prepared, const int64_t* N, float* out,
                             int64_t* idx_out, int B, int T, void* wsp, size_t ws_bytes) {
@@ -683,6 +732,42 @@ int tvc_knn_match_weighted_f32(tvc_ctx* ctx, void* stream, const float* src, con
     c.weight.neighbours = neighbours; c.weight.width = width; c.weight.sims_out = sims_out;
     c.index.prepared = prepared; c.index.N = N; c.index.M = M; c.index.weights = weights;
     return match_checked(ctx, stream, c, wsp, ws_bytes, "tvc_knn_match_weighted_f32");
+}
+// the joined stage call: the weighted match with `join` behind width, and the path's own outputs behind sims_out - anchor_out (nullable,
+// int32 [M][B][T]) and affinity_out (nullable, fp32 [M][B][T][4][4], frame 0's sixteen are zeros).  join == NULL is the weighted call.
+// Workspace: tvc_workspace_bytes_match_joined, the largest of the forms the entry takes (B rows of L / 480 columns).
+int tvc_workspace_bytes_match_joined(tvc_ctx* ctx, int B, int64_t L, const int64_t* N, int M, size_t* out_bytes) {
+    if (!ctx) return TVC_ERR_ARG;
+    const char* what = "tvc_workspace_bytes_match_joined";
+    TVC_CHECK(blend_check(ctx, B, M, kDryPtr, what));
+    if (!out_bytes || !N || L <= 0 || L % kHop != 0 || (int64_t)B * M * (L / kHop) > 0x7fffffff)
+        return fail(ctx, TVC_ERR_ARG, "%s: need B>0, L%%480==0, N[B * M], at most 2^31 - 1 query columns", what);
+    for (int b = 0; b < B * M; ++b)
+        if (N[b] < 4) return fail(ctx, TVC_ERR_ARG, "%s: N[%d] < 4", what, b);
+    std::vector<const float*> blobs((size_t)B * M);
+    for (size_t b = 0; b < blobs.size(); ++b) blobs[b] = kDryPtr + 64 * b;      // every (row, term) a segment of its own: the most a call can need
+    MatchCall c; c.src = c.f0 = c.alpha = c.protect = kDryPtr; c.out = kDryPtr; c.B = B; c.T = (int)(L / kHop);
+    c.join.join = kDryPtr;
+    c.index.prepared = blobs.data(); c.index.N = N; c.index.M = M; c.index.weights = kDryPtr;
+    const std::vector<KnnSegIn> in = term_row_segments(c.index, B, c.T);
+    size_t most = 0;
+    for (int blend = M == 1 ? 0 : 1; blend < 2; ++blend) {
+        size_t bytes = 0;
+        TVC_CHECK(measure(1, &bytes, [&](Ws& ws) { return match_walk(ctx, nullptr, ws, c, in, blend != 0); }));
+        if (bytes > most) most = bytes;
+    }
+    *out_bytes = most;
+    return TVC_OK;
+}
+int tvc_knn_match_joined_f32(tvc_ctx* ctx, void* stream, const float* src, const float* f0, const float* const* prepared, const int64_t* N, int M,
+                             const float* weights, const float* alpha, const float* protect, const int32_t* neighbours, const float* width,
+                             const float* join, float* out, int64_t* idx_out, float* sims_out, int32_t* anchor_out, float* affinity_out, int B, int T,
+                             void* wsp, size_t ws_bytes) {
+    MatchCall c; c.src = src; c.f0 = f0; c.alpha = alpha; c.protect = protect; c.out = out; c.idx_out = idx_out; c.B = B; c.T = T;
+    c.weight.neighbours = neighbours; c.weight.width = width; c.weight.sims_out = sims_out;
+    c.join.join = join; c.join.anchor_out = anchor_out; c.join.affinity_out = affinity_out;
+    c.index.prepared = prepared; c.index.N = N; c.index.M = M; c.index.weights = weights;
+    return match_checked(ctx, stream, c, wsp, ws_bytes, "tvc_knn_match_joined_f32");
 }
 
 // ---- the pitch stage calls: the register match, the tracker, the path and the per-frame share on the caller's own f0 / logits -------------

@@ -2,7 +2,8 @@
 // row, a weighted blend; each also in its alpha form, which keeps a share of the source), the index-sharded route's three steps (merge, slot
 // gather, finish) and the |max| bounds of `matched`.
 // Every route averages the four rows with mean4 and stores through store_tile_along_t: equal lists give equal bits on all of them.  The
-// weighted forms of the two merge + gather kernels (WeightIn) put weighted_mean4 - the k nearest, weighted by their similarities - in its place.
+// weighted forms of the two merge + gather kernels (WeightIn) put weighted_mean4 - the k nearest, weighted by their similarities - in its place;
+// their joined forms (JoinIn) form those weights around the neighbour a path over the utterance chose (the merge + affinity and path kernels).
 #include <type_traits>
 
 #include "knn_blob.h"
@@ -115,10 +116,26 @@ struct Weighted {
     WeightIn w;
     Mix mix;
 };
-template <class... A> struct Forms { static constexpr bool weighted = false, mixed = sizeof...(A) > 0; };
-template <class Mix> struct Forms<Weighted<Mix>> { static constexpr bool weighted = true, mixed = !std::is_same<Mix, NoMix>::value; };
+// The joined forms (tvc_*joined*_f32; the definition is in include/tinyvc_hip.h) are the weighted forms with the weights formed around an ANCHOR
+// per column instead of around neighbour 0: the path kernel below chose it, over the utterance as a whole.  The merge + affinity kernel left
+// the merged lists in workspace, so the merge threads read them there instead of merging again.
+struct JoinIn {
+    const int* sel;          // [M * ncols][4] the merged rows (never a sentinel)
+    const float* sims;       // [M * ncols][4] their similarities, as sims_out
+    const int* anchor;       // [M * ncols] the path's neighbour, 0 .. k - 1
+};
+template <class Mix>
+struct Joined {
+    WeightIn w;
+    JoinIn j;
+    Mix mix;
+};
+template <class... A> struct Forms { static constexpr bool weighted = false, joined = false, mixed = sizeof...(A) > 0; };
+template <class Mix> struct Forms<Weighted<Mix>> { static constexpr bool weighted = true, joined = false, mixed = !std::is_same<Mix, NoMix>::value; };
+template <class Mix> struct Forms<Joined<Mix>> { static constexpr bool weighted = true, joined = true, mixed = !std::is_same<Mix, NoMix>::value; };
 template <class AI> __device__ __forceinline__ const AI& mix_of(const AI& al) { return al; }
 template <class Mix> __device__ __forceinline__ const Mix& mix_of(const Weighted<Mix>& x) { return x.mix; }
+template <class Mix> __device__ __forceinline__ const Mix& mix_of(const Joined<Mix>& x) { return x.mix; }
 // w[0 .. 3] = the four weights of a column and w[4] = their sum W from its merged similarities s[0] >= ... >= s[3]: w_0 = 1, w_e = 1 - (s_0 - s_e) /
 // width clamped to [0, 1] for e < k - and 1 wherever that quotient is not a positive number (NaN, a tie under width 0, a negative width) -, 0 from
 // k on.  Every operation is rounded on its own; W >= 1 whatever the two arrays hold.
@@ -140,6 +157,42 @@ __device__ __forceinline__ float weighted_mean4(float r0, float r1, float r2, fl
     acc = w[1] != 0.f ? __fadd_rn(acc, __fmul_rn(w[1], r1)) : acc;
     acc = w[2] != 0.f ? __fadd_rn(acc, __fmul_rn(w[2], r2)) : acc;
     acc = w[3] != 0.f ? __fadd_rn(acc, __fmul_rn(w[3], r3)) : acc;
+    return __fdiv_rn(acc, w[4]);
+}
+// the joined forms' merge: column `col`'s merged rows and similarities as the merge + affinity kernel stored them -> sel[4], s[4]; returns the
+// path's anchor.  `& 3`: whatever the workspace held, the anchor indexes the four.  A column that is not live: row 0, zeros, anchor 0.
+__device__ __forceinline__ int joined_top4(const JoinIn& ji, long col, bool live, int* sel, float* s) {
+    for (int e = 0; e < 4; ++e) {
+        sel[e] = live ? ji.sel[col * 4 + e] : 0;
+        s[e] = live ? ji.sims[col * 4 + e] : 0.f;
+    }
+    return live ? ji.anchor[col] & 3 : 0;
+}
+// match_weights around the anchor p: w_p = 1, w_e = 1 - |s_p - s_e| / width clamped to [0, 1] for e < k, e != p - and 1 wherever the quotient is
+// not a positive number -, 0 from k on; w[4] = W >= 1.  p = 0 is match_weights bit for bit (s_0 - s_e >= 0 in a sorted list).
+__device__ __forceinline__ void join_weights(const WeightIn& wi, int row, const float* s, int p, float* w) {
+    int k = wi.neighbours ? wi.neighbours[row] : 4;
+    k = k < 1 ? 1 : (k > 4 ? 4 : k);
+    const float width = wi.width ? wi.width[row] : INFINITY;
+    const float sp = p == 0 ? s[0] : (p == 1 ? s[1] : (p == 2 ? s[2] : s[3]));
+    for (int e = 0; e < 4; ++e) {
+        const float t = __fdiv_rn(fabsf(__fsub_rn(sp, s[e])), width);
+        w[e] = e == p ? 1.f : (e < k ? (t > 0.f ? fmaxf(0.f, __fsub_rn(1.f, t)) : 1.f) : 0.f);
+    }
+    w[4] = __fadd_rn(__fadd_rn(__fadd_rn(w[0], w[1]), w[2]), w[3]);
+}
+// the mean around an anchor: the terms w_e * r_e with w_e != 0 in ascending e, the first of them starting the sum (neighbour 0 may weigh
+// nothing here), product and sum rounded separately, over W.  w[0] == 1 is weighted_mean4 bit for bit (1 * r0 == r0).
+__device__ __forceinline__ float joined_mean4(float r0, float r1, float r2, float r3, const float* w) {
+    const float r[4] = {r0, r1, r2, r3};
+    float acc = 0.f;
+    bool started = false;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float term = __fmul_rn(w[e], r[e]);
+        acc = w[e] != 0.f ? (started ? __fadd_rn(acc, term) : term) : acc;
+        started = started || w[e] != 0.f;
+    }
     return __fdiv_rn(acc, w[4]);
 }
 // store_tile_along_t with the source's share a of this thread's column mixed in (AI: AlphaIn or ShareIn)
@@ -172,7 +225,7 @@ static __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const floa
                                                                       float* __restrict__ out, int64_t* __restrict__ idx_out,
                                                                       const float* __restrict__ rv, const int* __restrict__ ri,
                                                                       const int* __restrict__ flags, const A... al) {
-    constexpr bool ALPHA = Forms<A...>::mixed, WEIGHTED = Forms<A...>::weighted;
+    constexpr bool ALPHA = Forms<A...>::mixed, WEIGHTED = Forms<A...>::weighted, JOINED = Forms<A...>::joined;
     __shared__ int sel[32][4];
     __shared__ float tile[32][193];
     __shared__ const float* sblob[32];
@@ -190,7 +243,12 @@ static __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const floa
         const int nc = n < ncols ? n : ncols - 1;      // (a column past the end gathers row 0 of the last column's blob: never stored)
         const int si = MULTI ? col2seg[nc] : 0;
         const KnnSeg g = seg_get(segs, si);
-        if constexpr (WEIGHTED) {
+        if constexpr (JOINED) {      // the lists were merged (and idx_out / sims_out written) by the merge + affinity kernel; the weights form around the path's anchor
+            const WeightIn& wi = (al.w, ...);
+            float sims[4];
+            const int p = joined_top4((al.j, ...), n, n < ncols, sel[tid], sims);
+            join_weights(wi, wi.col2b ? wi.rowmap[wi.col2b[nc]] : nc / T, sims, p, sw[tid]);
+        } else if constexpr (WEIGHTED) {
             const WeightIn& wi = (al.w, ...);
             float sims[4];
             merged_top4(g, si, flags, cand_v, cand_i, rv, ri, ncols, n, n < ncols, idx_out, sel[tid], sims, wi.sims_out);
@@ -217,7 +275,8 @@ static __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const floa
             for (int qq = 0; qq < 4; ++qq)
 #pragma unroll
                 for (int u = 0; u < 3; ++u) {
-                    if constexpr (WEIGHTED) tile[q0 + 4 * qq][lane + 64 * u] = weighted_mean4(r[qq][u][0], r[qq][u][1], r[qq][u][2], r[qq][u][3], sw[q0 + 4 * qq]);
+                    if constexpr (JOINED) tile[q0 + 4 * qq][lane + 64 * u] = joined_mean4(r[qq][u][0], r[qq][u][1], r[qq][u][2], r[qq][u][3], sw[q0 + 4 * qq]);
+                    else if constexpr (WEIGHTED) tile[q0 + 4 * qq][lane + 64 * u] = weighted_mean4(r[qq][u][0], r[qq][u][1], r[qq][u][2], r[qq][u][3], sw[q0 + 4 * qq]);
                     else tile[q0 + 4 * qq][lane + 64 * u] = mean4(r[qq][u][0], r[qq][u][1], r[qq][u][2], r[qq][u][3]);
                 }
         }
@@ -247,7 +306,7 @@ static __global__ __launch_bounds__(256) void knn_merge_blend_gather_kernel(cons
                                                                             const int* __restrict__ rowmap, float* __restrict__ out,
                                                                             int64_t* __restrict__ idx_out, const float* __restrict__ rv,
                                                                             const int* __restrict__ ri, const int* __restrict__ flags, const A... al) {
-    constexpr bool ALPHA = Forms<A...>::mixed, WEIGHTED = Forms<A...>::weighted;
+    constexpr bool ALPHA = Forms<A...>::mixed, WEIGHTED = Forms<A...>::weighted, JOINED = Forms<A...>::joined;
     __shared__ int sel[BLEND_MAX][32][4];
     __shared__ float tile[32][193];
     __shared__ const float* sblob[BLEND_MAX][32];
@@ -271,14 +330,17 @@ static __global__ __launch_bounds__(256) void knn_merge_blend_gather_kernel(cons
         const int si = col2seg ? col2seg[vc] : 0;
         const KnnSeg g = seg_get(segs, si);
         [[maybe_unused]] float sims[4];
-        if constexpr (WEIGHTED) merged_top4(g, si, flags, cand_v, cand_i, rv, ri, vcols, vc, live, idx_out, sel[m][q], sims, (al.w, ...).sims_out);
+        [[maybe_unused]] int anchor = 0;
+        if constexpr (JOINED) anchor = joined_top4((al.j, ...), vc, live, sel[m][q], sims);      // this term's own lists and path
+        else if constexpr (WEIGHTED) merged_top4(g, si, flags, cand_v, cand_i, rv, ri, vcols, vc, live, idx_out, sel[m][q], sims, (al.w, ...).sims_out);
         else merged_top4(g, si, flags, cand_v, cand_i, rv, ri, vcols, vc, live, idx_out, sel[m][q]);
         sblob[m][q] = g.blob;
         skind[m][q] = blob_kind(g.blob);
         sN[m][q] = g.N;
         const int row = col2b ? rowmap[col2b[nc]] : nc / T;
         sw[m][q] = weights[(long)row * M + m];
-        if constexpr (WEIGHTED) match_weights((al.w, ...), row, sims, snw[m][q]);      // every term's mu_m: the row's k and width, the term's own similarities
+        if constexpr (JOINED) join_weights((al.w, ...), row, sims, anchor, snw[m][q]);
+        else if constexpr (WEIGHTED) match_weights((al.w, ...), row, sims, snw[m][q]);      // every term's mu_m: the row's k and width, the term's own similarities
     }
     __syncthreads();
     const int lane = tid & 63, wave = tid >> 6;
@@ -295,7 +357,8 @@ static __global__ __launch_bounds__(256) void knn_merge_blend_gather_kernel(cons
 #pragma unroll
                     for (int u = 0; u < 3; ++u) {
                         float mu;
-                        if constexpr (WEIGHTED) mu = weighted_mean4(r[qq][u][0], r[qq][u][1], r[qq][u][2], r[qq][u][3], snw[m][q0 + 4 * qq]);
+                        if constexpr (JOINED) mu = joined_mean4(r[qq][u][0], r[qq][u][1], r[qq][u][2], r[qq][u][3], snw[m][q0 + 4 * qq]);
+                        else if constexpr (WEIGHTED) mu = weighted_mean4(r[qq][u][0], r[qq][u][1], r[qq][u][2], r[qq][u][3], snw[m][q0 + 4 * qq]);
                         else mu = mean4(r[qq][u][0], r[qq][u][1], r[qq][u][2], r[qq][u][3]);
                         const float term = __fmul_rn(w, mu);
                         acc[qq][u] = m == 0 ? term : __fadd_rn(acc[qq][u], term);
@@ -542,6 +605,267 @@ int run_knn_finish(tvc_ctx* ctx, hipStream_t s, const float* slots, float* out, 
     return launch_check(ctx, "knn_finish");
 }
 
+// ---- match along a path (tvc_*joined*_f32): merge + affinity, the path, then the joined form of the merge + gather above -------------------
+// 1. knn_join_affinity_kernel: one workgroup = 32 consecutive VIRTUAL columns (a blend's terms are columns m * ncols + n of the one search)
+//    and the column in front of them.  Threads 0 .. 32 merge their column's lists (merged_top4: idx_out and sims_out are written here) and
+//    leave rows and similarities in workspace for the other two kernels.  Then every wave walks 8 columns in order, the rows of the column
+//    before in registers and the next column's 48 loads in flight: lanes along the 768 channels as gather4x3 has them, the 16 dots
+//      dot[d][e] = sum_k row i_{t-1}[d][k] * row i_t[e][k]
+//    each in ONE order - lane l adds its channels l, l + 64, .., l + 704 in ascending order (product and sum rounded on their own), then the 64
+//    partial sums meet in a butterfly over lane distances 32, 16, 8, 4, 2, 1 (every lane adds its partner's value to its own: fp32 addition
+//    commutes, so all lanes hold the same bits) - and a = (dot * inv[i_{t-1}[d]]) * inv[i_t[e]].  The order knows nothing of tiles, splits,
+//    the batch or k.  The first frame of an utterance gets zeros.
+// 2. knn_join_path_kernel: one wavefront per (term, utterance), four to a workgroup; the definition's recursion on wave-uniform values, a
+//    chunk of 64 frames' similarities and affinities in the lanes' registers (lane j holds frame j's twenty floats, the next chunk's loads in
+//    flight), one byte of back-pointers per frame (2 bits per state) to workspace, and the walk back in the same launch.
+// MEMORY SAFETY: a back-pointer is the d < k of a comparison chain that starts at d = 0 and the last anchor the e < k of one that starts at
+// e = 0, so every anchor lies in 0 .. k - 1 whatever the scores are; the scores themselves stay finite by the definition's saturations.
+constexpr float JOIN_BIG = 3.402823466e38f;      // FLT_MAX
+__device__ __forceinline__ float join_sat(float x) { return fminf(fmaxf(x, -JOIN_BIG), JOIN_BIG); }      // (NaN: -FLT_MAX)
+__device__ __forceinline__ float join_finite(float x) { return fabsf(x) <= JOIN_BIG ? x : 0.f; }        // NaN and +-inf count as 0
+struct JoinWs {           // workspace of one joined call, [vcols] = M * B * T entries each
+    int* sel;             // [vcols][4]
+    float* sims;          // [vcols][4]
+    float* aff;           // [vcols][16], [d][e]
+    unsigned char* bp;    // [vcols]
+    int* anchor;          // [vcols]
+};
+static __global__ __launch_bounds__(256) void knn_join_affinity_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i, const KnnSegs segs,
+                                                                       const int* __restrict__ col2seg, int vcols, int ncols, int T,
+                                                                       const int* __restrict__ col2b, const int* __restrict__ pre,
+                                                                       int64_t* __restrict__ idx_out, float* __restrict__ sims_out,
+                                                                       const float* __restrict__ rv, const int* __restrict__ ri,
+                                                                       const int* __restrict__ flags, JoinWs jw, float* __restrict__ aff_out) {
+    __shared__ int sel[33][4];
+    __shared__ const float* sblob[33];
+    __shared__ int skind[33], sN[33], sfirst[33];
+    const int tid = threadIdx.x;
+    const int n0 = blockIdx.x * 32;
+    if (tid < 33) {      // slot 0: the column in front of the tile
+        const int vc = n0 - 1 + tid;
+        const bool live = vc >= 0 && vc < vcols;
+        const int vcc = vc < 0 ? 0 : (vc < vcols ? vc : vcols - 1);
+        const int si = col2seg ? col2seg[vcc] : 0;
+        const KnnSeg g = seg_get(segs, si);
+        const bool own = tid > 0;
+        float sims[4];
+        merged_top4(g, si, flags, cand_v, cand_i, rv, ri, vcols, vc, live, own ? idx_out : nullptr, sel[tid], sims, own ? sims_out : nullptr);
+        if (own && live)
+            for (int e = 0; e < 4; ++e) {
+                jw.sel[(long)vc * 4 + e] = sel[tid][e];
+                jw.sims[(long)vc * 4 + e] = sims[e];
+            }
+        sblob[tid] = g.blob;
+        skind[tid] = blob_kind(g.blob);
+        sN[tid] = g.N;
+        const int n = vcc % ncols;      // the real column: a path never leaves its term, its row or its utterance
+        sfirst[tid] = col2b ? n == pre[col2b[n]] : n % T == 0;
+    }
+    __syncthreads();
+    const int lane = tid & 63, wave = tid >> 6;
+    float prev[4][12], cur[4][12], nxt[4][12];
+    const auto load = [&](float (&r)[4][12], int slot) {
+        const float* blob = sblob[slot];
+        const int kind = skind[slot], N = sN[slot];
+        const long Npad = blob_npad(N);
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int u = 0; u < 12; ++u) r[e][u] = blob_row_value(blob, kind, N, Npad, sel[slot][e], lane + 64 * u);
+    };
+    load(prev, wave * 8);
+    load(cur, wave * 8 + 1);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int slot = wave * 8 + 1 + j;
+        const int vc = n0 + wave * 8 + j;
+        if (j < 7) load(nxt, slot + 1);
+        if (vc < vcols) {      // wave-uniform
+            float a = 0.f;
+            if (!sfirst[slot]) {
+                float mine = 0.f;
+#pragma unroll
+                for (int d = 0; d < 4; ++d)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        float acc = __fmul_rn(prev[d][0], cur[e][0]);
+#pragma unroll
+                        for (int u = 1; u < 12; ++u) acc = __fadd_rn(acc, __fmul_rn(prev[d][u], cur[e][u]));
+#pragma unroll
+                        for (int m = 32; m; m >>= 1) acc = __fadd_rn(acc, __shfl_xor(acc, m));
+                        mine = lane == d * 4 + e ? acc : mine;
+                    }
+                if (lane < 16) {
+                    const int d = lane >> 2, e = lane & 3;
+                    const float* ip = blob_inv(sblob[slot - 1], skind[slot - 1], sN[slot - 1], blob_npad(sN[slot - 1]));
+                    const float* ic = blob_inv(sblob[slot], skind[slot], sN[slot], blob_npad(sN[slot]));
+                    a = __fmul_rn(__fmul_rn(mine, ip[sel[slot - 1][d]]), ic[sel[slot][e]]);
+                }
+            }
+            if (lane < 16) {
+                jw.aff[(long)vc * 16 + lane] = a;
+                if (aff_out) aff_out[(long)vc * 16 + lane] = a;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int u = 0; u < 12; ++u) {
+                prev[e][u] = cur[e][u];
+                cur[e][u] = nxt[e][u];
+            }
+    }
+}
+
+// the (term, utterance) paths of one launch by value: virtual columns [start, start + len), row = the caller's row (k and the continuity weight)
+constexpr int JOIN_ROWS = 256;
+struct JoinRows {
+    int start[JOIN_ROWS], len[JOIN_ROWS], row[JOIN_ROWS];
+};
+// uniform_len >= 0: path i = columns [i * uniform_len, + uniform_len), row i % rowmod - any number of paths in one launch
+static __global__ __launch_bounds__(256) void knn_join_path_kernel(JoinRows rows, int nrows, int uniform_len, int rowmod, const int* __restrict__ neighbours,
+                                                                   const float* __restrict__ join, JoinWs jw, int* __restrict__ anchor_out) {
+    const int lane = threadIdx.x & 63;
+    const int u = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (u >= nrows) return;
+    const int len = uniform_len >= 0 ? uniform_len : rows.len[u];
+    if (len <= 0) return;
+    const long start = uniform_len >= 0 ? (long)u * uniform_len : (long)rows.start[u];
+    const int row = uniform_len >= 0 ? u % rowmod : rows.row[u];
+    int k = neighbours ? neighbours[row] : 4;
+    k = k < 1 ? 1 : (k > 4 ? 4 : k);
+    float c = join[row];
+    c = c > 0.f ? fminf(c, JOIN_BIG) : 0.f;      // NaN and negatives: 0; +inf: the largest finite float
+    const float4* __restrict__ sims4 = reinterpret_cast<const float4*>(jw.sims) + start;
+    const float4* __restrict__ aff4 = reinterpret_cast<const float4*>(jw.aff) + start * 4;
+    const auto bcast = [](float v, int j) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), j)); };
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 ns = lane < len ? sims4[lane] : zero, na[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) na[d] = lane < len ? aff4[lane * 4 + d] : zero;
+    float D[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int t0 = 0; t0 < len; t0 += 64) {
+        const int m = min(64, len - t0);
+        const float4 cs = ns;
+        float4 ca[4];
+#pragma unroll
+        for (int d = 0; d < 4; ++d) ca[d] = na[d];
+        if (t0 + 64 < len) {      // the next chunk's twenty floats per frame, in flight while this one is walked
+            const int t = t0 + 64 + lane;
+            ns = t < len ? sims4[t] : zero;
+#pragma unroll
+            for (int d = 0; d < 4; ++d) na[d] = t < len ? aff4[(long)t * 4 + d] : zero;
+        }
+        int mybp = 0;
+        for (int j = 0; j < m; ++j) {
+            const float s[4] = {join_finite(bcast(cs.x, j)), join_finite(bcast(cs.y, j)), join_finite(bcast(cs.z, j)), join_finite(bcast(cs.w, j))};
+            float x[4];
+            int bpj = 0;
+            if (t0 + j == 0) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) x[e] = s[e];
+            } else {
+                float jc[4][4];      // c * a_t[d][e], saturated
+#pragma unroll
+                for (int d = 0; d < 4; ++d) {
+                    jc[d][0] = join_sat(__fmul_rn(c, join_finite(bcast(ca[d].x, j))));
+                    jc[d][1] = join_sat(__fmul_rn(c, join_finite(bcast(ca[d].y, j))));
+                    jc[d][2] = join_sat(__fmul_rn(c, join_finite(bcast(ca[d].z, j))));
+                    jc[d][3] = join_sat(__fmul_rn(c, join_finite(bcast(ca[d].w, j))));
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float best = __fadd_rn(D[0], jc[0][e]);
+                    int bd = 0;
+#pragma unroll
+                    for (int d = 1; d < 4; ++d) {
+                        const float cand = __fadd_rn(D[d], jc[d][e]);
+                        const bool take = d < k && cand > best;      // ties keep the lowest d
+                        best = take ? cand : best;
+                        bd = take ? d : bd;
+                    }
+                    x[e] = join_sat(__fadd_rn(s[e], best));
+                    bpj |= bd << (2 * e);
+                }
+            }
+            float mx = x[0];
+#pragma unroll
+            for (int e = 1; e < 4; ++e) mx = e < k ? fmaxf(mx, x[e]) : mx;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) D[e] = join_sat(__fsub_rn(x[e], mx));
+            mybp = lane == j ? bpj : mybp;
+        }
+        if (lane < m) jw.bp[start + t0 + lane] = (unsigned char)mybp;
+    }
+    int p = 0;
+    {
+        float best = D[0];
+#pragma unroll
+        for (int e = 1; e < 4; ++e) {
+            const bool take = e < k && D[e] > best;
+            best = take ? D[e] : best;
+            p = take ? e : p;
+        }
+    }
+    __threadfence();      // the back-pointers the other lanes stored are read below
+    for (int t0 = (len - 1) / 64 * 64; t0 >= 0; t0 -= 64) {
+        const int m = min(64, len - t0);
+        const int mybp = lane < m ? (int)jw.bp[start + t0 + lane] : 0;
+        int mine = 0;
+        for (int j = m - 1; j >= 0; --j) {
+            mine = lane == j ? p : mine;
+            p = (__builtin_amdgcn_readlane(mybp, j) >> (2 * p)) & 3;      // frame t0 + j's back-pointer of state p: the anchor of the frame before
+        }
+        if (lane < m) {
+            jw.anchor[start + t0 + lane] = mine;
+            if (anchor_out) anchor_out[start + t0 + lane] = mine;
+        }
+    }
+}
+
+// what a joined call takes from the workspace, in both walks: the merged lists, the affinities, the back-pointers and the anchors
+static JoinWs join_workspace(Ws& ws, size_t vcols) {
+    JoinWs jw;
+    jw.sel = ws.get<int>(vcols * 4);
+    jw.sims = ws.get<float>(vcols * 4);
+    jw.aff = ws.get<float>(vcols * 16);
+    jw.bp = ws.get<unsigned char>(vcols);
+    jw.anchor = ws.get<int>(vcols);
+    return jw;
+}
+// the two launches in front of the joined gather: M terms of `ncols` real columns each (B rows of T, or the current ragged batch's utterances)
+// (under tvc_profile_enable each of the two is a region of its own, "knn.join_affinity" and "knn.join_path": tools/match_join_probe.py)
+static int run_knn_join(tvc_ctx* ctx, hipStream_t s, const Ws& ws, const KnnLists& L, int M, int B, int T, const KnnWeight& wt, const KnnJoin& jn,
+                        const JoinWs& jw, int64_t* idx_out) {
+    const RagHost* h = ctx->rag;
+    const int ncols = B * T, vcols = M * ncols;
+    {
+        ProfScope ps(ctx, s, ws, "knn.join_affinity");
+        hipLaunchKernelGGL(knn_join_affinity_kernel, dim3((vcols + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)L.col2seg, vcols, ncols, T,
+                           h ? (const int*)h->d_col2b : (const int*)nullptr, h ? (const int*)h->d_pre : (const int*)nullptr, idx_out, wt.sims_out, L.rv, L.ri,
+                           (const int*)L.flag, jw, jn.affinity_out);
+    }
+    TVC_CHECK(launch_check(ctx, "knn_join_affinity"));
+    ProfScope ps(ctx, s, ws, "knn.join_path");
+    JoinRows r = {};
+    if (!h) {      // equal rows: one launch however many
+        hipLaunchKernelGGL(knn_join_path_kernel, dim3((M * B + 3) / 4), dim3(256), 0, s, r, M * B, T, B, wt.neighbours, jn.join, jw, jn.anchor_out);
+        return launch_check(ctx, "knn_join_path");
+    }
+    const size_t n = (size_t)M * h->B;
+    for (size_t o = 0; o < n; o += JOIN_ROWS) {
+        const int cnt = (int)(n - o < JOIN_ROWS ? n - o : JOIN_ROWS);
+        for (int i = 0; i < cnt; ++i) {
+            const int m = (int)((o + i) / h->B), ui = (int)((o + i) % h->B);
+            r.start[i] = m * ncols + h->pre[ui];
+            r.len[i] = h->tb[ui];
+            r.row[i] = h->row[ui];
+        }
+        hipLaunchKernelGGL(knn_join_path_kernel, dim3((cnt + 3) / 4), dim3(256), 0, s, r, cnt, -1, 1, wt.neighbours, jn.join, jw, jn.anchor_out);
+    }
+    return launch_check(ctx, "knn_join_path");
+}
+
 // the weighted forms' launch: the same grid and lists with Weighted<Mix> as the one more argument (Mix: the store form's AlphaIn / ShareIn / NoMix)
 static WeightIn weight_in(const tvc_ctx* ctx, const KnnWeight& wt) {
     const RagHost* h = ctx->rag;
@@ -564,13 +888,42 @@ static int launch_weighted_blend(tvc_ctx* ctx, hipStream_t s, const KnnLists& L,
     return launch_check(ctx, "knn_match_blend_weighted");
 }
 
+// the joined forms' launch: Joined<Mix> in Weighted<Mix>'s place - the lists, the indices and the similarities are in workspace already
+template <class Mix>
+static int launch_joined(tvc_ctx* ctx, hipStream_t s, const KnnCall& c, const KnnLists& L, int T, float* out, const KnnWeight& wt, const JoinWs& jw, const Mix& mix) {
+    const Joined<Mix> x{weight_in(ctx, wt), JoinIn{jw.sel, jw.sims, jw.anchor}, mix};
+    const auto kernel = L.col2seg ? knn_merge_gather_kernel<true, Joined<Mix>> : knn_merge_gather_kernel<false, Joined<Mix>>;
+    hipLaunchKernelGGL(kernel, dim3((c.ncols + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)L.col2seg, c.ncols, T, out, (int64_t*)nullptr, L.rv, L.ri,
+                       (const int*)L.flag, x);
+    return launch_check(ctx, "knn_match_joined");
+}
+template <class Mix>
+static int launch_joined_blend(tvc_ctx* ctx, hipStream_t s, const KnnLists& L, int B, int T, int M, const float* weights, float* out, const KnnWeight& wt,
+                               const JoinWs& jw, const Mix& mix) {
+    const Joined<Mix> x{weight_in(ctx, wt), JoinIn{jw.sel, jw.sims, jw.anchor}, mix};
+    hipLaunchKernelGGL(knn_merge_blend_gather_kernel<Joined<Mix>>, dim3((B * T + 31) / 32), dim3(256), 0, s, L.cv, L.ci, L.segs, (const int*)L.col2seg, B * T, T, M,
+                       weights, x.w.col2b, x.w.rowmap, out, (int64_t*)nullptr, L.rv, L.ri, (const int*)L.flag, x);
+    return launch_check(ctx, "knn_match_blend_joined");
+}
+
 int run_knn_segs(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const KnnSegIn* in, int nin, float* out, int64_t* idx_out, int B, int T,
-                 const float* alpha, const float* share, const KnnWeight* wt) {
+                 const float* alpha, const float* share, const KnnWeight* wt, const KnnJoin* jn) {
     KnnCall c;
     TVC_CHECK(knn_call_plan(ctx, in, nin, B * T, &c));
     KnnLists L;
     TVC_CHECK(knn_candidates(ctx, s, ws, src, c, B, T, &L));
+    JoinWs jw{};
+    if (jn) jw = join_workspace(ws, (size_t)B * T);
     if (ws.dry) return 0;
+    if (jn) {      // the joined forms: merge + affinity, the path, then the weights around the path's anchor; the store form as below
+        const KnnWeight none{};
+        const KnnWeight& w = wt ? *wt : none;
+        const RagHost* h = ctx->rag;
+        TVC_CHECK(run_knn_join(ctx, s, ws, L, 1, B, T, w, *jn, jw, idx_out));
+        if (share) return launch_joined(ctx, s, c, L, T, out, w, jw, ShareIn{share, src});
+        if (alpha) return launch_joined(ctx, s, c, L, T, out, w, jw, AlphaIn{alpha, src, h ? (const int*)h->d_col2b : (const int*)nullptr, h ? (const int*)h->d_row : (const int*)nullptr});
+        return launch_joined(ctx, s, c, L, T, out, w, jw, NoMix{});
+    }
     if (wt) {      // the weighted forms: the same lists, the four rows weighted by their similarities; the store form as below
         const RagHost* h = ctx->rag;
         if (share) return launch_weighted(ctx, s, c, L, T, out, idx_out, *wt, ShareIn{share, src});
@@ -602,13 +955,23 @@ int run_knn_segs(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const Kn
 // knn_candidates walk - every pass one launch, as run_knn_segs -, then the blend gather.  idx_out (nullable): [M][B][T][4].  A ragged batch
 // (ctx->rag: B = 1, T = all its frames) finds a column's weight row through the batch's tables.
 int run_knn_blend(tvc_ctx* ctx, hipStream_t s, Ws& ws, const float* src, const KnnSegIn* in, int nin, int M, const float* weights, float* out,
-                  int64_t* idx_out, int B, int T, const float* alpha, const float* share, const KnnWeight* wt) {
+                  int64_t* idx_out, int B, int T, const float* alpha, const float* share, const KnnWeight* wt, const KnnJoin* jn) {
     KnnCall c;
     TVC_CHECK(knn_call_plan(ctx, in, nin, M * B * T, &c));
     KnnLists L;
     TVC_CHECK(knn_candidates(ctx, s, ws, src, c, M * B, T, &L, B));
+    JoinWs jw{};
+    if (jn) jw = join_workspace(ws, (size_t)M * B * T);
     if (ws.dry) return 0;
     const RagHost* h = ctx->rag;
+    if (jn) {      // every term a path of its own
+        const KnnWeight none{};
+        const KnnWeight& w = wt ? *wt : none;
+        TVC_CHECK(run_knn_join(ctx, s, ws, L, M, B, T, w, *jn, jw, idx_out));
+        if (share) return launch_joined_blend(ctx, s, L, B, T, M, weights, out, w, jw, ShareIn{share, src});
+        if (alpha) return launch_joined_blend(ctx, s, L, B, T, M, weights, out, w, jw, AlphaIn{alpha, src, h ? (const int*)h->d_col2b : (const int*)nullptr, h ? (const int*)h->d_row : (const int*)nullptr});
+        return launch_joined_blend(ctx, s, L, B, T, M, weights, out, w, jw, NoMix{});
+    }
     if (wt) {
         if (share) return launch_weighted_blend(ctx, s, L, B, T, M, weights, out, idx_out, *wt, ShareIn{share, src});
         if (alpha) return launch_weighted_blend(ctx, s, L, B, T, M, weights, out, idx_out, *wt, AlphaIn{alpha, src, h ? (const int*)h->d_col2b : (const int*)nullptr, h ? (const int*)h->d_row : (const int*)nullptr});

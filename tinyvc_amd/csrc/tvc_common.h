@@ -373,13 +373,21 @@ struct KnnWeight {
     const float* width = nullptr;
     float* sims_out = nullptr;
 };
+// jn (optional, both drivers; with or without wt, alpha / share): the joined form - the weights form around the neighbour a path over the
+// utterance chose (knn_gather.hip: merge + affinity, the path, the joined gather).  join: a DEVICE array of one continuity weight per caller's
+// row; anchor_out (nullable) [M][B][T] int32, affinity_out (nullable) [M][B][T][4][4].  Takes workspace (both walks): 101 bytes per virtual column.
+struct KnnJoin {
+    const float* join = nullptr;
+    int* anchor_out = nullptr;
+    float* affinity_out = nullptr;
+};
 int run_knn_segs(tvc_ctx*, hipStream_t, Ws&, const float* src, const KnnSegIn* in, int nin, float* out, int64_t* idx_out, int B, int T,
-                 const float* alpha = nullptr, const float* share = nullptr, const KnnWeight* wt = nullptr);
+                 const float* alpha = nullptr, const float* share = nullptr, const KnnWeight* wt = nullptr, const KnnJoin* jn = nullptr);
 // a weighted blend of M indices per row (knn_gather.hip): in[] = the (term, row) runs over M * B * T VIRTUAL query columns, term-major - term m's
 // search of real column n is column m * B * T + n -, weights = the caller's device array [rows][M] (read by the kernels, never by the host),
 // out [B][768][T] = w_0 * mu_0 + ... in term order, idx_out (nullable) [M][B][T][4]
 int run_knn_blend(tvc_ctx*, hipStream_t, Ws&, const float* src, const KnnSegIn* in, int nin, int M, const float* weights, float* out, int64_t* idx_out,
-                  int B, int T, const float* alpha = nullptr, const float* share = nullptr, const KnnWeight* wt = nullptr);
+                  int B, int T, const float* alpha = nullptr, const float* share = nullptr, const KnnWeight* wt = nullptr, const KnnJoin* jn = nullptr);
 // out[i] = sum_m |weights[rows[i]][m]| * *blob_amax(blobs[i * M + m]): the bound of row i's blended content
 int run_knn_blend_bound(tvc_ctx*, hipStream_t, const std::vector<const float*>& blobs, const std::vector<int>& rows, int M, const float* weights, float* out);
 // the content bound of an alpha call: out[i] = |1 - a| * idx_bound[i * stride] + |a| * srcmax[i] for utterance i < n, a = alpha[its row]
@@ -452,6 +460,9 @@ struct ConvertCall {
     // and protect's definitions, every term's mu_m of a blend.  A convex combination of index rows: the content bounds stay as they are.
     const int* neighbours = nullptr;
     const float* width = nullptr;
+    // tvc_joined_convert*_f32: join (device, one fp32 per caller's row) - the continuity weight of the match along a path (knn_gather.hip KnnJoin):
+    // the weights above form around the neighbour the path chose.  Still a convex combination of index rows.
+    const float* join = nullptr;
     // tvc_convert_*path_f32: path (host settings) puts the Viterbi decode of the call's own logits (run_pitch_path, directly behind the encoder) in
     // the place of the per-frame decode: protect's voicing weight, the automatic shift, a tracker, the shift and the decoder read its f0
     const tvc_pitch_path* path = nullptr;

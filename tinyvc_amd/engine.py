@@ -122,8 +122,19 @@ _WEIGHTED = {
 }
 
 
+# form "joined": the weighted rows' calls with the continuity weight `join` behind width - the match along a path.  The path takes workspace:
+# queries of its own.
+_JOINED = {
+    False: ("tvc_workspace_bytes_joined", "tvc_joined_convert_f32"),
+    True: ("tvc_workspace_bytes_ragged_joined", "tvc_joined_convert_ragged_f32"),
+    "match": ("tvc_workspace_bytes_match_joined", "tvc_knn_match_joined_f32"),
+}
+
+
 def _names(form, ragged=None):
     """(workspace query, entry) of a conversion (`ragged` a bool) or a match (None) from the tables above"""
+    if form == "joined":
+        return _JOINED["match" if ragged is None else ragged]
     if form == "weighted":
         return _WEIGHTED["match" if ragged is None else ragged]
     if form == "tuned":
@@ -139,7 +150,7 @@ def _names(form, ragged=None):
 _TrackArgs = collections.namedtuple("_TrackArgs", "start n W min_voiced slew ring count auto_shift")
 _CarryArgs = collections.namedtuple("_CarryArgs", "carry_frame carry")
 _SnapArgs = collections.namedtuple("_SnapArgs", "snap notes strength snap_carry_frame snap_note snap_ratio")
-_FEATURES_OFF = dict(lens=None, M=0, weights=None, alpha=None, protect=None, neighbours=None, width=None, path=None, target_f0=None, shift_out=None,
+_FEATURES_OFF = dict(lens=None, M=0, weights=None, alpha=None, protect=None, neighbours=None, width=None, join=None, path=None, target_f0=None, shift_out=None,
                      **_CarryArgs(0, None)._asdict(), **_SnapArgs(None, None, None, 0, None, None)._asdict(), **_TrackArgs(0, 0, 0, 0, 0.0, None, None, None)._asdict())
 
 
@@ -616,7 +627,7 @@ class Engine:
         if form == "table":
             blobs, ns = self._table(prepared, Ns, B)
             return dict(prepared=blobs, N=ns), dict(N=ns)
-        if form in ("auto", "track", "alpha", "protect", "path", "tuned", "weighted") and weights is None:
+        if form in ("auto", "track", "alpha", "protect", "path", "tuned", "weighted", "joined") and weights is None:
             blobs, ns = self._table(prepared, Ns, B)
             return dict(prepared=blobs, N=ns, M=1, weights=None), dict(N=ns, M=1)
         blobs, ns, M = self._blend_args(prepared, Ns, weights, B)
@@ -639,12 +650,14 @@ class Engine:
 
     # ---- kNN match: one driver, the public forms forward to it ----
     def _match(self, form, src, prepared, Ns, weights=None, want_indices=False, alpha=None, f0=None, protect=None, neighbours=None, width=None,
-               want_similarities=False):
+               want_similarities=False, join=None, want_anchors=False, want_affinities=False):
         """src [B, 768, T] matched against the index (`form`, prepared, Ns, weights: _index_args) -> matched [B, 768, T] (, indices [B, T, 4];
         [M, B, T, 4] for a blend: each term's own search).  form "alpha": the table (weights None) or blend form, and out = matched *
         (1 - alpha[b]) + src * alpha[b] (alpha: _per_row; indices always [M, B, T, 4]).  form "protect": the alpha form with the frame's share
         a_t = a + (1 - a) * (protect[b] * w[t]) in alpha's place, w from f0 [B, 1, T] / [B, T] (alpha None: a = 0).  form "weighted": the
-        protect form with alpha, protect and f0 all optional and neighbours / width (_weight_args) behind them (, similarities [M, B, T, 4])."""
+        protect form with alpha, protect and f0 all optional and neighbours / width (_weight_args) behind them (, similarities [M, B, T, 4]).
+        form "joined": the weighted form with join (_per_row: the continuity weight) behind width (, anchors [M, B, T] int32, affinities
+        [M, B, T, 4, 4])."""
         src = _prep(src, "source", self.device)
         B, C, T = src.shape
         if C != spec.SSL_DIM:
@@ -660,7 +673,7 @@ class Engine:
             named["alpha"] = _ptr(self._per_row(alpha, "alpha", B)) if alpha is not None else None
             named["protect"] = _ptr(self._per_row(protect, "protect", B))
             named["f0"] = _ptr(f0)
-        elif form == "weighted":
+        elif form in ("weighted", "joined"):
             if protect is not None:
                 f0 = _prep(f0, "f0", self.device)
                 if f0.numel() != B * T or f0.shape[0] != B:
@@ -669,6 +682,8 @@ class Engine:
             named["protect"] = _ptr(self._per_row(protect, "protect", B)) if protect is not None else None
             named["f0"] = _ptr(f0) if protect is not None else None
             named.update(self._weight_args(neighbours, width, B))
+            if form == "joined":
+                named["join"] = _ptr(self._per_row(join, "join", B))
         out = torch.empty_like(src)
         terms = (sized["M"],) if "M" in sized else ()      # a blend's terms
         idx = torch.empty(*terms, B, T, 4, dtype=torch.int64, device=self.device) if want_indices else None
@@ -676,10 +691,14 @@ class Engine:
         query, entry = _names(form)
         named["ws"], named["ws_bytes"] = self._query_ws(query, B=B, L=T * spec.HOP, **sized)
         named.update(ctx=self.ctx, stream=self._stream(), out=_ptr(out), idx_out=_ptr(idx))
-        if form == "weighted":
+        if form in ("weighted", "joined"):
             named["sims_out"] = _ptr(sims)
+        anchors = torch.empty(*terms, B, T, dtype=torch.int32, device=self.device) if want_anchors else None
+        aff = torch.empty(*terms, B, T, 4, 4, dtype=_F32, device=self.device) if want_affinities else None
+        if form == "joined":
+            named.update(anchor_out=_ptr(anchors), affinity_out=_ptr(aff))
         self._ok(getattr(self.lib, entry)(*_lib.arguments(entry, named)), entry)
-        res = (out,) + ((idx,) if want_indices else ()) + ((sims,) if want_similarities else ())
+        res = (out,) + ((idx,) if want_indices else ()) + ((sims,) if want_similarities else ()) + ((anchors,) if want_anchors else ()) + ((aff,) if want_affinities else ())
         return res if len(res) > 1 else out
 
     def knn_match(self, src, prepared, N, want_indices=False):
@@ -715,6 +734,16 @@ class Engine:
         (, indices [M, B, T, 4], similarities [M, B, T, 4]: what the lists held when the weights were formed): tvc_knn_match_weighted_f32;
         the definition is in include/tinyvc_hip.h."""
         return self._match("weighted", src, prepared, Ns, weights, want_indices, alpha, f0, protect, neighbours, width, want_similarities)
+
+    def knn_match_joined(self, src, prepared, Ns, join, neighbours=None, width=None, weights=None, alpha=None, f0=None, protect=None, want_indices=False,
+                         want_similarities=False, want_anchors=False, want_affinities=False):
+        """knn_match_weighted along a path: join a contiguous fp32 [B] device tensor, the continuity weight c of every row, read when the
+        kernels run - the weights form around the neighbour that a Viterbi path over the row's frames chose, a neighbour gaining by its
+        similarity to the query and by c times its cosine to the neighbour chosen for the frame before (, indices, similarities, anchors
+        [M, B, T] int32: the path, affinities [M, B, T, 4, 4]: the cosines between neighbouring frames' rows, frame 0's zeros):
+        tvc_knn_match_joined_f32; the definition is in include/tinyvc_hip.h."""
+        return self._match("joined", src, prepared, Ns, weights, want_indices, alpha, f0, protect, neighbours, width, want_similarities, join, want_anchors,
+                           want_affinities)
 
     def frame_share(self, f0_packed, start, counts, alpha, protect):
         """The per-frame share alone (tvc_frame_share_f32): f0_packed any contiguous fp32 device tensor, row i = its flattened values
@@ -773,7 +802,7 @@ class Engine:
         return _SnapArgs(ctypes.byref(tune.settings()), _ptr(notes), _ptr(strength), *state)
 
     def _convert(self, form, wav, prepared, Ns, pitch_shift, noise_angle=None, lengths=None, weights=None, target_f0=None, out=None, shift_out=None,
-                 track=None, alpha=None, protect=None, path=None, carry=None, tune=None, tune_carry=None, neighbours=None, width=None):
+                 track=None, alpha=None, protect=None, path=None, carry=None, tune=None, tune_carry=None, neighbours=None, width=None, join=None):
         """wav [B, L] converted toward the index (`form`, prepared, Ns, weights: _index_args) -> wave [B, L]; form "auto" / "track" ->
         (wave, shifts [B]).  "track": "auto" with the register taken from `track` (a PitchTrack: the streams' history), equal lengths only.
         "alpha": the table / blend call keeping the share alpha[b] of row b's own content features (alpha: _per_row); with target_f0 it is the
@@ -787,7 +816,9 @@ class Engine:
         (tvc_tuned_convert_f32 / tvc_tuned_convert_ragged_f32); `tune_carry` (equal lengths only): a SnapCarry of B streams, read at frame 0 and
         written behind frame tune_carry.hop_frames - 1.  "weighted": the "tuned" call with `tune` optional too and neighbours / width
         (_weight_args: k and the similarity width per row, either may be None) behind protect: the match is the weighted mean over the k
-        nearest rows (tvc_weighted_convert_f32 / tvc_weighted_convert_ragged_f32; the workspace is the tuned call's).
+        nearest rows (tvc_weighted_convert_f32 / tvc_weighted_convert_ragged_f32; the workspace is the tuned call's).  "joined": the "weighted"
+        call with join (_per_row: the continuity weight per row) behind width - the match along a path (tvc_joined_convert_f32 /
+        tvc_joined_convert_ragged_f32, queries of their own).
         lengths: a ragged batch (row b holds an utterance of lengths[b] samples, a multiple of 480, zero-padded behind it; every utterance
         is converted over its OWN length).  pitch_shift: a float, or one per row for every form but "shared".  Every host check comes
         first, then the noise draw (which advances torch's generator), then device work: a refused call leaves no trace.
@@ -806,27 +837,29 @@ class Engine:
             named["prepared_index"] = named.pop("prepared")      # the conversion's name for the stage call's `prepared`
         if ragged and (form == "track" or track is not None):
             raise ValueError("track: streams advance in lock step, there is no ragged form")
-        if carry is not None and (form not in ("path", "tuned", "weighted") or path is None or ragged):
+        if carry is not None and (form not in ("path", "tuned", "weighted", "joined") or path is None or ragged):
             raise ValueError("carry: the pitch path's state - it goes with form \"path\", and streams advance in lock step: there is no ragged form")
         found = form in ("auto", "track")      # the shifts are found on the device: pitch_shift is the offset, the applied shifts come back
-        if (form != "weighted" and (tune is None) != (form != "tuned")) or (tune_carry is not None and (tune is None or ragged)):
+        if (form not in ("weighted", "joined") and (tune is None) != (form != "tuned")) or (tune_carry is not None and (tune is None or ragged)):
             raise ValueError("tune goes with form \"tuned\" (and tune_carry with tune; streams advance in lock step: there is no ragged form)")
-        shares = form in ("alpha", "protect", "path", "tuned", "weighted")      # the table / blend call with or without target registers (and, equal lengths, a tracker), plus the source's share
+        shares = form in ("alpha", "protect", "path", "tuned", "weighted", "joined")      # the table / blend call with or without target registers (and, equal lengths, a tracker), plus the source's share
         if shares:
             found = target_f0 is not None
             if track is not None and not found:
                 raise ValueError("track needs target_f0: the tracker finds the register the automatic shift starts from")
             if form == "alpha" or alpha is not None:
                 named["alpha"] = _ptr(self._per_row(alpha, "alpha", B))
-            if form == "protect" or (form in ("path", "tuned", "weighted") and protect is not None):
+            if form == "protect" or (form in ("path", "tuned", "weighted", "joined") and protect is not None):
                 named["protect"] = _ptr(self._per_row(protect, "protect", B))
-            if form == "weighted":
+            if form in ("weighted", "joined"):
                 named.update(self._weight_args(neighbours, width, B))
-            if form == "path" or (form in ("tuned", "weighted") and path is not None):
+            if form == "joined":
+                named["join"] = _ptr(self._per_row(join, "join", B))
+            if form == "path" or (form in ("tuned", "weighted", "joined") and path is not None):
                 named["path"] = ctypes.byref(path.settings())
                 if carry is not None:
                     named.update(self._carry_args(carry, B, T)._asdict())
-            if form == "tuned" or (form == "weighted" and tune is not None):
+            if form == "tuned" or (form in ("weighted", "joined") and tune is not None):
                 named.update(self._snap_args(tune, tune_carry, B, T)._asdict())
         if found:
             named["target_f0"] = _ptr(self._per_row(target_f0, "target_f0", B))

@@ -6,7 +6,7 @@ from .. import utils
 from ...engine import loudness_in_place, pitch_shifts
 from .._base import HipModule
 from ..tinyvc import Decoder, Encoder
-from ..tinyvc.feature_retrieval import (alpha_rows, match_k_rows, match_width_rows, resolve_match_k, resolve_match_width, check_blend, check_references, check_tune_carry, resolve_tune, limit_rows, loudness_rows, prepare_reference, prepare_references,
+from ..tinyvc.feature_retrieval import (alpha_rows, continuity_rows, resolve_continuity, match_k_rows, match_width_rows, resolve_match_k, resolve_match_width, check_blend, check_references, check_tune_carry, resolve_tune, limit_rows, loudness_rows, prepare_reference, prepare_references,
                                         protect_rows, resolve_alpha, resolve_auto_pitch, resolve_f0_estimation, resolve_limit, resolve_loudness,
                                         resolve_protect, target_form, target_registers)
 
@@ -56,7 +56,7 @@ class Generator(HipModule):
     @torch.no_grad()
     def convert(self, wf, tgt, pitch_shift, f0_estimation="default", device=None, noise_angle=None, lengths=None, auto_pitch=None,
                 return_shift=False, track=None, alpha=None, protect=None, loudness=None, limit=None, carry=None, tune=None, tune_carry=None, k=None,
-                match_width=None):
+                match_width=None, continuity=None):
         """generator.py:26-34: wf [B, L], tgt [1 or B, 768, N] -> converted waveform [B, L'] (L' = L
         padded to a multiple of 480).  `f0_estimation` / `device` are accepted and ignored exactly as
         in the reference - but for `f0_estimation='viterbi'` or a feature_retrieval.PitchPath (extension): f0 is then the pitch path, a
@@ -130,7 +130,16 @@ class Generator(HipModule):
         row alone), B of them, or an fp32 [B] / [1] device tensor.  [B] tensors are used in place and read when the kernel runs, which
         clamps k and treats a NaN or negative width as inf; host values outside the ranges are refused before any engine work.  Every
         target form (a Blend: every term's match), equal and ragged batches, with every other keyword.  k = 4 with match_width = inf is
-        the call without them bit for bit, None for both (the default) launch for launch.  No width is suggested: nobody has listened."""
+        the call without them bit for bit, None for both (the default) launch for launch.  No width is suggested: nobody has listened.
+        `continuity` (extension; unit selection's join cost): match along a path - the neighbour a frame's weights form around is chosen
+        over the utterance as a whole (each row, each utterance of a ragged batch, each term of a Blend on its own), a neighbour gaining
+        by its cosine to the query and by `continuity` times its cosine to the neighbour chosen for the frame before, so the anchor of a
+        sharp match (k = 1 aside: that has no choice) stops alternating between two almost equally near rows.  A float >= 0, B of them,
+        or an fp32 [B] / [1] device tensor used in place (the kernel reads NaN and negatives as 0); a host value > 0 without a finite
+        host match_width or a width tensor is refused - under an infinite width it could have no effect.  Three launches in the gather's
+        place (tvc_joined_convert_f32 / tvc_joined_convert_ragged_f32; the definition is in include/tinyvc_hip.h and is exact: bit for
+        bit what tests/helpers_match_join.py computes).  0 is the call without it bit for bit, None (the default) launch for launch.
+        No value is suggested: nobody has listened."""
         # 1. classify the target once; malformed targets, registers and shift lists are refused before any engine or device work
         B = wf.shape[0] if wf.dim() == 2 else 1
         auto = auto_pitch is not None and auto_pitch is not False
@@ -165,7 +174,8 @@ class Generator(HipModule):
                 raise ValueError(f"carry: hop_frames = {carry.hop_frames} must be below the call's {-(-wf.shape[-1] // 480)} frames")
         near = resolve_match_k(k, B) if k is not None else None
         wide = resolve_match_width(match_width, B) if match_width is not None else None
-        weighted = near is not None or wide is not None
+        along = resolve_continuity(continuity, B, wide) if continuity is not None else None
+        weighted = near is not None or wide is not None or along is not None
         tune = resolve_tune(tune)
         if tune_carry is not None and lengths is not None:
             raise ValueError("tune_carry with lengths: streams advance in lock step, there is no ragged form")
@@ -208,7 +218,9 @@ class Generator(HipModule):
             if weighted:
                 rows["neighbours"] = match_k_rows(near, B, wf.device) if near is not None else None
                 rows["width"] = match_width_rows(wide, B, wf.device) if wide is not None else None
-            res = eng._convert("weighted" if weighted else "tuned" if tune is not None else "path" if path is not None else "alpha" if guard is None else "protect", wf, blobs, ns, pitch, noise_angle, lens, w,
+            if along is not None:
+                rows["join"] = continuity_rows(along, B, wf.device)
+            res = eng._convert("joined" if along is not None else "weighted" if weighted else "tuned" if tune is not None else "path" if path is not None else "alpha" if guard is None else "protect", wf, blobs, ns, pitch, noise_angle, lens, w,
                                target_registers(regs, B, wf.device) if auto else None, track=track, **rows)
             res = res if return_shift or not auto else res[0]
         elif not auto:

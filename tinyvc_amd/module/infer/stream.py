@@ -19,7 +19,7 @@ import torch
 from ...engine import (SOLA_CROSS, SOLA_DELAY, SOLA_SEARCH, loudness_geometry, loudness_levels, pitch_shifts, sola_geometry, stream_denoise_geometry,
                        stream_gate_geometry, stream_resample_geometry)
 from ...stream_state import CARRY_STATE, SNAP_STATE, DENOISE_STATE, DOOR_STATE, GATE_STATE, LIMITER_STATE, LOUDNESS_STATE, TRACK_STATE, addresses, allocate, reset
-from ..tinyvc.feature_retrieval import (PitchCarry, PitchTrack, SnapCarry, alpha_rows, match_k_rows, match_width_rows, resolve_match_k, resolve_match_width, check_f0_carry, check_stream_tune, gpu_device, limit_ceiling, limiter_settings, protect_rows, resolve_alpha,
+from ..tinyvc.feature_retrieval import (PitchCarry, PitchTrack, SnapCarry, alpha_rows, continuity_rows, resolve_continuity, match_k_rows, match_width_rows, resolve_match_k, resolve_match_width, check_f0_carry, check_stream_tune, gpu_device, limit_ceiling, limiter_settings, protect_rows, resolve_alpha,
                                         resolve_auto_pitch, resolve_f0_estimation, resolve_protect, target_form)
 from .generator import Generator
 
@@ -389,6 +389,9 @@ class BatchedStreamInfer:
     tensor): the weighted match - every frame the mean over its k nearest index rows, weighted by their similarities -, held as `self.k`
     and `self.match_width`, [S] device tensors read when a block runs: `stream.k.fill_(1)` / `stream.match_width.fill_(...)` between blocks
     replay the same captured graph (their addresses are part of the graph key).  None for both (the default) is the stream as it was.
+    `continuity` (convert's: a weight >= 0, one per stream, or an fp32 [S] / [1] device tensor): the match along a path, held as
+    `self.continuity`, a [S] device tensor like `self.match_width` (`stream.continuity.fill_(...)` replays the same graph).  Every window
+    decodes a path of its own over its frames; nothing is carried from window to window.  None (the default) is the stream as it was.
     `f0_estimation` (convert's): 'viterbi' or a feature_retrieval.PitchPath decodes every window's pitch as one path over its own frames
     (each window afresh unless f0_carry is set; the window's left context is what steadies the emitted frames); held as
     `self.f0_estimation`, and its settings - host values baked into the launch - are part of the graph key.  Every other name is ignored.
@@ -430,7 +433,7 @@ class BatchedStreamInfer:
     shorter than the three sizes say, and a look-ahead shorter than the pad is refused."""
 
     def __init__(self, generator: Generator, n_streams=1, target=None, pitch_shift=0., device=None,
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, k=None, match_width=None, denoise=None, loudness=None, gate=None, limiter=None, f0_carry=False, tune=None, door=None,
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, k=None, match_width=None, continuity=None, denoise=None, loudness=None, gate=None, limiter=None, f0_carry=False, tune=None, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         self.input_size, _ = check_window(block_size, extra_size, crossfade_size, sola_search_size, last_delay_size,
                                            auto_pitch is not None and auto_pitch is not False)
@@ -442,6 +445,7 @@ class BatchedStreamInfer:
         guard = resolve_protect(protect, n_streams) if protect is not None else None
         near = resolve_match_k(k, n_streams) if k is not None else None
         wide = resolve_match_width(match_width, n_streams) if match_width is not None else None
+        along = resolve_continuity(continuity, n_streams, wide) if continuity is not None else None
         self.n_streams, self.block_size = n_streams, block_size
         self.door, self.gate, self.denoise, self.loudness, self.limiter = (self._fits(name, stage) for name, stage in (
             ("door", door), ("gate", gate), ("denoise", denoise), ("loudness", loudness), ("limiter", limiter)))
@@ -464,6 +468,7 @@ class BatchedStreamInfer:
         # the weighted match: k and the similarity width of every stream, [S] device tensors read when a block runs, or None (four rows, equal weights)
         self.k = match_k_rows(near, n_streams, self.device) if near is not None else None
         self.match_width = match_width_rows(wide, n_streams, self.device) if wide is not None else None
+        self.continuity = continuity_rows(along, n_streams, self.device) if along is not None else None      # the match along a path, likewise
         self.extra_size = extra_size
         self.sola_search_size = sola_search_size
         self.last_dilay_size = last_delay_size          # (sic) the reference's attribute name, stream.py:49
@@ -577,12 +582,12 @@ class BatchedStreamInfer:
         if self.auto_pitch is None:
             y = self.generator.convert(self.input_wav, self.target, self.pitch_shift, device=self.device,
                                        f0_estimation=self.f0_estimation, noise_angle=noise_angle, alpha=self.alpha, protect=self.protect,
-                                       carry=self.pitch_carry, k=self.k, match_width=self.match_width, **self._tune_kw())
+                                       carry=self.pitch_carry, k=self.k, match_width=self.match_width, continuity=self.continuity, **self._tune_kw())
         else:
             y, pshift = self.generator.convert(self.input_wav, self.target, self.pitch_shift, device=self.device, f0_estimation=self.f0_estimation,
                                                noise_angle=noise_angle, auto_pitch=self.auto_pitch, return_shift=True, track=self.pitch_track,
                                                alpha=self.alpha, protect=self.protect, carry=self.pitch_carry, k=self.k, match_width=self.match_width,
-                                               **self._tune_kw())
+                                               continuity=self.continuity, **self._tune_kw())
         eng = self.generator.engine(self.device)
         out, shift = eng.sola(y, self.sola_buffer, self.fade_in_window, self.block_size, self.use_phase_vocoder, want_shift=True,
                               crossfade=self.crossfade_size, search=self.sola_search_size, delay=self.last_dilay_size)
@@ -631,6 +636,8 @@ class BatchedStreamInfer:
             tkey += (("k", self.k.data_ptr()),)
         if self.match_width is not None:
             tkey += (("match_width", self.match_width.data_ptr()),)
+        if self.continuity is not None:
+            tkey += (("continuity", self.continuity.data_ptr()),)
         path = resolve_f0_estimation(self.f0_estimation)
         if path is not None:      # the pitch path's settings ARE values: host numbers baked into the launch, so another PitchPath is another graph
             tkey += (("f0_estimation", path.params()),)
@@ -706,7 +713,7 @@ class StreamInfer(BatchedStreamInfer):
     """Single stream with the reference's constructor and 1-D buffers (stream.py:31-57)."""
 
     def __init__(self, generator: Generator, target=None, pitch_shift=0., device=torch.device("cpu"),
-                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, k=None, match_width=None, denoise=None, loudness=None, gate=None, limiter=None, f0_carry=False, tune=None, door=None,
+                 block_size=1920, extra_size=0, use_phase_vocoder=False, f0_estimation="default", use_graph=False, alpha=None, protect=None, k=None, match_width=None, continuity=None, denoise=None, loudness=None, gate=None, limiter=None, f0_carry=False, tune=None, door=None,
                  crossfade_size=SOLA_CROSS, sola_search_size=SOLA_SEARCH, last_delay_size=SOLA_DELAY, auto_pitch=None, pitch_track=None):
         dev = torch.device(device)
         if dev.type != "cuda":
@@ -714,7 +721,7 @@ class StreamInfer(BatchedStreamInfer):
         super().__init__(generator, n_streams=1, target=target, pitch_shift=pitch_shift, device=dev, block_size=block_size, extra_size=extra_size,
                          use_phase_vocoder=use_phase_vocoder, f0_estimation=f0_estimation, use_graph=use_graph, alpha=alpha, protect=protect, denoise=denoise, gate=gate,
                          limiter=limiter, door=door, crossfade_size=crossfade_size, sola_search_size=sola_search_size, last_delay_size=last_delay_size,
-                         auto_pitch=auto_pitch, pitch_track=pitch_track, loudness=loudness, f0_carry=f0_carry, tune=tune, k=k, match_width=match_width)
+                         auto_pitch=auto_pitch, pitch_track=pitch_track, loudness=loudness, f0_carry=f0_carry, tune=tune, k=k, match_width=match_width, continuity=continuity)
 
     @torch.no_grad()
     def audio_callback(self, block, noise_angle=None):

@@ -311,6 +311,31 @@ def match_width_rows(resolved, B, device):
     return alpha_rows(resolved, B, device, "match_width")
 
 
+def resolve_continuity(continuity, B, width=None):
+    """convert's continuity - the weight c of the match along a path: the neighbour a frame's weights form around is chosen over the
+    utterance as a whole, a neighbour gaining by its cosine to the query and by c times its cosine to the neighbour chosen for the frame
+    before (include/tinyvc_hip.h) - in alpha's forms: a float >= 0 (0: every frame on its own), B of them, or an fp32 [B] / [1] device
+    tensor, taken as it is (the kernel reads a NaN or negative value as 0).  A negative or NaN host value is refused under its own name.
+    `width`: resolve_match_width's result for the same call, or None - a host continuity > 0 with no finite host match_width and no
+    width tensor is refused too: under an infinite width every neighbour weighs 1 wherever the path goes, so it could have no effect.
+    The check is per call, not per row: one finite width anywhere passes every row's continuity, and k = 1, which has no choice to make
+    either, is not looked at - the refusal catches the keyword given alone, not every setting without an effect."""
+    res = resolve_alpha(continuity, B, "continuity")
+    if isinstance(res, torch.Tensor):
+        return res
+    for x in res:
+        if not x >= 0.0:
+            raise ValueError(f"continuity: a weight on the cosine between neighbouring frames' rows is >= 0, got {x!r}")
+    if any(x > 0.0 for x in res) and not isinstance(width, torch.Tensor) and not (width is not None and any(math.isfinite(w) for w in width)):
+        raise ValueError("continuity > 0 needs a finite match_width (or a match_width tensor): under an infinite width every neighbour weighs "
+                         "1 wherever the path goes, and continuity could have no effect")
+    return res
+
+
+def continuity_rows(resolved, B, device):
+    return alpha_rows(resolved, B, device, "continuity")
+
+
 class LoudnessMatch:
     """convert's loudness - how far the converted wave follows the loudness envelope of its source (tvc_loudness_match_f32; the definition is
     in include/tinyvc_hip.h; 1 - RVC's rms_mix_rate): every `sub_frame` samples the output is scaled by (Es / Eo)^(share / 2), Es and Eo the
@@ -872,6 +897,28 @@ def match_weight_keywords(args, script):
     if kw:
         print(f"Weighted match: the {kw.get('k', 4)} nearest rows of every frame, similarity width {kw.get('match_width', math.inf):g}")
     return kw
+
+
+def add_continuity_argument(parser):
+    """`--continuity C` for the entry scripts' parsers: absent (None) is the call without it"""
+    parser.add_argument("--continuity", type=float, default=None, metavar="C",
+                        help="match along a path: choose the neighbour a frame's weights form around over the utterance as a whole, a neighbour "
+                             "gaining C times its cosine to the neighbour chosen for the frame before (>= 0; needs a finite --match-width).  "
+                             "No value is suggested: nobody has listened.  default: absent")
+
+
+def continuity_keywords(args, script, so_far):
+    """what `--continuity` adds to the script's convert / stream call (`so_far`: match_weight_keywords' result for the same arguments):
+    nothing when it is absent (the call is today's), else {"continuity": C} and one printed line; a value outside its range, or one that
+    could have no effect, ends the script"""
+    if args.continuity is None:
+        return {}
+    if not args.continuity >= 0:
+        sys.exit(f"{script}: --continuity must be >= 0")
+    if args.continuity > 0 and not math.isfinite(so_far.get("match_width", math.inf)):
+        sys.exit(f"{script}: --continuity needs a finite --match-width: under an infinite width every neighbour weighs 1 wherever the path goes")
+    print(f"Match along a path: continuity {args.continuity:g}")
+    return {"continuity": float(args.continuity)}
 
 
 def gpu_device(device, sentence, cpu_ok=False):
